@@ -2,7 +2,8 @@
 """bench.py -- utterances/s of the ASG forward+backward hot path on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--mode graph|eager] [--launch single|streams|serial]
-                    [--graph-steps G] [--no-extra] [--no-cpu-baseline] [--config cfg3|cfg5]
+                    [--graph-steps G] [--dump-outputs DIR] [--full [--no-extra] [--no-cpu-baseline] [--no-pmc]]
+                    [--config cfg3|cfg5]
 
 One "step" = ASGLoss(inputs, targets, input_lengths, target_lengths) + loss.backward() on one batch of
 synthetic utterances already resident in HBM (SURVEY.md 8d inputs: cfg 3, T=400 B=64 N=40 L=30, fp32).
@@ -10,14 +11,17 @@ With N > 1 (launched by torch.distributed.run, one rank per GPU) every rank owns
 B=64*N batch (= cfg 4 at N=8), and the step ends with the single RCCL all-reduce of transition.grad
 (SURVEY.md 8e): weak scaling, no other collective.
 
-Timing.  After W warm-up steps, a block of EXACTLY K steps is timed between barrier + synchronize fences -- and that
-block is repeated (each repetition fenced the same way) until ~0.25 s of steps have run, because K steps of this
-workload are a millisecond or two, too short for one wall-clock reading; `ms_per_step` is the MEDIAN block / K, every
-block is listed in `timing.block_ms`, `timing.first_block_ms` is the first one.  In graph mode G consecutive steps
-(default: the largest divisor of K up to 10) are captured into ONE hipGraph and a block replays it K/G times: every
-step's kernels run in full, back to back on the stream, as inside a training loop whose host runs ahead of the GPU.
+Timing.  After W warm-up steps, ONE block of EXACTLY K steps is timed between barrier + synchronize fences;
+`ms_per_step` is that block / K.  In graph mode G consecutive steps (default: the largest divisor of K up to 10) are
+captured into ONE hipGraph and the block replays it K/G times: every step's kernels run in full, back to back on the
+stream, as inside a training loop whose host runs ahead of the GPU.  The inputs are drawn from fixed seeds, so the same
+arguments give the same inputs in every run; `--dump-outputs DIR` writes what the last timed step computed (loss,
+grad_inputs, grad_transition) as DIR/<name>.npy.
 
-Rank 0 prints ONE JSON line.  Besides the driver's contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run carries the driver's contract fields, `config` and `timing` only.  With
+`--full` it also carries
+  timing.repeated_blocks -- the K-step block repeated (each repetition fenced the same way) until ~0.25 s of steps have
+                  run: median / min / max block, since K steps of this workload are a millisecond or two
   roofline     -- dominant kernel (the fused recursion + assembly kernel): algorithmic bytes / its measured duration
   cpu_baseline -- the reference's own compiled CPU path (oracle/_ref) timed on this box's host cores (N=1 only)
   extra        -- (N=1 only) the other BASELINE.json configurations timed in the same process: cfg 2, cfg 4 on one GPU
@@ -40,6 +44,7 @@ import torch.distributed as dist  # noqa: E402
 T, B, N, L = 400, 64, 40, 30          # BASELINE.json configs[2] ("cfg 3"), per GPU
 HBM_PEAK_GBS = 8000.0                 # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 TARGET_TIMED_S = 0.25                 # wall time the repeated K-step blocks should add up to
+DUMP_MAX_ELEMS = 1 << 21              # --dump-outputs: a larger array is written as a fixed seeded sample of this many elements
 
 
 def algorithmic_bytes(T, B, N, L, w=4):
@@ -131,6 +136,22 @@ def graph_steps_for(steps, requested=0):
 def median(v):
     s = sorted(v)
     return s[len(s) // 2]
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every tensor of `arrays` as <path>/<name>.npy in its own dtype (float32 / float64).  A tensor of more than
+    DUMP_MAX_ELEMS elements is written as <name>_sample.npy: the elements at the same seeded flat indices in every run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.float()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = torch.randint(0, t.numel(), (DUMP_MAX_ELEMS,), generator=torch.Generator().manual_seed(0))
+            t = t.reshape(-1)[idx.to(t.device)]
+            name += "_sample"
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
 
 
 def capture_steps(one_step, gsteps, after_step=None, relaxed=False):
@@ -235,9 +256,9 @@ def time_small_config(name, T_, B_, N_, L_, variable, steps, eval_route=False, e
 CFG5 = dict(T=2000, B=32, N=10000, L=60)      # BASELINE.json configs[4]: large alphabet, variable lengths
 
 
-def measure_cfg5(steps, warmup):
+def measure_cfg5(steps, warmup, dump_dir=None):
     """The large-alphabet workload on the generic kernels (csrc/asg_generic_step.hip, asg_generic_grad.hip).  A step is ASGLoss forward + backward
-    on one batch (eager: a step is ~0.4 s of GPU time, launch overhead is nothing).
+    on one batch (eager: a step is ~0.4 s of GPU time, launch overhead is nothing).  dump_dir: --dump-outputs of the last timed step.
     The reference cannot run this size at all: fully_connected_lattice.cpp:77 allocates a [T-1,B,N,N] tensor = 25.6 TB."""
     import torch_asg_amd
     from torch_asg_amd import asg as asg_mod
@@ -268,6 +289,8 @@ def measure_cfg5(steps, warmup):
         loss = one_step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if dump_dir:
+        dump_outputs(dump_dir, {"loss": loss, "grad_inputs": x.grad, "grad_transition": m.transition.grad})
     # dominant kernel: the recursion over frames (alpha of frame n and beta of frame len-1-n together): forward alone
     # between HIP events / (T - 1) frame steps
     be = asg_mod.native()
@@ -417,7 +440,7 @@ def collect_pmc_traffic(timeout_s=170):
 def run_cfg5(args, real_stdout):
     """`--config cfg5`: the large-alphabet workload as the headline of the line (same JSON contract)."""
     torch.cuda.set_device(0)
-    r = measure_cfg5(args.steps, args.warmup)
+    r = measure_cfg5(args.steps, args.warmup, args.dump_outputs)
     out = {
         "metric": "utterances/sec fwd+bwd, T=2000 B=32 N=10000 (cfg 5, large alphabet); achieved HBM GB/s vs roofline",
         "value": r["utt_s"], "unit": "utterances/s", "n_gpus": 1, "steps": args.steps, "warmup": r["warmup"],
@@ -463,6 +486,116 @@ def extras(args):
     return ex
 
 
+def full_measurements(args, be, step_group, gsteps, fence, use_dist, dev, x, tg, il, tl, loss_mod):
+    """--full, on every rank: the headline's K-step block repeated, and the dominant kernel's duration."""
+    def agree(v):
+        if not use_dist:
+            return v
+        t = torch.tensor([v], dtype=torch.float64, device=dev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        return float(t.item())
+
+    blocks = timed_blocks(step_group, args.steps // gsteps, fence, agree)
+    if use_dist:
+        tb = torch.tensor(blocks, dtype=torch.float64, device=dev)
+        dist.all_reduce(tb, op=dist.ReduceOp.MAX)          # every block: the slowest rank's time
+        blocks = [float(v) for v in tb.tolist()]
+
+    # ---- dominant-kernel duration, measured live with HIP events on the launch stream: a hipGraph holding ONLY that
+    # kernel launch, replayed back to back between one pair of HIP events (launch gaps inside a graph are ~1 us); this is
+    # the number that tracks rocprofv3's kernel time.  Fallback: event pairs around single eager launches.
+    from torch_asg_amd import _lib as lib_mod
+    lflags = {"streams": lib_mod.FLAG_STREAMS, "single": lib_mod.FLAG_SINGLE_LAUNCH, "serial": 0}[args.launch]
+    xd = x.detach()
+    trd = loss_mod.transition.detach()
+    fused_step = args.launch == "single"      # ASGLoss' default route: recursions AND gradient assembly in one launch
+
+    def dominant_launch():
+        if fused_step:
+            be.loss_forward(xd, tg, trd, il, tl, "mean", lflags)
+        else:
+            be.forward(xd, tg, trd, il, tl, lflags)
+
+    for _ in range(5):
+        dominant_launch()
+    torch.cuda.synchronize()
+    nk = min(max(args.steps, 20), 200)
+    try:
+        per_graph = 25
+        kg = capture_steps(dominant_launch, per_graph)
+        for _ in range(3):
+            kg.replay()
+        torch.cuda.synchronize()
+        reps = []
+        for _ in range(max(nk // per_graph, 8)):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            kg.replay()
+            e1.record()
+            torch.cuda.synchronize()
+            reps.append(e0.elapsed_time(e1) / per_graph)
+        kern_ms_med = median(reps)
+        kern_ms_avg = sum(reps) / len(reps)
+        kern_method = "HIP events around a hipGraph of %d consecutive launches of this kernel only, per launch" % per_graph
+    except Exception as e:
+        sys.stderr.write("[bench] single-kernel graph timing failed (%s); eager event pairs\n" % (e,))
+        ev_pairs = []
+        for _ in range(nk):
+            torch.cuda._sleep(400000)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            dominant_launch()
+            e1.record()
+            ev_pairs.append((e0, e1))
+        torch.cuda.synchronize()
+        kern_ms = sorted(e0.elapsed_time(e1) for e0, e1 in ev_pairs)
+        kern_ms_avg = sum(kern_ms) / len(kern_ms)
+        kern_ms_med = kern_ms[len(kern_ms) // 2]
+        kern_method = "HIP events around single eager launches (includes ~3 us of dispatch)"
+    return {"repeated_blocks": {"protocol": "the K-step block repeated, each repetition between barrier + synchronize fences, until "
+                                            "~%.2f s of steps have run" % TARGET_TIMED_S,
+                                "timed_blocks": len(blocks), "first_block_ms": blocks[0] * 1e3, "min_block_ms": min(blocks) * 1e3,
+                                "median_block_ms": median(blocks) * 1e3, "max_block_ms": max(blocks) * 1e3,
+                                "median_ms_per_step": median(blocks) / args.steps * 1e3, "total_timed_s": sum(blocks)},
+            "fused_step": fused_step, "kern_ms_med": kern_ms_med, "kern_ms_avg": kern_ms_avg, "kern_method": kern_method}
+
+
+def full_roofline(args, full, ms_per_step, world):
+    """--full, rank 0: the `roofline` object of the headline (counter passes for its traffic unless --no-pmc)."""
+    fused_step, kern_ms_med = full["fused_step"], full["kern_ms_med"]
+    a_alg = algorithmic_bytes(T, B, N, L)
+    achieved = a_alg / (kern_ms_med * 1e-3) / 1e9
+    traffic, traffic_source, traffic_live, pmc = None, None, False, None
+    if fused_step and world == 1 and not args.no_pmc:
+        try:
+            pmc = collect_pmc_traffic()
+            traffic, traffic_live = pmc["dominant_kernel_hbm_bytes_per_launch"], True
+            traffic_source = ("measured by this run: rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (two passes of tools/pmc_probe.py) "
+                              "at csrc %s" % pmc["csrc_sha16"])
+        except Exception as e:
+            sys.stderr.write("[bench] counter passes failed (%s: %s); falling back to the committed collection\n" % (type(e).__name__, e))
+    if fused_step and traffic is None:
+        traffic, traffic_source = committed_traffic(("r06_pmc_cfg3.json", "r05_pmc_cfg3.json"))
+    return {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
+            "traffic_measured_in_run": traffic_live,
+            "traffic_detail": None if pmc is None else {k: pmc[k] for k in (
+                "dominant_kernel_fetch_bytes", "dominant_kernel_write_bytes", "backward_kernel_hbm_bytes_per_launch",
+                "step_hbm_bytes", "step_traffic_over_algorithmic", "calibration_copy_256MiB_raw_kb")},
+            "kernel": "fused_fwd_kernel (all four recursions of every utterance AND the gradient assembly in "
+                      "one launch: three workgroups per utterance)"
+                      if fused_step else "asg_forward launches (recursion kernels)",
+            "kernel_ms": kern_ms_med, "kernel_ms_avg": full["kern_ms_avg"], "kernel_timing": full["kern_method"],
+            "algorithmic_bytes_per_launch": a_alg,
+            "step_achieved": a_alg / (ms_per_step * 1e-3) / 1e9,
+            "note": "serial-latency-bound scan: 400 dependent steps x 64 utterances; see DESIGN.md",
+            # what actually bounds the dominant kernel: T-1 dependent recursion steps at the LDS-broadcast floor of
+            # this formulation (117 ns measured for the recursion wavefront alone, DESIGN.md section 5a)
+            "latency_floor": {"dependent_steps": T - 1, "ns_per_step": 117.0,
+                              "floor_ms": (T - 1) * 117.0e-6,
+                              "frac_of_kernel": (T - 1) * 117.0e-6 / kern_ms_med} if fused_step else None}
+
+
 def free_port():
     import socket
     with socket.socket() as so:
@@ -494,11 +627,16 @@ def main():
     ap.add_argument("--mode", choices=["graph", "eager"], default="graph")
     ap.add_argument("--launch", choices=["single", "streams", "serial"], default="single")
     ap.add_argument("--graph-steps", type=int, default=0, help="steps per captured hipGraph (0 = largest divisor of --steps <= 10)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the `extra` object (the other configurations)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline: repeated timed blocks, the dominant kernel's roofline, the "
+                         "CPU baseline and the other configurations (`extra`)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline`")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the `extra` object (the other configurations)")
     ap.add_argument("--no-pmc", action="store_true",
-                    help="do not run the two rocprofv3 counter passes that measure roofline.traffic (N=1 only; ~40 s); the committed "
-                         "collection is used if it belongs to this tree's sources")
+                    help="with --full: do not run the two rocprofv3 counter passes that measure roofline.traffic (N=1 only; ~40 s); the "
+                         "committed collection is used if it belongs to this tree's sources")
     ap.add_argument("--pmc-only", action="store_true", help="run only those two passes, print their JSON (-> profiles/<tag>_pmc_cfg3.json)")
     ap.add_argument("--force-dist", action="store_true", help="init the process group even with one rank (testing)")
     ap.add_argument("--dry-run", action="store_true",
@@ -506,6 +644,8 @@ def main():
     ap.add_argument("--config", choices=["cfg3", "cfg5"], default="cfg3",
                     help="cfg3 = BASELINE.json's headline workload (default); cfg5 = the large-alphabet workload, 1 GPU")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # keep stdout clean for the ONE JSON line: anything libraries print (RCCL banners etc.) goes to stderr
     sys.stdout.flush()
@@ -619,13 +759,15 @@ def main():
             mode = "eager"
             gsteps = 1
 
+    last = {}
+
     def step_group():                    # gsteps steps
         if graph is not None:
             graph()                      # GraphedStep.__call__: nothing to copy in, one hipGraph replay
             if not graph_has_collective:
                 sync_grads()
         else:
-            one_step()
+            last["loss"] = one_step()
             sync_grads()
 
     def fence():
@@ -638,94 +780,36 @@ def main():
     for _ in range(args.warmup % gsteps):      # the rest of the W warm-up steps, one at a time
         one_step()
         sync_grads()
-    def agree(v):
-        if not use_dist:
-            return v
-        t = torch.tensor([v], dtype=torch.float64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        return float(t.item())
 
-    blocks = timed_blocks(step_group, args.steps // gsteps, fence, agree)
+    # ---- the headline: ONE block of exactly `steps` steps (gsteps divides steps), fenced on both sides
+    fence()
+    t0 = time.perf_counter()
+    for _ in range(args.steps // gsteps):
+        step_group()
+    fence()
+    dt = time.perf_counter() - t0
     ranks_joined = 1
     if use_dist:
-        tb = torch.tensor(blocks, dtype=torch.float64, device=dev)
-        dist.all_reduce(tb, op=dist.ReduceOp.MAX)          # every block: the slowest rank's time
-        blocks = [float(v) for v in tb.tolist()]
+        tb = torch.tensor([dt], dtype=torch.float64, device=dev)
+        dist.all_reduce(tb, op=dist.ReduceOp.MAX)          # the slowest rank's time
+        dt = float(tb.item())
         rj = torch.ones(1, dtype=torch.int64, device=dev)
-        dist.all_reduce(rj)                                # ranks that ran every timed block and got here
+        dist.all_reduce(rj)                                # ranks that ran every timed step and got here
         ranks_joined = int(rj.item())
         if ranks_joined != world:
             raise SystemExit("bench.py: %d of %d ranks reached the end of the timed region" % (ranks_joined, world))
-    dt = median(blocks)
-
-    # ---- dominant-kernel duration, measured live with HIP events on the launch stream: a hipGraph holding ONLY that
-    # kernel launch, replayed back to back between one pair of HIP events (launch gaps inside a graph are ~1 us); this is
-    # the number that tracks rocprofv3's kernel time.  Fallback: event pairs around single eager launches.
-    from torch_asg_amd import _lib as lib_mod
-    lflags = {"streams": lib_mod.FLAG_STREAMS, "single": lib_mod.FLAG_SINGLE_LAUNCH, "serial": 0}[args.launch]
-    xd = x.detach()
-    trd = loss_mod.transition.detach()
-    fused_step = args.launch == "single"      # ASGLoss' default route: recursions AND gradient assembly in one launch
-
-    def dominant_launch():
-        if fused_step:
-            be.loss_forward(xd, tg, trd, il, tl, "mean", lflags)
+    if args.dump_outputs and rank == 0:
+        if graph is not None:
+            dump_outputs(args.dump_outputs, {"loss": graph.loss, "grad_inputs": graph.inputs_grad,
+                                             "grad_transition": loss_mod.transition.grad})
         else:
-            be.forward(xd, tg, trd, il, tl, lflags)
+            dump_outputs(args.dump_outputs, {"loss": last["loss"], "grad_inputs": x.grad, "grad_transition": loss_mod.transition.grad})
 
-    for _ in range(5):
-        dominant_launch()
-    torch.cuda.synchronize()
-    nk = min(max(args.steps, 20), 200)
-    try:
-        per_graph = 25
-        kg = capture_steps(dominant_launch, per_graph)
-        for _ in range(3):
-            kg.replay()
-        torch.cuda.synchronize()
-        reps = []
-        for _ in range(max(nk // per_graph, 8)):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            kg.replay()
-            e1.record()
-            torch.cuda.synchronize()
-            reps.append(e0.elapsed_time(e1) / per_graph)
-        kern_ms_med = median(reps)
-        kern_ms_avg = sum(reps) / len(reps)
-        kern_method = "HIP events around a hipGraph of %d consecutive launches of this kernel only, per launch" % per_graph
-    except Exception as e:
-        sys.stderr.write("[bench] single-kernel graph timing failed (%s); eager event pairs\n" % (e,))
-        ev_pairs = []
-        for _ in range(nk):
-            torch.cuda._sleep(400000)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            dominant_launch()
-            e1.record()
-            ev_pairs.append((e0, e1))
-        torch.cuda.synchronize()
-        kern_ms = sorted(e0.elapsed_time(e1) for e0, e1 in ev_pairs)
-        kern_ms_avg = sum(kern_ms) / len(kern_ms)
-        kern_ms_med = kern_ms[len(kern_ms) // 2]
-        kern_method = "HIP events around single eager launches (includes ~3 us of dispatch)"
-
+    if args.full:
+        full = full_measurements(args, be, step_group, gsteps, fence, use_dist, dev, x, tg, il, tl, loss_mod)
     if rank == 0:
-        a_alg = algorithmic_bytes(T, B, N, L)
         ms_per_step = dt / args.steps * 1e3
         value = global_batch * args.steps / dt
-        achieved = a_alg / (kern_ms_med * 1e-3) / 1e9
-        traffic, traffic_source, traffic_live, pmc = None, None, False, None
-        if fused_step and world == 1 and not args.no_pmc:
-            try:
-                pmc = collect_pmc_traffic()
-                traffic, traffic_live = pmc["dominant_kernel_hbm_bytes_per_launch"], True
-                traffic_source = ("measured by this run: rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (two passes of tools/pmc_probe.py) "
-                                  "at csrc %s" % pmc["csrc_sha16"])
-            except Exception as e:
-                sys.stderr.write("[bench] counter passes failed (%s: %s); falling back to the committed collection\n" % (type(e).__name__, e))
-        if fused_step and traffic is None:
-            traffic, traffic_source = committed_traffic(("r06_pmc_cfg3.json", "r05_pmc_cfg3.json"))
         out = {
             "metric": "utterances/sec fwd+bwd, T=400 B=64 N=40; achieved HBM GB/s vs roofline",
             "value": value,
@@ -758,34 +842,17 @@ def main():
                        "launcher": "self (bench.py started its ranks)" if os.environ.get("ASG_BENCH_SELF_LAUNCHED") == "1"
                                    else ("torch.distributed.run" if world > 1 else "none"),
                        "parallelism": "batch-sharded x%d" % world},
-            "timing": {"protocol": "blocks of exactly `steps` steps, each between barrier + synchronize fences; "
-                                   "ms_per_step and value come from the MEDIAN block",
-                       "timed_blocks": len(blocks), "first_block_ms": blocks[0] * 1e3,
-                       "min_block_ms": min(blocks) * 1e3, "median_block_ms": dt * 1e3, "max_block_ms": max(blocks) * 1e3,
-                       "total_timed_s": sum(blocks)},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
-                         "traffic_measured_in_run": traffic_live,
-                         "traffic_detail": None if pmc is None else {k: pmc[k] for k in (
-                             "dominant_kernel_fetch_bytes", "dominant_kernel_write_bytes", "backward_kernel_hbm_bytes_per_launch",
-                             "step_hbm_bytes", "step_traffic_over_algorithmic", "calibration_copy_256MiB_raw_kb")},
-                         "kernel": "fused_fwd_kernel (all four recursions of every utterance AND the gradient assembly in "
-                                   "one launch: three workgroups per utterance)"
-                                   if fused_step else "asg_forward launches (recursion kernels)",
-                         "kernel_ms": kern_ms_med, "kernel_ms_avg": kern_ms_avg, "kernel_timing": kern_method,
-                         "algorithmic_bytes_per_launch": a_alg,
-                         "step_achieved": a_alg / (ms_per_step * 1e-3) / 1e9,
-                         "note": "serial-latency-bound scan: 400 dependent steps x 64 utterances; see DESIGN.md",
-                         # what actually bounds the dominant kernel: T-1 dependent recursion steps at the LDS-broadcast floor of
-                         # this formulation (117 ns measured for the recursion wavefront alone)
-                         "latency_floor": {"dependent_steps": T - 1, "ns_per_step": 117.0,
-                                           "floor_ms": (T - 1) * 117.0e-6,
-                                           "frac_of_kernel": (T - 1) * 117.0e-6 / kern_ms_med} if fused_step else None},
+            "timing": {"protocol": "one block of exactly `steps` steps after `warmup` steps, between barrier + synchronize fences; "
+                                   "ms_per_step and value come from that block",
+                       "block_ms": dt * 1e3},
         }
-        if world == 1 and not args.no_extra:
-            out["extra"] = extras(args)
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline()
+        if args.full:
+            out["timing"]["repeated_blocks"] = full["repeated_blocks"]
+            out["roofline"] = full_roofline(args, full, ms_per_step, world)
+            if world == 1 and not args.no_extra:
+                out["extra"] = extras(args)
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline()
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
     if use_dist:

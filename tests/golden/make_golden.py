@@ -107,6 +107,20 @@ def save_large(name, T, B, N, L, seed, variable, reduction="mean"):
     print("wrote", name, "loss32", out["f32_loss"], "loss64", out["f64_loss"])
 
 
+def save_live(seed):
+    """The reference's compiled CPU path (oracle/ref_runner.py, reduction 'sum') on tests/util.py::live_case(seed), fp64."""
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.dirname(HERE))
+    import util
+    from oracle import ref_runner
+    tr, x, tg, il, tl = util.live_case(seed)
+    r = ref_runner.asg_loss(x, tg, tr, il, tl, "sum")
+    out = dict(transition=tr.numpy(), inputs=x.numpy(), targets=tg.numpy(), input_lengths=il.numpy(), target_lengths=tl.numpy(),
+               **{k: r[k].numpy() for k in ("loss_per_utt", "grad_inputs", "grad_transition")})
+    np.savez_compressed(os.path.join(HERE, "live_seed%d.npz" % seed), **out)
+    print("wrote live_seed%d" % seed, tuple(x.shape))
+
+
 def main():
     torch.manual_seed(0)
     torch.set_num_threads(8)
@@ -177,6 +191,8 @@ def main():
     save_large("cfg3", 400, 64, 40, 30, 0, False)
     save_large("cfg3_var", 400, 64, 40, 30, 0, True)
     save_large("cfg5_reduced", 64, 4, 1024, 16, 0, True)
+    for seed in range(3):
+        save_live(seed)
 
 
 if __name__ == "__main__":

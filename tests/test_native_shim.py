@@ -3,7 +3,6 @@
 torch_asg/asg.py runs unmodified.  The GPU tests drive the functions with the argument lists asg.py uses
 (asg.py:12-20, 30-32, 42-44, 51-53, 62-64, 76-77, 90-94) and compare with the oracle."""
 import inspect
-import os
 import sys
 
 import numpy as np
@@ -43,13 +42,43 @@ def test_install_makes_the_module_importable_under_the_reference_name():
             sys.modules["torch_asg_native"] = before
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/torch_asg"), reason="the reference tree is not on this machine")
-def test_reference_python_layer_imports_against_the_shim_and_cpu_tensors_are_refused():
-    """In the build container (reference present, no GPU): the reference's asg.py, untouched, resolves its
+# A stand-in for the reference's Python layer (torch_asg/asg.py), written to a temporary directory by the test below: like
+# asg.py it imports `torch_asg_native` at module level, and its CPU route (asg.py:124) calls fully_connected_forward and
+# force_aligned_forward with the argument lists of asg.py:9-20, 39-44.
+_STANDIN_ASG = '''
+import torch
+import torch_asg_native
+
+
+class ASGLoss(torch.nn.Module):
+    def __init__(self, num_labels):
+        super().__init__()
+        self.transition = torch.nn.Parameter(torch.zeros(num_labels, num_labels))
+
+    def forward(self, inputs, targets, input_lengths=None, target_lengths=None):
+        T, B, N = inputs.shape
+        S = targets.shape[1]
+        if input_lengths is None:
+            input_lengths = torch.full((B,), T, dtype=torch.int64)
+        if target_lengths is None:
+            target_lengths = torch.full((B,), S, dtype=torch.int64)
+        full = torch_asg_native.fully_connected_forward(inputs, self.transition, input_lengths, T, B, N)[0]
+        aligned = torch_asg_native.force_aligned_forward(inputs, targets, self.transition, input_lengths, target_lengths,
+                                                         T, B, N, S)[0]
+        return (full - aligned).mean()
+'''
+
+
+def test_reference_python_layer_imports_against_the_shim_and_cpu_tensors_are_refused(tmp_path):
+    """No GPU needed: a package laid out like the reference's (torch_asg/asg.py, stand-in above) resolves its
     `import torch_asg_native` to the shim; a CPU call reaches the shim and is refused there (no CPU path)."""
     import torch_asg_amd.native_shim as shim
+    pkg = tmp_path / "torch_asg"
+    pkg.mkdir()
+    (pkg / "__init__.py").write_text("from .asg import ASGLoss\n")
+    (pkg / "asg.py").write_text(_STANDIN_ASG)
     saved = {k: sys.modules.get(k) for k in ("torch_asg_native", "torch_asg", "torch_asg.asg")}
-    sys.path.insert(0, "/root/reference")
+    sys.path.insert(0, str(tmp_path))
     try:
         for k in ("torch_asg", "torch_asg.asg"):
             sys.modules.pop(k, None)
@@ -60,7 +89,7 @@ def test_reference_python_layer_imports_against_the_shim_and_cpu_tensors_are_ref
         with pytest.raises(RuntimeError, match="ROCm device"):
             m(torch.randn(6, 2, 7), torch.randint(0, 7, (2, 5)))
     finally:
-        sys.path.remove("/root/reference")
+        sys.path.remove(str(tmp_path))
         for k, v in saved.items():
             if v is None:
                 sys.modules.pop(k, None)

@@ -2,7 +2,7 @@
 
 (a) known-answer vectors of the reference's own tests (re-typed data + expected values),
 (b) committed golden fixtures generated from the real reference (tests/golden/make_golden.py),
-(c) live comparison with the reference's compiled CPU path (oracle/_ref) when it is present,
+(c) the reference's compiled CPU path on seeded random cases: its stored answers, and live when oracle/_ref is built,
 (d) brute-force path enumeration (independent of any recursion).
 """
 import math
@@ -151,18 +151,23 @@ def test_golden_cfg2_f32():
 
 
 # ---------------------------------------------------------------- (c) live reference
-@pytest.mark.skipif(not ref_runner.available(), reason="oracle/_ref not built")
 @pytest.mark.parametrize("seed", [0, 1, 2])
 def test_live_reference_matches_oracle(seed):
-    rng = np.random.default_rng(seed)
-    T, B, N, L = int(rng.integers(2, 30)), int(rng.integers(1, 5)), int(rng.integers(2, 12)), int(rng.integers(1, 8))
-    tr, x, tg, _, _ = util.synth(T, B, N, L, seed, False, torch.float64)
-    il = torch.from_numpy(rng.integers(1, T + 1, B))
-    tl = torch.from_numpy(rng.integers(1, L + 1, B))
-    ref = ref_runner.asg_loss(x, tg, tr, il, tl, "sum")
+    """Against the reference's compiled CPU path's answers stored by tests/golden/make_golden.py (golden/live_seed<seed>.npz),
+    and against that path itself, run live, when oracle/_ref is built."""
+    tr, x, tg, il, tl = util.live_case(seed)
     r = orc.asg_loss(x.numpy(), tg.numpy(), tr.numpy(), il.numpy(), tl.numpy(), "sum")
-    for k in ("loss_per_utt", "grad_inputs", "grad_transition"):
-        util.assert_close(r[k], ref[k].numpy(), 1e-10, k)
+    keys = ("loss_per_utt", "grad_inputs", "grad_transition")
+    stored = util.load("live_seed%d" % seed)
+    for k, v in (("transition", tr), ("inputs", x), ("targets", tg), ("input_lengths", il), ("target_lengths", tl)):
+        assert np.array_equal(stored[k], v.numpy()), k
+    refs = [("stored", stored)]
+    if ref_runner.available():
+        live = ref_runner.asg_loss(x, tg, tr, il, tl, "sum")
+        refs.append(("live", {k: live[k].numpy() for k in keys}))
+    for what, ref in refs:
+        for k in keys:
+            util.assert_close(r[k], ref[k], 1e-10, "%s %s" % (what, k))
 
 
 # ---------------------------------------------------------------- (d) brute force

@@ -29,6 +29,17 @@ def synth(T, B, N, L, seed=0, variable=False, dtype=torch.float32):
     return transition.to(dtype), inputs.to(dtype), targets, il, tl
 
 
+def live_case(seed):
+    """The small random case of tests/test_oracle.py::test_live_reference_matches_oracle (fp64; shapes drawn from the seed);
+    tests/golden/make_golden.py stores the reference's answer for it as golden/live_seed<seed>.npz."""
+    rng = np.random.default_rng(seed)
+    T, B, N, L = int(rng.integers(2, 30)), int(rng.integers(1, 5)), int(rng.integers(2, 12)), int(rng.integers(1, 8))
+    tr, x, tg, _, _ = synth(T, B, N, L, seed, False, torch.float64)
+    il = torch.from_numpy(rng.integers(1, T + 1, B))
+    tl = torch.from_numpy(rng.integers(1, L + 1, B))
+    return tr, x, tg, il, tl
+
+
 def load(name):
     z = np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
     return {k: z[k] for k in z.files}

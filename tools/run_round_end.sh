@@ -3,7 +3,7 @@
 # Everything under gpurun_out/<tag>/ ; tools/summarize_profiles.py + a few cp turn it into profiles/<tag>_*.
 cd $GRAFT_REPO_ROOT; TAG=${1:-r06}; O=gpurun_out/$TAG; mkdir -p $O
 (timeout 1500 python -m pytest tests -m gpu -q 2>&1 | tail -12) > $O/pytest.log; tail -3 $O/pytest.log
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; head -c 600 $O/bench.json; echo
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; head -c 600 $O/bench.json; echo
 timeout 900 bash tools/make_profiles.sh $TAG > $O/make_profiles.log 2>&1; tail -3 $O/make_profiles.log
 timeout 900 bash tools/run_cfg5.sh > $O/run_cfg5.log 2>&1; cp gpurun_out/cfg5/bench_cfg5.json $O/ 2>/dev/null; find gpurun_out/cfg5/trace -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/cfg5_kernel_stats.csv; tail -5 $O/run_cfg5.log | cut -c1-200
 timeout 900 bash tools/pmc_cfg5.sh > $O/pmc_cfg5.log 2>&1; cp gpurun_out/pmc_cfg5/pmc_cfg5.json $O/ 2>/dev/null; for c in FETCH_SIZE WRITE_SIZE; do cp gpurun_out/pmc_cfg5/$c.txt $O/pmc_cfg5_$c.txt; done; tail -4 $O/pmc_cfg5.log
