@@ -157,6 +157,25 @@ size_t asg_viterbi_work_bytes(const asg_problem *p);
 int asg_viterbi(asg_ctx *ctx, const asg_problem *p, void *work, size_t work_bytes, void *scores, int64_t *path,
                 int flags, void *stream);
 
+/* ---- Viterbi DECODING over the fully-connected lattice: the best label path under the transition matrix, and its tokens
+ * (wav2letter's viterbiPath).  No counterpart in the reference (README.md:33 lists Viterbi decoders as TODO).  For utterance b
+ * with len = clamp(input_lengths[b], 0, T):
+ *   v[0][i] = I[0][b][i];   v[t][i] = (max_j (v[t-1][j] + tr[i][j])) + I[t][b][i]   (1 <= t < len)
+ *   scores[b] = max_i v[len-1][i];   path[b][len-1] = argmax_i v[len-1][i];   path[b][t-1] = argmax_j (v[t-1][j] + tr[path[b][t]][j])
+ * in the dtype of the problem, adds and maxes only; every argmax takes the smallest index on a tie.  path[b][t] = -1 for
+ * t >= len; tokens[b] = path[b][0..len) with consecutive repeats collapsed, padded with -1; token_lengths[b] = their count.
+ * len == 0 or no finite path: scores[b] = -inf, path and tokens all -1, token_lengths[b] = 0.
+ * scores: [B] (dtype); path, tokens: [B][T] int64; token_lengths: [B] int64.  `targets`, `target_lengths` and `S` are ignored.
+ * `work` (asg_viterbi_decode_work_bytes):
+ *   resident route (N <= 256 in float32, N <= 128 in float64; one launch): B*T*N bytes of uint8 back-pointers;
+ *   streaming route (larger N; one launch per frame): align256(P*P*e) + T*B*P*e bytes, P = N rounded up to 64, e = 4 or 8
+ *   (the transposed transition matrix, then every frame's Viterbi vector).
+ * Every output is written by kernels (no memset), so a captured call replays with new inputs.  Limits: T, B <= 2^30,
+ * N <= 2^22 (ASG_ERR_UNSUPPORTED beyond); every index is 64-bit, so none of the loss's 32-bit state-offset limits apply. */
+size_t asg_viterbi_decode_work_bytes(const asg_problem *p);
+int asg_viterbi_decode(asg_ctx *ctx, const asg_problem *p, void *work, size_t work_bytes, void *scores, int64_t *path,
+                       int64_t *tokens, int64_t *token_lengths, int flags, void *stream);
+
 /* ---- whole-loss entry points (no counterpart in the reference's native layer: they fold the Python-side
  * `full - aligned` and reduction of asg.py:128,136-142 and their autograd into the kernels, so one ASGLoss
  * step is 2 + 2 kernel launches with no PyTorch glue kernels in between) ------------------------------------ */

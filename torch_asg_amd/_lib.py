@@ -18,7 +18,8 @@ SYMBOLS = ["asg_hip_version", "asg_hip_strerror", "asg_ctx_create", "asg_ctx_des
            "asg_aligned_backward", "asg_forward", "asg_forward_only", "asg_backward", "asg_loss_forward",
            "asg_loss_backward", "asg_viterbi_work_bytes", "asg_viterbi", "asg_loss_fused_supported",
            "asg_loss_fused_scratch_bytes", "asg_loss_fused_sync_bytes", "asg_loss_fused_forward",
-           "asg_loss_fused_backward", "asg_cluster_timeouts", "asg_reload_env", "asg_loss_forward_only", "asg_loss_forward_only_scores_bytes"]
+           "asg_loss_fused_backward", "asg_cluster_timeouts", "asg_reload_env", "asg_loss_forward_only", "asg_loss_forward_only_scores_bytes",
+           "asg_viterbi_decode_work_bytes", "asg_viterbi_decode"]
 ABI_VERSION = 230        # include/asg_hip.h: ASG_HIP_VERSION this package was written against
 
 
@@ -78,6 +79,9 @@ def lib():
     L.asg_viterbi_work_bytes.restype = sz
     L.asg_viterbi_work_bytes.argtypes = [pp]
     L.asg_viterbi.argtypes = [vp, pp, vp, sz, vp, vp, ci, vp]
+    L.asg_viterbi_decode_work_bytes.restype = sz
+    L.asg_viterbi_decode_work_bytes.argtypes = [pp]
+    L.asg_viterbi_decode.argtypes = [vp, pp, vp, sz, vp, vp, vp, vp, ci, vp]
     L.asg_loss_fused_supported.argtypes = [pp]
     L.asg_loss_fused_scratch_bytes.restype = sz
     L.asg_loss_fused_scratch_bytes.argtypes = [pp]

@@ -329,6 +329,27 @@ class HipBackend:
                        "asg_viterbi")
         return scores, path
 
+    def viterbi_decode(self, inputs, transition, input_lengths):
+        """Best label path over the full lattice -> (scores[B], path[B,T], tokens[B,T], token_lengths[B]); see
+        include/asg_hip.h::asg_viterbi_decode."""
+        self._check(inputs, transition, None, input_lengths, None)
+        if inputs.dtype not in (torch.float32, torch.float64):
+            raise RuntimeError("torch_asg_amd: expected scalar type Float or Double but found %s" % inputs.dtype)
+        L = _lib.lib()
+        T, B, N = inputs.shape
+        dev = inputs.device
+        with self._guard(dev):
+            p, keep = self._problem(inputs, transition, None, input_lengths, None)
+            work = self._buf(int(L.asg_viterbi_decode_work_bytes(ctypes.byref(p))), dev)
+            scores = torch.empty(B, dtype=inputs.dtype, device=dev)
+            out = torch.empty(2, B, T, dtype=torch.int64, device=dev)
+            token_lengths = torch.empty(B, dtype=torch.int64, device=dev)
+            # (no context: the call runs on one stream; nothing is created here, so it may run under capture)
+            _lib.check(L.asg_viterbi_decode(None, ctypes.byref(p), work.data_ptr(), work.numel(),
+                                            scores.data_ptr(), out[0].data_ptr(), out[1].data_ptr(),
+                                            token_lengths.data_ptr(), 0, self._stream(dev)), "asg_viterbi_decode")
+        return scores, out[0], out[1], token_lengths
+
     def backward(self, state, grad_full, grad_aligned, inputs, targets, transition, input_lengths, target_lengths,
                  flags=0):
         L = _lib.lib()
@@ -577,6 +598,27 @@ def viterbi_align(inputs, targets, transition, input_lengths=None, target_length
     return scores, pos, labels
 
 
+def viterbi_decode(inputs, transition, input_lengths=None):
+    """Viterbi decoding over the fully-connected ASG lattice (wav2letter's viterbiPath): the best label path under
+    `transition`, and its tokens.  No gradient.
+
+    inputs [T,B,N] emissions (time-major; a transposed [B,T,N] tensor is fine), transition [N,N] (transition[i,j] scores
+    the move from label j to label i), input_lengths int64 [B] or None (= T; clamped to [0, T]).  float16 / bfloat16
+    emissions are widened to the dtype of `transition` first.  Returns (scores [B] in the dtype of the emissions,
+    path [B,T] int64: the label of every frame, -1 for frames >= input_lengths[b], tokens [B,T] int64: the path with
+    consecutive repeats collapsed, padded with -1, token_lengths [B] int64).  Ties go to the smallest label index.  An
+    utterance of length 0, or one without a finite path, has score -inf, all -1 and no tokens.
+
+    The path is unchanged when a constant is added to every emission of a frame (so a model trained with
+    input_is_logits=True decodes its raw logits and their log_softmax to the same path); the score shifts by that
+    constant.
+    """
+    if inputs.dtype in (torch.float16, torch.bfloat16):
+        inputs = inputs.to(transition.dtype)
+    with torch.no_grad():
+        return native().viterbi_decode(inputs.detach(), transition.detach(), input_lengths)
+
+
 class FAC(torch.autograd.Function):
     """Force-aligned lattice score S_aligned[b]; same signature as the reference's FAC (asg.py:7-34)."""
 
@@ -774,6 +816,10 @@ class ASGLoss(nn.Module):
     def viterbi_align(self, inputs, targets, input_lengths=None, target_lengths=None):
         """Best-path force alignment under this module's transition matrix: see `torch_asg_amd.viterbi_align`."""
         return viterbi_align(inputs, targets, self.transition, input_lengths, target_lengths)
+
+    def viterbi_decode(self, inputs, input_lengths=None):
+        """Viterbi decoding under this module's transition matrix: see `torch_asg_amd.viterbi_decode`."""
+        return viterbi_decode(inputs, self.transition, input_lengths)
 
     @staticmethod
     def _canonical(inputs, targets, input_lengths, target_lengths):

@@ -476,6 +476,37 @@ int asg_viterbi(asg_ctx *ctx, const asg_problem *p, void *work, size_t work_byte
                                    launch_viterbi_small<double>(P, work, scores, path, (hipStream_t) stream)));
 }
 
+// Decoding reads no targets and keeps no lattice state: none of the loss's 32-bit-offset limits apply (every index into its
+// workspace and outputs is 64-bit).  The one shape limit: the transpose grid of the streaming route (N / 64 <= 65536 per axis).
+static int check_decode(const asg_problem *p) {
+    if (!p) return ASG_ERR_INVALID;
+    if (p->dtype != ASG_DTYPE_F32 && p->dtype != ASG_DTYPE_F64) return ASG_ERR_INVALID;
+    if (p->inputs_dtype != 0)
+        return (p->inputs_dtype == ASG_DTYPE_BF16 && p->dtype == ASG_DTYPE_F32) ? ASG_ERR_UNSUPPORTED : ASG_ERR_INVALID;
+    if (p->T < 1 || p->B < 1 || p->N < 1) return ASG_ERR_INVALID;
+    if (!p->inputs || !p->transition) return ASG_ERR_INVALID;
+    if (p->T > (1 << 30) || p->B > (1 << 30) || p->N > (1 << 22)) return ASG_ERR_UNSUPPORTED;
+    return ASG_OK;
+}
+
+size_t asg_viterbi_decode_work_bytes(const asg_problem *p) {
+    if (check_decode(p) != ASG_OK) return 0;
+    return decode_work_bytes(p->dtype == ASG_DTYPE_F64 ? 8 : 4, (int) p->T, (int) p->B, (int) p->N);
+}
+
+int asg_viterbi_decode(asg_ctx *ctx, const asg_problem *p, void *work, size_t work_bytes, void *scores, int64_t *path,
+                       int64_t *tokens, int64_t *token_lengths, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    int rc = check_decode(p);
+    if (rc) return rc;
+    if (!work || !scores || !path || !tokens || !token_lengths) return ASG_ERR_INVALID;
+    if (work_bytes < asg_viterbi_decode_work_bytes(p)) return ASG_ERR_WORKSPACE;
+    const Problem P = to_problem(p);
+    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths;
+    return hip_status(ASG_DISPATCH(p, launch_decode<float>(P, work, scores, pa, tk, tl, (hipStream_t) stream),
+                                   launch_decode<double>(P, work, scores, pa, tk, tl, (hipStream_t) stream)));
+}
+
 int asg_backward(asg_ctx *ctx, const asg_problem *p, const void *state, size_t state_bytes,
                  const void *grad_full, const void *grad_aligned, void *scratch, size_t scratch_bytes,
                  void *grad_transition, void *grad_inputs, int flags, void *stream) {

@@ -143,6 +143,15 @@ hipError_t launch_bwd_generic(const Problem &P, const State &W, const BwdArgs &A
 template <typename R>
 hipError_t launch_viterbi_small(const Problem &P, void *work, void *scores, void *path, hipStream_t stream);
 
+// ---- Viterbi decoding over the full lattice (asg_decode.hip).  Resident route (one launch) while decode_resident(): work =
+// [B][T][N] uint8 back-pointers; otherwise the streaming route: work = Tr^T [PAD][PAD] (256-byte aligned) + V [T][B][PAD],
+// PAD = N rounded up to 64 (decode_work_bytes)
+bool decode_resident(int elem, int N);
+size_t decode_work_bytes(int elem, int T, int B, int N);
+template <typename R>
+hipError_t launch_decode(const Problem &P, void *work, void *scores, long long *path, long long *tokens, long long *tlen,
+                         hipStream_t stream);
+
 // launches of the resident-slice forward kernel (256 < N <= 2048) of this process whose bounded waits ran out (asg_generic.hip)
 unsigned cluster_timeouts();
 
