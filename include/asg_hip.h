@@ -176,6 +176,46 @@ size_t asg_viterbi_decode_work_bytes(const asg_problem *p);
 int asg_viterbi_decode(asg_ctx *ctx, const asg_problem *p, void *work, size_t work_bytes, void *scores, int64_t *path,
                        int64_t *tokens, int64_t *token_lengths, int flags, void *stream);
 
+/* ---- Viterbi decoding over the ASG lattice COMPOSED with a deterministic weighted automaton over tokens (a token-level
+ * language model).  The product graph is compiled by the caller (torch_asg_amd.TokenGraph.compile): Q product states
+ * q = (label i, automaton state s'), one per pair for which some arc s --i--> s' exists, numbered in (s', i) order; per target q
+ * a CSR row of incoming edges from every q' = (j, s) with j != i and s --i--> s', ascending by source index.  For utterance b
+ * with len = clamp(input_lengths[b], 0, T), in the dtype of the problem, adds and maxes only:
+ *   v[0][q] = start_w[q] + I[0][i]
+ *   v[t][q] = best(stay: v[t-1][q] + tr[i][i];  edge e from q': (v[t-1][q'] + tr[i][src_label[e]]) + edge_w[e]) + I[t][i]
+ *   scores[b] = max_q (v[len-1][q] + final_w[q])
+ * "best" is the largest value, the smallest source index on a tie (the stay's source is q); the final max takes the smallest q.
+ * path[b][t] = label of the winning q at frame t, states[b][t] = its automaton state; tokens / token_lengths collapse the path as
+ * asg_viterbi_decode does.  Integer outputs are int64 [B][T] (token_lengths [B]) padded with -1; len == 0 or no finite path:
+ * score -inf, all -1, no tokens.  Every output is written by kernels (no memset), so a captured call replays with new inputs.
+ * `work` (asg_viterbi_decode_graph_work_bytes, the same on both routes): align256(T*B*Q*4) + 2*Q*B*e bytes (e = 4 or 8):
+ * int32 back-pointers, then the streaming route's Viterbi vectors (the resident route leaves them untouched).
+ *   resident route (2*(Q+N)*e <= 128 KiB, N <= 1024 and E <= 32768): one launch, one workgroup per utterance, both vectors
+ *   in LDS;  streaming route (otherwise, or ASG_FLAG_DECODE_GRAPH_STREAMING): one launch per frame, then one backtrace launch.
+ * Limits (ASG_ERR_UNSUPPORTED beyond): Q, E < 2^31, N <= 2^16, B <= 2^22, T <= 2^30.  The graph is read as given: src and
+ * src_label must hold valid indices (nothing is validated on the device). */
+#define ASG_FLAG_DECODE_GRAPH_STREAMING 16   /* asg_viterbi_decode_graph: take the streaming route even where the resident one
+                                                would be chosen (both routes give bit-identical results; for tests) */
+#define ASG_FLAG_DECODE_GRAPH_RESIDENT 32    /* ... and the resident route wherever the graph fits it (for tests and timings) */
+typedef struct asg_token_graph {
+    int64_t Q;                     /* product states                                                   */
+    int64_t E;                     /* incoming edges, the stay excluded                                */
+    int32_t N;                     /* alphabet size (= the problem's N)                                */
+    int32_t dtype;                 /* ASG_DTYPE_F32 / ASG_DTYPE_F64 of the weights (= the problem's)   */
+    const int32_t *label;          /* [Q] label i of q                                                 */
+    const int32_t *state;          /* [Q] automaton state s' of q                                      */
+    const int32_t *row;            /* [Q+1] CSR offsets of the incoming edges of q                     */
+    const int32_t *src;            /* [E] source product state of each edge, ascending within a row    */
+    const int32_t *src_label;      /* [E] label of that source                                         */
+    const void *start_w;           /* [Q] folded weight of the start arc into q, -inf if none          */
+    const void *final_w;           /* [Q] folded final weight of q's automaton state, -inf if none     */
+    const void *edge_w;            /* [E] folded arc weight of each edge                               */
+} asg_token_graph;
+size_t asg_viterbi_decode_graph_work_bytes(const asg_problem *p, const asg_token_graph *g);
+int asg_viterbi_decode_graph(asg_ctx *ctx, const asg_problem *p, const asg_token_graph *g, void *work, size_t work_bytes,
+                             void *scores, int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states,
+                             int flags, void *stream);
+
 /* ---- whole-loss entry points (no counterpart in the reference's native layer: they fold the Python-side
  * `full - aligned` and reduction of asg.py:128,136-142 and their autograd into the kernels, so one ASGLoss
  * step is 2 + 2 kernel launches with no PyTorch glue kernels in between) ------------------------------------ */

@@ -1,6 +1,7 @@
 """torch_asg_amd -- MI355X (gfx950) native ASG forward-backward hot path behind the ASGLoss surface
 of zh217/torch-asg (`from torch_asg import ASGLoss` -> `from torch_asg_amd import ASGLoss`)."""
-from .asg import ASGLoss, ASGLossFunction, FAC, FCC, ASGGPUFast, ASGGPUFastForwardOnly, viterbi_align, viterbi_decode  # noqa: F401
+from .asg import ASGLoss, ASGLossFunction, FAC, FCC, ASGGPUFast, ASGGPUFastForwardOnly, viterbi_align, viterbi_decode, viterbi_decode_graph  # noqa: F401
+from .graph import TokenGraph  # noqa: F401
 from .distributed import shard_batch, sharded_asg_loss, allreduce_transition_grad  # noqa: F401
 from ._graphed import graphed, GraphedStep  # noqa: F401
 from . import native_shim  # noqa: F401  (the reference's `torch_asg_native` on top of libasg_hip.so: native_shim.install())
@@ -30,4 +31,5 @@ def release():
 
 
 __all__ = ["ASGLoss", "ASGLossFunction", "FAC", "FCC", "ASGGPUFast", "ASGGPUFastForwardOnly", "viterbi_align", "viterbi_decode",
+           "viterbi_decode_graph", "TokenGraph",
            "shard_batch", "sharded_asg_loss", "allreduce_transition_grad", "reserve", "release", "check_faults", "graphed", "GraphedStep"]

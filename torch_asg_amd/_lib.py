@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("ASG_HIP_LIB") or os.path.join(_HERE, "csrc", "libasg_
 
 ASG_DTYPE_F32, ASG_DTYPE_F64, ASG_DTYPE_BF16 = 0, 1, 2
 FLAG_STREAMS, FLAG_SINGLE_LAUNCH, FLAG_ALPHA_SCORES = 1, 2, 8
+FLAG_DECODE_GRAPH_STREAMING, FLAG_DECODE_GRAPH_RESIDENT = 16, 32
 
 # every symbol include/asg_hip.h declares
 SYMBOLS = ["asg_hip_version", "asg_hip_strerror", "asg_ctx_create", "asg_ctx_destroy", "asg_stream_capture_id", "asg_state_bytes",
@@ -19,7 +20,8 @@ SYMBOLS = ["asg_hip_version", "asg_hip_strerror", "asg_ctx_create", "asg_ctx_des
            "asg_loss_backward", "asg_viterbi_work_bytes", "asg_viterbi", "asg_loss_fused_supported",
            "asg_loss_fused_scratch_bytes", "asg_loss_fused_sync_bytes", "asg_loss_fused_forward",
            "asg_loss_fused_backward", "asg_cluster_timeouts", "asg_reload_env", "asg_loss_forward_only", "asg_loss_forward_only_scores_bytes",
-           "asg_viterbi_decode_work_bytes", "asg_viterbi_decode"]
+           "asg_viterbi_decode_work_bytes", "asg_viterbi_decode", "asg_viterbi_decode_graph_work_bytes",
+           "asg_viterbi_decode_graph"]
 ABI_VERSION = 230        # include/asg_hip.h: ASG_HIP_VERSION this package was written against
 
 
@@ -30,6 +32,13 @@ class AsgProblem(ctypes.Structure):
                 ("input_lengths", ctypes.c_void_p), ("target_lengths", ctypes.c_void_p),
                 ("T", ctypes.c_int64), ("B", ctypes.c_int64), ("N", ctypes.c_int64), ("S", ctypes.c_int64),
                 ("dtype", ctypes.c_int32), ("inputs_dtype", ctypes.c_int32)]
+
+
+class AsgTokenGraph(ctypes.Structure):
+    _fields_ = [("Q", ctypes.c_int64), ("E", ctypes.c_int64), ("N", ctypes.c_int32), ("dtype", ctypes.c_int32),
+                ("label", ctypes.c_void_p), ("state", ctypes.c_void_p), ("row", ctypes.c_void_p), ("src", ctypes.c_void_p),
+                ("src_label", ctypes.c_void_p), ("start_w", ctypes.c_void_p), ("final_w", ctypes.c_void_p),
+                ("edge_w", ctypes.c_void_p)]
 
 
 _LIB = None
@@ -82,6 +91,10 @@ def lib():
     L.asg_viterbi_decode_work_bytes.restype = sz
     L.asg_viterbi_decode_work_bytes.argtypes = [pp]
     L.asg_viterbi_decode.argtypes = [vp, pp, vp, sz, vp, vp, vp, vp, ci, vp]
+    gp = ctypes.POINTER(AsgTokenGraph)
+    L.asg_viterbi_decode_graph_work_bytes.restype = sz
+    L.asg_viterbi_decode_graph_work_bytes.argtypes = [pp, gp]
+    L.asg_viterbi_decode_graph.argtypes = [vp, pp, gp, vp, sz, vp, vp, vp, vp, vp, ci, vp]
     L.asg_loss_fused_supported.argtypes = [pp]
     L.asg_loss_fused_scratch_bytes.restype = sz
     L.asg_loss_fused_scratch_bytes.argtypes = [pp]

@@ -350,6 +350,58 @@ class HipBackend:
                                             token_lengths.data_ptr(), 0, self._stream(dev)), "asg_viterbi_decode")
         return scores, out[0], out[1], token_lengths
 
+    def viterbi_decode_graph(self, inputs, transition, graph, input_lengths, lm_weight=1.0, token_score=0.0,
+                             max_work_bytes=1 << 30, flags=0):
+        """Best path over the lattice composed with a token automaton -> (scores[B], path[B,T], tokens[B,T],
+        token_lengths[B], states[B,T]); see include/asg_hip.h::asg_viterbi_decode_graph.  Utterances are decoded in
+        consecutive groups whose workspace fits `max_work_bytes` (at least one utterance per group)."""
+        from . import graph as _graph
+        self._check(inputs, transition, None, input_lengths, None)
+        if inputs.dtype not in (torch.float32, torch.float64):
+            raise RuntimeError("torch_asg_amd: expected scalar type Float or Double but found %s" % inputs.dtype)
+        if not isinstance(graph, _graph.TokenGraph):
+            raise TypeError("torch_asg_amd: graph must be a torch_asg_amd.TokenGraph")
+        T, B, N = inputs.shape
+        if graph.N != N:
+            raise RuntimeError("torch_asg_amd: the graph is over %d tokens but the emissions have N = %d" % (graph.N, N))
+        if input_lengths is not None and tuple(input_lengths.shape) != (B,):
+            raise RuntimeError("torch_asg_amd: input_lengths must have shape [%d]" % B)
+        L = _lib.lib()
+        dev = inputs.device
+        with self._guard(dev):
+            compiled = graph.compile(dev, inputs.dtype, lm_weight, token_score)
+            g = _graph.abi_graph(compiled)
+            p, keep = self._problem(inputs, transition, None, input_lengths, None)
+            if input_lengths is not None:
+                input_lengths = keep[-1]                       # (on the device, contiguous)
+
+            def work_bytes(nb):
+                p.B = nb
+                return int(L.asg_viterbi_decode_graph_work_bytes(ctypes.byref(p), ctypes.byref(g)))
+            per = max(work_bytes(1), 1)
+            gsz = max(1, min(B, int(max_work_bytes) // per))
+            while gsz > 1 and work_bytes(gsz) > max_work_bytes:
+                gsz -= 1
+            work = self._buf(work_bytes(gsz), dev)
+            scores = torch.empty(B, dtype=inputs.dtype, device=dev)
+            out = torch.empty(3, B, T, dtype=torch.int64, device=dev)        # path, tokens, states
+            token_lengths = torch.empty(B, dtype=torch.int64, device=dev)
+            stream = self._stream(dev)
+            # (no context: the call runs on one stream; nothing is created here once the graph is compiled, so it may run
+            # under capture)
+            for b0 in range(0, B, gsz):
+                b1 = min(B, b0 + gsz)
+                x = inputs[:, b0:b1]
+                p.inputs = x.data_ptr()
+                p.B = b1 - b0
+                if input_lengths is not None:
+                    p.input_lengths = input_lengths[b0:b1].data_ptr()
+                _lib.check(L.asg_viterbi_decode_graph(None, ctypes.byref(p), ctypes.byref(g), work.data_ptr(), work.numel(),
+                                                      scores[b0:].data_ptr(), out[0, b0].data_ptr(), out[1, b0].data_ptr(),
+                                                      token_lengths[b0:].data_ptr(), out[2, b0].data_ptr(), flags, stream),
+                           "asg_viterbi_decode_graph")
+        return scores, out[0], out[1], token_lengths, out[2]
+
     def backward(self, state, grad_full, grad_aligned, inputs, targets, transition, input_lengths, target_lengths,
                  flags=0):
         L = _lib.lib()
@@ -619,6 +671,31 @@ def viterbi_decode(inputs, transition, input_lengths=None):
         return native().viterbi_decode(inputs.detach(), transition.detach(), input_lengths)
 
 
+def viterbi_decode_graph(inputs, transition, graph, input_lengths=None, lm_weight=1.0, token_score=0.0,
+                         max_work_bytes=1 << 30):
+    """Exact Viterbi decoding over the ASG lattice composed with a token automaton `graph` (a `TokenGraph`, e.g. an n-gram
+    LM from `TokenGraph.from_ngram`).  No pruning and no gradient.
+
+    Every move to a new label is a token: it takes the automaton's arc for that token and adds
+    lm_weight * weight + token_score; the end adds lm_weight * final.  Repeated labels are one token and leave the automaton
+    where it is.  Arithmetic is in the dtype of the emissions (lm_weight and token_score rounded to it, then folded into the
+    arcs on the host); ties go to the smallest product-state index.  Inputs, strides, float16 / bfloat16 widening and errors
+    are those of `viterbi_decode`.  Returns (scores [B], path [B,T] int64 labels, tokens [B,T] int64, token_lengths [B] int64,
+    states [B,T] int64: the automaton state after every frame); integer outputs are padded with -1, and an utterance of
+    length 0 or without a finite path has score -inf, all -1 and no tokens.  With a one-state automaton of zero weights
+    and token_score = 0 the first four equal `viterbi_decode` bit for bit.
+
+    The graph is compiled for the device, dtype, lm_weight and token_score on first use and cached on it; later calls copy
+    nothing to the device and do not synchronise, so they can be captured.  The batch is decoded in consecutive groups of
+    utterances whose workspace (int32 back-pointers, T * Q * 4 bytes per utterance) fits `max_work_bytes`.
+    """
+    if inputs.dtype in (torch.float16, torch.bfloat16):
+        inputs = inputs.to(transition.dtype)
+    with torch.no_grad():
+        return native().viterbi_decode_graph(inputs.detach(), transition.detach(), graph, input_lengths, lm_weight,
+                                             token_score, max_work_bytes)
+
+
 class FAC(torch.autograd.Function):
     """Force-aligned lattice score S_aligned[b]; same signature as the reference's FAC (asg.py:7-34)."""
 
@@ -820,6 +897,11 @@ class ASGLoss(nn.Module):
     def viterbi_decode(self, inputs, input_lengths=None):
         """Viterbi decoding under this module's transition matrix: see `torch_asg_amd.viterbi_decode`."""
         return viterbi_decode(inputs, self.transition, input_lengths)
+
+    def viterbi_decode_graph(self, inputs, graph, input_lengths=None, lm_weight=1.0, token_score=0.0, max_work_bytes=1 << 30):
+        """Viterbi decoding with a token automaton under this module's transition matrix: see
+        `torch_asg_amd.viterbi_decode_graph`."""
+        return viterbi_decode_graph(inputs, self.transition, graph, input_lengths, lm_weight, token_score, max_work_bytes)
 
     @staticmethod
     def _canonical(inputs, targets, input_lengths, target_lengths):

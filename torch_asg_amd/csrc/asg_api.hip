@@ -507,6 +507,40 @@ int asg_viterbi_decode(asg_ctx *ctx, const asg_problem *p, void *work, size_t wo
                                    launch_decode<double>(P, work, scores, pa, tk, tl, (hipStream_t) stream)));
 }
 
+static int check_decode_graph(const asg_problem *p, const asg_token_graph *g) {
+    int rc = check_decode(p);
+    if (rc) return rc;
+    if (!g || g->dtype != p->dtype || g->N != p->N || g->Q < 0 || g->E < 0) return ASG_ERR_INVALID;
+    if (g->Q >= (int64_t) 1 << 31 || g->E >= (int64_t) 1 << 31 || p->N > (1 << 16) || p->B > (1 << 22)) return ASG_ERR_UNSUPPORTED;
+    if (g->Q > 0 && (!g->label || !g->state || !g->row || !g->start_w || !g->final_w)) return ASG_ERR_INVALID;
+    if (g->E > 0 && (!g->src || !g->src_label || !g->edge_w)) return ASG_ERR_INVALID;
+    return ASG_OK;
+}
+
+size_t asg_viterbi_decode_graph_work_bytes(const asg_problem *p, const asg_token_graph *g) {
+    if (check_decode_graph(p, g) != ASG_OK) return 0;
+    return graph_decode_work_bytes(p->dtype == ASG_DTYPE_F64 ? 8 : 4, (int) p->T, (int) p->B, (int) g->Q);
+}
+
+int asg_viterbi_decode_graph(asg_ctx *ctx, const asg_problem *p, const asg_token_graph *g, void *work, size_t work_bytes,
+                             void *scores, int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states,
+                             int flags, void *stream) {
+    (void) ctx;
+    int rc = check_decode_graph(p, g);
+    if (rc) return rc;
+    if (!work || !scores || !path || !tokens || !token_lengths || !states) return ASG_ERR_INVALID;
+    if (work_bytes < asg_viterbi_decode_graph_work_bytes(p, g)) return ASG_ERR_WORKSPACE;
+    const Problem P = to_problem(p);
+    GraphArgs G{};
+    G.Q = (int) g->Q; G.E = (int) g->E;
+    G.label = g->label; G.state = g->state; G.row = g->row; G.src = g->src; G.src_label = g->src_label;
+    G.start_w = g->start_w; G.final_w = g->final_w; G.edge_w = g->edge_w;
+    const int route = (flags & ASG_FLAG_DECODE_GRAPH_STREAMING) ? 1 : ((flags & ASG_FLAG_DECODE_GRAPH_RESIDENT) ? 2 : 0);
+    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
+    return hip_status(ASG_DISPATCH(p, launch_decode_graph<float>(P, G, route, work, scores, pa, tk, tl, st, (hipStream_t) stream),
+                                   launch_decode_graph<double>(P, G, route, work, scores, pa, tk, tl, st, (hipStream_t) stream)));
+}
+
 int asg_backward(asg_ctx *ctx, const asg_problem *p, const void *state, size_t state_bytes,
                  const void *grad_full, const void *grad_aligned, void *scratch, size_t scratch_bytes,
                  void *grad_transition, void *grad_inputs, int flags, void *stream) {

@@ -152,6 +152,22 @@ template <typename R>
 hipError_t launch_decode(const Problem &P, void *work, void *scores, long long *path, long long *tokens, long long *tlen,
                          hipStream_t stream);
 
+// ---- Viterbi decoding over the ASG lattice composed with a token automaton (asg_decode_graph.hip).  The compiled product
+// graph as the kernels read it (asg_token_graph; every array on the device, Q, E < 2^31).  Work = int32 back-pointers
+// [B][T][Q] (resident route) or [T][Q][B] (streaming route), 256-byte aligned, then the streaming route's Viterbi vectors
+// [2][Q][B]: the same size on both routes (graph_decode_work_bytes).
+struct GraphArgs {
+    int Q, E;
+    const int *label, *state, *row, *src, *src_label;     // [Q], [Q], [Q+1], [E], [E]
+    const void *start_w, *final_w, *edge_w;               // [Q], [Q], [E] in the dtype of the problem
+};
+// route: 0 = by graph_decode_resident, 1 = streaming, 2 = resident wherever the graph fits in LDS
+bool graph_decode_resident(int elem, int N, int Q, int E);
+size_t graph_decode_work_bytes(int elem, int T, int B, int Q);
+template <typename R>
+hipError_t launch_decode_graph(const Problem &P, const GraphArgs &G, int route, void *work, void *scores, long long *path,
+                               long long *tokens, long long *tlen, long long *states, hipStream_t stream);
+
 // launches of the resident-slice forward kernel (256 < N <= 2048) of this process whose bounded waits ran out (asg_generic.hip)
 unsigned cluster_timeouts();
 
