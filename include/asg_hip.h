@@ -216,6 +216,51 @@ int asg_viterbi_decode_graph(asg_ctx *ctx, const asg_problem *p, const asg_token
                              void *scores, int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states,
                              int flags, void *stream);
 
+/* ---- Full score of the ASG lattice COMPOSED with a token automaton (the log-semiring counterpart of the decoder above), its
+ * gradients, and the automaton's score of each target: the pieces of an ASG loss whose normaliser includes a token-level
+ * prior.  No counterpart in the reference.  For utterance b with len = clamp(input_lengths[b], 0, T), in the dtype of the problem:
+ *   alpha[0][q] = start_w[q] + I[0][i]
+ *   alpha[t][q] = lse(stay: alpha[t-1][q] + tr[i][i];  edge e from q': (alpha[t-1][q'] + tr[i][src_label[e]]) + edge_w[e]) + I[t][i]
+ *   scores[b]   = lse_q(alpha[len-1][q] + final_w[q])        (-inf, never NaN, when len == 0 or no path exists)
+ * every lse max-then-sum in a fixed candidate order (the stay first, then the edges ascending).
+ * Backward: grad_inputs [T,B,N] (contiguous, every element written, zero rows at t >= len) = grad_scores[b] * the label posteriors;
+ * grad_transition [N,N] (contiguous) = sum_b grad_scores[b] * the expected counts of every (i, j) move.  No float atomics and
+ * fixed reduction orders: bit-identical run to run on each route.  It needs the alpha that the forward stored in `work`
+ * (ASG_FLAG_GRAPH_LOSS_KEEP_ALPHA), the scores of that forward, and the same problem (the emissions and transitions are read again).
+ * Target scores: out[b] = arcw[start][y_1] + sum_k arcw[s_k][y_{k+1}] + finw[s_end] over targets[b][:target_lengths[b]] with
+ * consecutive equal labels merged, -inf if the automaton rejects them (reads targets, target_lengths and S).
+ *   work:    asg_graph_full_work_bytes(p, gl, store) = (store ? T : 2) * Q * B * e bytes (e = 4 or 8)
+ *   scratch: asg_graph_full_scratch_bytes(p, gl) = align256(2 * Q * B * e) + (Q + E) * B * e bytes
+ * Routes: resident (2*Q*e <= 128 KiB and E <= 4096; one workgroup per utterance) or streaming (one launch per frame and
+ * direction).  Limits and validation as asg_viterbi_decode_graph.  Every output is written by kernels (no memset). */
+#define ASG_FLAG_GRAPH_LOSS_KEEP_ALPHA 64        /* asg_graph_full_forward: store alpha in `work` for asg_graph_full_backward */
+#define ASG_FLAG_GRAPH_LOSS_STREAMING 128   /* take the streaming route (for tests and timings) */
+#define ASG_FLAG_GRAPH_LOSS_RESIDENT 256    /* take the resident route wherever the vectors fit (for tests and timings) */
+typedef struct asg_token_graph_loss {
+    const asg_token_graph *graph;  /* the product graph (its arrays on the device)                         */
+    int64_t S;                     /* automaton states                                                      */
+    int32_t start;                 /* start state                                                           */
+    int32_t reserved;
+    const int32_t *tgt;            /* [E] target product state of each incoming edge                       */
+    const int32_t *orow;           /* [Q+1] CSR offsets of the outgoing edges of q                         */
+    const int32_t *oedge;          /* [E] incoming-edge index of each outgoing edge, ascending by (src, tgt) */
+    const int32_t *lrow;           /* [N+1] CSR offsets of the product states of each label                */
+    const int32_t *lq;             /* [Q] product states grouped by label, ascending                       */
+    const int64_t *pkey;           /* [E] label pair label[tgt] * N + src_label of the edges in pedge order, ascending */
+    const int32_t *pedge;          /* [E] incoming-edge indices sorted by pair (stable)                    */
+    const int32_t *next;           /* [S,N] next state, -1 where no arc                                    */
+    const void *arcw;              /* [S,N] folded arc weights, -inf where no arc                          */
+    const void *finw;              /* [S] folded final weights, -inf where not accepting                   */
+} asg_token_graph_loss;
+size_t asg_graph_full_work_bytes(const asg_problem *p, const asg_token_graph_loss *gl, int store);
+size_t asg_graph_full_scratch_bytes(const asg_problem *p, const asg_token_graph_loss *gl);
+int asg_graph_full_forward(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_loss *gl, void *work, size_t work_bytes,
+                           void *scores, int flags, void *stream);
+int asg_graph_full_backward(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_loss *gl, const void *work,
+                            size_t work_bytes, const void *scores, const void *grad_scores, void *grad_inputs,
+                            void *grad_transition, void *scratch, size_t scratch_bytes, int flags, void *stream);
+int asg_graph_target_scores(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_loss *gl, void *out, void *stream);
+
 /* ---- whole-loss entry points (no counterpart in the reference's native layer: they fold the Python-side
  * `full - aligned` and reduction of asg.py:128,136-142 and their autograd into the kernels, so one ASGLoss
  * step is 2 + 2 kernel launches with no PyTorch glue kernels in between) ------------------------------------ */

@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("ASG_HIP_LIB") or os.path.join(_HERE, "csrc", "libasg_
 ASG_DTYPE_F32, ASG_DTYPE_F64, ASG_DTYPE_BF16 = 0, 1, 2
 FLAG_STREAMS, FLAG_SINGLE_LAUNCH, FLAG_ALPHA_SCORES = 1, 2, 8
 FLAG_DECODE_GRAPH_STREAMING, FLAG_DECODE_GRAPH_RESIDENT = 16, 32
+FLAG_GRAPH_LOSS_KEEP_ALPHA, FLAG_GRAPH_LOSS_STREAMING, FLAG_GRAPH_LOSS_RESIDENT = 64, 128, 256
 
 # every symbol include/asg_hip.h declares
 SYMBOLS = ["asg_hip_version", "asg_hip_strerror", "asg_ctx_create", "asg_ctx_destroy", "asg_stream_capture_id", "asg_state_bytes",
@@ -21,7 +22,8 @@ SYMBOLS = ["asg_hip_version", "asg_hip_strerror", "asg_ctx_create", "asg_ctx_des
            "asg_loss_fused_scratch_bytes", "asg_loss_fused_sync_bytes", "asg_loss_fused_forward",
            "asg_loss_fused_backward", "asg_cluster_timeouts", "asg_reload_env", "asg_loss_forward_only", "asg_loss_forward_only_scores_bytes",
            "asg_viterbi_decode_work_bytes", "asg_viterbi_decode", "asg_viterbi_decode_graph_work_bytes",
-           "asg_viterbi_decode_graph"]
+           "asg_viterbi_decode_graph", "asg_graph_full_work_bytes", "asg_graph_full_scratch_bytes", "asg_graph_full_forward",
+           "asg_graph_full_backward", "asg_graph_target_scores"]
 ABI_VERSION = 230        # include/asg_hip.h: ASG_HIP_VERSION this package was written against
 
 
@@ -39,6 +41,12 @@ class AsgTokenGraph(ctypes.Structure):
                 ("label", ctypes.c_void_p), ("state", ctypes.c_void_p), ("row", ctypes.c_void_p), ("src", ctypes.c_void_p),
                 ("src_label", ctypes.c_void_p), ("start_w", ctypes.c_void_p), ("final_w", ctypes.c_void_p),
                 ("edge_w", ctypes.c_void_p)]
+
+
+class AsgTokenGraphLoss(ctypes.Structure):
+    _fields_ = [("graph", ctypes.POINTER(AsgTokenGraph)), ("S", ctypes.c_int64), ("start", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)] + [(n, ctypes.c_void_p) for n in ("tgt", "orow", "oedge", "lrow", "lq", "pkey", "pedge",
+                                                                               "next", "arcw", "finw")]
 
 
 _LIB = None
@@ -95,6 +103,14 @@ def lib():
     L.asg_viterbi_decode_graph_work_bytes.restype = sz
     L.asg_viterbi_decode_graph_work_bytes.argtypes = [pp, gp]
     L.asg_viterbi_decode_graph.argtypes = [vp, pp, gp, vp, sz, vp, vp, vp, vp, vp, ci, vp]
+    lp = ctypes.POINTER(AsgTokenGraphLoss)
+    L.asg_graph_full_work_bytes.restype = sz
+    L.asg_graph_full_work_bytes.argtypes = [pp, lp, ci]
+    L.asg_graph_full_scratch_bytes.restype = sz
+    L.asg_graph_full_scratch_bytes.argtypes = [pp, lp]
+    L.asg_graph_full_forward.argtypes = [vp, pp, lp, vp, sz, vp, ci, vp]
+    L.asg_graph_full_backward.argtypes = [vp, pp, lp, vp, sz, vp, vp, vp, vp, vp, sz, ci, vp]
+    L.asg_graph_target_scores.argtypes = [vp, pp, lp, vp, vp]
     L.asg_loss_fused_supported.argtypes = [pp]
     L.asg_loss_fused_scratch_bytes.restype = sz
     L.asg_loss_fused_scratch_bytes.argtypes = [pp]

@@ -402,6 +402,108 @@ class HipBackend:
                            "asg_viterbi_decode_graph")
         return scores, out[0], out[1], token_lengths, out[2]
 
+    def _graph_loss_args(self, inputs, transition, graph, input_lengths, lm_weight, token_score):
+        """Checks shared by the graph-loss entry points -> the compiled graph and its asg_token_graph_loss view."""
+        from . import graph as _graph
+        self._check(inputs, transition, None, input_lengths, None)
+        if inputs.dtype not in (torch.float32, torch.float64):
+            raise RuntimeError("torch_asg_amd: expected scalar type Float or Double but found %s" % inputs.dtype)
+        if not isinstance(graph, _graph.TokenGraph):
+            raise TypeError("torch_asg_amd: graph must be a torch_asg_amd.TokenGraph")
+        T, B, N = inputs.shape
+        if graph.N != N:
+            raise RuntimeError("torch_asg_amd: the graph is over %d tokens but the emissions have N = %d" % (graph.N, N))
+        if input_lengths is not None and tuple(input_lengths.shape) != (B,):
+            raise RuntimeError("torch_asg_amd: input_lengths must have shape [%d]" % B)
+        compiled = graph.compile_loss(inputs.device, inputs.dtype, lm_weight, token_score)
+        return compiled, _graph.abi_graph_loss(compiled)
+
+    def graph_full_forward(self, inputs, transition, graph, input_lengths, lm_weight=1.0, token_score=0.0, store=False,
+                           max_work_bytes=1 << 30, flags=0):
+        """Full score of the lattice composed with a token automaton -> (scores[B], saved); see
+        include/asg_hip.h::asg_graph_full_forward.  Utterances run in consecutive groups whose workspace fits `max_work_bytes`.
+        With `store`, saved = [(b0, b1, work)]: each group's stored alpha, for graph_full_backward; None otherwise."""
+        L = _lib.lib()
+        dev = inputs.device
+        B = inputs.shape[1]
+        with self._guard(dev):
+            compiled, gl = self._graph_loss_args(inputs, transition, graph, input_lengths, lm_weight, token_score)
+            p, keep = self._problem(inputs, transition, None, input_lengths, None)
+            if input_lengths is not None:
+                input_lengths = keep[-1]
+
+            def work_bytes(nb):
+                p.B = nb
+                return int(L.asg_graph_full_work_bytes(ctypes.byref(p), ctypes.byref(gl), int(store)))
+            per = max(work_bytes(1), 1)
+            gsz = max(1, min(B, int(max_work_bytes) // per))
+            while gsz > 1 and work_bytes(gsz) > max_work_bytes:
+                gsz -= 1
+            scores = torch.empty(B, dtype=inputs.dtype, device=dev)
+            fl = flags | (_lib.FLAG_GRAPH_LOSS_KEEP_ALPHA if store else 0)
+            stream = self._stream(dev)
+            saved, work = [], None
+            for b0 in range(0, B, gsz):
+                b1 = min(B, b0 + gsz)
+                if store or work is None:
+                    work = self._buf(work_bytes(b1 - b0), dev)
+                p.inputs = inputs[:, b0:b1].data_ptr()
+                p.B = b1 - b0
+                if input_lengths is not None:
+                    p.input_lengths = input_lengths[b0:b1].data_ptr()
+                _lib.check(L.asg_graph_full_forward(None, ctypes.byref(p), ctypes.byref(gl), work.data_ptr(), work.numel(),
+                                                    scores[b0:].data_ptr(), fl, stream), "asg_graph_full_forward")
+                if store:
+                    saved.append((b0, b1, work))
+        return scores, (saved if store else None)
+
+    def graph_full_backward(self, saved, scores, grad_scores, inputs, transition, graph, input_lengths, lm_weight=1.0,
+                            token_score=0.0, flags=0):
+        """(grad_transition[N,N], grad_inputs[T,B,N]) of sum_b grad_scores[b] * scores[b] from graph_full_forward's saved alpha."""
+        L = _lib.lib()
+        dev = inputs.device
+        T, B, N = inputs.shape
+        with self._guard(dev):
+            compiled, gl = self._graph_loss_args(inputs, transition, graph, input_lengths, lm_weight, token_score)
+            p, keep = self._problem(inputs, transition, None, input_lengths, None)
+            if input_lengths is not None:
+                input_lengths = keep[-1]
+            gs = grad_scores.to(inputs.dtype).contiguous()
+            gin = torch.empty(T, B, N, dtype=inputs.dtype, device=dev)
+            gtr = None
+            stream = self._stream(dev)
+            for b0, b1, work in saved:
+                nb = b1 - b0
+                p.inputs = inputs[:, b0:b1].data_ptr()
+                p.B = nb
+                if input_lengths is not None:
+                    p.input_lengths = input_lengths[b0:b1].data_ptr()
+                scratch = self._buf(L.asg_graph_full_scratch_bytes(ctypes.byref(p), ctypes.byref(gl)), dev)
+                gin_g = gin if nb == B else torch.empty(T, nb, N, dtype=inputs.dtype, device=dev)
+                gtr_g = torch.empty(N, N, dtype=inputs.dtype, device=dev)
+                _lib.check(L.asg_graph_full_backward(None, ctypes.byref(p), ctypes.byref(gl), work.data_ptr(), work.numel(),
+                                                     scores[b0:].data_ptr(), gs[b0:].data_ptr(), gin_g.data_ptr(),
+                                                     gtr_g.data_ptr(), scratch.data_ptr(), scratch.numel(), flags, stream),
+                           "asg_graph_full_backward")
+                if nb != B:
+                    gin[:, b0:b1].copy_(gin_g)
+                gtr = gtr_g if gtr is None else gtr + gtr_g
+        return gtr, gin
+
+    def graph_target_scores(self, inputs, transition, graph, targets, target_lengths, lm_weight=1.0, token_score=0.0):
+        """[B]: the automaton's score of every target sequence (consecutive repeats merged), -inf where it rejects it; see
+        include/asg_hip.h::asg_graph_target_scores."""
+        L = _lib.lib()
+        dev = inputs.device
+        self._check(inputs, transition, targets, None, target_lengths)
+        with self._guard(dev):
+            compiled, gl = self._graph_loss_args(inputs, transition, graph, None, lm_weight, token_score)
+            p, keep = self._problem(inputs, transition, targets, None, target_lengths)
+            out = torch.empty(inputs.shape[1], dtype=inputs.dtype, device=dev)
+            _lib.check(L.asg_graph_target_scores(None, ctypes.byref(p), ctypes.byref(gl), out.data_ptr(), self._stream(dev)),
+                       "asg_graph_target_scores")
+        return out
+
     def backward(self, state, grad_full, grad_aligned, inputs, targets, transition, input_lengths, target_lengths,
                  flags=0):
         L = _lib.lib()
@@ -696,6 +798,82 @@ def viterbi_decode_graph(inputs, transition, graph, input_lengths=None, lm_weigh
                                              token_score, max_work_bytes)
 
 
+class GraphFullScore(torch.autograd.Function):
+    """Full score of the ASG lattice composed with a token automaton, [B] (asg_graph_full_forward / _backward).  alpha is
+    stored only when a gradient w.r.t. inputs or transition is needed."""
+
+    @staticmethod
+    def forward(ctx, inputs, transition, graph, input_lengths, lm_weight, token_score, max_work_bytes, flags):
+        store = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
+        scores, saved = native().graph_full_forward(inputs, transition, graph, input_lengths, lm_weight, token_score, store,
+                                                    max_work_bytes, flags)
+        ctx.save_for_backward(inputs, transition, input_lengths, scores)
+        ctx.saved, ctx.graph, ctx.args = saved, graph, (lm_weight, token_score, flags)
+        return scores
+
+    @staticmethod
+    def backward(ctx, grad):
+        inputs, transition, input_lengths, scores = ctx.saved_tensors
+        lw, ts, flags = ctx.args
+        gtr, gin = native().graph_full_backward(ctx.saved, scores, grad, inputs, transition, ctx.graph, input_lengths, lw, ts,
+                                                flags)
+        return gin, gtr, None, None, None, None, None, None
+
+
+def graph_full_score(inputs, transition, graph, input_lengths=None, lm_weight=1.0, token_score=0.0, max_work_bytes=1 << 30):
+    """logsumexp over every label path of the ASG lattice composed with a token automaton `graph` (a `TokenGraph`): each path
+    scores its emissions and transitions plus the automaton's score of its tokens (lm_weight * weight + token_score per token,
+    lm_weight * final at the end; -inf if the automaton rejects them) -- the log-semiring counterpart of `viterbi_decode_graph`.
+    Differentiable w.r.t. `inputs` and `transition` (the automaton, lm_weight and token_score are constants).  Returns [B] in the
+    dtype of the emissions; -inf for an utterance of length 0 or without any accepted path.  Inputs, strides, widening of
+    float16 / bfloat16 and the grouping under `max_work_bytes` (alpha, T * Q * e bytes per utterance when a gradient is
+    needed) are those of `viterbi_decode_graph`."""
+    if inputs.dtype in (torch.float16, torch.bfloat16):
+        inputs = inputs.to(transition.dtype)
+    return GraphFullScore.apply(inputs, transition, graph, input_lengths, lm_weight, token_score, max_work_bytes, 0)
+
+
+def _graph_loss_per_utterance(inputs, targets, transition, graph, input_lengths, target_lengths, lm_weight, token_score,
+                              max_work_bytes, flags):
+    """[B] losses full_graph - (FAC + A(collapse(target))); +inf (never NaN) where the target has no alignment or the automaton
+    rejects it, and then only the full-graph posterior reaches the gradients.  Lengths must be given (ASGLoss._canonical)."""
+    full = GraphFullScore.apply(inputs, transition, graph, input_lengths, lm_weight, token_score, max_work_bytes, flags)
+    with torch.no_grad():
+        walk = native().graph_target_scores(inputs.detach(), transition.detach(), graph, targets, target_lengths, lm_weight,
+                                            token_score)
+    aligned = FAC.apply(transition, inputs, targets, input_lengths, target_lengths) + walk
+    fd, ad = full.detach(), aligned.detach()
+    ok_f, ok_a = torch.isfinite(fd), torch.isfinite(ad)
+    zero = torch.zeros_like(fd)
+    value = torch.where(ok_a, fd - ad, torch.full_like(fd, float("inf")))
+    # value carries the numbers; the two zero-valued terms carry the gradients, masked where a score is infinite
+    return value + torch.where(ok_f, full - fd, zero) - torch.where(ok_a, aligned - ad, zero)
+
+
+def _reduce(per_utt, reduction):
+    if reduction == 'mean':
+        return per_utt.mean()
+    if reduction == 'sum':
+        return per_utt.sum()
+    return per_utt
+
+
+def graph_asg_loss(inputs, targets, transition, graph, input_lengths=None, target_lengths=None, lm_weight=1.0,
+                   token_score=0.0, reduction='none', max_work_bytes=1 << 30):
+    """ASG loss whose normaliser is the lattice composed with a token automaton `graph`:
+    loss[b] = graph_full_score[b] - (S_aligned[b] + A(collapse(targets[b]))), where S_aligned is the force-aligned score (`FAC`)
+    and A the automaton's score of the target with consecutive repeats merged.  exp(-loss) is the probability of the target
+    under the composed model.  +inf where the target cannot be aligned (target_length > input_length, length 0) or the automaton
+    rejects it; those utterances' gradient rows hold only the full-graph posterior.  Defaults and S > T truncation as
+    `ASGLoss.forward`; reduction 'none' (default), 'sum' or 'mean'."""
+    if inputs.dtype in (torch.float16, torch.bfloat16):
+        inputs = inputs.to(transition.dtype)
+    targets, input_lengths, target_lengths = ASGLoss._canonical(inputs, targets, input_lengths, target_lengths)
+    per = _graph_loss_per_utterance(inputs, targets, transition, graph, input_lengths, target_lengths, lm_weight,
+                                    token_score, max_work_bytes, 0)
+    return _reduce(per, reduction)
+
+
 class FAC(torch.autograd.Function):
     """Force-aligned lattice score S_aligned[b]; same signature as the reference's FAC (asg.py:7-34)."""
 
@@ -902,6 +1080,20 @@ class ASGLoss(nn.Module):
         """Viterbi decoding with a token automaton under this module's transition matrix: see
         `torch_asg_amd.viterbi_decode_graph`."""
         return viterbi_decode_graph(inputs, self.transition, graph, input_lengths, lm_weight, token_score, max_work_bytes)
+
+    def graph_loss(self, inputs, targets, graph, input_lengths=None, target_lengths=None, lm_weight=1.0, token_score=0.0,
+                   max_work_bytes=1 << 30):
+        """`torch_asg_amd.graph_asg_loss` under this module's transition matrix, reduction and scale_mode.  float16 / bfloat16
+        emissions are widened to the dtype of `transition`; batch-major views ([B,T,N] transposed) need no copy."""
+        if inputs.dtype in (torch.float16, torch.bfloat16):
+            inputs = inputs.to(self.transition.dtype)
+        targets, input_lengths, target_lengths = self._canonical(inputs, targets, input_lengths, target_lengths)
+        weights = self._utterance_weights(inputs, input_lengths, target_lengths)
+        per = _graph_loss_per_utterance(inputs, targets, self.transition, graph, input_lengths, target_lengths, lm_weight,
+                                        token_score, max_work_bytes, 0)
+        if weights is not None:
+            per = per * weights
+        return _reduce(per, self.reduction)
 
     @staticmethod
     def _canonical(inputs, targets, input_lengths, target_lengths):

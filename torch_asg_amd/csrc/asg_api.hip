@@ -541,6 +541,98 @@ int asg_viterbi_decode_graph(asg_ctx *ctx, const asg_problem *p, const asg_token
                                    launch_decode_graph<double>(P, G, route, work, scores, pa, tk, tl, st, (hipStream_t) stream)));
 }
 
+static int check_graph_loss(const asg_problem *p, const asg_token_graph_loss *gl) {
+    if (!gl) return ASG_ERR_INVALID;
+    int rc = check_decode_graph(p, gl->graph);
+    if (rc) return rc;
+    const asg_token_graph *g = gl->graph;
+    if (gl->S < 1 || gl->start < 0 || gl->start >= gl->S) return ASG_ERR_INVALID;
+    if (gl->S >= (int64_t) 1 << 31) return ASG_ERR_UNSUPPORTED;
+    if (!gl->orow || !gl->lrow || !gl->next || !gl->arcw || !gl->finw) return ASG_ERR_INVALID;
+    if (g->Q > 0 && !gl->lq) return ASG_ERR_INVALID;
+    if (g->E > 0 && (!gl->tgt || !gl->oedge || !gl->pkey || !gl->pedge)) return ASG_ERR_INVALID;
+    return ASG_OK;
+}
+
+static GraphArgs to_graph_args(const asg_token_graph *g) {
+    GraphArgs G{};
+    G.Q = (int) g->Q; G.E = (int) g->E;
+    G.label = g->label; G.state = g->state; G.row = g->row; G.src = g->src; G.src_label = g->src_label;
+    G.start_w = g->start_w; G.final_w = g->final_w; G.edge_w = g->edge_w;
+    return G;
+}
+
+static GraphLossArgs to_graph_loss_args(const asg_token_graph_loss *gl) {
+    GraphLossArgs L{};
+    L.S = (int) gl->S; L.start = gl->start;
+    L.tgt = gl->tgt; L.orow = gl->orow; L.oedge = gl->oedge; L.lrow = gl->lrow; L.lq = gl->lq; L.pedge = gl->pedge;
+    L.next = gl->next; L.pkey = gl->pkey; L.arcw = gl->arcw; L.finw = gl->finw;
+    return L;
+}
+
+static int graph_loss_route(int flags) {
+    return (flags & ASG_FLAG_GRAPH_LOSS_STREAMING) ? 1 : ((flags & ASG_FLAG_GRAPH_LOSS_RESIDENT) ? 2 : 0);
+}
+
+size_t asg_graph_full_work_bytes(const asg_problem *p, const asg_token_graph_loss *gl, int store) {
+    if (check_graph_loss(p, gl) != ASG_OK) return 0;
+    return graph_loss_work_bytes(p->dtype == ASG_DTYPE_F64 ? 8 : 4, (int) p->T, (int) p->B, (int) gl->graph->Q, store != 0);
+}
+
+size_t asg_graph_full_scratch_bytes(const asg_problem *p, const asg_token_graph_loss *gl) {
+    if (check_graph_loss(p, gl) != ASG_OK) return 0;
+    return graph_loss_scratch_bytes(p->dtype == ASG_DTYPE_F64 ? 8 : 4, (int) p->B, (int) gl->graph->Q, (int) gl->graph->E);
+}
+
+int asg_graph_full_forward(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_loss *gl, void *work, size_t work_bytes,
+                           void *scores, int flags, void *stream) {
+    (void) ctx;
+    int rc = check_graph_loss(p, gl);
+    if (rc) return rc;
+    const bool store = (flags & ASG_FLAG_GRAPH_LOSS_KEEP_ALPHA) != 0;
+    const size_t need = asg_graph_full_work_bytes(p, gl, store);
+    if (!scores || (need && !work)) return ASG_ERR_INVALID;
+    if (work_bytes < need) return ASG_ERR_WORKSPACE;
+    const Problem P = to_problem(p);
+    const GraphArgs G = to_graph_args(gl->graph);
+    const int route = graph_loss_route(flags);
+    return hip_status(ASG_DISPATCH(p, launch_graph_loss_forward<float>(P, G, route, store, work, scores, (hipStream_t) stream),
+                                   launch_graph_loss_forward<double>(P, G, route, store, work, scores, (hipStream_t) stream)));
+}
+
+int asg_graph_full_backward(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_loss *gl, const void *work,
+                            size_t work_bytes, const void *scores, const void *grad_scores, void *grad_inputs,
+                            void *grad_transition, void *scratch, size_t scratch_bytes, int flags, void *stream) {
+    (void) ctx;
+    int rc = check_graph_loss(p, gl);
+    if (rc) return rc;
+    const size_t wneed = asg_graph_full_work_bytes(p, gl, 1), sneed = asg_graph_full_scratch_bytes(p, gl);
+    if (!scores || !grad_scores || !grad_inputs || !grad_transition || (wneed && !work) || (sneed && !scratch))
+        return ASG_ERR_INVALID;
+    if (work_bytes < wneed || scratch_bytes < sneed) return ASG_ERR_WORKSPACE;
+    const Problem P = to_problem(p);
+    const GraphArgs G = to_graph_args(gl->graph);
+    const GraphLossArgs L = to_graph_loss_args(gl);
+    const int route = graph_loss_route(flags);
+    return hip_status(ASG_DISPATCH(p,
+        launch_graph_loss_backward<float>(P, G, L, route, work, scores, grad_scores, grad_inputs, grad_transition, scratch,
+                                          (hipStream_t) stream),
+        launch_graph_loss_backward<double>(P, G, L, route, work, scores, grad_scores, grad_inputs, grad_transition, scratch,
+                                           (hipStream_t) stream)));
+}
+
+int asg_graph_target_scores(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_loss *gl, void *out, void *stream) {
+    (void) ctx;
+    int rc = check_graph_loss(p, gl);
+    if (rc) return rc;
+    if (!out || !p->targets || p->S < 1) return ASG_ERR_INVALID;
+    if (p->S > (1 << 30)) return ASG_ERR_UNSUPPORTED;
+    const Problem P = to_problem(p);
+    const GraphLossArgs L = to_graph_loss_args(gl);
+    return hip_status(ASG_DISPATCH(p, launch_graph_target_scores<float>(P, L, out, (hipStream_t) stream),
+                                   launch_graph_target_scores<double>(P, L, out, (hipStream_t) stream)));
+}
+
 int asg_backward(asg_ctx *ctx, const asg_problem *p, const void *state, size_t state_bytes,
                  const void *grad_full, const void *grad_aligned, void *scratch, size_t scratch_bytes,
                  void *grad_transition, void *grad_inputs, int flags, void *stream) {

@@ -168,6 +168,29 @@ template <typename R>
 hipError_t launch_decode_graph(const Problem &P, const GraphArgs &G, int route, void *work, void *scores, long long *path,
                                long long *tokens, long long *tlen, long long *states, hipStream_t stream);
 
+// ---- Full score, gradients and target walk over the same composed lattice (asg_graph_loss.hip).  The loss-only arrays of
+// asg_token_graph_loss.  Work = alpha [T][Q][B] (stored) or [2][Q][B]; scratch = align256([2][Q][B] beta) + [Q+E][B]
+// per-stay / per-edge posterior sums.
+struct GraphLossArgs {
+    int S, start;
+    const int *tgt, *orow, *oedge, *lrow, *lq, *pedge, *next;   // [E], [Q+1], [E], [N+1], [Q], [E], [S*N]
+    const int64_t *pkey;                                          // [E] label pair i*N + j, ascending (pedge order)
+    const void *arcw, *finw;                                      // [S*N], [S] in the dtype of the problem
+};
+// route: 0 = by shape, 1 = streaming, 2 = resident wherever the vectors fit in LDS
+bool graph_loss_resident(int route, int elem, int Q, int64_t E);
+size_t graph_loss_work_bytes(int elem, int T, int B, int Q, bool store);
+size_t graph_loss_scratch_bytes(int elem, int B, int Q, int E);
+template <typename R>
+hipError_t launch_graph_loss_forward(const Problem &P, const GraphArgs &G, int route, bool store, void *work, void *scores,
+                                     hipStream_t stream);
+template <typename R>
+hipError_t launch_graph_loss_backward(const Problem &P, const GraphArgs &G, const GraphLossArgs &L, int route, const void *work,
+                                      const void *scores, const void *grad_scores, void *grad_inputs, void *grad_transition,
+                                      void *scratch, hipStream_t stream);
+template <typename R>
+hipError_t launch_graph_target_scores(const Problem &P, const GraphLossArgs &L, void *out, hipStream_t stream);
+
 // launches of the resident-slice forward kernel (256 < N <= 2048) of this process whose bounded waits ran out (asg_generic.hip)
 unsigned cluster_timeouts();
 

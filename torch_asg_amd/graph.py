@@ -155,6 +155,53 @@ class TokenGraph:
                 "row": row.astype(i32), "src": src.astype(i32), "src_label": label[src].astype(i32),
                 "edge_w": arcw[s_a[arc_of], i_a[arc_of]].astype(dt), "Q": Q, "E": E}
 
+    def compile_loss(self, device, dtype, lm_weight=1.0, token_score=0.0):
+        """What `compile` returns plus the arrays the loss kernels read (include/asg_hip.h::asg_token_graph_loss), cached apart
+        from `compile`'s entry (which stays as it is, so the decoder pays nothing for them)."""
+        base = self.compile(device, dtype, lm_weight, token_score)
+        device = base["label"].device
+        key = ("loss", device, dtype, float(lm_weight), float(token_score))
+        hit = self._compiled.get(key)
+        if hit is not None:
+            return hit
+        host = self.compile_loss_host(np.float32 if dtype == torch.float32 else np.float64, lm_weight, token_score)
+        dev = dict(base)
+        dev.update({n: torch.from_numpy(a).to(device) for n, a in host.items()})
+        dev["S"], dev["start"] = self.S, self.start
+        self._compiled[key] = dev
+        return dev
+
+    def compile_loss_host(self, dt, lm_weight=1.0, token_score=0.0):
+        """The loss-only arrays as numpy arrays: tgt [E] (target of each incoming edge), orow [Q+1] and oedge [E] (the outgoing
+        edges of each q as incoming-edge indices, ascending by (src, tgt)), lrow [N+1] and lq [Q] (the product states of each
+        label, ascending), pkey int64 and pedge [E] (the edges sorted by label pair label[tgt] * N + src_label, stably), and the
+        automaton for the target walk: next [S,N] (-1 where no arc), arcw [S,N] (-inf where no arc) and finw [S] in dtype dt."""
+        h = self.compile_host(dt, lm_weight, token_score)
+        dt = np.dtype(dt).type
+        Q, N = h["Q"], self.N
+        row = h["row"].astype(np.int64)
+        src = h["src"].astype(np.int64)
+        tgt = np.repeat(np.arange(Q, dtype=np.int64), np.diff(row))
+        oedge = np.lexsort((tgt, src))
+        orow = np.zeros(Q + 1, np.int64)
+        np.cumsum(np.bincount(src, minlength=Q), out=orow[1:])
+        label = h["label"].astype(np.int64)
+        lq = np.argsort(label, kind="stable")
+        lrow = np.zeros(N + 1, np.int64)
+        np.cumsum(np.bincount(label, minlength=N), out=lrow[1:])
+        pk = label[tgt] * N + h["src_label"].astype(np.int64)
+        pedge = np.argsort(pk, kind="stable")
+        lw, ts = dt(lm_weight), dt(token_score)
+        present = (self.next >= 0) & (self.weight != -np.inf)
+        with np.errstate(invalid="ignore", over="ignore"):
+            arcw = (lw * self.weight.astype(dt)).astype(dt) + ts        # as compile_host folds them
+            finw = np.where(self.final == -np.inf, dt(-np.inf), lw * self.final.astype(dt)).astype(dt)
+        i32 = np.int32
+        return {"tgt": tgt.astype(i32), "orow": orow.astype(i32), "oedge": oedge.astype(i32), "lrow": lrow.astype(i32),
+                "lq": lq.astype(i32), "pkey": pk[pedge].astype(np.int64), "pedge": pedge.astype(i32),
+                "next": np.where(present, self.next, -1).astype(i32), "arcw": np.where(present, arcw, dt(-np.inf)).astype(dt),
+                "finw": finw}
+
 
 def abi_graph(compiled):
     """The asg_token_graph view of a compiled graph (pointers into its device tensors)."""
@@ -165,3 +212,15 @@ def abi_graph(compiled):
         t = compiled[name]
         setattr(g, name, ctypes.c_void_p(t.data_ptr() if t.numel() else None))
     return g
+
+
+def abi_graph_loss(compiled):
+    """The asg_token_graph_loss view of a `compile_loss` result (it points at an asg_token_graph, which it keeps alive)."""
+    g = abi_graph(compiled)
+    gl = _lib.AsgTokenGraphLoss()
+    gl.graph = ctypes.pointer(g)
+    gl.S, gl.start = compiled["S"], compiled["start"]
+    for name in ("tgt", "orow", "oedge", "lrow", "lq", "pkey", "pedge", "next", "arcw", "finw"):
+        t = compiled[name]
+        setattr(gl, name, ctypes.c_void_p(t.data_ptr() if t.numel() else None))
+    return gl
