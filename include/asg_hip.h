@@ -216,6 +216,50 @@ int asg_viterbi_decode_graph(asg_ctx *ctx, const asg_problem *p, const asg_token
                              void *scores, int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states,
                              int flags, void *stream);
 
+/* ---- BEAM-PRUNED Viterbi decoding over the same composed lattice: asg_viterbi_decode_graph with at most beam_size product
+ * states kept per frame.  Work per frame is proportional to the kept states and their outgoing edges, never to Q or E, and the
+ * back-pointers are T*B*K instead of T*B*Q.  No counterpart in the reference.  The search is specified, not approximate.
+ * Product states, start_w, final_w, edge weights and the clamping of input_lengths are those of asg_viterbi_decode_graph; all
+ * arithmetic is in the dtype of the problem (beam_threshold rounded to it): adds, one subtraction and comparisons.  For utterance
+ * b with len = clamp(input_lengths[b], 0, T), an active set A_t of product states with values v_t:
+ *   t = 0:  c[q] = start_w[q] + I[0][i(q)] for every q.
+ *   t >= 1: candidates come only from sources in A_{t-1}: the stay v_{t-1}[q] + tr[i][i] when q is active (its source is q), and
+ *           (v_{t-1}[q'] + tr[i][j]) + edge_w for every edge q' -> q with q' active; best[q] = the largest candidate, the smallest
+ *           source index on a tie; c[q] = best[q] + I[t][i].  A q without a candidate, or with c[q] = -inf, is no candidate state.
+ *   prune (every frame, t = 0 included): m = max_q c[q], lo = fl(m - beam_threshold) (-inf for +inf).  With the candidate states
+ *           ordered by (c descending, q ascending), A_t = the first beam_size of them that also have c[q] >= lo; v_t = c there.
+ *           No candidate state: A_t is empty and stays empty.
+ *   end:    scores[b] = max over q in A_{len-1} of (v[q] + final_w[q]), the smallest q on a tie; path, states, tokens and
+ *           token_lengths follow the back-pointers as in asg_viterbi_decode_graph.  len == 0, an empty last set, or no active
+ *           state with a finite final_w: score -inf, integer outputs -1, no tokens.
+ * NaN anywhere and +inf emissions are unspecified.  -0 and +0 compare equal in every rule above.  With beam_size >= Q and
+ * beam_threshold = +inf every output equals asg_viterbi_decode_graph's; for any beam the score is <= the exact one and, when
+ * finite, is exactly the score of the returned path.  Results are bit-identical run to run (integer atomics only).
+ * The graph from the SOURCE side (torch_asg_amd.TokenGraph.compile_beam): per product state q' a CSR row of its outgoing edges,
+ * ascending by target, each with {target q, label of q} as one pair of int32 and the folded arc weight beside it (the same edges
+ * as asg_token_graph's, regrouped); start_q lists the q with start_w[q] > -inf, ascending, so that frame 0 does not scan Q;
+ * max_out is the largest out-degree (it sizes the list of targets a frame can touch).
+ * K = min(beam_size, max(Q, 1)).  `work` (asg_beam_decode_graph_work_bytes), per utterance and every part rounded up to 256 bytes:
+ *   2 * T*K*4 (product state and source slot of every kept state) + Q*8 + Q*e (one best-candidate slot per product state, emptied
+ *   by the kernel as it goes) + cap*(e + 4) (the targets touched in a frame), cap = max(min(Q, K*(max_out+1)), num_start), e = 4 / 8.
+ * One launch, one workgroup per utterance; every output and all scratch is written by the kernel (no memset), so a captured call
+ * replays with new inputs.  Limits (ASG_ERR_UNSUPPORTED beyond): those of asg_viterbi_decode_graph, and K <= 8192 (a beam_size
+ * above Q is treated as Q).  beam_size < 1, a negative or NaN beam_threshold: ASG_ERR_INVALID.  `flags` is reserved (pass 0). */
+typedef struct asg_token_graph_beam {
+    const asg_token_graph *graph;  /* the product graph (label, state, start_w, final_w are read; Q, E, N, dtype)  */
+    int64_t num_start;             /* entries of start_q                                                         */
+    int32_t max_out;               /* largest out-degree of a product state, the stay excluded                   */
+    int32_t reserved;
+    const int32_t *orow;           /* [Q+1] CSR offsets of the outgoing edges of q'                              */
+    const int32_t *oarc;           /* [E][2] {target q, label of q} of each outgoing edge, targets ascending within a row */
+    const void *ow;                /* [E] folded arc weight of each outgoing edge                                */
+    const int32_t *start_q;        /* [num_start] product states with start_w > -inf, ascending                  */
+} asg_token_graph_beam;
+size_t asg_beam_decode_graph_work_bytes(const asg_problem *p, const asg_token_graph_beam *gb, int beam_size);
+int asg_beam_decode_graph(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, int beam_size, double beam_threshold,
+                          void *work, size_t work_bytes, void *scores, int64_t *path, int64_t *tokens, int64_t *token_lengths,
+                          int64_t *states, int flags, void *stream);
+
 /* ---- Full score of the ASG lattice COMPOSED with a token automaton (the log-semiring counterpart of the decoder above), its
  * gradients, and the automaton's score of each target: the pieces of an ASG loss whose normaliser includes a token-level
  * prior.  No counterpart in the reference.  For utterance b with len = clamp(input_lengths[b], 0, T), in the dtype of the problem:

@@ -1,6 +1,6 @@
 """torch_asg_amd -- MI355X (gfx950) native ASG forward-backward hot path behind the ASGLoss surface
 of zh217/torch-asg (`from torch_asg import ASGLoss` -> `from torch_asg_amd import ASGLoss`)."""
-from .asg import ASGLoss, ASGLossFunction, FAC, FCC, ASGGPUFast, ASGGPUFastForwardOnly, viterbi_align, viterbi_decode, viterbi_decode_graph  # noqa: F401
+from .asg import ASGLoss, ASGLossFunction, FAC, FCC, ASGGPUFast, ASGGPUFastForwardOnly, viterbi_align, viterbi_decode, viterbi_decode_graph, beam_decode_graph  # noqa: F401
 from .asg import GraphFullScore, graph_full_score, graph_asg_loss  # noqa: F401
 from .graph import TokenGraph  # noqa: F401
 from .distributed import shard_batch, sharded_asg_loss, allreduce_transition_grad  # noqa: F401
@@ -32,5 +32,5 @@ def release():
 
 
 __all__ = ["ASGLoss", "ASGLossFunction", "FAC", "FCC", "ASGGPUFast", "ASGGPUFastForwardOnly", "viterbi_align", "viterbi_decode",
-           "viterbi_decode_graph", "TokenGraph", "GraphFullScore", "graph_full_score", "graph_asg_loss",
+           "viterbi_decode_graph", "beam_decode_graph", "TokenGraph", "GraphFullScore", "graph_full_score", "graph_asg_loss",
            "shard_batch", "sharded_asg_loss", "allreduce_transition_grad", "reserve", "release", "check_faults", "graphed", "GraphedStep"]

@@ -23,7 +23,7 @@ SYMBOLS = ["asg_hip_version", "asg_hip_strerror", "asg_ctx_create", "asg_ctx_des
            "asg_loss_fused_backward", "asg_cluster_timeouts", "asg_reload_env", "asg_loss_forward_only", "asg_loss_forward_only_scores_bytes",
            "asg_viterbi_decode_work_bytes", "asg_viterbi_decode", "asg_viterbi_decode_graph_work_bytes",
            "asg_viterbi_decode_graph", "asg_graph_full_work_bytes", "asg_graph_full_scratch_bytes", "asg_graph_full_forward",
-           "asg_graph_full_backward", "asg_graph_target_scores"]
+           "asg_graph_full_backward", "asg_graph_target_scores", "asg_beam_decode_graph_work_bytes", "asg_beam_decode_graph"]
 ABI_VERSION = 230        # include/asg_hip.h: ASG_HIP_VERSION this package was written against
 
 
@@ -47,6 +47,11 @@ class AsgTokenGraphLoss(ctypes.Structure):
     _fields_ = [("graph", ctypes.POINTER(AsgTokenGraph)), ("S", ctypes.c_int64), ("start", ctypes.c_int32),
                 ("reserved", ctypes.c_int32)] + [(n, ctypes.c_void_p) for n in ("tgt", "orow", "oedge", "lrow", "lq", "pkey", "pedge",
                                                                                "next", "arcw", "finw")]
+
+
+class AsgTokenGraphBeam(ctypes.Structure):
+    _fields_ = [("graph", ctypes.POINTER(AsgTokenGraph)), ("num_start", ctypes.c_int64), ("max_out", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)] + [(n, ctypes.c_void_p) for n in ("orow", "oarc", "ow", "start_q")]
 
 
 _LIB = None
@@ -103,6 +108,10 @@ def lib():
     L.asg_viterbi_decode_graph_work_bytes.restype = sz
     L.asg_viterbi_decode_graph_work_bytes.argtypes = [pp, gp]
     L.asg_viterbi_decode_graph.argtypes = [vp, pp, gp, vp, sz, vp, vp, vp, vp, vp, ci, vp]
+    bp = ctypes.POINTER(AsgTokenGraphBeam)
+    L.asg_beam_decode_graph_work_bytes.restype = sz
+    L.asg_beam_decode_graph_work_bytes.argtypes = [pp, bp, ci]
+    L.asg_beam_decode_graph.argtypes = [vp, pp, bp, ci, ctypes.c_double, vp, sz, vp, vp, vp, vp, vp, ci, vp]
     lp = ctypes.POINTER(AsgTokenGraphLoss)
     L.asg_graph_full_work_bytes.restype = sz
     L.asg_graph_full_work_bytes.argtypes = [pp, lp, ci]

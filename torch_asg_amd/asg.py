@@ -356,6 +356,44 @@ class HipBackend:
         token_lengths[B], states[B,T]); see include/asg_hip.h::asg_viterbi_decode_graph.  Utterances are decoded in
         consecutive groups whose workspace fits `max_work_bytes` (at least one utterance per group)."""
         from . import graph as _graph
+        L = _lib.lib()
+
+        def view(dev, dtype):
+            return _graph.abi_graph(graph.compile(dev, dtype, lm_weight, token_score))
+
+        def work_bytes(p, g):
+            return L.asg_viterbi_decode_graph_work_bytes(ctypes.byref(p), ctypes.byref(g))
+
+        def call(p, g, work, scores, path, tokens, token_lengths, states, stream):
+            return L.asg_viterbi_decode_graph(None, ctypes.byref(p), ctypes.byref(g), work.data_ptr(), work.numel(), scores, path,
+                                              tokens, token_lengths, states, flags, stream)
+        return self._decode_graph(inputs, transition, graph, input_lengths, max_work_bytes, view, work_bytes, call,
+                                  "asg_viterbi_decode_graph")
+
+    def beam_decode_graph(self, inputs, transition, graph, input_lengths, beam_size, beam_threshold=float("inf"), lm_weight=1.0,
+                          token_score=0.0, max_work_bytes=1 << 30, flags=0):
+        """Beam-pruned best path over the lattice composed with a token automaton -> the five tensors of
+        `viterbi_decode_graph`; see include/asg_hip.h::asg_beam_decode_graph.  Grouped under `max_work_bytes` likewise."""
+        from . import graph as _graph
+        beam_size, beam_threshold = min(int(beam_size), (1 << 31) - 1), float(beam_threshold)
+        L = _lib.lib()
+
+        def view(dev, dtype):
+            return _graph.abi_graph_beam(graph.compile_beam(dev, dtype, lm_weight, token_score))
+
+        def work_bytes(p, g):
+            return L.asg_beam_decode_graph_work_bytes(ctypes.byref(p), ctypes.byref(g), beam_size)
+
+        def call(p, g, work, scores, path, tokens, token_lengths, states, stream):
+            return L.asg_beam_decode_graph(None, ctypes.byref(p), ctypes.byref(g), beam_size, beam_threshold, work.data_ptr(),
+                                           work.numel(), scores, path, tokens, token_lengths, states, flags, stream)
+        return self._decode_graph(inputs, transition, graph, input_lengths, max_work_bytes, view, work_bytes, call,
+                                  "asg_beam_decode_graph")
+
+    def _decode_graph(self, inputs, transition, graph, input_lengths, max_work_bytes, view, work_bytes_of, call, what):
+        """What the two graph decoders share: the checks, the utterance groups under `max_work_bytes`, the outputs.  `view`
+        compiles the graph for (device, dtype) -> its C view."""
+        from . import graph as _graph
         self._check(inputs, transition, None, input_lengths, None)
         if inputs.dtype not in (torch.float32, torch.float64):
             raise RuntimeError("torch_asg_amd: expected scalar type Float or Double but found %s" % inputs.dtype)
@@ -366,18 +404,16 @@ class HipBackend:
             raise RuntimeError("torch_asg_amd: the graph is over %d tokens but the emissions have N = %d" % (graph.N, N))
         if input_lengths is not None and tuple(input_lengths.shape) != (B,):
             raise RuntimeError("torch_asg_amd: input_lengths must have shape [%d]" % B)
-        L = _lib.lib()
         dev = inputs.device
         with self._guard(dev):
-            compiled = graph.compile(dev, inputs.dtype, lm_weight, token_score)
-            g = _graph.abi_graph(compiled)
+            g = view(dev, inputs.dtype)
             p, keep = self._problem(inputs, transition, None, input_lengths, None)
             if input_lengths is not None:
                 input_lengths = keep[-1]                       # (on the device, contiguous)
 
             def work_bytes(nb):
                 p.B = nb
-                return int(L.asg_viterbi_decode_graph_work_bytes(ctypes.byref(p), ctypes.byref(g)))
+                return int(work_bytes_of(p, g))
             per = max(work_bytes(1), 1)
             gsz = max(1, min(B, int(max_work_bytes) // per))
             while gsz > 1 and work_bytes(gsz) > max_work_bytes:
@@ -396,10 +432,8 @@ class HipBackend:
                 p.B = b1 - b0
                 if input_lengths is not None:
                     p.input_lengths = input_lengths[b0:b1].data_ptr()
-                _lib.check(L.asg_viterbi_decode_graph(None, ctypes.byref(p), ctypes.byref(g), work.data_ptr(), work.numel(),
-                                                      scores[b0:].data_ptr(), out[0, b0].data_ptr(), out[1, b0].data_ptr(),
-                                                      token_lengths[b0:].data_ptr(), out[2, b0].data_ptr(), flags, stream),
-                           "asg_viterbi_decode_graph")
+                _lib.check(call(p, g, work, scores[b0:].data_ptr(), out[0, b0].data_ptr(), out[1, b0].data_ptr(),
+                                token_lengths[b0:].data_ptr(), out[2, b0].data_ptr(), stream), what)
         return scores, out[0], out[1], token_lengths, out[2]
 
     def _graph_loss_args(self, inputs, transition, graph, input_lengths, lm_weight, token_score):
@@ -798,6 +832,38 @@ def viterbi_decode_graph(inputs, transition, graph, input_lengths=None, lm_weigh
                                              token_score, max_work_bytes)
 
 
+def beam_decode_graph(inputs, transition, graph, input_lengths=None, beam_size=256, beam_threshold=float("inf"), lm_weight=1.0,
+                      token_score=0.0, max_work_bytes=1 << 30):
+    """Beam-pruned Viterbi decoding over the ASG lattice composed with a token automaton `graph`: `viterbi_decode_graph` that
+    keeps at most `beam_size` product states per frame, so the work per frame follows the beam and its outgoing arcs and not
+    the size of the automaton -- the decoder for large automata (`TokenGraph.from_lexicon`, high-order n-grams).  No gradient.
+
+    The search is specified exactly (include/asg_hip.h::asg_beam_decode_graph).  The candidates of a frame come only from the
+    states kept at the frame before; each target keeps its largest candidate (the smallest source index on a tie); with m the
+    largest of the frame's values, the states kept are the first `beam_size` in (value descending, product-state index
+    ascending) order whose value is >= m - beam_threshold.  The score is the largest value + final weight over the states kept at
+    the last frame.  Arithmetic, folding of lm_weight / token_score, inputs, strides, float16 / bfloat16 widening, outputs,
+    padding and errors are those of `viterbi_decode_graph`; with beam_size >= the number of product states and beam_threshold =
+    inf every output equals it bit for bit.  Otherwise the score is <= the exact one and, when finite, exactly the score of the
+    returned path; an utterance whose beam dies out, or ends in no accepting state, has score -inf, all -1 and no tokens.
+    Results are bit-identical run to run.  beam_size < 1 and a negative or NaN beam_threshold raise ValueError.
+
+    The graph is compiled for the device, dtype, lm_weight and token_score on first use and cached on it; later calls copy
+    nothing to the device and do not synchronise, so they can be captured.  The batch is decoded in consecutive groups of
+    utterances whose workspace (about T * beam_size * 8 bytes of back-pointers plus 12-16 bytes per product state and
+    utterance) fits `max_work_bytes`.
+    """
+    if int(beam_size) < 1:
+        raise ValueError("torch_asg_amd: beam_size must be >= 1, got %d" % int(beam_size))
+    if not float(beam_threshold) >= 0.0:
+        raise ValueError("torch_asg_amd: beam_threshold must be >= 0 (inf: none), got %r" % (beam_threshold,))
+    if inputs.dtype in (torch.float16, torch.bfloat16):
+        inputs = inputs.to(transition.dtype)
+    with torch.no_grad():
+        return native().beam_decode_graph(inputs.detach(), transition.detach(), graph, input_lengths, beam_size, beam_threshold,
+                                          lm_weight, token_score, max_work_bytes)
+
+
 class GraphFullScore(torch.autograd.Function):
     """Full score of the ASG lattice composed with a token automaton, [B] (asg_graph_full_forward / _backward).  alpha is
     stored only when a gradient w.r.t. inputs or transition is needed."""
@@ -1080,6 +1146,13 @@ class ASGLoss(nn.Module):
         """Viterbi decoding with a token automaton under this module's transition matrix: see
         `torch_asg_amd.viterbi_decode_graph`."""
         return viterbi_decode_graph(inputs, self.transition, graph, input_lengths, lm_weight, token_score, max_work_bytes)
+
+    def beam_decode_graph(self, inputs, graph, input_lengths=None, beam_size=256, beam_threshold=float("inf"), lm_weight=1.0,
+                          token_score=0.0, max_work_bytes=1 << 30):
+        """Beam-pruned decoding under this criterion's transitions composed with a token automaton; see
+        `torch_asg_amd.beam_decode_graph`."""
+        return beam_decode_graph(inputs, self.transition, graph, input_lengths, beam_size, beam_threshold, lm_weight, token_score,
+                                 max_work_bytes)
 
     def graph_loss(self, inputs, targets, graph, input_lengths=None, target_lengths=None, lm_weight=1.0, token_score=0.0,
                    max_work_bytes=1 << 30):

@@ -562,6 +562,53 @@ static GraphArgs to_graph_args(const asg_token_graph *g) {
     return G;
 }
 
+static int check_beam_graph(const asg_problem *p, const asg_token_graph_beam *gb, int beam_size) {
+    if (!gb) return ASG_ERR_INVALID;
+    int rc = check_decode_graph(p, gb->graph);
+    if (rc) return rc;
+    const asg_token_graph *g = gb->graph;
+    if (beam_size < 1 || gb->num_start < 0 || gb->num_start > g->Q || gb->max_out < 0) return ASG_ERR_INVALID;
+    if (g->Q > 0 && !gb->orow) return ASG_ERR_INVALID;
+    if (g->E > 0 && (!gb->oarc || !gb->ow)) return ASG_ERR_INVALID;
+    if (gb->num_start > 0 && !gb->start_q) return ASG_ERR_INVALID;
+    if (beam_graph_k((int) g->Q, beam_size) > kBeamMaxK) return ASG_ERR_UNSUPPORTED;
+    return ASG_OK;
+}
+
+static BeamGraphArgs to_beam_graph_args(const asg_token_graph_beam *gb) {
+    BeamGraphArgs BG{};
+    BG.num_start = (int) gb->num_start; BG.max_out = gb->max_out;
+    BG.orow = gb->orow; BG.oarc = gb->oarc; BG.ow = gb->ow; BG.start_q = gb->start_q;
+    return BG;
+}
+
+size_t asg_beam_decode_graph_work_bytes(const asg_problem *p, const asg_token_graph_beam *gb, int beam_size) {
+    if (check_beam_graph(p, gb, beam_size) != ASG_OK) return 0;
+    const int Q = (int) gb->graph->Q, K = beam_graph_k(Q, beam_size);
+    return beam_graph_work_bytes(p->dtype == ASG_DTYPE_F64 ? 8 : 4, (int) p->T, (int) p->B, Q, K,
+                                 beam_graph_cap(Q, K, gb->max_out, (int) gb->num_start));
+}
+
+int asg_beam_decode_graph(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, int beam_size, double beam_threshold,
+                          void *work, size_t work_bytes, void *scores, int64_t *path, int64_t *tokens, int64_t *token_lengths,
+                          int64_t *states, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    int rc = check_beam_graph(p, gb, beam_size);
+    if (rc) return rc;
+    if (!(beam_threshold >= 0.0)) return ASG_ERR_INVALID;                  // negative or NaN
+    if (!work || !scores || !path || !tokens || !token_lengths || !states) return ASG_ERR_INVALID;
+    if (work_bytes < asg_beam_decode_graph_work_bytes(p, gb, beam_size)) return ASG_ERR_WORKSPACE;
+    const Problem P = to_problem(p);
+    const GraphArgs G = to_graph_args(gb->graph);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    const int K = beam_graph_k(G.Q, beam_size);
+    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
+    return hip_status(ASG_DISPATCH(p, launch_beam_graph<float>(P, G, BG, K, beam_threshold, work, scores, pa, tk, tl, st,
+                                                               (hipStream_t) stream),
+                                   launch_beam_graph<double>(P, G, BG, K, beam_threshold, work, scores, pa, tk, tl, st,
+                                                             (hipStream_t) stream)));
+}
+
 static GraphLossArgs to_graph_loss_args(const asg_token_graph_loss *gl) {
     GraphLossArgs L{};
     L.S = (int) gl->S; L.start = gl->start;

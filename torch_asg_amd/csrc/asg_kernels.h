@@ -168,6 +168,26 @@ template <typename R>
 hipError_t launch_decode_graph(const Problem &P, const GraphArgs &G, int route, void *work, void *scores, long long *path,
                                long long *tokens, long long *tlen, long long *states, hipStream_t stream);
 
+// ---- Beam-pruned Viterbi decoding over the same composed lattice (asg_beam_graph.hip).  The source-side arrays of
+// asg_token_graph_beam.  K = beam_graph_k(Q, beam_size) slots; the touched list holds beam_graph_cap(..) targets.  Work, per
+// utterance and each part 256-byte aligned: int32 [T][K] product states, int32 [T][K] source slots, u64 arg [Q], key val [Q],
+// key [cap], int32 touched [cap] (key = 4 or 8 bytes).
+struct BeamGraphArgs {
+    int num_start, max_out;
+    const int *orow;             // [Q+1]
+    const void *oarc;            // [E] int32 pairs {target, label of the target}
+    const void *ow;              // [E] folded arc weights in the dtype of the problem
+    const int *start_q;          // [num_start]
+};
+constexpr int kBeamMaxK = 8192;  // the active set (value, q) stays in LDS
+int beam_graph_k(int Q, int beam_size);
+int beam_graph_cap(int Q, int K, int max_out, int num_start);
+size_t beam_graph_work_bytes(int elem, int T, int B, int Q, int K, int cap);
+template <typename R>
+hipError_t launch_beam_graph(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, int K, double theta, void *work,
+                             void *scores, long long *path, long long *tokens, long long *tlen, long long *states,
+                             hipStream_t stream);
+
 // ---- Full score, gradients and target walk over the same composed lattice (asg_graph_loss.hip).  The loss-only arrays of
 // asg_token_graph_loss.  Work = alpha [T][Q][B] (stored) or [2][Q][B]; scratch = align256([2][Q][B] beta) + [Q+E][B]
 // per-stay / per-edge posterior sums.

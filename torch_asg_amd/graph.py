@@ -1,5 +1,5 @@
 """Deterministic weighted automata over tokens, for Viterbi decoding of the ASG lattice composed with a token-level language
-model (`torch_asg_amd.viterbi_decode_graph`).
+model (`torch_asg_amd.viterbi_decode_graph`, exact, and `torch_asg_amd.beam_decode_graph`, beam-pruned).
 
 A `TokenGraph` is S states, a start state, next[S,N] (-1: no arc), weight[S,N] (log-score of emitting token i from state s;
 -inf: no arc) and final[S] (-inf: not accepting).  `compile` folds the LM weight and the token insertion score into the arcs
@@ -88,6 +88,54 @@ class TokenGraph:
         flat = lp.reshape(-1, N + 1)                            # row = context code over (N+1)^k
         weight = flat[code][:, :N]
         final = flat[code][:, N]
+        return cls(nxt, weight, final, 0)
+
+    @classmethod
+    def from_lexicon(cls, spellings, num_tokens, separator, word_scores=None):
+        """A lexicon as an automaton: a trie of the spellings whose word ends return to the root on `separator`.  `spellings`
+        is a list of non-empty token-id sequences without `separator`; `word_scores` one log-score per spelling (default 0;
+        the largest one counts when a spelling occurs twice).  State 0 is the root and the start; the other trie nodes are
+        numbered in order of first creation while the spellings are inserted in the given order; trie arcs weigh 0.  A node that
+        ends a word has an arc on `separator` to the root that weighs the word's score, and is final with the same score; the
+        root is final with 0 and has no `separator` arc; nothing else is final.  The lattice collapses repeated labels, so a
+        spelling with two equal consecutive tokens raises ValueError (spell those with a repetition label)."""
+        N, sep = int(num_tokens), int(separator)
+        if N < 1 or not 0 <= sep < N:
+            raise ValueError("TokenGraph.from_lexicon: separator must be in [0, %d)" % N)
+        if word_scores is None:
+            word_scores = [0.0] * len(spellings)
+        if len(word_scores) != len(spellings):
+            raise ValueError("TokenGraph.from_lexicon: %d scores for %d spellings" % (len(word_scores), len(spellings)))
+        children = [{}]                 # per node: token -> node
+        ends = {}                       # node -> score of the word that ends there
+        for w, sc in zip(spellings, word_scores):
+            toks = [int(x) for x in w]
+            if not toks:
+                raise ValueError("TokenGraph.from_lexicon: empty spelling")
+            if any(x == sep or not 0 <= x < N for x in toks):
+                raise ValueError("TokenGraph.from_lexicon: spelling %s has the separator or a token outside [0, %d)" % (toks, N))
+            if any(a == b for a, b in zip(toks, toks[1:])):
+                raise ValueError("TokenGraph.from_lexicon: spelling %s repeats a token; the lattice collapses repeats" % (toks,))
+            node = 0
+            for x in toks:
+                nxt = children[node].get(x)
+                if nxt is None:
+                    nxt = len(children)
+                    children[node][x] = nxt
+                    children.append({})
+                node = nxt
+            sc = float(sc)
+            ends[node] = max(ends[node], sc) if node in ends else sc
+        S = len(children)
+        nxt = np.full((S, N), -1, np.int64)
+        weight = np.full((S, N), -np.inf)
+        final = np.full(S, -np.inf)
+        for s, ch in enumerate(children):
+            for x, d in ch.items():
+                nxt[s, x], weight[s, x] = d, 0.0
+        for s, sc in ends.items():
+            nxt[s, sep], weight[s, sep], final[s] = 0, sc, sc
+        final[0] = 0.0
         return cls(nxt, weight, final, 0)
 
     def compile(self, device, dtype, lm_weight=1.0, token_score=0.0):
@@ -203,6 +251,43 @@ class TokenGraph:
                 "finw": finw}
 
 
+    def compile_beam(self, device, dtype, lm_weight=1.0, token_score=0.0):
+        """What `compile` returns plus the source-side arrays the beam decoder reads (include/asg_hip.h::asg_token_graph_beam),
+        cached apart from `compile`'s entry (which stays as it is)."""
+        base = self.compile(device, dtype, lm_weight, token_score)
+        device = base["label"].device
+        key = ("beam", device, dtype, float(lm_weight), float(token_score))
+        hit = self._compiled.get(key)
+        if hit is not None:
+            return hit
+        host = self.compile_beam_host(np.float32 if dtype == torch.float32 else np.float64, lm_weight, token_score)
+        dev = dict(base)
+        dev.update({n: torch.from_numpy(a).to(device) for n, a in host.items() if isinstance(a, np.ndarray)})
+        dev["num_start"], dev["max_out"] = host["num_start"], host["max_out"]
+        self._compiled[key] = dev
+        return dev
+
+    def compile_beam_host(self, dt, lm_weight=1.0, token_score=0.0):
+        """The beam-only arrays as numpy arrays: orow [Q+1] (CSR offsets of the outgoing edges of each q), oarc [E,2] (target and
+        the target's label of each outgoing edge, ascending by (source, target)), ow [E] (its folded weight, dtype dt), start_q
+        (the q with start_w > -inf, ascending), and the integers num_start and max_out (the largest out-degree)."""
+        h = self.compile_host(dt, lm_weight, token_score)
+        Q = h["Q"]
+        row = h["row"].astype(np.int64)
+        src = h["src"].astype(np.int64)
+        tgt = np.repeat(np.arange(Q, dtype=np.int64), np.diff(row))
+        order = np.lexsort((tgt, src))
+        deg = np.bincount(src, minlength=Q)
+        orow = np.zeros(Q + 1, np.int64)
+        np.cumsum(deg, out=orow[1:])
+        otgt = tgt[order]
+        oarc = np.stack([otgt, h["label"].astype(np.int64)[otgt]], axis=1) if Q else np.zeros((0, 2), np.int64)
+        start_q = np.nonzero(h["start_w"] > -np.inf)[0]
+        i32 = np.int32
+        return {"orow": orow.astype(i32), "oarc": np.ascontiguousarray(oarc.astype(i32)), "ow": h["edge_w"][order],
+                "start_q": start_q.astype(i32), "num_start": int(start_q.size), "max_out": int(deg.max(initial=0))}
+
+
 def abi_graph(compiled):
     """The asg_token_graph view of a compiled graph (pointers into its device tensors)."""
     g = _lib.AsgTokenGraph()
@@ -224,3 +309,15 @@ def abi_graph_loss(compiled):
         t = compiled[name]
         setattr(gl, name, ctypes.c_void_p(t.data_ptr() if t.numel() else None))
     return gl
+
+
+def abi_graph_beam(compiled):
+    """The asg_token_graph_beam view of a `compile_beam` result (it points at an asg_token_graph, which it keeps alive)."""
+    g = abi_graph(compiled)
+    gb = _lib.AsgTokenGraphBeam()
+    gb.graph = ctypes.pointer(g)
+    gb.num_start, gb.max_out = compiled["num_start"], compiled["max_out"]
+    for name in ("orow", "oarc", "ow", "start_q"):
+        t = compiled[name]
+        setattr(gb, name, ctypes.c_void_p(t.data_ptr() if t.numel() else None))
+    return gb
