@@ -305,6 +305,64 @@ int asg_graph_full_backward(asg_ctx *ctx, const asg_problem *p, const asg_token_
                             void *grad_transition, void *scratch, size_t scratch_bytes, int flags, void *stream);
 int asg_graph_target_scores(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_loss *gl, void *out, void *stream);
 
+/* ---- BEAM-PRUNED full score of the same composed lattice, and its gradients: asg_graph_full_forward / _backward over the
+ * lattice that asg_beam_decode_graph's search keeps -- a normaliser Z_K whose work per frame follows the beam and not Q or E, so a
+ * criterion can be trained with the automata (4-grams, lexicon tries) the beam decoder was built for.  No counterpart in the
+ * reference.  Per utterance b, len = clamp(input_lengths[b], 0, T); product graph, folding, start_w, final_w, edge_w as in
+ * asg_viterbi_decode_graph:
+ *   1. Kept sets.  A_t, t = 0 .. len-1, are exactly the active sets of asg_beam_decode_graph for the same emissions, transition,
+ *      graph, beam_size, beam_threshold, computed in the dtype of the problem (the same device code runs).  They are a discrete
+ *      function of the inputs and constants to the gradient.
+ *   2. Forced target states (only when p->targets is given).  y = targets[b][:clamp(target_lengths[b], 0, S)] with consecutive
+ *      equal labels merged, n = |y|, s_0 = start, s_k = next[s_{k-1}][y_k], q_k = the product state (y_k, s_k), k = 1 .. n.
+ *      F_t = { q_k : k-1 <= t and n-k <= len-1-t }.  Every F_t is empty when the target has no alignment (target length 0 or
+ *      > len), holds a label outside [0, N), or the automaton rejects it (a missing arc, or final_w[q_n] = -inf).  The forced
+ *      states do NOT feed back into the search of step 1.
+ *   3. Lattice.  U_t = A_t united with F_t, ascending by q, no duplicates.
+ *        alpha[0][q] = start_w[q] + I[0][i(q)]                                                          for q in U_0
+ *        alpha[t][q] = lse(stay: alpha[t-1][q] + tr[i][i] if q in U_{t-1};  every edge q' -> q with q' in U_{t-1}:
+ *                          (alpha[t-1][q'] + tr[i][j]) + edge_w) + I[t][i]                               for q in U_t
+ *        scores[b] = Z_K = lse over q in U_{len-1} of (alpha[len-1][q] + final_w[q])
+ *      Every lse is max-then-sum over the stay, then the edges ascending by source (asg_graph_full_forward's order restricted to
+ *      the kept sources; the lanes that share a target meet in a fixed tree); all candidates -inf gives -inf, never NaN.
+ *      len == 0 or an empty lattice: -inf.  beta, the label posteriors and the expected (i, j) counts are the mirror image
+ *      over the same U_t; grad_inputs [T,B,N] (contiguous, every element written, zero rows at t >= len) and grad_transition
+ *      [N,N] as asg_graph_full_backward.
+ *   Z_K <= asg_graph_full_forward's score (a subset of its paths); without targets Z_K >= asg_beam_decode_graph's score; with
+ *   beam_size >= Q and beam_threshold = +inf, U_t is every state with a finite alpha and everything equals asg_graph_full_*.
+ *   With targets, every alignment of the target runs through the F_t, so Z_K - (aligned score + automaton score) >= 0 for ANY beam.
+ * No float atomics: posteriors are summed as 64-bit fixed-point integers (62 fractional bits for a frame's label posteriors,
+ * 62 - ceil(log2(len)) for an utterance's (i, j) counts) and the utterances are added in ascending order: bit-identical run to
+ * run.  ASG_FLAG_BEAM_LOSS_ACCUMULATE (backward) continues that sum from what grad_transition holds, so a batch processed in
+ * consecutive groups gives the bits of one call.  Every output and all scratch that is read is written by kernels (no memset).
+ * K = min(beam_size, max(Q, 1)); nf = min(S, T) when p->targets is given, else 0; M = K + nf.  Every part rounded up to 256 bytes:
+ *   work:    asg_beam_graph_full_work_bytes(p, gl, beam_size, store) =
+ *            B * (asg_beam_decode_graph's bytes per utterance + 2*T*4 + 256 + nf*12 + T*M*4 + (store ? T : 2)*M*e)
+ *            + 2*B*8 + 3*B*T*8          (what the search itself returns)
+ *   scratch: asg_beam_graph_full_scratch_bytes(p, gl, beam_size) = B * (2*M*e + N*N*8)
+ * Neither depends on E; Q enters only through the search's own slot arrays (Q*(8+e) per utterance).
+ * The forward keeps alpha for the backward with ASG_FLAG_GRAPH_LOSS_KEEP_ALPHA; the backward takes the same problem (targets
+ * included: they size the layout), the same beam_size, that work buffer and the scores of that forward.
+ * Limits (ASG_ERR_UNSUPPORTED beyond): those of asg_beam_decode_graph (K <= 8192, ...), N <= 1024 (a frame's label posteriors
+ * are summed in LDS, and the (i, j) counts too while they fit beside the lattice), min(S, T) <= 2048 with targets, T <= 2^20.  beam_size < 1, a
+ * negative or NaN beam_threshold: ASG_ERR_INVALID.  float32 and float64. */
+#define ASG_FLAG_BEAM_LOSS_ACCUMULATE 512   /* asg_beam_graph_full_backward: grad_transition += (it must hold finite values) */
+typedef struct asg_token_graph_beam_loss {
+    const asg_token_graph_beam *beam;  /* the source-side graph of asg_beam_decode_graph (and through it the product graph) */
+    int64_t S;                         /* automaton states                                                               */
+    int32_t start;                     /* start state                                                                    */
+    int32_t reserved;
+    const int32_t *next;               /* [S,N] next state, -1 where no arc                                              */
+} asg_token_graph_beam_loss;
+size_t asg_beam_graph_full_work_bytes(const asg_problem *p, const asg_token_graph_beam_loss *gl, int beam_size, int store);
+size_t asg_beam_graph_full_scratch_bytes(const asg_problem *p, const asg_token_graph_beam_loss *gl, int beam_size);
+int asg_beam_graph_full_forward(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam_loss *gl, int beam_size,
+                                double beam_threshold, void *work, size_t work_bytes, void *scores, int flags, void *stream);
+int asg_beam_graph_full_backward(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam_loss *gl, int beam_size,
+                                 const void *work, size_t work_bytes, const void *scores, const void *grad_scores,
+                                 void *grad_inputs, void *grad_transition, void *scratch, size_t scratch_bytes, int flags,
+                                 void *stream);
+
 /* ---- whole-loss entry points (no counterpart in the reference's native layer: they fold the Python-side
  * `full - aligned` and reduction of asg.py:128,136-142 and their autograd into the kernels, so one ASGLoss
  * step is 2 + 2 kernel launches with no PyTorch glue kernels in between) ------------------------------------ */

@@ -13,6 +13,7 @@ ASG_DTYPE_F32, ASG_DTYPE_F64, ASG_DTYPE_BF16 = 0, 1, 2
 FLAG_STREAMS, FLAG_SINGLE_LAUNCH, FLAG_ALPHA_SCORES = 1, 2, 8
 FLAG_DECODE_GRAPH_STREAMING, FLAG_DECODE_GRAPH_RESIDENT = 16, 32
 FLAG_GRAPH_LOSS_KEEP_ALPHA, FLAG_GRAPH_LOSS_STREAMING, FLAG_GRAPH_LOSS_RESIDENT = 64, 128, 256
+FLAG_BEAM_LOSS_ACCUMULATE = 512
 
 # every symbol include/asg_hip.h declares
 SYMBOLS = ["asg_hip_version", "asg_hip_strerror", "asg_ctx_create", "asg_ctx_destroy", "asg_stream_capture_id", "asg_state_bytes",
@@ -23,7 +24,9 @@ SYMBOLS = ["asg_hip_version", "asg_hip_strerror", "asg_ctx_create", "asg_ctx_des
            "asg_loss_fused_backward", "asg_cluster_timeouts", "asg_reload_env", "asg_loss_forward_only", "asg_loss_forward_only_scores_bytes",
            "asg_viterbi_decode_work_bytes", "asg_viterbi_decode", "asg_viterbi_decode_graph_work_bytes",
            "asg_viterbi_decode_graph", "asg_graph_full_work_bytes", "asg_graph_full_scratch_bytes", "asg_graph_full_forward",
-           "asg_graph_full_backward", "asg_graph_target_scores", "asg_beam_decode_graph_work_bytes", "asg_beam_decode_graph"]
+           "asg_graph_full_backward", "asg_graph_target_scores", "asg_beam_decode_graph_work_bytes", "asg_beam_decode_graph",
+           "asg_beam_graph_full_work_bytes", "asg_beam_graph_full_scratch_bytes", "asg_beam_graph_full_forward",
+           "asg_beam_graph_full_backward"]
 ABI_VERSION = 230        # include/asg_hip.h: ASG_HIP_VERSION this package was written against
 
 
@@ -52,6 +55,11 @@ class AsgTokenGraphLoss(ctypes.Structure):
 class AsgTokenGraphBeam(ctypes.Structure):
     _fields_ = [("graph", ctypes.POINTER(AsgTokenGraph)), ("num_start", ctypes.c_int64), ("max_out", ctypes.c_int32),
                 ("reserved", ctypes.c_int32)] + [(n, ctypes.c_void_p) for n in ("orow", "oarc", "ow", "start_q")]
+
+
+class AsgTokenGraphBeamLoss(ctypes.Structure):
+    _fields_ = [("beam", ctypes.POINTER(AsgTokenGraphBeam)), ("S", ctypes.c_int64), ("start", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("next", ctypes.c_void_p)]
 
 
 _LIB = None
@@ -112,6 +120,13 @@ def lib():
     L.asg_beam_decode_graph_work_bytes.restype = sz
     L.asg_beam_decode_graph_work_bytes.argtypes = [pp, bp, ci]
     L.asg_beam_decode_graph.argtypes = [vp, pp, bp, ci, ctypes.c_double, vp, sz, vp, vp, vp, vp, vp, ci, vp]
+    blp = ctypes.POINTER(AsgTokenGraphBeamLoss)
+    L.asg_beam_graph_full_work_bytes.restype = sz
+    L.asg_beam_graph_full_work_bytes.argtypes = [pp, blp, ci, ci]
+    L.asg_beam_graph_full_scratch_bytes.restype = sz
+    L.asg_beam_graph_full_scratch_bytes.argtypes = [pp, blp, ci]
+    L.asg_beam_graph_full_forward.argtypes = [vp, pp, blp, ci, ctypes.c_double, vp, sz, vp, ci, vp]
+    L.asg_beam_graph_full_backward.argtypes = [vp, pp, blp, ci, vp, sz, vp, vp, vp, vp, vp, sz, ci, vp]
     lp = ctypes.POINTER(AsgTokenGraphLoss)
     L.asg_graph_full_work_bytes.restype = sz
     L.asg_graph_full_work_bytes.argtypes = [pp, lp, ci]

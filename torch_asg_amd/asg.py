@@ -524,6 +524,105 @@ class HipBackend:
                 gtr = gtr_g if gtr is None else gtr + gtr_g
         return gtr, gin
 
+    def _beam_loss_args(self, inputs, transition, graph, input_lengths, targets, target_lengths, lm_weight, token_score):
+        """Checks shared by the beam-pruned loss entry points -> the asg_token_graph_beam_loss view of the compiled graph."""
+        from . import graph as _graph
+        self._check(inputs, transition, targets, input_lengths, target_lengths)
+        if inputs.dtype not in (torch.float32, torch.float64):
+            raise RuntimeError("torch_asg_amd: expected scalar type Float or Double but found %s" % inputs.dtype)
+        if not isinstance(graph, _graph.TokenGraph):
+            raise TypeError("torch_asg_amd: graph must be a torch_asg_amd.TokenGraph")
+        T, B, N = inputs.shape
+        if graph.N != N:
+            raise RuntimeError("torch_asg_amd: the graph is over %d tokens but the emissions have N = %d" % (graph.N, N))
+        if input_lengths is not None and tuple(input_lengths.shape) != (B,):
+            raise RuntimeError("torch_asg_amd: input_lengths must have shape [%d]" % B)
+        return _graph.abi_graph_beam_loss(graph.compile_beam_loss(inputs.device, inputs.dtype, lm_weight, token_score))
+
+    @staticmethod
+    def _group_problem(p, b0, b1, inputs, targets, input_lengths, target_lengths):
+        """Point problem `p` at the utterances b0 .. b1 of the batch (lengths on the device, contiguous)."""
+        p.inputs = inputs[:, b0:b1].data_ptr()
+        p.B = b1 - b0
+        if targets is not None:
+            p.targets = targets[b0:b1].data_ptr()
+        if input_lengths is not None:
+            p.input_lengths = input_lengths[b0:b1].data_ptr()
+        if target_lengths is not None:
+            p.target_lengths = target_lengths[b0:b1].data_ptr()
+
+    def beam_graph_full_forward(self, inputs, transition, graph, input_lengths, beam_size, beam_threshold=float("inf"),
+                                lm_weight=1.0, token_score=0.0, targets=None, target_lengths=None, store=False,
+                                max_work_bytes=1 << 30):
+        """Beam-pruned full score of the lattice composed with a token automaton -> (scores[B], saved); see
+        include/asg_hip.h::asg_beam_graph_full_forward.  Utterances run in consecutive groups whose workspace fits
+        `max_work_bytes`.  With `store`, saved = [(b0, b1, work)] for beam_graph_full_backward; None otherwise."""
+        L = _lib.lib()
+        dev = inputs.device
+        B = inputs.shape[1]
+        beam_size, beam_threshold = min(int(beam_size), (1 << 31) - 1), float(beam_threshold)
+        with self._guard(dev):
+            gl = self._beam_loss_args(inputs, transition, graph, input_lengths, targets, target_lengths, lm_weight, token_score)
+            p, keep = self._problem(inputs, transition, targets, input_lengths, target_lengths)
+            targets, input_lengths, target_lengths = self.device_args(dev, targets, input_lengths, target_lengths)
+
+            def work_bytes(nb):
+                p.B = nb
+                return int(L.asg_beam_graph_full_work_bytes(ctypes.byref(p), ctypes.byref(gl), beam_size, int(store)))
+            per = work_bytes(1)
+            if per == 0:
+                p.B = B
+                _lib.check(L.asg_beam_graph_full_forward(None, ctypes.byref(p), ctypes.byref(gl), beam_size, beam_threshold, None,
+                                                         0, None, 0, None), "asg_beam_graph_full_forward")
+            gsz = max(1, min(B, int(max_work_bytes) // per))
+            while gsz > 1 and work_bytes(gsz) > max_work_bytes:
+                gsz -= 1
+            scores = torch.empty(B, dtype=inputs.dtype, device=dev)
+            fl = _lib.FLAG_GRAPH_LOSS_KEEP_ALPHA if store else 0
+            stream = self._stream(dev)
+            saved, work = [], None
+            for b0 in range(0, B, gsz):
+                b1 = min(B, b0 + gsz)
+                if store or work is None:
+                    work = self._buf(work_bytes(b1 - b0), dev)
+                self._group_problem(p, b0, b1, inputs, targets, input_lengths, target_lengths)
+                _lib.check(L.asg_beam_graph_full_forward(None, ctypes.byref(p), ctypes.byref(gl), beam_size, beam_threshold,
+                                                         work.data_ptr(), work.numel(), scores[b0:].data_ptr(), fl, stream),
+                           "asg_beam_graph_full_forward")
+                if store:
+                    saved.append((b0, b1, work))
+        return scores, (saved if store else None)
+
+    def beam_graph_full_backward(self, saved, scores, grad_scores, inputs, transition, graph, input_lengths, beam_size,
+                                 lm_weight=1.0, token_score=0.0, targets=None, target_lengths=None):
+        """(grad_transition[N,N], grad_inputs[T,B,N]) of sum_b grad_scores[b] * scores[b] from beam_graph_full_forward's saved
+        lattices.  The groups add into one grad_transition in batch order, so the result does not depend on the grouping."""
+        L = _lib.lib()
+        dev = inputs.device
+        T, B, N = inputs.shape
+        beam_size = min(int(beam_size), (1 << 31) - 1)
+        with self._guard(dev):
+            gl = self._beam_loss_args(inputs, transition, graph, input_lengths, targets, target_lengths, lm_weight, token_score)
+            p, keep = self._problem(inputs, transition, targets, input_lengths, target_lengths)
+            targets, input_lengths, target_lengths = self.device_args(dev, targets, input_lengths, target_lengths)
+            gs = grad_scores.to(inputs.dtype).contiguous()
+            gin = torch.empty(T, B, N, dtype=inputs.dtype, device=dev)
+            gtr = torch.empty(N, N, dtype=inputs.dtype, device=dev)
+            stream = self._stream(dev)
+            for n, (b0, b1, work) in enumerate(saved):
+                nb = b1 - b0
+                self._group_problem(p, b0, b1, inputs, targets, input_lengths, target_lengths)
+                scratch = self._buf(L.asg_beam_graph_full_scratch_bytes(ctypes.byref(p), ctypes.byref(gl), beam_size), dev)
+                gin_g = gin if nb == B else torch.empty(T, nb, N, dtype=inputs.dtype, device=dev)
+                _lib.check(L.asg_beam_graph_full_backward(None, ctypes.byref(p), ctypes.byref(gl), beam_size, work.data_ptr(),
+                                                          work.numel(), scores[b0:].data_ptr(), gs[b0:].data_ptr(),
+                                                          gin_g.data_ptr(), gtr.data_ptr(), scratch.data_ptr(), scratch.numel(),
+                                                          _lib.FLAG_BEAM_LOSS_ACCUMULATE if n else 0, stream),
+                           "asg_beam_graph_full_backward")
+                if nb != B:
+                    gin[:, b0:b1].copy_(gin_g)
+        return gtr, gin
+
     def graph_target_scores(self, inputs, transition, graph, targets, target_lengths, lm_weight=1.0, token_score=0.0):
         """[B]: the automaton's score of every target sequence (consecutive repeats merged), -inf where it rejects it; see
         include/asg_hip.h::asg_graph_target_scores."""
@@ -940,6 +1039,87 @@ def graph_asg_loss(inputs, targets, transition, graph, input_lengths=None, targe
     return _reduce(per, reduction)
 
 
+class BeamGraphFullScore(torch.autograd.Function):
+    """Beam-pruned full score of the ASG lattice composed with a token automaton, [B] (asg_beam_graph_full_forward /
+    _backward).  The kept sets are constants of the gradient; alpha is stored only when a gradient w.r.t. inputs or transition
+    is needed.  Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, inputs, transition, graph, input_lengths, beam_size, beam_threshold, lm_weight, token_score, targets,
+                target_lengths, max_work_bytes):
+        store = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
+        scores, saved = native().beam_graph_full_forward(inputs, transition, graph, input_lengths, beam_size, beam_threshold,
+                                                         lm_weight, token_score, targets, target_lengths, store, max_work_bytes)
+        ctx.save_for_backward(inputs, transition, input_lengths, targets, target_lengths, scores)
+        ctx.saved, ctx.graph, ctx.args = saved, graph, (beam_size, lm_weight, token_score)
+        return scores
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        inputs, transition, input_lengths, targets, target_lengths, scores = ctx.saved_tensors
+        K, lw, ts = ctx.args
+        gtr, gin = native().beam_graph_full_backward(ctx.saved, scores, grad, inputs, transition, ctx.graph, input_lengths, K, lw,
+                                                     ts, targets, target_lengths)
+        return (gin, gtr) + (None,) * 9
+
+
+def _check_beam(beam_size, beam_threshold):
+    if int(beam_size) < 1:
+        raise ValueError("torch_asg_amd: beam_size must be >= 1, got %d" % int(beam_size))
+    if not float(beam_threshold) >= 0.0:
+        raise ValueError("torch_asg_amd: beam_threshold must be >= 0 (inf: none), got %r" % (beam_threshold,))
+
+
+def beam_graph_full_score(inputs, transition, graph, input_lengths=None, beam_size=256, beam_threshold=float("inf"), lm_weight=1.0,
+                          token_score=0.0, targets=None, target_lengths=None, max_work_bytes=1 << 30):
+    """`graph_full_score` over the lattice that `beam_decode_graph`'s search keeps: the logsumexp over the label paths that
+    stay, at every frame, inside the beam's active set of that frame (the sets of `beam_decode_graph` for the same arguments,
+    bit for bit) -- and, when `targets` is given, inside those sets united with the product states every alignment of the
+    target passes through (include/asg_hip.h::asg_beam_graph_full_forward).  Work and memory follow beam_size, not the size of
+    the automaton.  Differentiable w.r.t. `inputs` and `transition` with the sets held constant; <= `graph_full_score`, equal to
+    it when beam_size >= the number of product states and beam_threshold = inf; without targets >= `beam_decode_graph`'s score.
+    Bit-identical run to run and for any `max_work_bytes`.  targets / target_lengths are taken as given (no defaults or
+    truncation here: `beam_graph_asg_loss` applies those)."""
+    _check_beam(beam_size, beam_threshold)
+    if inputs.dtype in (torch.float16, torch.bfloat16):
+        inputs = inputs.to(transition.dtype)
+    return BeamGraphFullScore.apply(inputs, transition, graph, input_lengths, beam_size, beam_threshold, lm_weight, token_score,
+                                    targets, target_lengths, max_work_bytes)
+
+
+def _beam_graph_loss_per_utterance(inputs, targets, transition, graph, input_lengths, target_lengths, beam_size, beam_threshold,
+                                   lm_weight, token_score, max_work_bytes):
+    """[B] losses Z_K - (FAC + A(collapse(target))) with the target forced into the lattice; conventions of
+    `_graph_loss_per_utterance`."""
+    full = BeamGraphFullScore.apply(inputs, transition, graph, input_lengths, beam_size, beam_threshold, lm_weight, token_score,
+                                    targets, target_lengths, max_work_bytes)
+    with torch.no_grad():
+        walk = native().graph_target_scores(inputs.detach(), transition.detach(), graph, targets, target_lengths, lm_weight,
+                                            token_score)
+    aligned = FAC.apply(transition, inputs, targets, input_lengths, target_lengths) + walk
+    fd, ad = full.detach(), aligned.detach()
+    ok_f, ok_a = torch.isfinite(fd), torch.isfinite(ad)
+    zero = torch.zeros_like(fd)
+    value = torch.where(ok_a, fd - ad, torch.full_like(fd, float("inf")))
+    return value + torch.where(ok_f, full - fd, zero) - torch.where(ok_a, aligned - ad, zero)
+
+
+def beam_graph_asg_loss(inputs, targets, transition, graph, input_lengths=None, target_lengths=None, beam_size=256,
+                        beam_threshold=float("inf"), lm_weight=1.0, token_score=0.0, reduction='none', max_work_bytes=1 << 30):
+    """`graph_asg_loss` with the beam-pruned normaliser: loss[b] = beam_graph_full_score[b] - (S_aligned[b] +
+    A(collapse(targets[b]))), the target forced into the beam's lattice, so every finite loss is >= 0 (up to rounding) for any
+    beam and equals `graph_asg_loss` once the beam holds every product state.  +inf exactly where `graph_asg_loss` is +inf; then
+    only the normaliser's posterior reaches the gradients.  Defaults and S > T truncation as `ASGLoss.forward`."""
+    _check_beam(beam_size, beam_threshold)
+    if inputs.dtype in (torch.float16, torch.bfloat16):
+        inputs = inputs.to(transition.dtype)
+    targets, input_lengths, target_lengths = ASGLoss._canonical(inputs, targets, input_lengths, target_lengths)
+    per = _beam_graph_loss_per_utterance(inputs, targets, transition, graph, input_lengths, target_lengths, beam_size,
+                                         beam_threshold, lm_weight, token_score, max_work_bytes)
+    return _reduce(per, reduction)
+
+
 class FAC(torch.autograd.Function):
     """Force-aligned lattice score S_aligned[b]; same signature as the reference's FAC (asg.py:7-34)."""
 
@@ -1164,6 +1344,20 @@ class ASGLoss(nn.Module):
         weights = self._utterance_weights(inputs, input_lengths, target_lengths)
         per = _graph_loss_per_utterance(inputs, targets, self.transition, graph, input_lengths, target_lengths, lm_weight,
                                         token_score, max_work_bytes, 0)
+        if weights is not None:
+            per = per * weights
+        return _reduce(per, self.reduction)
+
+    def beam_graph_loss(self, inputs, targets, graph, input_lengths=None, target_lengths=None, lm_weight=1.0, token_score=0.0,
+                        max_work_bytes=1 << 30, beam_size=256, beam_threshold=float("inf")):
+        """`torch_asg_amd.beam_graph_asg_loss` under this module's transition matrix, reduction and scale_mode."""
+        _check_beam(beam_size, beam_threshold)
+        if inputs.dtype in (torch.float16, torch.bfloat16):
+            inputs = inputs.to(self.transition.dtype)
+        targets, input_lengths, target_lengths = self._canonical(inputs, targets, input_lengths, target_lengths)
+        weights = self._utterance_weights(inputs, input_lengths, target_lengths)
+        per = _beam_graph_loss_per_utterance(inputs, targets, self.transition, graph, input_lengths, target_lengths, beam_size,
+                                             beam_threshold, lm_weight, token_score, max_work_bytes)
         if weights is not None:
             per = per * weights
         return _reduce(per, self.reduction)

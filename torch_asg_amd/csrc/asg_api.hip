@@ -609,6 +609,80 @@ int asg_beam_decode_graph(asg_ctx *ctx, const asg_problem *p, const asg_token_gr
                                                              (hipStream_t) stream)));
 }
 
+static int check_beam_loss(const asg_problem *p, const asg_token_graph_beam_loss *gl, int beam_size) {
+    if (!gl) return ASG_ERR_INVALID;
+    int rc = check_beam_graph(p, gl->beam, beam_size);
+    if (rc) return rc;
+    if (gl->S < 1 || gl->start < 0 || gl->start >= gl->S || !gl->next) return ASG_ERR_INVALID;
+    if (gl->S >= (int64_t) 1 << 31) return ASG_ERR_UNSUPPORTED;
+    if (p->targets && p->S < 1) return ASG_ERR_INVALID;
+    if (p->N > kBeamLossMaxN || p->T > (1 << 20)) return ASG_ERR_UNSUPPORTED;
+    const int64_t nf = p->targets ? (p->S < p->T ? p->S : p->T) : 0;
+    if (nf > kBeamLossMaxForced) return ASG_ERR_UNSUPPORTED;
+    const int K = beam_graph_k((int) gl->beam->graph->Q, beam_size);
+    if (!beam_loss_fits(p->dtype == ASG_DTYPE_F64 ? 8 : 4, K + (int) nf, (int) p->N)) return ASG_ERR_UNSUPPORTED;
+    return ASG_OK;
+}
+
+static int beam_loss_nf(const asg_problem *p) { return p->targets ? (int) (p->S < p->T ? p->S : p->T) : 0; }
+
+size_t asg_beam_graph_full_work_bytes(const asg_problem *p, const asg_token_graph_beam_loss *gl, int beam_size, int store) {
+    if (check_beam_loss(p, gl, beam_size) != ASG_OK) return 0;
+    const asg_token_graph_beam *gb = gl->beam;
+    const int Q = (int) gb->graph->Q, K = beam_graph_k(Q, beam_size);
+    return beam_loss_work_bytes(p->dtype == ASG_DTYPE_F64 ? 8 : 4, (int) p->T, (int) p->B, Q, K,
+                                beam_graph_cap(Q, K, gb->max_out, (int) gb->num_start), beam_loss_nf(p), store != 0);
+}
+
+size_t asg_beam_graph_full_scratch_bytes(const asg_problem *p, const asg_token_graph_beam_loss *gl, int beam_size) {
+    if (check_beam_loss(p, gl, beam_size) != ASG_OK) return 0;
+    const int K = beam_graph_k((int) gl->beam->graph->Q, beam_size);
+    return (size_t) p->B * beam_loss_scratch_per(p->dtype == ASG_DTYPE_F64 ? 8 : 4, K + beam_loss_nf(p), (int) p->N);
+}
+
+int asg_beam_graph_full_forward(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam_loss *gl, int beam_size,
+                                double beam_threshold, void *work, size_t work_bytes, void *scores, int flags, void *stream) {
+    (void) ctx;
+    int rc = check_beam_loss(p, gl, beam_size);
+    if (rc) return rc;
+    if (!(beam_threshold >= 0.0)) return ASG_ERR_INVALID;                  // negative or NaN
+    if (!work || !scores) return ASG_ERR_INVALID;
+    const bool store = (flags & ASG_FLAG_GRAPH_LOSS_KEEP_ALPHA) != 0;
+    if (work_bytes < asg_beam_graph_full_work_bytes(p, gl, beam_size, store)) return ASG_ERR_WORKSPACE;
+    const Problem P = to_problem(p);
+    const GraphArgs G = to_graph_args(gl->beam->graph);
+    const BeamGraphArgs BG = to_beam_graph_args(gl->beam);
+    BeamLossArgs L{};
+    L.S = (int) gl->S; L.start = gl->start; L.next = gl->next;
+    const int K = beam_graph_k(G.Q, beam_size);
+    return hip_status(ASG_DISPATCH(p,
+        launch_beam_loss_forward<float>(P, G, BG, L, K, beam_threshold, store, work, scores, (hipStream_t) stream),
+        launch_beam_loss_forward<double>(P, G, BG, L, K, beam_threshold, store, work, scores, (hipStream_t) stream)));
+}
+
+int asg_beam_graph_full_backward(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam_loss *gl, int beam_size,
+                                 const void *work, size_t work_bytes, const void *scores, const void *grad_scores,
+                                 void *grad_inputs, void *grad_transition, void *scratch, size_t scratch_bytes, int flags,
+                                 void *stream) {
+    (void) ctx;
+    int rc = check_beam_loss(p, gl, beam_size);
+    if (rc) return rc;
+    if (!work || !scores || !grad_scores || !grad_inputs || !grad_transition || !scratch) return ASG_ERR_INVALID;
+    if (work_bytes < asg_beam_graph_full_work_bytes(p, gl, beam_size, 1) ||
+        scratch_bytes < asg_beam_graph_full_scratch_bytes(p, gl, beam_size))
+        return ASG_ERR_WORKSPACE;
+    const Problem P = to_problem(p);
+    const GraphArgs G = to_graph_args(gl->beam->graph);
+    const BeamGraphArgs BG = to_beam_graph_args(gl->beam);
+    const int K = beam_graph_k(G.Q, beam_size);
+    const bool acc = (flags & ASG_FLAG_BEAM_LOSS_ACCUMULATE) != 0;
+    return hip_status(ASG_DISPATCH(p,
+        launch_beam_loss_backward<float>(P, G, BG, K, work, scores, grad_scores, grad_inputs, grad_transition, scratch, acc,
+                                         (hipStream_t) stream),
+        launch_beam_loss_backward<double>(P, G, BG, K, work, scores, grad_scores, grad_inputs, grad_transition, scratch, acc,
+                                          (hipStream_t) stream)));
+}
+
 static GraphLossArgs to_graph_loss_args(const asg_token_graph_loss *gl) {
     GraphLossArgs L{};
     L.S = (int) gl->S; L.start = gl->start;

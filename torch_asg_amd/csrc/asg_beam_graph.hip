@@ -159,8 +159,9 @@ __device__ __forceinline__ void find_digit(const int *hist, int need, int lane, 
 
 template <typename R, bool TRL>
 __global__ void __launch_bounds__(kBT) beam_graph_kernel(Problem P, GraphArgs g, BeamGraphArgs bg, int K, R theta, int cap,
-                                                         char *work, size_t per_utt, R *scores, long long *path,
-                                                         long long *tokens, long long *tlen, long long *states) {
+                                                         char *work, size_t per_utt, size_t cnt_off, R *scores,
+                                                         long long *path, long long *tokens, long long *tlen,
+                                                         long long *states) {
     using KT = Key<R>;
     using U = typename KT::U;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -187,6 +188,9 @@ __global__ void __launch_bounds__(kBT) beam_graph_kernel(Problem P, GraphArgs g,
     U *val = (U *) (wb + off);     off += ((size_t) Q * sizeof(U) + a256) & ~a256;
     U *ckey = (U *) (wb + off);    off += ((size_t) cap * sizeof(U) + a256) & ~a256;
     int *tl = (int *) (wb + off);
+    // cnt_off != 0 (asg_beam_loss.hip): |A_t| of every frame goes to int32 [T] at that offset of the utterance's workspace
+    int *cnt = cnt_off ? (int *) (wb + cnt_off) : nullptr;
+    if (cnt) for (int t = tid; t < T; t += kBT) cnt[t] = 0;
     auto TR = [&](int i, int j) -> R {
         if constexpr (TRL) return trs[i * N + j];
         else return tr[(int64_t) i * P.ts0 + (int64_t) j * P.ts1];
@@ -406,6 +410,7 @@ __global__ void __launch_bounds__(kBT) beam_graph_kernel(Problem P, GraphArgs g,
         }
         if (tid == 0) ctl.n = 0;
         __syncthreads();
+        if (cnt && tid == 0) cnt[t] = ctl.na < K ? ctl.na : K;
     }
 
     // ---- score: the largest v + final_w over the last active set, the smallest q on a tie
@@ -482,10 +487,10 @@ size_t beam_graph_work_bytes(int elem, int T, int B, int Q, int K, int cap) {
 template <typename R>
 hipError_t launch_beam_graph(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, int K, double theta, void *work,
                              void *scores, long long *path, long long *tokens, long long *tlen, long long *states,
-                             hipStream_t stream) {
+                             hipStream_t stream, size_t stride, size_t cnt_off) {
     const int N = P.N;
     const int cap = beam_graph_cap(G.Q, K, BG.max_out, BG.num_start);
-    const size_t per = beam_per_utt(sizeof(R), P.T, G.Q, K, cap);
+    const size_t per = stride ? stride : beam_per_utt(sizeof(R), P.T, G.Q, K, cap);
     const size_t beam = kFixedLds + (size_t) K * (sizeof(R) + 4) + 8;
     const bool trl = beam + (size_t) N * N * sizeof(R) <= kLdsMax;
     const size_t dyn = beam + (trl ? (size_t) N * N * sizeof(R) : 0);
@@ -495,15 +500,16 @@ hipError_t launch_beam_graph(const Problem &P, const GraphArgs &G, const BeamGra
         const void *fn = (const void *) beam_graph_kernel<R, TRL>;                                                        \
         if (dyn > 64 * 1024) (void) hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) dyn);     \
         hipLaunchKernelGGL((beam_graph_kernel<R, TRL>), dim3(P.B), dim3(kBT), dyn, stream, P, G, BG, K, (R) theta, cap,   \
-                           (char *) work, per, (R *) scores, path, tokens, tlen, states);                                 \
+                           (char *) work, per, cnt_off, (R *) scores, path, tokens, tlen, states);                               \
     } while (0)
     if (trl) ASG_BEAM(true); else ASG_BEAM(false);
 #undef ASG_BEAM
     return hipGetLastError();
 }
 template hipError_t launch_beam_graph<float>(const Problem &, const GraphArgs &, const BeamGraphArgs &, int, double, void *, void *,
-                                             long long *, long long *, long long *, long long *, hipStream_t);
+                                             long long *, long long *, long long *, long long *, hipStream_t, size_t, size_t);
 template hipError_t launch_beam_graph<double>(const Problem &, const GraphArgs &, const BeamGraphArgs &, int, double, void *, void *,
-                                              long long *, long long *, long long *, long long *, hipStream_t);
+                                              long long *, long long *, long long *, long long *, hipStream_t, size_t,
+                                              size_t);
 
 }  // namespace asg

@@ -183,10 +183,38 @@ constexpr int kBeamMaxK = 8192;  // the active set (value, q) stays in LDS
 int beam_graph_k(int Q, int beam_size);
 int beam_graph_cap(int Q, int K, int max_out, int num_start);
 size_t beam_graph_work_bytes(int elem, int T, int B, int Q, int K, int cap);
+// stride != 0: the utterances' workspaces lie `stride` bytes apart (each with the layout above at its front); cnt_off != 0: the
+// kernel also writes |A_t| of every frame, int32 [T], at that offset of each of them (asg_beam_loss.hip).  0, 0: the decoder.
 template <typename R>
 hipError_t launch_beam_graph(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, int K, double theta, void *work,
                              void *scores, long long *path, long long *tokens, long long *tlen, long long *states,
-                             hipStream_t stream);
+                             hipStream_t stream, size_t stride = 0, size_t cnt_off = 0);
+
+// ---- Beam-pruned full score and gradients over the same composed lattice (asg_beam_loss.hip): asg_beam_graph_full_*.
+struct BeamLossArgs {
+    int S, start;
+    const int *next;             // [S*N] next automaton state, -1 where no arc
+};
+// One utterance's workspace: the beam search's own layout at the front, then (byte offsets, each part 256-byte aligned) the
+// kept counts cnt [T], the lattice counts nu [T], hdr (word 0: forced states n), the target walk's keys [nf] int64 and forced
+// product states qk [nf], the lattice lists U [T][M], alpha [T or 2][M]; M = K + nf, nf = min(S, T) with targets, else 0.
+struct BeamLossLayout {
+    size_t cnt, nu, hdr, key, qk, U, A, per;
+    int M, nf;
+};
+constexpr int kBeamLossMaxN = 1024;        // a frame's label posteriors are summed in LDS
+constexpr int kBeamLossMaxForced = 2048;   // min(S, T): U_{t-1} with its values stays in LDS
+BeamLossLayout beam_loss_layout(int elem, int T, int Q, int K, int cap, int nf, bool store);
+size_t beam_loss_work_bytes(int elem, int T, int B, int Q, int K, int cap, int nf, bool store);
+size_t beam_loss_scratch_per(int elem, int M, int N);
+bool beam_loss_fits(int elem, int M, int N);
+template <typename R>
+hipError_t launch_beam_loss_forward(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const BeamLossArgs &L, int K,
+                                    double theta, bool store, void *work, void *scores, hipStream_t stream);
+template <typename R>
+hipError_t launch_beam_loss_backward(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, int K, const void *work,
+                                     const void *scores, const void *grad_scores, void *grad_inputs, void *grad_transition,
+                                     void *scratch, bool accumulate, hipStream_t stream);
 
 // ---- Full score, gradients and target walk over the same composed lattice (asg_graph_loss.hip).  The loss-only arrays of
 // asg_token_graph_loss.  Work = alpha [T][Q][B] (stored) or [2][Q][B]; scratch = align256([2][Q][B] beta) + [Q+E][B]

@@ -287,6 +287,23 @@ class TokenGraph:
         return {"orow": orow.astype(i32), "oarc": np.ascontiguousarray(oarc.astype(i32)), "ow": h["edge_w"][order],
                 "start_q": start_q.astype(i32), "num_start": int(start_q.size), "max_out": int(deg.max(initial=0))}
 
+    def compile_beam_loss(self, device, dtype, lm_weight=1.0, token_score=0.0):
+        """What `compile_beam` returns plus the automaton's transition table for the target walk of the beam-pruned loss
+        (include/asg_hip.h::asg_token_graph_beam_loss): next [S,N] int32, -1 where no arc.  Cached under its own key; the
+        results of `compile`, `compile_loss` and `compile_beam` stay as they are."""
+        base = self.compile_beam(device, dtype, lm_weight, token_score)
+        device = base["label"].device
+        key = ("beam_loss", device, dtype, float(lm_weight), float(token_score))
+        hit = self._compiled.get(key)
+        if hit is not None:
+            return hit
+        present = (self.next >= 0) & (self.weight != -np.inf)
+        dev = dict(base)
+        dev["next"] = torch.from_numpy(np.where(present, self.next, -1).astype(np.int32)).to(device)
+        dev["S"], dev["start"] = self.S, self.start
+        self._compiled[key] = dev
+        return dev
+
 
 def abi_graph(compiled):
     """The asg_token_graph view of a compiled graph (pointers into its device tensors)."""
@@ -321,3 +338,13 @@ def abi_graph_beam(compiled):
         t = compiled[name]
         setattr(gb, name, ctypes.c_void_p(t.data_ptr() if t.numel() else None))
     return gb
+
+
+def abi_graph_beam_loss(compiled):
+    """The asg_token_graph_beam_loss view of a `compile_beam_loss` result (it keeps the views it points at alive)."""
+    gb = abi_graph_beam(compiled)
+    gl = _lib.AsgTokenGraphBeamLoss()
+    gl.beam = ctypes.pointer(gb)
+    gl.S, gl.start = compiled["S"], compiled["start"]
+    gl.next = ctypes.c_void_p(compiled["next"].data_ptr())
+    return gl
