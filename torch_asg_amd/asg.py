@@ -998,15 +998,27 @@ def graph_full_score(inputs, transition, graph, input_lengths=None, lm_weight=1.
     return GraphFullScore.apply(inputs, transition, graph, input_lengths, lm_weight, token_score, max_work_bytes, 0)
 
 
+def _guarded_targets(targets, target_lengths, N):
+    """(targets with every label outside [0, N) replaced by 0, ok[B]): ok[b] is False where targets[b, :target_lengths[b]] holds
+    such a label.  The force-aligned kernels index emissions and transitions with the label as given, so they only ever see the
+    first; the caller turns the aligned score of an utterance with ok False into -inf.  On the device, no synchronisation."""
+    outside = (targets < 0) | (targets >= N)
+    pos = torch.arange(targets.shape[1], device=targets.device).unsqueeze(0) < target_lengths.to(targets.device).unsqueeze(1)
+    return targets.masked_fill(outside, 0), ~(outside & pos).any(dim=1)
+
+
 def _graph_loss_per_utterance(inputs, targets, transition, graph, input_lengths, target_lengths, lm_weight, token_score,
                               max_work_bytes, flags):
-    """[B] losses full_graph - (FAC + A(collapse(target))); +inf (never NaN) where the target has no alignment or the automaton
-    rejects it, and then only the full-graph posterior reaches the gradients.  Lengths must be given (ASGLoss._canonical)."""
+    """[B] losses full_graph - (FAC + A(collapse(target))); +inf (never NaN) where the target has no alignment, the automaton
+    rejects it or it holds a label outside [0, N) (`_guarded_targets`), and then only the full-graph posterior reaches the
+    gradients.  Lengths must be given (ASGLoss._canonical)."""
     full = GraphFullScore.apply(inputs, transition, graph, input_lengths, lm_weight, token_score, max_work_bytes, flags)
     with torch.no_grad():
         walk = native().graph_target_scores(inputs.detach(), transition.detach(), graph, targets, target_lengths, lm_weight,
                                             token_score)
-    aligned = FAC.apply(transition, inputs, targets, input_lengths, target_lengths) + walk
+    safe, inside = _guarded_targets(targets, target_lengths, inputs.shape[2])
+    aligned = FAC.apply(transition, inputs, safe, input_lengths, target_lengths) + walk
+    aligned = torch.where(inside.to(aligned.device), aligned, torch.full_like(aligned, float("-inf")))
     fd, ad = full.detach(), aligned.detach()
     ok_f, ok_a = torch.isfinite(fd), torch.isfinite(ad)
     zero = torch.zeros_like(fd)
@@ -1029,8 +1041,8 @@ def graph_asg_loss(inputs, targets, transition, graph, input_lengths=None, targe
     loss[b] = graph_full_score[b] - (S_aligned[b] + A(collapse(targets[b]))), where S_aligned is the force-aligned score (`FAC`)
     and A the automaton's score of the target with consecutive repeats merged.  exp(-loss) is the probability of the target
     under the composed model.  +inf where the target cannot be aligned (target_length > input_length, length 0) or the automaton
-    rejects it; those utterances' gradient rows hold only the full-graph posterior.  Defaults and S > T truncation as
-    `ASGLoss.forward`; reduction 'none' (default), 'sum' or 'mean'."""
+    rejects it, or it holds a label outside [0, N); those utterances' gradient rows hold only the full-graph posterior.
+    Defaults and S > T truncation as `ASGLoss.forward`; reduction 'none' (default), 'sum' or 'mean'."""
     if inputs.dtype in (torch.float16, torch.bfloat16):
         inputs = inputs.to(transition.dtype)
     targets, input_lengths, target_lengths = ASGLoss._canonical(inputs, targets, input_lengths, target_lengths)
@@ -1097,7 +1109,9 @@ def _beam_graph_loss_per_utterance(inputs, targets, transition, graph, input_len
     with torch.no_grad():
         walk = native().graph_target_scores(inputs.detach(), transition.detach(), graph, targets, target_lengths, lm_weight,
                                             token_score)
-    aligned = FAC.apply(transition, inputs, targets, input_lengths, target_lengths) + walk
+    safe, inside = _guarded_targets(targets, target_lengths, inputs.shape[2])
+    aligned = FAC.apply(transition, inputs, safe, input_lengths, target_lengths) + walk
+    aligned = torch.where(inside.to(aligned.device), aligned, torch.full_like(aligned, float("-inf")))
     fd, ad = full.detach(), aligned.detach()
     ok_f, ok_a = torch.isfinite(fd), torch.isfinite(ad)
     zero = torch.zeros_like(fd)
@@ -1109,8 +1123,9 @@ def beam_graph_asg_loss(inputs, targets, transition, graph, input_lengths=None, 
                         beam_threshold=float("inf"), lm_weight=1.0, token_score=0.0, reduction='none', max_work_bytes=1 << 30):
     """`graph_asg_loss` with the beam-pruned normaliser: loss[b] = beam_graph_full_score[b] - (S_aligned[b] +
     A(collapse(targets[b]))), the target forced into the beam's lattice, so every finite loss is >= 0 (up to rounding) for any
-    beam and equals `graph_asg_loss` once the beam holds every product state.  +inf exactly where `graph_asg_loss` is +inf; then
-    only the normaliser's posterior reaches the gradients.  Defaults and S > T truncation as `ASGLoss.forward`."""
+    beam and equals `graph_asg_loss` once the beam holds every product state.  +inf exactly where `graph_asg_loss` is +inf -- no
+    alignment, a target the automaton rejects, a label outside [0, N) within the target's length; then only the normaliser's
+    posterior reaches the gradients.  Defaults and S > T truncation as `ASGLoss.forward`."""
     _check_beam(beam_size, beam_threshold)
     if inputs.dtype in (torch.float16, torch.bfloat16):
         inputs = inputs.to(transition.dtype)

@@ -469,8 +469,9 @@ inline size_t bwd_lds(int elem, int M, int N, bool tl) {
     return kBLHead + (((size_t) M * (elem + 4) + 15) & ~(size_t) 15) + (size_t) N * 8 + (tl ? (size_t) N * N * 8 : 0);
 }
 
-inline void set_lds(const void *fn, size_t dyn) {
-    if (dyn > 64 * 1024) (void) hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) dyn);
+// a launch whose LDS -- dynamic plus the kernel's own `fixed` static bytes -- passes 64 KiB has to ask for it
+inline void set_lds(const void *fn, size_t dyn, size_t fixed = 0) {
+    if (dyn + fixed > 64 * 1024) (void) hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) dyn);
 }
 
 }  // namespace
@@ -522,6 +523,7 @@ hipError_t launch_beam_loss_forward(const Problem &P, const GraphArgs &G, const 
     hipLaunchKernelGGL((beam_loss_accept<R>), dim3((B + 63) / 64), dim3(64), 0, stream, G, lay, w, B);
     int P2 = 1;
     while (P2 < lay.M) P2 *= 2;
+    set_lds((const void *) beam_loss_sets, (size_t) P2 * 4, sizeof(int));    // (M > 8192: 64 KiB of slots beside its `int count`)
     hipLaunchKernelGGL(beam_loss_sets, dim3(T, B), dim3(kBS), (size_t) P2 * 4, stream, P, lay, K, P2, w);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
