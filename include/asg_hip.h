@@ -260,6 +260,42 @@ int asg_beam_decode_graph(asg_ctx *ctx, const asg_problem *p, const asg_token_gr
                           void *work, size_t work_bytes, void *scores, int64_t *path, int64_t *tokens, int64_t *token_lengths,
                           int64_t *states, int flags, void *stream);
 
+/* ---- The N BEST final hypotheses of that beam search, each with its score split into an acoustic and a graph part: what an
+ * n-best rescoring pass and the tuning of lm_weight / token_score need.  No counterpart in the reference.  The token automaton
+ * is deterministic, so a token sequence determines its product state and two survivors of the last frame always carry different
+ * transcripts: the n best final states are n distinct hypotheses, each the best path the pruned search found for its state.
+ * For utterance b with len = clamp(input_lengths[b], 0, T), the search of asg_beam_decode_graph runs unchanged (the same
+ * beam_size, beam_threshold, folding and dtype; the same device code).  A = A_{len-1} with values v; end[q] = v[q] + final_w[q].
+ * The candidates are the q in A with end[q] > -inf, ordered by end descending, then q ascending (-0 and +0 are equal).
+ *   num_hyps[b] = min(nbest, number of candidates): 0 for len == 0, an empty last set, or no finite end.
+ *   For r < num_hyps[b], with q_0 .. q_{len-1} the back-pointer path of the r-th candidate, i_t and s_t the label and the
+ *   automaton state of q_t:
+ *     scores[b][r] = end of that candidate;  path[b][r][t] = i_t;  states[b][r][t] = s_t;  tokens[b][r] and token_lengths[b][r]
+ *     the collapse of the path as in asg_viterbi_decode.
+ *     emission_scores[b][r], adds only, in frame order: a = I[0][i_0]; for t >= 1: a = (a + tr[i_t][i_{t-1}]) + I[t][i_t] (the
+ *     stay uses tr[i][i]).
+ *     graph_scores[b][r] likewise: g = start_w[q_0]; for every t >= 1 with q_t != q_{t-1}, in order, g = g + edge_w(q_{t-1} ->
+ *     q_t), the folded arc weight (an edge never joins a state to itself -- its labels differ -- so q_t == q_{t-1} is always the
+ *     stay); last g = g + final_w[q_{len-1}].
+ *   Rows r >= num_hyps[b] are padding: the three scores -inf, every integer output -1, token_lengths 0.  Frames t >= len: -1.
+ *   scores, emission_scores, graph_scores [B][nbest] in the dtype of the problem; path, tokens, states [B][nbest][T] int64;
+ *   token_lengths [B][nbest] int64; num_hyps [B] int64.  path and states may be NULL: they are then not written.
+ * Row 0 equals asg_beam_decode_graph's five outputs bit for bit (the same ordering rule).  scores is the search's own sum and
+ * not fl(emission_scores + graph_scores) -- the additions happen in another order -- but the two differ by no more than
+ * (3*len + 2) * eps * (the sum of the magnitudes of the terms on the path).
+ * K = min(beam_size, max(Q, 1)), nb = min(nbest, K).  `work` (asg_beam_decode_graph_nbest_work_bytes), every part rounded up to 256 bytes:
+ *   B * (asg_beam_decode_graph's bytes per utterance + (8 + K*e) (the size and the values of the last set) + T*nb*4 (the
+ *   product states of every hypothesis)) + 2*B*8 + 3*B*T*8 (what the search itself returns), e = 4 / 8.
+ * Two launches on one stream, one workgroup per utterance each; every output, padding row and scratch word that is read is
+ * written by a kernel (no memset, no copy, no synchronisation), so a captured call replays with new emissions and lengths.
+ * Results are bit-identical run to run (no float atomics).  nbest < 1: ASG_ERR_INVALID; nbest > 8192: ASG_ERR_UNSUPPORTED;
+ * everything else as for asg_beam_decode_graph.  `flags` is reserved (pass 0). */
+size_t asg_beam_decode_graph_nbest_work_bytes(const asg_problem *p, const asg_token_graph_beam *gb, int beam_size, int nbest);
+int asg_beam_decode_graph_nbest(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, int beam_size,
+                                double beam_threshold, int nbest, void *work, size_t work_bytes, void *scores,
+                                void *emission_scores, void *graph_scores, int64_t *path, int64_t *tokens, int64_t *token_lengths,
+                                int64_t *states, int64_t *num_hyps, int flags, void *stream);
+
 /* ---- Full score of the ASG lattice COMPOSED with a token automaton (the log-semiring counterpart of the decoder above), its
  * gradients, and the automaton's score of each target: the pieces of an ASG loss whose normaliser includes a token-level
  * prior.  No counterpart in the reference.  For utterance b with len = clamp(input_lengths[b], 0, T), in the dtype of the problem:

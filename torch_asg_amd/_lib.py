@@ -26,7 +26,7 @@ SYMBOLS = ["asg_hip_version", "asg_hip_strerror", "asg_ctx_create", "asg_ctx_des
            "asg_viterbi_decode_graph", "asg_graph_full_work_bytes", "asg_graph_full_scratch_bytes", "asg_graph_full_forward",
            "asg_graph_full_backward", "asg_graph_target_scores", "asg_beam_decode_graph_work_bytes", "asg_beam_decode_graph",
            "asg_beam_graph_full_work_bytes", "asg_beam_graph_full_scratch_bytes", "asg_beam_graph_full_forward",
-           "asg_beam_graph_full_backward"]
+           "asg_beam_graph_full_backward", "asg_beam_decode_graph_nbest_work_bytes", "asg_beam_decode_graph_nbest"]
 ABI_VERSION = 230        # include/asg_hip.h: ASG_HIP_VERSION this package was written against
 
 
@@ -120,6 +120,9 @@ def lib():
     L.asg_beam_decode_graph_work_bytes.restype = sz
     L.asg_beam_decode_graph_work_bytes.argtypes = [pp, bp, ci]
     L.asg_beam_decode_graph.argtypes = [vp, pp, bp, ci, ctypes.c_double, vp, sz, vp, vp, vp, vp, vp, ci, vp]
+    L.asg_beam_decode_graph_nbest_work_bytes.restype = sz
+    L.asg_beam_decode_graph_nbest_work_bytes.argtypes = [pp, bp, ci, ci]
+    L.asg_beam_decode_graph_nbest.argtypes = [vp, pp, bp, ci, ctypes.c_double, ci, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp]
     blp = ctypes.POINTER(AsgTokenGraphBeamLoss)
     L.asg_beam_graph_full_work_bytes.restype = sz
     L.asg_beam_graph_full_work_bytes.argtypes = [pp, blp, ci, ci]

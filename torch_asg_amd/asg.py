@@ -11,6 +11,7 @@ Mirrors the reference's Python interface (/root/reference/torch_asg/asg.py) so i
 All numerical work happens in hand-written HIP kernels behind the C ABI of include/asg_hip.h.
 CPU tensors are rejected: this package has no CPU fallback by design.
 """
+import collections
 import ctypes
 import os
 import threading
@@ -390,9 +391,8 @@ class HipBackend:
         return self._decode_graph(inputs, transition, graph, input_lengths, max_work_bytes, view, work_bytes, call,
                                   "asg_beam_decode_graph")
 
-    def _decode_graph(self, inputs, transition, graph, input_lengths, max_work_bytes, view, work_bytes_of, call, what):
-        """What the two graph decoders share: the checks, the utterance groups under `max_work_bytes`, the outputs.  `view`
-        compiles the graph for (device, dtype) -> its C view."""
+    def _check_decode_graph(self, inputs, transition, graph, input_lengths):
+        """The argument checks of the graph decoders."""
         from . import graph as _graph
         self._check(inputs, transition, None, input_lengths, None)
         if inputs.dtype not in (torch.float32, torch.float64):
@@ -404,6 +404,65 @@ class HipBackend:
             raise RuntimeError("torch_asg_amd: the graph is over %d tokens but the emissions have N = %d" % (graph.N, N))
         if input_lengths is not None and tuple(input_lengths.shape) != (B,):
             raise RuntimeError("torch_asg_amd: input_lengths must have shape [%d]" % B)
+
+    def beam_decode_graph_nbest(self, inputs, transition, graph, input_lengths, beam_size, nbest, beam_threshold=float("inf"),
+                                lm_weight=1.0, token_score=0.0, return_alignments=False, max_work_bytes=1 << 30):
+        """The n best final hypotheses of the beam search with their score split -> (scores, emission_scores, graph_scores
+        [B,nbest], tokens [B,nbest,T], token_lengths [B,nbest], num_hyps [B], path, states [B,nbest,T] or None); see
+        include/asg_hip.h::asg_beam_decode_graph_nbest.  Grouped under `max_work_bytes` as `_decode_graph` does."""
+        from . import graph as _graph
+        beam_size, beam_threshold = min(int(beam_size), (1 << 31) - 1), float(beam_threshold)
+        nbest = min(int(nbest), (1 << 31) - 1)
+        L = _lib.lib()
+        self._check_decode_graph(inputs, transition, graph, input_lengths)
+        T, B, N = inputs.shape
+        dev = inputs.device
+        with self._guard(dev):
+            g = _graph.abi_graph_beam(graph.compile_beam(dev, inputs.dtype, lm_weight, token_score))
+            p, keep = self._problem(inputs, transition, None, input_lengths, None)
+            if input_lengths is not None:
+                input_lengths = keep[-1]                       # (on the device, contiguous)
+
+            def work_bytes(nb):
+                p.B = nb
+                return int(L.asg_beam_decode_graph_nbest_work_bytes(ctypes.byref(p), ctypes.byref(g), beam_size, nbest))
+            per = work_bytes(1)
+            if per == 0:                                       # the library refuses the arguments: its call says why, before
+                p.B = B                                        # outputs are sized by them
+                _lib.check(L.asg_beam_decode_graph_nbest(None, ctypes.byref(p), ctypes.byref(g), beam_size, beam_threshold, nbest,
+                                                         None, 0, None, None, None, None, None, None, None, None, 0, None),
+                           "asg_beam_decode_graph_nbest")
+            per = max(per, 1)
+            gsz = max(1, min(B, int(max_work_bytes) // per))
+            while gsz > 1 and work_bytes(gsz) > max_work_bytes:
+                gsz -= 1
+            work = self._buf(work_bytes(gsz), dev)
+            sc = torch.empty(3, B, nbest, dtype=inputs.dtype, device=dev)      # scores, emission_scores, graph_scores
+            tokens = torch.empty(B, nbest, T, dtype=torch.int64, device=dev)
+            align = torch.empty(2, B, nbest, T, dtype=torch.int64, device=dev) if return_alignments else None
+            token_lengths = torch.empty(B, nbest, dtype=torch.int64, device=dev)
+            num_hyps = torch.empty(B, dtype=torch.int64, device=dev)
+            stream = self._stream(dev)
+            for b0 in range(0, B, gsz):
+                b1 = min(B, b0 + gsz)
+                p.inputs = inputs[:, b0:b1].data_ptr()
+                p.B = b1 - b0
+                if input_lengths is not None:
+                    p.input_lengths = input_lengths[b0:b1].data_ptr()
+                _lib.check(L.asg_beam_decode_graph_nbest(
+                    None, ctypes.byref(p), ctypes.byref(g), beam_size, beam_threshold, nbest, work.data_ptr(), work.numel(),
+                    sc[0, b0:].data_ptr(), sc[1, b0:].data_ptr(), sc[2, b0:].data_ptr(),
+                    align[0, b0:].data_ptr() if return_alignments else None, tokens[b0:].data_ptr(),
+                    token_lengths[b0:].data_ptr(), align[1, b0:].data_ptr() if return_alignments else None,
+                    num_hyps[b0:].data_ptr(), 0, stream), "asg_beam_decode_graph_nbest")
+        return BeamNbest(sc[0], sc[1], sc[2], tokens, token_lengths, num_hyps,
+                         align[0] if return_alignments else None, align[1] if return_alignments else None)
+
+    def _decode_graph(self, inputs, transition, graph, input_lengths, max_work_bytes, view, work_bytes_of, call, what):
+        """What the two graph decoders share: the checks, the utterance groups under `max_work_bytes`, the outputs.  `view`
+        compiles the graph for (device, dtype) -> its C view."""
+        self._check_decode_graph(inputs, transition, graph, input_lengths)
+        T, B, N = inputs.shape
         dev = inputs.device
         with self._guard(dev):
             g = view(dev, inputs.dtype)
@@ -963,6 +1022,41 @@ def beam_decode_graph(inputs, transition, graph, input_lengths=None, beam_size=2
                                           lm_weight, token_score, max_work_bytes)
 
 
+BeamNbest = collections.namedtuple("BeamNbest", ["scores", "emission_scores", "graph_scores", "tokens", "token_lengths",
+                                                 "num_hyps", "path", "states"])
+
+
+def beam_decode_graph_nbest(inputs, transition, graph, input_lengths=None, beam_size=256, nbest=10, beam_threshold=float("inf"),
+                            lm_weight=1.0, token_score=0.0, return_alignments=False, max_work_bytes=1 << 30):
+    """The `nbest` best final hypotheses of `beam_decode_graph`'s search, each with its score split into the acoustic part
+    (emissions and transitions) and the graph part (automaton weights, token_score and the final weight): what n-best
+    rescoring with a stronger model and the tuning of lm_weight / token_score need.  No gradient.
+
+    The search is `beam_decode_graph`'s, unchanged.  The token automaton is deterministic, so the states kept at the last
+    frame carry different transcripts; they are ranked by value + final weight (descending, product-state index ascending on a
+    tie) and the first `nbest` with a finite score are returned, each with the best path the pruned search found for it
+    (include/asg_hip.h::asg_beam_decode_graph_nbest).  -> a named tuple
+      scores, emission_scores, graph_scores  [B, nbest]     dtype of the emissions; -inf in the padding rows
+      tokens                                 [B, nbest, T]  int64, -1 behind each transcript
+      token_lengths                          [B, nbest]     int64
+      num_hyps                               [B]            int64, min(nbest, final states with a finite score)
+      path, states                           [B, nbest, T]  int64 label and automaton state per frame with `return_alignments`,
+                                                            else None (they then take no memory)
+    Row 0 equals `beam_decode_graph`'s result bit for bit.  `scores` is the search's own sum; emission_scores + graph_scores
+    adds the same terms in another order and agrees with it to rounding.  Inputs, widening, caching, capture and the
+    utterance groups under `max_work_bytes` are those of `beam_decode_graph`.  nbest < 1 raises ValueError, nbest > 8192
+    RuntimeError.
+    """
+    _check_beam(beam_size, beam_threshold)
+    if int(nbest) < 1:
+        raise ValueError("torch_asg_amd: nbest must be >= 1, got %d" % int(nbest))
+    if inputs.dtype in (torch.float16, torch.bfloat16):
+        inputs = inputs.to(transition.dtype)
+    with torch.no_grad():
+        return native().beam_decode_graph_nbest(inputs.detach(), transition.detach(), graph, input_lengths, beam_size, nbest,
+                                                beam_threshold, lm_weight, token_score, return_alignments, max_work_bytes)
+
+
 class GraphFullScore(torch.autograd.Function):
     """Full score of the ASG lattice composed with a token automaton, [B] (asg_graph_full_forward / _backward).  alpha is
     stored only when a gradient w.r.t. inputs or transition is needed."""
@@ -1348,6 +1442,13 @@ class ASGLoss(nn.Module):
         `torch_asg_amd.beam_decode_graph`."""
         return beam_decode_graph(inputs, self.transition, graph, input_lengths, beam_size, beam_threshold, lm_weight, token_score,
                                  max_work_bytes)
+
+    def beam_decode_graph_nbest(self, inputs, graph, input_lengths=None, beam_size=256, nbest=10, beam_threshold=float("inf"),
+                                lm_weight=1.0, token_score=0.0, return_alignments=False, max_work_bytes=1 << 30):
+        """The n best hypotheses of the beam search under this criterion's transitions, with their score split; see
+        `torch_asg_amd.beam_decode_graph_nbest`."""
+        return beam_decode_graph_nbest(inputs, self.transition, graph, input_lengths, beam_size, nbest, beam_threshold, lm_weight,
+                                       token_score, return_alignments, max_work_bytes)
 
     def graph_loss(self, inputs, targets, graph, input_lengths=None, target_lengths=None, lm_weight=1.0, token_score=0.0,
                    max_work_bytes=1 << 30):

@@ -609,6 +609,43 @@ int asg_beam_decode_graph(asg_ctx *ctx, const asg_problem *p, const asg_token_gr
                                                              (hipStream_t) stream)));
 }
 
+static int check_beam_nbest(const asg_problem *p, const asg_token_graph_beam *gb, int beam_size, int nbest) {
+    int rc = check_beam_graph(p, gb, beam_size);
+    if (rc) return rc;
+    if (nbest < 1) return ASG_ERR_INVALID;
+    if (nbest > kBeamMaxNbest) return ASG_ERR_UNSUPPORTED;
+    return ASG_OK;
+}
+
+size_t asg_beam_decode_graph_nbest_work_bytes(const asg_problem *p, const asg_token_graph_beam *gb, int beam_size, int nbest) {
+    if (check_beam_nbest(p, gb, beam_size, nbest) != ASG_OK) return 0;
+    const int Q = (int) gb->graph->Q, K = beam_graph_k(Q, beam_size);
+    return beam_nbest_work_bytes(p->dtype == ASG_DTYPE_F64 ? 8 : 4, (int) p->T, (int) p->B, Q, K,
+                                 beam_graph_cap(Q, K, gb->max_out, (int) gb->num_start), nbest);
+}
+
+int asg_beam_decode_graph_nbest(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, int beam_size,
+                                double beam_threshold, int nbest, void *work, size_t work_bytes, void *scores,
+                                void *emission_scores, void *graph_scores, int64_t *path, int64_t *tokens, int64_t *token_lengths,
+                                int64_t *states, int64_t *num_hyps, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    int rc = check_beam_nbest(p, gb, beam_size, nbest);
+    if (rc) return rc;
+    if (!(beam_threshold >= 0.0)) return ASG_ERR_INVALID;                  // negative or NaN
+    if (!work || !scores || !emission_scores || !graph_scores || !tokens || !token_lengths || !num_hyps) return ASG_ERR_INVALID;
+    if (work_bytes < asg_beam_decode_graph_nbest_work_bytes(p, gb, beam_size, nbest)) return ASG_ERR_WORKSPACE;
+    const Problem P = to_problem(p);
+    const GraphArgs G = to_graph_args(gb->graph);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    const int K = beam_graph_k(G.Q, beam_size);
+    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
+    long long *nh = (long long *) num_hyps;
+    return hip_status(ASG_DISPATCH(p, launch_beam_nbest<float>(P, G, BG, K, beam_threshold, nbest, work, scores, emission_scores,
+                                                               graph_scores, pa, tk, tl, st, nh, (hipStream_t) stream),
+                                   launch_beam_nbest<double>(P, G, BG, K, beam_threshold, nbest, work, scores, emission_scores,
+                                                             graph_scores, pa, tk, tl, st, nh, (hipStream_t) stream)));
+}
+
 static int check_beam_loss(const asg_problem *p, const asg_token_graph_beam_loss *gl, int beam_size) {
     if (!gl) return ASG_ERR_INVALID;
     int rc = check_beam_graph(p, gl->beam, beam_size);

@@ -28,6 +28,7 @@
 // earlier read may have left behind; everything else a workgroup hands between its wavefronts crosses __syncthreads.
 #include "asg_common.h"
 #include "asg_kernels.h"
+#include "asg_beam_common.h"
 
 namespace asg {
 
@@ -38,39 +39,11 @@ constexpr int kSlotBits = 16;      // arg = source q << 16 | source slot: K <= 2
 constexpr size_t kLdsMax = 160 * 1024;
 constexpr size_t kFixedLds = 4096; // histograms, counters, reduction slots
 
-template <typename R> struct Key;
-template <> struct Key<float> {
-    using U = unsigned int;
-    static constexpr int kBits = 32;
-    static __device__ __forceinline__ U enc(float x) {
-        const U b = __float_as_uint(x + 0.0f);              // -0 and +0 compare equal: one key (x + 0 is +0 for both)
-        return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-    }
-    static __device__ __forceinline__ float dec(U k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
-};
-template <> struct Key<double> {
-    using U = unsigned long long;
-    static constexpr int kBits = 64;
-    static __device__ __forceinline__ U enc(double x) {
-        const U b = (U) __double_as_longlong(x + 0.0);
-        return (b >> 63) ? ~b : (b | (1ull << 63));
-    }
-    static __device__ __forceinline__ double dec(U k) {
-        return __longlong_as_double((long long) ((k >> 63) ? (k & ~(1ull << 63)) : ~k));
-    }
-};
-
 template <typename U> __device__ __forceinline__ U dev_load(const U *p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 template <typename U> __device__ __forceinline__ void dev_store(U *p, U v) {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ int clamp_len(const int64_t *in_len, int b, int T) {
-    if (!in_len) return T;
-    const int64_t l = in_len[b];
-    return (int) (l < 0 ? 0 : (l > T ? T : l));
 }
 
 // One wavefront: tokens[0..T) of one utterance from its finished path[0..len), -1 behind them, and the token count (the
@@ -159,8 +132,8 @@ __device__ __forceinline__ void find_digit(const int *hist, int need, int lane, 
 
 template <typename R, bool TRL>
 __global__ void __launch_bounds__(kBT) beam_graph_kernel(Problem P, GraphArgs g, BeamGraphArgs bg, int K, R theta, int cap,
-                                                         char *work, size_t per_utt, size_t cnt_off, R *scores,
-                                                         long long *path, long long *tokens, long long *tlen,
+                                                         char *work, size_t per_utt, size_t cnt_off, size_t fin_off,
+                                                         R *scores, long long *path, long long *tokens, long long *tlen,
                                                          long long *states) {
     using KT = Key<R>;
     using U = typename KT::U;
@@ -191,6 +164,9 @@ __global__ void __launch_bounds__(kBT) beam_graph_kernel(Problem P, GraphArgs g,
     // cnt_off != 0 (asg_beam_loss.hip): |A_t| of every frame goes to int32 [T] at that offset of the utterance's workspace
     int *cnt = cnt_off ? (int *) (wb + cnt_off) : nullptr;
     if (cnt) for (int t = tid; t < T; t += kBT) cnt[t] = 0;
+    // fin_off != 0 (asg_beam_nbest.hip): |A_{len-1}| goes to the int32 at that offset and the values of that set, slot-aligned
+    // with bq[len-1], behind it from byte 8 on
+    int *fin_n = fin_off ? (int *) (wb + fin_off) : nullptr;
     auto TR = [&](int i, int j) -> R {
         if constexpr (TRL) return trs[i * N + j];
         else return tr[(int64_t) i * P.ts0 + (int64_t) j * P.ts1];
@@ -199,7 +175,7 @@ __global__ void __launch_bounds__(kBT) beam_graph_kernel(Problem P, GraphArgs g,
 
     if (len < 1) {
         for (int t = tid; t < T; t += kBT) { pb[t] = -1; tk[t] = -1; st[t] = -1; }
-        if (tid == 0) { scores[b] = NINF; tlen[b] = 0; }
+        if (tid == 0) { scores[b] = NINF; tlen[b] = 0; if (fin_n) *fin_n = 0; }
         return;
     }
     if constexpr (TRL)
@@ -415,6 +391,11 @@ __global__ void __launch_bounds__(kBT) beam_graph_kernel(Problem P, GraphArgs g,
 
     // ---- score: the largest v + final_w over the last active set, the smallest q on a tie
     const int na = ctl.na;
+    if (fin_n) {
+        R *fin_v = (R *) (wb + fin_off + 8);
+        for (int k = tid; k < na && k < K; k += kBT) fin_v[k] = cur_v[k];
+        if (tid == 0) *fin_n = na < K ? na : K;
+    }
     U bkey = 0;
     int bqq = 0x7FFFFFFF, bk = -1;
     for (int k = tid; k < na; k += kBT) {
@@ -487,7 +468,7 @@ size_t beam_graph_work_bytes(int elem, int T, int B, int Q, int K, int cap) {
 template <typename R>
 hipError_t launch_beam_graph(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, int K, double theta, void *work,
                              void *scores, long long *path, long long *tokens, long long *tlen, long long *states,
-                             hipStream_t stream, size_t stride, size_t cnt_off) {
+                             hipStream_t stream, size_t stride, size_t cnt_off, size_t fin_off) {
     const int N = P.N;
     const int cap = beam_graph_cap(G.Q, K, BG.max_out, BG.num_start);
     const size_t per = stride ? stride : beam_per_utt(sizeof(R), P.T, G.Q, K, cap);
@@ -500,16 +481,16 @@ hipError_t launch_beam_graph(const Problem &P, const GraphArgs &G, const BeamGra
         const void *fn = (const void *) beam_graph_kernel<R, TRL>;                                                        \
         if (dyn > 64 * 1024) (void) hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) dyn);     \
         hipLaunchKernelGGL((beam_graph_kernel<R, TRL>), dim3(P.B), dim3(kBT), dyn, stream, P, G, BG, K, (R) theta, cap,   \
-                           (char *) work, per, cnt_off, (R *) scores, path, tokens, tlen, states);                               \
+                           (char *) work, per, cnt_off, fin_off, (R *) scores, path, tokens, tlen, states);                      \
     } while (0)
     if (trl) ASG_BEAM(true); else ASG_BEAM(false);
 #undef ASG_BEAM
     return hipGetLastError();
 }
 template hipError_t launch_beam_graph<float>(const Problem &, const GraphArgs &, const BeamGraphArgs &, int, double, void *, void *,
-                                             long long *, long long *, long long *, long long *, hipStream_t, size_t, size_t);
+                                             long long *, long long *, long long *, long long *, hipStream_t, size_t, size_t, size_t);
 template hipError_t launch_beam_graph<double>(const Problem &, const GraphArgs &, const BeamGraphArgs &, int, double, void *, void *,
                                               long long *, long long *, long long *, long long *, hipStream_t, size_t,
-                                              size_t);
+                                              size_t, size_t);
 
 }  // namespace asg

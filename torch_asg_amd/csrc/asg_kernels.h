@@ -184,11 +184,30 @@ int beam_graph_k(int Q, int beam_size);
 int beam_graph_cap(int Q, int K, int max_out, int num_start);
 size_t beam_graph_work_bytes(int elem, int T, int B, int Q, int K, int cap);
 // stride != 0: the utterances' workspaces lie `stride` bytes apart (each with the layout above at its front); cnt_off != 0: the
-// kernel also writes |A_t| of every frame, int32 [T], at that offset of each of them (asg_beam_loss.hip).  0, 0: the decoder.
+// kernel also writes |A_t| of every frame, int32 [T], at that offset of each of them (asg_beam_loss.hip); fin_off != 0: it also
+// leaves |A_{len-1}| (int32) at that offset and that set's values, slot-aligned with its [K] product states, from byte 8 behind
+// it (asg_beam_nbest.hip).  0, 0, 0: the decoder.
 template <typename R>
 hipError_t launch_beam_graph(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, int K, double theta, void *work,
                              void *scores, long long *path, long long *tokens, long long *tlen, long long *states,
-                             hipStream_t stream, size_t stride = 0, size_t cnt_off = 0);
+                             hipStream_t stream, size_t stride = 0, size_t cnt_off = 0, size_t fin_off = 0);
+
+// ---- The n best final hypotheses of that search, with the score split (asg_beam_nbest.hip): asg_beam_decode_graph_nbest.
+// One utterance's workspace: the beam search's own layout at the front, then (byte offsets, each part 256-byte aligned) fin
+// (int32 |A_{len-1}|, then from byte 8 its values [K]) and rows (int32 [T][nb] product states of every hypothesis, frame-major),
+// nb = min(nbest, K).  Behind the utterances: what the search itself returns (beam_loss_tail_bytes' layout).
+struct BeamNbestLayout {
+    size_t fin, rows, per;
+    int nb;
+};
+constexpr int kBeamMaxNbest = 8192;
+BeamNbestLayout beam_nbest_layout(int elem, int T, int Q, int K, int cap, int nbest);
+size_t beam_nbest_work_bytes(int elem, int T, int B, int Q, int K, int cap, int nbest);
+// path / states may be null (then they are not written)
+template <typename R>
+hipError_t launch_beam_nbest(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, int K, double theta, int nbest,
+                             void *work, void *scores, void *emission_scores, void *graph_scores, long long *path,
+                             long long *tokens, long long *tlen, long long *states, long long *num_hyps, hipStream_t stream);
 
 // ---- Beam-pruned full score and gradients over the same composed lattice (asg_beam_loss.hip): asg_beam_graph_full_*.
 struct BeamLossArgs {
