@@ -296,6 +296,52 @@ int asg_beam_decode_graph_nbest(asg_ctx *ctx, const asg_problem *p, const asg_to
                                 void *emission_scores, void *graph_scores, int64_t *path, int64_t *tokens, int64_t *token_lengths,
                                 int64_t *states, int64_t *num_hyps, int flags, void *stream);
 
+/* ---- STREAMING beam decoding: the search of asg_beam_decode_graph carried across chunks of frames, for a service that receives
+ * an utterance a few frames at a time, shows a transcript while it is still arriving and needs the final one a chunk after the
+ * last frame, without a second search over everything.  No counterpart in the reference.
+ * A STREAM STATE is one device buffer that serves B utterance slots, for a fixed graph, dtype, K = min(beam_size, max(Q, 1)) and
+ * max_frames (every call on a state passes the same gb, B, beam_size and max_frames).  Per slot it holds: pos, the frames
+ * consumed so far; the active set A_{pos-1} with its values; the back-pointers (product state, source slot) of the frames
+ * 0 .. pos-1; a sticky overflow word; and the slot arrays of the search (best-candidate slot per product state, touched list,
+ * keys).  The contents are opaque; a state must be reset before its first use.
+ *   asg_beam_stream_reset: for every slot b with mask[b] != 0 (one byte per slot on the device; NULL: every slot): pos = 0, the
+ *     set empty, overflow = 0, and the best-candidate slots of all Q product states emptied (the only place where those Q
+ *     entries are written: a frame empties what it touched).  Written by a kernel.
+ *   asg_beam_stream_advance: p->inputs is a chunk [Tc = p->T, B, N] (any strides) and p->input_lengths the chunk's lengths (NULL:
+ *     Tc for every slot); p->transition and beam_threshold are used for the frames of this call (they may differ between calls).
+ *     For slot b: n = min(clamp(input_lengths[b], 0, Tc), max_frames - pos).  If the bound by max_frames cut anything, overflow = 1;
+ *     the frames beyond it are not consumed and nothing is written out of bounds.  The chunk's frames 0 .. n-1 are the frames
+ *     pos .. pos+n-1 of the utterance and run exactly the rules of asg_beam_decode_graph -- the same adds in the same order,
+ *     the same tie rules, the same prune; the same device code: frame 0 of the utterance takes its candidates from start_w, every
+ *     other frame -- the first frame of a chunk included -- from the stored set; an empty set stays empty.  Then pos += n.
+ *     Nothing is written besides the state.  Tc = 0 is allowed and changes nothing.
+ *   asg_beam_stream_result: reads the state and does not modify it; it may be called after any chunk, and the stream continues.
+ *     With L = pos and A = A_{L-1} with values v:  final != 0: end[q] = v[q] + final_w[q];  final == 0: end[q] = v[q], the best
+ *     PREFIX hypothesis, without a final weight.  The winner is the q in A with the largest end > -inf, the smallest q on a tie
+ *     (-0 and +0 are equal).  scores [B] (dtype) = its end; path, tokens, states [B][max_frames] int64 follow its back-pointers
+ *     as in asg_beam_decode_graph, -1 behind the data; token_lengths [B]; frames [B] = L; status [B] = the overflow word (0 / 1).
+ *     L == 0, an empty set or no finite end: score -inf, path / tokens / states all -1, token_lengths 0.
+ * REQUIRED PROPERTY.  Take a slot that was reset and then advanced by any sequence of chunks that concatenate to x[0:L],
+ * L <= max_frames (chunks of no frames included).  asg_beam_stream_result(final = 1) then equals asg_beam_decode_graph on x with
+ * T >= L frames, input_length = L, the same transition, beam_size, beam_threshold, folding and dtype: scores and token_lengths bit
+ * for bit; path, tokens and states equal on the columns < T and -1 elsewhere.  No tolerance: the search never looks ahead.
+ * State (asg_beam_stream_state_bytes; 0 for arguments that the calls refuse), every part rounded up to 256 bytes:
+ *   B * (asg_beam_decode_graph's bytes per utterance with T = max_frames + 256 (pos, set size, overflow) + K*(e + 4) (the stored
+ *   set: values, then product states)), e = 4 / 8.  The back-pointers keep asg_beam_decode_graph's [frame][K] layout.
+ * Each call is ONE launch on `stream`, one workgroup per slot for advance and result: no host synchronisation, no copy, no
+ * memset, so a captured call replays with new chunk contents and lengths, and a capture is one linear chain.  Integer atomics
+ * only: bit-identical run to run.  Limits: those of asg_beam_decode_graph with T = max_frames (K <= 8192, ...; ASG_ERR_UNSUPPORTED
+ * beyond); max_frames < 1, Tc < 0, B < 1, beam_size < 1, a negative or NaN beam_threshold, dtype not the graph's:
+ * ASG_ERR_INVALID; a state buffer smaller than asg_beam_stream_state_bytes: ASG_ERR_WORKSPACE.  `flags` is reserved (pass 0). */
+size_t asg_beam_stream_state_bytes(const asg_token_graph_beam *gb, int64_t B, int dtype, int beam_size, int64_t max_frames);
+int asg_beam_stream_reset(asg_ctx *ctx, const asg_token_graph_beam *gb, int64_t B, int beam_size, int64_t max_frames, void *state,
+                          size_t state_bytes, const uint8_t *mask, int flags, void *stream);
+int asg_beam_stream_advance(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, int beam_size,
+                            double beam_threshold, int64_t max_frames, void *state, size_t state_bytes, int flags, void *stream);
+int asg_beam_stream_result(asg_ctx *ctx, const asg_token_graph_beam *gb, int64_t B, int beam_size, int64_t max_frames,
+                           const void *state, size_t state_bytes, int final, void *scores, int64_t *path, int64_t *tokens,
+                           int64_t *token_lengths, int64_t *states, int64_t *frames, int64_t *status, int flags, void *stream);
+
 /* ---- Full score of the ASG lattice COMPOSED with a token automaton (the log-semiring counterpart of the decoder above), its
  * gradients, and the automaton's score of each target: the pieces of an ASG loss whose normaliser includes a token-level
  * prior.  No counterpart in the reference.  For utterance b with len = clamp(input_lengths[b], 0, T), in the dtype of the problem:

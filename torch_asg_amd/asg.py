@@ -1057,6 +1057,132 @@ def beam_decode_graph_nbest(inputs, transition, graph, input_lengths=None, beam_
                                                 beam_threshold, lm_weight, token_score, return_alignments, max_work_bytes)
 
 
+BeamStreamResult = collections.namedtuple("BeamStreamResult", ["scores", "path", "tokens", "token_lengths", "states", "frames",
+                                                               "status"])
+
+
+class BeamStream:
+    """`beam_decode_graph` for an utterance that arrives in chunks: the beam search carried from one chunk to the next, for
+    `batch_size` utterance slots at a time.  No gradient.
+
+        s = BeamStream(transition, graph, batch_size, max_frames, beam_size=256)
+        for chunk in chunks:                 # [Tc, B, N] each
+            s.advance(chunk)
+            partial = s.result()             # the best prefix hypothesis so far; the stream goes on
+        final = s.result(final=True)         # what beam_decode_graph returns for the whole utterance, bit for bit
+
+    The search is `beam_decode_graph`'s, frame by frame, with the same device code (include/asg_hip.h::asg_beam_stream_advance):
+    for any way of cutting an utterance of at most `max_frames` frames into chunks, `result(final=True)` equals the one-shot
+    decode of the whole utterance -- scores and token_lengths bit for bit, path / tokens / states on the one-shot's columns and
+    -1 beyond.  `transition` (a tensor or Parameter of dtype `dtype`; it is read again at every `advance`), `beam_threshold`,
+    `lm_weight` and `token_score` are those of `beam_decode_graph`; the attribute `beam_threshold` may be changed between chunks.
+
+    The state lives in one device buffer (about max_frames * beam_size * 8 bytes of back-pointers plus 12-16 bytes per product
+    state, per slot).  The graph is compiled in the constructor; `advance`, `result` and `reset` are one kernel launch each, copy
+    nothing and do not synchronise, so they can be captured in a graph and replayed with new chunk contents and lengths.
+    """
+
+    def __init__(self, transition, graph, batch_size, max_frames, beam_size=256, beam_threshold=float("inf"), lm_weight=1.0,
+                 token_score=0.0, dtype=torch.float32, device=None):
+        from . import graph as _graph
+        _check_beam(beam_size, beam_threshold)
+        if not isinstance(graph, _graph.TokenGraph):
+            raise TypeError("torch_asg_amd: graph must be a torch_asg_amd.TokenGraph")
+        if int(batch_size) < 1 or int(max_frames) < 1:
+            raise ValueError("torch_asg_amd: batch_size and max_frames must be >= 1, got %d and %d"
+                             % (int(batch_size), int(max_frames)))
+        if dtype not in (torch.float32, torch.float64):
+            raise RuntimeError("torch_asg_amd: expected scalar type Float or Double but found %s" % dtype)
+        device = torch.device(device) if device is not None else transition.device
+        if device.type != "cuda":
+            raise RuntimeError("torch_asg_amd: a BeamStream must live on a ROCm device (got %s); "
+                               "there is no CPU implementation in this package" % device)
+        if transition.dtype != dtype or transition.device != device or tuple(transition.shape) != (graph.N, graph.N):
+            raise RuntimeError("torch_asg_amd: transition must be [%d,%d] with the dtype/device of the stream" % (graph.N, graph.N))
+        self.transition, self.graph = transition, graph
+        self.batch_size, self.max_frames = int(batch_size), int(max_frames)
+        self.beam_size, self.beam_threshold = min(int(beam_size), (1 << 31) - 1), float(beam_threshold)
+        self.lm_weight, self.token_score, self.dtype, self.device = lm_weight, token_score, dtype, device
+        be = native()
+        L = _lib.lib()
+        with be._guard(device):
+            self._compiled = graph.compile_beam(device, dtype, lm_weight, token_score)
+            self._g = _graph.abi_graph_beam(self._compiled)
+            abi_dtype = _lib.ASG_DTYPE_F32 if dtype == torch.float32 else _lib.ASG_DTYPE_F64
+            nbytes = int(L.asg_beam_stream_state_bytes(ctypes.byref(self._g), self.batch_size, abi_dtype, self.beam_size,
+                                                       self.max_frames))
+            if nbytes == 0:                                    # the library refuses the arguments: its call says why
+                _lib.check(L.asg_beam_stream_reset(None, ctypes.byref(self._g), self.batch_size, self.beam_size, self.max_frames,
+                                                   None, 0, None, 0, None), "asg_beam_stream_reset")
+            self._state = be._buf(nbytes, device)
+        self._fed = 0                                          # frames offered since the last full reset (the host's bound)
+        self.reset()
+
+    def reset(self, mask=None):
+        """Start new utterances: in every slot (mask None), or in the slots where `mask` (bool or integer [B]) is not zero --
+        the other slots go on.  After a masked reset `advance`'s host-side check of `max_frames` is not tightened; the device
+        clamps and `result().status` reports it."""
+        be = native()
+        L = _lib.lib()
+        m = None
+        if mask is not None:
+            if tuple(mask.shape) != (self.batch_size,):
+                raise RuntimeError("torch_asg_amd: mask must have shape [%d]" % self.batch_size)
+            m = mask.to(self.device).ne(0).to(torch.uint8).contiguous()
+        with be._guard(self.device):
+            _lib.check(L.asg_beam_stream_reset(None, ctypes.byref(self._g), self.batch_size, self.beam_size, self.max_frames,
+                                               self._state.data_ptr(), self._state.numel(), m.data_ptr() if m is not None else None,
+                                               0, be._stream(self.device)), "asg_beam_stream_reset")
+        if mask is None:
+            self._fed = 0
+
+    def advance(self, chunk, chunk_lengths=None):
+        """Consume `chunk` [Tc, B, N]: slot b takes its first clamp(chunk_lengths[b], 0, Tc) frames (all Tc when
+        `chunk_lengths` is None) as the next frames of its utterance.  Chunk dtype, strides and float16 / bfloat16 widening as in
+        `beam_decode_graph`.  ValueError, without touching the device, once the Tc offered since the last full `reset()` exceed
+        `max_frames`."""
+        be = native()
+        L = _lib.lib()
+        transition = self.transition.detach()
+        if chunk.dtype in (torch.float16, torch.bfloat16):
+            chunk = chunk.to(transition.dtype)
+        chunk = chunk.detach()
+        be._check_decode_graph(chunk, transition, self.graph, chunk_lengths)
+        Tc, B, N = chunk.shape
+        if chunk.dtype != self.dtype or chunk.device != self.device or B != self.batch_size:
+            raise RuntimeError("torch_asg_amd: the stream takes chunks [Tc,%d,%d] of %s on %s, got %s of %s on %s"
+                               % (self.batch_size, N, self.dtype, self.device, tuple(chunk.shape), chunk.dtype, chunk.device))
+        _check_beam(self.beam_size, self.beam_threshold)
+        if self._fed + Tc > self.max_frames:
+            raise ValueError("torch_asg_amd: %d frames since the last reset() plus a chunk of %d exceed max_frames = %d"
+                             % (self._fed, Tc, self.max_frames))
+        with be._guard(self.device):
+            p, keep = be._problem(chunk, transition, None, chunk_lengths, None)
+            _lib.check(L.asg_beam_stream_advance(None, ctypes.byref(p), ctypes.byref(self._g), self.beam_size,
+                                                 float(self.beam_threshold), self.max_frames, self._state.data_ptr(),
+                                                 self._state.numel(), 0, be._stream(self.device)), "asg_beam_stream_advance")
+        self._fed += Tc
+
+    def result(self, final=False):
+        """The best hypothesis of every slot over the frames consumed so far, without changing the state -> a named tuple
+          scores [B]; path, tokens, states [B, max_frames] int64, -1 behind the data; token_lengths [B]; frames [B], the frames
+          consumed; status [B], 1 where frames beyond max_frames were offered and dropped.
+        final=True adds the final weights (the transcript of a finished utterance: `beam_decode_graph`'s result); final=False is
+        the best prefix hypothesis, largest value without a final weight.  A slot without frames or with an empty beam: -inf, -1, 0."""
+        be = native()
+        L = _lib.lib()
+        B, T, dev = self.batch_size, self.max_frames, self.device
+        with be._guard(dev):
+            scores = torch.empty(B, dtype=self.dtype, device=dev)
+            out = torch.empty(3, B, T, dtype=torch.int64, device=dev)          # path, tokens, states
+            small = torch.empty(3, B, dtype=torch.int64, device=dev)           # token_lengths, frames, status
+            _lib.check(L.asg_beam_stream_result(None, ctypes.byref(self._g), B, self.beam_size, T, self._state.data_ptr(),
+                                                self._state.numel(), 1 if final else 0, scores.data_ptr(), out[0].data_ptr(),
+                                                out[1].data_ptr(), small[0].data_ptr(), out[2].data_ptr(), small[1].data_ptr(),
+                                                small[2].data_ptr(), 0, be._stream(dev)), "asg_beam_stream_result")
+        return BeamStreamResult(scores, out[0], out[1], small[0], out[2], small[1], small[2])
+
+
 class GraphFullScore(torch.autograd.Function):
     """Full score of the ASG lattice composed with a token automaton, [B] (asg_graph_full_forward / _backward).  alpha is
     stored only when a gradient w.r.t. inputs or transition is needed."""
@@ -1449,6 +1575,13 @@ class ASGLoss(nn.Module):
         `torch_asg_amd.beam_decode_graph_nbest`."""
         return beam_decode_graph_nbest(inputs, self.transition, graph, input_lengths, beam_size, nbest, beam_threshold, lm_weight,
                                        token_score, return_alignments, max_work_bytes)
+
+    def beam_stream(self, graph, batch_size, max_frames, beam_size=256, beam_threshold=float("inf"), lm_weight=1.0,
+                    token_score=0.0):
+        """A streaming beam decoder under this module's transition matrix (read again at every chunk): see
+        `torch_asg_amd.BeamStream`."""
+        return BeamStream(self.transition, graph, batch_size, max_frames, beam_size, beam_threshold, lm_weight, token_score,
+                          self.transition.dtype, self.transition.device)
 
     def graph_loss(self, inputs, targets, graph, input_lengths=None, target_lengths=None, lm_weight=1.0, token_score=0.0,
                    max_work_bytes=1 << 30):

@@ -646,6 +646,85 @@ int asg_beam_decode_graph_nbest(asg_ctx *ctx, const asg_problem *p, const asg_to
                                                              graph_scores, pa, tk, tl, st, nh, (hipStream_t) stream)));
 }
 
+// A stream state is sized like a problem of max_frames frames: the graph, B, the dtype and the beam are checked through a
+// problem of that shape (its emissions are not read: any non-null pointer stands in for them).
+static int check_beam_stream(const asg_token_graph_beam *gb, int64_t B, int dtype, int beam_size, int64_t max_frames) {
+    if (!gb || !gb->graph) return ASG_ERR_INVALID;
+    asg_problem q{};
+    q.inputs = gb; q.transition = gb;
+    q.T = max_frames; q.B = B; q.N = gb->graph->N; q.S = 1; q.dtype = dtype;
+    return check_beam_graph(&q, gb, beam_size);
+}
+
+static size_t beam_stream_bytes(const asg_token_graph_beam *gb, int64_t B, int dtype, int beam_size, int64_t max_frames) {
+    const int Q = (int) gb->graph->Q, K = beam_graph_k(Q, beam_size);
+    return beam_stream_state_bytes(dtype == ASG_DTYPE_F64 ? 8 : 4, (int) max_frames, (int) B, Q, K,
+                                   beam_graph_cap(Q, K, gb->max_out, (int) gb->num_start));
+}
+
+size_t asg_beam_stream_state_bytes(const asg_token_graph_beam *gb, int64_t B, int dtype, int beam_size, int64_t max_frames) {
+    if (check_beam_stream(gb, B, dtype, beam_size, max_frames) != ASG_OK) return 0;
+    return beam_stream_bytes(gb, B, dtype, beam_size, max_frames);
+}
+
+int asg_beam_stream_reset(asg_ctx *ctx, const asg_token_graph_beam *gb, int64_t B, int beam_size, int64_t max_frames, void *state,
+                          size_t state_bytes, const uint8_t *mask, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    if (!gb || !gb->graph) return ASG_ERR_INVALID;
+    const int dtype = gb->graph->dtype;
+    int rc = check_beam_stream(gb, B, dtype, beam_size, max_frames);
+    if (rc) return rc;
+    if (!state) return ASG_ERR_INVALID;
+    if (state_bytes < beam_stream_bytes(gb, B, dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
+    const GraphArgs G = to_graph_args(gb->graph);
+    return hip_status(launch_beam_stream_reset(dtype == ASG_DTYPE_F64 ? 8 : 4, G, to_beam_graph_args(gb),
+                                               beam_graph_k(G.Q, beam_size), (int) max_frames, (int) B, state, mask,
+                                               (hipStream_t) stream));
+}
+
+int asg_beam_stream_advance(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, int beam_size,
+                            double beam_threshold, int64_t max_frames, void *state, size_t state_bytes, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    if (!p) return ASG_ERR_INVALID;
+    int rc = check_beam_stream(gb, p->B, p->dtype, beam_size, max_frames);
+    if (rc) return rc;
+    if (p->T < 0 || p->N != gb->graph->N) return ASG_ERR_INVALID;
+    if (p->T > 0 && (rc = check_beam_graph(p, gb, beam_size)) != ASG_OK) return rc;
+    if (!(beam_threshold >= 0.0)) return ASG_ERR_INVALID;                  // negative or NaN
+    if (!state) return ASG_ERR_INVALID;
+    if (state_bytes < beam_stream_bytes(gb, p->B, p->dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
+    if (p->T == 0) return ASG_OK;                                          // no frame: the state stays as it is
+    const Problem P = to_problem(p);
+    const GraphArgs G = to_graph_args(gb->graph);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    const int K = beam_graph_k(G.Q, beam_size);
+    return hip_status(ASG_DISPATCH(p, launch_beam_stream_advance<float>(P, G, BG, K, beam_threshold, (int) max_frames, state,
+                                                                        (hipStream_t) stream),
+                                   launch_beam_stream_advance<double>(P, G, BG, K, beam_threshold, (int) max_frames, state,
+                                                                      (hipStream_t) stream)));
+}
+
+int asg_beam_stream_result(asg_ctx *ctx, const asg_token_graph_beam *gb, int64_t B, int beam_size, int64_t max_frames,
+                           const void *state, size_t state_bytes, int final, void *scores, int64_t *path, int64_t *tokens,
+                           int64_t *token_lengths, int64_t *states, int64_t *frames, int64_t *status, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    if (!gb || !gb->graph) return ASG_ERR_INVALID;
+    const asg_token_graph *g = gb->graph;
+    int rc = check_beam_stream(gb, B, g->dtype, beam_size, max_frames);
+    if (rc) return rc;
+    if (!state || !scores || !path || !tokens || !token_lengths || !states || !frames || !status) return ASG_ERR_INVALID;
+    if (state_bytes < beam_stream_bytes(gb, B, g->dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
+    const GraphArgs G = to_graph_args(g);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    const int K = beam_graph_k(G.Q, beam_size);
+    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
+    long long *fr = (long long *) frames, *su = (long long *) status;
+    return hip_status(ASG_DISPATCH(g, launch_beam_stream_result<float>(G, BG, K, (int) max_frames, (int) B, state, final, scores, pa,
+                                                                       tk, tl, st, fr, su, (hipStream_t) stream),
+                                   launch_beam_stream_result<double>(G, BG, K, (int) max_frames, (int) B, state, final, scores, pa,
+                                                                     tk, tl, st, fr, su, (hipStream_t) stream)));
+}
+
 static int check_beam_loss(const asg_problem *p, const asg_token_graph_beam_loss *gl, int beam_size) {
     if (!gl) return ASG_ERR_INVALID;
     int rc = check_beam_graph(p, gl->beam, beam_size);

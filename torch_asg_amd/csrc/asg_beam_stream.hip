@@ -1,0 +1,206 @@
+// torch_asg_amd/csrc/asg_beam_stream.hip -- STREAMING beam decoding on gfx950: the search of asg_beam_graph.hip carried across
+// chunks of frames, so that a transcript exists while the utterance is still arriving.  The specification is
+// include/asg_hip.h::asg_beam_stream_advance; tests/beam_stream_ref.py restates it.  Decoding an utterance in chunks gives the
+// bits of decoding it in one call, for any chunking: the frames run the device code of the one-shot decoder (asg_beam_frame.h,
+// compiled into both translation units), and the search never looks ahead.
+//
+// A stream state serves B utterance slots.  One slot (beam_stream_layout; every part 256-byte aligned):
+//   the one-shot decoder's workspace of one utterance with T = max_frames: bq / bs int32 [max_frames][K] (product state and source
+//     slot of every kept state of every frame consumed so far), arg u64 [Q], val key [Q], ckey key [cap], touched int32 [cap];
+//   a 256-byte header: int32 pos (frames consumed), |A| (size of the stored set), overflow;
+//   the stored set: values [K] (dtype), then product states int32 [K].
+// Three kernels, each one launch, no host synchronisation, no copy, no memset:
+//   beam_stream_reset_kernel    per chosen slot: pos = 0, |A| = 0, overflow = 0, val = 0 and arg = none for all Q states.  The only
+//                               place the Q entries are written: a frame empties what it touched, so they are empty between calls.
+//   beam_stream_advance_kernel  one 1024-thread workgroup per slot: the transitions and the stored set into LDS, beam_frame for
+//                               the chunk's frames with the back-pointers into rows pos .. pos+n-1, the set and pos back.
+//   beam_stream_result_kernel   one workgroup per slot: the best end over the stored set (with or without the final weights), the
+//                               backtrace over pos frames, the token collapse, the padding.  It only reads the state.
+// What one call writes and the next reads crosses a kernel boundary, so plain stores and loads do; val / arg keep the
+// device-scope atomics of the frame body.  Integer atomics only: bit-identical run to run.
+#include "asg_common.h"
+#include "asg_kernels.h"
+#include "asg_beam_common.h"
+#include "asg_beam_frame.h"
+
+namespace asg {
+
+namespace {
+
+inline size_t a256(size_t x) { return (x + 255) / 256 * 256; }
+
+constexpr int kResetBlocks = 64;   // workgroups per slot in the reset
+
+__global__ void __launch_bounds__(256) beam_stream_reset_kernel(char *state, BeamStreamLayout lay, int Q, int key_bytes,
+                                                                 size_t arg_off, size_t val_off, const unsigned char *mask) {
+    const int b = blockIdx.x;
+    if (mask && !mask[b]) return;
+    char *wb = state + (size_t) b * lay.per;
+    unsigned long long *arg = (unsigned long long *) (wb + arg_off);
+    for (int q = blockIdx.y * 256 + threadIdx.x; q < Q; q += gridDim.y * 256) {
+        dev_store(arg + q, ~0ull);
+        if (key_bytes == 8) dev_store((unsigned long long *) (wb + val_off) + q, 0ull);
+        else dev_store((unsigned int *) (wb + val_off) + q, 0u);
+    }
+    if (blockIdx.y == 0 && threadIdx.x < 3) ((int *) (wb + lay.hdr))[threadIdx.x] = 0;      // pos, |A|, overflow
+}
+
+template <typename R, bool TRL>
+__global__ void __launch_bounds__(kBT) beam_stream_advance_kernel(Problem P, GraphArgs g, BeamGraphArgs bg, int K, R theta, int cap,
+                                                                  int max_frames, char *state, BeamStreamLayout lay) {
+    using KT = Key<R>;
+    using U = typename KT::U;
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    Ctl<U> &ctl = *(Ctl<U> *) lds;
+    R *cur_v = (R *) (lds + kFixedLds);                    // [K]
+    int *cur_q = (int *) (cur_v + K);                      // [K]
+    R *trs = (R *) (cur_q + K + (K & 1));                  // [N][N] if TRL
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const int N = P.N;
+    char *wb = state + (size_t) b * lay.per;
+    int *hdr = (int *) (wb + lay.hdr);
+    R *set_v = (R *) (wb + lay.set);                        // [K]
+    int *set_q = (int *) (set_v + K);                       // [K]
+    int pos = hdr[0];
+    pos = pos < 0 ? 0 : (pos > max_frames ? max_frames : pos);             // (a state that was reset holds 0 .. max_frames)
+    const int want = clamp_len(P.in_len, b, P.T);
+    const int n = want < max_frames - pos ? want : max_frames - pos;
+    if (n < want && tid == 0) hdr[2] = 1;                   // frames beyond max_frames are not consumed
+    if (n < 1) return;
+    const R *in = (const R *) P.inputs + (int64_t) b * P.is1;
+    const R *tr = (const R *) P.transition;
+    BeamFrame<R> f;
+    f.ctl = &ctl; f.cur_v = cur_v; f.cur_q = cur_q; f.trs = trs; f.tr = tr; f.ts0 = P.ts0; f.ts1 = P.ts1;
+    f.N = N; f.Q = g.Q; f.K = K; f.G = beam_lanes_per_state(K); f.theta = theta;
+    f.label = g.label; f.orow = bg.orow; f.start_q = bg.start_q; f.num_start = bg.num_start;
+    f.oarc = (const int2 *) bg.oarc; f.ow = (const R *) bg.ow; f.sw = (const R *) g.start_w;
+    int *bq, *bs;
+    f.bind_work(wb, max_frames, cap, bq, bs);
+
+    if constexpr (TRL)
+        for (int x = tid; x < N * N; x += kBT) trs[x] = tr[(int64_t) (x / N) * P.ts0 + (int64_t) (x % N) * P.ts1];
+    int na0 = pos >= 1 ? hdr[1] : 0;
+    na0 = na0 < 0 ? 0 : (na0 > K ? K : na0);
+    for (int k = tid; k < na0; k += kBT) { cur_v[k] = set_v[k]; cur_q[k] = set_q[k]; }
+    if (tid == 0) { ctl.na = na0; ctl.n = 0; }
+    __syncthreads();
+
+    for (int t = 0; t < n; ++t) {
+        const int gt = pos + t;                             // the frame's index in the utterance
+        const int na = ctl.na;
+        if (gt >= 1 && na == 0) break;                      // an empty beam stays empty
+        beam_frame<R, TRL>(f, gt == 0, na, in + (int64_t) t * P.is0, P.is2, bq, bs, gt);
+    }
+
+    int na = ctl.na;
+    na = na < K ? na : K;
+    for (int k = tid; k < na; k += kBT) { set_v[k] = cur_v[k]; set_q[k] = cur_q[k]; }
+    if (tid == 0) { hdr[1] = na; hdr[0] = pos + n; }
+}
+
+template <typename R>
+__global__ void __launch_bounds__(kBT) beam_stream_result_kernel(GraphArgs g, int K, int max_frames, const char *state,
+                                                                 BeamStreamLayout lay, int final, R *scores, long long *path,
+                                                                 long long *tokens, long long *tlen, long long *states,
+                                                                 long long *frames, long long *status) {
+    using U = typename Key<R>::U;
+    __shared__ Ctl<U> ctl;
+    const int tid = threadIdx.x, b = blockIdx.x, T = max_frames;
+    const R NINF = Num<R>::ninf();
+    const char *wb = state + (size_t) b * lay.per;
+    const int *hdr = (const int *) (wb + lay.hdr);
+    const R *set_v = (const R *) (wb + lay.set);
+    const int *set_q = (const int *) (set_v + K);
+    const int *bq = (const int *) wb;                                                        // [max_frames][K]
+    const int *bs = (const int *) (wb + (((size_t) T * K * 4 + 255) & ~(size_t) 255));       // [max_frames][K]
+    long long *pb = path + (int64_t) b * T, *tk = tokens + (int64_t) b * T, *st = states + (int64_t) b * T;
+    int L = hdr[0];
+    L = L < 0 ? 0 : (L > T ? T : L);
+    int na = L >= 1 ? hdr[1] : 0;
+    na = na < 0 ? 0 : (na > K ? K : na);
+    if (tid == 0) { frames[b] = L; status[b] = hdr[2] != 0; }
+    const R *fw = final ? (const R *) g.final_w : nullptr;
+    U bkey;
+    int bqq, bk;
+    beam_best_end<R>(ctl, set_q, set_v, na, fw, bkey, bqq, bk);
+    if (bkey == 0) {                                        // no frame yet, an empty set, or no finite end
+        beam_no_path(T, pb, tk, st, tlen + b);
+        if (tid == 0) scores[b] = NINF;
+        return;
+    }
+    // the score itself, from the winner's own sum (the key folds -0 into +0)
+    if (tid == 0) scores[b] = fw ? set_v[bk] + fw[bqq] : set_v[bk];
+    beam_backtrace(bq, bs, K, L, T, bk, g.label, g.state, pb, tk, st, tlen + b);
+}
+
+}  // namespace
+
+BeamStreamLayout beam_stream_layout(int elem, int max_frames, int Q, int K, int cap) {
+    BeamStreamLayout l{};
+    size_t off = beam_graph_work_bytes(elem, max_frames, 1, Q, K, cap);     // the one-shot decoder's part, at the front
+    l.hdr = off;  off += 256;
+    l.set = off;  off += a256((size_t) K * (elem + 4));
+    l.per = off;
+    return l;
+}
+
+size_t beam_stream_state_bytes(int elem, int max_frames, int B, int Q, int K, int cap) {
+    return (size_t) B * beam_stream_layout(elem, max_frames, Q, K, cap).per;
+}
+
+hipError_t launch_beam_stream_reset(int elem, const GraphArgs &G, const BeamGraphArgs &BG, int K, int max_frames, int B, void *state,
+                                    const unsigned char *mask, hipStream_t stream) {
+    const int cap = beam_graph_cap(G.Q, K, BG.max_out, BG.num_start);
+    const BeamStreamLayout lay = beam_stream_layout(elem, max_frames, G.Q, K, cap);
+    const size_t arg_off = 2 * a256((size_t) max_frames * K * 4), val_off = arg_off + a256((size_t) G.Q * 8);
+    int by = (G.Q + 255) / 256;
+    by = by < 1 ? 1 : (by > kResetBlocks ? kResetBlocks : by);
+    hipLaunchKernelGGL(beam_stream_reset_kernel, dim3(B, by), dim3(256), 0, stream, (char *) state, lay, G.Q, elem, arg_off, val_off,
+                       mask);
+    return hipGetLastError();
+}
+
+template <typename R>
+hipError_t launch_beam_stream_advance(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, int K, double theta,
+                                      int max_frames, void *state, hipStream_t stream) {
+    const int N = P.N;
+    const int cap = beam_graph_cap(G.Q, K, BG.max_out, BG.num_start);
+    const BeamStreamLayout lay = beam_stream_layout(sizeof(R), max_frames, G.Q, K, cap);
+    // the LDS of the one-shot decoder: control block, the set, and the transitions when they fit beside it
+    const size_t beam = kFixedLds + (size_t) K * (sizeof(R) + 4) + 8;
+    const bool trl = beam + (size_t) N * N * sizeof(R) <= kLdsMax;
+    const size_t dyn = beam + (trl ? (size_t) N * N * sizeof(R) : 0);
+#define ASG_BEAM_STREAM(TRL)                                                                                               \
+    do {                                                                                                                   \
+        const void *fn = (const void *) beam_stream_advance_kernel<R, TRL>;                                               \
+        if (dyn > 64 * 1024) (void) hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) dyn);     \
+        hipLaunchKernelGGL((beam_stream_advance_kernel<R, TRL>), dim3(P.B), dim3(kBT), dyn, stream, P, G, BG, K, (R) theta, \
+                           cap, max_frames, (char *) state, lay);                                                          \
+    } while (0)
+    if (trl) ASG_BEAM_STREAM(true); else ASG_BEAM_STREAM(false);
+#undef ASG_BEAM_STREAM
+    return hipGetLastError();
+}
+template hipError_t launch_beam_stream_advance<float>(const Problem &, const GraphArgs &, const BeamGraphArgs &, int, double, int,
+                                                      void *, hipStream_t);
+template hipError_t launch_beam_stream_advance<double>(const Problem &, const GraphArgs &, const BeamGraphArgs &, int, double, int,
+                                                       void *, hipStream_t);
+
+template <typename R>
+hipError_t launch_beam_stream_result(const GraphArgs &G, const BeamGraphArgs &BG, int K, int max_frames, int B, const void *state,
+                                     int final, void *scores, long long *path, long long *tokens, long long *tlen,
+                                     long long *states, long long *frames, long long *status, hipStream_t stream) {
+    const int cap = beam_graph_cap(G.Q, K, BG.max_out, BG.num_start);
+    const BeamStreamLayout lay = beam_stream_layout(sizeof(R), max_frames, G.Q, K, cap);
+    hipLaunchKernelGGL((beam_stream_result_kernel<R>), dim3(B), dim3(kBT), 0, stream, G, K, max_frames, (const char *) state, lay,
+                       final, (R *) scores, path, tokens, tlen, states, frames, status);
+    return hipGetLastError();
+}
+template hipError_t launch_beam_stream_result<float>(const GraphArgs &, const BeamGraphArgs &, int, int, int, const void *, int,
+                                                     void *, long long *, long long *, long long *, long long *, long long *,
+                                                     long long *, hipStream_t);
+template hipError_t launch_beam_stream_result<double>(const GraphArgs &, const BeamGraphArgs &, int, int, int, const void *, int,
+                                                      void *, long long *, long long *, long long *, long long *, long long *,
+                                                      long long *, hipStream_t);
+
+}  // namespace asg

@@ -192,6 +192,26 @@ hipError_t launch_beam_graph(const Problem &P, const GraphArgs &G, const BeamGra
                              void *scores, long long *path, long long *tokens, long long *tlen, long long *states,
                              hipStream_t stream, size_t stride = 0, size_t cnt_off = 0, size_t fin_off = 0);
 
+// ---- The same search carried across chunks of frames (asg_beam_stream.hip): asg_beam_stream_*.  One slot of the state (byte
+// offsets, each part 256-byte aligned): the beam search's own layout for T = max_frames at the front, then hdr (int32 pos, |A|,
+// overflow) and the stored set (values [K], then int32 product states [K]).
+struct BeamStreamLayout {
+    size_t hdr, set, per;
+};
+BeamStreamLayout beam_stream_layout(int elem, int max_frames, int Q, int K, int cap);
+size_t beam_stream_state_bytes(int elem, int max_frames, int B, int Q, int K, int cap);
+// mask: one byte per slot (null: every slot)
+hipError_t launch_beam_stream_reset(int elem, const GraphArgs &G, const BeamGraphArgs &BG, int K, int max_frames, int B, void *state,
+                                    const unsigned char *mask, hipStream_t stream);
+// P.T frames of P.inputs per slot at the most (P.in_len: the chunk's lengths)
+template <typename R>
+hipError_t launch_beam_stream_advance(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, int K, double theta,
+                                      int max_frames, void *state, hipStream_t stream);
+template <typename R>
+hipError_t launch_beam_stream_result(const GraphArgs &G, const BeamGraphArgs &BG, int K, int max_frames, int B, const void *state,
+                                     int final, void *scores, long long *path, long long *tokens, long long *tlen,
+                                     long long *states, long long *frames, long long *status, hipStream_t stream);
+
 // ---- The n best final hypotheses of that search, with the score split (asg_beam_nbest.hip): asg_beam_decode_graph_nbest.
 // One utterance's workspace: the beam search's own layout at the front, then (byte offsets, each part 256-byte aligned) fin
 // (int32 |A_{len-1}|, then from byte 8 its values [K]) and rows (int32 [T][nb] product states of every hypothesis, frame-major),
