@@ -342,6 +342,73 @@ int asg_beam_stream_result(asg_ctx *ctx, const asg_token_graph_beam *gb, int64_t
                            const void *state, size_t state_bytes, int final, void *scores, int64_t *path, int64_t *tokens,
                            int64_t *token_lengths, int64_t *states, int64_t *frames, int64_t *status, int flags, void *stream);
 
+/* ---- WINDOWED streaming beam decoding: the stream above in BOUNDED memory, for an open microphone, a meeting, a broadcast --
+ * utterances without a max_frames.  The search is asg_beam_stream_advance's (the same device code, the same sets and scores bit
+ * for bit); the back-pointers are kept only for a window of W frames, in a ring, and the prefix of the transcript on which all
+ * surviving hypotheses agree is COMMITTED: returned by the advance that finds it, never to change.  No counterpart in the reference.
+ * A WINDOW STREAM STATE serves B slots, for a fixed graph, dtype, K = min(beam_size, max(Q, 1)), window W >= 1 and commit period P,
+ * 1 <= P <= W (every call on a state passes the same gb, B, beam_size, W and P).  Per slot it holds: pos (int64), the frames
+ * consumed so far -- unbounded; base (int64), the frames committed so far, base <= pos; the stored set A_{pos-1} with its values;
+ * bq / bs int32 [W][K], the back-pointers (product state, source slot) of frame u in row u mod W (computed in 64 bits); carry
+ * (int32), the label of the last committed frame or -1; a sticky status word; and the slot arrays of the search as in
+ * asg_beam_stream_*.  The contents are opaque; a state must be reset before its first use.
+ *   asg_beam_window_reset: as asg_beam_stream_reset, and base = 0, carry = -1, status = 0 for the chosen slots.
+ *   asg_beam_window_advance: p->inputs is a chunk [Tc = p->T, B, N], p->input_lengths the chunk's lengths, p->transition and
+ *     beam_threshold those of this call, as for asg_beam_stream_advance.  For slot b, n = clamp(input_lengths[b], 0, Tc) -- there
+ *     is no other bound.  The chunk's frames are the frames pos .. pos+n-1 of the utterance and run exactly as in
+ *     asg_beam_stream_advance (frame 0 from start_w, the first frame of a chunk from the stored set, an empty set stays empty);
+ *     the back-pointers of frame u go to row u mod W.  After each frame, with pos now counting it, a COMMIT ATTEMPT runs if
+ *     pos mod P == 0 and the set is not empty:
+ *       1. Convergence.  R = all slots of A_{pos-1}.  If |R| == 1: c = pos-1.  Otherwise for u = pos-1 down to base+1:
+ *          R <- { bs[u][k] : k in R }; the first u at which |R| == 1 gives c = u-1; no such u: no c.  If c exists, the path from
+ *          that one slot of frame c back to frame base is committed: the frames base .. c in ascending order, and base = c+1.
+ *       2. Forced commit, if afterwards pos - base > W - P (the next P frames could overwrite live rows): F = (pos - base) -
+ *          (W - P).  The best prefix state of A_{pos-1} -- largest v, smallest q on a tie, -0 equal to +0: the rule of
+ *          asg_beam_stream_result(final = 0) -- is followed back to frame base+F-1; the frames base .. base+F-1 on that path are
+ *          committed, base += F and status |= 1.
+ *     Committing a frame with product state q appends label[q] to new_path and state[q] to new_states at the next free column of
+ *     this call's output row; if label[q] != carry it appends the label to new_tokens; then carry = label[q] (the collapse of
+ *     asg_viterbi_decode, carried across calls).  After an attempt pos - base <= W - P, between attempts pos - base <= W: no live
+ *     row is ever overwritten.  Then pos += n.
+ *     Outputs: new_path, new_states, new_tokens int64 [B][W + Tc] (committed <= (pos - base before the call) + n <= W + Tc), -1
+ *     behind the data; new_frames [B], the frames this call committed; new_token_lengths [B].  Every element is written by the
+ *     kernel.  Tc = 0 is allowed and writes the empty outputs.
+ *   asg_beam_window_result: reads the state only; the stream goes on.  The winner is chosen as in asg_beam_stream_result (final
+ *     != 0: v + final_w; final == 0: v; the smallest q on a tie).  scores [B]; path, states, tokens int64 [B][W], -1 behind the
+ *     data: path and states hold the winner's frames base .. pos-1 (the uncommitted TAIL), tokens their collapse started from
+ *     carry -- a first tail label equal to carry is no token; token_lengths [B]; frames [B] = pos; committed [B] = base;
+ *     status [B]: bit 0 = a forced commit has happened (sticky until the reset), bit 1 = pos >= 1 and the set is empty.  An empty
+ *     set or no finite end: score -inf, the tail all -1, token_lengths 0; what was committed stays committed.  The backtrace is at
+ *     most W steps, whatever pos.
+ * REQUIRED PROPERTIES (no tolerance in any).  1. Search identity: for any chunking of x[0:L], any W and P, result(final = 1).scores
+ * equals asg_beam_decode_graph's score on x bit for bit and result(final = 0).scores equals asg_beam_stream_result's: the window
+ * never touches the search.  2. Chunk invariance: at equal pos, base, carry, status and the concatenation of everything advance
+ * has returned are the same for every chunking, forced commits included -- attempts happen at frame indices, not at call
+ * boundaries.  3. Exactness: while status bit 0 is clear and the one-shot score is finite, concat(new_path of all calls) followed
+ * by the tail path equals the one-shot path[:L], the same for states, and concat(new_tokens) followed by the tail tokens equals
+ * the one-shot tokens[:token_length]; with W - P >= L a forced commit is impossible.  4. With status bit 0 set the outputs are
+ * still exactly those specified above: deterministic, the same for every chunking.
+ * State (asg_beam_window_state_bytes; 0 for arguments that the calls refuse), every part rounded up to 256 bytes:
+ *   B * (asg_beam_decode_graph's bytes per utterance with T = W + 256 (pos, base, set size, carry, status) + K*(e + 4) (the stored
+ *   set: values, then product states)), e = 4 / 8: the back-pointers take 2 * W*K*4 bytes, whatever the length of the utterance.
+ * Each call is ONE launch on `stream`, one 1024-thread workgroup per slot for advance and result: no host synchronisation, no
+ * copy, no memset, so a captured advance is one kernel node and replays with new chunk contents and lengths whatever the number
+ * of hardware queues.  Integer atomics only: bit-identical run to run.  Limits: those of asg_beam_decode_graph with T = W (K <=
+ * 8192, ...; ASG_ERR_UNSUPPORTED beyond); W < 1, P < 1, P > W, Tc < 0, B < 1, beam_size < 1, a negative or NaN beam_threshold,
+ * dtype not the graph's, a NULL output: ASG_ERR_INVALID; a state buffer smaller than asg_beam_window_state_bytes:
+ * ASG_ERR_WORKSPACE.  `flags` is reserved (pass 0). */
+size_t asg_beam_window_state_bytes(const asg_token_graph_beam *gb, int64_t B, int dtype, int beam_size, int64_t W, int64_t P);
+int asg_beam_window_reset(asg_ctx *ctx, const asg_token_graph_beam *gb, int64_t B, int beam_size, int64_t W, int64_t P, void *state,
+                          size_t state_bytes, const uint8_t *mask, int flags, void *stream);
+int asg_beam_window_advance(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, int beam_size,
+                            double beam_threshold, int64_t W, int64_t P, void *state, size_t state_bytes, int64_t *new_path,
+                            int64_t *new_states, int64_t *new_tokens, int64_t *new_frames, int64_t *new_token_lengths, int flags,
+                            void *stream);
+int asg_beam_window_result(asg_ctx *ctx, const asg_token_graph_beam *gb, int64_t B, int beam_size, int64_t W, int64_t P,
+                           const void *state, size_t state_bytes, int final, void *scores, int64_t *path, int64_t *tokens,
+                           int64_t *token_lengths, int64_t *states, int64_t *frames, int64_t *committed, int64_t *status, int flags,
+                           void *stream);
+
 /* ---- Full score of the ASG lattice COMPOSED with a token automaton (the log-semiring counterpart of the decoder above), its
  * gradients, and the automaton's score of each target: the pieces of an ASG loss whose normaliser includes a token-level
  * prior.  No counterpart in the reference.  For utterance b with len = clamp(input_lengths[b], 0, T), in the dtype of the problem:

@@ -5,6 +5,7 @@ from .asg import GraphFullScore, graph_full_score, graph_asg_loss  # noqa: F401
 from .asg import BeamGraphFullScore, beam_graph_full_score, beam_graph_asg_loss  # noqa: F401
 from .asg import BeamNbest, beam_decode_graph_nbest  # noqa: F401
 from .asg import BeamStream, BeamStreamResult  # noqa: F401
+from .asg import BeamWindowStream, BeamWindowCommit, BeamWindowResult  # noqa: F401
 from .graph import TokenGraph  # noqa: F401
 from .distributed import shard_batch, sharded_asg_loss, allreduce_transition_grad  # noqa: F401
 from ._graphed import graphed, GraphedStep  # noqa: F401
@@ -37,5 +38,5 @@ def release():
 __all__ = ["ASGLoss", "ASGLossFunction", "FAC", "FCC", "ASGGPUFast", "ASGGPUFastForwardOnly", "viterbi_align", "viterbi_decode",
            "viterbi_decode_graph", "beam_decode_graph", "TokenGraph", "GraphFullScore", "graph_full_score", "graph_asg_loss",
            "BeamGraphFullScore", "beam_graph_full_score", "beam_graph_asg_loss", "BeamNbest", "beam_decode_graph_nbest",
-           "BeamStream", "BeamStreamResult",
+           "BeamStream", "BeamStreamResult", "BeamWindowStream", "BeamWindowCommit", "BeamWindowResult",
            "shard_batch", "sharded_asg_loss", "allreduce_transition_grad", "reserve", "release", "check_faults", "graphed", "GraphedStep"]

@@ -1183,6 +1183,139 @@ class BeamStream:
         return BeamStreamResult(scores, out[0], out[1], small[0], out[2], small[1], small[2])
 
 
+BeamWindowCommit = collections.namedtuple("BeamWindowCommit", ["path", "states", "tokens", "token_lengths", "frames"])
+BeamWindowResult = collections.namedtuple("BeamWindowResult", ["scores", "path", "tokens", "token_lengths", "states", "frames",
+                                                               "committed", "status"])
+
+
+class BeamWindowStream:
+    """`BeamStream` in bounded memory, for utterances without an end in sight: the same beam search, the back-pointers kept only
+    for a window of `window` frames, and the prefix of the transcript on which all surviving hypotheses agree COMMITTED -- handed
+    out by the `advance` that finds it, never to change.  No gradient.
+
+        s = BeamWindowStream(transition, graph, batch_size, window=128, beam_size=256)
+        for chunk in chunks:                 # [Tc, B, N] each, for as long as the microphone is open
+            new = s.advance(chunk)           # new.tokens[b, :new.token_lengths[b]]: append them to slot b's transcript
+            tail = s.result()                # the best hypothesis for the frames that are not committed yet
+        last = s.result(final=True)          # the committed tokens + last.tokens are the transcript
+
+    After every frame whose count is a multiple of `commit_every` (default max(1, window // 4)) the device looks for the latest
+    frame at which all hypotheses of the beam share one ancestor and commits everything up to it; if the uncommitted frames would
+    not leave room for the next `commit_every` frames in the window, it commits the oldest ones along the best hypothesis and sets
+    bit 0 of `status` (include/asg_hip.h::asg_beam_window_advance).  Scores are `BeamStream`'s and `beam_decode_graph`'s bit for
+    bit, for every window; while bit 0 of `status` is clear the committed frames followed by the tail are `beam_decode_graph`'s
+    path, and the same for the tokens.  What is committed does not depend on how the frames were cut into chunks.
+
+    The state is one device buffer of about window * beam_size * 8 bytes of back-pointers plus 12-16 bytes per product state,
+    per slot, whatever the length of the utterance; `result` walks at most `window` frames.  `advance`, `result` and `reset` are
+    one kernel launch each, copy nothing and do not synchronise, so they can be captured and replayed.  The other arguments are
+    `BeamStream`'s; there is no bound on the number of frames.
+    """
+
+    def __init__(self, transition, graph, batch_size, window, commit_every=None, beam_size=256, beam_threshold=float("inf"),
+                 lm_weight=1.0, token_score=0.0, dtype=torch.float32, device=None):
+        from . import graph as _graph
+        _check_beam(beam_size, beam_threshold)
+        if not isinstance(graph, _graph.TokenGraph):
+            raise TypeError("torch_asg_amd: graph must be a torch_asg_amd.TokenGraph")
+        if int(batch_size) < 1 or int(window) < 1:
+            raise ValueError("torch_asg_amd: batch_size and window must be >= 1, got %d and %d" % (int(batch_size), int(window)))
+        commit_every = max(1, int(window) // 4) if commit_every is None else int(commit_every)
+        if not 1 <= commit_every <= int(window):
+            raise ValueError("torch_asg_amd: commit_every must be in 1 .. window = %d, got %d" % (int(window), commit_every))
+        if dtype not in (torch.float32, torch.float64):
+            raise RuntimeError("torch_asg_amd: expected scalar type Float or Double but found %s" % dtype)
+        device = torch.device(device) if device is not None else transition.device
+        if device.type != "cuda":
+            raise RuntimeError("torch_asg_amd: a BeamWindowStream must live on a ROCm device (got %s); "
+                               "there is no CPU implementation in this package" % device)
+        if transition.dtype != dtype or transition.device != device or tuple(transition.shape) != (graph.N, graph.N):
+            raise RuntimeError("torch_asg_amd: transition must be [%d,%d] with the dtype/device of the stream" % (graph.N, graph.N))
+        self.transition, self.graph = transition, graph
+        self.batch_size, self.window, self.commit_every = int(batch_size), int(window), commit_every
+        self.beam_size, self.beam_threshold = min(int(beam_size), (1 << 31) - 1), float(beam_threshold)
+        self.lm_weight, self.token_score, self.dtype, self.device = lm_weight, token_score, dtype, device
+        be = native()
+        L = _lib.lib()
+        with be._guard(device):
+            self._compiled = graph.compile_beam(device, dtype, lm_weight, token_score)
+            self._g = _graph.abi_graph_beam(self._compiled)
+            abi_dtype = _lib.ASG_DTYPE_F32 if dtype == torch.float32 else _lib.ASG_DTYPE_F64
+            nbytes = int(L.asg_beam_window_state_bytes(ctypes.byref(self._g), self.batch_size, abi_dtype, self.beam_size,
+                                                       self.window, self.commit_every))
+            if nbytes == 0:                                    # the library refuses the arguments: its call says why
+                _lib.check(L.asg_beam_window_reset(None, ctypes.byref(self._g), self.batch_size, self.beam_size, self.window,
+                                                   self.commit_every, None, 0, None, 0, None), "asg_beam_window_reset")
+            self._state = be._buf(nbytes, device)
+        self.reset()
+
+    def reset(self, mask=None):
+        """Start new utterances: in every slot (mask None), or in the slots where `mask` (bool or integer [B]) is not zero --
+        the other slots go on."""
+        be = native()
+        L = _lib.lib()
+        m = None
+        if mask is not None:
+            if tuple(mask.shape) != (self.batch_size,):
+                raise RuntimeError("torch_asg_amd: mask must have shape [%d]" % self.batch_size)
+            m = mask.to(self.device).ne(0).to(torch.uint8).contiguous()
+        with be._guard(self.device):
+            _lib.check(L.asg_beam_window_reset(None, ctypes.byref(self._g), self.batch_size, self.beam_size, self.window,
+                                               self.commit_every, self._state.data_ptr(), self._state.numel(),
+                                               m.data_ptr() if m is not None else None, 0, be._stream(self.device)),
+                       "asg_beam_window_reset")
+
+    def advance(self, chunk, chunk_lengths=None):
+        """Consume `chunk` [Tc, B, N] as `BeamStream.advance` does -> what this call committed, a named tuple
+          path, states, tokens [B, window + Tc] int64, -1 behind the data: label and automaton state of every newly committed
+          frame, and the tokens they add to the transcript (the collapse goes on across calls); token_lengths [B]; frames [B],
+          the number of frames committed by this call."""
+        be = native()
+        L = _lib.lib()
+        transition = self.transition.detach()
+        if chunk.dtype in (torch.float16, torch.bfloat16):
+            chunk = chunk.to(transition.dtype)
+        chunk = chunk.detach()
+        be._check_decode_graph(chunk, transition, self.graph, chunk_lengths)
+        Tc, B, N = chunk.shape
+        if chunk.dtype != self.dtype or chunk.device != self.device or B != self.batch_size:
+            raise RuntimeError("torch_asg_amd: the stream takes chunks [Tc,%d,%d] of %s on %s, got %s of %s on %s"
+                               % (self.batch_size, N, self.dtype, self.device, tuple(chunk.shape), chunk.dtype, chunk.device))
+        _check_beam(self.beam_size, self.beam_threshold)
+        dev = self.device
+        with be._guard(dev):
+            out = torch.empty(3, B, self.window + Tc, dtype=torch.int64, device=dev)       # path, states, tokens
+            small = torch.empty(2, B, dtype=torch.int64, device=dev)                       # frames, token_lengths
+            p, keep = be._problem(chunk, transition, None, chunk_lengths, None)
+            _lib.check(L.asg_beam_window_advance(None, ctypes.byref(p), ctypes.byref(self._g), self.beam_size,
+                                                 float(self.beam_threshold), self.window, self.commit_every,
+                                                 self._state.data_ptr(), self._state.numel(), out[0].data_ptr(), out[1].data_ptr(),
+                                                 out[2].data_ptr(), small[0].data_ptr(), small[1].data_ptr(), 0, be._stream(dev)),
+                       "asg_beam_window_advance")
+        return BeamWindowCommit(out[0], out[1], out[2], small[1], small[0])
+
+    def result(self, final=False):
+        """The best hypothesis of every slot for the frames that are not committed yet, without changing the state -> a named tuple
+          scores [B], the score of the whole hypothesis; path, tokens, states [B, window] int64, -1 behind the data: the
+          uncommitted tail (a first label that repeats the last committed one is no token); token_lengths [B]; frames [B], the
+          frames consumed; committed [B], the frames committed; status [B]: bit 0 = frames were committed before the hypotheses
+          agreed on them, bit 1 = the beam is empty.
+        final as for `BeamStream.result`.  A slot without frames or with an empty beam: -inf, -1, 0."""
+        be = native()
+        L = _lib.lib()
+        B, W, dev = self.batch_size, self.window, self.device
+        with be._guard(dev):
+            scores = torch.empty(B, dtype=self.dtype, device=dev)
+            out = torch.empty(3, B, W, dtype=torch.int64, device=dev)          # path, tokens, states
+            small = torch.empty(4, B, dtype=torch.int64, device=dev)           # token_lengths, frames, committed, status
+            _lib.check(L.asg_beam_window_result(None, ctypes.byref(self._g), B, self.beam_size, W, self.commit_every,
+                                                self._state.data_ptr(), self._state.numel(), 1 if final else 0, scores.data_ptr(),
+                                                out[0].data_ptr(), out[1].data_ptr(), small[0].data_ptr(), out[2].data_ptr(),
+                                                small[1].data_ptr(), small[2].data_ptr(), small[3].data_ptr(), 0, be._stream(dev)),
+                       "asg_beam_window_result")
+        return BeamWindowResult(scores, out[0], out[1], small[0], out[2], small[1], small[2], small[3])
+
+
 class GraphFullScore(torch.autograd.Function):
     """Full score of the ASG lattice composed with a token automaton, [B] (asg_graph_full_forward / _backward).  alpha is
     stored only when a gradient w.r.t. inputs or transition is needed."""
@@ -1582,6 +1715,13 @@ class ASGLoss(nn.Module):
         `torch_asg_amd.BeamStream`."""
         return BeamStream(self.transition, graph, batch_size, max_frames, beam_size, beam_threshold, lm_weight, token_score,
                           self.transition.dtype, self.transition.device)
+
+    def beam_window_stream(self, graph, batch_size, window, commit_every=None, beam_size=256, beam_threshold=float("inf"),
+                           lm_weight=1.0, token_score=0.0):
+        """A streaming beam decoder in bounded memory under this module's transition matrix (read again at every chunk): see
+        `torch_asg_amd.BeamWindowStream`."""
+        return BeamWindowStream(self.transition, graph, batch_size, window, commit_every, beam_size, beam_threshold, lm_weight,
+                                token_score, self.transition.dtype, self.transition.device)
 
     def graph_loss(self, inputs, targets, graph, input_lengths=None, target_lengths=None, lm_weight=1.0, token_score=0.0,
                    max_work_bytes=1 << 30):

@@ -725,6 +725,85 @@ int asg_beam_stream_result(asg_ctx *ctx, const asg_token_graph_beam *gb, int64_t
                                                                      tk, tl, st, fr, su, (hipStream_t) stream)));
 }
 
+// A window stream state is sized like a problem of W frames (the ring); P is the commit period.
+static int check_beam_window(const asg_token_graph_beam *gb, int64_t B, int dtype, int beam_size, int64_t W, int64_t P) {
+    if (W < 1 || P < 1 || P > W) return ASG_ERR_INVALID;
+    return check_beam_stream(gb, B, dtype, beam_size, W);
+}
+
+static size_t beam_window_bytes(const asg_token_graph_beam *gb, int64_t B, int dtype, int beam_size, int64_t W) {
+    const int Q = (int) gb->graph->Q, K = beam_graph_k(Q, beam_size);
+    return beam_window_state_bytes(dtype == ASG_DTYPE_F64 ? 8 : 4, (int) W, (int) B, Q, K,
+                                   beam_graph_cap(Q, K, gb->max_out, (int) gb->num_start));
+}
+
+size_t asg_beam_window_state_bytes(const asg_token_graph_beam *gb, int64_t B, int dtype, int beam_size, int64_t W, int64_t P) {
+    if (check_beam_window(gb, B, dtype, beam_size, W, P) != ASG_OK) return 0;
+    return beam_window_bytes(gb, B, dtype, beam_size, W);
+}
+
+int asg_beam_window_reset(asg_ctx *ctx, const asg_token_graph_beam *gb, int64_t B, int beam_size, int64_t W, int64_t P, void *state,
+                          size_t state_bytes, const uint8_t *mask, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    if (!gb || !gb->graph) return ASG_ERR_INVALID;
+    const int dtype = gb->graph->dtype;
+    int rc = check_beam_window(gb, B, dtype, beam_size, W, P);
+    if (rc) return rc;
+    if (!state) return ASG_ERR_INVALID;
+    if (state_bytes < beam_window_bytes(gb, B, dtype, beam_size, W)) return ASG_ERR_WORKSPACE;
+    const GraphArgs G = to_graph_args(gb->graph);
+    return hip_status(launch_beam_window_reset(dtype == ASG_DTYPE_F64 ? 8 : 4, G, to_beam_graph_args(gb),
+                                               beam_graph_k(G.Q, beam_size), (int) W, (int) B, state, mask, (hipStream_t) stream));
+}
+
+int asg_beam_window_advance(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, int beam_size,
+                            double beam_threshold, int64_t W, int64_t P, void *state, size_t state_bytes, int64_t *new_path,
+                            int64_t *new_states, int64_t *new_tokens, int64_t *new_frames, int64_t *new_token_lengths, int flags,
+                            void *stream) {
+    (void) ctx; (void) flags;
+    if (!p) return ASG_ERR_INVALID;
+    int rc = check_beam_window(gb, p->B, p->dtype, beam_size, W, P);
+    if (rc) return rc;
+    if (p->T < 0 || p->N != gb->graph->N) return ASG_ERR_INVALID;
+    if (p->T > 0 && (rc = check_beam_graph(p, gb, beam_size)) != ASG_OK) return rc;
+    if (!(beam_threshold >= 0.0)) return ASG_ERR_INVALID;                  // negative or NaN
+    if (!state || !new_path || !new_states || !new_tokens || !new_frames || !new_token_lengths) return ASG_ERR_INVALID;
+    if (state_bytes < beam_window_bytes(gb, p->B, p->dtype, beam_size, W)) return ASG_ERR_WORKSPACE;
+    const Problem Pr = to_problem(p);                                      // (no frame: the launch still writes the empty outputs)
+    const GraphArgs G = to_graph_args(gb->graph);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    const int K = beam_graph_k(G.Q, beam_size);
+    long long *np = (long long *) new_path, *ns = (long long *) new_states, *nt = (long long *) new_tokens;
+    long long *nf = (long long *) new_frames, *nl = (long long *) new_token_lengths;
+    return hip_status(ASG_DISPATCH(p, launch_beam_window_advance<float>(Pr, G, BG, K, beam_threshold, (int) W, (int) P, state, np, ns,
+                                                                        nt, nf, nl, (hipStream_t) stream),
+                                   launch_beam_window_advance<double>(Pr, G, BG, K, beam_threshold, (int) W, (int) P, state, np, ns,
+                                                                      nt, nf, nl, (hipStream_t) stream)));
+}
+
+int asg_beam_window_result(asg_ctx *ctx, const asg_token_graph_beam *gb, int64_t B, int beam_size, int64_t W, int64_t P,
+                           const void *state, size_t state_bytes, int final, void *scores, int64_t *path, int64_t *tokens,
+                           int64_t *token_lengths, int64_t *states, int64_t *frames, int64_t *committed, int64_t *status, int flags,
+                           void *stream) {
+    (void) ctx; (void) flags;
+    if (!gb || !gb->graph) return ASG_ERR_INVALID;
+    const asg_token_graph *g = gb->graph;
+    int rc = check_beam_window(gb, B, g->dtype, beam_size, W, P);
+    if (rc) return rc;
+    if (!state || !scores || !path || !tokens || !token_lengths || !states || !frames || !committed || !status)
+        return ASG_ERR_INVALID;
+    if (state_bytes < beam_window_bytes(gb, B, g->dtype, beam_size, W)) return ASG_ERR_WORKSPACE;
+    const GraphArgs G = to_graph_args(g);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    const int K = beam_graph_k(G.Q, beam_size);
+    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
+    long long *fr = (long long *) frames, *co = (long long *) committed, *su = (long long *) status;
+    return hip_status(ASG_DISPATCH(g, launch_beam_window_result<float>(G, BG, K, (int) W, (int) B, state, final, scores, pa, tk, tl,
+                                                                       st, fr, co, su, (hipStream_t) stream),
+                                   launch_beam_window_result<double>(G, BG, K, (int) W, (int) B, state, final, scores, pa, tk, tl,
+                                                                     st, fr, co, su, (hipStream_t) stream)));
+}
+
 static int check_beam_loss(const asg_problem *p, const asg_token_graph_beam_loss *gl, int beam_size) {
     if (!gl) return ASG_ERR_INVALID;
     int rc = check_beam_graph(p, gl->beam, beam_size);

@@ -47,6 +47,28 @@ __device__ inline void collapse_tokens(const long long *pb, int len, int T, long
     if (lane == 0) *tl = base;
 }
 
+// One wavefront: the same collapse for a SEGMENT of a path that continues an earlier one (asg_beam_window.hip): pb[0..len) are
+// the labels behind a frame whose label was `carry` (-1: none), so a first label equal to `carry` is no token.  The kept labels
+// go to tk[0..) -- the caller passes the next free column -- and nothing is padded.  -> the number appended; `carry` becomes the
+// segment's last label (unchanged for len == 0).  Every lane gets both.
+__device__ inline int collapse_tokens_from(const long long *pb, int len, long long &carry, long long *tk, int lane) {
+    int base = 0;
+    for (int c0 = 0; c0 < len; c0 += 64) {
+        const int t = c0 + lane;
+        const long long cur = t < len ? pb[t] : -1;
+        long long prv = __shfl_up(cur, 1);
+        if (lane == 0) prv = carry;
+        const bool keep = t < len && cur != prv;
+        const unsigned long long m = __ballot(keep);
+        const int pre = __popcll(m & ((1ull << lane) - 1ull));
+        if (keep) tk[base + pre] = cur;
+        base += __popcll(m);
+        const int last = len - c0 < 64 ? len - c0 - 1 : 63;
+        carry = __shfl(cur, last);
+    }
+    return base;
+}
+
 // Append for the lanes with `want` (all lanes of the wavefront that are in the enclosing loop call it): one bump of the LDS
 // counter per wavefront; -> the lane's position.
 __device__ __forceinline__ int wave_append(bool want, int *counter) {
