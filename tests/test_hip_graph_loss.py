@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from graph_loss_ref import full_graph_ref, target_scores_ref
+from graph_regime_cases import _ngram, _one_state       # (shared with tests/test_hip_graph_regimes.py)
 from util import assert_close
 
 pytestmark = pytest.mark.gpu
@@ -21,14 +22,6 @@ def _asg():
     return torch_asg_amd
 
 
-def _ngram(N, order, seed, holes=False):
-    rng = np.random.default_rng(seed)
-    lp = np.log(rng.dirichlet(np.ones(N + 1), size=(N + 1,) * (order - 1))) if order > 1 else np.log(rng.dirichlet(np.ones(N + 1)))
-    if holes:
-        lp[rng.random(size=lp.shape) < 0.2] = -np.inf
-    return _asg().TokenGraph.from_ngram(lp)
-
-
 def _random_graph(S, N, seed):
     rng = np.random.default_rng(seed)
     nxt = rng.integers(0, S // 2, size=(S, N))             # states >= S/2 are never entered
@@ -37,10 +30,6 @@ def _random_graph(S, N, seed):
     f = rng.normal(size=S)
     f[rng.random(size=S) < 0.3] = -np.inf
     return _asg().TokenGraph(nxt, w, f, start=0)
-
-
-def _one_state(N):
-    return _asg().TokenGraph(np.zeros((1, N), np.int64), np.zeros((1, N)), np.zeros(1))
 
 
 GRAPHS = {
