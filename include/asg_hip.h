@@ -409,6 +409,72 @@ int asg_beam_window_result(asg_ctx *ctx, const asg_token_graph_beam *gb, int64_t
                            int64_t *token_lengths, int64_t *states, int64_t *frames, int64_t *committed, int64_t *status, int flags,
                            void *stream);
 
+/* ---- Beam decoding with a LEXICON and a WORD n-gram LM, the LM composed ON THE FLY: the search of asg_beam_decode_graph over
+ * pairs (h, q) -- h a history state of a backoff word LM, q a product state of the lexicon automaton -- that exist only while the
+ * search holds them.  A static composition would need one slot per (history, product state); this needs none.  No counterpart in
+ * the reference.  The search is specified, not approximate.
+ * The lexicon: gb is torch_asg_amd.TokenGraph.from_lexicon compiled as for asg_beam_decode_graph with lm_weight 1 (automaton state
+ * 0 is the root; a word-end node has its one arc on `separator` to the root); word_of_state[s] is the id of the word that ends at
+ * automaton state s, -1 elsewhere.  The LM: H states, state 0 the empty history; row / word / next and lw describe the explicit
+ * arcs of each state (word ascending within a row), backoff / bw the backoff (backoff[0] = -1), ew the end of the sentence with the
+ * backoff resolved; every weight folded by the caller in the dtype of the problem (lw = fl(fl(lm_weight * logp) + word_score),
+ * bw = fl(lm_weight * bow), ew = fl(lm_weight * eos), -inf staying -inf): the device only adds.
+ *   step(h, w): a = 0; while w is not in row h: backoff[h] < 0 (or w < 0, or more than 64 backoff steps): rejected; else
+ *               a = a + bw[h], h = backoff[h].  Then a = a + lw[arc]: -> (next[arc], a).
+ * PAIR ORDER is h ascending, then q ascending; it takes the place of "q ascending" and "the smallest source index" in every
+ * rule of asg_beam_decode_graph.  All arithmetic is adds, one subtraction and comparisons in the dtype of the problem; -0 and +0
+ * are one value.  For utterance b with len = clamp(input_lengths[b], 0, T), a kept set A_t of pairs with values v_t:
+ *   t = 0:  for every q of start_q the pair (start, q) with c = start_w[q] + I[0][i(q)].
+ *   t >= 1: from every kept (h, q') with value v and label j: the stay gives (h, q') with v + tr[j][j]; an outgoing edge e to q
+ *           with label i != separator gives (h, q) with (v + tr[i][j]) + ow[e]; one with i == separator takes w =
+ *           word_of_state[state(q')], (h', a) = step(h, w), and gives (h', q) with ((v + tr[i][j]) + ow[e]) + a.  A rejected step
+ *           or a -inf value is no candidate.  Per target pair the largest candidate wins, the smallest source pair on a tie;
+ *           c = best + I[t][i].
+ *   prune:  asg_beam_decode_graph's rule: m = max c, lo = fl(m - beam_threshold); with the candidate pairs ordered by (c
+ *           descending, pair order), A_t = the first beam_size of them that also have c >= lo.
+ *   end:    end(h, q) = (v + final_w[q]) + endw, with endw = ew[h] when state(q) is the root, and, when state(q) ends a word w,
+ *           endw = a + ew[h'] for (h', a) = step(h, w) (rejected: no end); mid-word there is none.  scores[b] = the largest end
+ *           over A_{len-1}, the smallest pair on a tie.  len == 0, an empty last set, or no finite end: score -inf, every integer
+ *           output -1, no tokens, no words.
+ *   outputs: scores [B] (dtype); path, tokens, states, lm_states, words [B][T] int64, token_lengths, word_lengths [B] int64.
+ *           path / tokens / token_lengths / states as asg_beam_decode_graph; lm_states[b][t] = h of the winning path's pair at frame
+ *           t; words[b] = the word of every separator edge on the path, in order, then the word of the final step if the path
+ *           ends in a word-end node, -1 behind them; word_lengths[b] their count.
+ * K = beam_size (no clamp to Q: pairs are not bounded by Q).  `work` (asg_beam_decode_words_work_bytes), per utterance and every
+ * part rounded up to 256 bytes:
+ *   3 * T*K*4 (product state, LM state and source slot of every kept pair) + C*(16 + e) (an open-addressed table of C slots: key,
+ *   best candidate, its source; emptied by the kernel as it goes) + cap*(e + 12) (the pairs touched in a frame),
+ *   cap = max(K*(max_out+1), num_start), C = the power of two >= 2*cap, e = 4 / 8.  No term in H, V, A or Q.
+ * One launch, one workgroup per utterance; every output and all scratch is written by the kernel (no memset), so a captured call
+ * replays with new inputs.  Integer atomics only: bit-identical run to run, whatever the order in which pairs enter the table.
+ * Limits (ASG_ERR_UNSUPPORTED beyond): those of asg_viterbi_decode_graph, beam_size <= 8192, and H, Q <= 2^25 (a source pair and
+ * its slot are one 64-bit word), A < 2^31.  beam_size < 1, a negative or NaN beam_threshold, an LM of another dtype, start or
+ * separator out of range, a NULL array or output: ASG_ERR_INVALID.  Nothing of the graph or the LM is validated on the device.
+ * `flags` is reserved (pass 0). */
+typedef struct asg_word_lm {
+    int64_t H;                     /* history states                                                    */
+    int64_t A;                     /* explicit arcs                                                     */
+    int64_t V;                     /* words                                                             */
+    int64_t S;                     /* automaton states of the lexicon (entries of word_of_state)        */
+    int32_t start;                 /* the state after <s>                                               */
+    int32_t separator;             /* the token that ends a word                                        */
+    int32_t dtype;                 /* ASG_DTYPE_F32 / ASG_DTYPE_F64 of lw, bw, ew (= the problem's)     */
+    int32_t reserved;
+    const int32_t *row;            /* [H+1] offsets of the arcs of each state                           */
+    const int32_t *word;           /* [A] word of each arc, ascending within a row                      */
+    const int32_t *next;           /* [A] next state of each arc                                        */
+    const int32_t *backoff;        /* [H] backoff state, -1: none                                       */
+    const void *lw;                /* [A] folded arc weights                                            */
+    const void *bw;                /* [H] folded backoff weights                                        */
+    const void *ew;                /* [H] folded end-of-sentence weights, -inf: none                    */
+    const int32_t *word_of_state;  /* [S] word that ends at a lexicon state, -1: none                   */
+} asg_word_lm;
+size_t asg_beam_decode_words_work_bytes(const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm, int beam_size);
+int asg_beam_decode_words(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm, int beam_size,
+                          double beam_threshold, void *work, size_t work_bytes, void *scores, int64_t *path, int64_t *tokens,
+                          int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words, int64_t *word_lengths,
+                          int flags, void *stream);
+
 /* ---- Full score of the ASG lattice COMPOSED with a token automaton (the log-semiring counterpart of the decoder above), its
  * gradients, and the automaton's score of each target: the pieces of an ASG loss whose normaliser includes a token-level
  * prior.  No counterpart in the reference.  For utterance b with len = clamp(input_lengths[b], 0, T), in the dtype of the problem:

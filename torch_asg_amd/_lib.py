@@ -28,7 +28,8 @@ SYMBOLS = ["asg_hip_version", "asg_hip_strerror", "asg_ctx_create", "asg_ctx_des
            "asg_beam_graph_full_work_bytes", "asg_beam_graph_full_scratch_bytes", "asg_beam_graph_full_forward",
            "asg_beam_graph_full_backward", "asg_beam_decode_graph_nbest_work_bytes", "asg_beam_decode_graph_nbest",
            "asg_beam_stream_state_bytes", "asg_beam_stream_reset", "asg_beam_stream_advance", "asg_beam_stream_result",
-           "asg_beam_window_state_bytes", "asg_beam_window_reset", "asg_beam_window_advance", "asg_beam_window_result"]
+           "asg_beam_window_state_bytes", "asg_beam_window_reset", "asg_beam_window_advance", "asg_beam_window_result",
+           "asg_beam_decode_words_work_bytes", "asg_beam_decode_words"]
 ABI_VERSION = 230        # include/asg_hip.h: ASG_HIP_VERSION this package was written against
 
 
@@ -62,6 +63,12 @@ class AsgTokenGraphBeam(ctypes.Structure):
 class AsgTokenGraphBeamLoss(ctypes.Structure):
     _fields_ = [("beam", ctypes.POINTER(AsgTokenGraphBeam)), ("S", ctypes.c_int64), ("start", ctypes.c_int32),
                 ("reserved", ctypes.c_int32), ("next", ctypes.c_void_p)]
+
+
+class AsgWordLM(ctypes.Structure):
+    _fields_ = [("H", ctypes.c_int64), ("A", ctypes.c_int64), ("V", ctypes.c_int64), ("S", ctypes.c_int64),
+                ("start", ctypes.c_int32), ("separator", ctypes.c_int32), ("dtype", ctypes.c_int32), ("reserved", ctypes.c_int32)] + [
+                    (n, ctypes.c_void_p) for n in ("row", "word", "next", "backoff", "lw", "bw", "ew", "word_of_state")]
 
 
 _LIB = None
@@ -136,6 +143,10 @@ def lib():
     L.asg_beam_window_reset.argtypes = [vp, bp, i64, ci, i64, i64, vp, sz, vp, ci, vp]
     L.asg_beam_window_advance.argtypes = [vp, pp, bp, ci, ctypes.c_double, i64, i64, vp, sz, vp, vp, vp, vp, vp, ci, vp]
     L.asg_beam_window_result.argtypes = [vp, bp, i64, ci, i64, i64, vp, sz, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp]
+    wp = ctypes.POINTER(AsgWordLM)
+    L.asg_beam_decode_words_work_bytes.restype = sz
+    L.asg_beam_decode_words_work_bytes.argtypes = [pp, bp, wp, ci]
+    L.asg_beam_decode_words.argtypes = [vp, pp, bp, wp, ci, ctypes.c_double, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp]
     blp = ctypes.POINTER(AsgTokenGraphBeamLoss)
     L.asg_beam_graph_full_work_bytes.restype = sz
     L.asg_beam_graph_full_work_bytes.argtypes = [pp, blp, ci, ci]

@@ -391,6 +391,64 @@ class HipBackend:
         return self._decode_graph(inputs, transition, graph, input_lengths, max_work_bytes, view, work_bytes, call,
                                   "asg_beam_decode_graph")
 
+    def beam_decode_words(self, inputs, transition, lexicon, word_lm, input_lengths, beam_size, beam_threshold=float("inf"),
+                          lm_weight=1.0, word_score=0.0, token_score=0.0, max_work_bytes=1 << 30):
+        """Beam search over (LM history, lexicon product state) pairs -> BeamWords; see
+        include/asg_hip.h::asg_beam_decode_words.  Grouped under `max_work_bytes` as `_decode_graph` does."""
+        from . import wordlm as _wordlm
+        from . import graph as _graph
+        if not isinstance(lexicon, _wordlm.Lexicon):
+            raise TypeError("torch_asg_amd: lexicon must be a torch_asg_amd.Lexicon")
+        if not isinstance(word_lm, _wordlm.WordLM):
+            raise TypeError("torch_asg_amd: word_lm must be a torch_asg_amd.WordLM")
+        wmax = int(lexicon.word_of_state.max(initial=-1))
+        if wmax >= word_lm.V:
+            raise RuntimeError("torch_asg_amd: the lexicon has word id %d but the word LM knows %d words" % (wmax, word_lm.V))
+        beam_size, beam_threshold = min(int(beam_size), (1 << 31) - 1), float(beam_threshold)
+        L = _lib.lib()
+        self._check_decode_graph(inputs, transition, lexicon.graph, input_lengths)
+        T, B, N = inputs.shape
+        dev = inputs.device
+        with self._guard(dev):
+            lex = lexicon.compile_words(dev, inputs.dtype, token_score)
+            g = _graph.abi_graph_beam(lex)
+            w = _wordlm.abi_word_lm(word_lm.compile(dev, inputs.dtype, lm_weight, word_score), lex)
+            w.separator = lexicon.separator
+            p, keep = self._problem(inputs, transition, None, input_lengths, None)
+            if input_lengths is not None:
+                input_lengths = keep[-1]                       # (on the device, contiguous)
+
+            def work_bytes(nb):
+                p.B = nb
+                return int(L.asg_beam_decode_words_work_bytes(ctypes.byref(p), ctypes.byref(g), ctypes.byref(w), beam_size))
+            per = work_bytes(1)
+            if per == 0:                                       # the library refuses the arguments: its call says why
+                p.B = B
+                _lib.check(L.asg_beam_decode_words(None, ctypes.byref(p), ctypes.byref(g), ctypes.byref(w), beam_size,
+                                                   beam_threshold, None, 0, None, None, None, None, None, None, None, None, 0,
+                                                   None), "asg_beam_decode_words")
+            per = max(per, 1)
+            gsz = max(1, min(B, int(max_work_bytes) // per))
+            while gsz > 1 and work_bytes(gsz) > max_work_bytes:
+                gsz -= 1
+            work = self._buf(work_bytes(gsz), dev)
+            scores = torch.empty(B, dtype=inputs.dtype, device=dev)
+            out = torch.empty(5, B, T, dtype=torch.int64, device=dev)      # path, tokens, states, lm_states, words
+            lengths = torch.empty(2, B, dtype=torch.int64, device=dev)     # token_lengths, word_lengths
+            stream = self._stream(dev)
+            for b0 in range(0, B, gsz):
+                b1 = min(B, b0 + gsz)
+                p.inputs = inputs[:, b0:b1].data_ptr()
+                p.B = b1 - b0
+                if input_lengths is not None:
+                    p.input_lengths = input_lengths[b0:b1].data_ptr()
+                _lib.check(L.asg_beam_decode_words(
+                    None, ctypes.byref(p), ctypes.byref(g), ctypes.byref(w), beam_size, beam_threshold, work.data_ptr(),
+                    work.numel(), scores[b0:].data_ptr(), out[0, b0].data_ptr(), out[1, b0].data_ptr(), lengths[0, b0:].data_ptr(),
+                    out[2, b0].data_ptr(), out[3, b0].data_ptr(), out[4, b0].data_ptr(), lengths[1, b0:].data_ptr(), 0, stream),
+                    "asg_beam_decode_words")
+        return BeamWords(scores, out[0], out[1], lengths[0], out[2], out[3], out[4], lengths[1])
+
     def _check_decode_graph(self, inputs, transition, graph, input_lengths):
         """The argument checks of the graph decoders."""
         from . import graph as _graph
@@ -1020,6 +1078,49 @@ def beam_decode_graph(inputs, transition, graph, input_lengths=None, beam_size=2
     with torch.no_grad():
         return native().beam_decode_graph(inputs.detach(), transition.detach(), graph, input_lengths, beam_size, beam_threshold,
                                           lm_weight, token_score, max_work_bytes)
+
+
+BeamWords = collections.namedtuple("BeamWords", ["scores", "path", "tokens", "token_lengths", "states", "lm_states", "words",
+                                                 "word_lengths"])
+
+
+def beam_decode_words(inputs, transition, lexicon, word_lm, input_lengths=None, beam_size=256, beam_threshold=float("inf"),
+                      lm_weight=1.0, word_score=0.0, token_score=0.0, max_work_bytes=1 << 30):
+    """Beam decoding over the ASG lattice composed with a `Lexicon` and a word n-gram LM (`WordLM`), the LM composed on the fly:
+    the decoder for letter models with a word-level language model.  No gradient.
+
+    The search is `beam_decode_graph`'s over pairs (LM history h, product state q of `lexicon.graph`) that exist only while the
+    search holds them, so nothing is sized by the vocabulary, the LM or their product.  Inside a word the history stays; the
+    separator edge out of a word-end node walks the LM for that word -- backing off while the history has no arc for it, adding
+    lm_weight * bow per step, then lm_weight * logp + word_score -- and moves to the arc's next history.  The end adds
+    lm_weight * log p(</s> | h), after one more LM step when the path ends in a word-end node without its separator; a path
+    that ends mid-word does not count.  Every rule of `beam_decode_graph` holds with "pair order" (h, then q) in place of the
+    product-state index; the specification is include/asg_hip.h::asg_beam_decode_words.  token_score is added per token as in
+    `beam_decode_graph` (the lexicon graph is compiled with lm_weight 1, so `word_scores` of the lexicon count once).
+    Arithmetic is in the dtype of the emissions, weights folded on the host; float16 / bfloat16 emissions are widened to the
+    dtype of `transition`.  Results are bit-identical run to run.
+
+    Returns BeamWords(scores [B], path [B,T], tokens [B,T], token_lengths [B], states [B,T], lm_states [B,T], words [B,T],
+    word_lengths [B]): path, tokens, token_lengths and states as `beam_decode_graph`; lm_states the LM history at every frame;
+    words the word ids of the path in order, padded with -1.  An utterance of length 0, one whose beam dies out, or one
+    without a finite end has score -inf, every integer output -1 and no tokens or words.  beam_size < 1 and a negative or NaN
+    beam_threshold raise ValueError; beam_size > 8192 is refused by the library (there is no clamp: pairs are not bounded by the
+    number of product states).
+
+    Lexicon and LM are compiled for the device, dtype and weights on first use and cached on them; later calls copy nothing to
+    the device and do not synchronise, so they can be captured.  The batch is decoded in consecutive groups of utterances whose
+    workspace (about T * beam_size * 12 bytes of back-pointers plus 60-80 bytes per candidate a frame can have, beam_size *
+    (largest out-degree + 1)) fits `max_work_bytes`.
+    """
+    if int(beam_size) < 1:
+        raise ValueError("torch_asg_amd: beam_size must be >= 1, got %d" % int(beam_size))
+    if not float(beam_threshold) >= 0.0:
+        raise ValueError("torch_asg_amd: beam_threshold must be >= 0 (inf: none), got %r" % (beam_threshold,))
+    if inputs.dtype in (torch.float16, torch.bfloat16):
+        inputs = inputs.to(transition.dtype)
+    with torch.no_grad():
+        return native().beam_decode_words(inputs.detach(), transition.detach(), lexicon, word_lm, input_lengths, beam_size,
+                                          beam_threshold, lm_weight, word_score, token_score, max_work_bytes)
 
 
 BeamNbest = collections.namedtuple("BeamNbest", ["scores", "emission_scores", "graph_scores", "tokens", "token_lengths",
@@ -1701,6 +1802,13 @@ class ASGLoss(nn.Module):
         `torch_asg_amd.beam_decode_graph`."""
         return beam_decode_graph(inputs, self.transition, graph, input_lengths, beam_size, beam_threshold, lm_weight, token_score,
                                  max_work_bytes)
+
+    def beam_decode_words(self, inputs, lexicon, word_lm, input_lengths=None, beam_size=256, beam_threshold=float("inf"),
+                          lm_weight=1.0, word_score=0.0, token_score=0.0, max_work_bytes=1 << 30):
+        """Beam decoding with a lexicon and a word n-gram LM under this criterion's transitions; see
+        `torch_asg_amd.beam_decode_words`."""
+        return beam_decode_words(inputs, self.transition, lexicon, word_lm, input_lengths, beam_size, beam_threshold, lm_weight,
+                                 word_score, token_score, max_work_bytes)
 
     def beam_decode_graph_nbest(self, inputs, graph, input_lengths=None, beam_size=256, nbest=10, beam_threshold=float("inf"),
                                 lm_weight=1.0, token_score=0.0, return_alignments=False, max_work_bytes=1 << 30):

@@ -609,6 +609,51 @@ int asg_beam_decode_graph(asg_ctx *ctx, const asg_problem *p, const asg_token_gr
                                                              (hipStream_t) stream)));
 }
 
+static int check_beam_words(const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm, int beam_size) {
+    if (beam_size < 1) return ASG_ERR_INVALID;
+    int rc = check_beam_graph(p, gb, 1);                       // the graph's own checks: its beam clamps to Q, this one does not
+    if (rc) return rc;
+    if (!lm || lm->dtype != p->dtype || lm->H < 1 || lm->A < 0 || lm->V < 1 || lm->S < 1) return ASG_ERR_INVALID;
+    if (lm->start < 0 || lm->start >= lm->H || lm->separator < 0 || lm->separator >= p->N) return ASG_ERR_INVALID;
+    if (!lm->row || !lm->backoff || !lm->bw || !lm->ew || !lm->word_of_state) return ASG_ERR_INVALID;
+    if (lm->A > 0 && (!lm->word || !lm->next || !lm->lw)) return ASG_ERR_INVALID;
+    if (beam_size > kBeamMaxK || lm->H > kBeamWordMaxIndex || gb->graph->Q > kBeamWordMaxIndex || lm->A >= (int64_t) 1 << 31)
+        return ASG_ERR_UNSUPPORTED;
+    return ASG_OK;
+}
+
+size_t asg_beam_decode_words_work_bytes(const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm, int beam_size) {
+    if (check_beam_words(p, gb, lm, beam_size) != ASG_OK) return 0;
+    return beam_word_work_bytes(p->dtype == ASG_DTYPE_F64 ? 8 : 4, (int) p->T, (int) p->B, beam_size,
+                                beam_word_cap(beam_size, gb->max_out, (int) gb->num_start));
+}
+
+int asg_beam_decode_words(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm, int beam_size,
+                          double beam_threshold, void *work, size_t work_bytes, void *scores, int64_t *path, int64_t *tokens,
+                          int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words, int64_t *word_lengths,
+                          int flags, void *stream) {
+    (void) ctx; (void) flags;
+    int rc = check_beam_words(p, gb, lm, beam_size);
+    if (rc) return rc;
+    if (!(beam_threshold >= 0.0)) return ASG_ERR_INVALID;                  // negative or NaN
+    if (!work || !scores || !path || !tokens || !token_lengths || !states || !lm_states || !words || !word_lengths)
+        return ASG_ERR_INVALID;
+    if (work_bytes < asg_beam_decode_words_work_bytes(p, gb, lm, beam_size)) return ASG_ERR_WORKSPACE;
+    const Problem P = to_problem(p);
+    const GraphArgs G = to_graph_args(gb->graph);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    WordLmArgs LM{};
+    LM.H = (int) lm->H; LM.A = (int) lm->A; LM.start = lm->start; LM.sep = lm->separator;
+    LM.row = lm->row; LM.word = lm->word; LM.next = lm->next; LM.backoff = lm->backoff; LM.word_of_state = lm->word_of_state;
+    LM.lw = lm->lw; LM.bw = lm->bw; LM.ew = lm->ew;
+    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
+    long long *ls = (long long *) lm_states, *wd = (long long *) words, *wl = (long long *) word_lengths;
+    return hip_status(ASG_DISPATCH(p, launch_beam_words<float>(P, G, BG, LM, beam_size, beam_threshold, work, scores, pa, tk, tl,
+                                                               st, ls, wd, wl, (hipStream_t) stream),
+                                   launch_beam_words<double>(P, G, BG, LM, beam_size, beam_threshold, work, scores, pa, tk, tl,
+                                                             st, ls, wd, wl, (hipStream_t) stream)));
+}
+
 static int check_beam_nbest(const asg_problem *p, const asg_token_graph_beam *gb, int beam_size, int nbest) {
     int rc = check_beam_graph(p, gb, beam_size);
     if (rc) return rc;

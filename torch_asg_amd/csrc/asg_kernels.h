@@ -192,6 +192,25 @@ hipError_t launch_beam_graph(const Problem &P, const GraphArgs &G, const BeamGra
                              void *scores, long long *path, long long *tokens, long long *tlen, long long *states,
                              hipStream_t stream, size_t stride = 0, size_t cnt_off = 0, size_t fin_off = 0);
 
+// ---- Beam decoding with a lexicon and a word LM composed on the fly (asg_beam_word.hip): asg_beam_decode_words.  The search
+// state is a pair (LM state h, product state q of the lexicon automaton).  K = beam_size (no clamp to Q); the touched list holds
+// cap = beam_word_cap(..) target pairs; the table has C slots, the power of two >= 2 * cap.  Work, per utterance and each part
+// 256-byte aligned: int32 [T][K] product states, LM states and source slots, u64 key [C], u64 arg [C], key val [C], key [cap],
+// u64 pair [cap], int32 touched [cap].
+struct WordLmArgs {
+    int H, A, start, sep;
+    const int *row, *word, *next, *backoff;   // [H+1], [A], [A], [H]
+    const int *word_of_state;                 // [S] of the lexicon automaton
+    const void *lw, *bw, *ew;                 // [A], [H], [H] folded, in the dtype of the problem
+};
+constexpr int kBeamWordMaxIndex = 1 << 25;    // H, Q: (source pair, source slot) is one 64-bit word
+int beam_word_cap(int K, int max_out, int num_start);
+size_t beam_word_work_bytes(int elem, int T, int B, int K, int cap);
+template <typename R>
+hipError_t launch_beam_words(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int K,
+                             double theta, void *work, void *scores, long long *path, long long *tokens, long long *tlen,
+                             long long *states, long long *lm_states, long long *words, long long *wlen, hipStream_t stream);
+
 // ---- The same search carried across chunks of frames (asg_beam_stream.hip): asg_beam_stream_*.  One slot of the state (byte
 // offsets, each part 256-byte aligned): the beam search's own layout for T = max_frames at the front, then hdr (int32 pos, |A|,
 // overflow) and the stored set (values [K], then int32 product states [K]).
