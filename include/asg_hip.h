@@ -475,6 +475,67 @@ int asg_beam_decode_words(asg_ctx *ctx, const asg_problem *p, const asg_token_gr
                           int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words, int64_t *word_lengths,
                           int flags, void *stream);
 
+/* ---- STREAMING beam decoding with a lexicon and a word n-gram LM: the search of asg_beam_decode_words over pairs (h, q) carried
+ * across chunks of frames, as asg_beam_stream_* carries the search of asg_beam_decode_graph -- the growing stream, bounded by
+ * max_frames.  A live transcription service gets a word LM and a transcript while the utterance is still arriving.  No counterpart
+ * in the reference.  gb and lm are those of asg_beam_decode_words (the weights folded by the caller).
+ * A WORD STREAM STATE is one device buffer that serves B utterance slots, for a fixed lexicon, LM shape, dtype, K = beam_size (no
+ * clamp to Q) and max_frames (every call on a state passes the same gb, lm, B, beam_size and max_frames).  Per slot it holds:
+ * pos, the frames consumed so far; the kept set A_{pos-1} of pairs with its values; the back-pointers (product state, LM state,
+ * source slot) of the frames 0 .. pos-1; a sticky overflow word; and the table and lists of the search.  The contents are opaque;
+ * a state must be reset before its first use.
+ *   asg_beam_word_stream_reset: for every slot b with mask[b] != 0 (one byte per slot on the device; NULL: every slot): pos = 0,
+ *     the set empty, overflow = 0, and all C slots of the table emptied (the only place where all of them are written: a frame
+ *     empties what it touched).  Written by a kernel.
+ *   asg_beam_word_stream_advance: p->inputs is a chunk [Tc = p->T, B, N] (any strides) and p->input_lengths the chunk's lengths
+ *     (NULL: Tc for every slot); p->transition and beam_threshold are used for the frames of this call (they may differ between
+ *     calls).  For slot b: n = min(clamp(input_lengths[b], 0, Tc), max_frames - pos).  If the bound by max_frames cut anything,
+ *     overflow = 1; the frames beyond it are not consumed and nothing is written out of bounds.  The chunk's frames 0 .. n-1 are
+ *     the frames pos .. pos+n-1 of the utterance and run exactly the rules of asg_beam_decode_words -- the same adds in the same
+ *     order, the same LM walk, the same pair order in every tie, the same prune; the same device code: frame 0 of the utterance
+ *     takes the pairs (start, q) of start_q, every other frame -- the first frame of a chunk included, LM walk and all -- its
+ *     candidates from the stored set; an empty set stays empty.  Then pos += n (also for an empty set).  Nothing is written
+ *     besides the state.  Tc = 0 is allowed and changes nothing.
+ *   asg_beam_word_stream_result: reads the state and does not modify it; it may be called after any chunk, and the stream
+ *     continues.  With L = pos and A = A_{L-1} with values v:
+ *       final != 0: the end of asg_beam_decode_words: end(h, q) = (v + final_w[q]) + endw, endw = ew[h] at the root, a + ew[h'] after
+ *                   one more LM step in a word-end node (rejected: no end), no end mid-word; the word of that step is appended to
+ *                   words.
+ *       final == 0: end(h, q) = v, the best PREFIX hypothesis: no final weight, no LM end, no final word.  A prefix that ends
+ *                   mid-word is a valid prefix; words holds the words of the separator edges on the path only.
+ *     The winner is the pair of A with the largest end > -inf, the smallest pair on a tie (-0 and +0 are equal).  scores [B]
+ *     (dtype) = its end; path, tokens, states, lm_states, words [B][max_frames] int64 follow its back-pointers as in
+ *     asg_beam_decode_words, -1 behind the data; token_lengths, word_lengths [B]; frames [B] = L; status [B] = the overflow word
+ *     (0 / 1).  L == 0, an empty set or no finite end: score -inf, every integer array -1, both lengths 0.
+ * REQUIRED PROPERTY.  Take a slot that was reset and then advanced by any sequence of chunks that concatenate to x[0:L],
+ * L <= max_frames (chunks of no frames included).  asg_beam_word_stream_result(final = 1) then equals asg_beam_decode_words on x
+ * with T >= L frames, input_length = L, the same transition, beam_size, beam_threshold, folding and dtype: scores, token_lengths
+ * and word_lengths bit for bit; path, tokens, states, lm_states and words equal on the columns < T and -1 elsewhere.  No
+ * tolerance: the search over pairs never looks ahead, and the LM walk depends on the source pair alone.
+ * State (asg_beam_word_stream_state_bytes; 0 for arguments that the calls refuse), every part rounded up to 256 bytes:
+ *   B * (asg_beam_decode_words' bytes per utterance with T = max_frames + 256 (pos, set size, overflow) + K*(e + 8) (the stored
+ *   set: values, then product states, then LM states)), e = 4 / 8.  The back-pointers keep asg_beam_decode_words' [frame][K]
+ *   layout -- the source slots of all kept pairs, not only the winner's, as an n-best over pairs would need.  No term in H, V, A
+ *   or Q.
+ * Each call is ONE launch on `stream`, one 1024-thread workgroup per slot for advance and result: no host synchronisation, no
+ * copy, no memset, so a captured call replays with new chunk contents and lengths, and a capture is one linear chain.  Integer
+ * atomics only: bit-identical run to run.  Limits and errors: those of asg_beam_decode_words with T = max_frames (beam_size <=
+ * 8192, H, Q <= 2^25, A < 2^31; ASG_ERR_UNSUPPORTED beyond) and those of asg_beam_stream_*: max_frames < 1, Tc < 0, B < 1,
+ * beam_size < 1, a negative or NaN beam_threshold, a dtype that is not the graph's and the LM's, a NULL array or output:
+ * ASG_ERR_INVALID; a state buffer smaller than asg_beam_word_stream_state_bytes: ASG_ERR_WORKSPACE.  Not here: the windowed form
+ * with a committed prefix, n-best over pairs, a loss over pairs, LM look-ahead.  `flags` is reserved (pass 0). */
+size_t asg_beam_word_stream_state_bytes(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype, int beam_size,
+                                        int64_t max_frames);
+int asg_beam_word_stream_reset(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
+                               int64_t max_frames, void *state, size_t state_bytes, const uint8_t *mask, int flags, void *stream);
+int asg_beam_word_stream_advance(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                 int beam_size, double beam_threshold, int64_t max_frames, void *state, size_t state_bytes,
+                                 int flags, void *stream);
+int asg_beam_word_stream_result(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
+                                int64_t max_frames, const void *state, size_t state_bytes, int final, void *scores, int64_t *path,
+                                int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words,
+                                int64_t *word_lengths, int64_t *frames, int64_t *status, int flags, void *stream);
+
 /* ---- Full score of the ASG lattice COMPOSED with a token automaton (the log-semiring counterpart of the decoder above), its
  * gradients, and the automaton's score of each target: the pieces of an ASG loss whose normaliser includes a token-level
  * prior.  No counterpart in the reference.  For utterance b with len = clamp(input_lengths[b], 0, T), in the dtype of the problem:

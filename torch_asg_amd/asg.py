@@ -1284,6 +1284,155 @@ class BeamStream:
         return BeamStreamResult(scores, out[0], out[1], small[0], out[2], small[1], small[2])
 
 
+BeamWordStreamResult = collections.namedtuple("BeamWordStreamResult", ["scores", "path", "tokens", "token_lengths", "states",
+                                                                       "lm_states", "words", "word_lengths", "frames", "status"])
+
+
+class BeamWordStream:
+    """`beam_decode_words` for an utterance that arrives in chunks: the beam search over pairs (LM history, lexicon product
+    state), the word LM composed on the fly, carried from one chunk to the next for `batch_size` utterance slots at a time.
+    No gradient.
+
+        s = BeamWordStream(transition, lexicon, word_lm, batch_size, max_frames, beam_size=256)
+        for chunk in chunks:                 # [Tc, B, N] each
+            s.advance(chunk)
+            partial = s.result()             # the best prefix hypothesis so far, its words included; the stream goes on
+        final = s.result(final=True)         # what beam_decode_words returns for the whole utterance, bit for bit
+
+    The search is `beam_decode_words`', frame by frame, with the same device code
+    (include/asg_hip.h::asg_beam_word_stream_advance): for any way of cutting an utterance of at most `max_frames` frames into
+    chunks, `result(final=True)` equals the one-shot decode of the whole utterance -- scores, token_lengths and word_lengths bit
+    for bit, path / tokens / states / lm_states / words on the one-shot's columns and -1 beyond.  `transition` (a tensor or
+    Parameter of dtype `dtype`; it is read again at every `advance`), `beam_threshold`, `lm_weight`, `word_score` and
+    `token_score` are those of `beam_decode_words`; the attribute `beam_threshold` may be changed between chunks.  beam_size >
+    8192 is refused by the library (there is no clamp to the number of product states).
+
+    The state lives in one device buffer (about max_frames * beam_size * 12 bytes of back-pointers plus 60-80 bytes per
+    candidate a frame can have, per slot; nothing is sized by the vocabulary or the LM).  Lexicon and LM are compiled in the
+    constructor; `advance`, `result` and `reset` are one kernel launch each, copy nothing and do not synchronise, so they can be
+    captured in a graph and replayed with new chunk contents and lengths.  Not here: a windowed form with a committed prefix
+    (`BeamWindowStream` over pairs), n-best over pairs, a loss over pairs, LM look-ahead.
+    """
+
+    def __init__(self, transition, lexicon, word_lm, batch_size, max_frames, beam_size=256, beam_threshold=float("inf"),
+                 lm_weight=1.0, word_score=0.0, token_score=0.0, dtype=torch.float32, device=None):
+        from . import graph as _graph
+        from . import wordlm as _wordlm
+        _check_beam(beam_size, beam_threshold)
+        if not isinstance(lexicon, _wordlm.Lexicon):
+            raise TypeError("torch_asg_amd: lexicon must be a torch_asg_amd.Lexicon")
+        if not isinstance(word_lm, _wordlm.WordLM):
+            raise TypeError("torch_asg_amd: word_lm must be a torch_asg_amd.WordLM")
+        wmax = int(lexicon.word_of_state.max(initial=-1))
+        if wmax >= word_lm.V:
+            raise RuntimeError("torch_asg_amd: the lexicon has word id %d but the word LM knows %d words" % (wmax, word_lm.V))
+        if int(batch_size) < 1 or int(max_frames) < 1:
+            raise ValueError("torch_asg_amd: batch_size and max_frames must be >= 1, got %d and %d"
+                             % (int(batch_size), int(max_frames)))
+        if dtype not in (torch.float32, torch.float64):
+            raise RuntimeError("torch_asg_amd: expected scalar type Float or Double but found %s" % dtype)
+        device = torch.device(device) if device is not None else transition.device
+        if device.type != "cuda":
+            raise RuntimeError("torch_asg_amd: a BeamWordStream must live on a ROCm device (got %s); "
+                               "there is no CPU implementation in this package" % device)
+        graph = lexicon.graph
+        if transition.dtype != dtype or transition.device != device or tuple(transition.shape) != (graph.N, graph.N):
+            raise RuntimeError("torch_asg_amd: transition must be [%d,%d] with the dtype/device of the stream" % (graph.N, graph.N))
+        self.transition, self.lexicon, self.word_lm, self.graph = transition, lexicon, word_lm, graph
+        self.batch_size, self.max_frames = int(batch_size), int(max_frames)
+        self.beam_size, self.beam_threshold = min(int(beam_size), (1 << 31) - 1), float(beam_threshold)
+        self.lm_weight, self.word_score, self.token_score = lm_weight, word_score, token_score
+        self.dtype, self.device = dtype, device
+        be = native()
+        L = _lib.lib()
+        with be._guard(device):
+            self._lex = lexicon.compile_words(device, dtype, token_score)
+            self._g = _graph.abi_graph_beam(self._lex)
+            self._lm = word_lm.compile(device, dtype, lm_weight, word_score)
+            self._w = _wordlm.abi_word_lm(self._lm, self._lex)
+            self._w.separator = lexicon.separator
+            abi_dtype = _lib.ASG_DTYPE_F32 if dtype == torch.float32 else _lib.ASG_DTYPE_F64
+            nbytes = int(L.asg_beam_word_stream_state_bytes(ctypes.byref(self._g), ctypes.byref(self._w), self.batch_size,
+                                                            abi_dtype, self.beam_size, self.max_frames))
+            if nbytes == 0:                                    # the library refuses the arguments: its call says why
+                _lib.check(L.asg_beam_word_stream_reset(None, ctypes.byref(self._g), ctypes.byref(self._w), self.batch_size,
+                                                        self.beam_size, self.max_frames, None, 0, None, 0, None),
+                           "asg_beam_word_stream_reset")
+            self._state = be._buf(nbytes, device)
+        self._fed = 0                                          # frames offered since the last full reset (the host's bound)
+        self.reset()
+
+    def reset(self, mask=None):
+        """Start new utterances: in every slot (mask None), or in the slots where `mask` (bool or integer [B]) is not zero --
+        the other slots go on.  After a masked reset `advance`'s host-side check of `max_frames` is not tightened; the device
+        clamps and `result().status` reports it."""
+        be = native()
+        L = _lib.lib()
+        m = None
+        if mask is not None:
+            if tuple(mask.shape) != (self.batch_size,):
+                raise RuntimeError("torch_asg_amd: mask must have shape [%d]" % self.batch_size)
+            m = mask.to(self.device).ne(0).to(torch.uint8).contiguous()
+        with be._guard(self.device):
+            _lib.check(L.asg_beam_word_stream_reset(None, ctypes.byref(self._g), ctypes.byref(self._w), self.batch_size,
+                                                    self.beam_size, self.max_frames, self._state.data_ptr(), self._state.numel(),
+                                                    m.data_ptr() if m is not None else None, 0, be._stream(self.device)),
+                       "asg_beam_word_stream_reset")
+        if mask is None:
+            self._fed = 0
+
+    def advance(self, chunk, chunk_lengths=None):
+        """Consume `chunk` [Tc, B, N]: slot b takes its first clamp(chunk_lengths[b], 0, Tc) frames (all Tc when
+        `chunk_lengths` is None) as the next frames of its utterance.  Chunk dtype, strides and float16 / bfloat16 widening as in
+        `beam_decode_words`.  ValueError, without touching the device, once the Tc offered since the last full `reset()` exceed
+        `max_frames`."""
+        be = native()
+        L = _lib.lib()
+        transition = self.transition.detach()
+        if chunk.dtype in (torch.float16, torch.bfloat16):
+            chunk = chunk.to(transition.dtype)
+        chunk = chunk.detach()
+        be._check_decode_graph(chunk, transition, self.graph, chunk_lengths)
+        Tc, B, N = chunk.shape
+        if chunk.dtype != self.dtype or chunk.device != self.device or B != self.batch_size:
+            raise RuntimeError("torch_asg_amd: the stream takes chunks [Tc,%d,%d] of %s on %s, got %s of %s on %s"
+                               % (self.batch_size, N, self.dtype, self.device, tuple(chunk.shape), chunk.dtype, chunk.device))
+        _check_beam(self.beam_size, self.beam_threshold)
+        if self._fed + Tc > self.max_frames:
+            raise ValueError("torch_asg_amd: %d frames since the last reset() plus a chunk of %d exceed max_frames = %d"
+                             % (self._fed, Tc, self.max_frames))
+        with be._guard(self.device):
+            p, keep = be._problem(chunk, transition, None, chunk_lengths, None)
+            _lib.check(L.asg_beam_word_stream_advance(None, ctypes.byref(p), ctypes.byref(self._g), ctypes.byref(self._w),
+                                                      self.beam_size, float(self.beam_threshold), self.max_frames,
+                                                      self._state.data_ptr(), self._state.numel(), 0, be._stream(self.device)),
+                       "asg_beam_word_stream_advance")
+        self._fed += Tc
+
+    def result(self, final=False):
+        """The best hypothesis of every slot over the frames consumed so far, without changing the state -> a named tuple
+          scores [B]; path, tokens, states, lm_states, words [B, max_frames] int64, -1 behind the data; token_lengths,
+          word_lengths [B]; frames [B], the frames consumed; status [B], 1 where frames beyond max_frames were offered and dropped.
+        final=True is the end of `beam_decode_words` (final weight, the LM's end of the sentence, after one more LM step for a
+        path that ends in a word-end node, whose word is appended; a path that ends mid-word does not count).  final=False is the
+        best prefix hypothesis, the largest value without any end term: it may end mid-word, and `words` holds the words whose
+        separator the path has passed.  A slot without frames, with an empty beam or without a finite score: -inf, -1, 0."""
+        be = native()
+        L = _lib.lib()
+        B, T, dev = self.batch_size, self.max_frames, self.device
+        with be._guard(dev):
+            scores = torch.empty(B, dtype=self.dtype, device=dev)
+            out = torch.empty(5, B, T, dtype=torch.int64, device=dev)          # path, tokens, states, lm_states, words
+            small = torch.empty(4, B, dtype=torch.int64, device=dev)           # token_lengths, word_lengths, frames, status
+            _lib.check(L.asg_beam_word_stream_result(None, ctypes.byref(self._g), ctypes.byref(self._w), B, self.beam_size, T,
+                                                     self._state.data_ptr(), self._state.numel(), 1 if final else 0,
+                                                     scores.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), small[0].data_ptr(),
+                                                     out[2].data_ptr(), out[3].data_ptr(), out[4].data_ptr(), small[1].data_ptr(),
+                                                     small[2].data_ptr(), small[3].data_ptr(), 0, be._stream(dev)),
+                       "asg_beam_word_stream_result")
+        return BeamWordStreamResult(scores, out[0], out[1], small[0], out[2], out[3], out[4], small[1], small[2], small[3])
+
+
 BeamWindowCommit = collections.namedtuple("BeamWindowCommit", ["path", "states", "tokens", "token_lengths", "frames"])
 BeamWindowResult = collections.namedtuple("BeamWindowResult", ["scores", "path", "tokens", "token_lengths", "states", "frames",
                                                                "committed", "status"])
@@ -1823,6 +1972,13 @@ class ASGLoss(nn.Module):
         `torch_asg_amd.BeamStream`."""
         return BeamStream(self.transition, graph, batch_size, max_frames, beam_size, beam_threshold, lm_weight, token_score,
                           self.transition.dtype, self.transition.device)
+
+    def beam_word_stream(self, lexicon, word_lm, batch_size, max_frames, beam_size=256, beam_threshold=float("inf"), lm_weight=1.0,
+                         word_score=0.0, token_score=0.0):
+        """A streaming beam decoder with a lexicon and a word n-gram LM under this module's transition matrix (read again at
+        every chunk): see `torch_asg_amd.BeamWordStream`."""
+        return BeamWordStream(self.transition, lexicon, word_lm, batch_size, max_frames, beam_size, beam_threshold, lm_weight,
+                              word_score, token_score, self.transition.dtype, self.transition.device)
 
     def beam_window_stream(self, graph, batch_size, window, commit_every=None, beam_size=256, beam_threshold=float("inf"),
                            lm_weight=1.0, token_score=0.0):

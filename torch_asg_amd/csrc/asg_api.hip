@@ -770,6 +770,99 @@ int asg_beam_stream_result(asg_ctx *ctx, const asg_token_graph_beam *gb, int64_t
                                                                      tk, tl, st, fr, su, (hipStream_t) stream)));
 }
 
+static WordLmArgs to_word_lm_args(const asg_word_lm *lm) {
+    WordLmArgs LM{};
+    LM.H = (int) lm->H; LM.A = (int) lm->A; LM.start = lm->start; LM.sep = lm->separator;
+    LM.row = lm->row; LM.word = lm->word; LM.next = lm->next; LM.backoff = lm->backoff; LM.word_of_state = lm->word_of_state;
+    LM.lw = lm->lw; LM.bw = lm->bw; LM.ew = lm->ew;
+    return LM;
+}
+
+// A word stream state is sized like a problem of max_frames frames, as a stream state is: the checks of asg_beam_decode_words
+// through a problem of that shape (there is no clamp of the beam to Q).
+static int check_beam_word_stream(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype, int beam_size,
+                                  int64_t max_frames) {
+    if (!gb || !gb->graph) return ASG_ERR_INVALID;
+    asg_problem q{};
+    q.inputs = gb; q.transition = gb;
+    q.T = max_frames; q.B = B; q.N = gb->graph->N; q.S = 1; q.dtype = dtype;
+    return check_beam_words(&q, gb, lm, beam_size);
+}
+
+static size_t beam_word_stream_bytes(const asg_token_graph_beam *gb, int64_t B, int dtype, int beam_size, int64_t max_frames) {
+    return beam_word_stream_state_bytes(dtype == ASG_DTYPE_F64 ? 8 : 4, (int) max_frames, (int) B, beam_size,
+                                        beam_word_cap(beam_size, gb->max_out, (int) gb->num_start));
+}
+
+size_t asg_beam_word_stream_state_bytes(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype, int beam_size,
+                                        int64_t max_frames) {
+    if (check_beam_word_stream(gb, lm, B, dtype, beam_size, max_frames) != ASG_OK) return 0;
+    return beam_word_stream_bytes(gb, B, dtype, beam_size, max_frames);
+}
+
+int asg_beam_word_stream_reset(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
+                               int64_t max_frames, void *state, size_t state_bytes, const uint8_t *mask, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    if (!gb || !gb->graph) return ASG_ERR_INVALID;
+    const int dtype = gb->graph->dtype;
+    int rc = check_beam_word_stream(gb, lm, B, dtype, beam_size, max_frames);
+    if (rc) return rc;
+    if (!state) return ASG_ERR_INVALID;
+    if (state_bytes < beam_word_stream_bytes(gb, B, dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
+    return hip_status(launch_beam_word_stream_reset(dtype == ASG_DTYPE_F64 ? 8 : 4, to_beam_graph_args(gb), beam_size,
+                                                    (int) max_frames, (int) B, state, mask, (hipStream_t) stream));
+}
+
+int asg_beam_word_stream_advance(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                 int beam_size, double beam_threshold, int64_t max_frames, void *state, size_t state_bytes,
+                                 int flags, void *stream) {
+    (void) ctx; (void) flags;
+    if (!p) return ASG_ERR_INVALID;
+    int rc = check_beam_word_stream(gb, lm, p->B, p->dtype, beam_size, max_frames);
+    if (rc) return rc;
+    if (p->T < 0 || p->N != gb->graph->N) return ASG_ERR_INVALID;
+    if (p->T > 0 && (rc = check_beam_words(p, gb, lm, beam_size)) != ASG_OK) return rc;
+    if (!(beam_threshold >= 0.0)) return ASG_ERR_INVALID;                  // negative or NaN
+    if (!state) return ASG_ERR_INVALID;
+    if (state_bytes < beam_word_stream_bytes(gb, p->B, p->dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
+    if (p->T == 0) return ASG_OK;                                          // no frame: the state stays as it is
+    const Problem P = to_problem(p);
+    const GraphArgs G = to_graph_args(gb->graph);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    const WordLmArgs LM = to_word_lm_args(lm);
+    return hip_status(ASG_DISPATCH(p, launch_beam_word_stream_advance<float>(P, G, BG, LM, beam_size, beam_threshold,
+                                                                             (int) max_frames, state, (hipStream_t) stream),
+                                   launch_beam_word_stream_advance<double>(P, G, BG, LM, beam_size, beam_threshold,
+                                                                           (int) max_frames, state, (hipStream_t) stream)));
+}
+
+int asg_beam_word_stream_result(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
+                                int64_t max_frames, const void *state, size_t state_bytes, int final, void *scores, int64_t *path,
+                                int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words,
+                                int64_t *word_lengths, int64_t *frames, int64_t *status, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    if (!gb || !gb->graph) return ASG_ERR_INVALID;
+    const asg_token_graph *g = gb->graph;
+    int rc = check_beam_word_stream(gb, lm, B, g->dtype, beam_size, max_frames);
+    if (rc) return rc;
+    if (!state || !scores || !path || !tokens || !token_lengths || !states || !lm_states || !words || !word_lengths || !frames ||
+        !status)
+        return ASG_ERR_INVALID;
+    if (state_bytes < beam_word_stream_bytes(gb, B, g->dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
+    const GraphArgs G = to_graph_args(g);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    const WordLmArgs LM = to_word_lm_args(lm);
+    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
+    long long *ls = (long long *) lm_states, *wd = (long long *) words, *wl = (long long *) word_lengths;
+    long long *fr = (long long *) frames, *su = (long long *) status;
+    return hip_status(ASG_DISPATCH(g, launch_beam_word_stream_result<float>(G, BG, LM, beam_size, (int) max_frames, (int) B, state,
+                                                                            final, scores, pa, tk, tl, st, ls, wd, wl, fr, su,
+                                                                            (hipStream_t) stream),
+                                   launch_beam_word_stream_result<double>(G, BG, LM, beam_size, (int) max_frames, (int) B, state,
+                                                                          final, scores, pa, tk, tl, st, ls, wd, wl, fr, su,
+                                                                          (hipStream_t) stream)));
+}
+
 // A window stream state is sized like a problem of W frames (the ring); P is the commit period.
 static int check_beam_window(const asg_token_graph_beam *gb, int64_t B, int dtype, int beam_size, int64_t W, int64_t P) {
     if (W < 1 || P < 1 || P > W) return ASG_ERR_INVALID;

@@ -25,392 +25,11 @@
 #include "asg_common.h"
 #include "asg_kernels.h"
 #include "asg_beam_common.h"
-#include "asg_beam_frame.h"       // Ctl, find_digit, wave_append, collapse_tokens, dev_load / dev_store
+#include "asg_beam_word_frame.h"  // the frame and the end: the streaming decoder (asg_beam_word_stream.hip) compiles the same text
 
 namespace asg {
 
 namespace {
-
-constexpr int kWordSlotBits = 14;            // arg = source pair << 14 | source slot: K <= 8192 < 2^14, a pair < 2^50
-constexpr int kMaxBackoff = 64;              // an LM walk of more backoff steps rejects (no loop without a bound)
-constexpr size_t kWordCtlOff = 3072;         // WordCtl behind Ctl inside the fixed LDS
-static_assert(sizeof(Ctl<unsigned long long>) <= kWordCtlOff, "control block");
-
-struct WordCtl {
-    unsigned long long ppre, pcut;           // tie select over pairs: the digits fixed so far, the largest pair taken
-    unsigned long long rkey[kBT / 64], rpair[kBT / 64];
-    int rk[kBT / 64];
-};
-static_assert(kWordCtlOff + sizeof(WordCtl) <= kFixedLds, "control block");
-
-__device__ __forceinline__ int bits_of(int n) { return 32 - __clz(n > 1 ? n - 1 : 1); }   // >= 1
-
-template <typename R>
-struct BeamWordFrame {
-    using U = typename Key<R>::U;
-    Ctl<U> *ctl;
-    WordCtl *wctl;
-    R *cur_v;                    // LDS [K] values of the kept set
-    int *cur_q, *cur_h;          // LDS [K] its pairs
-    const R *trs;                // LDS [N][N] transitions (TRL)
-    const R *tr;                 // ... or in global memory
-    int64_t ts0, ts1;
-    int N, K, G, cap, sep;
-    int qbits, pbits;            // pair = h << qbits | q, pbits = hbits + qbits <= 50
-    R theta;
-    const int *label, *state, *orow, *start_q;
-    int num_start;
-    const int2 *oarc;
-    const R *ow, *sw;
-    // the word LM, weights folded
-    const int *lrow, *lword, *lnext, *lback, *wos;
-    const R *lw, *bw, *ew;
-    int lstart;
-    // the utterance's workspace
-    unsigned long long *tkey;    // [C] the table's keys: pair + 1, 0 = empty
-    unsigned long long *arg;     // [C]
-    U *val;                      // [C]
-    int tbits;                   // C = 1 << tbits
-    U *ckey;                     // [cap]
-    unsigned long long *cpair;   // [cap]
-    int *tl;                     // [cap] the touched slots
-
-    __device__ __forceinline__ void bind_work(char *wb, int T, int *&bq, int *&bh, int *&bs) {
-        const size_t a256 = 255, C = (size_t) 1 << tbits;
-        size_t off = 0;
-        bq = (int *) (wb + off);  off += ((size_t) T * K * 4 + a256) & ~a256;       // [T][K] product state of each slot
-        bh = (int *) (wb + off);  off += ((size_t) T * K * 4 + a256) & ~a256;       // [T][K] its LM state
-        bs = (int *) (wb + off);  off += ((size_t) T * K * 4 + a256) & ~a256;       // [T][K] its source's slot at t-1
-        tkey = (unsigned long long *) (wb + off);  off += (C * 8 + a256) & ~a256;
-        arg = (unsigned long long *) (wb + off);   off += (C * 8 + a256) & ~a256;
-        val = (U *) (wb + off);     off += (C * sizeof(U) + a256) & ~a256;
-        ckey = (U *) (wb + off);    off += ((size_t) cap * sizeof(U) + a256) & ~a256;
-        cpair = (unsigned long long *) (wb + off);  off += ((size_t) cap * 8 + a256) & ~a256;
-        tl = (int *) (wb + off);
-    }
-    __device__ __forceinline__ unsigned long long pair(int h, int q) const {
-        return ((unsigned long long) (unsigned) h << qbits) | (unsigned) q;
-    }
-    __device__ __forceinline__ unsigned home(unsigned long long key) const {
-        return (unsigned) ((key * 0x9E3779B97F4A7C15ull) >> (64 - tbits));
-    }
-    // The slot of `key`, inserted if it is not there (`fresh`: by this lane); -1 if the table is full (it cannot be: C >= 2 * cap).
-    __device__ __forceinline__ int insert(unsigned long long key, bool &fresh) const {
-        const unsigned mask = (1u << tbits) - 1u;
-        unsigned s = home(key);
-        for (unsigned p = 0; p <= mask; ++p) {
-            unsigned long long k = dev_load(tkey + s);
-            if (k == 0) {
-                k = atomicCAS(tkey + s, 0ull, key);
-                if (k == 0) { fresh = true; return (int) s; }
-            }
-            if (k == key) return (int) s;
-            s = (s + 1) & mask;
-        }
-        return -1;
-    }
-    __device__ __forceinline__ int find(unsigned long long key) const {
-        const unsigned mask = (1u << tbits) - 1u;
-        unsigned s = home(key);
-        for (unsigned p = 0; p <= mask; ++p) {
-            const unsigned long long k = dev_load(tkey + s);
-            if (k == key) return (int) s;
-            if (k == 0) return -1;
-            s = (s + 1) & mask;
-        }
-        return -1;
-    }
-    // The LM walk: word w after state h -> (h2, a = 0 + bw per backoff step + lw of the arc), adds in walk order; false: rejected.
-    __device__ __forceinline__ bool step(int h, int w, int &h2, R &a) const {
-        a = (R) 0;
-        if (w < 0) return false;
-        for (int n = 0; n <= kMaxBackoff; ++n) {
-            int lo = lrow[h];
-            const int end = lrow[h + 1];
-            int hi = end;
-            while (lo < hi) {
-                const int mid = (int) (((unsigned) lo + (unsigned) hi) >> 1);
-                if (lword[mid] < w) lo = mid + 1; else hi = mid;
-            }
-            if (lo < end && lword[lo] == w) { a = a + lw[lo]; h2 = lnext[lo]; return true; }
-            const int bo = lback[h];
-            if (bo < 0) return false;
-            a = a + bw[h];
-            h = bo;
-        }
-        return false;
-    }
-};
-
-// One frame: from the kept set (f.cur_h, f.cur_q, f.cur_v)[0..na) of the frame before -- or, with `first`, from the start states
-// -- to the new one, with (q, h, source slot) of every kept pair into row `row` of the [.][K] lists bq / bh / bs.  `xt` are the
-// frame's emissions (stride is2).  The whole workgroup calls it; it begins after and ends with a __syncthreads.  The table is
-// empty again on return (a first frame does not use it), f.ctl->na holds the new count and f.ctl->n is 0.
-template <typename R, bool TRL>
-__device__ __forceinline__ void beam_word_frame(const BeamWordFrame<R> &f, bool first, int na, const R *xt, int64_t is2, int *bq,
-                                                int *bh, int *bs, int row) {
-    using KT = Key<R>;
-    using U = typename KT::U;
-    Ctl<U> &ctl = *f.ctl;
-    WordCtl &wctl = *f.wctl;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int K = f.K, G = f.G, N = f.N, cap = f.cap;
-    (void) N;
-    const R NINF = Num<R>::ninf();
-    const R theta = f.theta;
-    R *cur_v = f.cur_v;
-    int *cur_q = f.cur_q, *cur_h = f.cur_h;
-    unsigned long long *arg = f.arg, *tkey = f.tkey, *cpair = f.cpair;
-    U *val = f.val, *ckey = f.ckey;
-    int *tl = f.tl;
-    const int2 *oarc = f.oarc;
-    const R *ow = f.ow, *sw = f.sw;
-    const unsigned long long qmask = (1ull << f.qbits) - 1ull;
-    auto TR = [&](int i, int j) -> R {
-        if constexpr (TRL) return f.trs[i * N + j];
-        else return f.tr[(int64_t) i * f.ts0 + (int64_t) j * f.ts1];
-    };
-    const unsigned long long ARG_NONE = ~0ull;
-
-    // ================================================================ candidates
-    if (first) {
-        if (tid == 0) ctl.n = f.num_start;
-    } else {
-        for (int phase = 0; phase < 2; ++phase) {
-            for (int k0 = 0; k0 < na; k0 += kBT / G) {
-                const int k = k0 + tid / G, lg = tid % G;
-                const bool act = k < na;
-                int qs = 0, hs = 0, j = 0, e = 0, e1 = 0;
-                R v = NINF;
-                if (act) {
-                    qs = cur_q[k]; hs = cur_h[k]; v = cur_v[k]; j = f.label[qs];
-                    e = f.orow[qs] + lg; e1 = f.orow[qs + 1];
-                }
-                const unsigned long long me = (f.pair(hs, qs) << kWordSlotBits) | (unsigned) k;
-                // the stay, then the row; the whole wavefront stays in the loop until its last lane is done (wave_append)
-                bool stay = act && lg == 0;
-                while (__any(stay || e < e1)) {
-                    int tq = -1, th = hs;
-                    R c = NINF;
-                    if (stay) { tq = qs; c = v + TR(j, j); stay = false; }
-                    else if (e < e1) {
-                        const int2 a = oarc[e];
-                        tq = a.x;
-                        c = (v + TR(a.y, j)) + ow[e];
-                        if (a.y == f.sep) {                           // a word ends: the LM moves
-                            R add;
-                            int h2;
-                            if (f.step(hs, f.wos[f.state[qs]], h2, add)) { th = h2; c = c + add; }
-                            else tq = -1;
-                        }
-                        e += G;
-                    }
-                    const bool ok = tq >= 0 && c > NINF;          // a -inf candidate never makes a candidate pair
-                    const U key = KT::enc(c);
-                    const unsigned long long pk = f.pair(th, tq) + 1ull;
-                    if (phase == 0) {
-                        bool fresh = false;
-                        if (ok) {
-                            const int s = f.insert(pk, fresh);
-                            if (s >= 0) atomicMax(val + s, key);
-                            if (fresh) th = s;                    // (th is done with: it carries the slot to the append)
-                        }
-                        const int pos = wave_append(fresh, &ctl.n);
-                        if (fresh && pos < cap) tl[pos] = th;
-                    } else if (ok) {
-                        const int s = f.find(pk);
-                        if (s >= 0 && dev_load(val + s) == key) atomicMin(arg + s, me);
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    if (tid < 256) { ctl.hist[0][tid] = 0; ctl.hist[1][tid] = 0; }
-    if (tid == 0) { ctl.kmax = 0; ctl.kmin = ~(U) 0; ctl.na = 0; ctl.done = 0; wctl.pcut = ~0ull; }
-    __syncthreads();
-    // ================================================================ select (the value part is asg_beam_frame.h's, verbatim)
-    const int n = ctl.n < cap ? ctl.n : cap;
-    {   // c = best + emission as keys, the pairs beside them; their maximum and minimum
-        U mx = 0, mn = ~(U) 0;
-        for (int j = tid; j < n; j += kBT) {
-            unsigned long long p;
-            R base;
-            if (first) { const int q = f.start_q[j]; p = f.pair(f.lstart, q); base = sw[q]; }
-            else { const int s = tl[j]; p = dev_load(tkey + s) - 1ull; base = KT::dec(dev_load(val + s)); }
-            const R c = base + xt[(int64_t) f.label[(int) (p & qmask)] * is2];
-            const U key = c > NINF ? KT::enc(c) : (U) 0;
-            ckey[j] = key;
-            cpair[j] = p;
-            if (key) { mx = key > mx ? key : mx; mn = key < mn ? key : mn; }
-        }
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const U a = (U) __shfl_xor(mx, o), c2 = (U) __shfl_xor(mn, o);
-            mx = a > mx ? a : mx; mn = c2 < mn ? c2 : mn;
-        }
-        if (lane == 0 && mx) { atomicMax(&ctl.kmax, mx); atomicMin(&ctl.kmin, mn); }
-    }
-    __syncthreads();
-    const U kmax = ctl.kmax;
-    U lokey = ~(U) 0;                                    // no candidate: nothing passes
-    if (kmax) {
-        lokey = KT::enc(KT::dec(kmax) - theta);
-        const U kmin = ctl.kmin;
-        const U from = lokey > kmin ? lokey : kmin;      // every key that passes lies in [from, kmax]
-        // ---- the K-th key: 8-bit digits below the bits that `from` and kmax share
-        int rem = from == kmax ? 0 : KT::kBits - (int) (sizeof(U) == 8 ? __clzll((long long) (from ^ kmax))
-                                                                       : __clz((int) (from ^ kmax)));
-        if (tid == 0) { ctl.pre = rem >= KT::kBits ? (U) 0 : (kmax >> rem); ctl.need = K; ctl.kth = lokey; }
-        __syncthreads();
-        bool first_pass = true;
-        int hb = 0;
-        if (rem == 0) {
-            // every passing key equals kmax: count them through one histogram bin
-            for (int j = tid; j < n; j += kBT) if (ckey[j] == kmax) atomicAdd(&ctl.hist[0][0], 1);
-            __syncthreads();
-            if (tid == 0) {
-                const int cnt = ctl.hist[0][0];
-                ctl.kth = kmax;
-                if (cnt <= K) ctl.done = 1; else ctl.need = K;
-                ctl.hist[0][0] = 0;
-            }
-            __syncthreads();
-            first_pass = false;
-        }
-        while (rem > 0) {
-            const int w = rem < 8 ? rem : 8, shift = rem - w;
-            const U pre = ctl.pre;
-            int *h = ctl.hist[hb];
-            for (int j = tid; j < n; j += kBT) {
-                const U key = ckey[j];
-                if (key >= lokey && key != 0 && (rem >= KT::kBits || (key >> rem) == pre))
-                    atomicAdd(&h[(int) ((key >> shift) & (U) ((1 << w) - 1))], 1);
-            }
-            if (tid < 256) ctl.hist[hb ^ 1][tid] = 0;
-            __syncthreads();
-            if (tid < 64) {
-                int total = 0;
-                if (first_pass) {                         // everything that passes lo: taken whole when it fits
-                    for (int x = 0; x < 4; ++x) total += h[4 * lane + x];
-#pragma unroll
-                    for (int o = 1; o < 64; o <<= 1) total += __shfl_xor(total, o);
-                }
-                if (first_pass && total <= K) {
-                    if (lane == 0) { ctl.done = 1; ctl.kth = lokey; }
-                } else {
-                    int d, before;
-                    find_digit<true>(h, ctl.need, lane, d, before);
-                    if (lane == 0) {
-                        ctl.need -= before;
-                        ctl.pre = (rem >= KT::kBits ? (U) 0 : (pre << w)) | (U) d;
-                        if (shift == 0) {
-                            ctl.kth = ctl.pre;
-                            if (h[d] == ctl.need) ctl.done = 1;      // every key tied with the K-th is taken
-                        }
-                    }
-                }
-            }
-            __syncthreads();
-            if (ctl.done) break;
-            first_pass = false;
-            rem = shift;
-            hb ^= 1;
-        }
-        // ---- ties at the K-th key: the `need` smallest pairs among them, over the pair's pbits bits
-        if (!ctl.done) {
-            const U kth = ctl.kth;
-            if (tid < 256) { ctl.hist[0][tid] = 0; ctl.hist[1][tid] = 0; }
-            if (tid == 0) wctl.ppre = 0;
-            __syncthreads();
-            int prem = f.pbits;
-            hb = 0;
-            while (prem > 0) {
-                const int w = prem < 8 ? prem : 8, shift = prem - w;
-                const unsigned long long pre = wctl.ppre;
-                int *h = ctl.hist[hb];
-                for (int j = tid; j < n; j += kBT) {
-                    if (ckey[j] != kth) continue;
-                    const unsigned long long p = cpair[j];
-                    if ((p >> prem) == pre) atomicAdd(&h[(int) ((p >> shift) & ((1ull << w) - 1ull))], 1);
-                }
-                if (tid < 256) ctl.hist[hb ^ 1][tid] = 0;
-                __syncthreads();
-                if (tid < 64) {
-                    int d, before;
-                    find_digit<false>(h, ctl.need, lane, d, before);
-                    if (lane == 0) {
-                        ctl.need -= before;
-                        wctl.ppre = (pre << w) | (unsigned long long) d;
-                        if (shift == 0) wctl.pcut = wctl.ppre;
-                    }
-                }
-                __syncthreads();
-                prem = shift;
-                hb ^= 1;
-            }
-        }
-    }
-    // ---- the new kept set, the frame's back-pointers, and the table emptied
-    {
-        const U kth = ctl.kth;
-        const unsigned long long pcut = wctl.pcut;
-        int *bqt = bq + (int64_t) row * K, *bht = bh + (int64_t) row * K, *bst = bs + (int64_t) row * K;
-        for (int j0 = 0; j0 < n; j0 += kBT) {
-            const int j = j0 + tid;
-            bool sel = false;
-            unsigned long long p = 0;
-            U key = 0;
-            int s = 0;
-            if (j < n) {
-                p = cpair[j];
-                key = ckey[j];
-                if (!first) s = tl[j];
-                sel = kmax != 0 && key != 0 && key >= lokey && (key > kth || (key == kth && p <= pcut));
-            }
-            const int slot = wave_append(sel, &ctl.na);
-            if (sel && slot < K) {                       // (never more than K: the select counted them)
-                const int q = (int) (p & qmask), h = (int) (p >> f.qbits);
-                cur_q[slot] = q;
-                cur_h[slot] = h;
-                cur_v[slot] = KT::dec(key);
-                bqt[slot] = q;
-                bht[slot] = h;
-                bst[slot] = first ? -1 : (int) (dev_load(arg + s) & ((1ull << kWordSlotBits) - 1ull));
-            }
-            if (j < n && !first) { dev_store(tkey + s, 0ull); dev_store(val + s, (U) 0); dev_store(arg + s, ARG_NONE); }
-        }
-    }
-    if (tid == 0) ctl.n = 0;
-    __syncthreads();
-}
-
-// The end of a kept pair (h, q) with value v: (v + final_w[q]) + endw, endw = ew[h] at the root, a + ew[h'] after the LM walk of
-// the word that ends in q's node; false: no end (mid-word, or the walk rejects).  `w`: that word, or -1.
-template <typename R>
-__device__ __forceinline__ bool word_end(const BeamWordFrame<R> &f, const R *fw, int h, int q, R v, R &e, int &w) {
-    const int s = f.state[q];
-    R endw;
-    w = -1;
-    if (s == 0) endw = f.ew[h];
-    else {
-        const int ww = f.wos[s];
-        int h2;
-        R a;
-        if (!f.step(h, ww, h2, a)) return false;
-        endw = a + f.ew[h2];
-        w = ww;
-    }
-    e = (v + fw[q]) + endw;
-    return true;
-}
-
-__device__ __forceinline__ void word_no_path(int T, long long *pb, long long *tk, long long *st, long long *lm, long long *wd,
-                                             long long *tlen, long long *wlen) {
-    const int tid = threadIdx.x;
-    for (int t = tid; t < T; t += kBT) { pb[t] = -1; tk[t] = -1; st[t] = -1; lm[t] = -1; wd[t] = -1; }
-    if (tid == 0) { *tlen = 0; *wlen = 0; }
-}
 
 template <typename R, bool TRL>
 __global__ void __launch_bounds__(kBT) beam_word_kernel(Problem P, GraphArgs g, BeamGraphArgs bg, WordLmArgs lm, int K, R theta,
@@ -426,7 +45,7 @@ __global__ void __launch_bounds__(kBT) beam_word_kernel(Problem P, GraphArgs g, 
     int *cur_q = (int *) (cur_v + K);                      // [K]
     int *cur_h = cur_q + K;                                // [K]
     R *trs = (R *) (cur_h + K);                            // [N][N] if TRL (2 * K ints: aligned)
-    const int tid = threadIdx.x, lane = tid & 63, b = blockIdx.x;
+    const int tid = threadIdx.x, b = blockIdx.x;
     const int N = P.N, T = P.T;
     const R NINF = Num<R>::ninf();
     const int len = clamp_len(P.in_len, b, T);
@@ -468,78 +87,21 @@ __global__ void __launch_bounds__(kBT) beam_word_kernel(Problem P, GraphArgs g, 
         beam_word_frame<R, TRL>(f, t == 0, na, in + (int64_t) t * P.is0, P.is2, bq, bh, bs, t);
     }
 
-    // ---- the best end over the last kept set, the smallest pair on a tie
+    // ---- the best end over the last kept set, the smallest pair on a tie; the backtrace, the words, the tokens
     const int na = ctl.na < K ? ctl.na : K;
-    U bkey = 0;
-    unsigned long long bpair = ~0ull;
-    int bk = -1;
-    for (int k = tid; k < na; k += kBT) {
-        R e;
-        int w;
-        if (!word_end<R>(f, fw, cur_h[k], cur_q[k], cur_v[k], e, w)) continue;
-        const U key = e > NINF ? KT::enc(e) : (U) 0;
-        const unsigned long long p = f.pair(cur_h[k], cur_q[k]);
-        if (key && (key > bkey || (key == bkey && p < bpair))) { bkey = key; bpair = p; bk = k; }
-    }
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const U ok = (U) __shfl_xor(bkey, o);
-        const unsigned long long op = __shfl_xor(bpair, o);
-        const int okk = __shfl_xor(bk, o);
-        if (ok > bkey || (ok == bkey && op < bpair)) { bkey = ok; bpair = op; bk = okk; }
-    }
-    if (lane == 0) { wctl.rkey[tid >> 6] = bkey; wctl.rpair[tid >> 6] = bpair; wctl.rk[tid >> 6] = bk; }
-    __syncthreads();
-    bkey = (U) wctl.rkey[0]; bpair = wctl.rpair[0]; bk = wctl.rk[0];
-    for (int s = 1; s < kBT / 64; ++s) {
-        const U ok = (U) wctl.rkey[s];
-        if (ok > bkey || (ok == bkey && wctl.rpair[s] < bpair)) { bkey = ok; bpair = wctl.rpair[s]; bk = wctl.rk[s]; }
-    }
+    U bkey;
+    int bk;
+    word_best_end<R>(f, fw, true, cur_h, cur_q, cur_v, na, bkey, bk);
     if (bkey == 0) {                                        // an empty beam, or no kept pair with a finite end
         word_no_path(T, pb, tk, st, ls, wd, tlen + b, wlen + b);
         if (tid == 0) scores[b] = NINF;
         return;
     }
-    // ---- the backtrace through the stored slots; the score from the winner's own sum (the key folds -0 into +0); the words
-    for (int t = len + tid; t < T; t += kBT) { pb[t] = -1; st[t] = -1; ls[t] = -1; }
-    __threadfence();
-    __syncthreads();
-    if (tid == 0) {
-        R e;
-        int wfin;
-        (void) word_end<R>(f, fw, cur_h[bk], cur_q[bk], cur_v[bk], e, wfin);
-        scores[b] = e;
-        int k = bk;
-        for (int t = len - 1; t >= 0; --t) {
-            if (k < 0 || k >= K) break;                      // (cannot happen: every kept pair stored its source's slot)
-            const int q = bq[(int64_t) t * K + k];
-            ls[t] = bh[(int64_t) t * K + k];
-            k = bs[(int64_t) t * K + k];
-            pb[t] = f.label[q];
-            st[t] = f.state[q];
-        }
-        // a separator edge is the one way into the separator's product state: its frames are those whose label is the separator
-        // behind another label, and the word is the one that ends in the node before
-        int nw = 0;
-        for (int t = 1; t < len; ++t)
-            if (pb[t] == f.sep && pb[t - 1] != f.sep) wd[nw++] = f.wos[st[t - 1]];
-        if (wfin >= 0) wd[nw++] = wfin;
-        wlen[b] = nw;
-        wctl.rk[0] = nw;
-    }
-    __threadfence();
-    __syncthreads();
-    for (int t = wctl.rk[0] + tid; t < T; t += kBT) wd[t] = -1;
-    if (tid < 64) collapse_tokens(pb, len, T, tk, tlen + b, tid);
+    word_backtrace<R>(f, fw, true, cur_h, cur_q, cur_v, bk, bq, bh, bs, len, T, scores + b, pb, tk, st, ls, wd, tlen + b,
+                      wlen + b);
 }
 
 inline size_t a256(size_t x) { return (x + 255) / 256 * 256; }
-
-inline int word_table_bits(int cap) {
-    int bits = 1;
-    while (((size_t) 1 << bits) < 2 * (size_t) cap) ++bits;
-    return bits;
-}
 
 inline size_t beam_word_per_utt(int elem, int T, int K, int cap) {
     const size_t C = (size_t) 1 << word_table_bits(cap);
@@ -589,3 +151,4 @@ template hipError_t launch_beam_words<double>(const Problem &, const GraphArgs &
                                               long long *, long long *, long long *, hipStream_t);
 
 }  // namespace asg
+

@@ -1,0 +1,241 @@
+// torch_asg_amd/csrc/asg_beam_word_stream.hip -- STREAMING beam decoding with a lexicon and a word n-gram LM composed on the fly,
+// on gfx950: the search of asg_beam_word.hip over pairs (LM history h, lexicon product state q) carried across chunks of frames.
+// The specification is include/asg_hip.h::asg_beam_word_stream_advance; tests/beam_word_stream_ref.py restates it.  Decoding an
+// utterance in chunks gives the bits of decoding it in one call, for any chunking: the frames and the end run the device code of
+// the one-shot decoder (asg_beam_word_frame.h, compiled into both translation units), and the search never looks ahead -- the LM
+// walk of a separator edge reads the source pair's h and nothing else, whether that pair was kept a frame or a call ago.
+//
+// A stream state serves B utterance slots.  One slot (beam_word_stream_layout; every part 256-byte aligned):
+//   the one-shot decoder's workspace of one utterance with T = max_frames: bq / bh / bs int32 [max_frames][K] (product state, LM
+//     state and source slot of every kept pair of every frame consumed so far), the table tkey u64 [C], arg u64 [C], val key [C],
+//     ckey key [cap], cpair u64 [cap], touched int32 [cap];
+//   a 256-byte header: int32 pos (frames consumed), |A| (size of the stored set), overflow;
+//   the stored set: values [K] (dtype), then product states int32 [K], then LM states int32 [K].
+// Nothing is sized by H, V, A or Q.  Three kernels, each one launch, no host synchronisation, no copy, no memset:
+//   beam_word_stream_reset_kernel    per chosen slot: pos = 0, |A| = 0, overflow = 0, and the whole table emptied (tkey = 0, val = 0,
+//                                    arg = none).  The only place all C slots are written: a frame empties what it touched, so
+//                                    the table is empty between calls.
+//   beam_word_stream_advance_kernel  one 1024-thread workgroup per slot: the transitions and the stored set into LDS,
+//                                    beam_word_frame for the chunk's frames with the back-pointers into rows pos .. pos+n-1, the
+//                                    set and pos back.
+//   beam_word_stream_result_kernel   one workgroup per slot: the best end over the stored set (the end of the one-shot decoder, or
+//                                    the best prefix), the backtrace over pos frames, the words, the token collapse, the padding.
+//                                    It only reads the state.
+// What one call writes and the next reads crosses a kernel boundary, so plain stores and loads do; the table keeps the
+// device-scope loads and atomics of the frame body.  Integer atomics only: bit-identical run to run.
+#include "asg_common.h"
+#include "asg_kernels.h"
+#include "asg_beam_common.h"
+#include "asg_beam_word_frame.h"
+
+namespace asg {
+
+namespace {
+
+inline size_t a256(size_t x) { return (x + 255) / 256 * 256; }
+
+constexpr int kResetBlocks = 64;   // workgroups per slot in the reset
+
+__global__ void __launch_bounds__(256) beam_word_stream_reset_kernel(char *state, BeamStreamLayout lay, unsigned C, int key_bytes,
+                                                                      size_t tkey_off, size_t arg_off, size_t val_off,
+                                                                      const unsigned char *mask) {
+    const int b = blockIdx.x;
+    if (mask && !mask[b]) return;
+    char *wb = state + (size_t) b * lay.per;
+    unsigned long long *tkey = (unsigned long long *) (wb + tkey_off), *arg = (unsigned long long *) (wb + arg_off);
+    for (unsigned s = blockIdx.y * 256 + threadIdx.x; s < C; s += gridDim.y * 256) {
+        dev_store(tkey + s, 0ull);
+        dev_store(arg + s, ~0ull);
+        if (key_bytes == 8) dev_store((unsigned long long *) (wb + val_off) + s, 0ull);
+        else dev_store((unsigned int *) (wb + val_off) + s, 0u);
+    }
+    if (blockIdx.y == 0 && threadIdx.x < 3) ((int *) (wb + lay.hdr))[threadIdx.x] = 0;      // pos, |A|, overflow
+}
+
+// The parts of a BeamWordFrame that do not depend on the call: the graph, the LM and the shape of the search.
+template <typename R>
+__device__ __forceinline__ void bind_graph(BeamWordFrame<R> &f, const GraphArgs &g, const BeamGraphArgs &bg, const WordLmArgs &lm,
+                                           int K, int cap, int tbits) {
+    f.K = K; f.G = beam_lanes_per_state(K); f.cap = cap; f.sep = lm.sep; f.tbits = tbits;
+    f.qbits = bits_of(g.Q); f.pbits = f.qbits + bits_of(lm.H);
+    f.label = g.label; f.state = g.state; f.orow = bg.orow; f.start_q = bg.start_q; f.num_start = bg.num_start;
+    f.oarc = (const int2 *) bg.oarc; f.ow = (const R *) bg.ow; f.sw = (const R *) g.start_w;
+    f.lrow = lm.row; f.lword = lm.word; f.lnext = lm.next; f.lback = lm.backoff; f.wos = lm.word_of_state;
+    f.lw = (const R *) lm.lw; f.bw = (const R *) lm.bw; f.ew = (const R *) lm.ew; f.lstart = lm.start;
+}
+
+template <typename R, bool TRL>
+__global__ void __launch_bounds__(kBT) beam_word_stream_advance_kernel(Problem P, GraphArgs g, BeamGraphArgs bg, WordLmArgs lm, int K,
+                                                                       R theta, int cap, int tbits, int max_frames, char *state,
+                                                                       BeamStreamLayout lay) {
+    using KT = Key<R>;
+    using U = typename KT::U;
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    Ctl<U> &ctl = *(Ctl<U> *) lds;
+    WordCtl &wctl = *(WordCtl *) (lds + kWordCtlOff);
+    R *cur_v = (R *) (lds + kFixedLds);                    // [K]
+    int *cur_q = (int *) (cur_v + K);                      // [K]
+    int *cur_h = cur_q + K;                                // [K]
+    R *trs = (R *) (cur_h + K);                            // [N][N] if TRL (2 * K ints: aligned)
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const int N = P.N;
+    char *wb = state + (size_t) b * lay.per;
+    int *hdr = (int *) (wb + lay.hdr);
+    R *set_v = (R *) (wb + lay.set);                        // [K]
+    int *set_q = (int *) (set_v + K);                       // [K]
+    int *set_h = set_q + K;                                 // [K]
+    int pos = hdr[0];
+    pos = pos < 0 ? 0 : (pos > max_frames ? max_frames : pos);             // (a state that was reset holds 0 .. max_frames)
+    const int want = clamp_len(P.in_len, b, P.T);
+    const int n = want < max_frames - pos ? want : max_frames - pos;
+    if (n < want && tid == 0) hdr[2] = 1;                   // frames beyond max_frames are not consumed
+    if (n < 1) return;
+    const R *in = (const R *) P.inputs + (int64_t) b * P.is1;
+    const R *tr = (const R *) P.transition;
+    BeamWordFrame<R> f;
+    f.ctl = &ctl; f.wctl = &wctl; f.cur_v = cur_v; f.cur_q = cur_q; f.cur_h = cur_h; f.trs = trs; f.tr = tr;
+    f.ts0 = P.ts0; f.ts1 = P.ts1; f.N = N; f.theta = theta;
+    bind_graph<R>(f, g, bg, lm, K, cap, tbits);
+    int *bq, *bh, *bs;
+    f.bind_work(wb, max_frames, bq, bh, bs);
+
+    if constexpr (TRL)
+        for (int x = tid; x < N * N; x += kBT) trs[x] = tr[(int64_t) (x / N) * P.ts0 + (int64_t) (x % N) * P.ts1];
+    int na0 = pos >= 1 ? hdr[1] : 0;
+    na0 = na0 < 0 ? 0 : (na0 > K ? K : na0);
+    for (int k = tid; k < na0; k += kBT) { cur_v[k] = set_v[k]; cur_q[k] = set_q[k]; cur_h[k] = set_h[k]; }
+    if (tid == 0) { ctl.na = na0; ctl.n = 0; }
+    __syncthreads();
+
+    for (int t = 0; t < n; ++t) {
+        const int gt = pos + t;                             // the frame's index in the utterance
+        const int na = ctl.na;
+        if (gt >= 1 && na == 0) break;                      // an empty beam stays empty (pos still advances)
+        beam_word_frame<R, TRL>(f, gt == 0, na, in + (int64_t) t * P.is0, P.is2, bq, bh, bs, gt);
+    }
+
+    int na = ctl.na;
+    na = na < K ? na : K;
+    for (int k = tid; k < na; k += kBT) { set_v[k] = cur_v[k]; set_q[k] = cur_q[k]; set_h[k] = cur_h[k]; }
+    if (tid == 0) { hdr[1] = na; hdr[0] = pos + n; }
+}
+
+template <typename R>
+__global__ void __launch_bounds__(kBT) beam_word_stream_result_kernel(GraphArgs g, WordLmArgs lm, int K, int cap, int tbits,
+                                                                      int max_frames, const char *state, BeamStreamLayout lay,
+                                                                      int final, R *scores, long long *path, long long *tokens,
+                                                                      long long *tlen, long long *states, long long *lm_states,
+                                                                      long long *words, long long *wlen, long long *frames,
+                                                                      long long *status) {
+    using U = typename Key<R>::U;
+    __shared__ WordCtl wctl;
+    const int tid = threadIdx.x, b = blockIdx.x, T = max_frames;
+    const R NINF = Num<R>::ninf();
+    char *wb = const_cast<char *>(state) + (size_t) b * lay.per;            // (only read: bind_work takes the workspace as it is)
+    const int *hdr = (const int *) (wb + lay.hdr);
+    const R *set_v = (const R *) (wb + lay.set);
+    const int *set_q = (const int *) (set_v + K);
+    const int *set_h = set_q + K;
+    long long *pb = path + (int64_t) b * T, *tk = tokens + (int64_t) b * T, *st = states + (int64_t) b * T;
+    long long *ls = lm_states + (int64_t) b * T, *wd = words + (int64_t) b * T;
+    BeamWordFrame<R> f;
+    f.ctl = nullptr; f.wctl = &wctl; f.cur_v = nullptr; f.cur_q = nullptr; f.cur_h = nullptr; f.trs = nullptr; f.tr = nullptr;
+    f.ts0 = 0; f.ts1 = 0; f.N = 0; f.theta = (R) 0;
+    bind_graph<R>(f, g, BeamGraphArgs{}, lm, K, cap, tbits);
+    int *bq, *bh, *bs;
+    f.bind_work(wb, T, bq, bh, bs);
+    int L = hdr[0];
+    L = L < 0 ? 0 : (L > T ? T : L);
+    int na = L >= 1 ? hdr[1] : 0;
+    na = na < 0 ? 0 : (na > K ? K : na);
+    if (tid == 0) { frames[b] = L; status[b] = hdr[2] != 0; }
+    const R *fw = (const R *) g.final_w;
+    U bkey;
+    int bk;
+    word_best_end<R>(f, fw, final != 0, set_h, set_q, set_v, na, bkey, bk);
+    if (bkey == 0) {                                        // no frame yet, an empty set, or no finite end
+        word_no_path(T, pb, tk, st, ls, wd, tlen + b, wlen + b);
+        if (tid == 0) scores[b] = NINF;
+        return;
+    }
+    word_backtrace<R>(f, fw, final != 0, set_h, set_q, set_v, bk, bq, bh, bs, L, T, scores + b, pb, tk, st, ls, wd, tlen + b,
+                      wlen + b);
+}
+
+}  // namespace
+
+BeamStreamLayout beam_word_stream_layout(int elem, int max_frames, int K, int cap) {
+    BeamStreamLayout l{};
+    size_t off = beam_word_work_bytes(elem, max_frames, 1, K, cap);         // the one-shot decoder's part, at the front
+    l.hdr = off;  off += 256;
+    l.set = off;  off += a256((size_t) K * (elem + 8));
+    l.per = off;
+    return l;
+}
+
+size_t beam_word_stream_state_bytes(int elem, int max_frames, int B, int K, int cap) {
+    return (size_t) B * beam_word_stream_layout(elem, max_frames, K, cap).per;
+}
+
+hipError_t launch_beam_word_stream_reset(int elem, const BeamGraphArgs &BG, int K, int max_frames, int B, void *state,
+                                         const unsigned char *mask, hipStream_t stream) {
+    const int cap = beam_word_cap(K, BG.max_out, BG.num_start);
+    const BeamStreamLayout lay = beam_word_stream_layout(elem, max_frames, K, cap);
+    const size_t C = (size_t) 1 << word_table_bits(cap);
+    const size_t tkey_off = 3 * a256((size_t) max_frames * K * 4), arg_off = tkey_off + a256(C * 8), val_off = arg_off + a256(C * 8);
+    size_t by = (C + 255) / 256;
+    by = by < 1 ? 1 : (by > (size_t) kResetBlocks ? (size_t) kResetBlocks : by);
+    hipLaunchKernelGGL(beam_word_stream_reset_kernel, dim3(B, (unsigned) by), dim3(256), 0, stream, (char *) state, lay, (unsigned) C,
+                       elem, tkey_off, arg_off, val_off, mask);
+    return hipGetLastError();
+}
+
+template <typename R>
+hipError_t launch_beam_word_stream_advance(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int K,
+                                           double theta, int max_frames, void *state, hipStream_t stream) {
+    const int N = P.N;
+    const int cap = beam_word_cap(K, BG.max_out, BG.num_start);
+    const int tbits = word_table_bits(cap);
+    const BeamStreamLayout lay = beam_word_stream_layout(sizeof(R), max_frames, K, cap);
+    // the LDS of the one-shot decoder: control block, the set, and the transitions when they fit beside it
+    const size_t beam = kFixedLds + (size_t) K * (sizeof(R) + 8);
+    const bool trl = beam + (size_t) N * N * sizeof(R) <= kLdsMax;
+    const size_t dyn = beam + (trl ? (size_t) N * N * sizeof(R) : 0);
+#define ASG_BEAM_WORD_STREAM(TRL)                                                                                            \
+    do {                                                                                                                     \
+        const void *fn = (const void *) beam_word_stream_advance_kernel<R, TRL>;                                            \
+        if (dyn > 64 * 1024) (void) hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) dyn);       \
+        hipLaunchKernelGGL((beam_word_stream_advance_kernel<R, TRL>), dim3(P.B), dim3(kBT), dyn, stream, P, G, BG, LM, K,   \
+                           (R) theta, cap, tbits, max_frames, (char *) state, lay);                                          \
+    } while (0)
+    if (trl) ASG_BEAM_WORD_STREAM(true); else ASG_BEAM_WORD_STREAM(false);
+#undef ASG_BEAM_WORD_STREAM
+    return hipGetLastError();
+}
+template hipError_t launch_beam_word_stream_advance<float>(const Problem &, const GraphArgs &, const BeamGraphArgs &,
+                                                           const WordLmArgs &, int, double, int, void *, hipStream_t);
+template hipError_t launch_beam_word_stream_advance<double>(const Problem &, const GraphArgs &, const BeamGraphArgs &,
+                                                            const WordLmArgs &, int, double, int, void *, hipStream_t);
+
+template <typename R>
+hipError_t launch_beam_word_stream_result(const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int K, int max_frames,
+                                          int B, const void *state, int final, void *scores, long long *path, long long *tokens,
+                                          long long *tlen, long long *states, long long *lm_states, long long *words,
+                                          long long *wlen, long long *frames, long long *status, hipStream_t stream) {
+    const int cap = beam_word_cap(K, BG.max_out, BG.num_start);
+    const BeamStreamLayout lay = beam_word_stream_layout(sizeof(R), max_frames, K, cap);
+    hipLaunchKernelGGL((beam_word_stream_result_kernel<R>), dim3(B), dim3(kBT), 0, stream, G, LM, K, cap, word_table_bits(cap),
+                       max_frames, (const char *) state, lay, final, (R *) scores, path, tokens, tlen, states, lm_states, words,
+                       wlen, frames, status);
+    return hipGetLastError();
+}
+template hipError_t launch_beam_word_stream_result<float>(const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &, int, int, int,
+                                                          const void *, int, void *, long long *, long long *, long long *,
+                                                          long long *, long long *, long long *, long long *, long long *,
+                                                          long long *, hipStream_t);
+template hipError_t launch_beam_word_stream_result<double>(const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &, int, int, int,
+                                                           const void *, int, void *, long long *, long long *, long long *,
+                                                           long long *, long long *, long long *, long long *, long long *,
+                                                           long long *, hipStream_t);
+
+}  // namespace asg

@@ -231,6 +231,22 @@ hipError_t launch_beam_stream_result(const GraphArgs &G, const BeamGraphArgs &BG
                                      int final, void *scores, long long *path, long long *tokens, long long *tlen,
                                      long long *states, long long *frames, long long *status, hipStream_t stream);
 
+// ---- The search over pairs carried across chunks of frames (asg_beam_word_stream.hip): asg_beam_word_stream_*.  One slot of the
+// state: the word decoder's own layout for T = max_frames at the front, then hdr (int32 pos, |A|, overflow) and the stored set
+// (values [K], then int32 product states [K], then int32 LM states [K]).  K = beam_size, cap = beam_word_cap(..).
+BeamStreamLayout beam_word_stream_layout(int elem, int max_frames, int K, int cap);
+size_t beam_word_stream_state_bytes(int elem, int max_frames, int B, int K, int cap);
+hipError_t launch_beam_word_stream_reset(int elem, const BeamGraphArgs &BG, int K, int max_frames, int B, void *state,
+                                         const unsigned char *mask, hipStream_t stream);
+template <typename R>
+hipError_t launch_beam_word_stream_advance(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int K,
+                                           double theta, int max_frames, void *state, hipStream_t stream);
+template <typename R>
+hipError_t launch_beam_word_stream_result(const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int K, int max_frames,
+                                          int B, const void *state, int final, void *scores, long long *path, long long *tokens,
+                                          long long *tlen, long long *states, long long *lm_states, long long *words,
+                                          long long *wlen, long long *frames, long long *status, hipStream_t stream);
+
 // ---- The stream in bounded memory (asg_beam_window.hip): asg_beam_window_*.  One slot of the state has the layout of a stream
 // of W frames -- the back-pointers are a ring, frame u in row u mod W -- with the header int64 pos, int64 base, int32 |A|, carry,
 // status.  CP: the commit period (a commit attempt after every frame whose count is a multiple of it), 1 <= CP <= W.
