@@ -44,6 +44,16 @@ def _current_stream_handle(idx):
     return int(torch.cuda.current_stream(idx).cuda_stream)
 
 
+def _on_device(t, dev, contiguous):
+    if t is None:
+        return None
+    if t.device != dev:
+        t = t.to(dev, non_blocking=True)
+    if contiguous and not t.is_contiguous():
+        t = t.contiguous()
+    return t
+
+
 class HipBackend:
     """Thin tensor <-> C-ABI adapter.  Every method launches HIP kernels on the current stream."""
 
@@ -119,15 +129,7 @@ class HipBackend:
     @staticmethod
     def device_args(dev, targets, input_lengths, target_lengths):
         """targets / lengths as the kernels read them: on `dev`, lengths contiguous."""
-        def conv(t, contiguous):
-            if t is None:
-                return None
-            if t.device != dev:
-                t = t.to(dev, non_blocking=True)
-            if contiguous and not t.is_contiguous():
-                t = t.contiguous()
-            return t
-        return conv(targets, False), conv(input_lengths, True), conv(target_lengths, True)
+        return _on_device(targets, dev, False), _on_device(input_lengths, dev, True), _on_device(target_lengths, dev, True)
 
     @staticmethod
     def _problem(inputs, transition, targets, input_lengths, target_lengths):
@@ -360,14 +362,15 @@ class HipBackend:
         L = _lib.lib()
 
         def view(dev, dtype):
-            return _graph.abi_graph(graph.compile(dev, dtype, lm_weight, token_score))
+            compiled = graph.compile(dev, dtype, lm_weight, token_score)
+            return _graph.abi_graph(compiled), compiled["Q"]
 
         def work_bytes(p, g):
             return L.asg_viterbi_decode_graph_work_bytes(ctypes.byref(p), ctypes.byref(g))
 
-        def call(p, g, work, scores, path, tokens, token_lengths, states, stream):
-            return L.asg_viterbi_decode_graph(None, ctypes.byref(p), ctypes.byref(g), work.data_ptr(), work.numel(), scores, path,
-                                              tokens, token_lengths, states, flags, stream)
+        def call(p, g, work, nbytes, scores, path, tokens, token_lengths, states, stream):
+            return L.asg_viterbi_decode_graph(None, ctypes.byref(p), ctypes.byref(g), work, nbytes, scores, path, tokens,
+                                              token_lengths, states, flags, stream)
         return self._decode_graph(inputs, transition, graph, input_lengths, max_work_bytes, view, work_bytes, call,
                                   "asg_viterbi_decode_graph")
 
@@ -380,269 +383,76 @@ class HipBackend:
         L = _lib.lib()
 
         def view(dev, dtype):
-            return _graph.abi_graph_beam(graph.compile_beam(dev, dtype, lm_weight, token_score))
+            compiled = graph.compile_beam(dev, dtype, lm_weight, token_score)
+            return _graph.abi_graph_beam(compiled), compiled["Q"]
 
         def work_bytes(p, g):
             return L.asg_beam_decode_graph_work_bytes(ctypes.byref(p), ctypes.byref(g), beam_size)
 
-        def call(p, g, work, scores, path, tokens, token_lengths, states, stream):
-            return L.asg_beam_decode_graph(None, ctypes.byref(p), ctypes.byref(g), beam_size, beam_threshold, work.data_ptr(),
-                                           work.numel(), scores, path, tokens, token_lengths, states, flags, stream)
+        def call(p, g, work, nbytes, scores, path, tokens, token_lengths, states, stream):
+            return L.asg_beam_decode_graph(None, ctypes.byref(p), ctypes.byref(g), beam_size, beam_threshold, work, nbytes, scores,
+                                           path, tokens, token_lengths, states, flags, stream)
         return self._decode_graph(inputs, transition, graph, input_lengths, max_work_bytes, view, work_bytes, call,
                                   "asg_beam_decode_graph")
 
-    def beam_decode_words(self, inputs, transition, lexicon, word_lm, input_lengths, beam_size, beam_threshold=float("inf"),
-                          lm_weight=1.0, word_score=0.0, token_score=0.0, max_work_bytes=1 << 30):
-        """Beam search over (LM history, lexicon product state) pairs -> BeamWords; see
-        include/asg_hip.h::asg_beam_decode_words.  Grouped under `max_work_bytes` as `_decode_graph` does."""
-        from . import wordlm as _wordlm
-        from . import graph as _graph
-        if not isinstance(lexicon, _wordlm.Lexicon):
-            raise TypeError("torch_asg_amd: lexicon must be a torch_asg_amd.Lexicon")
-        if not isinstance(word_lm, _wordlm.WordLM):
-            raise TypeError("torch_asg_amd: word_lm must be a torch_asg_amd.WordLM")
-        wmax = int(lexicon.word_of_state.max(initial=-1))
-        if wmax >= word_lm.V:
-            raise RuntimeError("torch_asg_amd: the lexicon has word id %d but the word LM knows %d words" % (wmax, word_lm.V))
-        beam_size, beam_threshold = min(int(beam_size), (1 << 31) - 1), float(beam_threshold)
-        L = _lib.lib()
-        self._check_decode_graph(inputs, transition, lexicon.graph, input_lengths)
-        T, B, N = inputs.shape
-        dev = inputs.device
-        with self._guard(dev):
-            lex = lexicon.compile_words(dev, inputs.dtype, token_score)
-            g = _graph.abi_graph_beam(lex)
-            w = _wordlm.abi_word_lm(word_lm.compile(dev, inputs.dtype, lm_weight, word_score), lex)
-            w.separator = lexicon.separator
-            p, keep = self._problem(inputs, transition, None, input_lengths, None)
-            if input_lengths is not None:
-                input_lengths = keep[-1]                       # (on the device, contiguous)
-
-            def work_bytes(nb):
-                p.B = nb
-                return int(L.asg_beam_decode_words_work_bytes(ctypes.byref(p), ctypes.byref(g), ctypes.byref(w), beam_size))
-            per = work_bytes(1)
-            if per == 0:                                       # the library refuses the arguments: its call says why
-                p.B = B
-                _lib.check(L.asg_beam_decode_words(None, ctypes.byref(p), ctypes.byref(g), ctypes.byref(w), beam_size,
-                                                   beam_threshold, None, 0, None, None, None, None, None, None, None, None, 0,
-                                                   None), "asg_beam_decode_words")
-            per = max(per, 1)
-            gsz = max(1, min(B, int(max_work_bytes) // per))
-            while gsz > 1 and work_bytes(gsz) > max_work_bytes:
-                gsz -= 1
-            work = self._buf(work_bytes(gsz), dev)
-            scores = torch.empty(B, dtype=inputs.dtype, device=dev)
-            out = torch.empty(5, B, T, dtype=torch.int64, device=dev)      # path, tokens, states, lm_states, words
-            lengths = torch.empty(2, B, dtype=torch.int64, device=dev)     # token_lengths, word_lengths
-            stream = self._stream(dev)
-            for b0 in range(0, B, gsz):
-                b1 = min(B, b0 + gsz)
-                p.inputs = inputs[:, b0:b1].data_ptr()
-                p.B = b1 - b0
-                if input_lengths is not None:
-                    p.input_lengths = input_lengths[b0:b1].data_ptr()
-                _lib.check(L.asg_beam_decode_words(
-                    None, ctypes.byref(p), ctypes.byref(g), ctypes.byref(w), beam_size, beam_threshold, work.data_ptr(),
-                    work.numel(), scores[b0:].data_ptr(), out[0, b0].data_ptr(), out[1, b0].data_ptr(), lengths[0, b0:].data_ptr(),
-                    out[2, b0].data_ptr(), out[3, b0].data_ptr(), out[4, b0].data_ptr(), lengths[1, b0:].data_ptr(), 0, stream),
-                    "asg_beam_decode_words")
-        return BeamWords(scores, out[0], out[1], lengths[0], out[2], out[3], out[4], lengths[1])
-
-    def _check_decode_graph(self, inputs, transition, graph, input_lengths):
-        """The argument checks of the graph decoders."""
-        from . import graph as _graph
-        self._check(inputs, transition, None, input_lengths, None)
-        if inputs.dtype not in (torch.float32, torch.float64):
-            raise RuntimeError("torch_asg_amd: expected scalar type Float or Double but found %s" % inputs.dtype)
-        if not isinstance(graph, _graph.TokenGraph):
-            raise TypeError("torch_asg_amd: graph must be a torch_asg_amd.TokenGraph")
-        T, B, N = inputs.shape
-        if graph.N != N:
-            raise RuntimeError("torch_asg_amd: the graph is over %d tokens but the emissions have N = %d" % (graph.N, N))
-        if input_lengths is not None and tuple(input_lengths.shape) != (B,):
-            raise RuntimeError("torch_asg_amd: input_lengths must have shape [%d]" % B)
-
-    def beam_decode_graph_nbest(self, inputs, transition, graph, input_lengths, beam_size, nbest, beam_threshold=float("inf"),
-                                lm_weight=1.0, token_score=0.0, return_alignments=False, max_work_bytes=1 << 30):
-        """The n best final hypotheses of the beam search with their score split -> (scores, emission_scores, graph_scores
-        [B,nbest], tokens [B,nbest,T], token_lengths [B,nbest], num_hyps [B], path, states [B,nbest,T] or None); see
-        include/asg_hip.h::asg_beam_decode_graph_nbest.  Grouped under `max_work_bytes` as `_decode_graph` does."""
-        from . import graph as _graph
-        beam_size, beam_threshold = min(int(beam_size), (1 << 31) - 1), float(beam_threshold)
-        nbest = min(int(nbest), (1 << 31) - 1)
-        L = _lib.lib()
-        self._check_decode_graph(inputs, transition, graph, input_lengths)
-        T, B, N = inputs.shape
-        dev = inputs.device
-        with self._guard(dev):
-            g = _graph.abi_graph_beam(graph.compile_beam(dev, inputs.dtype, lm_weight, token_score))
-            p, keep = self._problem(inputs, transition, None, input_lengths, None)
-            if input_lengths is not None:
-                input_lengths = keep[-1]                       # (on the device, contiguous)
-
-            def work_bytes(nb):
-                p.B = nb
-                return int(L.asg_beam_decode_graph_nbest_work_bytes(ctypes.byref(p), ctypes.byref(g), beam_size, nbest))
-            per = work_bytes(1)
-            if per == 0:                                       # the library refuses the arguments: its call says why, before
-                p.B = B                                        # outputs are sized by them
-                _lib.check(L.asg_beam_decode_graph_nbest(None, ctypes.byref(p), ctypes.byref(g), beam_size, beam_threshold, nbest,
-                                                         None, 0, None, None, None, None, None, None, None, None, 0, None),
-                           "asg_beam_decode_graph_nbest")
-            per = max(per, 1)
-            gsz = max(1, min(B, int(max_work_bytes) // per))
-            while gsz > 1 and work_bytes(gsz) > max_work_bytes:
-                gsz -= 1
-            work = self._buf(work_bytes(gsz), dev)
-            sc = torch.empty(3, B, nbest, dtype=inputs.dtype, device=dev)      # scores, emission_scores, graph_scores
-            tokens = torch.empty(B, nbest, T, dtype=torch.int64, device=dev)
-            align = torch.empty(2, B, nbest, T, dtype=torch.int64, device=dev) if return_alignments else None
-            token_lengths = torch.empty(B, nbest, dtype=torch.int64, device=dev)
-            num_hyps = torch.empty(B, dtype=torch.int64, device=dev)
-            stream = self._stream(dev)
-            for b0 in range(0, B, gsz):
-                b1 = min(B, b0 + gsz)
-                p.inputs = inputs[:, b0:b1].data_ptr()
-                p.B = b1 - b0
-                if input_lengths is not None:
-                    p.input_lengths = input_lengths[b0:b1].data_ptr()
-                _lib.check(L.asg_beam_decode_graph_nbest(
-                    None, ctypes.byref(p), ctypes.byref(g), beam_size, beam_threshold, nbest, work.data_ptr(), work.numel(),
-                    sc[0, b0:].data_ptr(), sc[1, b0:].data_ptr(), sc[2, b0:].data_ptr(),
-                    align[0, b0:].data_ptr() if return_alignments else None, tokens[b0:].data_ptr(),
-                    token_lengths[b0:].data_ptr(), align[1, b0:].data_ptr() if return_alignments else None,
-                    num_hyps[b0:].data_ptr(), 0, stream), "asg_beam_decode_graph_nbest")
-        return BeamNbest(sc[0], sc[1], sc[2], tokens, token_lengths, num_hyps,
-                         align[0] if return_alignments else None, align[1] if return_alignments else None)
-
-    def _decode_graph(self, inputs, transition, graph, input_lengths, max_work_bytes, view, work_bytes_of, call, what):
+    def _decode_graph(self, inputs, transition, graph, input_lengths, max_work_bytes, view, work_bytes, call, what):
         """What the two graph decoders share: the checks, the utterance groups under `max_work_bytes`, the outputs.  `view`
-        compiles the graph for (device, dtype) -> its C view."""
-        self._check_decode_graph(inputs, transition, graph, input_lengths)
+        compiles the graph for (device, dtype) -> its C view and its number of product states."""
+        self._check_graph_inputs(inputs, transition, graph, input_lengths)
         T, B, N = inputs.shape
         dev = inputs.device
         with self._guard(dev):
-            g = view(dev, inputs.dtype)
-            p, keep = self._problem(inputs, transition, None, input_lengths, None)
-            if input_lengths is not None:
-                input_lengths = keep[-1]                       # (on the device, contiguous)
-
-            def work_bytes(nb):
-                p.B = nb
-                return int(work_bytes_of(p, g))
-            per = max(work_bytes(1), 1)
-            gsz = max(1, min(B, int(max_work_bytes) // per))
-            while gsz > 1 and work_bytes(gsz) > max_work_bytes:
-                gsz -= 1
-            work = self._buf(work_bytes(gsz), dev)
+            g, Q = view(dev, inputs.dtype)
+            p, _, input_lengths, _ = self._device_problem(inputs, transition, None, input_lengths, None)
+            groups = self._groups(p, B, max_work_bytes, lambda: work_bytes(p, g), Q,
+                                  lambda: _lib.check(call(p, g, None, 0, None, None, None, None, None, None), what),
+                                  inputs, input_lengths=input_lengths)
             scores = torch.empty(B, dtype=inputs.dtype, device=dev)
             out = torch.empty(3, B, T, dtype=torch.int64, device=dev)        # path, tokens, states
             token_lengths = torch.empty(B, dtype=torch.int64, device=dev)
             stream = self._stream(dev)
             # (no context: the call runs on one stream; nothing is created here once the graph is compiled, so it may run
             # under capture)
-            for b0 in range(0, B, gsz):
-                b1 = min(B, b0 + gsz)
-                x = inputs[:, b0:b1]
-                p.inputs = x.data_ptr()
-                p.B = b1 - b0
-                if input_lengths is not None:
-                    p.input_lengths = input_lengths[b0:b1].data_ptr()
-                _lib.check(call(p, g, work, scores[b0:].data_ptr(), out[0, b0].data_ptr(), out[1, b0].data_ptr(),
-                                token_lengths[b0:].data_ptr(), out[2, b0].data_ptr(), stream), what)
+            for b0, b1, work in groups:
+                _lib.check(call(p, g, work.data_ptr(), work.numel(), scores[b0:].data_ptr(), out[0, b0].data_ptr(),
+                                out[1, b0].data_ptr(), token_lengths[b0:].data_ptr(), out[2, b0].data_ptr(), stream), what)
         return scores, out[0], out[1], token_lengths, out[2]
 
-    def _graph_loss_args(self, inputs, transition, graph, input_lengths, lm_weight, token_score):
-        """Checks shared by the graph-loss entry points -> the compiled graph and its asg_token_graph_loss view."""
-        from . import graph as _graph
-        self._check(inputs, transition, None, input_lengths, None)
-        if inputs.dtype not in (torch.float32, torch.float64):
-            raise RuntimeError("torch_asg_amd: expected scalar type Float or Double but found %s" % inputs.dtype)
-        if not isinstance(graph, _graph.TokenGraph):
-            raise TypeError("torch_asg_amd: graph must be a torch_asg_amd.TokenGraph")
-        T, B, N = inputs.shape
-        if graph.N != N:
-            raise RuntimeError("torch_asg_amd: the graph is over %d tokens but the emissions have N = %d" % (graph.N, N))
-        if input_lengths is not None and tuple(input_lengths.shape) != (B,):
-            raise RuntimeError("torch_asg_amd: input_lengths must have shape [%d]" % B)
-        compiled = graph.compile_loss(inputs.device, inputs.dtype, lm_weight, token_score)
-        return compiled, _graph.abi_graph_loss(compiled)
-
-    def graph_full_forward(self, inputs, transition, graph, input_lengths, lm_weight=1.0, token_score=0.0, store=False,
-                           max_work_bytes=1 << 30, flags=0):
-        """Full score of the lattice composed with a token automaton -> (scores[B], saved); see
-        include/asg_hip.h::asg_graph_full_forward.  Utterances run in consecutive groups whose workspace fits `max_work_bytes`.
-        With `store`, saved = [(b0, b1, work)]: each group's stored alpha, for graph_full_backward; None otherwise."""
+    def beam_decode_words(self, inputs, transition, lexicon, word_lm, input_lengths, beam_size, beam_threshold=float("inf"),
+                          lm_weight=1.0, word_score=0.0, token_score=0.0, max_work_bytes=1 << 30):
+        """Beam search over (LM history, lexicon product state) pairs -> BeamWords; see
+        include/asg_hip.h::asg_beam_decode_words.  Grouped under `max_work_bytes` as `_decode_graph` does."""
+        from . import wordlm as _wordlm
+        _wordlm.check_words(lexicon, word_lm)
+        beam_size, beam_threshold = min(int(beam_size), (1 << 31) - 1), float(beam_threshold)
         L = _lib.lib()
+        self._check_graph_inputs(inputs, transition, lexicon.graph, input_lengths)
+        T, B, N = inputs.shape
         dev = inputs.device
-        B = inputs.shape[1]
         with self._guard(dev):
-            compiled, gl = self._graph_loss_args(inputs, transition, graph, input_lengths, lm_weight, token_score)
-            p, keep = self._problem(inputs, transition, None, input_lengths, None)
-            if input_lengths is not None:
-                input_lengths = keep[-1]
+            g, w, (lex, _) = _wordlm.abi_words(lexicon, word_lm, dev, inputs.dtype, lm_weight, word_score, token_score)
+            p, _, input_lengths, _ = self._device_problem(inputs, transition, None, input_lengths, None)
 
-            def work_bytes(nb):
-                p.B = nb
-                return int(L.asg_graph_full_work_bytes(ctypes.byref(p), ctypes.byref(gl), int(store)))
-            per = max(work_bytes(1), 1)
-            gsz = max(1, min(B, int(max_work_bytes) // per))
-            while gsz > 1 and work_bytes(gsz) > max_work_bytes:
-                gsz -= 1
+            def call(work, nbytes, *outs):
+                return L.asg_beam_decode_words(None, ctypes.byref(p), ctypes.byref(g), ctypes.byref(w), beam_size, beam_threshold,
+                                               work, nbytes, *outs)
+            groups = self._groups(
+                p, B, max_work_bytes,
+                lambda: L.asg_beam_decode_words_work_bytes(ctypes.byref(p), ctypes.byref(g), ctypes.byref(w), beam_size), lex["Q"],
+                lambda: _lib.check(call(None, 0, *(None,) * 8, 0, None), "asg_beam_decode_words"),
+                inputs, input_lengths=input_lengths)
             scores = torch.empty(B, dtype=inputs.dtype, device=dev)
-            fl = flags | (_lib.FLAG_GRAPH_LOSS_KEEP_ALPHA if store else 0)
+            out = torch.empty(5, B, T, dtype=torch.int64, device=dev)      # path, tokens, states, lm_states, words
+            lengths = torch.empty(2, B, dtype=torch.int64, device=dev)     # token_lengths, word_lengths
             stream = self._stream(dev)
-            saved, work = [], None
-            for b0 in range(0, B, gsz):
-                b1 = min(B, b0 + gsz)
-                if store or work is None:
-                    work = self._buf(work_bytes(b1 - b0), dev)
-                p.inputs = inputs[:, b0:b1].data_ptr()
-                p.B = b1 - b0
-                if input_lengths is not None:
-                    p.input_lengths = input_lengths[b0:b1].data_ptr()
-                _lib.check(L.asg_graph_full_forward(None, ctypes.byref(p), ctypes.byref(gl), work.data_ptr(), work.numel(),
-                                                    scores[b0:].data_ptr(), fl, stream), "asg_graph_full_forward")
-                if store:
-                    saved.append((b0, b1, work))
-        return scores, (saved if store else None)
+            for b0, b1, work in groups:
+                _lib.check(call(work.data_ptr(), work.numel(), scores[b0:].data_ptr(), out[0, b0].data_ptr(),
+                                out[1, b0].data_ptr(), lengths[0, b0:].data_ptr(), out[2, b0].data_ptr(), out[3, b0].data_ptr(),
+                                out[4, b0].data_ptr(), lengths[1, b0:].data_ptr(), 0, stream), "asg_beam_decode_words")
+        return BeamWords(scores, out[0], out[1], lengths[0], out[2], out[3], out[4], lengths[1])
 
-    def graph_full_backward(self, saved, scores, grad_scores, inputs, transition, graph, input_lengths, lm_weight=1.0,
-                            token_score=0.0, flags=0):
-        """(grad_transition[N,N], grad_inputs[T,B,N]) of sum_b grad_scores[b] * scores[b] from graph_full_forward's saved alpha."""
-        L = _lib.lib()
-        dev = inputs.device
-        T, B, N = inputs.shape
-        with self._guard(dev):
-            compiled, gl = self._graph_loss_args(inputs, transition, graph, input_lengths, lm_weight, token_score)
-            p, keep = self._problem(inputs, transition, None, input_lengths, None)
-            if input_lengths is not None:
-                input_lengths = keep[-1]
-            gs = grad_scores.to(inputs.dtype).contiguous()
-            gin = torch.empty(T, B, N, dtype=inputs.dtype, device=dev)
-            gtr = None
-            stream = self._stream(dev)
-            for b0, b1, work in saved:
-                nb = b1 - b0
-                p.inputs = inputs[:, b0:b1].data_ptr()
-                p.B = nb
-                if input_lengths is not None:
-                    p.input_lengths = input_lengths[b0:b1].data_ptr()
-                scratch = self._buf(L.asg_graph_full_scratch_bytes(ctypes.byref(p), ctypes.byref(gl)), dev)
-                gin_g = gin if nb == B else torch.empty(T, nb, N, dtype=inputs.dtype, device=dev)
-                gtr_g = torch.empty(N, N, dtype=inputs.dtype, device=dev)
-                _lib.check(L.asg_graph_full_backward(None, ctypes.byref(p), ctypes.byref(gl), work.data_ptr(), work.numel(),
-                                                     scores[b0:].data_ptr(), gs[b0:].data_ptr(), gin_g.data_ptr(),
-                                                     gtr_g.data_ptr(), scratch.data_ptr(), scratch.numel(), flags, stream),
-                           "asg_graph_full_backward")
-                if nb != B:
-                    gin[:, b0:b1].copy_(gin_g)
-                gtr = gtr_g if gtr is None else gtr + gtr_g
-        return gtr, gin
-
-    def _beam_loss_args(self, inputs, transition, graph, input_lengths, targets, target_lengths, lm_weight, token_score):
-        """Checks shared by the beam-pruned loss entry points -> the asg_token_graph_beam_loss view of the compiled graph."""
+    def _check_graph_inputs(self, inputs, transition, graph, input_lengths, targets=None, target_lengths=None):
+        """The argument checks of every entry point that takes a token automaton."""
         from . import graph as _graph
         self._check(inputs, transition, targets, input_lengths, target_lengths)
         if inputs.dtype not in (torch.float32, torch.float64):
@@ -654,7 +464,13 @@ class HipBackend:
             raise RuntimeError("torch_asg_amd: the graph is over %d tokens but the emissions have N = %d" % (graph.N, N))
         if input_lengths is not None and tuple(input_lengths.shape) != (B,):
             raise RuntimeError("torch_asg_amd: input_lengths must have shape [%d]" % B)
-        return _graph.abi_graph_beam_loss(graph.compile_beam_loss(inputs.device, inputs.dtype, lm_weight, token_score))
+
+    def _device_problem(self, inputs, transition, targets, input_lengths, target_lengths):
+        """(p, targets, input_lengths, target_lengths): the problem block and the batch-indexed tensors it points at, as
+        `_groups` slices them (on the device, lengths contiguous)."""
+        targets, input_lengths, target_lengths = self.device_args(inputs.device, targets, input_lengths, target_lengths)
+        p, _ = self._problem(inputs, transition, targets, input_lengths, target_lengths)
+        return p, targets, input_lengths, target_lengths
 
     @staticmethod
     def _group_problem(p, b0, b1, inputs, targets, input_lengths, target_lengths):
@@ -668,6 +484,155 @@ class HipBackend:
         if target_lengths is not None:
             p.target_lengths = target_lengths[b0:b1].data_ptr()
 
+    def _groups(self, p, B, max_work_bytes, work_bytes, Q, refused, inputs, targets=None, input_lengths=None,
+                target_lengths=None, store=False, saved=None):
+        """The consecutive utterance groups of one call whose workspace fits `max_work_bytes` (at least one utterance per
+        group) -> an iterator of (b0, b1, work) that has pointed problem `p` at utterances b0 .. b1 (`_group_problem`) when
+        it yields them.  `work_bytes()` is the library's workspace size for `p` as it stands.  A size of 0 for one utterance
+        of an automaton with product states (Q > 0; with none there is nothing to keep) is the library refusing the
+        arguments: `refused()`, the entry point's own call without buffers, raises with its status -- here and not in the
+        iterator, so before the caller sizes outputs by those arguments.  One workspace of the first (largest) group's size
+        serves every group; with `store` every group gets its own, sized for it, for the caller to keep.  A batch that fits one
+        group is the problem as it stands: nothing is sliced (host time of the common call).  With `saved`, the
+        [(b0, b1, work)] such a call kept, nothing is sized: the iterator points `p` at those groups again (the backward
+        passes)."""
+        if saved is None:
+            def sized(nb):
+                p.B = nb
+                return int(work_bytes())
+            per = sized(1)
+            if per == 0 and Q:
+                p.B = B
+                refused()
+            gsz = max(1, min(B, int(max_work_bytes) // max(per, 1)))
+            while gsz > 1 and sized(gsz) > max_work_bytes:
+                gsz -= 1
+            if gsz == B:
+                return ((0, B, self._buf(sized(B), inputs.device)),)
+
+        def walk():
+            if saved is not None:
+                for b0, b1, work in saved:
+                    self._group_problem(p, b0, b1, inputs, targets, input_lengths, target_lengths)
+                    yield b0, b1, work
+                return
+            work = None
+            for b0 in range(0, B, gsz):
+                b1 = min(B, b0 + gsz)
+                if store or work is None:
+                    work = self._buf(sized(b1 - b0), inputs.device)
+                self._group_problem(p, b0, b1, inputs, targets, input_lengths, target_lengths)
+                yield b0, b1, work
+        return walk()
+
+    def beam_decode_graph_nbest(self, inputs, transition, graph, input_lengths, beam_size, nbest, beam_threshold=float("inf"),
+                                lm_weight=1.0, token_score=0.0, return_alignments=False, max_work_bytes=1 << 30):
+        """The n best final hypotheses of the beam search with their score split -> (scores, emission_scores, graph_scores
+        [B,nbest], tokens [B,nbest,T], token_lengths [B,nbest], num_hyps [B], path, states [B,nbest,T] or None); see
+        include/asg_hip.h::asg_beam_decode_graph_nbest.  Grouped under `max_work_bytes` as `_decode_graph` does."""
+        from . import graph as _graph
+        beam_size, beam_threshold = min(int(beam_size), (1 << 31) - 1), float(beam_threshold)
+        nbest = min(int(nbest), (1 << 31) - 1)
+        L = _lib.lib()
+        self._check_graph_inputs(inputs, transition, graph, input_lengths)
+        T, B, N = inputs.shape
+        dev = inputs.device
+        with self._guard(dev):
+            compiled = graph.compile_beam(dev, inputs.dtype, lm_weight, token_score)
+            g = _graph.abi_graph_beam(compiled)
+            p, _, input_lengths, _ = self._device_problem(inputs, transition, None, input_lengths, None)
+
+            def call(work, nbytes, *outs):
+                return L.asg_beam_decode_graph_nbest(None, ctypes.byref(p), ctypes.byref(g), beam_size, beam_threshold, nbest,
+                                                     work, nbytes, *outs)
+            groups = self._groups(
+                p, B, max_work_bytes,
+                lambda: L.asg_beam_decode_graph_nbest_work_bytes(ctypes.byref(p), ctypes.byref(g), beam_size, nbest), compiled["Q"],
+                lambda: _lib.check(call(None, 0, *(None,) * 8, 0, None), "asg_beam_decode_graph_nbest"),
+                inputs, input_lengths=input_lengths)
+            sc = torch.empty(3, B, nbest, dtype=inputs.dtype, device=dev)      # scores, emission_scores, graph_scores
+            tokens = torch.empty(B, nbest, T, dtype=torch.int64, device=dev)
+            align = torch.empty(2, B, nbest, T, dtype=torch.int64, device=dev) if return_alignments else None
+            token_lengths = torch.empty(B, nbest, dtype=torch.int64, device=dev)
+            num_hyps = torch.empty(B, dtype=torch.int64, device=dev)
+            stream = self._stream(dev)
+            for b0, b1, work in groups:
+                _lib.check(call(work.data_ptr(), work.numel(), sc[0, b0:].data_ptr(), sc[1, b0:].data_ptr(), sc[2, b0:].data_ptr(),
+                                align[0, b0:].data_ptr() if return_alignments else None, tokens[b0:].data_ptr(),
+                                token_lengths[b0:].data_ptr(), align[1, b0:].data_ptr() if return_alignments else None,
+                                num_hyps[b0:].data_ptr(), 0, stream), "asg_beam_decode_graph_nbest")
+        return BeamNbest(sc[0], sc[1], sc[2], tokens, token_lengths, num_hyps,
+                         align[0] if return_alignments else None, align[1] if return_alignments else None)
+
+    def _graph_loss_args(self, inputs, transition, graph, input_lengths, lm_weight, token_score, targets=None,
+                         target_lengths=None):
+        """Checks shared by the graph-loss entry points -> the compiled graph and its asg_token_graph_loss view."""
+        from . import graph as _graph
+        self._check_graph_inputs(inputs, transition, graph, input_lengths, targets, target_lengths)
+        compiled = graph.compile_loss(inputs.device, inputs.dtype, lm_weight, token_score)
+        return compiled, _graph.abi_graph_loss(compiled)
+
+    def graph_full_forward(self, inputs, transition, graph, input_lengths, lm_weight=1.0, token_score=0.0, store=False,
+                           max_work_bytes=1 << 30, flags=0):
+        """Full score of the lattice composed with a token automaton -> (scores[B], saved); see
+        include/asg_hip.h::asg_graph_full_forward.  Utterances run in consecutive groups whose workspace fits `max_work_bytes`.
+        With `store`, saved = [(b0, b1, work)]: each group's stored alpha, for graph_full_backward; None otherwise."""
+        L = _lib.lib()
+        dev = inputs.device
+        B = inputs.shape[1]
+        with self._guard(dev):
+            compiled, gl = self._graph_loss_args(inputs, transition, graph, input_lengths, lm_weight, token_score)
+            p, _, input_lengths, _ = self._device_problem(inputs, transition, None, input_lengths, None)
+            fl = flags | (_lib.FLAG_GRAPH_LOSS_KEEP_ALPHA if store else 0)
+
+            def call(work, nbytes, scores, stream):
+                return L.asg_graph_full_forward(None, ctypes.byref(p), ctypes.byref(gl), work, nbytes, scores, fl, stream)
+            groups = self._groups(p, B, max_work_bytes,
+                                  lambda: L.asg_graph_full_work_bytes(ctypes.byref(p), ctypes.byref(gl), int(store)), compiled["Q"],
+                                  lambda: _lib.check(call(None, 0, None, None), "asg_graph_full_forward"),
+                                  inputs, input_lengths=input_lengths, store=store)
+            scores = torch.empty(B, dtype=inputs.dtype, device=dev)
+            stream = self._stream(dev)
+            saved = []
+            for b0, b1, work in groups:
+                _lib.check(call(work.data_ptr(), work.numel(), scores[b0:].data_ptr(), stream), "asg_graph_full_forward")
+                saved.append((b0, b1, work))
+        return scores, (saved if store else None)
+
+    def graph_full_backward(self, saved, scores, grad_scores, inputs, transition, graph, input_lengths, lm_weight=1.0,
+                            token_score=0.0, flags=0):
+        """(grad_transition[N,N], grad_inputs[T,B,N]) of sum_b grad_scores[b] * scores[b] from graph_full_forward's saved alpha."""
+        L = _lib.lib()
+        dev = inputs.device
+        T, B, N = inputs.shape
+        with self._guard(dev):
+            compiled, gl = self._graph_loss_args(inputs, transition, graph, input_lengths, lm_weight, token_score)
+            p, _, input_lengths, _ = self._device_problem(inputs, transition, None, input_lengths, None)
+            gs = grad_scores.to(inputs.dtype).contiguous()
+            gin = torch.empty(T, B, N, dtype=inputs.dtype, device=dev)
+            gtr = None
+            stream = self._stream(dev)
+            for b0, b1, work in self._groups(p, B, None, None, None, None, inputs, input_lengths=input_lengths, saved=saved):
+                nb = b1 - b0
+                scratch = self._buf(L.asg_graph_full_scratch_bytes(ctypes.byref(p), ctypes.byref(gl)), dev)
+                gin_g = gin if nb == B else torch.empty(T, nb, N, dtype=inputs.dtype, device=dev)
+                gtr_g = torch.empty(N, N, dtype=inputs.dtype, device=dev)
+                _lib.check(L.asg_graph_full_backward(None, ctypes.byref(p), ctypes.byref(gl), work.data_ptr(), work.numel(),
+                                                     scores[b0:].data_ptr(), gs[b0:].data_ptr(), gin_g.data_ptr(),
+                                                     gtr_g.data_ptr(), scratch.data_ptr(), scratch.numel(), flags, stream),
+                           "asg_graph_full_backward")
+                if nb != B:
+                    gin[:, b0:b1].copy_(gin_g)
+                gtr = gtr_g if gtr is None else gtr + gtr_g
+        return gtr, gin
+
+    def _beam_loss_args(self, inputs, transition, graph, input_lengths, targets, target_lengths, lm_weight, token_score):
+        """Checks shared by the beam-pruned loss entry points -> the compiled graph and its asg_token_graph_beam_loss view."""
+        from . import graph as _graph
+        self._check_graph_inputs(inputs, transition, graph, input_lengths, targets, target_lengths)
+        compiled = graph.compile_beam_loss(inputs.device, inputs.dtype, lm_weight, token_score)
+        return compiled, _graph.abi_graph_beam_loss(compiled)
+
     def beam_graph_full_forward(self, inputs, transition, graph, input_lengths, beam_size, beam_threshold=float("inf"),
                                 lm_weight=1.0, token_score=0.0, targets=None, target_lengths=None, store=False,
                                 max_work_bytes=1 << 30):
@@ -679,35 +644,26 @@ class HipBackend:
         B = inputs.shape[1]
         beam_size, beam_threshold = min(int(beam_size), (1 << 31) - 1), float(beam_threshold)
         with self._guard(dev):
-            gl = self._beam_loss_args(inputs, transition, graph, input_lengths, targets, target_lengths, lm_weight, token_score)
-            p, keep = self._problem(inputs, transition, targets, input_lengths, target_lengths)
-            targets, input_lengths, target_lengths = self.device_args(dev, targets, input_lengths, target_lengths)
-
-            def work_bytes(nb):
-                p.B = nb
-                return int(L.asg_beam_graph_full_work_bytes(ctypes.byref(p), ctypes.byref(gl), beam_size, int(store)))
-            per = work_bytes(1)
-            if per == 0:
-                p.B = B
-                _lib.check(L.asg_beam_graph_full_forward(None, ctypes.byref(p), ctypes.byref(gl), beam_size, beam_threshold, None,
-                                                         0, None, 0, None), "asg_beam_graph_full_forward")
-            gsz = max(1, min(B, int(max_work_bytes) // per))
-            while gsz > 1 and work_bytes(gsz) > max_work_bytes:
-                gsz -= 1
-            scores = torch.empty(B, dtype=inputs.dtype, device=dev)
+            compiled, gl = self._beam_loss_args(inputs, transition, graph, input_lengths, targets, target_lengths, lm_weight,
+                                                token_score)
+            p, targets, input_lengths, target_lengths = self._device_problem(inputs, transition, targets, input_lengths,
+                                                                             target_lengths)
             fl = _lib.FLAG_GRAPH_LOSS_KEEP_ALPHA if store else 0
+
+            def call(work, nbytes, scores, stream):
+                return L.asg_beam_graph_full_forward(None, ctypes.byref(p), ctypes.byref(gl), beam_size, beam_threshold, work,
+                                                     nbytes, scores, fl, stream)
+            groups = self._groups(
+                p, B, max_work_bytes,
+                lambda: L.asg_beam_graph_full_work_bytes(ctypes.byref(p), ctypes.byref(gl), beam_size, int(store)), compiled["Q"],
+                lambda: _lib.check(call(None, 0, None, None), "asg_beam_graph_full_forward"),
+                inputs, targets, input_lengths, target_lengths, store=store)
+            scores = torch.empty(B, dtype=inputs.dtype, device=dev)
             stream = self._stream(dev)
-            saved, work = [], None
-            for b0 in range(0, B, gsz):
-                b1 = min(B, b0 + gsz)
-                if store or work is None:
-                    work = self._buf(work_bytes(b1 - b0), dev)
-                self._group_problem(p, b0, b1, inputs, targets, input_lengths, target_lengths)
-                _lib.check(L.asg_beam_graph_full_forward(None, ctypes.byref(p), ctypes.byref(gl), beam_size, beam_threshold,
-                                                         work.data_ptr(), work.numel(), scores[b0:].data_ptr(), fl, stream),
-                           "asg_beam_graph_full_forward")
-                if store:
-                    saved.append((b0, b1, work))
+            saved = []
+            for b0, b1, work in groups:
+                _lib.check(call(work.data_ptr(), work.numel(), scores[b0:].data_ptr(), stream), "asg_beam_graph_full_forward")
+                saved.append((b0, b1, work))
         return scores, (saved if store else None)
 
     def beam_graph_full_backward(self, saved, scores, grad_scores, inputs, transition, graph, input_lengths, beam_size,
@@ -719,16 +675,17 @@ class HipBackend:
         T, B, N = inputs.shape
         beam_size = min(int(beam_size), (1 << 31) - 1)
         with self._guard(dev):
-            gl = self._beam_loss_args(inputs, transition, graph, input_lengths, targets, target_lengths, lm_weight, token_score)
-            p, keep = self._problem(inputs, transition, targets, input_lengths, target_lengths)
-            targets, input_lengths, target_lengths = self.device_args(dev, targets, input_lengths, target_lengths)
+            compiled, gl = self._beam_loss_args(inputs, transition, graph, input_lengths, targets, target_lengths, lm_weight,
+                                                token_score)
+            p, targets, input_lengths, target_lengths = self._device_problem(inputs, transition, targets, input_lengths,
+                                                                             target_lengths)
             gs = grad_scores.to(inputs.dtype).contiguous()
             gin = torch.empty(T, B, N, dtype=inputs.dtype, device=dev)
             gtr = torch.empty(N, N, dtype=inputs.dtype, device=dev)
             stream = self._stream(dev)
-            for n, (b0, b1, work) in enumerate(saved):
+            groups = self._groups(p, B, None, None, None, None, inputs, targets, input_lengths, target_lengths, saved=saved)
+            for n, (b0, b1, work) in enumerate(groups):
                 nb = b1 - b0
-                self._group_problem(p, b0, b1, inputs, targets, input_lengths, target_lengths)
                 scratch = self._buf(L.asg_beam_graph_full_scratch_bytes(ctypes.byref(p), ctypes.byref(gl), beam_size), dev)
                 gin_g = gin if nb == B else torch.empty(T, nb, N, dtype=inputs.dtype, device=dev)
                 _lib.check(L.asg_beam_graph_full_backward(None, ctypes.byref(p), ctypes.byref(gl), beam_size, work.data_ptr(),
@@ -745,9 +702,8 @@ class HipBackend:
         include/asg_hip.h::asg_graph_target_scores."""
         L = _lib.lib()
         dev = inputs.device
-        self._check(inputs, transition, targets, None, target_lengths)
         with self._guard(dev):
-            compiled, gl = self._graph_loss_args(inputs, transition, graph, None, lm_weight, token_score)
+            compiled, gl = self._graph_loss_args(inputs, transition, graph, None, lm_weight, token_score, targets, target_lengths)
             p, keep = self._problem(inputs, transition, targets, None, target_lengths)
             out = torch.empty(inputs.shape[1], dtype=inputs.dtype, device=dev)
             _lib.check(L.asg_graph_target_scores(None, ctypes.byref(p), ctypes.byref(gl), out.data_ptr(), self._stream(dev)),
@@ -977,6 +933,25 @@ def native():
     return _backend
 
 
+def _check_beam(beam_size, beam_threshold):
+    if int(beam_size) < 1:
+        raise ValueError("torch_asg_amd: beam_size must be >= 1, got %d" % int(beam_size))
+    if not float(beam_threshold) >= 0.0:
+        raise ValueError("torch_asg_amd: beam_threshold must be >= 0 (inf: none), got %r" % (beam_threshold,))
+
+
+def _widen(inputs, transition):
+    """float16 / bfloat16 emissions widened to the dtype of `transition`; every other dtype as it is."""
+    if inputs.dtype in (torch.float16, torch.bfloat16):
+        return inputs.to(transition.dtype)
+    return inputs
+
+
+def _plain(inputs, transition):
+    """(emissions, transition) as a decoder takes them: half precision widened, no autograd history."""
+    return _widen(inputs, transition).detach(), transition.detach()
+
+
 def viterbi_align(inputs, targets, transition, input_lengths=None, target_lengths=None):
     """Best-path (Viterbi) force alignment of `targets` to `inputs` under the ASG transition model -- the
     force-aligned lattice of the loss (force_aligned_lattice.cpp:84-111) with max instead of logsumexp
@@ -1017,10 +992,8 @@ def viterbi_decode(inputs, transition, input_lengths=None):
     input_is_logits=True decodes its raw logits and their log_softmax to the same path); the score shifts by that
     constant.
     """
-    if inputs.dtype in (torch.float16, torch.bfloat16):
-        inputs = inputs.to(transition.dtype)
     with torch.no_grad():
-        return native().viterbi_decode(inputs.detach(), transition.detach(), input_lengths)
+        return native().viterbi_decode(*_plain(inputs, transition), input_lengths)
 
 
 def viterbi_decode_graph(inputs, transition, graph, input_lengths=None, lm_weight=1.0, token_score=0.0,
@@ -1041,11 +1014,9 @@ def viterbi_decode_graph(inputs, transition, graph, input_lengths=None, lm_weigh
     nothing to the device and do not synchronise, so they can be captured.  The batch is decoded in consecutive groups of
     utterances whose workspace (int32 back-pointers, T * Q * 4 bytes per utterance) fits `max_work_bytes`.
     """
-    if inputs.dtype in (torch.float16, torch.bfloat16):
-        inputs = inputs.to(transition.dtype)
     with torch.no_grad():
-        return native().viterbi_decode_graph(inputs.detach(), transition.detach(), graph, input_lengths, lm_weight,
-                                             token_score, max_work_bytes)
+        return native().viterbi_decode_graph(*_plain(inputs, transition), graph, input_lengths, lm_weight, token_score,
+                                             max_work_bytes)
 
 
 def beam_decode_graph(inputs, transition, graph, input_lengths=None, beam_size=256, beam_threshold=float("inf"), lm_weight=1.0,
@@ -1069,15 +1040,10 @@ def beam_decode_graph(inputs, transition, graph, input_lengths=None, beam_size=2
     utterances whose workspace (about T * beam_size * 8 bytes of back-pointers plus 12-16 bytes per product state and
     utterance) fits `max_work_bytes`.
     """
-    if int(beam_size) < 1:
-        raise ValueError("torch_asg_amd: beam_size must be >= 1, got %d" % int(beam_size))
-    if not float(beam_threshold) >= 0.0:
-        raise ValueError("torch_asg_amd: beam_threshold must be >= 0 (inf: none), got %r" % (beam_threshold,))
-    if inputs.dtype in (torch.float16, torch.bfloat16):
-        inputs = inputs.to(transition.dtype)
+    _check_beam(beam_size, beam_threshold)
     with torch.no_grad():
-        return native().beam_decode_graph(inputs.detach(), transition.detach(), graph, input_lengths, beam_size, beam_threshold,
-                                          lm_weight, token_score, max_work_bytes)
+        return native().beam_decode_graph(*_plain(inputs, transition), graph, input_lengths, beam_size, beam_threshold, lm_weight,
+                                          token_score, max_work_bytes)
 
 
 BeamWords = collections.namedtuple("BeamWords", ["scores", "path", "tokens", "token_lengths", "states", "lm_states", "words",
@@ -1112,15 +1078,10 @@ def beam_decode_words(inputs, transition, lexicon, word_lm, input_lengths=None, 
     workspace (about T * beam_size * 12 bytes of back-pointers plus 60-80 bytes per candidate a frame can have, beam_size *
     (largest out-degree + 1)) fits `max_work_bytes`.
     """
-    if int(beam_size) < 1:
-        raise ValueError("torch_asg_amd: beam_size must be >= 1, got %d" % int(beam_size))
-    if not float(beam_threshold) >= 0.0:
-        raise ValueError("torch_asg_amd: beam_threshold must be >= 0 (inf: none), got %r" % (beam_threshold,))
-    if inputs.dtype in (torch.float16, torch.bfloat16):
-        inputs = inputs.to(transition.dtype)
+    _check_beam(beam_size, beam_threshold)
     with torch.no_grad():
-        return native().beam_decode_words(inputs.detach(), transition.detach(), lexicon, word_lm, input_lengths, beam_size,
-                                          beam_threshold, lm_weight, word_score, token_score, max_work_bytes)
+        return native().beam_decode_words(*_plain(inputs, transition), lexicon, word_lm, input_lengths, beam_size, beam_threshold,
+                                          lm_weight, word_score, token_score, max_work_bytes)
 
 
 BeamNbest = collections.namedtuple("BeamNbest", ["scores", "emission_scores", "graph_scores", "tokens", "token_lengths",
@@ -1151,419 +1112,9 @@ def beam_decode_graph_nbest(inputs, transition, graph, input_lengths=None, beam_
     _check_beam(beam_size, beam_threshold)
     if int(nbest) < 1:
         raise ValueError("torch_asg_amd: nbest must be >= 1, got %d" % int(nbest))
-    if inputs.dtype in (torch.float16, torch.bfloat16):
-        inputs = inputs.to(transition.dtype)
     with torch.no_grad():
-        return native().beam_decode_graph_nbest(inputs.detach(), transition.detach(), graph, input_lengths, beam_size, nbest,
+        return native().beam_decode_graph_nbest(*_plain(inputs, transition), graph, input_lengths, beam_size, nbest,
                                                 beam_threshold, lm_weight, token_score, return_alignments, max_work_bytes)
-
-
-BeamStreamResult = collections.namedtuple("BeamStreamResult", ["scores", "path", "tokens", "token_lengths", "states", "frames",
-                                                               "status"])
-
-
-class BeamStream:
-    """`beam_decode_graph` for an utterance that arrives in chunks: the beam search carried from one chunk to the next, for
-    `batch_size` utterance slots at a time.  No gradient.
-
-        s = BeamStream(transition, graph, batch_size, max_frames, beam_size=256)
-        for chunk in chunks:                 # [Tc, B, N] each
-            s.advance(chunk)
-            partial = s.result()             # the best prefix hypothesis so far; the stream goes on
-        final = s.result(final=True)         # what beam_decode_graph returns for the whole utterance, bit for bit
-
-    The search is `beam_decode_graph`'s, frame by frame, with the same device code (include/asg_hip.h::asg_beam_stream_advance):
-    for any way of cutting an utterance of at most `max_frames` frames into chunks, `result(final=True)` equals the one-shot
-    decode of the whole utterance -- scores and token_lengths bit for bit, path / tokens / states on the one-shot's columns and
-    -1 beyond.  `transition` (a tensor or Parameter of dtype `dtype`; it is read again at every `advance`), `beam_threshold`,
-    `lm_weight` and `token_score` are those of `beam_decode_graph`; the attribute `beam_threshold` may be changed between chunks.
-
-    The state lives in one device buffer (about max_frames * beam_size * 8 bytes of back-pointers plus 12-16 bytes per product
-    state, per slot).  The graph is compiled in the constructor; `advance`, `result` and `reset` are one kernel launch each, copy
-    nothing and do not synchronise, so they can be captured in a graph and replayed with new chunk contents and lengths.
-    """
-
-    def __init__(self, transition, graph, batch_size, max_frames, beam_size=256, beam_threshold=float("inf"), lm_weight=1.0,
-                 token_score=0.0, dtype=torch.float32, device=None):
-        from . import graph as _graph
-        _check_beam(beam_size, beam_threshold)
-        if not isinstance(graph, _graph.TokenGraph):
-            raise TypeError("torch_asg_amd: graph must be a torch_asg_amd.TokenGraph")
-        if int(batch_size) < 1 or int(max_frames) < 1:
-            raise ValueError("torch_asg_amd: batch_size and max_frames must be >= 1, got %d and %d"
-                             % (int(batch_size), int(max_frames)))
-        if dtype not in (torch.float32, torch.float64):
-            raise RuntimeError("torch_asg_amd: expected scalar type Float or Double but found %s" % dtype)
-        device = torch.device(device) if device is not None else transition.device
-        if device.type != "cuda":
-            raise RuntimeError("torch_asg_amd: a BeamStream must live on a ROCm device (got %s); "
-                               "there is no CPU implementation in this package" % device)
-        if transition.dtype != dtype or transition.device != device or tuple(transition.shape) != (graph.N, graph.N):
-            raise RuntimeError("torch_asg_amd: transition must be [%d,%d] with the dtype/device of the stream" % (graph.N, graph.N))
-        self.transition, self.graph = transition, graph
-        self.batch_size, self.max_frames = int(batch_size), int(max_frames)
-        self.beam_size, self.beam_threshold = min(int(beam_size), (1 << 31) - 1), float(beam_threshold)
-        self.lm_weight, self.token_score, self.dtype, self.device = lm_weight, token_score, dtype, device
-        be = native()
-        L = _lib.lib()
-        with be._guard(device):
-            self._compiled = graph.compile_beam(device, dtype, lm_weight, token_score)
-            self._g = _graph.abi_graph_beam(self._compiled)
-            abi_dtype = _lib.ASG_DTYPE_F32 if dtype == torch.float32 else _lib.ASG_DTYPE_F64
-            nbytes = int(L.asg_beam_stream_state_bytes(ctypes.byref(self._g), self.batch_size, abi_dtype, self.beam_size,
-                                                       self.max_frames))
-            if nbytes == 0:                                    # the library refuses the arguments: its call says why
-                _lib.check(L.asg_beam_stream_reset(None, ctypes.byref(self._g), self.batch_size, self.beam_size, self.max_frames,
-                                                   None, 0, None, 0, None), "asg_beam_stream_reset")
-            self._state = be._buf(nbytes, device)
-        self._fed = 0                                          # frames offered since the last full reset (the host's bound)
-        self.reset()
-
-    def reset(self, mask=None):
-        """Start new utterances: in every slot (mask None), or in the slots where `mask` (bool or integer [B]) is not zero --
-        the other slots go on.  After a masked reset `advance`'s host-side check of `max_frames` is not tightened; the device
-        clamps and `result().status` reports it."""
-        be = native()
-        L = _lib.lib()
-        m = None
-        if mask is not None:
-            if tuple(mask.shape) != (self.batch_size,):
-                raise RuntimeError("torch_asg_amd: mask must have shape [%d]" % self.batch_size)
-            m = mask.to(self.device).ne(0).to(torch.uint8).contiguous()
-        with be._guard(self.device):
-            _lib.check(L.asg_beam_stream_reset(None, ctypes.byref(self._g), self.batch_size, self.beam_size, self.max_frames,
-                                               self._state.data_ptr(), self._state.numel(), m.data_ptr() if m is not None else None,
-                                               0, be._stream(self.device)), "asg_beam_stream_reset")
-        if mask is None:
-            self._fed = 0
-
-    def advance(self, chunk, chunk_lengths=None):
-        """Consume `chunk` [Tc, B, N]: slot b takes its first clamp(chunk_lengths[b], 0, Tc) frames (all Tc when
-        `chunk_lengths` is None) as the next frames of its utterance.  Chunk dtype, strides and float16 / bfloat16 widening as in
-        `beam_decode_graph`.  ValueError, without touching the device, once the Tc offered since the last full `reset()` exceed
-        `max_frames`."""
-        be = native()
-        L = _lib.lib()
-        transition = self.transition.detach()
-        if chunk.dtype in (torch.float16, torch.bfloat16):
-            chunk = chunk.to(transition.dtype)
-        chunk = chunk.detach()
-        be._check_decode_graph(chunk, transition, self.graph, chunk_lengths)
-        Tc, B, N = chunk.shape
-        if chunk.dtype != self.dtype or chunk.device != self.device or B != self.batch_size:
-            raise RuntimeError("torch_asg_amd: the stream takes chunks [Tc,%d,%d] of %s on %s, got %s of %s on %s"
-                               % (self.batch_size, N, self.dtype, self.device, tuple(chunk.shape), chunk.dtype, chunk.device))
-        _check_beam(self.beam_size, self.beam_threshold)
-        if self._fed + Tc > self.max_frames:
-            raise ValueError("torch_asg_amd: %d frames since the last reset() plus a chunk of %d exceed max_frames = %d"
-                             % (self._fed, Tc, self.max_frames))
-        with be._guard(self.device):
-            p, keep = be._problem(chunk, transition, None, chunk_lengths, None)
-            _lib.check(L.asg_beam_stream_advance(None, ctypes.byref(p), ctypes.byref(self._g), self.beam_size,
-                                                 float(self.beam_threshold), self.max_frames, self._state.data_ptr(),
-                                                 self._state.numel(), 0, be._stream(self.device)), "asg_beam_stream_advance")
-        self._fed += Tc
-
-    def result(self, final=False):
-        """The best hypothesis of every slot over the frames consumed so far, without changing the state -> a named tuple
-          scores [B]; path, tokens, states [B, max_frames] int64, -1 behind the data; token_lengths [B]; frames [B], the frames
-          consumed; status [B], 1 where frames beyond max_frames were offered and dropped.
-        final=True adds the final weights (the transcript of a finished utterance: `beam_decode_graph`'s result); final=False is
-        the best prefix hypothesis, largest value without a final weight.  A slot without frames or with an empty beam: -inf, -1, 0."""
-        be = native()
-        L = _lib.lib()
-        B, T, dev = self.batch_size, self.max_frames, self.device
-        with be._guard(dev):
-            scores = torch.empty(B, dtype=self.dtype, device=dev)
-            out = torch.empty(3, B, T, dtype=torch.int64, device=dev)          # path, tokens, states
-            small = torch.empty(3, B, dtype=torch.int64, device=dev)           # token_lengths, frames, status
-            _lib.check(L.asg_beam_stream_result(None, ctypes.byref(self._g), B, self.beam_size, T, self._state.data_ptr(),
-                                                self._state.numel(), 1 if final else 0, scores.data_ptr(), out[0].data_ptr(),
-                                                out[1].data_ptr(), small[0].data_ptr(), out[2].data_ptr(), small[1].data_ptr(),
-                                                small[2].data_ptr(), 0, be._stream(dev)), "asg_beam_stream_result")
-        return BeamStreamResult(scores, out[0], out[1], small[0], out[2], small[1], small[2])
-
-
-BeamWordStreamResult = collections.namedtuple("BeamWordStreamResult", ["scores", "path", "tokens", "token_lengths", "states",
-                                                                       "lm_states", "words", "word_lengths", "frames", "status"])
-
-
-class BeamWordStream:
-    """`beam_decode_words` for an utterance that arrives in chunks: the beam search over pairs (LM history, lexicon product
-    state), the word LM composed on the fly, carried from one chunk to the next for `batch_size` utterance slots at a time.
-    No gradient.
-
-        s = BeamWordStream(transition, lexicon, word_lm, batch_size, max_frames, beam_size=256)
-        for chunk in chunks:                 # [Tc, B, N] each
-            s.advance(chunk)
-            partial = s.result()             # the best prefix hypothesis so far, its words included; the stream goes on
-        final = s.result(final=True)         # what beam_decode_words returns for the whole utterance, bit for bit
-
-    The search is `beam_decode_words`', frame by frame, with the same device code
-    (include/asg_hip.h::asg_beam_word_stream_advance): for any way of cutting an utterance of at most `max_frames` frames into
-    chunks, `result(final=True)` equals the one-shot decode of the whole utterance -- scores, token_lengths and word_lengths bit
-    for bit, path / tokens / states / lm_states / words on the one-shot's columns and -1 beyond.  `transition` (a tensor or
-    Parameter of dtype `dtype`; it is read again at every `advance`), `beam_threshold`, `lm_weight`, `word_score` and
-    `token_score` are those of `beam_decode_words`; the attribute `beam_threshold` may be changed between chunks.  beam_size >
-    8192 is refused by the library (there is no clamp to the number of product states).
-
-    The state lives in one device buffer (about max_frames * beam_size * 12 bytes of back-pointers plus 60-80 bytes per
-    candidate a frame can have, per slot; nothing is sized by the vocabulary or the LM).  Lexicon and LM are compiled in the
-    constructor; `advance`, `result` and `reset` are one kernel launch each, copy nothing and do not synchronise, so they can be
-    captured in a graph and replayed with new chunk contents and lengths.  Not here: a windowed form with a committed prefix
-    (`BeamWindowStream` over pairs), n-best over pairs, a loss over pairs, LM look-ahead.
-    """
-
-    def __init__(self, transition, lexicon, word_lm, batch_size, max_frames, beam_size=256, beam_threshold=float("inf"),
-                 lm_weight=1.0, word_score=0.0, token_score=0.0, dtype=torch.float32, device=None):
-        from . import graph as _graph
-        from . import wordlm as _wordlm
-        _check_beam(beam_size, beam_threshold)
-        if not isinstance(lexicon, _wordlm.Lexicon):
-            raise TypeError("torch_asg_amd: lexicon must be a torch_asg_amd.Lexicon")
-        if not isinstance(word_lm, _wordlm.WordLM):
-            raise TypeError("torch_asg_amd: word_lm must be a torch_asg_amd.WordLM")
-        wmax = int(lexicon.word_of_state.max(initial=-1))
-        if wmax >= word_lm.V:
-            raise RuntimeError("torch_asg_amd: the lexicon has word id %d but the word LM knows %d words" % (wmax, word_lm.V))
-        if int(batch_size) < 1 or int(max_frames) < 1:
-            raise ValueError("torch_asg_amd: batch_size and max_frames must be >= 1, got %d and %d"
-                             % (int(batch_size), int(max_frames)))
-        if dtype not in (torch.float32, torch.float64):
-            raise RuntimeError("torch_asg_amd: expected scalar type Float or Double but found %s" % dtype)
-        device = torch.device(device) if device is not None else transition.device
-        if device.type != "cuda":
-            raise RuntimeError("torch_asg_amd: a BeamWordStream must live on a ROCm device (got %s); "
-                               "there is no CPU implementation in this package" % device)
-        graph = lexicon.graph
-        if transition.dtype != dtype or transition.device != device or tuple(transition.shape) != (graph.N, graph.N):
-            raise RuntimeError("torch_asg_amd: transition must be [%d,%d] with the dtype/device of the stream" % (graph.N, graph.N))
-        self.transition, self.lexicon, self.word_lm, self.graph = transition, lexicon, word_lm, graph
-        self.batch_size, self.max_frames = int(batch_size), int(max_frames)
-        self.beam_size, self.beam_threshold = min(int(beam_size), (1 << 31) - 1), float(beam_threshold)
-        self.lm_weight, self.word_score, self.token_score = lm_weight, word_score, token_score
-        self.dtype, self.device = dtype, device
-        be = native()
-        L = _lib.lib()
-        with be._guard(device):
-            self._lex = lexicon.compile_words(device, dtype, token_score)
-            self._g = _graph.abi_graph_beam(self._lex)
-            self._lm = word_lm.compile(device, dtype, lm_weight, word_score)
-            self._w = _wordlm.abi_word_lm(self._lm, self._lex)
-            self._w.separator = lexicon.separator
-            abi_dtype = _lib.ASG_DTYPE_F32 if dtype == torch.float32 else _lib.ASG_DTYPE_F64
-            nbytes = int(L.asg_beam_word_stream_state_bytes(ctypes.byref(self._g), ctypes.byref(self._w), self.batch_size,
-                                                            abi_dtype, self.beam_size, self.max_frames))
-            if nbytes == 0:                                    # the library refuses the arguments: its call says why
-                _lib.check(L.asg_beam_word_stream_reset(None, ctypes.byref(self._g), ctypes.byref(self._w), self.batch_size,
-                                                        self.beam_size, self.max_frames, None, 0, None, 0, None),
-                           "asg_beam_word_stream_reset")
-            self._state = be._buf(nbytes, device)
-        self._fed = 0                                          # frames offered since the last full reset (the host's bound)
-        self.reset()
-
-    def reset(self, mask=None):
-        """Start new utterances: in every slot (mask None), or in the slots where `mask` (bool or integer [B]) is not zero --
-        the other slots go on.  After a masked reset `advance`'s host-side check of `max_frames` is not tightened; the device
-        clamps and `result().status` reports it."""
-        be = native()
-        L = _lib.lib()
-        m = None
-        if mask is not None:
-            if tuple(mask.shape) != (self.batch_size,):
-                raise RuntimeError("torch_asg_amd: mask must have shape [%d]" % self.batch_size)
-            m = mask.to(self.device).ne(0).to(torch.uint8).contiguous()
-        with be._guard(self.device):
-            _lib.check(L.asg_beam_word_stream_reset(None, ctypes.byref(self._g), ctypes.byref(self._w), self.batch_size,
-                                                    self.beam_size, self.max_frames, self._state.data_ptr(), self._state.numel(),
-                                                    m.data_ptr() if m is not None else None, 0, be._stream(self.device)),
-                       "asg_beam_word_stream_reset")
-        if mask is None:
-            self._fed = 0
-
-    def advance(self, chunk, chunk_lengths=None):
-        """Consume `chunk` [Tc, B, N]: slot b takes its first clamp(chunk_lengths[b], 0, Tc) frames (all Tc when
-        `chunk_lengths` is None) as the next frames of its utterance.  Chunk dtype, strides and float16 / bfloat16 widening as in
-        `beam_decode_words`.  ValueError, without touching the device, once the Tc offered since the last full `reset()` exceed
-        `max_frames`."""
-        be = native()
-        L = _lib.lib()
-        transition = self.transition.detach()
-        if chunk.dtype in (torch.float16, torch.bfloat16):
-            chunk = chunk.to(transition.dtype)
-        chunk = chunk.detach()
-        be._check_decode_graph(chunk, transition, self.graph, chunk_lengths)
-        Tc, B, N = chunk.shape
-        if chunk.dtype != self.dtype or chunk.device != self.device or B != self.batch_size:
-            raise RuntimeError("torch_asg_amd: the stream takes chunks [Tc,%d,%d] of %s on %s, got %s of %s on %s"
-                               % (self.batch_size, N, self.dtype, self.device, tuple(chunk.shape), chunk.dtype, chunk.device))
-        _check_beam(self.beam_size, self.beam_threshold)
-        if self._fed + Tc > self.max_frames:
-            raise ValueError("torch_asg_amd: %d frames since the last reset() plus a chunk of %d exceed max_frames = %d"
-                             % (self._fed, Tc, self.max_frames))
-        with be._guard(self.device):
-            p, keep = be._problem(chunk, transition, None, chunk_lengths, None)
-            _lib.check(L.asg_beam_word_stream_advance(None, ctypes.byref(p), ctypes.byref(self._g), ctypes.byref(self._w),
-                                                      self.beam_size, float(self.beam_threshold), self.max_frames,
-                                                      self._state.data_ptr(), self._state.numel(), 0, be._stream(self.device)),
-                       "asg_beam_word_stream_advance")
-        self._fed += Tc
-
-    def result(self, final=False):
-        """The best hypothesis of every slot over the frames consumed so far, without changing the state -> a named tuple
-          scores [B]; path, tokens, states, lm_states, words [B, max_frames] int64, -1 behind the data; token_lengths,
-          word_lengths [B]; frames [B], the frames consumed; status [B], 1 where frames beyond max_frames were offered and dropped.
-        final=True is the end of `beam_decode_words` (final weight, the LM's end of the sentence, after one more LM step for a
-        path that ends in a word-end node, whose word is appended; a path that ends mid-word does not count).  final=False is the
-        best prefix hypothesis, the largest value without any end term: it may end mid-word, and `words` holds the words whose
-        separator the path has passed.  A slot without frames, with an empty beam or without a finite score: -inf, -1, 0."""
-        be = native()
-        L = _lib.lib()
-        B, T, dev = self.batch_size, self.max_frames, self.device
-        with be._guard(dev):
-            scores = torch.empty(B, dtype=self.dtype, device=dev)
-            out = torch.empty(5, B, T, dtype=torch.int64, device=dev)          # path, tokens, states, lm_states, words
-            small = torch.empty(4, B, dtype=torch.int64, device=dev)           # token_lengths, word_lengths, frames, status
-            _lib.check(L.asg_beam_word_stream_result(None, ctypes.byref(self._g), ctypes.byref(self._w), B, self.beam_size, T,
-                                                     self._state.data_ptr(), self._state.numel(), 1 if final else 0,
-                                                     scores.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), small[0].data_ptr(),
-                                                     out[2].data_ptr(), out[3].data_ptr(), out[4].data_ptr(), small[1].data_ptr(),
-                                                     small[2].data_ptr(), small[3].data_ptr(), 0, be._stream(dev)),
-                       "asg_beam_word_stream_result")
-        return BeamWordStreamResult(scores, out[0], out[1], small[0], out[2], out[3], out[4], small[1], small[2], small[3])
-
-
-BeamWindowCommit = collections.namedtuple("BeamWindowCommit", ["path", "states", "tokens", "token_lengths", "frames"])
-BeamWindowResult = collections.namedtuple("BeamWindowResult", ["scores", "path", "tokens", "token_lengths", "states", "frames",
-                                                               "committed", "status"])
-
-
-class BeamWindowStream:
-    """`BeamStream` in bounded memory, for utterances without an end in sight: the same beam search, the back-pointers kept only
-    for a window of `window` frames, and the prefix of the transcript on which all surviving hypotheses agree COMMITTED -- handed
-    out by the `advance` that finds it, never to change.  No gradient.
-
-        s = BeamWindowStream(transition, graph, batch_size, window=128, beam_size=256)
-        for chunk in chunks:                 # [Tc, B, N] each, for as long as the microphone is open
-            new = s.advance(chunk)           # new.tokens[b, :new.token_lengths[b]]: append them to slot b's transcript
-            tail = s.result()                # the best hypothesis for the frames that are not committed yet
-        last = s.result(final=True)          # the committed tokens + last.tokens are the transcript
-
-    After every frame whose count is a multiple of `commit_every` (default max(1, window // 4)) the device looks for the latest
-    frame at which all hypotheses of the beam share one ancestor and commits everything up to it; if the uncommitted frames would
-    not leave room for the next `commit_every` frames in the window, it commits the oldest ones along the best hypothesis and sets
-    bit 0 of `status` (include/asg_hip.h::asg_beam_window_advance).  Scores are `BeamStream`'s and `beam_decode_graph`'s bit for
-    bit, for every window; while bit 0 of `status` is clear the committed frames followed by the tail are `beam_decode_graph`'s
-    path, and the same for the tokens.  What is committed does not depend on how the frames were cut into chunks.
-
-    The state is one device buffer of about window * beam_size * 8 bytes of back-pointers plus 12-16 bytes per product state,
-    per slot, whatever the length of the utterance; `result` walks at most `window` frames.  `advance`, `result` and `reset` are
-    one kernel launch each, copy nothing and do not synchronise, so they can be captured and replayed.  The other arguments are
-    `BeamStream`'s; there is no bound on the number of frames.
-    """
-
-    def __init__(self, transition, graph, batch_size, window, commit_every=None, beam_size=256, beam_threshold=float("inf"),
-                 lm_weight=1.0, token_score=0.0, dtype=torch.float32, device=None):
-        from . import graph as _graph
-        _check_beam(beam_size, beam_threshold)
-        if not isinstance(graph, _graph.TokenGraph):
-            raise TypeError("torch_asg_amd: graph must be a torch_asg_amd.TokenGraph")
-        if int(batch_size) < 1 or int(window) < 1:
-            raise ValueError("torch_asg_amd: batch_size and window must be >= 1, got %d and %d" % (int(batch_size), int(window)))
-        commit_every = max(1, int(window) // 4) if commit_every is None else int(commit_every)
-        if not 1 <= commit_every <= int(window):
-            raise ValueError("torch_asg_amd: commit_every must be in 1 .. window = %d, got %d" % (int(window), commit_every))
-        if dtype not in (torch.float32, torch.float64):
-            raise RuntimeError("torch_asg_amd: expected scalar type Float or Double but found %s" % dtype)
-        device = torch.device(device) if device is not None else transition.device
-        if device.type != "cuda":
-            raise RuntimeError("torch_asg_amd: a BeamWindowStream must live on a ROCm device (got %s); "
-                               "there is no CPU implementation in this package" % device)
-        if transition.dtype != dtype or transition.device != device or tuple(transition.shape) != (graph.N, graph.N):
-            raise RuntimeError("torch_asg_amd: transition must be [%d,%d] with the dtype/device of the stream" % (graph.N, graph.N))
-        self.transition, self.graph = transition, graph
-        self.batch_size, self.window, self.commit_every = int(batch_size), int(window), commit_every
-        self.beam_size, self.beam_threshold = min(int(beam_size), (1 << 31) - 1), float(beam_threshold)
-        self.lm_weight, self.token_score, self.dtype, self.device = lm_weight, token_score, dtype, device
-        be = native()
-        L = _lib.lib()
-        with be._guard(device):
-            self._compiled = graph.compile_beam(device, dtype, lm_weight, token_score)
-            self._g = _graph.abi_graph_beam(self._compiled)
-            abi_dtype = _lib.ASG_DTYPE_F32 if dtype == torch.float32 else _lib.ASG_DTYPE_F64
-            nbytes = int(L.asg_beam_window_state_bytes(ctypes.byref(self._g), self.batch_size, abi_dtype, self.beam_size,
-                                                       self.window, self.commit_every))
-            if nbytes == 0:                                    # the library refuses the arguments: its call says why
-                _lib.check(L.asg_beam_window_reset(None, ctypes.byref(self._g), self.batch_size, self.beam_size, self.window,
-                                                   self.commit_every, None, 0, None, 0, None), "asg_beam_window_reset")
-            self._state = be._buf(nbytes, device)
-        self.reset()
-
-    def reset(self, mask=None):
-        """Start new utterances: in every slot (mask None), or in the slots where `mask` (bool or integer [B]) is not zero --
-        the other slots go on."""
-        be = native()
-        L = _lib.lib()
-        m = None
-        if mask is not None:
-            if tuple(mask.shape) != (self.batch_size,):
-                raise RuntimeError("torch_asg_amd: mask must have shape [%d]" % self.batch_size)
-            m = mask.to(self.device).ne(0).to(torch.uint8).contiguous()
-        with be._guard(self.device):
-            _lib.check(L.asg_beam_window_reset(None, ctypes.byref(self._g), self.batch_size, self.beam_size, self.window,
-                                               self.commit_every, self._state.data_ptr(), self._state.numel(),
-                                               m.data_ptr() if m is not None else None, 0, be._stream(self.device)),
-                       "asg_beam_window_reset")
-
-    def advance(self, chunk, chunk_lengths=None):
-        """Consume `chunk` [Tc, B, N] as `BeamStream.advance` does -> what this call committed, a named tuple
-          path, states, tokens [B, window + Tc] int64, -1 behind the data: label and automaton state of every newly committed
-          frame, and the tokens they add to the transcript (the collapse goes on across calls); token_lengths [B]; frames [B],
-          the number of frames committed by this call."""
-        be = native()
-        L = _lib.lib()
-        transition = self.transition.detach()
-        if chunk.dtype in (torch.float16, torch.bfloat16):
-            chunk = chunk.to(transition.dtype)
-        chunk = chunk.detach()
-        be._check_decode_graph(chunk, transition, self.graph, chunk_lengths)
-        Tc, B, N = chunk.shape
-        if chunk.dtype != self.dtype or chunk.device != self.device or B != self.batch_size:
-            raise RuntimeError("torch_asg_amd: the stream takes chunks [Tc,%d,%d] of %s on %s, got %s of %s on %s"
-                               % (self.batch_size, N, self.dtype, self.device, tuple(chunk.shape), chunk.dtype, chunk.device))
-        _check_beam(self.beam_size, self.beam_threshold)
-        dev = self.device
-        with be._guard(dev):
-            out = torch.empty(3, B, self.window + Tc, dtype=torch.int64, device=dev)       # path, states, tokens
-            small = torch.empty(2, B, dtype=torch.int64, device=dev)                       # frames, token_lengths
-            p, keep = be._problem(chunk, transition, None, chunk_lengths, None)
-            _lib.check(L.asg_beam_window_advance(None, ctypes.byref(p), ctypes.byref(self._g), self.beam_size,
-                                                 float(self.beam_threshold), self.window, self.commit_every,
-                                                 self._state.data_ptr(), self._state.numel(), out[0].data_ptr(), out[1].data_ptr(),
-                                                 out[2].data_ptr(), small[0].data_ptr(), small[1].data_ptr(), 0, be._stream(dev)),
-                       "asg_beam_window_advance")
-        return BeamWindowCommit(out[0], out[1], out[2], small[1], small[0])
-
-    def result(self, final=False):
-        """The best hypothesis of every slot for the frames that are not committed yet, without changing the state -> a named tuple
-          scores [B], the score of the whole hypothesis; path, tokens, states [B, window] int64, -1 behind the data: the
-          uncommitted tail (a first label that repeats the last committed one is no token); token_lengths [B]; frames [B], the
-          frames consumed; committed [B], the frames committed; status [B]: bit 0 = frames were committed before the hypotheses
-          agreed on them, bit 1 = the beam is empty.
-        final as for `BeamStream.result`.  A slot without frames or with an empty beam: -inf, -1, 0."""
-        be = native()
-        L = _lib.lib()
-        B, W, dev = self.batch_size, self.window, self.device
-        with be._guard(dev):
-            scores = torch.empty(B, dtype=self.dtype, device=dev)
-            out = torch.empty(3, B, W, dtype=torch.int64, device=dev)          # path, tokens, states
-            small = torch.empty(4, B, dtype=torch.int64, device=dev)           # token_lengths, frames, committed, status
-            _lib.check(L.asg_beam_window_result(None, ctypes.byref(self._g), B, self.beam_size, W, self.commit_every,
-                                                self._state.data_ptr(), self._state.numel(), 1 if final else 0, scores.data_ptr(),
-                                                out[0].data_ptr(), out[1].data_ptr(), small[0].data_ptr(), out[2].data_ptr(),
-                                                small[1].data_ptr(), small[2].data_ptr(), small[3].data_ptr(), 0, be._stream(dev)),
-                       "asg_beam_window_result")
-        return BeamWindowResult(scores, out[0], out[1], small[0], out[2], small[1], small[2], small[3])
 
 
 class GraphFullScore(torch.autograd.Function):
@@ -1596,9 +1147,8 @@ def graph_full_score(inputs, transition, graph, input_lengths=None, lm_weight=1.
     dtype of the emissions; -inf for an utterance of length 0 or without any accepted path.  Inputs, strides, widening of
     float16 / bfloat16 and the grouping under `max_work_bytes` (alpha, T * Q * e bytes per utterance when a gradient is
     needed) are those of `viterbi_decode_graph`."""
-    if inputs.dtype in (torch.float16, torch.bfloat16):
-        inputs = inputs.to(transition.dtype)
-    return GraphFullScore.apply(inputs, transition, graph, input_lengths, lm_weight, token_score, max_work_bytes, 0)
+    return GraphFullScore.apply(_widen(inputs, transition), transition, graph, input_lengths, lm_weight, token_score,
+                                max_work_bytes, 0)
 
 
 def _guarded_targets(targets, target_lengths, N):
@@ -1610,12 +1160,21 @@ def _guarded_targets(targets, target_lengths, N):
     return targets.masked_fill(outside, 0), ~(outside & pos).any(dim=1)
 
 
-def _graph_loss_per_utterance(inputs, targets, transition, graph, input_lengths, target_lengths, lm_weight, token_score,
-                              max_work_bytes, flags):
-    """[B] losses full_graph - (FAC + A(collapse(target))); +inf (never NaN) where the target has no alignment, the automaton
-    rejects it or it holds a label outside [0, N) (`_guarded_targets`), and then only the full-graph posterior reaches the
-    gradients.  Lengths must be given (ASGLoss._canonical)."""
-    full = GraphFullScore.apply(inputs, transition, graph, input_lengths, lm_weight, token_score, max_work_bytes, flags)
+def _graph_loss(inputs, targets, transition, graph, input_lengths, target_lengths, lm_weight, token_score, max_work_bytes,
+                reduction, beam=None, weights=None):
+    """What the graph losses share.  [B] losses full - (FAC + A(collapse(target))), then `weights(inputs, input_lengths,
+    target_lengths)` (None: none) and the reduction; `full` is the exact normaliser (`GraphFullScore`), or with beam =
+    (beam_size, beam_threshold) the beam-pruned one with the target forced into the lattice (`BeamGraphFullScore`).  A loss is
+    +inf (never NaN) where the target has no alignment, the automaton rejects it or it holds a label outside [0, N)
+    (`_guarded_targets`), and then only the normaliser's posterior reaches the gradients.  Defaults, S > T truncation and
+    widening as `ASGLoss.forward`."""
+    inputs = _widen(inputs, transition)
+    targets, input_lengths, target_lengths = ASGLoss._canonical(inputs, targets, input_lengths, target_lengths)
+    if beam is None:
+        full = GraphFullScore.apply(inputs, transition, graph, input_lengths, lm_weight, token_score, max_work_bytes, 0)
+    else:
+        full = BeamGraphFullScore.apply(inputs, transition, graph, input_lengths, *beam, lm_weight, token_score, targets,
+                                        target_lengths, max_work_bytes)
     with torch.no_grad():
         walk = native().graph_target_scores(inputs.detach(), transition.detach(), graph, targets, target_lengths, lm_weight,
                                             token_score)
@@ -1627,7 +1186,11 @@ def _graph_loss_per_utterance(inputs, targets, transition, graph, input_lengths,
     zero = torch.zeros_like(fd)
     value = torch.where(ok_a, fd - ad, torch.full_like(fd, float("inf")))
     # value carries the numbers; the two zero-valued terms carry the gradients, masked where a score is infinite
-    return value + torch.where(ok_f, full - fd, zero) - torch.where(ok_a, aligned - ad, zero)
+    per = value + torch.where(ok_f, full - fd, zero) - torch.where(ok_a, aligned - ad, zero)
+    w = weights(inputs, input_lengths, target_lengths) if weights is not None else None
+    if w is not None:
+        per = per * w
+    return _reduce(per, reduction)
 
 
 def _reduce(per_utt, reduction):
@@ -1646,12 +1209,8 @@ def graph_asg_loss(inputs, targets, transition, graph, input_lengths=None, targe
     under the composed model.  +inf where the target cannot be aligned (target_length > input_length, length 0) or the automaton
     rejects it, or it holds a label outside [0, N); those utterances' gradient rows hold only the full-graph posterior.
     Defaults and S > T truncation as `ASGLoss.forward`; reduction 'none' (default), 'sum' or 'mean'."""
-    if inputs.dtype in (torch.float16, torch.bfloat16):
-        inputs = inputs.to(transition.dtype)
-    targets, input_lengths, target_lengths = ASGLoss._canonical(inputs, targets, input_lengths, target_lengths)
-    per = _graph_loss_per_utterance(inputs, targets, transition, graph, input_lengths, target_lengths, lm_weight,
-                                    token_score, max_work_bytes, 0)
-    return _reduce(per, reduction)
+    return _graph_loss(inputs, targets, transition, graph, input_lengths, target_lengths, lm_weight, token_score, max_work_bytes,
+                       reduction)
 
 
 class BeamGraphFullScore(torch.autograd.Function):
@@ -1679,13 +1238,6 @@ class BeamGraphFullScore(torch.autograd.Function):
         return (gin, gtr) + (None,) * 9
 
 
-def _check_beam(beam_size, beam_threshold):
-    if int(beam_size) < 1:
-        raise ValueError("torch_asg_amd: beam_size must be >= 1, got %d" % int(beam_size))
-    if not float(beam_threshold) >= 0.0:
-        raise ValueError("torch_asg_amd: beam_threshold must be >= 0 (inf: none), got %r" % (beam_threshold,))
-
-
 def beam_graph_full_score(inputs, transition, graph, input_lengths=None, beam_size=256, beam_threshold=float("inf"), lm_weight=1.0,
                           token_score=0.0, targets=None, target_lengths=None, max_work_bytes=1 << 30):
     """`graph_full_score` over the lattice that `beam_decode_graph`'s search keeps: the logsumexp over the label paths that
@@ -1697,29 +1249,8 @@ def beam_graph_full_score(inputs, transition, graph, input_lengths=None, beam_si
     Bit-identical run to run and for any `max_work_bytes`.  targets / target_lengths are taken as given (no defaults or
     truncation here: `beam_graph_asg_loss` applies those)."""
     _check_beam(beam_size, beam_threshold)
-    if inputs.dtype in (torch.float16, torch.bfloat16):
-        inputs = inputs.to(transition.dtype)
-    return BeamGraphFullScore.apply(inputs, transition, graph, input_lengths, beam_size, beam_threshold, lm_weight, token_score,
-                                    targets, target_lengths, max_work_bytes)
-
-
-def _beam_graph_loss_per_utterance(inputs, targets, transition, graph, input_lengths, target_lengths, beam_size, beam_threshold,
-                                   lm_weight, token_score, max_work_bytes):
-    """[B] losses Z_K - (FAC + A(collapse(target))) with the target forced into the lattice; conventions of
-    `_graph_loss_per_utterance`."""
-    full = BeamGraphFullScore.apply(inputs, transition, graph, input_lengths, beam_size, beam_threshold, lm_weight, token_score,
-                                    targets, target_lengths, max_work_bytes)
-    with torch.no_grad():
-        walk = native().graph_target_scores(inputs.detach(), transition.detach(), graph, targets, target_lengths, lm_weight,
-                                            token_score)
-    safe, inside = _guarded_targets(targets, target_lengths, inputs.shape[2])
-    aligned = FAC.apply(transition, inputs, safe, input_lengths, target_lengths) + walk
-    aligned = torch.where(inside.to(aligned.device), aligned, torch.full_like(aligned, float("-inf")))
-    fd, ad = full.detach(), aligned.detach()
-    ok_f, ok_a = torch.isfinite(fd), torch.isfinite(ad)
-    zero = torch.zeros_like(fd)
-    value = torch.where(ok_a, fd - ad, torch.full_like(fd, float("inf")))
-    return value + torch.where(ok_f, full - fd, zero) - torch.where(ok_a, aligned - ad, zero)
+    return BeamGraphFullScore.apply(_widen(inputs, transition), transition, graph, input_lengths, beam_size, beam_threshold,
+                                    lm_weight, token_score, targets, target_lengths, max_work_bytes)
 
 
 def beam_graph_asg_loss(inputs, targets, transition, graph, input_lengths=None, target_lengths=None, beam_size=256,
@@ -1730,12 +1261,8 @@ def beam_graph_asg_loss(inputs, targets, transition, graph, input_lengths=None, 
     alignment, a target the automaton rejects, a label outside [0, N) within the target's length; then only the normaliser's
     posterior reaches the gradients.  Defaults and S > T truncation as `ASGLoss.forward`."""
     _check_beam(beam_size, beam_threshold)
-    if inputs.dtype in (torch.float16, torch.bfloat16):
-        inputs = inputs.to(transition.dtype)
-    targets, input_lengths, target_lengths = ASGLoss._canonical(inputs, targets, input_lengths, target_lengths)
-    per = _beam_graph_loss_per_utterance(inputs, targets, transition, graph, input_lengths, target_lengths, beam_size,
-                                         beam_threshold, lm_weight, token_score, max_work_bytes)
-    return _reduce(per, reduction)
+    return _graph_loss(inputs, targets, transition, graph, input_lengths, target_lengths, lm_weight, token_score, max_work_bytes,
+                       reduction, (beam_size, beam_threshold))
 
 
 class FAC(torch.autograd.Function):
@@ -1991,29 +1518,15 @@ class ASGLoss(nn.Module):
                    max_work_bytes=1 << 30):
         """`torch_asg_amd.graph_asg_loss` under this module's transition matrix, reduction and scale_mode.  float16 / bfloat16
         emissions are widened to the dtype of `transition`; batch-major views ([B,T,N] transposed) need no copy."""
-        if inputs.dtype in (torch.float16, torch.bfloat16):
-            inputs = inputs.to(self.transition.dtype)
-        targets, input_lengths, target_lengths = self._canonical(inputs, targets, input_lengths, target_lengths)
-        weights = self._utterance_weights(inputs, input_lengths, target_lengths)
-        per = _graph_loss_per_utterance(inputs, targets, self.transition, graph, input_lengths, target_lengths, lm_weight,
-                                        token_score, max_work_bytes, 0)
-        if weights is not None:
-            per = per * weights
-        return _reduce(per, self.reduction)
+        return _graph_loss(inputs, targets, self.transition, graph, input_lengths, target_lengths, lm_weight, token_score,
+                           max_work_bytes, self.reduction, None, self._utterance_weights)
 
     def beam_graph_loss(self, inputs, targets, graph, input_lengths=None, target_lengths=None, lm_weight=1.0, token_score=0.0,
                         max_work_bytes=1 << 30, beam_size=256, beam_threshold=float("inf")):
         """`torch_asg_amd.beam_graph_asg_loss` under this module's transition matrix, reduction and scale_mode."""
         _check_beam(beam_size, beam_threshold)
-        if inputs.dtype in (torch.float16, torch.bfloat16):
-            inputs = inputs.to(self.transition.dtype)
-        targets, input_lengths, target_lengths = self._canonical(inputs, targets, input_lengths, target_lengths)
-        weights = self._utterance_weights(inputs, input_lengths, target_lengths)
-        per = _beam_graph_loss_per_utterance(inputs, targets, self.transition, graph, input_lengths, target_lengths, beam_size,
-                                             beam_threshold, lm_weight, token_score, max_work_bytes)
-        if weights is not None:
-            per = per * weights
-        return _reduce(per, self.reduction)
+        return _graph_loss(inputs, targets, self.transition, graph, input_lengths, target_lengths, lm_weight, token_score,
+                           max_work_bytes, self.reduction, (beam_size, beam_threshold), self._utterance_weights)
 
     @staticmethod
     def _canonical(inputs, targets, input_lengths, target_lengths):
@@ -2142,3 +1655,8 @@ class ASGLoss(nn.Module):
         if self.reduction == 'sum':
             return per_utt.sum()
         return per_utt
+
+
+# the streaming decoders (stream.py looks this module's `native` up at every call, so it is imported once the module stands)
+from .stream import (BeamStream, BeamStreamResult, BeamWordStream, BeamWordStreamResult,  # noqa: E402,F401
+                     BeamWindowStream, BeamWindowCommit, BeamWindowResult)

@@ -622,6 +622,14 @@ static int check_beam_words(const asg_problem *p, const asg_token_graph_beam *gb
     return ASG_OK;
 }
 
+static WordLmArgs to_word_lm_args(const asg_word_lm *lm) {
+    WordLmArgs LM{};
+    LM.H = (int) lm->H; LM.A = (int) lm->A; LM.start = lm->start; LM.sep = lm->separator;
+    LM.row = lm->row; LM.word = lm->word; LM.next = lm->next; LM.backoff = lm->backoff; LM.word_of_state = lm->word_of_state;
+    LM.lw = lm->lw; LM.bw = lm->bw; LM.ew = lm->ew;
+    return LM;
+}
+
 size_t asg_beam_decode_words_work_bytes(const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm, int beam_size) {
     if (check_beam_words(p, gb, lm, beam_size) != ASG_OK) return 0;
     return beam_word_work_bytes(p->dtype == ASG_DTYPE_F64 ? 8 : 4, (int) p->T, (int) p->B, beam_size,
@@ -642,10 +650,7 @@ int asg_beam_decode_words(asg_ctx *ctx, const asg_problem *p, const asg_token_gr
     const Problem P = to_problem(p);
     const GraphArgs G = to_graph_args(gb->graph);
     const BeamGraphArgs BG = to_beam_graph_args(gb);
-    WordLmArgs LM{};
-    LM.H = (int) lm->H; LM.A = (int) lm->A; LM.start = lm->start; LM.sep = lm->separator;
-    LM.row = lm->row; LM.word = lm->word; LM.next = lm->next; LM.backoff = lm->backoff; LM.word_of_state = lm->word_of_state;
-    LM.lw = lm->lw; LM.bw = lm->bw; LM.ew = lm->ew;
+    const WordLmArgs LM = to_word_lm_args(lm);
     long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
     long long *ls = (long long *) lm_states, *wd = (long long *) words, *wl = (long long *) word_lengths;
     return hip_status(ASG_DISPATCH(p, launch_beam_words<float>(P, G, BG, LM, beam_size, beam_threshold, work, scores, pa, tk, tl,
@@ -768,14 +773,6 @@ int asg_beam_stream_result(asg_ctx *ctx, const asg_token_graph_beam *gb, int64_t
                                                                        tk, tl, st, fr, su, (hipStream_t) stream),
                                    launch_beam_stream_result<double>(G, BG, K, (int) max_frames, (int) B, state, final, scores, pa,
                                                                      tk, tl, st, fr, su, (hipStream_t) stream)));
-}
-
-static WordLmArgs to_word_lm_args(const asg_word_lm *lm) {
-    WordLmArgs LM{};
-    LM.H = (int) lm->H; LM.A = (int) lm->A; LM.start = lm->start; LM.sep = lm->separator;
-    LM.row = lm->row; LM.word = lm->word; LM.next = lm->next; LM.backoff = lm->backoff; LM.word_of_state = lm->word_of_state;
-    LM.lw = lm->lw; LM.bw = lm->bw; LM.ew = lm->ew;
-    return LM;
 }
 
 // A word stream state is sized like a problem of max_frames frames, as a stream state is: the checks of asg_beam_decode_words

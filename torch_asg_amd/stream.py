@@ -1,0 +1,356 @@
+"""The streaming beam decoders (`BeamStream`, `BeamWordStream`, `BeamWindowStream`) on one private base class.
+
+The three families of C entry points (include/asg_hip.h::asg_beam_stream_*, asg_beam_word_stream_*, asg_beam_window_*) take
+their arguments in one order,
+
+    (ctx, [p], views..., [B], K, [theta], shape..., state, nbytes, ..., flags, stream)
+
+where `views` is the automaton ((g,), or (g, w) with a word LM) and `shape` what sizes the state ((max_frames,) or
+(window, commit_every)).  `_Stream` owns everything that follows from that: the constructor checks, the state, `reset`, the
+chunk preamble, the host's bound and the launch of `advance`, the outputs of `result`.  A subclass names its entry points
+(`_API`), checks and compiles its automaton, checks its shape, and says what `result` (and `advance`, if anything) returns.
+The backend is looked up at every call (`asg.native()`), so that what replaces it in `torch_asg_amd.asg` is what the streams
+use.
+"""
+import collections
+import ctypes
+
+import torch
+
+from . import _lib
+from . import asg as _asg
+
+
+class _Stream:
+    _API = None                  # "asg_beam_stream": the prefix of _state_bytes, _reset, _advance and _result
+    _WIDE = _NARROW = 0          # the number of [B, frames] and of [B] int64 outputs of _result
+    max_frames = None            # set by a subclass whose state holds a fixed number of frames: the host's bound of `advance`
+
+    def __init__(self, transition, automaton, batch_size, shape, beam_size, beam_threshold, dtype, device):
+        _asg._check_beam(beam_size, beam_threshold)
+        graph = self._check_automaton(*automaton)
+        self._shape = self._check_shape(batch_size, *shape)
+        if dtype not in (torch.float32, torch.float64):
+            raise RuntimeError("torch_asg_amd: expected scalar type Float or Double but found %s" % dtype)
+        device = torch.device(device) if device is not None else transition.device
+        if device.type != "cuda":
+            raise RuntimeError("torch_asg_amd: a %s must live on a ROCm device (got %s); "
+                               "there is no CPU implementation in this package" % (type(self).__name__, device))
+        if transition.dtype != dtype or transition.device != device or tuple(transition.shape) != (graph.N, graph.N):
+            raise RuntimeError("torch_asg_amd: transition must be [%d,%d] with the dtype/device of the stream" % (graph.N, graph.N))
+        self.transition, self.graph, self.batch_size = transition, graph, int(batch_size)
+        self.beam_size, self.beam_threshold = min(int(beam_size), (1 << 31) - 1), float(beam_threshold)
+        self.dtype, self.device = dtype, device
+        be = _asg.native()
+        L = _lib.lib()
+        # (entry point, its name for error messages) of the three calls
+        self._c_reset, self._c_advance, self._c_result = ((getattr(L, self._API + s), self._API + s)
+                                                          for s in ("_reset", "_advance", "_result"))
+        with be._guard(device):
+            self._compiled = self._compile()                   # (the views point into it)
+            self._views = tuple(ctypes.byref(v) for v in self._compiled[0])
+            abi_dtype = _lib.ASG_DTYPE_F32 if dtype == torch.float32 else _lib.ASG_DTYPE_F64
+            nbytes = int(getattr(L, self._API + "_state_bytes")(*self._views, self.batch_size, abi_dtype, self.beam_size,
+                                                                *self._shape))
+            if nbytes == 0:                                    # the library refuses the arguments: its call says why
+                reset, what = self._c_reset
+                _lib.check(reset(None, *self._views, self.batch_size, self.beam_size, *self._shape, None, 0, None, 0, None), what)
+            self._state = be._buf(nbytes, device)
+        self._reset(None)
+
+    def _check_automaton(self, graph):
+        """The type checks of the constructor's automaton -> the TokenGraph the emissions are checked against."""
+        from . import graph as _graph
+        if not isinstance(graph, _graph.TokenGraph):
+            raise TypeError("torch_asg_amd: graph must be a torch_asg_amd.TokenGraph")
+        return graph
+
+    def _check_shape(self, batch_size, max_frames):
+        """The range checks of batch_size and of what sizes the state -> the shape tuple of the entry points."""
+        if int(batch_size) < 1 or int(max_frames) < 1:
+            raise ValueError("torch_asg_amd: batch_size and max_frames must be >= 1, got %d and %d"
+                             % (int(batch_size), int(max_frames)))
+        return (int(max_frames),)
+
+    def _compile(self):
+        """(the C views of the automaton in the entry points' order, what they point into), for self.device and self.dtype."""
+        from . import graph as _graph
+        compiled = self.graph.compile_beam(self.device, self.dtype, self.lm_weight, self.token_score)
+        return (_graph.abi_graph_beam(compiled),), compiled
+
+    def _reset(self, mask):
+        be = _asg.native()
+        m = None
+        if mask is not None:
+            if tuple(mask.shape) != (self.batch_size,):
+                raise RuntimeError("torch_asg_amd: mask must have shape [%d]" % self.batch_size)
+            m = mask.to(self.device).ne(0).to(torch.uint8).contiguous()
+        reset, what = self._c_reset
+        with be._guard(self.device):
+            _lib.check(reset(None, *self._views, self.batch_size, self.beam_size, *self._shape, self._state.data_ptr(),
+                             self._state.numel(), m.data_ptr() if m is not None else None, 0, be._stream(self.device)), what)
+        if mask is None:
+            self._fed = 0                                      # frames offered since the last full reset (the host's bound)
+
+    def _advance(self, chunk, chunk_lengths):
+        """`advance`: the chunk as the kernels read it, checked; the host's bound of a stream whose state holds `max_frames`
+        frames; one launch on the current stream, which also fills `_commit_outputs` -> those outputs."""
+        be = _asg.native()
+        transition = self.transition           # (the launch reads pointers, strides, dtype and device: there is no autograd
+        if chunk.dtype in (torch.float16, torch.bfloat16):               # history to cut, except of the widening copy)
+            chunk = chunk.detach().to(transition.dtype)
+        be._check_graph_inputs(chunk, transition, self.graph, chunk_lengths)
+        Tc, B, N = chunk.shape
+        if chunk.dtype != self.dtype or chunk.device != self.device or B != self.batch_size:
+            raise RuntimeError("torch_asg_amd: the stream takes chunks [Tc,%d,%d] of %s on %s, got %s of %s on %s"
+                               % (self.batch_size, N, self.dtype, self.device, tuple(chunk.shape), chunk.dtype, chunk.device))
+        _asg._check_beam(self.beam_size, self.beam_threshold)
+        if self.max_frames is not None and self._fed + Tc > self.max_frames:
+            raise ValueError("torch_asg_amd: %d frames since the last reset() plus a chunk of %d exceed max_frames = %d"
+                             % (self._fed, Tc, self.max_frames))
+        advance, what = self._c_advance
+        with be._guard(self.device):
+            outs = self._commit_outputs(Tc)
+            p, keep = be._problem(chunk, transition, None, chunk_lengths, None)
+            _lib.check(advance(None, ctypes.byref(p), *self._views, self.beam_size, float(self.beam_threshold), *self._shape,
+                               self._state.data_ptr(), self._state.numel(), *[t.data_ptr() for t in outs] if outs else outs, 0,
+                               be._stream(self.device)), what)
+        self._fed += Tc
+        return outs
+
+    @staticmethod
+    def _commit_outputs(Tc):
+        """The output tensors of `_advance` for a chunk of Tc frames, in the entry point's order."""
+        return ()
+
+    def _result(self, final):
+        """One `_result` launch into fresh outputs: scores [B], _WIDE tensors [B, shape[0]] and _NARROW tensors [B], handed to
+        `_outputs`, whose named tuple lists them in the order in which the entry point takes them."""
+        be = _asg.native()
+        B, dev = self.batch_size, self.device
+        with be._guard(dev):
+            scores = torch.empty(B, dtype=self.dtype, device=dev)
+            wide = torch.empty(self._WIDE, B, self._shape[0], dtype=torch.int64, device=dev)
+            narrow = torch.empty(self._NARROW, B, dtype=torch.int64, device=dev)
+            res = self._outputs(scores, wide, narrow)
+            result, what = self._c_result
+            _lib.check(result(None, *self._views, B, self.beam_size, *self._shape, self._state.data_ptr(), self._state.numel(),
+                              1 if final else 0, *[t.data_ptr() for t in res], 0, be._stream(dev)), what)
+        return res
+
+
+BeamStreamResult = collections.namedtuple("BeamStreamResult", ["scores", "path", "tokens", "token_lengths", "states", "frames",
+                                                               "status"])
+
+
+class BeamStream(_Stream):
+    """`beam_decode_graph` for an utterance that arrives in chunks: the beam search carried from one chunk to the next, for
+    `batch_size` utterance slots at a time.  No gradient.
+
+        s = BeamStream(transition, graph, batch_size, max_frames, beam_size=256)
+        for chunk in chunks:                 # [Tc, B, N] each
+            s.advance(chunk)
+            partial = s.result()             # the best prefix hypothesis so far; the stream goes on
+        final = s.result(final=True)         # what beam_decode_graph returns for the whole utterance, bit for bit
+
+    The search is `beam_decode_graph`'s, frame by frame, with the same device code (include/asg_hip.h::asg_beam_stream_advance):
+    for any way of cutting an utterance of at most `max_frames` frames into chunks, `result(final=True)` equals the one-shot
+    decode of the whole utterance -- scores and token_lengths bit for bit, path / tokens / states on the one-shot's columns and
+    -1 beyond.  `transition` (a tensor or Parameter of dtype `dtype`; it is read again at every `advance`), `beam_threshold`,
+    `lm_weight` and `token_score` are those of `beam_decode_graph`; the attribute `beam_threshold` may be changed between chunks.
+
+    The state lives in one device buffer (about max_frames * beam_size * 8 bytes of back-pointers plus 12-16 bytes per product
+    state, per slot).  The graph is compiled in the constructor; `advance`, `result` and `reset` are one kernel launch each, copy
+    nothing and do not synchronise, so they can be captured in a graph and replayed with new chunk contents and lengths.
+    """
+    _API, _WIDE, _NARROW = "asg_beam_stream", 3, 3
+
+    def __init__(self, transition, graph, batch_size, max_frames, beam_size=256, beam_threshold=float("inf"), lm_weight=1.0,
+                 token_score=0.0, dtype=torch.float32, device=None):
+        self.lm_weight, self.token_score = lm_weight, token_score
+        super().__init__(transition, (graph,), batch_size, (max_frames,), beam_size, beam_threshold, dtype, device)
+        (self.max_frames,) = self._shape
+
+    def reset(self, mask=None):
+        """Start new utterances: in every slot (mask None), or in the slots where `mask` (bool or integer [B]) is not zero --
+        the other slots go on.  After a masked reset `advance`'s host-side check of `max_frames` is not tightened; the device
+        clamps and `result().status` reports it."""
+        self._reset(mask)
+
+    def advance(self, chunk, chunk_lengths=None):
+        """Consume `chunk` [Tc, B, N]: slot b takes its first clamp(chunk_lengths[b], 0, Tc) frames (all Tc when
+        `chunk_lengths` is None) as the next frames of its utterance.  Chunk dtype, strides and float16 / bfloat16 widening as in
+        `beam_decode_graph`.  ValueError, without touching the device, once the Tc offered since the last full `reset()` exceed
+        `max_frames`."""
+        self._advance(chunk, chunk_lengths)
+
+    def result(self, final=False):
+        """The best hypothesis of every slot over the frames consumed so far, without changing the state -> a named tuple
+          scores [B]; path, tokens, states [B, max_frames] int64, -1 behind the data; token_lengths [B]; frames [B], the frames
+          consumed; status [B], 1 where frames beyond max_frames were offered and dropped.
+        final=True adds the final weights (the transcript of a finished utterance: `beam_decode_graph`'s result); final=False is
+        the best prefix hypothesis, largest value without a final weight.  A slot without frames or with an empty beam: -inf, -1, 0."""
+        return self._result(final)
+
+    @staticmethod
+    def _outputs(scores, wide, narrow):
+        path, tokens, states = wide
+        token_lengths, frames, status = narrow
+        return BeamStreamResult(scores, path, tokens, token_lengths, states, frames, status)
+
+
+BeamWordStreamResult = collections.namedtuple("BeamWordStreamResult", ["scores", "path", "tokens", "token_lengths", "states",
+                                                                       "lm_states", "words", "word_lengths", "frames", "status"])
+
+
+class BeamWordStream(_Stream):
+    """`beam_decode_words` for an utterance that arrives in chunks: the beam search over pairs (LM history, lexicon product
+    state), the word LM composed on the fly, carried from one chunk to the next for `batch_size` utterance slots at a time.
+    No gradient.
+
+        s = BeamWordStream(transition, lexicon, word_lm, batch_size, max_frames, beam_size=256)
+        for chunk in chunks:                 # [Tc, B, N] each
+            s.advance(chunk)
+            partial = s.result()             # the best prefix hypothesis so far, its words included; the stream goes on
+        final = s.result(final=True)         # what beam_decode_words returns for the whole utterance, bit for bit
+
+    The search is `beam_decode_words`', frame by frame, with the same device code
+    (include/asg_hip.h::asg_beam_word_stream_advance): for any way of cutting an utterance of at most `max_frames` frames into
+    chunks, `result(final=True)` equals the one-shot decode of the whole utterance -- scores, token_lengths and word_lengths bit
+    for bit, path / tokens / states / lm_states / words on the one-shot's columns and -1 beyond.  `transition` (a tensor or
+    Parameter of dtype `dtype`; it is read again at every `advance`), `beam_threshold`, `lm_weight`, `word_score` and
+    `token_score` are those of `beam_decode_words`; the attribute `beam_threshold` may be changed between chunks.  beam_size >
+    8192 is refused by the library (there is no clamp to the number of product states).
+
+    The state lives in one device buffer (about max_frames * beam_size * 12 bytes of back-pointers plus 60-80 bytes per
+    candidate a frame can have, per slot; nothing is sized by the vocabulary or the LM).  Lexicon and LM are compiled in the
+    constructor; `advance`, `result` and `reset` are one kernel launch each, copy nothing and do not synchronise, so they can be
+    captured in a graph and replayed with new chunk contents and lengths.  Not here: a windowed form with a committed prefix
+    (`BeamWindowStream` over pairs), n-best over pairs, a loss over pairs, LM look-ahead.
+    """
+    _API, _WIDE, _NARROW = "asg_beam_word_stream", 5, 4
+
+    def __init__(self, transition, lexicon, word_lm, batch_size, max_frames, beam_size=256, beam_threshold=float("inf"),
+                 lm_weight=1.0, word_score=0.0, token_score=0.0, dtype=torch.float32, device=None):
+        self.lm_weight, self.word_score, self.token_score = lm_weight, word_score, token_score
+        super().__init__(transition, (lexicon, word_lm), batch_size, (max_frames,), beam_size, beam_threshold, dtype, device)
+        (self.max_frames,) = self._shape
+
+    def _check_automaton(self, lexicon, word_lm):
+        from . import wordlm as _wordlm
+        _wordlm.check_words(lexicon, word_lm)
+        self.lexicon, self.word_lm = lexicon, word_lm
+        return lexicon.graph
+
+    def _compile(self):
+        from . import wordlm as _wordlm
+        g, w, keep = _wordlm.abi_words(self.lexicon, self.word_lm, self.device, self.dtype, self.lm_weight, self.word_score,
+                                       self.token_score)
+        return (g, w), keep
+
+    def reset(self, mask=None):
+        """Start new utterances: in every slot (mask None), or in the slots where `mask` (bool or integer [B]) is not zero --
+        the other slots go on.  After a masked reset `advance`'s host-side check of `max_frames` is not tightened; the device
+        clamps and `result().status` reports it."""
+        self._reset(mask)
+
+    def advance(self, chunk, chunk_lengths=None):
+        """Consume `chunk` [Tc, B, N]: slot b takes its first clamp(chunk_lengths[b], 0, Tc) frames (all Tc when
+        `chunk_lengths` is None) as the next frames of its utterance.  Chunk dtype, strides and float16 / bfloat16 widening as in
+        `beam_decode_words`.  ValueError, without touching the device, once the Tc offered since the last full `reset()` exceed
+        `max_frames`."""
+        self._advance(chunk, chunk_lengths)
+
+    def result(self, final=False):
+        """The best hypothesis of every slot over the frames consumed so far, without changing the state -> a named tuple
+          scores [B]; path, tokens, states, lm_states, words [B, max_frames] int64, -1 behind the data; token_lengths,
+          word_lengths [B]; frames [B], the frames consumed; status [B], 1 where frames beyond max_frames were offered and dropped.
+        final=True is the end of `beam_decode_words` (final weight, the LM's end of the sentence, after one more LM step for a
+        path that ends in a word-end node, whose word is appended; a path that ends mid-word does not count).  final=False is the
+        best prefix hypothesis, the largest value without any end term: it may end mid-word, and `words` holds the words whose
+        separator the path has passed.  A slot without frames, with an empty beam or without a finite score: -inf, -1, 0."""
+        return self._result(final)
+
+    @staticmethod
+    def _outputs(scores, wide, narrow):
+        path, tokens, states, lm_states, words = wide
+        token_lengths, word_lengths, frames, status = narrow
+        return BeamWordStreamResult(scores, path, tokens, token_lengths, states, lm_states, words, word_lengths, frames, status)
+
+
+BeamWindowCommit = collections.namedtuple("BeamWindowCommit", ["path", "states", "tokens", "token_lengths", "frames"])
+BeamWindowResult = collections.namedtuple("BeamWindowResult", ["scores", "path", "tokens", "token_lengths", "states", "frames",
+                                                               "committed", "status"])
+
+
+class BeamWindowStream(_Stream):
+    """`BeamStream` in bounded memory, for utterances without an end in sight: the same beam search, the back-pointers kept only
+    for a window of `window` frames, and the prefix of the transcript on which all surviving hypotheses agree COMMITTED -- handed
+    out by the `advance` that finds it, never to change.  No gradient.
+
+        s = BeamWindowStream(transition, graph, batch_size, window=128, beam_size=256)
+        for chunk in chunks:                 # [Tc, B, N] each, for as long as the microphone is open
+            new = s.advance(chunk)           # new.tokens[b, :new.token_lengths[b]]: append them to slot b's transcript
+            tail = s.result()                # the best hypothesis for the frames that are not committed yet
+        last = s.result(final=True)          # the committed tokens + last.tokens are the transcript
+
+    After every frame whose count is a multiple of `commit_every` (default max(1, window // 4)) the device looks for the latest
+    frame at which all hypotheses of the beam share one ancestor and commits everything up to it; if the uncommitted frames would
+    not leave room for the next `commit_every` frames in the window, it commits the oldest ones along the best hypothesis and sets
+    bit 0 of `status` (include/asg_hip.h::asg_beam_window_advance).  Scores are `BeamStream`'s and `beam_decode_graph`'s bit for
+    bit, for every window; while bit 0 of `status` is clear the committed frames followed by the tail are `beam_decode_graph`'s
+    path, and the same for the tokens.  What is committed does not depend on how the frames were cut into chunks.
+
+    The state is one device buffer of about window * beam_size * 8 bytes of back-pointers plus 12-16 bytes per product state,
+    per slot, whatever the length of the utterance; `result` walks at most `window` frames.  `advance`, `result` and `reset` are
+    one kernel launch each, copy nothing and do not synchronise, so they can be captured and replayed.  The other arguments are
+    `BeamStream`'s; there is no bound on the number of frames.
+    """
+    _API, _WIDE, _NARROW = "asg_beam_window", 3, 4
+
+    def __init__(self, transition, graph, batch_size, window, commit_every=None, beam_size=256, beam_threshold=float("inf"),
+                 lm_weight=1.0, token_score=0.0, dtype=torch.float32, device=None):
+        self.lm_weight, self.token_score = lm_weight, token_score
+        super().__init__(transition, (graph,), batch_size, (window, commit_every), beam_size, beam_threshold, dtype, device)
+        self.window, self.commit_every = self._shape
+
+    def _check_shape(self, batch_size, window, commit_every):
+        if int(batch_size) < 1 or int(window) < 1:
+            raise ValueError("torch_asg_amd: batch_size and window must be >= 1, got %d and %d" % (int(batch_size), int(window)))
+        commit_every = max(1, int(window) // 4) if commit_every is None else int(commit_every)
+        if not 1 <= commit_every <= int(window):
+            raise ValueError("torch_asg_amd: commit_every must be in 1 .. window = %d, got %d" % (int(window), commit_every))
+        return int(window), commit_every
+
+    def reset(self, mask=None):
+        """Start new utterances: in every slot (mask None), or in the slots where `mask` (bool or integer [B]) is not zero --
+        the other slots go on."""
+        self._reset(mask)
+
+    def advance(self, chunk, chunk_lengths=None):
+        """Consume `chunk` [Tc, B, N] as `BeamStream.advance` does -> what this call committed, a named tuple
+          path, states, tokens [B, window + Tc] int64, -1 behind the data: label and automaton state of every newly committed
+          frame, and the tokens they add to the transcript (the collapse goes on across calls); token_lengths [B]; frames [B],
+          the number of frames committed by this call."""
+        path, states, tokens, frames, token_lengths = self._advance(chunk, chunk_lengths)
+        return BeamWindowCommit(path, states, tokens, token_lengths, frames)
+
+    def _commit_outputs(self, Tc):
+        path, states, tokens = torch.empty(3, self.batch_size, self.window + Tc, dtype=torch.int64, device=self.device)
+        frames, token_lengths = torch.empty(2, self.batch_size, dtype=torch.int64, device=self.device)
+        return path, states, tokens, frames, token_lengths
+
+    def result(self, final=False):
+        """The best hypothesis of every slot for the frames that are not committed yet, without changing the state -> a named tuple
+          scores [B], the score of the whole hypothesis; path, tokens, states [B, window] int64, -1 behind the data: the
+          uncommitted tail (a first label that repeats the last committed one is no token); token_lengths [B]; frames [B], the
+          frames consumed; committed [B], the frames committed; status [B]: bit 0 = frames were committed before the hypotheses
+          agreed on them, bit 1 = the beam is empty.
+        final as for `BeamStream.result`.  A slot without frames or with an empty beam: -inf, -1, 0."""
+        return self._result(final)
+
+    @staticmethod
+    def _outputs(scores, wide, narrow):
+        path, tokens, states = wide
+        token_lengths, frames, committed, status = narrow
+        return BeamWindowResult(scores, path, tokens, token_lengths, states, frames, committed, status)

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .graph import TokenGraph, _host
+from .graph import TokenGraph, _host, abi_graph_beam
 
 _LN10 = float(np.log(np.float64(10.0)))
 MAX_PAIR_INDEX = 1 << 25            # H and Q of asg_beam_decode_words: (pair, slot) packs into one 64-bit word
@@ -282,3 +282,25 @@ def abi_word_lm(lm, lex):
         setattr(s, name, ctypes.c_void_p(t.data_ptr() if t.numel() else None))
     s.word_of_state = ctypes.c_void_p(lex["word_of_state"].data_ptr())
     return s
+
+
+def check_words(lexicon, word_lm):
+    """The argument checks of a (lexicon, word LM) pair: their types, and that the LM knows every word of the lexicon.  Apart
+    from `abi_words` because the callers report these before they look at the device."""
+    if not isinstance(lexicon, Lexicon):
+        raise TypeError("torch_asg_amd: lexicon must be a torch_asg_amd.Lexicon")
+    if not isinstance(word_lm, WordLM):
+        raise TypeError("torch_asg_amd: word_lm must be a torch_asg_amd.WordLM")
+    wmax = int(lexicon.word_of_state.max(initial=-1))
+    if wmax >= word_lm.V:
+        raise RuntimeError("torch_asg_amd: the lexicon has word id %d but the word LM knows %d words" % (wmax, word_lm.V))
+
+
+def abi_words(lexicon, word_lm, device, dtype, lm_weight, word_score, token_score):
+    """A checked (`check_words`) pair compiled for (device, dtype) and the weights -> (the asg_token_graph_beam view of the
+    lexicon, the asg_word_lm view, (the two compiled dicts the views point into: keep them alive with the views))."""
+    lex = lexicon.compile_words(device, dtype, token_score)
+    lm = word_lm.compile(device, dtype, lm_weight, word_score)
+    w = abi_word_lm(lm, lex)
+    w.separator = lexicon.separator
+    return abi_graph_beam(lex), w, (lex, lm)
