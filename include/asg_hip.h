@@ -515,7 +515,7 @@ int asg_beam_decode_words(asg_ctx *ctx, const asg_problem *p, const asg_token_gr
  * State (asg_beam_word_stream_state_bytes; 0 for arguments that the calls refuse), every part rounded up to 256 bytes:
  *   B * (asg_beam_decode_words' bytes per utterance with T = max_frames + 256 (pos, set size, overflow) + K*(e + 8) (the stored
  *   set: values, then product states, then LM states)), e = 4 / 8.  The back-pointers keep asg_beam_decode_words' [frame][K]
- *   layout -- the source slots of all kept pairs, not only the winner's, as an n-best over pairs would need.  No term in H, V, A
+ *   layout -- the source slots of all kept pairs, not only the winner's: asg_beam_word_stream_nbest walks them.  No term in H, V, A
  *   or Q.
  * Each call is ONE launch on `stream`, one 1024-thread workgroup per slot for advance and result: no host synchronisation, no
  * copy, no memset, so a captured call replays with new chunk contents and lengths, and a capture is one linear chain.  Integer
@@ -523,7 +523,8 @@ int asg_beam_decode_words(asg_ctx *ctx, const asg_problem *p, const asg_token_gr
  * 8192, H, Q <= 2^25, A < 2^31; ASG_ERR_UNSUPPORTED beyond) and those of asg_beam_stream_*: max_frames < 1, Tc < 0, B < 1,
  * beam_size < 1, a negative or NaN beam_threshold, a dtype that is not the graph's and the LM's, a NULL array or output:
  * ASG_ERR_INVALID; a state buffer smaller than asg_beam_word_stream_state_bytes: ASG_ERR_WORKSPACE.  Not here: the windowed form
- * with a committed prefix, n-best over pairs, a loss over pairs, LM look-ahead.  `flags` is reserved (pass 0). */
+ * with a committed prefix, a loss over pairs, LM look-ahead (n-best over pairs: asg_beam_word_stream_nbest below).  `flags` is
+ * reserved (pass 0). */
 size_t asg_beam_word_stream_state_bytes(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype, int beam_size,
                                         int64_t max_frames);
 int asg_beam_word_stream_reset(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
@@ -535,6 +536,74 @@ int asg_beam_word_stream_result(asg_ctx *ctx, const asg_token_graph_beam *gb, co
                                 int64_t max_frames, const void *state, size_t state_bytes, int final, void *scores, int64_t *path,
                                 int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words,
                                 int64_t *word_lengths, int64_t *frames, int64_t *status, int flags, void *stream);
+
+/* ---- The N BEST hypotheses of the search over pairs, each with its score split THREE ways -- acoustic, lexicon, LM -- and its
+ * words: what an n-best rescoring pass with a stronger LM and the tuning of lm_weight / word_score need.  No counterpart in the
+ * reference.  The search of asg_beam_decode_words runs unchanged: the same sets, the same back-pointers, the same bits (the same
+ * device code).  For utterance b with len = clamp(input_lengths[b], 0, T), A = A_{len-1} with values v:
+ *   candidates: every pair (h, q) of A whose end(h, q) = (v + final_w[q]) + endw is > -inf, endw exactly as in
+ *     asg_beam_decode_words: ew[h] when state(q) is the root; in a word-end node one more step(h, w), endw = a + ew[h'], no
+ *     candidate if the LM rejects; mid-word there is none.  Ordered by end descending (-0 and +0 are equal), then PAIR ORDER
+ *     (h ascending, then q ascending).  num_hyps[b] = min(nbest, number of candidates).
+ *   For r < num_hyps[b], with (h_t, q_t), t < len, the back-pointer path of the r-th candidate, i_t and s_t label and automaton
+ *   state of q_t:
+ *     scores[b][r] = the search's own end sum of that pair.  path[b][r][t] = i_t, states[b][r][t] = s_t, lm_states[b][r][t] =
+ *     h_t: optional, each may be NULL and is then not written.  tokens / token_lengths: the collapse of the path.  words /
+ *     word_lengths: the word of every separator edge on the path, in order, then the word of the final step if the path ends in
+ *     a word-end node (asg_beam_decode_words' rule).
+ *     Three sums over the path, in frame order, adds only, in the dtype of the problem:
+ *       emission_scores: a = I[0][i_0]; for t >= 1: a = (a + tr[i_t][i_{t-1}]) + I[t][i_t].
+ *       graph_scores (the lexicon automaton): g = start_w[q_0]; for every t >= 1 with q_t != q_{t-1}: g = g + ow[e] of the edge
+ *         q_{t-1} -> q_t; last g = g + final_w[q_{len-1}].
+ *       lm_scores: l = 0; for every separator edge (q_t != q_{t-1}, i_t == separator), in order: l = l + a, a the sum of
+ *         step(h_{t-1}, word) as step itself forms it (0, + bw per backoff step, + lw of the arc); last l = l + endw.
+ *   scores is the search's sum and NOT the rounded sum of the three parts: they agree within 2 * n * eps * (the sum of the
+ *   magnitudes of the terms), n the number of terms the three sums add, the inner terms of every LM walk included (two
+ *   summation orders of the same n terms).  With word_lengths the caller can re-weight: lm_scores = lm_weight * (raw LM) +
+ *   word_score * word_lengths up to rounding.
+ *   Rows r >= num_hyps[b] are padding: the four scores -inf, every integer output -1, both lengths 0.  Frames t >= len: -1.
+ *   Row 0 equals asg_beam_decode_words' eight outputs bit for bit.
+ *   DISTINCTNESS.  Lexicon and LM are deterministic, so a token sequence determines its pair: the rows are distinct token
+ *   sequences.  (Not every token sequence has a row: those whose histories the LM no longer tells apart -- after a backoff, or
+ *   beyond the order of the n-gram -- end in one pair, and the search keeps the best of them, as it does for the one best.)
+ *   Word sequences can repeat: the same words with and without a closing separator end at the root and in the
+ *   word-end node.  Rows are not merged; the better of the two comes first, and a caller who wants distinct word sequences drops
+ *   the later one.
+ *   scores, emission_scores, graph_scores, lm_scores [B][nbest] (dtype); path, tokens, states, lm_states, words [B][nbest][T]
+ *   int64; token_lengths, word_lengths [B][nbest] int64; num_hyps [B] int64.
+ * `work` (asg_beam_decode_words_nbest_work_bytes), every part rounded up to 256 bytes, nb = min(nbest, beam_size), e = 4 / 8:
+ *   B * (asg_beam_decode_words' bytes per utterance + (8 + K*(e + 8)) (size, values, product states and LM states of the last
+ *   set) + T*nb*4 (the product states of every hypothesis)) + 3*B*8 + 5*B*T*8 (what the one-best search itself returns).  No term
+ *   in H, V, A or Q.
+ * Two launches on one stream, one workgroup per utterance each; no memset, no copy, no synchronisation: a captured call replays
+ * with new emissions and lengths.  No float atomics: bit-identical run to run.  nbest < 1: ASG_ERR_INVALID; nbest > 8192:
+ * ASG_ERR_UNSUPPORTED (nbest > beam_size only adds padding rows); everything else as for asg_beam_decode_words.
+ *
+ * asg_beam_word_stream_nbest: the same over a word stream state, which it only reads (the same kernel, pointed at the stored set
+ * and at rows 0 .. pos-1).  final != 0: the rules above with len = pos.  final == 0: the n best PREFIXES: the candidates are the
+ * kept pairs with v > -inf, mid-word pairs included, ordered by v descending, then pair order; scores = v; graph_scores has no
+ * final_w, lm_scores no endw, and there is no final word.  Row 0 equals asg_beam_word_stream_result(final) bit for bit; frames and
+ * status are that call's.  A stream state keeps no emissions, so there is NO emission_scores here: a caller who kept the frames
+ * takes it from asg_beam_decode_words_nbest, the others have scores - (graph_scores + lm_scores) up to rounding.  For any chunking
+ * of an utterance of at most max_frames frames, the outputs with final != 0 equal asg_beam_decode_words_nbest's bit for bit (on
+ * that call's columns, -1 beyond): the n-best stage reads the set and the rows only, and those are the one-shot search's
+ * (REQUIRED PROPERTY above).  `work` (asg_beam_word_stream_nbest_work_bytes): B * max_frames*nb*4 rounded up to 256 bytes per
+ * slot; its contents mean nothing between calls.  One launch.  Errors: those of asg_beam_word_stream_result, the nbest limits
+ * above, a short `work`: ASG_ERR_WORKSPACE.  `flags` is reserved (pass 0). */
+size_t asg_beam_decode_words_nbest_work_bytes(const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                              int beam_size, int nbest);
+int asg_beam_decode_words_nbest(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                int beam_size, double beam_threshold, int nbest, void *work, size_t work_bytes, void *scores,
+                                void *emission_scores, void *graph_scores, void *lm_scores, int64_t *path, int64_t *tokens,
+                                int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words, int64_t *word_lengths,
+                                int64_t *num_hyps, int flags, void *stream);
+size_t asg_beam_word_stream_nbest_work_bytes(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype,
+                                             int beam_size, int64_t max_frames, int nbest);
+int asg_beam_word_stream_nbest(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
+                               int64_t max_frames, const void *state, size_t state_bytes, int final, int nbest, void *work,
+                               size_t work_bytes, void *scores, void *graph_scores, void *lm_scores, int64_t *path, int64_t *tokens,
+                               int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words, int64_t *word_lengths,
+                               int64_t *num_hyps, int64_t *frames, int64_t *status, int flags, void *stream);
 
 /* ---- Full score of the ASG lattice COMPOSED with a token automaton (the log-semiring counterpart of the decoder above), its
  * gradients, and the automaton's score of each target: the pieces of an ASG loss whose normaliser includes a token-level

@@ -31,7 +31,8 @@ SYMBOLS = ["asg_hip_version", "asg_hip_strerror", "asg_ctx_create", "asg_ctx_des
            "asg_beam_window_state_bytes", "asg_beam_window_reset", "asg_beam_window_advance", "asg_beam_window_result",
            "asg_beam_decode_words_work_bytes", "asg_beam_decode_words",
            "asg_beam_word_stream_state_bytes", "asg_beam_word_stream_reset", "asg_beam_word_stream_advance",
-           "asg_beam_word_stream_result"]
+           "asg_beam_word_stream_result", "asg_beam_decode_words_nbest_work_bytes", "asg_beam_decode_words_nbest",
+           "asg_beam_word_stream_nbest_work_bytes", "asg_beam_word_stream_nbest"]
 ABI_VERSION = 230        # include/asg_hip.h: ASG_HIP_VERSION this package was written against
 
 
@@ -154,6 +155,12 @@ def lib():
     L.asg_beam_word_stream_reset.argtypes = [vp, bp, wp, i64, ci, i64, vp, sz, vp, ci, vp]
     L.asg_beam_word_stream_advance.argtypes = [vp, pp, bp, wp, ci, ctypes.c_double, i64, vp, sz, ci, vp]
     L.asg_beam_word_stream_result.argtypes = [vp, bp, wp, i64, ci, i64, vp, sz, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp]
+    L.asg_beam_decode_words_nbest_work_bytes.restype = sz
+    L.asg_beam_decode_words_nbest_work_bytes.argtypes = [pp, bp, wp, ci, ci]
+    L.asg_beam_decode_words_nbest.argtypes = [vp, pp, bp, wp, ci, ctypes.c_double, ci, vp, sz] + [vp] * 12 + [ci, vp]
+    L.asg_beam_word_stream_nbest_work_bytes.restype = sz
+    L.asg_beam_word_stream_nbest_work_bytes.argtypes = [bp, wp, i64, ci, ci, i64, ci]
+    L.asg_beam_word_stream_nbest.argtypes = [vp, bp, wp, i64, ci, i64, vp, sz, ci, ci, vp, sz] + [vp] * 13 + [ci, vp]
     blp = ctypes.POINTER(AsgTokenGraphBeamLoss)
     L.asg_beam_graph_full_work_bytes.restype = sz
     L.asg_beam_graph_full_work_bytes.argtypes = [pp, blp, ci, ci]

@@ -451,6 +451,46 @@ class HipBackend:
                                 out[4, b0].data_ptr(), lengths[1, b0:].data_ptr(), 0, stream), "asg_beam_decode_words")
         return BeamWords(scores, out[0], out[1], lengths[0], out[2], out[3], out[4], lengths[1])
 
+    def beam_decode_words_nbest(self, inputs, transition, lexicon, word_lm, input_lengths, beam_size, nbest,
+                                beam_threshold=float("inf"), lm_weight=1.0, word_score=0.0, token_score=0.0,
+                                return_alignments=False, max_work_bytes=1 << 30):
+        """The n best hypotheses of the search over pairs with their score split three ways -> BeamWordsNbest; see
+        include/asg_hip.h::asg_beam_decode_words_nbest.  Grouped under `max_work_bytes` as `_decode_graph` does."""
+        from . import wordlm as _wordlm
+        _wordlm.check_words(lexicon, word_lm)
+        beam_size, beam_threshold = min(int(beam_size), (1 << 31) - 1), float(beam_threshold)
+        nbest = min(int(nbest), (1 << 31) - 1)
+        L = _lib.lib()
+        self._check_graph_inputs(inputs, transition, lexicon.graph, input_lengths)
+        T, B, N = inputs.shape
+        dev = inputs.device
+        with self._guard(dev):
+            g, w, (lex, _) = _wordlm.abi_words(lexicon, word_lm, dev, inputs.dtype, lm_weight, word_score, token_score)
+            p, _, input_lengths, _ = self._device_problem(inputs, transition, None, input_lengths, None)
+
+            def call(work, nbytes, *outs):
+                return L.asg_beam_decode_words_nbest(None, ctypes.byref(p), ctypes.byref(g), ctypes.byref(w), beam_size,
+                                                     beam_threshold, nbest, work, nbytes, *outs)
+            groups = self._groups(
+                p, B, max_work_bytes,
+                lambda: L.asg_beam_decode_words_nbest_work_bytes(ctypes.byref(p), ctypes.byref(g), ctypes.byref(w), beam_size, nbest),
+                lex["Q"], lambda: _lib.check(call(None, 0, *(None,) * 12, 0, None), "asg_beam_decode_words_nbest"),
+                inputs, input_lengths=input_lengths)
+            sc = torch.empty(4, B, nbest, dtype=inputs.dtype, device=dev)      # scores, emission, graph and LM scores
+            wide = torch.empty(2, B, nbest, T, dtype=torch.int64, device=dev)  # tokens, words
+            align = torch.empty(3, B, nbest, T, dtype=torch.int64, device=dev) if return_alignments else (None,) * 3
+            lengths = torch.empty(2, B, nbest, dtype=torch.int64, device=dev)  # token_lengths, word_lengths
+            num_hyps = torch.empty(B, dtype=torch.int64, device=dev)
+            al = lambda i, b0: align[i, b0:].data_ptr() if return_alignments else None      # noqa: E731
+            stream = self._stream(dev)
+            for b0, b1, work in groups:
+                _lib.check(call(work.data_ptr(), work.numel(), sc[0, b0:].data_ptr(), sc[1, b0:].data_ptr(), sc[2, b0:].data_ptr(),
+                                sc[3, b0:].data_ptr(), al(0, b0), wide[0, b0:].data_ptr(), lengths[0, b0:].data_ptr(), al(1, b0),
+                                al(2, b0), wide[1, b0:].data_ptr(), lengths[1, b0:].data_ptr(), num_hyps[b0:].data_ptr(), 0, stream),
+                           "asg_beam_decode_words_nbest")
+        return BeamWordsNbest(sc[0], sc[1], sc[2], sc[3], wide[0], lengths[0], wide[1], lengths[1], num_hyps, align[0], align[1],
+                              align[2])
+
     def _check_graph_inputs(self, inputs, transition, graph, input_lengths, targets=None, target_lengths=None):
         """The argument checks of every entry point that takes a token automaton."""
         from . import graph as _graph
@@ -1084,6 +1124,43 @@ def beam_decode_words(inputs, transition, lexicon, word_lm, input_lengths=None, 
                                           lm_weight, word_score, token_score, max_work_bytes)
 
 
+BeamWordsNbest = collections.namedtuple("BeamWordsNbest", ["scores", "emission_scores", "graph_scores", "lm_scores", "tokens",
+                                                           "token_lengths", "words", "word_lengths", "num_hyps", "path", "states",
+                                                           "lm_states"])
+
+
+def beam_decode_words_nbest(inputs, transition, lexicon, word_lm, input_lengths=None, beam_size=256, nbest=10,
+                            beam_threshold=float("inf"), lm_weight=1.0, word_score=0.0, token_score=0.0, return_alignments=False,
+                            max_work_bytes=1 << 30):
+    """The `nbest` best hypotheses of `beam_decode_words`' search, each with its words and its score split into the acoustic
+    part (emissions and transitions), the lexicon part (automaton weights, token_score, final weight) and the LM part (every
+    LM step and the end of the sentence, lm_weight and word_score folded in): what n-best rescoring with a stronger LM and the
+    tuning of lm_weight / word_score without decoding again need.  No gradient.
+
+    The search is `beam_decode_words`', unchanged.  The pairs kept at the last frame are ranked by their end (descending, pair
+    order -- LM history, then product state -- on a tie) and the first `nbest` with a finite end are returned, each with the
+    best path the pruned search found for it (include/asg_hip.h::asg_beam_decode_words_nbest).  -> a named tuple
+      scores, emission_scores, graph_scores, lm_scores  [B, nbest]     dtype of the emissions; -inf in the padding rows
+      tokens, words                                     [B, nbest, T]  int64, -1 behind the data
+      token_lengths, word_lengths                       [B, nbest]     int64
+      num_hyps                                          [B]            int64, min(nbest, pairs with a finite end)
+      path, states, lm_states                           [B, nbest, T]  int64 per frame with `return_alignments`, else None
+    Row 0 equals `beam_decode_words`' result bit for bit.  `scores` is the search's own sum; the three parts add the same terms
+    in another order and agree with it to rounding; lm_scores = lm_weight * (raw LM score) + word_score * word_lengths up to
+    rounding.  Lexicon and LM are deterministic, so the rows are distinct token sequences; the same WORD sequence can appear
+    twice, with and without a closing separator -- the better one comes first, rows are not merged.  Inputs, widening, caching,
+    capture and the utterance groups under `max_work_bytes` are those of `beam_decode_words`.  nbest < 1 raises ValueError,
+    nbest > 8192 RuntimeError; nbest > beam_size only adds padding rows.
+    """
+    _check_beam(beam_size, beam_threshold)
+    if int(nbest) < 1:
+        raise ValueError("torch_asg_amd: nbest must be >= 1, got %d" % int(nbest))
+    with torch.no_grad():
+        return native().beam_decode_words_nbest(*_plain(inputs, transition), lexicon, word_lm, input_lengths, beam_size, nbest,
+                                                beam_threshold, lm_weight, word_score, token_score, return_alignments,
+                                                max_work_bytes)
+
+
 BeamNbest = collections.namedtuple("BeamNbest", ["scores", "emission_scores", "graph_scores", "tokens", "token_lengths",
                                                  "num_hyps", "path", "states"])
 
@@ -1486,6 +1563,14 @@ class ASGLoss(nn.Module):
         return beam_decode_words(inputs, self.transition, lexicon, word_lm, input_lengths, beam_size, beam_threshold, lm_weight,
                                  word_score, token_score, max_work_bytes)
 
+    def beam_decode_words_nbest(self, inputs, lexicon, word_lm, input_lengths=None, beam_size=256, nbest=10,
+                                beam_threshold=float("inf"), lm_weight=1.0, word_score=0.0, token_score=0.0,
+                                return_alignments=False, max_work_bytes=1 << 30):
+        """The n best hypotheses of `beam_decode_words` under this module's transitions, with the score split: see
+        `torch_asg_amd.beam_decode_words_nbest`."""
+        return beam_decode_words_nbest(inputs, self.transition, lexicon, word_lm, input_lengths, beam_size, nbest, beam_threshold,
+                                       lm_weight, word_score, token_score, return_alignments, max_work_bytes)
+
     def beam_decode_graph_nbest(self, inputs, graph, input_lengths=None, beam_size=256, nbest=10, beam_threshold=float("inf"),
                                 lm_weight=1.0, token_score=0.0, return_alignments=False, max_work_bytes=1 << 30):
         """The n best hypotheses of the beam search under this criterion's transitions, with their score split; see
@@ -1658,5 +1743,5 @@ class ASGLoss(nn.Module):
 
 
 # the streaming decoders (stream.py looks this module's `native` up at every call, so it is imported once the module stands)
-from .stream import (BeamStream, BeamStreamResult, BeamWordStream, BeamWordStreamResult,  # noqa: E402,F401
+from .stream import (BeamStream, BeamStreamResult, BeamWordStream, BeamWordStreamResult, BeamWordStreamNbest,  # noqa: E402,F401
                      BeamWindowStream, BeamWindowCommit, BeamWindowResult)

@@ -659,6 +659,50 @@ int asg_beam_decode_words(asg_ctx *ctx, const asg_problem *p, const asg_token_gr
                                                              st, ls, wd, wl, (hipStream_t) stream)));
 }
 
+static int check_beam_words_nbest(const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm, int beam_size,
+                                  int nbest) {
+    int rc = check_beam_words(p, gb, lm, beam_size);
+    if (rc) return rc;
+    if (nbest < 1) return ASG_ERR_INVALID;
+    if (nbest > kBeamMaxNbest) return ASG_ERR_UNSUPPORTED;
+    return ASG_OK;
+}
+
+size_t asg_beam_decode_words_nbest_work_bytes(const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                              int beam_size, int nbest) {
+    if (check_beam_words_nbest(p, gb, lm, beam_size, nbest) != ASG_OK) return 0;
+    return beam_word_nbest_work_bytes(p->dtype == ASG_DTYPE_F64 ? 8 : 4, (int) p->T, (int) p->B, beam_size,
+                                      beam_word_cap(beam_size, gb->max_out, (int) gb->num_start), nbest);
+}
+
+int asg_beam_decode_words_nbest(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                int beam_size, double beam_threshold, int nbest, void *work, size_t work_bytes, void *scores,
+                                void *emission_scores, void *graph_scores, void *lm_scores, int64_t *path, int64_t *tokens,
+                                int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words, int64_t *word_lengths,
+                                int64_t *num_hyps, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    int rc = check_beam_words_nbest(p, gb, lm, beam_size, nbest);
+    if (rc) return rc;
+    if (!(beam_threshold >= 0.0)) return ASG_ERR_INVALID;                  // negative or NaN
+    if (!work || !scores || !emission_scores || !graph_scores || !lm_scores || !tokens || !token_lengths || !words ||
+        !word_lengths || !num_hyps)
+        return ASG_ERR_INVALID;
+    if (work_bytes < asg_beam_decode_words_nbest_work_bytes(p, gb, lm, beam_size, nbest)) return ASG_ERR_WORKSPACE;
+    const Problem P = to_problem(p);
+    const GraphArgs G = to_graph_args(gb->graph);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    const WordLmArgs LM = to_word_lm_args(lm);
+    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
+    long long *ls = (long long *) lm_states, *wd = (long long *) words, *wl = (long long *) word_lengths;
+    long long *nh = (long long *) num_hyps;
+    return hip_status(ASG_DISPATCH(p, launch_beam_words_nbest<float>(P, G, BG, LM, beam_size, beam_threshold, nbest, work, scores,
+                                                                     emission_scores, graph_scores, lm_scores, pa, tk, tl, st, ls,
+                                                                     wd, wl, nh, (hipStream_t) stream),
+                                   launch_beam_words_nbest<double>(P, G, BG, LM, beam_size, beam_threshold, nbest, work, scores,
+                                                                   emission_scores, graph_scores, lm_scores, pa, tk, tl, st, ls,
+                                                                   wd, wl, nh, (hipStream_t) stream)));
+}
+
 static int check_beam_nbest(const asg_problem *p, const asg_token_graph_beam *gb, int beam_size, int nbest) {
     int rc = check_beam_graph(p, gb, beam_size);
     if (rc) return rc;
@@ -858,6 +902,50 @@ int asg_beam_word_stream_result(asg_ctx *ctx, const asg_token_graph_beam *gb, co
                                    launch_beam_word_stream_result<double>(G, BG, LM, beam_size, (int) max_frames, (int) B, state,
                                                                           final, scores, pa, tk, tl, st, ls, wd, wl, fr, su,
                                                                           (hipStream_t) stream)));
+}
+
+static int check_beam_word_stream_nbest(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype, int beam_size,
+                                        int64_t max_frames, int nbest) {
+    int rc = check_beam_word_stream(gb, lm, B, dtype, beam_size, max_frames);
+    if (rc) return rc;
+    if (nbest < 1) return ASG_ERR_INVALID;
+    if (nbest > kBeamMaxNbest) return ASG_ERR_UNSUPPORTED;
+    return ASG_OK;
+}
+
+size_t asg_beam_word_stream_nbest_work_bytes(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype,
+                                             int beam_size, int64_t max_frames, int nbest) {
+    if (check_beam_word_stream_nbest(gb, lm, B, dtype, beam_size, max_frames, nbest) != ASG_OK) return 0;
+    return beam_word_stream_nbest_work_bytes((int) max_frames, (int) B, beam_size, nbest);
+}
+
+int asg_beam_word_stream_nbest(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
+                               int64_t max_frames, const void *state, size_t state_bytes, int final, int nbest, void *work,
+                               size_t work_bytes, void *scores, void *graph_scores, void *lm_scores, int64_t *path, int64_t *tokens,
+                               int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words, int64_t *word_lengths,
+                               int64_t *num_hyps, int64_t *frames, int64_t *status, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    if (!gb || !gb->graph) return ASG_ERR_INVALID;
+    const asg_token_graph *g = gb->graph;
+    int rc = check_beam_word_stream_nbest(gb, lm, B, g->dtype, beam_size, max_frames, nbest);
+    if (rc) return rc;
+    if (!state || !work || !scores || !graph_scores || !lm_scores || !tokens || !token_lengths || !words || !word_lengths ||
+        !num_hyps || !frames || !status)
+        return ASG_ERR_INVALID;
+    if (state_bytes < beam_word_stream_bytes(gb, B, g->dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
+    if (work_bytes < beam_word_stream_nbest_work_bytes((int) max_frames, (int) B, beam_size, nbest)) return ASG_ERR_WORKSPACE;
+    const GraphArgs G = to_graph_args(g);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    const WordLmArgs LM = to_word_lm_args(lm);
+    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
+    long long *ls = (long long *) lm_states, *wd = (long long *) words, *wl = (long long *) word_lengths;
+    long long *nh = (long long *) num_hyps, *fr = (long long *) frames, *su = (long long *) status;
+    return hip_status(ASG_DISPATCH(g, launch_beam_word_stream_nbest<float>(G, BG, LM, beam_size, (int) max_frames, (int) B, state,
+                                                                           final, nbest, work, scores, graph_scores, lm_scores, pa,
+                                                                           tk, tl, st, ls, wd, wl, nh, fr, su, (hipStream_t) stream),
+                                   launch_beam_word_stream_nbest<double>(G, BG, LM, beam_size, (int) max_frames, (int) B, state,
+                                                                         final, nbest, work, scores, graph_scores, lm_scores, pa,
+                                                                         tk, tl, st, ls, wd, wl, nh, fr, su, (hipStream_t) stream)));
 }
 
 // A window stream state is sized like a problem of W frames (the ring); P is the commit period.

@@ -31,11 +31,14 @@ namespace asg {
 
 namespace {
 
-template <typename R, bool TRL>
+// FIN: the instantiation behind the n-best stage (asg_beam_word_nbest.hip), which also leaves the last set in memory at fin_off;
+// the decoder's own (FIN false) is the code object it was before that stage existed.
+template <typename R, bool TRL, bool FIN>
 __global__ void __launch_bounds__(kBT) beam_word_kernel(Problem P, GraphArgs g, BeamGraphArgs bg, WordLmArgs lm, int K, R theta,
                                                         int cap, int tbits, char *work, size_t per_utt, R *scores,
                                                         long long *path, long long *tokens, long long *tlen, long long *states,
-                                                        long long *lm_states, long long *words, long long *wlen) {
+                                                        long long *lm_states, long long *words, long long *wlen,
+                                                        size_t fin_off) {
     using KT = Key<R>;
     using U = typename KT::U;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -89,6 +92,13 @@ __global__ void __launch_bounds__(kBT) beam_word_kernel(Problem P, GraphArgs g, 
 
     // ---- the best end over the last kept set, the smallest pair on a tie; the backtrace, the words, the tokens
     const int na = ctl.na < K ? ctl.na : K;
+    if constexpr (FIN) {                                    // the n-best stage reads the last set from memory
+        char *fin = work + (size_t) b * per_utt + fin_off;
+        R *fv = (R *) (fin + 8);
+        int *fq = (int *) (fv + K), *fh = fq + K;
+        for (int k = tid; k < na; k += kBT) { fv[k] = cur_v[k]; fq[k] = cur_q[k]; fh[k] = cur_h[k]; }
+        if (tid == 0) *(int *) fin = na;
+    }
     U bkey;
     int bk;
     word_best_end<R>(f, fw, true, cur_h, cur_q, cur_v, na, bkey, bk);
@@ -124,31 +134,34 @@ size_t beam_word_work_bytes(int elem, int T, int B, int K, int cap) { return (si
 template <typename R>
 hipError_t launch_beam_words(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int K,
                              double theta, void *work, void *scores, long long *path, long long *tokens, long long *tlen,
-                             long long *states, long long *lm_states, long long *words, long long *wlen, hipStream_t stream) {
+                             long long *states, long long *lm_states, long long *words, long long *wlen, hipStream_t stream,
+                             size_t stride, size_t fin_off) {
     const int N = P.N;
     const int cap = beam_word_cap(K, BG.max_out, BG.num_start);
     const int tbits = word_table_bits(cap);
-    const size_t per = beam_word_per_utt(sizeof(R), P.T, K, cap);
+    const size_t per = stride ? stride : beam_word_per_utt(sizeof(R), P.T, K, cap);
     const size_t beam = kFixedLds + (size_t) K * (sizeof(R) + 8);
     const bool trl = beam + (size_t) N * N * sizeof(R) <= kLdsMax;
     const size_t dyn = beam + (trl ? (size_t) N * N * sizeof(R) : 0);
-#define ASG_BEAM_WORD(TRL)                                                                                                 \
+#define ASG_BEAM_WORD(TRL, FIN)                                                                                            \
     do {                                                                                                                   \
-        const void *fn = (const void *) beam_word_kernel<R, TRL>;                                                         \
+        const void *fn = (const void *) beam_word_kernel<R, TRL, FIN>;                                                    \
         if (dyn > 64 * 1024) (void) hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) dyn);     \
-        hipLaunchKernelGGL((beam_word_kernel<R, TRL>), dim3(P.B), dim3(kBT), dyn, stream, P, G, BG, LM, K, (R) theta, cap, \
-                           tbits, (char *) work, per, (R *) scores, path, tokens, tlen, states, lm_states, words, wlen);   \
+        hipLaunchKernelGGL((beam_word_kernel<R, TRL, FIN>), dim3(P.B), dim3(kBT), dyn, stream, P, G, BG, LM, K, (R) theta, \
+                           cap, tbits, (char *) work, per, (R *) scores, path, tokens, tlen, states, lm_states, words,     \
+                           wlen, fin_off);                                                                                 \
     } while (0)
-    if (trl) ASG_BEAM_WORD(true); else ASG_BEAM_WORD(false);
+    if (fin_off) { if (trl) ASG_BEAM_WORD(true, true); else ASG_BEAM_WORD(false, true); }
+    else if (trl) ASG_BEAM_WORD(true, false); else ASG_BEAM_WORD(false, false);
 #undef ASG_BEAM_WORD
     return hipGetLastError();
 }
 template hipError_t launch_beam_words<float>(const Problem &, const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &, int,
                                              double, void *, void *, long long *, long long *, long long *, long long *,
-                                             long long *, long long *, long long *, hipStream_t);
+                                             long long *, long long *, long long *, hipStream_t, size_t, size_t);
 template hipError_t launch_beam_words<double>(const Problem &, const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &, int,
                                               double, void *, void *, long long *, long long *, long long *, long long *,
-                                              long long *, long long *, long long *, hipStream_t);
+                                              long long *, long long *, long long *, hipStream_t, size_t, size_t);
 
 }  // namespace asg
 

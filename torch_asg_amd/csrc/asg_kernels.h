@@ -206,10 +206,14 @@ struct WordLmArgs {
 constexpr int kBeamWordMaxIndex = 1 << 25;    // H, Q: (source pair, source slot) is one 64-bit word
 int beam_word_cap(int K, int max_out, int num_start);
 size_t beam_word_work_bytes(int elem, int T, int B, int K, int cap);
+// stride != 0: the utterances' workspaces lie `stride` bytes apart (each with the layout above at its front); fin_off != 0: the
+// kernel also leaves |A_{len-1}| (int32) at that offset of each and, from byte 8 behind it, that set's values [K], then its int32
+// product states [K], then its int32 LM states [K] (asg_beam_word_nbest.hip).  0, 0: the decoder.
 template <typename R>
 hipError_t launch_beam_words(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int K,
                              double theta, void *work, void *scores, long long *path, long long *tokens, long long *tlen,
-                             long long *states, long long *lm_states, long long *words, long long *wlen, hipStream_t stream);
+                             long long *states, long long *lm_states, long long *words, long long *wlen, hipStream_t stream,
+                             size_t stride = 0, size_t fin_off = 0);
 
 // ---- The same search carried across chunks of frames (asg_beam_stream.hip): asg_beam_stream_*.  One slot of the state (byte
 // offsets, each part 256-byte aligned): the beam search's own layout for T = max_frames at the front, then hdr (int32 pos, |A|,
@@ -246,6 +250,34 @@ hipError_t launch_beam_word_stream_result(const GraphArgs &G, const BeamGraphArg
                                           int B, const void *state, int final, void *scores, long long *path, long long *tokens,
                                           long long *tlen, long long *states, long long *lm_states, long long *words,
                                           long long *wlen, long long *frames, long long *status, hipStream_t stream);
+
+// ---- The n best hypotheses of the search over pairs, with the score split three ways (asg_beam_word_nbest.hip):
+// asg_beam_decode_words_nbest and asg_beam_word_stream_nbest.  One-shot, one utterance's workspace: the word decoder's own layout
+// at the front, then (byte offsets, each part 256-byte aligned) fin (int32 |A_{len-1}|, then from byte 8 its values [K], product
+// states [K], LM states [K]) and rows (int32 [T][nb] product states of every hypothesis, frame-major), nb = min(nbest, K).  Behind
+// the utterances: what the one-best search returns (scores, two lengths, five [B][T] arrays).  The stream's scratch is the rows
+// alone, [B][max_frames][nb].
+struct BeamWordNbestLayout {
+    size_t fin, rows, per;
+    int nb;
+};
+BeamWordNbestLayout beam_word_nbest_layout(int elem, int T, int K, int cap, int nbest);
+size_t beam_word_nbest_work_bytes(int elem, int T, int B, int K, int cap, int nbest);
+size_t beam_word_stream_nbest_work_bytes(int max_frames, int B, int K, int nbest);
+// path / states / lm_states may be null (then they are not written)
+template <typename R>
+hipError_t launch_beam_words_nbest(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int K,
+                                   double theta, int nbest, void *work, void *scores, void *emission_scores, void *graph_scores,
+                                   void *lm_scores, long long *path, long long *tokens, long long *tlen, long long *states,
+                                   long long *lm_states, long long *words, long long *wlen, long long *num_hyps,
+                                   hipStream_t stream);
+// The same kernel over a stream state (read only).  The state holds no emissions: there is no emission sum.
+template <typename R>
+hipError_t launch_beam_word_stream_nbest(const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int K, int max_frames,
+                                         int B, const void *state, int final, int nbest, void *work, void *scores,
+                                         void *graph_scores, void *lm_scores, long long *path, long long *tokens, long long *tlen,
+                                         long long *states, long long *lm_states, long long *words, long long *wlen,
+                                         long long *num_hyps, long long *frames, long long *status, hipStream_t stream);
 
 // ---- The stream in bounded memory (asg_beam_window.hip): asg_beam_window_*.  One slot of the state has the layout of a stream
 // of W frames -- the back-pointers are a ring, frame u in row u mod W -- with the header int64 pos, int64 base, int32 |A|, carry,

@@ -203,6 +203,11 @@ BeamWordStreamResult = collections.namedtuple("BeamWordStreamResult", ["scores",
                                                                        "lm_states", "words", "word_lengths", "frames", "status"])
 
 
+BeamWordStreamNbest = collections.namedtuple("BeamWordStreamNbest", ["scores", "graph_scores", "lm_scores", "tokens", "token_lengths",
+                                                                     "words", "word_lengths", "num_hyps", "path", "states",
+                                                                     "lm_states", "frames", "status"])
+
+
 class BeamWordStream(_Stream):
     """`beam_decode_words` for an utterance that arrives in chunks: the beam search over pairs (LM history, lexicon product
     state), the word LM composed on the fly, carried from one chunk to the next for `batch_size` utterance slots at a time.
@@ -225,14 +230,16 @@ class BeamWordStream(_Stream):
     The state lives in one device buffer (about max_frames * beam_size * 12 bytes of back-pointers plus 60-80 bytes per
     candidate a frame can have, per slot; nothing is sized by the vocabulary or the LM).  Lexicon and LM are compiled in the
     constructor; `advance`, `result` and `reset` are one kernel launch each, copy nothing and do not synchronise, so they can be
-    captured in a graph and replayed with new chunk contents and lengths.  Not here: a windowed form with a committed prefix
-    (`BeamWindowStream` over pairs), n-best over pairs, a loss over pairs, LM look-ahead.
+    captured in a graph and replayed with new chunk contents and lengths.  `result_nbest` gives the n best hypotheses or
+    prefixes with their score split.  Not here: a windowed form with a committed prefix (`BeamWindowStream` over pairs), a loss
+    over pairs, LM look-ahead.
     """
     _API, _WIDE, _NARROW = "asg_beam_word_stream", 5, 4
 
     def __init__(self, transition, lexicon, word_lm, batch_size, max_frames, beam_size=256, beam_threshold=float("inf"),
                  lm_weight=1.0, word_score=0.0, token_score=0.0, dtype=torch.float32, device=None):
         self.lm_weight, self.word_score, self.token_score = lm_weight, word_score, token_score
+        self._nbest_work = {}                                  # nbest -> the scratch of result_nbest (not part of the state)
         super().__init__(transition, (lexicon, word_lm), batch_size, (max_frames,), beam_size, beam_threshold, dtype, device)
         (self.max_frames,) = self._shape
 
@@ -270,6 +277,47 @@ class BeamWordStream(_Stream):
         best prefix hypothesis, the largest value without any end term: it may end mid-word, and `words` holds the words whose
         separator the path has passed.  A slot without frames, with an empty beam or without a finite score: -inf, -1, 0."""
         return self._result(final)
+
+    def result_nbest(self, nbest, final=False, return_alignments=False):
+        """The `nbest` best hypotheses of every slot over the frames consumed so far, without changing the state -> a named tuple
+          scores, graph_scores, lm_scores [B, nbest]; tokens, words [B, nbest, max_frames] int64, -1 behind the data;
+          token_lengths, word_lengths [B, nbest]; num_hyps [B]; path, states, lm_states [B, nbest, max_frames] with
+          `return_alignments`, else None; frames, status [B] as `result`.
+        final=True: `beam_decode_words_nbest`'s rows for the utterance so far, bit for bit, for any chunking.  final=False: the n
+        best PREFIXES -- the kept pairs by value, mid-word ones included; graph_scores without a final weight, lm_scores without
+        the end of the sentence, no final word.  Row 0 equals `result(final)`.  The state keeps no emissions, so there is no
+        emission_scores: scores - (graph_scores + lm_scores) is it up to rounding.  One launch; the scratch it needs is allocated
+        once per `nbest` and kept on the stream, so a captured call replays.  nbest < 1 raises ValueError, nbest > 8192
+        RuntimeError."""
+        if int(nbest) < 1:
+            raise ValueError("torch_asg_amd: nbest must be >= 1, got %d" % int(nbest))
+        nbest = min(int(nbest), (1 << 31) - 1)
+        be = _asg.native()
+        L = _lib.lib()
+        B, dev, T = self.batch_size, self.device, self.max_frames
+        with be._guard(dev):
+            def call(work, nbytes, *outs):
+                return L.asg_beam_word_stream_nbest(None, *self._views, B, self.beam_size, T, self._state.data_ptr(),
+                                                    self._state.numel(), 1 if final else 0, nbest, work, nbytes, *outs)
+            work = self._nbest_work.get(nbest)
+            if work is None:
+                abi_dtype = _lib.ASG_DTYPE_F32 if self.dtype == torch.float32 else _lib.ASG_DTYPE_F64
+                nbytes = int(L.asg_beam_word_stream_nbest_work_bytes(*self._views, B, abi_dtype, self.beam_size, T, nbest))
+                if nbytes == 0:                                # the library refuses the arguments: its call says why
+                    _lib.check(call(None, 0, *(None,) * 13, 0, None), "asg_beam_word_stream_nbest")
+                work = self._nbest_work[nbest] = be._buf(nbytes, dev)
+            sc = torch.empty(3, B, nbest, dtype=self.dtype, device=dev)        # scores, graph and LM scores
+            wide = torch.empty(2, B, nbest, T, dtype=torch.int64, device=dev)  # tokens, words
+            align = torch.empty(3, B, nbest, T, dtype=torch.int64, device=dev) if return_alignments else (None,) * 3
+            lengths = torch.empty(2, B, nbest, dtype=torch.int64, device=dev)  # token_lengths, word_lengths
+            narrow = torch.empty(3, B, dtype=torch.int64, device=dev)          # num_hyps, frames, status
+            al = lambda i: align[i].data_ptr() if return_alignments else None      # noqa: E731
+            _lib.check(call(work.data_ptr(), work.numel(), sc[0].data_ptr(), sc[1].data_ptr(), sc[2].data_ptr(), al(0),
+                            wide[0].data_ptr(), lengths[0].data_ptr(), al(1), al(2), wide[1].data_ptr(), lengths[1].data_ptr(),
+                            narrow[0].data_ptr(), narrow[1].data_ptr(), narrow[2].data_ptr(), 0, be._stream(dev)),
+                       "asg_beam_word_stream_nbest")
+        return BeamWordStreamNbest(sc[0], sc[1], sc[2], wide[0], lengths[0], wide[1], lengths[1], narrow[0], align[0], align[1],
+                                   align[2], narrow[1], narrow[2])
 
     @staticmethod
     def _outputs(scores, wide, narrow):
