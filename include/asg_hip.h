@@ -522,9 +522,9 @@ int asg_beam_decode_words(asg_ctx *ctx, const asg_problem *p, const asg_token_gr
  * atomics only: bit-identical run to run.  Limits and errors: those of asg_beam_decode_words with T = max_frames (beam_size <=
  * 8192, H, Q <= 2^25, A < 2^31; ASG_ERR_UNSUPPORTED beyond) and those of asg_beam_stream_*: max_frames < 1, Tc < 0, B < 1,
  * beam_size < 1, a negative or NaN beam_threshold, a dtype that is not the graph's and the LM's, a NULL array or output:
- * ASG_ERR_INVALID; a state buffer smaller than asg_beam_word_stream_state_bytes: ASG_ERR_WORKSPACE.  Not here: the windowed form
- * with a committed prefix, a loss over pairs, LM look-ahead (n-best over pairs: asg_beam_word_stream_nbest below).  `flags` is
- * reserved (pass 0). */
+ * ASG_ERR_INVALID; a state buffer smaller than asg_beam_word_stream_state_bytes: ASG_ERR_WORKSPACE.  Not here: a loss over
+ * pairs, LM look-ahead (n-best over pairs: asg_beam_word_stream_nbest below; the windowed form with a committed prefix:
+ * asg_beam_word_window_* further below).  `flags` is reserved (pass 0). */
 size_t asg_beam_word_stream_state_bytes(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype, int beam_size,
                                         int64_t max_frames);
 int asg_beam_word_stream_reset(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
@@ -604,6 +604,89 @@ int asg_beam_word_stream_nbest(asg_ctx *ctx, const asg_token_graph_beam *gb, con
                                size_t work_bytes, void *scores, void *graph_scores, void *lm_scores, int64_t *path, int64_t *tokens,
                                int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words, int64_t *word_lengths,
                                int64_t *num_hyps, int64_t *frames, int64_t *status, int flags, void *stream);
+
+/* ---- WINDOWED streaming beam decoding with a lexicon and a word n-gram LM: asg_beam_word_stream_* in BOUNDED memory, as
+ * asg_beam_window_* is asg_beam_stream_* in bounded memory -- an open microphone, a meeting, a broadcast, with a word LM and a
+ * transcript in WORDS.  The search is asg_beam_word_stream_advance's (the same device code, the same sets and scores bit for bit);
+ * the back-pointers are kept only for a window of W frames, in rings, and the prefix of the transcript on which all surviving
+ * hypotheses agree is COMMITTED: returned by the advance that finds it, never to change.  No counterpart in the reference.
+ * A WORD WINDOW STREAM STATE serves B slots, for a fixed lexicon, LM shape, dtype, K = beam_size (no clamp to Q), window W >= 1 and
+ * commit period P, 1 <= P <= W (every call on a state passes the same gb, lm, B, beam_size, W and P).  Per slot it holds: pos
+ * (int64), the frames consumed so far -- unbounded; base (int64), the frames committed so far, base <= pos; the stored set
+ * A_{pos-1} of pairs: values, then product states q, then LM states h, exactly asg_beam_word_stream_*'s; three rings bq / bh / bs
+ * int32 [W][K], the back-pointers (product state, LM state, source slot) of frame u in row u mod W (computed in 64 bits); carry
+ * (int32), the label of the last committed frame or -1; carry_state (int32), the automaton state of the last committed frame or
+ * -1; a sticky status word; and the table and lists of the search.  The contents are opaque; a state must be reset before its
+ * first use.
+ *   asg_beam_word_window_reset: as asg_beam_word_stream_reset (all C slots of the table emptied), and pos = base = 0, carry =
+ *     carry_state = -1, status = 0 for the chosen slots.
+ *   asg_beam_word_window_advance: p->inputs is a chunk [Tc = p->T, B, N], p->input_lengths the chunk's lengths, p->transition and
+ *     beam_threshold those of this call.  For slot b, n = clamp(input_lengths[b], 0, Tc) -- there is no max_frames and no overflow
+ *     word.  The chunk's frames are the frames pos .. pos+n-1 of the utterance and run exactly as in asg_beam_word_stream_advance
+ *     (frame 0 -- and only pos == 0 -- from start_q, the first frame of a chunk from the stored set, an empty set stays empty); the
+ *     back-pointers of frame u go to row u mod W.  After each frame, with pos now counting it, a COMMIT ATTEMPT runs if
+ *     pos mod P == 0 and the set is not empty.  It is asg_beam_window_advance's, over the slots of pairs:
+ *       1. Convergence.  R = all slots of A_{pos-1}.  If |R| == 1: c = pos-1.  Otherwise for u = pos-1 down to base+1:
+ *          R <- { bs[u][k] : k in R }; the first u at which |R| == 1 gives c = u-1; no such u: no c.  If c exists, the path from
+ *          that one slot of frame c back to frame base is committed: the frames base .. c in ascending order, and base = c+1.
+ *          (Slots, not product states: two pairs with one q and two histories are two slots.)
+ *       2. Forced commit, if afterwards pos - base > W - P: F = (pos - base) - (W - P).  The best prefix pair of A_{pos-1} --
+ *          largest v, smallest pair on a tie, -0 equal to +0: the rule of asg_beam_word_stream_result(final = 0) -- is followed
+ *          back to frame base+F-1; the frames base .. base+F-1 on that path are committed, base += F and status |= 1.
+ *     Committing a frame with pair (h, q) appends label[q] to new_path, state[q] to new_states and h to new_lm_states at the next
+ *     free column of this call's output row.  To new_tokens it appends label[q] if label[q] != carry.  To new_words it appends
+ *     word_of_state[carry_state] if label[q] == separator, carry != separator and carry != -1 (the frame is not frame 0): the
+ *     separator behind another label is a separator edge, and its word ends in the state before -- asg_beam_decode_words' rule
+ *     for words, continued across segments: the label and the state before the first frame of a segment are those of the last
+ *     frame committed before it, in this call or an earlier one, so an edge that straddles two commits or two calls yields its
+ *     word exactly once.  (A forced commit may splice two paths; the state before a separator is then whatever was committed, and
+ *     its word may be -1.)  Then carry = label[q], carry_state = state[q].  After an attempt pos - base <= W - P, between attempts
+ *     pos - base <= W: no live row is ever overwritten.  Then pos += n.
+ *     Outputs: new_path, new_states, new_lm_states, new_tokens, new_words int64 [B][W + Tc] (committed <= (pos - base before the
+ *     call) + n <= W + Tc), -1 behind the data; new_frames [B], the frames this call committed; new_token_lengths,
+ *     new_word_lengths [B].  Every element of all eight is written by the kernel.  Tc = 0 is allowed and writes the empty outputs.
+ *   asg_beam_word_window_result: reads the state only; the stream goes on.  The winner is chosen as in
+ *     asg_beam_word_stream_result: final != 0: end(h, q) = (v + final_w[q]) + endw, the end of asg_beam_decode_words; final == 0:
+ *     v, the best prefix; the smallest pair on a tie.  scores [B]; path, states, lm_states, tokens, words int64 [B][W], -1 behind
+ *     the data: path, states and lm_states hold the winner's frames base .. pos-1 (the uncommitted TAIL, at most W); tokens their
+ *     collapse started from carry; words the words of the tail by the rule above, started from carry / carry_state, then, with
+ *     final != 0, the word of the final step if the winner ends in a word-end node (also when the tail is empty).  token_lengths,
+ *     word_lengths [B]; frames [B] = pos; committed [B] = base; status [B]: bit 0 = a forced commit has happened (sticky until the
+ *     reset), bit 1 = pos >= 1 and the set is empty.  No frame, an empty set or no finite end: score -inf, the integer arrays -1,
+ *     both lengths 0; what was committed stays committed.  The backtrace is at most W steps, whatever pos.
+ * REQUIRED PROPERTIES (no tolerance in any).  1. Search identity: for any chunking of x[0:L], any W and P, result(final = 1).scores
+ * equals asg_beam_decode_words' score on x bit for bit and result(final = 0).scores equals asg_beam_word_stream_result's: the
+ * rings cannot alter a score, the frame reads its sources from the set.  2. Chunk invariance: at equal pos, base, carry,
+ * carry_state, status and the concatenation of everything advance has returned are the same for every chunking, forced commits
+ * included -- attempts happen at frame indices, not at call boundaries.  3. Exactness: while status bit 0 is clear and the
+ * one-shot score is finite, concat(new_path of all calls) followed by the tail path equals the one-shot path[:L], the same for
+ * states and lm_states, concat(new_tokens) followed by the tail tokens equals the one-shot tokens[:token_length], and
+ * concat(new_words) followed by the tail words (final = 1) equals the one-shot words[:word_length]; with W - P >= L a forced commit
+ * is impossible.  4. With status bit 0 set the outputs are still exactly those specified above.
+ * State (asg_beam_word_window_state_bytes; 0 for arguments that the calls refuse), every part rounded up to 256 bytes:
+ *   B * (asg_beam_decode_words' bytes per utterance with T = W, 3 * W*K*4 + C*(16 + e) + cap*(e + 12), + 256 (pos, base, set size,
+ *   carry, carry_state, status) + K*(e + 8) (the stored set)), e = 4 / 8.  No term in H, V, A, Q or pos.
+ * Each call is ONE launch on `stream`, one 1024-thread workgroup per slot for advance and result: no host synchronisation, no
+ * copy, no memset, so a captured advance or result is one kernel node of a linear chain and replays with new chunk contents and
+ * lengths.  Integer atomics only: bit-identical run to run.  Limits and errors: those of asg_beam_decode_words with T = W
+ * (beam_size <= 8192 with no clamp to Q, H, Q <= 2^25, A < 2^31, W within asg_beam_window_*'s bound; ASG_ERR_UNSUPPORTED beyond);
+ * W < 1, P < 1, P > W, Tc < 0, B < 1, beam_size < 1, a negative or NaN beam_threshold, a dtype that is not the graph's and the
+ * LM's, a NULL array or output: ASG_ERR_INVALID; a state buffer smaller than asg_beam_word_window_state_bytes: ASG_ERR_WORKSPACE.
+ * Not here: n-best from the window, LM look-ahead, a commit rule that looks at scores.  `flags` is reserved (pass 0). */
+size_t asg_beam_word_window_state_bytes(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype, int beam_size,
+                                        int64_t W, int64_t P);
+int asg_beam_word_window_reset(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
+                               int64_t W, int64_t P, void *state, size_t state_bytes, const uint8_t *mask, int flags, void *stream);
+int asg_beam_word_window_advance(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                 int beam_size, double beam_threshold, int64_t W, int64_t P, void *state, size_t state_bytes,
+                                 int64_t *new_path, int64_t *new_states, int64_t *new_lm_states, int64_t *new_tokens,
+                                 int64_t *new_words, int64_t *new_frames, int64_t *new_token_lengths, int64_t *new_word_lengths,
+                                 int flags, void *stream);
+int asg_beam_word_window_result(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
+                                int64_t W, int64_t P, const void *state, size_t state_bytes, int final, void *scores, int64_t *path,
+                                int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words,
+                                int64_t *word_lengths, int64_t *frames, int64_t *committed, int64_t *status, int flags,
+                                void *stream);
 
 /* ---- Full score of the ASG lattice COMPOSED with a token automaton (the log-semiring counterpart of the decoder above), its
  * gradients, and the automaton's score of each target: the pieces of an ASG loss whose normaliser includes a token-level

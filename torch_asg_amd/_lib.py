@@ -32,7 +32,9 @@ SYMBOLS = ["asg_hip_version", "asg_hip_strerror", "asg_ctx_create", "asg_ctx_des
            "asg_beam_decode_words_work_bytes", "asg_beam_decode_words",
            "asg_beam_word_stream_state_bytes", "asg_beam_word_stream_reset", "asg_beam_word_stream_advance",
            "asg_beam_word_stream_result", "asg_beam_decode_words_nbest_work_bytes", "asg_beam_decode_words_nbest",
-           "asg_beam_word_stream_nbest_work_bytes", "asg_beam_word_stream_nbest"]
+           "asg_beam_word_stream_nbest_work_bytes", "asg_beam_word_stream_nbest",
+           "asg_beam_word_window_state_bytes", "asg_beam_word_window_reset", "asg_beam_word_window_advance",
+           "asg_beam_word_window_result"]
 ABI_VERSION = 230        # include/asg_hip.h: ASG_HIP_VERSION this package was written against
 
 
@@ -161,6 +163,11 @@ def lib():
     L.asg_beam_word_stream_nbest_work_bytes.restype = sz
     L.asg_beam_word_stream_nbest_work_bytes.argtypes = [bp, wp, i64, ci, ci, i64, ci]
     L.asg_beam_word_stream_nbest.argtypes = [vp, bp, wp, i64, ci, i64, vp, sz, ci, ci, vp, sz] + [vp] * 13 + [ci, vp]
+    L.asg_beam_word_window_state_bytes.restype = sz
+    L.asg_beam_word_window_state_bytes.argtypes = [bp, wp, i64, ci, ci, i64, i64]
+    L.asg_beam_word_window_reset.argtypes = [vp, bp, wp, i64, ci, i64, i64, vp, sz, vp, ci, vp]
+    L.asg_beam_word_window_advance.argtypes = [vp, pp, bp, wp, ci, ctypes.c_double, i64, i64, vp, sz] + [vp] * 8 + [ci, vp]
+    L.asg_beam_word_window_result.argtypes = [vp, bp, wp, i64, ci, i64, i64, vp, sz, ci] + [vp] * 11 + [ci, vp]
     blp = ctypes.POINTER(AsgTokenGraphBeamLoss)
     L.asg_beam_graph_full_work_bytes.restype = sz
     L.asg_beam_graph_full_work_bytes.argtypes = [pp, blp, ci, ci]

@@ -1599,6 +1599,13 @@ class ASGLoss(nn.Module):
         return BeamWindowStream(self.transition, graph, batch_size, window, commit_every, beam_size, beam_threshold, lm_weight,
                                 token_score, self.transition.dtype, self.transition.device)
 
+    def beam_word_window_stream(self, lexicon, word_lm, batch_size, window, commit_every=None, beam_size=256,
+                                beam_threshold=float("inf"), lm_weight=1.0, word_score=0.0, token_score=0.0):
+        """A streaming beam decoder with a lexicon and a word n-gram LM in bounded memory under this module's transition matrix
+        (read again at every chunk): see `torch_asg_amd.BeamWordWindowStream`."""
+        return BeamWordWindowStream(self.transition, lexicon, word_lm, batch_size, window, commit_every, beam_size, beam_threshold,
+                                    lm_weight, word_score, token_score, self.transition.dtype, self.transition.device)
+
     def graph_loss(self, inputs, targets, graph, input_lengths=None, target_lengths=None, lm_weight=1.0, token_score=0.0,
                    max_work_bytes=1 << 30):
         """`torch_asg_amd.graph_asg_loss` under this module's transition matrix, reduction and scale_mode.  float16 / bfloat16
@@ -1744,4 +1751,5 @@ class ASGLoss(nn.Module):
 
 # the streaming decoders (stream.py looks this module's `native` up at every call, so it is imported once the module stands)
 from .stream import (BeamStream, BeamStreamResult, BeamWordStream, BeamWordStreamResult, BeamWordStreamNbest,  # noqa: E402,F401
-                     BeamWindowStream, BeamWindowCommit, BeamWindowResult)
+                     BeamWindowStream, BeamWindowCommit, BeamWindowResult, BeamWordWindowStream, BeamWordWindowCommit,
+                     BeamWordWindowResult)

@@ -1027,6 +1027,101 @@ int asg_beam_window_result(asg_ctx *ctx, const asg_token_graph_beam *gb, int64_t
                                                                      st, fr, co, su, (hipStream_t) stream)));
 }
 
+// A word window stream state is sized like a word stream of W frames (the rings); P is the commit period.
+static int check_beam_word_window(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype, int beam_size,
+                                  int64_t W, int64_t P) {
+    if (W < 1 || P < 1 || P > W) return ASG_ERR_INVALID;
+    return check_beam_word_stream(gb, lm, B, dtype, beam_size, W);
+}
+
+static size_t beam_word_window_bytes(const asg_token_graph_beam *gb, int64_t B, int dtype, int beam_size, int64_t W) {
+    return beam_word_window_state_bytes(dtype == ASG_DTYPE_F64 ? 8 : 4, (int) W, (int) B, beam_size,
+                                        beam_word_cap(beam_size, gb->max_out, (int) gb->num_start));
+}
+
+// The number of automaton states word_of_state is indexed by, as the kernels clamp to it.
+static int word_lm_states(const asg_word_lm *lm) { return lm->S < ((int64_t) 1 << 31) - 1 ? (int) lm->S : (1 << 31) - 1; }
+
+size_t asg_beam_word_window_state_bytes(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype, int beam_size,
+                                        int64_t W, int64_t P) {
+    if (check_beam_word_window(gb, lm, B, dtype, beam_size, W, P) != ASG_OK) return 0;
+    return beam_word_window_bytes(gb, B, dtype, beam_size, W);
+}
+
+int asg_beam_word_window_reset(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
+                               int64_t W, int64_t P, void *state, size_t state_bytes, const uint8_t *mask, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    if (!gb || !gb->graph) return ASG_ERR_INVALID;
+    const int dtype = gb->graph->dtype;
+    int rc = check_beam_word_window(gb, lm, B, dtype, beam_size, W, P);
+    if (rc) return rc;
+    if (!state) return ASG_ERR_INVALID;
+    if (state_bytes < beam_word_window_bytes(gb, B, dtype, beam_size, W)) return ASG_ERR_WORKSPACE;
+    return hip_status(launch_beam_word_window_reset(dtype == ASG_DTYPE_F64 ? 8 : 4, to_beam_graph_args(gb), beam_size, (int) W,
+                                                    (int) B, state, mask, (hipStream_t) stream));
+}
+
+int asg_beam_word_window_advance(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                 int beam_size, double beam_threshold, int64_t W, int64_t P, void *state, size_t state_bytes,
+                                 int64_t *new_path, int64_t *new_states, int64_t *new_lm_states, int64_t *new_tokens,
+                                 int64_t *new_words, int64_t *new_frames, int64_t *new_token_lengths, int64_t *new_word_lengths,
+                                 int flags, void *stream) {
+    (void) ctx; (void) flags;
+    if (!p) return ASG_ERR_INVALID;
+    int rc = check_beam_word_window(gb, lm, p->B, p->dtype, beam_size, W, P);
+    if (rc) return rc;
+    if (p->T < 0 || p->N != gb->graph->N) return ASG_ERR_INVALID;
+    if (p->T > 0 && (rc = check_beam_words(p, gb, lm, beam_size)) != ASG_OK) return rc;
+    if (!(beam_threshold >= 0.0)) return ASG_ERR_INVALID;                  // negative or NaN
+    if (!state || !new_path || !new_states || !new_lm_states || !new_tokens || !new_words || !new_frames || !new_token_lengths ||
+        !new_word_lengths)
+        return ASG_ERR_INVALID;
+    if (state_bytes < beam_word_window_bytes(gb, p->B, p->dtype, beam_size, W)) return ASG_ERR_WORKSPACE;
+    const Problem Pr = to_problem(p);                                      // (no frame: the launch still writes the empty outputs)
+    const GraphArgs G = to_graph_args(gb->graph);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    const WordLmArgs LM = to_word_lm_args(lm);
+    const int S = word_lm_states(lm);
+    long long *np = (long long *) new_path, *ns = (long long *) new_states, *nl = (long long *) new_lm_states;
+    long long *nt = (long long *) new_tokens, *nw = (long long *) new_words, *nf = (long long *) new_frames;
+    long long *tl = (long long *) new_token_lengths, *wl = (long long *) new_word_lengths;
+    return hip_status(ASG_DISPATCH(p, launch_beam_word_window_advance<float>(Pr, G, BG, LM, S, beam_size, beam_threshold, (int) W,
+                                                                             (int) P, state, np, ns, nl, nt, nw, nf, tl, wl,
+                                                                             (hipStream_t) stream),
+                                   launch_beam_word_window_advance<double>(Pr, G, BG, LM, S, beam_size, beam_threshold, (int) W,
+                                                                           (int) P, state, np, ns, nl, nt, nw, nf, tl, wl,
+                                                                           (hipStream_t) stream)));
+}
+
+int asg_beam_word_window_result(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
+                                int64_t W, int64_t P, const void *state, size_t state_bytes, int final, void *scores, int64_t *path,
+                                int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words,
+                                int64_t *word_lengths, int64_t *frames, int64_t *committed, int64_t *status, int flags,
+                                void *stream) {
+    (void) ctx; (void) flags;
+    if (!gb || !gb->graph) return ASG_ERR_INVALID;
+    const asg_token_graph *g = gb->graph;
+    int rc = check_beam_word_window(gb, lm, B, g->dtype, beam_size, W, P);
+    if (rc) return rc;
+    if (!state || !scores || !path || !tokens || !token_lengths || !states || !lm_states || !words || !word_lengths || !frames ||
+        !committed || !status)
+        return ASG_ERR_INVALID;
+    if (state_bytes < beam_word_window_bytes(gb, B, g->dtype, beam_size, W)) return ASG_ERR_WORKSPACE;
+    const GraphArgs G = to_graph_args(g);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    const WordLmArgs LM = to_word_lm_args(lm);
+    const int S = word_lm_states(lm);
+    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
+    long long *ls = (long long *) lm_states, *wd = (long long *) words, *wl = (long long *) word_lengths;
+    long long *fr = (long long *) frames, *co = (long long *) committed, *su = (long long *) status;
+    return hip_status(ASG_DISPATCH(g, launch_beam_word_window_result<float>(G, BG, LM, S, beam_size, (int) W, (int) B, state, final,
+                                                                            scores, pa, tk, tl, st, ls, wd, wl, fr, co, su,
+                                                                            (hipStream_t) stream),
+                                   launch_beam_word_window_result<double>(G, BG, LM, S, beam_size, (int) W, (int) B, state, final,
+                                                                          scores, pa, tk, tl, st, ls, wd, wl, fr, co, su,
+                                                                          (hipStream_t) stream)));
+}
+
 static int check_beam_loss(const asg_problem *p, const asg_token_graph_beam_loss *gl, int beam_size) {
     if (!gl) return ASG_ERR_INVALID;
     int rc = check_beam_graph(p, gl->beam, beam_size);

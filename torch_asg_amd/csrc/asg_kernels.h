@@ -296,6 +296,29 @@ hipError_t launch_beam_window_result(const GraphArgs &G, const BeamGraphArgs &BG
                                      void *scores, long long *path, long long *tokens, long long *tlen, long long *states,
                                      long long *frames, long long *committed, long long *status, hipStream_t stream);
 
+// ---- The search over pairs in bounded memory (asg_beam_word_window.hip): asg_beam_word_window_*.  One slot of the state has the
+// layout of a word stream of W frames -- bq / bh / bs are rings, frame u in row u mod W -- with the header int64 pos, int64 base,
+// int32 |A|, carry, carry_state, status.  K = beam_size, cap = beam_word_cap(..), CP the commit period, S the number of states of
+// the lexicon automaton (word_of_state has S entries).
+BeamStreamLayout beam_word_window_layout(int elem, int W, int K, int cap);
+size_t beam_word_window_state_bytes(int elem, int W, int B, int K, int cap);
+hipError_t launch_beam_word_window_reset(int elem, const BeamGraphArgs &BG, int K, int W, int B, void *state,
+                                         const unsigned char *mask, hipStream_t stream);
+// new_path / new_states / new_lm_states / new_tokens / new_words [B][W + P.T], new_frames / new_tlen / new_wlen [B]: every element
+// is written
+template <typename R>
+hipError_t launch_beam_word_window_advance(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int S,
+                                           int K, double theta, int W, int CP, void *state, long long *new_path,
+                                           long long *new_states, long long *new_lm_states, long long *new_tokens,
+                                           long long *new_words, long long *new_frames, long long *new_tlen, long long *new_wlen,
+                                           hipStream_t stream);
+template <typename R>
+hipError_t launch_beam_word_window_result(const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int S, int K, int W,
+                                          int B, const void *state, int final, void *scores, long long *path, long long *tokens,
+                                          long long *tlen, long long *states, long long *lm_states, long long *words,
+                                          long long *wlen, long long *frames, long long *committed, long long *status,
+                                          hipStream_t stream);
+
 // ---- The n best final hypotheses of that search, with the score split (asg_beam_nbest.hip): asg_beam_decode_graph_nbest.
 // One utterance's workspace: the beam search's own layout at the front, then (byte offsets, each part 256-byte aligned) fin
 // (int32 |A_{len-1}|, then from byte 8 its values [K]) and rows (int32 [T][nb] product states of every hypothesis, frame-major),

@@ -1,7 +1,8 @@
-"""The streaming beam decoders (`BeamStream`, `BeamWordStream`, `BeamWindowStream`) on one private base class.
+"""The streaming beam decoders (`BeamStream`, `BeamWordStream`, `BeamWindowStream`, `BeamWordWindowStream`) on one private base
+class.
 
-The three families of C entry points (include/asg_hip.h::asg_beam_stream_*, asg_beam_word_stream_*, asg_beam_window_*) take
-their arguments in one order,
+The four families of C entry points (include/asg_hip.h::asg_beam_stream_*, asg_beam_word_stream_*, asg_beam_window_*,
+asg_beam_word_window_*) take their arguments in one order,
 
     (ctx, [p], views..., [B], K, [theta], shape..., state, nbytes, ..., flags, stream)
 
@@ -231,7 +232,7 @@ class BeamWordStream(_Stream):
     candidate a frame can have, per slot; nothing is sized by the vocabulary or the LM).  Lexicon and LM are compiled in the
     constructor; `advance`, `result` and `reset` are one kernel launch each, copy nothing and do not synchronise, so they can be
     captured in a graph and replayed with new chunk contents and lengths.  `result_nbest` gives the n best hypotheses or
-    prefixes with their score split.  Not here: a windowed form with a committed prefix (`BeamWindowStream` over pairs), a loss
+    prefixes with their score split.  The windowed form with a committed prefix is `BeamWordWindowStream`.  Not here: a loss
     over pairs, LM look-ahead.
     """
     _API, _WIDE, _NARROW = "asg_beam_word_stream", 5, 4
@@ -402,3 +403,87 @@ class BeamWindowStream(_Stream):
         path, tokens, states = wide
         token_lengths, frames, committed, status = narrow
         return BeamWindowResult(scores, path, tokens, token_lengths, states, frames, committed, status)
+
+
+BeamWordWindowCommit = collections.namedtuple("BeamWordWindowCommit", ["path", "states", "lm_states", "tokens", "token_lengths",
+                                                                       "words", "word_lengths", "frames"])
+BeamWordWindowResult = collections.namedtuple("BeamWordWindowResult", ["scores", "path", "tokens", "token_lengths", "states",
+                                                                       "lm_states", "words", "word_lengths", "frames", "committed",
+                                                                       "status"])
+
+
+class BeamWordWindowStream(_Stream):
+    """`BeamWordStream` in bounded memory, for utterances without an end in sight: the beam search over pairs (LM history,
+    lexicon product state) with the word LM composed on the fly, the back-pointers kept only for a window of `window` frames,
+    and the prefix of the transcript on which all surviving hypotheses agree COMMITTED -- handed out, in tokens and in WORDS, by
+    the `advance` that finds it, never to change.  No gradient.
+
+        s = BeamWordWindowStream(transition, lexicon, word_lm, batch_size, window=128, beam_size=256)
+        for chunk in chunks:                 # [Tc, B, N] each, for as long as the microphone is open
+            new = s.advance(chunk)           # new.words[b, :new.word_lengths[b]]: append them to slot b's transcript
+            tail = s.result()                # the best hypothesis for the frames that are not committed yet
+        last = s.result(final=True)          # the committed words + last.words are the transcript
+
+    The commit rule is `BeamWindowStream`'s over the kept pairs (include/asg_hip.h::asg_beam_word_window_advance): after every
+    frame whose count is a multiple of `commit_every` (default max(1, window // 4)) the device looks for the latest frame at
+    which all hypotheses of the beam share one ancestor and commits everything up to it; if the uncommitted frames would not
+    leave room for the next `commit_every` frames in the window, it commits the oldest ones along the best prefix hypothesis
+    and sets bit 0 of `status`.  A word is committed with the frame of its separator, exactly once, wherever commits and calls
+    cut the utterance.  Scores are `BeamWordStream`'s and `beam_decode_words`' bit for bit, for every window; while bit 0 of
+    `status` is clear the committed frames followed by the tail are `beam_decode_words`' path, and the same for states,
+    lm_states, tokens and words.  What is committed does not depend on how the frames were cut into chunks.
+
+    The state is one device buffer of about window * beam_size * 12 bytes of back-pointers plus 60-80 bytes per candidate a
+    frame can have, per slot, whatever the length of the utterance; `result` walks at most `window` frames.  `advance`, `result`
+    and `reset` are one kernel launch each, copy nothing and do not synchronise, so they can be captured and replayed.  The other
+    arguments are `BeamWordStream`'s (`dtype` None: the transition's); there is no bound on the number of frames and no
+    n-best.
+    """
+    _API, _WIDE, _NARROW = "asg_beam_word_window", 5, 5
+    _check_automaton, _compile = BeamWordStream._check_automaton, BeamWordStream._compile      # the automaton is BeamWordStream's,
+    _check_shape = BeamWindowStream._check_shape                                               # the shape BeamWindowStream's
+
+    def __init__(self, transition, lexicon, word_lm, batch_size, window, commit_every=None, beam_size=256,
+                 beam_threshold=float("inf"), lm_weight=1.0, word_score=0.0, token_score=0.0, dtype=None, device=None):
+        self.lm_weight, self.word_score, self.token_score = lm_weight, word_score, token_score
+        super().__init__(transition, (lexicon, word_lm), batch_size, (window, commit_every), beam_size, beam_threshold,
+                         transition.dtype if dtype is None else dtype, device)
+        self.window, self.commit_every = self._shape
+
+    def reset(self, mask=None):
+        """Start new utterances: in every slot (mask None), or in the slots where `mask` (bool or integer [B]) is not zero --
+        the other slots go on."""
+        self._reset(mask)
+
+    def advance(self, chunk, chunk_lengths=None):
+        """Consume `chunk` [Tc, B, N] as `BeamWordStream.advance` does, without a bound on the frames -> what this call
+        committed, a named tuple
+          path, states, lm_states, tokens, words [B, window + Tc] int64, -1 behind the data: label, automaton state and LM state
+          of every newly committed frame, and the tokens and words they add to the transcript (both go on across calls);
+          token_lengths, word_lengths [B]; frames [B], the number of frames committed by this call."""
+        path, states, lm_states, tokens, words, frames, token_lengths, word_lengths = self._advance(chunk, chunk_lengths)
+        return BeamWordWindowCommit(path, states, lm_states, tokens, token_lengths, words, word_lengths, frames)
+
+    def _commit_outputs(self, Tc):
+        wide = torch.empty(5, self.batch_size, self.window + Tc, dtype=torch.int64, device=self.device)
+        narrow = torch.empty(3, self.batch_size, dtype=torch.int64, device=self.device)
+        return tuple(wide) + tuple(narrow)                     # path, states, lm_states, tokens, words; frames, two lengths
+
+    def result(self, final=False):
+        """The best hypothesis of every slot for the frames that are not committed yet, without changing the state -> a named
+        tuple
+          scores [B], the score of the whole hypothesis; path, tokens, states, lm_states, words [B, window] int64, -1 behind the
+          data: the uncommitted tail (a first label that repeats the last committed one is no token; a separator behind the
+          last committed label ends a word); token_lengths, word_lengths [B]; frames [B], the frames consumed; committed [B],
+          the frames committed; status [B]: bit 0 = frames were committed before the hypotheses agreed on them, bit 1 = the beam
+          is empty.
+        final as for `BeamWordStream.result`: final=True appends the word of a path that ends in a word-end node.  A slot
+        without frames, with an empty beam or without a finite score: -inf, -1, 0."""
+        return self._result(final)
+
+    @staticmethod
+    def _outputs(scores, wide, narrow):
+        path, tokens, states, lm_states, words = wide
+        token_lengths, word_lengths, frames, committed, status = narrow
+        return BeamWordWindowResult(scores, path, tokens, token_lengths, states, lm_states, words, word_lengths, frames, committed,
+                                    status)
