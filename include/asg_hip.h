@@ -475,6 +475,72 @@ int asg_beam_decode_words(asg_ctx *ctx, const asg_problem *p, const asg_token_gr
                           int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words, int64_t *word_lengths,
                           int flags, void *stream);
 
+/* ---- asg_beam_decode_words with LM LOOK-AHEAD: inside a word, a pair's value also carries the best LM score that any word below
+ * its trie node can still get after the pair's history, so that a narrow beam ranks partial words by more than acoustics.  The
+ * term telescopes: every edge adds the difference between the look-ahead of its two ends, the separator edge takes back what the
+ * word entered with, and a complete hypothesis sums the terms of asg_beam_decode_words plus terms that cancel.  One value per
+ * pair stays the only search state; table, select, prune, pair order, back-pointers, the eight outputs and the workspace
+ * (asg_beam_decode_words_work_bytes serves both calls) are asg_beam_decode_words'.  No counterpart in the reference.
+ * The arrays (torch_asg_amd.WordLookahead builds them):
+ *   ranks:  the trie (automaton states of the lexicon, root 0, the separator arcs left out) in pre-order, children by ascending
+ *           token; the word of a word-end node takes the next rank when the node is entered.  rlo[n] / rhi[n] are the counter on
+ *           entry and on exit, so the words below n, its own included, have the ranks [rlo[n], rhi[n]).  LM words the lexicon does
+ *           not spell have no rank; a lexicon word without an LM arc has a rank and no arcs.
+ *   rows:   for every LM state s its arcs whose word has a rank, sorted by rank: krow [H+1] offsets, krank [A'] ascending within
+ *           a row.  E(s, n) = the largest lw over the arcs of row s with rank in [rlo[n], rhi[n]), -inf if there is none.
+ *           tab [levels][A']: tab[k][i] = the largest lw over the arcs i .. i + 2^k - 1 that lie in the row of i (tab[0] is lw in
+ *           rank order), 2^(levels-1) <= the longest row; E is two binary searches in krank and two reads.  -0 is stored as +0,
+ *           so a maximum is one bit pattern and the values, not the layout, are what is specified.  dense0 [S] holds E(0, n)
+ *           for every node: state 0, the empty history, ends the backoff chains and has the longest row, so its answer is
+ *           one read (the same value, another layout).
+ *   la_state [H]: the history whose rows the look-ahead of h reads: h backed off until at most order - 1 backoff steps remain
+ *           to a state without a backoff (order 1: one state for all h, unigram smearing; order >= the LM's: h itself).
+ *   The caller guarantees: every ranked word with an arc in any row has an arc in every state without a backoff (an ARPA LM: all
+ *   unigrams in state 0).  Then LA = -inf says that no word below the node is accepted, whatever the truncation.
+ * All sums in the dtype of the problem, in the order written ("max(r, x)" is x if x > r, else r):
+ *   LA(s, n):  r = -inf; a = 0
+ *              loop: r = max(r, a + E(s, n));  if backoff[s] < 0: return r;  a = a + bw[s];  s = backoff[s]
+ *   L(h, n) = 0 if n is the root, else LA(la_state[h], n)
+ *   t = 0:  for a start state q, c = (start_w[q] + L(start, state(q))) + I[0][i(q)].
+ *   stay:   unchanged: the same node, nothing added.
+ *   edge from a kept (h, q') to q with label i != separator: L(h, state(q)) == -inf is no candidate (a dead end is pruned here);
+ *           else c = ((v + tr[i][j]) + ow[e]) + (L(h, state(q)) - L(h, state(q'))).
+ *   separator edge out of a word-end node, (h', a) = step(h, w): c = ((v + tr[i][j]) + ow[e]) + (a - L(h, state(q'))); the
+ *           target is the root, whose L is 0.
+ *   end:    at the root (v + final_w[q]) + ew[h]; in a word-end node (v + final_w[q]) + ((a - L(h, state(q))) + ew[h']); mid-word
+ *           none.
+ * L(h, state(q')) of a kept pair is finite by construction (it entered its node through a finite L, start pairs included), so no
+ * -inf - -inf is formed.  Every other rule is asg_beam_decode_words', verbatim.
+ * Consequences: with beam_size >= all pairs and an infinite threshold the kept paths are those of asg_beam_decode_words, and
+ * `scores` differs from that call's only by the rounding of the cancelling terms (bit-equal when no sum rounds).  With a beam
+ * that prunes, the two searches keep different sets: that is the point.
+ * Cost: per expanded edge and backoff level of la_state[h] two binary searches in a row of krank and two reads; L of the source
+ * pair once per pair and candidate phase; at state 0 one read.  No workspace of its own, no atomics, nothing to clear;
+ * (A' * levels + S) * e bytes of table.
+ * Limits and errors: those of asg_beam_decode_words; a NULL look-ahead, one of another dtype, a NULL or mis-sized array (A' < 0,
+ * A' > A, levels outside 1 .. 31 or beyond what A' arcs can fill) or one built for another lexicon / LM shape (S, H):
+ * ASG_ERR_INVALID.  Nothing of it is validated on the device.
+ * Not there: look-ahead in asg_beam_word_stream_*, asg_beam_word_window_* and the n-best calls -- the prefix result (final = 0)
+ * and the three-way score split need rules of their own for the term that has not cancelled yet. */
+typedef struct asg_word_lookahead {
+    int64_t S;                     /* automaton states of the lexicon (entries of rlo, rhi) = asg_word_lm.S */
+    int64_t H;                     /* history states (entries of la_state) = asg_word_lm.H                  */
+    int64_t A;                     /* ranked arcs A'                                                        */
+    int32_t levels;                /* levels of tab                                                         */
+    int32_t dtype;                 /* ASG_DTYPE_F32 / ASG_DTYPE_F64 of tab (= the problem's)               */
+    const int32_t *rlo;            /* [S]                                                                   */
+    const int32_t *rhi;            /* [S]                                                                   */
+    const int32_t *la_state;       /* [H]                                                                   */
+    const int32_t *krow;           /* [H+1]                                                                 */
+    const int32_t *krank;          /* [A']                                                                  */
+    const void *tab;               /* [levels][A']                                                          */
+    const void *dense0;            /* [S] E(0, n) of every node n                                           */
+} asg_word_lookahead;
+int asg_beam_decode_words_la(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                             const asg_word_lookahead *la, int beam_size, double beam_threshold, void *work, size_t work_bytes,
+                             void *scores, int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states,
+                             int64_t *lm_states, int64_t *words, int64_t *word_lengths, int flags, void *stream);
+
 /* ---- STREAMING beam decoding with a lexicon and a word n-gram LM: the search of asg_beam_decode_words over pairs (h, q) carried
  * across chunks of frames, as asg_beam_stream_* carries the search of asg_beam_decode_graph -- the growing stream, bounded by
  * max_frames.  A live transcription service gets a word LM and a transcript while the utterance is still arriving.  No counterpart

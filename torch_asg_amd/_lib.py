@@ -29,7 +29,7 @@ SYMBOLS = ["asg_hip_version", "asg_hip_strerror", "asg_ctx_create", "asg_ctx_des
            "asg_beam_graph_full_backward", "asg_beam_decode_graph_nbest_work_bytes", "asg_beam_decode_graph_nbest",
            "asg_beam_stream_state_bytes", "asg_beam_stream_reset", "asg_beam_stream_advance", "asg_beam_stream_result",
            "asg_beam_window_state_bytes", "asg_beam_window_reset", "asg_beam_window_advance", "asg_beam_window_result",
-           "asg_beam_decode_words_work_bytes", "asg_beam_decode_words",
+           "asg_beam_decode_words_work_bytes", "asg_beam_decode_words", "asg_beam_decode_words_la",
            "asg_beam_word_stream_state_bytes", "asg_beam_word_stream_reset", "asg_beam_word_stream_advance",
            "asg_beam_word_stream_result", "asg_beam_decode_words_nbest_work_bytes", "asg_beam_decode_words_nbest",
            "asg_beam_word_stream_nbest_work_bytes", "asg_beam_word_stream_nbest",
@@ -74,6 +74,11 @@ class AsgWordLM(ctypes.Structure):
     _fields_ = [("H", ctypes.c_int64), ("A", ctypes.c_int64), ("V", ctypes.c_int64), ("S", ctypes.c_int64),
                 ("start", ctypes.c_int32), ("separator", ctypes.c_int32), ("dtype", ctypes.c_int32), ("reserved", ctypes.c_int32)] + [
                     (n, ctypes.c_void_p) for n in ("row", "word", "next", "backoff", "lw", "bw", "ew", "word_of_state")]
+
+
+class AsgWordLookahead(ctypes.Structure):
+    _fields_ = [("S", ctypes.c_int64), ("H", ctypes.c_int64), ("A", ctypes.c_int64), ("levels", ctypes.c_int32),
+                ("dtype", ctypes.c_int32)] + [(n, ctypes.c_void_p) for n in ("rlo", "rhi", "la_state", "krow", "krank", "tab", "dense0")]
 
 
 _LIB = None
@@ -152,6 +157,8 @@ def lib():
     L.asg_beam_decode_words_work_bytes.restype = sz
     L.asg_beam_decode_words_work_bytes.argtypes = [pp, bp, wp, ci]
     L.asg_beam_decode_words.argtypes = [vp, pp, bp, wp, ci, ctypes.c_double, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp]
+    L.asg_beam_decode_words_la.argtypes = [vp, pp, bp, wp, ctypes.POINTER(AsgWordLookahead), ci, ctypes.c_double, vp, sz, vp, vp, vp,
+                                           vp, vp, vp, vp, vp, ci, vp]
     L.asg_beam_word_stream_state_bytes.restype = sz
     L.asg_beam_word_stream_state_bytes.argtypes = [bp, wp, i64, ci, ci, i64]
     L.asg_beam_word_stream_reset.argtypes = [vp, bp, wp, i64, ci, i64, vp, sz, vp, ci, vp]

@@ -419,11 +419,14 @@ class HipBackend:
         return scores, out[0], out[1], token_lengths, out[2]
 
     def beam_decode_words(self, inputs, transition, lexicon, word_lm, input_lengths, beam_size, beam_threshold=float("inf"),
-                          lm_weight=1.0, word_score=0.0, token_score=0.0, max_work_bytes=1 << 30):
+                          lm_weight=1.0, word_score=0.0, token_score=0.0, max_work_bytes=1 << 30, lookahead=None):
         """Beam search over (LM history, lexicon product state) pairs -> BeamWords; see
-        include/asg_hip.h::asg_beam_decode_words.  Grouped under `max_work_bytes` as `_decode_graph` does."""
+        include/asg_hip.h::asg_beam_decode_words and, with a `WordLookahead`, asg_beam_decode_words_la.  Grouped under
+        `max_work_bytes` as `_decode_graph` does."""
         from . import wordlm as _wordlm
         _wordlm.check_words(lexicon, word_lm)
+        if lookahead is not None:
+            _wordlm.check_lookahead(lookahead, lexicon, word_lm)
         beam_size, beam_threshold = min(int(beam_size), (1 << 31) - 1), float(beam_threshold)
         L = _lib.lib()
         self._check_graph_inputs(inputs, transition, lexicon.graph, input_lengths)
@@ -432,14 +435,22 @@ class HipBackend:
         with self._guard(dev):
             g, w, (lex, _) = _wordlm.abi_words(lexicon, word_lm, dev, inputs.dtype, lm_weight, word_score, token_score)
             p, _, input_lengths, _ = self._device_problem(inputs, transition, None, input_lengths, None)
+            what = "asg_beam_decode_words"
+            if lookahead is not None:
+                what = "asg_beam_decode_words_la"
+                la_dev = lookahead.compile(dev, inputs.dtype, lm_weight, word_score)
+                la = _wordlm.abi_lookahead(la_dev)
 
             def call(work, nbytes, *outs):
+                if lookahead is not None:
+                    return L.asg_beam_decode_words_la(None, ctypes.byref(p), ctypes.byref(g), ctypes.byref(w), ctypes.byref(la),
+                                                      beam_size, beam_threshold, work, nbytes, *outs)
                 return L.asg_beam_decode_words(None, ctypes.byref(p), ctypes.byref(g), ctypes.byref(w), beam_size, beam_threshold,
                                                work, nbytes, *outs)
             groups = self._groups(
                 p, B, max_work_bytes,
                 lambda: L.asg_beam_decode_words_work_bytes(ctypes.byref(p), ctypes.byref(g), ctypes.byref(w), beam_size), lex["Q"],
-                lambda: _lib.check(call(None, 0, *(None,) * 8, 0, None), "asg_beam_decode_words"),
+                lambda: _lib.check(call(None, 0, *(None,) * 8, 0, None), what),
                 inputs, input_lengths=input_lengths)
             scores = torch.empty(B, dtype=inputs.dtype, device=dev)
             out = torch.empty(5, B, T, dtype=torch.int64, device=dev)      # path, tokens, states, lm_states, words
@@ -448,7 +459,7 @@ class HipBackend:
             for b0, b1, work in groups:
                 _lib.check(call(work.data_ptr(), work.numel(), scores[b0:].data_ptr(), out[0, b0].data_ptr(),
                                 out[1, b0].data_ptr(), lengths[0, b0:].data_ptr(), out[2, b0].data_ptr(), out[3, b0].data_ptr(),
-                                out[4, b0].data_ptr(), lengths[1, b0:].data_ptr(), 0, stream), "asg_beam_decode_words")
+                                out[4, b0].data_ptr(), lengths[1, b0:].data_ptr(), 0, stream), what)
         return BeamWords(scores, out[0], out[1], lengths[0], out[2], out[3], out[4], lengths[1])
 
     def beam_decode_words_nbest(self, inputs, transition, lexicon, word_lm, input_lengths, beam_size, nbest,
@@ -1091,7 +1102,7 @@ BeamWords = collections.namedtuple("BeamWords", ["scores", "path", "tokens", "to
 
 
 def beam_decode_words(inputs, transition, lexicon, word_lm, input_lengths=None, beam_size=256, beam_threshold=float("inf"),
-                      lm_weight=1.0, word_score=0.0, token_score=0.0, max_work_bytes=1 << 30):
+                      lm_weight=1.0, word_score=0.0, token_score=0.0, max_work_bytes=1 << 30, lookahead=None):
     """Beam decoding over the ASG lattice composed with a `Lexicon` and a word n-gram LM (`WordLM`), the LM composed on the fly:
     the decoder for letter models with a word-level language model.  No gradient.
 
@@ -1117,11 +1128,19 @@ def beam_decode_words(inputs, transition, lexicon, word_lm, input_lengths=None, 
     the device and do not synchronise, so they can be captured.  The batch is decoded in consecutive groups of utterances whose
     workspace (about T * beam_size * 12 bytes of back-pointers plus 60-80 bytes per candidate a frame can have, beam_size *
     (largest out-degree + 1)) fits `max_work_bytes`.
+
+    `lookahead`, a `WordLookahead(lexicon, word_lm, order)`, adds LM look-ahead: inside a word a pair's value also carries the
+    best LM score any word below its trie node can get after the history (the history truncated to `order`), so that a narrow
+    beam ranks partial words by more than acoustics; a node below which the LM accepts no word is pruned when it is entered.
+    The term is taken back when the word ends, so a complete hypothesis sums the same terms as without it: with a beam that
+    prunes nothing the result is the same path, and the score differs only by the rounding of terms that cancel
+    (include/asg_hip.h::asg_beam_decode_words_la).  None is the search without it, byte for byte.  The word streams and
+    `beam_decode_words_nbest` take no look-ahead.
     """
     _check_beam(beam_size, beam_threshold)
     with torch.no_grad():
         return native().beam_decode_words(*_plain(inputs, transition), lexicon, word_lm, input_lengths, beam_size, beam_threshold,
-                                          lm_weight, word_score, token_score, max_work_bytes)
+                                          lm_weight, word_score, token_score, max_work_bytes, lookahead)
 
 
 BeamWordsNbest = collections.namedtuple("BeamWordsNbest", ["scores", "emission_scores", "graph_scores", "lm_scores", "tokens",
@@ -1557,11 +1576,11 @@ class ASGLoss(nn.Module):
                                  max_work_bytes)
 
     def beam_decode_words(self, inputs, lexicon, word_lm, input_lengths=None, beam_size=256, beam_threshold=float("inf"),
-                          lm_weight=1.0, word_score=0.0, token_score=0.0, max_work_bytes=1 << 30):
+                          lm_weight=1.0, word_score=0.0, token_score=0.0, max_work_bytes=1 << 30, lookahead=None):
         """Beam decoding with a lexicon and a word n-gram LM under this criterion's transitions; see
         `torch_asg_amd.beam_decode_words`."""
         return beam_decode_words(inputs, self.transition, lexicon, word_lm, input_lengths, beam_size, beam_threshold, lm_weight,
-                                 word_score, token_score, max_work_bytes)
+                                 word_score, token_score, max_work_bytes, lookahead)
 
     def beam_decode_words_nbest(self, inputs, lexicon, word_lm, input_lengths=None, beam_size=256, nbest=10,
                                 beam_threshold=float("inf"), lm_weight=1.0, word_score=0.0, token_score=0.0,

@@ -659,6 +659,44 @@ int asg_beam_decode_words(asg_ctx *ctx, const asg_problem *p, const asg_token_gr
                                                              st, ls, wd, wl, (hipStream_t) stream)));
 }
 
+// The look-ahead of a (lexicon, LM) pair: its arrays, sized for that pair's S and H.
+static int check_word_lookahead(const asg_problem *p, const asg_word_lm *lm, const asg_word_lookahead *la) {
+    if (!la || la->dtype != p->dtype || la->S != lm->S || la->H != lm->H) return ASG_ERR_INVALID;
+    if (la->A < 0 || la->A > lm->A || la->levels < 1 || la->levels > 31) return ASG_ERR_INVALID;
+    if (la->A > 0 && ((int64_t) 1 << (la->levels - 1)) > la->A) return ASG_ERR_INVALID;      // a level no row can fill
+    if (!la->rlo || !la->rhi || !la->la_state || !la->krow || !la->dense0) return ASG_ERR_INVALID;
+    if (la->A > 0 && (!la->krank || !la->tab)) return ASG_ERR_INVALID;
+    return ASG_OK;
+}
+
+int asg_beam_decode_words_la(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                             const asg_word_lookahead *la, int beam_size, double beam_threshold, void *work, size_t work_bytes,
+                             void *scores, int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states,
+                             int64_t *lm_states, int64_t *words, int64_t *word_lengths, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    int rc = check_beam_words(p, gb, lm, beam_size);
+    if (rc) return rc;
+    if ((rc = check_word_lookahead(p, lm, la)) != ASG_OK) return rc;
+    if (!(beam_threshold >= 0.0)) return ASG_ERR_INVALID;                  // negative or NaN
+    if (!work || !scores || !path || !tokens || !token_lengths || !states || !lm_states || !words || !word_lengths)
+        return ASG_ERR_INVALID;
+    if (work_bytes < asg_beam_decode_words_work_bytes(p, gb, lm, beam_size)) return ASG_ERR_WORKSPACE;
+    const Problem P = to_problem(p);
+    const GraphArgs G = to_graph_args(gb->graph);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    const WordLmArgs LM = to_word_lm_args(lm);
+    WordLookArgs LA{};
+    LA.A = (int) la->A; LA.levels = la->levels;
+    LA.rlo = la->rlo; LA.rhi = la->rhi; LA.la_state = la->la_state; LA.krow = la->krow; LA.krank = la->krank; LA.tab = la->tab;
+    LA.dense0 = la->dense0;
+    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
+    long long *ls = (long long *) lm_states, *wd = (long long *) words, *wl = (long long *) word_lengths;
+    return hip_status(ASG_DISPATCH(p, launch_beam_words_la<float>(P, G, BG, LM, LA, beam_size, beam_threshold, work, scores, pa, tk,
+                                                                  tl, st, ls, wd, wl, (hipStream_t) stream),
+                                   launch_beam_words_la<double>(P, G, BG, LM, LA, beam_size, beam_threshold, work, scores, pa, tk,
+                                                                tl, st, ls, wd, wl, (hipStream_t) stream)));
+}
+
 static int check_beam_words_nbest(const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm, int beam_size,
                                   int nbest) {
     int rc = check_beam_words(p, gb, lm, beam_size);

@@ -29,7 +29,21 @@ static_assert(kWordCtlOff + sizeof(WordCtl) <= kFixedLds, "control block");
 
 __device__ __forceinline__ int bits_of(int n) { return 32 - __clz(n > 1 ? n - 1 : 1); }   // >= 1
 
+// LM look-ahead (asg_beam_word_la.hip, include/asg_hip.h::asg_beam_decode_words_la) is a compile-time flag of the frame and the
+// end, off by default: every other translation unit compiles the text it compiled before the flag existed.
+template <typename R, bool LA>
+struct WordLook {};
 template <typename R>
+struct WordLook<R, true> {
+    const int *rlo, *rhi;        // [S] the ranks of the words below a trie node: [rlo, rhi)
+    const int *la_state;         // [H] the history the look-ahead of h is taken from
+    const int *krow, *krank;     // [H+1], [A'] the ranked arcs of each LM state, rank ascending
+    const R *tab;                // [levels][A'] tab[k][i] = max of lw over the 2^k ranked arcs from i (inside the row of i)
+    const R *dense0;             // [S] E(0, n): what the search in row 0, the longest, would find
+    int A;                       // A'
+};
+
+template <typename R, bool LA = false>
 struct BeamWordFrame {
     using U = typename Key<R>::U;
     Ctl<U> *ctl;
@@ -124,14 +138,55 @@ struct BeamWordFrame {
         }
         return false;
     }
+    // L(h, n): the look-ahead of trie node n after history h -- 0 at the root; else, from s = la_state[h] down the backoff
+    // chain, the largest (backoff sum so far) + E(s, n), E the range maximum of row s over the ranks of n: two binary searches
+    // in krank and two reads of the table per level, one read of dense0 at state 0.  -inf: the LM accepts no word below n.
+    __device__ R look(int h, int n) const {
+        if (n == 0) return (R) 0;
+        const int r0 = la.rlo[n], r1 = la.rhi[n];
+        int s = la.la_state[h];
+        R r = Num<R>::ninf(), a = (R) 0;
+        for (int it = 0; it <= kMaxBackoff; ++it) {
+            R e = Num<R>::ninf();
+            if (s == 0) e = la.dense0[n];
+            else {
+                const int end = la.krow[s + 1];
+                int lo = la.krow[s], hi = end;
+                while (lo < hi) {
+                    const int mid = (int) (((unsigned) lo + (unsigned) hi) >> 1);
+                    if (la.krank[mid] < r0) lo = mid + 1; else hi = mid;
+                }
+                const int first = lo;
+                hi = end;
+                while (lo < hi) {
+                    const int mid = (int) (((unsigned) lo + (unsigned) hi) >> 1);
+                    if (la.krank[mid] < r1) lo = mid + 1; else hi = mid;
+                }
+                if (first < lo) {
+                    const int k = 31 - __clz(lo - first);
+                    const R *row = la.tab + (int64_t) k * la.A;
+                    const R x = row[first], y = row[lo - (1 << k)];
+                    e = x > y ? x : y;
+                }
+            }
+            const R c = a + e;
+            r = c > r ? c : r;
+            const int bo = lback[s];
+            if (bo < 0) break;
+            a = a + bw[s];
+            s = bo;
+        }
+        return r;
+    }
+    WordLook<R, LA> la;
 };
 
 // One frame: from the kept set (f.cur_h, f.cur_q, f.cur_v)[0..na) of the frame before -- or, with `first`, from the start states
 // -- to the new one, with (q, h, source slot) of every kept pair into row `row` of the [.][K] lists bq / bh / bs.  `xt` are the
 // frame's emissions (stride is2).  The whole workgroup calls it; it begins after and ends with a __syncthreads.  The table is
 // empty again on return (a first frame does not use it), f.ctl->na holds the new count and f.ctl->n is 0.
-template <typename R, bool TRL>
-__device__ __forceinline__ void beam_word_frame(const BeamWordFrame<R> &f, bool first, int na, const R *xt, int64_t is2, int *bq,
+template <typename R, bool TRL, bool LA = false>
+__device__ __forceinline__ void beam_word_frame(const BeamWordFrame<R, LA> &f, bool first, int na, const R *xt, int64_t is2, int *bq,
                                                 int *bh, int *bs, int row) {
     using KT = Key<R>;
     using U = typename KT::U;
@@ -166,9 +221,11 @@ __device__ __forceinline__ void beam_word_frame(const BeamWordFrame<R> &f, bool 
                 const bool act = k < na;
                 int qs = 0, hs = 0, j = 0, e = 0, e1 = 0;
                 R v = NINF;
+                [[maybe_unused]] R ls = (R) 0;                        // L(hs, state(qs)): one value for all edges of the pair
                 if (act) {
                     qs = cur_q[k]; hs = cur_h[k]; v = cur_v[k]; j = f.label[qs];
                     e = f.orow[qs] + lg; e1 = f.orow[qs + 1];
+                    if constexpr (LA) ls = f.look(hs, f.state[qs]);
                 }
                 const unsigned long long me = (f.pair(hs, qs) << kWordSlotBits) | (unsigned) k;
                 // the stay, then the row; the whole wavefront stays in the loop until its last lane is done (wave_append)
@@ -184,8 +241,13 @@ __device__ __forceinline__ void beam_word_frame(const BeamWordFrame<R> &f, bool 
                         if (a.y == f.sep) {                           // a word ends: the LM moves
                             R add;
                             int h2;
-                            if (f.step(hs, f.wos[f.state[qs]], h2, add)) { th = h2; c = c + add; }
-                            else tq = -1;
+                            if (f.step(hs, f.wos[f.state[qs]], h2, add)) {
+                                th = h2;
+                                if constexpr (LA) c = c + (add - ls); else c = c + add;
+                            } else tq = -1;
+                        } else if constexpr (LA) {                    // into a node: its look-ahead for the source's
+                            const R lt = f.look(hs, f.state[tq]);
+                            if (lt > NINF) c = c + (lt - ls); else tq = -1;       // a dead end is pruned here
                         }
                         e += G;
                     }
@@ -220,7 +282,12 @@ __device__ __forceinline__ void beam_word_frame(const BeamWordFrame<R> &f, bool 
         for (int j = tid; j < n; j += kBT) {
             unsigned long long p;
             R base;
-            if (first) { const int q = f.start_q[j]; p = f.pair(f.lstart, q); base = sw[q]; }
+            if (first) {
+                const int q = f.start_q[j];
+                p = f.pair(f.lstart, q);
+                base = sw[q];
+                if constexpr (LA) base = base + f.look(f.lstart, f.state[q]);
+            }
             else { const int s = tl[j]; p = dev_load(tkey + s) - 1ull; base = KT::dec(dev_load(val + s)); }
             const R c = base + xt[(int64_t) f.label[(int) (p & qmask)] * is2];
             const U key = c > NINF ? KT::enc(c) : (U) 0;
@@ -371,8 +438,8 @@ __device__ __forceinline__ void beam_word_frame(const BeamWordFrame<R> &f, bool 
 
 // The end of a kept pair (h, q) with value v: (v + final_w[q]) + endw, endw = ew[h] at the root, a + ew[h'] after the LM walk of
 // the word that ends in q's node; false: no end (mid-word, or the walk rejects).  `w`: that word, or -1.
-template <typename R>
-__device__ __forceinline__ bool word_end(const BeamWordFrame<R> &f, const R *fw, int h, int q, R v, R &e, int &w) {
+template <typename R, bool LA = false>
+__device__ __forceinline__ bool word_end(const BeamWordFrame<R, LA> &f, const R *fw, int h, int q, R v, R &e, int &w) {
     const int s = f.state[q];
     R endw;
     w = -1;
@@ -382,7 +449,7 @@ __device__ __forceinline__ bool word_end(const BeamWordFrame<R> &f, const R *fw,
         int h2;
         R a;
         if (!f.step(h, ww, h2, a)) return false;
-        endw = a + f.ew[h2];
+        if constexpr (LA) endw = (a - f.look(h, s)) + f.ew[h2]; else endw = a + f.ew[h2];
         w = ww;
     }
     e = (v + fw[q]) + endw;
@@ -399,8 +466,8 @@ __device__ __forceinline__ void word_no_path(int T, long long *pb, long long *tk
 // The best end over a set (sh, sq, sv)[0..na), the smallest pair on a tie (-0 and +0 are one key): with `final` the end of
 // word_end, without it the value itself -- the best PREFIX, which may end mid-word.  Every thread of the workgroup gets (key,
 // slot); key 0: no finite end.  One __syncthreads; f.wctl holds the reduction slots.
-template <typename R>
-__device__ __forceinline__ void word_best_end(const BeamWordFrame<R> &f, const R *fw, bool final, const int *sh, const int *sq,
+template <typename R, bool LA = false>
+__device__ __forceinline__ void word_best_end(const BeamWordFrame<R, LA> &f, const R *fw, bool final, const int *sh, const int *sq,
                                               const R *sv, int na, typename Key<R>::U &bkey, int &bk) {
     using KT = Key<R>;
     using U = typename KT::U;
@@ -414,7 +481,7 @@ __device__ __forceinline__ void word_best_end(const BeamWordFrame<R> &f, const R
         R e;
         int w;
         if (!final) e = sv[k];
-        else if (!word_end<R>(f, fw, sh[k], sq[k], sv[k], e, w)) continue;
+        else if (!word_end<R, LA>(f, fw, sh[k], sq[k], sv[k], e, w)) continue;
         const U key = e > NINF ? KT::enc(e) : (U) 0;
         const unsigned long long p = f.pair(sh[k], sq[k]);
         if (key && (key > bkey || (key == bkey && p < bpair))) { bkey = key; bpair = p; bk = k; }
@@ -438,8 +505,8 @@ __device__ __forceinline__ void word_best_end(const BeamWordFrame<R> &f, const R
 // The path that ends in slot bk of frame len-1, through the [.][K] lists bq / bh / bs, into pb / st / ls [T] (-1 behind len);
 // the score from the winner's own sum (the key folds -0 into +0); the words of its separator edges and, with `final`, the word
 // of the last step; the tokens; -1 behind everything.  The whole workgroup calls it, after word_best_end.
-template <typename R>
-__device__ __forceinline__ void word_backtrace(const BeamWordFrame<R> &f, const R *fw, bool final, const int *sh, const int *sq,
+template <typename R, bool LA = false>
+__device__ __forceinline__ void word_backtrace(const BeamWordFrame<R, LA> &f, const R *fw, bool final, const int *sh, const int *sq,
                                                const R *sv, int bk, const int *bq, const int *bh, const int *bs, int len, int T,
                                                R *score, long long *pb, long long *tk, long long *st, long long *ls,
                                                long long *wd, long long *tlen, long long *wlen) {
@@ -451,7 +518,7 @@ __device__ __forceinline__ void word_backtrace(const BeamWordFrame<R> &f, const 
     if (tid == 0) {
         R e = sv[bk];
         int wfin = -1;
-        if (final) (void) word_end<R>(f, fw, sh[bk], sq[bk], sv[bk], e, wfin);
+        if (final) (void) word_end<R, LA>(f, fw, sh[bk], sq[bk], sv[bk], e, wfin);
         *score = e;
         int k = bk;
         for (int t = len - 1; t >= 0; --t) {

@@ -235,6 +235,22 @@ hipError_t launch_beam_stream_result(const GraphArgs &G, const BeamGraphArgs &BG
                                      int final, void *scores, long long *path, long long *tokens, long long *tlen,
                                      long long *states, long long *frames, long long *status, hipStream_t stream);
 
+// ---- The same search with LM look-ahead (asg_beam_word_la.hip): asg_beam_decode_words_la.  K, cap, the table and the workspace
+// are those of launch_beam_words; the look-ahead adds read-only arrays and nothing per utterance.
+struct WordLookArgs {
+    int A, levels;                            // ranked arcs A', levels of the range-maximum table
+    const int *rlo, *rhi;                     // [S] rank range of the words below each trie node
+    const int *la_state;                      // [H] the (truncated) history whose rows the look-ahead of h reads
+    const int *krow, *krank;                  // [H+1], [A'] ranked arcs of each LM state, rank ascending
+    const void *tab;                          // [levels][A'] in the dtype of the problem
+    const void *dense0;                       // [S] E(0, n): the range maximum of state 0 for every node
+};
+template <typename R>
+hipError_t launch_beam_words_la(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                                const WordLookArgs &LA, int K, double theta, void *work, void *scores, long long *path,
+                                long long *tokens, long long *tlen, long long *states, long long *lm_states, long long *words,
+                                long long *wlen, hipStream_t stream);
+
 // ---- The search over pairs carried across chunks of frames (asg_beam_word_stream.hip): asg_beam_word_stream_*.  One slot of the
 // state: the word decoder's own layout for T = max_frames at the front, then hdr (int32 pos, |A|, overflow) and the stored set
 // (values [K], then int32 product states [K], then int32 LM states [K]).  K = beam_size, cap = beam_word_cap(..).

@@ -271,6 +271,165 @@ class WordLM:
         return dev
 
 
+class WordLookahead:
+    """LM look-ahead for `beam_decode_words(..., lookahead=)`: what lets a partial word be ranked by the best LM score any word
+    below its trie node can still get, instead of by acoustics alone (include/asg_hip.h::asg_beam_decode_words_la).
+
+    Ranks: the trie of `lexicon.graph` is walked in pre-order, children by ascending token; the word of a word-end node takes
+    the next rank when the node is entered.  `rlo` / `rhi` [S] int32 are the counter on entry and on exit: the words below node
+    n, its own included, have the ranks [rlo[n], rhi[n]).  `word_rank` [V] is the rank of a word, -1 for an LM word the lexicon
+    does not spell.  Rows: the arcs of every LM state whose word has a rank, sorted by rank: offsets `krow` [H+1], ranks
+    `krank` [A'] and `karc` [A'], the arc of the LM each one is.  `la_state` [H] int32 is h backed off until at most
+    `order - 1` backoff steps remain to a state without a backoff (`depth`): order 1 is unigram smearing, an order at or above
+    the LM's the full look-ahead.  E(s, n) is the largest folded arc weight of row s over the ranks of node n, -inf without
+    one; `compile_host` builds the sparse table that answers it with two binary searches and two reads, `range_max` is that
+    query on the host.
+
+    order < 1 raises ValueError; so does a ranked word that has an arc in some row but none in a state without a backoff (an
+    ARPA-built LM has state 0 as the only such state and every unigram in it): with that rule a look-ahead of -inf says that no
+    word below the node is accepted, whatever the truncation."""
+
+    def __init__(self, lexicon, word_lm, order=2):
+        check_words(lexicon, word_lm)
+        order = int(order)
+        if order < 1:
+            raise ValueError("WordLookahead: order must be >= 1")
+        self.order = order
+        self.S, self.H, self.V = lexicon.graph.S, word_lm.H, word_lm.V
+        self._lm, self._lexicon = word_lm, lexicon
+        nxt = np.asarray(lexicon.graph.next, np.int64)
+        wos = lexicon.word_of_state
+        sep = lexicon.separator
+        S = self.S
+        rlo, rhi = np.zeros(S, np.int32), np.zeros(S, np.int32)
+        word_rank = np.full(self.V, -1, np.int64)
+        count = 0
+        stack = [(0, False)]
+        while stack:
+            n, leaving = stack.pop()
+            if leaving:
+                rhi[n] = count
+                continue
+            rlo[n] = count
+            if wos[n] >= 0:
+                word_rank[wos[n]] = count
+                count += 1
+            stack.append((n, True))
+            kids = [int(nxt[n, x]) for x in np.flatnonzero(nxt[n] >= 0) if x != sep]
+            stack.extend((c, False) for c in reversed(kids))
+        self.rlo, self.rhi, self.word_rank, self.num_ranks = rlo, rhi, word_rank, count
+        lm = word_lm
+        rid = np.repeat(np.arange(lm.H), np.diff(lm.row))
+        rank = word_rank[lm.word]
+        arcs = np.flatnonzero(rank >= 0)
+        arcs = arcs[np.argsort(rid[arcs] * (count + 1) + rank[arcs], kind="stable")]
+        self.karc = arcs
+        self.krank = rank[arcs].astype(np.int32)
+        self.krow = np.concatenate([[0], np.cumsum(np.bincount(rid[arcs], minlength=lm.H))]).astype(np.int32)
+        self.A = int(arcs.size)
+        # every ranked word with an arc anywhere must have one in every state without a backoff
+        seen = np.zeros(count + 1, bool)
+        seen[self.krank] = True
+        for s in np.flatnonzero(lm.backoff < 0):
+            here = np.zeros(count + 1, bool)
+            here[self.krank[self.krow[s]:self.krow[s + 1]]] = True
+            if (seen & ~here).any():
+                w = int(np.flatnonzero(word_rank == np.flatnonzero(seen & ~here)[0])[0])
+                raise ValueError("WordLookahead: word %d has an arc in the LM but none in state %d, which has no backoff" % (w, s))
+        depth = np.where(lm.backoff < 0, 0, -1)
+        while (depth < 0).any():                     # (WordLM has checked that the chains end)
+            todo = depth < 0
+            d = depth[lm.backoff[todo]]
+            depth[todo] = np.where(d >= 0, d + 1, -1)
+        self.depth = depth
+        la_state = np.arange(lm.H)
+        while (depth[la_state] > order - 1).any():
+            la_state = np.where(depth[la_state] > order - 1, lm.backoff[la_state], la_state)
+        self.la_state = la_state.astype(np.int32)
+        longest = int(np.diff(self.krow).max(initial=0))
+        self.levels = max(1, longest.bit_length())   # tab[k] for 2^k <= the longest row
+        self._compiled = {}
+
+    def compile_host(self, dt, lm_weight=1.0, word_score=0.0):
+        """tab [levels][A'] in dtype dt: tab[k][i] = the largest of `WordLM.compile_host`'s lw over the arcs i .. i + 2^k - 1 of
+        the rank-ordered rows that lie in the row of i.  (-0 is stored as +0, so that a maximum is one bit pattern.)"""
+        dt = np.dtype(dt).type
+        lw = self._lm.compile_host(dt, lm_weight, word_score)["lw"]
+        tab = np.full((self.levels, self.A), -np.inf, dt)
+        tab[0] = lw[self.karc] + dt(0)
+        end = np.repeat(self.krow[1:], np.diff(self.krow)).astype(np.int64)       # the end of each arc's row
+        idx = np.arange(self.A)
+        for k in range(1, self.levels):
+            far = idx + (1 << (k - 1))
+            ok = far < end
+            tab[k] = tab[k - 1]
+            tab[k, ok] = np.maximum(tab[k - 1, ok], tab[k - 1, far[ok]])
+        return tab
+
+    def dense_host(self, tab):
+        """dense0 [S]: E(0, n) of every trie node from a `compile_host` table -- the empty history is where every backoff
+        chain of an ARPA LM ends and has the longest row, so the device reads its answer instead of searching for it."""
+        b0, b1 = int(self.krow[0]), int(self.krow[1])
+        lo = b0 + np.searchsorted(self.krank[b0:b1], self.rlo)
+        hi = b0 + np.searchsorted(self.krank[b0:b1], self.rhi)
+        out = np.full(self.S, -np.inf, tab.dtype)
+        ok = np.flatnonzero(lo < hi)
+        k = np.floor(np.log2(hi[ok] - lo[ok])).astype(np.int64)
+        out[ok] = np.maximum(tab[k, lo[ok]], tab[k, hi[ok] - (1 << k)])
+        return out
+
+    def range_max(self, tab, s, n):
+        """E(s, n) from a `compile_host` table: two binary searches in row s of krank, two reads."""
+        b0, b1 = int(self.krow[s]), int(self.krow[s + 1])
+        lo = b0 + int(np.searchsorted(self.krank[b0:b1], self.rlo[n]))
+        hi = b0 + int(np.searchsorted(self.krank[b0:b1], self.rhi[n]))
+        if lo >= hi:
+            return tab.dtype.type(-np.inf)
+        k = (hi - lo).bit_length() - 1
+        return max(tab[k, lo], tab[k, hi - (1 << k)])
+
+    def compile(self, device, dtype, lm_weight=1.0, word_score=0.0):
+        """The arrays on `device` for decoding in `dtype`, cached per (device, dtype, lm_weight, word_score) as `WordLM.compile`
+        is: a dict of device tensors (rlo, rhi, la_state, krow, krank int32; tab, dense0) plus S, H, A, levels."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if dtype not in (torch.float32, torch.float64):
+            raise RuntimeError("torch_asg_amd: expected scalar type Float or Double but found %s" % dtype)
+        key = (device, dtype, float(lm_weight), float(word_score))
+        hit = self._compiled.get(key)
+        if hit is not None:
+            return hit
+        host = {n: getattr(self, n) for n in ("rlo", "rhi", "la_state", "krow", "krank")}
+        host["tab"] = self.compile_host(np.float32 if dtype == torch.float32 else np.float64, lm_weight, word_score)
+        host["dense0"] = self.dense_host(host["tab"])
+        dev = {n: torch.from_numpy(np.ascontiguousarray(a)).to(device) for n, a in host.items()}
+        dev["S"], dev["H"], dev["A"], dev["levels"], dev["dtype"] = self.S, self.H, self.A, self.levels, dtype
+        self._compiled[key] = dev
+        return dev
+
+
+def check_lookahead(lookahead, lexicon, word_lm):
+    """The argument checks of `lookahead=`: its type, and that it was built for this very lexicon and LM (its tables hold
+    this LM's weights in this trie's ranks: another pair of equal shape would give wrong values without any error)."""
+    if not isinstance(lookahead, WordLookahead):
+        raise TypeError("torch_asg_amd: lookahead must be a torch_asg_amd.WordLookahead or None")
+    if lookahead._lexicon is not lexicon or lookahead._lm is not word_lm:
+        raise RuntimeError("torch_asg_amd: the look-ahead was built for another lexicon or word LM (%d lexicon states and %d LM "
+                           "states; the call has %d and %d)" % (lookahead.S, lookahead.H, lexicon.graph.S, word_lm.H))
+
+
+def abi_lookahead(la):
+    """The asg_word_lookahead view of a `WordLookahead.compile` result (pointers into its tensors)."""
+    s = _lib.AsgWordLookahead()
+    s.S, s.H, s.A, s.levels = la["S"], la["H"], la["A"], la["levels"]
+    s.dtype = _lib.ASG_DTYPE_F32 if la["dtype"] == torch.float32 else _lib.ASG_DTYPE_F64
+    for name in ("rlo", "rhi", "la_state", "krow", "krank", "tab", "dense0"):
+        t = la[name]
+        setattr(s, name, ctypes.c_void_p(t.data_ptr() if t.numel() else None))
+    return s
+
+
 def abi_word_lm(lm, lex):
     """The asg_word_lm view of a `WordLM.compile` result and a `Lexicon.compile_words` result (pointers into their tensors)."""
     s = _lib.AsgWordLM()
