@@ -171,6 +171,13 @@ def two_components_automaton(N=6):
     return nxt, np.zeros((5, N)), np.zeros(5)
 
 
+def chain_automaton(S, N):
+    """One chain walked DOWN from its last state: every token leads from s to s - 1.  The product states are sorted by automaton
+    state, so a search from the start lives in the LAST product states.  -> next, weight, final, start."""
+    nxt = np.repeat(np.arange(-1, S - 1)[:, None], N, 1)
+    return nxt, np.log(np.random.default_rng(S).dirichlet(np.ones(N), size=S)), np.zeros(S), S - 1
+
+
 def two_component_emissions(T, B, N, dtype, seed=5):
     """Label 0 and label N/2 ahead by 1 in every frame, the others at 0 (slot 0) or at 0 / 0.25 (the other slots): with zero
     transitions and a token score below zero the two best hypotheses are "stay on 0" and "stay on N/2", tied, one per half."""

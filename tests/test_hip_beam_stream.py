@@ -10,6 +10,7 @@ import torch
 
 from beam_decode_ref import beam_decode_ref
 from beam_stream_ref import BeamStreamRef
+from beam_window_ref import chain_automaton
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -298,6 +299,40 @@ def test_masked_reset_mid_stream():
     assert res[5].tolist() == [0, T - 6] and res[0][0] == -INF and res[0][1] > -INF
     s.reset()
     assert _res(s)[5].tolist() == [0, 0]
+
+
+def test_masked_reset_of_a_used_slot_beyond_one_pass_of_the_reset():
+    """The reset shares the Q entries of val / arg among 64 workgroups of 256 threads: 16384 per pass.  A chain of Q a little
+    above that, walked down from its last state, keeps the search in the product states of the SECOND pass.  Slot 0 decodes,
+    is reset under a mask and decodes other emissions; every output of every call against the streaming restatement
+    (tests/beam_stream_ref.py), byte for byte.  A frame empties the entries it touched, so what fails when entries >= 16384
+    are not cleared (or are cleared at a wrong offset) is the constructor's reset of the freshly allocated, poisoned state;
+    the masked reset of the used slot is checked for its header and for leaving slot 1 alone."""
+    S, N = 3290, 5
+    graph = _asg().TokenGraph(*chain_automaton(S, N))
+    h = graph.compile_host(np.float32, LW, TS)
+    T, B, K = 6, 2, 4
+    assert 16384 < h["Q"] < 16384 + 128 and np.nonzero(h["state"] >= S - 1 - T)[0].min() >= 16384
+    x, tr, _ = _case(T, B, N, 61)
+    y, _, _ = _case(T, B, N, 62)
+    s, ref = _stream(tr, graph, B, 2 * T, K), _ref_stream(tr, graph, B, 2 * T, K)
+
+    def both(z, what):
+        for t0, t1 in ((0, 2), (2, T)):
+            s.advance(z[t0:t1].to(DEV))
+            ref.advance(z[t0:t1].numpy())
+            for final in (False, True):
+                _same(_res(s, final), ref.result(final), "%s after frame %d final=%s" % (what, t1, final))
+    both(x, "the first utterance")
+    st = ref.result(True)[4]
+    assert (ref.result(True)[0] > -INF).all() and st[st >= 0].min() >= S - 1 - T        # the states the search used
+    mask = torch.tensor([True, False])
+    s.reset(mask.to(DEV))
+    ref.reset(mask.numpy())
+    for final in (False, True):
+        _same(_res(s, final), ref.result(final), "after the masked reset final=%s" % final)
+    both(y, "the second utterance")                                  # slot 0 from its start, slot 1 goes on down the chain
+    assert ref.result(True)[5].tolist() == [T, 2 * T]
 
 
 @DTYPES

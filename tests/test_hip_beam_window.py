@@ -10,7 +10,7 @@ import torch
 
 from beam_decode_ref import beam_decode_ref
 from beam_stream_ref import BeamStreamRef
-from beam_window_ref import BeamWindowRef, two_component_emissions, two_components_automaton
+from beam_window_ref import BeamWindowRef, chain_automaton, two_component_emissions, two_components_automaton
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -282,6 +282,33 @@ def test_masked_reset_mid_stream():
     s.reset(torch.tensor([1, 0], dtype=torch.int32))                 # an integer mask from the host
     out = s.result()
     assert out.frames.tolist() == [0, T - 6] and out.committed.tolist()[0] == 0 and out.status.tolist()[0] == 0
+
+
+def test_masked_reset_of_a_used_slot_beyond_one_pass_of_the_reset():
+    """The reset shares the Q entries of val / arg among 64 workgroups of 256 threads: 16384 per pass.  A chain of Q a little
+    above that, walked down from its last state, keeps the search in the product states of the SECOND pass.  Slot 0 decodes,
+    is reset under a mask and decodes other emissions; every output of every call against the restatement, byte for byte.
+    What this can and cannot see: a frame empties the entries it touched, so val / arg of a used slot are empty before the
+    masked reset as well, and a reset that skipped the second pass would pass the second half.  The constructor's reset of
+    the freshly allocated (poisoned) state is the part that fails when entries >= 16384 are not cleared or the clearing lands
+    at a wrong offset; the masked reset is checked for its header and for leaving slot 1 alone."""
+    S, N = 3290, 5
+    graph = _asg().TokenGraph(*chain_automaton(S, N))
+    h = graph.compile_host(np.float32, LW, TS)
+    T, B, K, W, P = 6, 2, 4, 4, 1
+    assert 16384 < h["Q"] < 16384 + 128 and np.nonzero(h["state"] >= S - 1 - T)[0].min() >= 16384
+    x, tr, _ = _case(T, B, N, 61)
+    y, _, _ = _case(T, B, N, 62)
+    s, ref = _pair(tr, graph, B, W, P, K)
+    _feed(s, ref, x, None, [0, 2, T], "the first utterance")
+    st = ref.result(True)[4]
+    assert (ref.result(True)[0] > -INF).all() and st[st >= 0].min() >= S - 1 - T        # the states the search used
+    mask = torch.tensor([True, False])
+    s.reset(mask.to(DEV))
+    ref.reset(mask.numpy())
+    _results(s, ref, "after the masked reset")
+    _feed(s, ref, y, None, [0, 2, T], "the second utterance")      # slot 0 from its start, slot 1 goes on down the chain
+    assert ref.result(True)[5].tolist() == [T, 2 * T]
 
 
 def test_capture_and_replay():

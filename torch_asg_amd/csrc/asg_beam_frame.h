@@ -4,7 +4,9 @@
 // the set an earlier call left, beam_stream_result_kernel is the end as a call of its own).  Both translation units compile this
 // one text, so the sets, the back-pointers and every tie are the same bit for bit: that is what "decoding in chunks equals
 // decoding in one call" rests on (include/asg_hip.h::asg_beam_stream_advance), as the beam-pruned loss already rests on it.
-// The steps of a frame are described at the top of asg_beam_graph.hip.
+// The steps of a frame are described at the top of asg_beam_graph.hip.  Behind the frame: what the two streams (asg_beam_stream.hip,
+// asg_beam_window.hip) share around it -- the clearing loop of their resets (beam_reset_tables) and the way their advance kernels
+// enter and leave the frame loop (beam_load_set, beam_store_set).
 #pragma once
 #include "asg_common.h"
 #include "asg_kernels.h"
@@ -155,16 +157,11 @@ struct BeamFrame {
     U *ckey;                     // [cap]
     int *tl;                     // [cap] the touched list
 
-    // The utterance's slot arrays inside its workspace `wb` (5i's layout for T frames); -> the [T][K] lists through bq / bs.
+    // The utterance's slot arrays inside its workspace `wb` (beam_work for T frames); -> the [T][K] lists through bq / bs.
     __device__ __forceinline__ void bind_work(char *wb, int T, int cap, int *&bq, int *&bs) {
-        const size_t a256 = 255;
-        size_t off = 0;
-        bq = (int *) (wb + off);  off += ((size_t) T * K * 4 + a256) & ~a256;       // [T][K] product state of each slot
-        bs = (int *) (wb + off);  off += ((size_t) T * K * 4 + a256) & ~a256;       // [T][K] its source's slot at t-1
-        arg = (unsigned long long *) (wb + off);  off += ((size_t) Q * 8 + a256) & ~a256;
-        val = (U *) (wb + off);     off += ((size_t) Q * sizeof(U) + a256) & ~a256;
-        ckey = (U *) (wb + off);    off += ((size_t) cap * sizeof(U) + a256) & ~a256;
-        tl = (int *) (wb + off);
+        const BeamWork<char *> l = beam_work(wb, sizeof(U), T, Q, K, cap);
+        bq = (int *) l.bq;  bs = (int *) l.bs;  arg = (unsigned long long *) l.arg;
+        val = (U *) l.val;  ckey = (U *) l.ckey;  tl = (int *) l.tl;
     }
 };
 
@@ -396,6 +393,40 @@ __device__ __forceinline__ void beam_frame(const BeamFrame<R> &f, bool first, in
     }
     if (tid == 0) ctl.n = 0;
     __syncthreads();
+}
+
+// A stream's reset (asg_beam_stream.hip, asg_beam_window.hip): val = 0 and arg = none for all Q states of the slot at `wb`, shared
+// among the workgroups of 256 threads that blockIdx.y counts; key_bytes is 4 or 8.
+__device__ __forceinline__ void beam_reset_tables(char *wb, const BeamWorkLayout &l, int Q, int key_bytes) {
+    unsigned long long *arg = (unsigned long long *) (wb + l.arg);
+    for (int q = blockIdx.y * 256 + threadIdx.x; q < Q; q += gridDim.y * 256) {
+        dev_store(arg + q, ~0ull);
+        if (key_bytes == 8) dev_store((unsigned long long *) (wb + l.val) + q, 0ull);
+        else dev_store((unsigned int *) (wb + l.val) + q, 0u);
+    }
+}
+
+// A stream's advance (asg_beam_stream.hip, asg_beam_window.hip) enters the frame loop with the set an earlier call left at
+// `set_v` -- values [K], then product states int32 [K]: the transitions into LDS when they live there, the na0 stored states into
+// f.cur_v / f.cur_q, the counters.  The whole workgroup calls it; it ends with a __syncthreads.
+template <typename R, bool TRL>
+__device__ __forceinline__ void beam_load_set(const BeamFrame<R> &f, R *trs, const R *set_v, int na0) {
+    const int tid = threadIdx.x, N = f.N;
+    const int *set_q = (const int *) (set_v + f.K);
+    if constexpr (TRL)
+        for (int x = tid; x < N * N; x += kBT) trs[x] = f.tr[(int64_t) (x / N) * f.ts0 + (int64_t) (x % N) * f.ts1];
+    for (int k = tid; k < na0; k += kBT) { f.cur_v[k] = set_v[k]; f.cur_q[k] = set_q[k]; }
+    if (tid == 0) { f.ctl->na = na0; f.ctl->n = 0; }
+    __syncthreads();
+}
+// ... and leaves it: the set back to `set_v`; -> its size, for the header.
+template <typename R>
+__device__ __forceinline__ int beam_store_set(const BeamFrame<R> &f, R *set_v) {
+    int *set_q = (int *) (set_v + f.K);
+    int na = f.ctl->na;
+    na = na < f.K ? na : f.K;
+    for (int k = threadIdx.x; k < na; k += kBT) { set_v[k] = f.cur_v[k]; set_q[k] = f.cur_q[k]; }
+    return na;
 }
 
 // The best end over a set (sq, sv)[0..na): end = sv + fw[sq], or sv itself when fw is null; the largest, the smallest q on a

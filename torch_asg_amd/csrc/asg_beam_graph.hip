@@ -57,7 +57,7 @@ __global__ void __launch_bounds__(kBT) beam_graph_kernel(Problem P, GraphArgs g,
     const R *tr = (const R *) P.transition;
     const R *fw = (const R *) g.final_w;
     long long *pb = path + (int64_t) b * T, *tk = tokens + (int64_t) b * T, *st = states + (int64_t) b * T;
-    // the utterance's workspace (beam_graph_layout)
+    // the utterance's workspace (asg_beam_common.h, beam_work_layout)
     char *wb = work + (size_t) b * per_utt;
     BeamFrame<R> f;
     f.ctl = &ctl; f.cur_v = cur_v; f.cur_q = cur_q; f.trs = trs; f.tr = tr; f.ts0 = P.ts0; f.ts1 = P.ts1;
@@ -112,13 +112,6 @@ __global__ void __launch_bounds__(kBT) beam_graph_kernel(Problem P, GraphArgs g,
     beam_backtrace(bq, bs, K, len, T, bk, g.label, g.state, pb, tk, st, tlen + b);
 }
 
-inline size_t a256(size_t x) { return (x + 255) / 256 * 256; }
-
-inline size_t beam_per_utt(int elem, int T, int Q, int K, int cap) {
-    return 2 * a256((size_t) T * K * 4) + a256((size_t) Q * 8) + a256((size_t) Q * elem) + a256((size_t) cap * elem) +
-           a256((size_t) cap * 4);
-}
-
 }  // namespace
 
 int beam_graph_k(int Q, int beam_size) { return Q < 1 ? 1 : (beam_size < Q ? beam_size : Q); }
@@ -132,7 +125,7 @@ int beam_graph_cap(int Q, int K, int max_out, int num_start) {
 }
 
 size_t beam_graph_work_bytes(int elem, int T, int B, int Q, int K, int cap) {
-    return (size_t) B * beam_per_utt(elem, T, Q, K, cap);
+    return (size_t) B * beam_work_layout(elem, T, Q, K, cap).end;
 }
 
 template <typename R>
@@ -141,7 +134,7 @@ hipError_t launch_beam_graph(const Problem &P, const GraphArgs &G, const BeamGra
                              hipStream_t stream, size_t stride, size_t cnt_off, size_t fin_off) {
     const int N = P.N;
     const int cap = beam_graph_cap(G.Q, K, BG.max_out, BG.num_start);
-    const size_t per = stride ? stride : beam_per_utt(sizeof(R), P.T, G.Q, K, cap);
+    const size_t per = stride ? stride : beam_work_layout(sizeof(R), P.T, G.Q, K, cap).end;
     const size_t beam = kFixedLds + (size_t) K * (sizeof(R) + 4) + 8;
     const bool trl = beam + (size_t) N * N * sizeof(R) <= kLdsMax;
     const size_t dyn = beam + (trl ? (size_t) N * N * sizeof(R) : 0);

@@ -26,6 +26,7 @@
 // written by these kernels: no memset, so both directions can be captured and replayed.
 #include "asg_common.h"
 #include "asg_kernels.h"
+#include "asg_beam_common.h"     // a256, beam_work_layout: the beam search's own part lies at the front of the workspace
 
 namespace asg {
 
@@ -463,8 +464,6 @@ __global__ void __launch_bounds__(kBS) beam_loss_tr_reduce(Problem P, int M, con
     gtr[x] = s;
 }
 
-inline size_t a256(size_t x) { return (x + 255) / 256 * 256; }
-
 inline size_t bwd_lds(int elem, int M, int N, bool tl) {
     return kBLHead + (((size_t) M * (elem + 4) + 15) & ~(size_t) 15) + (size_t) N * 8 + (tl ? (size_t) N * N * 8 : 0);
 }
@@ -480,7 +479,7 @@ BeamLossLayout beam_loss_layout(int elem, int T, int Q, int K, int cap, int nf, 
     BeamLossLayout l{};
     l.nf = nf;
     l.M = K + nf;
-    size_t off = beam_graph_work_bytes(elem, T, 1, Q, K, cap);               // the beam search's own part, at the front
+    size_t off = beam_work_layout(elem, T, Q, K, cap).end;                 // the beam search's own part, at the front
     l.cnt = off; off += a256((size_t) T * 4);
     l.nu = off;  off += a256((size_t) T * 4);
     l.hdr = off; off += 256;

@@ -32,8 +32,6 @@ namespace {
 constexpr int kNT = 1024;          // workgroup
 constexpr int kSlotBits = 16;      // q << 16 | slot: K <= 2^16 slots, q < 2^31
 
-inline size_t a256(size_t x) { return (x + 255) / 256 * 256; }
-
 // behind the utterances: what the beam search writes besides its sets (scores [B], lengths [B], path / tokens / states [3][B][T])
 inline size_t tail_bytes(int T, int B) { return 2 * a256((size_t) B * 8) + a256((size_t) 3 * B * T * 8); }
 
@@ -44,7 +42,7 @@ __device__ __forceinline__ bool pair_less(U ka, unsigned long long qa, U kb, uns
 
 template <typename R>
 __global__ void __launch_bounds__(kNT) beam_nbest_kernel(Problem P, GraphArgs g, BeamGraphArgs bg, BeamNbestLayout lay, int K,
-                                                         int nbest, int P2max, char *work, R *scores, R *escores, R *gscores,
+                                                         int cap, int nbest, int P2max, char *work, R *scores, R *escores, R *gscores,
                                                          long long *path, long long *tokens, long long *tlen,
                                                          long long *states, long long *nhyp) {
     using KT = Key<R>;
@@ -63,8 +61,8 @@ __global__ void __launch_bounds__(kNT) beam_nbest_kernel(Problem P, GraphArgs g,
     const R *sw = (const R *) g.start_w, *fw = (const R *) g.final_w, *ow = (const R *) bg.ow;
     const int2 *oarc = (const int2 *) bg.oarc;
     char *wb = work + (size_t) b * lay.per;
-    const int *bq = (const int *) wb;                                                        // [T][K] (beam_graph_kernel's layout)
-    const int *bs = (const int *) (wb + (((size_t) T * K * 4 + 255) & ~(size_t) 255));       // [T][K]
+    const BeamWorkLayout wl = beam_work_layout(sizeof(R), T, g.Q, K, cap);
+    const int *bq = (const int *) (wb + wl.bq), *bs = (const int *) (wb + wl.bs);            // [T][K] what beam_graph_kernel left
     const R *fin_v = (const R *) (wb + lay.fin + 8);
     int *rows = (int *) (wb + lay.rows);                                                     // [T][nb]
     const int64_t ob = (int64_t) b * nbest;                                                  // the utterance's first output row
@@ -195,7 +193,7 @@ __global__ void __launch_bounds__(kNT) beam_nbest_kernel(Problem P, GraphArgs g,
 BeamNbestLayout beam_nbest_layout(int elem, int T, int Q, int K, int cap, int nbest) {
     BeamNbestLayout l{};
     l.nb = nbest < K ? nbest : K;
-    size_t off = beam_graph_work_bytes(elem, T, 1, Q, K, cap);              // the beam search's own part, at the front
+    size_t off = beam_work_layout(elem, T, Q, K, cap).end;                // the beam search's own part, at the front
     l.fin = off;  off += a256(8 + (size_t) K * elem);
     l.rows = off; off += a256((size_t) T * l.nb * 4);
     l.per = off;
@@ -225,7 +223,8 @@ hipError_t launch_beam_nbest(const Problem &P, const GraphArgs &G, const BeamGra
     const size_t dyn = (size_t) P2 * (8 + sizeof(typename Key<R>::U));
     const void *fn = (const void *) beam_nbest_kernel<R>;
     if (dyn + 64 > 64 * 1024) (void) hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) dyn);
-    hipLaunchKernelGGL((beam_nbest_kernel<R>), dim3(B), dim3(kNT), dyn, stream, P, G, BG, lay, K, nbest, P2, w, (R *) scores,
+    hipLaunchKernelGGL((beam_nbest_kernel<R>), dim3(B), dim3(kNT), dyn, stream, P, G, BG, lay, K, cap, nbest, P2, w,
+                       (R *) scores,
                        (R *) emission_scores, (R *) graph_scores, path, tokens, tlen, states, num_hyps);
     return hipGetLastError();
 }

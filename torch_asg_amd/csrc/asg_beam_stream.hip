@@ -5,8 +5,9 @@
 // compiled into both translation units), and the search never looks ahead.
 //
 // A stream state serves B utterance slots.  One slot (beam_stream_layout; every part 256-byte aligned):
-//   the one-shot decoder's workspace of one utterance with T = max_frames: bq / bs int32 [max_frames][K] (product state and source
-//     slot of every kept state of every frame consumed so far), arg u64 [Q], val key [Q], ckey key [cap], touched int32 [cap];
+//   the one-shot decoder's workspace of one utterance with T = max_frames (asg_beam_common.h, beam_work_layout): bq / bs int32
+//     [max_frames][K] (product state and source slot of every kept state of every frame consumed so far), arg u64 [Q], val key
+//     [Q], ckey key [cap], touched int32 [cap];
 //   a 256-byte header: int32 pos (frames consumed), |A| (size of the stored set), overflow;
 //   the stored set: values [K] (dtype), then product states int32 [K].
 // Three kernels, each one launch, no host synchronisation, no copy, no memset:
@@ -27,21 +28,12 @@ namespace asg {
 
 namespace {
 
-inline size_t a256(size_t x) { return (x + 255) / 256 * 256; }
-
-constexpr int kResetBlocks = 64;   // workgroups per slot in the reset
-
-__global__ void __launch_bounds__(256) beam_stream_reset_kernel(char *state, BeamStreamLayout lay, int Q, int key_bytes,
-                                                                 size_t arg_off, size_t val_off, const unsigned char *mask) {
+__global__ void __launch_bounds__(256) beam_stream_reset_kernel(char *state, BeamStreamLayout lay, BeamWorkLayout wl, int Q,
+                                                                 int key_bytes, const unsigned char *mask) {
     const int b = blockIdx.x;
     if (mask && !mask[b]) return;
     char *wb = state + (size_t) b * lay.per;
-    unsigned long long *arg = (unsigned long long *) (wb + arg_off);
-    for (int q = blockIdx.y * 256 + threadIdx.x; q < Q; q += gridDim.y * 256) {
-        dev_store(arg + q, ~0ull);
-        if (key_bytes == 8) dev_store((unsigned long long *) (wb + val_off) + q, 0ull);
-        else dev_store((unsigned int *) (wb + val_off) + q, 0u);
-    }
+    beam_reset_tables(wb, wl, Q, key_bytes);
     if (blockIdx.y == 0 && threadIdx.x < 3) ((int *) (wb + lay.hdr))[threadIdx.x] = 0;      // pos, |A|, overflow
 }
 
@@ -59,8 +51,7 @@ __global__ void __launch_bounds__(kBT) beam_stream_advance_kernel(Problem P, Gra
     const int N = P.N;
     char *wb = state + (size_t) b * lay.per;
     int *hdr = (int *) (wb + lay.hdr);
-    R *set_v = (R *) (wb + lay.set);                        // [K]
-    int *set_q = (int *) (set_v + K);                       // [K]
+    R *set_v = (R *) (wb + lay.set);                        // values [K], then product states [K]
     int pos = hdr[0];
     pos = pos < 0 ? 0 : (pos > max_frames ? max_frames : pos);             // (a state that was reset holds 0 .. max_frames)
     const int want = clamp_len(P.in_len, b, P.T);
@@ -77,13 +68,9 @@ __global__ void __launch_bounds__(kBT) beam_stream_advance_kernel(Problem P, Gra
     int *bq, *bs;
     f.bind_work(wb, max_frames, cap, bq, bs);
 
-    if constexpr (TRL)
-        for (int x = tid; x < N * N; x += kBT) trs[x] = tr[(int64_t) (x / N) * P.ts0 + (int64_t) (x % N) * P.ts1];
     int na0 = pos >= 1 ? hdr[1] : 0;
     na0 = na0 < 0 ? 0 : (na0 > K ? K : na0);
-    for (int k = tid; k < na0; k += kBT) { cur_v[k] = set_v[k]; cur_q[k] = set_q[k]; }
-    if (tid == 0) { ctl.na = na0; ctl.n = 0; }
-    __syncthreads();
+    beam_load_set<R, TRL>(f, trs, set_v, na0);
 
     for (int t = 0; t < n; ++t) {
         const int gt = pos + t;                             // the frame's index in the utterance
@@ -92,17 +79,15 @@ __global__ void __launch_bounds__(kBT) beam_stream_advance_kernel(Problem P, Gra
         beam_frame<R, TRL>(f, gt == 0, na, in + (int64_t) t * P.is0, P.is2, bq, bs, gt);
     }
 
-    int na = ctl.na;
-    na = na < K ? na : K;
-    for (int k = tid; k < na; k += kBT) { set_v[k] = cur_v[k]; set_q[k] = cur_q[k]; }
+    const int na = beam_store_set<R>(f, set_v);
     if (tid == 0) { hdr[1] = na; hdr[0] = pos + n; }
 }
 
 template <typename R>
-__global__ void __launch_bounds__(kBT) beam_stream_result_kernel(GraphArgs g, int K, int max_frames, const char *state,
-                                                                 BeamStreamLayout lay, int final, R *scores, long long *path,
-                                                                 long long *tokens, long long *tlen, long long *states,
-                                                                 long long *frames, long long *status) {
+__global__ void __launch_bounds__(kBT) beam_stream_result_kernel(GraphArgs g, int K, int cap, int max_frames,
+                                                                 const char *state, BeamStreamLayout lay, int final, R *scores,
+                                                                 long long *path, long long *tokens, long long *tlen,
+                                                                 long long *states, long long *frames, long long *status) {
     using U = typename Key<R>::U;
     __shared__ Ctl<U> ctl;
     const int tid = threadIdx.x, b = blockIdx.x, T = max_frames;
@@ -111,8 +96,8 @@ __global__ void __launch_bounds__(kBT) beam_stream_result_kernel(GraphArgs g, in
     const int *hdr = (const int *) (wb + lay.hdr);
     const R *set_v = (const R *) (wb + lay.set);
     const int *set_q = (const int *) (set_v + K);
-    const int *bq = (const int *) wb;                                                        // [max_frames][K]
-    const int *bs = (const int *) (wb + (((size_t) T * K * 4 + 255) & ~(size_t) 255));       // [max_frames][K]
+    const BeamWorkLayout wl = beam_work_layout(sizeof(R), T, g.Q, K, cap);
+    const int *bq = (const int *) (wb + wl.bq), *bs = (const int *) (wb + wl.bs);             // [max_frames][K]
     long long *pb = path + (int64_t) b * T, *tk = tokens + (int64_t) b * T, *st = states + (int64_t) b * T;
     int L = hdr[0];
     L = L < 0 ? 0 : (L > T ? T : L);
@@ -137,7 +122,7 @@ __global__ void __launch_bounds__(kBT) beam_stream_result_kernel(GraphArgs g, in
 
 BeamStreamLayout beam_stream_layout(int elem, int max_frames, int Q, int K, int cap) {
     BeamStreamLayout l{};
-    size_t off = beam_graph_work_bytes(elem, max_frames, 1, Q, K, cap);     // the one-shot decoder's part, at the front
+    size_t off = beam_work_layout(elem, max_frames, Q, K, cap).end;       // the one-shot decoder's part, at the front
     l.hdr = off;  off += 256;
     l.set = off;  off += a256((size_t) K * (elem + 4));
     l.per = off;
@@ -152,11 +137,8 @@ hipError_t launch_beam_stream_reset(int elem, const GraphArgs &G, const BeamGrap
                                     const unsigned char *mask, hipStream_t stream) {
     const int cap = beam_graph_cap(G.Q, K, BG.max_out, BG.num_start);
     const BeamStreamLayout lay = beam_stream_layout(elem, max_frames, G.Q, K, cap);
-    const size_t arg_off = 2 * a256((size_t) max_frames * K * 4), val_off = arg_off + a256((size_t) G.Q * 8);
-    int by = (G.Q + 255) / 256;
-    by = by < 1 ? 1 : (by > kResetBlocks ? kResetBlocks : by);
-    hipLaunchKernelGGL(beam_stream_reset_kernel, dim3(B, by), dim3(256), 0, stream, (char *) state, lay, G.Q, elem, arg_off, val_off,
-                       mask);
+    hipLaunchKernelGGL(beam_stream_reset_kernel, dim3(B, reset_blocks(G.Q)), dim3(256), 0, stream, (char *) state, lay,
+                       beam_work_layout(elem, max_frames, G.Q, K, cap), G.Q, elem, mask);
     return hipGetLastError();
 }
 
@@ -192,8 +174,8 @@ hipError_t launch_beam_stream_result(const GraphArgs &G, const BeamGraphArgs &BG
                                      long long *states, long long *frames, long long *status, hipStream_t stream) {
     const int cap = beam_graph_cap(G.Q, K, BG.max_out, BG.num_start);
     const BeamStreamLayout lay = beam_stream_layout(sizeof(R), max_frames, G.Q, K, cap);
-    hipLaunchKernelGGL((beam_stream_result_kernel<R>), dim3(B), dim3(kBT), 0, stream, G, K, max_frames, (const char *) state, lay,
-                       final, (R *) scores, path, tokens, tlen, states, frames, status);
+    hipLaunchKernelGGL((beam_stream_result_kernel<R>), dim3(B), dim3(kBT), 0, stream, G, K, cap, max_frames, (const char *) state,
+                       lay, final, (R *) scores, path, tokens, tlen, states, frames, status);
     return hipGetLastError();
 }
 template hipError_t launch_beam_stream_result<float>(const GraphArgs &, const BeamGraphArgs &, int, int, int, const void *, int,

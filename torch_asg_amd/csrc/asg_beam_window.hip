@@ -6,8 +6,8 @@
 // frame body reads its sources from the set in LDS and writes the row it is given.
 //
 // One slot of the state (beam_window_layout; every part 256-byte aligned):
-//   the one-shot decoder's workspace of one utterance with T = W: bq / bs int32 [W][K], arg u64 [Q], val key [Q], ckey key [cap],
-//     touched int32 [cap];
+//   the one-shot decoder's workspace of one utterance with T = W (asg_beam_common.h, beam_work_layout): bq / bs int32 [W][K], arg
+//     u64 [Q], val key [Q], ckey key [cap], touched int32 [cap];
 //   a 256-byte header: int64 pos (frames consumed), int64 base (frames committed), int32 |A|, carry (label of the last committed
 //     frame, -1: none), status (bit 0: a forced commit has happened);
 //   the stored set: values [K] (dtype), then product states int32 [K].
@@ -17,23 +17,20 @@
 //                               after every frame whose count is a multiple of P, the five outputs of the call with their padding.
 //   beam_window_result_kernel   one workgroup per slot: the best end over the stored set, the backtrace over the uncommitted tail
 //                               (at most W steps), its collapse started from carry.  It only reads the state.
-// A commit attempt: the convergence scan marks, frame by frame backwards, the slots that some survivor descends from -- two K-bit
-// sets in LDS, lanes striding over the slots, an integer atomicOr per marked slot, a popcount to count them -- and stops where one
-// slot is left; one lane then walks that slot's chain down to `base`.  The rows of this call's frames were written by this
-// workgroup with plain stores and are read after a __syncthreads (beam_frame ends with one); those of earlier calls cross a
-// kernel boundary.  Integer atomics only, and the marks are a set: bit-identical run to run.
+// A commit attempt is the text of asg_beam_window_common.h, which asg_beam_word_window.hip compiles too: the convergence scan
+// (window_converge) finds the latest frame at which every survivor has the same ancestor, window_commit walks that slot's chain
+// down to `base` and collapses the labels, window_forced says when the ring is about to overwrite a live row; the clamp of a
+// slot's header (window_header) is there as well.  This unit keeps its header, its control blocks and its call of beam_best_end.
 #include "asg_common.h"
 #include "asg_kernels.h"
 #include "asg_beam_common.h"
 #include "asg_beam_frame.h"
+#include "asg_beam_window_common.h"   // the commit attempt, shared with asg_beam_word_window.hip
 
 namespace asg {
 
 namespace {
 
-inline size_t a256(size_t x) { return (x + 255) / 256 * 256; }
-
-constexpr int kResetBlocks = 64;       // workgroups per slot in the reset
 constexpr size_t kWinCtlOff = 3072;    // the window's control block sits behind the search's inside the fixed LDS
 
 // The header of a slot.
@@ -48,25 +45,16 @@ struct WinCtl {
     long long base;          // frames committed so far
     int carry, status;
     int ncommit, ntok;       // frames / tokens this call has appended to its outputs
-    int cnt[2];              // |R| of the scan's steps, alternating
-    int slot;                // a marked slot (the one, when |R| == 1)
+    WinScan scan;
 };
 constexpr size_t kWinOutOff = kWinCtlOff + 64;
 
-// The bytes of the two mark sets for K slots, kept a multiple of 16 so that the set behind them stays aligned.
-__host__ __device__ inline size_t mark_bytes(int K) { return ((size_t) 2 * ((K + 31) / 32) * 4 + 15) & ~(size_t) 15; }
-
-__global__ void __launch_bounds__(256) beam_window_reset_kernel(char *state, BeamStreamLayout lay, int Q, int key_bytes,
-                                                                 size_t arg_off, size_t val_off, const unsigned char *mask) {
+__global__ void __launch_bounds__(256) beam_window_reset_kernel(char *state, BeamStreamLayout lay, BeamWorkLayout wl, int Q,
+                                                                 int key_bytes, const unsigned char *mask) {
     const int b = blockIdx.x;
     if (mask && !mask[b]) return;
     char *wb = state + (size_t) b * lay.per;
-    unsigned long long *arg = (unsigned long long *) (wb + arg_off);
-    for (int q = blockIdx.y * 256 + threadIdx.x; q < Q; q += gridDim.y * 256) {
-        dev_store(arg + q, ~0ull);
-        if (key_bytes == 8) dev_store((unsigned long long *) (wb + val_off) + q, 0ull);
-        else dev_store((unsigned int *) (wb + val_off) + q, 0u);
-    }
+    beam_reset_tables(wb, wl, Q, key_bytes);
     if (blockIdx.y == 0 && threadIdx.x == 0) {
         WinHdr *h = (WinHdr *) (wb + lay.hdr);
         h->pos = 0; h->base = 0; h->na = 0; h->carry = -1; h->status = 0;
@@ -76,6 +64,7 @@ __global__ void __launch_bounds__(256) beam_window_reset_kernel(char *state, Bea
 // What the commits of one call write to, and the ring they read (LDS, behind WinCtl: a commit is rare, and the frame loop
 // keeps its scalar registers for the search).
 struct WinOut {
+    static constexpr bool kWords = false;    // (window_commit: no ring of LM states, no words)
     const int *bq, *bs;          // the ring [W][K]
     int K, Q, W;
     const int *label, *state;
@@ -84,41 +73,6 @@ struct WinOut {
 };
 static_assert(sizeof(Ctl<unsigned long long>) <= kWinCtlOff && sizeof(WinCtl) <= 64 && kWinOutOff + sizeof(WinOut) <= kFixedLds,
               "control blocks");
-
-// Commit the frames base .. cto on the path that passes slot k of frame `top`, which lives in row `r` (base <= cto <= top <
-// base + W): one lane walks the chain, one wavefront collapses the segment behind `carry`.  The whole workgroup calls it; it
-// begins after and ends with a __syncthreads.
-__device__ __forceinline__ void window_commit(WinCtl &wc, const WinOut &o, long long top, int r, long long cto, int k) {
-    const int tid = threadIdx.x;
-    const long long base = wc.base;
-    const int c0 = wc.ncommit;
-    long long room = o.cols - c0;                            // (never short: committed <= the live frames before the call + n)
-    int len = (int) (cto - base + 1);
-    len = len < 0 ? 0 : ((long long) len > room ? (int) room : len);
-    if (tid == 0) {
-        const int K = o.K, W = o.W;
-        long long t = top;
-        for (; t > cto && (unsigned) k < (unsigned) K; --t, r = r == 0 ? W - 1 : r - 1) k = o.bs[(int64_t) r * K + k];
-        for (; t > base + len - 1; --t) r = r == 0 ? W - 1 : r - 1;       // (only if the output row were short)
-        for (; t >= base; --t, r = r == 0 ? W - 1 : r - 1) {
-            if ((unsigned) k >= (unsigned) K) break;         // (cannot happen: every kept state stored its source's slot)
-            const int64_t at = (int64_t) r * K + k;
-            int q = o.bq[at];
-            q = (unsigned) q < (unsigned) o.Q ? q : 0;
-            k = o.bs[at];
-            o.np[c0 + (t - base)] = o.label[q];
-            o.ns[c0 + (t - base)] = o.state[q];
-        }
-    }
-    __threadfence();
-    __syncthreads();
-    if (tid < 64) {
-        long long carry = wc.carry;
-        const int nt = collapse_tokens_from(o.np + c0, len, carry, o.nt + wc.ntok, tid);
-        if (tid == 0) { wc.ntok += nt; wc.carry = (int) carry; wc.ncommit = c0 + len; wc.base = base + len; }
-    }
-    __syncthreads();
-}
 
 template <typename R, bool TRL>
 __global__ void __launch_bounds__(kBT) beam_window_advance_kernel(Problem P, GraphArgs g, BeamGraphArgs bg, int K, R theta, int cap,
@@ -131,17 +85,15 @@ __global__ void __launch_bounds__(kBT) beam_window_advance_kernel(Problem P, Gra
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     Ctl<U> &ctl = *(Ctl<U> *) lds;
     WinCtl &wc = *(WinCtl *) (lds + kWinCtlOff);
-    const int nw = (K + 31) / 32;                          // words of a mark set
-    unsigned *mark = (unsigned *) (lds + kFixedLds);       // [2][nw]
+    unsigned *mark = (unsigned *) (lds + kFixedLds);       // the two mark sets of the scan
     R *cur_v = (R *) (lds + kFixedLds + mark_bytes(K));    // [K]
     int *cur_q = (int *) (cur_v + K);                      // [K]
     R *trs = (R *) (cur_q + K + (K & 1));                  // [N][N] if TRL
-    const int tid = threadIdx.x, lane = tid & 63, b = blockIdx.x;
+    const int tid = threadIdx.x, b = blockIdx.x;
     const int N = P.N;
     char *wb = state + (size_t) b * lay.per;
     WinHdr *hdr = (WinHdr *) (wb + lay.hdr);
-    R *set_v = (R *) (wb + lay.set);                        // [K]
-    int *set_q = (int *) (set_v + K);                       // [K]
+    R *set_v = (R *) (wb + lay.set);                        // values [K], then product states [K]
     const long long cols = (long long) W + P.T;
     WinOut &o = *(WinOut *) (lds + kWinOutOff);
     long long *np = new_path + (int64_t) b * cols, *ns = new_states + (int64_t) b * cols, *nt = new_tokens + (int64_t) b * cols;
@@ -151,16 +103,10 @@ __global__ void __launch_bounds__(kBT) beam_window_advance_kernel(Problem P, Gra
         o.np = np; o.ns = ns; o.nt = nt;
     }
 
-    // (a state that was reset holds 0 <= base <= pos, and pos <= base + W while its set is not empty: behind an empty set pos
-    // goes on alone, and base is never used again)
-    long long pos = hdr->pos;
-    pos = pos < 0 ? 0 : pos;
-    int na0 = pos >= 1 ? hdr->na : 0;
-    na0 = na0 < 0 ? 0 : (na0 > K ? K : na0);
-    long long base0 = hdr->base;
-    base0 = base0 > pos ? pos : base0;
-    base0 = na0 > 0 && base0 < pos - W ? pos - W : base0;
-    base0 = base0 < 0 ? 0 : base0;
+    long long pos = hdr->pos, base0 = hdr->base;
+    int na0 = hdr->na;
+    window_header(pos, base0, na0, K);
+    if (na0 > 0) base0 = window_live_base(pos, base0, W);
     const int n = clamp_len(P.in_len, b, P.T);
     if (tid == 0) { wc.base = base0; wc.carry = hdr->carry; wc.status = hdr->status; wc.ncommit = 0; wc.ntok = 0; }
 
@@ -176,11 +122,7 @@ __global__ void __launch_bounds__(kBT) beam_window_advance_kernel(Problem P, Gra
         f.bind_work(wb, W, cap, bq, bs);
         if (tid == 0) { o.bq = bq; o.bs = bs; }
 
-        if constexpr (TRL)
-            for (int x = tid; x < N * N; x += kBT) trs[x] = tr[(int64_t) (x / N) * P.ts0 + (int64_t) (x % N) * P.ts1];
-        for (int k = tid; k < na0; k += kBT) { cur_v[k] = set_v[k]; cur_q[k] = set_q[k]; }
-        if (tid == 0) { ctl.na = na0; ctl.n = 0; }
-        __syncthreads();
+        beam_load_set<R, TRL>(f, trs, set_v, na0);
 
         int row = (int) (pos % W), ph = (int) (pos % CP);   // the next frame's row, and pos mod P; both kept by stepping
         for (int t = 0; t < n; ++t) {
@@ -198,55 +140,15 @@ __global__ void __launch_bounds__(kBT) beam_window_advance_kernel(Problem P, Gra
             // ================================================================ commit attempt
             // ---- convergence: the latest frame at which every survivor has the same ancestor
             long long base = wc.base;
-            long long c = -1;
-            int cslot = 0, crow = fr;
-            if (na == 1) c = p1 - 1;
-            else {
-                unsigned *cur = mark, *nxt = mark + nw;
-                for (int w = tid; w < nw; w += kBT) {
-                    const int lo = w * 32;
-                    cur[w] = na >= lo + 32 ? ~0u : (na > lo ? (1u << (na - lo)) - 1u : 0u);
-                    nxt[w] = 0;
-                }
-                if (tid == 0) { wc.cnt[0] = 0; wc.cnt[1] = 0; }
-                __syncthreads();
-                int par = 0, ru = fr;                       // ru: the row of frame u
-                for (long long u = p1 - 1; u > base; --u, par ^= 1, ru = ru == 0 ? W - 1 : ru - 1) {
-                    const int *bsu = bs + (int64_t) ru * K;
-                    for (int k = tid; k < K; k += kBT)
-                        if ((cur[k >> 5] >> (k & 31)) & 1u) {
-                            const int s = bsu[k];
-                            if ((unsigned) s < (unsigned) K) atomicOr(&nxt[s >> 5], 1u << (s & 31));
-                        }
-                    __syncthreads();
-                    int mine = 0;
-                    for (int w = tid; w < nw; w += kBT) {
-                        const unsigned x = nxt[w];
-                        cur[w] = 0;
-                        mine += __popc(x);
-                        if (x) wc.slot = w * 32 + __ffs((int) x) - 1;
-                    }
-#pragma unroll
-                    for (int d = 1; d < 64; d <<= 1) mine += __shfl_xor(mine, d);
-                    if (lane == 0 && mine) atomicAdd(&wc.cnt[par], mine);
-                    if (tid == 0) wc.cnt[par ^ 1] = 0;
-                    __syncthreads();
-                    const int cnt = wc.cnt[par];
-                    unsigned *sw = cur; cur = nxt; nxt = sw;
-                    if (cnt <= 1) {                         // (never 0: every kept state stored its source's slot)
-                        if (cnt == 1) { c = u - 1; cslot = wc.slot; crow = ru == 0 ? W - 1 : ru - 1; }
-                        break;
-                    }
-                }
-            }
+            int cslot, crow;
+            const long long c = window_converge(bs, K, W, na, p1, base, fr, mark, wc.scan, cslot, crow);
             if (c >= base) {
                 window_commit(wc, o, c, crow, c, cslot);
                 base = wc.base;
             }
             // ---- forced commit: the next CP frames must not overwrite a live row
-            const long long live = p1 - base;
-            if (live > W - CP) {
-                const long long F = live - (W - CP);
+            const long long F = window_forced(p1, base, W, CP);
+            if (F > 0) {
                 U bkey;
                 int bqq, bk;
                 beam_best_end<R>(ctl, cur_q, cur_v, na, nullptr, bkey, bqq, bk);
@@ -257,9 +159,7 @@ __global__ void __launch_bounds__(kBT) beam_window_advance_kernel(Problem P, Gra
                 }
             }
         }
-        int na = ctl.na;
-        na = na < K ? na : K;
-        for (int k = tid; k < na; k += kBT) { set_v[k] = cur_v[k]; set_q[k] = cur_q[k]; }
+        const int na = beam_store_set<R>(f, set_v);
         if (tid == 0) hdr->na = na;
     }
     __syncthreads();
@@ -274,10 +174,10 @@ __global__ void __launch_bounds__(kBT) beam_window_advance_kernel(Problem P, Gra
 }
 
 template <typename R>
-__global__ void __launch_bounds__(kBT) beam_window_result_kernel(GraphArgs g, int K, int W, const char *state, BeamStreamLayout lay,
-                                                                 int final, R *scores, long long *path, long long *tokens,
-                                                                 long long *tlen, long long *states, long long *frames,
-                                                                 long long *committed, long long *status) {
+__global__ void __launch_bounds__(kBT) beam_window_result_kernel(GraphArgs g, int K, int cap, int W, const char *state,
+                                                                 BeamStreamLayout lay, int final, R *scores, long long *path,
+                                                                 long long *tokens, long long *tlen, long long *states,
+                                                                 long long *frames, long long *committed, long long *status) {
     using U = typename Key<R>::U;
     __shared__ Ctl<U> ctl;
     const int tid = threadIdx.x, b = blockIdx.x;
@@ -286,16 +186,12 @@ __global__ void __launch_bounds__(kBT) beam_window_result_kernel(GraphArgs g, in
     const WinHdr *hdr = (const WinHdr *) (wb + lay.hdr);
     const R *set_v = (const R *) (wb + lay.set);
     const int *set_q = (const int *) (set_v + K);
-    const int *bq = (const int *) wb;                                                        // [W][K]
-    const int *bs = (const int *) (wb + (((size_t) W * K * 4 + 255) & ~(size_t) 255));       // [W][K]
+    const BeamWorkLayout wl = beam_work_layout(sizeof(R), W, g.Q, K, cap);
+    const int *bq = (const int *) (wb + wl.bq), *bs = (const int *) (wb + wl.bs);             // the ring [W][K]
     long long *pb = path + (int64_t) b * W, *tk = tokens + (int64_t) b * W, *st = states + (int64_t) b * W;
-    long long pos = hdr->pos;
-    pos = pos < 0 ? 0 : pos;
-    long long base = hdr->base;
-    base = base > pos ? pos : base;
-    base = base < 0 ? 0 : base;
-    int na = pos >= 1 ? hdr->na : 0;
-    na = na < 0 ? 0 : (na > K ? K : na);
+    long long pos = hdr->pos, base = hdr->base;
+    int na = hdr->na;
+    window_header(pos, base, na, K);
     if (tid == 0) {
         frames[b] = pos;
         committed[b] = base;
@@ -311,7 +207,7 @@ __global__ void __launch_bounds__(kBT) beam_window_result_kernel(GraphArgs g, in
         return;
     }
     if (tid == 0) scores[b] = fw ? set_v[bk] + fw[bqq] : set_v[bk];
-    base = base < pos - W ? pos - W : base;                 // (a set that is not empty has pos <= base + W)
+    base = window_live_base(pos, base, W);                  // (a set that is not empty has pos <= base + W)
     const int live = (int) (pos - base);                    // 0 .. W
     for (int t = live + tid; t < W; t += kBT) { pb[t] = -1; st[t] = -1; }
     if (tid == 0) {
@@ -341,14 +237,7 @@ __global__ void __launch_bounds__(kBT) beam_window_result_kernel(GraphArgs g, in
 }  // namespace
 
 // The slot of a window stream is the slot of a stream of W frames: the ring has the [frame][K] layout with W rows.
-BeamStreamLayout beam_window_layout(int elem, int W, int Q, int K, int cap) {
-    BeamStreamLayout l{};
-    size_t off = beam_graph_work_bytes(elem, W, 1, Q, K, cap);
-    l.hdr = off;  off += 256;
-    l.set = off;  off += a256((size_t) K * (elem + 4));
-    l.per = off;
-    return l;
-}
+BeamStreamLayout beam_window_layout(int elem, int W, int Q, int K, int cap) { return beam_stream_layout(elem, W, Q, K, cap); }
 
 size_t beam_window_state_bytes(int elem, int W, int B, int Q, int K, int cap) {
     return (size_t) B * beam_window_layout(elem, W, Q, K, cap).per;
@@ -358,11 +247,8 @@ hipError_t launch_beam_window_reset(int elem, const GraphArgs &G, const BeamGrap
                                     const unsigned char *mask, hipStream_t stream) {
     const int cap = beam_graph_cap(G.Q, K, BG.max_out, BG.num_start);
     const BeamStreamLayout lay = beam_window_layout(elem, W, G.Q, K, cap);
-    const size_t arg_off = 2 * a256((size_t) W * K * 4), val_off = arg_off + a256((size_t) G.Q * 8);
-    int by = (G.Q + 255) / 256;
-    by = by < 1 ? 1 : (by > kResetBlocks ? kResetBlocks : by);
-    hipLaunchKernelGGL(beam_window_reset_kernel, dim3(B, by), dim3(256), 0, stream, (char *) state, lay, G.Q, elem, arg_off, val_off,
-                       mask);
+    hipLaunchKernelGGL(beam_window_reset_kernel, dim3(B, reset_blocks(G.Q)), dim3(256), 0, stream, (char *) state, lay,
+                       beam_work_layout(elem, W, G.Q, K, cap), G.Q, elem, mask);
     return hipGetLastError();
 }
 
@@ -401,7 +287,7 @@ hipError_t launch_beam_window_result(const GraphArgs &G, const BeamGraphArgs &BG
                                      long long *frames, long long *committed, long long *status, hipStream_t stream) {
     const int cap = beam_graph_cap(G.Q, K, BG.max_out, BG.num_start);
     const BeamStreamLayout lay = beam_window_layout(sizeof(R), W, G.Q, K, cap);
-    hipLaunchKernelGGL((beam_window_result_kernel<R>), dim3(B), dim3(kBT), 0, stream, G, K, W, (const char *) state, lay, final,
+    hipLaunchKernelGGL((beam_window_result_kernel<R>), dim3(B), dim3(kBT), 0, stream, G, K, cap, W, (const char *) state, lay, final,
                        (R *) scores, path, tokens, tlen, states, frames, committed, status);
     return hipGetLastError();
 }

@@ -111,14 +111,6 @@ __global__ void __launch_bounds__(kBT) beam_word_kernel(Problem P, GraphArgs g, 
                       wlen + b);
 }
 
-inline size_t a256(size_t x) { return (x + 255) / 256 * 256; }
-
-inline size_t beam_word_per_utt(int elem, int T, int K, int cap) {
-    const size_t C = (size_t) 1 << word_table_bits(cap);
-    return 3 * a256((size_t) T * K * 4) + 2 * a256(C * 8) + a256(C * elem) + a256((size_t) cap * elem) + a256((size_t) cap * 8) +
-           a256((size_t) cap * 4);
-}
-
 }  // namespace
 
 // The touched list holds the target pairs of one frame: at most K * (largest out-degree + 1), at least the start states.  (No
@@ -129,7 +121,9 @@ int beam_word_cap(int K, int max_out, int num_start) {
     return (int) (c < 1 ? 1 : c);
 }
 
-size_t beam_word_work_bytes(int elem, int T, int B, int K, int cap) { return (size_t) B * beam_word_per_utt(elem, T, K, cap); }
+size_t beam_word_work_bytes(int elem, int T, int B, int K, int cap) {
+    return (size_t) B * beam_word_work_layout(elem, T, K, cap, word_table_bits(cap)).end;
+}
 
 template <typename R>
 hipError_t launch_beam_words(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int K,
@@ -139,7 +133,7 @@ hipError_t launch_beam_words(const Problem &P, const GraphArgs &G, const BeamGra
     const int N = P.N;
     const int cap = beam_word_cap(K, BG.max_out, BG.num_start);
     const int tbits = word_table_bits(cap);
-    const size_t per = stride ? stride : beam_word_per_utt(sizeof(R), P.T, K, cap);
+    const size_t per = stride ? stride : beam_word_work_layout(sizeof(R), P.T, K, cap, tbits).end;
     const size_t beam = kFixedLds + (size_t) K * (sizeof(R) + 8);
     const bool trl = beam + (size_t) N * N * sizeof(R) <= kLdsMax;
     const size_t dyn = beam + (trl ? (size_t) N * N * sizeof(R) : 0);

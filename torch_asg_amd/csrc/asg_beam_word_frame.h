@@ -4,7 +4,9 @@
 // loop with the set an earlier call left, beam_word_stream_result_kernel is the end as a call of its own).  Both translation
 // units compile this text, as asg_beam_graph.hip and asg_beam_stream.hip compile asg_beam_frame.h: that is what "decoding in
 // chunks gives the bits of decoding in one call" rests on (include/asg_hip.h::asg_beam_word_stream_advance).  The frame is
-// described at the top of asg_beam_word.hip.
+// described at the top of asg_beam_word.hip.  Also here, for the two word streams (asg_beam_word_stream.hip,
+// asg_beam_word_window.hip): bind_graph, the clearing loop of their resets (beam_word_reset_tables), the way their advance kernels
+// enter and leave the frame loop (beam_word_load_set, beam_word_store_set), and collapse_words_from for the window's commits.
 #pragma once
 #include "asg_common.h"
 #include "asg_kernels.h"
@@ -73,18 +75,12 @@ struct BeamWordFrame {
     unsigned long long *cpair;   // [cap]
     int *tl;                     // [cap] the touched slots
 
+    // The utterance's slot arrays inside its workspace `wb` (beam_word_work for T frames); -> the [T][K] lists.
     __device__ __forceinline__ void bind_work(char *wb, int T, int *&bq, int *&bh, int *&bs) {
-        const size_t a256 = 255, C = (size_t) 1 << tbits;
-        size_t off = 0;
-        bq = (int *) (wb + off);  off += ((size_t) T * K * 4 + a256) & ~a256;       // [T][K] product state of each slot
-        bh = (int *) (wb + off);  off += ((size_t) T * K * 4 + a256) & ~a256;       // [T][K] its LM state
-        bs = (int *) (wb + off);  off += ((size_t) T * K * 4 + a256) & ~a256;       // [T][K] its source's slot at t-1
-        tkey = (unsigned long long *) (wb + off);  off += (C * 8 + a256) & ~a256;
-        arg = (unsigned long long *) (wb + off);   off += (C * 8 + a256) & ~a256;
-        val = (U *) (wb + off);     off += (C * sizeof(U) + a256) & ~a256;
-        ckey = (U *) (wb + off);    off += ((size_t) cap * sizeof(U) + a256) & ~a256;
-        cpair = (unsigned long long *) (wb + off);  off += ((size_t) cap * 8 + a256) & ~a256;
-        tl = (int *) (wb + off);
+        const BeamWordWork<char *> l = beam_word_work(wb, sizeof(U), T, K, cap, tbits);
+        bq = (int *) l.bq;  bh = (int *) l.bh;  bs = (int *) l.bs;
+        tkey = (unsigned long long *) l.tkey;  arg = (unsigned long long *) l.arg;  val = (U *) l.val;
+        ckey = (U *) l.ckey;  cpair = (unsigned long long *) l.cpair;  tl = (int *) l.tl;
     }
     __device__ __forceinline__ unsigned long long pair(int h, int q) const {
         return ((unsigned long long) (unsigned) h << qbits) | (unsigned) q;
@@ -180,6 +176,30 @@ struct BeamWordFrame {
     }
     WordLook<R, LA> la;
 };
+
+// The parts of a BeamWordFrame that do not depend on the call: the graph, the LM and the shape of the search.
+template <typename R, bool LA>
+__device__ __forceinline__ void bind_graph(BeamWordFrame<R, LA> &f, const GraphArgs &g, const BeamGraphArgs &bg, const WordLmArgs &lm,
+                                           int K, int cap, int tbits) {
+    f.K = K; f.G = beam_lanes_per_state(K); f.cap = cap; f.sep = lm.sep; f.tbits = tbits;
+    f.qbits = bits_of(g.Q); f.pbits = f.qbits + bits_of(lm.H);
+    f.label = g.label; f.state = g.state; f.orow = bg.orow; f.start_q = bg.start_q; f.num_start = bg.num_start;
+    f.oarc = (const int2 *) bg.oarc; f.ow = (const R *) bg.ow; f.sw = (const R *) g.start_w;
+    f.lrow = lm.row; f.lword = lm.word; f.lnext = lm.next; f.lback = lm.backoff; f.wos = lm.word_of_state;
+    f.lw = (const R *) lm.lw; f.bw = (const R *) lm.bw; f.ew = (const R *) lm.ew; f.lstart = lm.start;
+}
+
+// A word stream's reset (asg_beam_word_stream.hip, asg_beam_word_window.hip): the whole table of the slot whose workspace is
+// `wb` emptied -- tkey = 0, val = 0, arg = none for all C slots -- by the workgroups of 256 threads that blockIdx.y counts.
+__device__ __forceinline__ void beam_word_reset_tables(char *wb, const BeamWordWorkLayout &l, unsigned C, int key_bytes) {
+    unsigned long long *tkey = (unsigned long long *) (wb + l.tkey), *arg = (unsigned long long *) (wb + l.arg);
+    for (unsigned s = blockIdx.y * 256 + threadIdx.x; s < C; s += gridDim.y * 256) {
+        dev_store(tkey + s, 0ull);
+        dev_store(arg + s, ~0ull);
+        if (key_bytes == 8) dev_store((unsigned long long *) (wb + l.val) + s, 0ull);
+        else dev_store((unsigned int *) (wb + l.val) + s, 0u);
+    }
+}
 
 // One frame: from the kept set (f.cur_h, f.cur_q, f.cur_v)[0..na) of the frame before -- or, with `first`, from the start states
 // -- to the new one, with (q, h, source slot) of every kept pair into row `row` of the [.][K] lists bq / bh / bs.  `xt` are the
@@ -436,6 +456,30 @@ __device__ __forceinline__ void beam_word_frame(const BeamWordFrame<R, LA> &f, b
     __syncthreads();
 }
 
+// A word stream's advance (asg_beam_word_stream.hip, asg_beam_word_window.hip) enters the frame loop with the set an earlier call
+// left at `set_v` -- values [K], then product states int32 [K], then LM states int32 [K]: the transitions into LDS when they live
+// there, the na0 stored pairs into f.cur_v / f.cur_q / f.cur_h, the counters.  The whole workgroup calls it; it ends with a
+// __syncthreads.
+template <typename R, bool TRL>
+__device__ __forceinline__ void beam_word_load_set(const BeamWordFrame<R> &f, R *trs, const R *set_v, int na0) {
+    const int tid = threadIdx.x, N = f.N;
+    const int *set_q = (const int *) (set_v + f.K), *set_h = set_q + f.K;
+    if constexpr (TRL)
+        for (int x = tid; x < N * N; x += kBT) trs[x] = f.tr[(int64_t) (x / N) * f.ts0 + (int64_t) (x % N) * f.ts1];
+    for (int k = tid; k < na0; k += kBT) { f.cur_v[k] = set_v[k]; f.cur_q[k] = set_q[k]; f.cur_h[k] = set_h[k]; }
+    if (tid == 0) { f.ctl->na = na0; f.ctl->n = 0; }
+    __syncthreads();
+}
+// ... and leaves it: the set back to `set_v`; -> its size, for the header.
+template <typename R>
+__device__ __forceinline__ int beam_word_store_set(const BeamWordFrame<R> &f, R *set_v) {
+    int *set_q = (int *) (set_v + f.K), *set_h = set_q + f.K;
+    int na = f.ctl->na;
+    na = na < f.K ? na : f.K;
+    for (int k = threadIdx.x; k < na; k += kBT) { set_v[k] = f.cur_v[k]; set_q[k] = f.cur_q[k]; set_h[k] = f.cur_h[k]; }
+    return na;
+}
+
 // The end of a kept pair (h, q) with value v: (v + final_w[q]) + endw, endw = ew[h] at the root, a + ew[h'] after the LM walk of
 // the word that ends in q's node; false: no end (mid-word, or the walk rejects).  `w`: that word, or -1.
 template <typename R, bool LA = false>
@@ -461,6 +505,29 @@ __device__ __forceinline__ void word_no_path(int T, long long *pb, long long *tk
     const int tid = threadIdx.x;
     for (int t = tid; t < T; t += kBT) { pb[t] = -1; tk[t] = -1; st[t] = -1; lm[t] = -1; wd[t] = -1; }
     if (tid == 0) { *tlen = 0; *wlen = 0; }
+}
+
+// One wavefront: the words of a SEGMENT of a path that continues an earlier one (asg_beam_word_window.hip).  pb / st [0..len)
+// are the labels and automaton states behind a frame whose label was `carry` and whose state was `carry_state` (-1: there is no
+// such frame).  A word ends where the separator stands behind another label: it is the word of the state before.  They go to
+// wd[0..), nothing is padded.  -> the number appended; every lane gets it.
+__device__ inline int collapse_words_from(const long long *pb, const long long *st, int len, long long carry, long long carry_state,
+                                          int sep, const int *wos, int S, long long *wd, int lane) {
+    int base = 0;
+    for (int c0 = 0; c0 < len; c0 += 64) {
+        const int t = c0 + lane;
+        const long long cur = t < len ? pb[t] : -1, curs = t < len ? st[t] : -1;
+        long long prv = __shfl_up(cur, 1), prvs = __shfl_up(curs, 1);
+        if (lane == 0) { prv = carry; prvs = carry_state; }
+        const bool keep = t < len && cur == sep && prv != sep && prv >= 0;
+        const unsigned long long m = __ballot(keep);
+        const int pre = __popcll(m & ((1ull << lane) - 1ull));
+        if (keep) wd[base + pre] = wos[(unsigned long long) prvs < (unsigned long long) S ? (int) prvs : 0];
+        base += __popcll(m);
+        carry = __shfl(cur, 63);             // (the last block's carries are not used again)
+        carry_state = __shfl(curs, 63);
+    }
+    return base;
 }
 
 // The best end over a set (sh, sq, sv)[0..na), the smallest pair on a tie (-0 and +0 are one key): with `final` the end of

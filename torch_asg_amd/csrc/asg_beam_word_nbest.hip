@@ -37,8 +37,6 @@ namespace {
 
 constexpr int kNT = 1024;          // workgroup
 
-inline size_t a256(size_t x) { return (x + 255) / 256 * 256; }
-
 // behind the utterances of the one-shot call: what the one-best search writes (scores [B], token and word lengths [B], path /
 // tokens / states / lm_states / words [5][B][T])
 inline size_t tail_bytes(int T, int B) { return 3 * a256((size_t) B * 8) + a256((size_t) 5 * B * T * 8); }
@@ -61,7 +59,8 @@ __device__ __forceinline__ bool entry_less(U ka, unsigned long long pa, U kb, un
 
 template <typename R>
 __global__ void __launch_bounds__(kNT) beam_word_nbest_kernel(Problem P, GraphArgs g, BeamGraphArgs bg, WordLmArgs lm,
-                                                              BeamWordNbestSrc src, int K, int nbest, int P2max, int final,
+                                                              BeamWordNbestSrc src, int K, int cap, int tbits, int nbest, int P2max,
+                                                              int final,
                                                               R *scores, R *escores, R *gscores, R *lscores, long long *path,
                                                               long long *tokens, long long *tlen, long long *states,
                                                               long long *lm_states, long long *words, long long *wlen,
@@ -82,8 +81,8 @@ __global__ void __launch_bounds__(kNT) beam_word_nbest_kernel(Problem P, GraphAr
     const R *tr = (const R *) P.transition;
     const R *sw = (const R *) g.start_w, *fw = (const R *) g.final_w, *ow = (const R *) bg.ow;
     const int2 *oarc = (const int2 *) bg.oarc;
-    const size_t rowb = ((size_t) T * K * 4 + 255) & ~(size_t) 255;
-    const int *bq = (const int *) wb, *bh = (const int *) (wb + rowb), *bs = (const int *) (wb + 2 * rowb);   // [T][K] each
+    const BeamWordWorkLayout wl = beam_word_work_layout(sizeof(R), T, K, cap, tbits);
+    const int *bq = (const int *) (wb + wl.bq), *bh = (const int *) (wb + wl.bh), *bs = (const int *) (wb + wl.bs);
     const R *set_v = (const R *) (wb + src.set_off);
     const int *set_q = (const int *) (set_v + K), *set_h = set_q + K;
     int *cols = (int *) (src.cols + (size_t) b * src.cols_per);           // [T][nb]
@@ -273,9 +272,11 @@ hipError_t launch_nbest_kernel(const Problem &P, const GraphArgs &G, const BeamG
     int P2 = 1;
     while (P2 < K) P2 *= 2;
     const size_t dyn = (size_t) P2 * (8 + sizeof(typename Key<R>::U));
+    const int cap = beam_word_cap(K, BG.max_out, BG.num_start);
     const void *fn = (const void *) beam_word_nbest_kernel<R>;
     if (dyn + 64 > 64 * 1024) (void) hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) dyn);
-    hipLaunchKernelGGL((beam_word_nbest_kernel<R>), dim3(B), dim3(kNT), dyn, stream, P, G, BG, LM, src, K, nbest, P2, final,
+    hipLaunchKernelGGL((beam_word_nbest_kernel<R>), dim3(B), dim3(kNT), dyn, stream, P, G, BG, LM, src, K, cap, word_table_bits(cap),
+                       nbest, P2, final,
                        (R *) scores, (R *) escores, (R *) gscores, (R *) lscores, path, tokens, tlen, states, lm_states, words,
                        wlen, num_hyps, frames, status);
     return hipGetLastError();
@@ -286,7 +287,7 @@ hipError_t launch_nbest_kernel(const Problem &P, const GraphArgs &G, const BeamG
 BeamWordNbestLayout beam_word_nbest_layout(int elem, int T, int K, int cap, int nbest) {
     BeamWordNbestLayout l{};
     l.nb = nbest < K ? nbest : K;
-    size_t off = beam_word_work_bytes(elem, T, 1, K, cap);                  // the word decoder's own part, at the front
+    size_t off = beam_word_work_layout(elem, T, K, cap, word_table_bits(cap)).end;   // the word decoder's own part, at the front
     l.fin = off;  off += a256(8 + (size_t) K * (elem + 8));
     l.rows = off; off += a256((size_t) T * l.nb * 4);
     l.per = off;

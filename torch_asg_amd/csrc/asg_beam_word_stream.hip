@@ -6,9 +6,9 @@
 // walk of a separator edge reads the source pair's h and nothing else, whether that pair was kept a frame or a call ago.
 //
 // A stream state serves B utterance slots.  One slot (beam_word_stream_layout; every part 256-byte aligned):
-//   the one-shot decoder's workspace of one utterance with T = max_frames: bq / bh / bs int32 [max_frames][K] (product state, LM
-//     state and source slot of every kept pair of every frame consumed so far), the table tkey u64 [C], arg u64 [C], val key [C],
-//     ckey key [cap], cpair u64 [cap], touched int32 [cap];
+//   the one-shot decoder's workspace of one utterance with T = max_frames (asg_beam_common.h, beam_word_work_layout): bq / bh / bs
+//     int32 [max_frames][K] (product state, LM state and source slot of every kept pair of every frame consumed so far), the table
+//     tkey u64 [C], arg u64 [C], val key [C], ckey key [cap], cpair u64 [cap], touched int32 [cap];
 //   a 256-byte header: int32 pos (frames consumed), |A| (size of the stored set), overflow;
 //   the stored set: values [K] (dtype), then product states int32 [K], then LM states int32 [K].
 // Nothing is sized by H, V, A or Q.  Three kernels, each one launch, no host synchronisation, no copy, no memset:
@@ -32,36 +32,13 @@ namespace asg {
 
 namespace {
 
-inline size_t a256(size_t x) { return (x + 255) / 256 * 256; }
-
-constexpr int kResetBlocks = 64;   // workgroups per slot in the reset
-
-__global__ void __launch_bounds__(256) beam_word_stream_reset_kernel(char *state, BeamStreamLayout lay, unsigned C, int key_bytes,
-                                                                      size_t tkey_off, size_t arg_off, size_t val_off,
-                                                                      const unsigned char *mask) {
+__global__ void __launch_bounds__(256) beam_word_stream_reset_kernel(char *state, BeamStreamLayout lay, BeamWordWorkLayout wl,
+                                                                      unsigned C, int key_bytes, const unsigned char *mask) {
     const int b = blockIdx.x;
     if (mask && !mask[b]) return;
     char *wb = state + (size_t) b * lay.per;
-    unsigned long long *tkey = (unsigned long long *) (wb + tkey_off), *arg = (unsigned long long *) (wb + arg_off);
-    for (unsigned s = blockIdx.y * 256 + threadIdx.x; s < C; s += gridDim.y * 256) {
-        dev_store(tkey + s, 0ull);
-        dev_store(arg + s, ~0ull);
-        if (key_bytes == 8) dev_store((unsigned long long *) (wb + val_off) + s, 0ull);
-        else dev_store((unsigned int *) (wb + val_off) + s, 0u);
-    }
+    beam_word_reset_tables(wb, wl, C, key_bytes);
     if (blockIdx.y == 0 && threadIdx.x < 3) ((int *) (wb + lay.hdr))[threadIdx.x] = 0;      // pos, |A|, overflow
-}
-
-// The parts of a BeamWordFrame that do not depend on the call: the graph, the LM and the shape of the search.
-template <typename R>
-__device__ __forceinline__ void bind_graph(BeamWordFrame<R> &f, const GraphArgs &g, const BeamGraphArgs &bg, const WordLmArgs &lm,
-                                           int K, int cap, int tbits) {
-    f.K = K; f.G = beam_lanes_per_state(K); f.cap = cap; f.sep = lm.sep; f.tbits = tbits;
-    f.qbits = bits_of(g.Q); f.pbits = f.qbits + bits_of(lm.H);
-    f.label = g.label; f.state = g.state; f.orow = bg.orow; f.start_q = bg.start_q; f.num_start = bg.num_start;
-    f.oarc = (const int2 *) bg.oarc; f.ow = (const R *) bg.ow; f.sw = (const R *) g.start_w;
-    f.lrow = lm.row; f.lword = lm.word; f.lnext = lm.next; f.lback = lm.backoff; f.wos = lm.word_of_state;
-    f.lw = (const R *) lm.lw; f.bw = (const R *) lm.bw; f.ew = (const R *) lm.ew; f.lstart = lm.start;
 }
 
 template <typename R, bool TRL>
@@ -81,9 +58,7 @@ __global__ void __launch_bounds__(kBT) beam_word_stream_advance_kernel(Problem P
     const int N = P.N;
     char *wb = state + (size_t) b * lay.per;
     int *hdr = (int *) (wb + lay.hdr);
-    R *set_v = (R *) (wb + lay.set);                        // [K]
-    int *set_q = (int *) (set_v + K);                       // [K]
-    int *set_h = set_q + K;                                 // [K]
+    R *set_v = (R *) (wb + lay.set);                        // values [K], then product states [K], then LM states [K]
     int pos = hdr[0];
     pos = pos < 0 ? 0 : (pos > max_frames ? max_frames : pos);             // (a state that was reset holds 0 .. max_frames)
     const int want = clamp_len(P.in_len, b, P.T);
@@ -99,13 +74,9 @@ __global__ void __launch_bounds__(kBT) beam_word_stream_advance_kernel(Problem P
     int *bq, *bh, *bs;
     f.bind_work(wb, max_frames, bq, bh, bs);
 
-    if constexpr (TRL)
-        for (int x = tid; x < N * N; x += kBT) trs[x] = tr[(int64_t) (x / N) * P.ts0 + (int64_t) (x % N) * P.ts1];
     int na0 = pos >= 1 ? hdr[1] : 0;
     na0 = na0 < 0 ? 0 : (na0 > K ? K : na0);
-    for (int k = tid; k < na0; k += kBT) { cur_v[k] = set_v[k]; cur_q[k] = set_q[k]; cur_h[k] = set_h[k]; }
-    if (tid == 0) { ctl.na = na0; ctl.n = 0; }
-    __syncthreads();
+    beam_word_load_set<R, TRL>(f, trs, set_v, na0);
 
     for (int t = 0; t < n; ++t) {
         const int gt = pos + t;                             // the frame's index in the utterance
@@ -114,9 +85,7 @@ __global__ void __launch_bounds__(kBT) beam_word_stream_advance_kernel(Problem P
         beam_word_frame<R, TRL>(f, gt == 0, na, in + (int64_t) t * P.is0, P.is2, bq, bh, bs, gt);
     }
 
-    int na = ctl.na;
-    na = na < K ? na : K;
-    for (int k = tid; k < na; k += kBT) { set_v[k] = cur_v[k]; set_q[k] = cur_q[k]; set_h[k] = cur_h[k]; }
+    const int na = beam_word_store_set<R>(f, set_v);
     if (tid == 0) { hdr[1] = na; hdr[0] = pos + n; }
 }
 
@@ -166,7 +135,7 @@ __global__ void __launch_bounds__(kBT) beam_word_stream_result_kernel(GraphArgs 
 
 BeamStreamLayout beam_word_stream_layout(int elem, int max_frames, int K, int cap) {
     BeamStreamLayout l{};
-    size_t off = beam_word_work_bytes(elem, max_frames, 1, K, cap);         // the one-shot decoder's part, at the front
+    size_t off = beam_word_work_layout(elem, max_frames, K, cap, word_table_bits(cap)).end;   // the one-shot decoder's part
     l.hdr = off;  off += 256;
     l.set = off;  off += a256((size_t) K * (elem + 8));
     l.per = off;
@@ -181,12 +150,10 @@ hipError_t launch_beam_word_stream_reset(int elem, const BeamGraphArgs &BG, int 
                                          const unsigned char *mask, hipStream_t stream) {
     const int cap = beam_word_cap(K, BG.max_out, BG.num_start);
     const BeamStreamLayout lay = beam_word_stream_layout(elem, max_frames, K, cap);
-    const size_t C = (size_t) 1 << word_table_bits(cap);
-    const size_t tkey_off = 3 * a256((size_t) max_frames * K * 4), arg_off = tkey_off + a256(C * 8), val_off = arg_off + a256(C * 8);
-    size_t by = (C + 255) / 256;
-    by = by < 1 ? 1 : (by > (size_t) kResetBlocks ? (size_t) kResetBlocks : by);
-    hipLaunchKernelGGL(beam_word_stream_reset_kernel, dim3(B, (unsigned) by), dim3(256), 0, stream, (char *) state, lay, (unsigned) C,
-                       elem, tkey_off, arg_off, val_off, mask);
+    const int tbits = word_table_bits(cap);
+    const size_t C = (size_t) 1 << tbits;
+    hipLaunchKernelGGL(beam_word_stream_reset_kernel, dim3(B, reset_blocks(C)), dim3(256), 0, stream, (char *) state, lay,
+                       beam_word_work_layout(elem, max_frames, K, cap, tbits), (unsigned) C, elem, mask);
     return hipGetLastError();
 }
 
