@@ -520,8 +520,9 @@ int asg_beam_decode_words(asg_ctx *ctx, const asg_problem *p, const asg_token_gr
  * Limits and errors: those of asg_beam_decode_words; a NULL look-ahead, one of another dtype, a NULL or mis-sized array (A' < 0,
  * A' > A, levels outside 1 .. 31 or beyond what A' arcs can fill) or one built for another lexicon / LM shape (S, H):
  * ASG_ERR_INVALID.  Nothing of it is validated on the device.
- * Not there: look-ahead in asg_beam_word_stream_*, asg_beam_word_window_* and the n-best calls -- the prefix result (final = 0)
- * and the three-way score split need rules of their own for the term that has not cancelled yet. */
+ * The two word streams take the look-ahead through asg_beam_word_stream_*_la and asg_beam_word_window_*_la (below, with the rule
+ * for the prefix result).  Not there: look-ahead in the n-best calls -- the three-way score split needs a rule of its own for the
+ * term that has not cancelled yet. */
 typedef struct asg_word_lookahead {
     int64_t S;                     /* automaton states of the lexicon (entries of rlo, rhi) = asg_word_lm.S */
     int64_t H;                     /* history states (entries of la_state) = asg_word_lm.H                  */
@@ -589,8 +590,9 @@ int asg_beam_decode_words_la(asg_ctx *ctx, const asg_problem *p, const asg_token
  * 8192, H, Q <= 2^25, A < 2^31; ASG_ERR_UNSUPPORTED beyond) and those of asg_beam_stream_*: max_frames < 1, Tc < 0, B < 1,
  * beam_size < 1, a negative or NaN beam_threshold, a dtype that is not the graph's and the LM's, a NULL array or output:
  * ASG_ERR_INVALID; a state buffer smaller than asg_beam_word_stream_state_bytes: ASG_ERR_WORKSPACE.  Not here: a loss over
- * pairs, LM look-ahead (n-best over pairs: asg_beam_word_stream_nbest below; the windowed form with a committed prefix:
- * asg_beam_word_window_* further below).  `flags` is reserved (pass 0). */
+ * pairs (n-best over pairs: asg_beam_word_stream_nbest below; the windowed form with a committed prefix:
+ * asg_beam_word_window_* further below; LM look-ahead: asg_beam_word_stream_advance_la behind those).  `flags` is reserved
+ * (pass 0). */
 size_t asg_beam_word_stream_state_bytes(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype, int beam_size,
                                         int64_t max_frames);
 int asg_beam_word_stream_reset(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
@@ -738,7 +740,8 @@ int asg_beam_word_stream_nbest(asg_ctx *ctx, const asg_token_graph_beam *gb, con
  * (beam_size <= 8192 with no clamp to Q, H, Q <= 2^25, A < 2^31, W within asg_beam_window_*'s bound; ASG_ERR_UNSUPPORTED beyond);
  * W < 1, P < 1, P > W, Tc < 0, B < 1, beam_size < 1, a negative or NaN beam_threshold, a dtype that is not the graph's and the
  * LM's, a NULL array or output: ASG_ERR_INVALID; a state buffer smaller than asg_beam_word_window_state_bytes: ASG_ERR_WORKSPACE.
- * Not here: n-best from the window, LM look-ahead, a commit rule that looks at scores.  `flags` is reserved (pass 0). */
+ * Not here: n-best from the window, a commit rule that looks at scores (LM look-ahead: asg_beam_word_window_advance_la below).
+ * `flags` is reserved (pass 0). */
 size_t asg_beam_word_window_state_bytes(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype, int beam_size,
                                         int64_t W, int64_t P);
 int asg_beam_word_window_reset(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
@@ -753,6 +756,54 @@ int asg_beam_word_window_result(asg_ctx *ctx, const asg_token_graph_beam *gb, co
                                 int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words,
                                 int64_t *word_lengths, int64_t *frames, int64_t *committed, int64_t *status, int flags,
                                 void *stream);
+
+/* ---- The two word streams with LM LOOK-AHEAD: asg_beam_word_stream_* and asg_beam_word_window_* over the search of
+ * asg_beam_decode_words_la.  Each entry point is the plain call with `la`, the look-ahead of that call, behind `lm`; everything
+ * the plain call's text says holds with the changes below.  No counterpart in the reference.
+ *   Frames.  Every frame a stream consumes runs the rules of asg_beam_decode_words_la, verbatim: t = 0 (frame 0 of the utterance,
+ *     and only pos == 0), stay, the edge into a node with its dead-end prune, the separator edge.  The stored set holds the values
+ *     as the search ranks them, L(h, state(q)) included.  L reads static arrays and the pair's own (h, q) -- nothing of the frame,
+ *     the chunk or the call -- so a pair kept a call ago expands as one kept a frame ago, separator edge on the first frame of a
+ *     chunk included.
+ *   result, final != 0: the end of asg_beam_decode_words_la: (v + final_w[q]) + ew[h] at the root, (v + final_w[q]) +
+ *     ((a - L(h, state(q))) + ew[h']) in a word-end node, none mid-word.
+ *   result, final == 0, the best PREFIX: end(h, q) = v - L(h, state(q)) -- the estimate that has not cancelled yet is taken
+ *     back.  L is 0 at the root and finite for every kept pair, so the end of a kept pair is finite.  The winner is the largest
+ *     end, the smallest pair on a tie, -0 equal to +0; scores = that end; path, words and tokens follow the plain call's prefix
+ *     rules.  A prefix score thus means what it means without look-ahead: a beam that prunes nothing returns the prefix of the
+ *     plain stream (bit for bit when no sum rounds), and where the two differ pruning is the cause, not the reporting.
+ *   Window.  asg_beam_word_window_advance word for word over the frame above.  Convergence looks at slots only and does not change;
+ *     the forced commit follows "the best prefix pair", which is the rule above (largest v - L); result as above for both values
+ *     of `final`.
+ * REQUIRED PROPERTIES (no tolerance).  asg_beam_word_stream_result_la(final = 1) after any chunking of x[0:L] equals
+ * asg_beam_decode_words_la on x as the plain stream equals asg_beam_decode_words; the properties 1 - 4 of asg_beam_word_window_*
+ * hold with asg_beam_decode_words_la and asg_beam_word_stream_result_la in the place of the plain calls.
+ * Mixing.  A state advanced with a look-ahead must be read, and advanced further, with the same look-ahead, and a state advanced
+ * without one by the plain calls: the stored values do not say which estimate they carry, and NOTHING HERE CAN CHECK IT -- the
+ * caller guarantees it (torch_asg_amd's stream objects bind the look-ahead in their constructor).
+ * State.  asg_beam_word_{stream,window}_state_bytes and _reset serve both forms: the look-ahead adds no byte to a state and
+ * nothing to clear.  One launch per call as the plain calls, no workspace, integer atomics only, capturable.
+ * Limits and errors: the plain call's, and asg_beam_decode_words_la's for `la`: a NULL look-ahead, one of another dtype, a NULL
+ * or mis-sized array, or S / H other than the LM view's: ASG_ERR_INVALID.  Not there: look-ahead in asg_beam_word_stream_nbest. */
+int asg_beam_word_stream_advance_la(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                    const asg_word_lookahead *la, int beam_size, double beam_threshold, int64_t max_frames,
+                                    void *state, size_t state_bytes, int flags, void *stream);
+int asg_beam_word_stream_result_la(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                   const asg_word_lookahead *la, int64_t B, int beam_size, int64_t max_frames, const void *state,
+                                   size_t state_bytes, int final, void *scores, int64_t *path, int64_t *tokens,
+                                   int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words,
+                                   int64_t *word_lengths, int64_t *frames, int64_t *status, int flags, void *stream);
+int asg_beam_word_window_advance_la(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                    const asg_word_lookahead *la, int beam_size, double beam_threshold, int64_t W, int64_t P,
+                                    void *state, size_t state_bytes, int64_t *new_path, int64_t *new_states,
+                                    int64_t *new_lm_states, int64_t *new_tokens, int64_t *new_words, int64_t *new_frames,
+                                    int64_t *new_token_lengths, int64_t *new_word_lengths, int flags, void *stream);
+int asg_beam_word_window_result_la(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                   const asg_word_lookahead *la, int64_t B, int beam_size, int64_t W, int64_t P, const void *state,
+                                   size_t state_bytes, int final, void *scores, int64_t *path, int64_t *tokens,
+                                   int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words,
+                                   int64_t *word_lengths, int64_t *frames, int64_t *committed, int64_t *status, int flags,
+                                   void *stream);
 
 /* ---- Full score of the ASG lattice COMPOSED with a token automaton (the log-semiring counterpart of the decoder above), its
  * gradients, and the automaton's score of each target: the pieces of an ASG loss whose normaliser includes a token-level

@@ -1605,11 +1605,11 @@ class ASGLoss(nn.Module):
                           self.transition.dtype, self.transition.device)
 
     def beam_word_stream(self, lexicon, word_lm, batch_size, max_frames, beam_size=256, beam_threshold=float("inf"), lm_weight=1.0,
-                         word_score=0.0, token_score=0.0):
+                         word_score=0.0, token_score=0.0, lookahead=None):
         """A streaming beam decoder with a lexicon and a word n-gram LM under this module's transition matrix (read again at
         every chunk): see `torch_asg_amd.BeamWordStream`."""
         return BeamWordStream(self.transition, lexicon, word_lm, batch_size, max_frames, beam_size, beam_threshold, lm_weight,
-                              word_score, token_score, self.transition.dtype, self.transition.device)
+                              word_score, token_score, self.transition.dtype, self.transition.device, lookahead)
 
     def beam_window_stream(self, graph, batch_size, window, commit_every=None, beam_size=256, beam_threshold=float("inf"),
                            lm_weight=1.0, token_score=0.0):
@@ -1619,11 +1619,11 @@ class ASGLoss(nn.Module):
                                 token_score, self.transition.dtype, self.transition.device)
 
     def beam_word_window_stream(self, lexicon, word_lm, batch_size, window, commit_every=None, beam_size=256,
-                                beam_threshold=float("inf"), lm_weight=1.0, word_score=0.0, token_score=0.0):
+                                beam_threshold=float("inf"), lm_weight=1.0, word_score=0.0, token_score=0.0, lookahead=None):
         """A streaming beam decoder with a lexicon and a word n-gram LM in bounded memory under this module's transition matrix
         (read again at every chunk): see `torch_asg_amd.BeamWordWindowStream`."""
         return BeamWordWindowStream(self.transition, lexicon, word_lm, batch_size, window, commit_every, beam_size, beam_threshold,
-                                    lm_weight, word_score, token_score, self.transition.dtype, self.transition.device)
+                                    lm_weight, word_score, token_score, self.transition.dtype, self.transition.device, lookahead)
 
     def graph_loss(self, inputs, targets, graph, input_lengths=None, target_lengths=None, lm_weight=1.0, token_score=0.0,
                    max_work_bytes=1 << 30):

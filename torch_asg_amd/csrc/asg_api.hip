@@ -660,13 +660,21 @@ int asg_beam_decode_words(asg_ctx *ctx, const asg_problem *p, const asg_token_gr
 }
 
 // The look-ahead of a (lexicon, LM) pair: its arrays, sized for that pair's S and H.
-static int check_word_lookahead(const asg_problem *p, const asg_word_lm *lm, const asg_word_lookahead *la) {
-    if (!la || la->dtype != p->dtype || la->S != lm->S || la->H != lm->H) return ASG_ERR_INVALID;
+static int check_word_lookahead(int dtype, const asg_word_lm *lm, const asg_word_lookahead *la) {
+    if (!la || la->dtype != dtype || la->S != lm->S || la->H != lm->H) return ASG_ERR_INVALID;
     if (la->A < 0 || la->A > lm->A || la->levels < 1 || la->levels > 31) return ASG_ERR_INVALID;
     if (la->A > 0 && ((int64_t) 1 << (la->levels - 1)) > la->A) return ASG_ERR_INVALID;      // a level no row can fill
     if (!la->rlo || !la->rhi || !la->la_state || !la->krow || !la->dense0) return ASG_ERR_INVALID;
     if (la->A > 0 && (!la->krank || !la->tab)) return ASG_ERR_INVALID;
     return ASG_OK;
+}
+
+static WordLookArgs to_word_look_args(const asg_word_lookahead *la) {
+    WordLookArgs LA{};
+    LA.A = (int) la->A; LA.levels = la->levels;
+    LA.rlo = la->rlo; LA.rhi = la->rhi; LA.la_state = la->la_state; LA.krow = la->krow; LA.krank = la->krank; LA.tab = la->tab;
+    LA.dense0 = la->dense0;
+    return LA;
 }
 
 int asg_beam_decode_words_la(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
@@ -676,7 +684,7 @@ int asg_beam_decode_words_la(asg_ctx *ctx, const asg_problem *p, const asg_token
     (void) ctx; (void) flags;
     int rc = check_beam_words(p, gb, lm, beam_size);
     if (rc) return rc;
-    if ((rc = check_word_lookahead(p, lm, la)) != ASG_OK) return rc;
+    if ((rc = check_word_lookahead(p->dtype, lm, la)) != ASG_OK) return rc;
     if (!(beam_threshold >= 0.0)) return ASG_ERR_INVALID;                  // negative or NaN
     if (!work || !scores || !path || !tokens || !token_lengths || !states || !lm_states || !words || !word_lengths)
         return ASG_ERR_INVALID;
@@ -685,10 +693,7 @@ int asg_beam_decode_words_la(asg_ctx *ctx, const asg_problem *p, const asg_token
     const GraphArgs G = to_graph_args(gb->graph);
     const BeamGraphArgs BG = to_beam_graph_args(gb);
     const WordLmArgs LM = to_word_lm_args(lm);
-    WordLookArgs LA{};
-    LA.A = (int) la->A; LA.levels = la->levels;
-    LA.rlo = la->rlo; LA.rhi = la->rhi; LA.la_state = la->la_state; LA.krow = la->krow; LA.krank = la->krank; LA.tab = la->tab;
-    LA.dense0 = la->dense0;
+    const WordLookArgs LA = to_word_look_args(la);
     long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
     long long *ls = (long long *) lm_states, *wd = (long long *) words, *wl = (long long *) word_lengths;
     return hip_status(ASG_DISPATCH(p, launch_beam_words_la<float>(P, G, BG, LM, LA, beam_size, beam_threshold, work, scores, pa, tk,
@@ -892,13 +897,15 @@ int asg_beam_word_stream_reset(asg_ctx *ctx, const asg_token_graph_beam *gb, con
                                                     (int) max_frames, (int) B, state, mask, (hipStream_t) stream));
 }
 
-int asg_beam_word_stream_advance(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
-                                 int beam_size, double beam_threshold, int64_t max_frames, void *state, size_t state_bytes,
-                                 int flags, void *stream) {
-    (void) ctx; (void) flags;
+// The four calls of the word streams that run the search or read its values, with a look-ahead (`with_la`: la is checked as
+// asg_beam_decode_words_la checks it, behind the LM) or without one: asg_beam_word_{stream,window}_{advance,result}[_la].
+static int beam_word_stream_advance(const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                    const asg_word_lookahead *la, bool with_la, int beam_size, double beam_threshold,
+                                    int64_t max_frames, void *state, size_t state_bytes, void *stream) {
     if (!p) return ASG_ERR_INVALID;
     int rc = check_beam_word_stream(gb, lm, p->B, p->dtype, beam_size, max_frames);
     if (rc) return rc;
+    if (with_la && (rc = check_word_lookahead(p->dtype, lm, la)) != ASG_OK) return rc;
     if (p->T < 0 || p->N != gb->graph->N) return ASG_ERR_INVALID;
     if (p->T > 0 && (rc = check_beam_words(p, gb, lm, beam_size)) != ASG_OK) return rc;
     if (!(beam_threshold >= 0.0)) return ASG_ERR_INVALID;                  // negative or NaN
@@ -909,21 +916,38 @@ int asg_beam_word_stream_advance(asg_ctx *ctx, const asg_problem *p, const asg_t
     const GraphArgs G = to_graph_args(gb->graph);
     const BeamGraphArgs BG = to_beam_graph_args(gb);
     const WordLmArgs LM = to_word_lm_args(lm);
-    return hip_status(ASG_DISPATCH(p, launch_beam_word_stream_advance<float>(P, G, BG, LM, beam_size, beam_threshold,
+    const WordLookArgs LA = with_la ? to_word_look_args(la) : WordLookArgs{};
+    const WordLookArgs *look = with_la ? &LA : nullptr;
+    return hip_status(ASG_DISPATCH(p, launch_beam_word_stream_advance<float>(P, G, BG, LM, look, beam_size, beam_threshold,
                                                                              (int) max_frames, state, (hipStream_t) stream),
-                                   launch_beam_word_stream_advance<double>(P, G, BG, LM, beam_size, beam_threshold,
+                                   launch_beam_word_stream_advance<double>(P, G, BG, LM, look, beam_size, beam_threshold,
                                                                            (int) max_frames, state, (hipStream_t) stream)));
 }
 
-int asg_beam_word_stream_result(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
-                                int64_t max_frames, const void *state, size_t state_bytes, int final, void *scores, int64_t *path,
-                                int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words,
-                                int64_t *word_lengths, int64_t *frames, int64_t *status, int flags, void *stream) {
+int asg_beam_word_stream_advance(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                 int beam_size, double beam_threshold, int64_t max_frames, void *state, size_t state_bytes,
+                                 int flags, void *stream) {
     (void) ctx; (void) flags;
+    return beam_word_stream_advance(p, gb, lm, nullptr, false, beam_size, beam_threshold, max_frames, state, state_bytes, stream);
+}
+
+int asg_beam_word_stream_advance_la(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                    const asg_word_lookahead *la, int beam_size, double beam_threshold, int64_t max_frames,
+                                    void *state, size_t state_bytes, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    return beam_word_stream_advance(p, gb, lm, la, true, beam_size, beam_threshold, max_frames, state, state_bytes, stream);
+}
+
+static int beam_word_stream_result(const asg_token_graph_beam *gb, const asg_word_lm *lm, const asg_word_lookahead *la, bool with_la,
+                                   int64_t B, int beam_size, int64_t max_frames, const void *state, size_t state_bytes, int final,
+                                   void *scores, int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states,
+                                   int64_t *lm_states, int64_t *words, int64_t *word_lengths, int64_t *frames, int64_t *status,
+                                   void *stream) {
     if (!gb || !gb->graph) return ASG_ERR_INVALID;
     const asg_token_graph *g = gb->graph;
     int rc = check_beam_word_stream(gb, lm, B, g->dtype, beam_size, max_frames);
     if (rc) return rc;
+    if (with_la && (rc = check_word_lookahead(g->dtype, lm, la)) != ASG_OK) return rc;
     if (!state || !scores || !path || !tokens || !token_lengths || !states || !lm_states || !words || !word_lengths || !frames ||
         !status)
         return ASG_ERR_INVALID;
@@ -934,12 +958,33 @@ int asg_beam_word_stream_result(asg_ctx *ctx, const asg_token_graph_beam *gb, co
     long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
     long long *ls = (long long *) lm_states, *wd = (long long *) words, *wl = (long long *) word_lengths;
     long long *fr = (long long *) frames, *su = (long long *) status;
-    return hip_status(ASG_DISPATCH(g, launch_beam_word_stream_result<float>(G, BG, LM, beam_size, (int) max_frames, (int) B, state,
-                                                                            final, scores, pa, tk, tl, st, ls, wd, wl, fr, su,
-                                                                            (hipStream_t) stream),
-                                   launch_beam_word_stream_result<double>(G, BG, LM, beam_size, (int) max_frames, (int) B, state,
-                                                                          final, scores, pa, tk, tl, st, ls, wd, wl, fr, su,
-                                                                          (hipStream_t) stream)));
+    const WordLookArgs LA = with_la ? to_word_look_args(la) : WordLookArgs{};
+    const WordLookArgs *look = with_la ? &LA : nullptr;
+    return hip_status(ASG_DISPATCH(g, launch_beam_word_stream_result<float>(G, BG, LM, look, beam_size, (int) max_frames, (int) B,
+                                                                            state, final, scores, pa, tk, tl, st, ls, wd, wl, fr,
+                                                                            su, (hipStream_t) stream),
+                                   launch_beam_word_stream_result<double>(G, BG, LM, look, beam_size, (int) max_frames, (int) B,
+                                                                          state, final, scores, pa, tk, tl, st, ls, wd, wl, fr,
+                                                                          su, (hipStream_t) stream)));
+}
+
+int asg_beam_word_stream_result(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
+                                int64_t max_frames, const void *state, size_t state_bytes, int final, void *scores, int64_t *path,
+                                int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words,
+                                int64_t *word_lengths, int64_t *frames, int64_t *status, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    return beam_word_stream_result(gb, lm, nullptr, false, B, beam_size, max_frames, state, state_bytes, final, scores, path, tokens,
+                                   token_lengths, states, lm_states, words, word_lengths, frames, status, stream);
+}
+
+int asg_beam_word_stream_result_la(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                   const asg_word_lookahead *la, int64_t B, int beam_size, int64_t max_frames, const void *state,
+                                   size_t state_bytes, int final, void *scores, int64_t *path, int64_t *tokens,
+                                   int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words,
+                                   int64_t *word_lengths, int64_t *frames, int64_t *status, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    return beam_word_stream_result(gb, lm, la, true, B, beam_size, max_frames, state, state_bytes, final, scores, path, tokens,
+                                   token_lengths, states, lm_states, words, word_lengths, frames, status, stream);
 }
 
 static int check_beam_word_stream_nbest(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype, int beam_size,
@@ -1099,15 +1144,15 @@ int asg_beam_word_window_reset(asg_ctx *ctx, const asg_token_graph_beam *gb, con
                                                     (int) B, state, mask, (hipStream_t) stream));
 }
 
-int asg_beam_word_window_advance(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
-                                 int beam_size, double beam_threshold, int64_t W, int64_t P, void *state, size_t state_bytes,
-                                 int64_t *new_path, int64_t *new_states, int64_t *new_lm_states, int64_t *new_tokens,
-                                 int64_t *new_words, int64_t *new_frames, int64_t *new_token_lengths, int64_t *new_word_lengths,
-                                 int flags, void *stream) {
-    (void) ctx; (void) flags;
+static int beam_word_window_advance(const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                    const asg_word_lookahead *la, bool with_la, int beam_size, double beam_threshold, int64_t W,
+                                    int64_t P, void *state, size_t state_bytes, int64_t *new_path, int64_t *new_states,
+                                    int64_t *new_lm_states, int64_t *new_tokens, int64_t *new_words, int64_t *new_frames,
+                                    int64_t *new_token_lengths, int64_t *new_word_lengths, void *stream) {
     if (!p) return ASG_ERR_INVALID;
     int rc = check_beam_word_window(gb, lm, p->B, p->dtype, beam_size, W, P);
     if (rc) return rc;
+    if (with_la && (rc = check_word_lookahead(p->dtype, lm, la)) != ASG_OK) return rc;
     if (p->T < 0 || p->N != gb->graph->N) return ASG_ERR_INVALID;
     if (p->T > 0 && (rc = check_beam_words(p, gb, lm, beam_size)) != ASG_OK) return rc;
     if (!(beam_threshold >= 0.0)) return ASG_ERR_INVALID;                  // negative or NaN
@@ -1123,24 +1168,47 @@ int asg_beam_word_window_advance(asg_ctx *ctx, const asg_problem *p, const asg_t
     long long *np = (long long *) new_path, *ns = (long long *) new_states, *nl = (long long *) new_lm_states;
     long long *nt = (long long *) new_tokens, *nw = (long long *) new_words, *nf = (long long *) new_frames;
     long long *tl = (long long *) new_token_lengths, *wl = (long long *) new_word_lengths;
-    return hip_status(ASG_DISPATCH(p, launch_beam_word_window_advance<float>(Pr, G, BG, LM, S, beam_size, beam_threshold, (int) W,
-                                                                             (int) P, state, np, ns, nl, nt, nw, nf, tl, wl,
-                                                                             (hipStream_t) stream),
-                                   launch_beam_word_window_advance<double>(Pr, G, BG, LM, S, beam_size, beam_threshold, (int) W,
-                                                                           (int) P, state, np, ns, nl, nt, nw, nf, tl, wl,
-                                                                           (hipStream_t) stream)));
+    const WordLookArgs LA = with_la ? to_word_look_args(la) : WordLookArgs{};
+    const WordLookArgs *look = with_la ? &LA : nullptr;
+    return hip_status(ASG_DISPATCH(p, launch_beam_word_window_advance<float>(Pr, G, BG, LM, look, S, beam_size, beam_threshold,
+                                                                             (int) W, (int) P, state, np, ns, nl, nt, nw, nf, tl,
+                                                                             wl, (hipStream_t) stream),
+                                   launch_beam_word_window_advance<double>(Pr, G, BG, LM, look, S, beam_size, beam_threshold,
+                                                                           (int) W, (int) P, state, np, ns, nl, nt, nw, nf, tl,
+                                                                           wl, (hipStream_t) stream)));
 }
 
-int asg_beam_word_window_result(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
-                                int64_t W, int64_t P, const void *state, size_t state_bytes, int final, void *scores, int64_t *path,
-                                int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words,
-                                int64_t *word_lengths, int64_t *frames, int64_t *committed, int64_t *status, int flags,
-                                void *stream) {
+int asg_beam_word_window_advance(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                 int beam_size, double beam_threshold, int64_t W, int64_t P, void *state, size_t state_bytes,
+                                 int64_t *new_path, int64_t *new_states, int64_t *new_lm_states, int64_t *new_tokens,
+                                 int64_t *new_words, int64_t *new_frames, int64_t *new_token_lengths, int64_t *new_word_lengths,
+                                 int flags, void *stream) {
     (void) ctx; (void) flags;
+    return beam_word_window_advance(p, gb, lm, nullptr, false, beam_size, beam_threshold, W, P, state, state_bytes, new_path,
+                                    new_states, new_lm_states, new_tokens, new_words, new_frames, new_token_lengths,
+                                    new_word_lengths, stream);
+}
+
+int asg_beam_word_window_advance_la(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                    const asg_word_lookahead *la, int beam_size, double beam_threshold, int64_t W, int64_t P,
+                                    void *state, size_t state_bytes, int64_t *new_path, int64_t *new_states,
+                                    int64_t *new_lm_states, int64_t *new_tokens, int64_t *new_words, int64_t *new_frames,
+                                    int64_t *new_token_lengths, int64_t *new_word_lengths, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    return beam_word_window_advance(p, gb, lm, la, true, beam_size, beam_threshold, W, P, state, state_bytes, new_path, new_states,
+                                    new_lm_states, new_tokens, new_words, new_frames, new_token_lengths, new_word_lengths, stream);
+}
+
+static int beam_word_window_result(const asg_token_graph_beam *gb, const asg_word_lm *lm, const asg_word_lookahead *la, bool with_la,
+                                   int64_t B, int beam_size, int64_t W, int64_t P, const void *state, size_t state_bytes, int final,
+                                   void *scores, int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states,
+                                   int64_t *lm_states, int64_t *words, int64_t *word_lengths, int64_t *frames, int64_t *committed,
+                                   int64_t *status, void *stream) {
     if (!gb || !gb->graph) return ASG_ERR_INVALID;
     const asg_token_graph *g = gb->graph;
     int rc = check_beam_word_window(gb, lm, B, g->dtype, beam_size, W, P);
     if (rc) return rc;
+    if (with_la && (rc = check_word_lookahead(g->dtype, lm, la)) != ASG_OK) return rc;
     if (!state || !scores || !path || !tokens || !token_lengths || !states || !lm_states || !words || !word_lengths || !frames ||
         !committed || !status)
         return ASG_ERR_INVALID;
@@ -1152,12 +1220,35 @@ int asg_beam_word_window_result(asg_ctx *ctx, const asg_token_graph_beam *gb, co
     long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
     long long *ls = (long long *) lm_states, *wd = (long long *) words, *wl = (long long *) word_lengths;
     long long *fr = (long long *) frames, *co = (long long *) committed, *su = (long long *) status;
-    return hip_status(ASG_DISPATCH(g, launch_beam_word_window_result<float>(G, BG, LM, S, beam_size, (int) W, (int) B, state, final,
-                                                                            scores, pa, tk, tl, st, ls, wd, wl, fr, co, su,
+    const WordLookArgs LA = with_la ? to_word_look_args(la) : WordLookArgs{};
+    const WordLookArgs *look = with_la ? &LA : nullptr;
+    return hip_status(ASG_DISPATCH(g, launch_beam_word_window_result<float>(G, BG, LM, look, S, beam_size, (int) W, (int) B, state,
+                                                                            final, scores, pa, tk, tl, st, ls, wd, wl, fr, co, su,
                                                                             (hipStream_t) stream),
-                                   launch_beam_word_window_result<double>(G, BG, LM, S, beam_size, (int) W, (int) B, state, final,
-                                                                          scores, pa, tk, tl, st, ls, wd, wl, fr, co, su,
+                                   launch_beam_word_window_result<double>(G, BG, LM, look, S, beam_size, (int) W, (int) B, state,
+                                                                          final, scores, pa, tk, tl, st, ls, wd, wl, fr, co, su,
                                                                           (hipStream_t) stream)));
+}
+
+int asg_beam_word_window_result(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
+                                int64_t W, int64_t P, const void *state, size_t state_bytes, int final, void *scores, int64_t *path,
+                                int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words,
+                                int64_t *word_lengths, int64_t *frames, int64_t *committed, int64_t *status, int flags,
+                                void *stream) {
+    (void) ctx; (void) flags;
+    return beam_word_window_result(gb, lm, nullptr, false, B, beam_size, W, P, state, state_bytes, final, scores, path, tokens,
+                                   token_lengths, states, lm_states, words, word_lengths, frames, committed, status, stream);
+}
+
+int asg_beam_word_window_result_la(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                   const asg_word_lookahead *la, int64_t B, int beam_size, int64_t W, int64_t P, const void *state,
+                                   size_t state_bytes, int final, void *scores, int64_t *path, int64_t *tokens,
+                                   int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words,
+                                   int64_t *word_lengths, int64_t *frames, int64_t *committed, int64_t *status, int flags,
+                                   void *stream) {
+    (void) ctx; (void) flags;
+    return beam_word_window_result(gb, lm, la, true, B, beam_size, W, P, state, state_bytes, final, scores, path, tokens,
+                                   token_lengths, states, lm_states, words, word_lengths, frames, committed, status, stream);
 }
 
 static int check_beam_loss(const asg_problem *p, const asg_token_graph_beam_loss *gl, int beam_size) {

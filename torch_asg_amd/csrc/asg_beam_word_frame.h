@@ -8,6 +8,7 @@
 // asg_beam_word_window.hip): bind_graph, the clearing loop of their resets (beam_word_reset_tables), the way their advance kernels
 // enter and leave the frame loop (beam_word_load_set, beam_word_store_set), and collapse_words_from for the window's commits.
 #pragma once
+#include <type_traits>
 #include "asg_common.h"
 #include "asg_kernels.h"
 #include "asg_beam_common.h"
@@ -31,8 +32,9 @@ static_assert(kWordCtlOff + sizeof(WordCtl) <= kFixedLds, "control block");
 
 __device__ __forceinline__ int bits_of(int n) { return 32 - __clz(n > 1 ? n - 1 : 1); }   // >= 1
 
-// LM look-ahead (asg_beam_word_la.hip, include/asg_hip.h::asg_beam_decode_words_la) is a compile-time flag of the frame and the
-// end, off by default: every other translation unit compiles the text it compiled before the flag existed.
+// LM look-ahead (asg_beam_word_la.hip, include/asg_hip.h::asg_beam_decode_words_la; the `_la` forms of the two word streams) is a
+// compile-time flag of the frame and the end, off by default: every instantiation without it compiles the text it compiled
+// before the flag existed.
 template <typename R, bool LA>
 struct WordLook {};
 template <typename R>
@@ -176,6 +178,18 @@ struct BeamWordFrame {
     }
     WordLook<R, LA> la;
 };
+
+// What a kernel with the look-ahead flag takes beside the LM: the look-ahead's arrays with it, nothing without.
+struct WordNoLook {};
+template <bool LA>
+using WordLookParam = std::conditional_t<LA, WordLookArgs, WordNoLook>;
+template <typename R>
+__device__ __forceinline__ void bind_look(BeamWordFrame<R, true> &f, const WordLookArgs &la) {
+    f.la.rlo = la.rlo; f.la.rhi = la.rhi; f.la.la_state = la.la_state; f.la.krow = la.krow; f.la.krank = la.krank;
+    f.la.tab = (const R *) la.tab; f.la.dense0 = (const R *) la.dense0; f.la.A = la.A;
+}
+template <typename R>
+__device__ __forceinline__ void bind_look(BeamWordFrame<R, false> &, const WordNoLook &) {}
 
 // The parts of a BeamWordFrame that do not depend on the call: the graph, the LM and the shape of the search.
 template <typename R, bool LA>
@@ -460,8 +474,8 @@ __device__ __forceinline__ void beam_word_frame(const BeamWordFrame<R, LA> &f, b
 // left at `set_v` -- values [K], then product states int32 [K], then LM states int32 [K]: the transitions into LDS when they live
 // there, the na0 stored pairs into f.cur_v / f.cur_q / f.cur_h, the counters.  The whole workgroup calls it; it ends with a
 // __syncthreads.
-template <typename R, bool TRL>
-__device__ __forceinline__ void beam_word_load_set(const BeamWordFrame<R> &f, R *trs, const R *set_v, int na0) {
+template <typename R, bool TRL, bool LA>
+__device__ __forceinline__ void beam_word_load_set(const BeamWordFrame<R, LA> &f, R *trs, const R *set_v, int na0) {
     const int tid = threadIdx.x, N = f.N;
     const int *set_q = (const int *) (set_v + f.K), *set_h = set_q + f.K;
     if constexpr (TRL)
@@ -471,8 +485,8 @@ __device__ __forceinline__ void beam_word_load_set(const BeamWordFrame<R> &f, R 
     __syncthreads();
 }
 // ... and leaves it: the set back to `set_v`; -> its size, for the header.
-template <typename R>
-__device__ __forceinline__ int beam_word_store_set(const BeamWordFrame<R> &f, R *set_v) {
+template <typename R, bool LA>
+__device__ __forceinline__ int beam_word_store_set(const BeamWordFrame<R, LA> &f, R *set_v) {
     int *set_q = (int *) (set_v + f.K), *set_h = set_q + f.K;
     int na = f.ctl->na;
     na = na < f.K ? na : f.K;
@@ -530,8 +544,16 @@ __device__ inline int collapse_words_from(const long long *pb, const long long *
     return base;
 }
 
+// The value of a kept pair (h, q) as a PREFIX score: the value itself -- with look-ahead, the value without the estimate
+// L(h, state(q)) it still carries (0 at the root, finite for every kept pair).
+template <typename R, bool LA>
+__device__ __forceinline__ R word_prefix(const BeamWordFrame<R, LA> &f, int h, int q, R v) {
+    if constexpr (LA) return v - f.look(h, f.state[q]);
+    else return v;
+}
+
 // The best end over a set (sh, sq, sv)[0..na), the smallest pair on a tie (-0 and +0 are one key): with `final` the end of
-// word_end, without it the value itself -- the best PREFIX, which may end mid-word.  Every thread of the workgroup gets (key,
+// word_end, without it word_prefix -- the best PREFIX, which may end mid-word.  Every thread of the workgroup gets (key,
 // slot); key 0: no finite end.  One __syncthreads; f.wctl holds the reduction slots.
 template <typename R, bool LA = false>
 __device__ __forceinline__ void word_best_end(const BeamWordFrame<R, LA> &f, const R *fw, bool final, const int *sh, const int *sq,
@@ -547,7 +569,7 @@ __device__ __forceinline__ void word_best_end(const BeamWordFrame<R, LA> &f, con
     for (int k = tid; k < na; k += kBT) {
         R e;
         int w;
-        if (!final) e = sv[k];
+        if (!final) e = word_prefix<R, LA>(f, sh[k], sq[k], sv[k]);
         else if (!word_end<R, LA>(f, fw, sh[k], sq[k], sv[k], e, w)) continue;
         const U key = e > NINF ? KT::enc(e) : (U) 0;
         const unsigned long long p = f.pair(sh[k], sq[k]);
@@ -586,6 +608,7 @@ __device__ __forceinline__ void word_backtrace(const BeamWordFrame<R, LA> &f, co
         R e = sv[bk];
         int wfin = -1;
         if (final) (void) word_end<R, LA>(f, fw, sh[bk], sq[bk], sv[bk], e, wfin);
+        else e = word_prefix<R, LA>(f, sh[bk], sq[bk], sv[bk]);
         *score = e;
         int k = bk;
         for (int t = len - 1; t >= 0; --t) {

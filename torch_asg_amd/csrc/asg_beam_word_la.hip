@@ -53,8 +53,7 @@ __global__ void __launch_bounds__(kBT) beam_word_la_kernel(Problem P, GraphArgs 
     f.oarc = (const int2 *) bg.oarc; f.ow = (const R *) bg.ow; f.sw = (const R *) g.start_w;
     f.lrow = lm.row; f.lword = lm.word; f.lnext = lm.next; f.lback = lm.backoff; f.wos = lm.word_of_state;
     f.lw = (const R *) lm.lw; f.bw = (const R *) lm.bw; f.ew = (const R *) lm.ew; f.lstart = lm.start;
-    f.la.rlo = la.rlo; f.la.rhi = la.rhi; f.la.la_state = la.la_state; f.la.krow = la.krow; f.la.krank = la.krank;
-    f.la.tab = (const R *) la.tab; f.la.dense0 = (const R *) la.dense0; f.la.A = la.A;
+    bind_look<R>(f, la);
     f.tbits = tbits;
     int *bq, *bh, *bs;
     f.bind_work(work + (size_t) b * per_utt, T, bq, bh, bs);

@@ -23,6 +23,11 @@
 //                                    It only reads the state.
 // What one call writes and the next reads crosses a kernel boundary, so plain stores and loads do; the table keeps the
 // device-scope loads and atomics of the frame body.  Integer atomics only: bit-identical run to run.
+//
+// With LM look-ahead (include/asg_hip.h::asg_beam_word_stream_advance_la) the advance and result kernels are compiled a second
+// time with the frame's look-ahead flag on, as asg_beam_word_la.hip compiles the one-shot kernel: the stored values then carry
+// L(h, state(q)), the end takes it back as the one-shot's does and the best prefix by word_prefix.  `look` reads static arrays
+// and the pair's own (h, q), so the argument above holds as it stands; the state has the same bytes.
 #include "asg_common.h"
 #include "asg_kernels.h"
 #include "asg_beam_common.h"
@@ -41,10 +46,10 @@ __global__ void __launch_bounds__(256) beam_word_stream_reset_kernel(char *state
     if (blockIdx.y == 0 && threadIdx.x < 3) ((int *) (wb + lay.hdr))[threadIdx.x] = 0;      // pos, |A|, overflow
 }
 
-template <typename R, bool TRL>
+template <typename R, bool TRL, bool LA = false>
 __global__ void __launch_bounds__(kBT) beam_word_stream_advance_kernel(Problem P, GraphArgs g, BeamGraphArgs bg, WordLmArgs lm, int K,
                                                                        R theta, int cap, int tbits, int max_frames, char *state,
-                                                                       BeamStreamLayout lay) {
+                                                                       BeamStreamLayout lay, WordLookParam<LA> la) {
     using KT = Key<R>;
     using U = typename KT::U;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -67,35 +72,36 @@ __global__ void __launch_bounds__(kBT) beam_word_stream_advance_kernel(Problem P
     if (n < 1) return;
     const R *in = (const R *) P.inputs + (int64_t) b * P.is1;
     const R *tr = (const R *) P.transition;
-    BeamWordFrame<R> f;
+    BeamWordFrame<R, LA> f;
     f.ctl = &ctl; f.wctl = &wctl; f.cur_v = cur_v; f.cur_q = cur_q; f.cur_h = cur_h; f.trs = trs; f.tr = tr;
     f.ts0 = P.ts0; f.ts1 = P.ts1; f.N = N; f.theta = theta;
     bind_graph<R>(f, g, bg, lm, K, cap, tbits);
+    bind_look<R>(f, la);
     int *bq, *bh, *bs;
     f.bind_work(wb, max_frames, bq, bh, bs);
 
     int na0 = pos >= 1 ? hdr[1] : 0;
     na0 = na0 < 0 ? 0 : (na0 > K ? K : na0);
-    beam_word_load_set<R, TRL>(f, trs, set_v, na0);
+    beam_word_load_set<R, TRL, LA>(f, trs, set_v, na0);
 
     for (int t = 0; t < n; ++t) {
         const int gt = pos + t;                             // the frame's index in the utterance
         const int na = ctl.na;
         if (gt >= 1 && na == 0) break;                      // an empty beam stays empty (pos still advances)
-        beam_word_frame<R, TRL>(f, gt == 0, na, in + (int64_t) t * P.is0, P.is2, bq, bh, bs, gt);
+        beam_word_frame<R, TRL, LA>(f, gt == 0, na, in + (int64_t) t * P.is0, P.is2, bq, bh, bs, gt);
     }
 
-    const int na = beam_word_store_set<R>(f, set_v);
+    const int na = beam_word_store_set<R, LA>(f, set_v);
     if (tid == 0) { hdr[1] = na; hdr[0] = pos + n; }
 }
 
-template <typename R>
+template <typename R, bool LA = false>
 __global__ void __launch_bounds__(kBT) beam_word_stream_result_kernel(GraphArgs g, WordLmArgs lm, int K, int cap, int tbits,
                                                                       int max_frames, const char *state, BeamStreamLayout lay,
                                                                       int final, R *scores, long long *path, long long *tokens,
                                                                       long long *tlen, long long *states, long long *lm_states,
                                                                       long long *words, long long *wlen, long long *frames,
-                                                                      long long *status) {
+                                                                      long long *status, WordLookParam<LA> la) {
     using U = typename Key<R>::U;
     __shared__ WordCtl wctl;
     const int tid = threadIdx.x, b = blockIdx.x, T = max_frames;
@@ -107,10 +113,11 @@ __global__ void __launch_bounds__(kBT) beam_word_stream_result_kernel(GraphArgs 
     const int *set_h = set_q + K;
     long long *pb = path + (int64_t) b * T, *tk = tokens + (int64_t) b * T, *st = states + (int64_t) b * T;
     long long *ls = lm_states + (int64_t) b * T, *wd = words + (int64_t) b * T;
-    BeamWordFrame<R> f;
+    BeamWordFrame<R, LA> f;
     f.ctl = nullptr; f.wctl = &wctl; f.cur_v = nullptr; f.cur_q = nullptr; f.cur_h = nullptr; f.trs = nullptr; f.tr = nullptr;
     f.ts0 = 0; f.ts1 = 0; f.N = 0; f.theta = (R) 0;
     bind_graph<R>(f, g, BeamGraphArgs{}, lm, K, cap, tbits);
+    bind_look<R>(f, la);
     int *bq, *bh, *bs;
     f.bind_work(wb, T, bq, bh, bs);
     int L = hdr[0];
@@ -121,13 +128,13 @@ __global__ void __launch_bounds__(kBT) beam_word_stream_result_kernel(GraphArgs 
     const R *fw = (const R *) g.final_w;
     U bkey;
     int bk;
-    word_best_end<R>(f, fw, final != 0, set_h, set_q, set_v, na, bkey, bk);
+    word_best_end<R, LA>(f, fw, final != 0, set_h, set_q, set_v, na, bkey, bk);
     if (bkey == 0) {                                        // no frame yet, an empty set, or no finite end
         word_no_path(T, pb, tk, st, ls, wd, tlen + b, wlen + b);
         if (tid == 0) scores[b] = NINF;
         return;
     }
-    word_backtrace<R>(f, fw, final != 0, set_h, set_q, set_v, bk, bq, bh, bs, L, T, scores + b, pb, tk, st, ls, wd, tlen + b,
+    word_backtrace<R, LA>(f, fw, final != 0, set_h, set_q, set_v, bk, bq, bh, bs, L, T, scores + b, pb, tk, st, ls, wd, tlen + b,
                       wlen + b);
 }
 
@@ -158,8 +165,9 @@ hipError_t launch_beam_word_stream_reset(int elem, const BeamGraphArgs &BG, int 
 }
 
 template <typename R>
-hipError_t launch_beam_word_stream_advance(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int K,
-                                           double theta, int max_frames, void *state, hipStream_t stream) {
+hipError_t launch_beam_word_stream_advance(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                                           const WordLookArgs *LA, int K, double theta, int max_frames, void *state,
+                                           hipStream_t stream) {
     const int N = P.N;
     const int cap = beam_word_cap(K, BG.max_out, BG.num_start);
     const int tbits = word_table_bits(cap);
@@ -168,40 +176,47 @@ hipError_t launch_beam_word_stream_advance(const Problem &P, const GraphArgs &G,
     const size_t beam = kFixedLds + (size_t) K * (sizeof(R) + 8);
     const bool trl = beam + (size_t) N * N * sizeof(R) <= kLdsMax;
     const size_t dyn = beam + (trl ? (size_t) N * N * sizeof(R) : 0);
-#define ASG_BEAM_WORD_STREAM(TRL)                                                                                            \
+#define ASG_BEAM_WORD_STREAM(TRL, LAF, LOOK)                                                                                 \
     do {                                                                                                                     \
-        const void *fn = (const void *) beam_word_stream_advance_kernel<R, TRL>;                                            \
+        const void *fn = (const void *) beam_word_stream_advance_kernel<R, TRL, LAF>;                                       \
         if (dyn > 64 * 1024) (void) hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) dyn);       \
-        hipLaunchKernelGGL((beam_word_stream_advance_kernel<R, TRL>), dim3(P.B), dim3(kBT), dyn, stream, P, G, BG, LM, K,   \
-                           (R) theta, cap, tbits, max_frames, (char *) state, lay);                                          \
+        hipLaunchKernelGGL((beam_word_stream_advance_kernel<R, TRL, LAF>), dim3(P.B), dim3(kBT), dyn, stream, P, G, BG, LM, \
+                           K, (R) theta, cap, tbits, max_frames, (char *) state, lay, LOOK);                                 \
     } while (0)
-    if (trl) ASG_BEAM_WORD_STREAM(true); else ASG_BEAM_WORD_STREAM(false);
+    if (LA) { if (trl) ASG_BEAM_WORD_STREAM(true, true, *LA); else ASG_BEAM_WORD_STREAM(false, true, *LA); }
+    else if (trl) ASG_BEAM_WORD_STREAM(true, false, WordNoLook{}); else ASG_BEAM_WORD_STREAM(false, false, WordNoLook{});
 #undef ASG_BEAM_WORD_STREAM
     return hipGetLastError();
 }
 template hipError_t launch_beam_word_stream_advance<float>(const Problem &, const GraphArgs &, const BeamGraphArgs &,
-                                                           const WordLmArgs &, int, double, int, void *, hipStream_t);
+                                                           const WordLmArgs &, const WordLookArgs *, int, double, int, void *,
+                                                           hipStream_t);
 template hipError_t launch_beam_word_stream_advance<double>(const Problem &, const GraphArgs &, const BeamGraphArgs &,
-                                                            const WordLmArgs &, int, double, int, void *, hipStream_t);
+                                                            const WordLmArgs &, const WordLookArgs *, int, double, int, void *,
+                                                            hipStream_t);
 
 template <typename R>
-hipError_t launch_beam_word_stream_result(const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int K, int max_frames,
-                                          int B, const void *state, int final, void *scores, long long *path, long long *tokens,
+hipError_t launch_beam_word_stream_result(const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                                          const WordLookArgs *LA, int K, int max_frames, int B, const void *state, int final,
+                                          void *scores, long long *path, long long *tokens,
                                           long long *tlen, long long *states, long long *lm_states, long long *words,
                                           long long *wlen, long long *frames, long long *status, hipStream_t stream) {
     const int cap = beam_word_cap(K, BG.max_out, BG.num_start);
     const BeamStreamLayout lay = beam_word_stream_layout(sizeof(R), max_frames, K, cap);
-    hipLaunchKernelGGL((beam_word_stream_result_kernel<R>), dim3(B), dim3(kBT), 0, stream, G, LM, K, cap, word_table_bits(cap),
-                       max_frames, (const char *) state, lay, final, (R *) scores, path, tokens, tlen, states, lm_states, words,
-                       wlen, frames, status);
+#define ASG_BEAM_WORD_STREAM_RESULT(LAF, LOOK)                                                                               \
+    hipLaunchKernelGGL((beam_word_stream_result_kernel<R, LAF>), dim3(B), dim3(kBT), 0, stream, G, LM, K, cap,               \
+                       word_table_bits(cap), max_frames, (const char *) state, lay, final, (R *) scores, path, tokens, tlen, \
+                       states, lm_states, words, wlen, frames, status, LOOK)
+    if (LA) ASG_BEAM_WORD_STREAM_RESULT(true, *LA); else ASG_BEAM_WORD_STREAM_RESULT(false, WordNoLook{});
+#undef ASG_BEAM_WORD_STREAM_RESULT
     return hipGetLastError();
 }
-template hipError_t launch_beam_word_stream_result<float>(const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &, int, int, int,
-                                                          const void *, int, void *, long long *, long long *, long long *,
+template hipError_t launch_beam_word_stream_result<float>(const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &,
+                                                          const WordLookArgs *, int, int, int, const void *, int, void *, long long *, long long *, long long *,
                                                           long long *, long long *, long long *, long long *, long long *,
                                                           long long *, hipStream_t);
-template hipError_t launch_beam_word_stream_result<double>(const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &, int, int, int,
-                                                           const void *, int, void *, long long *, long long *, long long *,
+template hipError_t launch_beam_word_stream_result<double>(const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &,
+                                                           const WordLookArgs *, int, int, int, const void *, int, void *, long long *, long long *, long long *,
                                                            long long *, long long *, long long *, long long *, long long *,
                                                            long long *, hipStream_t);
 

@@ -26,6 +26,10 @@
 // the separator behind another label, and the label and state before the first frame of a segment are the carries, so an edge
 // that straddles two commits or two calls gives its word once.  This unit keeps its header, its control blocks and its call of
 // word_best_end.
+//
+// With LM look-ahead (include/asg_hip.h::asg_beam_word_window_advance_la) the advance and result kernels are compiled a second
+// time with the frame's look-ahead flag on.  Convergence looks at slots only and is the same text; the forced commit follows the
+// best prefix pair, which word_best_end then ranks by value minus look-ahead (word_prefix); the state has the same bytes.
 #include "asg_common.h"
 #include "asg_kernels.h"
 #include "asg_beam_common.h"
@@ -80,14 +84,14 @@ __global__ void __launch_bounds__(256) beam_word_window_reset_kernel(char *state
     }
 }
 
-template <typename R, bool TRL>
+template <typename R, bool TRL, bool LA = false>
 __global__ void __launch_bounds__(kBT) beam_word_window_advance_kernel(Problem P, GraphArgs g, BeamGraphArgs bg, WordLmArgs lm, int S,
                                                                        int K, R theta, int cap, int tbits, int W, int CP,
                                                                        char *state, BeamStreamLayout lay, long long *new_path,
                                                                        long long *new_states, long long *new_lm_states,
                                                                        long long *new_tokens, long long *new_words,
                                                                        long long *new_frames, long long *new_tlen,
-                                                                       long long *new_wlen) {
+                                                                       long long *new_wlen, WordLookParam<LA> la) {
     using KT = Key<R>;
     using U = typename KT::U;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -127,15 +131,16 @@ __global__ void __launch_bounds__(kBT) beam_word_window_advance_kernel(Problem P
     if (n >= 1) {
         const R *in = (const R *) P.inputs + (int64_t) b * P.is1;
         const R *tr = (const R *) P.transition;
-        BeamWordFrame<R> f;
+        BeamWordFrame<R, LA> f;
         f.ctl = &ctl; f.wctl = &wctl; f.cur_v = cur_v; f.cur_q = cur_q; f.cur_h = cur_h; f.trs = trs; f.tr = tr;
         f.ts0 = P.ts0; f.ts1 = P.ts1; f.N = N; f.theta = theta;
         bind_graph<R>(f, g, bg, lm, K, cap, tbits);
+        bind_look<R>(f, la);
         int *bq, *bh, *bs;
         f.bind_work(wb, W, bq, bh, bs);
         if (tid == 0) { o.bq = bq; o.bh = bh; o.bs = bs; }
 
-        beam_word_load_set<R, TRL>(f, trs, set_v, na0);
+        beam_word_load_set<R, TRL, LA>(f, trs, set_v, na0);
 
         int row = (int) (pos % W), ph = (int) (pos % CP);   // the next frame's row, and pos mod P; both kept by stepping
         for (int t = 0; t < n; ++t) {
@@ -143,7 +148,7 @@ __global__ void __launch_bounds__(kBT) beam_word_window_advance_kernel(Problem P
             int na = ctl.na;
             if (gt >= 1 && na == 0) break;                  // an empty beam stays empty (and commits nothing more)
             const int fr = row;
-            beam_word_frame<R, TRL>(f, gt == 0, na, in + (int64_t) t * P.is0, P.is2, bq, bh, bs, fr);
+            beam_word_frame<R, TRL, LA>(f, gt == 0, na, in + (int64_t) t * P.is0, P.is2, bq, bh, bs, fr);
             const long long p1 = gt + 1;                    // pos, counting this frame
             row = row + 1 == W ? 0 : row + 1;
             ph = ph + 1 == CP ? 0 : ph + 1;
@@ -164,7 +169,7 @@ __global__ void __launch_bounds__(kBT) beam_word_window_advance_kernel(Problem P
             if (F > 0) {
                 U bkey;
                 int bk;
-                word_best_end<R>(f, nullptr, false, cur_h, cur_q, cur_v, na, bkey, bk);      // the best prefix
+                word_best_end<R, LA>(f, nullptr, false, cur_h, cur_q, cur_v, na, bkey, bk);  // the best prefix
                 __syncthreads();                            // (the reduction slots are read before anything reuses them)
                 if (bkey != 0 && bk >= 0) {
                     if (tid == 0) wc.status |= 1;
@@ -172,7 +177,7 @@ __global__ void __launch_bounds__(kBT) beam_word_window_advance_kernel(Problem P
                 }
             }
         }
-        const int na = beam_word_store_set<R>(f, set_v);
+        const int na = beam_word_store_set<R, LA>(f, set_v);
         if (tid == 0) hdr->na = na;
     }
     __syncthreads();
@@ -188,13 +193,13 @@ __global__ void __launch_bounds__(kBT) beam_word_window_advance_kernel(Problem P
     }
 }
 
-template <typename R>
+template <typename R, bool LA = false>
 __global__ void __launch_bounds__(kBT) beam_word_window_result_kernel(GraphArgs g, WordLmArgs lm, int S, int K, int cap, int tbits,
                                                                       int W, const char *state, BeamStreamLayout lay, int final,
                                                                       R *scores, long long *path, long long *tokens, long long *tlen,
                                                                       long long *states, long long *lm_states, long long *words,
                                                                       long long *wlen, long long *frames, long long *committed,
-                                                                      long long *status) {
+                                                                      long long *status, WordLookParam<LA> la) {
     using U = typename Key<R>::U;
     __shared__ WordCtl wctl;
     __shared__ int wfin_s;
@@ -207,10 +212,11 @@ __global__ void __launch_bounds__(kBT) beam_word_window_result_kernel(GraphArgs 
     const int *set_h = set_q + K;
     long long *pb = path + (int64_t) b * W, *tk = tokens + (int64_t) b * W, *st = states + (int64_t) b * W;
     long long *ls = lm_states + (int64_t) b * W, *wd = words + (int64_t) b * W;
-    BeamWordFrame<R> f;
+    BeamWordFrame<R, LA> f;
     f.ctl = nullptr; f.wctl = &wctl; f.cur_v = nullptr; f.cur_q = nullptr; f.cur_h = nullptr; f.trs = nullptr; f.tr = nullptr;
     f.ts0 = 0; f.ts1 = 0; f.N = 0; f.theta = (R) 0;
     bind_graph<R>(f, g, BeamGraphArgs{}, lm, K, cap, tbits);
+    bind_look<R>(f, la);
     int *bq, *bh, *bs;
     f.bind_work(wb, W, bq, bh, bs);
     long long pos = hdr->pos, base = hdr->base;
@@ -224,7 +230,7 @@ __global__ void __launch_bounds__(kBT) beam_word_window_result_kernel(GraphArgs 
     const R *fw = (const R *) g.final_w;
     U bkey;
     int bk;
-    word_best_end<R>(f, fw, final != 0, set_h, set_q, set_v, na, bkey, bk);
+    word_best_end<R, LA>(f, fw, final != 0, set_h, set_q, set_v, na, bkey, bk);
     if (bkey == 0 || bk < 0) {                              // no frame yet, an empty set, or no finite end
         word_no_path(W, pb, tk, st, ls, wd, tlen + b, wlen + b);
         if (tid == 0) scores[b] = NINF;
@@ -236,7 +242,8 @@ __global__ void __launch_bounds__(kBT) beam_word_window_result_kernel(GraphArgs 
     if (tid == 0) {
         R e = set_v[bk];
         int wfin = -1;
-        if (final) (void) word_end<R>(f, fw, set_h[bk], set_q[bk], set_v[bk], e, wfin);
+        if (final) (void) word_end<R, LA>(f, fw, set_h[bk], set_q[bk], set_v[bk], e, wfin);
+        else e = word_prefix<R, LA>(f, set_h[bk], set_q[bk], set_v[bk]);
         scores[b] = e;
         wfin_s = wfin;
         int k = bk, r = (int) ((pos + W - 1) % W);          // the row of frame pos - 1
@@ -295,8 +302,9 @@ hipError_t launch_beam_word_window_reset(int elem, const BeamGraphArgs &BG, int 
 }
 
 template <typename R>
-hipError_t launch_beam_word_window_advance(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int S,
-                                           int K, double theta, int W, int CP, void *state, long long *new_path,
+hipError_t launch_beam_word_window_advance(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                                           const WordLookArgs *LA, int S, int K, double theta, int W, int CP, void *state,
+                                           long long *new_path,
                                            long long *new_states, long long *new_lm_states, long long *new_tokens,
                                            long long *new_words, long long *new_frames, long long *new_tlen, long long *new_wlen,
                                            hipStream_t stream) {
@@ -308,46 +316,50 @@ hipError_t launch_beam_word_window_advance(const Problem &P, const GraphArgs &G,
     const size_t beam = kFixedLds + mark_bytes(K) + (size_t) K * (sizeof(R) + 8);
     const bool trl = beam + (size_t) N * N * sizeof(R) <= kLdsMax;
     const size_t dyn = beam + (trl ? (size_t) N * N * sizeof(R) : 0);
-#define ASG_BEAM_WORD_WINDOW(TRL)                                                                                              \
+#define ASG_BEAM_WORD_WINDOW(TRL, LAF, LOOK)                                                                                   \
     do {                                                                                                                       \
-        const void *fn = (const void *) beam_word_window_advance_kernel<R, TRL>;                                              \
+        const void *fn = (const void *) beam_word_window_advance_kernel<R, TRL, LAF>;                                         \
         if (dyn > 64 * 1024) (void) hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) dyn);         \
-        hipLaunchKernelGGL((beam_word_window_advance_kernel<R, TRL>), dim3(P.B), dim3(kBT), dyn, stream, P, G, BG, LM, S, K,  \
-                           (R) theta, cap, tbits, W, CP, (char *) state, lay, new_path, new_states, new_lm_states, new_tokens, \
-                           new_words, new_frames, new_tlen, new_wlen);                                                         \
+        hipLaunchKernelGGL((beam_word_window_advance_kernel<R, TRL, LAF>), dim3(P.B), dim3(kBT), dyn, stream, P, G, BG, LM,   \
+                           S, K, (R) theta, cap, tbits, W, CP, (char *) state, lay, new_path, new_states, new_lm_states,       \
+                           new_tokens, new_words, new_frames, new_tlen, new_wlen, LOOK);                                       \
     } while (0)
-    if (trl) ASG_BEAM_WORD_WINDOW(true); else ASG_BEAM_WORD_WINDOW(false);
+    if (LA) { if (trl) ASG_BEAM_WORD_WINDOW(true, true, *LA); else ASG_BEAM_WORD_WINDOW(false, true, *LA); }
+    else if (trl) ASG_BEAM_WORD_WINDOW(true, false, WordNoLook{}); else ASG_BEAM_WORD_WINDOW(false, false, WordNoLook{});
 #undef ASG_BEAM_WORD_WINDOW
     return hipGetLastError();
 }
 template hipError_t launch_beam_word_window_advance<float>(const Problem &, const GraphArgs &, const BeamGraphArgs &,
-                                                           const WordLmArgs &, int, int, double, int, int, void *, long long *,
+                                                           const WordLmArgs &, const WordLookArgs *, int, int, double, int, int, void *, long long *,
                                                            long long *, long long *, long long *, long long *, long long *,
                                                            long long *, long long *, hipStream_t);
 template hipError_t launch_beam_word_window_advance<double>(const Problem &, const GraphArgs &, const BeamGraphArgs &,
-                                                            const WordLmArgs &, int, int, double, int, int, void *, long long *,
+                                                            const WordLmArgs &, const WordLookArgs *, int, int, double, int, int, void *, long long *,
                                                             long long *, long long *, long long *, long long *, long long *,
                                                             long long *, long long *, hipStream_t);
 
 template <typename R>
-hipError_t launch_beam_word_window_result(const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int S, int K, int W,
-                                          int B, const void *state, int final, void *scores, long long *path, long long *tokens,
+hipError_t launch_beam_word_window_result(const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                                          const WordLookArgs *LA, int S, int K, int W, int B, const void *state, int final, void *scores, long long *path, long long *tokens,
                                           long long *tlen, long long *states, long long *lm_states, long long *words,
                                           long long *wlen, long long *frames, long long *committed, long long *status,
                                           hipStream_t stream) {
     const int cap = beam_word_cap(K, BG.max_out, BG.num_start);
     const BeamStreamLayout lay = beam_word_window_layout(sizeof(R), W, K, cap);
-    hipLaunchKernelGGL((beam_word_window_result_kernel<R>), dim3(B), dim3(kBT), 0, stream, G, LM, S, K, cap, word_table_bits(cap), W,
-                       (const char *) state, lay, final, (R *) scores, path, tokens, tlen, states, lm_states, words, wlen, frames,
-                       committed, status);
+#define ASG_BEAM_WORD_WINDOW_RESULT(LAF, LOOK)                                                                                 \
+    hipLaunchKernelGGL((beam_word_window_result_kernel<R, LAF>), dim3(B), dim3(kBT), 0, stream, G, LM, S, K, cap,              \
+                       word_table_bits(cap), W, (const char *) state, lay, final, (R *) scores, path, tokens, tlen, states,    \
+                       lm_states, words, wlen, frames, committed, status, LOOK)
+    if (LA) ASG_BEAM_WORD_WINDOW_RESULT(true, *LA); else ASG_BEAM_WORD_WINDOW_RESULT(false, WordNoLook{});
+#undef ASG_BEAM_WORD_WINDOW_RESULT
     return hipGetLastError();
 }
-template hipError_t launch_beam_word_window_result<float>(const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &, int, int, int,
-                                                          int, const void *, int, void *, long long *, long long *, long long *,
+template hipError_t launch_beam_word_window_result<float>(const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &,
+                                                          const WordLookArgs *, int, int, int, int, const void *, int, void *, long long *, long long *, long long *,
                                                           long long *, long long *, long long *, long long *, long long *,
                                                           long long *, long long *, hipStream_t);
-template hipError_t launch_beam_word_window_result<double>(const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &, int, int, int,
-                                                           int, const void *, int, void *, long long *, long long *, long long *,
+template hipError_t launch_beam_word_window_result<double>(const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &,
+                                                           const WordLookArgs *, int, int, int, int, const void *, int, void *, long long *, long long *, long long *,
                                                            long long *, long long *, long long *, long long *, long long *,
                                                            long long *, long long *, hipStream_t);
 

@@ -253,17 +253,20 @@ hipError_t launch_beam_words_la(const Problem &P, const GraphArgs &G, const Beam
 
 // ---- The search over pairs carried across chunks of frames (asg_beam_word_stream.hip): asg_beam_word_stream_*.  One slot of the
 // state: the word decoder's own layout for T = max_frames at the front, then hdr (int32 pos, |A|, overflow) and the stored set
-// (values [K], then int32 product states [K], then int32 LM states [K]).  K = beam_size, cap = beam_word_cap(..).
+// (values [K], then int32 product states [K], then int32 LM states [K]).  K = beam_size, cap = beam_word_cap(..).  LA: the
+// look-ahead of asg_beam_word_stream_*_la, nullptr without one (the state, its size and its reset do not depend on it).
 BeamStreamLayout beam_word_stream_layout(int elem, int max_frames, int K, int cap);
 size_t beam_word_stream_state_bytes(int elem, int max_frames, int B, int K, int cap);
 hipError_t launch_beam_word_stream_reset(int elem, const BeamGraphArgs &BG, int K, int max_frames, int B, void *state,
                                          const unsigned char *mask, hipStream_t stream);
 template <typename R>
-hipError_t launch_beam_word_stream_advance(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int K,
-                                           double theta, int max_frames, void *state, hipStream_t stream);
+hipError_t launch_beam_word_stream_advance(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                                           const WordLookArgs *LA, int K, double theta, int max_frames, void *state,
+                                           hipStream_t stream);
 template <typename R>
-hipError_t launch_beam_word_stream_result(const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int K, int max_frames,
-                                          int B, const void *state, int final, void *scores, long long *path, long long *tokens,
+hipError_t launch_beam_word_stream_result(const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                                          const WordLookArgs *LA, int K, int max_frames, int B, const void *state, int final,
+                                          void *scores, long long *path, long long *tokens,
                                           long long *tlen, long long *states, long long *lm_states, long long *words,
                                           long long *wlen, long long *frames, long long *status, hipStream_t stream);
 
@@ -315,7 +318,7 @@ hipError_t launch_beam_window_result(const GraphArgs &G, const BeamGraphArgs &BG
 // ---- The search over pairs in bounded memory (asg_beam_word_window.hip): asg_beam_word_window_*.  One slot of the state has the
 // layout of a word stream of W frames -- bq / bh / bs are rings, frame u in row u mod W -- with the header int64 pos, int64 base,
 // int32 |A|, carry, carry_state, status.  K = beam_size, cap = beam_word_cap(..), CP the commit period, S the number of states of
-// the lexicon automaton (word_of_state has S entries).
+// the lexicon automaton (word_of_state has S entries).  LA: the look-ahead of asg_beam_word_window_*_la, nullptr without one.
 BeamStreamLayout beam_word_window_layout(int elem, int W, int K, int cap);
 size_t beam_word_window_state_bytes(int elem, int W, int B, int K, int cap);
 hipError_t launch_beam_word_window_reset(int elem, const BeamGraphArgs &BG, int K, int W, int B, void *state,
@@ -323,14 +326,16 @@ hipError_t launch_beam_word_window_reset(int elem, const BeamGraphArgs &BG, int 
 // new_path / new_states / new_lm_states / new_tokens / new_words [B][W + P.T], new_frames / new_tlen / new_wlen [B]: every element
 // is written
 template <typename R>
-hipError_t launch_beam_word_window_advance(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int S,
-                                           int K, double theta, int W, int CP, void *state, long long *new_path,
+hipError_t launch_beam_word_window_advance(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                                           const WordLookArgs *LA, int S, int K, double theta, int W, int CP, void *state,
+                                           long long *new_path,
                                            long long *new_states, long long *new_lm_states, long long *new_tokens,
                                            long long *new_words, long long *new_frames, long long *new_tlen, long long *new_wlen,
                                            hipStream_t stream);
 template <typename R>
-hipError_t launch_beam_word_window_result(const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int S, int K, int W,
-                                          int B, const void *state, int final, void *scores, long long *path, long long *tokens,
+hipError_t launch_beam_word_window_result(const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                                          const WordLookArgs *LA, int S, int K, int W, int B, const void *state, int final,
+                                          void *scores, long long *path, long long *tokens,
                                           long long *tlen, long long *states, long long *lm_states, long long *words,
                                           long long *wlen, long long *frames, long long *committed, long long *status,
                                           hipStream_t stream);

@@ -10,6 +10,8 @@ where `views` is the automaton ((g,), or (g, w) with a word LM) and `shape` what
 (window, commit_every)).  `_Stream` owns everything that follows from that: the constructor checks, the state, `reset`, the
 chunk preamble, the host's bound and the launch of `advance`, the outputs of `result`.  A subclass names its entry points
 (`_API`), checks and compiles its automaton, checks its shape, and says what `result` (and `advance`, if anything) returns.
+A word stream with LM look-ahead (`lookahead=`) calls the `_la` forms of `_advance` and `_result`, which take one more view
+behind the automaton's (`_look`); state size and reset are the plain calls'.
 The backend is looked up at every call (`asg.native()`), so that what replaces it in `torch_asg_amd.asg` is what the streams
 use.
 """
@@ -26,6 +28,8 @@ class _Stream:
     _API = None                  # "asg_beam_stream": the prefix of _state_bytes, _reset, _advance and _result
     _WIDE = _NARROW = 0          # the number of [B, frames] and of [B] int64 outputs of _result
     max_frames = None            # set by a subclass whose state holds a fixed number of frames: the host's bound of `advance`
+    lookahead = None             # set by a word stream: its WordLookahead, or None
+    _look = ()                   # ... and the view of it that `_advance_la` and `_result_la` take behind `_views`
 
     def __init__(self, transition, automaton, batch_size, shape, beam_size, beam_threshold, dtype, device):
         _asg._check_beam(beam_size, beam_threshold)
@@ -45,8 +49,9 @@ class _Stream:
         be = _asg.native()
         L = _lib.lib()
         # (entry point, its name for error messages) of the three calls
+        la = "" if self.lookahead is None else "_la"
         self._c_reset, self._c_advance, self._c_result = ((getattr(L, self._API + s), self._API + s)
-                                                          for s in ("_reset", "_advance", "_result"))
+                                                          for s in ("_reset", "_advance" + la, "_result" + la))
         with be._guard(device):
             self._compiled = self._compile()                   # (the views point into it)
             self._views = tuple(ctypes.byref(v) for v in self._compiled[0])
@@ -113,9 +118,9 @@ class _Stream:
         with be._guard(self.device):
             outs = self._commit_outputs(Tc)
             p, keep = be._problem(chunk, transition, None, chunk_lengths, None)
-            _lib.check(advance(None, ctypes.byref(p), *self._views, self.beam_size, float(self.beam_threshold), *self._shape,
-                               self._state.data_ptr(), self._state.numel(), *[t.data_ptr() for t in outs] if outs else outs, 0,
-                               be._stream(self.device)), what)
+            _lib.check(advance(None, ctypes.byref(p), *self._views, *self._look, self.beam_size, float(self.beam_threshold),
+                               *self._shape, self._state.data_ptr(), self._state.numel(),
+                               *[t.data_ptr() for t in outs] if outs else outs, 0, be._stream(self.device)), what)
         self._fed += Tc
         return outs
 
@@ -135,8 +140,8 @@ class _Stream:
             narrow = torch.empty(self._NARROW, B, dtype=torch.int64, device=dev)
             res = self._outputs(scores, wide, narrow)
             result, what = self._c_result
-            _lib.check(result(None, *self._views, B, self.beam_size, *self._shape, self._state.data_ptr(), self._state.numel(),
-                              1 if final else 0, *[t.data_ptr() for t in res], 0, be._stream(dev)), what)
+            _lib.check(result(None, *self._views, *self._look, B, self.beam_size, *self._shape, self._state.data_ptr(),
+                              self._state.numel(), 1 if final else 0, *[t.data_ptr() for t in res], 0, be._stream(dev)), what)
         return res
 
 
@@ -232,14 +237,19 @@ class BeamWordStream(_Stream):
     candidate a frame can have, per slot; nothing is sized by the vocabulary or the LM).  Lexicon and LM are compiled in the
     constructor; `advance`, `result` and `reset` are one kernel launch each, copy nothing and do not synchronise, so they can be
     captured in a graph and replayed with new chunk contents and lengths.  `result_nbest` gives the n best hypotheses or
-    prefixes with their score split.  The windowed form with a committed prefix is `BeamWordWindowStream`.  Not here: a loss
-    over pairs, LM look-ahead.
+    prefixes with their score split.  The windowed form with a committed prefix is `BeamWordWindowStream`.
+
+    `lookahead`, a `WordLookahead(lexicon, word_lm, order)`, makes every frame `beam_decode_words(..., lookahead=)`'s
+    (include/asg_hip.h::asg_beam_word_stream_advance_la): `result(final=True)` then equals that call, bit for bit, for any
+    chunking, and a prefix result takes the estimate that has not cancelled yet back (see `result`).  The stream is bound to
+    its look-ahead for life -- the values in the state carry it -- and the state has the same size with or without.
+    Not here: a loss over pairs; `result_nbest` of a stream with a look-ahead.
     """
     _API, _WIDE, _NARROW = "asg_beam_word_stream", 5, 4
 
     def __init__(self, transition, lexicon, word_lm, batch_size, max_frames, beam_size=256, beam_threshold=float("inf"),
-                 lm_weight=1.0, word_score=0.0, token_score=0.0, dtype=torch.float32, device=None):
-        self.lm_weight, self.word_score, self.token_score = lm_weight, word_score, token_score
+                 lm_weight=1.0, word_score=0.0, token_score=0.0, dtype=torch.float32, device=None, lookahead=None):
+        self.lm_weight, self.word_score, self.token_score, self.lookahead = lm_weight, word_score, token_score, lookahead
         self._nbest_work = {}                                  # nbest -> the scratch of result_nbest (not part of the state)
         super().__init__(transition, (lexicon, word_lm), batch_size, (max_frames,), beam_size, beam_threshold, dtype, device)
         (self.max_frames,) = self._shape
@@ -247,6 +257,8 @@ class BeamWordStream(_Stream):
     def _check_automaton(self, lexicon, word_lm):
         from . import wordlm as _wordlm
         _wordlm.check_words(lexicon, word_lm)
+        if self.lookahead is not None:
+            _wordlm.check_lookahead(self.lookahead, lexicon, word_lm)
         self.lexicon, self.word_lm = lexicon, word_lm
         return lexicon.graph
 
@@ -254,6 +266,11 @@ class BeamWordStream(_Stream):
         from . import wordlm as _wordlm
         g, w, keep = _wordlm.abi_words(self.lexicon, self.word_lm, self.device, self.dtype, self.lm_weight, self.word_score,
                                        self.token_score)
+        if self.lookahead is not None:                         # with the stream's weights, through the look-ahead's own cache
+            la_dev = self.lookahead.compile(self.device, self.dtype, self.lm_weight, self.word_score)
+            la = _wordlm.abi_lookahead(la_dev)
+            self._look = (ctypes.byref(la),)
+            keep = (keep, la, la_dev)
         return (g, w), keep
 
     def reset(self, mask=None):
@@ -276,7 +293,9 @@ class BeamWordStream(_Stream):
         final=True is the end of `beam_decode_words` (final weight, the LM's end of the sentence, after one more LM step for a
         path that ends in a word-end node, whose word is appended; a path that ends mid-word does not count).  final=False is the
         best prefix hypothesis, the largest value without any end term: it may end mid-word, and `words` holds the words whose
-        separator the path has passed.  A slot without frames, with an empty beam or without a finite score: -inf, -1, 0."""
+        separator the path has passed.  With a look-ahead the value of a prefix is taken without the estimate it still carries
+        (v - L(h, node)), so a prefix score means what it means without look-ahead and a beam that prunes nothing returns the
+        plain stream's prefix.  A slot without frames, with an empty beam or without a finite score: -inf, -1, 0."""
         return self._result(final)
 
     def result_nbest(self, nbest, final=False, return_alignments=False):
@@ -289,7 +308,11 @@ class BeamWordStream(_Stream):
         the end of the sentence, no final word.  Row 0 equals `result(final)`.  The state keeps no emissions, so there is no
         emission_scores: scores - (graph_scores + lm_scores) is it up to rounding.  One launch; the scratch it needs is allocated
         once per `nbest` and kept on the stream, so a captured call replays.  nbest < 1 raises ValueError, nbest > 8192
-        RuntimeError."""
+        RuntimeError.  A stream built with a look-ahead raises NotImplementedError: the three-way split has no rule yet for
+        the estimate that has not cancelled."""
+        if self.lookahead is not None:
+            raise NotImplementedError("torch_asg_amd: result_nbest of a stream with a look-ahead is not there (the score split "
+                                      "needs a rule for the look-ahead term); build the stream without `lookahead`")
         if int(nbest) < 1:
             raise ValueError("torch_asg_amd: nbest must be >= 1, got %d" % int(nbest))
         nbest = min(int(nbest), (1 << 31) - 1)
@@ -436,16 +459,19 @@ class BeamWordWindowStream(_Stream):
     The state is one device buffer of about window * beam_size * 12 bytes of back-pointers plus 60-80 bytes per candidate a
     frame can have, per slot, whatever the length of the utterance; `result` walks at most `window` frames.  `advance`, `result`
     and `reset` are one kernel launch each, copy nothing and do not synchronise, so they can be captured and replayed.  The other
-    arguments are `BeamWordStream`'s (`dtype` None: the transition's); there is no bound on the number of frames and no
-    n-best.
+    arguments are `BeamWordStream`'s (`dtype` None: the transition's), `lookahead` included
+    (include/asg_hip.h::asg_beam_word_window_advance_la: the forced commit then follows the best prefix by value minus
+    look-ahead, everything above holds with `beam_decode_words(..., lookahead=)` in the place of `beam_decode_words`); there is
+    no bound on the number of frames and no n-best.
     """
     _API, _WIDE, _NARROW = "asg_beam_word_window", 5, 5
     _check_automaton, _compile = BeamWordStream._check_automaton, BeamWordStream._compile      # the automaton is BeamWordStream's,
     _check_shape = BeamWindowStream._check_shape                                               # the shape BeamWindowStream's
 
     def __init__(self, transition, lexicon, word_lm, batch_size, window, commit_every=None, beam_size=256,
-                 beam_threshold=float("inf"), lm_weight=1.0, word_score=0.0, token_score=0.0, dtype=None, device=None):
-        self.lm_weight, self.word_score, self.token_score = lm_weight, word_score, token_score
+                 beam_threshold=float("inf"), lm_weight=1.0, word_score=0.0, token_score=0.0, dtype=None, device=None,
+                 lookahead=None):
+        self.lm_weight, self.word_score, self.token_score, self.lookahead = lm_weight, word_score, token_score, lookahead
         super().__init__(transition, (lexicon, word_lm), batch_size, (window, commit_every), beam_size, beam_threshold,
                          transition.dtype if dtype is None else dtype, device)
         self.window, self.commit_every = self._shape
