@@ -475,6 +475,69 @@ int asg_beam_decode_words(asg_ctx *ctx, const asg_problem *p, const asg_token_gr
                           int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words, int64_t *word_lengths,
                           int flags, void *stream);
 
+/* ---- BEAM-PRUNED full score over the PAIRS of asg_beam_decode_words, and its gradients: asg_beam_graph_full_forward / _backward
+ * with the lattice state widened from a product state to a pair (h, q) -- a normaliser Z_K whose work per frame follows the beam
+ * and never H * Q, so a criterion can be trained against what the word decoder searches.  No counterpart in the reference.  Per
+ * utterance b, len = clamp(input_lengths[b], 0, T); lexicon graph, folding, start_w, final_w, ow, the LM's folded lw / bw / ew,
+ * step(h, w) and PAIR ORDER exactly as in asg_beam_decode_words:
+ *   1. Kept sets.  A_t, t = 0 .. len-1, are exactly the sets of pairs asg_beam_decode_words keeps for the same emissions,
+ *      transition, lexicon, LM, beam_size, beam_threshold, computed in the dtype of the problem (the same device code runs).  They
+ *      are a discrete function of the inputs and constants to the gradient.  No look-ahead.
+ *   2. Forced pairs (only when p->targets is given).  y = targets[b][:clamp(target_lengths[b], 0, S)] with consecutive equal
+ *      labels merged, n = |y|.  The lexicon automaton is walked along y from the start with h = start; on a separator out of a
+ *      word-end node (h, a) = step(h, word of the node).  This gives p_k = (h_k, q_k), k = 1 .. n, and
+ *      F_t = { p_k : k-1 <= t and n-k <= len-1-t }.  Every F_t is empty when the target has no alignment (target length 0 or
+ *      > len), holds a label outside [0, N), a lexicon arc is missing, an LM step is rejected, the path ends mid-word, or the end
+ *      final_w[q_n] + endw(p_n) is -inf.  The forced pairs do NOT feed back into the search of step 1.
+ *   3. Lattice.  U_t = A_t united with F_t, ascending in pair order, no duplicates.  For p' = (h', q') with label i':
+ *        alpha[0][p'] = start_w[q'] + I[0][i']                                         for the start pairs (start, q') in U_0
+ *        alpha[t][p'] = lse over p = (h, q) in U_{t-1} with an edge p -> p' of
+ *                          ((alpha[t-1][p] + tr[i'][i]) + w(p -> p')) + I[t][i']                                for p' in U_t
+ *      The edges are the search's own candidates: the stay (w = 0, the same pair); a lexicon edge e with a label other than the
+ *      separator (h' = h, w = ow[e]); a separator edge out of a word-end node ((h', a) = step(h, word of the node), w = ow[e] + a;
+ *      a rejected step is no edge).
+ *        scores[b] = Z_K = lse over p in U_{len-1} of (alpha[len-1][p] + final_w[q]) + endw(p)
+ *      with endw as in asg_beam_decode_words: ew[h] at the root, a + ew[h'] after one more step in a word-end node, no end
+ *      mid-word.  Every lse is max-then-sum; the maximum and the sum of a target are integer reductions (the order-preserving key
+ *      of a value; exp(c - max) as a 64-bit fixed-point number with 48 fractional bits), so no order of arrival changes a bit.
+ *      All candidates -inf gives -inf, never NaN; len == 0 or an empty lattice: -inf.  beta, the label posteriors and the
+ *      expected (i, j) counts are the mirror image over the same U_t; grad_inputs [T,B,N] (contiguous, every element written, zero
+ *      rows at t >= len) and grad_transition [N,N] as asg_beam_graph_full_backward.  Lexicon, LM and their weights are constants.
+ *   4. Z_K >= asg_beam_decode_words' score without targets.  With targets every alignment of the target runs through the F_t, so
+ *      Z_K - (aligned score + asg_words_target_scores) >= 0 for ANY beam.  With weights and emissions such that the search's sums
+ *      do not round, beam_size at least the number of reachable pairs and beam_threshold = +inf, Z_K equals
+ *      asg_graph_full_forward's score on the static composition of the lexicon with the LM.
+ * No float atomics (label posteriors and (i, j) counts as in asg_beam_graph_full_backward; utterances added in ascending order):
+ * bit-identical run to run.  ASG_FLAG_BEAM_LOSS_ACCUMULATE (backward) continues grad_transition from what it holds, so a batch
+ * processed in consecutive groups gives the bits of one call.  Every output and all scratch that is read is written by kernels (no
+ * memset, no host synchronisation): both calls can be captured.
+ * K = beam_size; nf = min(S, T) when p->targets is given, else 0; M = K + nf; e = 4 / 8.  Every part rounded up to 256 bytes:
+ *   work:    asg_beam_words_full_work_bytes(p, gb, lm, beam_size, store) =
+ *            B * (asg_beam_decode_words' bytes per utterance + 2*T*4 + 256 + nf*8 + T*M*8 + (store ? T : 2)*M*e)
+ *   scratch: asg_beam_words_full_scratch_bytes(p, gb, lm, beam_size) = B * (2*M*e + N*N*8)
+ * No term in H, V, A or Q (the search has none either).
+ * The forward keeps alpha for the backward with ASG_FLAG_GRAPH_LOSS_KEEP_ALPHA; the backward takes the same problem (targets
+ * included: they size the layout), the same beam_size, that work buffer and the scores of that forward.
+ * Limits (ASG_ERR_UNSUPPORTED beyond): those of asg_beam_decode_words (beam_size <= 8192, ...), N <= 1024, min(S, T) <= 2048 with
+ * targets, T <= 2^20, and M <= (160 KiB - 256) / (16 + e) = 8179 (float32) / 6816 (float64): a frame's lattice set stays in LDS
+ * with a 64-bit pair, a 64-bit sum and a maximum per member.  beam_size < 1, a negative or NaN beam_threshold, and everything
+ * asg_beam_decode_words refuses: ASG_ERR_INVALID.  float32 and float64.
+ * asg_words_target_scores: out[b] = the lexicon + LM score of targets[b] with consecutive equal labels merged -- start_w, then
+ * w(p -> p') of every edge of the walk of step 2, then final_w[q_n] + endw(p_n) -- or -inf where step 2 rejects it (input
+ * lengths are not looked at; an empty target is -inf).  The pair twin of asg_graph_target_scores. */
+size_t asg_beam_words_full_work_bytes(const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm, int beam_size,
+                                      int store);
+size_t asg_beam_words_full_scratch_bytes(const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm, int beam_size);
+int asg_beam_words_full_forward(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                int beam_size, double beam_threshold, void *work, size_t work_bytes, void *scores, int flags,
+                                void *stream);
+int asg_beam_words_full_backward(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                 int beam_size, const void *work, size_t work_bytes, const void *scores, const void *grad_scores,
+                                 void *grad_inputs, void *grad_transition, void *scratch, size_t scratch_bytes, int flags,
+                                 void *stream);
+int asg_words_target_scores(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm, void *out,
+                            void *stream);
+
 /* ---- asg_beam_decode_words with LM LOOK-AHEAD: inside a word, a pair's value also carries the best LM score that any word below
  * its trie node can still get after the pair's history, so that a narrow beam ranks partial words by more than acoustics.  The
  * term telescopes: every edge adds the difference between the look-ahead of its two ends, the separator edge takes back what the
@@ -589,10 +652,10 @@ int asg_beam_decode_words_la(asg_ctx *ctx, const asg_problem *p, const asg_token
  * atomics only: bit-identical run to run.  Limits and errors: those of asg_beam_decode_words with T = max_frames (beam_size <=
  * 8192, H, Q <= 2^25, A < 2^31; ASG_ERR_UNSUPPORTED beyond) and those of asg_beam_stream_*: max_frames < 1, Tc < 0, B < 1,
  * beam_size < 1, a negative or NaN beam_threshold, a dtype that is not the graph's and the LM's, a NULL array or output:
- * ASG_ERR_INVALID; a state buffer smaller than asg_beam_word_stream_state_bytes: ASG_ERR_WORKSPACE.  Not here: a loss over
- * pairs (n-best over pairs: asg_beam_word_stream_nbest below; the windowed form with a committed prefix:
- * asg_beam_word_window_* further below; LM look-ahead: asg_beam_word_stream_advance_la behind those).  `flags` is reserved
- * (pass 0). */
+ * ASG_ERR_INVALID; a state buffer smaller than asg_beam_word_stream_state_bytes: ASG_ERR_WORKSPACE.  Not here: a loss over a
+ * stream (the one-shot loss over pairs: asg_beam_words_full_forward above; n-best over pairs: asg_beam_word_stream_nbest
+ * below; the windowed form with a committed prefix: asg_beam_word_window_* further below; LM look-ahead:
+ * asg_beam_word_stream_advance_la behind those).  `flags` is reserved (pass 0). */
 size_t asg_beam_word_stream_state_bytes(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype, int beam_size,
                                         int64_t max_frames);
 int asg_beam_word_stream_reset(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,

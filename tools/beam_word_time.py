@@ -26,7 +26,7 @@ DEV = "cuda:0"
 SHAPES = [(400, 64, 40, 20000, 50), (400, 64, 40, 2000, 50)]
 
 
-def make_lexicon(N, words, seed=0):
+def make_spellings(N, words, seed=0):
     rng = np.random.default_rng(seed)
     seen, out = set(), []
     while len(out) < words:
@@ -36,7 +36,11 @@ def make_lexicon(N, words, seed=0):
             continue
         seen.add(w.tobytes())
         out.append(w.tolist())
-    return torch_asg_amd.Lexicon(out, N, N - 1)
+    return out
+
+
+def make_lexicon(N, words, seed=0):
+    return torch_asg_amd.Lexicon(make_spellings(N, words, seed), N, N - 1)
 
 
 def make_bigram(V, successors, seed=0):

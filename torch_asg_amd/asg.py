@@ -761,6 +761,94 @@ class HipBackend:
                        "asg_graph_target_scores")
         return out
 
+    def _word_loss_args(self, inputs, transition, lexicon, word_lm, input_lengths, targets, target_lengths, weights):
+        """Checks shared by the pair-loss entry points -> (the lexicon's asg_token_graph_beam view, the asg_word_lm view, the
+        compiled dicts they point into), through the caches of `Lexicon.compile_words` and `WordLM.compile`."""
+        from . import wordlm as _wordlm
+        _wordlm.check_words(lexicon, word_lm)
+        self._check_graph_inputs(inputs, transition, lexicon.graph, input_lengths, targets, target_lengths)
+        return _wordlm.abi_words(lexicon, word_lm, inputs.device, inputs.dtype, *weights)
+
+    def beam_words_full_forward(self, inputs, transition, lexicon, word_lm, input_lengths, beam_size, beam_threshold=float("inf"),
+                                lm_weight=1.0, word_score=0.0, token_score=0.0, targets=None, target_lengths=None, store=False,
+                                max_work_bytes=1 << 30):
+        """Beam-pruned full score over the pairs `beam_decode_words` keeps -> (scores[B], saved); see
+        include/asg_hip.h::asg_beam_words_full_forward.  Grouped and saved as `beam_graph_full_forward` does."""
+        L = _lib.lib()
+        dev = inputs.device
+        B = inputs.shape[1]
+        beam_size, beam_threshold = min(int(beam_size), (1 << 31) - 1), float(beam_threshold)
+        with self._guard(dev):
+            g, w, keep = self._word_loss_args(inputs, transition, lexicon, word_lm, input_lengths, targets, target_lengths,
+                                              (lm_weight, word_score, token_score))
+            p, targets, input_lengths, target_lengths = self._device_problem(inputs, transition, targets, input_lengths,
+                                                                             target_lengths)
+            fl = _lib.FLAG_GRAPH_LOSS_KEEP_ALPHA if store else 0
+
+            def call(work, nbytes, scores, stream):
+                return L.asg_beam_words_full_forward(None, ctypes.byref(p), ctypes.byref(g), ctypes.byref(w), beam_size,
+                                                     beam_threshold, work, nbytes, scores, fl, stream)
+            groups = self._groups(
+                p, B, max_work_bytes,
+                lambda: L.asg_beam_words_full_work_bytes(ctypes.byref(p), ctypes.byref(g), ctypes.byref(w), beam_size, int(store)),
+                keep[0]["Q"], lambda: _lib.check(call(None, 0, None, None), "asg_beam_words_full_forward"),
+                inputs, targets, input_lengths, target_lengths, store=store)
+            scores = torch.empty(B, dtype=inputs.dtype, device=dev)
+            stream = self._stream(dev)
+            saved = []
+            for b0, b1, work in groups:
+                _lib.check(call(work.data_ptr(), work.numel(), scores[b0:].data_ptr(), stream), "asg_beam_words_full_forward")
+                saved.append((b0, b1, work))
+        return scores, (saved if store else None)
+
+    def beam_words_full_backward(self, saved, scores, grad_scores, inputs, transition, lexicon, word_lm, input_lengths, beam_size,
+                                 lm_weight=1.0, word_score=0.0, token_score=0.0, targets=None, target_lengths=None):
+        """(grad_transition[N,N], grad_inputs[T,B,N]) of sum_b grad_scores[b] * scores[b] from beam_words_full_forward's saved
+        lattices.  The groups add into one grad_transition in batch order, so the result does not depend on the grouping."""
+        L = _lib.lib()
+        dev = inputs.device
+        T, B, N = inputs.shape
+        beam_size = min(int(beam_size), (1 << 31) - 1)
+        with self._guard(dev):
+            g, w, keep = self._word_loss_args(inputs, transition, lexicon, word_lm, input_lengths, targets, target_lengths,
+                                              (lm_weight, word_score, token_score))
+            p, targets, input_lengths, target_lengths = self._device_problem(inputs, transition, targets, input_lengths,
+                                                                             target_lengths)
+            gs = grad_scores.to(inputs.dtype).contiguous()
+            gin = torch.empty(T, B, N, dtype=inputs.dtype, device=dev)
+            gtr = torch.empty(N, N, dtype=inputs.dtype, device=dev)
+            stream = self._stream(dev)
+            groups = self._groups(p, B, None, None, None, None, inputs, targets, input_lengths, target_lengths, saved=saved)
+            for n, (b0, b1, work) in enumerate(groups):
+                nb = b1 - b0
+                scratch = self._buf(L.asg_beam_words_full_scratch_bytes(ctypes.byref(p), ctypes.byref(g), ctypes.byref(w),
+                                                                        beam_size), dev)
+                gin_g = gin if nb == B else torch.empty(T, nb, N, dtype=inputs.dtype, device=dev)
+                _lib.check(L.asg_beam_words_full_backward(None, ctypes.byref(p), ctypes.byref(g), ctypes.byref(w), beam_size,
+                                                          work.data_ptr(), work.numel(), scores[b0:].data_ptr(),
+                                                          gs[b0:].data_ptr(), gin_g.data_ptr(), gtr.data_ptr(),
+                                                          scratch.data_ptr(), scratch.numel(),
+                                                          _lib.FLAG_BEAM_LOSS_ACCUMULATE if n else 0, stream),
+                           "asg_beam_words_full_backward")
+                if nb != B:
+                    gin[:, b0:b1].copy_(gin_g)
+        return gtr, gin
+
+    def words_target_scores(self, inputs, transition, lexicon, word_lm, targets, target_lengths, lm_weight=1.0, word_score=0.0,
+                            token_score=0.0):
+        """[B]: the lexicon + LM score of every target sequence (consecutive repeats merged), end terms included, -inf where
+        either rejects it; see include/asg_hip.h::asg_words_target_scores."""
+        L = _lib.lib()
+        dev = inputs.device
+        with self._guard(dev):
+            g, w, keep = self._word_loss_args(inputs, transition, lexicon, word_lm, None, targets, target_lengths,
+                                              (lm_weight, word_score, token_score))
+            p, keep_p = self._problem(inputs, transition, targets, None, target_lengths)
+            out = torch.empty(inputs.shape[1], dtype=inputs.dtype, device=dev)
+            _lib.check(L.asg_words_target_scores(None, ctypes.byref(p), ctypes.byref(g), ctypes.byref(w), out.data_ptr(),
+                                                 self._stream(dev)), "asg_words_target_scores")
+        return out
+
     def backward(self, state, grad_full, grad_aligned, inputs, targets, transition, input_lengths, target_lengths,
                  flags=0):
         L = _lib.lib()
@@ -1257,23 +1345,32 @@ def _guarded_targets(targets, target_lengths, N):
 
 
 def _graph_loss(inputs, targets, transition, graph, input_lengths, target_lengths, lm_weight, token_score, max_work_bytes,
-                reduction, beam=None, weights=None):
+                reduction, beam=None, weights=None, words=None):
     """What the graph losses share.  [B] losses full - (FAC + A(collapse(target))), then `weights(inputs, input_lengths,
     target_lengths)` (None: none) and the reduction; `full` is the exact normaliser (`GraphFullScore`), or with beam =
-    (beam_size, beam_threshold) the beam-pruned one with the target forced into the lattice (`BeamGraphFullScore`).  A loss is
+    (beam_size, beam_threshold) the beam-pruned one with the target forced into the lattice (`BeamGraphFullScore`).  With
+    words = (word_lm, word_score), `graph` is a `Lexicon`, the normaliser runs over the pairs of `beam_decode_words`
+    (`BeamWordsFullScore`; `beam` is required) and A is the lexicon + LM score of the target (`words_target_scores`).  A loss is
     +inf (never NaN) where the target has no alignment, the automaton rejects it or it holds a label outside [0, N)
     (`_guarded_targets`), and then only the normaliser's posterior reaches the gradients.  Defaults, S > T truncation and
     widening as `ASGLoss.forward`."""
     inputs = _widen(inputs, transition)
     targets, input_lengths, target_lengths = ASGLoss._canonical(inputs, targets, input_lengths, target_lengths)
-    if beam is None:
+    if words is not None:
+        full = BeamWordsFullScore.apply(inputs, transition, graph, words[0], input_lengths, *beam, lm_weight, words[1],
+                                        token_score, targets, target_lengths, max_work_bytes)
+    elif beam is None:
         full = GraphFullScore.apply(inputs, transition, graph, input_lengths, lm_weight, token_score, max_work_bytes, 0)
     else:
         full = BeamGraphFullScore.apply(inputs, transition, graph, input_lengths, *beam, lm_weight, token_score, targets,
                                         target_lengths, max_work_bytes)
     with torch.no_grad():
-        walk = native().graph_target_scores(inputs.detach(), transition.detach(), graph, targets, target_lengths, lm_weight,
-                                            token_score)
+        if words is not None:
+            walk = native().words_target_scores(inputs.detach(), transition.detach(), graph, words[0], targets, target_lengths,
+                                                lm_weight, words[1], token_score)
+        else:
+            walk = native().graph_target_scores(inputs.detach(), transition.detach(), graph, targets, target_lengths, lm_weight,
+                                                token_score)
     safe, inside = _guarded_targets(targets, target_lengths, inputs.shape[2])
     aligned = FAC.apply(transition, inputs, safe, input_lengths, target_lengths) + walk
     aligned = torch.where(inside.to(aligned.device), aligned, torch.full_like(aligned, float("-inf")))
@@ -1359,6 +1456,63 @@ def beam_graph_asg_loss(inputs, targets, transition, graph, input_lengths=None, 
     _check_beam(beam_size, beam_threshold)
     return _graph_loss(inputs, targets, transition, graph, input_lengths, target_lengths, lm_weight, token_score, max_work_bytes,
                        reduction, (beam_size, beam_threshold))
+
+
+class BeamWordsFullScore(torch.autograd.Function):
+    """Beam-pruned full score of the ASG lattice composed with a lexicon and a word LM over the pairs `beam_decode_words`
+    keeps, [B] (asg_beam_words_full_forward / _backward).  The kept sets are constants of the gradient; alpha is stored only
+    when a gradient w.r.t. inputs or transition is needed.  Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, inputs, transition, lexicon, word_lm, input_lengths, beam_size, beam_threshold, lm_weight, word_score,
+                token_score, targets, target_lengths, max_work_bytes):
+        store = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
+        scores, saved = native().beam_words_full_forward(inputs, transition, lexicon, word_lm, input_lengths, beam_size,
+                                                         beam_threshold, lm_weight, word_score, token_score, targets,
+                                                         target_lengths, store, max_work_bytes)
+        ctx.save_for_backward(inputs, transition, input_lengths, targets, target_lengths, scores)
+        ctx.saved, ctx.words, ctx.args = saved, (lexicon, word_lm), (beam_size, lm_weight, word_score, token_score)
+        return scores
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        inputs, transition, input_lengths, targets, target_lengths, scores = ctx.saved_tensors
+        K, lw, ws, ts = ctx.args
+        gtr, gin = native().beam_words_full_backward(ctx.saved, scores, grad, inputs, transition, *ctx.words, input_lengths, K,
+                                                     lw, ws, ts, targets, target_lengths)
+        return (gin, gtr) + (None,) * 11
+
+
+def beam_words_full_score(inputs, transition, lexicon, word_lm, input_lengths=None, beam_size=256, beam_threshold=float("inf"),
+                          lm_weight=1.0, word_score=0.0, token_score=0.0, targets=None, target_lengths=None,
+                          max_work_bytes=1 << 30):
+    """`beam_graph_full_score` over the pairs (LM history, lexicon product state) that `beam_decode_words`' search keeps: the
+    logsumexp over the label paths whose pair stays, at every frame, inside the kept set of that frame (the sets of
+    `beam_decode_words` for the same arguments without look-ahead, bit for bit) -- and, when `targets` is given, inside those
+    sets united with the pairs every alignment of the target passes through (include/asg_hip.h::asg_beam_words_full_forward).
+    A path's score is `beam_decode_words`': emissions, transitions, the lexicon's weights, the LM walk of every word and the
+    end of the sentence.  Work and memory follow beam_size, never the sizes of the lexicon or the LM.  Differentiable w.r.t.
+    `inputs` and `transition` with the sets held constant; without targets >= `beam_decode_words`' score.  Bit-identical run to
+    run and for any `max_work_bytes`.  targets / target_lengths are taken as given (`beam_words_asg_loss` applies defaults and
+    truncation)."""
+    _check_beam(beam_size, beam_threshold)
+    return BeamWordsFullScore.apply(_widen(inputs, transition), transition, lexicon, word_lm, input_lengths, beam_size,
+                                    beam_threshold, lm_weight, word_score, token_score, targets, target_lengths, max_work_bytes)
+
+
+def beam_words_asg_loss(inputs, targets, transition, lexicon, word_lm, input_lengths=None, target_lengths=None, beam_size=256,
+                        beam_threshold=float("inf"), lm_weight=1.0, word_score=0.0, token_score=0.0, reduction='none',
+                        max_work_bytes=1 << 30):
+    """ASG loss against what `beam_decode_words` searches: loss[b] = beam_words_full_score[b] - (S_aligned[b] + the lexicon + LM
+    score of targets[b] with consecutive repeats merged), the target forced into the beam's lattice, so every finite loss is
+    >= 0 (up to rounding) for any beam.  `targets` are token labels that spell words of the lexicon, each followed by the
+    separator or ending the sequence.  +inf (never NaN) where the target cannot be aligned, the lexicon or the LM rejects it,
+    it ends mid-word, or it holds a label outside [0, N) within its length; then only the normaliser's posterior reaches the
+    gradients.  Defaults and S > T truncation as `ASGLoss.forward`; reduction 'none' (default), 'sum' or 'mean'."""
+    _check_beam(beam_size, beam_threshold)
+    return _graph_loss(inputs, targets, transition, lexicon, input_lengths, target_lengths, lm_weight, token_score,
+                       max_work_bytes, reduction, (beam_size, beam_threshold), None, (word_lm, word_score))
 
 
 class FAC(torch.autograd.Function):
@@ -1638,6 +1792,14 @@ class ASGLoss(nn.Module):
         _check_beam(beam_size, beam_threshold)
         return _graph_loss(inputs, targets, self.transition, graph, input_lengths, target_lengths, lm_weight, token_score,
                            max_work_bytes, self.reduction, (beam_size, beam_threshold), self._utterance_weights)
+
+    def beam_word_loss(self, inputs, targets, lexicon, word_lm, input_lengths=None, target_lengths=None, lm_weight=1.0,
+                       word_score=0.0, token_score=0.0, max_work_bytes=1 << 30, beam_size=256, beam_threshold=float("inf")):
+        """`torch_asg_amd.beam_words_asg_loss` under this module's transition matrix, reduction and scale_mode."""
+        _check_beam(beam_size, beam_threshold)
+        return _graph_loss(inputs, targets, self.transition, lexicon, input_lengths, target_lengths, lm_weight, token_score,
+                           max_work_bytes, self.reduction, (beam_size, beam_threshold), self._utterance_weights,
+                           (word_lm, word_score))
 
     @staticmethod
     def _canonical(inputs, targets, input_lengths, target_lengths):

@@ -1325,6 +1325,86 @@ int asg_beam_graph_full_backward(asg_ctx *ctx, const asg_problem *p, const asg_t
                                           (hipStream_t) stream)));
 }
 
+static int check_beam_words_loss(const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm, int beam_size) {
+    int rc = check_beam_words(p, gb, lm, beam_size);
+    if (rc) return rc;
+    if (p->targets && p->S < 1) return ASG_ERR_INVALID;
+    if (p->N > kBeamLossMaxN || p->T > (1 << 20)) return ASG_ERR_UNSUPPORTED;
+    const int64_t nf = p->targets ? (p->S < p->T ? p->S : p->T) : 0;
+    if (nf > kBeamLossMaxForced) return ASG_ERR_UNSUPPORTED;
+    if (!beam_word_loss_fits(p->dtype == ASG_DTYPE_F64 ? 8 : 4, beam_size + (int) nf, (int) p->N)) return ASG_ERR_UNSUPPORTED;
+    return ASG_OK;
+}
+
+size_t asg_beam_words_full_work_bytes(const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm, int beam_size,
+                                      int store) {
+    if (check_beam_words_loss(p, gb, lm, beam_size) != ASG_OK) return 0;
+    return beam_word_loss_work_bytes(p->dtype == ASG_DTYPE_F64 ? 8 : 4, (int) p->T, (int) p->B, beam_size,
+                                     beam_word_cap(beam_size, gb->max_out, (int) gb->num_start), beam_loss_nf(p), store != 0);
+}
+
+size_t asg_beam_words_full_scratch_bytes(const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm, int beam_size) {
+    if (check_beam_words_loss(p, gb, lm, beam_size) != ASG_OK) return 0;
+    return (size_t) p->B * beam_word_loss_scratch_per(p->dtype == ASG_DTYPE_F64 ? 8 : 4, beam_size + beam_loss_nf(p), (int) p->N);
+}
+
+int asg_beam_words_full_forward(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                int beam_size, double beam_threshold, void *work, size_t work_bytes, void *scores, int flags,
+                                void *stream) {
+    (void) ctx;
+    int rc = check_beam_words_loss(p, gb, lm, beam_size);
+    if (rc) return rc;
+    if (!(beam_threshold >= 0.0)) return ASG_ERR_INVALID;                  // negative or NaN
+    if (!work || !scores) return ASG_ERR_INVALID;
+    const bool store = (flags & ASG_FLAG_GRAPH_LOSS_KEEP_ALPHA) != 0;
+    if (work_bytes < asg_beam_words_full_work_bytes(p, gb, lm, beam_size, store)) return ASG_ERR_WORKSPACE;
+    const Problem P = to_problem(p);
+    const GraphArgs G = to_graph_args(gb->graph);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    const WordLmArgs LM = to_word_lm_args(lm);
+    return hip_status(ASG_DISPATCH(p,
+        launch_beam_word_loss_forward<float>(P, G, BG, LM, beam_size, beam_threshold, store, work, scores, (hipStream_t) stream),
+        launch_beam_word_loss_forward<double>(P, G, BG, LM, beam_size, beam_threshold, store, work, scores, (hipStream_t) stream)));
+}
+
+int asg_beam_words_full_backward(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                 int beam_size, const void *work, size_t work_bytes, const void *scores, const void *grad_scores,
+                                 void *grad_inputs, void *grad_transition, void *scratch, size_t scratch_bytes, int flags,
+                                 void *stream) {
+    (void) ctx;
+    int rc = check_beam_words_loss(p, gb, lm, beam_size);
+    if (rc) return rc;
+    if (!work || !scores || !grad_scores || !grad_inputs || !grad_transition || !scratch) return ASG_ERR_INVALID;
+    if (work_bytes < asg_beam_words_full_work_bytes(p, gb, lm, beam_size, 1) ||
+        scratch_bytes < asg_beam_words_full_scratch_bytes(p, gb, lm, beam_size))
+        return ASG_ERR_WORKSPACE;
+    const Problem P = to_problem(p);
+    const GraphArgs G = to_graph_args(gb->graph);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    const WordLmArgs LM = to_word_lm_args(lm);
+    const bool acc = (flags & ASG_FLAG_BEAM_LOSS_ACCUMULATE) != 0;
+    return hip_status(ASG_DISPATCH(p,
+        launch_beam_word_loss_backward<float>(P, G, BG, LM, beam_size, work, scores, grad_scores, grad_inputs, grad_transition,
+                                              scratch, acc, (hipStream_t) stream),
+        launch_beam_word_loss_backward<double>(P, G, BG, LM, beam_size, work, scores, grad_scores, grad_inputs, grad_transition,
+                                               scratch, acc, (hipStream_t) stream)));
+}
+
+int asg_words_target_scores(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm, void *out,
+                            void *stream) {
+    (void) ctx;
+    int rc = check_beam_words(p, gb, lm, 1);
+    if (rc) return rc;
+    if (!out || !p->targets || p->S < 1) return ASG_ERR_INVALID;
+    if (p->S > (1 << 30)) return ASG_ERR_UNSUPPORTED;
+    const Problem P = to_problem(p);
+    const GraphArgs G = to_graph_args(gb->graph);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    const WordLmArgs LM = to_word_lm_args(lm);
+    return hip_status(ASG_DISPATCH(p, launch_beam_word_target_scores<float>(P, G, BG, LM, out, (hipStream_t) stream),
+                                   launch_beam_word_target_scores<double>(P, G, BG, LM, out, (hipStream_t) stream)));
+}
+
 static GraphLossArgs to_graph_loss_args(const asg_token_graph_loss *gl) {
     GraphLossArgs L{};
     L.S = (int) gl->S; L.start = gl->start;

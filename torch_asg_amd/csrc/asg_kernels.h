@@ -383,6 +383,30 @@ hipError_t launch_beam_loss_backward(const Problem &P, const GraphArgs &G, const
                                      const void *scores, const void *grad_scores, void *grad_inputs, void *grad_transition,
                                      void *scratch, bool accumulate, hipStream_t stream);
 
+// ---- Beam-pruned full score and gradients over the pairs of the word decoder (asg_beam_word_loss.hip): asg_beam_words_full_*.
+// One utterance's workspace: the word decoder's own layout at the front (bq, bh: its [T][K] lists), then (byte offsets, each part
+// 256-byte aligned) the kept counts cnt [T], the lattice counts nu [T], hdr (word 0: forced pairs n), the forced pairs' keys
+// [nf] u64, the lattice lists U [T][M] u64, alpha [T or 2][M]; M = K + nf, nf = min(S, T) with targets, else 0.
+struct BeamWordLossLayout {
+    size_t bq, bh, cnt, nu, hdr, key, U, A, per;
+    int M, nf;
+};
+BeamWordLossLayout beam_word_loss_layout(int elem, int T, int K, int cap, int nf, bool store);
+size_t beam_word_loss_work_bytes(int elem, int T, int B, int K, int cap, int nf, bool store);
+size_t beam_word_loss_scratch_per(int elem, int M, int N);
+// the one bound on M: a frame's lattice set with a maximum and a sum per member stays in LDS (M <= 8179 float32, 6816 float64)
+bool beam_word_loss_fits(int elem, int M, int N);
+template <typename R>
+hipError_t launch_beam_word_loss_forward(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int K,
+                                         double theta, bool store, void *work, void *scores, hipStream_t stream);
+template <typename R>
+hipError_t launch_beam_word_loss_backward(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int K,
+                                          const void *work, const void *scores, const void *grad_scores, void *grad_inputs,
+                                          void *grad_transition, void *scratch, bool accumulate, hipStream_t stream);
+template <typename R>
+hipError_t launch_beam_word_target_scores(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                                          void *out, hipStream_t stream);
+
 // ---- Full score, gradients and target walk over the same composed lattice (asg_graph_loss.hip).  The loss-only arrays of
 // asg_token_graph_loss.  Work = alpha [T][Q][B] (stored) or [2][Q][B]; scratch = align256([2][Q][B] beta) + [Q+E][B]
 // per-stay / per-edge posterior sums.

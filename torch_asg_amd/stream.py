@@ -243,7 +243,8 @@ class BeamWordStream(_Stream):
     (include/asg_hip.h::asg_beam_word_stream_advance_la): `result(final=True)` then equals that call, bit for bit, for any
     chunking, and a prefix result takes the estimate that has not cancelled yet back (see `result`).  The stream is bound to
     its look-ahead for life -- the values in the state carry it -- and the state has the same size with or without.
-    Not here: a loss over pairs; `result_nbest` of a stream with a look-ahead.
+    Not here: a loss over a stream (the one-shot loss over pairs is `beam_words_asg_loss`); `result_nbest` of a stream with a
+    look-ahead.
     """
     _API, _WIDE, _NARROW = "asg_beam_word_stream", 5, 4
 
