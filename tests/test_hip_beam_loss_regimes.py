@@ -395,6 +395,32 @@ def test_groups_accumulate_into_a_tile_in_scratch_bit_for_bit(monkeypatch):
         assert torch.equal(u, v)
 
 
+def test_a_batch_of_65536_utterances_is_one_call():
+    """beam_loss_sets has the utterances in grid x and the frames strided over y, so B has no limit of its own (with the frames
+    in x and the utterances in y, B > 65535 was a launch error).  Forward only: two different utterances (lengths 2 and 1)
+    alternate over B = 65 536, T = 2, N = 2, the one-state automaton, K = 1, float32.  The whole batch's workspace is
+    188 743 680 bytes (asg_beam_graph_full_work_bytes for these sizes, Q = 2, num_start = 2, max_out = 1; at T = 2 the same
+    with and without the stored alphas), given as max_work_bytes: one group."""
+    B, T, N, K, WORK = 65536, 2, 2, 1, 188743680
+    graph = _one_state(N)
+    x2, tr, _ = _case(T, 2, N, 3, F32)
+    il2 = torch.tensor([2, 1])
+    be = _asg().asg.native()
+
+    def run(nb, max_work_bytes):
+        x = x2.repeat(1, nb // 2, 1).contiguous().to(DEV)
+        Z, saved = be.beam_graph_full_forward(x, tr.to(DEV), graph, il2.repeat(nb // 2).to(DEV), K, store=True,
+                                              max_work_bytes=max_work_bytes)
+        torch.cuda.synchronize()
+        return Z.cpu().view(torch.int32), saved                # the bits
+    Z, saved = run(B, WORK)
+    assert len(saved) == 1 and saved[0][:2] == (0, B) and saved[0][2].numel() == WORK
+    small, _ = run(2, 1 << 30)
+    assert torch.isfinite(small.view(torch.float32)).all() and small[0] != small[1]
+    assert torch.equal(Z[0::2], Z[0].expand(B // 2)) and torch.equal(Z[1::2], Z[1].expand(B // 2))
+    assert torch.equal(Z[:2], small)
+
+
 # ---- 4: length steps and long utterances ------------------------------------------------------------------------------------
 
 LONG_T = 3000

@@ -555,6 +555,9 @@ class HipBackend:
             if per == 0 and Q:
                 p.B = B
                 refused()
+            whole = sized(B)
+            if whole <= max_work_bytes:          # (B * per overstates it: the parts behind the utterances are rounded once)
+                return ((0, B, self._buf(whole, inputs.device)),)
             gsz = max(1, min(B, int(max_work_bytes) // max(per, 1)))
             while gsz > 1 and sized(gsz) > max_work_bytes:
                 gsz -= 1
@@ -615,6 +618,66 @@ class HipBackend:
         return BeamNbest(sc[0], sc[1], sc[2], tokens, token_lengths, num_hyps,
                          align[0] if return_alignments else None, align[1] if return_alignments else None)
 
+    def _lattice_forward(self, entry, sizer, prepare, size_args, call_args, inputs, transition, targets, input_lengths,
+                         target_lengths, store, max_work_bytes, flags=0):
+        """The forward of the graph loss and of the two beam-pruned losses -> (scores[B], saved).  `entry` / `sizer` name the
+        library's *_full_forward / *_full_work_bytes; `prepare()`, called under the device guard, checks the family's
+        arguments and returns (the ctypes views that follow the problem in both calls, Q, what those views point into); `size_args` / `call_args` are what
+        follows the views in the size call (before `store`) and in the forward (before the workspace)."""
+        L = _lib.lib()
+        forward, work_bytes = getattr(L, entry), getattr(L, sizer)
+        dev = inputs.device
+        B = inputs.shape[1]
+        with self._guard(dev):
+            views, Q, keep = prepare()
+            p, targets, input_lengths, target_lengths = self._device_problem(inputs, transition, targets, input_lengths,
+                                                                             target_lengths)
+            fl = flags | (_lib.FLAG_GRAPH_LOSS_KEEP_ALPHA if store else 0)
+            head = [ctypes.byref(p)] + [ctypes.byref(v) for v in views]
+
+            def call(work, nbytes, scores, stream):
+                return forward(None, *head, *call_args, work, nbytes, scores, fl, stream)
+            groups = self._groups(p, B, max_work_bytes, lambda: work_bytes(*head, *size_args, int(store)), Q,
+                                  lambda: _lib.check(call(None, 0, None, None), entry),
+                                  inputs, targets, input_lengths, target_lengths, store=store)
+            scores = torch.empty(B, dtype=inputs.dtype, device=dev)
+            stream = self._stream(dev)
+            saved = []
+            for b0, b1, work in groups:
+                _lib.check(call(work.data_ptr(), work.numel(), scores[b0:].data_ptr(), stream), entry)
+                saved.append((b0, b1, work))
+        return scores, (saved if store else None)
+
+    def _lattice_backward(self, entry, sizer, prepare, size_args, saved, scores, grad_scores, inputs, transition, targets,
+                          input_lengths, target_lengths):
+        """The backward of the two beam-pruned losses -> (grad_transition[N,N], grad_inputs[T,B,N]); `entry` / `sizer` name
+        the library's *_full_backward / *_full_scratch_bytes, `prepare` and `size_args` are `_lattice_forward`'s.  The groups
+        add into one grad_transition in batch order (ASG_FLAG_BEAM_LOSS_ACCUMULATE from the second on)."""
+        L = _lib.lib()
+        backward, scratch_bytes = getattr(L, entry), getattr(L, sizer)
+        dev = inputs.device
+        T, B, N = inputs.shape
+        with self._guard(dev):
+            views, _, keep = prepare()
+            p, targets, input_lengths, target_lengths = self._device_problem(inputs, transition, targets, input_lengths,
+                                                                             target_lengths)
+            head = [ctypes.byref(p)] + [ctypes.byref(v) for v in views]
+            gs = grad_scores.to(inputs.dtype).contiguous()
+            gin = torch.empty(T, B, N, dtype=inputs.dtype, device=dev)
+            gtr = torch.empty(N, N, dtype=inputs.dtype, device=dev)
+            stream = self._stream(dev)
+            groups = self._groups(p, B, None, None, None, None, inputs, targets, input_lengths, target_lengths, saved=saved)
+            for n, (b0, b1, work) in enumerate(groups):
+                nb = b1 - b0
+                scratch = self._buf(scratch_bytes(*head, *size_args), dev)
+                gin_g = gin if nb == B else torch.empty(T, nb, N, dtype=inputs.dtype, device=dev)
+                _lib.check(backward(None, *head, *size_args, work.data_ptr(), work.numel(), scores[b0:].data_ptr(),
+                                    gs[b0:].data_ptr(), gin_g.data_ptr(), gtr.data_ptr(), scratch.data_ptr(), scratch.numel(),
+                                    _lib.FLAG_BEAM_LOSS_ACCUMULATE if n else 0, stream), entry)
+                if nb != B:
+                    gin[:, b0:b1].copy_(gin_g)
+        return gtr, gin
+
     def _graph_loss_args(self, inputs, transition, graph, input_lengths, lm_weight, token_score, targets=None,
                          target_lengths=None):
         """Checks shared by the graph-loss entry points -> the compiled graph and its asg_token_graph_loss view."""
@@ -628,27 +691,11 @@ class HipBackend:
         """Full score of the lattice composed with a token automaton -> (scores[B], saved); see
         include/asg_hip.h::asg_graph_full_forward.  Utterances run in consecutive groups whose workspace fits `max_work_bytes`.
         With `store`, saved = [(b0, b1, work)]: each group's stored alpha, for graph_full_backward; None otherwise."""
-        L = _lib.lib()
-        dev = inputs.device
-        B = inputs.shape[1]
-        with self._guard(dev):
+        def prepare():
             compiled, gl = self._graph_loss_args(inputs, transition, graph, input_lengths, lm_weight, token_score)
-            p, _, input_lengths, _ = self._device_problem(inputs, transition, None, input_lengths, None)
-            fl = flags | (_lib.FLAG_GRAPH_LOSS_KEEP_ALPHA if store else 0)
-
-            def call(work, nbytes, scores, stream):
-                return L.asg_graph_full_forward(None, ctypes.byref(p), ctypes.byref(gl), work, nbytes, scores, fl, stream)
-            groups = self._groups(p, B, max_work_bytes,
-                                  lambda: L.asg_graph_full_work_bytes(ctypes.byref(p), ctypes.byref(gl), int(store)), compiled["Q"],
-                                  lambda: _lib.check(call(None, 0, None, None), "asg_graph_full_forward"),
-                                  inputs, input_lengths=input_lengths, store=store)
-            scores = torch.empty(B, dtype=inputs.dtype, device=dev)
-            stream = self._stream(dev)
-            saved = []
-            for b0, b1, work in groups:
-                _lib.check(call(work.data_ptr(), work.numel(), scores[b0:].data_ptr(), stream), "asg_graph_full_forward")
-                saved.append((b0, b1, work))
-        return scores, (saved if store else None)
+            return (gl,), compiled["Q"], compiled
+        return self._lattice_forward("asg_graph_full_forward", "asg_graph_full_work_bytes", prepare, (), (), inputs, transition,
+                                     None, input_lengths, None, store, max_work_bytes, flags)
 
     def graph_full_backward(self, saved, scores, grad_scores, inputs, transition, graph, input_lengths, lm_weight=1.0,
                             token_score=0.0, flags=0):
@@ -678,11 +725,12 @@ class HipBackend:
         return gtr, gin
 
     def _beam_loss_args(self, inputs, transition, graph, input_lengths, targets, target_lengths, lm_weight, token_score):
-        """Checks shared by the beam-pruned loss entry points -> the compiled graph and its asg_token_graph_beam_loss view."""
+        """Checks shared by the beam-pruned loss entry points -> ((the asg_token_graph_beam_loss view,), Q, the compiled graph it
+        points into): `_lattice_forward`'s `prepare`."""
         from . import graph as _graph
         self._check_graph_inputs(inputs, transition, graph, input_lengths, targets, target_lengths)
         compiled = graph.compile_beam_loss(inputs.device, inputs.dtype, lm_weight, token_score)
-        return compiled, _graph.abi_graph_beam_loss(compiled)
+        return (_graph.abi_graph_beam_loss(compiled),), compiled["Q"], compiled
 
     def beam_graph_full_forward(self, inputs, transition, graph, input_lengths, beam_size, beam_threshold=float("inf"),
                                 lm_weight=1.0, token_score=0.0, targets=None, target_lengths=None, store=False,
@@ -690,63 +738,22 @@ class HipBackend:
         """Beam-pruned full score of the lattice composed with a token automaton -> (scores[B], saved); see
         include/asg_hip.h::asg_beam_graph_full_forward.  Utterances run in consecutive groups whose workspace fits
         `max_work_bytes`.  With `store`, saved = [(b0, b1, work)] for beam_graph_full_backward; None otherwise."""
-        L = _lib.lib()
-        dev = inputs.device
-        B = inputs.shape[1]
         beam_size, beam_threshold = min(int(beam_size), (1 << 31) - 1), float(beam_threshold)
-        with self._guard(dev):
-            compiled, gl = self._beam_loss_args(inputs, transition, graph, input_lengths, targets, target_lengths, lm_weight,
-                                                token_score)
-            p, targets, input_lengths, target_lengths = self._device_problem(inputs, transition, targets, input_lengths,
-                                                                             target_lengths)
-            fl = _lib.FLAG_GRAPH_LOSS_KEEP_ALPHA if store else 0
-
-            def call(work, nbytes, scores, stream):
-                return L.asg_beam_graph_full_forward(None, ctypes.byref(p), ctypes.byref(gl), beam_size, beam_threshold, work,
-                                                     nbytes, scores, fl, stream)
-            groups = self._groups(
-                p, B, max_work_bytes,
-                lambda: L.asg_beam_graph_full_work_bytes(ctypes.byref(p), ctypes.byref(gl), beam_size, int(store)), compiled["Q"],
-                lambda: _lib.check(call(None, 0, None, None), "asg_beam_graph_full_forward"),
-                inputs, targets, input_lengths, target_lengths, store=store)
-            scores = torch.empty(B, dtype=inputs.dtype, device=dev)
-            stream = self._stream(dev)
-            saved = []
-            for b0, b1, work in groups:
-                _lib.check(call(work.data_ptr(), work.numel(), scores[b0:].data_ptr(), stream), "asg_beam_graph_full_forward")
-                saved.append((b0, b1, work))
-        return scores, (saved if store else None)
+        return self._lattice_forward(
+            "asg_beam_graph_full_forward", "asg_beam_graph_full_work_bytes",
+            lambda: self._beam_loss_args(inputs, transition, graph, input_lengths, targets, target_lengths, lm_weight, token_score),
+            (beam_size,), (beam_size, beam_threshold), inputs, transition, targets, input_lengths, target_lengths, store,
+            max_work_bytes)
 
     def beam_graph_full_backward(self, saved, scores, grad_scores, inputs, transition, graph, input_lengths, beam_size,
                                  lm_weight=1.0, token_score=0.0, targets=None, target_lengths=None):
         """(grad_transition[N,N], grad_inputs[T,B,N]) of sum_b grad_scores[b] * scores[b] from beam_graph_full_forward's saved
         lattices.  The groups add into one grad_transition in batch order, so the result does not depend on the grouping."""
-        L = _lib.lib()
-        dev = inputs.device
-        T, B, N = inputs.shape
         beam_size = min(int(beam_size), (1 << 31) - 1)
-        with self._guard(dev):
-            compiled, gl = self._beam_loss_args(inputs, transition, graph, input_lengths, targets, target_lengths, lm_weight,
-                                                token_score)
-            p, targets, input_lengths, target_lengths = self._device_problem(inputs, transition, targets, input_lengths,
-                                                                             target_lengths)
-            gs = grad_scores.to(inputs.dtype).contiguous()
-            gin = torch.empty(T, B, N, dtype=inputs.dtype, device=dev)
-            gtr = torch.empty(N, N, dtype=inputs.dtype, device=dev)
-            stream = self._stream(dev)
-            groups = self._groups(p, B, None, None, None, None, inputs, targets, input_lengths, target_lengths, saved=saved)
-            for n, (b0, b1, work) in enumerate(groups):
-                nb = b1 - b0
-                scratch = self._buf(L.asg_beam_graph_full_scratch_bytes(ctypes.byref(p), ctypes.byref(gl), beam_size), dev)
-                gin_g = gin if nb == B else torch.empty(T, nb, N, dtype=inputs.dtype, device=dev)
-                _lib.check(L.asg_beam_graph_full_backward(None, ctypes.byref(p), ctypes.byref(gl), beam_size, work.data_ptr(),
-                                                          work.numel(), scores[b0:].data_ptr(), gs[b0:].data_ptr(),
-                                                          gin_g.data_ptr(), gtr.data_ptr(), scratch.data_ptr(), scratch.numel(),
-                                                          _lib.FLAG_BEAM_LOSS_ACCUMULATE if n else 0, stream),
-                           "asg_beam_graph_full_backward")
-                if nb != B:
-                    gin[:, b0:b1].copy_(gin_g)
-        return gtr, gin
+        return self._lattice_backward(
+            "asg_beam_graph_full_backward", "asg_beam_graph_full_scratch_bytes",
+            lambda: self._beam_loss_args(inputs, transition, graph, input_lengths, targets, target_lengths, lm_weight, token_score),
+            (beam_size,), saved, scores, grad_scores, inputs, transition, targets, input_lengths, target_lengths)
 
     def graph_target_scores(self, inputs, transition, graph, targets, target_lengths, lm_weight=1.0, token_score=0.0):
         """[B]: the automaton's score of every target sequence (consecutive repeats merged), -inf where it rejects it; see
@@ -762,77 +769,38 @@ class HipBackend:
         return out
 
     def _word_loss_args(self, inputs, transition, lexicon, word_lm, input_lengths, targets, target_lengths, weights):
-        """Checks shared by the pair-loss entry points -> (the lexicon's asg_token_graph_beam view, the asg_word_lm view, the
-        compiled dicts they point into), through the caches of `Lexicon.compile_words` and `WordLM.compile`."""
+        """Checks shared by the pair-loss entry points -> ((the lexicon's asg_token_graph_beam view, the asg_word_lm view), Q,
+        the compiled dicts they point into), through the caches of `Lexicon.compile_words` and `WordLM.compile`:
+        `_lattice_forward`'s `prepare`."""
         from . import wordlm as _wordlm
         _wordlm.check_words(lexicon, word_lm)
         self._check_graph_inputs(inputs, transition, lexicon.graph, input_lengths, targets, target_lengths)
-        return _wordlm.abi_words(lexicon, word_lm, inputs.device, inputs.dtype, *weights)
+        g, w, keep = _wordlm.abi_words(lexicon, word_lm, inputs.device, inputs.dtype, *weights)
+        return (g, w), keep[0]["Q"], keep
 
     def beam_words_full_forward(self, inputs, transition, lexicon, word_lm, input_lengths, beam_size, beam_threshold=float("inf"),
                                 lm_weight=1.0, word_score=0.0, token_score=0.0, targets=None, target_lengths=None, store=False,
                                 max_work_bytes=1 << 30):
         """Beam-pruned full score over the pairs `beam_decode_words` keeps -> (scores[B], saved); see
         include/asg_hip.h::asg_beam_words_full_forward.  Grouped and saved as `beam_graph_full_forward` does."""
-        L = _lib.lib()
-        dev = inputs.device
-        B = inputs.shape[1]
         beam_size, beam_threshold = min(int(beam_size), (1 << 31) - 1), float(beam_threshold)
-        with self._guard(dev):
-            g, w, keep = self._word_loss_args(inputs, transition, lexicon, word_lm, input_lengths, targets, target_lengths,
-                                              (lm_weight, word_score, token_score))
-            p, targets, input_lengths, target_lengths = self._device_problem(inputs, transition, targets, input_lengths,
-                                                                             target_lengths)
-            fl = _lib.FLAG_GRAPH_LOSS_KEEP_ALPHA if store else 0
-
-            def call(work, nbytes, scores, stream):
-                return L.asg_beam_words_full_forward(None, ctypes.byref(p), ctypes.byref(g), ctypes.byref(w), beam_size,
-                                                     beam_threshold, work, nbytes, scores, fl, stream)
-            groups = self._groups(
-                p, B, max_work_bytes,
-                lambda: L.asg_beam_words_full_work_bytes(ctypes.byref(p), ctypes.byref(g), ctypes.byref(w), beam_size, int(store)),
-                keep[0]["Q"], lambda: _lib.check(call(None, 0, None, None), "asg_beam_words_full_forward"),
-                inputs, targets, input_lengths, target_lengths, store=store)
-            scores = torch.empty(B, dtype=inputs.dtype, device=dev)
-            stream = self._stream(dev)
-            saved = []
-            for b0, b1, work in groups:
-                _lib.check(call(work.data_ptr(), work.numel(), scores[b0:].data_ptr(), stream), "asg_beam_words_full_forward")
-                saved.append((b0, b1, work))
-        return scores, (saved if store else None)
+        return self._lattice_forward(
+            "asg_beam_words_full_forward", "asg_beam_words_full_work_bytes",
+            lambda: self._word_loss_args(inputs, transition, lexicon, word_lm, input_lengths, targets, target_lengths,
+                                         (lm_weight, word_score, token_score)),
+            (beam_size,), (beam_size, beam_threshold), inputs, transition, targets, input_lengths, target_lengths, store,
+            max_work_bytes)
 
     def beam_words_full_backward(self, saved, scores, grad_scores, inputs, transition, lexicon, word_lm, input_lengths, beam_size,
                                  lm_weight=1.0, word_score=0.0, token_score=0.0, targets=None, target_lengths=None):
         """(grad_transition[N,N], grad_inputs[T,B,N]) of sum_b grad_scores[b] * scores[b] from beam_words_full_forward's saved
         lattices.  The groups add into one grad_transition in batch order, so the result does not depend on the grouping."""
-        L = _lib.lib()
-        dev = inputs.device
-        T, B, N = inputs.shape
         beam_size = min(int(beam_size), (1 << 31) - 1)
-        with self._guard(dev):
-            g, w, keep = self._word_loss_args(inputs, transition, lexicon, word_lm, input_lengths, targets, target_lengths,
-                                              (lm_weight, word_score, token_score))
-            p, targets, input_lengths, target_lengths = self._device_problem(inputs, transition, targets, input_lengths,
-                                                                             target_lengths)
-            gs = grad_scores.to(inputs.dtype).contiguous()
-            gin = torch.empty(T, B, N, dtype=inputs.dtype, device=dev)
-            gtr = torch.empty(N, N, dtype=inputs.dtype, device=dev)
-            stream = self._stream(dev)
-            groups = self._groups(p, B, None, None, None, None, inputs, targets, input_lengths, target_lengths, saved=saved)
-            for n, (b0, b1, work) in enumerate(groups):
-                nb = b1 - b0
-                scratch = self._buf(L.asg_beam_words_full_scratch_bytes(ctypes.byref(p), ctypes.byref(g), ctypes.byref(w),
-                                                                        beam_size), dev)
-                gin_g = gin if nb == B else torch.empty(T, nb, N, dtype=inputs.dtype, device=dev)
-                _lib.check(L.asg_beam_words_full_backward(None, ctypes.byref(p), ctypes.byref(g), ctypes.byref(w), beam_size,
-                                                          work.data_ptr(), work.numel(), scores[b0:].data_ptr(),
-                                                          gs[b0:].data_ptr(), gin_g.data_ptr(), gtr.data_ptr(),
-                                                          scratch.data_ptr(), scratch.numel(),
-                                                          _lib.FLAG_BEAM_LOSS_ACCUMULATE if n else 0, stream),
-                           "asg_beam_words_full_backward")
-                if nb != B:
-                    gin[:, b0:b1].copy_(gin_g)
-        return gtr, gin
+        return self._lattice_backward(
+            "asg_beam_words_full_backward", "asg_beam_words_full_scratch_bytes",
+            lambda: self._word_loss_args(inputs, transition, lexicon, word_lm, input_lengths, targets, target_lengths,
+                                         (lm_weight, word_score, token_score)),
+            (beam_size,), saved, scores, grad_scores, inputs, transition, targets, input_lengths, target_lengths)
 
     def words_target_scores(self, inputs, transition, lexicon, word_lm, targets, target_lengths, lm_weight=1.0, word_score=0.0,
                             token_score=0.0):
@@ -841,8 +809,8 @@ class HipBackend:
         L = _lib.lib()
         dev = inputs.device
         with self._guard(dev):
-            g, w, keep = self._word_loss_args(inputs, transition, lexicon, word_lm, None, targets, target_lengths,
-                                              (lm_weight, word_score, token_score))
+            (g, w), _, keep = self._word_loss_args(inputs, transition, lexicon, word_lm, None, targets, target_lengths,
+                                                   (lm_weight, word_score, token_score))
             p, keep_p = self._problem(inputs, transition, targets, None, target_lengths)
             out = torch.empty(inputs.shape[1], dtype=inputs.dtype, device=dev)
             _lib.check(L.asg_words_target_scores(None, ctypes.byref(p), ctypes.byref(g), ctypes.byref(w), out.data_ptr(),

@@ -1251,19 +1251,38 @@ int asg_beam_word_window_result_la(asg_ctx *ctx, const asg_token_graph_beam *gb,
                                    token_lengths, states, lm_states, words, word_lengths, frames, committed, status, stream);
 }
 
+// What the two beam-pruned losses check alike behind their search's own checks: the targets, the limits of the lattice pass and
+// whether a frame's set of M = K + nf members fits the family's kernels.
+static int check_lattice(const asg_problem *p, int K, bool (*fits)(int, int, int)) {
+    if (p->targets && p->S < 1) return ASG_ERR_INVALID;
+    if (p->N > kBeamLossMaxN || p->T > (1 << 20)) return ASG_ERR_UNSUPPORTED;
+    const int64_t nf = p->targets ? (p->S < p->T ? p->S : p->T) : 0;
+    if (nf > kBeamLossMaxForced) return ASG_ERR_UNSUPPORTED;
+    if (!fits(p->dtype == ASG_DTYPE_F64 ? 8 : 4, K + (int) nf, (int) p->N)) return ASG_ERR_UNSUPPORTED;
+    return ASG_OK;
+}
+
+// The two *_full_backward entry points: rc is the family's check (the two sizes are 0 when it fails), then the buffers, their
+// sizes, the flag, and `launch` (const Problem &, bool accumulate, element type tag) on the dtype of the problem.
+extern "C++" template <typename Launch>
+static int lattice_full_backward(const asg_problem *p, int rc, size_t work_need, size_t scratch_need, const void *work,
+                                 size_t work_bytes, const void *scores, const void *grad_scores, void *grad_inputs,
+                                 void *grad_transition, void *scratch, size_t scratch_bytes, int flags, Launch launch) {
+    if (rc) return rc;
+    if (!work || !scores || !grad_scores || !grad_inputs || !grad_transition || !scratch) return ASG_ERR_INVALID;
+    if (work_bytes < work_need || scratch_bytes < scratch_need) return ASG_ERR_WORKSPACE;
+    const Problem P = to_problem(p);
+    const bool acc = (flags & ASG_FLAG_BEAM_LOSS_ACCUMULATE) != 0;
+    return hip_status(ASG_DISPATCH(p, launch(P, acc, float()), launch(P, acc, double())));
+}
+
 static int check_beam_loss(const asg_problem *p, const asg_token_graph_beam_loss *gl, int beam_size) {
     if (!gl) return ASG_ERR_INVALID;
     int rc = check_beam_graph(p, gl->beam, beam_size);
     if (rc) return rc;
     if (gl->S < 1 || gl->start < 0 || gl->start >= gl->S || !gl->next) return ASG_ERR_INVALID;
     if (gl->S >= (int64_t) 1 << 31) return ASG_ERR_UNSUPPORTED;
-    if (p->targets && p->S < 1) return ASG_ERR_INVALID;
-    if (p->N > kBeamLossMaxN || p->T > (1 << 20)) return ASG_ERR_UNSUPPORTED;
-    const int64_t nf = p->targets ? (p->S < p->T ? p->S : p->T) : 0;
-    if (nf > kBeamLossMaxForced) return ASG_ERR_UNSUPPORTED;
-    const int K = beam_graph_k((int) gl->beam->graph->Q, beam_size);
-    if (!beam_loss_fits(p->dtype == ASG_DTYPE_F64 ? 8 : 4, K + (int) nf, (int) p->N)) return ASG_ERR_UNSUPPORTED;
-    return ASG_OK;
+    return check_lattice(p, beam_graph_k((int) gl->beam->graph->Q, beam_size), beam_loss_fits);
 }
 
 static int beam_loss_nf(const asg_problem *p) { return p->targets ? (int) (p->S < p->T ? p->S : p->T) : 0; }
@@ -1307,33 +1326,21 @@ int asg_beam_graph_full_backward(asg_ctx *ctx, const asg_problem *p, const asg_t
                                  void *grad_inputs, void *grad_transition, void *scratch, size_t scratch_bytes, int flags,
                                  void *stream) {
     (void) ctx;
-    int rc = check_beam_loss(p, gl, beam_size);
-    if (rc) return rc;
-    if (!work || !scores || !grad_scores || !grad_inputs || !grad_transition || !scratch) return ASG_ERR_INVALID;
-    if (work_bytes < asg_beam_graph_full_work_bytes(p, gl, beam_size, 1) ||
-        scratch_bytes < asg_beam_graph_full_scratch_bytes(p, gl, beam_size))
-        return ASG_ERR_WORKSPACE;
-    const Problem P = to_problem(p);
-    const GraphArgs G = to_graph_args(gl->beam->graph);
-    const BeamGraphArgs BG = to_beam_graph_args(gl->beam);
-    const int K = beam_graph_k(G.Q, beam_size);
-    const bool acc = (flags & ASG_FLAG_BEAM_LOSS_ACCUMULATE) != 0;
-    return hip_status(ASG_DISPATCH(p,
-        launch_beam_loss_backward<float>(P, G, BG, K, work, scores, grad_scores, grad_inputs, grad_transition, scratch, acc,
-                                         (hipStream_t) stream),
-        launch_beam_loss_backward<double>(P, G, BG, K, work, scores, grad_scores, grad_inputs, grad_transition, scratch, acc,
-                                          (hipStream_t) stream)));
+    return lattice_full_backward(
+        p, check_beam_loss(p, gl, beam_size), asg_beam_graph_full_work_bytes(p, gl, beam_size, 1),
+        asg_beam_graph_full_scratch_bytes(p, gl, beam_size), work, work_bytes, scores, grad_scores, grad_inputs, grad_transition, scratch, scratch_bytes, flags,
+        [&](const Problem &P, bool acc, auto r) {
+            const GraphArgs G = to_graph_args(gl->beam->graph);
+            return launch_beam_loss_backward<decltype(r)>(P, G, to_beam_graph_args(gl->beam), beam_graph_k(G.Q, beam_size), work, scores,
+                                                          grad_scores, grad_inputs, grad_transition, scratch, acc,
+                                                          (hipStream_t) stream);
+        });
 }
 
 static int check_beam_words_loss(const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm, int beam_size) {
     int rc = check_beam_words(p, gb, lm, beam_size);
     if (rc) return rc;
-    if (p->targets && p->S < 1) return ASG_ERR_INVALID;
-    if (p->N > kBeamLossMaxN || p->T > (1 << 20)) return ASG_ERR_UNSUPPORTED;
-    const int64_t nf = p->targets ? (p->S < p->T ? p->S : p->T) : 0;
-    if (nf > kBeamLossMaxForced) return ASG_ERR_UNSUPPORTED;
-    if (!beam_word_loss_fits(p->dtype == ASG_DTYPE_F64 ? 8 : 4, beam_size + (int) nf, (int) p->N)) return ASG_ERR_UNSUPPORTED;
-    return ASG_OK;
+    return check_lattice(p, beam_size, beam_word_loss_fits);
 }
 
 size_t asg_beam_words_full_work_bytes(const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm, int beam_size,
@@ -1372,22 +1379,14 @@ int asg_beam_words_full_backward(asg_ctx *ctx, const asg_problem *p, const asg_t
                                  void *grad_inputs, void *grad_transition, void *scratch, size_t scratch_bytes, int flags,
                                  void *stream) {
     (void) ctx;
-    int rc = check_beam_words_loss(p, gb, lm, beam_size);
-    if (rc) return rc;
-    if (!work || !scores || !grad_scores || !grad_inputs || !grad_transition || !scratch) return ASG_ERR_INVALID;
-    if (work_bytes < asg_beam_words_full_work_bytes(p, gb, lm, beam_size, 1) ||
-        scratch_bytes < asg_beam_words_full_scratch_bytes(p, gb, lm, beam_size))
-        return ASG_ERR_WORKSPACE;
-    const Problem P = to_problem(p);
-    const GraphArgs G = to_graph_args(gb->graph);
-    const BeamGraphArgs BG = to_beam_graph_args(gb);
-    const WordLmArgs LM = to_word_lm_args(lm);
-    const bool acc = (flags & ASG_FLAG_BEAM_LOSS_ACCUMULATE) != 0;
-    return hip_status(ASG_DISPATCH(p,
-        launch_beam_word_loss_backward<float>(P, G, BG, LM, beam_size, work, scores, grad_scores, grad_inputs, grad_transition,
-                                              scratch, acc, (hipStream_t) stream),
-        launch_beam_word_loss_backward<double>(P, G, BG, LM, beam_size, work, scores, grad_scores, grad_inputs, grad_transition,
-                                               scratch, acc, (hipStream_t) stream)));
+    return lattice_full_backward(
+        p, check_beam_words_loss(p, gb, lm, beam_size), asg_beam_words_full_work_bytes(p, gb, lm, beam_size, 1),
+        asg_beam_words_full_scratch_bytes(p, gb, lm, beam_size), work, work_bytes, scores, grad_scores, grad_inputs,
+        grad_transition, scratch, scratch_bytes, flags, [&](const Problem &P, bool acc, auto r) {
+            return launch_beam_word_loss_backward<decltype(r)>(P, to_graph_args(gb->graph), to_beam_graph_args(gb), to_word_lm_args(lm),
+                                                               beam_size, work, scores, grad_scores, grad_inputs, grad_transition,
+                                                               scratch, acc, (hipStream_t) stream);
+        });
 }
 
 int asg_words_target_scores(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm, void *out,

@@ -8,7 +8,7 @@
 //      so the same kept sets bit for bit) that leaves |A_t| of every frame beside the [T][K] lists bq / bh; no end, no backtrace;
 //   2  beam_word_loss_targets: one thread per utterance walks the lexicon's outgoing rows along the merged target, the LM walk
 //      on every separator edge included -> the forced pairs as 64-bit keys h << qbits | q; hdr[0] = n (0: nothing is forced);
-//   3  beam_word_loss_sets: one workgroup per (utterance, frame) -- utterances in x, frames strided over y -- sorts the keys of A_t
+//   3  beam_loss_sets<WordSets>: one workgroup per (utterance, frame) -- utterances in x, frames strided over y -- sorts the keys of A_t
 //      with those of F_t in LDS (bitonic over the power of two its own count needs), blanks the duplicates and sorts again:
 //      U[t][0 .. nu[t]) ascending in pair order;
 //   4  beam_word_loss_fwd: one 1024-thread workgroup per utterance walks the frames.  There is no incoming-edge list over pairs
@@ -19,86 +19,24 @@
 //      target has at most |U_{t-1}| + 1 < 2^14 candidates of at most 1 each: no overflow).  Integer max and add are associative:
 //      the order the lanes arrive in cannot change a bit.  alpha = (max + log(sum)) + emission goes to the workspace ([T][M] when
 //      a gradient is wanted, else two rows).
-// Backward, two launches: beam_word_loss_bwd (beta PULLS: a pair's own outgoing row is a gather against U_{t+1} in LDS, no
-// atomics on values; it owns the label posteriors and the (i, j) counts, summed as 64-bit fixed-point integers as in
-// asg_beam_loss.hip, the counts in LDS while the [N][N] tile fits, else in the utterance's scratch) and
-// beam_word_loss_tr_reduce (the utterances in ascending order).  NO FLOAT ATOMICS anywhere.  Every output, padding row and
+// Backward, two launches: beam_loss_bwd<R, TL, WordLat<R>> (beta PULLS: a pair's own outgoing row is a gather against U_{t+1} in
+// LDS, no atomics on values; it owns the label posteriors and the (i, j) counts, summed as 64-bit fixed-point integers, the
+// counts in LDS while the [N][N] tile fits, else in the utterance's scratch) and beam_loss_tr_reduce (the utterances in
+// ascending order).  NO FLOAT ATOMICS anywhere.  Launch 3, the backward, the end of 4 (Z_K) and the small helpers are the text
+// of asg_beam_lattice.h, shared with asg_beam_loss.hip; WordSets / WordLat tell it what a pair key is and how a pair's edges
+// are walked (the LM step on a separator edge).  Every output, padding row and
 // scratch word that is read is written by these kernels: no memset, so both directions can be captured and replayed.
 #include "asg_common.h"
 #include "asg_kernels.h"
 #include "asg_beam_common.h"
 #include "asg_beam_word_frame.h"  // the frame of the search, the LM walk and the end of a pair
+#include "asg_beam_lattice.h"     // everything behind the search that the token family's loss shares
 
 namespace asg {
 
 namespace {
 
-constexpr int kWL = 1024;                       // forward / backward workgroup
-constexpr int kWS = 256;                        // set / reduction workgroups
-constexpr size_t kWLHead = 256;                 // reduction slots in front of the dynamic LDS
-constexpr size_t kWLLds = 160 * 1024;
-constexpr double kWGammaScale = 4611686018427387904.0;       // 2^62
-constexpr double kWSumScale = 281474976710656.0;              // 2^48: a target's sum of exp(c - max) over < 2^14 candidates
-
-template <typename R> __device__ __forceinline__ R wexp(R x);
-template <> __device__ __forceinline__ float wexp<float>(float x) { return expf(x); }
-template <> __device__ __forceinline__ double wexp<double>(double x) { return ::exp(x); }
-template <typename R> __device__ __forceinline__ R wlog(R x);
-template <> __device__ __forceinline__ float wlog<float>(float x) { return logf(x); }
-template <> __device__ __forceinline__ double wlog<double>(double x) { return ::log(x); }
-template <typename R> __device__ __forceinline__ R wmax(R a, R b) { return b > a ? b : a; }
-
-__device__ __forceinline__ unsigned long long w_fixed(double p, double scale) {
-    return p > 0.0 ? (unsigned long long) (p * scale) : 0ull;
-}
-
-// position of pair p in the ascending list a[0 .. n), -1 if absent
-__device__ __forceinline__ int find_pair(const unsigned long long *a, int n, unsigned long long p) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (a[mid] < p) lo = mid + 1; else hi = mid;
-    }
-    return (lo < n && a[lo] == p) ? lo : -1;
-}
-
-template <typename R> __device__ __forceinline__ R wgroup_max(R v, int G) {
-    for (int o = 1; o < G; o <<= 1) v = wmax(v, (R) __shfl_xor(v, o));
-    return v;
-}
-template <typename R> __device__ __forceinline__ R wgroup_sum(R v, int G) {
-    for (int o = 1; o < G; o <<= 1) v += (R) __shfl_xor(v, o);
-    return v;
-}
-template <typename R>
-__device__ R wwg_max(R v, R *red) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    v = wgroup_max(v, 64);
-    if (lane == 0) red[w] = v;
-    __syncthreads();
-    v = red[0];
-    for (int s = 1; s < kWL / 64; ++s) v = wmax(v, red[s]);
-    __syncthreads();
-    return v;
-}
-template <typename R>
-__device__ R wwg_sum(R v, R *red) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    v = wgroup_sum(v, 64);
-    if (lane == 0) red[w] = v;
-    __syncthreads();
-    v = red[0];
-    for (int s = 1; s < kWL / 64; ++s) v += red[s];
-    __syncthreads();
-    return v;
-}
-
-// lanes per source pair: the largest power of two <= 64 with G * m <= 1024
-__device__ __forceinline__ int wsubgroup(int m) {
-    int G = 1;
-    while (G < 64 && G * 2 * m <= kWL) G *= 2;
-    return G;
-}
+constexpr double kBSumScale = 281474976710656.0;              // 2^48: a target's sum of exp(c - max) over < 2^14 candidates
 
 // The read-only part of a BeamWordFrame for the kernels that only walk the graph and the LM.
 template <typename R>
@@ -241,92 +179,32 @@ __global__ void __launch_bounds__(64) beam_word_target_scores(Problem P, GraphAr
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// 3: U_t = A_t united with F_t, ascending in pair order, without duplicates.  Block x = utterance; the blocks of y stride over
-// the frames (gridDim.y <= 65535).  Dynamic LDS: u64 [P2], P2 a power of two >= M; a frame sorts only the p2 <= P2 slots its
-// own |A_t| + |F_t| needs.  A pair key is below 2^50: bit 63 flags a duplicate, all other bits set pads.
+// 3: beam_loss_sets<WordSets> (asg_beam_lattice.h).  A key is a pair h << qbits | q, below 2^50.
 // ---------------------------------------------------------------------------------------------------------------------
-__device__ void bitonic_sort64(unsigned long long *v, int P2) {
-    for (int k = 2; k <= P2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int x = threadIdx.x; x < P2; x += kWS) {
-                const int y = x ^ j;
-                if (y > x) {
-                    const unsigned long long a = v[x], c = v[y];
-                    const bool up = (x & k) == 0;
-                    if ((a > c) == up) { v[x] = c; v[y] = a; }
-                }
-            }
-            __syncthreads();
-        }
-}
-
-__global__ void __launch_bounds__(kWS) beam_word_loss_sets(Problem P, BeamWordLossLayout lay, int K, int qbits, int P2, char *work) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    __shared__ int count;
-    unsigned long long *v = (unsigned long long *) lds;
-    const int b = blockIdx.x, tid = threadIdx.x, T = P.T, M = lay.M;
-    char *wb = work + (size_t) b * lay.per;
-    int *nu = (int *) (wb + lay.nu);
-    const int len = clamp_len(P.in_len, b, T);
-    const unsigned long long *fk = (const unsigned long long *) (wb + lay.key);
-    const int n = ((const int *) (wb + lay.hdr))[0];
-    const unsigned long long FLAG = 1ull << 63, BIG = ~FLAG;
-    for (int t = blockIdx.y; t < T; t += gridDim.y) {
-        if (t >= len) { if (tid == 0) nu[t] = 0; continue; }
-        const int *bq = (const int *) (wb + lay.bq) + (int64_t) t * K, *bh = (const int *) (wb + lay.bh) + (int64_t) t * K;
-        int na = ((const int *) (wb + lay.cnt))[t];
-        na = na < 0 ? 0 : (na > K ? K : na);
-        // F_t = { p_k : k - 1 <= t and n - k <= len - 1 - t }, k = 1 .. n
-        int k0 = n - (len - 1 - t), k1 = t + 1;
-        if (k0 < 1) k0 = 1;
-        if (k1 > n) k1 = n;
-        int nf = k1 >= k0 ? k1 - k0 + 1 : 0;
-        if (na + nf > M) nf = M - na;                                           // (cannot happen: n <= lay.nf)
-        int p2 = 2;
-        while (p2 < na + nf) p2 *= 2;                                           // <= P2: na + nf <= M <= P2
-        for (int x = tid; x < p2; x += kWS) {
-            unsigned long long p = BIG;
-            if (x < na) p = ((unsigned long long) (unsigned) bh[x] << qbits) | (unsigned) bq[x];
-            else if (x < na + nf) p = fk[k0 - 1 + (x - na)];
-            v[x] = p;
-        }
-        if (tid == 0) count = 0;
-        __syncthreads();
-        bitonic_sort64(v, p2);
-        // duplicates: flag them in bit 63 (the neighbour's comparison masks it), then blank them and count the rest
-        for (int x = tid; x < p2; x += kWS) {
-            const unsigned long long a = v[x] & BIG;
-            if (x > 0 && a != BIG && a == (v[x - 1] & BIG)) atomicOr(&v[x], FLAG);
-        }
-        __syncthreads();
-        int c = 0;
-        for (int x = tid; x < p2; x += kWS) {
-            if (v[x] & FLAG) v[x] = BIG;
-            else if (v[x] != BIG) ++c;
-        }
-        if (c) atomicAdd(&count, c);
-        __syncthreads();
-        bitonic_sort64(v, p2);
-        const int m = count;
-        unsigned long long *U = (unsigned long long *) (wb + lay.U) + (int64_t) t * M;
-        for (int x = tid; x < m; x += kWS) U[x] = v[x];
-        if (tid == 0) nu[t] = m;
-        __syncthreads();                                                        // v and count are the next frame's
+struct WordSets {
+    using Key = unsigned long long;
+    static constexpr Key kFlag = 1ull << 63;
+    BeamWordLossLayout lay;
+    int K, qbits;
+    __device__ Key kept(const char *wb, int t, int x) const {                 // the search's [T][K] lists bh and bq
+        const int64_t at = (int64_t) t * K + x;
+        return ((Key) (unsigned) ((const int *) (wb + lay.bh))[at] << qbits) | (unsigned) ((const int *) (wb + lay.bq))[at];
     }
-}
+    __device__ const Key *forced(const char *wb) const { return (const Key *) (wb + lay.key); }
+};
 
 // ---------------------------------------------------------------------------------------------------------------------
 // 4: alpha over the U_t, and Z_K.  Dynamic LDS: [reduction slots][ut u64 M][sm u64 M][mk key M].
 // ---------------------------------------------------------------------------------------------------------------------
 template <typename R>
-__global__ void __launch_bounds__(kWL) beam_word_loss_fwd(Problem P, GraphArgs g, BeamGraphArgs bg, WordLmArgs lm,
+__global__ void __launch_bounds__(kBL) beam_word_loss_fwd(Problem P, GraphArgs g, BeamGraphArgs bg, WordLmArgs lm,
                                                           BeamWordLossLayout lay, int store, char *work, R *scores) {
     using KT = Key<R>;
     using KU = typename KT::U;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     R *red = (R *) lds;
     const int M = lay.M;
-    unsigned long long *ut = (unsigned long long *) (lds + kWLHead);      // [M] U_t
+    unsigned long long *ut = (unsigned long long *) (lds + kBLHead);      // [M] U_t
     unsigned long long *sm = ut + M;                                      // [M] sum of exp(c - max), 48 fractional bits
     KU *mk = (KU *) (sm + M);                                             // [M] max candidate as a key, 0: none
     const int tid = threadIdx.x, b = blockIdx.x, T = P.T;
@@ -346,7 +224,7 @@ __global__ void __launch_bounds__(kWL) beam_word_loss_fwd(Problem P, GraphArgs g
     auto tr = [&](int i, int j) -> R { return trm[(int64_t) i * P.ts0 + (int64_t) j * P.ts1]; };
 
     int mp = nu[0];
-    for (int x = tid; x < mp; x += kWL) {
+    for (int x = tid; x < mp; x += kBL) {
         const unsigned long long p = U[x];
         const int q = (int) (p & qmask), h = (int) (p >> f.qbits);
         dev_store(A + x, h == f.lstart ? f.sw[q] + in[(int64_t) f.label[q] * P.is2] : NINF);
@@ -359,9 +237,9 @@ __global__ void __launch_bounds__(kWL) beam_word_loss_fwd(Problem P, GraphArgs g
         const R *Ap = A + (int64_t) (store ? t - 1 : ((t - 1) & 1)) * M;
         R *Arow = A + (int64_t) (store ? t : (t & 1)) * M;
         const R *xt = in + (int64_t) t * P.is0;
-        for (int x = tid; x < mt; x += kWL) { ut[x] = Ut[x]; sm[x] = 0ull; mk[x] = (KU) 0; }
+        for (int x = tid; x < mt; x += kBL) { ut[x] = Ut[x]; sm[x] = 0ull; mk[x] = (KU) 0; }
         __syncthreads();
-        const int G = wsubgroup(mp), per = kWL / G;
+        const int G = subgroup(mp), per = kBL / G;
         for (int pass = 0; pass < 2; ++pass) {
             for (int k0 = 0; k0 < mp; k0 += per) {
                 const int k = k0 + tid / G, lg = tid % G;
@@ -373,11 +251,11 @@ __global__ void __launch_bounds__(kWL) beam_word_loss_fwd(Problem P, GraphArgs g
                 const int j = f.label[qs];
                 auto offer = [&](unsigned long long tp, R c) {
                     if (!(c > NINF)) return;
-                    const int pos = find_pair(ut, mt, tp);
+                    const int pos = find_sorted(ut, mt, tp);
                     if (pos < 0) return;
                     if (pass == 0) atomicMax(mk + pos, KT::enc(c));
                     else {
-                        const unsigned long long fx = w_fixed((double) wexp(c - KT::dec(mk[pos])), kWSumScale);
+                        const unsigned long long fx = to_fixed((double) bexp(c - KT::dec(mk[pos])), kBSumScale);
                         if (fx) atomicAdd(sm + pos, fx);
                     }
                 };
@@ -399,12 +277,12 @@ __global__ void __launch_bounds__(kWL) beam_word_loss_fwd(Problem P, GraphArgs g
             }
             __syncthreads();
         }
-        for (int x = tid; x < mt; x += kWL) {
+        for (int x = tid; x < mt; x += kBL) {
             const KU key = mk[x];
             R v = NINF;
             if (key != 0 && sm[x] != 0ull) {
-                const R s = (R) ((double) sm[x] * (1.0 / kWSumScale));
-                v = (KT::dec(key) + wlog(s)) + xt[(int64_t) f.label[(int) (ut[x] & qmask)] * P.is2];
+                const R s = (R) ((double) sm[x] * (1.0 / kBSumScale));
+                v = (KT::dec(key) + blog(s)) + xt[(int64_t) f.label[(int) (ut[x] & qmask)] * P.is2];
             }
             dev_store(Arow + x, v);
         }
@@ -423,186 +301,51 @@ __global__ void __launch_bounds__(kWL) beam_word_loss_fwd(Problem P, GraphArgs g
         if (!(a > NINF) || !word_end<R>(f, fw, (int) (p >> f.qbits), (int) (p & qmask), a, e, w)) return NINF;
         return e;
     };
-    R m = NINF;
-    for (int x = tid; x < mp; x += kWL) m = wmax(m, end_of(x));
-    m = wwg_max(m, red);
-    R Z = NINF;
-    if (m > NINF) {
-        R s = R(0);
-        for (int x = tid; x < mp; x += kWL) {
-            const R e = end_of(x);
-            if (e > NINF) s += wexp(e - m);
-        }
-        s = wwg_sum(s, red);
-        Z = m + wlog(s);
-    }
+    const R Z = lattice_z<R>(mp, red, end_of);
     if (tid == 0) scores[b] = Z;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Backward.  Dynamic LDS: [reduction slots][nq u64 M][nb R M][gi u64 N][tile u64 N*N if TL].
+// Backward: beam_loss_bwd<R, TL, WordLat<R>> (asg_beam_lattice.h).  beta PULLS: a pair's own outgoing row is a gather against
+// U_{t+1} in LDS; a separator edge walks the LM.
 // ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int wtile_shift(int len) {       // fractional bits of an utterance's (i, j) counts
-    int c = 0;
-    while ((1 << c) < len && c < 30) ++c;
-    return 62 - c;
-}
-
-__host__ __device__ inline size_t wbwd_front(int elem, int M) { return ((size_t) M * (8 + elem) + 15) & ~(size_t) 15; }
-
-template <typename R, bool TL>
-__global__ void __launch_bounds__(kWL) beam_word_loss_bwd(Problem P, GraphArgs g, BeamGraphArgs bg, WordLmArgs lm,
-                                                          BeamWordLossLayout lay, const char *work, const R *Zs, const R *gs, R *gin,
-                                                          char *scratch, size_t sper) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    const int M = lay.M, N = P.N, T = P.T;
-    unsigned long long *nq = (unsigned long long *) (lds + kWLHead);      // [M] U_t
-    R *nb = (R *) (nq + M);                                               // [M] beta[t] of U_t
-    unsigned long long *gi = (unsigned long long *) (lds + kWLHead + wbwd_front(sizeof(R), M));
-    const int tid = threadIdx.x, b = blockIdx.x;
-    const int64_t B = P.B;
-    const R NINF = Num<R>::ninf();
-    const int len = clamp_len(P.in_len, b, T);
-    const R Z = Zs[b], gb = gs[b];
-    const bool ok = len >= 1 && Z > NINF;
-    char *sb = scratch + (size_t) b * sper;
-    R *Bv = (R *) sb;                                                          // [2][M]
-    unsigned long long *gtile = (unsigned long long *) (sb + a256(2 * (size_t) M * sizeof(R)));
-    unsigned long long *tile = TL ? gi + N : gtile;
-    const int t0 = ok ? len : 0;
-    for (int64_t x = tid; x < (int64_t) (T - t0) * N; x += kWL) gin[((int64_t) (t0 + x / N) * B + b) * N + x % N] = R(0);
-    for (int x = tid; x < N * N; x += kWL) tile[x] = 0ull;
-    if (!ok) {
-        if (TL) for (int x = tid; x < N * N; x += kWL) gtile[x] = 0ull;
-        return;
-    }
-    for (int x = tid; x < N; x += kWL) gi[x] = 0ull;
-    const char *wb = work + (size_t) b * lay.per;
-    const unsigned long long *U = (const unsigned long long *) (wb + lay.U);
-    const int *nu = (const int *) (wb + lay.nu);
-    const R *A = (const R *) (wb + lay.A);
-    const R *in = (const R *) P.inputs + (int64_t) b * P.is1;
-    const R *trm = (const R *) P.transition;
-    const R *fw = (const R *) g.final_w;
-    BeamWordFrame<R> f;
-    bind_walk<R>(f, g, bg, lm);
-    const unsigned long long qmask = (1ull << f.qbits) - 1ull;
-    auto tr = [&](int i, int j) -> R { return trm[(int64_t) i * P.ts0 + (int64_t) j * P.ts1]; };
-    const double tscale = (double) (1ull << wtile_shift(len));
-
-    int mt = nu[len - 1];
-    for (int x = tid; x < mt; x += kWL) {
-        const unsigned long long p = U[(int64_t) (len - 1) * M + x];
-        R e;
-        int w;
-        nq[x] = p;
-        nb[x] = word_end<R>(f, fw, (int) (p >> f.qbits), (int) (p & qmask), (R) 0, e, w) ? e : NINF;
-    }
-    __threadfence();
-    __syncthreads();
-    for (int t = len - 1; t >= 0; --t) {
-        const R *At = A + (int64_t) t * M;
-        for (int x = tid; x < mt; x += kWL) {
-            const R gam = wexp((At[x] + nb[x]) - Z);
-            const unsigned long long fx = w_fixed((double) gam, kWGammaScale);
-            if (fx) atomicAdd(&gi[f.label[(int) (nq[x] & qmask)]], fx);
-        }
-        __syncthreads();
-        for (int i = tid; i < N; i += kWL) {
-            gin[((int64_t) t * B + b) * N + i] = gb * (R) ((double) gi[i] * (1.0 / kWGammaScale));
-            gi[i] = 0ull;
-        }
-        if (t == 0) break;
-        const int mp = nu[t - 1];
-        const unsigned long long *Up = U + (int64_t) (t - 1) * M;
-        const R *Ap = A + (int64_t) (t - 1) * M;
-        R *Brow = Bv + (int64_t) ((t - 1) & 1) * M;
-        const R *xt = in + (int64_t) t * P.is0;
-        const int G = wsubgroup(mp), per = kWL / G;
-        for (int k0 = 0; k0 < mp; k0 += per) {
-            const int k = k0 + tid / G, lg = tid % G;
-            const bool act = k < mp;
-            const unsigned long long pp = act ? Up[k] : 0ull;
-            const int qp = (int) (pp & qmask), hp = (int) (pp >> f.qbits);
-            const int ip = act ? f.label[qp] : 0;
-            const int e0 = act ? f.orow[qp] : 0, e1 = act ? f.orow[qp + 1] : 0;
-            // every surviving candidate out of the pair that this lane owns: fn(value, label of the target)
-            auto visit = [&](auto fn) {
-                if (!act) return;
-                if (lg == 0) {
-                    const int pos = find_pair(nq, mt, pp);
-                    if (pos >= 0) fn((nb[pos] + tr(ip, ip)) + xt[(int64_t) ip * P.is2], ip);
-                }
-                for (int e = e0 + lg; e < e1; e += G) {
-                    const int2 arc = f.oarc[e];
-                    int th = hp;
-                    R w = f.ow[e];
-                    if (arc.y == f.sep) {
-                        R add;
-                        int h2;
-                        if (!f.step(hp, f.wos[f.state[qp]], h2, add)) continue;
-                        th = h2;
-                        w = w + add;
-                    }
-                    const int pos = find_pair(nq, mt, f.pair(th, arc.x));
-                    if (pos >= 0) fn(((nb[pos] + tr(arc.y, ip)) + w) + xt[(int64_t) arc.y * P.is2], arc.y);
-                }
-            };
-            R mx = NINF;
-            visit([&](R c, int) { mx = wmax(mx, c); });
-            mx = wgroup_max(mx, G);
-            R s = R(0);
-            if (mx > NINF) {
-                const R a = Ap[k < mp ? k : 0];
-                visit([&](R c, int i) {
-                    if (!(c > NINF)) return;
-                    s += wexp(c - mx);
-                    const unsigned long long fx = w_fixed((double) wexp((a + c) - Z), tscale);
-                    if (fx) atomicAdd(&tile[(int64_t) i * N + ip], fx);
-                });
-            }
-            s = wgroup_sum(s, G);
-            if (act && lg == 0) dev_store(Brow + k, mx > NINF ? mx + wlog(s) : NINF);
-        }
-        __threadfence();
-        __syncthreads();
-        for (int x = tid; x < mp; x += kWL) { nq[x] = Up[x]; nb[x] = dev_load(Brow + x); }
-        mt = mp;
-        __syncthreads();
-    }
-    if (TL) {
-        __syncthreads();
-        for (int x = tid; x < N * N; x += kWL) gtile[x] = tile[x];
-    }
-}
-
-// grad_transition[i][j] (+)= sum over the utterances, ascending, of grad_scores[b] * tile_b[i][j]
 template <typename R>
-__global__ void __launch_bounds__(kWS) beam_word_loss_tr_reduce(Problem P, int M, const char *scratch, size_t sper, const R *Zs,
-                                                                const R *gs, int accumulate, R *gtr) {
-    const int x = blockIdx.x * kWS + threadIdx.x, N = P.N;
-    if (x >= N * N) return;
-    R s = accumulate ? gtr[x] : R(0);
-    const size_t toff = a256(2 * (size_t) M * sizeof(R));
-    for (int b = 0; b < P.B; ++b) {
-        const int len = clamp_len(P.in_len, b, P.T);
-        if (len < 1 || !(Zs[b] > Num<R>::ninf())) continue;
-        const unsigned long long v = ((const unsigned long long *) (scratch + (size_t) b * sper + toff))[x];
-        s += gs[b] * (R) ((double) v / (double) (1ull << wtile_shift(len)));
+struct WordLat {
+    using Key = unsigned long long;
+    struct Args { GraphArgs g; BeamGraphArgs bg; WordLmArgs lm; BeamWordLossLayout lay; };
+    BeamWordFrame<R> f;
+    const R *fw;
+    Key qmask;
+    __device__ void bind(const Args &a) {
+        bind_walk<R>(f, a.g, a.bg, a.lm);
+        fw = (const R *) a.g.final_w;
+        qmask = (1ull << f.qbits) - 1ull;
     }
-    gtr[x] = s;
-}
+    __device__ int label(Key p) const { return f.label[(int) (p & qmask)]; }
+    __device__ void end(Key p, R &e) const {
+        int w;
+        if (!word_end<R>(f, fw, (int) (p >> f.qbits), (int) (p & qmask), (R) 0, e, w)) e = Num<R>::ninf();
+    }
+    template <typename F> __device__ void for_each_out(Key p, int lg, int G, F fn) const {
+        const int q = (int) (p & qmask), h = (int) (p >> f.qbits);
+        const int e1 = f.orow[q + 1];
+        for (int e = f.orow[q] + lg; e < e1; e += G) {
+            const int2 arc = f.oarc[e];
+            int th = h;
+            R w = f.ow[e];
+            if (arc.y == f.sep) {                                             // a word ends: the LM moves
+                R add;
+                int h2;
+                if (!f.step(h, f.wos[f.state[q]], h2, add)) continue;
+                th = h2;
+                w = w + add;
+            }
+            fn(f.pair(th, arc.x), [&]() -> R { return w; }, arc.y);
+        }
+    }
+};
 
-inline size_t wfwd_lds(int elem, int M) { return kWLHead + (size_t) M * (16 + elem); }
-inline size_t wbwd_lds(int elem, int M, int N, bool tl) {
-    return kWLHead + wbwd_front(elem, M) + (size_t) N * 8 + (tl ? (size_t) N * N * 8 : 0);
-}
-
-// a launch whose LDS -- dynamic plus the kernel's own `fixed` static bytes -- passes 64 KiB has to ask for it
-inline void wset_lds(const void *fn, size_t dyn, size_t fixed = 0) {
-    if (dyn + fixed > 64 * 1024) (void) hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) dyn);
-}
-
+inline size_t wfwd_lds(int elem, int M) { return kBLHead + (size_t) M * (16 + elem); }
 }  // namespace
 
 BeamWordLossLayout beam_word_loss_layout(int elem, int T, int K, int cap, int nf, bool store) {
@@ -627,12 +370,10 @@ size_t beam_word_loss_work_bytes(int elem, int T, int B, int K, int cap, int nf,
     return (size_t) B * beam_word_loss_layout(elem, T, K, cap, nf, store).per;
 }
 
-size_t beam_word_loss_scratch_per(int elem, int M, int N) { return a256(2 * (size_t) M * elem) + a256((size_t) N * N * 8); }
-
 // THE bound on M = K + nf: a frame's lattice set with the maximum and the sum of every member (forward), and with its beta
 // and the label posteriors (backward), stays in 160 KiB of LDS.
 bool beam_word_loss_fits(int elem, int M, int N) {
-    return wfwd_lds(elem, M) <= kWLLds && wbwd_lds(elem, M, N, false) <= kWLLds;
+    return wfwd_lds(elem, M) <= kBLLds && bwd_lds(elem, 8, M, N, false) <= kBLLds;
 }
 
 template <typename R>
@@ -649,11 +390,11 @@ hipError_t launch_beam_word_loss_forward(const Problem &P, const GraphArgs &G, c
         const bool trl = beam + (size_t) N * N * sizeof(R) <= kLdsMax;
         const size_t dyn = beam + (trl ? (size_t) N * N * sizeof(R) : 0);
         if (trl) {
-            wset_lds((const void *) beam_word_loss_search<R, true>, dyn);
+            set_lds((const void *) beam_word_loss_search<R, true>, dyn);
             hipLaunchKernelGGL((beam_word_loss_search<R, true>), dim3(B), dim3(kBT), dyn, stream, P, G, BG, LM, K, (R) theta, cap,
                                tbits, w, lay.per, lay.cnt);
         } else {
-            wset_lds((const void *) beam_word_loss_search<R, false>, dyn);
+            set_lds((const void *) beam_word_loss_search<R, false>, dyn);
             hipLaunchKernelGGL((beam_word_loss_search<R, false>), dim3(B), dim3(kBT), dyn, stream, P, G, BG, LM, K, (R) theta, cap,
                                tbits, w, lay.per, lay.cnt);
         }
@@ -661,18 +402,13 @@ hipError_t launch_beam_word_loss_forward(const Problem &P, const GraphArgs &G, c
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((beam_word_loss_targets<R>), dim3((B + 63) / 64), dim3(64), 0, stream, P, G, BG, LM, lay, w);
-    int P2 = 2;
-    while (P2 < lay.M) P2 *= 2;
     int qbits = 1;
     while (((int64_t) 1 << qbits) < G.Q) ++qbits;                                // (bits_of on the host)
-    wset_lds((const void *) beam_word_loss_sets, (size_t) P2 * 8, sizeof(int));
-    hipLaunchKernelGGL(beam_word_loss_sets, dim3(B, T < 65535 ? T : 65535), dim3(kWS), (size_t) P2 * 8, stream, P, lay, K, qbits,
-                       P2, w);
-    e = hipGetLastError();
+    e = launch_beam_loss_sets(P, WordSets{lay, K, qbits}, w, stream);
     if (e != hipSuccess) return e;
     const size_t dyn = wfwd_lds(sizeof(R), lay.M);
-    wset_lds((const void *) beam_word_loss_fwd<R>, dyn);
-    hipLaunchKernelGGL((beam_word_loss_fwd<R>), dim3(B), dim3(kWL), dyn, stream, P, G, BG, LM, lay, (int) store, w, (R *) scores);
+    set_lds((const void *) beam_word_loss_fwd<R>, dyn);
+    hipLaunchKernelGGL((beam_word_loss_fwd<R>), dim3(B), dim3(kBL), dyn, stream, P, G, BG, LM, lay, (int) store, w, (R *) scores);
     return hipGetLastError();
 }
 
@@ -680,28 +416,11 @@ template <typename R>
 hipError_t launch_beam_word_loss_backward(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int K,
                                           const void *work, const void *scores, const void *grad_scores, void *grad_inputs,
                                           void *grad_transition, void *scratch, bool accumulate, hipStream_t stream) {
-    const int T = P.T, B = P.B, N = P.N;
+    const int T = P.T;
     const int cap = beam_word_cap(K, BG.max_out, BG.num_start);
     const int nf = P.targets ? (P.S < T ? P.S : T) : 0;
-    const BeamWordLossLayout lay = beam_word_loss_layout(sizeof(R), T, K, cap, nf, true);
-    const size_t sper = beam_word_loss_scratch_per(sizeof(R), lay.M, N);
-    const bool tl = wbwd_lds(sizeof(R), lay.M, N, true) <= kWLLds;
-    const size_t dyn = wbwd_lds(sizeof(R), lay.M, N, tl);
-    if (tl) {
-        wset_lds((const void *) beam_word_loss_bwd<R, true>, dyn);
-        hipLaunchKernelGGL((beam_word_loss_bwd<R, true>), dim3(B), dim3(kWL), dyn, stream, P, G, BG, LM, lay, (const char *) work,
-                           (const R *) scores, (const R *) grad_scores, (R *) grad_inputs, (char *) scratch, sper);
-    } else {
-        wset_lds((const void *) beam_word_loss_bwd<R, false>, dyn);
-        hipLaunchKernelGGL((beam_word_loss_bwd<R, false>), dim3(B), dim3(kWL), dyn, stream, P, G, BG, LM, lay, (const char *) work,
-                           (const R *) scores, (const R *) grad_scores, (R *) grad_inputs, (char *) scratch, sper);
-    }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((beam_word_loss_tr_reduce<R>), dim3((N * N + kWS - 1) / kWS), dim3(kWS), 0, stream, P, lay.M,
-                       (const char *) scratch, sper, (const R *) scores, (const R *) grad_scores, (int) accumulate,
-                       (R *) grad_transition);
-    return hipGetLastError();
+    return launch_lattice_backward<R, WordLat<R>>(P, {G, BG, LM, beam_word_loss_layout(sizeof(R), T, K, cap, nf, true)}, work, scores,
+                                                  grad_scores, grad_inputs, grad_transition, scratch, accumulate, stream);
 }
 
 template <typename R>

@@ -393,7 +393,7 @@ struct BeamWordLossLayout {
 };
 BeamWordLossLayout beam_word_loss_layout(int elem, int T, int K, int cap, int nf, bool store);
 size_t beam_word_loss_work_bytes(int elem, int T, int B, int K, int cap, int nf, bool store);
-size_t beam_word_loss_scratch_per(int elem, int M, int N);
+inline size_t beam_word_loss_scratch_per(int elem, int M, int N) { return beam_loss_scratch_per(elem, M, N); }   // the same pass
 // the one bound on M: a frame's lattice set with a maximum and a sum per member stays in LDS (M <= 8179 float32, 6816 float64)
 bool beam_word_loss_fits(int elem, int M, int N);
 template <typename R>
