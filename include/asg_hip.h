@@ -482,7 +482,8 @@ int asg_beam_decode_words(asg_ctx *ctx, const asg_problem *p, const asg_token_gr
  * step(h, w) and PAIR ORDER exactly as in asg_beam_decode_words:
  *   1. Kept sets.  A_t, t = 0 .. len-1, are exactly the sets of pairs asg_beam_decode_words keeps for the same emissions,
  *      transition, lexicon, LM, beam_size, beam_threshold, computed in the dtype of the problem (the same device code runs).  They
- *      are a discrete function of the inputs and constants to the gradient.  No look-ahead.
+ *      are a discrete function of the inputs and constants to the gradient.  No look-ahead (asg_beam_words_full_forward_la, below,
+ *      takes the sets of the look-ahead search).
  *   2. Forced pairs (only when p->targets is given).  y = targets[b][:clamp(target_lengths[b], 0, S)] with consecutive equal
  *      labels merged, n = |y|.  The lexicon automaton is walked along y from the start with h = start; on a separator out of a
  *      word-end node (h, a) = step(h, word of the node).  This gives p_k = (h_k, q_k), k = 1 .. n, and
@@ -537,6 +538,41 @@ int asg_beam_words_full_backward(asg_ctx *ctx, const asg_problem *p, const asg_t
                                  void *stream);
 int asg_words_target_scores(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm, void *out,
                             void *stream);
+
+/* ---- asg_beam_words_full_forward with the sets of a LOOK-AHEAD search: the normaliser over what asg_beam_decode_words_la (below)
+ * keeps, so a criterion can be trained against the lattice a look-ahead decoder searches at test time.  `la` is that call's
+ * look-ahead (asg_word_lookahead, below), built for the same lexicon, LM and folding.  No counterpart in the reference.
+ *   1. Kept sets.  A_t, t = 0 .. len-1, are exactly the sets of pairs asg_beam_decode_words_la keeps for the same emissions,
+ *      transition, lexicon, LM, look-ahead, beam_size and beam_threshold, bit for bit: the same device code runs -- the dead-end
+ *      prune on entry (an edge into a node n with L(h, n) = -inf is no candidate), and the candidates ranked and pruned by their
+ *      values WITH L(h, state(q)) included.  The sets are constants of the gradient.
+ *   2. Forced pairs.  F_t exactly as in asg_beam_words_full_forward.  The look-ahead does not enter the walk of the target (a
+ *      target through a dead-end node is forced in like any other, and its end then rejects it: every F_t empty), and the forced
+ *      pairs do not feed back into the search.
+ *   3. Lattice.  Step 3 of asg_beam_words_full_forward verbatim over U_t = A_t united with F_t, with the PLAIN weights: no
+ *      look-ahead term in alpha, beta, the end or the gradients.  Why: the look-ahead changes a pair's value by L(h, state(q)),
+ *      which is 0 at the root and taken back on the separator edge or at the end, so along every complete path the terms
+ *      telescope to zero and the sum over the complete paths of a lattice is the same real number with or without them.
+ *      Carrying them would only add the rounding of terms that cancel, and would make the forward and backward kernels read the
+ *      tables.  The look-ahead decides WHICH pairs are in the lattice and nothing else.
+ *   4. With targets a finite scores[b] - (aligned score + asg_words_target_scores) is >= 0 for any beam, as before: the target is
+ *      forced in.  Without targets Z_K >= the plain path score (asg_beam_decode_words' sums, no cancelling terms) of the path
+ *      asg_beam_decode_words_la returns, since that path runs through the A_t; this is >= that call's `scores` exactly when no
+ *      sum rounds (weights and emissions in eighths, say), otherwise up to the rounding of the cancelling terms.  With a beam
+ *      that prunes nothing (beam_size >= the pairs of any frame, beam_threshold = +inf) and no dead-end node, U_t is
+ *      asg_beam_words_full_forward's: scores and both gradients have that call's bits.  A dead-end node (no word below it that
+ *      the LM accepts after h) never lies on a complete path and leads only to other dead ends, so leaving its pairs out removes
+ *      members whose beta and end are -inf and changes no other member's alpha: Z_K and both gradients are the same real
+ *      numbers as with those pairs in.  Not a promise of the same bits: alpha is (integer reductions), but the members that
+ *      remain change place in the floating-point sums of Z_K and of beta, so there the two agree up to that rounding.
+ * asg_beam_words_full_backward, asg_beam_words_full_work_bytes and asg_beam_words_full_scratch_bytes serve both forms unchanged:
+ * the backward reads the stored U and alpha only, and the look-ahead has no workspace of its own.  Launches, determinism and
+ * capture as asg_beam_words_full_forward.  Limits and errors: that call's, then asg_beam_decode_words_la's for `la` (a NULL
+ * look-ahead or array, another dtype, a bad A' or levels, S or H other than the LM's: ASG_ERR_INVALID). */
+struct asg_word_lookahead;
+int asg_beam_words_full_forward_la(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                   const struct asg_word_lookahead *la, int beam_size, double beam_threshold, void *work,
+                                   size_t work_bytes, void *scores, int flags, void *stream);
 
 /* ---- asg_beam_decode_words with LM LOOK-AHEAD: inside a word, a pair's value also carries the best LM score that any word below
  * its trie node can still get after the pair's history, so that a narrow beam ranks partial words by more than acoustics.  The

@@ -37,7 +37,7 @@ SYMBOLS = ["asg_hip_version", "asg_hip_strerror", "asg_ctx_create", "asg_ctx_des
            "asg_beam_word_window_result", "asg_beam_word_stream_advance_la", "asg_beam_word_stream_result_la",
            "asg_beam_word_window_advance_la", "asg_beam_word_window_result_la",
            "asg_beam_words_full_work_bytes", "asg_beam_words_full_scratch_bytes", "asg_beam_words_full_forward",
-           "asg_beam_words_full_backward", "asg_words_target_scores"]
+           "asg_beam_words_full_backward", "asg_words_target_scores", "asg_beam_words_full_forward_la"]
 ABI_VERSION = 230        # include/asg_hip.h: ASG_HIP_VERSION this package was written against
 
 
@@ -195,6 +195,8 @@ def lib():
     L.asg_beam_words_full_scratch_bytes.restype = sz
     L.asg_beam_words_full_scratch_bytes.argtypes = [pp, bp, wp, ci]
     L.asg_beam_words_full_forward.argtypes = [vp, pp, bp, wp, ci, ctypes.c_double, vp, sz, vp, ci, vp]
+    L.asg_beam_words_full_forward_la.argtypes = [vp, pp, bp, wp, ctypes.POINTER(AsgWordLookahead), ci, ctypes.c_double, vp, sz, vp,
+                                                 ci, vp]
     L.asg_beam_words_full_backward.argtypes = [vp, pp, bp, wp, ci, vp, sz, vp, vp, vp, vp, vp, sz, ci, vp]
     L.asg_words_target_scores.argtypes = [vp, pp, bp, wp, vp, vp]
     lp = ctypes.POINTER(AsgTokenGraphLoss)

@@ -622,21 +622,24 @@ class HipBackend:
                          target_lengths, store, max_work_bytes, flags=0):
         """The forward of the graph loss and of the two beam-pruned losses -> (scores[B], saved).  `entry` / `sizer` name the
         library's *_full_forward / *_full_work_bytes; `prepare()`, called under the device guard, checks the family's
-        arguments and returns (the ctypes views that follow the problem in both calls, Q, what those views point into); `size_args` / `call_args` are what
-        follows the views in the size call (before `store`) and in the forward (before the workspace)."""
+        arguments and returns (the ctypes views that follow the problem in both calls, Q, what those views point into) and,
+        as an optional fourth element, the views that follow those in the forward alone (a look-ahead: it sizes nothing);
+        `size_args` / `call_args` are what follows the views in the size call (before `store`) and in the forward (before the
+        workspace)."""
         L = _lib.lib()
         forward, work_bytes = getattr(L, entry), getattr(L, sizer)
         dev = inputs.device
         B = inputs.shape[1]
         with self._guard(dev):
-            views, Q, keep = prepare()
+            views, Q, keep, *only = prepare()
             p, targets, input_lengths, target_lengths = self._device_problem(inputs, transition, targets, input_lengths,
                                                                              target_lengths)
             fl = flags | (_lib.FLAG_GRAPH_LOSS_KEEP_ALPHA if store else 0)
             head = [ctypes.byref(p)] + [ctypes.byref(v) for v in views]
+            tail = [ctypes.byref(v) for v in (only[0] if only else ())]
 
             def call(work, nbytes, scores, stream):
-                return forward(None, *head, *call_args, work, nbytes, scores, fl, stream)
+                return forward(None, *head, *tail, *call_args, work, nbytes, scores, fl, stream)
             groups = self._groups(p, B, max_work_bytes, lambda: work_bytes(*head, *size_args, int(store)), Q,
                                   lambda: _lib.check(call(None, 0, None, None), entry),
                                   inputs, targets, input_lengths, target_lengths, store=store)
@@ -768,26 +771,36 @@ class HipBackend:
                        "asg_graph_target_scores")
         return out
 
-    def _word_loss_args(self, inputs, transition, lexicon, word_lm, input_lengths, targets, target_lengths, weights):
+    def _word_loss_args(self, inputs, transition, lexicon, word_lm, input_lengths, targets, target_lengths, weights,
+                        lookahead=None):
         """Checks shared by the pair-loss entry points -> ((the lexicon's asg_token_graph_beam view, the asg_word_lm view), Q,
         the compiled dicts they point into), through the caches of `Lexicon.compile_words` and `WordLM.compile`:
-        `_lattice_forward`'s `prepare`."""
+        `_lattice_forward`'s `prepare`.  With a `WordLookahead`, checked before anything looks at the device and compiled with
+        the call's lm_weight and word_score through its own cache, a fourth element: (the asg_word_lookahead view,)."""
         from . import wordlm as _wordlm
         _wordlm.check_words(lexicon, word_lm)
+        if lookahead is not None:
+            _wordlm.check_lookahead(lookahead, lexicon, word_lm)
         self._check_graph_inputs(inputs, transition, lexicon.graph, input_lengths, targets, target_lengths)
         g, w, keep = _wordlm.abi_words(lexicon, word_lm, inputs.device, inputs.dtype, *weights)
-        return (g, w), keep[0]["Q"], keep
+        if lookahead is None:
+            return (g, w), keep[0]["Q"], keep
+        la_dev = lookahead.compile(inputs.device, inputs.dtype, weights[0], weights[1])
+        return (g, w), keep[0]["Q"], keep + (la_dev,), (_wordlm.abi_lookahead(la_dev),)
 
     def beam_words_full_forward(self, inputs, transition, lexicon, word_lm, input_lengths, beam_size, beam_threshold=float("inf"),
                                 lm_weight=1.0, word_score=0.0, token_score=0.0, targets=None, target_lengths=None, store=False,
-                                max_work_bytes=1 << 30):
+                                max_work_bytes=1 << 30, lookahead=None):
         """Beam-pruned full score over the pairs `beam_decode_words` keeps -> (scores[B], saved); see
-        include/asg_hip.h::asg_beam_words_full_forward.  Grouped and saved as `beam_graph_full_forward` does."""
+        include/asg_hip.h::asg_beam_words_full_forward and, with a `WordLookahead` (the sets of
+        `beam_decode_words(..., lookahead=)`), asg_beam_words_full_forward_la.  Grouped and saved as `beam_graph_full_forward`
+        does; `beam_words_full_backward` serves both."""
         beam_size, beam_threshold = min(int(beam_size), (1 << 31) - 1), float(beam_threshold)
         return self._lattice_forward(
-            "asg_beam_words_full_forward", "asg_beam_words_full_work_bytes",
+            "asg_beam_words_full_forward" if lookahead is None else "asg_beam_words_full_forward_la",
+            "asg_beam_words_full_work_bytes",
             lambda: self._word_loss_args(inputs, transition, lexicon, word_lm, input_lengths, targets, target_lengths,
-                                         (lm_weight, word_score, token_score)),
+                                         (lm_weight, word_score, token_score), lookahead),
             (beam_size,), (beam_size, beam_threshold), inputs, transition, targets, input_lengths, target_lengths, store,
             max_work_bytes)
 
@@ -1313,12 +1326,13 @@ def _guarded_targets(targets, target_lengths, N):
 
 
 def _graph_loss(inputs, targets, transition, graph, input_lengths, target_lengths, lm_weight, token_score, max_work_bytes,
-                reduction, beam=None, weights=None, words=None):
+                reduction, beam=None, weights=None, words=None, lookahead=None):
     """What the graph losses share.  [B] losses full - (FAC + A(collapse(target))), then `weights(inputs, input_lengths,
     target_lengths)` (None: none) and the reduction; `full` is the exact normaliser (`GraphFullScore`), or with beam =
     (beam_size, beam_threshold) the beam-pruned one with the target forced into the lattice (`BeamGraphFullScore`).  With
     words = (word_lm, word_score), `graph` is a `Lexicon`, the normaliser runs over the pairs of `beam_decode_words`
-    (`BeamWordsFullScore`; `beam` is required) and A is the lexicon + LM score of the target (`words_target_scores`).  A loss is
+    (`BeamWordsFullScore`; `beam` is required; with `lookahead` the pairs of `beam_decode_words(..., lookahead=)`) and A is
+    the lexicon + LM score of the target (`words_target_scores`, which no look-ahead enters).  A loss is
     +inf (never NaN) where the target has no alignment, the automaton rejects it or it holds a label outside [0, N)
     (`_guarded_targets`), and then only the normaliser's posterior reaches the gradients.  Defaults, S > T truncation and
     widening as `ASGLoss.forward`."""
@@ -1326,7 +1340,7 @@ def _graph_loss(inputs, targets, transition, graph, input_lengths, target_length
     targets, input_lengths, target_lengths = ASGLoss._canonical(inputs, targets, input_lengths, target_lengths)
     if words is not None:
         full = BeamWordsFullScore.apply(inputs, transition, graph, words[0], input_lengths, *beam, lm_weight, words[1],
-                                        token_score, targets, target_lengths, max_work_bytes)
+                                        token_score, targets, target_lengths, max_work_bytes, lookahead)
     elif beam is None:
         full = GraphFullScore.apply(inputs, transition, graph, input_lengths, lm_weight, token_score, max_work_bytes, 0)
     else:
@@ -1428,16 +1442,18 @@ def beam_graph_asg_loss(inputs, targets, transition, graph, input_lengths=None, 
 
 class BeamWordsFullScore(torch.autograd.Function):
     """Beam-pruned full score of the ASG lattice composed with a lexicon and a word LM over the pairs `beam_decode_words`
-    keeps, [B] (asg_beam_words_full_forward / _backward).  The kept sets are constants of the gradient; alpha is stored only
-    when a gradient w.r.t. inputs or transition is needed.  Once differentiable."""
+    keeps, [B] (asg_beam_words_full_forward / _backward) -- with `lookahead`, the pairs `beam_decode_words(..., lookahead=)`
+    keeps (asg_beam_words_full_forward_la; the backward reads the stored lattice and does not need it).  The kept sets are
+    constants of the gradient; alpha is stored only when a gradient w.r.t. inputs or transition is needed.  Once
+    differentiable."""
 
     @staticmethod
     def forward(ctx, inputs, transition, lexicon, word_lm, input_lengths, beam_size, beam_threshold, lm_weight, word_score,
-                token_score, targets, target_lengths, max_work_bytes):
+                token_score, targets, target_lengths, max_work_bytes, lookahead=None):
         store = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
         scores, saved = native().beam_words_full_forward(inputs, transition, lexicon, word_lm, input_lengths, beam_size,
                                                          beam_threshold, lm_weight, word_score, token_score, targets,
-                                                         target_lengths, store, max_work_bytes)
+                                                         target_lengths, store, max_work_bytes, lookahead)
         ctx.save_for_backward(inputs, transition, input_lengths, targets, target_lengths, scores)
         ctx.saved, ctx.words, ctx.args = saved, (lexicon, word_lm), (beam_size, lm_weight, word_score, token_score)
         return scores
@@ -1449,12 +1465,12 @@ class BeamWordsFullScore(torch.autograd.Function):
         K, lw, ws, ts = ctx.args
         gtr, gin = native().beam_words_full_backward(ctx.saved, scores, grad, inputs, transition, *ctx.words, input_lengths, K,
                                                      lw, ws, ts, targets, target_lengths)
-        return (gin, gtr) + (None,) * 11
+        return (gin, gtr) + (None,) * 12
 
 
 def beam_words_full_score(inputs, transition, lexicon, word_lm, input_lengths=None, beam_size=256, beam_threshold=float("inf"),
                           lm_weight=1.0, word_score=0.0, token_score=0.0, targets=None, target_lengths=None,
-                          max_work_bytes=1 << 30):
+                          max_work_bytes=1 << 30, lookahead=None):
     """`beam_graph_full_score` over the pairs (LM history, lexicon product state) that `beam_decode_words`' search keeps: the
     logsumexp over the label paths whose pair stays, at every frame, inside the kept set of that frame (the sets of
     `beam_decode_words` for the same arguments without look-ahead, bit for bit) -- and, when `targets` is given, inside those
@@ -1463,24 +1479,33 @@ def beam_words_full_score(inputs, transition, lexicon, word_lm, input_lengths=No
     end of the sentence.  Work and memory follow beam_size, never the sizes of the lexicon or the LM.  Differentiable w.r.t.
     `inputs` and `transition` with the sets held constant; without targets >= `beam_decode_words`' score.  Bit-identical run to
     run and for any `max_work_bytes`.  targets / target_lengths are taken as given (`beam_words_asg_loss` applies defaults and
-    truncation)."""
+    truncation).
+
+    With `lookahead`, a `WordLookahead(lexicon, word_lm, order)`, the sets are those of `beam_decode_words(..., lookahead=)`
+    for the same arguments, bit for bit (asg_beam_words_full_forward_la): the lattice a look-ahead decoder searches at test
+    time.  Only the sets change: a path's score stays the plain one above -- along a complete path the look-ahead terms cancel
+    -- so without targets the score is >= the plain score of the look-ahead decoder's best path, which is that call's score up
+    to the rounding of the cancelling terms.  Work and memory are unchanged; the look-ahead is compiled with the call's
+    lm_weight and word_score through its cache, so a warm call copies nothing."""
     _check_beam(beam_size, beam_threshold)
     return BeamWordsFullScore.apply(_widen(inputs, transition), transition, lexicon, word_lm, input_lengths, beam_size,
-                                    beam_threshold, lm_weight, word_score, token_score, targets, target_lengths, max_work_bytes)
+                                    beam_threshold, lm_weight, word_score, token_score, targets, target_lengths, max_work_bytes,
+                                    lookahead)
 
 
 def beam_words_asg_loss(inputs, targets, transition, lexicon, word_lm, input_lengths=None, target_lengths=None, beam_size=256,
                         beam_threshold=float("inf"), lm_weight=1.0, word_score=0.0, token_score=0.0, reduction='none',
-                        max_work_bytes=1 << 30):
-    """ASG loss against what `beam_decode_words` searches: loss[b] = beam_words_full_score[b] - (S_aligned[b] + the lexicon + LM
-    score of targets[b] with consecutive repeats merged), the target forced into the beam's lattice, so every finite loss is
-    >= 0 (up to rounding) for any beam.  `targets` are token labels that spell words of the lexicon, each followed by the
+                        max_work_bytes=1 << 30, lookahead=None):
+    """ASG loss against what `beam_decode_words` searches (without look-ahead, bit for bit; with `lookahead`, a
+    `WordLookahead`, what `beam_decode_words(..., lookahead=)` searches): loss[b] = beam_words_full_score[b] - (S_aligned[b] +
+    the lexicon + LM score of targets[b] with consecutive repeats merged), the target forced into the beam's lattice, so every
+    finite loss is >= 0 (up to rounding) for any beam, with or without look-ahead.  `targets` are token labels that spell words of the lexicon, each followed by the
     separator or ending the sequence.  +inf (never NaN) where the target cannot be aligned, the lexicon or the LM rejects it,
     it ends mid-word, or it holds a label outside [0, N) within its length; then only the normaliser's posterior reaches the
     gradients.  Defaults and S > T truncation as `ASGLoss.forward`; reduction 'none' (default), 'sum' or 'mean'."""
     _check_beam(beam_size, beam_threshold)
     return _graph_loss(inputs, targets, transition, lexicon, input_lengths, target_lengths, lm_weight, token_score,
-                       max_work_bytes, reduction, (beam_size, beam_threshold), None, (word_lm, word_score))
+                       max_work_bytes, reduction, (beam_size, beam_threshold), None, (word_lm, word_score), lookahead)
 
 
 class FAC(torch.autograd.Function):
@@ -1762,12 +1787,14 @@ class ASGLoss(nn.Module):
                            max_work_bytes, self.reduction, (beam_size, beam_threshold), self._utterance_weights)
 
     def beam_word_loss(self, inputs, targets, lexicon, word_lm, input_lengths=None, target_lengths=None, lm_weight=1.0,
-                       word_score=0.0, token_score=0.0, max_work_bytes=1 << 30, beam_size=256, beam_threshold=float("inf")):
-        """`torch_asg_amd.beam_words_asg_loss` under this module's transition matrix, reduction and scale_mode."""
+                       word_score=0.0, token_score=0.0, max_work_bytes=1 << 30, beam_size=256, beam_threshold=float("inf"),
+                       lookahead=None):
+        """`torch_asg_amd.beam_words_asg_loss` under this module's transition matrix, reduction and scale_mode; `lookahead`
+        takes the sets of `beam_decode_words(..., lookahead=)`."""
         _check_beam(beam_size, beam_threshold)
         return _graph_loss(inputs, targets, self.transition, lexicon, input_lengths, target_lengths, lm_weight, token_score,
                            max_work_bytes, self.reduction, (beam_size, beam_threshold), self._utterance_weights,
-                           (word_lm, word_score))
+                           (word_lm, word_score), lookahead)
 
     @staticmethod
     def _canonical(inputs, targets, input_lengths, target_lengths):

@@ -1355,12 +1355,14 @@ size_t asg_beam_words_full_scratch_bytes(const asg_problem *p, const asg_token_g
     return (size_t) p->B * beam_word_loss_scratch_per(p->dtype == ASG_DTYPE_F64 ? 8 : 4, beam_size + beam_loss_nf(p), (int) p->N);
 }
 
-int asg_beam_words_full_forward(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
-                                int beam_size, double beam_threshold, void *work, size_t work_bytes, void *scores, int flags,
-                                void *stream) {
-    (void) ctx;
+// asg_beam_words_full_forward with a look-ahead (`with_la`: la is checked as asg_beam_decode_words_la checks it, behind the LM) or
+// without one.  Only the search reads it; the workspace has the same bytes either way.
+static int beam_words_full_forward(const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                   const asg_word_lookahead *la, bool with_la, int beam_size, double beam_threshold, void *work,
+                                   size_t work_bytes, void *scores, int flags, void *stream) {
     int rc = check_beam_words_loss(p, gb, lm, beam_size);
     if (rc) return rc;
+    if (with_la && (rc = check_word_lookahead(p->dtype, lm, la)) != ASG_OK) return rc;
     if (!(beam_threshold >= 0.0)) return ASG_ERR_INVALID;                  // negative or NaN
     if (!work || !scores) return ASG_ERR_INVALID;
     const bool store = (flags & ASG_FLAG_GRAPH_LOSS_KEEP_ALPHA) != 0;
@@ -1369,9 +1371,25 @@ int asg_beam_words_full_forward(asg_ctx *ctx, const asg_problem *p, const asg_to
     const GraphArgs G = to_graph_args(gb->graph);
     const BeamGraphArgs BG = to_beam_graph_args(gb);
     const WordLmArgs LM = to_word_lm_args(lm);
+    const WordLookArgs LA = with_la ? to_word_look_args(la) : WordLookArgs{};
+    const WordLookArgs *look = with_la ? &LA : nullptr;
     return hip_status(ASG_DISPATCH(p,
-        launch_beam_word_loss_forward<float>(P, G, BG, LM, beam_size, beam_threshold, store, work, scores, (hipStream_t) stream),
-        launch_beam_word_loss_forward<double>(P, G, BG, LM, beam_size, beam_threshold, store, work, scores, (hipStream_t) stream)));
+        launch_beam_word_loss_forward<float>(P, G, BG, LM, look, beam_size, beam_threshold, store, work, scores, (hipStream_t) stream),
+        launch_beam_word_loss_forward<double>(P, G, BG, LM, look, beam_size, beam_threshold, store, work, scores, (hipStream_t) stream)));
+}
+
+int asg_beam_words_full_forward(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                int beam_size, double beam_threshold, void *work, size_t work_bytes, void *scores, int flags,
+                                void *stream) {
+    (void) ctx;
+    return beam_words_full_forward(p, gb, lm, nullptr, false, beam_size, beam_threshold, work, work_bytes, scores, flags, stream);
+}
+
+int asg_beam_words_full_forward_la(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                   const asg_word_lookahead *la, int beam_size, double beam_threshold, void *work, size_t work_bytes,
+                                   void *scores, int flags, void *stream) {
+    (void) ctx;
+    return beam_words_full_forward(p, gb, lm, la, true, beam_size, beam_threshold, work, work_bytes, scores, flags, stream);
 }
 
 int asg_beam_words_full_backward(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,

@@ -45,11 +45,15 @@ __device__ __forceinline__ void bind_walk(BeamWordFrame<R> &f, const GraphArgs &
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// 1: the search.  beam_word_kernel's frame loop; cnt[t] = |A_t| for t < len.
+// 1: the search.  beam_word_kernel's frame loop; cnt[t] = |A_t| for t < len.  With LA it is beam_word_la_kernel's frame loop
+// (include/asg_hip.h::asg_beam_words_full_forward_la): the frame compiled with the look-ahead flag on, as the two word streams
+// compile theirs, so the sets are the look-ahead decoder's.  The values the frame ranks by stay in LDS: launches 2 - 4 and the
+// backward read the pairs alone and weigh them plainly.
 // ---------------------------------------------------------------------------------------------------------------------
-template <typename R, bool TRL>
+template <typename R, bool TRL, bool LA = false>
 __global__ void __launch_bounds__(kBT) beam_word_loss_search(Problem P, GraphArgs g, BeamGraphArgs bg, WordLmArgs lm, int K, R theta,
-                                                             int cap, int tbits, char *work, size_t per_utt, size_t cnt_off) {
+                                                             int cap, int tbits, char *work, size_t per_utt, size_t cnt_off,
+                                                             WordLookParam<LA> la) {
     using U = typename Key<R>::U;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     Ctl<U> &ctl = *(Ctl<U> *) lds;
@@ -63,10 +67,11 @@ __global__ void __launch_bounds__(kBT) beam_word_loss_search(Problem P, GraphArg
     const int len = clamp_len(P.in_len, b, T);
     const R *in = (const R *) P.inputs + (int64_t) b * P.is1;
     const R *tr = (const R *) P.transition;
-    BeamWordFrame<R> f;
+    BeamWordFrame<R, LA> f;
     f.ctl = &ctl; f.wctl = &wctl; f.cur_v = cur_v; f.cur_q = cur_q; f.cur_h = cur_h; f.trs = trs; f.tr = tr;
     f.ts0 = P.ts0; f.ts1 = P.ts1; f.N = N; f.theta = theta;
-    bind_graph<R, false>(f, g, bg, lm, K, cap, tbits);
+    bind_graph<R, LA>(f, g, bg, lm, K, cap, tbits);
+    bind_look<R>(f, la);
     int *bq, *bh, *bs;
     char *wb = work + (size_t) b * per_utt;
     f.bind_work(wb, T, bq, bh, bs);
@@ -84,7 +89,7 @@ __global__ void __launch_bounds__(kBT) beam_word_loss_search(Problem P, GraphArg
     for (; t < len; ++t) {
         const int na = ctl.na;
         if (t >= 1 && na == 0) break;                       // an empty beam stays empty
-        beam_word_frame<R, TRL>(f, t == 0, na, in + (int64_t) t * P.is0, P.is2, bq, bh, bs, t);
+        beam_word_frame<R, TRL, LA>(f, t == 0, na, in + (int64_t) t * P.is0, P.is2, bq, bh, bs, t);
         if (tid == 0) cnt[t] = ctl.na < K ? ctl.na : K;
     }
     for (int u = t + tid; u < len; u += kBT) cnt[u] = 0;
@@ -377,8 +382,9 @@ bool beam_word_loss_fits(int elem, int M, int N) {
 }
 
 template <typename R>
-hipError_t launch_beam_word_loss_forward(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int K,
-                                         double theta, bool store, void *work, void *scores, hipStream_t stream) {
+hipError_t launch_beam_word_loss_forward(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                                         const WordLookArgs *LA, int K, double theta, bool store, void *work, void *scores,
+                                         hipStream_t stream) {
     const int T = P.T, B = P.B, N = P.N;
     const int cap = beam_word_cap(K, BG.max_out, BG.num_start);
     const int tbits = word_table_bits(cap);
@@ -389,15 +395,16 @@ hipError_t launch_beam_word_loss_forward(const Problem &P, const GraphArgs &G, c
         const size_t beam = kFixedLds + (size_t) K * (sizeof(R) + 8);
         const bool trl = beam + (size_t) N * N * sizeof(R) <= kLdsMax;
         const size_t dyn = beam + (trl ? (size_t) N * N * sizeof(R) : 0);
-        if (trl) {
-            set_lds((const void *) beam_word_loss_search<R, true>, dyn);
-            hipLaunchKernelGGL((beam_word_loss_search<R, true>), dim3(B), dim3(kBT), dyn, stream, P, G, BG, LM, K, (R) theta, cap,
-                               tbits, w, lay.per, lay.cnt);
-        } else {
-            set_lds((const void *) beam_word_loss_search<R, false>, dyn);
-            hipLaunchKernelGGL((beam_word_loss_search<R, false>), dim3(B), dim3(kBT), dyn, stream, P, G, BG, LM, K, (R) theta, cap,
-                               tbits, w, lay.per, lay.cnt);
-        }
+#define ASG_BEAM_WORD_LOSS_SEARCH(TRL, LAF, LOOK)                                                                             \
+    do {                                                                                                                     \
+        set_lds((const void *) beam_word_loss_search<R, TRL, LAF>, dyn);                                                    \
+        hipLaunchKernelGGL((beam_word_loss_search<R, TRL, LAF>), dim3(B), dim3(kBT), dyn, stream, P, G, BG, LM, K,         \
+                           (R) theta, cap, tbits, w, lay.per, lay.cnt, LOOK);                                                \
+    } while (0)
+        if (LA) { if (trl) ASG_BEAM_WORD_LOSS_SEARCH(true, true, *LA); else ASG_BEAM_WORD_LOSS_SEARCH(false, true, *LA); }
+        else if (trl) ASG_BEAM_WORD_LOSS_SEARCH(true, false, WordNoLook{});
+        else ASG_BEAM_WORD_LOSS_SEARCH(false, false, WordNoLook{});
+#undef ASG_BEAM_WORD_LOSS_SEARCH
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -432,7 +439,8 @@ hipError_t launch_beam_word_target_scores(const Problem &P, const GraphArgs &G, 
 
 #define ASG_WORD_LOSS_INST(R)                                                                                                    \
     template hipError_t launch_beam_word_loss_forward<R>(const Problem &, const GraphArgs &, const BeamGraphArgs &,             \
-                                                         const WordLmArgs &, int, double, bool, void *, void *, hipStream_t);   \
+                                                         const WordLmArgs &, const WordLookArgs *, int, double, bool, void *,   \
+                                                         void *, hipStream_t);                                                  \
     template hipError_t launch_beam_word_loss_backward<R>(const Problem &, const GraphArgs &, const BeamGraphArgs &,            \
                                                           const WordLmArgs &, int, const void *, const void *, const void *,    \
                                                           void *, void *, void *, bool, hipStream_t);                           \

@@ -396,9 +396,11 @@ size_t beam_word_loss_work_bytes(int elem, int T, int B, int K, int cap, int nf,
 inline size_t beam_word_loss_scratch_per(int elem, int M, int N) { return beam_loss_scratch_per(elem, M, N); }   // the same pass
 // the one bound on M: a frame's lattice set with a maximum and a sum per member stays in LDS (M <= 8179 float32, 6816 float64)
 bool beam_word_loss_fits(int elem, int M, int N);
+// LA: the look-ahead the search takes its sets with (asg_beam_words_full_forward_la), or NULL; nothing else of the pass reads it.
 template <typename R>
-hipError_t launch_beam_word_loss_forward(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int K,
-                                         double theta, bool store, void *work, void *scores, hipStream_t stream);
+hipError_t launch_beam_word_loss_forward(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                                         const WordLookArgs *LA, int K, double theta, bool store, void *work, void *scores,
+                                         hipStream_t stream);
 template <typename R>
 hipError_t launch_beam_word_loss_backward(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int K,
                                           const void *work, const void *scores, const void *grad_scores, void *grad_inputs,
