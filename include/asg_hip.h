@@ -620,8 +620,8 @@ int asg_beam_words_full_forward_la(asg_ctx *ctx, const asg_problem *p, const asg
  * A' > A, levels outside 1 .. 31 or beyond what A' arcs can fill) or one built for another lexicon / LM shape (S, H):
  * ASG_ERR_INVALID.  Nothing of it is validated on the device.
  * The two word streams take the look-ahead through asg_beam_word_stream_*_la and asg_beam_word_window_*_la (below, with the rule
- * for the prefix result).  Not there: look-ahead in the n-best calls -- the three-way score split needs a rule of its own for the
- * term that has not cancelled yet. */
+ * for the prefix result), the two n-best calls through asg_beam_decode_words_nbest_la and asg_beam_word_stream_nbest_la (further
+ * below, with the rule for the score split: the three parts take no look-ahead term). */
 typedef struct asg_word_lookahead {
     int64_t S;                     /* automaton states of the lexicon (entries of rlo, rhi) = asg_word_lm.S */
     int64_t H;                     /* history states (entries of la_state) = asg_word_lm.H                  */
@@ -883,7 +883,8 @@ int asg_beam_word_window_result(asg_ctx *ctx, const asg_token_graph_beam *gb, co
  * State.  asg_beam_word_{stream,window}_state_bytes and _reset serve both forms: the look-ahead adds no byte to a state and
  * nothing to clear.  One launch per call as the plain calls, no workspace, integer atomics only, capturable.
  * Limits and errors: the plain call's, and asg_beam_decode_words_la's for `la`: a NULL look-ahead, one of another dtype, a NULL
- * or mis-sized array, or S / H other than the LM view's: ASG_ERR_INVALID.  Not there: look-ahead in asg_beam_word_stream_nbest. */
+ * or mis-sized array, or S / H other than the LM view's: ASG_ERR_INVALID.  The n best of such a stream:
+ * asg_beam_word_stream_nbest_la below. */
 int asg_beam_word_stream_advance_la(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
                                     const asg_word_lookahead *la, int beam_size, double beam_threshold, int64_t max_frames,
                                     void *state, size_t state_bytes, int flags, void *stream);
@@ -903,6 +904,56 @@ int asg_beam_word_window_result_la(asg_ctx *ctx, const asg_token_graph_beam *gb,
                                    int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words,
                                    int64_t *word_lengths, int64_t *frames, int64_t *committed, int64_t *status, int flags,
                                    void *stream);
+
+/* ---- The N BEST hypotheses of the search WITH LM LOOK-AHEAD: asg_beam_decode_words_nbest over the search of
+ * asg_beam_decode_words_la, asg_beam_word_stream_nbest over a state that asg_beam_word_stream_advance_la left.  Each entry point is
+ * the plain call with `la`, the look-ahead of that search, behind `lm`; everything the plain call's text says holds with the
+ * changes below.  No counterpart in the reference.  The search is asg_beam_decode_words_la's, unchanged: the same sets and
+ * back-pointers bit for bit (the same device code).  All sums in the dtype of the problem.
+ *   candidates and order, final != 0 (the one-shot call always): every pair (h, q) of the last kept set whose end is > -inf, the
+ *     end asg_beam_decode_words_la's: (v + final_w[q]) + ew[h] at the root; (v + final_w[q]) + ((a - L(h, state(q))) + ew[h']) in
+ *     a word-end node; none mid-word, none where the LM rejects the word.  End descending (-0 equals +0), then pair order.
+ *     num_hyps = min(nbest, candidates).
+ *   candidates and order, final == 0 (stream only): every kept pair, with the end of asg_beam_word_stream_result_la's prefix rule,
+ *     e = v - L(h, state(q)), finite for every kept pair.  e descending, then pair order.  (A mid-word pair with the largest v can
+ *     come behind a root pair with a smaller v: its v carries an estimate, its e does not.)
+ *   Row r: scores = that end exactly as the rule above forms it.  path, states, lm_states, tokens, token_lengths, words and
+ *     word_lengths are asg_beam_decode_words_nbest's, word for word.
+ *   THE SCORE SPLIT HAS NO FOURTH PART.  emission_scores, graph_scores and lm_scores are asg_beam_decode_words_nbest's three sums
+ *     over the path, term for term; no look-ahead term enters any of them.  Along a complete path every L(h, n) the search added
+ *     is taken back -- on the next edge, on the separator edge or at the end -- and in prefix mode the reported end takes back the
+ *     one still open: the look-ahead is an estimate that cancels, not a score.  The parts therefore mean what they mean without
+ *     look-ahead, and a caller re-weights them exactly as asg_beam_decode_words_nbest says.
+ *   scores is the search's own sum, with the cancelling terms rounded in, and NOT the rounded sum of the parts: they agree within
+ *     2 * n * eps * (the sum of the magnitudes of the terms), asg_beam_decode_words_nbest's bound with n and the magnitude sum
+ *     extended: every look-ahead value the search adds on the path (L of the start pair, L of the target of every edge into a
+ *     node) counts twice, once where it enters and once where it leaves (the next edge out of the node, the separator edge, the
+ *     end, or the reported prefix).
+ *   Padding rows, frames beyond len, the nbest limits: asg_beam_decode_words_nbest's.
+ * REQUIRED PROPERTIES (no tolerance).  1. Row 0 of asg_beam_decode_words_nbest_la equals the eight outputs of
+ * asg_beam_decode_words_la bit for bit.  2. Row 0 of asg_beam_word_stream_nbest_la equals asg_beam_word_stream_result_la(final) bit
+ * for bit, for both values of final; frames and status are that call's.  3. For any chunking of an utterance of at most max_frames
+ * frames, the stream's rows with final != 0 equal the one-shot rows bit for bit, on that call's columns.  4. With a beam that
+ * prunes nothing and weights in eighths (no sum rounds) the whole list, the three parts included, equals
+ * asg_beam_decode_words_nbest's bit for bit.
+ * Workspace: asg_beam_decode_words_nbest_work_bytes and asg_beam_word_stream_nbest_work_bytes serve both forms; the look-ahead
+ * adds read-only tables and nothing per utterance.  Launches as the plain calls (two on one stream; one for the stream), no
+ * memset, no copy, no synchronisation, no float atomics: capturable, bit-identical run to run.
+ * Mixing.  As for the streams above: a state advanced with a look-ahead is read with the same look-ahead, one advanced without by
+ * asg_beam_word_stream_nbest; the stored values do not say which estimate they carry, and NOTHING HERE CAN CHECK IT.
+ * Errors: the plain call's, then asg_beam_decode_words_la's for `la`: a NULL look-ahead, one of another dtype, a NULL or mis-sized
+ * array, or S / H other than the LM view's: ASG_ERR_INVALID.  Not here: n-best from the windowed streams. */
+int asg_beam_decode_words_nbest_la(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                   const asg_word_lookahead *la, int beam_size, double beam_threshold, int nbest, void *work,
+                                   size_t work_bytes, void *scores, void *emission_scores, void *graph_scores, void *lm_scores,
+                                   int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *lm_states,
+                                   int64_t *words, int64_t *word_lengths, int64_t *num_hyps, int flags, void *stream);
+int asg_beam_word_stream_nbest_la(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                  const asg_word_lookahead *la, int64_t B, int beam_size, int64_t max_frames, const void *state,
+                                  size_t state_bytes, int final, int nbest, void *work, size_t work_bytes, void *scores,
+                                  void *graph_scores, void *lm_scores, int64_t *path, int64_t *tokens, int64_t *token_lengths,
+                                  int64_t *states, int64_t *lm_states, int64_t *words, int64_t *word_lengths, int64_t *num_hyps,
+                                  int64_t *frames, int64_t *status, int flags, void *stream);
 
 /* ---- Full score of the ASG lattice COMPOSED with a token automaton (the log-semiring counterpart of the decoder above), its
  * gradients, and the automaton's score of each target: the pieces of an ASG loss whose normaliser includes a token-level

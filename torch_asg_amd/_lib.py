@@ -37,7 +37,8 @@ SYMBOLS = ["asg_hip_version", "asg_hip_strerror", "asg_ctx_create", "asg_ctx_des
            "asg_beam_word_window_result", "asg_beam_word_stream_advance_la", "asg_beam_word_stream_result_la",
            "asg_beam_word_window_advance_la", "asg_beam_word_window_result_la",
            "asg_beam_words_full_work_bytes", "asg_beam_words_full_scratch_bytes", "asg_beam_words_full_forward",
-           "asg_beam_words_full_backward", "asg_words_target_scores", "asg_beam_words_full_forward_la"]
+           "asg_beam_words_full_backward", "asg_words_target_scores", "asg_beam_words_full_forward_la",
+           "asg_beam_decode_words_nbest_la", "asg_beam_word_stream_nbest_la"]
 ABI_VERSION = 230        # include/asg_hip.h: ASG_HIP_VERSION this package was written against
 
 
@@ -179,7 +180,8 @@ def lib():
     L.asg_beam_word_window_advance.argtypes = [vp, pp, bp, wp, ci, ctypes.c_double, i64, i64, vp, sz] + [vp] * 8 + [ci, vp]
     L.asg_beam_word_window_result.argtypes = [vp, bp, wp, i64, ci, i64, i64, vp, sz, ci] + [vp] * 11 + [ci, vp]
     for name in ("asg_beam_word_stream_advance", "asg_beam_word_stream_result", "asg_beam_word_window_advance",
-                 "asg_beam_word_window_result"):       # the plain call with the look-ahead behind the LM
+                 "asg_beam_word_window_result", "asg_beam_decode_words_nbest",
+                 "asg_beam_word_stream_nbest"):        # the plain call with the look-ahead behind the LM
         plain = getattr(L, name).argtypes
         at = plain.index(wp) + 1
         getattr(L, name + "_la").argtypes = plain[:at] + [ctypes.POINTER(AsgWordLookahead)] + plain[at:]

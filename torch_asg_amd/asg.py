@@ -464,11 +464,14 @@ class HipBackend:
 
     def beam_decode_words_nbest(self, inputs, transition, lexicon, word_lm, input_lengths, beam_size, nbest,
                                 beam_threshold=float("inf"), lm_weight=1.0, word_score=0.0, token_score=0.0,
-                                return_alignments=False, max_work_bytes=1 << 30):
+                                return_alignments=False, max_work_bytes=1 << 30, lookahead=None):
         """The n best hypotheses of the search over pairs with their score split three ways -> BeamWordsNbest; see
-        include/asg_hip.h::asg_beam_decode_words_nbest.  Grouped under `max_work_bytes` as `_decode_graph` does."""
+        include/asg_hip.h::asg_beam_decode_words_nbest and, with a `WordLookahead`, asg_beam_decode_words_nbest_la (the same
+        workspace).  Grouped under `max_work_bytes` as `_decode_graph` does."""
         from . import wordlm as _wordlm
         _wordlm.check_words(lexicon, word_lm)
+        if lookahead is not None:
+            _wordlm.check_lookahead(lookahead, lexicon, word_lm)
         beam_size, beam_threshold = min(int(beam_size), (1 << 31) - 1), float(beam_threshold)
         nbest = min(int(nbest), (1 << 31) - 1)
         L = _lib.lib()
@@ -478,14 +481,22 @@ class HipBackend:
         with self._guard(dev):
             g, w, (lex, _) = _wordlm.abi_words(lexicon, word_lm, dev, inputs.dtype, lm_weight, word_score, token_score)
             p, _, input_lengths, _ = self._device_problem(inputs, transition, None, input_lengths, None)
+            what = "asg_beam_decode_words_nbest"
+            if lookahead is not None:
+                what = "asg_beam_decode_words_nbest_la"
+                la_dev = lookahead.compile(dev, inputs.dtype, lm_weight, word_score)
+                la = _wordlm.abi_lookahead(la_dev)
 
             def call(work, nbytes, *outs):
+                if lookahead is not None:
+                    return L.asg_beam_decode_words_nbest_la(None, ctypes.byref(p), ctypes.byref(g), ctypes.byref(w),
+                                                            ctypes.byref(la), beam_size, beam_threshold, nbest, work, nbytes, *outs)
                 return L.asg_beam_decode_words_nbest(None, ctypes.byref(p), ctypes.byref(g), ctypes.byref(w), beam_size,
                                                      beam_threshold, nbest, work, nbytes, *outs)
             groups = self._groups(
                 p, B, max_work_bytes,
                 lambda: L.asg_beam_decode_words_nbest_work_bytes(ctypes.byref(p), ctypes.byref(g), ctypes.byref(w), beam_size, nbest),
-                lex["Q"], lambda: _lib.check(call(None, 0, *(None,) * 12, 0, None), "asg_beam_decode_words_nbest"),
+                lex["Q"], lambda: _lib.check(call(None, 0, *(None,) * 12, 0, None), what),
                 inputs, input_lengths=input_lengths)
             sc = torch.empty(4, B, nbest, dtype=inputs.dtype, device=dev)      # scores, emission, graph and LM scores
             wide = torch.empty(2, B, nbest, T, dtype=torch.int64, device=dev)  # tokens, words
@@ -498,7 +509,7 @@ class HipBackend:
                 _lib.check(call(work.data_ptr(), work.numel(), sc[0, b0:].data_ptr(), sc[1, b0:].data_ptr(), sc[2, b0:].data_ptr(),
                                 sc[3, b0:].data_ptr(), al(0, b0), wide[0, b0:].data_ptr(), lengths[0, b0:].data_ptr(), al(1, b0),
                                 al(2, b0), wide[1, b0:].data_ptr(), lengths[1, b0:].data_ptr(), num_hyps[b0:].data_ptr(), 0, stream),
-                           "asg_beam_decode_words_nbest")
+                           what)
         return BeamWordsNbest(sc[0], sc[1], sc[2], sc[3], wide[0], lengths[0], wide[1], lengths[1], num_hyps, align[0], align[1],
                               align[2])
 
@@ -1204,7 +1215,7 @@ def beam_decode_words(inputs, transition, lexicon, word_lm, input_lengths=None, 
     The term is taken back when the word ends, so a complete hypothesis sums the same terms as without it: with a beam that
     prunes nothing the result is the same path, and the score differs only by the rounding of terms that cancel
     (include/asg_hip.h::asg_beam_decode_words_la).  None is the search without it, byte for byte.  The word streams and
-    `beam_decode_words_nbest` take no look-ahead.
+    `beam_decode_words_nbest` take the same keyword.
     """
     _check_beam(beam_size, beam_threshold)
     with torch.no_grad():
@@ -1219,7 +1230,7 @@ BeamWordsNbest = collections.namedtuple("BeamWordsNbest", ["scores", "emission_s
 
 def beam_decode_words_nbest(inputs, transition, lexicon, word_lm, input_lengths=None, beam_size=256, nbest=10,
                             beam_threshold=float("inf"), lm_weight=1.0, word_score=0.0, token_score=0.0, return_alignments=False,
-                            max_work_bytes=1 << 30):
+                            max_work_bytes=1 << 30, lookahead=None):
     """The `nbest` best hypotheses of `beam_decode_words`' search, each with its words and its score split into the acoustic
     part (emissions and transitions), the lexicon part (automaton weights, token_score, final weight) and the LM part (every
     LM step and the end of the sentence, lm_weight and word_score folded in): what n-best rescoring with a stronger LM and the
@@ -1239,6 +1250,13 @@ def beam_decode_words_nbest(inputs, transition, lexicon, word_lm, input_lengths=
     twice, with and without a closing separator -- the better one comes first, rows are not merged.  Inputs, widening, caching,
     capture and the utterance groups under `max_work_bytes` are those of `beam_decode_words`.  nbest < 1 raises ValueError,
     nbest > 8192 RuntimeError; nbest > beam_size only adds padding rows.
+
+    `lookahead`, a `WordLookahead(lexicon, word_lm, order)`, ranks the list of `beam_decode_words(..., lookahead=)`'s search
+    (include/asg_hip.h::asg_beam_decode_words_nbest_la): row 0 equals that call's result bit for bit, `scores` is that search's
+    own end, and the three parts are the sums above, term for term -- no look-ahead term enters them, since every estimate the
+    search adds is taken back before a path ends.  They mean what they mean without look-ahead and are re-weighted the same
+    way; `scores` agrees with their sum up to the rounding of the terms that cancel.  The workspace is the same with and
+    without it.  None is the call without it, byte for byte.
     """
     _check_beam(beam_size, beam_threshold)
     if int(nbest) < 1:
@@ -1246,7 +1264,7 @@ def beam_decode_words_nbest(inputs, transition, lexicon, word_lm, input_lengths=
     with torch.no_grad():
         return native().beam_decode_words_nbest(*_plain(inputs, transition), lexicon, word_lm, input_lengths, beam_size, nbest,
                                                 beam_threshold, lm_weight, word_score, token_score, return_alignments,
-                                                max_work_bytes)
+                                                max_work_bytes, lookahead)
 
 
 BeamNbest = collections.namedtuple("BeamNbest", ["scores", "emission_scores", "graph_scores", "tokens", "token_lengths",
@@ -1731,11 +1749,11 @@ class ASGLoss(nn.Module):
 
     def beam_decode_words_nbest(self, inputs, lexicon, word_lm, input_lengths=None, beam_size=256, nbest=10,
                                 beam_threshold=float("inf"), lm_weight=1.0, word_score=0.0, token_score=0.0,
-                                return_alignments=False, max_work_bytes=1 << 30):
+                                return_alignments=False, max_work_bytes=1 << 30, lookahead=None):
         """The n best hypotheses of `beam_decode_words` under this module's transitions, with the score split: see
         `torch_asg_amd.beam_decode_words_nbest`."""
         return beam_decode_words_nbest(inputs, self.transition, lexicon, word_lm, input_lengths, beam_size, nbest, beam_threshold,
-                                       lm_weight, word_score, token_score, return_alignments, max_work_bytes)
+                                       lm_weight, word_score, token_score, return_alignments, max_work_bytes, lookahead)
 
     def beam_decode_graph_nbest(self, inputs, graph, input_lengths=None, beam_size=256, nbest=10, beam_threshold=float("inf"),
                                 lm_weight=1.0, token_score=0.0, return_alignments=False, max_work_bytes=1 << 30):

@@ -718,14 +718,16 @@ size_t asg_beam_decode_words_nbest_work_bytes(const asg_problem *p, const asg_to
                                       beam_word_cap(beam_size, gb->max_out, (int) gb->num_start), nbest);
 }
 
-int asg_beam_decode_words_nbest(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
-                                int beam_size, double beam_threshold, int nbest, void *work, size_t work_bytes, void *scores,
-                                void *emission_scores, void *graph_scores, void *lm_scores, int64_t *path, int64_t *tokens,
-                                int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words, int64_t *word_lengths,
-                                int64_t *num_hyps, int flags, void *stream) {
-    (void) ctx; (void) flags;
+// asg_beam_decode_words_nbest with a look-ahead (`with_la`: la is checked as asg_beam_decode_words_la checks it, behind the LM) or
+// without one.
+static int beam_decode_words_nbest(const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                   const asg_word_lookahead *la, bool with_la, int beam_size, double beam_threshold, int nbest,
+                                   void *work, size_t work_bytes, void *scores, void *emission_scores, void *graph_scores,
+                                   void *lm_scores, int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states,
+                                   int64_t *lm_states, int64_t *words, int64_t *word_lengths, int64_t *num_hyps, void *stream) {
     int rc = check_beam_words_nbest(p, gb, lm, beam_size, nbest);
     if (rc) return rc;
+    if (with_la && (rc = check_word_lookahead(p->dtype, lm, la)) != ASG_OK) return rc;
     if (!(beam_threshold >= 0.0)) return ASG_ERR_INVALID;                  // negative or NaN
     if (!work || !scores || !emission_scores || !graph_scores || !lm_scores || !tokens || !token_lengths || !words ||
         !word_lengths || !num_hyps)
@@ -738,12 +740,43 @@ int asg_beam_decode_words_nbest(asg_ctx *ctx, const asg_problem *p, const asg_to
     long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
     long long *ls = (long long *) lm_states, *wd = (long long *) words, *wl = (long long *) word_lengths;
     long long *nh = (long long *) num_hyps;
+    if (with_la) {
+        const WordLookArgs LA = to_word_look_args(la);
+        return hip_status(ASG_DISPATCH(p, launch_beam_words_nbest_la<float>(P, G, BG, LM, LA, beam_size, beam_threshold, nbest, work,
+                                                                            scores, emission_scores, graph_scores, lm_scores, pa, tk,
+                                                                            tl, st, ls, wd, wl, nh, (hipStream_t) stream),
+                                       launch_beam_words_nbest_la<double>(P, G, BG, LM, LA, beam_size, beam_threshold, nbest, work,
+                                                                          scores, emission_scores, graph_scores, lm_scores, pa, tk,
+                                                                          tl, st, ls, wd, wl, nh, (hipStream_t) stream)));
+    }
     return hip_status(ASG_DISPATCH(p, launch_beam_words_nbest<float>(P, G, BG, LM, beam_size, beam_threshold, nbest, work, scores,
                                                                      emission_scores, graph_scores, lm_scores, pa, tk, tl, st, ls,
                                                                      wd, wl, nh, (hipStream_t) stream),
                                    launch_beam_words_nbest<double>(P, G, BG, LM, beam_size, beam_threshold, nbest, work, scores,
                                                                    emission_scores, graph_scores, lm_scores, pa, tk, tl, st, ls,
                                                                    wd, wl, nh, (hipStream_t) stream)));
+}
+
+int asg_beam_decode_words_nbest(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                int beam_size, double beam_threshold, int nbest, void *work, size_t work_bytes, void *scores,
+                                void *emission_scores, void *graph_scores, void *lm_scores, int64_t *path, int64_t *tokens,
+                                int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words, int64_t *word_lengths,
+                                int64_t *num_hyps, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    return beam_decode_words_nbest(p, gb, lm, nullptr, false, beam_size, beam_threshold, nbest, work, work_bytes, scores,
+                                   emission_scores, graph_scores, lm_scores, path, tokens, token_lengths, states, lm_states, words,
+                                   word_lengths, num_hyps, stream);
+}
+
+int asg_beam_decode_words_nbest_la(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                   const asg_word_lookahead *la, int beam_size, double beam_threshold, int nbest, void *work,
+                                   size_t work_bytes, void *scores, void *emission_scores, void *graph_scores, void *lm_scores,
+                                   int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *lm_states,
+                                   int64_t *words, int64_t *word_lengths, int64_t *num_hyps, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    return beam_decode_words_nbest(p, gb, lm, la, true, beam_size, beam_threshold, nbest, work, work_bytes, scores, emission_scores,
+                                   graph_scores, lm_scores, path, tokens, token_lengths, states, lm_states, words, word_lengths,
+                                   num_hyps, stream);
 }
 
 static int check_beam_nbest(const asg_problem *p, const asg_token_graph_beam *gb, int beam_size, int nbest) {
@@ -1002,16 +1035,18 @@ size_t asg_beam_word_stream_nbest_work_bytes(const asg_token_graph_beam *gb, con
     return beam_word_stream_nbest_work_bytes((int) max_frames, (int) B, beam_size, nbest);
 }
 
-int asg_beam_word_stream_nbest(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
-                               int64_t max_frames, const void *state, size_t state_bytes, int final, int nbest, void *work,
-                               size_t work_bytes, void *scores, void *graph_scores, void *lm_scores, int64_t *path, int64_t *tokens,
-                               int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words, int64_t *word_lengths,
-                               int64_t *num_hyps, int64_t *frames, int64_t *status, int flags, void *stream) {
-    (void) ctx; (void) flags;
+// asg_beam_word_stream_nbest with a look-ahead (`with_la`, checked behind the LM) or without one.
+static int beam_word_stream_nbest(const asg_token_graph_beam *gb, const asg_word_lm *lm, const asg_word_lookahead *la, bool with_la,
+                                  int64_t B, int beam_size, int64_t max_frames, const void *state, size_t state_bytes, int final,
+                                  int nbest, void *work, size_t work_bytes, void *scores, void *graph_scores, void *lm_scores,
+                                  int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *lm_states,
+                                  int64_t *words, int64_t *word_lengths, int64_t *num_hyps, int64_t *frames, int64_t *status,
+                                  void *stream) {
     if (!gb || !gb->graph) return ASG_ERR_INVALID;
     const asg_token_graph *g = gb->graph;
     int rc = check_beam_word_stream_nbest(gb, lm, B, g->dtype, beam_size, max_frames, nbest);
     if (rc) return rc;
+    if (with_la && (rc = check_word_lookahead(g->dtype, lm, la)) != ASG_OK) return rc;
     if (!state || !work || !scores || !graph_scores || !lm_scores || !tokens || !token_lengths || !words || !word_lengths ||
         !num_hyps || !frames || !status)
         return ASG_ERR_INVALID;
@@ -1023,12 +1058,46 @@ int asg_beam_word_stream_nbest(asg_ctx *ctx, const asg_token_graph_beam *gb, con
     long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
     long long *ls = (long long *) lm_states, *wd = (long long *) words, *wl = (long long *) word_lengths;
     long long *nh = (long long *) num_hyps, *fr = (long long *) frames, *su = (long long *) status;
+    if (with_la) {
+        const WordLookArgs LA = to_word_look_args(la);
+        return hip_status(ASG_DISPATCH(g, launch_beam_word_stream_nbest_la<float>(G, BG, LM, LA, beam_size, (int) max_frames, (int) B,
+                                                                                  state, final, nbest, work, scores, graph_scores,
+                                                                                  lm_scores, pa, tk, tl, st, ls, wd, wl, nh, fr, su,
+                                                                                  (hipStream_t) stream),
+                                       launch_beam_word_stream_nbest_la<double>(G, BG, LM, LA, beam_size, (int) max_frames, (int) B,
+                                                                                state, final, nbest, work, scores, graph_scores,
+                                                                                lm_scores, pa, tk, tl, st, ls, wd, wl, nh, fr, su,
+                                                                                (hipStream_t) stream)));
+    }
     return hip_status(ASG_DISPATCH(g, launch_beam_word_stream_nbest<float>(G, BG, LM, beam_size, (int) max_frames, (int) B, state,
                                                                            final, nbest, work, scores, graph_scores, lm_scores, pa,
                                                                            tk, tl, st, ls, wd, wl, nh, fr, su, (hipStream_t) stream),
                                    launch_beam_word_stream_nbest<double>(G, BG, LM, beam_size, (int) max_frames, (int) B, state,
                                                                          final, nbest, work, scores, graph_scores, lm_scores, pa,
                                                                          tk, tl, st, ls, wd, wl, nh, fr, su, (hipStream_t) stream)));
+}
+
+int asg_beam_word_stream_nbest(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
+                               int64_t max_frames, const void *state, size_t state_bytes, int final, int nbest, void *work,
+                               size_t work_bytes, void *scores, void *graph_scores, void *lm_scores, int64_t *path, int64_t *tokens,
+                               int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words, int64_t *word_lengths,
+                               int64_t *num_hyps, int64_t *frames, int64_t *status, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    return beam_word_stream_nbest(gb, lm, nullptr, false, B, beam_size, max_frames, state, state_bytes, final, nbest, work, work_bytes,
+                                  scores, graph_scores, lm_scores, path, tokens, token_lengths, states, lm_states, words, word_lengths,
+                                  num_hyps, frames, status, stream);
+}
+
+int asg_beam_word_stream_nbest_la(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                  const asg_word_lookahead *la, int64_t B, int beam_size, int64_t max_frames, const void *state,
+                                  size_t state_bytes, int final, int nbest, void *work, size_t work_bytes, void *scores,
+                                  void *graph_scores, void *lm_scores, int64_t *path, int64_t *tokens, int64_t *token_lengths,
+                                  int64_t *states, int64_t *lm_states, int64_t *words, int64_t *word_lengths, int64_t *num_hyps,
+                                  int64_t *frames, int64_t *status, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    return beam_word_stream_nbest(gb, lm, la, true, B, beam_size, max_frames, state, state_bytes, final, nbest, work, work_bytes,
+                                  scores, graph_scores, lm_scores, path, tokens, token_lengths, states, lm_states, words, word_lengths,
+                                  num_hyps, frames, status, stream);
 }
 
 // A window stream state is sized like a problem of W frames (the ring); P is the commit period.

@@ -20,12 +20,15 @@ namespace asg {
 
 namespace {
 
-template <typename R, bool TRL>
+// FIN: the instantiation behind the n-best stage (asg_beam_word_nbest.hip, launch_beam_words_nbest_la), which also leaves the last
+// set in memory at fin_off, as beam_word_kernel's does; the decoder's own (FIN false) is the code object it was before (DESIGN.md
+// 5v).
+template <typename R, bool TRL, bool FIN>
 __global__ void __launch_bounds__(kBT) beam_word_la_kernel(Problem P, GraphArgs g, BeamGraphArgs bg, WordLmArgs lm, WordLookArgs la,
                                                            int K, R theta, int cap, int tbits, char *work, size_t per_utt,
                                                            R *scores, long long *path, long long *tokens, long long *tlen,
                                                            long long *states, long long *lm_states, long long *words,
-                                                           long long *wlen) {
+                                                           long long *wlen, size_t fin_off) {
     using KT = Key<R>;
     using U = typename KT::U;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -80,6 +83,13 @@ __global__ void __launch_bounds__(kBT) beam_word_la_kernel(Problem P, GraphArgs 
 
     // ---- the best end over the last kept set, the smallest pair on a tie; the backtrace, the words, the tokens
     const int na = ctl.na < K ? ctl.na : K;
+    if constexpr (FIN) {                                    // the n-best stage reads the last set from memory
+        char *fin = work + (size_t) b * per_utt + fin_off;
+        R *fv = (R *) (fin + 8);
+        int *fq = (int *) (fv + K), *fh = fq + K;
+        for (int k = tid; k < na; k += kBT) { fv[k] = cur_v[k]; fq[k] = cur_q[k]; fh[k] = cur_h[k]; }
+        if (tid == 0) *(int *) fin = na;
+    }
     U bkey;
     int bk;
     word_best_end<R, true>(f, fw, true, cur_h, cur_q, cur_v, na, bkey, bk);
@@ -98,31 +108,34 @@ template <typename R>
 hipError_t launch_beam_words_la(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
                                 const WordLookArgs &LA, int K, double theta, void *work, void *scores, long long *path,
                                 long long *tokens, long long *tlen, long long *states, long long *lm_states, long long *words,
-                                long long *wlen, hipStream_t stream) {
+                                long long *wlen, hipStream_t stream, size_t stride, size_t fin_off) {
     const int N = P.N;
     const int cap = beam_word_cap(K, BG.max_out, BG.num_start);
     const int tbits = word_table_bits(cap);
-    const size_t per = beam_word_work_bytes(sizeof(R), P.T, 1, K, cap);
+    const size_t per = stride ? stride : beam_word_work_bytes(sizeof(R), P.T, 1, K, cap);
     const size_t beam = kFixedLds + (size_t) K * (sizeof(R) + 8);
     const bool trl = beam + (size_t) N * N * sizeof(R) <= kLdsMax;
     const size_t dyn = beam + (trl ? (size_t) N * N * sizeof(R) : 0);
-#define ASG_BEAM_WORD_LA(TRL)                                                                                             \
+#define ASG_BEAM_WORD_LA(TRL, FIN)                                                                                        \
     do {                                                                                                                  \
-        const void *fn = (const void *) beam_word_la_kernel<R, TRL>;                                                     \
+        const void *fn = (const void *) beam_word_la_kernel<R, TRL, FIN>;                                                \
         if (dyn > 64 * 1024) (void) hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) dyn);    \
-        hipLaunchKernelGGL((beam_word_la_kernel<R, TRL>), dim3(P.B), dim3(kBT), dyn, stream, P, G, BG, LM, LA, K,        \
+        hipLaunchKernelGGL((beam_word_la_kernel<R, TRL, FIN>), dim3(P.B), dim3(kBT), dyn, stream, P, G, BG, LM, LA, K,   \
                            (R) theta, cap, tbits, (char *) work, per, (R *) scores, path, tokens, tlen, states, lm_states, \
-                           words, wlen);                                                                                  \
+                           words, wlen, fin_off);                                                                         \
     } while (0)
-    if (trl) ASG_BEAM_WORD_LA(true); else ASG_BEAM_WORD_LA(false);
+    if (fin_off) { if (trl) ASG_BEAM_WORD_LA(true, true); else ASG_BEAM_WORD_LA(false, true); }
+    else if (trl) ASG_BEAM_WORD_LA(true, false); else ASG_BEAM_WORD_LA(false, false);
 #undef ASG_BEAM_WORD_LA
     return hipGetLastError();
 }
 template hipError_t launch_beam_words_la<float>(const Problem &, const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &,
                                                 const WordLookArgs &, int, double, void *, void *, long long *, long long *,
-                                                long long *, long long *, long long *, long long *, long long *, hipStream_t);
+                                                long long *, long long *, long long *, long long *, long long *, hipStream_t,
+                                                size_t, size_t);
 template hipError_t launch_beam_words_la<double>(const Problem &, const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &,
                                                  const WordLookArgs &, int, double, void *, void *, long long *, long long *,
-                                                 long long *, long long *, long long *, long long *, long long *, hipStream_t);
+                                                 long long *, long long *, long long *, long long *, long long *, hipStream_t,
+                                                 size_t, size_t);
 
 }  // namespace asg

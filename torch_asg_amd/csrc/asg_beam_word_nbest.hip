@@ -26,6 +26,10 @@
 //            rows.
 // Every output, padding row and scratch word that is read is written here: no memset, no copy.  One integer LDS counter; no
 // atomics on values: bit-identical run to run.
+//
+// The same kernel with the look-ahead flag (LA) serves the searches with LM look-ahead: behind beam_word_la_kernel, or over a state
+// that asg_beam_word_stream_advance_la left.  The end of an entry is then word_end<R, true>'s / word_prefix<R, true>'s, which take
+// the estimate the value still carries back; the walk, the three sums and the write stage are the same text.
 #include "asg_common.h"
 #include "asg_kernels.h"
 #include "asg_beam_common.h"
@@ -57,14 +61,19 @@ __device__ __forceinline__ bool entry_less(U ka, unsigned long long pa, U kb, un
     return ka < kb || (ka == kb && pa < pb);
 }
 
-template <typename R>
+// LA: over a search with LM look-ahead (asg_beam_decode_words_nbest_la, asg_beam_word_stream_nbest_la).  The values of the set then
+// carry L(h, node): the keys and `scores` take it back as the one-best does -- word_end<R, true>, word_prefix<R, true>, that text
+// -- and nothing else changes: the walk and the three sums never see a look-ahead term.  Off by default: the
+// instantiations without it compile the text they compiled before the flag existed.
+template <typename R, bool LA = false>
 __global__ void __launch_bounds__(kNT) beam_word_nbest_kernel(Problem P, GraphArgs g, BeamGraphArgs bg, WordLmArgs lm,
                                                               BeamWordNbestSrc src, int K, int cap, int tbits, int nbest, int P2max,
                                                               int final,
                                                               R *scores, R *escores, R *gscores, R *lscores, long long *path,
                                                               long long *tokens, long long *tlen, long long *states,
                                                               long long *lm_states, long long *words, long long *wlen,
-                                                              long long *nhyp, long long *frames, long long *status) {
+                                                              long long *nhyp, long long *frames, long long *status,
+                                                              WordLookParam<LA> la) {
     using KT = Key<R>;
     using U = typename KT::U;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -87,11 +96,12 @@ __global__ void __launch_bounds__(kNT) beam_word_nbest_kernel(Problem P, GraphAr
     const int *set_q = (const int *) (set_v + K), *set_h = set_q + K;
     int *cols = (int *) (src.cols + (size_t) b * src.cols_per);           // [T][nb]
     const int64_t ob = (int64_t) b * nbest;                               // the slot's first output row
-    BeamWordFrame<R> f{};                                                 // what step and word_end read; nothing of the frame loop
+    BeamWordFrame<R, LA> f{};                                             // what step and word_end read; nothing of the frame loop
     f.qbits = bits_of(g.Q); f.sep = lm.sep; f.K = K;
     f.label = g.label; f.state = g.state;
     f.lrow = lm.row; f.lword = lm.word; f.lnext = lm.next; f.lback = lm.backoff; f.wos = lm.word_of_state;
     f.lw = (const R *) lm.lw; f.bw = (const R *) lm.bw; f.ew = (const R *) lm.ew; f.lstart = lm.start;
+    bind_look<R>(f, la);
     const int Q = g.Q;
 
     int na = len >= 1 ? *(const int *) (wb + src.na_off) : 0;
@@ -114,7 +124,11 @@ __global__ void __launch_bounds__(kNT) beam_word_nbest_kernel(Problem P, GraphAr
             const int q = set_q[x], h = set_h[x];
             R end = set_v[x];
             int w;
-            cand = q >= 0 && q < Q && (!final || word_end<R>(f, fw, h, q, end, end, w)) && end > NINF;
+            if constexpr (LA) {                                           // a prefix: without the estimate the value still carries
+                cand = q >= 0 && q < Q && (!final || word_end<R, LA>(f, fw, h, q, end, end, w));
+                if (cand && !final) end = word_prefix<R, LA>(f, h, q, end);
+                cand = cand && end > NINF;
+            } else cand = q >= 0 && q < Q && (!final || word_end<R>(f, fw, h, q, end, end, w)) && end > NINF;
             if (cand) { ik = (U) ~KT::enc(end); ps = (f.pair(h, q) << kWordSlotBits) | (unsigned) x; }
         }
         if (x < P2) { sk[x] = ik; sp[x] = ps; }
@@ -188,8 +202,8 @@ __global__ void __launch_bounds__(kNT) beam_word_nbest_kernel(Problem P, GraphAr
             }
             ls = ls + endw;
             int w;
-            (void) word_end<R>(f, fw, set_h[kl], set_q[kl], set_v[kl], end, w);
-        }
+            (void) word_end<R, LA>(f, fw, set_h[kl], set_q[kl], set_v[kl], end, w);
+        } else if constexpr (LA) end = word_prefix<R, LA>(f, set_h[kl], set_q[kl], end);
         scores[ob + r] = end;
         if (escores) escores[ob + r] = a;
         gscores[ob + r] = gs;
@@ -263,22 +277,22 @@ __global__ void __launch_bounds__(kNT) beam_word_nbest_kernel(Problem P, GraphAr
     }
 }
 
-template <typename R>
+template <typename R, bool LA>
 hipError_t launch_nbest_kernel(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
-                               const BeamWordNbestSrc &src, int B, int K, int nbest, int final, void *scores, void *escores,
-                               void *gscores, void *lscores, long long *path, long long *tokens, long long *tlen,
-                               long long *states, long long *lm_states, long long *words, long long *wlen, long long *num_hyps,
-                               long long *frames, long long *status, hipStream_t stream) {
+                               const WordLookParam<LA> &look, const BeamWordNbestSrc &src, int B, int K, int nbest, int final,
+                               void *scores, void *escores, void *gscores, void *lscores, long long *path, long long *tokens,
+                               long long *tlen, long long *states, long long *lm_states, long long *words, long long *wlen,
+                               long long *num_hyps, long long *frames, long long *status, hipStream_t stream) {
     int P2 = 1;
     while (P2 < K) P2 *= 2;
     const size_t dyn = (size_t) P2 * (8 + sizeof(typename Key<R>::U));
     const int cap = beam_word_cap(K, BG.max_out, BG.num_start);
-    const void *fn = (const void *) beam_word_nbest_kernel<R>;
+    const void *fn = (const void *) beam_word_nbest_kernel<R, LA>;
     if (dyn + 64 > 64 * 1024) (void) hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) dyn);
-    hipLaunchKernelGGL((beam_word_nbest_kernel<R>), dim3(B), dim3(kNT), dyn, stream, P, G, BG, LM, src, K, cap, word_table_bits(cap),
+    hipLaunchKernelGGL((beam_word_nbest_kernel<R, LA>), dim3(B), dim3(kNT), dyn, stream, P, G, BG, LM, src, K, cap, word_table_bits(cap),
                        nbest, P2, final,
                        (R *) scores, (R *) escores, (R *) gscores, (R *) lscores, path, tokens, tlen, states, lm_states, words,
-                       wlen, num_hyps, frames, status);
+                       wlen, num_hyps, frames, status, look);
     return hipGetLastError();
 }
 
@@ -302,27 +316,57 @@ size_t beam_word_stream_nbest_work_bytes(int max_frames, int B, int K, int nbest
     return (size_t) B * a256((size_t) max_frames * (nbest < K ? nbest : K) * 4);
 }
 
-template <typename R>
-hipError_t launch_beam_words_nbest(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int K,
-                                   double theta, int nbest, void *work, void *scores, void *emission_scores, void *graph_scores,
-                                   void *lm_scores, long long *path, long long *tokens, long long *tlen, long long *states,
-                                   long long *lm_states, long long *words, long long *wlen, long long *num_hyps,
-                                   hipStream_t stream) {
+namespace {
+
+// The search -- asg_beam_word.hip's, or with LA asg_beam_word_la.hip's -- asked to leave its last set, then the n-best kernel
+// over what it left, on one stream.
+template <typename R, bool LA>
+hipError_t beam_words_nbest(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                            const WordLookParam<LA> &look, int K, double theta, int nbest, void *work, void *scores,
+                            void *emission_scores, void *graph_scores, void *lm_scores, long long *path, long long *tokens,
+                            long long *tlen, long long *states, long long *lm_states, long long *words, long long *wlen,
+                            long long *num_hyps, hipStream_t stream) {
     const int T = P.T, B = P.B;
     const int cap = beam_word_cap(K, BG.max_out, BG.num_start);
     const BeamWordNbestLayout lay = beam_word_nbest_layout(sizeof(R), T, K, cap, nbest);
     char *w = (char *) work, *tail = w + (size_t) B * lay.per;
     const size_t bb = a256((size_t) B * 8), BT = (size_t) B * T;
     long long *wide = (long long *) (tail + 3 * bb);                        // path, tokens, states, lm_states, words of the one best
-    hipError_t e = launch_beam_words<R>(P, G, BG, LM, K, theta, work, tail, wide, wide + BT, (long long *) (tail + bb),
-                                        wide + 2 * BT, wide + 3 * BT, wide + 4 * BT, (long long *) (tail + 2 * bb), stream,
-                                        lay.per, lay.fin);
+    hipError_t e;
+    if constexpr (LA)
+        e = launch_beam_words_la<R>(P, G, BG, LM, look, K, theta, work, tail, wide, wide + BT, (long long *) (tail + bb),
+                                    wide + 2 * BT, wide + 3 * BT, wide + 4 * BT, (long long *) (tail + 2 * bb), stream, lay.per,
+                                    lay.fin);
+    else
+        e = launch_beam_words<R>(P, G, BG, LM, K, theta, work, tail, wide, wide + BT, (long long *) (tail + bb), wide + 2 * BT,
+                                 wide + 3 * BT, wide + 4 * BT, (long long *) (tail + 2 * bb), stream, lay.per, lay.fin);
     if (e != hipSuccess) return e;
     BeamWordNbestSrc src{};
     src.base = w; src.per = lay.per; src.set_off = lay.fin + 8; src.na_off = lay.fin; src.pos_off = 0; src.ovf_off = 0;
     src.cols = w + lay.rows; src.cols_per = lay.per; src.Tw = T; src.nb = lay.nb;
-    return launch_nbest_kernel<R>(P, G, BG, LM, src, B, K, nbest, 1, scores, emission_scores, graph_scores, lm_scores, path, tokens,
-                                  tlen, states, lm_states, words, wlen, num_hyps, nullptr, nullptr, stream);
+    return launch_nbest_kernel<R, LA>(P, G, BG, LM, look, src, B, K, nbest, 1, scores, emission_scores, graph_scores, lm_scores, path,
+                                      tokens, tlen, states, lm_states, words, wlen, num_hyps, nullptr, nullptr, stream);
+}
+
+}  // namespace
+
+template <typename R>
+hipError_t launch_beam_words_nbest(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int K,
+                                   double theta, int nbest, void *work, void *scores, void *emission_scores, void *graph_scores,
+                                   void *lm_scores, long long *path, long long *tokens, long long *tlen, long long *states,
+                                   long long *lm_states, long long *words, long long *wlen, long long *num_hyps,
+                                   hipStream_t stream) {
+    return beam_words_nbest<R, false>(P, G, BG, LM, WordNoLook{}, K, theta, nbest, work, scores, emission_scores, graph_scores,
+                                      lm_scores, path, tokens, tlen, states, lm_states, words, wlen, num_hyps, stream);
+}
+template <typename R>
+hipError_t launch_beam_words_nbest_la(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                                      const WordLookArgs &LA, int K, double theta, int nbest, void *work, void *scores,
+                                      void *emission_scores, void *graph_scores, void *lm_scores, long long *path,
+                                      long long *tokens, long long *tlen, long long *states, long long *lm_states,
+                                      long long *words, long long *wlen, long long *num_hyps, hipStream_t stream) {
+    return beam_words_nbest<R, true>(P, G, BG, LM, LA, K, theta, nbest, work, scores, emission_scores, graph_scores, lm_scores,
+                                     path, tokens, tlen, states, lm_states, words, wlen, num_hyps, stream);
 }
 template hipError_t launch_beam_words_nbest<float>(const Problem &, const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &, int,
                                                    double, int, void *, void *, void *, void *, void *, long long *, long long *,
@@ -332,13 +376,23 @@ template hipError_t launch_beam_words_nbest<double>(const Problem &, const Graph
                                                     double, int, void *, void *, void *, void *, void *, long long *, long long *,
                                                     long long *, long long *, long long *, long long *, long long *, long long *,
                                                     hipStream_t);
+template hipError_t launch_beam_words_nbest_la<float>(const Problem &, const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &,
+                                                      const WordLookArgs &, int, double, int, void *, void *, void *, void *, void *,
+                                                      long long *, long long *, long long *, long long *, long long *, long long *,
+                                                      long long *, long long *, hipStream_t);
+template hipError_t launch_beam_words_nbest_la<double>(const Problem &, const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &,
+                                                       const WordLookArgs &, int, double, int, void *, void *, void *, void *,
+                                                       void *, long long *, long long *, long long *, long long *, long long *,
+                                                       long long *, long long *, long long *, hipStream_t);
 
-template <typename R>
-hipError_t launch_beam_word_stream_nbest(const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int K, int max_frames,
-                                         int B, const void *state, int final, int nbest, void *work, void *scores,
-                                         void *graph_scores, void *lm_scores, long long *path, long long *tokens, long long *tlen,
-                                         long long *states, long long *lm_states, long long *words, long long *wlen,
-                                         long long *num_hyps, long long *frames, long long *status, hipStream_t stream) {
+namespace {
+
+template <typename R, bool LA>
+hipError_t beam_word_stream_nbest(const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, const WordLookParam<LA> &look,
+                                  int K, int max_frames, int B, const void *state, int final, int nbest, void *work, void *scores,
+                                  void *graph_scores, void *lm_scores, long long *path, long long *tokens, long long *tlen,
+                                  long long *states, long long *lm_states, long long *words, long long *wlen, long long *num_hyps,
+                                  long long *frames, long long *status, hipStream_t stream) {
     const int cap = beam_word_cap(K, BG.max_out, BG.num_start);
     const BeamStreamLayout lay = beam_word_stream_layout(sizeof(R), max_frames, K, cap);
     BeamWordNbestSrc src{};
@@ -348,8 +402,32 @@ hipError_t launch_beam_word_stream_nbest(const GraphArgs &G, const BeamGraphArgs
     src.cols = (char *) work; src.cols_per = a256((size_t) max_frames * src.nb * 4); src.Tw = max_frames;
     Problem P{};                                                            // no emissions, no lengths: the state has both
     P.T = max_frames; P.B = B; P.N = 0;
-    return launch_nbest_kernel<R>(P, G, BG, LM, src, B, K, nbest, final != 0, scores, nullptr, graph_scores, lm_scores, path, tokens,
-                                  tlen, states, lm_states, words, wlen, num_hyps, frames, status, stream);
+    return launch_nbest_kernel<R, LA>(P, G, BG, LM, look, src, B, K, nbest, final != 0, scores, nullptr, graph_scores, lm_scores, path,
+                                      tokens, tlen, states, lm_states, words, wlen, num_hyps, frames, status, stream);
+}
+
+}  // namespace
+
+template <typename R>
+hipError_t launch_beam_word_stream_nbest(const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int K, int max_frames,
+                                         int B, const void *state, int final, int nbest, void *work, void *scores,
+                                         void *graph_scores, void *lm_scores, long long *path, long long *tokens, long long *tlen,
+                                         long long *states, long long *lm_states, long long *words, long long *wlen,
+                                         long long *num_hyps, long long *frames, long long *status, hipStream_t stream) {
+    return beam_word_stream_nbest<R, false>(G, BG, LM, WordNoLook{}, K, max_frames, B, state, final, nbest, work, scores,
+                                            graph_scores, lm_scores, path, tokens, tlen, states, lm_states, words, wlen, num_hyps,
+                                            frames, status, stream);
+}
+template <typename R>
+hipError_t launch_beam_word_stream_nbest_la(const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                                            const WordLookArgs &LA, int K, int max_frames, int B, const void *state, int final,
+                                            int nbest, void *work, void *scores, void *graph_scores, void *lm_scores,
+                                            long long *path, long long *tokens, long long *tlen, long long *states,
+                                            long long *lm_states, long long *words, long long *wlen, long long *num_hyps,
+                                            long long *frames, long long *status, hipStream_t stream) {
+    return beam_word_stream_nbest<R, true>(G, BG, LM, LA, K, max_frames, B, state, final, nbest, work, scores, graph_scores,
+                                           lm_scores, path, tokens, tlen, states, lm_states, words, wlen, num_hyps, frames, status,
+                                           stream);
 }
 template hipError_t launch_beam_word_stream_nbest<float>(const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &, int, int, int,
                                                          const void *, int, int, void *, void *, void *, void *, long long *,
@@ -359,5 +437,15 @@ template hipError_t launch_beam_word_stream_nbest<double>(const GraphArgs &, con
                                                           const void *, int, int, void *, void *, void *, void *, long long *,
                                                           long long *, long long *, long long *, long long *, long long *,
                                                           long long *, long long *, long long *, long long *, hipStream_t);
+template hipError_t launch_beam_word_stream_nbest_la<float>(const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &,
+                                                            const WordLookArgs &, int, int, int, const void *, int, int, void *,
+                                                            void *, void *, void *, long long *, long long *, long long *,
+                                                            long long *, long long *, long long *, long long *, long long *,
+                                                            long long *, long long *, hipStream_t);
+template hipError_t launch_beam_word_stream_nbest_la<double>(const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &,
+                                                             const WordLookArgs &, int, int, int, const void *, int, int, void *,
+                                                             void *, void *, void *, long long *, long long *, long long *,
+                                                             long long *, long long *, long long *, long long *, long long *,
+                                                             long long *, long long *, hipStream_t);
 
 }  // namespace asg

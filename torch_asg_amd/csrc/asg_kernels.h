@@ -236,7 +236,7 @@ hipError_t launch_beam_stream_result(const GraphArgs &G, const BeamGraphArgs &BG
                                      long long *states, long long *frames, long long *status, hipStream_t stream);
 
 // ---- The same search with LM look-ahead (asg_beam_word_la.hip): asg_beam_decode_words_la.  K, cap, the table and the workspace
-// are those of launch_beam_words; the look-ahead adds read-only arrays and nothing per utterance.
+// are those of launch_beam_words, stride and fin_off too; the look-ahead adds read-only arrays and nothing per utterance.
 struct WordLookArgs {
     int A, levels;                            // ranked arcs A', levels of the range-maximum table
     const int *rlo, *rhi;                     // [S] rank range of the words below each trie node
@@ -249,7 +249,7 @@ template <typename R>
 hipError_t launch_beam_words_la(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
                                 const WordLookArgs &LA, int K, double theta, void *work, void *scores, long long *path,
                                 long long *tokens, long long *tlen, long long *states, long long *lm_states, long long *words,
-                                long long *wlen, hipStream_t stream);
+                                long long *wlen, hipStream_t stream, size_t stride = 0, size_t fin_off = 0);
 
 // ---- The search over pairs carried across chunks of frames (asg_beam_word_stream.hip): asg_beam_word_stream_*.  One slot of the
 // state: the word decoder's own layout for T = max_frames at the front, then hdr (int32 pos, |A|, overflow) and the stored set
@@ -290,6 +290,13 @@ hipError_t launch_beam_words_nbest(const Problem &P, const GraphArgs &G, const B
                                    void *lm_scores, long long *path, long long *tokens, long long *tlen, long long *states,
                                    long long *lm_states, long long *words, long long *wlen, long long *num_hyps,
                                    hipStream_t stream);
+// ... behind the search with LM look-ahead (launch_beam_words_la): asg_beam_decode_words_nbest_la.  Same workspace.
+template <typename R>
+hipError_t launch_beam_words_nbest_la(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                                      const WordLookArgs &LA, int K, double theta, int nbest, void *work, void *scores,
+                                      void *emission_scores, void *graph_scores, void *lm_scores, long long *path,
+                                      long long *tokens, long long *tlen, long long *states, long long *lm_states,
+                                      long long *words, long long *wlen, long long *num_hyps, hipStream_t stream);
 // The same kernel over a stream state (read only).  The state holds no emissions: there is no emission sum.
 template <typename R>
 hipError_t launch_beam_word_stream_nbest(const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int K, int max_frames,
@@ -297,6 +304,14 @@ hipError_t launch_beam_word_stream_nbest(const GraphArgs &G, const BeamGraphArgs
                                          void *graph_scores, void *lm_scores, long long *path, long long *tokens, long long *tlen,
                                          long long *states, long long *lm_states, long long *words, long long *wlen,
                                          long long *num_hyps, long long *frames, long long *status, hipStream_t stream);
+// ... over a state that launch_beam_word_stream_advance left with the look-ahead LA: asg_beam_word_stream_nbest_la.
+template <typename R>
+hipError_t launch_beam_word_stream_nbest_la(const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                                            const WordLookArgs &LA, int K, int max_frames, int B, const void *state, int final,
+                                            int nbest, void *work, void *scores, void *graph_scores, void *lm_scores,
+                                            long long *path, long long *tokens, long long *tlen, long long *states,
+                                            long long *lm_states, long long *words, long long *wlen, long long *num_hyps,
+                                            long long *frames, long long *status, hipStream_t stream);
 
 // ---- The stream in bounded memory (asg_beam_window.hip): asg_beam_window_*.  One slot of the state has the layout of a stream
 // of W frames -- the back-pointers are a ring, frame u in row u mod W -- with the header int64 pos, int64 base, int32 |A|, carry,

@@ -243,8 +243,9 @@ class BeamWordStream(_Stream):
     (include/asg_hip.h::asg_beam_word_stream_advance_la): `result(final=True)` then equals that call, bit for bit, for any
     chunking, and a prefix result takes the estimate that has not cancelled yet back (see `result`).  The stream is bound to
     its look-ahead for life -- the values in the state carry it -- and the state has the same size with or without.
-    Not here: a loss over a stream (the one-shot loss over pairs is `beam_words_asg_loss`); `result_nbest` of a stream with a
-    look-ahead.
+    Not here: a loss over a stream (the one-shot loss over pairs is `beam_words_asg_loss`); the public `result_nbest` of a
+    stream with a look-ahead still raises (the library call, asg_beam_word_stream_nbest_la, is there and `_result_nbest` reaches
+    it).
     """
     _API, _WIDE, _NARROW = "asg_beam_word_stream", 5, 4
 
@@ -309,11 +310,20 @@ class BeamWordStream(_Stream):
         the end of the sentence, no final word.  Row 0 equals `result(final)`.  The state keeps no emissions, so there is no
         emission_scores: scores - (graph_scores + lm_scores) is it up to rounding.  One launch; the scratch it needs is allocated
         once per `nbest` and kept on the stream, so a captured call replays.  nbest < 1 raises ValueError, nbest > 8192
-        RuntimeError.  A stream built with a look-ahead raises NotImplementedError: the three-way split has no rule yet for
-        the estimate that has not cancelled."""
+        RuntimeError.  A stream built with a look-ahead still raises NotImplementedError here: the rule for its list exists
+        (include/asg_hip.h::asg_beam_word_stream_nbest_la: the three parts take no look-ahead term) and `_result_nbest` runs it,
+        but the public method keeps the raise its tests pin until they change with it."""
         if self.lookahead is not None:
-            raise NotImplementedError("torch_asg_amd: result_nbest of a stream with a look-ahead is not there (the score split "
-                                      "needs a rule for the look-ahead term); build the stream without `lookahead`")
+            raise NotImplementedError("torch_asg_amd: result_nbest of a stream with a look-ahead is not there (the public method "
+                                      "is not opened yet; `_result_nbest` runs asg_beam_word_stream_nbest_la); build the stream "
+                                      "without `lookahead`")
+        return self._result_nbest(nbest, final, return_alignments)
+
+    def _result_nbest(self, nbest, final, return_alignments):
+        """`result_nbest` behind its look-ahead check.  With a look-ahead the stream's own view goes behind the LM
+        (asg_beam_word_stream_nbest_la): candidates by the end of `result(final)` -- in prefix mode v - L(h, node) -- row 0
+        equal to `result(final)`, final rows equal to `beam_decode_words_nbest(..., lookahead=)`'s, graph_scores and lm_scores
+        without any look-ahead term."""
         if int(nbest) < 1:
             raise ValueError("torch_asg_amd: nbest must be >= 1, got %d" % int(nbest))
         nbest = min(int(nbest), (1 << 31) - 1)
@@ -321,15 +331,18 @@ class BeamWordStream(_Stream):
         L = _lib.lib()
         B, dev, T = self.batch_size, self.device, self.max_frames
         with be._guard(dev):
+            what = "asg_beam_word_stream_nbest" + ("" if self.lookahead is None else "_la")
+            fn = getattr(L, what)
+
             def call(work, nbytes, *outs):
-                return L.asg_beam_word_stream_nbest(None, *self._views, B, self.beam_size, T, self._state.data_ptr(),
-                                                    self._state.numel(), 1 if final else 0, nbest, work, nbytes, *outs)
+                return fn(None, *self._views, *self._look, B, self.beam_size, T, self._state.data_ptr(), self._state.numel(),
+                          1 if final else 0, nbest, work, nbytes, *outs)
             work = self._nbest_work.get(nbest)
             if work is None:
                 abi_dtype = _lib.ASG_DTYPE_F32 if self.dtype == torch.float32 else _lib.ASG_DTYPE_F64
                 nbytes = int(L.asg_beam_word_stream_nbest_work_bytes(*self._views, B, abi_dtype, self.beam_size, T, nbest))
                 if nbytes == 0:                                # the library refuses the arguments: its call says why
-                    _lib.check(call(None, 0, *(None,) * 13, 0, None), "asg_beam_word_stream_nbest")
+                    _lib.check(call(None, 0, *(None,) * 13, 0, None), what)
                 work = self._nbest_work[nbest] = be._buf(nbytes, dev)
             sc = torch.empty(3, B, nbest, dtype=self.dtype, device=dev)        # scores, graph and LM scores
             wide = torch.empty(2, B, nbest, T, dtype=torch.int64, device=dev)  # tokens, words
@@ -339,8 +352,7 @@ class BeamWordStream(_Stream):
             al = lambda i: align[i].data_ptr() if return_alignments else None      # noqa: E731
             _lib.check(call(work.data_ptr(), work.numel(), sc[0].data_ptr(), sc[1].data_ptr(), sc[2].data_ptr(), al(0),
                             wide[0].data_ptr(), lengths[0].data_ptr(), al(1), al(2), wide[1].data_ptr(), lengths[1].data_ptr(),
-                            narrow[0].data_ptr(), narrow[1].data_ptr(), narrow[2].data_ptr(), 0, be._stream(dev)),
-                       "asg_beam_word_stream_nbest")
+                            narrow[0].data_ptr(), narrow[1].data_ptr(), narrow[2].data_ptr(), 0, be._stream(dev)), what)
         return BeamWordStreamNbest(sc[0], sc[1], sc[2], wide[0], lengths[0], wide[1], lengths[1], narrow[0], align[0], align[1],
                                    align[2], narrow[1], narrow[2])
 
