@@ -31,9 +31,21 @@ def words_below(lexicon):
     return below
 
 
-def truncated_state(lm, order):
-    """la_state [H]: h backed off until at most order - 1 backoff steps remain to a state without a backoff."""
+def truncated_state(lm, order, whole_arrays=None):
+    """la_state [H]: h backed off until at most order - 1 backoff steps remain to a state without a backoff.  `whole_arrays`
+    chooses between the plain loop and the same states computed whole arrays at a time (default: above 4096 states, for LMs
+    of millions of states; tests/test_beam_word_regimes_cpu.py holds the two forms to each other)."""
     backoff = np.asarray(lm.backoff, np.int64)
+    if len(backoff) > 4096 if whole_arrays is None else whole_arrays:
+        depth = np.where(backoff < 0, 0, -1)
+        while (depth < 0).any():
+            todo = depth < 0
+            d = depth[backoff[todo]]
+            depth[todo] = np.where(d >= 0, d + 1, -1)
+        out = np.arange(len(backoff))
+        while (depth[out] > order - 1).any():
+            out = np.where(depth[out] > order - 1, backoff[out], out)
+        return out.tolist()
 
     def depth(h):
         d = 0
@@ -48,6 +60,12 @@ def truncated_state(lm, order):
     return out
 
 
+# A test module that runs many restatements over one large lexicon and LM may lend them a dict for the time it runs (a fixture
+# of tests/test_hip_beam_word_regimes.py does): (lexicon, LM, order, dtype, folded weights) -> the memos of E and L, with the two
+# objects kept alive beside them so that their ids stay theirs.  None: every Look has its own memos.
+shared_memos = None
+
+
 class Look:
     """E, LA and L of the header by plain loops, in dtype dt with the folded weights lw / bw."""
 
@@ -58,9 +76,14 @@ class Look:
         self.la_state = truncated_state(lm, order)
         self.row, self.word, self.backoff = (np.asarray(a, np.int64) for a in (lm.row, lm.word, lm.backoff))
         self.lw, self.bw = lw, bw
-        self.memo = {}
+        self.memo, self.ememo = {}, {}
+        if shared_memos is not None:
+            key = (id(lexicon), id(lm), int(order), np.dtype(dt).str, hash(np.asarray(lw).tobytes()), hash(np.asarray(bw).tobytes()))
+            self.memo, self.ememo, _, _ = shared_memos.setdefault(key, (self.memo, self.ememo, lexicon, lm))
 
     def E(self, s, n):
+        if (s, n) in self.ememo:                            # (a row of thousands of arcs is looped over once per node)
+            return self.ememo[s, n]
         dt = self.dt
         best = dt(-np.inf)
         for k in range(self.row[s], self.row[s + 1]):
@@ -68,6 +91,7 @@ class Look:
                 x = dt(self.lw[k] + dt(0))                  # (-0 counts as +0)
                 if x > best:
                     best = x
+        self.ememo[s, n] = best
         return best
 
     def LA(self, s, n):

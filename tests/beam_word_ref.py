@@ -25,13 +25,22 @@ def fold_lm(lm, dt, lm_weight, word_score):
 
 
 def beam_word_ref(inputs, transition, lexicon, lm, input_lengths=None, beam_size=1, beam_threshold=np.inf, lm_weight=1.0,
-                  word_score=0.0, token_score=0.0, info=None):
+                  word_score=0.0, token_score=0.0, info=None, rank=None, max_backoff=None,
+                  rank_where=("cut", "source", "end")):
     """inputs [T,B,N], transition [N,N]; lexicon: an object with .graph (next, weight, final, start = 0), .word_of_state and
     .separator; lm: an object with row, word, logp, next, backoff, bow, start, eos.
     -> dict scores [B], path, tokens, states, lm_states, words [B,T], token_lengths, word_lengths [B].
     `info`, if a dict, receives per utterance: sizes (|A_t|), cands (candidates of frame t, the -inf ones excluded), kept (the
     pairs of A_t as a sorted list), and the totals tie_cuts (frames whose K-th and (K+1)-th candidate state had equal values)
-    and src_ties (targets whose best value came from more than one source)."""
+    and src_ties (targets whose best value came from more than one source); Q, qbits and pbits (the pair (h, q) as the integer
+    h << qbits | q, qbits = bits_of(Q), pbits = qbits + bits_of(H)); cuts, one (b, t, last pair taken, first pair dropped) per
+    tie cut; tied, one (b, t, target pair, sorted source pairs at the best value) per source tie.
+    Two hooks for the tests that ask whether an input can tell a wrong kernel from a right one; the defaults are the
+    specification.  `rank`: pairs order by rank(h << qbits | q) instead of by (h, q), wherever pairs are compared (the cut, the
+    source of a target, the winning end; `rank_where` names those of the three that use it).  Two pairs that the wrong rank cannot
+    tell apart come out in REVERSED true order: one representative of what a kernel that ignores those bits may do.  Where the
+    bits ignored are the last of the pair (9 bits: the second digit is bit 0) the bite of the hook rests on that choice alone.
+    `max_backoff`: an LM walk of more backoff steps than this rejects."""
     x = np.asarray(inputs)
     T, B, N = x.shape
     dt = x.dtype.type
@@ -52,25 +61,35 @@ def beam_word_ref(inputs, transition, lexicon, lm, input_lengths=None, beam_size
         out_edges[s_].append((int(t_), arcw[state[s_], label[t_]]))
     lw, bw, ew = fold_lm(lm, dt, lm_weight, word_score)
     row, word, lnext, backoff = (np.asarray(a, np.int64) for a in (lm.row, lm.word, lm.next, lm.backoff))
+    qbits = max(1, int(Q - 1).bit_length())
+    pbits = qbits + max(1, int(len(backoff) - 1).bit_length())
+    plain = lambda p: p                                    # noqa: E731
+    # (two pairs that a wrong rank cannot tell apart come out in the wrong order)
+    wrong = plain if rank is None else (lambda p: (rank(p[0] << qbits | p[1]), -p[0], -p[1]))
+    rk_cut, rk_src, rk_end = (wrong if n in rank_where else plain for n in ("cut", "source", "end"))
 
     def step(h, w):
         a = dt(0)
+        n = 0
         while True:
             lo, hi = row[h], row[h + 1]
             k = lo + np.searchsorted(word[lo:hi], w)
             if k < hi and word[k] == w:
                 return int(lnext[k]), dt(a + lw[k])
-            if backoff[h] < 0:
+            if backoff[h] < 0 or (max_backoff is not None and n >= max_backoff):
                 return None
             a = dt(a + bw[h])
             h = int(backoff[h])
+            n += 1
 
     lens = _clamped_lengths(input_lengths, T, B)
     res = {"scores": np.full(B, -np.inf, dt), "token_lengths": np.zeros(B, np.int64), "word_lengths": np.zeros(B, np.int64)}
     for n in ("path", "tokens", "states", "lm_states", "words"):
         res[n] = np.full((B, T), -1, np.int64)
     if info is not None:
-        info.update(sizes=[], cands=[], kept=[], tie_cuts=0, src_ties=0)
+        info.update(sizes=[], cands=[], kept=[], tie_cuts=0, src_ties=0, Q=Q, qbits=qbits, pbits=pbits, cuts=[], tied=[],
+                    out_degree=[len(e) for e in out_edges], sep_q=[q for q in range(Q) if state[q] == 0])
+    at = [0, 0]                                            # (b, t) of the frame in hand, for info
 
     def prune(cand):
         """{pair: c} -> the kept list [(pair, c)]."""
@@ -78,9 +97,10 @@ def beam_word_ref(inputs, transition, lexicon, lm, input_lengths=None, beam_size
         if not items:
             return []
         lo = dt(max(c for _, c in items) - theta)
-        items = [it for it in sorted(items, key=lambda it: (-it[1], it[0])) if it[1] >= lo]
+        items = [it for it in sorted(items, key=lambda it: (-it[1], rk_cut(it[0]))) if it[1] >= lo]
         if info is not None and len(items) > K and items[K - 1][1] == items[K][1]:
             info["tie_cuts"] += 1
+            info["cuts"].append((at[0], at[1], items[K - 1][0], items[K][0]))
         return items[:K]
 
     with np.errstate(invalid="ignore", over="ignore"):
@@ -92,6 +112,7 @@ def beam_word_ref(inputs, transition, lexicon, lm, input_lengths=None, beam_size
                     info["sizes"].append(sizes), info["cands"].append(ncand), info["kept"].append(keptl)
                 continue
             xb = x[:, b]
+            at[:] = b, 0
             cand = {(lm.start, q): dt(start_w[q] + xb[0, label[q]]) for q in range(Q) if start_w[q] > ninf}
             A = prune(cand)
             back = [{p: None for p, _ in A}]
@@ -103,10 +124,11 @@ def beam_word_ref(inputs, transition, lexicon, lm, input_lengths=None, beam_size
                 def offer(tp, c, sp):
                     cur = best.get(tp)
                     if cur is None or c > cur[0]:
-                        best[tp] = [c, sp, 1]
+                        best[tp] = [c, sp, 1, [sp]]
                     elif c == cur[0]:
                         cur[2] += 1
-                        if sp < cur[1]:
+                        cur[3].append(sp)
+                        if rk_src(sp) < rk_src(cur[1]):
                             cur[1] = sp
                 for (h, q), v in A:
                     j = label[q]
@@ -129,6 +151,8 @@ def beam_word_ref(inputs, transition, lexicon, lm, input_lengths=None, beam_size
                             offer((h2, q2), c, (h, q))
                 if info is not None:
                     info["src_ties"] += sum(1 for v_ in best.values() if v_[2] > 1)
+                    info["tied"] += [(b, t, tp, sorted(v_[3])) for tp, v_ in best.items() if v_[2] > 1]
+                at[:] = b, t
                 A = prune({tp: dt(v_[0] + xb[t, label[tp[1]]]) for tp, v_ in best.items()})
                 back.append({p: best[p][1] for p, _ in A})
                 sizes.append(len(A)), ncand.append(nc), keptl.append(sorted(p for p, _ in A))
@@ -149,7 +173,7 @@ def beam_word_ref(inputs, transition, lexicon, lm, input_lengths=None, beam_size
                 else:
                     continue
                 e = dt(dt(v + finw[s]) + endw)
-                if e > ninf and (win is None or e > win[0] or (e == win[0] and (h, q) < win[1])):
+                if e > ninf and (win is None or e > win[0] or (e == win[0] and rk_end((h, q)) < rk_end(win[1]))):
                     win = (e, (h, q), fw)
             if win is None:
                 continue
