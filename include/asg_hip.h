@@ -574,6 +574,64 @@ int asg_beam_words_full_forward_la(asg_ctx *ctx, const asg_problem *p, const asg
                                    const struct asg_word_lookahead *la, int beam_size, double beam_threshold, void *work,
                                    size_t work_bytes, void *scores, int flags, void *stream);
 
+/* ---- WORD CONFIDENCES and END FRAMES of asg_beam_decode_words' hypothesis, from the lattice its search kept: for every word of
+ * the winning path, the frame it ends at and how much of the probability mass inside the kept sets agrees that this word ends
+ * there -- what captions, keyword hits and pseudo-labels need beside the words.  No counterpart in the reference.  Per utterance b,
+ * len = clamp(input_lengths[b], 0, T); lexicon graph, folded LM, step(h, w), PAIR ORDER, the kept sets A_t and the edges exactly
+ * as in asg_beam_decode_words / asg_beam_words_full_forward, WITHOUT targets (p->targets is not looked at): U_t = A_t.
+ *   1. Lattice paths.  A path is p_0 .. p_{len-1} with p_t in A_t, p_0 a start pair, consecutive pairs joined by one of the
+ *      search's edges (stay, lexicon edge, separator edge with its LM step), and a finite end.  Its weight is what step 3 of
+ *      asg_beam_words_full_forward sums: start, edges, transitions, emissions, end.  Z_K = lse over all of them = that call's
+ *      score without targets, bit for bit (the same kernels run).  The decoder's winning path is one of these paths.
+ *   2. Word events.  A path COMPLETES word w AT FRAME t, 1 <= t <= len-1, when its edge p_{t-1} -> p_t is a separator edge out of
+ *      a word-end node with word_of_state = w; it completes w AT FRAME len when it ends in a word-end node of w (the final step
+ *      of the end rule).  P(w, t) = sum over the paths with that event of exp(weight - Z_K): histories and source pairs are
+ *      summed over, only the word and the frame identify the event.
+ *   3. Hypothesis.  The k-th word of the winning path, k < word_lengths[b], is w_k = words[b][k]; its end frame t_k is the frame
+ *      of its separator edge (the frame whose label is the separator behind another label), or len for the word of the final
+ *      step.  t_k ascends strictly.
+ *   4. Outputs.  scores, path, tokens, token_lengths, states, lm_states, words, word_lengths: asg_beam_decode_words' own, bit for
+ *      bit (the same device text searches, ends and backtraces).  Beyond them:
+ *        word_frames      [B][T] int64: t_k, then -1 behind the words;
+ *        word_confidences [B][T] dtype: conf_k = sum over t in [t_k - tol, t_k + tol] meet [1, len] of P(w_k, t), then 0;
+ *        normalisers      [B]    dtype: Z_K.
+ *      tol = frame_tolerance.  At tol = 0, conf_k is a probability: exp(scores[b] - Z_K) <= conf_k <= 1 up to rounding (the
+ *      winning path has the event).  At tol > 0 it is the EXPECTED NUMBER of completions of w_k inside the window: it passes 1
+ *      only where a path completes a short word twice inside it, and is returned unclipped.
+ *   5. Degenerate utterances.  len == 0, an empty last set or no finite end: score -inf, normaliser -inf, integer outputs -1,
+ *      lengths 0, confidences 0.  Never a NaN.
+ * An arc posterior is exp((alpha[t-1][p] + c) - Z_K), c = beta[t][p'] + the edge's terms, with alpha of asg_beam_words_full_forward
+ * and beta its mirror image (max-then-sum per pair, the sums of asg_beam_words_full_backward); a final-step posterior is
+ * exp((alpha[len-1][p] + (final_w[q] + endw(p))) - Z_K).  Each is added to the words it counts for as a 64-bit fixed-point integer
+ * with 54 fractional bits: integer adds only, NO FLOAT ATOMICS, bit-identical run to run and for any grouping of the batch.
+ * Every output and every workspace word that is read is written by kernels (no memset, no host synchronisation): the call can be
+ * captured and replayed.  The frame loop of the search runs ONCE per utterance.
+ * K = beam_size, M = K, e = 4 / 8.  Every part rounded up to 256 bytes:
+ *   work: asg_beam_words_confidence_work_bytes(p, gb, lm, beam_size) =
+ *         B * (asg_beam_words_full_work_bytes' bytes per utterance without targets at store = 1, i.e.
+ *              asg_beam_decode_words' bytes per utterance + 2*T*4 + 256 + T*M*8 + T*M*e,     + 2*M*e (two rows of beta))
+ * The word accumulators live in LDS and need no workspace.  No term in H, V, A or Q.
+ * Limits (ASG_ERR_UNSUPPORTED beyond): those of asg_beam_words_full_forward without targets (beam_size <= 8192, N <= 1024,
+ * T <= 2^20, M <= 8179 float32 / 6816 float64), and frame_tolerance <= 64; frame_tolerance < 0: ASG_ERR_INVALID.  Argument
+ * errors: those of asg_beam_decode_words (a NULL output among them), then asg_beam_decode_words_la's for `la`.  float32 and
+ * float64.
+ * asg_beam_words_confidence_la: sets, hypothesis and the eight decoder outputs are asg_beam_decode_words_la's, bit for bit; the
+ * lattice keeps the PLAIN weights, exactly as asg_beam_words_full_forward_la does (look-ahead terms cancel along complete
+ * paths), so normalisers has that call's bits and scores[b] - Z_K <= 0 holds up to the rounding of the cancelling terms. */
+size_t asg_beam_words_confidence_work_bytes(const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                            int beam_size);
+int asg_beam_words_confidence(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                              int beam_size, double beam_threshold, int frame_tolerance, void *work, size_t work_bytes,
+                              void *scores, int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states,
+                              int64_t *lm_states, int64_t *words, int64_t *word_lengths, int64_t *word_frames,
+                              void *word_confidences, void *normalisers, int flags, void *stream);
+int asg_beam_words_confidence_la(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                 const struct asg_word_lookahead *la, int beam_size, double beam_threshold, int frame_tolerance,
+                                 void *work, size_t work_bytes, void *scores, int64_t *path, int64_t *tokens,
+                                 int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words,
+                                 int64_t *word_lengths, int64_t *word_frames, void *word_confidences, void *normalisers,
+                                 int flags, void *stream);
+
 /* ---- asg_beam_decode_words with LM LOOK-AHEAD: inside a word, a pair's value also carries the best LM score that any word below
  * its trie node can still get after the pair's history, so that a narrow beam ranks partial words by more than acoustics.  The
  * term telescopes: every edge adds the difference between the look-ahead of its two ends, the separator edge takes back what the

@@ -462,6 +462,54 @@ class HipBackend:
                                 out[4, b0].data_ptr(), lengths[1, b0:].data_ptr(), 0, stream), what)
         return BeamWords(scores, out[0], out[1], lengths[0], out[2], out[3], out[4], lengths[1])
 
+    def beam_decode_words_confidence(self, inputs, transition, lexicon, word_lm, input_lengths, beam_size,
+                                     beam_threshold=float("inf"), lm_weight=1.0, word_score=0.0, token_score=0.0,
+                                     frame_tolerance=0, max_work_bytes=1 << 30, lookahead=None):
+        """`beam_decode_words` with the end frame and the lattice posterior of every word of the hypothesis -> BeamWordsConfidence;
+        see include/asg_hip.h::asg_beam_words_confidence and, with a `WordLookahead`, asg_beam_words_confidence_la.  Grouped under
+        `max_work_bytes` as `_decode_graph` does."""
+        from . import wordlm as _wordlm
+        _wordlm.check_words(lexicon, word_lm)
+        if lookahead is not None:
+            _wordlm.check_lookahead(lookahead, lexicon, word_lm)
+        beam_size, beam_threshold = min(int(beam_size), (1 << 31) - 1), float(beam_threshold)
+        tol = max(-1, min(int(frame_tolerance), (1 << 31) - 1))
+        L = _lib.lib()
+        self._check_graph_inputs(inputs, transition, lexicon.graph, input_lengths)
+        T, B, N = inputs.shape
+        dev = inputs.device
+        with self._guard(dev):
+            g, w, (lex, _) = _wordlm.abi_words(lexicon, word_lm, dev, inputs.dtype, lm_weight, word_score, token_score)
+            p, _, input_lengths, _ = self._device_problem(inputs, transition, None, input_lengths, None)
+            what = "asg_beam_words_confidence"
+            if lookahead is not None:
+                what = "asg_beam_words_confidence_la"
+                la_dev = lookahead.compile(dev, inputs.dtype, lm_weight, word_score)
+                la = _wordlm.abi_lookahead(la_dev)
+
+            def call(work, nbytes, *outs):
+                if lookahead is not None:
+                    return L.asg_beam_words_confidence_la(None, ctypes.byref(p), ctypes.byref(g), ctypes.byref(w), ctypes.byref(la),
+                                                          beam_size, beam_threshold, tol, work, nbytes, *outs)
+                return L.asg_beam_words_confidence(None, ctypes.byref(p), ctypes.byref(g), ctypes.byref(w), beam_size,
+                                                   beam_threshold, tol, work, nbytes, *outs)
+            groups = self._groups(
+                p, B, max_work_bytes,
+                lambda: L.asg_beam_words_confidence_work_bytes(ctypes.byref(p), ctypes.byref(g), ctypes.byref(w), beam_size),
+                lex["Q"], lambda: _lib.check(call(None, 0, *(None,) * 11, 0, None), what),
+                inputs, input_lengths=input_lengths)
+            real = torch.empty(2, B, dtype=inputs.dtype, device=dev)       # scores, normalisers
+            conf = torch.empty(B, T, dtype=inputs.dtype, device=dev)
+            out = torch.empty(6, B, T, dtype=torch.int64, device=dev)      # path, tokens, states, lm_states, words, word_frames
+            lengths = torch.empty(2, B, dtype=torch.int64, device=dev)     # token_lengths, word_lengths
+            stream = self._stream(dev)
+            for b0, b1, work in groups:
+                _lib.check(call(work.data_ptr(), work.numel(), real[0, b0:].data_ptr(), out[0, b0].data_ptr(),
+                                out[1, b0].data_ptr(), lengths[0, b0:].data_ptr(), out[2, b0].data_ptr(), out[3, b0].data_ptr(),
+                                out[4, b0].data_ptr(), lengths[1, b0:].data_ptr(), out[5, b0].data_ptr(), conf[b0].data_ptr(),
+                                real[1, b0:].data_ptr(), 0, stream), what)
+        return BeamWordsConfidence(real[0], out[0], out[1], lengths[0], out[2], out[3], out[4], lengths[1], out[5], conf, real[1])
+
     def beam_decode_words_nbest(self, inputs, transition, lexicon, word_lm, input_lengths, beam_size, nbest,
                                 beam_threshold=float("inf"), lm_weight=1.0, word_score=0.0, token_score=0.0,
                                 return_alignments=False, max_work_bytes=1 << 30, lookahead=None):
@@ -1223,6 +1271,43 @@ def beam_decode_words(inputs, transition, lexicon, word_lm, input_lengths=None, 
                                           lm_weight, word_score, token_score, max_work_bytes, lookahead)
 
 
+BeamWordsConfidence = collections.namedtuple("BeamWordsConfidence", BeamWords._fields + ("word_frames", "word_confidences",
+                                                                                       "normalisers"))
+
+
+def beam_decode_words_confidence(inputs, transition, lexicon, word_lm, input_lengths=None, beam_size=256,
+                                 beam_threshold=float("inf"), lm_weight=1.0, word_score=0.0, token_score=0.0, frame_tolerance=0,
+                                 max_work_bytes=1 << 30, lookahead=None):
+    """`beam_decode_words` that also says where every word of its hypothesis ends and how sure the search is of it: what
+    captions, keyword hits and pseudo-labels need beside the words.  No gradient.
+
+    The search is `beam_decode_words`', run once.  The sets of pairs it kept span a lattice (the one `beam_words_full_score`
+    sums without targets); a lattice path completes word w at frame t when it takes a separator edge out of a word-end node of
+    w into frame t, or, at t = len, when it ends in such a node.  P(w, t) is the share of the lattice's probability mass,
+    exp(weight - Z_K), on the paths with that event, whatever their LM history
+    (include/asg_hip.h::asg_beam_words_confidence).  -> BeamWordsConfidence: the eight fields of `BeamWords`, bit for bit, and
+      word_frames      [B, T] int64  the frame t_k at which word k of the hypothesis ends (len for a word ended by the end of
+                                     the utterance), -1 behind the words
+      word_confidences [B, T] dtype  the sum of P(words[k], t) over |t - t_k| <= frame_tolerance, 0 behind the words
+      normalisers      [B]    dtype  Z_K, bit-equal to `beam_words_full_score` without targets
+    With frame_tolerance = 0 a confidence is a probability, between exp(scores - normalisers) and 1 up to rounding.  With a
+    tolerance it is the expected number of completions of the word inside the window: it can pass 1 where a path completes a
+    short word twice within it, and is returned unclipped.  A narrow beam keeps little competing mass, so its confidences are
+    high: they are posteriors given what the search kept.  Utterances without a path have score and normaliser -inf, integer
+    outputs -1 and confidences 0; there is never a NaN.  frame_tolerance < 0 or > 64 is refused by the library (RuntimeError).
+
+    Results are bit-identical run to run and for any `max_work_bytes`; inputs, widening, caching, capture and the utterance
+    groups are those of `beam_decode_words`, with a workspace about T * beam_size * (24 + 8 or 16) bytes per utterance.
+    `lookahead` takes the sets and the hypothesis of `beam_decode_words(..., lookahead=)`; the lattice keeps the plain weights,
+    as `beam_words_full_score(..., lookahead=)` does.
+    """
+    _check_beam(beam_size, beam_threshold)
+    with torch.no_grad():
+        return native().beam_decode_words_confidence(*_plain(inputs, transition), lexicon, word_lm, input_lengths, beam_size,
+                                                     beam_threshold, lm_weight, word_score, token_score, frame_tolerance,
+                                                     max_work_bytes, lookahead)
+
+
 BeamWordsNbest = collections.namedtuple("BeamWordsNbest", ["scores", "emission_scores", "graph_scores", "lm_scores", "tokens",
                                                            "token_lengths", "words", "word_lengths", "num_hyps", "path", "states",
                                                            "lm_states"])
@@ -1746,6 +1831,14 @@ class ASGLoss(nn.Module):
         `torch_asg_amd.beam_decode_words`."""
         return beam_decode_words(inputs, self.transition, lexicon, word_lm, input_lengths, beam_size, beam_threshold, lm_weight,
                                  word_score, token_score, max_work_bytes, lookahead)
+
+    def beam_decode_words_confidence(self, inputs, lexicon, word_lm, input_lengths=None, beam_size=256,
+                                     beam_threshold=float("inf"), lm_weight=1.0, word_score=0.0, token_score=0.0,
+                                     frame_tolerance=0, max_work_bytes=1 << 30, lookahead=None):
+        """`beam_decode_words` under this criterion's transitions with the end frame and the lattice posterior of every word;
+        see `torch_asg_amd.beam_decode_words_confidence`."""
+        return beam_decode_words_confidence(inputs, self.transition, lexicon, word_lm, input_lengths, beam_size, beam_threshold,
+                                            lm_weight, word_score, token_score, frame_tolerance, max_work_bytes, lookahead)
 
     def beam_decode_words_nbest(self, inputs, lexicon, word_lm, input_lengths=None, beam_size=256, nbest=10,
                                 beam_threshold=float("inf"), lm_weight=1.0, word_score=0.0, token_score=0.0,

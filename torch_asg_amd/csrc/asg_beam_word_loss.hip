@@ -30,6 +30,7 @@
 #include "asg_kernels.h"
 #include "asg_beam_common.h"
 #include "asg_beam_word_frame.h"  // the frame of the search, the LM walk and the end of a pair
+#include "asg_beam_word_lat.h"    // bind_walk and WordLat: how a pair's edges are walked (shared with asg_beam_word_conf.hip)
 #include "asg_beam_lattice.h"     // everything behind the search that the token family's loss shares
 
 namespace asg {
@@ -37,12 +38,6 @@ namespace asg {
 namespace {
 
 constexpr double kBSumScale = 281474976710656.0;              // 2^48: a target's sum of exp(c - max) over < 2^14 candidates
-
-// The read-only part of a BeamWordFrame for the kernels that only walk the graph and the LM.
-template <typename R>
-__device__ __forceinline__ void bind_walk(BeamWordFrame<R> &f, const GraphArgs &g, const BeamGraphArgs &bg, const WordLmArgs &lm) {
-    bind_graph<R, false>(f, g, bg, lm, 1, 1, 1);
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // 1: the search.  beam_word_kernel's frame loop; cnt[t] = |A_t| for t < len.  With LA it is beam_word_la_kernel's frame loop
@@ -311,44 +306,8 @@ __global__ void __launch_bounds__(kBL) beam_word_loss_fwd(Problem P, GraphArgs g
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Backward: beam_loss_bwd<R, TL, WordLat<R>> (asg_beam_lattice.h).  beta PULLS: a pair's own outgoing row is a gather against
-// U_{t+1} in LDS; a separator edge walks the LM.
+// Backward: beam_loss_bwd<R, TL, WordLat<R>> (asg_beam_lattice.h) with the WordLat of asg_beam_word_lat.h.
 // ---------------------------------------------------------------------------------------------------------------------
-template <typename R>
-struct WordLat {
-    using Key = unsigned long long;
-    struct Args { GraphArgs g; BeamGraphArgs bg; WordLmArgs lm; BeamWordLossLayout lay; };
-    BeamWordFrame<R> f;
-    const R *fw;
-    Key qmask;
-    __device__ void bind(const Args &a) {
-        bind_walk<R>(f, a.g, a.bg, a.lm);
-        fw = (const R *) a.g.final_w;
-        qmask = (1ull << f.qbits) - 1ull;
-    }
-    __device__ int label(Key p) const { return f.label[(int) (p & qmask)]; }
-    __device__ void end(Key p, R &e) const {
-        int w;
-        if (!word_end<R>(f, fw, (int) (p >> f.qbits), (int) (p & qmask), (R) 0, e, w)) e = Num<R>::ninf();
-    }
-    template <typename F> __device__ void for_each_out(Key p, int lg, int G, F fn) const {
-        const int q = (int) (p & qmask), h = (int) (p >> f.qbits);
-        const int e1 = f.orow[q + 1];
-        for (int e = f.orow[q] + lg; e < e1; e += G) {
-            const int2 arc = f.oarc[e];
-            int th = h;
-            R w = f.ow[e];
-            if (arc.y == f.sep) {                                             // a word ends: the LM moves
-                R add;
-                int h2;
-                if (!f.step(h, f.wos[f.state[q]], h2, add)) continue;
-                th = h2;
-                w = w + add;
-            }
-            fn(f.pair(th, arc.x), [&]() -> R { return w; }, arc.y);
-        }
-    }
-};
 
 inline size_t wfwd_lds(int elem, int M) { return kBLHead + (size_t) M * (16 + elem); }
 }  // namespace
@@ -406,12 +365,23 @@ hipError_t launch_beam_word_loss_forward(const Problem &P, const GraphArgs &G, c
         else ASG_BEAM_WORD_LOSS_SEARCH(false, false, WordNoLook{});
 #undef ASG_BEAM_WORD_LOSS_SEARCH
     }
-    hipError_t e = hipGetLastError();
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
+    return launch_beam_word_loss_lattice<R>(P, G, BG, LM, lay, K, store, work, scores, stream);
+}
+
+// Launches 2 - 4 behind a search that left bq / bh / cnt in the layout `lay` (lay.per: the distance of the utterances, which a
+// caller with parts of its own behind the layout may have widened -- asg_beam_word_conf.hip).
+template <typename R>
+hipError_t launch_beam_word_loss_lattice(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                                         const BeamWordLossLayout &lay, int K, bool store, void *work, void *scores,
+                                         hipStream_t stream) {
+    const int B = P.B;
+    char *w = (char *) work;
     hipLaunchKernelGGL((beam_word_loss_targets<R>), dim3((B + 63) / 64), dim3(64), 0, stream, P, G, BG, LM, lay, w);
     int qbits = 1;
     while (((int64_t) 1 << qbits) < G.Q) ++qbits;                                // (bits_of on the host)
-    e = launch_beam_loss_sets(P, WordSets{lay, K, qbits}, w, stream);
+    const hipError_t e = launch_beam_loss_sets(P, WordSets{lay, K, qbits}, w, stream);
     if (e != hipSuccess) return e;
     const size_t dyn = wfwd_lds(sizeof(R), lay.M);
     set_lds((const void *) beam_word_loss_fwd<R>, dyn);
@@ -440,6 +410,9 @@ hipError_t launch_beam_word_target_scores(const Problem &P, const GraphArgs &G, 
 #define ASG_WORD_LOSS_INST(R)                                                                                                    \
     template hipError_t launch_beam_word_loss_forward<R>(const Problem &, const GraphArgs &, const BeamGraphArgs &,             \
                                                          const WordLmArgs &, const WordLookArgs *, int, double, bool, void *,   \
+                                                         void *, hipStream_t);                                                  \
+    template hipError_t launch_beam_word_loss_lattice<R>(const Problem &, const GraphArgs &, const BeamGraphArgs &,             \
+                                                         const WordLmArgs &, const BeamWordLossLayout &, int, bool, void *,     \
                                                          void *, hipStream_t);                                                  \
     template hipError_t launch_beam_word_loss_backward<R>(const Problem &, const GraphArgs &, const BeamGraphArgs &,            \
                                                           const WordLmArgs &, int, const void *, const void *, const void *,    \

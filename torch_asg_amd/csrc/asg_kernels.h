@@ -416,6 +416,11 @@ template <typename R>
 hipError_t launch_beam_word_loss_forward(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
                                          const WordLookArgs *LA, int K, double theta, bool store, void *work, void *scores,
                                          hipStream_t stream);
+// launches 2 - 4 of that forward alone (target walk, sets, alpha and Z_K) behind a search that left bq / bh / cnt in `lay`
+template <typename R>
+hipError_t launch_beam_word_loss_lattice(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                                         const BeamWordLossLayout &lay, int K, bool store, void *work, void *scores,
+                                         hipStream_t stream);
 template <typename R>
 hipError_t launch_beam_word_loss_backward(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int K,
                                           const void *work, const void *scores, const void *grad_scores, void *grad_inputs,
@@ -423,6 +428,23 @@ hipError_t launch_beam_word_loss_backward(const Problem &P, const GraphArgs &G, 
 template <typename R>
 hipError_t launch_beam_word_target_scores(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
                                           void *out, hipStream_t stream);
+
+// ---- Word confidences and end frames from the lattice of the word decoder (asg_beam_word_conf.hip):
+// asg_beam_words_confidence.  One utterance's workspace: the pair loss's layout without targets with alpha stored for all frames
+// (M = K), then two rows of beta [2][M] that the pull hands from one frame to the next.  The accumulators of the hypothesis'
+// words live in LDS.  LA: the look-ahead of the search, or NULL; nothing behind the search reads it.
+constexpr int kBeamWordConfMaxTol = 64;     // a ring of 256 accumulators holds every word whose window is open
+struct BeamWordConfLayout {
+    BeamWordLossLayout lat;      // lat.per is this layout's `per`
+    size_t beta, per;
+};
+BeamWordConfLayout beam_word_conf_layout(int elem, int T, int K, int cap);
+size_t beam_word_conf_work_bytes(int elem, int T, int B, int K, int cap);
+template <typename R>
+hipError_t launch_beam_word_conf(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                                 const WordLookArgs *LA, int K, double theta, int tol, void *work, void *scores, long long *path,
+                                 long long *tokens, long long *tlen, long long *states, long long *lm_states, long long *words,
+                                 long long *wlen, long long *word_frames, void *word_conf, void *normalisers, hipStream_t stream);
 
 // ---- Full score, gradients and target walk over the same composed lattice (asg_graph_loss.hip).  The loss-only arrays of
 // asg_token_graph_loss.  Work = alpha [T][Q][B] (stored) or [2][Q][B]; scratch = align256([2][Q][B] beta) + [Q+E][B]
