@@ -11,6 +11,7 @@ order by h, then q.
 """
 import numpy as np
 
+from beam_decode_ref import select_info
 from graph_decode_ref import _clamped_lengths, fold, product
 
 
@@ -34,7 +35,9 @@ def beam_word_ref(inputs, transition, lexicon, lm, input_lengths=None, beam_size
     pairs of A_t as a sorted list), and the totals tie_cuts (frames whose K-th and (K+1)-th candidate state had equal values)
     and src_ties (targets whose best value came from more than one source); Q, qbits and pbits (the pair (h, q) as the integer
     h << qbits | q, qbits = bits_of(Q), pbits = qbits + bits_of(H)); cuts, one (b, t, last pair taken, first pair dropped) per
-    tie cut; tied, one (b, t, target pair, sorted source pairs at the best value) per source tie.
+    tie cut; tied, one (b, t, target pair, sorted source pairs at the best value) per source tie; select, per utterance and frame
+    the record of tests/beam_decode_ref.py::select_info (the width `rem` of the key select and the exit it takes), the pairs as
+    the integers h << qbits | q.
     Two hooks for the tests that ask whether an input can tell a wrong kernel from a right one; the defaults are the
     specification.  `rank`: pairs order by rank(h << qbits | q) instead of by (h, q), wherever pairs are compared (the cut, the
     source of a target, the winning end; `rank_where` names those of the three that use it).  Two pairs that the wrong rank cannot
@@ -88,12 +91,15 @@ def beam_word_ref(inputs, transition, lexicon, lm, input_lengths=None, beam_size
         res[n] = np.full((B, T), -1, np.int64)
     if info is not None:
         info.update(sizes=[], cands=[], kept=[], tie_cuts=0, src_ties=0, Q=Q, qbits=qbits, pbits=pbits, cuts=[], tied=[],
-                    out_degree=[len(e) for e in out_edges], sep_q=[q for q in range(Q) if state[q] == 0])
+                    select=[], out_degree=[len(e) for e in out_edges], sep_q=[q for q in range(Q) if state[q] == 0])
     at = [0, 0]                                            # (b, t) of the frame in hand, for info
 
     def prune(cand):
         """{pair: c} -> the kept list [(pair, c)]."""
         items = [(p, c) for p, c in cand.items() if c > ninf]
+        if info is not None:
+            info["select"][-1].append(select_info(np.array([p[0] << qbits | p[1] for p, _ in items], np.int64),
+                                                  np.array([c for _, c in items], dt), K, theta))
         if not items:
             return []
         lo = dt(max(c for _, c in items) - theta)
@@ -107,6 +113,8 @@ def beam_word_ref(inputs, transition, lexicon, lm, input_lengths=None, beam_size
         for b in range(B):
             L = int(lens[b])
             sizes, ncand, keptl = [], [], []
+            if info is not None:
+                info["select"].append([])
             if L == 0 or Q == 0:
                 if info is not None:
                     info["sizes"].append(sizes), info["cands"].append(ncand), info["kept"].append(keptl)
