@@ -632,6 +632,58 @@ int asg_beam_words_confidence_la(asg_ctx *ctx, const asg_problem *p, const asg_t
                                  int64_t *word_lengths, int64_t *word_frames, void *word_confidences, void *normalisers,
                                  int flags, void *stream);
 
+/* ---- WORD CONFIDENCES and END FRAMES for EVERY ROW of asg_beam_decode_words_nbest's list: what rescoring with a stronger LM,
+ * confusion-network / ROVER combination of the rows and pseudo-labelling on their agreement need.  The quantity is not new:
+ * P(w, t) of asg_beam_words_confidence does not depend on the hypothesis; a row only selects which (word, frame) cells are read.
+ * Per utterance b everything is asg_beam_decode_words_nbest's (or _nbest_la's) and asg_beam_words_confidence's (or _la's) on the
+ * same arguments: the same search, run ONCE; the same kept sets A_t; the lattice with U_t = A_t and the plain weights; the same
+ * Z_K; the same word events P(w, t).  The argument order is asg_beam_decode_words_nbest's with frame_tolerance behind nbest and
+ * word_frames, word_confidences, normalisers behind num_hyps; the _la form takes the look-ahead behind the LM.
+ *   1. The twelve n-best outputs of asg_beam_decode_words_nbest / _la, bit for bit (the same device text ranks, walks and
+ *      writes).  path, states and lm_states may be NULL.
+ *   2. word_frames [B][nbest][T] int64.  For row r < num_hyps[b] and k < word_lengths[b][r], t_{r,k} is the frame of the k-th
+ *      separator edge of the row's path (step 3 of asg_beam_words_confidence, applied to the row's path), or len for the word
+ *      closed by the final step.  It ascends strictly within a row.  -1 behind the words and in padding rows.
+ *   3. word_confidences [B][nbest][T] dtype.  conf_{r,k} = sum of P(words[b][r][k], t) over t in [t_{r,k} - tol, t_{r,k} + tol]
+ *      meet [1, len]; 0 behind the words and in padding rows; unclipped.  tol = frame_tolerance.
+ *   4. normalisers [B] dtype: Z_K.
+ * Properties.  Row 0's frames and confidences are asg_beam_words_confidence's on the same arguments, bit for bit: an event is
+ * added as the same 54-bit fixed-point integer, and an integer sum does not depend on its order.  At tol = 0,
+ * exp(scores[b][r] - Z_K) <= conf_{r,k} <= 1 up to rounding for every row: a row's path is a lattice path that has the event.
+ * Rows that hold the same word ending at the same frame get the same bits (they read one cell).  Degenerate utterances (len == 0,
+ * an empty last set, no finite end): num_hyps 0, normaliser -inf, frames -1, confidences 0; never a NaN.  NO FLOAT ATOMICS, no
+ * memset, no host synchronisation: bit-identical run to run and for any grouping of the batch, and the call can be captured and
+ * replayed.  The frame loop of the search runs ONCE per utterance.
+ * K = beam_size, M = K, e = 4 / 8, nb = min(nbest, K), P2(x) = the power of two >= max(x, 2).  Every part rounded up to 256 bytes:
+ *   work: asg_beam_words_nbest_confidence_work_bytes(p, gb, lm, beam_size, nbest) =
+ *         B * (asg_beam_words_confidence_work_bytes' bytes per utterance
+ *              + 8 + K*(e+8) (the last set) + T*nb*4 (the rows' product states) + 256 + (T+2)*4 (the first cell of every frame)
+ *              + P2(nb*T)*8 (the rows' queries) + nb*T*8 (the cells) + nb*T*8 (their sums))
+ *         + 3 * (B*8) + 6*B*T*8 (the one-best outputs of the search).
+ * No term in H, V, A or Q.
+ * Limits: the union of the two parent calls': nbest < 1 or frame_tolerance < 0: ASG_ERR_INVALID; nbest > 8192 or
+ * frame_tolerance > 64: ASG_ERR_UNSUPPORTED; the limits of asg_beam_words_confidence.  ONE new limit (ASG_ERR_UNSUPPORTED
+ * beyond): the accumulators of the open cells live in LDS beside a frame's lattice set,
+ *         16 * ceil(M*(e+8) / 16) + 1024 + 12 * P2(min(nbest, K) * (2*frame_tolerance + 2)) <= 163840   and   nb*T <= 2^30.
+ * Argument errors, in this order: asg_beam_words_confidence's for p, gb, lm and beam_size; nbest; frame_tolerance and the new
+ * limit; `la` as asg_beam_decode_words_la checks it; the threshold; a NULL among work and the outputs other than path, states,
+ * lm_states; the workspace.  float32 and float64. */
+size_t asg_beam_words_nbest_confidence_work_bytes(const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                                  int beam_size, int nbest);
+int asg_beam_words_nbest_confidence(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                    int beam_size, double beam_threshold, int nbest, int frame_tolerance, void *work,
+                                    size_t work_bytes, void *scores, void *emission_scores, void *graph_scores, void *lm_scores,
+                                    int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *lm_states,
+                                    int64_t *words, int64_t *word_lengths, int64_t *num_hyps, int64_t *word_frames,
+                                    void *word_confidences, void *normalisers, int flags, void *stream);
+int asg_beam_words_nbest_confidence_la(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                       const struct asg_word_lookahead *la, int beam_size, double beam_threshold, int nbest,
+                                       int frame_tolerance, void *work, size_t work_bytes, void *scores, void *emission_scores,
+                                       void *graph_scores, void *lm_scores, int64_t *path, int64_t *tokens, int64_t *token_lengths,
+                                       int64_t *states, int64_t *lm_states, int64_t *words, int64_t *word_lengths,
+                                       int64_t *num_hyps, int64_t *word_frames, void *word_confidences, void *normalisers,
+                                       int flags, void *stream);
+
 /* ---- asg_beam_decode_words with LM LOOK-AHEAD: inside a word, a pair's value also carries the best LM score that any word below
  * its trie node can still get after the pair's history, so that a narrow beam ranks partial words by more than acoustics.  The
  * term telescopes: every edge adds the difference between the look-ahead of its two ends, the separator edge takes back what the

@@ -39,7 +39,8 @@ SYMBOLS = ["asg_hip_version", "asg_hip_strerror", "asg_ctx_create", "asg_ctx_des
            "asg_beam_words_full_work_bytes", "asg_beam_words_full_scratch_bytes", "asg_beam_words_full_forward",
            "asg_beam_words_full_backward", "asg_words_target_scores", "asg_beam_words_full_forward_la",
            "asg_beam_decode_words_nbest_la", "asg_beam_word_stream_nbest_la",
-           "asg_beam_words_confidence_work_bytes", "asg_beam_words_confidence", "asg_beam_words_confidence_la"]
+           "asg_beam_words_confidence_work_bytes", "asg_beam_words_confidence", "asg_beam_words_confidence_la",
+           "asg_beam_words_nbest_confidence_work_bytes", "asg_beam_words_nbest_confidence", "asg_beam_words_nbest_confidence_la"]
 ABI_VERSION = 230        # include/asg_hip.h: ASG_HIP_VERSION this package was written against
 
 
@@ -207,6 +208,11 @@ def lib():
     L.asg_beam_words_confidence.argtypes = [vp, pp, bp, wp, ci, ctypes.c_double, ci, vp, sz] + [vp] * 11 + [ci, vp]
     L.asg_beam_words_confidence_la.argtypes = [vp, pp, bp, wp, ctypes.POINTER(AsgWordLookahead), ci, ctypes.c_double, ci, vp,
                                                sz] + [vp] * 11 + [ci, vp]
+    L.asg_beam_words_nbest_confidence_work_bytes.restype = sz
+    L.asg_beam_words_nbest_confidence_work_bytes.argtypes = [pp, bp, wp, ci, ci]
+    L.asg_beam_words_nbest_confidence.argtypes = [vp, pp, bp, wp, ci, ctypes.c_double, ci, ci, vp, sz] + [vp] * 15 + [ci, vp]
+    L.asg_beam_words_nbest_confidence_la.argtypes = [vp, pp, bp, wp, ctypes.POINTER(AsgWordLookahead), ci, ctypes.c_double, ci,
+                                                     ci, vp, sz] + [vp] * 15 + [ci, vp]
     lp = ctypes.POINTER(AsgTokenGraphLoss)
     L.asg_graph_full_work_bytes.restype = sz
     L.asg_graph_full_work_bytes.argtypes = [pp, lp, ci]

@@ -561,6 +561,62 @@ class HipBackend:
         return BeamWordsNbest(sc[0], sc[1], sc[2], sc[3], wide[0], lengths[0], wide[1], lengths[1], num_hyps, align[0], align[1],
                               align[2])
 
+    def beam_decode_words_nbest_confidence(self, inputs, transition, lexicon, word_lm, input_lengths, beam_size, nbest,
+                                           beam_threshold=float("inf"), lm_weight=1.0, word_score=0.0, token_score=0.0,
+                                           frame_tolerance=0, return_alignments=False, max_work_bytes=1 << 30, lookahead=None):
+        """`beam_decode_words_nbest` with the end frame and the lattice posterior of every word of every row, from one search
+        -> BeamWordsNbestConfidence; see include/asg_hip.h::asg_beam_words_nbest_confidence and, with a `WordLookahead`,
+        asg_beam_words_nbest_confidence_la.  Grouped under `max_work_bytes` as `_decode_graph` does."""
+        from . import wordlm as _wordlm
+        _wordlm.check_words(lexicon, word_lm)
+        if lookahead is not None:
+            _wordlm.check_lookahead(lookahead, lexicon, word_lm)
+        beam_size, beam_threshold = min(int(beam_size), (1 << 31) - 1), float(beam_threshold)
+        nbest = min(int(nbest), (1 << 31) - 1)
+        tol = max(-1, min(int(frame_tolerance), (1 << 31) - 1))
+        L = _lib.lib()
+        self._check_graph_inputs(inputs, transition, lexicon.graph, input_lengths)
+        T, B, N = inputs.shape
+        dev = inputs.device
+        with self._guard(dev):
+            g, w, (lex, _) = _wordlm.abi_words(lexicon, word_lm, dev, inputs.dtype, lm_weight, word_score, token_score)
+            p, _, input_lengths, _ = self._device_problem(inputs, transition, None, input_lengths, None)
+            what = "asg_beam_words_nbest_confidence"
+            if lookahead is not None:
+                what = "asg_beam_words_nbest_confidence_la"
+                la_dev = lookahead.compile(dev, inputs.dtype, lm_weight, word_score)
+                la = _wordlm.abi_lookahead(la_dev)
+
+            def call(work, nbytes, *outs):
+                if lookahead is not None:
+                    return L.asg_beam_words_nbest_confidence_la(None, ctypes.byref(p), ctypes.byref(g), ctypes.byref(w),
+                                                                ctypes.byref(la), beam_size, beam_threshold, nbest, tol, work, nbytes,
+                                                                *outs)
+                return L.asg_beam_words_nbest_confidence(None, ctypes.byref(p), ctypes.byref(g), ctypes.byref(w), beam_size,
+                                                         beam_threshold, nbest, tol, work, nbytes, *outs)
+            groups = self._groups(
+                p, B, max_work_bytes,
+                lambda: L.asg_beam_words_nbest_confidence_work_bytes(ctypes.byref(p), ctypes.byref(g), ctypes.byref(w), beam_size,
+                                                                     nbest),
+                lex["Q"], lambda: _lib.check(call(None, 0, *(None,) * 15, 0, None), what),
+                inputs, input_lengths=input_lengths)
+            sc = torch.empty(4, B, nbest, dtype=inputs.dtype, device=dev)      # scores, emission, graph and LM scores
+            wide = torch.empty(3, B, nbest, T, dtype=torch.int64, device=dev)  # tokens, words, word_frames
+            conf = torch.empty(B, nbest, T, dtype=inputs.dtype, device=dev)
+            align = torch.empty(3, B, nbest, T, dtype=torch.int64, device=dev) if return_alignments else (None,) * 3
+            lengths = torch.empty(2, B, nbest, dtype=torch.int64, device=dev)  # token_lengths, word_lengths
+            num_hyps = torch.empty(B, dtype=torch.int64, device=dev)
+            norm = torch.empty(B, dtype=inputs.dtype, device=dev)
+            al = lambda i, b0: align[i, b0:].data_ptr() if return_alignments else None      # noqa: E731
+            stream = self._stream(dev)
+            for b0, b1, work in groups:
+                _lib.check(call(work.data_ptr(), work.numel(), sc[0, b0:].data_ptr(), sc[1, b0:].data_ptr(), sc[2, b0:].data_ptr(),
+                                sc[3, b0:].data_ptr(), al(0, b0), wide[0, b0:].data_ptr(), lengths[0, b0:].data_ptr(), al(1, b0),
+                                al(2, b0), wide[1, b0:].data_ptr(), lengths[1, b0:].data_ptr(), num_hyps[b0:].data_ptr(),
+                                wide[2, b0:].data_ptr(), conf[b0:].data_ptr(), norm[b0:].data_ptr(), 0, stream), what)
+        return BeamWordsNbestConfidence(sc[0], sc[1], sc[2], sc[3], wide[0], lengths[0], wide[1], lengths[1], num_hyps, align[0],
+                                        align[1], align[2], wide[2], conf, norm)
+
     def _check_graph_inputs(self, inputs, transition, graph, input_lengths, targets=None, target_lengths=None):
         """The argument checks of every entry point that takes a token automaton."""
         from . import graph as _graph
@@ -1352,6 +1408,46 @@ def beam_decode_words_nbest(inputs, transition, lexicon, word_lm, input_lengths=
                                                 max_work_bytes, lookahead)
 
 
+BeamWordsNbestConfidence = collections.namedtuple("BeamWordsNbestConfidence", BeamWordsNbest._fields + (
+    "word_frames", "word_confidences", "normalisers"))
+
+
+def beam_decode_words_nbest_confidence(inputs, transition, lexicon, word_lm, input_lengths=None, beam_size=256, nbest=10,
+                                       beam_threshold=float("inf"), lm_weight=1.0, word_score=0.0, token_score=0.0,
+                                       frame_tolerance=0, return_alignments=False, max_work_bytes=1 << 30, lookahead=None):
+    """`beam_decode_words_nbest` that also says, for every word of EVERY row, where it ends and how sure the search is of it:
+    what rescoring with a per-word posterior as a feature, confusion-network or ROVER-style combination of the rows and
+    pseudo-labelling on the words the rows agree on need.  One search serves both.  No gradient.
+
+    The quantity is `beam_decode_words_confidence`'s: P(w, t), the share of the kept lattice's probability mass on the paths
+    that complete word w at frame t, does not depend on the hypothesis; a row only selects which (word, frame) cells are read
+    (include/asg_hip.h::asg_beam_words_nbest_confidence).  -> BeamWordsNbestConfidence: the twelve fields of `BeamWordsNbest`,
+    bit for bit (path, states and lm_states are None unless `return_alignments`), and
+      word_frames      [B, nbest, T] int64  the frame at which word k of row r ends (len for a word ended by the end of the
+                                            utterance), -1 behind the words and in the padding rows
+      word_confidences [B, nbest, T] dtype  the sum of P(words[r][k], t) over |t - word_frames[r][k]| <= frame_tolerance, 0
+                                            behind the words and in the padding rows
+      normalisers      [B]           dtype  Z_K, bit-equal to `beam_words_full_score` without targets
+    Row 0's frames and confidences are `beam_decode_words_confidence`'s, bit for bit, and rows that hold the same word ending
+    at the same frame carry the same bits.  With frame_tolerance = 0 a confidence lies between exp(scores[r] - normalisers)
+    and 1 up to rounding; with a tolerance it is an expected count, returned unclipped.  Utterances without a path have
+    num_hyps 0, normaliser -inf, frames -1 and confidences 0; there is never a NaN.  frame_tolerance < 0 or > 64, nbest < 1
+    or > 8192, and a min(nbest, beam_size) * (2 * frame_tolerance + 2) whose accumulators do not fit the LDS beside a frame's
+    lattice set are refused by the library (RuntimeError).
+
+    Results are bit-identical run to run and for any `max_work_bytes`; inputs, widening, caching, capture and the utterance
+    groups are those of `beam_decode_words_nbest`.  `lookahead` takes the sets and the rows of
+    `beam_decode_words_nbest(..., lookahead=)`; the lattice keeps the plain weights.
+    """
+    _check_beam(beam_size, beam_threshold)
+    if int(nbest) < 1:
+        raise ValueError("torch_asg_amd: nbest must be >= 1, got %d" % int(nbest))
+    with torch.no_grad():
+        return native().beam_decode_words_nbest_confidence(*_plain(inputs, transition), lexicon, word_lm, input_lengths, beam_size,
+                                                           nbest, beam_threshold, lm_weight, word_score, token_score,
+                                                           frame_tolerance, return_alignments, max_work_bytes, lookahead)
+
+
 BeamNbest = collections.namedtuple("BeamNbest", ["scores", "emission_scores", "graph_scores", "tokens", "token_lengths",
                                                  "num_hyps", "path", "states"])
 
@@ -1839,6 +1935,15 @@ class ASGLoss(nn.Module):
         see `torch_asg_amd.beam_decode_words_confidence`."""
         return beam_decode_words_confidence(inputs, self.transition, lexicon, word_lm, input_lengths, beam_size, beam_threshold,
                                             lm_weight, word_score, token_score, frame_tolerance, max_work_bytes, lookahead)
+
+    def beam_decode_words_nbest_confidence(self, inputs, lexicon, word_lm, input_lengths=None, beam_size=256, nbest=10,
+                                           beam_threshold=float("inf"), lm_weight=1.0, word_score=0.0, token_score=0.0,
+                                           frame_tolerance=0, return_alignments=False, max_work_bytes=1 << 30, lookahead=None):
+        """`beam_decode_words_nbest` under this criterion's transitions with the end frame and the lattice posterior of every
+        word of every row; see `torch_asg_amd.beam_decode_words_nbest_confidence`."""
+        return beam_decode_words_nbest_confidence(inputs, self.transition, lexicon, word_lm, input_lengths, beam_size, nbest,
+                                                  beam_threshold, lm_weight, word_score, token_score, frame_tolerance,
+                                                  return_alignments, max_work_bytes, lookahead)
 
     def beam_decode_words_nbest(self, inputs, lexicon, word_lm, input_lengths=None, beam_size=256, nbest=10,
                                 beam_threshold=float("inf"), lm_weight=1.0, word_score=0.0, token_score=0.0,

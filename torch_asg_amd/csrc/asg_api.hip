@@ -1563,6 +1563,87 @@ int asg_beam_words_confidence_la(asg_ctx *ctx, const asg_problem *p, const asg_t
                                  normalisers, stream);
 }
 
+// The n-best confidences: the checks of asg_beam_words_confidence, then those of asg_beam_decode_words_nbest.
+static int check_beam_words_nbest_conf(const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm, int beam_size,
+                                       int nbest) {
+    int rc = check_beam_words_conf(p, gb, lm, beam_size);
+    if (rc) return rc;
+    if (nbest < 1) return ASG_ERR_INVALID;
+    if (nbest > kBeamMaxNbest) return ASG_ERR_UNSUPPORTED;
+    return ASG_OK;
+}
+
+size_t asg_beam_words_nbest_confidence_work_bytes(const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                                  int beam_size, int nbest) {
+    if (check_beam_words_nbest_conf(p, gb, lm, beam_size, nbest) != ASG_OK) return 0;
+    return beam_word_nbest_conf_work_bytes(p->dtype == ASG_DTYPE_F64 ? 8 : 4, (int) p->T, (int) p->B, beam_size,
+                                           beam_word_cap(beam_size, gb->max_out, (int) gb->num_start), nbest);
+}
+
+// asg_beam_words_nbest_confidence with a look-ahead (`with_la`) or without one.  The order of the checks: the decoder's, the
+// n-best's, the tolerance and the limit of the row sink, the look-ahead's, then threshold, buffers and workspace as everywhere.
+static int beam_words_nbest_confidence(const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                       const asg_word_lookahead *la, bool with_la, int beam_size, double beam_threshold, int nbest,
+                                       int frame_tolerance, void *work, size_t work_bytes, void *scores, void *emission_scores,
+                                       void *graph_scores, void *lm_scores, int64_t *path, int64_t *tokens, int64_t *token_lengths,
+                                       int64_t *states, int64_t *lm_states, int64_t *words, int64_t *word_lengths,
+                                       int64_t *num_hyps, int64_t *word_frames, void *word_confidences, void *normalisers,
+                                       void *stream) {
+    int rc = check_beam_words_nbest_conf(p, gb, lm, beam_size, nbest);
+    if (rc) return rc;
+    if (frame_tolerance < 0) return ASG_ERR_INVALID;
+    if (frame_tolerance > kBeamWordConfMaxTol) return ASG_ERR_UNSUPPORTED;
+    if (!beam_word_nbest_conf_fits(p->dtype == ASG_DTYPE_F64 ? 8 : 4, (int) p->T, beam_size, nbest, frame_tolerance))
+        return ASG_ERR_UNSUPPORTED;
+    if (with_la && (rc = check_word_lookahead(p->dtype, lm, la)) != ASG_OK) return rc;
+    if (!(beam_threshold >= 0.0)) return ASG_ERR_INVALID;                  // negative or NaN
+    if (!work || !scores || !emission_scores || !graph_scores || !lm_scores || !tokens || !token_lengths || !words ||
+        !word_lengths || !num_hyps || !word_frames || !word_confidences || !normalisers)
+        return ASG_ERR_INVALID;
+    if (work_bytes < asg_beam_words_nbest_confidence_work_bytes(p, gb, lm, beam_size, nbest)) return ASG_ERR_WORKSPACE;
+    const Problem P = to_problem(p);
+    const GraphArgs G = to_graph_args(gb->graph);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    const WordLmArgs LM = to_word_lm_args(lm);
+    const WordLookArgs LA = with_la ? to_word_look_args(la) : WordLookArgs{};
+    const WordLookArgs *look = with_la ? &LA : nullptr;
+    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
+    long long *ls = (long long *) lm_states, *wd = (long long *) words, *wl = (long long *) word_lengths;
+    long long *nh = (long long *) num_hyps, *wf = (long long *) word_frames;
+    return hip_status(ASG_DISPATCH(p,
+        launch_beam_word_nbest_conf<float>(P, G, BG, LM, look, beam_size, beam_threshold, nbest, frame_tolerance, work, scores,
+                                           emission_scores, graph_scores, lm_scores, pa, tk, tl, st, ls, wd, wl, nh, wf,
+                                           word_confidences, normalisers, (hipStream_t) stream),
+        launch_beam_word_nbest_conf<double>(P, G, BG, LM, look, beam_size, beam_threshold, nbest, frame_tolerance, work, scores,
+                                            emission_scores, graph_scores, lm_scores, pa, tk, tl, st, ls, wd, wl, nh, wf,
+                                            word_confidences, normalisers, (hipStream_t) stream)));
+}
+
+int asg_beam_words_nbest_confidence(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                    int beam_size, double beam_threshold, int nbest, int frame_tolerance, void *work,
+                                    size_t work_bytes, void *scores, void *emission_scores, void *graph_scores, void *lm_scores,
+                                    int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *lm_states,
+                                    int64_t *words, int64_t *word_lengths, int64_t *num_hyps, int64_t *word_frames,
+                                    void *word_confidences, void *normalisers, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    return beam_words_nbest_confidence(p, gb, lm, nullptr, false, beam_size, beam_threshold, nbest, frame_tolerance, work, work_bytes,
+                                       scores, emission_scores, graph_scores, lm_scores, path, tokens, token_lengths, states,
+                                       lm_states, words, word_lengths, num_hyps, word_frames, word_confidences, normalisers, stream);
+}
+
+int asg_beam_words_nbest_confidence_la(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                       const asg_word_lookahead *la, int beam_size, double beam_threshold, int nbest,
+                                       int frame_tolerance, void *work, size_t work_bytes, void *scores, void *emission_scores,
+                                       void *graph_scores, void *lm_scores, int64_t *path, int64_t *tokens, int64_t *token_lengths,
+                                       int64_t *states, int64_t *lm_states, int64_t *words, int64_t *word_lengths,
+                                       int64_t *num_hyps, int64_t *word_frames, void *word_confidences, void *normalisers,
+                                       int flags, void *stream) {
+    (void) ctx; (void) flags;
+    return beam_words_nbest_confidence(p, gb, lm, la, true, beam_size, beam_threshold, nbest, frame_tolerance, work, work_bytes, scores,
+                                       emission_scores, graph_scores, lm_scores, path, tokens, token_lengths, states, lm_states,
+                                       words, word_lengths, num_hyps, word_frames, word_confidences, normalisers, stream);
+}
+
 static GraphLossArgs to_graph_loss_args(const asg_token_graph_loss *gl) {
     GraphLossArgs L{};
     L.S = (int) gl->S; L.start = gl->start;

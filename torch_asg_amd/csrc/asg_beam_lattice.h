@@ -12,7 +12,8 @@
 //     `for_each_out(key, lg, G, fn)`: fn(target key, w, target label) for the outgoing edges that lane lg of G owns, where
 //     w() gives the edge weight -- a callable, so that the weight of an edge whose target is not kept is never loaded;
 //   - beam_loss_tr_reduce<R> and the body of the backward launcher.
-// asg_beam_word_conf.hip includes it for the small helpers alone: its beta pull is a kernel of its own.
+// asg_beam_word_conf_pull.h includes it for the small helpers alone: the beta pull of the two confidence calls
+// is a text of its own.
 // The two alpha kernels are different algorithms (a pull through incoming rows, a push with integer atomics) and stay in
 // their units, as do the searches and the target walks.
 #pragma once

@@ -10,7 +10,7 @@
 //      edges and, for the word of the final step, len.
 //   2 - 4  launch_beam_word_loss_lattice: the target walk (there is no target: it writes the header's 0), beam_loss_sets<WordSets>
 //      and beam_word_loss_fwd with alpha stored for every frame -> U, alpha, Z_K (the normalisers).  Unchanged kernels.
-//   5  beam_word_conf_bwd: beam_loss_bwd's beta pull (one 1024-thread workgroup per utterance, frames len-1 .. 1, U_{t+1} with its
+//   5  beam_word_conf_bwd: asg_beam_word_conf_pull.h over HypSink -- beam_loss_bwd's beta pull (one 1024-thread workgroup per utterance, frames len-1 .. 1, U_{t+1} with its
 //      beta in LDS, G lanes per source pair, a max pass and a sum pass) without label posteriors, (i, j) tile and transition
 //      gradient.  The sum pass also forms the posterior exp(alpha + c - Z_K) of every SEPARATOR edge -- the event "word w ends at
 //      frame t" -- and, before the first frame, the posteriors of the final step.  An event is added, as a 64-bit fixed-point
@@ -27,12 +27,12 @@
 #include "asg_beam_word_frame.h"  // the frame of the search and its end
 #include "asg_beam_lattice.h"     // the helpers of the lattice pass: subgroup, find_sorted, the butterflies, to_fixed
 #include "asg_beam_word_lat.h"    // WordLat: how a pair's edges are walked
+#include "asg_beam_word_conf_pull.h"  // the beta pull, shared with asg_beam_word_nbest_conf.hip
 
 namespace asg {
 
 namespace {
 
-constexpr double kConfScale = 18014398509481984.0;            // 2^54: a word sums at most 129 completions of at most 1 (+ rounding)
 constexpr int kConfRing = 256;                                // >= 2 * kBeamWordConfMaxTol + 2, a power of two
 static_assert(kConfRing >= 2 * kBeamWordConfMaxTol + 2 && (kConfRing & (kConfRing - 1)) == 0, "ring");
 
@@ -45,12 +45,15 @@ __device__ __forceinline__ void conf_no_path(int T, long long *pb, long long *tk
     for (int t = threadIdx.x; t < T; t += kBT) wf[t] = -1;
 }
 
-template <typename R, bool TRL, bool LA>
+// FIN: the instantiation behind the n-best confidences (asg_beam_word_nbest_conf.hip), which also leaves the last set in memory
+// at fin_off, as beam_word_kernel<R, TRL, FIN> does; without it the text is what it was before the flag existed.
+template <typename R, bool TRL, bool LA, bool FIN>
 __global__ void __launch_bounds__(kBT) beam_word_conf_search(Problem P, GraphArgs g, BeamGraphArgs bg, WordLmArgs lm, int K, R theta,
                                                              int cap, int tbits, char *work, size_t per_utt, size_t cnt_off,
                                                              WordLookParam<LA> la, R *scores, long long *path, long long *tokens,
                                                              long long *tlen, long long *states, long long *lm_states,
-                                                             long long *words, long long *wlen, long long *wframes) {
+                                                             long long *words, long long *wlen, long long *wframes,
+                                                             size_t fin_off) {
     using U = typename Key<R>::U;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     Ctl<U> &ctl = *(Ctl<U> *) lds;
@@ -101,6 +104,13 @@ __global__ void __launch_bounds__(kBT) beam_word_conf_search(Problem P, GraphArg
 
     // ---- the decoder's end: the best end over the last kept set, the smallest pair on a tie; the backtrace, the words, the tokens
     const int na = ctl.na < K ? ctl.na : K;
+    if constexpr (FIN) {                                    // the n-best stage reads the last set from memory
+        char *fin = wb + fin_off;
+        R *fv = (R *) (fin + 8);
+        int *fq = (int *) (fv + K), *fh = fq + K;
+        for (int k = tid; k < na; k += kBT) { fv[k] = cur_v[k]; fq[k] = cur_q[k]; fh[k] = cur_h[k]; }
+        if (tid == 0) *(int *) fin = na;
+    }
     U bkey;
     int bk;
     word_best_end<R, LA>(f, fw, true, cur_h, cur_q, cur_v, na, bkey, bk);
@@ -128,6 +138,42 @@ __global__ void __launch_bounds__(kBT) beam_word_conf_search(Problem P, GraphArg
 // 5: beta with the word-event sink.  Dynamic LDS: [nq u64 M][nb R M][pad to 16][ring u64 256].  beta[t-1] crosses from the lanes
 // that sum it to the workgroup through the utterance's two rows in the workspace, as in beam_loss_bwd.
 // ---------------------------------------------------------------------------------------------------------------------
+// 5x's sink: the words of ONE hypothesis in frame order.  The words whose window holds the frame the workgroup stands at are
+// [ka, kb), the same in every thread; a word's accumulator is slot k mod 256 of the ring.
+template <typename R>
+struct HypSink {
+    static constexpr bool kBarrier = false;
+    const long long *wd, *wf;
+    R *cf;
+    unsigned long long *ring;
+    int tol, ka, kb;
+    // moves the range to frame t (frames descend) and finishes the words that leave it: no later event can reach them
+    __device__ __forceinline__ void window(int t) {
+        const int tid = threadIdx.x;
+        int nkb = kb;
+        while (nkb > 0 && wf[nkb - 1] > (long long) t + tol) --nkb;
+        for (int k = nkb + tid; k < kb; k += kBL) {
+            unsigned long long &slot = ring[k & (kConfRing - 1)];
+            cf[k] = (R) ((double) slot * (1.0 / kConfScale));
+            slot = 0ull;
+        }
+        kb = nkb;
+        if (ka > kb) ka = kb;
+        while (ka > 0 && wf[ka - 1] >= (long long) t - tol) --ka;
+    }
+    __device__ __forceinline__ bool open() const { return ka < kb; }
+    // word w completed with posterior exp(x) at the frame the window stands at
+    __device__ __forceinline__ void add(int w, R x) {
+        unsigned long long fx = 0ull;
+        bool have = false;
+        for (int k = ka; k < kb; ++k) {
+            if (wd[k] != (long long) w) continue;
+            if (!have) { fx = to_fixed((double) bexp(x), kConfScale); have = true; }
+            if (fx) atomicAdd(&ring[k & (kConfRing - 1)], fx);
+        }
+    }
+};
+
 inline size_t conf_lds(int elem, int M) { return bwd_front(elem, 8, M) + (size_t) kConfRing * 8; }
 
 template <typename R>
@@ -145,7 +191,8 @@ __global__ void __launch_bounds__(kBL) beam_word_conf_bwd(Problem P, typename Wo
     const int len = clamp_len(P.in_len, b, T);
     const R Z = Zs[b];
     R *cf = conf + (int64_t) b * T;
-    const long long *wd = words + (int64_t) b * T, *wf = wframes + (int64_t) b * T;
+    HypSink<R> sink;
+    sink.wd = words + (int64_t) b * T; sink.wf = wframes + (int64_t) b * T; sink.cf = cf; sink.ring = ring; sink.tol = tol;
     int nw = 0;
     if (len >= 1 && Z > NINF) {
         const long long n = wlen[b];
@@ -154,106 +201,8 @@ __global__ void __launch_bounds__(kBL) beam_word_conf_bwd(Problem P, typename Wo
     for (int k = nw + tid; k < T; k += kBL) cf[k] = R(0);
     if (nw == 0) return;
     for (int x = tid; x < kConfRing; x += kBL) ring[x] = 0ull;
-    char *wb = work + (size_t) b * args.lay.per;
-    const KeyT *U = (const KeyT *) (wb + args.lay.U);
-    const int *nu = (const int *) (wb + args.lay.nu);
-    const R *A = (const R *) (wb + args.lay.A);
-    R *Bv = (R *) (wb + beta_off);                                             // [2][M]
-    const R *in = (const R *) P.inputs + (int64_t) b * P.is1;
-    const R *trm = (const R *) P.transition;
-    WordLat<R> lat;
-    lat.bind(args);
-    const int sep = lat.f.sep;
-    auto tr = [&](int i, int j) -> R { return trm[(int64_t) i * P.ts0 + (int64_t) j * P.ts1]; };
-
-    // The words whose window holds the frame the workgroup stands at: [ka, kb), the same in every thread.  `window` moves it to
-    // frame t (frames descend) and finishes the words that leave it: no later event can reach them.
-    int ka = nw, kb = nw;
-    auto window = [&](int t) {
-        int nkb = kb;
-        while (nkb > 0 && wf[nkb - 1] > (long long) t + tol) --nkb;
-        for (int k = nkb + tid; k < kb; k += kBL) {
-            unsigned long long &slot = ring[k & (kConfRing - 1)];
-            cf[k] = (R) ((double) slot * (1.0 / kConfScale));
-            slot = 0ull;
-        }
-        kb = nkb;
-        if (ka > kb) ka = kb;
-        while (ka > 0 && wf[ka - 1] >= (long long) t - tol) --ka;
-    };
-    // the sink: word w completed with posterior exp(x) at the frame the window stands at
-    auto sink = [&](int w, R x) {
-        unsigned long long fx = 0ull;
-        bool have = false;
-        for (int k = ka; k < kb; ++k) {
-            if (wd[k] != (long long) w) continue;
-            if (!have) { fx = to_fixed((double) bexp(x), kConfScale); have = true; }
-            if (fx) atomicAdd(&ring[k & (kConfRing - 1)], fx);
-        }
-    };
-    __syncthreads();                                                           // the ring is zero
-
-    // frame len: the final step out of the word-end nodes of the last set
-    window(len);
-    int mt = nu[len - 1];
-    for (int x = tid; x < mt; x += kBL) {
-        const KeyT p = U[(int64_t) (len - 1) * M + x];
-        R e;
-        lat.end(p, e);
-        nq[x] = p;
-        nb[x] = e;
-        const int s = lat.f.state[(int) (p & lat.qmask)];
-        if (ka < kb && s != 0 && e > NINF) sink(lat.f.wos[s], (A[(int64_t) (len - 1) * M + x] + e) - Z);
-    }
-    for (int t = len - 1; t >= 1; --t) {
-        __syncthreads();                                                       // nq, nb and the adds of frame t + 1
-        window(t);
-        const bool open = ka < kb;
-        const int mp = nu[t - 1];
-        const KeyT *Up = U + (int64_t) (t - 1) * M;
-        const R *Ap = A + (int64_t) (t - 1) * M;
-        R *Brow = Bv + (int64_t) ((t - 1) & 1) * M;
-        const R *xt = in + (int64_t) t * P.is0;
-        const int G = subgroup(mp), per = kBL / G;
-        for (int k0 = 0; k0 < mp; k0 += per) {
-            const int k = k0 + tid / G, lg = tid % G;
-            const bool act = k < mp;
-            const KeyT pp = act ? Up[k] : (KeyT) 0;
-            const int ip = act ? lat.label(pp) : 0;
-            // every surviving candidate out of pp that this lane owns: f(value, is it a separator edge)
-            auto visit = [&](auto f) {
-                if (!act) return;
-                if (lg == 0) {
-                    const int pos = find_sorted(nq, mt, pp);
-                    if (pos >= 0) f((nb[pos] + tr(ip, ip)) + xt[(int64_t) ip * P.is2], false);
-                }
-                lat.for_each_out(pp, lg, G, [&](KeyT tp, auto w, int i) {
-                    const int pos = find_sorted(nq, mt, tp);
-                    if (pos >= 0) f(((nb[pos] + tr(i, ip)) + w()) + xt[(int64_t) i * P.is2], i == sep);
-                });
-            };
-            R mx = NINF;
-            visit([&](R c, bool) { mx = bmax(mx, c); });
-            mx = group_max(mx, G);
-            R s = R(0);
-            if (mx > NINF) {
-                const R a = Ap[k];
-                const int w = open ? lat.f.wos[lat.f.state[(int) (pp & lat.qmask)]] : -1;
-                visit([&](R c, bool word) {
-                    s += bexp(c - mx);
-                    if (word && open) sink(w, (a + c) - Z);
-                });
-            }
-            s = group_sum(s, G);
-            if (act && lg == 0) dev_store(Brow + k, mx > NINF ? mx + blog(s) : NINF);
-        }
-        __threadfence();
-        __syncthreads();
-        for (int x = tid; x < mp; x += kBL) { nq[x] = Up[x]; nb[x] = dev_load(Brow + x); }
-        mt = mp;
-    }
-    __syncthreads();
-    window(-tol - 1);                                                          // t + tol < 1: every window is closed
+    sink.ka = sink.kb = nw;
+    beam_word_conf_pull<R>(P, args, work + (size_t) b * args.lay.per, beta_off, Z, len, -tol - 1, nq, nb, sink);
 }
 
 }  // namespace
@@ -271,6 +220,40 @@ size_t beam_word_conf_work_bytes(int elem, int T, int B, int K, int cap) {
     return (size_t) B * beam_word_conf_layout(elem, T, K, cap).per;
 }
 
+// Launch 1 alone.  `per` and `cnt_off` say where an utterance's block starts and where its kept counts go; with fin_off != 0 the
+// search also leaves |A_{len-1}| and its last set there (the FIN instantiations: the n-best confidences).
+template <typename R>
+hipError_t launch_beam_word_conf_search(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                                        const WordLookArgs *LA, int K, double theta, void *work, size_t per, size_t cnt_off,
+                                        size_t fin_off, void *scores, long long *path, long long *tokens, long long *tlen,
+                                        long long *states, long long *lm_states, long long *words, long long *wlen,
+                                        long long *word_frames, hipStream_t stream) {
+    const int B = P.B, N = P.N;
+    const int cap = beam_word_cap(K, BG.max_out, BG.num_start);
+    const int tbits = word_table_bits(cap);
+    char *w = (char *) work;
+    const size_t beam = kFixedLds + (size_t) K * (sizeof(R) + 8);
+    const bool trl = beam + (size_t) N * N * sizeof(R) <= kLdsMax;
+    const size_t dyn = beam + (trl ? (size_t) N * N * sizeof(R) : 0);
+#define ASG_BEAM_WORD_CONF_SEARCH(TRL, LAF, FIN, LOOK)                                                                        \
+    do {                                                                                                                     \
+        set_lds((const void *) beam_word_conf_search<R, TRL, LAF, FIN>, dyn);                                               \
+        hipLaunchKernelGGL((beam_word_conf_search<R, TRL, LAF, FIN>), dim3(B), dim3(kBT), dyn, stream, P, G, BG, LM, K,    \
+                           (R) theta, cap, tbits, w, per, cnt_off, LOOK, (R *) scores, path, tokens, tlen, states,           \
+                           lm_states, words, wlen, word_frames, fin_off);                                                    \
+    } while (0)
+#define ASG_BEAM_WORD_CONF_SEARCH_F(TRL, LAF, LOOK)                                                                           \
+    do {                                                                                                                     \
+        if (fin_off) ASG_BEAM_WORD_CONF_SEARCH(TRL, LAF, true, LOOK); else ASG_BEAM_WORD_CONF_SEARCH(TRL, LAF, false, LOOK); \
+    } while (0)
+    if (LA) { if (trl) ASG_BEAM_WORD_CONF_SEARCH_F(true, true, *LA); else ASG_BEAM_WORD_CONF_SEARCH_F(false, true, *LA); }
+    else if (trl) ASG_BEAM_WORD_CONF_SEARCH_F(true, false, WordNoLook{});
+    else ASG_BEAM_WORD_CONF_SEARCH_F(false, false, WordNoLook{});
+#undef ASG_BEAM_WORD_CONF_SEARCH_F
+#undef ASG_BEAM_WORD_CONF_SEARCH
+    return hipGetLastError();
+}
+
 template <typename R>
 hipError_t launch_beam_word_conf(const Problem &P0, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
                                  const WordLookArgs *LA, int K, double theta, int tol, void *work, void *scores, long long *path,
@@ -279,28 +262,12 @@ hipError_t launch_beam_word_conf(const Problem &P0, const GraphArgs &G, const Be
     Problem P = P0;
     P.targets = nullptr;                                                         // the lattice of the search alone: U_t = A_t
     P.tg_len = nullptr;
-    const int T = P.T, B = P.B, N = P.N;
+    const int T = P.T, B = P.B;
     const int cap = beam_word_cap(K, BG.max_out, BG.num_start);
-    const int tbits = word_table_bits(cap);
     const BeamWordConfLayout lay = beam_word_conf_layout(sizeof(R), T, K, cap);
     char *w = (char *) work;
-    {
-        const size_t beam = kFixedLds + (size_t) K * (sizeof(R) + 8);
-        const bool trl = beam + (size_t) N * N * sizeof(R) <= kLdsMax;
-        const size_t dyn = beam + (trl ? (size_t) N * N * sizeof(R) : 0);
-#define ASG_BEAM_WORD_CONF_SEARCH(TRL, LAF, LOOK)                                                                             \
-    do {                                                                                                                     \
-        set_lds((const void *) beam_word_conf_search<R, TRL, LAF>, dyn);                                                    \
-        hipLaunchKernelGGL((beam_word_conf_search<R, TRL, LAF>), dim3(B), dim3(kBT), dyn, stream, P, G, BG, LM, K,         \
-                           (R) theta, cap, tbits, w, lay.per, lay.lat.cnt, LOOK, (R *) scores, path, tokens, tlen, states,   \
-                           lm_states, words, wlen, word_frames);                                                             \
-    } while (0)
-        if (LA) { if (trl) ASG_BEAM_WORD_CONF_SEARCH(true, true, *LA); else ASG_BEAM_WORD_CONF_SEARCH(false, true, *LA); }
-        else if (trl) ASG_BEAM_WORD_CONF_SEARCH(true, false, WordNoLook{});
-        else ASG_BEAM_WORD_CONF_SEARCH(false, false, WordNoLook{});
-#undef ASG_BEAM_WORD_CONF_SEARCH
-    }
-    hipError_t e = hipGetLastError();
+    hipError_t e = launch_beam_word_conf_search<R>(P, G, BG, LM, LA, K, theta, work, lay.per, lay.lat.cnt, 0, scores, path, tokens,
+                                                   tlen, states, lm_states, words, wlen, word_frames, stream);
     if (e != hipSuccess) return e;
     e = launch_beam_word_loss_lattice<R>(P, G, BG, LM, lay.lat, K, true, work, normalisers, stream);
     if (e != hipSuccess) return e;
@@ -316,7 +283,12 @@ hipError_t launch_beam_word_conf(const Problem &P0, const GraphArgs &G, const Be
     template hipError_t launch_beam_word_conf<R>(const Problem &, const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &, \
                                                  const WordLookArgs *, int, double, int, void *, void *, long long *,           \
                                                  long long *, long long *, long long *, long long *, long long *, long long *,  \
-                                                 long long *, void *, void *, hipStream_t);
+                                                 long long *, void *, void *, hipStream_t);                     \
+    template hipError_t launch_beam_word_conf_search<R>(const Problem &, const GraphArgs &, const BeamGraphArgs &,             \
+                                                        const WordLmArgs &, const WordLookArgs *, int, double, void *, size_t,  \
+                                                        size_t, size_t, void *, long long *, long long *, long long *,          \
+                                                        long long *, long long *, long long *, long long *, long long *,        \
+                                                        hipStream_t);
 ASG_WORD_CONF_INST(float)
 ASG_WORD_CONF_INST(double)
 #undef ASG_WORD_CONF_INST

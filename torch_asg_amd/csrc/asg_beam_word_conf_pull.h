@@ -1,0 +1,110 @@
+// torch_asg_amd/csrc/asg_beam_word_conf_pull.h -- the beta pull with a WORD-EVENT SINK, the text asg_beam_word_conf.hip
+// (confidences of the one best) and asg_beam_word_nbest_conf.hip (of every row of the n-best list, 5y) both compile:
+// beam_loss_bwd's pull (one 1024-thread workgroup per utterance, frames len-1 .. 1, U_{t+1} with its beta in LDS, G lanes per
+// source pair, a max pass and a sum pass) without label posteriors, (i, j) tile and transition gradient.  The sum pass forms the
+// posterior exp((alpha + c) - Z_K) of every SEPARATOR edge -- the event "word w ends at frame t" -- and, before the first frame,
+// the posteriors of the final step, and hands each to the sink.  The adds and their order do not depend on the sink: beta and
+// every event's value are the same bits under both.  A Sink has
+//   kBarrier          whether `window` writes LDS that `add` reads (then a barrier follows it)
+//   window(t)         every thread, frames descending from len, at last with a t whose windows are all closed: moves the open
+//                     range to frame t and finishes what leaves it
+//   open()            whether anything is open at the frame the sink stands at (the same in every thread)
+//   add(w, x)         word w completed with posterior exp(x) at that frame
+// nq [M] / nb [M]: the dynamic LDS in front of the sink's own (bwd_front).  beta[t-1] crosses from the lanes that sum it to the
+// workgroup through the utterance's two rows in the workspace at beta_off, as in beam_loss_bwd.
+#pragma once
+#include "asg_beam_lattice.h"
+#include "asg_beam_word_lat.h"
+
+namespace asg {
+
+namespace {
+
+constexpr double kConfScale = 18014398509481984.0;            // 2^54: a word sums at most 129 completions of at most 1 (+ rounding)
+
+template <typename R, typename Sink>
+__device__ __forceinline__ void beam_word_conf_pull(const Problem &P, const typename WordLat<R>::Args &args, char *wb, size_t beta_off,
+                                                    R Z, int len, int last, unsigned long long *nq, R *nb, Sink &sink) {
+    using KeyT = unsigned long long;
+    const int M = args.lay.M, tid = threadIdx.x, b = blockIdx.x;
+    const R NINF = Num<R>::ninf();
+    const KeyT *U = (const KeyT *) (wb + args.lay.U);
+    const int *nu = (const int *) (wb + args.lay.nu);
+    const R *A = (const R *) (wb + args.lay.A);
+    R *Bv = (R *) (wb + beta_off);                                             // [2][M]
+    const R *in = (const R *) P.inputs + (int64_t) b * P.is1;
+    const R *trm = (const R *) P.transition;
+    WordLat<R> lat;
+    lat.bind(args);
+    const int sep = lat.f.sep;
+    auto tr = [&](int i, int j) -> R { return trm[(int64_t) i * P.ts0 + (int64_t) j * P.ts1]; };
+    __syncthreads();                                                           // the sink's LDS is ready
+
+    // frame len: the final step out of the word-end nodes of the last set
+    sink.window(len);
+    if constexpr (Sink::kBarrier) __syncthreads();
+    int mt = nu[len - 1];
+    for (int x = tid; x < mt; x += kBL) {
+        const KeyT p = U[(int64_t) (len - 1) * M + x];
+        R e;
+        lat.end(p, e);
+        nq[x] = p;
+        nb[x] = e;
+        const int s = lat.f.state[(int) (p & lat.qmask)];
+        if (sink.open() && s != 0 && e > NINF) sink.add(lat.f.wos[s], (A[(int64_t) (len - 1) * M + x] + e) - Z);
+    }
+    for (int t = len - 1; t >= 1; --t) {
+        __syncthreads();                                                       // nq, nb and the adds of frame t + 1
+        sink.window(t);
+        if constexpr (Sink::kBarrier) __syncthreads();
+        const bool open = sink.open();
+        const int mp = nu[t - 1];
+        const KeyT *Up = U + (int64_t) (t - 1) * M;
+        const R *Ap = A + (int64_t) (t - 1) * M;
+        R *Brow = Bv + (int64_t) ((t - 1) & 1) * M;
+        const R *xt = in + (int64_t) t * P.is0;
+        const int G = subgroup(mp), per = kBL / G;
+        for (int k0 = 0; k0 < mp; k0 += per) {
+            const int k = k0 + tid / G, lg = tid % G;
+            const bool act = k < mp;
+            const KeyT pp = act ? Up[k] : (KeyT) 0;
+            const int ip = act ? lat.label(pp) : 0;
+            // every surviving candidate out of pp that this lane owns: f(value, is it a separator edge)
+            auto visit = [&](auto f) {
+                if (!act) return;
+                if (lg == 0) {
+                    const int pos = find_sorted(nq, mt, pp);
+                    if (pos >= 0) f((nb[pos] + tr(ip, ip)) + xt[(int64_t) ip * P.is2], false);
+                }
+                lat.for_each_out(pp, lg, G, [&](KeyT tp, auto w, int i) {
+                    const int pos = find_sorted(nq, mt, tp);
+                    if (pos >= 0) f(((nb[pos] + tr(i, ip)) + w()) + xt[(int64_t) i * P.is2], i == sep);
+                });
+            };
+            R mx = NINF;
+            visit([&](R c, bool) { mx = bmax(mx, c); });
+            mx = group_max(mx, G);
+            R s = R(0);
+            if (mx > NINF) {
+                const R a = Ap[k];
+                const int w = open ? lat.f.wos[lat.f.state[(int) (pp & lat.qmask)]] : -1;
+                visit([&](R c, bool word) {
+                    s += bexp(c - mx);
+                    if (word && open) sink.add(w, (a + c) - Z);
+                });
+            }
+            s = group_sum(s, G);
+            if (act && lg == 0) dev_store(Brow + k, mx > NINF ? mx + blog(s) : NINF);
+        }
+        __threadfence();
+        __syncthreads();
+        for (int x = tid; x < mp; x += kBL) { nq[x] = Up[x]; nb[x] = dev_load(Brow + x); }
+        mt = mp;
+    }
+    __syncthreads();
+    sink.window(last);                                                         // every window is closed
+}
+
+}  // namespace
+
+}  // namespace asg

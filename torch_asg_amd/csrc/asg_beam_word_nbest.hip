@@ -45,17 +45,6 @@ constexpr int kNT = 1024;          // workgroup
 // tokens / states / lm_states / words [5][B][T])
 inline size_t tail_bytes(int T, int B) { return 3 * a256((size_t) B * 8) + a256((size_t) 5 * B * T * 8); }
 
-// Where the search left its results.  Slot b's block starts at base + b * per: the [Tw][K] rows bq / bh / bs at its front; the
-// set (values [K], product states [K], LM states [K]) at set_off; int32 |A| at na_off; the length from the problem's lengths
-// (pos_off == 0) or the int32 at pos_off; with ovf_off, the stream's overflow word.
-struct BeamWordNbestSrc {
-    const char *base;
-    size_t per, set_off, na_off, pos_off, ovf_off;
-    char *cols;                    // slot b's [Tw][nb] column block at cols + b * cols_per
-    size_t cols_per;
-    int Tw, nb;
-};
-
 template <typename U>
 __device__ __forceinline__ bool entry_less(U ka, unsigned long long pa, U kb, unsigned long long pb) {
     return ka < kb || (ka == kb && pa < pb);
@@ -297,6 +286,30 @@ hipError_t launch_nbest_kernel(const Problem &P, const GraphArgs &G, const BeamG
 }
 
 }  // namespace
+
+// The n-best kernel alone over what a search of this family left (src), one-shot (final = 1, the lengths of the problem): behind
+// the decoder's search here, behind beam_word_conf_search in asg_beam_word_nbest_conf.hip.  LA: that search's look-ahead, or NULL.
+template <typename R>
+hipError_t launch_beam_word_nbest_over(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                                       const WordLookArgs *LA, const BeamWordNbestSrc &src, int K, int nbest, void *scores,
+                                       void *emission_scores, void *graph_scores, void *lm_scores, long long *path,
+                                       long long *tokens, long long *tlen, long long *states, long long *lm_states,
+                                       long long *words, long long *wlen, long long *num_hyps, hipStream_t stream) {
+    if (LA)
+        return launch_nbest_kernel<R, true>(P, G, BG, LM, *LA, src, P.B, K, nbest, 1, scores, emission_scores, graph_scores, lm_scores,
+                                            path, tokens, tlen, states, lm_states, words, wlen, num_hyps, nullptr, nullptr, stream);
+    return launch_nbest_kernel<R, false>(P, G, BG, LM, WordNoLook{}, src, P.B, K, nbest, 1, scores, emission_scores, graph_scores,
+                                         lm_scores, path, tokens, tlen, states, lm_states, words, wlen, num_hyps, nullptr, nullptr,
+                                         stream);
+}
+template hipError_t launch_beam_word_nbest_over<float>(const Problem &, const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &,
+                                                       const WordLookArgs *, const BeamWordNbestSrc &, int, int, void *, void *,
+                                                       void *, void *, long long *, long long *, long long *, long long *,
+                                                       long long *, long long *, long long *, long long *, hipStream_t);
+template hipError_t launch_beam_word_nbest_over<double>(const Problem &, const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &,
+                                                        const WordLookArgs *, const BeamWordNbestSrc &, int, int, void *, void *,
+                                                        void *, void *, long long *, long long *, long long *, long long *,
+                                                        long long *, long long *, long long *, long long *, hipStream_t);
 
 BeamWordNbestLayout beam_word_nbest_layout(int elem, int T, int K, int cap, int nbest) {
     BeamWordNbestLayout l{};

@@ -283,6 +283,23 @@ struct BeamWordNbestLayout {
 BeamWordNbestLayout beam_word_nbest_layout(int elem, int T, int K, int cap, int nbest);
 size_t beam_word_nbest_work_bytes(int elem, int T, int B, int K, int cap, int nbest);
 size_t beam_word_stream_nbest_work_bytes(int max_frames, int B, int K, int nbest);
+// Where a search left its results for the n-best kernel.  Slot b's block starts at base + b * per: the [Tw][K] rows bq / bh / bs
+// at its front; the set (values [K], product states [K], LM states [K]) at set_off; int32 |A| at na_off; the length from the
+// problem's lengths (pos_off == 0) or the int32 at pos_off; with ovf_off, the stream's overflow word.
+struct BeamWordNbestSrc {
+    const char *base;
+    size_t per, set_off, na_off, pos_off, ovf_off;
+    char *cols;                    // slot b's [Tw][nb] column block at cols + b * cols_per
+    size_t cols_per;
+    int Tw, nb;
+};
+// the n-best kernel alone, one-shot, over what a search left at `src` (LA: that search's look-ahead, or NULL)
+template <typename R>
+hipError_t launch_beam_word_nbest_over(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                                       const WordLookArgs *LA, const BeamWordNbestSrc &src, int K, int nbest, void *scores,
+                                       void *emission_scores, void *graph_scores, void *lm_scores, long long *path,
+                                       long long *tokens, long long *tlen, long long *states, long long *lm_states,
+                                       long long *words, long long *wlen, long long *num_hyps, hipStream_t stream);
 // path / states / lm_states may be null (then they are not written)
 template <typename R>
 hipError_t launch_beam_words_nbest(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int K,
@@ -445,6 +462,49 @@ hipError_t launch_beam_word_conf(const Problem &P, const GraphArgs &G, const Bea
                                  const WordLookArgs *LA, int K, double theta, int tol, void *work, void *scores, long long *path,
                                  long long *tokens, long long *tlen, long long *states, long long *lm_states, long long *words,
                                  long long *wlen, long long *word_frames, void *word_conf, void *normalisers, hipStream_t stream);
+
+// launch 1 of that call alone: the search with the decoder's end.  With fin_off != 0 it also leaves int32 |A_{len-1}| and, from
+// byte 8, the last set (values [K], product states [K], LM states [K]) at that offset of every utterance's block.
+template <typename R>
+hipError_t launch_beam_word_conf_search(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                                        const WordLookArgs *LA, int K, double theta, void *work, size_t per, size_t cnt_off,
+                                        size_t fin_off, void *scores, long long *path, long long *tokens, long long *tlen,
+                                        long long *states, long long *lm_states, long long *words, long long *wlen,
+                                        long long *word_frames, hipStream_t stream);
+
+// ---- Word confidences and end frames for every row of the n-best list (asg_beam_word_nbest_conf.hip):
+// asg_beam_words_nbest_confidence.  One utterance's workspace: asg_beam_words_confidence's layout at the front (the search's
+// [T][K] rows first), then (byte offsets, each part 256-byte aligned) fin and rows as in BeamWordNbestLayout, hdr (int32 number
+// of cells), foff (int32 [T + 2]: the first cell of every frame), qk (u64 [P2(nb * T)]: the rows' (frame, word) queries, sorted
+// there when they pass the LDS), cells (u64 [nb * T]: the distinct queries, ascending) and acc (u64 [nb * T]: a cell's fixed-point
+// sum).  Behind the utterances: what the one-best search returns (scores, two lengths, six [B][T] arrays).
+struct BeamWordNbestConfLayout {
+    BeamWordConfLayout conf;     // conf.lat.per and conf.per are this layout's `per`
+    size_t fin, rows, hdr, foff, qk, cells, acc, per;
+    size_t qcap;                 // P2(nb * T)
+    int nb;
+};
+constexpr int kBeamWordNbestConfSortLds = 2048;   // queries the prep kernel sorts in LDS; more are sorted in the workspace
+// the ring of the row sink: the power of two >= min(nbest, K) * (2 tol + 2)
+inline size_t beam_word_nbest_conf_ring(int K, int nbest, int tol) {
+    const size_t need = (size_t) (nbest < K ? nbest : K) * (2 * (size_t) tol + 2);
+    size_t r = 1;
+    while (r < need) r *= 2;
+    return r;
+}
+// THE new limit: bwd_front + ring (u64) + mirror (int32) + window offsets and filter (1024 bytes) within 160 KiB of LDS, and
+// nb * T <= 2^30.
+bool beam_word_nbest_conf_fits(int elem, int T, int K, int nbest, int tol);
+BeamWordNbestConfLayout beam_word_nbest_conf_layout(int elem, int T, int K, int cap, int nbest);
+size_t beam_word_nbest_conf_work_bytes(int elem, int T, int B, int K, int cap, int nbest);
+// path / states / lm_states may be null (then they are not written)
+template <typename R>
+hipError_t launch_beam_word_nbest_conf(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                                       const WordLookArgs *LA, int K, double theta, int nbest, int tol, void *work, void *scores,
+                                       void *emission_scores, void *graph_scores, void *lm_scores, long long *path,
+                                       long long *tokens, long long *tlen, long long *states, long long *lm_states,
+                                       long long *words, long long *wlen, long long *num_hyps, long long *word_frames,
+                                       void *word_conf, void *normalisers, hipStream_t stream);
 
 // ---- Full score, gradients and target walk over the same composed lattice (asg_graph_loss.hip).  The loss-only arrays of
 // asg_token_graph_loss.  Work = alpha [T][Q][B] (stored) or [2][Q][B]; scratch = align256([2][Q][B] beta) + [Q+E][B]
