@@ -1514,7 +1514,8 @@ __global__ void __launch_bounds__(256) fused_bwd_kernel(Problem P, State W, Fuse
                 const int total = T * N;
                 for (int k = threadIdx.x; k < total; k += 256) {
                     const int t = k / N, i = k - t * N;
-                    const R v = gi[(int64_t) t * B * N + i] * g;
+                    // (rows behind the utterance's length are +0 whatever the sign of g: 0 * g would leave -0 there)
+                    const R v = t < len_ld ? gi[(int64_t) t * B * N + i] * g : R(0);
                     if (P.in_bf16) gh[(int64_t) t * B * N + i] = float_to_bf16_bits(v);
                     else gi[(int64_t) t * B * N + i] = v;
                 }
