@@ -1168,6 +1168,52 @@ int asg_beam_graph_full_backward(asg_ctx *ctx, const asg_problem *p, const asg_t
                                  void *grad_inputs, void *grad_transition, void *scratch, size_t scratch_bytes, int flags,
                                  void *stream);
 
+/* ---- TOKEN CONFIDENCES and START FRAMES of asg_beam_decode_graph's hypothesis, from the lattice its search kept: for every token
+ * of the winning path, the frame it starts at and how much of the probability mass inside the kept sets agrees that a token with
+ * this label starts there -- what pseudo-label filters, highlighting of doubtful characters and token time stamps need.  With a
+ * lexicon trie (TokenGraph.from_lexicon) the confidence of a separator token is the confidence of a word boundary.  No counterpart
+ * in the reference.  Per utterance b, len = clamp(input_lengths[b], 0, T); graph, folded weights, the kept sets A_t
+ * (K = min(beam_size, max(Q, 1))), the edges and the end exactly as in asg_beam_decode_graph / asg_beam_graph_full_forward WITHOUT
+ * targets (p->targets is not looked at): U_t = A_t.
+ *   1. Lattice paths.  A path is p_0 .. p_{len-1} with p_t in A_t, consecutive states equal (the stay) or joined by one outgoing
+ *      edge of the product graph, and a finite end.  Its weight is what step 3 of asg_beam_graph_full_forward sums.  Z_K = lse over
+ *      all of them = that call's score without targets, bit for bit (the same kernels run).  The winning path is one of them.
+ *   2. Token events.  A path STARTS A TOKEN WITH LABEL i AT FRAME t when t == 0 and p_0 has label i, or 1 <= t <= len-1,
+ *      p_t != p_{t-1} and p_t has label i (an edge of the product graph always changes the label: "not the stay").
+ *      P(i, t) = sum over the paths with that event of exp(weight - Z_K): automaton states and source states are summed over.
+ *   3. Hypothesis.  Token k of the winning path, k < token_lengths[b], has label c_k = tokens[b][k] and starts at s_k, the first
+ *      frame of its run in path[b] (s_0 = 0).  s_k ascends strictly.
+ *   4. Outputs.  scores, path, tokens, token_lengths, states: asg_beam_decode_graph's own, bit for bit (the same device code
+ *      searches, ends and backtraces).  Beyond them:
+ *        token_frames      [B][T] int64: s_k, then -1 behind the tokens;
+ *        token_confidences [B][T] dtype: conf_k = sum over t in [s_k - tol, s_k + tol] meet [0, len-1] of P(c_k, t), then 0;
+ *        normalisers       [B]    dtype: Z_K.
+ *      tol = frame_tolerance.  At tol = 0, conf_k is a probability: exp(scores[b] - Z_K) <= conf_k <= 1 up to rounding (the
+ *      winning path has the event).  At tol > 0 it is the EXPECTED NUMBER of starts of label c_k inside the window: it can pass 1
+ *      ("a b a" inside one window starts a twice) and is returned unclipped.
+ *   5. Degenerate utterances.  len == 0, an empty last set or no finite end: score -inf, normaliser -inf, integer outputs -1,
+ *      lengths 0, confidences 0.  Never a NaN.
+ * An edge posterior is exp((alpha[t-1][p] + c) - Z_K), c = beta[t][p'] + the edge's terms, with alpha of
+ * asg_beam_graph_full_forward and beta its mirror image (max-then-sum per state, the sums of asg_beam_graph_full_backward); the
+ * posterior of a start at frame 0 is exp((alpha[0][q] + beta[0][q]) - Z_K).  Each is added to the tokens it counts for as a 64-bit
+ * fixed-point integer with 54 fractional bits: integer adds only, NO FLOAT ATOMICS, bit-identical run to run and for any grouping
+ * of the batch.  Every output and every workspace word that is read is written by kernels (no memset, no host synchronisation):
+ * the call can be captured and replayed.  The frame loop of the search runs ONCE per utterance.
+ * M = K, e = 4 / 8.  Every part rounded up to 256 bytes:
+ *   work: asg_beam_graph_confidence_work_bytes(p, gl, beam_size) =
+ *         B * (asg_beam_graph_full_work_bytes' bytes per utterance without targets at store = 1, i.e.
+ *              asg_beam_decode_graph's bytes per utterance + 2*T*4 + 256 + T*M*4 + T*M*e,     + 2*M*e (two rows of beta))
+ * The search writes the caller's outputs, so there is no part behind the utterances; the token accumulators live in LDS.  No term
+ * in S or E and none in N*N (no (i, j) tile is kept); targets in the problem change nothing.
+ * Limits (ASG_ERR_UNSUPPORTED beyond): those of asg_beam_graph_full_forward without targets, and frame_tolerance <= 64;
+ * frame_tolerance < 0: ASG_ERR_INVALID.  Argument errors, in this order: asg_beam_graph_full_forward's for p, gl and beam_size;
+ * beam_threshold; frame_tolerance; a NULL buffer; ASG_ERR_WORKSPACE.  float32 and float64. */
+size_t asg_beam_graph_confidence_work_bytes(const asg_problem *p, const asg_token_graph_beam_loss *gl, int beam_size);
+int asg_beam_graph_confidence(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam_loss *gl, int beam_size,
+                              double beam_threshold, int frame_tolerance, void *work, size_t work_bytes, void *scores,
+                              int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *token_frames,
+                              void *token_confidences, void *normalisers, int flags, void *stream);
+
 /* ---- whole-loss entry points (no counterpart in the reference's native layer: they fold the Python-side
  * `full - aligned` and reduction of asg.py:128,136-142 and their autograd into the kernels, so one ASGLoss
  * step is 2 + 2 kernel launches with no PyTorch glue kernels in between) ------------------------------------ */

@@ -40,7 +40,8 @@ SYMBOLS = ["asg_hip_version", "asg_hip_strerror", "asg_ctx_create", "asg_ctx_des
            "asg_beam_words_full_backward", "asg_words_target_scores", "asg_beam_words_full_forward_la",
            "asg_beam_decode_words_nbest_la", "asg_beam_word_stream_nbest_la",
            "asg_beam_words_confidence_work_bytes", "asg_beam_words_confidence", "asg_beam_words_confidence_la",
-           "asg_beam_words_nbest_confidence_work_bytes", "asg_beam_words_nbest_confidence", "asg_beam_words_nbest_confidence_la"]
+           "asg_beam_words_nbest_confidence_work_bytes", "asg_beam_words_nbest_confidence", "asg_beam_words_nbest_confidence_la",
+           "asg_beam_graph_confidence_work_bytes", "asg_beam_graph_confidence"]
 ABI_VERSION = 230        # include/asg_hip.h: ASG_HIP_VERSION this package was written against
 
 
@@ -194,6 +195,9 @@ def lib():
     L.asg_beam_graph_full_scratch_bytes.argtypes = [pp, blp, ci]
     L.asg_beam_graph_full_forward.argtypes = [vp, pp, blp, ci, ctypes.c_double, vp, sz, vp, ci, vp]
     L.asg_beam_graph_full_backward.argtypes = [vp, pp, blp, ci, vp, sz, vp, vp, vp, vp, vp, sz, ci, vp]
+    L.asg_beam_graph_confidence_work_bytes.restype = sz
+    L.asg_beam_graph_confidence_work_bytes.argtypes = [pp, blp, ci]
+    L.asg_beam_graph_confidence.argtypes = [vp, pp, blp, ci, ctypes.c_double, ci, vp, sz] + [vp] * 8 + [ci, vp]
     L.asg_beam_words_full_work_bytes.restype = sz
     L.asg_beam_words_full_work_bytes.argtypes = [pp, bp, wp, ci, ci]
     L.asg_beam_words_full_scratch_bytes.restype = sz

@@ -873,6 +873,43 @@ class HipBackend:
             lambda: self._beam_loss_args(inputs, transition, graph, input_lengths, targets, target_lengths, lm_weight, token_score),
             (beam_size,), saved, scores, grad_scores, inputs, transition, targets, input_lengths, target_lengths)
 
+    def beam_decode_graph_confidence(self, inputs, transition, graph, input_lengths, beam_size, beam_threshold=float("inf"),
+                                     lm_weight=1.0, token_score=0.0, frame_tolerance=0, max_work_bytes=1 << 30):
+        """`beam_decode_graph` with the start frame and the lattice posterior of every token of the hypothesis ->
+        BeamGraphConfidence; see include/asg_hip.h::asg_beam_graph_confidence.  The graph goes through the compile of the
+        beam-pruned loss (`_beam_loss_args`, cached on it); grouped under `max_work_bytes` as `_decode_graph` does."""
+        beam_size, beam_threshold = min(int(beam_size), (1 << 31) - 1), float(beam_threshold)
+        tol = max(-1, min(int(frame_tolerance), (1 << 31) - 1))
+        L = _lib.lib()
+        what = "asg_beam_graph_confidence"
+        from . import graph as _graph
+        if not isinstance(graph, _graph.TokenGraph):                           # the graph is checked before the device
+            raise TypeError("torch_asg_amd: graph must be a torch_asg_amd.TokenGraph")
+        if inputs.dim() == 3 and graph.N != inputs.shape[2]:
+            raise RuntimeError("torch_asg_amd: the graph is over %d tokens but the emissions have N = %d" % (graph.N, inputs.shape[2]))
+        dev = inputs.device
+        with self._guard(dev):
+            (gl,), Q, keep = self._beam_loss_args(inputs, transition, graph, input_lengths, None, None, lm_weight, token_score)
+            T, B, N = inputs.shape
+            p, _, input_lengths, _ = self._device_problem(inputs, transition, None, input_lengths, None)
+
+            def call(work, nbytes, *outs):
+                return L.asg_beam_graph_confidence(None, ctypes.byref(p), ctypes.byref(gl), beam_size, beam_threshold, tol, work,
+                                                   nbytes, *outs)
+            groups = self._groups(
+                p, B, max_work_bytes, lambda: L.asg_beam_graph_confidence_work_bytes(ctypes.byref(p), ctypes.byref(gl), beam_size),
+                Q, lambda: _lib.check(call(None, 0, *(None,) * 8, 0, None), what), inputs, input_lengths=input_lengths)
+            real = torch.empty(2, B, dtype=inputs.dtype, device=dev)       # scores, normalisers
+            conf = torch.empty(B, T, dtype=inputs.dtype, device=dev)
+            out = torch.empty(4, B, T, dtype=torch.int64, device=dev)      # path, tokens, states, token_frames
+            token_lengths = torch.empty(B, dtype=torch.int64, device=dev)
+            stream = self._stream(dev)
+            for b0, b1, work in groups:
+                _lib.check(call(work.data_ptr(), work.numel(), real[0, b0:].data_ptr(), out[0, b0].data_ptr(),
+                                out[1, b0].data_ptr(), token_lengths[b0:].data_ptr(), out[2, b0].data_ptr(), out[3, b0].data_ptr(),
+                                conf[b0].data_ptr(), real[1, b0:].data_ptr(), 0, stream), what)
+        return BeamGraphConfidence(real[0], out[0], out[1], token_lengths, out[2], out[3], conf, real[1])
+
     def graph_target_scores(self, inputs, transition, graph, targets, target_lengths, lm_weight=1.0, token_score=0.0):
         """[B]: the automaton's score of every target sequence (consecutive repeats merged), -inf where it rejects it; see
         include/asg_hip.h::asg_graph_target_scores."""
@@ -1279,6 +1316,42 @@ def beam_decode_graph(inputs, transition, graph, input_lengths=None, beam_size=2
     with torch.no_grad():
         return native().beam_decode_graph(*_plain(inputs, transition), graph, input_lengths, beam_size, beam_threshold, lm_weight,
                                           token_score, max_work_bytes)
+
+
+BeamGraphConfidence = collections.namedtuple("BeamGraphConfidence", ["scores", "path", "tokens", "token_lengths", "states",
+                                                                     "token_frames", "token_confidences", "normalisers"])
+
+
+def beam_decode_graph_confidence(inputs, transition, graph, input_lengths=None, beam_size=256, beam_threshold=float("inf"),
+                                 lm_weight=1.0, token_score=0.0, frame_tolerance=0, max_work_bytes=1 << 30):
+    """`beam_decode_graph` that also says where every token of its hypothesis starts and how sure the search is of it: what
+    pseudo-label filters, highlighting of doubtful characters and token time stamps need beside the tokens.  No gradient.
+
+    The search is `beam_decode_graph`'s, run once.  The sets of product states it kept span a lattice (the one
+    `beam_graph_full_score` sums without targets); a lattice path starts a token with label i at frame t when it stands in a
+    state with that label at t = 0, or takes an edge (anything but the stay) into such a state at t >= 1.  P(i, t) is the share
+    of the lattice's probability mass, exp(weight - Z_K), on the paths with that event, whatever their automaton state
+    (include/asg_hip.h::asg_beam_graph_confidence).  -> BeamGraphConfidence: the five tensors of `beam_decode_graph`, bit for
+    bit, and
+      token_frames      [B, T] int64  the frame s_k at which token k of the hypothesis starts, -1 behind the tokens
+      token_confidences [B, T] dtype  the sum of P(tokens[k], t) over |t - s_k| <= frame_tolerance, 0 behind the tokens
+      normalisers       [B]    dtype  Z_K, bit-equal to `beam_graph_full_score` without targets
+    With frame_tolerance = 0 a confidence is a probability, between exp(scores - normalisers) and 1 up to rounding.  With a
+    tolerance it is the expected number of starts of that label inside the window: it can pass 1 ("a b a" inside one window)
+    and is returned unclipped.  With a `TokenGraph.from_lexicon` graph the confidence of a separator token is the confidence of
+    a word boundary.  A narrow beam keeps little competing mass, so its confidences are high: they are posteriors given what
+    the search kept.  Utterances without a path have score and normaliser -inf, integer outputs -1 and confidences 0; there is
+    never a NaN.  frame_tolerance < 0 or > 64 is refused by the library (RuntimeError).
+
+    Results are bit-identical run to run and for any `max_work_bytes`; inputs, widening, caching, capture and the utterance
+    groups are those of `beam_decode_graph` (the graph is compiled once more, for `beam_graph_full_score`'s kernels, and cached
+    on it), with a workspace about T * beam_size * (12 + 4 or 8) bytes per utterance (back-pointers, the sorted sets and alpha)
+    plus the search's 12-16 bytes per product state.
+    """
+    _check_beam(beam_size, beam_threshold)
+    with torch.no_grad():
+        return native().beam_decode_graph_confidence(*_plain(inputs, transition), graph, input_lengths, beam_size, beam_threshold,
+                                                     lm_weight, token_score, frame_tolerance, max_work_bytes)
 
 
 BeamWords = collections.namedtuple("BeamWords", ["scores", "path", "tokens", "token_lengths", "states", "lm_states", "words",
@@ -1920,6 +1993,13 @@ class ASGLoss(nn.Module):
         `torch_asg_amd.beam_decode_graph`."""
         return beam_decode_graph(inputs, self.transition, graph, input_lengths, beam_size, beam_threshold, lm_weight, token_score,
                                  max_work_bytes)
+
+    def beam_decode_graph_confidence(self, inputs, graph, input_lengths=None, beam_size=256, beam_threshold=float("inf"),
+                                     lm_weight=1.0, token_score=0.0, frame_tolerance=0, max_work_bytes=1 << 30):
+        """`beam_decode_graph` under this criterion's transitions with the start frame and the lattice posterior of every token;
+        see `torch_asg_amd.beam_decode_graph_confidence`."""
+        return beam_decode_graph_confidence(inputs, self.transition, graph, input_lengths, beam_size, beam_threshold, lm_weight,
+                                            token_score, frame_tolerance, max_work_bytes)
 
     def beam_decode_words(self, inputs, lexicon, word_lm, input_lengths=None, beam_size=256, beam_threshold=float("inf"),
                           lm_weight=1.0, word_score=0.0, token_score=0.0, max_work_bytes=1 << 30, lookahead=None):

@@ -1406,6 +1406,50 @@ int asg_beam_graph_full_backward(asg_ctx *ctx, const asg_problem *p, const asg_t
         });
 }
 
+// The token confidences: the checks of the beam-pruned loss WITHOUT targets (targets in the problem are not looked at).
+static int check_beam_conf(const asg_problem *p, const asg_token_graph_beam_loss *gl, int beam_size) {
+    if (!p) return ASG_ERR_INVALID;
+    asg_problem q = *p;
+    q.targets = nullptr;
+    return check_beam_loss(&q, gl, beam_size);
+}
+
+size_t asg_beam_graph_confidence_work_bytes(const asg_problem *p, const asg_token_graph_beam_loss *gl, int beam_size) {
+    if (check_beam_conf(p, gl, beam_size) != ASG_OK) return 0;
+    const asg_token_graph_beam *gb = gl->beam;
+    const int Q = (int) gb->graph->Q, K = beam_graph_k(Q, beam_size);
+    return beam_conf_work_bytes(p->dtype == ASG_DTYPE_F64 ? 8 : 4, (int) p->T, (int) p->B, Q, K,
+                                beam_graph_cap(Q, K, gb->max_out, (int) gb->num_start));
+}
+
+int asg_beam_graph_confidence(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam_loss *gl, int beam_size,
+                              double beam_threshold, int frame_tolerance, void *work, size_t work_bytes, void *scores,
+                              int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *token_frames,
+                              void *token_confidences, void *normalisers, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    int rc = check_beam_conf(p, gl, beam_size);
+    if (rc) return rc;
+    if (!(beam_threshold >= 0.0)) return ASG_ERR_INVALID;                  // negative or NaN
+    if (frame_tolerance < 0) return ASG_ERR_INVALID;
+    if (frame_tolerance > kBeamConfMaxTol) return ASG_ERR_UNSUPPORTED;
+    if (!work || !scores || !path || !tokens || !token_lengths || !states || !token_frames || !token_confidences || !normalisers)
+        return ASG_ERR_INVALID;
+    if (work_bytes < asg_beam_graph_confidence_work_bytes(p, gl, beam_size)) return ASG_ERR_WORKSPACE;
+    const Problem P = to_problem(p);
+    const GraphArgs G = to_graph_args(gl->beam->graph);
+    const BeamGraphArgs BG = to_beam_graph_args(gl->beam);
+    BeamLossArgs L{};
+    L.S = (int) gl->S; L.start = gl->start; L.next = gl->next;
+    const int K = beam_graph_k(G.Q, beam_size);
+    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
+    long long *tf = (long long *) token_frames;
+    return hip_status(ASG_DISPATCH(p,
+        launch_beam_conf<float>(P, G, BG, L, K, beam_threshold, frame_tolerance, work, scores, pa, tk, tl, st, tf, token_confidences,
+                                normalisers, (hipStream_t) stream),
+        launch_beam_conf<double>(P, G, BG, L, K, beam_threshold, frame_tolerance, work, scores, pa, tk, tl, st, tf, token_confidences,
+                                 normalisers, (hipStream_t) stream)));
+}
+
 static int check_beam_words_loss(const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm, int beam_size) {
     int rc = check_beam_words(p, gb, lm, beam_size);
     if (rc) return rc;

@@ -32,6 +32,7 @@
 #include "asg_kernels.h"
 #include "asg_beam_common.h"     // a256, beam_work_layout: the beam search's own part lies at the front of the workspace
 #include "asg_beam_lattice.h"    // everything behind the search that the word family's loss shares
+#include "asg_beam_token_lat.h"  // TokenLat: how a product state's edges are walked (shared with asg_beam_conf.hip)
 
 namespace asg {
 
@@ -197,26 +198,7 @@ __global__ void __launch_bounds__(kBL) beam_loss_fwd(Problem P, GraphArgs g, Bea
 // ---------------------------------------------------------------------------------------------------------------------
 // Backward: beam_loss_bwd<R, TL, TokenLat<R>> (asg_beam_lattice.h), the mirror image of 4 through the outgoing CSR.
 // ---------------------------------------------------------------------------------------------------------------------
-template <typename R>
-struct TokenLat {
-    using Key = int;
-    struct Args { GraphArgs g; BeamGraphArgs bg; BeamLossLayout lay; };
-    const int *lab, *orow;
-    const int2 *oarc;
-    const R *ow, *fw;
-    __device__ void bind(const Args &a) {
-        lab = a.g.label; orow = a.bg.orow; oarc = (const int2 *) a.bg.oarc; ow = (const R *) a.bg.ow; fw = (const R *) a.g.final_w;
-    }
-    __device__ int label(int q) const { return lab[q]; }
-    __device__ void end(int q, R &e) const { e = fw[q]; }
-    template <typename F> __device__ void for_each_out(int q, int lg, int G, F fn) const {
-        const int e1 = orow[q + 1];
-        for (int e = orow[q] + lg; e < e1; e += G) {
-            const int2 a = oarc[e];
-            fn(a.x, [&]() -> R { return ow[e]; }, a.y);
-        }
-    }
-};
+// TokenLat<R> (asg_beam_token_lat.h): the edges are bg's outgoing CSR; the token confidences (asg_beam_conf.hip) walk them too.
 
 }  // namespace
 
@@ -249,19 +231,16 @@ bool beam_loss_fits(int elem, int M, int N) {
     return kBLHead + (size_t) M * (elem + 4) <= kBLLds && bwd_lds(elem, 4, M, N, false) <= kBLLds;
 }
 
+// The forward's launches behind a layout the caller made: `lay.per` may be wider than beam_loss_layout's (a caller with parts of
+// its own behind the layout -- asg_beam_conf.hip), and the five outputs of the search go where the caller says.
 template <typename R>
-hipError_t launch_beam_loss_forward(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const BeamLossArgs &L, int K,
-                                    double theta, bool store, void *work, void *scores, hipStream_t stream) {
-    const int T = P.T, B = P.B;
-    const int cap = beam_graph_cap(G.Q, K, BG.max_out, BG.num_start);
-    const int nf = P.targets ? (P.S < T ? P.S : T) : 0;
-    const BeamLossLayout lay = beam_loss_layout(sizeof(R), T, G.Q, K, cap, nf, store);
-    char *w = (char *) work, *tail = w + (size_t) B * lay.per;
-    R *bsc = (R *) tail;
-    long long *btl = (long long *) (tail + a256((size_t) B * 8));
-    long long *bpa = (long long *) (tail + 2 * a256((size_t) B * 8));
-    hipError_t e = launch_beam_graph<R>(P, G, BG, K, theta, work, bsc, bpa, bpa + (size_t) B * T, btl, bpa + 2 * (size_t) B * T,
-                                        stream, lay.per, lay.cnt);
+hipError_t launch_beam_loss_lattice(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const BeamLossArgs &L,
+                                    const BeamLossLayout &lay, int K, double theta, bool store, void *work, void *scores,
+                                    void *beam_scores, long long *path, long long *tokens, long long *tlen, long long *states,
+                                    hipStream_t stream) {
+    const int B = P.B;
+    char *w = (char *) work;
+    hipError_t e = launch_beam_graph<R>(P, G, BG, K, theta, work, beam_scores, path, tokens, tlen, states, stream, lay.per, lay.cnt);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(beam_loss_targets, dim3(B), dim3(kBS), 0, stream, P, G, L, lay, w);
     hipLaunchKernelGGL((beam_loss_accept<R>), dim3((B + 63) / 64), dim3(64), 0, stream, G, lay, w, B);
@@ -271,6 +250,20 @@ hipError_t launch_beam_loss_forward(const Problem &P, const GraphArgs &G, const 
     set_lds((const void *) beam_loss_fwd<R>, dyn);
     hipLaunchKernelGGL((beam_loss_fwd<R>), dim3(B), dim3(kBL), dyn, stream, P, G, lay, (int) store, w, (R *) scores);
     return hipGetLastError();
+}
+
+template <typename R>
+hipError_t launch_beam_loss_forward(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const BeamLossArgs &L, int K,
+                                    double theta, bool store, void *work, void *scores, hipStream_t stream) {
+    const int T = P.T, B = P.B;
+    const int cap = beam_graph_cap(G.Q, K, BG.max_out, BG.num_start);
+    const int nf = P.targets ? (P.S < T ? P.S : T) : 0;
+    const BeamLossLayout lay = beam_loss_layout(sizeof(R), T, G.Q, K, cap, nf, store);
+    char *tail = (char *) work + (size_t) B * lay.per;
+    long long *btl = (long long *) (tail + a256((size_t) B * 8));
+    long long *bpa = (long long *) (tail + 2 * a256((size_t) B * 8));
+    return launch_beam_loss_lattice<R>(P, G, BG, L, lay, K, theta, store, work, scores, tail, bpa, bpa + (size_t) B * T, btl,
+                                       bpa + 2 * (size_t) B * T, stream);
 }
 
 template <typename R>
@@ -288,6 +281,14 @@ template hipError_t launch_beam_loss_forward<float>(const Problem &, const Graph
                                                     int, double, bool, void *, void *, hipStream_t);
 template hipError_t launch_beam_loss_forward<double>(const Problem &, const GraphArgs &, const BeamGraphArgs &, const BeamLossArgs &,
                                                      int, double, bool, void *, void *, hipStream_t);
+#define ASG_BEAM_LOSS_LATTICE_INST(R)                                                                                        \
+    template hipError_t launch_beam_loss_lattice<R>(const Problem &, const GraphArgs &, const BeamGraphArgs &,                 \
+                                                    const BeamLossArgs &, const BeamLossLayout &, int, double, bool, void *,    \
+                                                    void *, void *, long long *, long long *, long long *, long long *,        \
+                                                    hipStream_t);
+ASG_BEAM_LOSS_LATTICE_INST(float)
+ASG_BEAM_LOSS_LATTICE_INST(double)
+#undef ASG_BEAM_LOSS_LATTICE_INST
 template hipError_t launch_beam_loss_backward<float>(const Problem &, const GraphArgs &, const BeamGraphArgs &, int, const void *,
                                                      const void *, const void *, void *, void *, void *, bool, hipStream_t);
 template hipError_t launch_beam_loss_backward<double>(const Problem &, const GraphArgs &, const BeamGraphArgs &, int, const void *,

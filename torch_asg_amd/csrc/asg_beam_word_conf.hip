@@ -28,13 +28,11 @@
 #include "asg_beam_lattice.h"     // the helpers of the lattice pass: subgroup, find_sorted, the butterflies, to_fixed
 #include "asg_beam_word_lat.h"    // WordLat: how a pair's edges are walked
 #include "asg_beam_word_conf_pull.h"  // the beta pull, shared with asg_beam_word_nbest_conf.hip
+#include "asg_beam_conf_sink.h"   // HypSink and its ring, shared with asg_beam_conf.hip
 
 namespace asg {
 
 namespace {
-
-constexpr int kConfRing = 256;                                // >= 2 * kBeamWordConfMaxTol + 2, a power of two
-static_assert(kConfRing >= 2 * kBeamWordConfMaxTol + 2 && (kConfRing & (kConfRing - 1)) == 0, "ring");
 
 // ---------------------------------------------------------------------------------------------------------------------
 // 1: the search with its end.  beam_word_loss_search's loop (cnt[t] = |A_t| for t < len), then beam_word_kernel's end.
@@ -138,42 +136,8 @@ __global__ void __launch_bounds__(kBT) beam_word_conf_search(Problem P, GraphArg
 // 5: beta with the word-event sink.  Dynamic LDS: [nq u64 M][nb R M][pad to 16][ring u64 256].  beta[t-1] crosses from the lanes
 // that sum it to the workgroup through the utterance's two rows in the workspace, as in beam_loss_bwd.
 // ---------------------------------------------------------------------------------------------------------------------
-// 5x's sink: the words of ONE hypothesis in frame order.  The words whose window holds the frame the workgroup stands at are
-// [ka, kb), the same in every thread; a word's accumulator is slot k mod 256 of the ring.
-template <typename R>
-struct HypSink {
-    static constexpr bool kBarrier = false;
-    const long long *wd, *wf;
-    R *cf;
-    unsigned long long *ring;
-    int tol, ka, kb;
-    // moves the range to frame t (frames descend) and finishes the words that leave it: no later event can reach them
-    __device__ __forceinline__ void window(int t) {
-        const int tid = threadIdx.x;
-        int nkb = kb;
-        while (nkb > 0 && wf[nkb - 1] > (long long) t + tol) --nkb;
-        for (int k = nkb + tid; k < kb; k += kBL) {
-            unsigned long long &slot = ring[k & (kConfRing - 1)];
-            cf[k] = (R) ((double) slot * (1.0 / kConfScale));
-            slot = 0ull;
-        }
-        kb = nkb;
-        if (ka > kb) ka = kb;
-        while (ka > 0 && wf[ka - 1] >= (long long) t - tol) --ka;
-    }
-    __device__ __forceinline__ bool open() const { return ka < kb; }
-    // word w completed with posterior exp(x) at the frame the window stands at
-    __device__ __forceinline__ void add(int w, R x) {
-        unsigned long long fx = 0ull;
-        bool have = false;
-        for (int k = ka; k < kb; ++k) {
-            if (wd[k] != (long long) w) continue;
-            if (!have) { fx = to_fixed((double) bexp(x), kConfScale); have = true; }
-            if (fx) atomicAdd(&ring[k & (kConfRing - 1)], fx);
-        }
-    }
-};
-
+// The sink is HypSink (asg_beam_conf_sink.h): the words whose window holds the frame are [ka, kb), a word's accumulator slot
+// k mod 256 of the ring.
 inline size_t conf_lds(int elem, int M) { return bwd_front(elem, 8, M) + (size_t) kConfRing * 8; }
 
 template <typename R>

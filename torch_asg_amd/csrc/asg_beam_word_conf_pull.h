@@ -15,12 +15,11 @@
 #pragma once
 #include "asg_beam_lattice.h"
 #include "asg_beam_word_lat.h"
+#include "asg_beam_conf_sink.h"   // kConfScale: the fixed point of every sink
 
 namespace asg {
 
 namespace {
-
-constexpr double kConfScale = 18014398509481984.0;            // 2^54: a word sums at most 129 completions of at most 1 (+ rounding)
 
 template <typename R, typename Sink>
 __device__ __forceinline__ void beam_word_conf_pull(const Problem &P, const typename WordLat<R>::Args &args, char *wb, size_t beta_off,

@@ -415,6 +415,29 @@ hipError_t launch_beam_loss_backward(const Problem &P, const GraphArgs &G, const
                                      const void *scores, const void *grad_scores, void *grad_inputs, void *grad_transition,
                                      void *scratch, bool accumulate, hipStream_t stream);
 
+// launches 1 - 4 of that forward behind a layout the caller made (`lay.per` may be wider than beam_loss_layout's: a caller with
+// parts of its own behind an utterance's block), the search writing its five outputs where the caller says
+template <typename R>
+hipError_t launch_beam_loss_lattice(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const BeamLossArgs &L,
+                                    const BeamLossLayout &lay, int K, double theta, bool store, void *work, void *scores,
+                                    void *beam_scores, long long *path, long long *tokens, long long *tlen, long long *states,
+                                    hipStream_t stream);
+
+// ---- Token confidences and start frames from the lattice of that search (asg_beam_conf.hip): asg_beam_graph_confidence.  One
+// utterance's workspace: the beam-pruned loss's layout without targets with alpha stored for all frames (M = K), then two rows
+// of beta [2][M] that the pull hands from one frame to the next.  The accumulators of the hypothesis' tokens live in LDS.
+constexpr int kBeamConfMaxTol = 64;        // a ring of 256 accumulators holds every token whose window is open
+struct BeamConfLayout {
+    BeamLossLayout lat;          // lat.per is this layout's `per`
+    size_t beta, per;
+};
+BeamConfLayout beam_conf_layout(int elem, int T, int Q, int K, int cap);
+size_t beam_conf_work_bytes(int elem, int T, int B, int Q, int K, int cap);
+template <typename R>
+hipError_t launch_beam_conf(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const BeamLossArgs &L, int K, double theta,
+                            int tol, void *work, void *scores, long long *path, long long *tokens, long long *tlen,
+                            long long *states, long long *token_frames, void *token_conf, void *normalisers, hipStream_t stream);
+
 // ---- Beam-pruned full score and gradients over the pairs of the word decoder (asg_beam_word_loss.hip): asg_beam_words_full_*.
 // One utterance's workspace: the word decoder's own layout at the front (bq, bh: its [T][K] lists), then (byte offsets, each part
 // 256-byte aligned) the kept counts cnt [T], the lattice counts nu [T], hdr (word 0: forced pairs n), the forced pairs' keys
