@@ -1214,6 +1214,53 @@ int asg_beam_graph_confidence(asg_ctx *ctx, const asg_problem *p, const asg_toke
                               int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *token_frames,
                               void *token_confidences, void *normalisers, int flags, void *stream);
 
+/* ---- TOKEN CONFIDENCES and START FRAMES for EVERY ROW of asg_beam_decode_graph_nbest's list: what rescoring with a per-token
+ * posterior, ROVER-style combination of the rows and pseudo-labelling on the tokens the rows agree on need, from ONE search.  The
+ * quantity is not new: P(i, t) of asg_beam_graph_confidence does not depend on the hypothesis; a row only selects which
+ * (frame, label) cells are read.  Per utterance b everything is asg_beam_decode_graph_nbest's and asg_beam_graph_confidence's on
+ * the same arguments: the same search, run ONCE; the same kept sets A_t, candidates, order and num_hyps; the lattice with
+ * U_t = A_t (p->targets is not looked at); the same Z_K; the same token events P(i, t).  The argument order is
+ * asg_beam_decode_graph_nbest's with the view of asg_beam_graph_confidence in place of the beam view, frame_tolerance behind nbest
+ * and token_frames, token_confidences, normalisers behind num_hyps.
+ *   1. The eight n-best outputs of asg_beam_decode_graph_nbest, bit for bit (the same device text ranks, walks and writes).
+ *      path and states may be NULL.
+ *   2. token_frames [B][nbest][T] int64.  For row r < num_hyps[b] and k < token_lengths[b][r], s_{r,k} is the first frame of the
+ *      k-th run of labels in the row's back-pointer path (step 3 of asg_beam_graph_confidence, applied to the row's path;
+ *      s_{r,0} = 0).  It ascends strictly within a row.  -1 behind the tokens and in padding rows.
+ *   3. token_confidences [B][nbest][T] dtype.  conf_{r,k} = sum of P(tokens[b][r][k], t) over t in [s_{r,k} - tol, s_{r,k} + tol]
+ *      meet [0, len-1]; 0 behind the tokens and in padding rows; unclipped.  tol = frame_tolerance.
+ *   4. normalisers [B] dtype: Z_K, asg_beam_graph_full_forward's score without targets bit for bit.
+ * Properties.  Row 0's frames and confidences are asg_beam_graph_confidence's on the same arguments, bit for bit: an event is
+ * added as the same 54-bit fixed-point integer, an integer sum does not depend on its order, and the conversion is the same
+ * expression.  At tol = 0, exp(scores[b][r] - Z_K) <= conf_{r,k} <= 1 up to rounding for every row: a row's path is a lattice
+ * path that has the event.  Rows that start the same label at the same frame get the same bits (they read one cell).  Degenerate
+ * utterances (len == 0, an empty last set, no finite end): num_hyps 0, scores -inf, normaliser -inf, frames -1, confidences 0;
+ * never a NaN.  NO FLOAT ATOMICS, no memset, no host synchronisation: bit-identical run to run and for any grouping of the
+ * batch, and the call can be captured and replayed.  The frame loop of the search runs ONCE per utterance.
+ * K = min(beam_size, max(Q, 1)), M = K, e = 4 / 8, nb = min(nbest, K), P2(x) = the power of two >= max(x, 2).  Every part rounded
+ * up to 256 bytes:
+ *   work: asg_beam_graph_nbest_confidence_work_bytes(p, gl, beam_size, nbest) =
+ *         B * (asg_beam_graph_confidence_work_bytes' bytes per utterance
+ *              + 8 + K*e (the last set) + T*nb*4 (the rows' product states) + 256 + (T+2)*4 (the first cell of every frame)
+ *              + P2(nb*T)*8 (the rows' queries) + nb*T*8 (the cells) + nb*T*8 (their sums))
+ *         + 2 * (B*8) + 3*B*T*8 (the one-best outputs of the search).
+ * No term in S, E or N*N; targets in the problem change nothing.
+ * Limits: the union of the two parent calls': nbest < 1 or frame_tolerance < 0: ASG_ERR_INVALID; nbest > 8192 or
+ * frame_tolerance > 64: ASG_ERR_UNSUPPORTED; the limits of asg_beam_graph_confidence.  ONE new limit (ASG_ERR_UNSUPPORTED
+ * beyond): the accumulators of the open cells live in LDS beside a frame's lattice set,
+ *         16 * ceil(M*(e+4) / 16) + 1024 + 12 * P2(min(nbest, K) * (2*frame_tolerance + 2)) <= 163840   and   nb*T <= 2^30.
+ * (A frame holds a label once among its cells, so min(nbest, K, N) rows would do; the bound keeps the expression of
+ * asg_beam_words_nbest_confidence, whose ring function it shares.)
+ * Argument errors, in this order: asg_beam_graph_confidence's for p, gl and beam_size; nbest; frame_tolerance and the new limit;
+ * the threshold; a NULL among work and the outputs other than path and states; the workspace.  float32 and float64. */
+size_t asg_beam_graph_nbest_confidence_work_bytes(const asg_problem *p, const asg_token_graph_beam_loss *gl, int beam_size,
+                                                  int nbest);
+int asg_beam_graph_nbest_confidence(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam_loss *gl, int beam_size,
+                                    double beam_threshold, int nbest, int frame_tolerance, void *work, size_t work_bytes,
+                                    void *scores, void *emission_scores, void *graph_scores, int64_t *path, int64_t *tokens,
+                                    int64_t *token_lengths, int64_t *states, int64_t *num_hyps, int64_t *token_frames,
+                                    void *token_confidences, void *normalisers, int flags, void *stream);
+
 /* ---- whole-loss entry points (no counterpart in the reference's native layer: they fold the Python-side
  * `full - aligned` and reduction of asg.py:128,136-142 and their autograd into the kernels, so one ASGLoss
  * step is 2 + 2 kernel launches with no PyTorch glue kernels in between) ------------------------------------ */

@@ -41,7 +41,8 @@ SYMBOLS = ["asg_hip_version", "asg_hip_strerror", "asg_ctx_create", "asg_ctx_des
            "asg_beam_decode_words_nbest_la", "asg_beam_word_stream_nbest_la",
            "asg_beam_words_confidence_work_bytes", "asg_beam_words_confidence", "asg_beam_words_confidence_la",
            "asg_beam_words_nbest_confidence_work_bytes", "asg_beam_words_nbest_confidence", "asg_beam_words_nbest_confidence_la",
-           "asg_beam_graph_confidence_work_bytes", "asg_beam_graph_confidence"]
+           "asg_beam_graph_confidence_work_bytes", "asg_beam_graph_confidence",
+           "asg_beam_graph_nbest_confidence_work_bytes", "asg_beam_graph_nbest_confidence"]
 ABI_VERSION = 230        # include/asg_hip.h: ASG_HIP_VERSION this package was written against
 
 
@@ -198,6 +199,9 @@ def lib():
     L.asg_beam_graph_confidence_work_bytes.restype = sz
     L.asg_beam_graph_confidence_work_bytes.argtypes = [pp, blp, ci]
     L.asg_beam_graph_confidence.argtypes = [vp, pp, blp, ci, ctypes.c_double, ci, vp, sz] + [vp] * 8 + [ci, vp]
+    L.asg_beam_graph_nbest_confidence_work_bytes.restype = sz
+    L.asg_beam_graph_nbest_confidence_work_bytes.argtypes = [pp, blp, ci, ci]
+    L.asg_beam_graph_nbest_confidence.argtypes = [vp, pp, blp, ci, ctypes.c_double, ci, ci, vp, sz] + [vp] * 11 + [ci, vp]
     L.asg_beam_words_full_work_bytes.restype = sz
     L.asg_beam_words_full_work_bytes.argtypes = [pp, bp, wp, ci, ci]
     L.asg_beam_words_full_scratch_bytes.restype = sz

@@ -910,6 +910,52 @@ class HipBackend:
                                 conf[b0].data_ptr(), real[1, b0:].data_ptr(), 0, stream), what)
         return BeamGraphConfidence(real[0], out[0], out[1], token_lengths, out[2], out[3], conf, real[1])
 
+    def beam_decode_graph_nbest_confidence(self, inputs, transition, graph, input_lengths, beam_size, nbest,
+                                           beam_threshold=float("inf"), lm_weight=1.0, token_score=0.0, return_alignments=False,
+                                           frame_tolerance=0, max_work_bytes=1 << 30):
+        """`beam_decode_graph_nbest` with the start frame and the lattice posterior of every token of every row, from one
+        search -> BeamNbestConfidence; see include/asg_hip.h::asg_beam_graph_nbest_confidence.  The graph goes through the
+        compile of the beam-pruned loss (`_beam_loss_args`, cached on it); grouped under `max_work_bytes` as `_decode_graph`
+        does."""
+        beam_size, beam_threshold = min(int(beam_size), (1 << 31) - 1), float(beam_threshold)
+        nbest = min(int(nbest), (1 << 31) - 1)
+        tol = max(-1, min(int(frame_tolerance), (1 << 31) - 1))
+        L = _lib.lib()
+        what = "asg_beam_graph_nbest_confidence"
+        from . import graph as _graph
+        if not isinstance(graph, _graph.TokenGraph):                           # the graph is checked before the device
+            raise TypeError("torch_asg_amd: graph must be a torch_asg_amd.TokenGraph")
+        if inputs.dim() == 3 and graph.N != inputs.shape[2]:
+            raise RuntimeError("torch_asg_amd: the graph is over %d tokens but the emissions have N = %d" % (graph.N, inputs.shape[2]))
+        dev = inputs.device
+        with self._guard(dev):
+            (gl,), Q, keep = self._beam_loss_args(inputs, transition, graph, input_lengths, None, None, lm_weight, token_score)
+            T, B, N = inputs.shape
+            p, _, input_lengths, _ = self._device_problem(inputs, transition, None, input_lengths, None)
+
+            def call(work, nbytes, *outs):
+                return L.asg_beam_graph_nbest_confidence(None, ctypes.byref(p), ctypes.byref(gl), beam_size, beam_threshold, nbest,
+                                                         tol, work, nbytes, *outs)
+            groups = self._groups(
+                p, B, max_work_bytes,
+                lambda: L.asg_beam_graph_nbest_confidence_work_bytes(ctypes.byref(p), ctypes.byref(gl), beam_size, nbest),
+                Q, lambda: _lib.check(call(None, 0, *(None,) * 11, 0, None), what), inputs, input_lengths=input_lengths)
+            sc = torch.empty(3, B, nbest, dtype=inputs.dtype, device=dev)      # scores, emission_scores, graph_scores
+            wide = torch.empty(2, B, nbest, T, dtype=torch.int64, device=dev)  # tokens, token_frames
+            conf = torch.empty(B, nbest, T, dtype=inputs.dtype, device=dev)
+            align = torch.empty(2, B, nbest, T, dtype=torch.int64, device=dev) if return_alignments else (None,) * 2
+            token_lengths = torch.empty(B, nbest, dtype=torch.int64, device=dev)
+            num_hyps = torch.empty(B, dtype=torch.int64, device=dev)
+            norm = torch.empty(B, dtype=inputs.dtype, device=dev)
+            al = lambda i, b0: align[i, b0:].data_ptr() if return_alignments else None      # noqa: E731
+            stream = self._stream(dev)
+            for b0, b1, work in groups:
+                _lib.check(call(work.data_ptr(), work.numel(), sc[0, b0:].data_ptr(), sc[1, b0:].data_ptr(), sc[2, b0:].data_ptr(),
+                                al(0, b0), wide[0, b0:].data_ptr(), token_lengths[b0:].data_ptr(), al(1, b0),
+                                num_hyps[b0:].data_ptr(), wide[1, b0:].data_ptr(), conf[b0:].data_ptr(), norm[b0:].data_ptr(), 0,
+                                stream), what)
+        return BeamNbestConfidence(sc[0], sc[1], sc[2], wide[0], token_lengths, num_hyps, align[0], align[1], wide[1], conf, norm)
+
     def graph_target_scores(self, inputs, transition, graph, targets, target_lengths, lm_weight=1.0, token_score=0.0):
         """[B]: the automaton's score of every target sequence (consecutive repeats merged), -inf where it rejects it; see
         include/asg_hip.h::asg_graph_target_scores."""
@@ -1554,6 +1600,45 @@ def beam_decode_graph_nbest(inputs, transition, graph, input_lengths=None, beam_
                                                 beam_threshold, lm_weight, token_score, return_alignments, max_work_bytes)
 
 
+BeamNbestConfidence = collections.namedtuple("BeamNbestConfidence",
+                                             BeamNbest._fields + ("token_frames", "token_confidences", "normalisers"))
+
+
+def beam_decode_graph_nbest_confidence(inputs, transition, graph, input_lengths=None, beam_size=256, nbest=10,
+                                       beam_threshold=float("inf"), lm_weight=1.0, token_score=0.0, return_alignments=False,
+                                       frame_tolerance=0, max_work_bytes=1 << 30):
+    """`beam_decode_graph_nbest` that also says, for EVERY row of the list, where each token starts and how sure the search is of
+    it: what rescoring with a per-token posterior, ROVER-style combination of the rows and pseudo-labelling on the tokens the
+    rows agree on need -- from one search instead of `beam_decode_graph_nbest` plus `beam_decode_graph_confidence`, which
+    would search twice and still give posteriors for row 0 only.  No gradient.
+
+    Nothing is re-defined.  The search, the candidates, their order and `num_hyps` are `beam_decode_graph_nbest`'s; the lattice
+    of the kept sets, the token events P(i, t) and Z_K are `beam_decode_graph_confidence`'s
+    (include/asg_hip.h::asg_beam_graph_nbest_confidence).  P(i, t) does not depend on the hypothesis: a row only selects which
+    (frame, label) cells are read.  -> BeamNbestConfidence: the eight fields of `BeamNbest`, bit for bit, and
+      token_frames      [B, nbest, T] int64  the frame at which token k of row r starts, -1 behind the tokens and in padding rows
+      token_confidences [B, nbest, T] dtype  the sum of P(tokens[r][k], t) over |t - frame| <= frame_tolerance, 0 there
+      normalisers       [B]           dtype  Z_K, bit-equal to `beam_graph_full_score` without targets
+    Row 0's frames and confidences are `beam_decode_graph_confidence`'s bit for bit; rows that start the same label at the same
+    frame carry the same bits.  With frame_tolerance = 0 a confidence lies between exp(scores[r] - normalisers) and 1 up to
+    rounding.  Utterances without a path have num_hyps 0, scores and normaliser -inf, frames -1 and confidences 0; there is
+    never a NaN.  nbest < 1 raises ValueError; nbest > 8192, frame_tolerance outside 0 .. 64, and a combination of beam_size,
+    nbest and frame_tolerance whose open cells do not fit the LDS beside a frame's lattice set
+    (12 * P2(min(nbest, K) * (2 * frame_tolerance + 2)) bytes, see the header) are refused by the library (RuntimeError).
+
+    Results are bit-identical run to run and for any `max_work_bytes`; inputs, widening, caching, capture and the utterance
+    groups are those of `beam_decode_graph_confidence`, with min(nbest, K) * T * 28 bytes per utterance on top for the rows,
+    their cells and the cells' sums.
+    """
+    _check_beam(beam_size, beam_threshold)
+    if int(nbest) < 1:
+        raise ValueError("torch_asg_amd: nbest must be >= 1, got %d" % int(nbest))
+    with torch.no_grad():
+        return native().beam_decode_graph_nbest_confidence(*_plain(inputs, transition), graph, input_lengths, beam_size, nbest,
+                                                           beam_threshold, lm_weight, token_score, return_alignments,
+                                                           frame_tolerance, max_work_bytes)
+
+
 class GraphFullScore(torch.autograd.Function):
     """Full score of the ASG lattice composed with a token automaton, [B] (asg_graph_full_forward / _backward).  alpha is
     stored only when a gradient w.r.t. inputs or transition is needed."""
@@ -2039,6 +2124,14 @@ class ASGLoss(nn.Module):
         `torch_asg_amd.beam_decode_graph_nbest`."""
         return beam_decode_graph_nbest(inputs, self.transition, graph, input_lengths, beam_size, nbest, beam_threshold, lm_weight,
                                        token_score, return_alignments, max_work_bytes)
+
+    def beam_decode_graph_nbest_confidence(self, inputs, graph, input_lengths=None, beam_size=256, nbest=10,
+                                           beam_threshold=float("inf"), lm_weight=1.0, token_score=0.0, return_alignments=False,
+                                           frame_tolerance=0, max_work_bytes=1 << 30):
+        """The n best hypotheses under this criterion's transitions with the start frame and the lattice posterior of every
+        token of every row; see `torch_asg_amd.beam_decode_graph_nbest_confidence`."""
+        return beam_decode_graph_nbest_confidence(inputs, self.transition, graph, input_lengths, beam_size, nbest, beam_threshold,
+                                                  lm_weight, token_score, return_alignments, frame_tolerance, max_work_bytes)
 
     def beam_stream(self, graph, batch_size, max_frames, beam_size=256, beam_threshold=float("inf"), lm_weight=1.0,
                     token_score=0.0):

@@ -1450,6 +1450,57 @@ int asg_beam_graph_confidence(asg_ctx *ctx, const asg_problem *p, const asg_toke
                                  normalisers, (hipStream_t) stream)));
 }
 
+// The n-best token confidences: the checks of asg_beam_graph_confidence, then those of asg_beam_decode_graph_nbest.
+static int check_beam_nbest_conf(const asg_problem *p, const asg_token_graph_beam_loss *gl, int beam_size, int nbest) {
+    int rc = check_beam_conf(p, gl, beam_size);
+    if (rc) return rc;
+    if (nbest < 1) return ASG_ERR_INVALID;
+    if (nbest > kBeamMaxNbest) return ASG_ERR_UNSUPPORTED;
+    return ASG_OK;
+}
+
+size_t asg_beam_graph_nbest_confidence_work_bytes(const asg_problem *p, const asg_token_graph_beam_loss *gl, int beam_size,
+                                                  int nbest) {
+    if (check_beam_nbest_conf(p, gl, beam_size, nbest) != ASG_OK) return 0;
+    const asg_token_graph_beam *gb = gl->beam;
+    const int Q = (int) gb->graph->Q, K = beam_graph_k(Q, beam_size);
+    return beam_nbest_conf_work_bytes(p->dtype == ASG_DTYPE_F64 ? 8 : 4, (int) p->T, (int) p->B, Q, K,
+                                      beam_graph_cap(Q, K, gb->max_out, (int) gb->num_start), nbest);
+}
+
+// The order of the checks: the one-best confidence's, the n-best's, the tolerance and the limit of the row sink, then threshold,
+// buffers and workspace as everywhere.
+int asg_beam_graph_nbest_confidence(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam_loss *gl, int beam_size,
+                                    double beam_threshold, int nbest, int frame_tolerance, void *work, size_t work_bytes,
+                                    void *scores, void *emission_scores, void *graph_scores, int64_t *path, int64_t *tokens,
+                                    int64_t *token_lengths, int64_t *states, int64_t *num_hyps, int64_t *token_frames,
+                                    void *token_confidences, void *normalisers, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    int rc = check_beam_nbest_conf(p, gl, beam_size, nbest);
+    if (rc) return rc;
+    if (frame_tolerance < 0) return ASG_ERR_INVALID;
+    if (frame_tolerance > kBeamConfMaxTol) return ASG_ERR_UNSUPPORTED;
+    const int K = beam_graph_k((int) gl->beam->graph->Q, beam_size);
+    if (!beam_nbest_conf_fits(p->dtype == ASG_DTYPE_F64 ? 8 : 4, (int) p->T, K, nbest, frame_tolerance)) return ASG_ERR_UNSUPPORTED;
+    if (!(beam_threshold >= 0.0)) return ASG_ERR_INVALID;                  // negative or NaN
+    if (!work || !scores || !emission_scores || !graph_scores || !tokens || !token_lengths || !num_hyps || !token_frames ||
+        !token_confidences || !normalisers)
+        return ASG_ERR_INVALID;
+    if (work_bytes < asg_beam_graph_nbest_confidence_work_bytes(p, gl, beam_size, nbest)) return ASG_ERR_WORKSPACE;
+    const Problem P = to_problem(p);
+    const GraphArgs G = to_graph_args(gl->beam->graph);
+    const BeamGraphArgs BG = to_beam_graph_args(gl->beam);
+    BeamLossArgs L{};
+    L.S = (int) gl->S; L.start = gl->start; L.next = gl->next;
+    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
+    long long *nh = (long long *) num_hyps, *tf = (long long *) token_frames;
+    return hip_status(ASG_DISPATCH(p,
+        launch_beam_nbest_conf<float>(P, G, BG, L, K, beam_threshold, nbest, frame_tolerance, work, scores, emission_scores,
+                                      graph_scores, pa, tk, tl, st, nh, tf, token_confidences, normalisers, (hipStream_t) stream),
+        launch_beam_nbest_conf<double>(P, G, BG, L, K, beam_threshold, nbest, frame_tolerance, work, scores, emission_scores,
+                                       graph_scores, pa, tk, tl, st, nh, tf, token_confidences, normalisers, (hipStream_t) stream)));
+}
+
 static int check_beam_words_loss(const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm, int beam_size) {
     int rc = check_beam_words(p, gb, lm, beam_size);
     if (rc) return rc;

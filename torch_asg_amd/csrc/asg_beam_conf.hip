@@ -20,7 +20,8 @@
 //      that has its label, slot k mod 256 of a ring in LDS; a token that leaves the range is converted, stored and its slot
 //      zeroed.  Integer adds only, no float atomics: no order of arrival changes a bit.  Every output and every workspace word
 //      that is read is written by these kernels: no memset, no host synchronisation, the call captures and replays.
-// The pull is a sibling of beam_word_conf_pull (asg_beam_word_conf_pull.h), not that template over another lattice type: what an
+// The pull (asg_beam_conf_pull.h, a template over the sink: asg_beam_nbest_conf.hip compiles it with the rows' sink) is a
+// sibling of beam_word_conf_pull (asg_beam_word_conf_pull.h), not that template over another lattice type: what an
 // event is (every edge but the stay, named by the target's label, against a separator edge named by the source's word), the
 // final step (none here) and the step at frame 0 (none there) all differ; the sink, the ring and 2^54 are shared.
 #include "asg_common.h"
@@ -29,94 +30,13 @@
 #include "asg_beam_lattice.h"     // the helpers of the lattice pass: subgroup, find_sorted, the butterflies, to_fixed
 #include "asg_beam_token_lat.h"   // TokenLat: how a product state's edges are walked (shared with asg_beam_loss.hip)
 #include "asg_beam_conf_sink.h"   // HypSink, the ring and 2^54 (shared with asg_beam_word_conf.hip)
+#include "asg_beam_conf_pull.h"   // the beta pull over a sink (shared with asg_beam_nbest_conf.hip)
 
 namespace asg {
 
 namespace {
 
 static_assert(kBeamConfMaxTol == kBeamWordConfMaxTol, "the ring of HypSink is sized by the word call's tolerance");
-
-// The beta pull with the token-event sink.  nb [M] / nq [M]: the dynamic LDS in front of the sink's ring (bwd_front).
-template <typename R, typename Sink>
-__device__ __forceinline__ void beam_conf_pull(const Problem &P, const typename TokenLat<R>::Args &args, char *wb, size_t beta_off,
-                                               R Z, int len, int last, int *nq, R *nb, Sink &sink) {
-    using KeyT = int;
-    const int M = args.lay.M, tid = threadIdx.x, b = blockIdx.x;
-    const R NINF = Num<R>::ninf();
-    const KeyT *U = (const KeyT *) (wb + args.lay.U);
-    const int *nu = (const int *) (wb + args.lay.nu);
-    const R *A = (const R *) (wb + args.lay.A);
-    R *Bv = (R *) (wb + beta_off);                                             // [2][M]
-    const R *in = (const R *) P.inputs + (int64_t) b * P.is1;
-    const R *trm = (const R *) P.transition;
-    TokenLat<R> lat;
-    lat.bind(args);
-    auto tr = [&](int i, int j) -> R { return trm[(int64_t) i * P.ts0 + (int64_t) j * P.ts1]; };
-
-    int mt = nu[len - 1];
-    for (int x = tid; x < mt; x += kBL) {
-        const KeyT p = U[(int64_t) (len - 1) * M + x];
-        R e;
-        lat.end(p, e);
-        nq[x] = p;
-        nb[x] = e;
-    }
-    for (int t = len - 1; t >= 1; --t) {
-        __syncthreads();                                                       // nq, nb, the sink's LDS and the adds of frame t + 1
-        sink.window(t);
-        if constexpr (Sink::kBarrier) __syncthreads();
-        const bool open = sink.open();
-        const int mp = nu[t - 1];
-        const KeyT *Up = U + (int64_t) (t - 1) * M;
-        const R *Ap = A + (int64_t) (t - 1) * M;
-        R *Brow = Bv + (int64_t) ((t - 1) & 1) * M;
-        const R *xt = in + (int64_t) t * P.is0;
-        const int G = subgroup(mp), per = kBL / G;
-        for (int k0 = 0; k0 < mp; k0 += per) {
-            const int k = k0 + tid / G, lg = tid % G;
-            const bool act = k < mp;
-            const KeyT pp = act ? Up[k] : (KeyT) 0;
-            const int ip = act ? lat.label(pp) : 0;
-            // every surviving candidate out of pp that this lane owns: f(value, label of the target, is it an edge)
-            auto visit = [&](auto f) {
-                if (!act) return;
-                if (lg == 0) {
-                    const int pos = find_sorted(nq, mt, pp);
-                    if (pos >= 0) f((nb[pos] + tr(ip, ip)) + xt[(int64_t) ip * P.is2], ip, false);
-                }
-                lat.for_each_out(pp, lg, G, [&](KeyT tp, auto w, int i) {
-                    const int pos = find_sorted(nq, mt, tp);
-                    if (pos >= 0) f(((nb[pos] + tr(i, ip)) + w()) + xt[(int64_t) i * P.is2], i, true);
-                });
-            };
-            R mx = NINF;
-            visit([&](R c, int, bool) { mx = bmax(mx, c); });
-            mx = group_max(mx, G);
-            R s = R(0);
-            if (mx > NINF) {
-                const R a = Ap[k];
-                visit([&](R c, int i, bool edge) {
-                    s += bexp(c - mx);
-                    if (edge && open) sink.add(i, (a + c) - Z);
-                });
-            }
-            s = group_sum(s, G);
-            if (act && lg == 0) dev_store(Brow + k, mx > NINF ? mx + blog(s) : NINF);
-        }
-        __threadfence();
-        __syncthreads();
-        for (int x = tid; x < mp; x += kBL) { nq[x] = Up[x]; nb[x] = dev_load(Brow + x); }
-        mt = mp;
-    }
-    // frame 0: every state of U_0 starts a token with its label
-    __syncthreads();
-    sink.window(0);
-    if constexpr (Sink::kBarrier) __syncthreads();
-    if (sink.open())
-        for (int x = tid; x < mt; x += kBL) sink.add(lat.label(nq[x]), (A[x] + nb[x]) - Z);
-    __syncthreads();
-    sink.window(last);                                                         // every window is closed
-}
 
 inline size_t conf_lds(int elem, int M) { return bwd_front(elem, 4, M) + (size_t) kConfRing * 8; }
 
@@ -196,7 +116,7 @@ hipError_t launch_beam_conf(const Problem &P0, const GraphArgs &G, const BeamGra
     const int cap = beam_graph_cap(G.Q, K, BG.max_out, BG.num_start);
     const BeamConfLayout lay = beam_conf_layout(sizeof(R), P.T, G.Q, K, cap);
     hipError_t e = launch_beam_loss_lattice<R>(P, G, BG, L, lay.lat, K, theta, true, work, normalisers, scores, path, tokens, tlen,
-                                               states, stream);
+                                               states, 0, stream);
     if (e != hipSuccess) return e;
     const size_t dyn = conf_lds(sizeof(R), lay.lat.M);
     set_lds((const void *) beam_conf_bwd<R>, dyn);

@@ -1,0 +1,102 @@
+// torch_asg_amd/csrc/asg_beam_conf_pull.h -- the beta pull with a TOKEN-EVENT SINK, the text asg_beam_conf.hip (confidences of the
+// one best) and asg_beam_nbest_conf.hip (of every row of the n-best list, 5aa) both compile: beam_loss_bwd's pull
+// through TokenLat<R> (one 1024-thread workgroup per utterance, frames len-1 .. 1, U_{t+1} with its beta in LDS, G lanes per
+// source state, a max pass and a sum pass) without label posteriors, (i, j) tile and transition gradient.  The sum pass forms the
+// posterior exp((alpha[t-1][p] + c) - Z_K) of every edge that is NOT the stay -- the event "a token with the label of the edge's
+// target starts at frame t" -- and, behind the last frame of the loop, exp((alpha[0][q] + beta[0][q]) - Z_K) of every state of
+// U_0, and hands each to the sink.  The adds and their order do not depend on the sink: beta and every event's value are the
+// same bits under both.  A Sink is what asg_beam_word_conf_pull.h says it is, with "label" for "word": HypSink
+// (asg_beam_conf_sink.h) or RowSink (asg_beam_row_sink.h).
+#pragma once
+#include "asg_beam_lattice.h"     // the helpers of the lattice pass: subgroup, find_sorted, the butterflies, to_fixed
+#include "asg_beam_token_lat.h"   // TokenLat: how a product state's edges are walked (shared with asg_beam_loss.hip)
+
+namespace asg {
+
+namespace {
+
+// The beta pull with the token-event sink.  nb [M] / nq [M]: the dynamic LDS in front of the sink's ring (bwd_front).
+template <typename R, typename Sink>
+__device__ __forceinline__ void beam_conf_pull(const Problem &P, const typename TokenLat<R>::Args &args, char *wb, size_t beta_off,
+                                               R Z, int len, int last, int *nq, R *nb, Sink &sink) {
+    using KeyT = int;
+    const int M = args.lay.M, tid = threadIdx.x, b = blockIdx.x;
+    const R NINF = Num<R>::ninf();
+    const KeyT *U = (const KeyT *) (wb + args.lay.U);
+    const int *nu = (const int *) (wb + args.lay.nu);
+    const R *A = (const R *) (wb + args.lay.A);
+    R *Bv = (R *) (wb + beta_off);                                             // [2][M]
+    const R *in = (const R *) P.inputs + (int64_t) b * P.is1;
+    const R *trm = (const R *) P.transition;
+    TokenLat<R> lat;
+    lat.bind(args);
+    auto tr = [&](int i, int j) -> R { return trm[(int64_t) i * P.ts0 + (int64_t) j * P.ts1]; };
+
+    int mt = nu[len - 1];
+    for (int x = tid; x < mt; x += kBL) {
+        const KeyT p = U[(int64_t) (len - 1) * M + x];
+        R e;
+        lat.end(p, e);
+        nq[x] = p;
+        nb[x] = e;
+    }
+    for (int t = len - 1; t >= 1; --t) {
+        __syncthreads();                                                       // nq, nb, the sink's LDS and the adds of frame t + 1
+        sink.window(t);
+        if constexpr (Sink::kBarrier) __syncthreads();
+        const bool open = sink.open();
+        const int mp = nu[t - 1];
+        const KeyT *Up = U + (int64_t) (t - 1) * M;
+        const R *Ap = A + (int64_t) (t - 1) * M;
+        R *Brow = Bv + (int64_t) ((t - 1) & 1) * M;
+        const R *xt = in + (int64_t) t * P.is0;
+        const int G = subgroup(mp), per = kBL / G;
+        for (int k0 = 0; k0 < mp; k0 += per) {
+            const int k = k0 + tid / G, lg = tid % G;
+            const bool act = k < mp;
+            const KeyT pp = act ? Up[k] : (KeyT) 0;
+            const int ip = act ? lat.label(pp) : 0;
+            // every surviving candidate out of pp that this lane owns: f(value, label of the target, is it an edge)
+            auto visit = [&](auto f) {
+                if (!act) return;
+                if (lg == 0) {
+                    const int pos = find_sorted(nq, mt, pp);
+                    if (pos >= 0) f((nb[pos] + tr(ip, ip)) + xt[(int64_t) ip * P.is2], ip, false);
+                }
+                lat.for_each_out(pp, lg, G, [&](KeyT tp, auto w, int i) {
+                    const int pos = find_sorted(nq, mt, tp);
+                    if (pos >= 0) f(((nb[pos] + tr(i, ip)) + w()) + xt[(int64_t) i * P.is2], i, true);
+                });
+            };
+            R mx = NINF;
+            visit([&](R c, int, bool) { mx = bmax(mx, c); });
+            mx = group_max(mx, G);
+            R s = R(0);
+            if (mx > NINF) {
+                const R a = Ap[k];
+                visit([&](R c, int i, bool edge) {
+                    s += bexp(c - mx);
+                    if (edge && open) sink.add(i, (a + c) - Z);
+                });
+            }
+            s = group_sum(s, G);
+            if (act && lg == 0) dev_store(Brow + k, mx > NINF ? mx + blog(s) : NINF);
+        }
+        __threadfence();
+        __syncthreads();
+        for (int x = tid; x < mp; x += kBL) { nq[x] = Up[x]; nb[x] = dev_load(Brow + x); }
+        mt = mp;
+    }
+    // frame 0: every state of U_0 starts a token with its label
+    __syncthreads();
+    sink.window(0);
+    if constexpr (Sink::kBarrier) __syncthreads();
+    if (sink.open())
+        for (int x = tid; x < mt; x += kBL) sink.add(lat.label(nq[x]), (A[x] + nb[x]) - Z);
+    __syncthreads();
+    sink.window(last);                                                         // every window is closed
+}
+
+}  // namespace
+
+}  // namespace asg

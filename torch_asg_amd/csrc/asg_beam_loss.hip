@@ -232,15 +232,16 @@ bool beam_loss_fits(int elem, int M, int N) {
 }
 
 // The forward's launches behind a layout the caller made: `lay.per` may be wider than beam_loss_layout's (a caller with parts of
-// its own behind the layout -- asg_beam_conf.hip), and the five outputs of the search go where the caller says.
+// its own behind the layout -- asg_beam_conf.hip), and the five outputs of the search go where the caller says.  fin_off != 0: the
+// search also leaves its last set there (launch_beam_graph's fin_off), for an n-best stage behind it (asg_beam_nbest_conf.hip).
 template <typename R>
 hipError_t launch_beam_loss_lattice(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const BeamLossArgs &L,
                                     const BeamLossLayout &lay, int K, double theta, bool store, void *work, void *scores,
                                     void *beam_scores, long long *path, long long *tokens, long long *tlen, long long *states,
-                                    hipStream_t stream) {
+                                    size_t fin_off, hipStream_t stream) {
     const int B = P.B;
     char *w = (char *) work;
-    hipError_t e = launch_beam_graph<R>(P, G, BG, K, theta, work, beam_scores, path, tokens, tlen, states, stream, lay.per, lay.cnt);
+    hipError_t e = launch_beam_graph<R>(P, G, BG, K, theta, work, beam_scores, path, tokens, tlen, states, stream, lay.per, lay.cnt, fin_off);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(beam_loss_targets, dim3(B), dim3(kBS), 0, stream, P, G, L, lay, w);
     hipLaunchKernelGGL((beam_loss_accept<R>), dim3((B + 63) / 64), dim3(64), 0, stream, G, lay, w, B);
@@ -263,7 +264,7 @@ hipError_t launch_beam_loss_forward(const Problem &P, const GraphArgs &G, const 
     long long *btl = (long long *) (tail + a256((size_t) B * 8));
     long long *bpa = (long long *) (tail + 2 * a256((size_t) B * 8));
     return launch_beam_loss_lattice<R>(P, G, BG, L, lay, K, theta, store, work, scores, tail, bpa, bpa + (size_t) B * T, btl,
-                                       bpa + 2 * (size_t) B * T, stream);
+                                       bpa + 2 * (size_t) B * T, 0, stream);
 }
 
 template <typename R>
@@ -285,7 +286,7 @@ template hipError_t launch_beam_loss_forward<double>(const Problem &, const Grap
     template hipError_t launch_beam_loss_lattice<R>(const Problem &, const GraphArgs &, const BeamGraphArgs &,                 \
                                                     const BeamLossArgs &, const BeamLossLayout &, int, double, bool, void *,    \
                                                     void *, void *, long long *, long long *, long long *, long long *,        \
-                                                    hipStream_t);
+                                                    size_t, hipStream_t);
 ASG_BEAM_LOSS_LATTICE_INST(float)
 ASG_BEAM_LOSS_LATTICE_INST(double)
 #undef ASG_BEAM_LOSS_LATTICE_INST

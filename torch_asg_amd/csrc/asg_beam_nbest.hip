@@ -218,6 +218,17 @@ hipError_t launch_beam_nbest(const Problem &P, const GraphArgs &G, const BeamGra
     hipError_t e = launch_beam_graph<R>(P, G, BG, K, theta, work, bsc, bpa, bpa + (size_t) B * T, btl, bpa + 2 * (size_t) B * T,
                                         stream, lay.per, 0, lay.fin);
     if (e != hipSuccess) return e;
+    return launch_beam_nbest_over<R>(P, G, BG, lay, K, nbest, work, scores, emission_scores, graph_scores, path, tokens, tlen, states,
+                                     num_hyps, stream);
+}
+
+template <typename R>
+hipError_t launch_beam_nbest_over(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const BeamNbestLayout &lay, int K,
+                                  int nbest, void *work, void *scores, void *emission_scores, void *graph_scores, long long *path,
+                                  long long *tokens, long long *tlen, long long *states, long long *num_hyps, hipStream_t stream) {
+    const int B = P.B;
+    const int cap = beam_graph_cap(G.Q, K, BG.max_out, BG.num_start);
+    char *w = (char *) work;
     int P2 = 1;
     while (P2 < K) P2 *= 2;
     const size_t dyn = (size_t) P2 * (8 + sizeof(typename Key<R>::U));
@@ -234,5 +245,12 @@ template hipError_t launch_beam_nbest<float>(const Problem &, const GraphArgs &,
 template hipError_t launch_beam_nbest<double>(const Problem &, const GraphArgs &, const BeamGraphArgs &, int, double, int, void *,
                                               void *, void *, void *, long long *, long long *, long long *, long long *,
                                               long long *, hipStream_t);
+#define ASG_BEAM_NBEST_OVER_INST(R)                                                                                            \
+    template hipError_t launch_beam_nbest_over<R>(const Problem &, const GraphArgs &, const BeamGraphArgs &,                     \
+                                                  const BeamNbestLayout &, int, int, void *, void *, void *, void *, long long *, \
+                                                  long long *, long long *, long long *, long long *, hipStream_t);
+ASG_BEAM_NBEST_OVER_INST(float)
+ASG_BEAM_NBEST_OVER_INST(double)
+#undef ASG_BEAM_NBEST_OVER_INST
 
 }  // namespace asg

@@ -29,35 +29,15 @@
 #include "asg_beam_lattice.h"     // subgroup, find_sorted, the butterflies, to_fixed, bwd_front
 #include "asg_beam_word_lat.h"    // WordLat: how a pair's edges are walked
 #include "asg_beam_word_conf_pull.h"  // the beta pull and 2^54, shared with asg_beam_word_conf.hip
+#include "asg_beam_row_sink.h"        // sort_u64, RowSink: shared with asg_beam_nbest_conf.hip
 
 namespace asg {
 
 namespace {
 
-constexpr int kNP = 1024;                                     // prep / fill workgroup
-constexpr int kSinkFixed = 1024;                              // window offsets int32 [2 * 64 + 2], then the filter u32 [8]
-constexpr int kSinkFiltOff = 768;
-static_assert((2 * kBeamWordConfMaxTol + 2) * 4 <= kSinkFiltOff && kSinkFiltOff + 32 <= kSinkFixed, "sink head");
-
 // behind the utterances: what the one-best search writes (scores [B], token and word lengths [B], path / tokens / states /
 // lm_states / words / word_frames [6][B][T])
 inline size_t tail_bytes(int T, int B) { return 3 * a256((size_t) B * 8) + a256((size_t) 6 * B * T * 8); }
-
-// ascending bitonic network over v[0 .. P2), LDS or workspace (the workgroup's own stores are visible to it behind a barrier)
-__device__ void sort_u64(unsigned long long *v, int P2) {
-    for (int k = 2; k <= P2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int x = threadIdx.x; x < P2; x += kNP) {
-                const int y = x ^ j;
-                if (y > x) {
-                    const unsigned long long a = v[x], c = v[y];
-                    if ((a > c) == ((x & k) == 0)) { v[x] = c; v[y] = a; }
-                }
-            }
-            __threadfence_block();
-            __syncthreads();
-        }
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // 3: word_frames of every row, the queries, the cells.
@@ -132,98 +112,13 @@ __global__ void __launch_bounds__(kNP) nbest_conf_prep(const int64_t *in_len, co
     __threadfence_block();
     __syncthreads();
     if (nq > 1) sort_u64(v, P2);
-    // ---- the distinct queries, in order: a ballot per wavefront, the wavefronts' counts through LDS, strips of 1024
-    if (tid == 0) run_s = 0;
-    __syncthreads();
-    for (int x0 = 0; x0 < nq; x0 += kNP) {
-        const int x = x0 + tid;
-        const unsigned long long me = x < nq ? v[x] : ~0ull;
-        const bool head = x < nq && me != ~0ull && (x == 0 || v[x - 1] != me);
-        const unsigned long long m = __ballot(head);
-        if (lane == 0) wsum[wave] = __popcll(m);
-        __syncthreads();
-        int pre = run_s;
-        for (int s = 0; s < wave; ++s) pre += wsum[s];
-        if (head) cells[pre + __popcll(m & ((1ull << lane) - 1ull))] = me;
-        __syncthreads();
-        if (tid == kNP - 1) run_s = pre + __popcll(m);
-        __syncthreads();
-    }
-    __threadfence_block();
-    __syncthreads();
-    const int nc = run_s;
-    if (tid == 0) hdr[0] = nc;
-    // ---- the first cell of every frame 0 .. T + 1 (cells live at frames 1 .. len)
-    for (int u = tid; u < T + 2; u += kNP) {
-        const unsigned long long key = (unsigned long long) u << 32;
-        int lo = 0, hi = nc;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (cells[mid] < key) lo = mid + 1; else hi = mid;
-        }
-        foff[u] = lo;
-    }
+#include "asg_beam_cells.inc"   // the cells and the first cell of every frame 0 .. T + 1
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // 7: beta with the row sink.  Dynamic LDS: [nq u64 M][nb R M][pad to 16][fo int32, filter: 1024 bytes][ring u64][mirror int32].
 // The pull is asg_beam_word_conf_pull.h's, the text beam_word_conf_bwd compiles.
 // ---------------------------------------------------------------------------------------------------------------------
-// The row sink: the cells of EVERY row in (frame, word) order.  The cells whose window holds the frame the workgroup stands at
-// are [ca, cb), the cells of nfr frames, the same in every thread; a cell's accumulator is slot (cell index & ring_mask) of the
-// ring, its word sits in the same slot of the mirror mw, and fo holds the first cell of each open frame.
-struct RowSink {
-    static constexpr bool kBarrier = true;
-    const int *foff;
-    const unsigned long long *cells;
-    unsigned long long *acc, *ring;
-    int *mw, *fo;
-    const unsigned *filt;
-    int tol, T, ring_mask, ca, cb, nfr;
-    // moves the range to frame t (frames descend), stores the cells that leave it -- no later event can reach them -- and
-    // mirrors the words of those that enter
-    __device__ __forceinline__ void window(int t) {
-        const int tid = threadIdx.x;
-        const int lo = t - tol < 0 ? 0 : (t - tol > T + 1 ? T + 1 : t - tol);
-        const int hi = t + tol + 1 < 0 ? 0 : (t + tol + 1 > T + 1 ? T + 1 : t + tol + 1);
-        const int nca = foff[lo], ncb = foff[hi];
-        for (int c = ncb + tid; c < cb; c += kBL) {
-            unsigned long long &slot = ring[c & ring_mask];
-            acc[c] = slot;
-            slot = 0ull;
-        }
-        for (int c = nca + tid; c < ca; c += kBL) mw[c & ring_mask] = (int) (unsigned) cells[c];
-        nfr = hi - lo;
-        for (int j = tid; j <= nfr; j += kBL) fo[j] = foff[lo + j];
-        ca = nca;
-        cb = ncb;
-    }
-    __device__ __forceinline__ bool open() const { return ca < cb; }
-    // word w completed with posterior exp(x) at the frame the window stands at.  Within a frame the cells ascend in their
-    // word, and a frame holds a word once: a binary search per open frame.
-    template <typename R>
-    __device__ __forceinline__ void add(int w, R x) {
-        if (!((filt[((unsigned) w & 255u) >> 5] >> ((unsigned) w & 31u)) & 1u)) return;
-        unsigned long long fx = 0ull;
-        bool have = false;
-        for (int j = 0; j < nfr; ++j) {
-            int lo = fo[j];
-            const int e1 = fo[j + 1];
-            int hi = e1;
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (mw[mid & ring_mask] < w) lo = mid + 1; else hi = mid;
-            }
-            if (lo < e1 && mw[lo & ring_mask] == w) {
-                if (!have) { fx = to_fixed((double) bexp(x), kConfScale); have = true; }
-                if (fx) atomicAdd(&ring[lo & ring_mask], fx);
-            }
-        }
-    }
-};
-
-inline size_t sink_lds(int elem, int M, size_t ring) { return bwd_front(elem, 8, M) + kSinkFixed + ring * 12; }
-
 template <typename R>
 __global__ void __launch_bounds__(kBL) nbest_conf_bwd(Problem P, typename WordLat<R>::Args args, char *work, size_t beta_off,
                                                       size_t hdr_off, size_t foff_off, size_t cells_off, size_t acc_off,
@@ -292,18 +187,12 @@ __global__ void __launch_bounds__(kNP) nbest_conf_fill(const int64_t *in_len, in
     }
 }
 
-size_t p2_size(size_t n) {
-    size_t r = 2;
-    while (r < n) r *= 2;
-    return r;
-}
-
 }  // namespace
 
 bool beam_word_nbest_conf_fits(int elem, int T, int K, int nbest, int tol) {
     const size_t nb = (size_t) (nbest < K ? nbest : K);
     if (nb * (size_t) T > ((size_t) 1 << 30)) return false;
-    return sink_lds(elem, K, beam_word_nbest_conf_ring(K, nbest, tol)) <= kBLLds;
+    return sink_lds(elem, 8, K, beam_word_nbest_conf_ring(K, nbest, tol)) <= kBLLds;
 }
 
 BeamWordNbestConfLayout beam_word_nbest_conf_layout(int elem, int T, int K, int cap, int nbest) {
@@ -363,7 +252,7 @@ hipError_t launch_beam_word_nbest_conf(const Problem &P0, const GraphArgs &G, co
     e = launch_beam_word_loss_lattice<R>(P, G, BG, LM, lay.conf.lat, K, true, work, normalisers, stream);
     if (e != hipSuccess) return e;
     const size_t ring = beam_word_nbest_conf_ring(K, nbest, tol);
-    const size_t dyn = sink_lds(sizeof(R), lay.conf.lat.M, ring);
+    const size_t dyn = sink_lds(sizeof(R), 8, lay.conf.lat.M, ring);
     set_lds((const void *) nbest_conf_bwd<R>, dyn);
     hipLaunchKernelGGL((nbest_conf_bwd<R>), dim3(B), dim3(kBL), dyn, stream, P, typename WordLat<R>::Args{G, BG, LM, lay.conf.lat}, w,
                        lay.conf.beta, lay.hdr, lay.foff, lay.cells, lay.acc, (const R *) normalisers, tol, (int) (ring - 1));

@@ -388,6 +388,13 @@ template <typename R>
 hipError_t launch_beam_nbest(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, int K, double theta, int nbest,
                              void *work, void *scores, void *emission_scores, void *graph_scores, long long *path,
                              long long *tokens, long long *tlen, long long *states, long long *num_hyps, hipStream_t stream);
+// the n-best kernel alone over what a search left in blocks of `lay` (any `lay.per`, with the search's own layout at the front
+// of a block, its last set at lay.fin and room for the [T][nb] rows at lay.rows): behind the decoder's search in
+// launch_beam_nbest, behind the lattice's search in asg_beam_nbest_conf.hip
+template <typename R>
+hipError_t launch_beam_nbest_over(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const BeamNbestLayout &lay, int K,
+                                  int nbest, void *work, void *scores, void *emission_scores, void *graph_scores, long long *path,
+                                  long long *tokens, long long *tlen, long long *states, long long *num_hyps, hipStream_t stream);
 
 // ---- Beam-pruned full score and gradients over the same composed lattice (asg_beam_loss.hip): asg_beam_graph_full_*.
 struct BeamLossArgs {
@@ -407,6 +414,8 @@ BeamLossLayout beam_loss_layout(int elem, int T, int Q, int K, int cap, int nf, 
 size_t beam_loss_work_bytes(int elem, int T, int B, int Q, int K, int cap, int nf, bool store);
 size_t beam_loss_scratch_per(int elem, int M, int N);
 bool beam_loss_fits(int elem, int M, int N);
+// behind the utterances: what the search returns besides its sets (scores [B], lengths [B], path / tokens / states [3][B][T])
+size_t beam_loss_tail_bytes(int T, int B);
 template <typename R>
 hipError_t launch_beam_loss_forward(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const BeamLossArgs &L, int K,
                                     double theta, bool store, void *work, void *scores, hipStream_t stream);
@@ -416,12 +425,13 @@ hipError_t launch_beam_loss_backward(const Problem &P, const GraphArgs &G, const
                                      void *scratch, bool accumulate, hipStream_t stream);
 
 // launches 1 - 4 of that forward behind a layout the caller made (`lay.per` may be wider than beam_loss_layout's: a caller with
-// parts of its own behind an utterance's block), the search writing its five outputs where the caller says
+// parts of its own behind an utterance's block), the search writing its five outputs where the caller says; fin_off is
+// launch_beam_graph's (0: the last set is not left)
 template <typename R>
 hipError_t launch_beam_loss_lattice(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const BeamLossArgs &L,
                                     const BeamLossLayout &lay, int K, double theta, bool store, void *work, void *scores,
                                     void *beam_scores, long long *path, long long *tokens, long long *tlen, long long *states,
-                                    hipStream_t stream);
+                                    size_t fin_off, hipStream_t stream);
 
 // ---- Token confidences and start frames from the lattice of that search (asg_beam_conf.hip): asg_beam_graph_confidence.  One
 // utterance's workspace: the beam-pruned loss's layout without targets with alpha stored for all frames (M = K), then two rows
@@ -437,6 +447,32 @@ template <typename R>
 hipError_t launch_beam_conf(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const BeamLossArgs &L, int K, double theta,
                             int tol, void *work, void *scores, long long *path, long long *tokens, long long *tlen,
                             long long *states, long long *token_frames, void *token_conf, void *normalisers, hipStream_t stream);
+
+// ---- Token confidences and start frames for every row of the n-best list (asg_beam_nbest_conf.hip):
+// asg_beam_graph_nbest_confidence.  One utterance's workspace: asg_beam_graph_confidence's layout at the front (the search's
+// [T][K] rows first), then (byte offsets, each part 256-byte aligned) fin and rows as in BeamNbestLayout, hdr (int32 number of
+// cells), foff (int32 [T + 2]: the first cell of every frame), qk (u64 [P2(nb * T)]: the rows' (frame, label) queries, sorted
+// there when they pass the LDS), cells (u64 [nb * T]: the distinct queries, ascending) and acc (u64 [nb * T]: a cell's fixed-point
+// sum).  Behind the utterances: what the one-best search returns (beam_loss_tail_bytes).
+struct BeamNbestConfLayout {
+    BeamConfLayout conf;         // conf.lat.per and conf.per are this layout's `per`
+    BeamNbestLayout nbest;       // fin, rows, nb; nbest.per is this layout's `per`
+    size_t hdr, foff, qk, cells, acc, per;
+    size_t qcap;                 // P2(nb * T)
+    int nb;
+};
+// THE new limit: bwd_front + ring (u64) + mirror (int32) + window offsets and filter (1024 bytes) within 160 KiB of LDS, the
+// ring beam_word_nbest_conf_ring's (the power of two >= min(nbest, K) * (2 tol + 2)), and nb * T <= 2^30.
+bool beam_nbest_conf_fits(int elem, int T, int K, int nbest, int tol);
+BeamNbestConfLayout beam_nbest_conf_layout(int elem, int T, int Q, int K, int cap, int nbest);
+size_t beam_nbest_conf_work_bytes(int elem, int T, int B, int Q, int K, int cap, int nbest);
+// path / states may be null (then they are not written)
+template <typename R>
+hipError_t launch_beam_nbest_conf(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const BeamLossArgs &L, int K,
+                                  double theta, int nbest, int tol, void *work, void *scores, void *emission_scores,
+                                  void *graph_scores, long long *path, long long *tokens, long long *tlen, long long *states,
+                                  long long *num_hyps, long long *token_frames, void *token_conf, void *normalisers,
+                                  hipStream_t stream);
 
 // ---- Beam-pruned full score and gradients over the pairs of the word decoder (asg_beam_word_loss.hip): asg_beam_words_full_*.
 // One utterance's workspace: the word decoder's own layout at the front (bq, bh: its [T][K] lists), then (byte offsets, each part
