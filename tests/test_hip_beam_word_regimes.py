@@ -17,7 +17,10 @@ assert_close in float32 with the infinity pattern exact.
 
 Out of scope: pairs wider than 37 bits (they need a lexicon or an LM too large for a test), chains deeper than 64 passed
 through the C API, the separate LDS layout of the n-best kernel, and the losses at K = 8192 (their own bound on the lattice set,
-tests/test_hip_beam_word_loss.py::test_both_sides_of_the_bound_on_the_lattice_set, is below it)."""
+tests/test_hip_beam_word_loss.py::test_both_sides_of_the_bound_on_the_lattice_set, is below it).
+
+The two confidence entry points, `beam_decode_words_confidence` and `beam_decode_words_nbest_confidence`, have these sizes in
+tests/test_hip_beam_word_conf_regimes.py."""
 import numpy as np
 import pytest
 import torch
