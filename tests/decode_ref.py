@@ -24,9 +24,11 @@ def _frame(v, tr):
     return out
 
 
-def decode_ref(inputs, transition, input_lengths=None):
+def decode_ref(inputs, transition, input_lengths=None, argmax=np.argmax):
     """inputs [T,B,N], transition [N,N] (tr[i][j] = score of j -> i), input_lengths [B] or None.
-    -> scores [B] (dtype of inputs), path [B,T] int64, tokens [B,T] int64, token_lengths [B] int64."""
+    -> scores [B] (dtype of inputs), path [B,T] int64, tokens [B,T] int64, token_lengths [B] int64.
+    argmax(vector) -> index: the default is the kernels' first index of the max.  Tests pass another rule only to build WRONG
+    variants and show that their inputs tell the two apart."""
     x = np.asarray(inputs)
     T, B, N = x.shape
     dt = x.dtype
@@ -51,10 +53,10 @@ def decode_ref(inputs, transition, input_lengths=None):
         if not best > -np.inf:                      # no finite path (NaN is unspecified)
             continue
         scores[b] = best
-        s = int(np.argmax(last))                    # first index of the max
+        s = int(argmax(last))                       # first index of the max
         path[b, L - 1] = s
         for t in range(L - 1, 0, -1):
-            s = int(np.argmax(vs[t - 1][b] + tr[s]))
+            s = int(argmax(vs[t - 1][b] + tr[s]))
             path[b, t - 1] = s
         p = path[b, :L]
         keep = np.ones(L, bool)

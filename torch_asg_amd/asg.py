@@ -327,7 +327,8 @@ class HipBackend:
             work = self._buf(int(L.asg_viterbi_work_bytes(ctypes.byref(p))), inputs.device)
             scores = torch.empty(B, dtype=inputs.dtype, device=inputs.device)
             path = torch.empty(B, T, dtype=torch.int64, device=inputs.device)
-            _lib.check(L.asg_viterbi(self._context(inputs.device), ctypes.byref(p), work.data_ptr(), work.numel(),
+            # (no context: asg_viterbi ignores it and runs on one stream; nothing is created here, so it may run under capture)
+            _lib.check(L.asg_viterbi(None, ctypes.byref(p), work.data_ptr(), work.numel(),
                                      scores.data_ptr(), path.data_ptr(), 0, self._stream(inputs.device)),
                        "asg_viterbi")
         return scores, path
@@ -1275,7 +1276,9 @@ def viterbi_align(inputs, targets, transition, input_lengths=None, target_length
     force-aligned lattice of the loss (force_aligned_lattice.cpp:84-111) with max instead of logsumexp
     (doc/tech_report.tex:84-88; a TODO in the reference, README.md:33).  No gradient.
 
-    inputs [T,B,N] (time-major emissions), targets [B,S] int64, transition [N,N], lengths int64 [B] or None.
+    inputs [T,B,N] (time-major emissions), targets [B,S] int64, transition [N,N], lengths int64 [B] or None.  float16 /
+    bfloat16 emissions are widened to the dtype of `transition` first, as the decoders do (so the tokens of `viterbi_decode`
+    align against the emissions they were decoded from); the scores then have the dtype of `transition`.
     Returns (scores [B], positions [B,T] int64, labels [B,T] int64): the score of the best alignment, the target
     position occupied at every frame and the label emitted there; -1 for frames >= input_lengths[b] and for
     utterances that have no finite alignment (score -inf).  Same defaults and S > T truncation as ASGLoss.forward.
@@ -1290,7 +1293,8 @@ def viterbi_align(inputs, targets, transition, input_lengths=None, target_length
         targets = targets[:, :T]
         target_lengths = torch.clamp(target_lengths, max=T)
     with torch.no_grad():
-        scores, pos = native().viterbi(inputs.detach(), targets, transition.detach(), input_lengths, target_lengths)
+        inputs, transition = _plain(inputs, transition)
+        scores, pos = native().viterbi(inputs, targets, transition, input_lengths, target_lengths)
         labels = torch.where(pos >= 0, torch.gather(targets.to(pos.device), 1, pos.clamp(min=0)), pos)
     return scores, pos, labels
 
