@@ -409,6 +409,62 @@ int asg_beam_window_result(asg_ctx *ctx, const asg_token_graph_beam *gb, int64_t
                            int64_t *token_lengths, int64_t *states, int64_t *frames, int64_t *committed, int64_t *status, int flags,
                            void *stream);
 
+/* ---- The N BEST hypotheses of the two streams above: asg_beam_decode_graph_nbest's list from a stream state or a window stream
+ * state, which the call only reads -- the same kernel, pointed at the stored set and at the rows the state keeps -- so that a
+ * service that rescores the final list needs neither the emissions nor a second search.  Throughout K = min(beam_size, max(Q, 1))
+ * and nb = min(nbest, K).  No counterpart in the reference.
+ * asg_beam_stream_nbest.  With L = pos and A = A_{L-1} with values v: the candidates and their order are those of
+ *   asg_beam_stream_result -- end[q] = v[q] + final_w[q] (final != 0) or v[q] (final == 0, the n best PREFIXES), end > -inf,
+ *   descending, q ascending on a tie, -0 equal to +0.  num_hyps [B] = min(nbest, candidates).  Row r < num_hyps: scores [B][nbest]
+ *   (dtype) = the candidate's end; path / states int64 [B][nbest][max_frames] follow its back-pointers (either may be NULL: not
+ *   written); tokens [B][nbest][max_frames] and token_lengths [B][nbest] the collapse of its path; graph_scores [B][nbest] by
+ *   asg_beam_decode_graph_nbest's rule -- start_w of the first state, plus the weight of every edge taken, in frame order, plus
+ *   final_w of the last state, WITHOUT that final weight when final == 0.  Padding as there: rows >= num_hyps have scores and
+ *   graph_scores -inf, token_lengths 0 and every wide column -1; columns behind the data are -1.  frames [B] = L and status [B] =
+ *   the overflow word, as asg_beam_stream_result writes them.  Row 0 equals asg_beam_stream_result(final) bit for bit.
+ *   REQUIRED PROPERTY: for any chunking of x[0:L], L <= max_frames, the final != 0 outputs equal asg_beam_decode_graph_nbest's on
+ *   x (T >= L frames, input_length = L, the same arguments) bit for bit -- scores, graph_scores, token_lengths, num_hyps; path,
+ *   tokens and states on that call's columns and -1 beyond.  The same adds in the same order: no tolerance.
+ *   There is no emission_scores: the state keeps no emissions.  A caller who kept the frames has the one-shot call; the others
+ *   have scores - graph_scores, which is it up to rounding.
+ *   `work` (asg_beam_stream_nbest_work_bytes): B * (max_frames*nb*4 rounded up to 256) bytes; its contents mean nothing between
+ *   calls.
+ * asg_beam_window_nbest.  The candidates, their order, num_hyps and scores are asg_beam_stream_nbest's at equal pos, bit for bit
+ *   (the window's property 1, for every row).  Row r holds the candidate's TAIL: path / states int64 [B][nbest][W] (either may be
+ *   NULL) are the frames base .. pos-1 on ITS OWN chain of back-pointers, column t = frame base + t, walked through the ring in at
+ *   most W steps; tokens [B][nbest][W] is the collapse of the tail started from carry -- a first tail label equal to carry is no
+ *   token -- and token_lengths its count.  The tail may be empty (base == pos, after a commit up to the last frame): the row still
+ *   counts, with its score, token_lengths 0 and -1 everywhere.  frames = pos, committed = base and status (bit 0: a forced commit
+ *   has happened, bit 1: pos >= 1 and the set is empty) as asg_beam_window_result writes them.  Padding as above.
+ *   REQUIRED PROPERTY, while status bit 0 is clear: for EVERY row, everything advance has committed followed by the row's tail
+ *   equals the row of asg_beam_stream_nbest at equal pos, for path, states and tokens.  Why: a convergence commit stops at a frame
+ *   c at which every survivor of that moment has the same ancestor, so the committed chain is an ancestor chain of every survivor
+ *   of that frame, and every later survivor descends from one of those -- each row's full chain begins with exactly what was
+ *   committed.  With bit 0 set some frames were committed along the best hypothesis of the moment only; the rows are then still
+ *   exactly the chains specified above (deterministic, the same for every chunking), but need not continue the committed prefix.
+ *   There is no graph_scores: the edge into frame `base` needs the product state of frame base-1, whose row the ring may
+ *   already have overwritten, and the header keeps only its label (carry).  The window state is not widened for it.
+ *   `work` (asg_beam_window_nbest_work_bytes): B * (W*nb*4 rounded up to 256) bytes.
+ * Each call is ONE launch on `stream`, one 1024-thread workgroup per slot: no host synchronisation, no copy, no memset -- every
+ * output element and every scratch word that is read is written by the kernel -- so a captured call replays.  One integer LDS
+ * counter, no atomics on values: bit-identical run to run.  LDS: P2(K) * (8 + e) bytes, P2 the power of two >= K.  Errors: those
+ * of asg_beam_stream_result / asg_beam_window_result; nbest < 1: ASG_ERR_INVALID; nbest > 8192: ASG_ERR_UNSUPPORTED; a `work`
+ * smaller than *_work_bytes: ASG_ERR_WORKSPACE; NULL state, work, scores, graph_scores, tokens, token_lengths, num_hyps, frames,
+ * committed or status: ASG_ERR_INVALID.  *_work_bytes returns 0 for arguments the call refuses.  `flags` is reserved (pass 0).
+ * Not here: emission_scores from a stream, graph_scores from the window, confidences from any stream, the two word windows. */
+size_t asg_beam_stream_nbest_work_bytes(const asg_token_graph_beam *gb, int64_t B, int dtype, int beam_size, int64_t max_frames,
+                                        int nbest);
+int asg_beam_stream_nbest(asg_ctx *ctx, const asg_token_graph_beam *gb, int64_t B, int beam_size, int64_t max_frames,
+                          const void *state, size_t state_bytes, int final, int nbest, void *work, size_t work_bytes, void *scores,
+                          void *graph_scores, int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states,
+                          int64_t *num_hyps, int64_t *frames, int64_t *status, int flags, void *stream);
+size_t asg_beam_window_nbest_work_bytes(const asg_token_graph_beam *gb, int64_t B, int dtype, int beam_size, int64_t W, int64_t P,
+                                        int nbest);
+int asg_beam_window_nbest(asg_ctx *ctx, const asg_token_graph_beam *gb, int64_t B, int beam_size, int64_t W, int64_t P,
+                          const void *state, size_t state_bytes, int final, int nbest, void *work, size_t work_bytes, void *scores,
+                          int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *num_hyps,
+                          int64_t *frames, int64_t *committed, int64_t *status, int flags, void *stream);
+
 /* ---- Beam decoding with a LEXICON and a WORD n-gram LM, the LM composed ON THE FLY: the search of asg_beam_decode_graph over
  * pairs (h, q) -- h a history state of a backoff word LM, q a product state of the lexicon automaton -- that exist only while the
  * search holds them.  A static composition would need one slot per (history, product state); this needs none.  No counterpart in

@@ -42,7 +42,8 @@ SYMBOLS = ["asg_hip_version", "asg_hip_strerror", "asg_ctx_create", "asg_ctx_des
            "asg_beam_words_confidence_work_bytes", "asg_beam_words_confidence", "asg_beam_words_confidence_la",
            "asg_beam_words_nbest_confidence_work_bytes", "asg_beam_words_nbest_confidence", "asg_beam_words_nbest_confidence_la",
            "asg_beam_graph_confidence_work_bytes", "asg_beam_graph_confidence",
-           "asg_beam_graph_nbest_confidence_work_bytes", "asg_beam_graph_nbest_confidence"]
+           "asg_beam_graph_nbest_confidence_work_bytes", "asg_beam_graph_nbest_confidence",
+           "asg_beam_stream_nbest_work_bytes", "asg_beam_stream_nbest", "asg_beam_window_nbest_work_bytes", "asg_beam_window_nbest"]
 ABI_VERSION = 230        # include/asg_hip.h: ASG_HIP_VERSION this package was written against
 
 
@@ -161,6 +162,12 @@ def lib():
     L.asg_beam_window_reset.argtypes = [vp, bp, i64, ci, i64, i64, vp, sz, vp, ci, vp]
     L.asg_beam_window_advance.argtypes = [vp, pp, bp, ci, ctypes.c_double, i64, i64, vp, sz, vp, vp, vp, vp, vp, ci, vp]
     L.asg_beam_window_result.argtypes = [vp, bp, i64, ci, i64, i64, vp, sz, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp]
+    L.asg_beam_stream_nbest_work_bytes.restype = sz
+    L.asg_beam_stream_nbest_work_bytes.argtypes = [bp, i64, ci, ci, i64, ci]
+    L.asg_beam_stream_nbest.argtypes = [vp, bp, i64, ci, i64, vp, sz, ci, ci, vp, sz] + [vp] * 9 + [ci, vp]
+    L.asg_beam_window_nbest_work_bytes.restype = sz
+    L.asg_beam_window_nbest_work_bytes.argtypes = [bp, i64, ci, ci, i64, i64, ci]
+    L.asg_beam_window_nbest.argtypes = [vp, bp, i64, ci, i64, i64, vp, sz, ci, ci, vp, sz] + [vp] * 9 + [ci, vp]
     wp = ctypes.POINTER(AsgWordLM)
     L.asg_beam_decode_words_work_bytes.restype = sz
     L.asg_beam_decode_words_work_bytes.argtypes = [pp, bp, wp, ci]

@@ -1179,6 +1179,91 @@ int asg_beam_window_result(asg_ctx *ctx, const asg_token_graph_beam *gb, int64_t
                                                                      st, fr, co, su, (hipStream_t) stream)));
 }
 
+// The n best of the two token-graph streams: the checks of the corresponding _result call, then nbest.
+static int check_beam_stream_nbest(const asg_token_graph_beam *gb, int64_t B, int dtype, int beam_size, int64_t max_frames,
+                                   int nbest) {
+    int rc = check_beam_stream(gb, B, dtype, beam_size, max_frames);
+    if (rc) return rc;
+    if (nbest < 1) return ASG_ERR_INVALID;
+    if (nbest > kBeamMaxNbest) return ASG_ERR_UNSUPPORTED;
+    return ASG_OK;
+}
+
+static size_t beam_stream_nbest_bytes(const asg_token_graph_beam *gb, int64_t B, int beam_size, int64_t rows, int nbest) {
+    return beam_stream_nbest_work_bytes((int) rows, (int) B, beam_graph_k((int) gb->graph->Q, beam_size), nbest);
+}
+
+size_t asg_beam_stream_nbest_work_bytes(const asg_token_graph_beam *gb, int64_t B, int dtype, int beam_size, int64_t max_frames,
+                                        int nbest) {
+    if (check_beam_stream_nbest(gb, B, dtype, beam_size, max_frames, nbest) != ASG_OK) return 0;
+    return beam_stream_nbest_bytes(gb, B, beam_size, max_frames, nbest);
+}
+
+int asg_beam_stream_nbest(asg_ctx *ctx, const asg_token_graph_beam *gb, int64_t B, int beam_size, int64_t max_frames,
+                          const void *state, size_t state_bytes, int final, int nbest, void *work, size_t work_bytes, void *scores,
+                          void *graph_scores, int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states,
+                          int64_t *num_hyps, int64_t *frames, int64_t *status, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    if (!gb || !gb->graph) return ASG_ERR_INVALID;
+    const asg_token_graph *g = gb->graph;
+    int rc = check_beam_stream_nbest(gb, B, g->dtype, beam_size, max_frames, nbest);
+    if (rc) return rc;
+    if (!state || !work || !scores || !graph_scores || !tokens || !token_lengths || !num_hyps || !frames || !status)
+        return ASG_ERR_INVALID;
+    if (state_bytes < beam_stream_bytes(gb, B, g->dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
+    if (work_bytes < beam_stream_nbest_bytes(gb, B, beam_size, max_frames, nbest)) return ASG_ERR_WORKSPACE;
+    const GraphArgs G = to_graph_args(g);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    const int K = beam_graph_k(G.Q, beam_size);
+    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
+    long long *nh = (long long *) num_hyps, *fr = (long long *) frames, *su = (long long *) status;
+    return hip_status(ASG_DISPATCH(g, launch_beam_stream_nbest<float>(G, BG, K, (int) max_frames, (int) B, state, final, nbest, work,
+                                                                      scores, graph_scores, pa, tk, tl, st, nh, fr, su,
+                                                                      (hipStream_t) stream),
+                                   launch_beam_stream_nbest<double>(G, BG, K, (int) max_frames, (int) B, state, final, nbest, work,
+                                                                    scores, graph_scores, pa, tk, tl, st, nh, fr, su,
+                                                                    (hipStream_t) stream)));
+}
+
+static int check_beam_window_nbest(const asg_token_graph_beam *gb, int64_t B, int dtype, int beam_size, int64_t W, int64_t P,
+                                   int nbest) {
+    int rc = check_beam_window(gb, B, dtype, beam_size, W, P);
+    if (rc) return rc;
+    if (nbest < 1) return ASG_ERR_INVALID;
+    if (nbest > kBeamMaxNbest) return ASG_ERR_UNSUPPORTED;
+    return ASG_OK;
+}
+
+size_t asg_beam_window_nbest_work_bytes(const asg_token_graph_beam *gb, int64_t B, int dtype, int beam_size, int64_t W, int64_t P,
+                                        int nbest) {
+    if (check_beam_window_nbest(gb, B, dtype, beam_size, W, P, nbest) != ASG_OK) return 0;
+    return beam_stream_nbest_bytes(gb, B, beam_size, W, nbest);
+}
+
+int asg_beam_window_nbest(asg_ctx *ctx, const asg_token_graph_beam *gb, int64_t B, int beam_size, int64_t W, int64_t P,
+                          const void *state, size_t state_bytes, int final, int nbest, void *work, size_t work_bytes, void *scores,
+                          int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *num_hyps,
+                          int64_t *frames, int64_t *committed, int64_t *status, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    if (!gb || !gb->graph) return ASG_ERR_INVALID;
+    const asg_token_graph *g = gb->graph;
+    int rc = check_beam_window_nbest(gb, B, g->dtype, beam_size, W, P, nbest);
+    if (rc) return rc;
+    if (!state || !work || !scores || !tokens || !token_lengths || !num_hyps || !frames || !committed || !status)
+        return ASG_ERR_INVALID;
+    if (state_bytes < beam_window_bytes(gb, B, g->dtype, beam_size, W)) return ASG_ERR_WORKSPACE;
+    if (work_bytes < beam_stream_nbest_bytes(gb, B, beam_size, W, nbest)) return ASG_ERR_WORKSPACE;
+    const GraphArgs G = to_graph_args(g);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    const int K = beam_graph_k(G.Q, beam_size);
+    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
+    long long *nh = (long long *) num_hyps, *fr = (long long *) frames, *co = (long long *) committed, *su = (long long *) status;
+    return hip_status(ASG_DISPATCH(g, launch_beam_window_nbest<float>(G, BG, K, (int) W, (int) B, state, final, nbest, work, scores,
+                                                                      pa, tk, tl, st, nh, fr, co, su, (hipStream_t) stream),
+                                   launch_beam_window_nbest<double>(G, BG, K, (int) W, (int) B, state, final, nbest, work, scores,
+                                                                    pa, tk, tl, st, nh, fr, co, su, (hipStream_t) stream)));
+}
+
 // A word window stream state is sized like a word stream of W frames (the rings); P is the commit period.
 static int check_beam_word_window(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype, int beam_size,
                                   int64_t W, int64_t P) {

@@ -33,12 +33,8 @@ namespace {
 
 constexpr size_t kWinCtlOff = 3072;    // the window's control block sits behind the search's inside the fixed LDS
 
-// The header of a slot.
-struct WinHdr {
-    long long pos, base;
-    int na, carry, status;
-};
-static_assert(sizeof(WinHdr) <= 256, "header");
+// The header of a slot (asg_beam_window_common.h has it, for the n-best kernel that reads it).
+using WinHdr = TokenWinHdr;
 
 // What a commit attempt shares (LDS, behind Ctl inside the first kFixedLds bytes).
 struct WinCtl {

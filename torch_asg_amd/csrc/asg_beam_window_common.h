@@ -7,6 +7,8 @@
 // of this call's frames were written by this workgroup with plain stores and are read after a __syncthreads (a frame ends with
 // one); those of earlier calls cross a kernel boundary.  Integer atomics only, and the marks are a set: bit-identical run to run.
 // Each unit includes its frame header first and keeps its own WinHdr, WinCtl and WinOut; WinOut::kWords selects the word parts.
+// (The token family's WinHdr is TokenWinHdr below: asg_beam_nbest.hip reads a window's header too, with window_header,
+// window_live_base and ring_prev.)
 #pragma once
 #include "asg_beam_frame.h"
 
@@ -25,6 +27,14 @@ struct WinScan {
     int cnt[2];              // |R| of the scan's steps, alternating
     int slot;                // a marked slot (the one, when |R| == 1)
 };
+
+// The header of a slot of the token family's window: asg_beam_window.hip keeps it (as its WinHdr), and the n-best kernel of
+// asg_beam_nbest.hip reads it.
+struct TokenWinHdr {
+    long long pos, base;
+    int na, carry, status;
+};
+static_assert(sizeof(TokenWinHdr) <= 256, "header");
 
 // The header of a slot as the kernels use it.  A state that was reset holds 0 <= base <= pos, and pos <= base + W while its set
 // is not empty: behind an empty set pos goes on alone, and base is never used again.  -> pos >= 0, 0 <= na <= K (0 before the

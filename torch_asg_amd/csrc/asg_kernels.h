@@ -395,6 +395,35 @@ template <typename R>
 hipError_t launch_beam_nbest_over(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const BeamNbestLayout &lay, int K,
                                   int nbest, void *work, void *scores, void *emission_scores, void *graph_scores, long long *path,
                                   long long *tokens, long long *tlen, long long *states, long long *num_hyps, hipStream_t stream);
+// Where a search of this family lives for the n-best kernel (its three instantiations per dtype: kBeamNbestShot, kBeamNbestStream,
+// kBeamNbestWindow).  Slot b's block starts at base + b * per, with the [Tw][K] rows bq / bs at its front (beam_work_layout for
+// T = Tw); its int32 [Tw][nb] column block at cols + b * cols_per.
+//   one-shot   fin: int32 |A_{len-1}|, from byte 8 that set's values [K]; its states are row len-1 of bq; the length comes from
+//              the problem's lengths.
+//   stream     hdr: int32 pos, |A|, overflow; set: values [K], then int32 product states [K].  Tw = max_frames.
+//   window     hdr: int64 pos, int64 base, int32 |A|, carry, status; set as the stream's.  Tw = W, and the rows are a ring:
+//              frame u in row u mod W.
+struct BeamNbestSrc {
+    const char *base;
+    size_t per, fin, hdr, set;
+    char *cols;
+    size_t cols_per;
+    int Tw, nb;
+};
+enum { kBeamNbestShot = 0, kBeamNbestStream = 1, kBeamNbestWindow = 2 };
+// The same kernel over a stream state / a window state (read only).  The state holds no emissions: there is no emission sum,
+// and for the window no graph sum either.  work: [B] blocks of a256(rows * nb * 4) bytes, rows = max_frames / W.
+size_t beam_stream_nbest_work_bytes(int rows, int B, int K, int nbest);
+template <typename R>
+hipError_t launch_beam_stream_nbest(const GraphArgs &G, const BeamGraphArgs &BG, int K, int max_frames, int B, const void *state,
+                                    int final, int nbest, void *work, void *scores, void *graph_scores, long long *path,
+                                    long long *tokens, long long *tlen, long long *states, long long *num_hyps, long long *frames,
+                                    long long *status, hipStream_t stream);
+template <typename R>
+hipError_t launch_beam_window_nbest(const GraphArgs &G, const BeamGraphArgs &BG, int K, int W, int B, const void *state, int final,
+                                    int nbest, void *work, void *scores, long long *path, long long *tokens, long long *tlen,
+                                    long long *states, long long *num_hyps, long long *frames, long long *committed,
+                                    long long *status, hipStream_t stream);
 
 // ---- Beam-pruned full score and gradients over the same composed lattice (asg_beam_loss.hip): asg_beam_graph_full_*.
 struct BeamLossArgs {

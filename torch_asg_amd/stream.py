@@ -144,9 +144,47 @@ class _Stream:
                               self._state.numel(), 1 if final else 0, *[t.data_ptr() for t in res], 0, be._stream(dev)), what)
         return res
 
+    def _token_nbest(self, nbest, final, return_alignments, graph_scores):
+        """`result_nbest` of the two token-graph streams: one `_API + "_nbest"` launch over the state, which it only reads ->
+        (scores, graph_scores or None, tokens, token_lengths, num_hyps, path, states, narrow), `narrow` the [B] int64 outputs
+        behind num_hyps (frames, [committed,] status).  The wide outputs are [B, nbest, shape[0]].  The scratch is allocated
+        once per `nbest` and kept on the stream (it is not part of the state), so a captured call replays."""
+        if int(nbest) < 1:
+            raise ValueError("torch_asg_amd: nbest must be >= 1, got %d" % int(nbest))
+        nbest = min(int(nbest), (1 << 31) - 1)
+        be = _asg.native()
+        L = _lib.lib()
+        B, dev, T = self.batch_size, self.device, self._shape[0]
+        n_narrow = self._NARROW - 1                            # `_result`'s narrow outputs without token_lengths
+        with be._guard(dev):
+            what = self._API + "_nbest"
+            fn = getattr(L, what)
+
+            def call(work, nbytes, *outs):
+                return fn(None, *self._views, B, self.beam_size, *self._shape, self._state.data_ptr(), self._state.numel(),
+                          1 if final else 0, nbest, work, nbytes, *outs)
+            work = self._nbest_work.get(nbest)
+            if work is None:
+                abi_dtype = _lib.ASG_DTYPE_F32 if self.dtype == torch.float32 else _lib.ASG_DTYPE_F64
+                nbytes = int(getattr(L, what + "_work_bytes")(*self._views, B, abi_dtype, self.beam_size, *self._shape, nbest))
+                if nbytes == 0:                                # the library refuses the arguments: its call says why
+                    _lib.check(call(None, 0, *(None,) * 9, 0, None), what)
+                work = self._nbest_work[nbest] = be._buf(nbytes, dev)
+            sc = torch.empty(2 if graph_scores else 1, B, nbest, dtype=self.dtype, device=dev)
+            tokens = torch.empty(B, nbest, T, dtype=torch.int64, device=dev)
+            align = torch.empty(2, B, nbest, T, dtype=torch.int64, device=dev) if return_alignments else (None, None)
+            token_lengths = torch.empty(B, nbest, dtype=torch.int64, device=dev)
+            narrow = torch.empty(1 + n_narrow, B, dtype=torch.int64, device=dev)     # num_hyps, frames, [committed,] status
+            al = lambda i: align[i].data_ptr() if return_alignments else None      # noqa: E731
+            _lib.check(call(work.data_ptr(), work.numel(), *[t.data_ptr() for t in sc], al(0), tokens.data_ptr(),
+                            token_lengths.data_ptr(), al(1), *[t.data_ptr() for t in narrow], 0, be._stream(dev)), what)
+        return sc[0], (sc[1] if graph_scores else None), tokens, token_lengths, narrow[0], align[0], align[1], narrow[1:]
+
 
 BeamStreamResult = collections.namedtuple("BeamStreamResult", ["scores", "path", "tokens", "token_lengths", "states", "frames",
                                                                "status"])
+BeamStreamNbest = collections.namedtuple("BeamStreamNbest", ["scores", "graph_scores", "tokens", "token_lengths", "num_hyps", "path",
+                                                             "states", "frames", "status"])
 
 
 class BeamStream(_Stream):
@@ -168,12 +206,15 @@ class BeamStream(_Stream):
     The state lives in one device buffer (about max_frames * beam_size * 8 bytes of back-pointers plus 12-16 bytes per product
     state, per slot).  The graph is compiled in the constructor; `advance`, `result` and `reset` are one kernel launch each, copy
     nothing and do not synchronise, so they can be captured in a graph and replayed with new chunk contents and lengths.
+    `result_nbest` gives the n best hypotheses or prefixes from the same state, with the graph part of each score: the list
+    `beam_decode_graph_nbest` returns for the whole utterance, without keeping the emissions or searching twice.
     """
     _API, _WIDE, _NARROW = "asg_beam_stream", 3, 3
 
     def __init__(self, transition, graph, batch_size, max_frames, beam_size=256, beam_threshold=float("inf"), lm_weight=1.0,
                  token_score=0.0, dtype=torch.float32, device=None):
         self.lm_weight, self.token_score = lm_weight, token_score
+        self._nbest_work = {}                                  # nbest -> the scratch of result_nbest (not part of the state)
         super().__init__(transition, (graph,), batch_size, (max_frames,), beam_size, beam_threshold, dtype, device)
         (self.max_frames,) = self._shape
 
@@ -197,6 +238,19 @@ class BeamStream(_Stream):
         final=True adds the final weights (the transcript of a finished utterance: `beam_decode_graph`'s result); final=False is
         the best prefix hypothesis, largest value without a final weight.  A slot without frames or with an empty beam: -inf, -1, 0."""
         return self._result(final)
+
+    def result_nbest(self, nbest, final=False, return_alignments=False):
+        """The `nbest` best hypotheses of every slot over the frames consumed so far, without changing the state -> a named tuple
+          scores, graph_scores [B, nbest]; tokens [B, nbest, max_frames] int64, -1 behind the data; token_lengths [B, nbest];
+          num_hyps [B]; path, states [B, nbest, max_frames] with `return_alignments`, else None; frames, status [B] as `result`.
+        final=True: `beam_decode_graph_nbest`'s rows for the utterance so far, bit for bit, for any chunking.  final=False: the n
+        best PREFIXES -- the kept states by value -- with graph_scores without a final weight.  Row 0 equals `result(final)`.
+        Rows behind num_hyps: -inf, -1, 0.  The state keeps no emissions, so there is no emission_scores: a caller who kept the
+        frames has `beam_decode_graph_nbest`, the others have scores - graph_scores up to rounding.  One launch
+        (include/asg_hip.h::asg_beam_stream_nbest); the scratch it needs is allocated once per `nbest` and kept on the stream,
+        so a captured call replays.  nbest < 1 raises ValueError, nbest > 8192 RuntimeError."""
+        scores, gscores, tokens, tlen, nh, path, states, (frames, status) = self._token_nbest(nbest, final, return_alignments, True)
+        return BeamStreamNbest(scores, gscores, tokens, tlen, nh, path, states, frames, status)
 
     @staticmethod
     def _outputs(scores, wide, narrow):
@@ -366,6 +420,8 @@ class BeamWordStream(_Stream):
 BeamWindowCommit = collections.namedtuple("BeamWindowCommit", ["path", "states", "tokens", "token_lengths", "frames"])
 BeamWindowResult = collections.namedtuple("BeamWindowResult", ["scores", "path", "tokens", "token_lengths", "states", "frames",
                                                                "committed", "status"])
+BeamWindowNbest = collections.namedtuple("BeamWindowNbest", ["scores", "tokens", "token_lengths", "num_hyps", "path", "states",
+                                                             "frames", "committed", "status"])
 
 
 class BeamWindowStream(_Stream):
@@ -389,13 +445,15 @@ class BeamWindowStream(_Stream):
     The state is one device buffer of about window * beam_size * 8 bytes of back-pointers plus 12-16 bytes per product state,
     per slot, whatever the length of the utterance; `result` walks at most `window` frames.  `advance`, `result` and `reset` are
     one kernel launch each, copy nothing and do not synchronise, so they can be captured and replayed.  The other arguments are
-    `BeamStream`'s; there is no bound on the number of frames.
+    `BeamStream`'s; there is no bound on the number of frames.  `result_nbest` gives the n best hypotheses as their uncommitted
+    tails, with `BeamStream.result_nbest`'s scores.
     """
     _API, _WIDE, _NARROW = "asg_beam_window", 3, 4
 
     def __init__(self, transition, graph, batch_size, window, commit_every=None, beam_size=256, beam_threshold=float("inf"),
                  lm_weight=1.0, token_score=0.0, dtype=torch.float32, device=None):
         self.lm_weight, self.token_score = lm_weight, token_score
+        self._nbest_work = {}                                  # nbest -> the scratch of result_nbest (not part of the state)
         super().__init__(transition, (graph,), batch_size, (window, commit_every), beam_size, beam_threshold, dtype, device)
         self.window, self.commit_every = self._shape
 
@@ -433,6 +491,23 @@ class BeamWindowStream(_Stream):
           agreed on them, bit 1 = the beam is empty.
         final as for `BeamStream.result`.  A slot without frames or with an empty beam: -inf, -1, 0."""
         return self._result(final)
+
+    def result_nbest(self, nbest, final=False, return_alignments=False):
+        """The `nbest` best hypotheses of every slot, each as its uncommitted TAIL, without changing the state -> a named tuple
+          scores [B, nbest], the scores of the whole hypotheses: `BeamStream.result_nbest`'s at equal position, bit for bit;
+          tokens [B, nbest, window] int64, -1 behind the data: the collapse of the row's tail, started from the last committed
+          label; token_lengths [B, nbest]; num_hyps [B]; path, states [B, nbest, window] with `return_alignments`, else None: the
+          frames committed .. frames-1 on the row's own chain; frames, committed, status [B] as `result`.
+        While bit 0 of `status` is clear, what `advance` has committed followed by a row's tail is that row of
+        `BeamStream.result_nbest` -- a commit by convergence is an ancestor of every later hypothesis; after a forced commit the
+        rows are still their own chains, but need not continue the committed prefix.  A tail may be empty (everything is
+        committed): the row still counts.  There is no graph_scores: the edge into the first tail frame needs the state of the
+        frame before it, which the window may have dropped.  One launch (include/asg_hip.h::asg_beam_window_nbest), at most
+        `window` steps per row; the scratch is kept on the stream per `nbest`, so a captured call replays.  nbest < 1 raises
+        ValueError, nbest > 8192 RuntimeError."""
+        scores, _, tokens, tlen, nh, path, states, (frames, committed, status) = self._token_nbest(nbest, final, return_alignments,
+                                                                                                   False)
+        return BeamWindowNbest(scores, tokens, tlen, nh, path, states, frames, committed, status)
 
     @staticmethod
     def _outputs(scores, wide, narrow):
