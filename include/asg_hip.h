@@ -451,7 +451,8 @@ int asg_beam_window_result(asg_ctx *ctx, const asg_token_graph_beam *gb, int64_t
  * of asg_beam_stream_result / asg_beam_window_result; nbest < 1: ASG_ERR_INVALID; nbest > 8192: ASG_ERR_UNSUPPORTED; a `work`
  * smaller than *_work_bytes: ASG_ERR_WORKSPACE; NULL state, work, scores, graph_scores, tokens, token_lengths, num_hyps, frames,
  * committed or status: ASG_ERR_INVALID.  *_work_bytes returns 0 for arguments the call refuses.  `flags` is reserved (pass 0).
- * Not here: emission_scores from a stream, graph_scores from the window, confidences from any stream, the two word windows. */
+ * Not here: emission_scores from a stream, graph_scores from the window, confidences from any stream.  (The word family's window:
+ * asg_beam_word_window_nbest.) */
 size_t asg_beam_stream_nbest_work_bytes(const asg_token_graph_beam *gb, int64_t B, int dtype, int beam_size, int64_t max_frames,
                                         int nbest);
 int asg_beam_stream_nbest(asg_ctx *ctx, const asg_token_graph_beam *gb, int64_t B, int beam_size, int64_t max_frames,
@@ -1005,7 +1006,8 @@ int asg_beam_word_stream_nbest(asg_ctx *ctx, const asg_token_graph_beam *gb, con
  * (beam_size <= 8192 with no clamp to Q, H, Q <= 2^25, A < 2^31, W within asg_beam_window_*'s bound; ASG_ERR_UNSUPPORTED beyond);
  * W < 1, P < 1, P > W, Tc < 0, B < 1, beam_size < 1, a negative or NaN beam_threshold, a dtype that is not the graph's and the
  * LM's, a NULL array or output: ASG_ERR_INVALID; a state buffer smaller than asg_beam_word_window_state_bytes: ASG_ERR_WORKSPACE.
- * Not here: n-best from the window, a commit rule that looks at scores (LM look-ahead: asg_beam_word_window_advance_la below).
+ * The n best of the window: asg_beam_word_window_nbest below.  Not here: a commit rule that looks at scores (LM look-ahead:
+ * asg_beam_word_window_advance_la below).
  * `flags` is reserved (pass 0). */
 size_t asg_beam_word_window_state_bytes(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype, int beam_size,
                                         int64_t W, int64_t P);
@@ -1071,6 +1073,69 @@ int asg_beam_word_window_result_la(asg_ctx *ctx, const asg_token_graph_beam *gb,
                                    int64_t *word_lengths, int64_t *frames, int64_t *committed, int64_t *status, int flags,
                                    void *stream);
 
+/* ---- The N BEST hypotheses of the WINDOWED word stream: asg_beam_word_stream_nbest's list from a state of asg_beam_word_window_*,
+ * which the call only reads -- the same kernel, pointed at the stored set and at the rings -- so that an open microphone with a
+ * lexicon and a word LM can hand a list to a rescorer in bounded memory.  The arguments are asg_beam_word_window_result's
+ * (asg_beam_word_window_result_la's), then nbest, work, work_bytes, then the outputs.  Throughout K = beam_size (no clamp to Q)
+ * and nb = min(nbest, K).  No counterpart in the reference.
+ * asg_beam_word_window_nbest.  The candidates, their order, num_hyps and scores are asg_beam_word_stream_nbest's at equal pos, bit
+ *   for bit (the window's property 1, for every row): every entry (h, q) of the stored set with a valid q whose end is > -inf --
+ *   final != 0: end = (v + final_w[q]) + endw, the end of asg_beam_decode_words (none mid-word, none where the LM rejects the
+ *   word); final == 0: end = v, the n best PREFIXES --, end descending, then pair order ascending, -0 equal to +0.  num_hyps [B] =
+ *   min(nbest, candidates): 0 for pos == 0 or an empty set.  scores [B][nbest] (dtype) = the candidate's end.
+ *   Row r < num_hyps holds the candidate's TAIL, the frames base .. pos-1 on ITS OWN chain of back-pointers through the rings
+ *   (frame u in row u mod W), column t = frame base + t, walked in at most W steps; all row outputs are int64 [B][nbest][W], -1
+ *   behind the data.  path = label[q], states = state[q], lm_states = the ring bh of every tail frame (any of the three may be
+ *   NULL: not written).  tokens is the collapse of the tail started from carry -- a first tail label equal to carry is no token.
+ *   words follows asg_beam_word_window_advance's rule started from carry / carry_state: a tail frame whose label is the separator
+ *   behind a label that is neither the separator nor -1 appends word_of_state[the automaton state of the frame before], and before
+ *   column 0 that label and state are carry and carry_state -- a separator edge on the first uncommitted frame yields its word
+ *   exactly once, here and not in any commit.  With final != 0 the word of the final step is appended if the candidate ends in a
+ *   word-end node, also behind an empty tail, while fewer than W words stand in the row (asg_beam_word_window_result's bound).
+ *   token_lengths, word_lengths [B][nbest].  The tail may be empty (base == pos, after a commit up to the last frame): the row
+ *   still counts, with its score, its final word if it has one, and -1 elsewhere.  Rows >= num_hyps: scores -inf, every wide
+ *   column -1, both lengths 0.  frames [B] = pos, committed [B] = base and status [B] (bit 0: a forced commit has happened,
+ *   bit 1: pos >= 1 and the set is empty) as asg_beam_word_window_result writes them.
+ * asg_beam_word_window_nbest_la, over a state that asg_beam_word_window_advance_la left: the same with the ends of
+ *   asg_beam_word_stream_nbest_la -- final != 0: (v + final_w[q]) + ew[h] at the root, (v + final_w[q]) + ((a - L(h, state(q))) +
+ *   ew[h']) in a word-end node; final == 0: v - L(h, state(q)), the prefix WITHOUT the estimate it still carries.  Rows as above.
+ *   Mixing as for asg_beam_word_window_result_la: NOTHING HERE CAN CHECK which estimate a state carries.
+ * REQUIRED PROPERTIES (no tolerance in any).  (a) Row 0 equals asg_beam_word_window_result(final) (_result_la) on every shared
+ * field -- scores, path, tokens, token_lengths, states, lm_states, words, word_lengths, frames, committed, status -- bit for bit.
+ * (b) While status bit 0 is clear: for EVERY row, everything advance has committed followed by the row's tail equals row r of
+ * asg_beam_word_stream_nbest (_la) on a growing stream fed the same frames, for path, states, lm_states, tokens and words.  Why: a
+ * convergence commit stops at a frame c at which every survivor of that moment has the same ancestor slot, so the committed chain
+ * is an ancestor chain of every survivor of that frame and of every later one; carry / carry_state are the label and state of
+ * frame base-1 on that chain, hence on every row's.  (c) With bit 0 set some frames were committed along the best prefix of the
+ * moment only; the rows are then still exactly the chains specified above (deterministic, the same for every chunking) but need
+ * not continue the committed prefix, and the word of a separator in column 0 is word_of_state[carry_state], whatever was
+ * committed.  (d) The state is only read.
+ * There are no emission_scores, graph_scores or lm_scores: the sums of the committed part are gone, and the header keeps
+ * carry_state, not the product state or the LM history of frame base-1 that the edge into frame `base` would need.  The state is
+ * not widened for them: asg_beam_word_window_state_bytes is unchanged.
+ * `work` (asg_beam_word_window_nbest_work_bytes; serves both forms): B * (W*nb*4 rounded up to 256) bytes; its contents mean
+ * nothing between calls.  ONE launch on `stream`, one 1024-thread workgroup per slot: no host synchronisation, no copy, no memset
+ * -- every output element and every scratch word that is read is written by the kernel -- so a captured call replays.  One integer
+ * LDS counter, no atomics on values: bit-identical run to run.  LDS: P2(K) * (8 + e) bytes, P2 the power of two >= K.
+ * Errors: those of asg_beam_word_window_result (_result_la), first; nbest < 1: ASG_ERR_INVALID; nbest > 8192:
+ * ASG_ERR_UNSUPPORTED; NULL state, work, scores, tokens, token_lengths, words, word_lengths, num_hyps, frames, committed or status:
+ * ASG_ERR_INVALID; a `work` smaller than asg_beam_word_window_nbest_work_bytes: ASG_ERR_WORKSPACE.
+ * asg_beam_word_window_nbest_work_bytes returns 0 for arguments the call refuses.  `flags` is reserved (pass 0).
+ * Not here: score parts from the window, confidences from any stream. */
+size_t asg_beam_word_window_nbest_work_bytes(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype,
+                                             int beam_size, int64_t W, int64_t P, int nbest);
+int asg_beam_word_window_nbest(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
+                               int64_t W, int64_t P, const void *state, size_t state_bytes, int final, int nbest, void *work,
+                               size_t work_bytes, void *scores, int64_t *path, int64_t *tokens, int64_t *token_lengths,
+                               int64_t *states, int64_t *lm_states, int64_t *words, int64_t *word_lengths, int64_t *num_hyps,
+                               int64_t *frames, int64_t *committed, int64_t *status, int flags, void *stream);
+int asg_beam_word_window_nbest_la(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                  const asg_word_lookahead *la, int64_t B, int beam_size, int64_t W, int64_t P, const void *state,
+                                  size_t state_bytes, int final, int nbest, void *work, size_t work_bytes, void *scores,
+                                  int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *lm_states,
+                                  int64_t *words, int64_t *word_lengths, int64_t *num_hyps, int64_t *frames, int64_t *committed,
+                                  int64_t *status, int flags, void *stream);
+
 /* ---- The N BEST hypotheses of the search WITH LM LOOK-AHEAD: asg_beam_decode_words_nbest over the search of
  * asg_beam_decode_words_la, asg_beam_word_stream_nbest over a state that asg_beam_word_stream_advance_la left.  Each entry point is
  * the plain call with `la`, the look-ahead of that search, behind `lm`; everything the plain call's text says holds with the
@@ -1108,7 +1173,8 @@ int asg_beam_word_window_result_la(asg_ctx *ctx, const asg_token_graph_beam *gb,
  * Mixing.  As for the streams above: a state advanced with a look-ahead is read with the same look-ahead, one advanced without by
  * asg_beam_word_stream_nbest; the stored values do not say which estimate they carry, and NOTHING HERE CAN CHECK IT.
  * Errors: the plain call's, then asg_beam_decode_words_la's for `la`: a NULL look-ahead, one of another dtype, a NULL or mis-sized
- * array, or S / H other than the LM view's: ASG_ERR_INVALID.  Not here: n-best from the windowed streams. */
+ * array, or S / H other than the LM view's: ASG_ERR_INVALID.  The n best of a window state with look-ahead:
+ * asg_beam_word_window_nbest_la above. */
 int asg_beam_decode_words_nbest_la(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
                                    const asg_word_lookahead *la, int beam_size, double beam_threshold, int nbest, void *work,
                                    size_t work_bytes, void *scores, void *emission_scores, void *graph_scores, void *lm_scores,

@@ -12,7 +12,7 @@ from .asg import BeamWordsConfidence, beam_decode_words_confidence  # noqa: F401
 from .asg import BeamGraphConfidence, beam_decode_graph_confidence  # noqa: F401
 from .asg import BeamNbestConfidence, beam_decode_graph_nbest_confidence  # noqa: F401
 from .asg import BeamWordStream, BeamWordStreamResult  # noqa: F401
-from .asg import BeamWordWindowStream, BeamWordWindowCommit, BeamWordWindowResult  # noqa: F401
+from .asg import BeamWordWindowStream, BeamWordWindowCommit, BeamWordWindowResult, BeamWordWindowNbest  # noqa: F401
 from .asg import BeamWordsNbest, beam_decode_words_nbest, BeamWordStreamNbest  # noqa: F401
 from .asg import BeamWordsNbestConfidence, beam_decode_words_nbest_confidence  # noqa: F401
 from .asg import BeamWordsFullScore, beam_words_full_score, beam_words_asg_loss  # noqa: F401
@@ -51,5 +51,5 @@ __all__ = ["ASGLoss", "ASGLossFunction", "FAC", "FCC", "ASGGPUFast", "ASGGPUFast
            "BeamGraphFullScore", "beam_graph_full_score", "beam_graph_asg_loss", "BeamNbest", "beam_decode_graph_nbest",
            "BeamStream", "BeamStreamResult", "BeamWindowStream", "BeamWindowCommit", "BeamWindowResult",
            "BeamStreamNbest", "BeamWindowNbest",
-           "BeamWords", "beam_decode_words", "BeamWordsConfidence", "beam_decode_words_confidence", "BeamGraphConfidence", "beam_decode_graph_confidence", "BeamNbestConfidence", "beam_decode_graph_nbest_confidence", "BeamWordStream", "BeamWordStreamResult", "BeamWordsNbest", "beam_decode_words_nbest", "BeamWordStreamNbest", "BeamWordsNbestConfidence", "beam_decode_words_nbest_confidence", "BeamWordWindowStream", "BeamWordWindowCommit", "BeamWordWindowResult", "BeamWordsFullScore", "beam_words_full_score",
+           "BeamWords", "beam_decode_words", "BeamWordsConfidence", "beam_decode_words_confidence", "BeamGraphConfidence", "beam_decode_graph_confidence", "BeamNbestConfidence", "beam_decode_graph_nbest_confidence", "BeamWordStream", "BeamWordStreamResult", "BeamWordsNbest", "beam_decode_words_nbest", "BeamWordStreamNbest", "BeamWordsNbestConfidence", "beam_decode_words_nbest_confidence", "BeamWordWindowStream", "BeamWordWindowCommit", "BeamWordWindowResult", "BeamWordWindowNbest", "BeamWordsFullScore", "beam_words_full_score",
            "beam_words_asg_loss", "Lexicon", "WordLM", "WordLookahead", "shard_batch", "sharded_asg_loss", "allreduce_transition_grad", "reserve", "release", "check_faults", "graphed", "GraphedStep"]

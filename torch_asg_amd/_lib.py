@@ -43,7 +43,8 @@ SYMBOLS = ["asg_hip_version", "asg_hip_strerror", "asg_ctx_create", "asg_ctx_des
            "asg_beam_words_nbest_confidence_work_bytes", "asg_beam_words_nbest_confidence", "asg_beam_words_nbest_confidence_la",
            "asg_beam_graph_confidence_work_bytes", "asg_beam_graph_confidence",
            "asg_beam_graph_nbest_confidence_work_bytes", "asg_beam_graph_nbest_confidence",
-           "asg_beam_stream_nbest_work_bytes", "asg_beam_stream_nbest", "asg_beam_window_nbest_work_bytes", "asg_beam_window_nbest"]
+           "asg_beam_stream_nbest_work_bytes", "asg_beam_stream_nbest", "asg_beam_window_nbest_work_bytes", "asg_beam_window_nbest",
+           "asg_beam_word_window_nbest_work_bytes", "asg_beam_word_window_nbest", "asg_beam_word_window_nbest_la"]
 ABI_VERSION = 230        # include/asg_hip.h: ASG_HIP_VERSION this package was written against
 
 
@@ -190,9 +191,12 @@ def lib():
     L.asg_beam_word_window_reset.argtypes = [vp, bp, wp, i64, ci, i64, i64, vp, sz, vp, ci, vp]
     L.asg_beam_word_window_advance.argtypes = [vp, pp, bp, wp, ci, ctypes.c_double, i64, i64, vp, sz] + [vp] * 8 + [ci, vp]
     L.asg_beam_word_window_result.argtypes = [vp, bp, wp, i64, ci, i64, i64, vp, sz, ci] + [vp] * 11 + [ci, vp]
+    L.asg_beam_word_window_nbest_work_bytes.restype = sz
+    L.asg_beam_word_window_nbest_work_bytes.argtypes = [bp, wp, i64, ci, ci, i64, i64, ci]
+    L.asg_beam_word_window_nbest.argtypes = [vp, bp, wp, i64, ci, i64, i64, vp, sz, ci, ci, vp, sz] + [vp] * 12 + [ci, vp]
     for name in ("asg_beam_word_stream_advance", "asg_beam_word_stream_result", "asg_beam_word_window_advance",
                  "asg_beam_word_window_result", "asg_beam_decode_words_nbest",
-                 "asg_beam_word_stream_nbest"):        # the plain call with the look-ahead behind the LM
+                 "asg_beam_word_stream_nbest", "asg_beam_word_window_nbest"):      # the plain call with the look-ahead behind the LM
         plain = getattr(L, name).argtypes
         at = plain.index(wp) + 1
         getattr(L, name + "_la").argtypes = plain[:at] + [ctypes.POINTER(AsgWordLookahead)] + plain[at:]

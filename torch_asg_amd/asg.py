@@ -2321,4 +2321,4 @@ class ASGLoss(nn.Module):
 # the streaming decoders (stream.py looks this module's `native` up at every call, so it is imported once the module stands)
 from .stream import (BeamStream, BeamStreamResult, BeamWordStream, BeamWordStreamResult, BeamWordStreamNbest,  # noqa: E402,F401
                      BeamWindowStream, BeamWindowCommit, BeamWindowResult, BeamWordWindowStream, BeamWordWindowCommit,
-                     BeamWordWindowResult, BeamStreamNbest, BeamWindowNbest)
+                     BeamWordWindowResult, BeamStreamNbest, BeamWindowNbest, BeamWordWindowNbest)

@@ -1405,6 +1405,78 @@ int asg_beam_word_window_result_la(asg_ctx *ctx, const asg_token_graph_beam *gb,
                                    token_lengths, states, lm_states, words, word_lengths, frames, committed, status, stream);
 }
 
+static int check_beam_word_window_nbest(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype, int beam_size,
+                                        int64_t W, int64_t P, int nbest) {
+    int rc = check_beam_word_window(gb, lm, B, dtype, beam_size, W, P);
+    if (rc) return rc;
+    if (nbest < 1) return ASG_ERR_INVALID;
+    if (nbest > kBeamMaxNbest) return ASG_ERR_UNSUPPORTED;
+    return ASG_OK;
+}
+
+size_t asg_beam_word_window_nbest_work_bytes(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype,
+                                             int beam_size, int64_t W, int64_t P, int nbest) {
+    if (check_beam_word_window_nbest(gb, lm, B, dtype, beam_size, W, P, nbest) != ASG_OK) return 0;
+    return beam_word_window_nbest_work_bytes((int) W, (int) B, beam_size, nbest);
+}
+
+// asg_beam_word_window_nbest with a look-ahead (`with_la`, checked behind the LM) or without one.
+static int beam_word_window_nbest(const asg_token_graph_beam *gb, const asg_word_lm *lm, const asg_word_lookahead *la, bool with_la,
+                                  int64_t B, int beam_size, int64_t W, int64_t P, const void *state, size_t state_bytes, int final,
+                                  int nbest, void *work, size_t work_bytes, void *scores, int64_t *path, int64_t *tokens,
+                                  int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words,
+                                  int64_t *word_lengths, int64_t *num_hyps, int64_t *frames, int64_t *committed, int64_t *status,
+                                  void *stream) {
+    if (!gb || !gb->graph) return ASG_ERR_INVALID;
+    const asg_token_graph *g = gb->graph;
+    int rc = check_beam_word_window_nbest(gb, lm, B, g->dtype, beam_size, W, P, nbest);
+    if (rc) return rc;
+    if (with_la && (rc = check_word_lookahead(g->dtype, lm, la)) != ASG_OK) return rc;
+    if (!state || !work || !scores || !tokens || !token_lengths || !words || !word_lengths || !num_hyps || !frames || !committed ||
+        !status)
+        return ASG_ERR_INVALID;
+    if (state_bytes < beam_word_window_bytes(gb, B, g->dtype, beam_size, W)) return ASG_ERR_WORKSPACE;
+    if (work_bytes < beam_word_window_nbest_work_bytes((int) W, (int) B, beam_size, nbest)) return ASG_ERR_WORKSPACE;
+    const GraphArgs G = to_graph_args(g);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    const WordLmArgs LM = to_word_lm_args(lm);
+    const int S = word_lm_states(lm);
+    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
+    long long *ls = (long long *) lm_states, *wd = (long long *) words, *wl = (long long *) word_lengths;
+    long long *nh = (long long *) num_hyps, *fr = (long long *) frames, *co = (long long *) committed, *su = (long long *) status;
+    const WordLookArgs LA = with_la ? to_word_look_args(la) : WordLookArgs{};
+    const WordLookArgs *look = with_la ? &LA : nullptr;
+    return hip_status(ASG_DISPATCH(g, launch_beam_word_window_nbest<float>(G, BG, LM, look, S, beam_size, (int) W, (int) B, state,
+                                                                           final, nbest, work, scores, pa, tk, tl, st, ls, wd, wl,
+                                                                           nh, fr, co, su, (hipStream_t) stream),
+                                   launch_beam_word_window_nbest<double>(G, BG, LM, look, S, beam_size, (int) W, (int) B, state,
+                                                                         final, nbest, work, scores, pa, tk, tl, st, ls, wd, wl,
+                                                                         nh, fr, co, su, (hipStream_t) stream)));
+}
+
+int asg_beam_word_window_nbest(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
+                               int64_t W, int64_t P, const void *state, size_t state_bytes, int final, int nbest, void *work,
+                               size_t work_bytes, void *scores, int64_t *path, int64_t *tokens, int64_t *token_lengths,
+                               int64_t *states, int64_t *lm_states, int64_t *words, int64_t *word_lengths, int64_t *num_hyps,
+                               int64_t *frames, int64_t *committed, int64_t *status, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    return beam_word_window_nbest(gb, lm, nullptr, false, B, beam_size, W, P, state, state_bytes, final, nbest, work, work_bytes,
+                                  scores, path, tokens, token_lengths, states, lm_states, words, word_lengths, num_hyps, frames,
+                                  committed, status, stream);
+}
+
+int asg_beam_word_window_nbest_la(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                  const asg_word_lookahead *la, int64_t B, int beam_size, int64_t W, int64_t P, const void *state,
+                                  size_t state_bytes, int final, int nbest, void *work, size_t work_bytes, void *scores,
+                                  int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *lm_states,
+                                  int64_t *words, int64_t *word_lengths, int64_t *num_hyps, int64_t *frames, int64_t *committed,
+                                  int64_t *status, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    return beam_word_window_nbest(gb, lm, la, true, B, beam_size, W, P, state, state_bytes, final, nbest, work, work_bytes, scores,
+                                  path, tokens, token_lengths, states, lm_states, words, word_lengths, num_hyps, frames, committed,
+                                  status, stream);
+}
+
 // What the two beam-pruned losses check alike behind their search's own checks: the targets, the limits of the lattice pass and
 // whether a frame's set of M = K + nf members fits the family's kernels.
 static int check_lattice(const asg_problem *p, int K, bool (*fits)(int, int, int)) {

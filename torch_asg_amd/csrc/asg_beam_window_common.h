@@ -7,8 +7,8 @@
 // of this call's frames were written by this workgroup with plain stores and are read after a __syncthreads (a frame ends with
 // one); those of earlier calls cross a kernel boundary.  Integer atomics only, and the marks are a set: bit-identical run to run.
 // Each unit includes its frame header first and keeps its own WinHdr, WinCtl and WinOut; WinOut::kWords selects the word parts.
-// (The token family's WinHdr is TokenWinHdr below: asg_beam_nbest.hip reads a window's header too, with window_header,
-// window_live_base and ring_prev.)
+// (The families' WinHdr are TokenWinHdr and WordWinHdr below: asg_beam_nbest.hip and asg_beam_word_nbest.hip read a window's
+// header too, with window_header, window_live_base and ring_prev.)
 #pragma once
 #include "asg_beam_frame.h"
 
@@ -35,6 +35,14 @@ struct TokenWinHdr {
     int na, carry, status;
 };
 static_assert(sizeof(TokenWinHdr) <= 256, "header");
+
+// The header of a slot of the word family's window: asg_beam_word_window.hip keeps it (as its WinHdr), and the n-best kernel of
+// asg_beam_word_nbest.hip reads it.
+struct WordWinHdr {
+    long long pos, base;
+    int na, carry, carry_state, status;
+};
+static_assert(sizeof(WordWinHdr) <= 256, "header");
 
 // The header of a slot as the kernels use it.  A state that was reset holds 0 <= base <= pos, and pos <= base + W while its set
 // is not empty: behind an empty set pos goes on alone, and base is never used again.  -> pos >= 0, 0 <= na <= K (0 before the

@@ -11,6 +11,8 @@
 //   one-shot   behind beam_word_kernel on the same stream (the decoder's own device code, so the same sets and back-pointers bit
 //              for bit), asked to leave |A_{len-1}| and that set beside its rows;
 //   stream     over a stream state, which holds the set in memory already; it is only read.
+//   window     over a window state of asg_beam_word_window.hip, whose rows are rings: every row is the uncommitted tail of its
+//              chain, without sums (the kernel's third source, described at its template below); it is only read.
 //   keys     per entry of the last set the end -- with `final` word_end's (v + final_w) + endw, the LM walk of a word-end node
 //            done here once, without it the value v -- as (~key of end, pair << 14 | slot).
 //   sort     a fixed bitonic network in LDS over the power of two >= |A|, padded with all-ones entries, ascending: end
@@ -34,6 +36,7 @@
 #include "asg_kernels.h"
 #include "asg_beam_common.h"
 #include "asg_beam_word_frame.h"  // step, word_end, the pair: the bits of the ends are the one-best decoder's
+#include "asg_beam_window_common.h"  // the window's header and its clamps, the ring's step
 
 namespace asg {
 
@@ -54,17 +57,32 @@ __device__ __forceinline__ bool entry_less(U ka, unsigned long long pa, U kb, un
 // carry L(h, node): the keys and `scores` take it back as the one-best does -- word_end<R, true>, word_prefix<R, true>, that text
 // -- and nothing else changes: the walk and the three sums never see a look-ahead term.  Off by default: the
 // instantiations without it compile the text they compiled before the flag existed.
-template <typename R, bool LA = false>
+//
+// SRC says where the search lives (asg_kernels.h).  kBeamWordNbestRows is the text above, for the one-shot workspace and the stream
+// state.  kBeamWordNbestWindow (asg_beam_word_window_nbest, with LA asg_beam_word_window_nbest_la) reads a window state, and what
+// differs is selected with `if constexpr`:
+//   header   WordWinHdr through window_header and window_live_base; frames, committed and status as beam_word_window_result_kernel
+//            writes them; a row has len = pos - base frames, 0 .. W, and an empty tail still counts.
+//   walk     the row of frame pos-1 from a 64-bit remainder, then ring_prev: at most W steps into column t = frame - base; no
+//            forward pass and no sums (the edge into frame `base` needs the product state and the history of frame base-1, which
+//            the header does not keep).
+//   write    tokens collapsed from the header's `carry` (collapse_tokens_from's rule); words by collapse_words_from's rule, the
+//            label and automaton state before column 0 being `carry` / `carry_state`, so a separator edge on the first
+//            uncommitted frame gives its word once; the final word from the set's own q, also behind an empty tail, bounded by W
+//            as the result kernel bounds it.
+// The state is only read.
+template <typename R, bool LA = false, int SRC = kBeamWordNbestRows>
 __global__ void __launch_bounds__(kNT) beam_word_nbest_kernel(Problem P, GraphArgs g, BeamGraphArgs bg, WordLmArgs lm,
                                                               BeamWordNbestSrc src, int K, int cap, int tbits, int nbest, int P2max,
                                                               int final,
                                                               R *scores, R *escores, R *gscores, R *lscores, long long *path,
                                                               long long *tokens, long long *tlen, long long *states,
                                                               long long *lm_states, long long *words, long long *wlen,
-                                                              long long *nhyp, long long *frames, long long *status,
-                                                              WordLookParam<LA> la) {
+                                                              long long *nhyp, long long *frames, long long *committed,
+                                                              long long *status, WordLookParam<LA> la) {
     using KT = Key<R>;
     using U = typename KT::U;
+    constexpr bool kWin = SRC == kBeamWordNbestWindow;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     __shared__ int ncand;
     unsigned long long *sp = (unsigned long long *) lds;                  // [P2max] pair << 14 | slot
@@ -73,8 +91,29 @@ __global__ void __launch_bounds__(kNT) beam_word_nbest_kernel(Problem P, GraphAr
     const int T = src.Tw, nb = src.nb;
     const R NINF = Num<R>::ninf();
     const char *wb = src.base + (size_t) b * src.per;
-    int len = src.pos_off ? *(const int *) (wb + src.pos_off) : clamp_len(P.in_len, b, T);
-    len = len < 0 ? 0 : (len > T ? T : len);
+    int len, na;
+    [[maybe_unused]] int row_top = 0, cstate0 = -1;                       // the window: the ring's row of frame pos-1, and the
+    [[maybe_unused]] long long carry0 = -1;                               // automaton state and label the collapses start from
+    if constexpr (kWin) {
+        const WordWinHdr *hdr = (const WordWinHdr *) (wb + src.pos_off);
+        long long pos = hdr->pos, base = hdr->base;
+        na = hdr->na;
+        window_header(pos, base, na, K);
+        if (tid == 0) {
+            frames[b] = pos;
+            committed[b] = base;
+            status[b] = (hdr->status & 1) | (pos >= 1 && na == 0 ? 2 : 0);
+        }
+        base = window_live_base(pos, base, T);                            // (a set that is not empty has pos <= base + W)
+        len = na > 0 ? (int) (pos - base) : 0;                            // 0 .. W: the tail may be empty, and its row still counts
+        row_top = pos >= 1 ? (int) ((pos - 1) % T) : 0;
+        carry0 = hdr->carry; cstate0 = hdr->carry_state;
+    } else {
+        len = src.pos_off ? *(const int *) (wb + src.pos_off) : clamp_len(P.in_len, b, T);
+        len = len < 0 ? 0 : (len > T ? T : len);
+        na = len >= 1 ? *(const int *) (wb + src.na_off) : 0;
+        na = na < 0 ? 0 : (na > K ? K : na);
+    }
     const R *in = P.inputs ? (const R *) P.inputs + (int64_t) b * P.is1 : nullptr;   // the stream keeps no emissions
     const R *tr = (const R *) P.transition;
     const R *sw = (const R *) g.start_w, *fw = (const R *) g.final_w, *ow = (const R *) bg.ow;
@@ -93,14 +132,14 @@ __global__ void __launch_bounds__(kNT) beam_word_nbest_kernel(Problem P, GraphAr
     bind_look<R>(f, la);
     const int Q = g.Q;
 
-    int na = len >= 1 ? *(const int *) (wb + src.na_off) : 0;
-    na = na < 0 ? 0 : (na > K ? K : na);
     int P2 = 1;
     while (P2 < na) P2 *= 2;                                              // (<= P2max: na <= K)
     if (tid == 0) {
         ncand = 0;
-        if (frames) frames[b] = len;
-        if (status) status[b] = *(const int *) (wb + src.ovf_off) != 0;
+        if constexpr (!kWin) {
+            if (frames) frames[b] = len;
+            if (status) status[b] = *(const int *) (wb + src.ovf_off) != 0;
+        }
     }
     __syncthreads();
     // ---- the ends of the last set as keys (the LM walk of a word-end pair: once, here)
@@ -147,13 +186,24 @@ __global__ void __launch_bounds__(kNT) beam_word_nbest_kernel(Problem P, GraphAr
         int k = (int) (sp[r] & ((1ull << kWordSlotBits) - 1ull));
         const int kl = k;
         long long *lsr = lm_states ? lm_states + (ob + r) * T : nullptr;
+        [[maybe_unused]] int rr = row_top;                                // (the ring: the row of frame base + t, stepped)
         for (int t = len - 1; t >= 0; --t) {
             if (k < 0 || k >= K) k = 0;                                   // (cannot happen: every kept pair stored its source's slot)
-            int q = bq[(size_t) t * K + k];
+            const size_t at = (size_t) (kWin ? rr : t) * K + k;
+            int q = bq[at];
             q = q < 0 ? 0 : (q >= Q ? Q - 1 : q);                         // (nor this: the column indexes the graph's arrays)
             cols[(size_t) t * nb + r] = q;
-            if (lsr) lsr[t] = bh[(size_t) t * K + k];
-            k = bs[(size_t) t * K + k];
+            if (lsr) lsr[t] = bh[at];
+            k = bs[at];
+            if constexpr (kWin) rr = ring_prev(rr, T);
+        }
+        if constexpr (kWin) {                                             // no forward pass: the score alone, from the pair's own sum
+            R end = set_v[kl];
+            int w;
+            if (final) (void) word_end<R, LA>(f, fw, set_h[kl], set_q[kl], set_v[kl], end, w);
+            else if constexpr (LA) end = word_prefix<R, LA>(f, set_h[kl], set_q[kl], end);
+            scores[ob + r] = end;
+            continue;
         }
         int qp = cols[r], ip = f.label[qp], h = f.lstart;
         R a = in ? in[(int64_t) ip * P.is2] : NINF;
@@ -214,14 +264,17 @@ __global__ void __launch_bounds__(kNT) beam_word_nbest_kernel(Problem P, GraphAr
                 if (ls) ls[t] = -1;
             }
             if (lane == 0) {
-                scores[ob + r] = NINF; gscores[ob + r] = NINF; lscores[ob + r] = NINF;
-                if (escores) escores[ob + r] = NINF;
+                scores[ob + r] = NINF;
+                if constexpr (!kWin) {
+                    gscores[ob + r] = NINF; lscores[ob + r] = NINF;
+                    if (escores) escores[ob + r] = NINF;
+                }
                 tlen[ob + r] = 0; wlen[ob + r] = 0;
             }
             continue;
         }
         int base = 0, wbase = 0;
-        long long carry = -1;
+        long long carry = kWin ? carry0 : -1;
         int carry_q = -1;
         for (int c0 = 0; c0 < len; c0 += 64) {
             const int t = c0 + lane;
@@ -242,19 +295,34 @@ __global__ void __launch_bounds__(kNT) beam_word_nbest_kernel(Problem P, GraphAr
             if (keep) tk[base + pre] = cur;
             base += __popcll(m);
             // a separator edge is the one way into the separator's product state: the word is the one that ends in the node before
-            const bool wend = keep && t >= 1 && cur == f.sep;
+            // (the window: the label before column 0 is the last committed one, and there is none before the first frame)
+            const bool wend = keep && cur == f.sep && (kWin ? prv >= 0 : t >= 1);
             const unsigned long long mw = __ballot(wend);
             const int wpre = __popcll(mw & ((1ull << lane) - 1ull));
-            if (wend) wd[wbase + wpre] = f.wos[f.state[qv]];
+            if constexpr (kWin) {                                         // ... and its automaton state the carried one
+                if (wend) wd[wbase + wpre] = f.wos[t >= 1 ? f.state[qv] : ((unsigned) cstate0 < (unsigned) src.S ? cstate0 : 0)];
+            } else if (wend) wd[wbase + wpre] = f.wos[f.state[qv]];
             wbase += __popcll(mw);
             carry = __shfl(cur, 63);
             carry_q = __shfl(q, 63);
         }
-        if (final && lane == 0) {                                         // the word of the last step (every row has an end)
-            const int s = f.state[cols[(size_t) (len - 1) * nb + r]];
-            if (s != 0) wd[wbase] = f.wos[s];
+        if constexpr (kWin) {
+            if (final) {                                                  // the word of the last step, from the set: the tail may be empty
+                int q = set_q[(int) (sp[r] & ((1ull << kWordSlotBits) - 1ull))];
+                q = q < 0 ? 0 : (q >= Q ? Q - 1 : q);
+                const int s = f.state[q], wfin = s != 0 ? f.wos[s] : -1;
+                if (wfin >= 0 && wbase < T) {                             // (a path that ends in a word has fewer separator edges than frames)
+                    if (lane == 0) wd[wbase] = wfin;
+                    ++wbase;
+                }
+            }
+        } else {
+            if (final && lane == 0) {                                     // the word of the last step (every row has an end)
+                const int s = f.state[cols[(size_t) (len - 1) * nb + r]];
+                if (s != 0) wd[wbase] = f.wos[s];
+            }
+            if (final) wbase += f.state[cols[(size_t) (len - 1) * nb + r]] != 0;
         }
-        if (final) wbase += f.state[cols[(size_t) (len - 1) * nb + r]] != 0;
         for (int t = base + lane; t < T; t += 64) tk[t] = -1;
         for (int t = wbase + lane; t < T; t += 64) wd[t] = -1;
         for (int t = len + lane; t < T; t += 64) {
@@ -266,22 +334,23 @@ __global__ void __launch_bounds__(kNT) beam_word_nbest_kernel(Problem P, GraphAr
     }
 }
 
-template <typename R, bool LA>
+template <typename R, bool LA, int SRC = kBeamWordNbestRows>
 hipError_t launch_nbest_kernel(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
                                const WordLookParam<LA> &look, const BeamWordNbestSrc &src, int B, int K, int nbest, int final,
                                void *scores, void *escores, void *gscores, void *lscores, long long *path, long long *tokens,
                                long long *tlen, long long *states, long long *lm_states, long long *words, long long *wlen,
-                               long long *num_hyps, long long *frames, long long *status, hipStream_t stream) {
+                               long long *num_hyps, long long *frames, long long *status, hipStream_t stream,
+                               long long *committed = nullptr) {
     int P2 = 1;
     while (P2 < K) P2 *= 2;
     const size_t dyn = (size_t) P2 * (8 + sizeof(typename Key<R>::U));
     const int cap = beam_word_cap(K, BG.max_out, BG.num_start);
-    const void *fn = (const void *) beam_word_nbest_kernel<R, LA>;
+    const void *fn = (const void *) beam_word_nbest_kernel<R, LA, SRC>;
     if (dyn + 64 > 64 * 1024) (void) hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) dyn);
-    hipLaunchKernelGGL((beam_word_nbest_kernel<R, LA>), dim3(B), dim3(kNT), dyn, stream, P, G, BG, LM, src, K, cap, word_table_bits(cap),
-                       nbest, P2, final,
+    hipLaunchKernelGGL((beam_word_nbest_kernel<R, LA, SRC>), dim3(B), dim3(kNT), dyn, stream, P, G, BG, LM, src, K, cap,
+                       word_table_bits(cap), nbest, P2, final,
                        (R *) scores, (R *) escores, (R *) gscores, (R *) lscores, path, tokens, tlen, states, lm_states, words,
-                       wlen, num_hyps, frames, status, look);
+                       wlen, num_hyps, frames, committed, status, look);
     return hipGetLastError();
 }
 
@@ -460,5 +529,43 @@ template hipError_t launch_beam_word_stream_nbest_la<double>(const GraphArgs &, 
                                                              void *, void *, void *, long long *, long long *, long long *,
                                                              long long *, long long *, long long *, long long *, long long *,
                                                              long long *, long long *, hipStream_t);
+
+size_t beam_word_window_nbest_work_bytes(int W, int B, int K, int nbest) {
+    return (size_t) B * a256((size_t) W * (nbest < K ? nbest : K) * 4);
+}
+
+// The kernel over a window state: the slot is a word stream's of W frames with the rows kept as rings and WordWinHdr at lay.hdr.
+template <typename R>
+hipError_t launch_beam_word_window_nbest(const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                                         const WordLookArgs *LA, int S, int K, int W, int B, const void *state, int final,
+                                         int nbest, void *work, void *scores, long long *path, long long *tokens, long long *tlen,
+                                         long long *states, long long *lm_states, long long *words, long long *wlen,
+                                         long long *num_hyps, long long *frames, long long *committed, long long *status,
+                                         hipStream_t stream) {
+    const int cap = beam_word_cap(K, BG.max_out, BG.num_start);
+    const BeamStreamLayout lay = beam_word_window_layout(sizeof(R), W, K, cap);
+    BeamWordNbestSrc src{};
+    src.base = (const char *) state; src.per = lay.per; src.set_off = lay.set; src.pos_off = lay.hdr;
+    src.nb = nbest < K ? nbest : K;
+    src.cols = (char *) work; src.cols_per = a256((size_t) W * src.nb * 4); src.Tw = W; src.S = S;
+    Problem P{};                                                            // no emissions, no lengths: the state has both
+    P.T = W; P.B = B; P.N = 0;
+    if (LA)
+        return launch_nbest_kernel<R, true, kBeamWordNbestWindow>(P, G, BG, LM, *LA, src, B, K, nbest, final != 0, scores, nullptr,
+                                                                  nullptr, nullptr, path, tokens, tlen, states, lm_states, words,
+                                                                  wlen, num_hyps, frames, status, stream, committed);
+    return launch_nbest_kernel<R, false, kBeamWordNbestWindow>(P, G, BG, LM, WordNoLook{}, src, B, K, nbest, final != 0, scores,
+                                                               nullptr, nullptr, nullptr, path, tokens, tlen, states, lm_states,
+                                                               words, wlen, num_hyps, frames, status, stream, committed);
+}
+#define ASG_BEAM_WORD_WINDOW_NBEST_INST(R)                                                                                      \
+    template hipError_t launch_beam_word_window_nbest<R>(const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &,           \
+                                                         const WordLookArgs *, int, int, int, int, const void *, int, int, void *, \
+                                                         void *, long long *, long long *, long long *, long long *, long long *, \
+                                                         long long *, long long *, long long *, long long *, long long *,        \
+                                                         long long *, hipStream_t);
+ASG_BEAM_WORD_WINDOW_NBEST_INST(float)
+ASG_BEAM_WORD_WINDOW_NBEST_INST(double)
+#undef ASG_BEAM_WORD_WINDOW_NBEST_INST
 
 }  // namespace asg

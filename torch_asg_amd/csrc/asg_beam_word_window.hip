@@ -45,12 +45,8 @@ namespace {
 constexpr size_t kWinCtlOff = (kWordCtlOff + sizeof(WordCtl) + 63) & ~(size_t) 63;
 constexpr size_t kWinOutOff = kWinCtlOff + 64;
 
-// The header of a slot.
-struct WinHdr {
-    long long pos, base;
-    int na, carry, carry_state, status;
-};
-static_assert(sizeof(WinHdr) <= 256, "header");
+// The header of a slot (asg_beam_window_common.h has it, for the n-best kernel that reads it).
+using WinHdr = WordWinHdr;
 
 // What a commit attempt shares.
 struct WinCtl {

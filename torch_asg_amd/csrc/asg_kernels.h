@@ -285,14 +285,20 @@ size_t beam_word_nbest_work_bytes(int elem, int T, int B, int K, int cap, int nb
 size_t beam_word_stream_nbest_work_bytes(int max_frames, int B, int K, int nbest);
 // Where a search left its results for the n-best kernel.  Slot b's block starts at base + b * per: the [Tw][K] rows bq / bh / bs
 // at its front; the set (values [K], product states [K], LM states [K]) at set_off; int32 |A| at na_off; the length from the
-// problem's lengths (pos_off == 0) or the int32 at pos_off; with ovf_off, the stream's overflow word.
+// problem's lengths (pos_off == 0) or the int32 at pos_off; with ovf_off, the stream's overflow word.  A window state
+// (kBeamWordNbestWindow) has its header -- int64 pos, int64 base, int32 |A|, carry, carry_state, status -- at pos_off instead, its
+// rows are rings (Tw = W, frame u in row u mod W), and S is the number of automaton states word_of_state is indexed by.
 struct BeamWordNbestSrc {
     const char *base;
     size_t per, set_off, na_off, pos_off, ovf_off;
     char *cols;                    // slot b's [Tw][nb] column block at cols + b * cols_per
     size_t cols_per;
     int Tw, nb;
+    int S;
 };
+// The kernel's compile-time source.  kBeamWordNbestRows: rows from frame 0 on -- the one-shot workspace and the stream state, which
+// one instantiation has always told apart by pos_off.  kBeamWordNbestWindow: the ring of a window state.
+enum { kBeamWordNbestRows = 0, kBeamWordNbestWindow = 1 };
 // the n-best kernel alone, one-shot, over what a search left at `src` (LA: that search's look-ahead, or NULL)
 template <typename R>
 hipError_t launch_beam_word_nbest_over(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
@@ -371,6 +377,17 @@ hipError_t launch_beam_word_window_result(const GraphArgs &G, const BeamGraphArg
                                           long long *tlen, long long *states, long long *lm_states, long long *words,
                                           long long *wlen, long long *frames, long long *committed, long long *status,
                                           hipStream_t stream);
+// The n-best kernel of asg_beam_word_nbest.hip over a window state (read only): asg_beam_word_window_nbest, with LA
+// asg_beam_word_window_nbest_la.  Every row is the uncommitted tail of its chain, [B][nbest][W]; no sums.  work: [B] blocks of
+// a256(W * nb * 4) bytes.  path / states / lm_states may be null.
+size_t beam_word_window_nbest_work_bytes(int W, int B, int K, int nbest);
+template <typename R>
+hipError_t launch_beam_word_window_nbest(const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                                         const WordLookArgs *LA, int S, int K, int W, int B, const void *state, int final,
+                                         int nbest, void *work, void *scores, long long *path, long long *tokens, long long *tlen,
+                                         long long *states, long long *lm_states, long long *words, long long *wlen,
+                                         long long *num_hyps, long long *frames, long long *committed, long long *status,
+                                         hipStream_t stream);
 
 // ---- The n best final hypotheses of that search, with the score split (asg_beam_nbest.hip): asg_beam_decode_graph_nbest.
 // One utterance's workspace: the beam search's own layout at the front, then (byte offsets, each part 256-byte aligned) fin

@@ -523,6 +523,11 @@ BeamWordWindowResult = collections.namedtuple("BeamWordWindowResult", ["scores",
                                                                        "status"])
 
 
+BeamWordWindowNbest = collections.namedtuple("BeamWordWindowNbest", ["scores", "tokens", "token_lengths", "words", "word_lengths",
+                                                                     "num_hyps", "path", "states", "lm_states", "frames",
+                                                                     "committed", "status"])
+
+
 class BeamWordWindowStream(_Stream):
     """`BeamWordStream` in bounded memory, for utterances without an end in sight: the beam search over pairs (LM history,
     lexicon product state) with the word LM composed on the fly, the back-pointers kept only for a window of `window` frames,
@@ -550,7 +555,8 @@ class BeamWordWindowStream(_Stream):
     arguments are `BeamWordStream`'s (`dtype` None: the transition's), `lookahead` included
     (include/asg_hip.h::asg_beam_word_window_advance_la: the forced commit then follows the best prefix by value minus
     look-ahead, everything above holds with `beam_decode_words(..., lookahead=)` in the place of `beam_decode_words`); there is
-    no bound on the number of frames and no n-best.
+    no bound on the number of frames.  `result_nbest` gives the n best hypotheses as their uncommitted tails, with
+    `BeamWordStream.result_nbest`'s scores, with or without a look-ahead.
     """
     _API, _WIDE, _NARROW = "asg_beam_word_window", 5, 5
     _check_automaton, _compile = BeamWordStream._check_automaton, BeamWordStream._compile      # the automaton is BeamWordStream's,
@@ -560,6 +566,7 @@ class BeamWordWindowStream(_Stream):
                  beam_threshold=float("inf"), lm_weight=1.0, word_score=0.0, token_score=0.0, dtype=None, device=None,
                  lookahead=None):
         self.lm_weight, self.word_score, self.token_score, self.lookahead = lm_weight, word_score, token_score, lookahead
+        self._nbest_work = {}                                  # nbest -> the scratch of result_nbest (not part of the state)
         super().__init__(transition, (lexicon, word_lm), batch_size, (window, commit_every), beam_size, beam_threshold,
                          transition.dtype if dtype is None else dtype, device)
         self.window, self.commit_every = self._shape
@@ -594,6 +601,56 @@ class BeamWordWindowStream(_Stream):
         final as for `BeamWordStream.result`: final=True appends the word of a path that ends in a word-end node.  A slot
         without frames, with an empty beam or without a finite score: -inf, -1, 0."""
         return self._result(final)
+
+    def result_nbest(self, nbest, final=False, return_alignments=False):
+        """The `nbest` best hypotheses of every slot, each as its uncommitted TAIL, without changing the state -> a named tuple
+          scores [B, nbest], the scores of the whole hypotheses: `BeamWordStream.result_nbest`'s at equal position, bit for bit
+          (with a look-ahead a prefix score is taken without the estimate it still carries, as in `result`); tokens, words
+          [B, nbest, window] int64, -1 behind the data: the tokens and words of the row's tail, started from the last committed
+          label and automaton state -- a separator on the first uncommitted frame gives its word here, once -- and with
+          final=True the word of a row that ends in a word-end node, also behind an empty tail; token_lengths, word_lengths
+          [B, nbest]; num_hyps [B]; path, states, lm_states [B, nbest, window] with `return_alignments`, else None: the frames
+          committed .. frames-1 on the row's own chain; frames, committed, status [B] as `result`.
+        Row 0 equals `result(final)`.  While bit 0 of `status` is clear, what `advance` has committed followed by a row's tail is
+        that row of `BeamWordStream.result_nbest` -- a commit by convergence is an ancestor of every later hypothesis; after a
+        forced commit the rows are still their own chains, but need not continue the committed prefix.  A tail may be empty
+        (everything is committed): the row still counts.  There are no graph_scores or lm_scores: the sums of the committed part
+        are gone, and the edge into the first tail frame needs the pair of the frame before it, which the window does not keep.
+        One launch (include/asg_hip.h::asg_beam_word_window_nbest, with a look-ahead asg_beam_word_window_nbest_la), at most
+        `window` steps per row; the scratch is kept on the stream per `nbest`, so a captured call replays.  nbest < 1 raises
+        ValueError, nbest > 8192 RuntimeError."""
+        if int(nbest) < 1:
+            raise ValueError("torch_asg_amd: nbest must be >= 1, got %d" % int(nbest))
+        nbest = min(int(nbest), (1 << 31) - 1)
+        be = _asg.native()
+        L = _lib.lib()
+        B, dev, W = self.batch_size, self.device, self.window
+        with be._guard(dev):
+            what = "asg_beam_word_window_nbest" + ("" if self.lookahead is None else "_la")
+            fn = getattr(L, what)
+
+            def call(work, nbytes, *outs):
+                return fn(None, *self._views, *self._look, B, self.beam_size, *self._shape, self._state.data_ptr(),
+                          self._state.numel(), 1 if final else 0, nbest, work, nbytes, *outs)
+            work = self._nbest_work.get(nbest)
+            if work is None:
+                abi_dtype = _lib.ASG_DTYPE_F32 if self.dtype == torch.float32 else _lib.ASG_DTYPE_F64
+                nbytes = int(L.asg_beam_word_window_nbest_work_bytes(*self._views, B, abi_dtype, self.beam_size, *self._shape,
+                                                                     nbest))
+                if nbytes == 0:                                # the library refuses the arguments: its call says why
+                    _lib.check(call(None, 0, *(None,) * 12, 0, None), what)
+                work = self._nbest_work[nbest] = be._buf(nbytes, dev)
+            scores = torch.empty(B, nbest, dtype=self.dtype, device=dev)
+            wide = torch.empty(2, B, nbest, W, dtype=torch.int64, device=dev)  # tokens, words
+            align = torch.empty(3, B, nbest, W, dtype=torch.int64, device=dev) if return_alignments else (None,) * 3
+            lengths = torch.empty(2, B, nbest, dtype=torch.int64, device=dev)  # token_lengths, word_lengths
+            narrow = torch.empty(4, B, dtype=torch.int64, device=dev)          # num_hyps, frames, committed, status
+            al = lambda i: align[i].data_ptr() if return_alignments else None      # noqa: E731
+            _lib.check(call(work.data_ptr(), work.numel(), scores.data_ptr(), al(0), wide[0].data_ptr(), lengths[0].data_ptr(),
+                            al(1), al(2), wide[1].data_ptr(), lengths[1].data_ptr(), *[t.data_ptr() for t in narrow], 0,
+                            be._stream(dev)), what)
+        return BeamWordWindowNbest(scores, wide[0], lengths[0], wide[1], lengths[1], narrow[0], align[0], align[1], align[2],
+                                   narrow[1], narrow[2], narrow[3])
 
     @staticmethod
     def _outputs(scores, wide, narrow):
