@@ -44,7 +44,10 @@ SYMBOLS = ["asg_hip_version", "asg_hip_strerror", "asg_ctx_create", "asg_ctx_des
            "asg_beam_graph_confidence_work_bytes", "asg_beam_graph_confidence",
            "asg_beam_graph_nbest_confidence_work_bytes", "asg_beam_graph_nbest_confidence",
            "asg_beam_stream_nbest_work_bytes", "asg_beam_stream_nbest", "asg_beam_window_nbest_work_bytes", "asg_beam_window_nbest",
-           "asg_beam_word_window_nbest_work_bytes", "asg_beam_word_window_nbest", "asg_beam_word_window_nbest_la"]
+           "asg_beam_word_window_nbest_work_bytes", "asg_beam_word_window_nbest", "asg_beam_word_window_nbest_la",
+           "asg_beam_conf_stream_state_bytes", "asg_beam_conf_stream_reset", "asg_beam_conf_stream_advance",
+           "asg_beam_conf_stream_result", "asg_beam_conf_stream_nbest_work_bytes", "asg_beam_conf_stream_nbest",
+           "asg_beam_conf_stream_confidence"]
 ABI_VERSION = 230        # include/asg_hip.h: ASG_HIP_VERSION this package was written against
 
 
@@ -210,6 +213,15 @@ def lib():
     L.asg_beam_graph_confidence_work_bytes.restype = sz
     L.asg_beam_graph_confidence_work_bytes.argtypes = [pp, blp, ci]
     L.asg_beam_graph_confidence.argtypes = [vp, pp, blp, ci, ctypes.c_double, ci, vp, sz] + [vp] * 8 + [ci, vp]
+    L.asg_beam_conf_stream_state_bytes.restype = sz
+    L.asg_beam_conf_stream_state_bytes.argtypes = [blp, i64, ci, ci, i64]
+    L.asg_beam_conf_stream_reset.argtypes = [vp, blp, i64, ci, i64, vp, sz, vp, ci, vp]
+    L.asg_beam_conf_stream_advance.argtypes = [vp, pp, blp, ci, ctypes.c_double, i64, vp, sz, ci, vp]
+    L.asg_beam_conf_stream_result.argtypes = [vp, blp, i64, ci, i64, vp, sz, ci, vp, vp, vp, vp, vp, vp, vp, ci, vp]
+    L.asg_beam_conf_stream_nbest_work_bytes.restype = sz
+    L.asg_beam_conf_stream_nbest_work_bytes.argtypes = [blp, i64, ci, ci, i64, ci]
+    L.asg_beam_conf_stream_nbest.argtypes = [vp, blp, i64, ci, i64, vp, sz, ci, ci, vp, sz] + [vp] * 9 + [ci, vp]
+    L.asg_beam_conf_stream_confidence.argtypes = [vp, blp, i64, ci, i64, vp, sz, vp, ctypes.POINTER(i64), ci, ci] + [vp] * 10 + [ci, vp]
     L.asg_beam_graph_nbest_confidence_work_bytes.restype = sz
     L.asg_beam_graph_nbest_confidence_work_bytes.argtypes = [pp, blp, ci, ci]
     L.asg_beam_graph_nbest_confidence.argtypes = [vp, pp, blp, ci, ctypes.c_double, ci, ci, vp, sz] + [vp] * 11 + [ci, vp]

@@ -2138,11 +2138,11 @@ class ASGLoss(nn.Module):
                                                   lm_weight, token_score, return_alignments, frame_tolerance, max_work_bytes)
 
     def beam_stream(self, graph, batch_size, max_frames, beam_size=256, beam_threshold=float("inf"), lm_weight=1.0,
-                    token_score=0.0):
+                    token_score=0.0, keep_lattice=False):
         """A streaming beam decoder under this module's transition matrix (read again at every chunk): see
-        `torch_asg_amd.BeamStream`."""
+        `torch_asg_amd.BeamStream`.  `keep_lattice=True`: the stream keeps its lattice and has `result_confidence`."""
         return BeamStream(self.transition, graph, batch_size, max_frames, beam_size, beam_threshold, lm_weight, token_score,
-                          self.transition.dtype, self.transition.device)
+                          self.transition.dtype, self.transition.device, keep_lattice)
 
     def beam_word_stream(self, lexicon, word_lm, batch_size, max_frames, beam_size=256, beam_threshold=float("inf"), lm_weight=1.0,
                          word_score=0.0, token_score=0.0, lookahead=None):
@@ -2321,4 +2321,4 @@ class ASGLoss(nn.Module):
 # the streaming decoders (stream.py looks this module's `native` up at every call, so it is imported once the module stands)
 from .stream import (BeamStream, BeamStreamResult, BeamWordStream, BeamWordStreamResult, BeamWordStreamNbest,  # noqa: E402,F401
                      BeamWindowStream, BeamWindowCommit, BeamWindowResult, BeamWordWindowStream, BeamWordWindowCommit,
-                     BeamWordWindowResult, BeamStreamNbest, BeamWindowNbest, BeamWordWindowNbest)
+                     BeamWordWindowResult, BeamStreamNbest, BeamWindowNbest, BeamWordWindowNbest, BeamStreamConfidence)

@@ -1607,6 +1607,174 @@ int asg_beam_graph_confidence(asg_ctx *ctx, const asg_problem *p, const asg_toke
                                  normalisers, (hipStream_t) stream)));
 }
 
+// The lattice-keeping stream: the checks of a plain stream state through the beam view, then those of the token confidences
+// through a problem of max_frames frames without targets (its emissions are not read).
+static int check_beam_conf_stream(const asg_token_graph_beam_loss *gl, int64_t B, int dtype, int beam_size, int64_t max_frames) {
+    if (!gl) return ASG_ERR_INVALID;
+    int rc = check_beam_stream(gl->beam, B, dtype, beam_size, max_frames);
+    if (rc) return rc;
+    asg_problem q{};
+    q.inputs = gl; q.transition = gl;
+    q.T = max_frames; q.B = B; q.N = gl->beam->graph->N; q.S = 1; q.dtype = dtype;
+    return check_beam_loss(&q, gl, beam_size);
+}
+
+static size_t beam_conf_stream_bytes(const asg_token_graph_beam_loss *gl, int64_t B, int dtype, int beam_size, int64_t max_frames) {
+    const asg_token_graph_beam *gb = gl->beam;
+    const int Q = (int) gb->graph->Q, K = beam_graph_k(Q, beam_size);
+    return beam_conf_stream_state_bytes(dtype == ASG_DTYPE_F64 ? 8 : 4, (int) max_frames, (int) B, Q, K,
+                                        beam_graph_cap(Q, K, gb->max_out, (int) gb->num_start), (int) gb->graph->N);
+}
+
+// the stride of a slot, for the plain stream's result and n-best kernels
+static size_t beam_conf_stream_per(const asg_token_graph_beam_loss *gl, int dtype, int beam_size, int64_t max_frames) {
+    return beam_conf_stream_bytes(gl, 1, dtype, beam_size, max_frames);
+}
+
+size_t asg_beam_conf_stream_state_bytes(const asg_token_graph_beam_loss *gl, int64_t B, int dtype, int beam_size,
+                                        int64_t max_frames) {
+    if (check_beam_conf_stream(gl, B, dtype, beam_size, max_frames) != ASG_OK) return 0;
+    return beam_conf_stream_bytes(gl, B, dtype, beam_size, max_frames);
+}
+
+int asg_beam_conf_stream_reset(asg_ctx *ctx, const asg_token_graph_beam_loss *gl, int64_t B, int beam_size, int64_t max_frames,
+                               void *state, size_t state_bytes, const uint8_t *mask, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    if (!gl || !gl->beam || !gl->beam->graph) return ASG_ERR_INVALID;
+    const asg_token_graph_beam *gb = gl->beam;
+    const int dtype = gb->graph->dtype;
+    int rc = check_beam_conf_stream(gl, B, dtype, beam_size, max_frames);
+    if (rc) return rc;
+    if (!state) return ASG_ERR_INVALID;
+    if (state_bytes < beam_conf_stream_bytes(gl, B, dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
+    const GraphArgs G = to_graph_args(gb->graph);
+    return hip_status(launch_beam_conf_stream_reset(dtype == ASG_DTYPE_F64 ? 8 : 4, G, to_beam_graph_args(gb),
+                                                    beam_graph_k(G.Q, beam_size), (int) max_frames, (int) B, (int) gb->graph->N,
+                                                    state, mask, (hipStream_t) stream));
+}
+
+int asg_beam_conf_stream_advance(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam_loss *gl, int beam_size,
+                                 double beam_threshold, int64_t max_frames, void *state, size_t state_bytes, int flags,
+                                 void *stream) {
+    (void) ctx; (void) flags;
+    if (!p) return ASG_ERR_INVALID;
+    int rc = check_beam_conf_stream(gl, p->B, p->dtype, beam_size, max_frames);
+    if (rc) return rc;
+    const asg_token_graph_beam *gb = gl->beam;
+    if (p->T < 0 || p->N != gb->graph->N) return ASG_ERR_INVALID;
+    if (p->T > 0 && (rc = check_beam_graph(p, gb, beam_size)) != ASG_OK) return rc;
+    if (!(beam_threshold >= 0.0)) return ASG_ERR_INVALID;                  // negative or NaN
+    if (!state) return ASG_ERR_INVALID;
+    if (state_bytes < beam_conf_stream_bytes(gl, p->B, p->dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
+    if (p->T == 0) return ASG_OK;                                          // no frame: the state stays as it is
+    const Problem P = to_problem(p);
+    const GraphArgs G = to_graph_args(gb->graph);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    const int K = beam_graph_k(G.Q, beam_size);
+    return hip_status(ASG_DISPATCH(p, launch_beam_conf_stream_advance<float>(P, G, BG, K, beam_threshold, (int) max_frames, state,
+                                                                             (hipStream_t) stream),
+                                   launch_beam_conf_stream_advance<double>(P, G, BG, K, beam_threshold, (int) max_frames, state,
+                                                                           (hipStream_t) stream)));
+}
+
+int asg_beam_conf_stream_result(asg_ctx *ctx, const asg_token_graph_beam_loss *gl, int64_t B, int beam_size, int64_t max_frames,
+                                const void *state, size_t state_bytes, int final, void *scores, int64_t *path, int64_t *tokens,
+                                int64_t *token_lengths, int64_t *states, int64_t *frames, int64_t *status, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    if (!gl || !gl->beam || !gl->beam->graph) return ASG_ERR_INVALID;
+    const asg_token_graph_beam *gb = gl->beam;
+    const asg_token_graph *g = gb->graph;
+    int rc = check_beam_conf_stream(gl, B, g->dtype, beam_size, max_frames);
+    if (rc) return rc;
+    if (!state || !scores || !path || !tokens || !token_lengths || !states || !frames || !status) return ASG_ERR_INVALID;
+    if (state_bytes < beam_conf_stream_bytes(gl, B, g->dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
+    const GraphArgs G = to_graph_args(g);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    const int K = beam_graph_k(G.Q, beam_size);
+    const size_t per = beam_conf_stream_per(gl, g->dtype, beam_size, max_frames);
+    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
+    long long *fr = (long long *) frames, *su = (long long *) status;
+    return hip_status(ASG_DISPATCH(g, launch_beam_stream_result<float>(G, BG, K, (int) max_frames, (int) B, state, final, scores, pa,
+                                                                       tk, tl, st, fr, su, (hipStream_t) stream, per),
+                                   launch_beam_stream_result<double>(G, BG, K, (int) max_frames, (int) B, state, final, scores, pa,
+                                                                     tk, tl, st, fr, su, (hipStream_t) stream, per)));
+}
+
+static int check_beam_conf_stream_nbest(const asg_token_graph_beam_loss *gl, int64_t B, int dtype, int beam_size, int64_t max_frames,
+                                        int nbest) {
+    int rc = check_beam_conf_stream(gl, B, dtype, beam_size, max_frames);
+    if (rc) return rc;
+    if (nbest < 1) return ASG_ERR_INVALID;
+    if (nbest > kBeamMaxNbest) return ASG_ERR_UNSUPPORTED;
+    return ASG_OK;
+}
+
+size_t asg_beam_conf_stream_nbest_work_bytes(const asg_token_graph_beam_loss *gl, int64_t B, int dtype, int beam_size,
+                                             int64_t max_frames, int nbest) {
+    if (check_beam_conf_stream_nbest(gl, B, dtype, beam_size, max_frames, nbest) != ASG_OK) return 0;
+    return beam_stream_nbest_bytes(gl->beam, B, beam_size, max_frames, nbest);
+}
+
+int asg_beam_conf_stream_nbest(asg_ctx *ctx, const asg_token_graph_beam_loss *gl, int64_t B, int beam_size, int64_t max_frames,
+                               const void *state, size_t state_bytes, int final, int nbest, void *work, size_t work_bytes,
+                               void *scores, void *graph_scores, int64_t *path, int64_t *tokens, int64_t *token_lengths,
+                               int64_t *states, int64_t *num_hyps, int64_t *frames, int64_t *status, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    if (!gl || !gl->beam || !gl->beam->graph) return ASG_ERR_INVALID;
+    const asg_token_graph_beam *gb = gl->beam;
+    const asg_token_graph *g = gb->graph;
+    int rc = check_beam_conf_stream_nbest(gl, B, g->dtype, beam_size, max_frames, nbest);
+    if (rc) return rc;
+    if (!state || !work || !scores || !graph_scores || !tokens || !token_lengths || !num_hyps || !frames || !status)
+        return ASG_ERR_INVALID;
+    if (state_bytes < beam_conf_stream_bytes(gl, B, g->dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
+    if (work_bytes < beam_stream_nbest_bytes(gb, B, beam_size, max_frames, nbest)) return ASG_ERR_WORKSPACE;
+    const GraphArgs G = to_graph_args(g);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    const int K = beam_graph_k(G.Q, beam_size);
+    const size_t per = beam_conf_stream_per(gl, g->dtype, beam_size, max_frames);
+    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
+    long long *nh = (long long *) num_hyps, *fr = (long long *) frames, *su = (long long *) status;
+    return hip_status(ASG_DISPATCH(g, launch_beam_stream_nbest<float>(G, BG, K, (int) max_frames, (int) B, state, final, nbest, work,
+                                                                      scores, graph_scores, pa, tk, tl, st, nh, fr, su,
+                                                                      (hipStream_t) stream, per),
+                                   launch_beam_stream_nbest<double>(G, BG, K, (int) max_frames, (int) B, state, final, nbest, work,
+                                                                    scores, graph_scores, pa, tk, tl, st, nh, fr, su,
+                                                                    (hipStream_t) stream, per)));
+}
+
+int asg_beam_conf_stream_confidence(asg_ctx *ctx, const asg_token_graph_beam_loss *gl, int64_t B, int beam_size, int64_t max_frames,
+                                    void *state, size_t state_bytes, const void *transition, const int64_t *transition_strides,
+                                    int final, int frame_tolerance, void *scores, int64_t *path, int64_t *tokens,
+                                    int64_t *token_lengths, int64_t *states, int64_t *token_frames, void *token_confidences,
+                                    void *normalisers, int64_t *frames, int64_t *status, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    if (!gl || !gl->beam || !gl->beam->graph) return ASG_ERR_INVALID;
+    const asg_token_graph_beam *gb = gl->beam;
+    const asg_token_graph *g = gb->graph;
+    int rc = check_beam_conf_stream(gl, B, g->dtype, beam_size, max_frames);
+    if (rc) return rc;
+    if (frame_tolerance < 0) return ASG_ERR_INVALID;
+    if (frame_tolerance > kBeamConfMaxTol) return ASG_ERR_UNSUPPORTED;
+    if (!state || !transition || !transition_strides || !scores || !path || !tokens || !token_lengths || !states || !token_frames ||
+        !token_confidences || !normalisers || !frames || !status)
+        return ASG_ERR_INVALID;
+    if (state_bytes < beam_conf_stream_bytes(gl, B, g->dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
+    Problem P{};
+    P.transition = transition; P.ts0 = transition_strides[0]; P.ts1 = transition_strides[1];
+    P.T = (int) max_frames; P.B = (int) B; P.N = g->N; P.S = 1;
+    const GraphArgs G = to_graph_args(g);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    const int K = beam_graph_k(G.Q, beam_size);
+    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
+    long long *tf = (long long *) token_frames, *fr = (long long *) frames, *su = (long long *) status;
+    return hip_status(ASG_DISPATCH(g,
+        launch_beam_conf_stream_confidence<float>(P, G, BG, K, (int) max_frames, state, final, frame_tolerance, scores, pa, tk, tl, st,
+                                                  tf, token_confidences, normalisers, fr, su, (hipStream_t) stream),
+        launch_beam_conf_stream_confidence<double>(P, G, BG, K, (int) max_frames, state, final, frame_tolerance, scores, pa, tk, tl, st,
+                                                   tf, token_confidences, normalisers, fr, su, (hipStream_t) stream)));
+}
+
 // The n-best token confidences: the checks of asg_beam_graph_confidence, then those of asg_beam_decode_graph_nbest.
 static int check_beam_nbest_conf(const asg_problem *p, const asg_token_graph_beam_loss *gl, int beam_size, int nbest) {
     int rc = check_beam_conf(p, gl, beam_size);

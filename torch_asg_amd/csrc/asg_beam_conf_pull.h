@@ -16,8 +16,10 @@ namespace asg {
 namespace {
 
 // The beta pull with the token-event sink.  nb [M] / nq [M]: the dynamic LDS in front of the sink's ring (bwd_front).
-template <typename R, typename Sink>
-__device__ __forceinline__ void beam_conf_pull(const Problem &P, const typename TokenLat<R>::Args &args, char *wb, size_t beta_off,
+// Lat: TokenLat<R>, or a lattice with its edges and labels and an end term of its own (the prefix mode of the lattice-keeping
+// stream, asg_beam_stream_conf.hip); Lat::Args starts with TokenLat<R>::Args' members.
+template <typename R, typename Sink, typename Lat = TokenLat<R>>
+__device__ __forceinline__ void beam_conf_pull(const Problem &P, const typename Lat::Args &args, char *wb, size_t beta_off,
                                                R Z, int len, int last, int *nq, R *nb, Sink &sink) {
     using KeyT = int;
     const int M = args.lay.M, tid = threadIdx.x, b = blockIdx.x;
@@ -28,7 +30,7 @@ __device__ __forceinline__ void beam_conf_pull(const Problem &P, const typename 
     R *Bv = (R *) (wb + beta_off);                                             // [2][M]
     const R *in = (const R *) P.inputs + (int64_t) b * P.is1;
     const R *trm = (const R *) P.transition;
-    TokenLat<R> lat;
+    Lat lat;
     lat.bind(args);
     auto tr = [&](int i, int j) -> R { return trm[(int64_t) i * P.ts0 + (int64_t) j * P.ts1]; };
 

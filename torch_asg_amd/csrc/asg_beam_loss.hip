@@ -15,7 +15,8 @@
 //      target q pull through q's incoming CSR row and find each source in U_{t-1} by binary search in LDS; when the row is
 //      longer than |U_{t-1}| (the root of a lexicon trie) they walk U_{t-1} instead and binary-search each kept source in the
 //      row.  Max pass, then sum pass; partial results of the G lanes meet in a fixed butterfly.  The alpha of a frame goes to
-//      the workspace ([T][M] when a gradient is wanted, else two rows) and comes back into LDS with device-scope loads.
+//      the workspace ([T][M] when a gradient is wanted, else two rows) and comes back into LDS with device-scope loads.  The body
+//      of a frame is asg_beam_alpha.inc, which the catch-up of the lattice-keeping stream (asg_beam_stream_conf.hip) includes too.
 // Backward, two launches: beam_loss_bwd<R, TL, TokenLat<R>> (the mirror image through the outgoing CSR against U_{t+1} in LDS; it
 // owns beta, the label posteriors and the posteriors of every stay and edge) and beam_loss_tr_reduce.
 // Launches 3 and the backward, the end of 4 (Z_K) and every small helper are written once for this unit and
@@ -147,49 +148,7 @@ __global__ void __launch_bounds__(kBL) beam_loss_fwd(Problem P, GraphArgs g, Bea
         const int *Ut = U + (int64_t) t * M;
         R *Arow = A + (int64_t) (store ? t : (t & 1)) * M;
         const R *xt = in + (int64_t) t * P.is0;
-        const int G = subgroup(mt), per = kBL / G;
-        for (int k0 = 0; k0 < mt; k0 += per) {
-            const int k = k0 + tid / G, lg = tid % G;
-            const bool act = k < mt;
-            const int q = act ? Ut[k] : 0;
-            const int i = act ? g.label[q] : 0;
-            const int e0 = act ? g.row[q] : 0, e1 = act ? g.row[q + 1] : 0;
-            const bool by_row = e1 - e0 <= mp;
-            // every surviving candidate of q that this lane owns, in ascending source order: f(value)
-            auto visit = [&](auto f) {
-                if (!act) return;
-                if (lg == 0) {
-                    const int pos = find_sorted(pq, mp, q);
-                    if (pos >= 0) f(pa[pos] + tr(i, i));
-                }
-                if (by_row) {
-                    for (int e = e0 + lg; e < e1; e += G) {
-                        const int pos = find_sorted(pq, mp, g.src[e]);
-                        if (pos >= 0) f((pa[pos] + tr(i, g.src_label[e])) + ew[e]);
-                    }
-                } else {
-                    for (int p = lg; p < mp; p += G) {
-                        const int pos = find_sorted(g.src + e0, e1 - e0, pq[p]);
-                        if (pos >= 0) f((pa[p] + tr(i, g.src_label[e0 + pos])) + ew[e0 + pos]);
-                    }
-                }
-            };
-            R mx = NINF;
-            visit([&](R c) { mx = bmax(mx, c); });
-            mx = group_max(mx, G);
-            R s = R(0);
-            if (mx > NINF) visit([&](R c) { s += bexp(c - mx); });
-            s = group_sum(s, G);
-            if (act && lg == 0) {
-                const R x = mx > NINF ? (mx + blog(s)) + xt[(int64_t) i * P.is2] : NINF;
-                dev_store(Arow + k, x);
-            }
-        }
-        __threadfence();
-        __syncthreads();
-        for (int x = tid; x < mt; x += kBL) { pq[x] = Ut[x]; pa[x] = dev_load(Arow + x); }
-        mp = mt;
-        __syncthreads();
+#include "asg_beam_alpha.inc"       // the frame body (shared with asg_beam_stream_conf.hip)
     }
     const R Z = lattice_z<R>(mp, red, [&](int x) -> R { return pa[x] + fw[pq[x]]; });
     if (tid == 0) scores[b] = Z;

@@ -338,10 +338,11 @@ namespace {
 
 // The source of a stream (rows = max_frames) or a window (rows = W) state: both have the slot of beam_stream_layout.
 inline BeamNbestSrc stream_src(int elem, const GraphArgs &G, const BeamGraphArgs &BG, int K, int rows, const void *state, int nbest,
-                               void *work) {
+                               void *work, size_t stride = 0) {
     const BeamStreamLayout lay = beam_stream_layout(elem, rows, G.Q, K, beam_graph_cap(G.Q, K, BG.max_out, BG.num_start));
     BeamNbestSrc src{};
-    src.base = (const char *) state; src.per = lay.per; src.hdr = lay.hdr; src.set = lay.set;
+    src.base = (const char *) state; src.hdr = lay.hdr; src.set = lay.set;
+    src.per = stride ? stride : lay.per;                                    // (a slot with parts of the caller's behind it)
     src.nb = nbest < K ? nbest : K;
     src.cols = (char *) work; src.cols_per = a256((size_t) rows * src.nb * 4); src.Tw = rows;
     return src;
@@ -353,10 +354,10 @@ template <typename R>
 hipError_t launch_beam_stream_nbest(const GraphArgs &G, const BeamGraphArgs &BG, int K, int max_frames, int B, const void *state,
                                     int final, int nbest, void *work, void *scores, void *graph_scores, long long *path,
                                     long long *tokens, long long *tlen, long long *states, long long *num_hyps, long long *frames,
-                                    long long *status, hipStream_t stream) {
+                                    long long *status, hipStream_t stream, size_t stride) {
     Problem P{};                                                            // no emissions, no lengths: the state has both
     P.T = max_frames; P.B = B; P.N = 0;
-    return launch_nbest_kernel<R, kBeamNbestStream>(P, G, BG, stream_src(sizeof(R), G, BG, K, max_frames, state, nbest, work), B, K,
+    return launch_nbest_kernel<R, kBeamNbestStream>(P, G, BG, stream_src(sizeof(R), G, BG, K, max_frames, state, nbest, work, stride), B, K,
                                                     nbest, final != 0, scores, nullptr, graph_scores, path, tokens, tlen, states,
                                                     num_hyps, frames, nullptr, status, stream);
 }
@@ -374,7 +375,7 @@ hipError_t launch_beam_window_nbest(const GraphArgs &G, const BeamGraphArgs &BG,
 #define ASG_BEAM_STREAM_NBEST_INST(R)                                                                                            \
     template hipError_t launch_beam_stream_nbest<R>(const GraphArgs &, const BeamGraphArgs &, int, int, int, const void *, int, int, \
                                                     void *, void *, void *, long long *, long long *, long long *, long long *,    \
-                                                    long long *, long long *, long long *, hipStream_t);                           \
+                                                    long long *, long long *, long long *, hipStream_t, size_t);                   \
     template hipError_t launch_beam_window_nbest<R>(const GraphArgs &, const BeamGraphArgs &, int, int, int, const void *, int, int, \
                                                     void *, void *, long long *, long long *, long long *, long long *,            \
                                                     long long *, long long *, long long *, long long *, hipStream_t);

@@ -171,18 +171,19 @@ template hipError_t launch_beam_stream_advance<double>(const Problem &, const Gr
 template <typename R>
 hipError_t launch_beam_stream_result(const GraphArgs &G, const BeamGraphArgs &BG, int K, int max_frames, int B, const void *state,
                                      int final, void *scores, long long *path, long long *tokens, long long *tlen,
-                                     long long *states, long long *frames, long long *status, hipStream_t stream) {
+                                     long long *states, long long *frames, long long *status, hipStream_t stream, size_t stride) {
     const int cap = beam_graph_cap(G.Q, K, BG.max_out, BG.num_start);
-    const BeamStreamLayout lay = beam_stream_layout(sizeof(R), max_frames, G.Q, K, cap);
+    BeamStreamLayout lay = beam_stream_layout(sizeof(R), max_frames, G.Q, K, cap);
+    if (stride) lay.per = stride;                                           // (a slot with parts of the caller's behind it)
     hipLaunchKernelGGL((beam_stream_result_kernel<R>), dim3(B), dim3(kBT), 0, stream, G, K, cap, max_frames, (const char *) state,
                        lay, final, (R *) scores, path, tokens, tlen, states, frames, status);
     return hipGetLastError();
 }
 template hipError_t launch_beam_stream_result<float>(const GraphArgs &, const BeamGraphArgs &, int, int, int, const void *, int,
                                                      void *, long long *, long long *, long long *, long long *, long long *,
-                                                     long long *, hipStream_t);
+                                                     long long *, hipStream_t, size_t);
 template hipError_t launch_beam_stream_result<double>(const GraphArgs &, const BeamGraphArgs &, int, int, int, const void *, int,
                                                       void *, long long *, long long *, long long *, long long *, long long *,
-                                                      long long *, hipStream_t);
+                                                      long long *, hipStream_t, size_t);
 
 }  // namespace asg

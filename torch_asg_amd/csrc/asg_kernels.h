@@ -233,7 +233,8 @@ hipError_t launch_beam_stream_advance(const Problem &P, const GraphArgs &G, cons
 template <typename R>
 hipError_t launch_beam_stream_result(const GraphArgs &G, const BeamGraphArgs &BG, int K, int max_frames, int B, const void *state,
                                      int final, void *scores, long long *path, long long *tokens, long long *tlen,
-                                     long long *states, long long *frames, long long *status, hipStream_t stream);
+                                     long long *states, long long *frames, long long *status, hipStream_t stream,
+                                     size_t stride = 0);      // != 0: the slots lie `stride` bytes apart (asg_beam_stream_conf.hip)
 
 // ---- The same search with LM look-ahead (asg_beam_word_la.hip): asg_beam_decode_words_la.  K, cap, the table and the workspace
 // are those of launch_beam_words, stride and fin_off too; the look-ahead adds read-only arrays and nothing per utterance.
@@ -435,7 +436,7 @@ template <typename R>
 hipError_t launch_beam_stream_nbest(const GraphArgs &G, const BeamGraphArgs &BG, int K, int max_frames, int B, const void *state,
                                     int final, int nbest, void *work, void *scores, void *graph_scores, long long *path,
                                     long long *tokens, long long *tlen, long long *states, long long *num_hyps, long long *frames,
-                                    long long *status, hipStream_t stream);
+                                    long long *status, hipStream_t stream, size_t stride = 0);   // as launch_beam_stream_result's
 template <typename R>
 hipError_t launch_beam_window_nbest(const GraphArgs &G, const BeamGraphArgs &BG, int K, int W, int B, const void *state, int final,
                                     int nbest, void *work, void *scores, long long *path, long long *tokens, long long *tlen,
@@ -493,6 +494,31 @@ template <typename R>
 hipError_t launch_beam_conf(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const BeamLossArgs &L, int K, double theta,
                             int tol, void *work, void *scores, long long *path, long long *tokens, long long *tlen,
                             long long *states, long long *token_frames, void *token_conf, void *normalisers, hipStream_t stream);
+
+// ---- The streaming search with a state that keeps its lattice (asg_beam_stream_conf.hip): asg_beam_conf_stream_*.  One slot: the
+// plain stream's slot (beam_stream_layout) unchanged at the front, then (byte offsets, each part 256-byte aligned) cnt int32
+// [max_frames], the emissions [max_frames][N], nu int32 [max_frames], U int32 [max_frames][K], A [max_frames][K], beta [2][K].
+// Header word 3 is apos, the frames whose U / nu / A rows are valid.  `lat` is a BeamLossLayout (M = K, nf = 0) over those parts,
+// so TokenLat<R>::Args and beam_conf_pull take it as they take BeamConfLayout's; st.per, lat.per and per are the slot's stride.
+struct BeamConfStreamLayout {
+    BeamStreamLayout st;
+    BeamLossLayout lat;
+    size_t em, beta, per;
+};
+BeamConfStreamLayout beam_conf_stream_layout(int elem, int max_frames, int Q, int K, int cap, int N);
+size_t beam_conf_stream_state_bytes(int elem, int max_frames, int B, int Q, int K, int cap, int N);
+hipError_t launch_beam_conf_stream_reset(int elem, const GraphArgs &G, const BeamGraphArgs &BG, int K, int max_frames, int B, int N,
+                                         void *state, const unsigned char *mask, hipStream_t stream);
+template <typename R>
+hipError_t launch_beam_conf_stream_advance(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, int K, double theta,
+                                           int max_frames, void *state, hipStream_t stream);
+// P: B, N and the transition (its emissions and lengths are not read: the state has both).  Two launches: the catch-up of U / nu /
+// A from apos to pos (the only write to the state from a result path), then the hypothesis, Z and the beta pull.
+template <typename R>
+hipError_t launch_beam_conf_stream_confidence(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, int K, int max_frames,
+                                              void *state, int final, int tol, void *scores, long long *path, long long *tokens,
+                                              long long *tlen, long long *states, long long *token_frames, void *token_conf,
+                                              void *normalisers, long long *frames, long long *status, hipStream_t stream);
 
 // ---- Token confidences and start frames for every row of the n-best list (asg_beam_nbest_conf.hip):
 // asg_beam_graph_nbest_confidence.  One utterance's workspace: asg_beam_graph_confidence's layout at the front (the search's

@@ -185,6 +185,9 @@ BeamStreamResult = collections.namedtuple("BeamStreamResult", ["scores", "path",
                                                                "status"])
 BeamStreamNbest = collections.namedtuple("BeamStreamNbest", ["scores", "graph_scores", "tokens", "token_lengths", "num_hyps", "path",
                                                              "states", "frames", "status"])
+BeamStreamConfidence = collections.namedtuple("BeamStreamConfidence", ["scores", "path", "tokens", "token_lengths", "states",
+                                                                       "token_frames", "token_confidences", "normalisers", "frames",
+                                                                       "status"])
 
 
 class BeamStream(_Stream):
@@ -208,12 +211,20 @@ class BeamStream(_Stream):
     nothing and do not synchronise, so they can be captured in a graph and replayed with new chunk contents and lengths.
     `result_nbest` gives the n best hypotheses or prefixes from the same state, with the graph part of each score: the list
     `beam_decode_graph_nbest` returns for the whole utterance, without keeping the emissions or searching twice.
+
+    `keep_lattice=True` makes the state keep the lattice of the search as well (include/asg_hip.h::asg_beam_conf_stream_*: the
+    kept sets, the emissions and, lazily, alpha -- about max_frames * (N + 2 * beam_size) values more per slot), and then
+    `result_confidence` gives a confidence and a start frame per token at any point of the stream.  `advance`, `result`,
+    `result_nbest` and `reset` return what they return without it, byte for byte.
     """
     _API, _WIDE, _NARROW = "asg_beam_stream", 3, 3
 
     def __init__(self, transition, graph, batch_size, max_frames, beam_size=256, beam_threshold=float("inf"), lm_weight=1.0,
-                 token_score=0.0, dtype=torch.float32, device=None):
+                 token_score=0.0, dtype=torch.float32, device=None, keep_lattice=False):
         self.lm_weight, self.token_score = lm_weight, token_score
+        self.keep_lattice = bool(keep_lattice)
+        if self.keep_lattice:
+            self._API = "asg_beam_conf_stream"                 # the same calls in the same order over the wider state
         self._nbest_work = {}                                  # nbest -> the scratch of result_nbest (not part of the state)
         super().__init__(transition, (graph,), batch_size, (max_frames,), beam_size, beam_threshold, dtype, device)
         (self.max_frames,) = self._shape
@@ -251,6 +262,48 @@ class BeamStream(_Stream):
         so a captured call replays.  nbest < 1 raises ValueError, nbest > 8192 RuntimeError."""
         scores, gscores, tokens, tlen, nh, path, states, (frames, status) = self._token_nbest(nbest, final, return_alignments, True)
         return BeamStreamNbest(scores, gscores, tokens, tlen, nh, path, states, frames, status)
+
+    def result_confidence(self, frame_tolerance=0, final=False):
+        """`result(final)` with a confidence and a start frame for every token, from the lattice the stream kept
+        (`keep_lattice=True`; RuntimeError without it, without touching the device) -> a named tuple
+          scores, path, tokens, token_lengths, states, frames, status as `result(final)` returns them;
+          token_frames [B, max_frames] int64, the frame at which token k starts, -1 behind the tokens;
+          token_confidences [B, max_frames], the posterior, over the paths through the kept sets, that a token with this label
+          starts within `frame_tolerance` frames of that frame, 0 behind the tokens; normalisers [B], log of the mass of all paths.
+        final=True: `beam_decode_graph_confidence`'s result for the utterance so far, bit for bit, for any chunking and wherever
+        `result_confidence` was called in between.  final=False: paths may end in any kept state of the last frame, without a
+        final weight.  `transition` must not change within an utterance.  Two launches, no synchronisation: the call captures and
+        replays.  The first of them brings the stored alpha rows up to the frames consumed -- the only write to the state from a
+        result call; every frame's alpha is computed once.  frame_tolerance < 0 raises ValueError, > 64 RuntimeError."""
+        if not self.keep_lattice:
+            raise RuntimeError("torch_asg_amd: result_confidence needs the lattice of the search: build the stream with "
+                               "keep_lattice=True")
+        if int(frame_tolerance) < 0:
+            raise ValueError("torch_asg_amd: frame_tolerance must be >= 0, got %d" % int(frame_tolerance))
+        tol = min(int(frame_tolerance), (1 << 31) - 1)
+        be = _asg.native()
+        L = _lib.lib()
+        B, dev, T = self.batch_size, self.device, self.max_frames
+        transition = self.transition
+        with be._guard(dev):
+            real = torch.empty(2, B, dtype=self.dtype, device=dev)                 # scores, normalisers
+            wide = torch.empty(4, B, T, dtype=torch.int64, device=dev)             # path, tokens, states, token_frames
+            conf = torch.empty(B, T, dtype=self.dtype, device=dev)
+            narrow = torch.empty(3, B, dtype=torch.int64, device=dev)              # token_lengths, frames, status
+            ts = (ctypes.c_int64 * 2)(*transition.stride())
+            _lib.check(L.asg_beam_conf_stream_confidence(
+                None, *self._views, B, self.beam_size, T, self._state.data_ptr(), self._state.numel(), transition.data_ptr(), ts,
+                1 if final else 0, tol, real[0].data_ptr(), wide[0].data_ptr(), wide[1].data_ptr(), narrow[0].data_ptr(),
+                wide[2].data_ptr(), wide[3].data_ptr(), conf.data_ptr(), real[1].data_ptr(), narrow[1].data_ptr(),
+                narrow[2].data_ptr(), 0, be._stream(dev)), "asg_beam_conf_stream_confidence")
+        return BeamStreamConfidence(real[0], wide[0], wide[1], narrow[0], wide[2], wide[3], conf, real[1], narrow[1], narrow[2])
+
+    def _compile(self):
+        if not self.keep_lattice:
+            return super()._compile()
+        from . import graph as _graph
+        compiled = self.graph.compile_beam_loss(self.device, self.dtype, self.lm_weight, self.token_score)
+        return (_graph.abi_graph_beam_loss(compiled),), compiled
 
     @staticmethod
     def _outputs(scores, wide, narrow):
