@@ -1445,6 +1445,101 @@ int asg_beam_conf_stream_confidence(asg_ctx *ctx, const asg_token_graph_beam_los
                                     int64_t *token_lengths, int64_t *states, int64_t *token_frames, void *token_confidences,
                                     void *normalisers, int64_t *frames, int64_t *status, int flags, void *stream);
 
+/* ---- the LATTICE-KEEPING word-LM beam stream: asg_beam_word_stream_* with a state that also keeps what asg_beam_words_confidence
+ * computes its word confidences from, so that a stream over a lexicon and a word n-gram LM gives a confidence and an end frame per
+ * word while the utterance is arriving (additions only; asg_beam_word_stream_* and its state formula are unchanged).  The family
+ * takes the word stream's own views, asg_token_graph_beam + asg_word_lm (+ asg_word_lookahead behind them in the _la forms), as
+ * asg_beam_words_confidence takes them, in asg_beam_word_stream_*'s argument order and with its error order.
+ *
+ * STATE.  With a256(x) = x rounded up to 256, e = 4 or 8 (the dtype), T = max_frames, K = beam_size, N = gb->graph->N, one slot is
+ *     per = P + a256(4 T) + a256(e T N) + a256(4 T) + a256(8 T K) + a256(e T K) + a256(2 e K),
+ * where P = asg_beam_word_stream_state_bytes(gb, lm, 1, dtype, beam_size, max_frames) is the plain word stream's slot, unchanged, at
+ * the front (the search's workspace, the header, the stored set), and behind it: cnt int32 [T] (|A_t| of every consumed frame),
+ * the emissions [T][N], nu int32 [T], U u64 [T][K] (the pairs of A_t as keys h << qbits | q, ascending), A [T][K] (alpha), beta
+ * [2][K].  The header's fourth int32 word is apos, the number of frames whose U / nu / A rows are valid (0 <= apos <= pos).
+ * asg_beam_word_conf_stream_state_bytes = B * per; no term in H, V, A or Q.  The state is the same with and without a look-ahead.
+ *
+ * _reset, _advance[_la], _result[_la], _nbest[_la] and _nbest_work_bytes: asg_beam_word_stream_*'s, argument for argument and bit
+ * for bit (the frames run the same device text; _result and _nbest run the plain stream's kernels over the wider slots).  _reset
+ * also sets apos = 0, a masked reset in the chosen slots only.  _advance also writes, for every frame gt it consumes, cnt[gt] =
+ * min(|A_gt|, K) -- 0 for the frames an empty beam skips -- and the frame's N emissions into row gt (a coalesced copy from the
+ * chunk's strides).
+ *
+ * _confidence[_la](final, frame_tolerance): TWO launches, no host synchronisation, no memset, no copy; it captures and replays.
+ *   (a) catch-up: for every slot U, nu and A are brought from apos up to pos (the sets are the keys of A_t sorted: no targets,
+ *       nothing forced; alpha is asg_beam_words_full_forward's push, the same device text, resumed from rows apos-1 or from the
+ *       start weights), then apos = pos.  THE ONE CALL OF THE FAMILY THAT WRITES THE STATE FROM A RESULT PATH: what it writes is
+ *       idempotent and does not depend on `final` or the tolerance -- every frame's alpha is computed once, however often
+ *       confidences are asked for -- and an _advance costs the plain one's plus a copy of N values per frame.
+ *   (b) the hypothesis, Z and the beta pull.  Let L = pos.  The lattice: the kept pair sets A_0 .. A_{L-1}, the edges and PLAIN
+ *       weights of asg_beam_words_confidence; with a look-ahead the sets are the look-ahead search's and the weights stay plain.
+ *       final = 1: everything is asg_beam_words_confidence's (asg_beam_words_confidence_la's with the same look-ahead) on x[0:L].
+ *         For ANY chunking of x[0:L], L <= max_frames, and wherever _confidence calls fall in between, _confidence(1, tol) equals
+ *         that call at tol: scores, normalisers, both lengths, word_frames and word_confidences bit for bit; the integer arrays on
+ *         the one-shot's columns and -1 beyond; the confidences 0 beyond.  No tolerance is involved.
+ *       final = 0 (prefix): a path ends in any pair of A_{L-1} with end weight 0 -- no final weight, no LM end, no final word; Z
+ *         (normalisers) is the log-sum-exp of alpha over A_{L-1}; the hypothesis is _result(final = 0)'s (with a look-ahead the
+ *         prefix of largest value without the estimate it still carries, and that value); word events are separator edges only,
+ *         at frames 1 .. L-1: the event at frame L of asg_beam_words_confidence does not exist, and word_lengths counts the
+ *         separator words.  At frame_tolerance 0, exp(scores - Z) <= confidence <= 1 up to rounding.
+ *       L = 0, an empty last set or no finite end: -inf, -inf, -1 and 0, never a NaN.  status is the overflow word, frames is L.
+ *   outputs: scores [B], path / tokens / states / lm_states / words / word_frames [B][max_frames] int64, token_lengths and
+ *   word_lengths [B], word_confidences [B][max_frames] and normalisers [B] in the dtype, frames [B], status [B].
+ *   `transition` ([N][N] in the dtype, strides in elements) MUST NOT CHANGE within an utterance for the property to hold: _advance
+ *   reads it at the chunk, the lattice pass at the call, and a change in between gives sets and weights from different matrices.
+ * Limits: asg_beam_word_stream_*'s and asg_beam_words_confidence's for T = max_frames -- a frame's set with a maximum and a sum per
+ * member must stay in LDS (beam_size <= 8179 float32, 6816 float64), so a lattice-keeping stream refuses, with
+ * ASG_ERR_UNSUPPORTED from _state_bytes (0) on, a beam_size that the plain stream accepts.  frame_tolerance in 0 .. 64: negative
+ * is ASG_ERR_INVALID, larger ASG_ERR_UNSUPPORTED; a state that is too small ASG_ERR_WORKSPACE.  float32 and float64. */
+size_t asg_beam_word_conf_stream_state_bytes(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype,
+                                             int beam_size, int64_t max_frames);
+int asg_beam_word_conf_stream_reset(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
+                                    int64_t max_frames, void *state, size_t state_bytes, const uint8_t *mask, int flags,
+                                    void *stream);
+int asg_beam_word_conf_stream_advance(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                      int beam_size, double beam_threshold, int64_t max_frames, void *state, size_t state_bytes,
+                                      int flags, void *stream);
+int asg_beam_word_conf_stream_advance_la(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                         const asg_word_lookahead *la, int beam_size, double beam_threshold, int64_t max_frames,
+                                         void *state, size_t state_bytes, int flags, void *stream);
+int asg_beam_word_conf_stream_result(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
+                                     int64_t max_frames, const void *state, size_t state_bytes, int final, void *scores,
+                                     int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *lm_states,
+                                     int64_t *words, int64_t *word_lengths, int64_t *frames, int64_t *status, int flags,
+                                     void *stream);
+int asg_beam_word_conf_stream_result_la(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                        const asg_word_lookahead *la, int64_t B, int beam_size, int64_t max_frames,
+                                        const void *state, size_t state_bytes, int final, void *scores, int64_t *path,
+                                        int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words,
+                                        int64_t *word_lengths, int64_t *frames, int64_t *status, int flags, void *stream);
+size_t asg_beam_word_conf_stream_nbest_work_bytes(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype,
+                                                  int beam_size, int64_t max_frames, int nbest);
+int asg_beam_word_conf_stream_nbest(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
+                                    int64_t max_frames, const void *state, size_t state_bytes, int final, int nbest, void *work,
+                                    size_t work_bytes, void *scores, void *graph_scores, void *lm_scores, int64_t *path,
+                                    int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words,
+                                    int64_t *word_lengths, int64_t *num_hyps, int64_t *frames, int64_t *status, int flags,
+                                    void *stream);
+int asg_beam_word_conf_stream_nbest_la(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                       const asg_word_lookahead *la, int64_t B, int beam_size, int64_t max_frames, const void *state,
+                                       size_t state_bytes, int final, int nbest, void *work, size_t work_bytes, void *scores,
+                                       void *graph_scores, void *lm_scores, int64_t *path, int64_t *tokens, int64_t *token_lengths,
+                                       int64_t *states, int64_t *lm_states, int64_t *words, int64_t *word_lengths,
+                                       int64_t *num_hyps, int64_t *frames, int64_t *status, int flags, void *stream);
+int asg_beam_word_conf_stream_confidence(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B,
+                                         int beam_size, int64_t max_frames, void *state, size_t state_bytes, const void *transition,
+                                         const int64_t *transition_strides, int final, int frame_tolerance, void *scores,
+                                         int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *lm_states,
+                                         int64_t *words, int64_t *word_lengths, int64_t *word_frames, void *word_confidences,
+                                         void *normalisers, int64_t *frames, int64_t *status, int flags, void *stream);
+int asg_beam_word_conf_stream_confidence_la(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                            const asg_word_lookahead *la, int64_t B, int beam_size, int64_t max_frames, void *state,
+                                            size_t state_bytes, const void *transition, const int64_t *transition_strides, int final,
+                                            int frame_tolerance, void *scores, int64_t *path, int64_t *tokens,
+                                            int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words,
+                                            int64_t *word_lengths, int64_t *word_frames, void *word_confidences, void *normalisers,
+                                            int64_t *frames, int64_t *status, int flags, void *stream);
+
 /* ---- whole-loss entry points (no counterpart in the reference's native layer: they fold the Python-side
  * `full - aligned` and reduction of asg.py:128,136-142 and their autograd into the kernels, so one ASGLoss
  * step is 2 + 2 kernel launches with no PyTorch glue kernels in between) ------------------------------------ */

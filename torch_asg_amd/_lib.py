@@ -47,7 +47,11 @@ SYMBOLS = ["asg_hip_version", "asg_hip_strerror", "asg_ctx_create", "asg_ctx_des
            "asg_beam_word_window_nbest_work_bytes", "asg_beam_word_window_nbest", "asg_beam_word_window_nbest_la",
            "asg_beam_conf_stream_state_bytes", "asg_beam_conf_stream_reset", "asg_beam_conf_stream_advance",
            "asg_beam_conf_stream_result", "asg_beam_conf_stream_nbest_work_bytes", "asg_beam_conf_stream_nbest",
-           "asg_beam_conf_stream_confidence"]
+           "asg_beam_conf_stream_confidence",
+           "asg_beam_word_conf_stream_state_bytes", "asg_beam_word_conf_stream_reset", "asg_beam_word_conf_stream_advance",
+           "asg_beam_word_conf_stream_advance_la", "asg_beam_word_conf_stream_result", "asg_beam_word_conf_stream_result_la",
+           "asg_beam_word_conf_stream_nbest_work_bytes", "asg_beam_word_conf_stream_nbest", "asg_beam_word_conf_stream_nbest_la",
+           "asg_beam_word_conf_stream_confidence", "asg_beam_word_conf_stream_confidence_la"]
 ABI_VERSION = 230        # include/asg_hip.h: ASG_HIP_VERSION this package was written against
 
 
@@ -197,9 +201,22 @@ def lib():
     L.asg_beam_word_window_nbest_work_bytes.restype = sz
     L.asg_beam_word_window_nbest_work_bytes.argtypes = [bp, wp, i64, ci, ci, i64, i64, ci]
     L.asg_beam_word_window_nbest.argtypes = [vp, bp, wp, i64, ci, i64, i64, vp, sz, ci, ci, vp, sz] + [vp] * 12 + [ci, vp]
+    # the lattice-keeping word stream: the plain word stream's calls over the wider state, and _confidence
+    L.asg_beam_word_conf_stream_state_bytes.restype = sz
+    L.asg_beam_word_conf_stream_state_bytes.argtypes = L.asg_beam_word_stream_state_bytes.argtypes
+    L.asg_beam_word_conf_stream_reset.argtypes = L.asg_beam_word_stream_reset.argtypes
+    L.asg_beam_word_conf_stream_advance.argtypes = L.asg_beam_word_stream_advance.argtypes
+    L.asg_beam_word_conf_stream_result.argtypes = L.asg_beam_word_stream_result.argtypes
+    L.asg_beam_word_conf_stream_nbest_work_bytes.restype = sz
+    L.asg_beam_word_conf_stream_nbest_work_bytes.argtypes = L.asg_beam_word_stream_nbest_work_bytes.argtypes
+    L.asg_beam_word_conf_stream_nbest.argtypes = L.asg_beam_word_stream_nbest.argtypes
+    L.asg_beam_word_conf_stream_confidence.argtypes = [vp, bp, wp, i64, ci, i64, vp, sz, vp, ctypes.POINTER(i64), ci,
+                                                       ci] + [vp] * 13 + [ci, vp]
     for name in ("asg_beam_word_stream_advance", "asg_beam_word_stream_result", "asg_beam_word_window_advance",
                  "asg_beam_word_window_result", "asg_beam_decode_words_nbest",
-                 "asg_beam_word_stream_nbest", "asg_beam_word_window_nbest"):      # the plain call with the look-ahead behind the LM
+                 "asg_beam_word_stream_nbest", "asg_beam_word_window_nbest", "asg_beam_word_conf_stream_advance",
+                 "asg_beam_word_conf_stream_result", "asg_beam_word_conf_stream_nbest",
+                 "asg_beam_word_conf_stream_confidence"):                          # the plain call with the look-ahead behind the LM
         plain = getattr(L, name).argtypes
         at = plain.index(wp) + 1
         getattr(L, name + "_la").argtypes = plain[:at] + [ctypes.POINTER(AsgWordLookahead)] + plain[at:]

@@ -2145,11 +2145,12 @@ class ASGLoss(nn.Module):
                           self.transition.dtype, self.transition.device, keep_lattice)
 
     def beam_word_stream(self, lexicon, word_lm, batch_size, max_frames, beam_size=256, beam_threshold=float("inf"), lm_weight=1.0,
-                         word_score=0.0, token_score=0.0, lookahead=None):
+                         word_score=0.0, token_score=0.0, lookahead=None, keep_lattice=False):
         """A streaming beam decoder with a lexicon and a word n-gram LM under this module's transition matrix (read again at
-        every chunk): see `torch_asg_amd.BeamWordStream`."""
+        every chunk): see `torch_asg_amd.BeamWordStream`.  `keep_lattice=True`: the stream keeps its lattice and has
+        `result_confidence`."""
         return BeamWordStream(self.transition, lexicon, word_lm, batch_size, max_frames, beam_size, beam_threshold, lm_weight,
-                              word_score, token_score, self.transition.dtype, self.transition.device, lookahead)
+                              word_score, token_score, self.transition.dtype, self.transition.device, lookahead, keep_lattice)
 
     def beam_window_stream(self, graph, batch_size, window, commit_every=None, beam_size=256, beam_threshold=float("inf"),
                            lm_weight=1.0, token_score=0.0):
@@ -2321,4 +2322,5 @@ class ASGLoss(nn.Module):
 # the streaming decoders (stream.py looks this module's `native` up at every call, so it is imported once the module stands)
 from .stream import (BeamStream, BeamStreamResult, BeamWordStream, BeamWordStreamResult, BeamWordStreamNbest,  # noqa: E402,F401
                      BeamWindowStream, BeamWindowCommit, BeamWindowResult, BeamWordWindowStream, BeamWordWindowCommit,
-                     BeamWordWindowResult, BeamStreamNbest, BeamWindowNbest, BeamWordWindowNbest, BeamStreamConfidence)
+                     BeamWordWindowResult, BeamStreamNbest, BeamWindowNbest, BeamWordWindowNbest, BeamStreamConfidence,
+                     BeamWordStreamConfidence)

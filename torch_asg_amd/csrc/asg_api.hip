@@ -1983,6 +1983,285 @@ int asg_beam_words_confidence_la(asg_ctx *ctx, const asg_problem *p, const asg_t
                                  normalisers, stream);
 }
 
+// The lattice-keeping word stream: the checks of a plain word stream state, then those of the word confidences through a problem
+// of max_frames frames without targets (its emissions are not read).
+static int check_beam_word_conf_stream(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype, int beam_size,
+                                       int64_t max_frames) {
+    int rc = check_beam_word_stream(gb, lm, B, dtype, beam_size, max_frames);
+    if (rc) return rc;
+    asg_problem q{};
+    q.inputs = gb; q.transition = gb;
+    q.T = max_frames; q.B = B; q.N = gb->graph->N; q.S = 1; q.dtype = dtype;
+    return check_lattice(&q, beam_size, beam_word_loss_fits);
+}
+
+static size_t beam_word_conf_stream_bytes(const asg_token_graph_beam *gb, int64_t B, int dtype, int beam_size, int64_t max_frames) {
+    return beam_word_conf_stream_state_bytes(dtype == ASG_DTYPE_F64 ? 8 : 4, (int) max_frames, (int) B, beam_size,
+                                             beam_word_cap(beam_size, gb->max_out, (int) gb->num_start), (int) gb->graph->N);
+}
+
+size_t asg_beam_word_conf_stream_state_bytes(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype,
+                                             int beam_size, int64_t max_frames) {
+    if (check_beam_word_conf_stream(gb, lm, B, dtype, beam_size, max_frames) != ASG_OK) return 0;
+    return beam_word_conf_stream_bytes(gb, B, dtype, beam_size, max_frames);
+}
+
+int asg_beam_word_conf_stream_reset(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
+                                    int64_t max_frames, void *state, size_t state_bytes, const uint8_t *mask, int flags,
+                                    void *stream) {
+    (void) ctx; (void) flags;
+    if (!gb || !gb->graph) return ASG_ERR_INVALID;
+    const int dtype = gb->graph->dtype;
+    int rc = check_beam_word_conf_stream(gb, lm, B, dtype, beam_size, max_frames);
+    if (rc) return rc;
+    if (!state) return ASG_ERR_INVALID;
+    if (state_bytes < beam_word_conf_stream_bytes(gb, B, dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
+    return hip_status(launch_beam_word_conf_stream_reset(dtype == ASG_DTYPE_F64 ? 8 : 4, to_beam_graph_args(gb), beam_size,
+                                                         (int) max_frames, (int) B, (int) gb->graph->N, state, mask,
+                                                         (hipStream_t) stream));
+}
+
+// The calls of the lattice-keeping word stream that run the search or read its values, with a look-ahead (`with_la`, checked
+// behind the LM as asg_beam_word_stream_*_la check it) or without one.
+static int beam_word_conf_stream_advance(const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                         const asg_word_lookahead *la, bool with_la, int beam_size, double beam_threshold,
+                                         int64_t max_frames, void *state, size_t state_bytes, void *stream) {
+    if (!p) return ASG_ERR_INVALID;
+    int rc = check_beam_word_conf_stream(gb, lm, p->B, p->dtype, beam_size, max_frames);
+    if (rc) return rc;
+    if (with_la && (rc = check_word_lookahead(p->dtype, lm, la)) != ASG_OK) return rc;
+    if (p->T < 0 || p->N != gb->graph->N) return ASG_ERR_INVALID;
+    if (p->T > 0 && (rc = check_beam_words(p, gb, lm, beam_size)) != ASG_OK) return rc;
+    if (!(beam_threshold >= 0.0)) return ASG_ERR_INVALID;                  // negative or NaN
+    if (!state) return ASG_ERR_INVALID;
+    if (state_bytes < beam_word_conf_stream_bytes(gb, p->B, p->dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
+    if (p->T == 0) return ASG_OK;                                          // no frame: the state stays as it is
+    const Problem P = to_problem(p);
+    const GraphArgs G = to_graph_args(gb->graph);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    const WordLmArgs LM = to_word_lm_args(lm);
+    const WordLookArgs LA = with_la ? to_word_look_args(la) : WordLookArgs{};
+    const WordLookArgs *look = with_la ? &LA : nullptr;
+    return hip_status(ASG_DISPATCH(p, launch_beam_word_conf_stream_advance<float>(P, G, BG, LM, look, beam_size, beam_threshold,
+                                                                                  (int) max_frames, state, (hipStream_t) stream),
+                                   launch_beam_word_conf_stream_advance<double>(P, G, BG, LM, look, beam_size, beam_threshold,
+                                                                                (int) max_frames, state, (hipStream_t) stream)));
+}
+
+int asg_beam_word_conf_stream_advance(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                      int beam_size, double beam_threshold, int64_t max_frames, void *state, size_t state_bytes,
+                                      int flags, void *stream) {
+    (void) ctx; (void) flags;
+    return beam_word_conf_stream_advance(p, gb, lm, nullptr, false, beam_size, beam_threshold, max_frames, state, state_bytes,
+                                         stream);
+}
+
+int asg_beam_word_conf_stream_advance_la(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                         const asg_word_lookahead *la, int beam_size, double beam_threshold, int64_t max_frames,
+                                         void *state, size_t state_bytes, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    return beam_word_conf_stream_advance(p, gb, lm, la, true, beam_size, beam_threshold, max_frames, state, state_bytes, stream);
+}
+
+static int beam_word_conf_stream_result(const asg_token_graph_beam *gb, const asg_word_lm *lm, const asg_word_lookahead *la,
+                                        bool with_la, int64_t B, int beam_size, int64_t max_frames, const void *state,
+                                        size_t state_bytes, int final, void *scores, int64_t *path, int64_t *tokens,
+                                        int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words,
+                                        int64_t *word_lengths, int64_t *frames, int64_t *status, void *stream) {
+    if (!gb || !gb->graph) return ASG_ERR_INVALID;
+    const asg_token_graph *g = gb->graph;
+    int rc = check_beam_word_conf_stream(gb, lm, B, g->dtype, beam_size, max_frames);
+    if (rc) return rc;
+    if (with_la && (rc = check_word_lookahead(g->dtype, lm, la)) != ASG_OK) return rc;
+    if (!state || !scores || !path || !tokens || !token_lengths || !states || !lm_states || !words || !word_lengths || !frames ||
+        !status)
+        return ASG_ERR_INVALID;
+    if (state_bytes < beam_word_conf_stream_bytes(gb, B, g->dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
+    const GraphArgs G = to_graph_args(g);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    const WordLmArgs LM = to_word_lm_args(lm);
+    const size_t per = beam_word_conf_stream_bytes(gb, 1, g->dtype, beam_size, max_frames);   // the stride of a slot
+    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
+    long long *ls = (long long *) lm_states, *wd = (long long *) words, *wl = (long long *) word_lengths;
+    long long *fr = (long long *) frames, *su = (long long *) status;
+    const WordLookArgs LA = with_la ? to_word_look_args(la) : WordLookArgs{};
+    const WordLookArgs *look = with_la ? &LA : nullptr;
+    return hip_status(ASG_DISPATCH(g, launch_beam_word_stream_result<float>(G, BG, LM, look, beam_size, (int) max_frames, (int) B,
+                                                                            state, final, scores, pa, tk, tl, st, ls, wd, wl, fr,
+                                                                            su, (hipStream_t) stream, per),
+                                   launch_beam_word_stream_result<double>(G, BG, LM, look, beam_size, (int) max_frames, (int) B,
+                                                                          state, final, scores, pa, tk, tl, st, ls, wd, wl, fr,
+                                                                          su, (hipStream_t) stream, per)));
+}
+
+int asg_beam_word_conf_stream_result(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
+                                     int64_t max_frames, const void *state, size_t state_bytes, int final, void *scores,
+                                     int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *lm_states,
+                                     int64_t *words, int64_t *word_lengths, int64_t *frames, int64_t *status, int flags,
+                                     void *stream) {
+    (void) ctx; (void) flags;
+    return beam_word_conf_stream_result(gb, lm, nullptr, false, B, beam_size, max_frames, state, state_bytes, final, scores, path,
+                                        tokens, token_lengths, states, lm_states, words, word_lengths, frames, status, stream);
+}
+
+int asg_beam_word_conf_stream_result_la(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                        const asg_word_lookahead *la, int64_t B, int beam_size, int64_t max_frames,
+                                        const void *state, size_t state_bytes, int final, void *scores, int64_t *path,
+                                        int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words,
+                                        int64_t *word_lengths, int64_t *frames, int64_t *status, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    return beam_word_conf_stream_result(gb, lm, la, true, B, beam_size, max_frames, state, state_bytes, final, scores, path, tokens,
+                                        token_lengths, states, lm_states, words, word_lengths, frames, status, stream);
+}
+
+static int check_beam_word_conf_stream_nbest(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype,
+                                             int beam_size, int64_t max_frames, int nbest) {
+    int rc = check_beam_word_conf_stream(gb, lm, B, dtype, beam_size, max_frames);
+    if (rc) return rc;
+    if (nbest < 1) return ASG_ERR_INVALID;
+    if (nbest > kBeamMaxNbest) return ASG_ERR_UNSUPPORTED;
+    return ASG_OK;
+}
+
+size_t asg_beam_word_conf_stream_nbest_work_bytes(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype,
+                                                  int beam_size, int64_t max_frames, int nbest) {
+    if (check_beam_word_conf_stream_nbest(gb, lm, B, dtype, beam_size, max_frames, nbest) != ASG_OK) return 0;
+    return beam_word_stream_nbest_work_bytes((int) max_frames, (int) B, beam_size, nbest);
+}
+
+static int beam_word_conf_stream_nbest(const asg_token_graph_beam *gb, const asg_word_lm *lm, const asg_word_lookahead *la,
+                                       bool with_la, int64_t B, int beam_size, int64_t max_frames, const void *state,
+                                       size_t state_bytes, int final, int nbest, void *work, size_t work_bytes, void *scores,
+                                       void *graph_scores, void *lm_scores, int64_t *path, int64_t *tokens, int64_t *token_lengths,
+                                       int64_t *states, int64_t *lm_states, int64_t *words, int64_t *word_lengths,
+                                       int64_t *num_hyps, int64_t *frames, int64_t *status, void *stream) {
+    if (!gb || !gb->graph) return ASG_ERR_INVALID;
+    const asg_token_graph *g = gb->graph;
+    int rc = check_beam_word_conf_stream_nbest(gb, lm, B, g->dtype, beam_size, max_frames, nbest);
+    if (rc) return rc;
+    if (with_la && (rc = check_word_lookahead(g->dtype, lm, la)) != ASG_OK) return rc;
+    if (!state || !work || !scores || !graph_scores || !lm_scores || !tokens || !token_lengths || !words || !word_lengths ||
+        !num_hyps || !frames || !status)
+        return ASG_ERR_INVALID;
+    if (state_bytes < beam_word_conf_stream_bytes(gb, B, g->dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
+    if (work_bytes < beam_word_stream_nbest_work_bytes((int) max_frames, (int) B, beam_size, nbest)) return ASG_ERR_WORKSPACE;
+    const GraphArgs G = to_graph_args(g);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    const WordLmArgs LM = to_word_lm_args(lm);
+    const size_t per = beam_word_conf_stream_bytes(gb, 1, g->dtype, beam_size, max_frames);   // the stride of a slot
+    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
+    long long *ls = (long long *) lm_states, *wd = (long long *) words, *wl = (long long *) word_lengths;
+    long long *nh = (long long *) num_hyps, *fr = (long long *) frames, *su = (long long *) status;
+    if (with_la) {
+        const WordLookArgs LA = to_word_look_args(la);
+        return hip_status(ASG_DISPATCH(g, launch_beam_word_stream_nbest_la<float>(G, BG, LM, LA, beam_size, (int) max_frames, (int) B,
+                                                                                  state, final, nbest, work, scores, graph_scores,
+                                                                                  lm_scores, pa, tk, tl, st, ls, wd, wl, nh, fr, su,
+                                                                                  (hipStream_t) stream, per),
+                                       launch_beam_word_stream_nbest_la<double>(G, BG, LM, LA, beam_size, (int) max_frames, (int) B,
+                                                                                state, final, nbest, work, scores, graph_scores,
+                                                                                lm_scores, pa, tk, tl, st, ls, wd, wl, nh, fr, su,
+                                                                                (hipStream_t) stream, per)));
+    }
+    return hip_status(ASG_DISPATCH(g, launch_beam_word_stream_nbest<float>(G, BG, LM, beam_size, (int) max_frames, (int) B, state,
+                                                                           final, nbest, work, scores, graph_scores, lm_scores, pa,
+                                                                           tk, tl, st, ls, wd, wl, nh, fr, su, (hipStream_t) stream,
+                                                                           per),
+                                   launch_beam_word_stream_nbest<double>(G, BG, LM, beam_size, (int) max_frames, (int) B, state,
+                                                                         final, nbest, work, scores, graph_scores, lm_scores, pa,
+                                                                         tk, tl, st, ls, wd, wl, nh, fr, su, (hipStream_t) stream,
+                                                                         per)));
+}
+
+int asg_beam_word_conf_stream_nbest(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
+                                    int64_t max_frames, const void *state, size_t state_bytes, int final, int nbest, void *work,
+                                    size_t work_bytes, void *scores, void *graph_scores, void *lm_scores, int64_t *path,
+                                    int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words,
+                                    int64_t *word_lengths, int64_t *num_hyps, int64_t *frames, int64_t *status, int flags,
+                                    void *stream) {
+    (void) ctx; (void) flags;
+    return beam_word_conf_stream_nbest(gb, lm, nullptr, false, B, beam_size, max_frames, state, state_bytes, final, nbest, work,
+                                       work_bytes, scores, graph_scores, lm_scores, path, tokens, token_lengths, states, lm_states,
+                                       words, word_lengths, num_hyps, frames, status, stream);
+}
+
+int asg_beam_word_conf_stream_nbest_la(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                       const asg_word_lookahead *la, int64_t B, int beam_size, int64_t max_frames, const void *state,
+                                       size_t state_bytes, int final, int nbest, void *work, size_t work_bytes, void *scores,
+                                       void *graph_scores, void *lm_scores, int64_t *path, int64_t *tokens, int64_t *token_lengths,
+                                       int64_t *states, int64_t *lm_states, int64_t *words, int64_t *word_lengths,
+                                       int64_t *num_hyps, int64_t *frames, int64_t *status, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    return beam_word_conf_stream_nbest(gb, lm, la, true, B, beam_size, max_frames, state, state_bytes, final, nbest, work,
+                                       work_bytes, scores, graph_scores, lm_scores, path, tokens, token_lengths, states, lm_states,
+                                       words, word_lengths, num_hyps, frames, status, stream);
+}
+
+static int beam_word_conf_stream_confidence(const asg_token_graph_beam *gb, const asg_word_lm *lm, const asg_word_lookahead *la,
+                                            bool with_la, int64_t B, int beam_size, int64_t max_frames, void *state,
+                                            size_t state_bytes, const void *transition, const int64_t *transition_strides,
+                                            int final, int frame_tolerance, void *scores, int64_t *path, int64_t *tokens,
+                                            int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words,
+                                            int64_t *word_lengths, int64_t *word_frames, void *word_confidences, void *normalisers,
+                                            int64_t *frames, int64_t *status, void *stream) {
+    if (!gb || !gb->graph) return ASG_ERR_INVALID;
+    const asg_token_graph *g = gb->graph;
+    int rc = check_beam_word_conf_stream(gb, lm, B, g->dtype, beam_size, max_frames);
+    if (rc) return rc;
+    if (with_la && (rc = check_word_lookahead(g->dtype, lm, la)) != ASG_OK) return rc;
+    if (frame_tolerance < 0) return ASG_ERR_INVALID;
+    if (frame_tolerance > kBeamWordConfMaxTol) return ASG_ERR_UNSUPPORTED;
+    if (!state || !transition || !transition_strides || !scores || !path || !tokens || !token_lengths || !states || !lm_states ||
+        !words || !word_lengths || !word_frames || !word_confidences || !normalisers || !frames || !status)
+        return ASG_ERR_INVALID;
+    if (state_bytes < beam_word_conf_stream_bytes(gb, B, g->dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
+    Problem P{};
+    P.transition = transition; P.ts0 = transition_strides[0]; P.ts1 = transition_strides[1];
+    P.T = (int) max_frames; P.B = (int) B; P.N = g->N; P.S = 1;
+    const GraphArgs G = to_graph_args(g);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    const WordLmArgs LM = to_word_lm_args(lm);
+    const WordLookArgs LA = with_la ? to_word_look_args(la) : WordLookArgs{};
+    const WordLookArgs *look = with_la ? &LA : nullptr;
+    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
+    long long *ls = (long long *) lm_states, *wd = (long long *) words, *wl = (long long *) word_lengths;
+    long long *wf = (long long *) word_frames, *fr = (long long *) frames, *su = (long long *) status;
+    return hip_status(ASG_DISPATCH(g,
+        launch_beam_word_conf_stream_confidence<float>(P, G, BG, LM, look, beam_size, (int) max_frames, state, final, frame_tolerance,
+                                                       scores, pa, tk, tl, st, ls, wd, wl, wf, word_confidences, normalisers, fr, su,
+                                                       (hipStream_t) stream),
+        launch_beam_word_conf_stream_confidence<double>(P, G, BG, LM, look, beam_size, (int) max_frames, state, final, frame_tolerance,
+                                                        scores, pa, tk, tl, st, ls, wd, wl, wf, word_confidences, normalisers, fr, su,
+                                                        (hipStream_t) stream)));
+}
+
+int asg_beam_word_conf_stream_confidence(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B,
+                                         int beam_size, int64_t max_frames, void *state, size_t state_bytes, const void *transition,
+                                         const int64_t *transition_strides, int final, int frame_tolerance, void *scores,
+                                         int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *lm_states,
+                                         int64_t *words, int64_t *word_lengths, int64_t *word_frames, void *word_confidences,
+                                         void *normalisers, int64_t *frames, int64_t *status, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    return beam_word_conf_stream_confidence(gb, lm, nullptr, false, B, beam_size, max_frames, state, state_bytes, transition,
+                                            transition_strides, final, frame_tolerance, scores, path, tokens, token_lengths, states,
+                                            lm_states, words, word_lengths, word_frames, word_confidences, normalisers, frames,
+                                            status, stream);
+}
+
+int asg_beam_word_conf_stream_confidence_la(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                            const asg_word_lookahead *la, int64_t B, int beam_size, int64_t max_frames, void *state,
+                                            size_t state_bytes, const void *transition, const int64_t *transition_strides, int final,
+                                            int frame_tolerance, void *scores, int64_t *path, int64_t *tokens,
+                                            int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words,
+                                            int64_t *word_lengths, int64_t *word_frames, void *word_confidences, void *normalisers,
+                                            int64_t *frames, int64_t *status, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    return beam_word_conf_stream_confidence(gb, lm, la, true, B, beam_size, max_frames, state, state_bytes, transition,
+                                            transition_strides, final, frame_tolerance, scores, path, tokens, token_lengths, states,
+                                            lm_states, words, word_lengths, word_frames, word_confidences, normalisers, frames,
+                                            status, stream);
+}
+
 // The n-best confidences: the checks of asg_beam_words_confidence, then those of asg_beam_decode_words_nbest.
 static int check_beam_words_nbest_conf(const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm, int beam_size,
                                        int nbest) {

@@ -1,5 +1,6 @@
 // torch_asg_amd/csrc/asg_beam_word_conf_pull.h -- the beta pull with a WORD-EVENT SINK, the text asg_beam_word_conf.hip
-// (confidences of the one best) and asg_beam_word_nbest_conf.hip (of every row of the n-best list, 5y) both compile:
+// (confidences of the one best), asg_beam_word_nbest_conf.hip (of every row of the n-best list, 5y) and
+// asg_beam_word_stream_conf.hip (of a stream's hypothesis or prefix, 5ae) all compile:
 // beam_loss_bwd's pull (one 1024-thread workgroup per utterance, frames len-1 .. 1, U_{t+1} with its beta in LDS, G lanes per
 // source pair, a max pass and a sum pass) without label posteriors, (i, j) tile and transition gradient.  The sum pass forms the
 // posterior exp((alpha + c) - Z_K) of every SEPARATOR edge -- the event "word w ends at frame t" -- and, before the first frame,
@@ -21,8 +22,11 @@ namespace asg {
 
 namespace {
 
-template <typename R, typename Sink>
-__device__ __forceinline__ void beam_word_conf_pull(const Problem &P, const typename WordLat<R>::Args &args, char *wb, size_t beta_off,
+// Lat: WordLat<R>, or a lattice with its edges and labels, an end term of its own and its own answer to whether the event of
+// frame len exists (the prefix mode of the lattice-keeping stream, asg_beam_word_stream_conf.hip); Lat::Args starts with
+// WordLat<R>::Args' members.
+template <typename R, typename Sink, typename Lat = WordLat<R>>
+__device__ __forceinline__ void beam_word_conf_pull(const Problem &P, const typename Lat::Args &args, char *wb, size_t beta_off,
                                                     R Z, int len, int last, unsigned long long *nq, R *nb, Sink &sink) {
     using KeyT = unsigned long long;
     const int M = args.lay.M, tid = threadIdx.x, b = blockIdx.x;
@@ -33,7 +37,7 @@ __device__ __forceinline__ void beam_word_conf_pull(const Problem &P, const type
     R *Bv = (R *) (wb + beta_off);                                             // [2][M]
     const R *in = (const R *) P.inputs + (int64_t) b * P.is1;
     const R *trm = (const R *) P.transition;
-    WordLat<R> lat;
+    Lat lat;
     lat.bind(args);
     const int sep = lat.f.sep;
     auto tr = [&](int i, int j) -> R { return trm[(int64_t) i * P.ts0 + (int64_t) j * P.ts1]; };
@@ -50,7 +54,7 @@ __device__ __forceinline__ void beam_word_conf_pull(const Problem &P, const type
         nq[x] = p;
         nb[x] = e;
         const int s = lat.f.state[(int) (p & lat.qmask)];
-        if (sink.open() && s != 0 && e > NINF) sink.add(lat.f.wos[s], (A[(int64_t) (len - 1) * M + x] + e) - Z);
+        if (lat.end_event() && sink.open() && s != 0 && e > NINF) sink.add(lat.f.wos[s], (A[(int64_t) (len - 1) * M + x] + e) - Z);
     }
     for (int t = len - 1; t >= 1; --t) {
         __syncthreads();                                                       // nq, nb and the adds of frame t + 1

@@ -12,6 +12,9 @@ namespace asg {
 
 namespace {
 
+// the alpha push (asg_beam_word_alpha.inc)
+constexpr double kBSumScale = 281474976710656.0;              // 2^48: a target's sum of exp(c - max) over < 2^14 candidates
+
 // The read-only part of a BeamWordFrame for the kernels that only walk the graph and the LM.
 template <typename R>
 __device__ __forceinline__ void bind_walk(BeamWordFrame<R> &f, const GraphArgs &g, const BeamGraphArgs &bg, const WordLmArgs &lm) {
@@ -36,6 +39,8 @@ struct WordLat {
         int w;
         if (!word_end<R>(f, fw, (int) (p >> f.qbits), (int) (p & qmask), (R) 0, e, w)) e = Num<R>::ninf();
     }
+    // whether an end in a word-end node completes its word at frame len (the event of the final step)
+    __device__ constexpr bool end_event() const { return true; }
     template <typename F> __device__ void for_each_out(Key p, int lg, int G, F fn) const {
         const int q = (int) (p & qmask), h = (int) (p >> f.qbits);
         const int e1 = f.orow[q + 1];

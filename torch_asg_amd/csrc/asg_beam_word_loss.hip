@@ -18,7 +18,8 @@
 //      order-preserving key, -- pass 2 -- add exp(c - max) to its sum as a 64-bit fixed-point integer with 48 fractional bits (a
 //      target has at most |U_{t-1}| + 1 < 2^14 candidates of at most 1 each: no overflow).  Integer max and add are associative:
 //      the order the lanes arrive in cannot change a bit.  alpha = (max + log(sum)) + emission goes to the workspace ([T][M] when
-//      a gradient is wanted, else two rows).
+//      a gradient is wanted, else two rows).  The body of its frame loop is asg_beam_word_alpha.inc, which the catch-up of the
+//      lattice-keeping word stream (asg_beam_word_stream_conf.hip) compiles too.
 // Backward, two launches: beam_loss_bwd<R, TL, WordLat<R>> (beta PULLS: a pair's own outgoing row is a gather against U_{t+1} in
 // LDS, no atomics on values; it owns the label posteriors and the (i, j) counts, summed as 64-bit fixed-point integers, the
 // counts in LDS while the [N][N] tile fits, else in the utterance's scratch) and beam_loss_tr_reduce (the utterances in
@@ -36,8 +37,6 @@
 namespace asg {
 
 namespace {
-
-constexpr double kBSumScale = 281474976710656.0;              // 2^48: a target's sum of exp(c - max) over < 2^14 candidates
 
 // ---------------------------------------------------------------------------------------------------------------------
 // 1: the search.  beam_word_kernel's frame loop; cnt[t] = |A_t| for t < len.  With LA it is beam_word_la_kernel's frame loop
@@ -237,58 +236,7 @@ __global__ void __launch_bounds__(kBL) beam_word_loss_fwd(Problem P, GraphArgs g
         const R *Ap = A + (int64_t) (store ? t - 1 : ((t - 1) & 1)) * M;
         R *Arow = A + (int64_t) (store ? t : (t & 1)) * M;
         const R *xt = in + (int64_t) t * P.is0;
-        for (int x = tid; x < mt; x += kBL) { ut[x] = Ut[x]; sm[x] = 0ull; mk[x] = (KU) 0; }
-        __syncthreads();
-        const int G = subgroup(mp), per = kBL / G;
-        for (int pass = 0; pass < 2; ++pass) {
-            for (int k0 = 0; k0 < mp; k0 += per) {
-                const int k = k0 + tid / G, lg = tid % G;
-                if (k >= mp) continue;
-                const R a = dev_load(Ap + k);
-                if (!(a > NINF)) continue;
-                const unsigned long long p = Up[k];
-                const int qs = (int) (p & qmask), hs = (int) (p >> f.qbits);
-                const int j = f.label[qs];
-                auto offer = [&](unsigned long long tp, R c) {
-                    if (!(c > NINF)) return;
-                    const int pos = find_sorted(ut, mt, tp);
-                    if (pos < 0) return;
-                    if (pass == 0) atomicMax(mk + pos, KT::enc(c));
-                    else {
-                        const unsigned long long fx = to_fixed((double) bexp(c - KT::dec(mk[pos])), kBSumScale);
-                        if (fx) atomicAdd(sm + pos, fx);
-                    }
-                };
-                if (lg == 0) offer(p, a + tr(j, j));
-                const int e1 = f.orow[qs + 1];
-                for (int e = f.orow[qs] + lg; e < e1; e += G) {
-                    const int2 arc = f.oarc[e];
-                    int th = hs;
-                    R w = f.ow[e];
-                    if (arc.y == f.sep) {                             // a word ends: the LM moves
-                        R add;
-                        int h2;
-                        if (!f.step(hs, f.wos[f.state[qs]], h2, add)) continue;
-                        th = h2;
-                        w = w + add;
-                    }
-                    offer(f.pair(th, arc.x), (a + tr(arc.y, j)) + w);
-                }
-            }
-            __syncthreads();
-        }
-        for (int x = tid; x < mt; x += kBL) {
-            const KU key = mk[x];
-            R v = NINF;
-            if (key != 0 && sm[x] != 0ull) {
-                const R s = (R) ((double) sm[x] * (1.0 / kBSumScale));
-                v = (KT::dec(key) + blog(s)) + xt[(int64_t) f.label[(int) (ut[x] & qmask)] * P.is2];
-            }
-            dev_store(Arow + x, v);
-        }
-        __threadfence();
-        __syncthreads();
-        mp = mt;
+#include "asg_beam_word_alpha.inc"   // the frame body, shared with asg_beam_word_stream_conf.hip
     }
     // Z_K over the last lattice set: every kind of end through word_end
     const unsigned long long *Ul = U + (int64_t) (len - 1) * M;

@@ -474,11 +474,12 @@ hipError_t beam_word_stream_nbest(const GraphArgs &G, const BeamGraphArgs &BG, c
                                   int K, int max_frames, int B, const void *state, int final, int nbest, void *work, void *scores,
                                   void *graph_scores, void *lm_scores, long long *path, long long *tokens, long long *tlen,
                                   long long *states, long long *lm_states, long long *words, long long *wlen, long long *num_hyps,
-                                  long long *frames, long long *status, hipStream_t stream) {
+                                  long long *frames, long long *status, hipStream_t stream, size_t stride) {
     const int cap = beam_word_cap(K, BG.max_out, BG.num_start);
     const BeamStreamLayout lay = beam_word_stream_layout(sizeof(R), max_frames, K, cap);
     BeamWordNbestSrc src{};
-    src.base = (const char *) state; src.per = lay.per; src.set_off = lay.set; src.na_off = lay.hdr + 4; src.pos_off = lay.hdr;
+    src.base = (const char *) state; src.per = stride ? stride : lay.per;   // (a slot with parts of the caller's behind it)
+    src.set_off = lay.set; src.na_off = lay.hdr + 4; src.pos_off = lay.hdr;
     src.ovf_off = lay.hdr + 8;
     src.nb = nbest < K ? nbest : K;
     src.cols = (char *) work; src.cols_per = a256((size_t) max_frames * src.nb * 4); src.Tw = max_frames;
@@ -495,10 +496,11 @@ hipError_t launch_beam_word_stream_nbest(const GraphArgs &G, const BeamGraphArgs
                                          int B, const void *state, int final, int nbest, void *work, void *scores,
                                          void *graph_scores, void *lm_scores, long long *path, long long *tokens, long long *tlen,
                                          long long *states, long long *lm_states, long long *words, long long *wlen,
-                                         long long *num_hyps, long long *frames, long long *status, hipStream_t stream) {
+                                         long long *num_hyps, long long *frames, long long *status, hipStream_t stream,
+                                         size_t stride) {
     return beam_word_stream_nbest<R, false>(G, BG, LM, WordNoLook{}, K, max_frames, B, state, final, nbest, work, scores,
                                             graph_scores, lm_scores, path, tokens, tlen, states, lm_states, words, wlen, num_hyps,
-                                            frames, status, stream);
+                                            frames, status, stream, stride);
 }
 template <typename R>
 hipError_t launch_beam_word_stream_nbest_la(const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
@@ -506,29 +508,29 @@ hipError_t launch_beam_word_stream_nbest_la(const GraphArgs &G, const BeamGraphA
                                             int nbest, void *work, void *scores, void *graph_scores, void *lm_scores,
                                             long long *path, long long *tokens, long long *tlen, long long *states,
                                             long long *lm_states, long long *words, long long *wlen, long long *num_hyps,
-                                            long long *frames, long long *status, hipStream_t stream) {
+                                            long long *frames, long long *status, hipStream_t stream, size_t stride) {
     return beam_word_stream_nbest<R, true>(G, BG, LM, LA, K, max_frames, B, state, final, nbest, work, scores, graph_scores,
                                            lm_scores, path, tokens, tlen, states, lm_states, words, wlen, num_hyps, frames, status,
-                                           stream);
+                                           stream, stride);
 }
 template hipError_t launch_beam_word_stream_nbest<float>(const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &, int, int, int,
                                                          const void *, int, int, void *, void *, void *, void *, long long *,
                                                          long long *, long long *, long long *, long long *, long long *,
-                                                         long long *, long long *, long long *, long long *, hipStream_t);
+                                                         long long *, long long *, long long *, long long *, hipStream_t, size_t);
 template hipError_t launch_beam_word_stream_nbest<double>(const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &, int, int, int,
                                                           const void *, int, int, void *, void *, void *, void *, long long *,
                                                           long long *, long long *, long long *, long long *, long long *,
-                                                          long long *, long long *, long long *, long long *, hipStream_t);
+                                                          long long *, long long *, long long *, long long *, hipStream_t, size_t);
 template hipError_t launch_beam_word_stream_nbest_la<float>(const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &,
                                                             const WordLookArgs &, int, int, int, const void *, int, int, void *,
                                                             void *, void *, void *, long long *, long long *, long long *,
                                                             long long *, long long *, long long *, long long *, long long *,
-                                                            long long *, long long *, hipStream_t);
+                                                            long long *, long long *, hipStream_t, size_t);
 template hipError_t launch_beam_word_stream_nbest_la<double>(const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &,
                                                              const WordLookArgs &, int, int, int, const void *, int, int, void *,
                                                              void *, void *, void *, long long *, long long *, long long *,
                                                              long long *, long long *, long long *, long long *, long long *,
-                                                             long long *, long long *, hipStream_t);
+                                                             long long *, long long *, hipStream_t, size_t);
 
 size_t beam_word_window_nbest_work_bytes(int W, int B, int K, int nbest) {
     return (size_t) B * a256((size_t) W * (nbest < K ? nbest : K) * 4);

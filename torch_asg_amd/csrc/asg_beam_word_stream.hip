@@ -200,9 +200,11 @@ hipError_t launch_beam_word_stream_result(const GraphArgs &G, const BeamGraphArg
                                           const WordLookArgs *LA, int K, int max_frames, int B, const void *state, int final,
                                           void *scores, long long *path, long long *tokens,
                                           long long *tlen, long long *states, long long *lm_states, long long *words,
-                                          long long *wlen, long long *frames, long long *status, hipStream_t stream) {
+                                          long long *wlen, long long *frames, long long *status, hipStream_t stream,
+                                          size_t stride) {
     const int cap = beam_word_cap(K, BG.max_out, BG.num_start);
-    const BeamStreamLayout lay = beam_word_stream_layout(sizeof(R), max_frames, K, cap);
+    BeamStreamLayout lay = beam_word_stream_layout(sizeof(R), max_frames, K, cap);
+    if (stride) lay.per = stride;                                           // (a slot with parts of the caller's behind it)
 #define ASG_BEAM_WORD_STREAM_RESULT(LAF, LOOK)                                                                               \
     hipLaunchKernelGGL((beam_word_stream_result_kernel<R, LAF>), dim3(B), dim3(kBT), 0, stream, G, LM, K, cap,               \
                        word_table_bits(cap), max_frames, (const char *) state, lay, final, (R *) scores, path, tokens, tlen, \
@@ -214,10 +216,10 @@ hipError_t launch_beam_word_stream_result(const GraphArgs &G, const BeamGraphArg
 template hipError_t launch_beam_word_stream_result<float>(const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &,
                                                           const WordLookArgs *, int, int, int, const void *, int, void *, long long *, long long *, long long *,
                                                           long long *, long long *, long long *, long long *, long long *,
-                                                          long long *, hipStream_t);
+                                                          long long *, hipStream_t, size_t);
 template hipError_t launch_beam_word_stream_result<double>(const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &,
                                                            const WordLookArgs *, int, int, int, const void *, int, void *, long long *, long long *, long long *,
                                                            long long *, long long *, long long *, long long *, long long *,
-                                                           long long *, hipStream_t);
+                                                           long long *, hipStream_t, size_t);
 
 }  // namespace asg

@@ -269,7 +269,8 @@ hipError_t launch_beam_word_stream_result(const GraphArgs &G, const BeamGraphArg
                                           const WordLookArgs *LA, int K, int max_frames, int B, const void *state, int final,
                                           void *scores, long long *path, long long *tokens,
                                           long long *tlen, long long *states, long long *lm_states, long long *words,
-                                          long long *wlen, long long *frames, long long *status, hipStream_t stream);
+                                          long long *wlen, long long *frames, long long *status, hipStream_t stream,
+                                          size_t stride = 0);   // != 0: the slots lie `stride` bytes apart (asg_beam_word_stream_conf.hip)
 
 // ---- The n best hypotheses of the search over pairs, with the score split three ways (asg_beam_word_nbest.hip):
 // asg_beam_decode_words_nbest and asg_beam_word_stream_nbest.  One-shot, one utterance's workspace: the word decoder's own layout
@@ -327,7 +328,8 @@ hipError_t launch_beam_word_stream_nbest(const GraphArgs &G, const BeamGraphArgs
                                          int B, const void *state, int final, int nbest, void *work, void *scores,
                                          void *graph_scores, void *lm_scores, long long *path, long long *tokens, long long *tlen,
                                          long long *states, long long *lm_states, long long *words, long long *wlen,
-                                         long long *num_hyps, long long *frames, long long *status, hipStream_t stream);
+                                         long long *num_hyps, long long *frames, long long *status, hipStream_t stream,
+                                         size_t stride = 0);    // as launch_beam_word_stream_result's
 // ... over a state that launch_beam_word_stream_advance left with the look-ahead LA: asg_beam_word_stream_nbest_la.
 template <typename R>
 hipError_t launch_beam_word_stream_nbest_la(const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
@@ -335,7 +337,7 @@ hipError_t launch_beam_word_stream_nbest_la(const GraphArgs &G, const BeamGraphA
                                             int nbest, void *work, void *scores, void *graph_scores, void *lm_scores,
                                             long long *path, long long *tokens, long long *tlen, long long *states,
                                             long long *lm_states, long long *words, long long *wlen, long long *num_hyps,
-                                            long long *frames, long long *status, hipStream_t stream);
+                                            long long *frames, long long *status, hipStream_t stream, size_t stride = 0);
 
 // ---- The stream in bounded memory (asg_beam_window.hip): asg_beam_window_*.  One slot of the state has the layout of a stream
 // of W frames -- the back-pointers are a ring, frame u in row u mod W -- with the header int64 pos, int64 base, int32 |A|, carry,
@@ -602,6 +604,37 @@ hipError_t launch_beam_word_conf_search(const Problem &P, const GraphArgs &G, co
                                         size_t fin_off, void *scores, long long *path, long long *tokens, long long *tlen,
                                         long long *states, long long *lm_states, long long *words, long long *wlen,
                                         long long *word_frames, hipStream_t stream);
+
+// ---- The search over pairs carried across chunks with a state that keeps its lattice (asg_beam_word_stream_conf.hip):
+// asg_beam_word_conf_stream_*.  One slot: the plain word stream's slot (beam_word_stream_layout) unchanged at the front, then (byte
+// offsets, each part 256-byte aligned) cnt int32 [max_frames], the emissions [max_frames][N], nu int32 [max_frames], U u64
+// [max_frames][K] (pair keys h << qbits | q, ascending), A [max_frames][K], beta [2][K]:
+//     per = P + a256(4 T) + a256(e T N) + a256(4 T) + a256(8 T K) + a256(e T K) + a256(2 e K),   P = beam_word_stream_layout(..).per.
+// Header word 3 is apos, the frames whose U / nu / A rows are valid.  `lat` is a BeamWordLossLayout (M = K, nf = 0) over bq / bh /
+// cnt / nu / U / A, so WordSets, WordLat<R>::Args and beam_word_conf_pull take it as they take BeamWordConfLayout's; st.per, lat.per
+// and per are the slot's stride.  K = beam_size with beam_word_loss_fits(elem, K, N); LA as for the plain word stream.
+struct BeamWordConfStreamLayout {
+    BeamStreamLayout st;
+    BeamWordLossLayout lat;
+    size_t em, beta, per;
+};
+BeamWordConfStreamLayout beam_word_conf_stream_layout(int elem, int max_frames, int K, int cap, int N);
+size_t beam_word_conf_stream_state_bytes(int elem, int max_frames, int B, int K, int cap, int N);
+hipError_t launch_beam_word_conf_stream_reset(int elem, const BeamGraphArgs &BG, int K, int max_frames, int B, int N, void *state,
+                                              const unsigned char *mask, hipStream_t stream);
+template <typename R>
+hipError_t launch_beam_word_conf_stream_advance(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                                                const WordLookArgs *LA, int K, double theta, int max_frames, void *state,
+                                                hipStream_t stream);
+// P: B, N and the transition (its emissions and lengths are not read: the state has both).  Two launches: the catch-up of U / nu /
+// A from apos to pos (the only write to the state from a result path), then the hypothesis, Z and the beta pull.
+template <typename R>
+hipError_t launch_beam_word_conf_stream_confidence(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG,
+                                                   const WordLmArgs &LM, const WordLookArgs *LA, int K, int max_frames, void *state,
+                                                   int final, int tol, void *scores, long long *path, long long *tokens,
+                                                   long long *tlen, long long *states, long long *lm_states, long long *words,
+                                                   long long *wlen, long long *word_frames, void *word_conf, void *normalisers,
+                                                   long long *frames, long long *status, hipStream_t stream);
 
 // ---- Word confidences and end frames for every row of the n-best list (asg_beam_word_nbest_conf.hip):
 // asg_beam_words_nbest_confidence.  One utterance's workspace: asg_beam_words_confidence's layout at the front (the search's

@@ -319,6 +319,10 @@ BeamWordStreamResult = collections.namedtuple("BeamWordStreamResult", ["scores",
 BeamWordStreamNbest = collections.namedtuple("BeamWordStreamNbest", ["scores", "graph_scores", "lm_scores", "tokens", "token_lengths",
                                                                      "words", "word_lengths", "num_hyps", "path", "states",
                                                                      "lm_states", "frames", "status"])
+BeamWordStreamConfidence = collections.namedtuple("BeamWordStreamConfidence", ["scores", "path", "tokens", "token_lengths", "states",
+                                                                               "lm_states", "words", "word_lengths", "word_frames",
+                                                                               "word_confidences", "normalisers", "frames",
+                                                                               "status"])
 
 
 class BeamWordStream(_Stream):
@@ -350,6 +354,12 @@ class BeamWordStream(_Stream):
     (include/asg_hip.h::asg_beam_word_stream_advance_la): `result(final=True)` then equals that call, bit for bit, for any
     chunking, and a prefix result takes the estimate that has not cancelled yet back (see `result`).  The stream is bound to
     its look-ahead for life -- the values in the state carry it -- and the state has the same size with or without.
+
+    `keep_lattice=True` makes the state keep the lattice of the search as well (include/asg_hip.h::asg_beam_word_conf_stream_*:
+    the kept pair sets, the emissions and, lazily, alpha -- about max_frames * (N + 4 * beam_size) values more per slot), and then
+    `result_confidence` gives a confidence and an end frame per word at any point of the stream, with or without a look-ahead.
+    `advance`, `result`, `result_nbest` and `reset` return what they return without it, byte for byte.  The lattice pass keeps a
+    frame's set in LDS, so beam_size is bounded as for `beam_decode_words_confidence` (8179 float32, 6816 float64).
     Not here: a loss over a stream (the one-shot loss over pairs is `beam_words_asg_loss`); the public `result_nbest` of a
     stream with a look-ahead still raises (the library call, asg_beam_word_stream_nbest_la, is there and `_result_nbest` reaches
     it).
@@ -357,8 +367,12 @@ class BeamWordStream(_Stream):
     _API, _WIDE, _NARROW = "asg_beam_word_stream", 5, 4
 
     def __init__(self, transition, lexicon, word_lm, batch_size, max_frames, beam_size=256, beam_threshold=float("inf"),
-                 lm_weight=1.0, word_score=0.0, token_score=0.0, dtype=torch.float32, device=None, lookahead=None):
+                 lm_weight=1.0, word_score=0.0, token_score=0.0, dtype=torch.float32, device=None, lookahead=None,
+                 keep_lattice=False):
         self.lm_weight, self.word_score, self.token_score, self.lookahead = lm_weight, word_score, token_score, lookahead
+        self.keep_lattice = bool(keep_lattice)
+        if self.keep_lattice:
+            self._API = "asg_beam_word_conf_stream"            # the same calls in the same order over the wider state
         self._nbest_work = {}                                  # nbest -> the scratch of result_nbest (not part of the state)
         super().__init__(transition, (lexicon, word_lm), batch_size, (max_frames,), beam_size, beam_threshold, dtype, device)
         (self.max_frames,) = self._shape
@@ -438,7 +452,7 @@ class BeamWordStream(_Stream):
         L = _lib.lib()
         B, dev, T = self.batch_size, self.device, self.max_frames
         with be._guard(dev):
-            what = "asg_beam_word_stream_nbest" + ("" if self.lookahead is None else "_la")
+            what = self._API + "_nbest" + ("" if self.lookahead is None else "_la")
             fn = getattr(L, what)
 
             def call(work, nbytes, *outs):
@@ -447,7 +461,7 @@ class BeamWordStream(_Stream):
             work = self._nbest_work.get(nbest)
             if work is None:
                 abi_dtype = _lib.ASG_DTYPE_F32 if self.dtype == torch.float32 else _lib.ASG_DTYPE_F64
-                nbytes = int(L.asg_beam_word_stream_nbest_work_bytes(*self._views, B, abi_dtype, self.beam_size, T, nbest))
+                nbytes = int(getattr(L, self._API + "_nbest_work_bytes")(*self._views, B, abi_dtype, self.beam_size, T, nbest))
                 if nbytes == 0:                                # the library refuses the arguments: its call says why
                     _lib.check(call(None, 0, *(None,) * 13, 0, None), what)
                 work = self._nbest_work[nbest] = be._buf(nbytes, dev)
@@ -462,6 +476,49 @@ class BeamWordStream(_Stream):
                             narrow[0].data_ptr(), narrow[1].data_ptr(), narrow[2].data_ptr(), 0, be._stream(dev)), what)
         return BeamWordStreamNbest(sc[0], sc[1], sc[2], wide[0], lengths[0], wide[1], lengths[1], narrow[0], align[0], align[1],
                                    align[2], narrow[1], narrow[2])
+
+    def result_confidence(self, frame_tolerance=0, final=False):
+        """`result(final)` with a confidence and an end frame for every word, from the lattice the stream kept
+        (`keep_lattice=True`; RuntimeError without it, without touching the device) -> a named tuple
+          scores, path, tokens, token_lengths, states, lm_states, words, word_lengths, frames, status as `result(final)` returns
+          them;
+          word_frames [B, max_frames] int64, the frame at which word k ends (the frame of its separator, or the number of frames
+          for the word of the final step), -1 behind the words;
+          word_confidences [B, max_frames], the posterior, over the paths through the kept pair sets, that this word ends within
+          `frame_tolerance` frames of that frame, 0 behind the words; normalisers [B], log of the mass of all paths.
+        final=True: `beam_decode_words_confidence`'s result (with the stream's look-ahead, if it has one) for the utterance so
+        far, bit for bit, for any chunking and wherever `result_confidence` was called in between.  final=False: paths may end in
+        any kept pair of the last frame, mid-word ones included, without any end term; the words are those whose separator the
+        path has passed, and no word ends at the last frame by the end rule.  With a look-ahead the sets are the look-ahead
+        search's and the lattice is weighed plainly, as in `beam_decode_words_confidence`.  `transition` must not change within
+        an utterance.  Two launches, no synchronisation: the call captures and replays.  The first of them brings the stored
+        alpha rows up to the frames consumed -- the only write to the state from a result call; every frame's alpha is computed
+        once.  frame_tolerance < 0 raises ValueError, > 64 RuntimeError."""
+        if not self.keep_lattice:
+            raise RuntimeError("torch_asg_amd: result_confidence needs the lattice of the search: build the stream with "
+                               "keep_lattice=True")
+        if int(frame_tolerance) < 0:
+            raise ValueError("torch_asg_amd: frame_tolerance must be >= 0, got %d" % int(frame_tolerance))
+        tol = min(int(frame_tolerance), (1 << 31) - 1)
+        be = _asg.native()
+        L = _lib.lib()
+        B, dev, T = self.batch_size, self.device, self.max_frames
+        transition = self.transition
+        what = "asg_beam_word_conf_stream_confidence" + ("" if self.lookahead is None else "_la")
+        with be._guard(dev):
+            real = torch.empty(2, B, dtype=self.dtype, device=dev)                 # scores, normalisers
+            wide = torch.empty(6, B, T, dtype=torch.int64, device=dev)             # path, tokens, states, lm_states, words, frames
+            conf = torch.empty(B, T, dtype=self.dtype, device=dev)
+            narrow = torch.empty(4, B, dtype=torch.int64, device=dev)              # two lengths, frames, status
+            ts = (ctypes.c_int64 * 2)(*transition.stride())
+            _lib.check(getattr(L, what)(
+                None, *self._views, *self._look, B, self.beam_size, T, self._state.data_ptr(), self._state.numel(),
+                transition.data_ptr(), ts, 1 if final else 0, tol, real[0].data_ptr(), wide[0].data_ptr(), wide[1].data_ptr(),
+                narrow[0].data_ptr(), wide[2].data_ptr(), wide[3].data_ptr(), wide[4].data_ptr(), narrow[1].data_ptr(),
+                wide[5].data_ptr(), conf.data_ptr(), real[1].data_ptr(), narrow[2].data_ptr(), narrow[3].data_ptr(), 0,
+                be._stream(dev)), what)
+        return BeamWordStreamConfidence(real[0], wide[0], wide[1], narrow[0], wide[2], wide[3], wide[4], narrow[1], wide[5], conf,
+                                        real[1], narrow[2], narrow[3])
 
     @staticmethod
     def _outputs(scores, wide, narrow):
