@@ -11,6 +11,7 @@ import torch
 from beam_conf_ref import beam_conf_ref, window_confidences
 from beam_loss_cases import DEV, GRAPHS, INF, _asg, _lexicon, _ngram
 from beam_stream_conf_ref import BeamStreamConfRef
+from beam_stream_ref import BeamStreamRef
 from util import assert_close
 
 pytestmark = pytest.mark.gpu
@@ -290,6 +291,42 @@ def test_a_beam_that_empties_inside_a_chunk_on_its_first_and_on_its_last_frame(d
         assert pre.scores[0].item() == -INF and pre.normalisers[0].item() == -INF and pre.token_lengths[0].item() == 0
         assert (pre.token_frames[0] == -1).all() and (pre.token_confidences[0] == 0).all()
         assert not torch.isnan(pre.token_confidences).any()
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_the_plain_stream_and_the_lattice_keeping_one_run_one_advance(dtype):
+    """The two states are advanced by ONE kernel text (csrc/asg_beam_stream.hip, with and without the keep policy): for the same
+    chunks `result(final=False)`, `result(final=True)` and `result_nbest(2)` are the same bytes, at the smallest shape that
+    reaches every branch of the shared loop.  B = 3, N = 4, max_frames = 6, beam_size = 3 < Q = 4, a finite threshold; chunks of
+    1, 2 and 4 frames with per-slot lengths (1, 1, 1), (2, 2, 1), (4, 4, 2).  Checked with tests/beam_stream_ref.py, and asserted
+    below from it: slots 0 and 1 are offered 7 > 6 frames, take 3 of the last chunk's 4 and set `status`; slot 2 takes 4 frames
+    and does not; slot 1, whose emissions are -inf from frame 2 on, keeps 3, 3, 0, 0, 0, 0 states -- its beam empties on the
+    second frame of the second chunk and skips the third chunk from its first frame, the only slot whose beam empties --, and
+    slots 0 and 2 keep 3 states in every frame and have finite scores after every chunk."""
+    N, B, M, K, th = 4, 3, 6, 3, 4.0
+    graph = _asg().TokenGraph(np.zeros((1, N), np.int64), np.zeros((1, N)), np.zeros(1))
+    x, tr = _case(7, B, N, 41, dtype)
+    x[2:, 1] = -INF
+    chunks = [(x[0:1], torch.tensor([1, 1, 1])), (x[1:3], torch.tensor([2, 2, 1])), (x[3:7], torch.tensor([4, 4, 2]))]
+    ref = BeamStreamRef(tr.numpy(), graph.next, graph.weight, graph.final, graph.start, B, M, K, th, *W, dtype=_np(dtype))
+    s, plain = _stream(graph, tr, B, M, K, th), _stream(graph, tr, B, M, K, th, keep=False)
+    for i, (c, cl) in enumerate(chunks):
+        ref.advance(c.numpy(), cl.numpy())
+        for st in (s, plain):
+            st._fed = 0                                    # (the host's bound counts offered frames; the device's clamp is the subject)
+            st.advance(c.to(DEV), cl.to(DEV))
+        finite = np.isfinite(ref.result(False)[0])
+        assert finite.tolist() == [True, i < 1, True]
+        for final in (False, True):
+            a, b = s.result(final), plain.result(final)
+            assert _bits(a) == _bits(b), (i, final)
+            assert torch.isfinite(a.scores).cpu().numpy().tolist() == np.isfinite(ref.result(final)[0]).tolist()
+            assert _bits(s.result_nbest(2, final, True)) == _bits(plain.result_nbest(2, final, True)), (i, final)
+    assert ref.sizes() == [[3] * 6, [3, 3, 0, 0, 0, 0], [3] * 4]
+    got = s.result()
+    assert got.frames.tolist() == [6, 6, 4] == ref.result()[5].tolist() and got.status.tolist() == [1, 1, 0] == ref.result()[6].tolist()
+    conf = s.result_confidence(1, final=False)             # (the catch-up reads the kept counts of the skipped frames: 0)
+    assert conf.normalisers[1].item() == -INF and torch.isfinite(conf.normalisers[[0, 2]]).all()
 
 
 @pytest.mark.parametrize("dtype", DTYPES)

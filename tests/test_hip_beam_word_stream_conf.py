@@ -366,6 +366,47 @@ def test_a_beam_that_empties_inside_a_chunk_on_its_first_and_on_its_last_frame(d
 
 
 @DTYPES
+@pytest.mark.parametrize("order", [None, 2], ids=["plain", "la2"])
+def test_the_plain_stream_and_the_lattice_keeping_one_run_one_advance(order, dtype):
+    """The two states are advanced by ONE kernel text (csrc/asg_beam_word_stream.hip, with and without the keep policy, with and
+    without the look-ahead flag): for the same chunks `result(final=False)`, `result(final=True)` and the two best of the n-best
+    list are the same bytes, at the smallest shape that reaches every branch of the shared loop.  A two-word lexicon (0 1 and 2,
+    separator 3: N = 4) with a bigram; B = 3, max_frames = 6, beam_size = 3, a finite threshold; chunks of 1, 2 and 4 frames with
+    per-slot lengths (1, 1, 1), (2, 2, 1), (4, 4, 2).  Checked with tests/beam_word_stream_ref.py and
+    tests/beam_word_la_stream_ref.py (through the restatement that derives from them), and asserted below from it: slots 0 and 1
+    are offered 7 > 6 frames, take 3 of the last chunk's 4 and set `status`; slot 2 takes 4 frames and does not; slot 1, whose
+    emissions are -inf from frame 2 on, keeps 2, 3, 0, 0, 0, 0 pairs -- its beam empties on the second frame of the second chunk
+    and skips the third chunk from its first frame, the only slot whose beam empties --, and slots 0 and 2 keep 2 pairs in frame
+    0, 3 in every later frame, and have a finite best prefix after every chunk."""
+    A = _asg()
+    B, M, K, th = 3, 6, 3, 6.0
+    lex = A.Lexicon([[0, 1], [2]], 4, 3)
+    lm = arpa_lm(2, 2, 7)
+    la = None if order is None else A.WordLookahead(lex, lm, order)
+    x, tr = _normal(7, B, 4, 41, dtype)
+    x[2:, 1] = -INF
+    chunks = [(x[0:1], torch.tensor([1, 1, 1])), (x[1:3], torch.tensor([2, 2, 1])), (x[3:7], torch.tensor([4, 4, 2]))]
+    ref = _ref(tr, lex, lm, B, M, K, th, la=la)
+    s, plain = _stream(tr, lex, lm, B, M, K, th, la=la), _stream(tr, lex, lm, B, M, K, th, keep=False, la=la)
+    for i, (c, cl) in enumerate(chunks):
+        ref.advance(c.numpy(), cl.numpy())
+        for st in (s, plain):
+            st._fed = 0                                    # (the host's bound counts offered frames; the device's clamp is the subject)
+            st.advance(c.to(DEV), cl.to(DEV))
+        assert np.isfinite(ref.result(False)["scores"]).tolist() == [True, i < 1, True]
+        for final in (False, True):
+            a, b = s.result(final), plain.result(final)
+            assert _bits(a) == _bits(b), (i, final)
+            assert torch.isfinite(a.scores).cpu().numpy().tolist() == np.isfinite(ref.result(final)["scores"]).tolist()
+            assert _bits(s._result_nbest(2, final, True)) == _bits(plain._result_nbest(2, final, True)), (i, final)
+    assert ref.sizes() == [[2, 3, 3, 3, 3, 3], [2, 3, 0, 0, 0, 0], [2, 3, 3, 3]]
+    got, want = s.result(), ref.result()
+    assert got.frames.tolist() == [6, 6, 4] == want["frames"].tolist() and got.status.tolist() == [1, 1, 0] == want["status"].tolist()
+    conf = s.result_confidence(1, final=False)             # (the catch-up reads the kept counts of the skipped frames: 0)
+    assert conf.normalisers[1].item() == -INF and torch.isfinite(conf.normalisers[[0, 2]]).all()
+
+
+@DTYPES
 def test_the_end_rule_at_the_last_frame_the_unfinished_word_and_the_double_completion(dtype):
     lex, lm, x, tr = rescue_case(_np(dtype))                               # 0, 1 | 2, separator
     x, tr = torch.from_numpy(x), torch.from_numpy(tr)

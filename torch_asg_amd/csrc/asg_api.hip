@@ -837,62 +837,104 @@ size_t asg_beam_stream_state_bytes(const asg_token_graph_beam *gb, int64_t B, in
     return beam_stream_bytes(gb, B, dtype, beam_size, max_frames);
 }
 
-int asg_beam_stream_reset(asg_ctx *ctx, const asg_token_graph_beam *gb, int64_t B, int beam_size, int64_t max_frames, void *state,
-                          size_t state_bytes, const uint8_t *mask, int flags, void *stream) {
-    (void) ctx; (void) flags;
+// ONE host path for the calls a growing token-graph stream has with a plain state (asg_beam_stream_*) and with a lattice-keeping
+// one (asg_beam_conf_stream_*): reset, advance, result, n-best.  gl: the loss view a lattice-keeping state is checked and sized
+// through (gb is its beam view), null for a plain state.  The kernels are the same; what differs is the state's checks, its
+// bytes, the stride of a slot, and the advance kernel's keep policy.
+static int check_beam_conf_stream(const asg_token_graph_beam_loss *gl, int64_t B, int dtype, int beam_size, int64_t max_frames);
+static size_t beam_conf_stream_bytes(const asg_token_graph_beam_loss *gl, int64_t B, int dtype, int beam_size, int64_t max_frames);
+
+static int check_stream_state(const asg_token_graph_beam *gb, const asg_token_graph_beam_loss *gl, int64_t B, int dtype, int beam_size,
+                              int64_t max_frames) {
+    return gl ? check_beam_conf_stream(gl, B, dtype, beam_size, max_frames) : check_beam_stream(gb, B, dtype, beam_size, max_frames);
+}
+
+static size_t stream_state_bytes(const asg_token_graph_beam *gb, const asg_token_graph_beam_loss *gl, int64_t B, int dtype,
+                                 int beam_size, int64_t max_frames) {
+    return gl ? beam_conf_stream_bytes(gl, B, dtype, beam_size, max_frames) : beam_stream_bytes(gb, B, dtype, beam_size, max_frames);
+}
+
+// the stride of a slot for the launchers: 0 (their own layout's) for a plain state
+static size_t stream_state_per(const asg_token_graph_beam_loss *gl, int dtype, int beam_size, int64_t max_frames) {
+    return gl ? beam_conf_stream_bytes(gl, 1, dtype, beam_size, max_frames) : 0;
+}
+
+static int beam_stream_reset(const asg_token_graph_beam *gb, const asg_token_graph_beam_loss *gl, int64_t B, int beam_size,
+                             int64_t max_frames, void *state, size_t state_bytes, const uint8_t *mask, void *stream) {
     if (!gb || !gb->graph) return ASG_ERR_INVALID;
     const int dtype = gb->graph->dtype;
-    int rc = check_beam_stream(gb, B, dtype, beam_size, max_frames);
+    int rc = check_stream_state(gb, gl, B, dtype, beam_size, max_frames);
     if (rc) return rc;
     if (!state) return ASG_ERR_INVALID;
-    if (state_bytes < beam_stream_bytes(gb, B, dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
+    if (state_bytes < stream_state_bytes(gb, gl, B, dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
     const GraphArgs G = to_graph_args(gb->graph);
     return hip_status(launch_beam_stream_reset(dtype == ASG_DTYPE_F64 ? 8 : 4, G, to_beam_graph_args(gb),
                                                beam_graph_k(G.Q, beam_size), (int) max_frames, (int) B, state, mask,
-                                               (hipStream_t) stream));
+                                               (hipStream_t) stream, stream_state_per(gl, dtype, beam_size, max_frames)));
 }
 
-int asg_beam_stream_advance(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, int beam_size,
-                            double beam_threshold, int64_t max_frames, void *state, size_t state_bytes, int flags, void *stream) {
-    (void) ctx; (void) flags;
+static int beam_stream_advance(const asg_problem *p, const asg_token_graph_beam *gb, const asg_token_graph_beam_loss *gl,
+                               int beam_size, double beam_threshold, int64_t max_frames, void *state, size_t state_bytes,
+                               void *stream) {
     if (!p) return ASG_ERR_INVALID;
-    int rc = check_beam_stream(gb, p->B, p->dtype, beam_size, max_frames);
+    int rc = check_stream_state(gb, gl, p->B, p->dtype, beam_size, max_frames);
     if (rc) return rc;
     if (p->T < 0 || p->N != gb->graph->N) return ASG_ERR_INVALID;
     if (p->T > 0 && (rc = check_beam_graph(p, gb, beam_size)) != ASG_OK) return rc;
     if (!(beam_threshold >= 0.0)) return ASG_ERR_INVALID;                  // negative or NaN
     if (!state) return ASG_ERR_INVALID;
-    if (state_bytes < beam_stream_bytes(gb, p->B, p->dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
+    if (state_bytes < stream_state_bytes(gb, gl, p->B, p->dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
     if (p->T == 0) return ASG_OK;                                          // no frame: the state stays as it is
     const Problem P = to_problem(p);
     const GraphArgs G = to_graph_args(gb->graph);
     const BeamGraphArgs BG = to_beam_graph_args(gb);
     const int K = beam_graph_k(G.Q, beam_size);
     return hip_status(ASG_DISPATCH(p, launch_beam_stream_advance<float>(P, G, BG, K, beam_threshold, (int) max_frames, state,
-                                                                        (hipStream_t) stream),
+                                                                        (hipStream_t) stream, gl != nullptr),
                                    launch_beam_stream_advance<double>(P, G, BG, K, beam_threshold, (int) max_frames, state,
-                                                                      (hipStream_t) stream)));
+                                                                      (hipStream_t) stream, gl != nullptr)));
+}
+
+static int beam_stream_result(const asg_token_graph_beam *gb, const asg_token_graph_beam_loss *gl, int64_t B, int beam_size,
+                              int64_t max_frames, const void *state, size_t state_bytes, int final, void *scores, int64_t *path,
+                              int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *frames, int64_t *status,
+                              void *stream) {
+    if (!gb || !gb->graph) return ASG_ERR_INVALID;
+    const asg_token_graph *g = gb->graph;
+    int rc = check_stream_state(gb, gl, B, g->dtype, beam_size, max_frames);
+    if (rc) return rc;
+    if (!state || !scores || !path || !tokens || !token_lengths || !states || !frames || !status) return ASG_ERR_INVALID;
+    if (state_bytes < stream_state_bytes(gb, gl, B, g->dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
+    const GraphArgs G = to_graph_args(g);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    const int K = beam_graph_k(G.Q, beam_size);
+    const size_t per = stream_state_per(gl, g->dtype, beam_size, max_frames);
+    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
+    long long *fr = (long long *) frames, *su = (long long *) status;
+    return hip_status(ASG_DISPATCH(g, launch_beam_stream_result<float>(G, BG, K, (int) max_frames, (int) B, state, final, scores, pa,
+                                                                       tk, tl, st, fr, su, (hipStream_t) stream, per),
+                                   launch_beam_stream_result<double>(G, BG, K, (int) max_frames, (int) B, state, final, scores, pa,
+                                                                     tk, tl, st, fr, su, (hipStream_t) stream, per)));
+}
+
+int asg_beam_stream_reset(asg_ctx *ctx, const asg_token_graph_beam *gb, int64_t B, int beam_size, int64_t max_frames, void *state,
+                          size_t state_bytes, const uint8_t *mask, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    return beam_stream_reset(gb, nullptr, B, beam_size, max_frames, state, state_bytes, mask, stream);
+}
+
+int asg_beam_stream_advance(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, int beam_size,
+                            double beam_threshold, int64_t max_frames, void *state, size_t state_bytes, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    return beam_stream_advance(p, gb, nullptr, beam_size, beam_threshold, max_frames, state, state_bytes, stream);
 }
 
 int asg_beam_stream_result(asg_ctx *ctx, const asg_token_graph_beam *gb, int64_t B, int beam_size, int64_t max_frames,
                            const void *state, size_t state_bytes, int final, void *scores, int64_t *path, int64_t *tokens,
                            int64_t *token_lengths, int64_t *states, int64_t *frames, int64_t *status, int flags, void *stream) {
     (void) ctx; (void) flags;
-    if (!gb || !gb->graph) return ASG_ERR_INVALID;
-    const asg_token_graph *g = gb->graph;
-    int rc = check_beam_stream(gb, B, g->dtype, beam_size, max_frames);
-    if (rc) return rc;
-    if (!state || !scores || !path || !tokens || !token_lengths || !states || !frames || !status) return ASG_ERR_INVALID;
-    if (state_bytes < beam_stream_bytes(gb, B, g->dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
-    const GraphArgs G = to_graph_args(g);
-    const BeamGraphArgs BG = to_beam_graph_args(gb);
-    const int K = beam_graph_k(G.Q, beam_size);
-    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
-    long long *fr = (long long *) frames, *su = (long long *) status;
-    return hip_status(ASG_DISPATCH(g, launch_beam_stream_result<float>(G, BG, K, (int) max_frames, (int) B, state, final, scores, pa,
-                                                                       tk, tl, st, fr, su, (hipStream_t) stream),
-                                   launch_beam_stream_result<double>(G, BG, K, (int) max_frames, (int) B, state, final, scores, pa,
-                                                                     tk, tl, st, fr, su, (hipStream_t) stream)));
+    return beam_stream_result(gb, nullptr, B, beam_size, max_frames, state, state_bytes, final, scores, path, tokens, token_lengths,
+                              states, frames, status, stream);
 }
 
 // A word stream state is sized like a problem of max_frames frames, as a stream state is: the checks of asg_beam_decode_words
@@ -917,33 +959,63 @@ size_t asg_beam_word_stream_state_bytes(const asg_token_graph_beam *gb, const as
     return beam_word_stream_bytes(gb, B, dtype, beam_size, max_frames);
 }
 
+// ONE host path for the calls a growing word stream has with a plain state (asg_beam_word_stream_*) and with a lattice-keeping
+// one (asg_beam_word_conf_stream_*): reset, advance, result, n-best, each with a look-ahead or without.  `lattice` chooses the
+// state's checks, its bytes, the stride of a slot and the advance kernel's keep policy; the kernels are the same.
+static int check_beam_word_conf_stream(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype, int beam_size,
+                                       int64_t max_frames);
+static size_t beam_word_conf_stream_bytes(const asg_token_graph_beam *gb, int64_t B, int dtype, int beam_size, int64_t max_frames);
+
+static int check_word_stream_state(const asg_token_graph_beam *gb, const asg_word_lm *lm, bool lattice, int64_t B, int dtype,
+                                   int beam_size, int64_t max_frames) {
+    return lattice ? check_beam_word_conf_stream(gb, lm, B, dtype, beam_size, max_frames)
+                   : check_beam_word_stream(gb, lm, B, dtype, beam_size, max_frames);
+}
+
+static size_t word_stream_state_bytes(const asg_token_graph_beam *gb, bool lattice, int64_t B, int dtype, int beam_size,
+                                      int64_t max_frames) {
+    return lattice ? beam_word_conf_stream_bytes(gb, B, dtype, beam_size, max_frames)
+                   : beam_word_stream_bytes(gb, B, dtype, beam_size, max_frames);
+}
+
+// the stride of a slot for the launchers: 0 (their own layout's) for a plain state
+static size_t word_stream_state_per(const asg_token_graph_beam *gb, bool lattice, int dtype, int beam_size, int64_t max_frames) {
+    return lattice ? beam_word_conf_stream_bytes(gb, 1, dtype, beam_size, max_frames) : 0;
+}
+
+static int beam_word_stream_reset(const asg_token_graph_beam *gb, const asg_word_lm *lm, bool lattice, int64_t B, int beam_size,
+                                  int64_t max_frames, void *state, size_t state_bytes, const uint8_t *mask, void *stream) {
+    if (!gb || !gb->graph) return ASG_ERR_INVALID;
+    const int dtype = gb->graph->dtype;
+    int rc = check_word_stream_state(gb, lm, lattice, B, dtype, beam_size, max_frames);
+    if (rc) return rc;
+    if (!state) return ASG_ERR_INVALID;
+    if (state_bytes < word_stream_state_bytes(gb, lattice, B, dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
+    return hip_status(launch_beam_word_stream_reset(dtype == ASG_DTYPE_F64 ? 8 : 4, to_beam_graph_args(gb), beam_size,
+                                                    (int) max_frames, (int) B, state, mask, (hipStream_t) stream,
+                                                    word_stream_state_per(gb, lattice, dtype, beam_size, max_frames)));
+}
+
 int asg_beam_word_stream_reset(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
                                int64_t max_frames, void *state, size_t state_bytes, const uint8_t *mask, int flags, void *stream) {
     (void) ctx; (void) flags;
-    if (!gb || !gb->graph) return ASG_ERR_INVALID;
-    const int dtype = gb->graph->dtype;
-    int rc = check_beam_word_stream(gb, lm, B, dtype, beam_size, max_frames);
-    if (rc) return rc;
-    if (!state) return ASG_ERR_INVALID;
-    if (state_bytes < beam_word_stream_bytes(gb, B, dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
-    return hip_status(launch_beam_word_stream_reset(dtype == ASG_DTYPE_F64 ? 8 : 4, to_beam_graph_args(gb), beam_size,
-                                                    (int) max_frames, (int) B, state, mask, (hipStream_t) stream));
+    return beam_word_stream_reset(gb, lm, false, B, beam_size, max_frames, state, state_bytes, mask, stream);
 }
 
 // The four calls of the word streams that run the search or read its values, with a look-ahead (`with_la`: la is checked as
 // asg_beam_decode_words_la checks it, behind the LM) or without one: asg_beam_word_{stream,window}_{advance,result}[_la].
 static int beam_word_stream_advance(const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
-                                    const asg_word_lookahead *la, bool with_la, int beam_size, double beam_threshold,
+                                    const asg_word_lookahead *la, bool with_la, bool lattice, int beam_size, double beam_threshold,
                                     int64_t max_frames, void *state, size_t state_bytes, void *stream) {
     if (!p) return ASG_ERR_INVALID;
-    int rc = check_beam_word_stream(gb, lm, p->B, p->dtype, beam_size, max_frames);
+    int rc = check_word_stream_state(gb, lm, lattice, p->B, p->dtype, beam_size, max_frames);
     if (rc) return rc;
     if (with_la && (rc = check_word_lookahead(p->dtype, lm, la)) != ASG_OK) return rc;
     if (p->T < 0 || p->N != gb->graph->N) return ASG_ERR_INVALID;
     if (p->T > 0 && (rc = check_beam_words(p, gb, lm, beam_size)) != ASG_OK) return rc;
     if (!(beam_threshold >= 0.0)) return ASG_ERR_INVALID;                  // negative or NaN
     if (!state) return ASG_ERR_INVALID;
-    if (state_bytes < beam_word_stream_bytes(gb, p->B, p->dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
+    if (state_bytes < word_stream_state_bytes(gb, lattice, p->B, p->dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
     if (p->T == 0) return ASG_OK;                                          // no frame: the state stays as it is
     const Problem P = to_problem(p);
     const GraphArgs G = to_graph_args(gb->graph);
@@ -952,42 +1024,45 @@ static int beam_word_stream_advance(const asg_problem *p, const asg_token_graph_
     const WordLookArgs LA = with_la ? to_word_look_args(la) : WordLookArgs{};
     const WordLookArgs *look = with_la ? &LA : nullptr;
     return hip_status(ASG_DISPATCH(p, launch_beam_word_stream_advance<float>(P, G, BG, LM, look, beam_size, beam_threshold,
-                                                                             (int) max_frames, state, (hipStream_t) stream),
+                                                                             (int) max_frames, state, (hipStream_t) stream, lattice),
                                    launch_beam_word_stream_advance<double>(P, G, BG, LM, look, beam_size, beam_threshold,
-                                                                           (int) max_frames, state, (hipStream_t) stream)));
+                                                                           (int) max_frames, state, (hipStream_t) stream, lattice)));
 }
 
 int asg_beam_word_stream_advance(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
                                  int beam_size, double beam_threshold, int64_t max_frames, void *state, size_t state_bytes,
                                  int flags, void *stream) {
     (void) ctx; (void) flags;
-    return beam_word_stream_advance(p, gb, lm, nullptr, false, beam_size, beam_threshold, max_frames, state, state_bytes, stream);
+    return beam_word_stream_advance(p, gb, lm, nullptr, false, false, beam_size, beam_threshold, max_frames, state, state_bytes,
+                                    stream);
 }
 
 int asg_beam_word_stream_advance_la(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
                                     const asg_word_lookahead *la, int beam_size, double beam_threshold, int64_t max_frames,
                                     void *state, size_t state_bytes, int flags, void *stream) {
     (void) ctx; (void) flags;
-    return beam_word_stream_advance(p, gb, lm, la, true, beam_size, beam_threshold, max_frames, state, state_bytes, stream);
+    return beam_word_stream_advance(p, gb, lm, la, true, false, beam_size, beam_threshold, max_frames, state, state_bytes, stream);
 }
 
 static int beam_word_stream_result(const asg_token_graph_beam *gb, const asg_word_lm *lm, const asg_word_lookahead *la, bool with_la,
-                                   int64_t B, int beam_size, int64_t max_frames, const void *state, size_t state_bytes, int final,
+                                   bool lattice, int64_t B, int beam_size, int64_t max_frames, const void *state, size_t state_bytes,
+                                   int final,
                                    void *scores, int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states,
                                    int64_t *lm_states, int64_t *words, int64_t *word_lengths, int64_t *frames, int64_t *status,
                                    void *stream) {
     if (!gb || !gb->graph) return ASG_ERR_INVALID;
     const asg_token_graph *g = gb->graph;
-    int rc = check_beam_word_stream(gb, lm, B, g->dtype, beam_size, max_frames);
+    int rc = check_word_stream_state(gb, lm, lattice, B, g->dtype, beam_size, max_frames);
     if (rc) return rc;
     if (with_la && (rc = check_word_lookahead(g->dtype, lm, la)) != ASG_OK) return rc;
     if (!state || !scores || !path || !tokens || !token_lengths || !states || !lm_states || !words || !word_lengths || !frames ||
         !status)
         return ASG_ERR_INVALID;
-    if (state_bytes < beam_word_stream_bytes(gb, B, g->dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
+    if (state_bytes < word_stream_state_bytes(gb, lattice, B, g->dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
     const GraphArgs G = to_graph_args(g);
     const BeamGraphArgs BG = to_beam_graph_args(gb);
     const WordLmArgs LM = to_word_lm_args(lm);
+    const size_t per = word_stream_state_per(gb, lattice, g->dtype, beam_size, max_frames);
     long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
     long long *ls = (long long *) lm_states, *wd = (long long *) words, *wl = (long long *) word_lengths;
     long long *fr = (long long *) frames, *su = (long long *) status;
@@ -995,10 +1070,10 @@ static int beam_word_stream_result(const asg_token_graph_beam *gb, const asg_wor
     const WordLookArgs *look = with_la ? &LA : nullptr;
     return hip_status(ASG_DISPATCH(g, launch_beam_word_stream_result<float>(G, BG, LM, look, beam_size, (int) max_frames, (int) B,
                                                                             state, final, scores, pa, tk, tl, st, ls, wd, wl, fr,
-                                                                            su, (hipStream_t) stream),
+                                                                            su, (hipStream_t) stream, per),
                                    launch_beam_word_stream_result<double>(G, BG, LM, look, beam_size, (int) max_frames, (int) B,
                                                                           state, final, scores, pa, tk, tl, st, ls, wd, wl, fr,
-                                                                          su, (hipStream_t) stream)));
+                                                                          su, (hipStream_t) stream, per)));
 }
 
 int asg_beam_word_stream_result(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
@@ -1006,8 +1081,8 @@ int asg_beam_word_stream_result(asg_ctx *ctx, const asg_token_graph_beam *gb, co
                                 int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words,
                                 int64_t *word_lengths, int64_t *frames, int64_t *status, int flags, void *stream) {
     (void) ctx; (void) flags;
-    return beam_word_stream_result(gb, lm, nullptr, false, B, beam_size, max_frames, state, state_bytes, final, scores, path, tokens,
-                                   token_lengths, states, lm_states, words, word_lengths, frames, status, stream);
+    return beam_word_stream_result(gb, lm, nullptr, false, false, B, beam_size, max_frames, state, state_bytes, final, scores, path,
+                                   tokens, token_lengths, states, lm_states, words, word_lengths, frames, status, stream);
 }
 
 int asg_beam_word_stream_result_la(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm,
@@ -1016,13 +1091,13 @@ int asg_beam_word_stream_result_la(asg_ctx *ctx, const asg_token_graph_beam *gb,
                                    int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words,
                                    int64_t *word_lengths, int64_t *frames, int64_t *status, int flags, void *stream) {
     (void) ctx; (void) flags;
-    return beam_word_stream_result(gb, lm, la, true, B, beam_size, max_frames, state, state_bytes, final, scores, path, tokens,
-                                   token_lengths, states, lm_states, words, word_lengths, frames, status, stream);
+    return beam_word_stream_result(gb, lm, la, true, false, B, beam_size, max_frames, state, state_bytes, final, scores, path,
+                                   tokens, token_lengths, states, lm_states, words, word_lengths, frames, status, stream);
 }
 
-static int check_beam_word_stream_nbest(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype, int beam_size,
-                                        int64_t max_frames, int nbest) {
-    int rc = check_beam_word_stream(gb, lm, B, dtype, beam_size, max_frames);
+static int check_beam_word_stream_nbest(const asg_token_graph_beam *gb, const asg_word_lm *lm, bool lattice, int64_t B, int dtype,
+                                        int beam_size, int64_t max_frames, int nbest) {
+    int rc = check_word_stream_state(gb, lm, lattice, B, dtype, beam_size, max_frames);
     if (rc) return rc;
     if (nbest < 1) return ASG_ERR_INVALID;
     if (nbest > kBeamMaxNbest) return ASG_ERR_UNSUPPORTED;
@@ -1031,30 +1106,32 @@ static int check_beam_word_stream_nbest(const asg_token_graph_beam *gb, const as
 
 size_t asg_beam_word_stream_nbest_work_bytes(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype,
                                              int beam_size, int64_t max_frames, int nbest) {
-    if (check_beam_word_stream_nbest(gb, lm, B, dtype, beam_size, max_frames, nbest) != ASG_OK) return 0;
+    if (check_beam_word_stream_nbest(gb, lm, false, B, dtype, beam_size, max_frames, nbest) != ASG_OK) return 0;
     return beam_word_stream_nbest_work_bytes((int) max_frames, (int) B, beam_size, nbest);
 }
 
 // asg_beam_word_stream_nbest with a look-ahead (`with_la`, checked behind the LM) or without one.
 static int beam_word_stream_nbest(const asg_token_graph_beam *gb, const asg_word_lm *lm, const asg_word_lookahead *la, bool with_la,
-                                  int64_t B, int beam_size, int64_t max_frames, const void *state, size_t state_bytes, int final,
+                                  bool lattice, int64_t B, int beam_size, int64_t max_frames, const void *state, size_t state_bytes,
+                                  int final,
                                   int nbest, void *work, size_t work_bytes, void *scores, void *graph_scores, void *lm_scores,
                                   int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *lm_states,
                                   int64_t *words, int64_t *word_lengths, int64_t *num_hyps, int64_t *frames, int64_t *status,
                                   void *stream) {
     if (!gb || !gb->graph) return ASG_ERR_INVALID;
     const asg_token_graph *g = gb->graph;
-    int rc = check_beam_word_stream_nbest(gb, lm, B, g->dtype, beam_size, max_frames, nbest);
+    int rc = check_beam_word_stream_nbest(gb, lm, lattice, B, g->dtype, beam_size, max_frames, nbest);
     if (rc) return rc;
     if (with_la && (rc = check_word_lookahead(g->dtype, lm, la)) != ASG_OK) return rc;
     if (!state || !work || !scores || !graph_scores || !lm_scores || !tokens || !token_lengths || !words || !word_lengths ||
         !num_hyps || !frames || !status)
         return ASG_ERR_INVALID;
-    if (state_bytes < beam_word_stream_bytes(gb, B, g->dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
+    if (state_bytes < word_stream_state_bytes(gb, lattice, B, g->dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
     if (work_bytes < beam_word_stream_nbest_work_bytes((int) max_frames, (int) B, beam_size, nbest)) return ASG_ERR_WORKSPACE;
     const GraphArgs G = to_graph_args(g);
     const BeamGraphArgs BG = to_beam_graph_args(gb);
     const WordLmArgs LM = to_word_lm_args(lm);
+    const size_t per = word_stream_state_per(gb, lattice, g->dtype, beam_size, max_frames);
     long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
     long long *ls = (long long *) lm_states, *wd = (long long *) words, *wl = (long long *) word_lengths;
     long long *nh = (long long *) num_hyps, *fr = (long long *) frames, *su = (long long *) status;
@@ -1063,18 +1140,20 @@ static int beam_word_stream_nbest(const asg_token_graph_beam *gb, const asg_word
         return hip_status(ASG_DISPATCH(g, launch_beam_word_stream_nbest_la<float>(G, BG, LM, LA, beam_size, (int) max_frames, (int) B,
                                                                                   state, final, nbest, work, scores, graph_scores,
                                                                                   lm_scores, pa, tk, tl, st, ls, wd, wl, nh, fr, su,
-                                                                                  (hipStream_t) stream),
+                                                                                  (hipStream_t) stream, per),
                                        launch_beam_word_stream_nbest_la<double>(G, BG, LM, LA, beam_size, (int) max_frames, (int) B,
                                                                                 state, final, nbest, work, scores, graph_scores,
                                                                                 lm_scores, pa, tk, tl, st, ls, wd, wl, nh, fr, su,
-                                                                                (hipStream_t) stream)));
+                                                                                (hipStream_t) stream, per)));
     }
     return hip_status(ASG_DISPATCH(g, launch_beam_word_stream_nbest<float>(G, BG, LM, beam_size, (int) max_frames, (int) B, state,
                                                                            final, nbest, work, scores, graph_scores, lm_scores, pa,
-                                                                           tk, tl, st, ls, wd, wl, nh, fr, su, (hipStream_t) stream),
+                                                                           tk, tl, st, ls, wd, wl, nh, fr, su, (hipStream_t) stream,
+                                                                           per),
                                    launch_beam_word_stream_nbest<double>(G, BG, LM, beam_size, (int) max_frames, (int) B, state,
                                                                          final, nbest, work, scores, graph_scores, lm_scores, pa,
-                                                                         tk, tl, st, ls, wd, wl, nh, fr, su, (hipStream_t) stream)));
+                                                                         tk, tl, st, ls, wd, wl, nh, fr, su, (hipStream_t) stream,
+                                                                         per)));
 }
 
 int asg_beam_word_stream_nbest(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
@@ -1083,9 +1162,9 @@ int asg_beam_word_stream_nbest(asg_ctx *ctx, const asg_token_graph_beam *gb, con
                                int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words, int64_t *word_lengths,
                                int64_t *num_hyps, int64_t *frames, int64_t *status, int flags, void *stream) {
     (void) ctx; (void) flags;
-    return beam_word_stream_nbest(gb, lm, nullptr, false, B, beam_size, max_frames, state, state_bytes, final, nbest, work, work_bytes,
-                                  scores, graph_scores, lm_scores, path, tokens, token_lengths, states, lm_states, words, word_lengths,
-                                  num_hyps, frames, status, stream);
+    return beam_word_stream_nbest(gb, lm, nullptr, false, false, B, beam_size, max_frames, state, state_bytes, final, nbest, work,
+                                  work_bytes, scores, graph_scores, lm_scores, path, tokens, token_lengths, states, lm_states, words,
+                                  word_lengths, num_hyps, frames, status, stream);
 }
 
 int asg_beam_word_stream_nbest_la(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm,
@@ -1095,9 +1174,9 @@ int asg_beam_word_stream_nbest_la(asg_ctx *ctx, const asg_token_graph_beam *gb, 
                                   int64_t *states, int64_t *lm_states, int64_t *words, int64_t *word_lengths, int64_t *num_hyps,
                                   int64_t *frames, int64_t *status, int flags, void *stream) {
     (void) ctx; (void) flags;
-    return beam_word_stream_nbest(gb, lm, la, true, B, beam_size, max_frames, state, state_bytes, final, nbest, work, work_bytes,
-                                  scores, graph_scores, lm_scores, path, tokens, token_lengths, states, lm_states, words, word_lengths,
-                                  num_hyps, frames, status, stream);
+    return beam_word_stream_nbest(gb, lm, la, true, false, B, beam_size, max_frames, state, state_bytes, final, nbest, work,
+                                  work_bytes, scores, graph_scores, lm_scores, path, tokens, token_lengths, states, lm_states, words,
+                                  word_lengths, num_hyps, frames, status, stream);
 }
 
 // A window stream state is sized like a problem of W frames (the ring); P is the commit period.
@@ -1179,10 +1258,10 @@ int asg_beam_window_result(asg_ctx *ctx, const asg_token_graph_beam *gb, int64_t
                                                                      st, fr, co, su, (hipStream_t) stream)));
 }
 
-// The n best of the two token-graph streams: the checks of the corresponding _result call, then nbest.
-static int check_beam_stream_nbest(const asg_token_graph_beam *gb, int64_t B, int dtype, int beam_size, int64_t max_frames,
-                                   int nbest) {
-    int rc = check_beam_stream(gb, B, dtype, beam_size, max_frames);
+// The n best of the token-graph streams: the checks of the corresponding _result call, then nbest.
+static int check_beam_stream_nbest(const asg_token_graph_beam *gb, const asg_token_graph_beam_loss *gl, int64_t B, int dtype,
+                                   int beam_size, int64_t max_frames, int nbest) {
+    int rc = check_stream_state(gb, gl, B, dtype, beam_size, max_frames);
     if (rc) return rc;
     if (nbest < 1) return ASG_ERR_INVALID;
     if (nbest > kBeamMaxNbest) return ASG_ERR_UNSUPPORTED;
@@ -1195,8 +1274,36 @@ static size_t beam_stream_nbest_bytes(const asg_token_graph_beam *gb, int64_t B,
 
 size_t asg_beam_stream_nbest_work_bytes(const asg_token_graph_beam *gb, int64_t B, int dtype, int beam_size, int64_t max_frames,
                                         int nbest) {
-    if (check_beam_stream_nbest(gb, B, dtype, beam_size, max_frames, nbest) != ASG_OK) return 0;
+    if (check_beam_stream_nbest(gb, nullptr, B, dtype, beam_size, max_frames, nbest) != ASG_OK) return 0;
     return beam_stream_nbest_bytes(gb, B, beam_size, max_frames, nbest);
+}
+
+// gl: as for beam_stream_result
+static int beam_stream_nbest(const asg_token_graph_beam *gb, const asg_token_graph_beam_loss *gl, int64_t B, int beam_size,
+                             int64_t max_frames, const void *state, size_t state_bytes, int final, int nbest, void *work,
+                             size_t work_bytes, void *scores, void *graph_scores, int64_t *path, int64_t *tokens,
+                             int64_t *token_lengths, int64_t *states, int64_t *num_hyps, int64_t *frames, int64_t *status,
+                             void *stream) {
+    if (!gb || !gb->graph) return ASG_ERR_INVALID;
+    const asg_token_graph *g = gb->graph;
+    int rc = check_beam_stream_nbest(gb, gl, B, g->dtype, beam_size, max_frames, nbest);
+    if (rc) return rc;
+    if (!state || !work || !scores || !graph_scores || !tokens || !token_lengths || !num_hyps || !frames || !status)
+        return ASG_ERR_INVALID;
+    if (state_bytes < stream_state_bytes(gb, gl, B, g->dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
+    if (work_bytes < beam_stream_nbest_bytes(gb, B, beam_size, max_frames, nbest)) return ASG_ERR_WORKSPACE;
+    const GraphArgs G = to_graph_args(g);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    const int K = beam_graph_k(G.Q, beam_size);
+    const size_t per = stream_state_per(gl, g->dtype, beam_size, max_frames);
+    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
+    long long *nh = (long long *) num_hyps, *fr = (long long *) frames, *su = (long long *) status;
+    return hip_status(ASG_DISPATCH(g, launch_beam_stream_nbest<float>(G, BG, K, (int) max_frames, (int) B, state, final, nbest, work,
+                                                                      scores, graph_scores, pa, tk, tl, st, nh, fr, su,
+                                                                      (hipStream_t) stream, per),
+                                   launch_beam_stream_nbest<double>(G, BG, K, (int) max_frames, (int) B, state, final, nbest, work,
+                                                                    scores, graph_scores, pa, tk, tl, st, nh, fr, su,
+                                                                    (hipStream_t) stream, per)));
 }
 
 int asg_beam_stream_nbest(asg_ctx *ctx, const asg_token_graph_beam *gb, int64_t B, int beam_size, int64_t max_frames,
@@ -1204,25 +1311,8 @@ int asg_beam_stream_nbest(asg_ctx *ctx, const asg_token_graph_beam *gb, int64_t 
                           void *graph_scores, int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states,
                           int64_t *num_hyps, int64_t *frames, int64_t *status, int flags, void *stream) {
     (void) ctx; (void) flags;
-    if (!gb || !gb->graph) return ASG_ERR_INVALID;
-    const asg_token_graph *g = gb->graph;
-    int rc = check_beam_stream_nbest(gb, B, g->dtype, beam_size, max_frames, nbest);
-    if (rc) return rc;
-    if (!state || !work || !scores || !graph_scores || !tokens || !token_lengths || !num_hyps || !frames || !status)
-        return ASG_ERR_INVALID;
-    if (state_bytes < beam_stream_bytes(gb, B, g->dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
-    if (work_bytes < beam_stream_nbest_bytes(gb, B, beam_size, max_frames, nbest)) return ASG_ERR_WORKSPACE;
-    const GraphArgs G = to_graph_args(g);
-    const BeamGraphArgs BG = to_beam_graph_args(gb);
-    const int K = beam_graph_k(G.Q, beam_size);
-    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
-    long long *nh = (long long *) num_hyps, *fr = (long long *) frames, *su = (long long *) status;
-    return hip_status(ASG_DISPATCH(g, launch_beam_stream_nbest<float>(G, BG, K, (int) max_frames, (int) B, state, final, nbest, work,
-                                                                      scores, graph_scores, pa, tk, tl, st, nh, fr, su,
-                                                                      (hipStream_t) stream),
-                                   launch_beam_stream_nbest<double>(G, BG, K, (int) max_frames, (int) B, state, final, nbest, work,
-                                                                    scores, graph_scores, pa, tk, tl, st, nh, fr, su,
-                                                                    (hipStream_t) stream)));
+    return beam_stream_nbest(gb, nullptr, B, beam_size, max_frames, state, state_bytes, final, nbest, work, work_bytes, scores,
+                             graph_scores, path, tokens, token_lengths, states, num_hyps, frames, status, stream);
 }
 
 static int check_beam_window_nbest(const asg_token_graph_beam *gb, int64_t B, int dtype, int beam_size, int64_t W, int64_t P,
@@ -1626,92 +1716,40 @@ static size_t beam_conf_stream_bytes(const asg_token_graph_beam_loss *gl, int64_
                                         beam_graph_cap(Q, K, gb->max_out, (int) gb->num_start), (int) gb->graph->N);
 }
 
-// the stride of a slot, for the plain stream's result and n-best kernels
-static size_t beam_conf_stream_per(const asg_token_graph_beam_loss *gl, int dtype, int beam_size, int64_t max_frames) {
-    return beam_conf_stream_bytes(gl, 1, dtype, beam_size, max_frames);
-}
-
 size_t asg_beam_conf_stream_state_bytes(const asg_token_graph_beam_loss *gl, int64_t B, int dtype, int beam_size,
                                         int64_t max_frames) {
     if (check_beam_conf_stream(gl, B, dtype, beam_size, max_frames) != ASG_OK) return 0;
     return beam_conf_stream_bytes(gl, B, dtype, beam_size, max_frames);
 }
 
+// reset, advance, result and n-best: the plain stream's host path (beam_stream_reset and its siblings above) with the loss view
 int asg_beam_conf_stream_reset(asg_ctx *ctx, const asg_token_graph_beam_loss *gl, int64_t B, int beam_size, int64_t max_frames,
                                void *state, size_t state_bytes, const uint8_t *mask, int flags, void *stream) {
     (void) ctx; (void) flags;
-    if (!gl || !gl->beam || !gl->beam->graph) return ASG_ERR_INVALID;
-    const asg_token_graph_beam *gb = gl->beam;
-    const int dtype = gb->graph->dtype;
-    int rc = check_beam_conf_stream(gl, B, dtype, beam_size, max_frames);
-    if (rc) return rc;
-    if (!state) return ASG_ERR_INVALID;
-    if (state_bytes < beam_conf_stream_bytes(gl, B, dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
-    const GraphArgs G = to_graph_args(gb->graph);
-    return hip_status(launch_beam_conf_stream_reset(dtype == ASG_DTYPE_F64 ? 8 : 4, G, to_beam_graph_args(gb),
-                                                    beam_graph_k(G.Q, beam_size), (int) max_frames, (int) B, (int) gb->graph->N,
-                                                    state, mask, (hipStream_t) stream));
+    if (!gl) return ASG_ERR_INVALID;
+    return beam_stream_reset(gl->beam, gl, B, beam_size, max_frames, state, state_bytes, mask, stream);
 }
 
 int asg_beam_conf_stream_advance(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam_loss *gl, int beam_size,
                                  double beam_threshold, int64_t max_frames, void *state, size_t state_bytes, int flags,
                                  void *stream) {
     (void) ctx; (void) flags;
-    if (!p) return ASG_ERR_INVALID;
-    int rc = check_beam_conf_stream(gl, p->B, p->dtype, beam_size, max_frames);
-    if (rc) return rc;
-    const asg_token_graph_beam *gb = gl->beam;
-    if (p->T < 0 || p->N != gb->graph->N) return ASG_ERR_INVALID;
-    if (p->T > 0 && (rc = check_beam_graph(p, gb, beam_size)) != ASG_OK) return rc;
-    if (!(beam_threshold >= 0.0)) return ASG_ERR_INVALID;                  // negative or NaN
-    if (!state) return ASG_ERR_INVALID;
-    if (state_bytes < beam_conf_stream_bytes(gl, p->B, p->dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
-    if (p->T == 0) return ASG_OK;                                          // no frame: the state stays as it is
-    const Problem P = to_problem(p);
-    const GraphArgs G = to_graph_args(gb->graph);
-    const BeamGraphArgs BG = to_beam_graph_args(gb);
-    const int K = beam_graph_k(G.Q, beam_size);
-    return hip_status(ASG_DISPATCH(p, launch_beam_conf_stream_advance<float>(P, G, BG, K, beam_threshold, (int) max_frames, state,
-                                                                             (hipStream_t) stream),
-                                   launch_beam_conf_stream_advance<double>(P, G, BG, K, beam_threshold, (int) max_frames, state,
-                                                                           (hipStream_t) stream)));
+    if (!gl) return ASG_ERR_INVALID;
+    return beam_stream_advance(p, gl->beam, gl, beam_size, beam_threshold, max_frames, state, state_bytes, stream);
 }
 
 int asg_beam_conf_stream_result(asg_ctx *ctx, const asg_token_graph_beam_loss *gl, int64_t B, int beam_size, int64_t max_frames,
                                 const void *state, size_t state_bytes, int final, void *scores, int64_t *path, int64_t *tokens,
                                 int64_t *token_lengths, int64_t *states, int64_t *frames, int64_t *status, int flags, void *stream) {
     (void) ctx; (void) flags;
-    if (!gl || !gl->beam || !gl->beam->graph) return ASG_ERR_INVALID;
-    const asg_token_graph_beam *gb = gl->beam;
-    const asg_token_graph *g = gb->graph;
-    int rc = check_beam_conf_stream(gl, B, g->dtype, beam_size, max_frames);
-    if (rc) return rc;
-    if (!state || !scores || !path || !tokens || !token_lengths || !states || !frames || !status) return ASG_ERR_INVALID;
-    if (state_bytes < beam_conf_stream_bytes(gl, B, g->dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
-    const GraphArgs G = to_graph_args(g);
-    const BeamGraphArgs BG = to_beam_graph_args(gb);
-    const int K = beam_graph_k(G.Q, beam_size);
-    const size_t per = beam_conf_stream_per(gl, g->dtype, beam_size, max_frames);
-    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
-    long long *fr = (long long *) frames, *su = (long long *) status;
-    return hip_status(ASG_DISPATCH(g, launch_beam_stream_result<float>(G, BG, K, (int) max_frames, (int) B, state, final, scores, pa,
-                                                                       tk, tl, st, fr, su, (hipStream_t) stream, per),
-                                   launch_beam_stream_result<double>(G, BG, K, (int) max_frames, (int) B, state, final, scores, pa,
-                                                                     tk, tl, st, fr, su, (hipStream_t) stream, per)));
-}
-
-static int check_beam_conf_stream_nbest(const asg_token_graph_beam_loss *gl, int64_t B, int dtype, int beam_size, int64_t max_frames,
-                                        int nbest) {
-    int rc = check_beam_conf_stream(gl, B, dtype, beam_size, max_frames);
-    if (rc) return rc;
-    if (nbest < 1) return ASG_ERR_INVALID;
-    if (nbest > kBeamMaxNbest) return ASG_ERR_UNSUPPORTED;
-    return ASG_OK;
+    if (!gl) return ASG_ERR_INVALID;
+    return beam_stream_result(gl->beam, gl, B, beam_size, max_frames, state, state_bytes, final, scores, path, tokens, token_lengths,
+                              states, frames, status, stream);
 }
 
 size_t asg_beam_conf_stream_nbest_work_bytes(const asg_token_graph_beam_loss *gl, int64_t B, int dtype, int beam_size,
                                              int64_t max_frames, int nbest) {
-    if (check_beam_conf_stream_nbest(gl, B, dtype, beam_size, max_frames, nbest) != ASG_OK) return 0;
+    if (!gl || check_beam_stream_nbest(gl->beam, gl, B, dtype, beam_size, max_frames, nbest) != ASG_OK) return 0;
     return beam_stream_nbest_bytes(gl->beam, B, beam_size, max_frames, nbest);
 }
 
@@ -1720,27 +1758,9 @@ int asg_beam_conf_stream_nbest(asg_ctx *ctx, const asg_token_graph_beam_loss *gl
                                void *scores, void *graph_scores, int64_t *path, int64_t *tokens, int64_t *token_lengths,
                                int64_t *states, int64_t *num_hyps, int64_t *frames, int64_t *status, int flags, void *stream) {
     (void) ctx; (void) flags;
-    if (!gl || !gl->beam || !gl->beam->graph) return ASG_ERR_INVALID;
-    const asg_token_graph_beam *gb = gl->beam;
-    const asg_token_graph *g = gb->graph;
-    int rc = check_beam_conf_stream_nbest(gl, B, g->dtype, beam_size, max_frames, nbest);
-    if (rc) return rc;
-    if (!state || !work || !scores || !graph_scores || !tokens || !token_lengths || !num_hyps || !frames || !status)
-        return ASG_ERR_INVALID;
-    if (state_bytes < beam_conf_stream_bytes(gl, B, g->dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
-    if (work_bytes < beam_stream_nbest_bytes(gb, B, beam_size, max_frames, nbest)) return ASG_ERR_WORKSPACE;
-    const GraphArgs G = to_graph_args(g);
-    const BeamGraphArgs BG = to_beam_graph_args(gb);
-    const int K = beam_graph_k(G.Q, beam_size);
-    const size_t per = beam_conf_stream_per(gl, g->dtype, beam_size, max_frames);
-    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
-    long long *nh = (long long *) num_hyps, *fr = (long long *) frames, *su = (long long *) status;
-    return hip_status(ASG_DISPATCH(g, launch_beam_stream_nbest<float>(G, BG, K, (int) max_frames, (int) B, state, final, nbest, work,
-                                                                      scores, graph_scores, pa, tk, tl, st, nh, fr, su,
-                                                                      (hipStream_t) stream, per),
-                                   launch_beam_stream_nbest<double>(G, BG, K, (int) max_frames, (int) B, state, final, nbest, work,
-                                                                    scores, graph_scores, pa, tk, tl, st, nh, fr, su,
-                                                                    (hipStream_t) stream, per)));
+    if (!gl) return ASG_ERR_INVALID;
+    return beam_stream_nbest(gl->beam, gl, B, beam_size, max_frames, state, state_bytes, final, nbest, work, work_bytes, scores,
+                             graph_scores, path, tokens, token_lengths, states, num_hyps, frames, status, stream);
 }
 
 int asg_beam_conf_stream_confidence(asg_ctx *ctx, const asg_token_graph_beam_loss *gl, int64_t B, int beam_size, int64_t max_frames,
@@ -2006,92 +2026,27 @@ size_t asg_beam_word_conf_stream_state_bytes(const asg_token_graph_beam *gb, con
     return beam_word_conf_stream_bytes(gb, B, dtype, beam_size, max_frames);
 }
 
+// reset, advance, result and n-best: the plain word stream's host path (beam_word_stream_reset and its siblings) with lattice = true
 int asg_beam_word_conf_stream_reset(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
                                     int64_t max_frames, void *state, size_t state_bytes, const uint8_t *mask, int flags,
                                     void *stream) {
     (void) ctx; (void) flags;
-    if (!gb || !gb->graph) return ASG_ERR_INVALID;
-    const int dtype = gb->graph->dtype;
-    int rc = check_beam_word_conf_stream(gb, lm, B, dtype, beam_size, max_frames);
-    if (rc) return rc;
-    if (!state) return ASG_ERR_INVALID;
-    if (state_bytes < beam_word_conf_stream_bytes(gb, B, dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
-    return hip_status(launch_beam_word_conf_stream_reset(dtype == ASG_DTYPE_F64 ? 8 : 4, to_beam_graph_args(gb), beam_size,
-                                                         (int) max_frames, (int) B, (int) gb->graph->N, state, mask,
-                                                         (hipStream_t) stream));
-}
-
-// The calls of the lattice-keeping word stream that run the search or read its values, with a look-ahead (`with_la`, checked
-// behind the LM as asg_beam_word_stream_*_la check it) or without one.
-static int beam_word_conf_stream_advance(const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
-                                         const asg_word_lookahead *la, bool with_la, int beam_size, double beam_threshold,
-                                         int64_t max_frames, void *state, size_t state_bytes, void *stream) {
-    if (!p) return ASG_ERR_INVALID;
-    int rc = check_beam_word_conf_stream(gb, lm, p->B, p->dtype, beam_size, max_frames);
-    if (rc) return rc;
-    if (with_la && (rc = check_word_lookahead(p->dtype, lm, la)) != ASG_OK) return rc;
-    if (p->T < 0 || p->N != gb->graph->N) return ASG_ERR_INVALID;
-    if (p->T > 0 && (rc = check_beam_words(p, gb, lm, beam_size)) != ASG_OK) return rc;
-    if (!(beam_threshold >= 0.0)) return ASG_ERR_INVALID;                  // negative or NaN
-    if (!state) return ASG_ERR_INVALID;
-    if (state_bytes < beam_word_conf_stream_bytes(gb, p->B, p->dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
-    if (p->T == 0) return ASG_OK;                                          // no frame: the state stays as it is
-    const Problem P = to_problem(p);
-    const GraphArgs G = to_graph_args(gb->graph);
-    const BeamGraphArgs BG = to_beam_graph_args(gb);
-    const WordLmArgs LM = to_word_lm_args(lm);
-    const WordLookArgs LA = with_la ? to_word_look_args(la) : WordLookArgs{};
-    const WordLookArgs *look = with_la ? &LA : nullptr;
-    return hip_status(ASG_DISPATCH(p, launch_beam_word_conf_stream_advance<float>(P, G, BG, LM, look, beam_size, beam_threshold,
-                                                                                  (int) max_frames, state, (hipStream_t) stream),
-                                   launch_beam_word_conf_stream_advance<double>(P, G, BG, LM, look, beam_size, beam_threshold,
-                                                                                (int) max_frames, state, (hipStream_t) stream)));
+    return beam_word_stream_reset(gb, lm, true, B, beam_size, max_frames, state, state_bytes, mask, stream);
 }
 
 int asg_beam_word_conf_stream_advance(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
                                       int beam_size, double beam_threshold, int64_t max_frames, void *state, size_t state_bytes,
                                       int flags, void *stream) {
     (void) ctx; (void) flags;
-    return beam_word_conf_stream_advance(p, gb, lm, nullptr, false, beam_size, beam_threshold, max_frames, state, state_bytes,
-                                         stream);
+    return beam_word_stream_advance(p, gb, lm, nullptr, false, true, beam_size, beam_threshold, max_frames, state, state_bytes,
+                                    stream);
 }
 
 int asg_beam_word_conf_stream_advance_la(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
                                          const asg_word_lookahead *la, int beam_size, double beam_threshold, int64_t max_frames,
                                          void *state, size_t state_bytes, int flags, void *stream) {
     (void) ctx; (void) flags;
-    return beam_word_conf_stream_advance(p, gb, lm, la, true, beam_size, beam_threshold, max_frames, state, state_bytes, stream);
-}
-
-static int beam_word_conf_stream_result(const asg_token_graph_beam *gb, const asg_word_lm *lm, const asg_word_lookahead *la,
-                                        bool with_la, int64_t B, int beam_size, int64_t max_frames, const void *state,
-                                        size_t state_bytes, int final, void *scores, int64_t *path, int64_t *tokens,
-                                        int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words,
-                                        int64_t *word_lengths, int64_t *frames, int64_t *status, void *stream) {
-    if (!gb || !gb->graph) return ASG_ERR_INVALID;
-    const asg_token_graph *g = gb->graph;
-    int rc = check_beam_word_conf_stream(gb, lm, B, g->dtype, beam_size, max_frames);
-    if (rc) return rc;
-    if (with_la && (rc = check_word_lookahead(g->dtype, lm, la)) != ASG_OK) return rc;
-    if (!state || !scores || !path || !tokens || !token_lengths || !states || !lm_states || !words || !word_lengths || !frames ||
-        !status)
-        return ASG_ERR_INVALID;
-    if (state_bytes < beam_word_conf_stream_bytes(gb, B, g->dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
-    const GraphArgs G = to_graph_args(g);
-    const BeamGraphArgs BG = to_beam_graph_args(gb);
-    const WordLmArgs LM = to_word_lm_args(lm);
-    const size_t per = beam_word_conf_stream_bytes(gb, 1, g->dtype, beam_size, max_frames);   // the stride of a slot
-    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
-    long long *ls = (long long *) lm_states, *wd = (long long *) words, *wl = (long long *) word_lengths;
-    long long *fr = (long long *) frames, *su = (long long *) status;
-    const WordLookArgs LA = with_la ? to_word_look_args(la) : WordLookArgs{};
-    const WordLookArgs *look = with_la ? &LA : nullptr;
-    return hip_status(ASG_DISPATCH(g, launch_beam_word_stream_result<float>(G, BG, LM, look, beam_size, (int) max_frames, (int) B,
-                                                                            state, final, scores, pa, tk, tl, st, ls, wd, wl, fr,
-                                                                            su, (hipStream_t) stream, per),
-                                   launch_beam_word_stream_result<double>(G, BG, LM, look, beam_size, (int) max_frames, (int) B,
-                                                                          state, final, scores, pa, tk, tl, st, ls, wd, wl, fr,
-                                                                          su, (hipStream_t) stream, per)));
+    return beam_word_stream_advance(p, gb, lm, la, true, true, beam_size, beam_threshold, max_frames, state, state_bytes, stream);
 }
 
 int asg_beam_word_conf_stream_result(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
@@ -2100,8 +2055,8 @@ int asg_beam_word_conf_stream_result(asg_ctx *ctx, const asg_token_graph_beam *g
                                      int64_t *words, int64_t *word_lengths, int64_t *frames, int64_t *status, int flags,
                                      void *stream) {
     (void) ctx; (void) flags;
-    return beam_word_conf_stream_result(gb, lm, nullptr, false, B, beam_size, max_frames, state, state_bytes, final, scores, path,
-                                        tokens, token_lengths, states, lm_states, words, word_lengths, frames, status, stream);
+    return beam_word_stream_result(gb, lm, nullptr, false, true, B, beam_size, max_frames, state, state_bytes, final, scores, path,
+                                   tokens, token_lengths, states, lm_states, words, word_lengths, frames, status, stream);
 }
 
 int asg_beam_word_conf_stream_result_la(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm,
@@ -2110,67 +2065,14 @@ int asg_beam_word_conf_stream_result_la(asg_ctx *ctx, const asg_token_graph_beam
                                         int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words,
                                         int64_t *word_lengths, int64_t *frames, int64_t *status, int flags, void *stream) {
     (void) ctx; (void) flags;
-    return beam_word_conf_stream_result(gb, lm, la, true, B, beam_size, max_frames, state, state_bytes, final, scores, path, tokens,
-                                        token_lengths, states, lm_states, words, word_lengths, frames, status, stream);
-}
-
-static int check_beam_word_conf_stream_nbest(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype,
-                                             int beam_size, int64_t max_frames, int nbest) {
-    int rc = check_beam_word_conf_stream(gb, lm, B, dtype, beam_size, max_frames);
-    if (rc) return rc;
-    if (nbest < 1) return ASG_ERR_INVALID;
-    if (nbest > kBeamMaxNbest) return ASG_ERR_UNSUPPORTED;
-    return ASG_OK;
+    return beam_word_stream_result(gb, lm, la, true, true, B, beam_size, max_frames, state, state_bytes, final, scores, path, tokens,
+                                   token_lengths, states, lm_states, words, word_lengths, frames, status, stream);
 }
 
 size_t asg_beam_word_conf_stream_nbest_work_bytes(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype,
                                                   int beam_size, int64_t max_frames, int nbest) {
-    if (check_beam_word_conf_stream_nbest(gb, lm, B, dtype, beam_size, max_frames, nbest) != ASG_OK) return 0;
+    if (check_beam_word_stream_nbest(gb, lm, true, B, dtype, beam_size, max_frames, nbest) != ASG_OK) return 0;
     return beam_word_stream_nbest_work_bytes((int) max_frames, (int) B, beam_size, nbest);
-}
-
-static int beam_word_conf_stream_nbest(const asg_token_graph_beam *gb, const asg_word_lm *lm, const asg_word_lookahead *la,
-                                       bool with_la, int64_t B, int beam_size, int64_t max_frames, const void *state,
-                                       size_t state_bytes, int final, int nbest, void *work, size_t work_bytes, void *scores,
-                                       void *graph_scores, void *lm_scores, int64_t *path, int64_t *tokens, int64_t *token_lengths,
-                                       int64_t *states, int64_t *lm_states, int64_t *words, int64_t *word_lengths,
-                                       int64_t *num_hyps, int64_t *frames, int64_t *status, void *stream) {
-    if (!gb || !gb->graph) return ASG_ERR_INVALID;
-    const asg_token_graph *g = gb->graph;
-    int rc = check_beam_word_conf_stream_nbest(gb, lm, B, g->dtype, beam_size, max_frames, nbest);
-    if (rc) return rc;
-    if (with_la && (rc = check_word_lookahead(g->dtype, lm, la)) != ASG_OK) return rc;
-    if (!state || !work || !scores || !graph_scores || !lm_scores || !tokens || !token_lengths || !words || !word_lengths ||
-        !num_hyps || !frames || !status)
-        return ASG_ERR_INVALID;
-    if (state_bytes < beam_word_conf_stream_bytes(gb, B, g->dtype, beam_size, max_frames)) return ASG_ERR_WORKSPACE;
-    if (work_bytes < beam_word_stream_nbest_work_bytes((int) max_frames, (int) B, beam_size, nbest)) return ASG_ERR_WORKSPACE;
-    const GraphArgs G = to_graph_args(g);
-    const BeamGraphArgs BG = to_beam_graph_args(gb);
-    const WordLmArgs LM = to_word_lm_args(lm);
-    const size_t per = beam_word_conf_stream_bytes(gb, 1, g->dtype, beam_size, max_frames);   // the stride of a slot
-    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
-    long long *ls = (long long *) lm_states, *wd = (long long *) words, *wl = (long long *) word_lengths;
-    long long *nh = (long long *) num_hyps, *fr = (long long *) frames, *su = (long long *) status;
-    if (with_la) {
-        const WordLookArgs LA = to_word_look_args(la);
-        return hip_status(ASG_DISPATCH(g, launch_beam_word_stream_nbest_la<float>(G, BG, LM, LA, beam_size, (int) max_frames, (int) B,
-                                                                                  state, final, nbest, work, scores, graph_scores,
-                                                                                  lm_scores, pa, tk, tl, st, ls, wd, wl, nh, fr, su,
-                                                                                  (hipStream_t) stream, per),
-                                       launch_beam_word_stream_nbest_la<double>(G, BG, LM, LA, beam_size, (int) max_frames, (int) B,
-                                                                                state, final, nbest, work, scores, graph_scores,
-                                                                                lm_scores, pa, tk, tl, st, ls, wd, wl, nh, fr, su,
-                                                                                (hipStream_t) stream, per)));
-    }
-    return hip_status(ASG_DISPATCH(g, launch_beam_word_stream_nbest<float>(G, BG, LM, beam_size, (int) max_frames, (int) B, state,
-                                                                           final, nbest, work, scores, graph_scores, lm_scores, pa,
-                                                                           tk, tl, st, ls, wd, wl, nh, fr, su, (hipStream_t) stream,
-                                                                           per),
-                                   launch_beam_word_stream_nbest<double>(G, BG, LM, beam_size, (int) max_frames, (int) B, state,
-                                                                         final, nbest, work, scores, graph_scores, lm_scores, pa,
-                                                                         tk, tl, st, ls, wd, wl, nh, fr, su, (hipStream_t) stream,
-                                                                         per)));
 }
 
 int asg_beam_word_conf_stream_nbest(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
@@ -2180,9 +2082,9 @@ int asg_beam_word_conf_stream_nbest(asg_ctx *ctx, const asg_token_graph_beam *gb
                                     int64_t *word_lengths, int64_t *num_hyps, int64_t *frames, int64_t *status, int flags,
                                     void *stream) {
     (void) ctx; (void) flags;
-    return beam_word_conf_stream_nbest(gb, lm, nullptr, false, B, beam_size, max_frames, state, state_bytes, final, nbest, work,
-                                       work_bytes, scores, graph_scores, lm_scores, path, tokens, token_lengths, states, lm_states,
-                                       words, word_lengths, num_hyps, frames, status, stream);
+    return beam_word_stream_nbest(gb, lm, nullptr, false, true, B, beam_size, max_frames, state, state_bytes, final, nbest, work,
+                                  work_bytes, scores, graph_scores, lm_scores, path, tokens, token_lengths, states, lm_states, words,
+                                  word_lengths, num_hyps, frames, status, stream);
 }
 
 int asg_beam_word_conf_stream_nbest_la(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm,
@@ -2192,9 +2094,9 @@ int asg_beam_word_conf_stream_nbest_la(asg_ctx *ctx, const asg_token_graph_beam 
                                        int64_t *states, int64_t *lm_states, int64_t *words, int64_t *word_lengths,
                                        int64_t *num_hyps, int64_t *frames, int64_t *status, int flags, void *stream) {
     (void) ctx; (void) flags;
-    return beam_word_conf_stream_nbest(gb, lm, la, true, B, beam_size, max_frames, state, state_bytes, final, nbest, work,
-                                       work_bytes, scores, graph_scores, lm_scores, path, tokens, token_lengths, states, lm_states,
-                                       words, word_lengths, num_hyps, frames, status, stream);
+    return beam_word_stream_nbest(gb, lm, la, true, true, B, beam_size, max_frames, state, state_bytes, final, nbest, work,
+                                  work_bytes, scores, graph_scores, lm_scores, path, tokens, token_lengths, states, lm_states, words,
+                                  word_lengths, num_hyps, frames, status, stream);
 }
 
 static int beam_word_conf_stream_confidence(const asg_token_graph_beam *gb, const asg_word_lm *lm, const asg_word_lookahead *la,

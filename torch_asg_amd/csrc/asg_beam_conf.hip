@@ -50,8 +50,7 @@ __global__ void __launch_bounds__(kBL) beam_conf_bwd(Problem P, typename TokenLa
     R *nb = (R *) lds;                                                         // [M] beta[t] of U_t
     int *nq = (int *) (lds + (size_t) M * sizeof(R));                          // [M] U_t
     unsigned long long *ring = (unsigned long long *) (lds + bwd_front(sizeof(R), 4, M));
-    const int tid = threadIdx.x, b = blockIdx.x;
-    const R NINF = Num<R>::ninf();
+    const int b = blockIdx.x;
     const int len = clamp_len(P.in_len, b, T);
     const R Z = Zs[b];
     const long long *pb = path + (int64_t) b * T;
@@ -62,33 +61,8 @@ __global__ void __launch_bounds__(kBL) beam_conf_bwd(Problem P, typename TokenLa
         const long long l = tlen[b];
         n = (int) (l < 0 ? 0 : (l > len ? len : l));                           // (a path of len frames starts at most len tokens)
     }
-    // ---- where the tokens start: the frames at which collapse_tokens kept a label
-    for (int k = n + tid; k < T; k += kBL) tf[k] = -1;
-    if (tid < 64 && n > 0) {
-        int base = 0;
-        long long carry = -1;
-        for (int c0 = 0; c0 < len; c0 += 64) {
-            const int t = c0 + tid;
-            const long long cur = t < len ? pb[t] : -1;
-            long long prv = __shfl_up(cur, 1);
-            if (tid == 0) prv = carry;
-            const bool keep = t < len && cur != prv;
-            const unsigned long long m = __ballot(keep);
-            const int pre = base + __popcll(m & ((1ull << tid) - 1ull));
-            if (keep && pre < n) tf[pre] = t;
-            base += __popcll(m);
-            carry = __shfl(cur, 63);
-        }
-    }
-    const int nw = Z > NINF ? n : 0;
-    for (int k = nw + tid; k < T; k += kBL) cf[k] = R(0);
-    if (nw == 0) return;
-    for (int x = tid; x < kConfRing; x += kBL) ring[x] = 0ull;
-    __threadfence();                                                           // the frames, for the windows of every wavefront
-    HypSink<R> sink;
-    sink.wd = tokens + (int64_t) b * T; sink.wf = tf; sink.cf = cf; sink.ring = ring; sink.tol = tol;
-    sink.ka = sink.kb = nw;
-    beam_conf_pull<R>(P, args, work + (size_t) b * args.lay.per, beta_off, Z, len, -tol - 1, nq, nb, sink);
+    beam_conf_tokens<R>(P, args, work + (size_t) b * args.lay.per, beta_off, Z, len, n, T, tol, pb, tokens + (int64_t) b * T, tf, cf,
+                        ring, nq, nb);
 }
 
 }  // namespace

@@ -10,6 +10,7 @@
 #pragma once
 #include "asg_beam_lattice.h"     // the helpers of the lattice pass: subgroup, find_sorted, the butterflies, to_fixed
 #include "asg_beam_token_lat.h"   // TokenLat: how a product state's edges are walked (shared with asg_beam_loss.hip)
+#include "asg_beam_conf_sink.h"   // HypSink, the ring and 2^54 (shared with the word confidences)
 
 namespace asg {
 
@@ -97,6 +98,44 @@ __device__ __forceinline__ void beam_conf_pull(const Problem &P, const typename 
         for (int x = tid; x < mt; x += kBL) sink.add(lat.label(nq[x]), (A[x] + nb[x]) - Z);
     __syncthreads();
     sink.window(last);                                                         // every window is closed
+}
+
+// The tail of a one-best confidence kernel (beam_conf_bwd of asg_beam_conf.hip, beam_stream_conf_bwd of asg_beam_stream_conf.hip),
+// behind the hypothesis -- pb: its path of len frames, tk: its n tokens -- and Z: token_frames from the path (one wavefront, the
+// ballot / popcount walk of collapse_tokens, so token k's frame is the frame its label was kept at), the zero fill of the
+// confidences, the ring, HypSink and the pull.  nb [M] / nq [M] / ring: the dynamic LDS (bwd_front, then kConfRing words).
+template <typename R, typename Lat = TokenLat<R>>
+__device__ __forceinline__ void beam_conf_tokens(const Problem &P, const typename Lat::Args &args, char *wb, size_t beta_off, R Z,
+                                                 int len, int n, int T, int tol, const long long *pb, const long long *tk,
+                                                 long long *tf, R *cf, unsigned long long *ring, int *nq, R *nb) {
+    const int tid = threadIdx.x;
+    // ---- where the tokens start: the frames at which collapse_tokens kept a label
+    for (int k = n + tid; k < T; k += kBL) tf[k] = -1;
+    if (tid < 64 && n > 0) {
+        int base = 0;
+        long long carry = -1;
+        for (int c0 = 0; c0 < len; c0 += 64) {
+            const int t = c0 + tid;
+            const long long cur = t < len ? pb[t] : -1;
+            long long prv = __shfl_up(cur, 1);
+            if (tid == 0) prv = carry;
+            const bool keep = t < len && cur != prv;
+            const unsigned long long m = __ballot(keep);
+            const int pre = base + __popcll(m & ((1ull << tid) - 1ull));
+            if (keep && pre < n) tf[pre] = t;
+            base += __popcll(m);
+            carry = __shfl(cur, 63);
+        }
+    }
+    const int nw = Z > Num<R>::ninf() ? n : 0;
+    for (int k = nw + tid; k < T; k += kBL) cf[k] = R(0);
+    if (nw == 0) return;
+    for (int x = tid; x < kConfRing; x += kBL) ring[x] = 0ull;
+    __threadfence();                                                           // the frames, for the windows of every wavefront
+    HypSink<R> sink;
+    sink.wd = tk; sink.wf = tf; sink.cf = cf; sink.ring = ring; sink.tol = tol;
+    sink.ka = sink.kb = nw;
+    beam_conf_pull<R, HypSink<R>, Lat>(P, args, wb, beta_off, Z, len, -tol - 1, nq, nb, sink);
 }
 
 }  // namespace

@@ -111,11 +111,13 @@ inline void set_lds(const void *fn, size_t dyn, size_t fixed = 0) {
 // power of two >= max(M, 2); a frame sorts only the p2 <= P2 slots its own |A_t| + |F_t| needs.  The sorted unique set does not
 // depend on how many pads were sorted with it.
 // ---------------------------------------------------------------------------------------------------------------------
-template <typename KeyT>
-__device__ void bitonic_sort(KeyT *v, int P2) {
+// (bitonic_sort_wg: ascending sort of v[0 .. P2), P2 a power of two, by a whole workgroup of WG threads -- kBS here, kBL in the
+// catch-up of the lattice-keeping streams, asg_beam_stream_lat.h)
+template <typename KeyT, int WG>
+__device__ void bitonic_sort_wg(KeyT *v, int P2) {
     for (int k = 2; k <= P2; k <<= 1)
         for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int x = threadIdx.x; x < P2; x += kBS) {
+            for (int x = threadIdx.x; x < P2; x += WG) {
                 const int y = x ^ j;
                 if (y > x) {
                     const KeyT a = v[x], c = v[y];
@@ -155,7 +157,7 @@ __global__ void __launch_bounds__(kBS) beam_loss_sets(Problem P, Pol pol, char *
         for (int x = tid; x < p2; x += kBS) v[x] = x < na ? pol.kept(wb, t, x) : (x < na + nf ? fk[k0 - 1 + (x - na)] : BIG);
         if (tid == 0) count = 0;
         __syncthreads();
-        bitonic_sort(v, p2);
+        bitonic_sort_wg<KeyT, kBS>(v, p2);
         // duplicates: flag them in the top bit (the neighbour's comparison masks it), then blank them and count the rest
         for (int x = tid; x < p2; x += kBS) {
             const KeyT a = v[x] & BIG;
@@ -169,7 +171,7 @@ __global__ void __launch_bounds__(kBS) beam_loss_sets(Problem P, Pol pol, char *
         }
         if (c) atomicAdd(&count, c);
         __syncthreads();
-        bitonic_sort(v, p2);
+        bitonic_sort_wg<KeyT, kBS>(v, p2);
         const int m = count;
         KeyT *U = (KeyT *) (wb + pol.lay.U) + (int64_t) t * M;
 #pragma nounroll                                                                // (unrolled 16 times it costs the int keys 32 VGPRs)

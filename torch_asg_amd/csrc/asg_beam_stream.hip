@@ -8,21 +8,27 @@
 //   the one-shot decoder's workspace of one utterance with T = max_frames (asg_beam_common.h, beam_work_layout): bq / bs int32
 //     [max_frames][K] (product state and source slot of every kept state of every frame consumed so far), arg u64 [Q], val key
 //     [Q], ckey key [cap], touched int32 [cap];
-//   a 256-byte header: int32 pos (frames consumed), |A| (size of the stored set), overflow;
+//   a 256-byte header: int32 pos (frames consumed), |A| (size of the stored set), overflow, and a word a plain state never reads
+//     (asg_beam_stream_lat.h);
 //   the stored set: values [K] (dtype), then product states int32 [K].
+// A LATTICE-KEEPING state (asg_beam_stream_conf.hip) has this slot at its front and more behind it.  Its search is this unit's: the
+// launchers take the slot's stride, and the advance kernel is a template over a keep policy (asg_beam_stream_lat.h)
+// -- KeepNone, empty, for the plain state; KeepLattice, which also writes |A_t| of every frame and the chunk's emissions.
 // Three kernels, each one launch, no host synchronisation, no copy, no memset:
-//   beam_stream_reset_kernel    per chosen slot: pos = 0, |A| = 0, overflow = 0, val = 0 and arg = none for all Q states.  The only
+//   beam_stream_reset_kernel    per chosen slot: the header zeroed, val = 0 and arg = none for all Q states.  The only
 //                               place the Q entries are written: a frame empties what it touched, so they are empty between calls.
 //   beam_stream_advance_kernel  one 1024-thread workgroup per slot: the transitions and the stored set into LDS, beam_frame for
 //                               the chunk's frames with the back-pointers into rows pos .. pos+n-1, the set and pos back.
-//   beam_stream_result_kernel   one workgroup per slot: the best end over the stored set (with or without the final weights), the
-//                               backtrace over pos frames, the token collapse, the padding.  It only reads the state.
+//   beam_stream_result_kernel   one workgroup per slot: beam_stream_hyp (asg_beam_stream_lat.h) -- the best end over the stored set
+//                               (with or without the final weights), the backtrace over pos frames, the token collapse, the
+//                               padding.  It only reads the state.
 // What one call writes and the next reads crosses a kernel boundary, so plain stores and loads do; val / arg keep the
 // device-scope atomics of the frame body.  Integer atomics only: bit-identical run to run.
 #include "asg_common.h"
 #include "asg_kernels.h"
 #include "asg_beam_common.h"
 #include "asg_beam_frame.h"
+#include "asg_beam_stream_lat.h"
 
 namespace asg {
 
@@ -34,12 +40,12 @@ __global__ void __launch_bounds__(256) beam_stream_reset_kernel(char *state, Bea
     if (mask && !mask[b]) return;
     char *wb = state + (size_t) b * lay.per;
     beam_reset_tables(wb, wl, Q, key_bytes);
-    if (blockIdx.y == 0 && threadIdx.x < 3) ((int *) (wb + lay.hdr))[threadIdx.x] = 0;      // pos, |A|, overflow
+    if (blockIdx.y == 0 && threadIdx.x < kHdrWords) ((int *) (wb + lay.hdr))[threadIdx.x] = 0;      // pos, |A|, overflow, apos
 }
 
-template <typename R, bool TRL>
+template <typename R, bool TRL, typename Keep>
 __global__ void __launch_bounds__(kBT) beam_stream_advance_kernel(Problem P, GraphArgs g, BeamGraphArgs bg, int K, R theta, int cap,
-                                                                  int max_frames, char *state, BeamStreamLayout lay) {
+                                                                  int max_frames, char *state, BeamStreamLayout lay, Keep keep) {
     using KT = Key<R>;
     using U = typename KT::U;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -52,13 +58,13 @@ __global__ void __launch_bounds__(kBT) beam_stream_advance_kernel(Problem P, Gra
     char *wb = state + (size_t) b * lay.per;
     int *hdr = (int *) (wb + lay.hdr);
     R *set_v = (R *) (wb + lay.set);                        // values [K], then product states [K]
-    int pos = hdr[0];
-    pos = pos < 0 ? 0 : (pos > max_frames ? max_frames : pos);             // (a state that was reset holds 0 .. max_frames)
+    const int pos = stream_pos(hdr, max_frames);
     const int want = clamp_len(P.in_len, b, P.T);
     const int n = want < max_frames - pos ? want : max_frames - pos;
     if (n < want && tid == 0) hdr[2] = 1;                   // frames beyond max_frames are not consumed
     if (n < 1) return;
     const R *in = (const R *) P.inputs + (int64_t) b * P.is1;
+    keep.chunk(wb, in, P, pos, n);
     const R *tr = (const R *) P.transition;
     BeamFrame<R> f;
     f.ctl = &ctl; f.cur_v = cur_v; f.cur_q = cur_q; f.trs = trs; f.tr = tr; f.ts0 = P.ts0; f.ts1 = P.ts1;
@@ -68,16 +74,17 @@ __global__ void __launch_bounds__(kBT) beam_stream_advance_kernel(Problem P, Gra
     int *bq, *bs;
     f.bind_work(wb, max_frames, cap, bq, bs);
 
-    int na0 = pos >= 1 ? hdr[1] : 0;
-    na0 = na0 < 0 ? 0 : (na0 > K ? K : na0);
-    beam_load_set<R, TRL>(f, trs, set_v, na0);
+    beam_load_set<R, TRL>(f, trs, set_v, stream_na(hdr, pos, K));
 
-    for (int t = 0; t < n; ++t) {
+    int t = 0;
+    for (; t < n; ++t) {
         const int gt = pos + t;                             // the frame's index in the utterance
         const int na = ctl.na;
         if (gt >= 1 && na == 0) break;                      // an empty beam stays empty
         beam_frame<R, TRL>(f, gt == 0, na, in + (int64_t) t * P.is0, P.is2, bq, bs, gt);
+        keep.frame(wb, gt, ctl.na < K ? ctl.na : K);
     }
+    keep.skipped(wb, pos, t, n);
 
     const int na = beam_store_set<R>(f, set_v);
     if (tid == 0) { hdr[1] = na; hdr[0] = pos + n; }
@@ -88,34 +95,10 @@ __global__ void __launch_bounds__(kBT) beam_stream_result_kernel(GraphArgs g, in
                                                                  const char *state, BeamStreamLayout lay, int final, R *scores,
                                                                  long long *path, long long *tokens, long long *tlen,
                                                                  long long *states, long long *frames, long long *status) {
-    using U = typename Key<R>::U;
-    __shared__ Ctl<U> ctl;
-    const int tid = threadIdx.x, b = blockIdx.x, T = max_frames;
-    const R NINF = Num<R>::ninf();
-    const char *wb = state + (size_t) b * lay.per;
-    const int *hdr = (const int *) (wb + lay.hdr);
-    const R *set_v = (const R *) (wb + lay.set);
-    const int *set_q = (const int *) (set_v + K);
-    const BeamWorkLayout wl = beam_work_layout(sizeof(R), T, g.Q, K, cap);
-    const int *bq = (const int *) (wb + wl.bq), *bs = (const int *) (wb + wl.bs);             // [max_frames][K]
-    long long *pb = path + (int64_t) b * T, *tk = tokens + (int64_t) b * T, *st = states + (int64_t) b * T;
-    int L = hdr[0];
-    L = L < 0 ? 0 : (L > T ? T : L);
-    int na = L >= 1 ? hdr[1] : 0;
-    na = na < 0 ? 0 : (na > K ? K : na);
-    if (tid == 0) { frames[b] = L; status[b] = hdr[2] != 0; }
-    const R *fw = final ? (const R *) g.final_w : nullptr;
-    U bkey;
-    int bqq, bk;
-    beam_best_end<R>(ctl, set_q, set_v, na, fw, bkey, bqq, bk);
-    if (bkey == 0) {                                        // no frame yet, an empty set, or no finite end
-        beam_no_path(T, pb, tk, st, tlen + b);
-        if (tid == 0) scores[b] = NINF;
-        return;
-    }
-    // the score itself, from the winner's own sum (the key folds -0 into +0)
-    if (tid == 0) scores[b] = fw ? set_v[bk] + fw[bqq] : set_v[bk];
-    beam_backtrace(bq, bs, K, L, T, bk, g.label, g.state, pb, tk, st, tlen + b);
+    __shared__ Ctl<typename Key<R>::U> ctl;
+    int len;
+    beam_stream_hyp<R>(ctl, g, K, cap, max_frames, state + (size_t) blockIdx.x * lay.per, lay, final, scores, path, tokens, tlen,
+                       states, frames, status, len);
 }
 
 }  // namespace
@@ -134,39 +117,54 @@ size_t beam_stream_state_bytes(int elem, int max_frames, int B, int Q, int K, in
 }
 
 hipError_t launch_beam_stream_reset(int elem, const GraphArgs &G, const BeamGraphArgs &BG, int K, int max_frames, int B, void *state,
-                                    const unsigned char *mask, hipStream_t stream) {
+                                    const unsigned char *mask, hipStream_t stream, size_t stride) {
     const int cap = beam_graph_cap(G.Q, K, BG.max_out, BG.num_start);
-    const BeamStreamLayout lay = beam_stream_layout(elem, max_frames, G.Q, K, cap);
+    BeamStreamLayout lay = beam_stream_layout(elem, max_frames, G.Q, K, cap);
+    if (stride) lay.per = stride;                                           // (a slot with parts of the caller's behind it)
     hipLaunchKernelGGL(beam_stream_reset_kernel, dim3(B, reset_blocks(G.Q)), dim3(256), 0, stream, (char *) state, lay,
                        beam_work_layout(elem, max_frames, G.Q, K, cap), G.Q, elem, mask);
     return hipGetLastError();
 }
 
-template <typename R>
-hipError_t launch_beam_stream_advance(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, int K, double theta,
-                                      int max_frames, void *state, hipStream_t stream) {
+namespace {
+
+template <typename R, typename Keep>
+hipError_t beam_stream_advance(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, int K, double theta, int cap,
+                               int max_frames, void *state, const BeamStreamLayout &lay, Keep keep, hipStream_t stream) {
     const int N = P.N;
-    const int cap = beam_graph_cap(G.Q, K, BG.max_out, BG.num_start);
-    const BeamStreamLayout lay = beam_stream_layout(sizeof(R), max_frames, G.Q, K, cap);
     // the LDS of the one-shot decoder: control block, the set, and the transitions when they fit beside it
     const size_t beam = kFixedLds + (size_t) K * (sizeof(R) + 4) + 8;
     const bool trl = beam + (size_t) N * N * sizeof(R) <= kLdsMax;
     const size_t dyn = beam + (trl ? (size_t) N * N * sizeof(R) : 0);
 #define ASG_BEAM_STREAM(TRL)                                                                                               \
     do {                                                                                                                   \
-        const void *fn = (const void *) beam_stream_advance_kernel<R, TRL>;                                               \
+        const void *fn = (const void *) beam_stream_advance_kernel<R, TRL, Keep>;                                         \
         if (dyn > 64 * 1024) (void) hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) dyn);     \
-        hipLaunchKernelGGL((beam_stream_advance_kernel<R, TRL>), dim3(P.B), dim3(kBT), dyn, stream, P, G, BG, K, (R) theta, \
-                           cap, max_frames, (char *) state, lay);                                                          \
+        hipLaunchKernelGGL((beam_stream_advance_kernel<R, TRL, Keep>), dim3(P.B), dim3(kBT), dyn, stream, P, G, BG, K,   \
+                           (R) theta, cap, max_frames, (char *) state, lay, keep);                                         \
     } while (0)
     if (trl) ASG_BEAM_STREAM(true); else ASG_BEAM_STREAM(false);
 #undef ASG_BEAM_STREAM
     return hipGetLastError();
 }
+
+}  // namespace
+
+template <typename R>
+hipError_t launch_beam_stream_advance(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, int K, double theta,
+                                      int max_frames, void *state, hipStream_t stream, bool lattice) {
+    const int cap = beam_graph_cap(G.Q, K, BG.max_out, BG.num_start);
+    if (lattice) {
+        const BeamConfStreamLayout lay = beam_conf_stream_layout(sizeof(R), max_frames, G.Q, K, cap, P.N);
+        return beam_stream_advance<R>(P, G, BG, K, theta, cap, max_frames, state, lay.st, KeepLattice{lay.lat.cnt, lay.em}, stream);
+    }
+    return beam_stream_advance<R>(P, G, BG, K, theta, cap, max_frames, state, beam_stream_layout(sizeof(R), max_frames, G.Q, K, cap),
+                                  KeepNone{}, stream);
+}
 template hipError_t launch_beam_stream_advance<float>(const Problem &, const GraphArgs &, const BeamGraphArgs &, int, double, int,
-                                                      void *, hipStream_t);
+                                                      void *, hipStream_t, bool);
 template hipError_t launch_beam_stream_advance<double>(const Problem &, const GraphArgs &, const BeamGraphArgs &, int, double, int,
-                                                       void *, hipStream_t);
+                                                       void *, hipStream_t, bool);
 
 template <typename R>
 hipError_t launch_beam_stream_result(const GraphArgs &G, const BeamGraphArgs &BG, int K, int max_frames, int B, const void *state,

@@ -119,17 +119,7 @@ __global__ void __launch_bounds__(kBT) beam_word_conf_search(Problem P, GraphArg
     }
     word_backtrace<R, LA>(f, fw, true, cur_h, cur_q, cur_v, bk, bq, bh, bs, len, T, scores + b, pb, tk, st, ls, wd, tlen + b,
                           wlen + b);
-    // ---- where the words end: the frames of the separator edges word_backtrace read its words from, then len for the word of
-    // the final step (the one word it appended behind them)
-    for (int u = tid; u < T; u += kBT) wf[u] = -1;
-    __threadfence();
-    __syncthreads();
-    if (tid == 0) {
-        int nw = 0;
-        for (int u = 1; u < len; ++u)
-            if (pb[u] == f.sep && pb[u - 1] != f.sep) wf[nw++] = u;
-        if (nw < (int) wlen[b]) wf[nw] = len;
-    }
+    word_end_frames(pb, f.sep, len, T, wlen + b, wf);      // (with the word of the final step)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -150,23 +140,17 @@ __global__ void __launch_bounds__(kBL) beam_word_conf_bwd(Problem P, typename Wo
     KeyT *nq = (KeyT *) lds;                                                   // [M] U_t
     R *nb = (R *) (lds + (size_t) M * sizeof(KeyT));                           // [M] beta[t] of U_t
     unsigned long long *ring = (unsigned long long *) (lds + bwd_front(sizeof(R), sizeof(KeyT), M));
-    const int tid = threadIdx.x, b = blockIdx.x;
+    const int b = blockIdx.x;
     const R NINF = Num<R>::ninf();
     const int len = clamp_len(P.in_len, b, T);
     const R Z = Zs[b];
-    R *cf = conf + (int64_t) b * T;
-    HypSink<R> sink;
-    sink.wd = words + (int64_t) b * T; sink.wf = wframes + (int64_t) b * T; sink.cf = cf; sink.ring = ring; sink.tol = tol;
     int nw = 0;
     if (len >= 1 && Z > NINF) {
         const long long n = wlen[b];
         nw = (int) (n < 0 ? 0 : (n > len ? len : n));                          // (a path of len frames ends at most len words)
     }
-    for (int k = nw + tid; k < T; k += kBL) cf[k] = R(0);
-    if (nw == 0) return;
-    for (int x = tid; x < kConfRing; x += kBL) ring[x] = 0ull;
-    sink.ka = sink.kb = nw;
-    beam_word_conf_pull<R>(P, args, work + (size_t) b * args.lay.per, beta_off, Z, len, -tol - 1, nq, nb, sink);
+    beam_word_conf_words<R>(P, args, work + (size_t) b * args.lay.per, beta_off, Z, len, nw, T, tol, words + (int64_t) b * T,
+                            wframes + (int64_t) b * T, conf + (int64_t) b * T, ring, nq, nb);
 }
 
 }  // namespace

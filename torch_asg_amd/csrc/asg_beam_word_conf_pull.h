@@ -108,6 +108,40 @@ __device__ __forceinline__ void beam_word_conf_pull(const Problem &P, const type
     sink.window(last);                                                         // every window is closed
 }
 
+// Where the words of a hypothesis end, behind word_backtrace (pb: its path of len frames, *wlen: its word count): the frames of
+// the separator edges word_backtrace read its words from, then len for the word of a final step (the one word it appended behind
+// them; a prefix has none: its word count is the separator count).  Every thread of the search's or the pull's workgroup.
+static_assert(kBT == kBL, "word_end_frames strides by either workgroup");
+__device__ __forceinline__ void word_end_frames(const long long *pb, int sep, int len, int T, const long long *wlen, long long *wf) {
+    for (int u = threadIdx.x; u < T; u += kBL) wf[u] = -1;
+    __threadfence();
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int nw = 0;
+        for (int u = 1; u < len; ++u)
+            if (pb[u] == sep && pb[u - 1] != sep) wf[nw++] = u;
+        if (nw < (int) *wlen) wf[nw] = len;
+    }
+}
+
+// The tail of a one-best confidence kernel (beam_word_conf_bwd of asg_beam_word_conf.hip, beam_word_stream_conf_bwd of
+// asg_beam_word_stream_conf.hip), behind Z and the count nw of the hypothesis' words that get a confidence: the zero fill, the ring,
+// HypSink over the words wd and their frames wf, and the pull.  nq [M] / nb [M] / ring: the dynamic LDS (bwd_front, then kConfRing
+// words).
+template <typename R, typename Lat = WordLat<R>>
+__device__ __forceinline__ void beam_word_conf_words(const Problem &P, const typename Lat::Args &args, char *wb, size_t beta_off, R Z,
+                                                     int len, int nw, int T, int tol, const long long *wd, const long long *wf, R *cf,
+                                                     unsigned long long *ring, unsigned long long *nq, R *nb) {
+    const int tid = threadIdx.x;
+    for (int k = nw + tid; k < T; k += kBL) cf[k] = R(0);
+    if (nw == 0) return;
+    for (int x = tid; x < kConfRing; x += kBL) ring[x] = 0ull;
+    HypSink<R> sink;
+    sink.wd = wd; sink.wf = wf; sink.cf = cf; sink.ring = ring; sink.tol = tol;
+    sink.ka = sink.kb = nw;
+    beam_word_conf_pull<R, HypSink<R>, Lat>(P, args, wb, beta_off, Z, len, -tol - 1, nq, nb, sink);
+}
+
 }  // namespace
 
 }  // namespace asg

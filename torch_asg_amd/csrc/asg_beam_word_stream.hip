@@ -9,18 +9,23 @@
 //   the one-shot decoder's workspace of one utterance with T = max_frames (asg_beam_common.h, beam_word_work_layout): bq / bh / bs
 //     int32 [max_frames][K] (product state, LM state and source slot of every kept pair of every frame consumed so far), the table
 //     tkey u64 [C], arg u64 [C], val key [C], ckey key [cap], cpair u64 [cap], touched int32 [cap];
-//   a 256-byte header: int32 pos (frames consumed), |A| (size of the stored set), overflow;
+//   a 256-byte header: int32 pos (frames consumed), |A| (size of the stored set), overflow, and a word a plain state never reads
+//     (asg_beam_stream_lat.h);
 //   the stored set: values [K] (dtype), then product states int32 [K], then LM states int32 [K].
+// A LATTICE-KEEPING state (asg_beam_word_stream_conf.hip) has this slot at its front and more behind it.  Its search is this
+// unit's: the launchers take the slot's stride, and the advance kernel is a template over a keep policy (asg_beam_stream_lat.h,
+// DESIGN.md 5af) -- KeepNone, empty, for the plain state; KeepLattice, which also writes |A_t| of every frame and the chunk's
+// emissions.
 // Nothing is sized by H, V, A or Q.  Three kernels, each one launch, no host synchronisation, no copy, no memset:
-//   beam_word_stream_reset_kernel    per chosen slot: pos = 0, |A| = 0, overflow = 0, and the whole table emptied (tkey = 0, val = 0,
+//   beam_word_stream_reset_kernel    per chosen slot: the header zeroed, and the whole table emptied (tkey = 0, val = 0,
 //                                    arg = none).  The only place all C slots are written: a frame empties what it touched, so
 //                                    the table is empty between calls.
 //   beam_word_stream_advance_kernel  one 1024-thread workgroup per slot: the transitions and the stored set into LDS,
 //                                    beam_word_frame for the chunk's frames with the back-pointers into rows pos .. pos+n-1, the
 //                                    set and pos back.
-//   beam_word_stream_result_kernel   one workgroup per slot: the best end over the stored set (the end of the one-shot decoder, or
-//                                    the best prefix), the backtrace over pos frames, the words, the token collapse, the padding.
-//                                    It only reads the state.
+//   beam_word_stream_result_kernel   one workgroup per slot: beam_word_stream_hyp (asg_beam_stream_lat.h) -- the best end over the
+//                                    stored set (the end of the one-shot decoder, or the best prefix), the backtrace over pos
+//                                    frames, the words, the token collapse, the padding.  It only reads the state.
 // What one call writes and the next reads crosses a kernel boundary, so plain stores and loads do; the table keeps the
 // device-scope loads and atomics of the frame body.  Integer atomics only: bit-identical run to run.
 //
@@ -32,6 +37,7 @@
 #include "asg_kernels.h"
 #include "asg_beam_common.h"
 #include "asg_beam_word_frame.h"
+#include "asg_beam_stream_lat.h"
 
 namespace asg {
 
@@ -43,13 +49,13 @@ __global__ void __launch_bounds__(256) beam_word_stream_reset_kernel(char *state
     if (mask && !mask[b]) return;
     char *wb = state + (size_t) b * lay.per;
     beam_word_reset_tables(wb, wl, C, key_bytes);
-    if (blockIdx.y == 0 && threadIdx.x < 3) ((int *) (wb + lay.hdr))[threadIdx.x] = 0;      // pos, |A|, overflow
+    if (blockIdx.y == 0 && threadIdx.x < kHdrWords) ((int *) (wb + lay.hdr))[threadIdx.x] = 0;      // pos, |A|, overflow, apos
 }
 
-template <typename R, bool TRL, bool LA = false>
+template <typename R, bool TRL, bool LA, typename Keep>
 __global__ void __launch_bounds__(kBT) beam_word_stream_advance_kernel(Problem P, GraphArgs g, BeamGraphArgs bg, WordLmArgs lm, int K,
                                                                        R theta, int cap, int tbits, int max_frames, char *state,
-                                                                       BeamStreamLayout lay, WordLookParam<LA> la) {
+                                                                       BeamStreamLayout lay, WordLookParam<LA> la, Keep keep) {
     using KT = Key<R>;
     using U = typename KT::U;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -64,13 +70,13 @@ __global__ void __launch_bounds__(kBT) beam_word_stream_advance_kernel(Problem P
     char *wb = state + (size_t) b * lay.per;
     int *hdr = (int *) (wb + lay.hdr);
     R *set_v = (R *) (wb + lay.set);                        // values [K], then product states [K], then LM states [K]
-    int pos = hdr[0];
-    pos = pos < 0 ? 0 : (pos > max_frames ? max_frames : pos);             // (a state that was reset holds 0 .. max_frames)
+    const int pos = stream_pos(hdr, max_frames);
     const int want = clamp_len(P.in_len, b, P.T);
     const int n = want < max_frames - pos ? want : max_frames - pos;
     if (n < want && tid == 0) hdr[2] = 1;                   // frames beyond max_frames are not consumed
     if (n < 1) return;
     const R *in = (const R *) P.inputs + (int64_t) b * P.is1;
+    keep.chunk(wb, in, P, pos, n);
     const R *tr = (const R *) P.transition;
     BeamWordFrame<R, LA> f;
     f.ctl = &ctl; f.wctl = &wctl; f.cur_v = cur_v; f.cur_q = cur_q; f.cur_h = cur_h; f.trs = trs; f.tr = tr;
@@ -80,16 +86,17 @@ __global__ void __launch_bounds__(kBT) beam_word_stream_advance_kernel(Problem P
     int *bq, *bh, *bs;
     f.bind_work(wb, max_frames, bq, bh, bs);
 
-    int na0 = pos >= 1 ? hdr[1] : 0;
-    na0 = na0 < 0 ? 0 : (na0 > K ? K : na0);
-    beam_word_load_set<R, TRL, LA>(f, trs, set_v, na0);
+    beam_word_load_set<R, TRL, LA>(f, trs, set_v, stream_na(hdr, pos, K));
 
-    for (int t = 0; t < n; ++t) {
+    int t = 0;
+    for (; t < n; ++t) {
         const int gt = pos + t;                             // the frame's index in the utterance
         const int na = ctl.na;
         if (gt >= 1 && na == 0) break;                      // an empty beam stays empty (pos still advances)
         beam_word_frame<R, TRL, LA>(f, gt == 0, na, in + (int64_t) t * P.is0, P.is2, bq, bh, bs, gt);
+        keep.frame(wb, gt, ctl.na < K ? ctl.na : K);
     }
+    keep.skipped(wb, pos, t, n);
 
     const int na = beam_word_store_set<R, LA>(f, set_v);
     if (tid == 0) { hdr[1] = na; hdr[0] = pos + n; }
@@ -102,40 +109,12 @@ __global__ void __launch_bounds__(kBT) beam_word_stream_result_kernel(GraphArgs 
                                                                       long long *tlen, long long *states, long long *lm_states,
                                                                       long long *words, long long *wlen, long long *frames,
                                                                       long long *status, WordLookParam<LA> la) {
-    using U = typename Key<R>::U;
     __shared__ WordCtl wctl;
-    const int tid = threadIdx.x, b = blockIdx.x, T = max_frames;
-    const R NINF = Num<R>::ninf();
-    char *wb = const_cast<char *>(state) + (size_t) b * lay.per;            // (only read: bind_work takes the workspace as it is)
-    const int *hdr = (const int *) (wb + lay.hdr);
-    const R *set_v = (const R *) (wb + lay.set);
-    const int *set_q = (const int *) (set_v + K);
-    const int *set_h = set_q + K;
-    long long *pb = path + (int64_t) b * T, *tk = tokens + (int64_t) b * T, *st = states + (int64_t) b * T;
-    long long *ls = lm_states + (int64_t) b * T, *wd = words + (int64_t) b * T;
+    char *wb = const_cast<char *>(state) + (size_t) blockIdx.x * lay.per;   // (only read: bind_work takes the workspace as it is)
     BeamWordFrame<R, LA> f;
-    f.ctl = nullptr; f.wctl = &wctl; f.cur_v = nullptr; f.cur_q = nullptr; f.cur_h = nullptr; f.trs = nullptr; f.tr = nullptr;
-    f.ts0 = 0; f.ts1 = 0; f.N = 0; f.theta = (R) 0;
-    bind_graph<R>(f, g, BeamGraphArgs{}, lm, K, cap, tbits);
-    bind_look<R>(f, la);
-    int *bq, *bh, *bs;
-    f.bind_work(wb, T, bq, bh, bs);
-    int L = hdr[0];
-    L = L < 0 ? 0 : (L > T ? T : L);
-    int na = L >= 1 ? hdr[1] : 0;
-    na = na < 0 ? 0 : (na > K ? K : na);
-    if (tid == 0) { frames[b] = L; status[b] = hdr[2] != 0; }
-    const R *fw = (const R *) g.final_w;
-    U bkey;
-    int bk;
-    word_best_end<R, LA>(f, fw, final != 0, set_h, set_q, set_v, na, bkey, bk);
-    if (bkey == 0) {                                        // no frame yet, an empty set, or no finite end
-        word_no_path(T, pb, tk, st, ls, wd, tlen + b, wlen + b);
-        if (tid == 0) scores[b] = NINF;
-        return;
-    }
-    word_backtrace<R, LA>(f, fw, final != 0, set_h, set_q, set_v, bk, bq, bh, bs, L, T, scores + b, pb, tk, st, ls, wd, tlen + b,
-                      wlen + b);
+    int len;
+    beam_word_stream_hyp<R, LA>(f, wctl, g, lm, la, K, cap, tbits, max_frames, wb, lay, final != 0, scores, path, tokens, tlen,
+                                states, lm_states, words, wlen, frames, status, len);
 }
 
 }  // namespace
@@ -154,9 +133,10 @@ size_t beam_word_stream_state_bytes(int elem, int max_frames, int B, int K, int 
 }
 
 hipError_t launch_beam_word_stream_reset(int elem, const BeamGraphArgs &BG, int K, int max_frames, int B, void *state,
-                                         const unsigned char *mask, hipStream_t stream) {
+                                         const unsigned char *mask, hipStream_t stream, size_t stride) {
     const int cap = beam_word_cap(K, BG.max_out, BG.num_start);
-    const BeamStreamLayout lay = beam_word_stream_layout(elem, max_frames, K, cap);
+    BeamStreamLayout lay = beam_word_stream_layout(elem, max_frames, K, cap);
+    if (stride) lay.per = stride;                                           // (a slot with parts of the caller's behind it)
     const int tbits = word_table_bits(cap);
     const size_t C = (size_t) 1 << tbits;
     hipLaunchKernelGGL(beam_word_stream_reset_kernel, dim3(B, reset_blocks(C)), dim3(256), 0, stream, (char *) state, lay,
@@ -164,36 +144,52 @@ hipError_t launch_beam_word_stream_reset(int elem, const BeamGraphArgs &BG, int 
     return hipGetLastError();
 }
 
-template <typename R>
-hipError_t launch_beam_word_stream_advance(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
-                                           const WordLookArgs *LA, int K, double theta, int max_frames, void *state,
-                                           hipStream_t stream) {
+namespace {
+
+template <typename R, typename Keep>
+hipError_t beam_word_stream_advance(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                                    const WordLookArgs *LA, int K, double theta, int cap, int max_frames, void *state,
+                                    const BeamStreamLayout &lay, Keep keep, hipStream_t stream) {
     const int N = P.N;
-    const int cap = beam_word_cap(K, BG.max_out, BG.num_start);
     const int tbits = word_table_bits(cap);
-    const BeamStreamLayout lay = beam_word_stream_layout(sizeof(R), max_frames, K, cap);
     // the LDS of the one-shot decoder: control block, the set, and the transitions when they fit beside it
     const size_t beam = kFixedLds + (size_t) K * (sizeof(R) + 8);
     const bool trl = beam + (size_t) N * N * sizeof(R) <= kLdsMax;
     const size_t dyn = beam + (trl ? (size_t) N * N * sizeof(R) : 0);
 #define ASG_BEAM_WORD_STREAM(TRL, LAF, LOOK)                                                                                 \
     do {                                                                                                                     \
-        const void *fn = (const void *) beam_word_stream_advance_kernel<R, TRL, LAF>;                                       \
+        const void *fn = (const void *) beam_word_stream_advance_kernel<R, TRL, LAF, Keep>;                                 \
         if (dyn > 64 * 1024) (void) hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) dyn);       \
-        hipLaunchKernelGGL((beam_word_stream_advance_kernel<R, TRL, LAF>), dim3(P.B), dim3(kBT), dyn, stream, P, G, BG, LM, \
-                           K, (R) theta, cap, tbits, max_frames, (char *) state, lay, LOOK);                                 \
+        hipLaunchKernelGGL((beam_word_stream_advance_kernel<R, TRL, LAF, Keep>), dim3(P.B), dim3(kBT), dyn, stream, P, G,  \
+                           BG, LM, K, (R) theta, cap, tbits, max_frames, (char *) state, lay, LOOK, keep);                   \
     } while (0)
     if (LA) { if (trl) ASG_BEAM_WORD_STREAM(true, true, *LA); else ASG_BEAM_WORD_STREAM(false, true, *LA); }
     else if (trl) ASG_BEAM_WORD_STREAM(true, false, WordNoLook{}); else ASG_BEAM_WORD_STREAM(false, false, WordNoLook{});
 #undef ASG_BEAM_WORD_STREAM
     return hipGetLastError();
 }
+
+}  // namespace
+
+template <typename R>
+hipError_t launch_beam_word_stream_advance(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                                           const WordLookArgs *LA, int K, double theta, int max_frames, void *state,
+                                           hipStream_t stream, bool lattice) {
+    const int cap = beam_word_cap(K, BG.max_out, BG.num_start);
+    if (lattice) {
+        const BeamWordConfStreamLayout lay = beam_word_conf_stream_layout(sizeof(R), max_frames, K, cap, P.N);
+        return beam_word_stream_advance<R>(P, G, BG, LM, LA, K, theta, cap, max_frames, state, lay.st,
+                                           KeepLattice{lay.lat.cnt, lay.em}, stream);
+    }
+    return beam_word_stream_advance<R>(P, G, BG, LM, LA, K, theta, cap, max_frames, state,
+                                       beam_word_stream_layout(sizeof(R), max_frames, K, cap), KeepNone{}, stream);
+}
 template hipError_t launch_beam_word_stream_advance<float>(const Problem &, const GraphArgs &, const BeamGraphArgs &,
                                                            const WordLmArgs &, const WordLookArgs *, int, double, int, void *,
-                                                           hipStream_t);
+                                                           hipStream_t, bool);
 template hipError_t launch_beam_word_stream_advance<double>(const Problem &, const GraphArgs &, const BeamGraphArgs &,
                                                             const WordLmArgs &, const WordLookArgs *, int, double, int, void *,
-                                                            hipStream_t);
+                                                            hipStream_t, bool);
 
 template <typename R>
 hipError_t launch_beam_word_stream_result(const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,

@@ -217,19 +217,21 @@ hipError_t launch_beam_words(const Problem &P, const GraphArgs &G, const BeamGra
 
 // ---- The same search carried across chunks of frames (asg_beam_stream.hip): asg_beam_stream_*.  One slot of the state (byte
 // offsets, each part 256-byte aligned): the beam search's own layout for T = max_frames at the front, then hdr (int32 pos, |A|,
-// overflow) and the stored set (values [K], then int32 product states [K]).
+// overflow, apos -- the last is the lattice-keeping state's, asg_beam_stream_lat.h) and the stored set (values [K], then int32
+// product states [K]).
 struct BeamStreamLayout {
     size_t hdr, set, per;
 };
 BeamStreamLayout beam_stream_layout(int elem, int max_frames, int Q, int K, int cap);
 size_t beam_stream_state_bytes(int elem, int max_frames, int B, int Q, int K, int cap);
-// mask: one byte per slot (null: every slot)
+// mask: one byte per slot (null: every slot); stride as launch_beam_stream_result's
 hipError_t launch_beam_stream_reset(int elem, const GraphArgs &G, const BeamGraphArgs &BG, int K, int max_frames, int B, void *state,
-                                    const unsigned char *mask, hipStream_t stream);
-// P.T frames of P.inputs per slot at the most (P.in_len: the chunk's lengths)
+                                    const unsigned char *mask, hipStream_t stream, size_t stride = 0);
+// P.T frames of P.inputs per slot at the most (P.in_len: the chunk's lengths).  lattice: the state is a lattice-keeping one
+// (beam_conf_stream_layout below) -- the same kernel with the policy that also keeps cnt and the emissions (asg_beam_stream_lat.h).
 template <typename R>
 hipError_t launch_beam_stream_advance(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, int K, double theta,
-                                      int max_frames, void *state, hipStream_t stream);
+                                      int max_frames, void *state, hipStream_t stream, bool lattice = false);
 template <typename R>
 hipError_t launch_beam_stream_result(const GraphArgs &G, const BeamGraphArgs &BG, int K, int max_frames, int B, const void *state,
                                      int final, void *scores, long long *path, long long *tokens, long long *tlen,
@@ -258,12 +260,13 @@ hipError_t launch_beam_words_la(const Problem &P, const GraphArgs &G, const Beam
 // look-ahead of asg_beam_word_stream_*_la, nullptr without one (the state, its size and its reset do not depend on it).
 BeamStreamLayout beam_word_stream_layout(int elem, int max_frames, int K, int cap);
 size_t beam_word_stream_state_bytes(int elem, int max_frames, int B, int K, int cap);
+// stride / lattice: as launch_beam_stream_reset's and launch_beam_stream_advance's (beam_word_conf_stream_layout below)
 hipError_t launch_beam_word_stream_reset(int elem, const BeamGraphArgs &BG, int K, int max_frames, int B, void *state,
-                                         const unsigned char *mask, hipStream_t stream);
+                                         const unsigned char *mask, hipStream_t stream, size_t stride = 0);
 template <typename R>
 hipError_t launch_beam_word_stream_advance(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
                                            const WordLookArgs *LA, int K, double theta, int max_frames, void *state,
-                                           hipStream_t stream);
+                                           hipStream_t stream, bool lattice = false);
 template <typename R>
 hipError_t launch_beam_word_stream_result(const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
                                           const WordLookArgs *LA, int K, int max_frames, int B, const void *state, int final,
@@ -509,11 +512,7 @@ struct BeamConfStreamLayout {
 };
 BeamConfStreamLayout beam_conf_stream_layout(int elem, int max_frames, int Q, int K, int cap, int N);
 size_t beam_conf_stream_state_bytes(int elem, int max_frames, int B, int Q, int K, int cap, int N);
-hipError_t launch_beam_conf_stream_reset(int elem, const GraphArgs &G, const BeamGraphArgs &BG, int K, int max_frames, int B, int N,
-                                         void *state, const unsigned char *mask, hipStream_t stream);
-template <typename R>
-hipError_t launch_beam_conf_stream_advance(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, int K, double theta,
-                                           int max_frames, void *state, hipStream_t stream);
+// (reset, advance, result and n-best are the plain stream's launchers with this layout's stride / lattice = true)
 // P: B, N and the transition (its emissions and lengths are not read: the state has both).  Two launches: the catch-up of U / nu /
 // A from apos to pos (the only write to the state from a result path), then the hypothesis, Z and the beta pull.
 template <typename R>
@@ -620,12 +619,7 @@ struct BeamWordConfStreamLayout {
 };
 BeamWordConfStreamLayout beam_word_conf_stream_layout(int elem, int max_frames, int K, int cap, int N);
 size_t beam_word_conf_stream_state_bytes(int elem, int max_frames, int B, int K, int cap, int N);
-hipError_t launch_beam_word_conf_stream_reset(int elem, const BeamGraphArgs &BG, int K, int max_frames, int B, int N, void *state,
-                                              const unsigned char *mask, hipStream_t stream);
-template <typename R>
-hipError_t launch_beam_word_conf_stream_advance(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
-                                                const WordLookArgs *LA, int K, double theta, int max_frames, void *state,
-                                                hipStream_t stream);
+// (reset, advance, result and n-best are the plain word stream's launchers with this layout's stride / lattice = true)
 // P: B, N and the transition (its emissions and lengths are not read: the state has both).  Two launches: the catch-up of U / nu /
 // A from apos to pos (the only write to the state from a result path), then the hypothesis, Z and the beta pull.
 template <typename R>
