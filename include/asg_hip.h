@@ -1445,6 +1445,97 @@ int asg_beam_conf_stream_confidence(asg_ctx *ctx, const asg_token_graph_beam_los
                                     int64_t *token_lengths, int64_t *states, int64_t *token_frames, void *token_confidences,
                                     void *normalisers, int64_t *frames, int64_t *status, int flags, void *stream);
 
+/* ---- the LATTICE-KEEPING window stream: asg_beam_window_* with a state that also keeps, in a ring, what
+ * asg_beam_graph_confidence computes its token confidences from, so that a stream WITHOUT A BOUND on its frames gives a confidence
+ * and a start frame for every token at the moment it commits it (additions only; asg_beam_window_* and its state formula are
+ * unchanged).  The family takes the asg_token_graph_beam_loss view, as asg_beam_conf_stream_* does, in asg_beam_window_*'s
+ * argument order with two more parameters of the state behind W and P: frame_tolerance (tol, 0 .. 64) and max_chunk (C >= 1, the
+ * longest chunk an _advance may bring).  The state is sized by them and every call passes the same four values.
+ *
+ * DEFINITION.  The window never touches the search, so the kept sets A_0 .. A_{pos-1} are those of asg_beam_conf_stream_* fed the
+ * same frames, and the lattice is its lattice: those sets with the edges and weights of asg_beam_graph_confidence.  A confidence
+ * belongs to a (frame, label) cell.  Take a commit attempt behind frame p1 - 1 (pos, counting the frame, is p1, and p1 mod P == 0).
+ * For a token that attempt commits, with label i and a run that starts at frame f:
+ *   new_token_frames      = f, the absolute frame at which the carried collapse kept the label (a first committed label that
+ *                           differs from `carry` starts at the old base);
+ *   new_token_confidences = the prefix-mode posterior of asg_beam_conf_stream_confidence over A_0 .. A_{p1-1}: a path ends in any
+ *                           state of A_{p1-1} with end weight 0, Z is the log-sum-exp of alpha over A_{p1-1}, and the value sums
+ *                           the event "a token with label i starts at frame t" over t in [f - tol, f + tol] clipped to [0, p1-1].
+ * It is what a listener knows at the moment the token becomes final.  A forced commit of the same attempt uses the same p1: one
+ * attempt is one lattice end.  No finite Z at the attempt: confidence 0, the frame still written; never a NaN.
+ *   - The five outputs of asg_beam_window_advance, and _result, _nbest and _reset, are the plain family's byte for byte.
+ *   - The concatenation of all new_token_frames / new_token_confidences is the same bits for every chunking (attempts, and so
+ *     lattice ends, happen at frame indices).
+ *   - While status bit 0 is clear, the tokens an attempt at p1 commits carry, at the same token indices, the token_frames and
+ *     token_confidences of asg_beam_conf_stream_confidence(final = 0, tol) of a growing stream that stands at pos = p1, bit for
+ *     bit: the alpha text is the same, resumed from stored rows; the sets are the same ascending lists; Z is the same; the beta
+ *     recursion is the same from frame p1 - 1 downwards, and the integer accumulators do not depend on the order of the adds.
+ *   - With status bit 0 set the values are still the cell posteriors defined above.
+ *
+ * STATE.  With a256(x) = x rounded up to 256, e = 4 or 8 (the dtype), K = min(beam_size, Q), N = gl->beam->graph->N,
+ *     RW = W + tol + 1 + C   (rows of the lattice ring; frame t lives in row t mod RW, computed in 64 bits),
+ *     L  = C / P + 1         (entries of the attempt log, integer division),
+ * one slot is
+ *     per = PW + a256(4 RW) + a256(e RW N) + a256(4 RW) + a256(4 RW K) + a256(e RW K) + a256(24 L) + L a256(2 e K),
+ * where PW = asg_beam_window_state_bytes(gl->beam, 1, dtype, beam_size, W, P) is the plain window's slot, unchanged, at the front,
+ * and behind it: cnt int32 [RW], the emissions [RW][N], nu int32 [RW], U int32 [RW][K] (A_t, ascending once caught up), A [RW][K]
+ * (alpha), the attempt log (int64 p1, int64 base before the attempt, int32 first and one-past-last token of the call's output
+ * row), beta [L][2][K].  The slot's 256-byte header block holds, at byte 64, int64 apos (the frames whose U / nu / A rows are
+ * valid, pos - C <= apos <= pos) and int32 the number of attempts the last _advance logged.  asg_beam_conf_window_state_bytes =
+ * B * per.  The ring is large enough: an attempt at p1 with old base b0 reads the frames b0 - tol - 1 .. p1 - 1, p1 - b0 <= W, and
+ * the call has written at most C frames behind p1.
+ *
+ * _advance: THREE launches, no host synchronisation, no memset, no copy; it captures and replays.
+ *   (a) the search: asg_beam_window_advance's kernel, which also copies the chunk's emissions, |A_t| and the kept states of every
+ *       frame into the ring, writes new_token_frames, and logs every attempt that committed a token;
+ *   (b) the catch-up over [apos, pos): the rows' states sorted, alpha by asg_beam_graph_full_forward's pull, resumed from row
+ *       apos - 1 (or the start weights); apos = pos;
+ *   (c) the pull, one workgroup per (slot, logged attempt): Z over row p1 - 1, beta from frame p1 - 1 down to max(b0 - tol, 0),
+ *       with the frame-0 term when it gets there; the attempt's tokens are its sink.
+ *   outputs: asg_beam_window_advance's five, then new_token_frames int64 [B][W + Tc] (-1 behind the data) and
+ *   new_token_confidences [B][W + Tc] in the dtype (0 behind the data).  Every element is written, also for Tc = 0.
+ *   Tc > max_chunk is ASG_ERR_UNSUPPORTED.  p->transition MUST NOT CHANGE within an utterance.
+ * _reset, _result, _nbest, _nbest_work_bytes: asg_beam_window_*'s over the wider slot (a reset needs nothing more: the next
+ *   _advance finds pos = 0 and takes apos back to it).
+ * _confidence(final): TWO launches; it only reads the state (beta rows apart).  _result(final)'s eight outputs, and for the
+ *   tokens of the uncommitted tail token_frames int64 [B][W] (absolute, -1 behind the data), token_confidences [B][W] (0 behind
+ *   the data) and normalisers [B]: one pull from frame pos - 1 down to base - tol with the state's tolerance, end weight 0
+ *   (final = 0) or the final weights (final = 1).  With final = 1 and status bit 0 clear the tail's values are
+ *   asg_beam_graph_confidence's for those tokens on the frames consumed, bit for bit, and the start frames of all _advance calls
+ *   followed by the tail's are its token_frames.  The catch-up was done by _advance.
+ * Limits: asg_beam_window_*'s and asg_beam_graph_confidence's (for T = W); frame_tolerance < 0 or max_chunk < 1 is
+ * ASG_ERR_INVALID, frame_tolerance > 64 ASG_ERR_UNSUPPORTED; L = max_chunk / P + 1 > 65535 (the pull runs one workgroup per slot
+ * and log entry) ASG_ERR_UNSUPPORTED, from every call of the family; a state that is too small ASG_ERR_WORKSPACE.  float32 and
+ * float64.  alpha and Z grow with pos, as the search's own scores do: in float32 a posterior loses resolution as |Z| passes about 1e5, so
+ * streams of hours want float64 (a rebased alpha is not there). */
+size_t asg_beam_conf_window_state_bytes(const asg_token_graph_beam_loss *gl, int64_t B, int dtype, int beam_size, int64_t W,
+                                        int64_t P, int frame_tolerance, int64_t max_chunk);
+int asg_beam_conf_window_reset(asg_ctx *ctx, const asg_token_graph_beam_loss *gl, int64_t B, int beam_size, int64_t W, int64_t P,
+                               int frame_tolerance, int64_t max_chunk, void *state, size_t state_bytes, const uint8_t *mask,
+                               int flags, void *stream);
+int asg_beam_conf_window_advance(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam_loss *gl, int beam_size,
+                                 double beam_threshold, int64_t W, int64_t P, int frame_tolerance, int64_t max_chunk, void *state,
+                                 size_t state_bytes, int64_t *new_path, int64_t *new_states, int64_t *new_tokens,
+                                 int64_t *new_frames, int64_t *new_token_lengths, int64_t *new_token_frames,
+                                 void *new_token_confidences, int flags, void *stream);
+int asg_beam_conf_window_result(asg_ctx *ctx, const asg_token_graph_beam_loss *gl, int64_t B, int beam_size, int64_t W, int64_t P,
+                                int frame_tolerance, int64_t max_chunk, const void *state, size_t state_bytes, int final,
+                                void *scores, int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states,
+                                int64_t *frames, int64_t *committed, int64_t *status, int flags, void *stream);
+size_t asg_beam_conf_window_nbest_work_bytes(const asg_token_graph_beam_loss *gl, int64_t B, int dtype, int beam_size, int64_t W,
+                                             int64_t P, int frame_tolerance, int64_t max_chunk, int nbest);
+int asg_beam_conf_window_nbest(asg_ctx *ctx, const asg_token_graph_beam_loss *gl, int64_t B, int beam_size, int64_t W, int64_t P,
+                               int frame_tolerance, int64_t max_chunk, const void *state, size_t state_bytes, int final, int nbest,
+                               void *work, size_t work_bytes, void *scores, int64_t *path, int64_t *tokens,
+                               int64_t *token_lengths, int64_t *states, int64_t *num_hyps, int64_t *frames, int64_t *committed,
+                               int64_t *status, int flags, void *stream);
+int asg_beam_conf_window_confidence(asg_ctx *ctx, const asg_token_graph_beam_loss *gl, int64_t B, int beam_size, int64_t W,
+                                    int64_t P, int frame_tolerance, int64_t max_chunk, void *state, size_t state_bytes,
+                                    const void *transition, const int64_t *transition_strides, int final, void *scores,
+                                    int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *token_frames,
+                                    void *token_confidences, void *normalisers, int64_t *frames, int64_t *committed,
+                                    int64_t *status, int flags, void *stream);
+
 /* ---- the LATTICE-KEEPING word-LM beam stream: asg_beam_word_stream_* with a state that also keeps what asg_beam_words_confidence
  * computes its word confidences from, so that a stream over a lexicon and a word n-gram LM gives a confidence and an end frame per
  * word while the utterance is arriving (additions only; asg_beam_word_stream_* and its state formula are unchanged).  The family

@@ -8,6 +8,7 @@ from .asg import BeamStream, BeamStreamResult  # noqa: F401
 from .asg import BeamWindowStream, BeamWindowCommit, BeamWindowResult  # noqa: F401
 from .asg import BeamStreamNbest, BeamWindowNbest  # noqa: F401
 from .asg import BeamStreamConfidence, BeamWordStreamConfidence  # noqa: F401
+from .asg import BeamWindowConfCommit, BeamWindowConfidence  # noqa: F401
 from .asg import BeamWords, beam_decode_words  # noqa: F401
 from .asg import BeamWordsConfidence, beam_decode_words_confidence  # noqa: F401
 from .asg import BeamGraphConfidence, beam_decode_graph_confidence  # noqa: F401
@@ -52,5 +53,6 @@ __all__ = ["ASGLoss", "ASGLossFunction", "FAC", "FCC", "ASGGPUFast", "ASGGPUFast
            "BeamGraphFullScore", "beam_graph_full_score", "beam_graph_asg_loss", "BeamNbest", "beam_decode_graph_nbest",
            "BeamStream", "BeamStreamResult", "BeamWindowStream", "BeamWindowCommit", "BeamWindowResult",
            "BeamStreamNbest", "BeamWindowNbest", "BeamStreamConfidence", "BeamWordStreamConfidence",
+           "BeamWindowConfCommit", "BeamWindowConfidence",
            "BeamWords", "beam_decode_words", "BeamWordsConfidence", "beam_decode_words_confidence", "BeamGraphConfidence", "beam_decode_graph_confidence", "BeamNbestConfidence", "beam_decode_graph_nbest_confidence", "BeamWordStream", "BeamWordStreamResult", "BeamWordsNbest", "beam_decode_words_nbest", "BeamWordStreamNbest", "BeamWordsNbestConfidence", "beam_decode_words_nbest_confidence", "BeamWordWindowStream", "BeamWordWindowCommit", "BeamWordWindowResult", "BeamWordWindowNbest", "BeamWordsFullScore", "beam_words_full_score",
            "beam_words_asg_loss", "Lexicon", "WordLM", "WordLookahead", "shard_batch", "sharded_asg_loss", "allreduce_transition_grad", "reserve", "release", "check_faults", "graphed", "GraphedStep"]

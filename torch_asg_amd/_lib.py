@@ -48,6 +48,9 @@ SYMBOLS = ["asg_hip_version", "asg_hip_strerror", "asg_ctx_create", "asg_ctx_des
            "asg_beam_conf_stream_state_bytes", "asg_beam_conf_stream_reset", "asg_beam_conf_stream_advance",
            "asg_beam_conf_stream_result", "asg_beam_conf_stream_nbest_work_bytes", "asg_beam_conf_stream_nbest",
            "asg_beam_conf_stream_confidence",
+           "asg_beam_conf_window_state_bytes", "asg_beam_conf_window_reset", "asg_beam_conf_window_advance",
+           "asg_beam_conf_window_result", "asg_beam_conf_window_nbest_work_bytes", "asg_beam_conf_window_nbest",
+           "asg_beam_conf_window_confidence",
            "asg_beam_word_conf_stream_state_bytes", "asg_beam_word_conf_stream_reset", "asg_beam_word_conf_stream_advance",
            "asg_beam_word_conf_stream_advance_la", "asg_beam_word_conf_stream_result", "asg_beam_word_conf_stream_result_la",
            "asg_beam_word_conf_stream_nbest_work_bytes", "asg_beam_word_conf_stream_nbest", "asg_beam_word_conf_stream_nbest_la",
@@ -239,6 +242,17 @@ def lib():
     L.asg_beam_conf_stream_nbest_work_bytes.argtypes = [blp, i64, ci, ci, i64, ci]
     L.asg_beam_conf_stream_nbest.argtypes = [vp, blp, i64, ci, i64, vp, sz, ci, ci, vp, sz] + [vp] * 9 + [ci, vp]
     L.asg_beam_conf_stream_confidence.argtypes = [vp, blp, i64, ci, i64, vp, sz, vp, ctypes.POINTER(i64), ci, ci] + [vp] * 10 + [ci, vp]
+    shape = [i64, i64, ci, i64]                                                    # W, P, frame_tolerance, max_chunk
+    L.asg_beam_conf_window_state_bytes.restype = sz
+    L.asg_beam_conf_window_state_bytes.argtypes = [blp, i64, ci, ci] + shape
+    L.asg_beam_conf_window_reset.argtypes = [vp, blp, i64, ci] + shape + [vp, sz, vp, ci, vp]
+    L.asg_beam_conf_window_advance.argtypes = [vp, pp, blp, ci, ctypes.c_double] + shape + [vp, sz] + [vp] * 7 + [ci, vp]
+    L.asg_beam_conf_window_result.argtypes = [vp, blp, i64, ci] + shape + [vp, sz, ci] + [vp] * 8 + [ci, vp]
+    L.asg_beam_conf_window_nbest_work_bytes.restype = sz
+    L.asg_beam_conf_window_nbest_work_bytes.argtypes = [blp, i64, ci, ci] + shape + [ci]
+    L.asg_beam_conf_window_nbest.argtypes = [vp, blp, i64, ci] + shape + [vp, sz, ci, ci, vp, sz] + [vp] * 9 + [ci, vp]
+    L.asg_beam_conf_window_confidence.argtypes = ([vp, blp, i64, ci] + shape + [vp, sz, vp, ctypes.POINTER(i64), ci] + [vp] * 11 +
+                                                  [ci, vp])
     L.asg_beam_graph_nbest_confidence_work_bytes.restype = sz
     L.asg_beam_graph_nbest_confidence_work_bytes.argtypes = [pp, blp, ci, ci]
     L.asg_beam_graph_nbest_confidence.argtypes = [vp, pp, blp, ci, ctypes.c_double, ci, ci, vp, sz] + [vp] * 11 + [ci, vp]

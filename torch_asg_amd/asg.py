@@ -2153,11 +2153,12 @@ class ASGLoss(nn.Module):
                               word_score, token_score, self.transition.dtype, self.transition.device, lookahead, keep_lattice)
 
     def beam_window_stream(self, graph, batch_size, window, commit_every=None, beam_size=256, beam_threshold=float("inf"),
-                           lm_weight=1.0, token_score=0.0):
+                           lm_weight=1.0, token_score=0.0, keep_lattice=False, frame_tolerance=0, max_chunk=None):
         """A streaming beam decoder in bounded memory under this module's transition matrix (read again at every chunk): see
-        `torch_asg_amd.BeamWindowStream`."""
+        `torch_asg_amd.BeamWindowStream`.  `keep_lattice=True`: `advance` also returns a confidence and a start frame for every
+        token it commits, and the stream has `result_confidence`."""
         return BeamWindowStream(self.transition, graph, batch_size, window, commit_every, beam_size, beam_threshold, lm_weight,
-                                token_score, self.transition.dtype, self.transition.device)
+                                token_score, self.transition.dtype, self.transition.device, keep_lattice, frame_tolerance, max_chunk)
 
     def beam_word_window_stream(self, lexicon, word_lm, batch_size, window, commit_every=None, beam_size=256,
                                 beam_threshold=float("inf"), lm_weight=1.0, word_score=0.0, token_score=0.0, lookahead=None):
@@ -2323,4 +2324,4 @@ class ASGLoss(nn.Module):
 from .stream import (BeamStream, BeamStreamResult, BeamWordStream, BeamWordStreamResult, BeamWordStreamNbest,  # noqa: E402,F401
                      BeamWindowStream, BeamWindowCommit, BeamWindowResult, BeamWordWindowStream, BeamWordWindowCommit,
                      BeamWordWindowResult, BeamStreamNbest, BeamWindowNbest, BeamWordWindowNbest, BeamStreamConfidence,
-                     BeamWordStreamConfidence)
+                     BeamWordStreamConfidence, BeamWindowConfCommit, BeamWindowConfidence)

@@ -1795,6 +1795,188 @@ int asg_beam_conf_stream_confidence(asg_ctx *ctx, const asg_token_graph_beam_los
                                                    tf, token_confidences, normalisers, fr, su, (hipStream_t) stream)));
 }
 
+// The lattice-keeping window stream: the checks of a plain window state through the beam view, the two parameters that size the
+// ring, then those of the token confidences through a problem of W frames without targets (its emissions are not read).
+static int check_beam_conf_window(const asg_token_graph_beam_loss *gl, int64_t B, int dtype, int beam_size, int64_t W, int64_t P,
+                                  int frame_tolerance, int64_t max_chunk) {
+    if (!gl) return ASG_ERR_INVALID;
+    int rc = check_beam_window(gl->beam, B, dtype, beam_size, W, P);
+    if (rc) return rc;
+    if (frame_tolerance < 0 || max_chunk < 1) return ASG_ERR_INVALID;
+    if (frame_tolerance > kBeamConfMaxTol) return ASG_ERR_UNSUPPORTED;
+    if (W + frame_tolerance + 1 + max_chunk > (int64_t) 0x7FFFFFFF) return ASG_ERR_UNSUPPORTED;      // the rows of the ring
+    if (max_chunk / P + 1 > kBeamConfWindowMaxLog) return ASG_ERR_UNSUPPORTED;      // the log's entries are the pull's grid rows
+    asg_problem q{};
+    q.inputs = gl; q.transition = gl;
+    q.T = W; q.B = B; q.N = gl->beam->graph->N; q.S = 1; q.dtype = dtype;
+    return check_beam_loss(&q, gl, beam_size);
+}
+
+static size_t beam_conf_window_bytes(const asg_token_graph_beam_loss *gl, int64_t B, int dtype, int beam_size, int64_t W, int64_t P,
+                                     int frame_tolerance, int64_t max_chunk) {
+    const asg_token_graph_beam *gb = gl->beam;
+    const int Q = (int) gb->graph->Q, K = beam_graph_k(Q, beam_size);
+    return beam_conf_window_state_bytes(dtype == ASG_DTYPE_F64 ? 8 : 4, (int) W, (int) P, frame_tolerance, (int) max_chunk, (int) B, Q,
+                                        K, beam_graph_cap(Q, K, gb->max_out, (int) gb->num_start), (int) gb->graph->N);
+}
+
+size_t asg_beam_conf_window_state_bytes(const asg_token_graph_beam_loss *gl, int64_t B, int dtype, int beam_size, int64_t W,
+                                        int64_t P, int frame_tolerance, int64_t max_chunk) {
+    if (check_beam_conf_window(gl, B, dtype, beam_size, W, P, frame_tolerance, max_chunk) != ASG_OK) return 0;
+    return beam_conf_window_bytes(gl, B, dtype, beam_size, W, P, frame_tolerance, max_chunk);
+}
+
+// reset, result and n-best: the plain window's kernels over the wider slot
+int asg_beam_conf_window_reset(asg_ctx *ctx, const asg_token_graph_beam_loss *gl, int64_t B, int beam_size, int64_t W, int64_t P,
+                               int frame_tolerance, int64_t max_chunk, void *state, size_t state_bytes, const uint8_t *mask,
+                               int flags, void *stream) {
+    (void) ctx; (void) flags;
+    if (!gl || !gl->beam || !gl->beam->graph) return ASG_ERR_INVALID;
+    const asg_token_graph_beam *gb = gl->beam;
+    const int dtype = gb->graph->dtype;
+    int rc = check_beam_conf_window(gl, B, dtype, beam_size, W, P, frame_tolerance, max_chunk);
+    if (rc) return rc;
+    if (!state) return ASG_ERR_INVALID;
+    if (state_bytes < beam_conf_window_bytes(gl, B, dtype, beam_size, W, P, frame_tolerance, max_chunk)) return ASG_ERR_WORKSPACE;
+    const GraphArgs G = to_graph_args(gb->graph);
+    return hip_status(launch_beam_window_reset(dtype == ASG_DTYPE_F64 ? 8 : 4, G, to_beam_graph_args(gb),
+                                               beam_graph_k(G.Q, beam_size), (int) W, (int) B, state, mask, (hipStream_t) stream,
+                                               beam_conf_window_bytes(gl, 1, dtype, beam_size, W, P, frame_tolerance, max_chunk)));
+}
+
+int asg_beam_conf_window_advance(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam_loss *gl, int beam_size,
+                                 double beam_threshold, int64_t W, int64_t P, int frame_tolerance, int64_t max_chunk, void *state,
+                                 size_t state_bytes, int64_t *new_path, int64_t *new_states, int64_t *new_tokens,
+                                 int64_t *new_frames, int64_t *new_token_lengths, int64_t *new_token_frames,
+                                 void *new_token_confidences, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    if (!p || !gl || !gl->beam || !gl->beam->graph) return ASG_ERR_INVALID;
+    const asg_token_graph_beam *gb = gl->beam;
+    int rc = check_beam_conf_window(gl, p->B, p->dtype, beam_size, W, P, frame_tolerance, max_chunk);
+    if (rc) return rc;
+    if (p->T < 0 || p->N != gb->graph->N) return ASG_ERR_INVALID;
+    if (p->T > max_chunk) return ASG_ERR_UNSUPPORTED;                      // the ring holds max_chunk frames behind an attempt
+    if (p->T > 0 && (rc = check_beam_graph(p, gb, beam_size)) != ASG_OK) return rc;
+    if (!p->transition) return ASG_ERR_INVALID;                            // (the catch-up reads it also when no frame comes)
+    if (!(beam_threshold >= 0.0)) return ASG_ERR_INVALID;                  // negative or NaN
+    if (!state || !new_path || !new_states || !new_tokens || !new_frames || !new_token_lengths || !new_token_frames ||
+        !new_token_confidences)
+        return ASG_ERR_INVALID;
+    if (state_bytes < beam_conf_window_bytes(gl, p->B, p->dtype, beam_size, W, P, frame_tolerance, max_chunk))
+        return ASG_ERR_WORKSPACE;
+    const Problem Pr = to_problem(p);                                      // (no frame: the launches still write the empty outputs)
+    const GraphArgs G = to_graph_args(gb->graph);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    const int K = beam_graph_k(G.Q, beam_size);
+    long long *np = (long long *) new_path, *ns = (long long *) new_states, *nt = (long long *) new_tokens;
+    long long *nf = (long long *) new_frames, *nl = (long long *) new_token_lengths, *tf = (long long *) new_token_frames;
+    return hip_status(ASG_DISPATCH(p,
+        launch_beam_conf_window_advance<float>(Pr, G, BG, K, beam_threshold, (int) W, (int) P, frame_tolerance, (int) max_chunk, state,
+                                               np, ns, nt, nf, nl, tf, new_token_confidences, (hipStream_t) stream),
+        launch_beam_conf_window_advance<double>(Pr, G, BG, K, beam_threshold, (int) W, (int) P, frame_tolerance, (int) max_chunk,
+                                                state, np, ns, nt, nf, nl, tf, new_token_confidences, (hipStream_t) stream)));
+}
+
+int asg_beam_conf_window_result(asg_ctx *ctx, const asg_token_graph_beam_loss *gl, int64_t B, int beam_size, int64_t W, int64_t P,
+                                int frame_tolerance, int64_t max_chunk, const void *state, size_t state_bytes, int final,
+                                void *scores, int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states,
+                                int64_t *frames, int64_t *committed, int64_t *status, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    if (!gl || !gl->beam || !gl->beam->graph) return ASG_ERR_INVALID;
+    const asg_token_graph_beam *gb = gl->beam;
+    const asg_token_graph *g = gb->graph;
+    int rc = check_beam_conf_window(gl, B, g->dtype, beam_size, W, P, frame_tolerance, max_chunk);
+    if (rc) return rc;
+    if (!state || !scores || !path || !tokens || !token_lengths || !states || !frames || !committed || !status)
+        return ASG_ERR_INVALID;
+    if (state_bytes < beam_conf_window_bytes(gl, B, g->dtype, beam_size, W, P, frame_tolerance, max_chunk)) return ASG_ERR_WORKSPACE;
+    const GraphArgs G = to_graph_args(g);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    const int K = beam_graph_k(G.Q, beam_size);
+    const size_t per = beam_conf_window_bytes(gl, 1, g->dtype, beam_size, W, P, frame_tolerance, max_chunk);
+    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
+    long long *fr = (long long *) frames, *co = (long long *) committed, *su = (long long *) status;
+    return hip_status(ASG_DISPATCH(g, launch_beam_window_result<float>(G, BG, K, (int) W, (int) B, state, final, scores, pa, tk, tl,
+                                                                       st, fr, co, su, (hipStream_t) stream, per),
+                                   launch_beam_window_result<double>(G, BG, K, (int) W, (int) B, state, final, scores, pa, tk, tl,
+                                                                     st, fr, co, su, (hipStream_t) stream, per)));
+}
+
+static int check_beam_conf_window_nbest(const asg_token_graph_beam_loss *gl, int64_t B, int dtype, int beam_size, int64_t W,
+                                        int64_t P, int frame_tolerance, int64_t max_chunk, int nbest) {
+    int rc = check_beam_conf_window(gl, B, dtype, beam_size, W, P, frame_tolerance, max_chunk);
+    if (rc) return rc;
+    if (nbest < 1) return ASG_ERR_INVALID;
+    if (nbest > kBeamMaxNbest) return ASG_ERR_UNSUPPORTED;
+    return ASG_OK;
+}
+
+size_t asg_beam_conf_window_nbest_work_bytes(const asg_token_graph_beam_loss *gl, int64_t B, int dtype, int beam_size, int64_t W,
+                                             int64_t P, int frame_tolerance, int64_t max_chunk, int nbest) {
+    if (check_beam_conf_window_nbest(gl, B, dtype, beam_size, W, P, frame_tolerance, max_chunk, nbest) != ASG_OK) return 0;
+    return beam_stream_nbest_bytes(gl->beam, B, beam_size, W, nbest);
+}
+
+int asg_beam_conf_window_nbest(asg_ctx *ctx, const asg_token_graph_beam_loss *gl, int64_t B, int beam_size, int64_t W, int64_t P,
+                               int frame_tolerance, int64_t max_chunk, const void *state, size_t state_bytes, int final, int nbest,
+                               void *work, size_t work_bytes, void *scores, int64_t *path, int64_t *tokens,
+                               int64_t *token_lengths, int64_t *states, int64_t *num_hyps, int64_t *frames, int64_t *committed,
+                               int64_t *status, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    if (!gl || !gl->beam || !gl->beam->graph) return ASG_ERR_INVALID;
+    const asg_token_graph_beam *gb = gl->beam;
+    const asg_token_graph *g = gb->graph;
+    int rc = check_beam_conf_window_nbest(gl, B, g->dtype, beam_size, W, P, frame_tolerance, max_chunk, nbest);
+    if (rc) return rc;
+    if (!state || !work || !scores || !tokens || !token_lengths || !num_hyps || !frames || !committed || !status)
+        return ASG_ERR_INVALID;
+    if (state_bytes < beam_conf_window_bytes(gl, B, g->dtype, beam_size, W, P, frame_tolerance, max_chunk)) return ASG_ERR_WORKSPACE;
+    if (work_bytes < beam_stream_nbest_bytes(gb, B, beam_size, W, nbest)) return ASG_ERR_WORKSPACE;
+    const GraphArgs G = to_graph_args(g);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    const int K = beam_graph_k(G.Q, beam_size);
+    const size_t per = beam_conf_window_bytes(gl, 1, g->dtype, beam_size, W, P, frame_tolerance, max_chunk);
+    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
+    long long *nh = (long long *) num_hyps, *fr = (long long *) frames, *co = (long long *) committed, *su = (long long *) status;
+    return hip_status(ASG_DISPATCH(g, launch_beam_window_nbest<float>(G, BG, K, (int) W, (int) B, state, final, nbest, work, scores,
+                                                                      pa, tk, tl, st, nh, fr, co, su, (hipStream_t) stream, per),
+                                   launch_beam_window_nbest<double>(G, BG, K, (int) W, (int) B, state, final, nbest, work, scores,
+                                                                    pa, tk, tl, st, nh, fr, co, su, (hipStream_t) stream, per)));
+}
+
+int asg_beam_conf_window_confidence(asg_ctx *ctx, const asg_token_graph_beam_loss *gl, int64_t B, int beam_size, int64_t W,
+                                    int64_t P, int frame_tolerance, int64_t max_chunk, void *state, size_t state_bytes,
+                                    const void *transition, const int64_t *transition_strides, int final, void *scores,
+                                    int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *token_frames,
+                                    void *token_confidences, void *normalisers, int64_t *frames, int64_t *committed,
+                                    int64_t *status, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    if (!gl || !gl->beam || !gl->beam->graph) return ASG_ERR_INVALID;
+    const asg_token_graph_beam *gb = gl->beam;
+    const asg_token_graph *g = gb->graph;
+    int rc = check_beam_conf_window(gl, B, g->dtype, beam_size, W, P, frame_tolerance, max_chunk);
+    if (rc) return rc;
+    if (!state || !transition || !transition_strides || !scores || !path || !tokens || !token_lengths || !states || !token_frames ||
+        !token_confidences || !normalisers || !frames || !committed || !status)
+        return ASG_ERR_INVALID;
+    if (state_bytes < beam_conf_window_bytes(gl, B, g->dtype, beam_size, W, P, frame_tolerance, max_chunk)) return ASG_ERR_WORKSPACE;
+    Problem Pr{};
+    Pr.transition = transition; Pr.ts0 = transition_strides[0]; Pr.ts1 = transition_strides[1];
+    Pr.T = (int) W; Pr.B = (int) B; Pr.N = g->N; Pr.S = 1;
+    const GraphArgs G = to_graph_args(g);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    const int K = beam_graph_k(G.Q, beam_size);
+    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
+    long long *tf = (long long *) token_frames, *fr = (long long *) frames, *co = (long long *) committed, *su = (long long *) status;
+    return hip_status(ASG_DISPATCH(g,
+        launch_beam_conf_window_confidence<float>(Pr, G, BG, K, (int) W, (int) P, frame_tolerance, (int) max_chunk, state, final, scores,
+                                                  pa, tk, tl, st, tf, token_confidences, normalisers, fr, co, su,
+                                                  (hipStream_t) stream),
+        launch_beam_conf_window_confidence<double>(Pr, G, BG, K, (int) W, (int) P, frame_tolerance, (int) max_chunk, state, final,
+                                                   scores, pa, tk, tl, st, tf, token_confidences, normalisers, fr, co, su,
+                                                   (hipStream_t) stream)));
+}
+
 // The n-best token confidences: the checks of asg_beam_graph_confidence, then those of asg_beam_decode_graph_nbest.
 static int check_beam_nbest_conf(const asg_problem *p, const asg_token_graph_beam_loss *gl, int beam_size, int nbest) {
     int rc = check_beam_conf(p, gl, beam_size);

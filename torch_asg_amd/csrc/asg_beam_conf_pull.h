@@ -16,12 +16,23 @@ namespace asg {
 
 namespace {
 
+// Where the lattice rows of a frame lie.  FlatRows: frame t in row t, and the pull ends with the frame-0 term -- every caller
+// with a workspace or a state of T rows.  A state that keeps its rows in a ring (asg_beam_conf_window.hip) passes a policy of its
+// own: row(t) of the frames 0 .. len-1 it is called with, and first() -- whether its frame 0 is the utterance's.  (kFlat: the
+// row of the top frame is chosen by a constant, not by a call of row() -- with the call the flat callers' kernels came out with
+// another register allocation; this way their listings are the ones they had before there was a policy)
+struct FlatRows {
+    static constexpr bool kFlat = true;
+    __device__ __forceinline__ int row(int t) const { return t; }
+    __device__ __forceinline__ bool first() const { return true; }
+};
+
 // The beta pull with the token-event sink.  nb [M] / nq [M]: the dynamic LDS in front of the sink's ring (bwd_front).
 // Lat: TokenLat<R>, or a lattice with its edges and labels and an end term of its own (the prefix mode of the lattice-keeping
-// stream, asg_beam_stream_conf.hip); Lat::Args starts with TokenLat<R>::Args' members.
-template <typename R, typename Sink, typename Lat = TokenLat<R>>
+// stream, asg_beam_stream_conf.hip); Lat::Args starts with TokenLat<R>::Args' members.  Rows: see FlatRows.
+template <typename R, typename Sink, typename Lat = TokenLat<R>, typename Rows = FlatRows>
 __device__ __forceinline__ void beam_conf_pull(const Problem &P, const typename Lat::Args &args, char *wb, size_t beta_off,
-                                               R Z, int len, int last, int *nq, R *nb, Sink &sink) {
+                                               R Z, int len, int last, int *nq, R *nb, Sink &sink, Rows rows = Rows{}) {
     using KeyT = int;
     const int M = args.lay.M, tid = threadIdx.x, b = blockIdx.x;
     const R NINF = Num<R>::ninf();
@@ -35,9 +46,11 @@ __device__ __forceinline__ void beam_conf_pull(const Problem &P, const typename 
     lat.bind(args);
     auto tr = [&](int i, int j) -> R { return trm[(int64_t) i * P.ts0 + (int64_t) j * P.ts1]; };
 
-    int mt = nu[len - 1];
+    int top = len - 1;                                                         // the row of the last frame
+    if constexpr (!Rows::kFlat) top = rows.row(len - 1);
+    int mt = nu[top];
     for (int x = tid; x < mt; x += kBL) {
-        const KeyT p = U[(int64_t) (len - 1) * M + x];
+        const KeyT p = U[(int64_t) top * M + x];
         R e;
         lat.end(p, e);
         nq[x] = p;
@@ -48,11 +61,11 @@ __device__ __forceinline__ void beam_conf_pull(const Problem &P, const typename 
         sink.window(t);
         if constexpr (Sink::kBarrier) __syncthreads();
         const bool open = sink.open();
-        const int mp = nu[t - 1];
-        const KeyT *Up = U + (int64_t) (t - 1) * M;
-        const R *Ap = A + (int64_t) (t - 1) * M;
+        const int mp = nu[rows.row(t - 1)];
+        const KeyT *Up = U + (int64_t) rows.row(t - 1) * M;
+        const R *Ap = A + (int64_t) rows.row(t - 1) * M;
         R *Brow = Bv + (int64_t) ((t - 1) & 1) * M;
-        const R *xt = in + (int64_t) t * P.is0;
+        const R *xt = in + (int64_t) rows.row(t) * P.is0;
         const int G = subgroup(mp), per = kBL / G;
         for (int k0 = 0; k0 < mp; k0 += per) {
             const int k = k0 + tid / G, lg = tid % G;
@@ -94,7 +107,7 @@ __device__ __forceinline__ void beam_conf_pull(const Problem &P, const typename 
     __syncthreads();
     sink.window(0);
     if constexpr (Sink::kBarrier) __syncthreads();
-    if (sink.open())
+    if (rows.first() && sink.open())
         for (int x = tid; x < mt; x += kBL) sink.add(lat.label(nq[x]), (A[x] + nb[x]) - Z);
     __syncthreads();
     sink.window(last);                                                         // every window is closed

@@ -365,10 +365,10 @@ template <typename R>
 hipError_t launch_beam_window_nbest(const GraphArgs &G, const BeamGraphArgs &BG, int K, int W, int B, const void *state, int final,
                                     int nbest, void *work, void *scores, long long *path, long long *tokens, long long *tlen,
                                     long long *states, long long *num_hyps, long long *frames, long long *committed,
-                                    long long *status, hipStream_t stream) {
+                                    long long *status, hipStream_t stream, size_t stride) {
     Problem P{};
     P.T = W; P.B = B; P.N = 0;
-    return launch_nbest_kernel<R, kBeamNbestWindow>(P, G, BG, stream_src(sizeof(R), G, BG, K, W, state, nbest, work), B, K, nbest,
+    return launch_nbest_kernel<R, kBeamNbestWindow>(P, G, BG, stream_src(sizeof(R), G, BG, K, W, state, nbest, work, stride), B, K, nbest,
                                                     final != 0, scores, nullptr, nullptr, path, tokens, tlen, states, num_hyps,
                                                     frames, committed, status, stream);
 }
@@ -378,7 +378,7 @@ hipError_t launch_beam_window_nbest(const GraphArgs &G, const BeamGraphArgs &BG,
                                                     long long *, long long *, long long *, hipStream_t, size_t);                   \
     template hipError_t launch_beam_window_nbest<R>(const GraphArgs &, const BeamGraphArgs &, int, int, int, const void *, int, int, \
                                                     void *, void *, long long *, long long *, long long *, long long *,            \
-                                                    long long *, long long *, long long *, long long *, hipStream_t);
+                                                    long long *, long long *, long long *, long long *, hipStream_t, size_t);
 ASG_BEAM_STREAM_NBEST_INST(float)
 ASG_BEAM_STREAM_NBEST_INST(double)
 #undef ASG_BEAM_STREAM_NBEST_INST

@@ -95,15 +95,6 @@ __global__ void __launch_bounds__(kBL) beam_stream_conf_catchup(Problem P, Graph
     if (tid == 0) hdr[kHdrApos] = L;
 }
 
-// TokenLat with the end term of a prefix: a path may end in any kept state of the last set with weight 0.
-template <typename R>
-struct PrefixLat : TokenLat<R> {
-    struct Args : TokenLat<R>::Args { int fin; };
-    int fin;
-    __device__ void bind(const Args &a) { TokenLat<R>::bind(a); fin = a.fin; }
-    __device__ void end(int q, R &e) const { e = fin ? this->fw[q] : R(0); }
-};
-
 inline size_t stream_conf_lds(int elem, int K) { return bwd_front(elem, 4, K) + (size_t) kConfRing * 8; }
 
 // Dynamic LDS: [nb R K][nq int K][pad to 16][ring u64 256] (beam_conf_bwd's).

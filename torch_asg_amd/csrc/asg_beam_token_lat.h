@@ -30,6 +30,16 @@ struct TokenLat {
     }
 };
 
+// TokenLat with the end term of a prefix: a path may end in any kept state of the last set with weight 0 (the lattice-keeping
+// streams, asg_beam_stream_conf.hip and asg_beam_conf_window.hip).
+template <typename R>
+struct PrefixLat : TokenLat<R> {
+    struct Args : TokenLat<R>::Args { int fin; };
+    int fin;
+    __device__ void bind(const Args &a) { TokenLat<R>::bind(a); fin = a.fin; }
+    __device__ void end(int q, R &e) const { e = fin ? this->fw[q] : R(0); }
+};
+
 }  // namespace
 
 }  // namespace asg

@@ -26,6 +26,7 @@
 #include "asg_beam_common.h"
 #include "asg_beam_frame.h"
 #include "asg_beam_window_common.h"   // the commit attempt, shared with asg_beam_word_window.hip
+#include "asg_beam_window_lat.h"      // the keep policy: what a lattice-keeping state keeps besides (asg_beam_conf_window.hip)
 
 namespace asg {
 
@@ -59,24 +60,28 @@ __global__ void __launch_bounds__(256) beam_window_reset_kernel(char *state, Bea
 
 // What the commits of one call write to, and the ring they read (LDS, behind WinCtl: a commit is rare, and the frame loop
 // keeps its scalar registers for the search).
-struct WinOut {
+template <bool FR>
+struct WinOutT {
     static constexpr bool kWords = false;    // (window_commit: no ring of LM states, no words)
+    static constexpr bool kFrames = FR;      // (... and the tokens' start frames for a lattice-keeping state)
     const int *bq, *bs;          // the ring [W][K]
     int K, Q, W;
     const int *label, *state;
     long long *np, *ns, *nt;     // this slot's rows of new_path / new_states / new_tokens
     long long cols;              // W + Tc
+    long long *tf;               // kFrames: this slot's row of new_token_frames
 };
-static_assert(sizeof(Ctl<unsigned long long>) <= kWinCtlOff && sizeof(WinCtl) <= 64 && kWinOutOff + sizeof(WinOut) <= kFixedLds,
-              "control blocks");
+static_assert(sizeof(Ctl<unsigned long long>) <= kWinCtlOff && sizeof(WinCtl) <= 64 &&
+              kWinOutOff + sizeof(WinOutT<true>) <= kFixedLds, "control blocks");
 
-template <typename R, bool TRL>
+template <typename R, bool TRL, typename Keep>
 __global__ void __launch_bounds__(kBT) beam_window_advance_kernel(Problem P, GraphArgs g, BeamGraphArgs bg, int K, R theta, int cap,
                                                                   int W, int CP, char *state, BeamStreamLayout lay,
                                                                   long long *new_path, long long *new_states,
                                                                   long long *new_tokens, long long *new_frames,
-                                                                  long long *new_tlen) {
+                                                                  long long *new_tlen, Keep keep) {
     using KT = Key<R>;
+    using WinOut = WinOutT<Keep::kLattice>;
     using U = typename KT::U;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     Ctl<U> &ctl = *(Ctl<U> *) lds;
@@ -97,6 +102,7 @@ __global__ void __launch_bounds__(kBT) beam_window_advance_kernel(Problem P, Gra
         o.bq = nullptr; o.bs = nullptr;
         o.K = K; o.Q = g.Q; o.W = W; o.label = g.label; o.state = g.state; o.cols = cols;
         o.np = np; o.ns = ns; o.nt = nt;
+        if constexpr (Keep::kLattice) o.tf = keep.tf + (int64_t) b * cols;
     }
 
     long long pos = hdr->pos, base0 = hdr->base;
@@ -105,6 +111,8 @@ __global__ void __launch_bounds__(kBT) beam_window_advance_kernel(Problem P, Gra
     if (na0 > 0) base0 = window_live_base(pos, base0, W);
     const int n = clamp_len(P.in_len, b, P.T);
     if (tid == 0) { wc.base = base0; wc.carry = hdr->carry; wc.status = hdr->status; wc.ncommit = 0; wc.ntok = 0; }
+    keep.chunk(wb, (const R *) P.inputs + (int64_t) b * P.is1, P, pos, n);
+    int logged = 0;                                         // (a lattice-keeping state's: the attempts in its log)
 
     if (n >= 1) {
         const R *in = (const R *) P.inputs + (int64_t) b * P.is1;
@@ -121,12 +129,17 @@ __global__ void __launch_bounds__(kBT) beam_window_advance_kernel(Problem P, Gra
         beam_load_set<R, TRL>(f, trs, set_v, na0);
 
         int row = (int) (pos % W), ph = (int) (pos % CP);   // the next frame's row, and pos mod P; both kept by stepping
+        int ran = 0;
         for (int t = 0; t < n; ++t) {
             const long long gt = pos + t;                   // the frame's index in the utterance
             int na = ctl.na;
             if (gt >= 1 && na == 0) break;                  // an empty beam stays empty (and commits nothing more)
             const int fr = row;
             beam_frame<R, TRL>(f, gt == 0, na, in + (int64_t) t * P.is0, P.is2, bq, bs, fr);
+            if constexpr (Keep::kLattice) {
+                ran = t + 1;
+                keep.frame(wb, gt, ctl.na < K ? ctl.na : K, bq + (int64_t) fr * K, K);
+            }
             const long long p1 = gt + 1;                    // pos, counting this frame
             row = row + 1 == W ? 0 : row + 1;
             ph = ph + 1 == CP ? 0 : ph + 1;
@@ -136,6 +149,9 @@ __global__ void __launch_bounds__(kBT) beam_window_advance_kernel(Problem P, Gra
             // ================================================================ commit attempt
             // ---- convergence: the latest frame at which every survivor has the same ancestor
             long long base = wc.base;
+            const long long b0 = base;
+            int tk0 = 0;
+            if constexpr (Keep::kLattice) tk0 = wc.ntok;
             int cslot, crow;
             const long long c = window_converge(bs, K, W, na, p1, base, fr, mark, wc.scan, cslot, crow);
             if (c >= base) {
@@ -154,7 +170,12 @@ __global__ void __launch_bounds__(kBT) beam_window_advance_kernel(Problem P, Gra
                     window_commit(wc, o, p1 - 1, fr, base + F - 1, bk);
                 }
             }
+            if constexpr (Keep::kLattice) {                 // one attempt is one lattice end, whatever it committed
+                const int tk1 = wc.ntok;
+                if (tk1 > tk0) keep.attempt(wb, logged++, p1, b0, tk0, tk1);
+            }
         }
+        keep.skipped(wb, pos, ran, n);
         const int na = beam_store_set<R>(f, set_v);
         if (tid == 0) hdr->na = na;
     }
@@ -162,6 +183,7 @@ __global__ void __launch_bounds__(kBT) beam_window_advance_kernel(Problem P, Gra
     const int nc = wc.ncommit, ntk = wc.ntok;
     for (long long x = nc + tid; x < cols; x += kBT) { np[x] = -1; ns[x] = -1; }
     for (long long x = ntk + tid; x < cols; x += kBT) nt[x] = -1;
+    keep.done(wb, logged, ntk, cols);
     if (tid == 0) {
         new_frames[b] = nc;
         new_tlen[b] = ntk;
@@ -240,58 +262,81 @@ size_t beam_window_state_bytes(int elem, int W, int B, int Q, int K, int cap) {
 }
 
 hipError_t launch_beam_window_reset(int elem, const GraphArgs &G, const BeamGraphArgs &BG, int K, int W, int B, void *state,
-                                    const unsigned char *mask, hipStream_t stream) {
+                                    const unsigned char *mask, hipStream_t stream, size_t stride) {
     const int cap = beam_graph_cap(G.Q, K, BG.max_out, BG.num_start);
-    const BeamStreamLayout lay = beam_window_layout(elem, W, G.Q, K, cap);
+    BeamStreamLayout lay = beam_window_layout(elem, W, G.Q, K, cap);
+    if (stride) lay.per = stride;                                           // (a slot with parts of the caller's behind it)
     hipLaunchKernelGGL(beam_window_reset_kernel, dim3(B, reset_blocks(G.Q)), dim3(256), 0, stream, (char *) state, lay,
                        beam_work_layout(elem, W, G.Q, K, cap), G.Q, elem, mask);
     return hipGetLastError();
 }
 
-template <typename R>
-hipError_t launch_beam_window_advance(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, int K, double theta, int W,
-                                      int CP, void *state, long long *new_path, long long *new_states, long long *new_tokens,
-                                      long long *new_frames, long long *new_tlen, hipStream_t stream) {
+namespace {
+
+template <typename R, typename Keep>
+hipError_t beam_window_advance(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, int K, double theta, int cap, int W,
+                               int CP, void *state, const BeamStreamLayout &lay, long long *new_path, long long *new_states,
+                               long long *new_tokens, long long *new_frames, long long *new_tlen, Keep keep, hipStream_t stream) {
     const int N = P.N;
-    const int cap = beam_graph_cap(G.Q, K, BG.max_out, BG.num_start);
-    const BeamStreamLayout lay = beam_window_layout(sizeof(R), W, G.Q, K, cap);
     // the LDS of the one-shot decoder plus the two mark sets: control blocks, marks, the set, and the transitions when they fit
     const size_t beam = kFixedLds + mark_bytes(K) + (size_t) K * (sizeof(R) + 4) + 8;
     const bool trl = beam + (size_t) N * N * sizeof(R) <= kLdsMax;
     const size_t dyn = beam + (trl ? (size_t) N * N * sizeof(R) : 0);
 #define ASG_BEAM_WINDOW(TRL)                                                                                               \
     do {                                                                                                                   \
-        const void *fn = (const void *) beam_window_advance_kernel<R, TRL>;                                               \
+        const void *fn = (const void *) beam_window_advance_kernel<R, TRL, Keep>;                                         \
         if (dyn > 64 * 1024) (void) hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) dyn);     \
-        hipLaunchKernelGGL((beam_window_advance_kernel<R, TRL>), dim3(P.B), dim3(kBT), dyn, stream, P, G, BG, K, (R) theta, \
-                           cap, W, CP, (char *) state, lay, new_path, new_states, new_tokens, new_frames, new_tlen);        \
+        hipLaunchKernelGGL((beam_window_advance_kernel<R, TRL, Keep>), dim3(P.B), dim3(kBT), dyn, stream, P, G, BG, K,   \
+                           (R) theta, cap, W, CP, (char *) state, lay, new_path, new_states, new_tokens, new_frames,       \
+                           new_tlen, keep);                                                                                \
     } while (0)
     if (trl) ASG_BEAM_WINDOW(true); else ASG_BEAM_WINDOW(false);
 #undef ASG_BEAM_WINDOW
     return hipGetLastError();
 }
+
+}  // namespace
+
+template <typename R>
+hipError_t launch_beam_window_advance(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, int K, double theta, int W,
+                                      int CP, void *state, long long *new_path, long long *new_states, long long *new_tokens,
+                                      long long *new_frames, long long *new_tlen, hipStream_t stream,
+                                      const BeamConfWindowLayout *cw, long long *new_token_frames) {
+    const int cap = beam_graph_cap(G.Q, K, BG.max_out, BG.num_start);
+    if (cw) {
+        WinKeepLattice keep{};
+        keep.hdr = cw->st.hdr; keep.cnt = cw->lat.cnt; keep.em = cw->em; keep.U = cw->lat.U; keep.log = cw->log;
+        keep.RW = cw->RW; keep.nlog = cw->nlog; keep.tf = new_token_frames;
+        return beam_window_advance<R>(P, G, BG, K, theta, cap, W, CP, state, cw->st, new_path, new_states, new_tokens, new_frames,
+                                      new_tlen, keep, stream);
+    }
+    return beam_window_advance<R>(P, G, BG, K, theta, cap, W, CP, state, beam_window_layout(sizeof(R), W, G.Q, K, cap), new_path,
+                                  new_states, new_tokens, new_frames, new_tlen, WinKeepNone{}, stream);
+}
 template hipError_t launch_beam_window_advance<float>(const Problem &, const GraphArgs &, const BeamGraphArgs &, int, double, int,
                                                       int, void *, long long *, long long *, long long *, long long *, long long *,
-                                                      hipStream_t);
+                                                      hipStream_t, const BeamConfWindowLayout *, long long *);
 template hipError_t launch_beam_window_advance<double>(const Problem &, const GraphArgs &, const BeamGraphArgs &, int, double, int,
                                                        int, void *, long long *, long long *, long long *, long long *,
-                                                       long long *, hipStream_t);
+                                                       long long *, hipStream_t, const BeamConfWindowLayout *, long long *);
 
 template <typename R>
 hipError_t launch_beam_window_result(const GraphArgs &G, const BeamGraphArgs &BG, int K, int W, int B, const void *state, int final,
                                      void *scores, long long *path, long long *tokens, long long *tlen, long long *states,
-                                     long long *frames, long long *committed, long long *status, hipStream_t stream) {
+                                     long long *frames, long long *committed, long long *status, hipStream_t stream,
+                                     size_t stride) {
     const int cap = beam_graph_cap(G.Q, K, BG.max_out, BG.num_start);
-    const BeamStreamLayout lay = beam_window_layout(sizeof(R), W, G.Q, K, cap);
+    BeamStreamLayout lay = beam_window_layout(sizeof(R), W, G.Q, K, cap);
+    if (stride) lay.per = stride;                                           // (a slot with parts of the caller's behind it)
     hipLaunchKernelGGL((beam_window_result_kernel<R>), dim3(B), dim3(kBT), 0, stream, G, K, cap, W, (const char *) state, lay, final,
                        (R *) scores, path, tokens, tlen, states, frames, committed, status);
     return hipGetLastError();
 }
 template hipError_t launch_beam_window_result<float>(const GraphArgs &, const BeamGraphArgs &, int, int, int, const void *, int,
                                                      void *, long long *, long long *, long long *, long long *, long long *,
-                                                     long long *, long long *, hipStream_t);
+                                                     long long *, long long *, hipStream_t, size_t);
 template hipError_t launch_beam_window_result<double>(const GraphArgs &, const BeamGraphArgs &, int, int, int, const void *, int,
                                                       void *, long long *, long long *, long long *, long long *, long long *,
-                                                      long long *, long long *, hipStream_t);
+                                                      long long *, long long *, hipStream_t, size_t);
 
 }  // namespace asg

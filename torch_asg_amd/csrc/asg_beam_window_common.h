@@ -116,9 +116,30 @@ __device__ __forceinline__ long long window_forced(long long p1, long long base,
     return live > W - CP ? live - (W - CP) : 0;
 }
 
+// One wavefront, behind collapse_tokens_from over the same segment: the absolute frame at which every kept label was kept --
+// frame `first` + t for pb[t] -- to tf[0..), the walk of beam_conf_tokens (asg_beam_conf_pull.h) with the segment's carry.
+__device__ inline void collapse_frames_from(const long long *pb, int len, long long carry, long long first, long long *tf,
+                                            int lane) {
+    int base = 0;
+    for (int c0 = 0; c0 < len; c0 += 64) {
+        const int t = c0 + lane;
+        const long long cur = t < len ? pb[t] : -1;
+        long long prv = __shfl_up(cur, 1);
+        if (lane == 0) prv = carry;
+        const bool keep = t < len && cur != prv;
+        const unsigned long long m = __ballot(keep);
+        const int pre = __popcll(m & ((1ull << lane) - 1ull));
+        if (keep) tf[base + pre] = first + t;
+        base += __popcll(m);
+        carry = __shfl(cur, 63);                             // (only read when another 64 frames follow)
+    }
+}
+
 // Commit the frames base .. cto on the path that passes slot k of frame `top`, which lives in row `r` (base <= cto <= top <
 // base + W): one lane walks the chain, one wavefront collapses the segment's labels behind `carry`, and with WO::kWords another
-// finds its words behind `carry` / `carry_state`.  The whole workgroup calls it; it begins after and ends with a __syncthreads.
+// finds its words behind `carry` / `carry_state`; with WO::kFrames (the lattice-keeping token window, asg_beam_conf_window.hip)
+// the first wavefront also writes every committed token's start frame to o.tf.  The whole workgroup calls it; it begins after and
+// ends with a __syncthreads.
 // (A slot outside 0 .. K-1 cannot happen; if it did, the token family would stop writing the segment, the word family pad with -1.)
 template <typename WC, typename WO>
 __device__ __forceinline__ void window_commit(WC &wc, const WO &o, long long top, int r, long long cto, int k) {
@@ -158,6 +179,7 @@ __device__ __forceinline__ void window_commit(WC &wc, const WO &o, long long top
     if (tid < 64) {
         const int t0 = wc.ntok;
         long long carry = wc.carry;
+        if constexpr (WO::kFrames) collapse_frames_from(o.np + c0, len, carry, base, o.tf + t0, tid);
         const int nt = collapse_tokens_from(o.np + c0, len, carry, o.nt + t0, tid);
         if (tid == 0) { wc.ntok = t0 + nt; wc.carry = (int) carry; wc.ncommit = c0 + len; wc.base = base + len; }
     }

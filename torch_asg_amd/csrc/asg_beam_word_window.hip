@@ -60,6 +60,7 @@ struct WinCtl {
 // registers for the search).
 struct WinOut {
     static constexpr bool kWords = true;     // (window_commit: the ring bh, the output nl, the wavefront that finds the words)
+    static constexpr bool kFrames = false;   // (... and no start frames of the tokens)
     const int *bq, *bh, *bs;     // the ring [W][K]
     int K, Q, W, S, sep;
     const int *label, *state, *wos;

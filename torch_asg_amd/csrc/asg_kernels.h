@@ -347,17 +347,23 @@ hipError_t launch_beam_word_stream_nbest_la(const GraphArgs &G, const BeamGraphA
 // status.  CP: the commit period (a commit attempt after every frame whose count is a multiple of it), 1 <= CP <= W.
 BeamStreamLayout beam_window_layout(int elem, int W, int Q, int K, int cap);
 size_t beam_window_state_bytes(int elem, int W, int B, int Q, int K, int cap);
+// (stride, here and below: as launch_beam_stream_result's -- a lattice-keeping state's slots, asg_beam_conf_window.hip)
 hipError_t launch_beam_window_reset(int elem, const GraphArgs &G, const BeamGraphArgs &BG, int K, int W, int B, void *state,
-                                    const unsigned char *mask, hipStream_t stream);
-// new_path / new_states / new_tokens [B][W + P.T], new_frames / new_tlen [B]: every element is written
+                                    const unsigned char *mask, hipStream_t stream, size_t stride = 0);
+// new_path / new_states / new_tokens [B][W + P.T], new_frames / new_tlen [B]: every element is written.  cw: the state is a
+// lattice-keeping one (beam_conf_window_layout below) -- the same kernel with the policy that also keeps the ring's cnt, emissions
+// and unsorted sets, writes new_token_frames [B][W + P.T] and logs the attempts that committed (asg_beam_window_lat.h).
+struct BeamConfWindowLayout;
 template <typename R>
 hipError_t launch_beam_window_advance(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, int K, double theta, int W,
                                       int CP, void *state, long long *new_path, long long *new_states, long long *new_tokens,
-                                      long long *new_frames, long long *new_tlen, hipStream_t stream);
+                                      long long *new_frames, long long *new_tlen, hipStream_t stream,
+                                      const BeamConfWindowLayout *cw = nullptr, long long *new_token_frames = nullptr);
 template <typename R>
 hipError_t launch_beam_window_result(const GraphArgs &G, const BeamGraphArgs &BG, int K, int W, int B, const void *state, int final,
                                      void *scores, long long *path, long long *tokens, long long *tlen, long long *states,
-                                     long long *frames, long long *committed, long long *status, hipStream_t stream);
+                                     long long *frames, long long *committed, long long *status, hipStream_t stream,
+                                     size_t stride = 0);
 
 // ---- The search over pairs in bounded memory (asg_beam_word_window.hip): asg_beam_word_window_*.  One slot of the state has the
 // layout of a word stream of W frames -- bq / bh / bs are rings, frame u in row u mod W -- with the header int64 pos, int64 base,
@@ -446,7 +452,7 @@ template <typename R>
 hipError_t launch_beam_window_nbest(const GraphArgs &G, const BeamGraphArgs &BG, int K, int W, int B, const void *state, int final,
                                     int nbest, void *work, void *scores, long long *path, long long *tokens, long long *tlen,
                                     long long *states, long long *num_hyps, long long *frames, long long *committed,
-                                    long long *status, hipStream_t stream);
+                                    long long *status, hipStream_t stream, size_t stride = 0);   // as launch_beam_stream_result's
 
 // ---- Beam-pruned full score and gradients over the same composed lattice (asg_beam_loss.hip): asg_beam_graph_full_*.
 struct BeamLossArgs {
@@ -520,6 +526,36 @@ hipError_t launch_beam_conf_stream_confidence(const Problem &P, const GraphArgs 
                                               void *state, int final, int tol, void *scores, long long *path, long long *tokens,
                                               long long *tlen, long long *states, long long *token_frames, void *token_conf,
                                               void *normalisers, long long *frames, long long *status, hipStream_t stream);
+
+// ---- The window stream with a state that keeps its lattice in a ring (asg_beam_conf_window.hip): asg_beam_conf_window_*.  One
+// slot: the plain window's slot (beam_window_layout) unchanged at the front -- its header block also holds apos and the number of
+// logged attempts (asg_beam_window_lat.h) --, then (byte offsets, each part 256-byte aligned) a ring of RW = W + tol + 1 + C rows,
+// frame t in row t mod RW: cnt int32 [RW], the emissions [RW][N], nu int32 [RW], U int32 [RW][K], A [RW][K]; the attempt log of
+// nlog = C / CP + 1 entries; beta [nlog][2][K], a pair of rows per logged attempt.  C: the longest chunk an advance may bring.
+constexpr int kBeamConfWindowMaxLog = 65535;   // C / CP + 1: the pull's grid is (B, log entries)
+struct BeamConfWindowLayout {
+    BeamStreamLayout st;
+    BeamLossLayout lat;          // cnt, nu, U, A over the ring (M = K, nf = 0); lat.per is the slot's stride
+    size_t em, log, beta, per;
+    int RW, nlog;
+};
+BeamConfWindowLayout beam_conf_window_layout(int elem, int W, int CP, int tol, int C, int Q, int K, int cap, int N);
+size_t beam_conf_window_state_bytes(int elem, int W, int CP, int tol, int C, int B, int Q, int K, int cap, int N);
+// Three launches: the search (launch_beam_window_advance with cw), the catch-up of U / nu / A over [apos, pos), the pull of every
+// logged attempt.  new_token_frames / new_token_conf [B][W + P.T]: every element is written.
+template <typename R>
+hipError_t launch_beam_conf_window_advance(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, int K, double theta, int W,
+                                           int CP, int tol, int C, void *state, long long *new_path, long long *new_states,
+                                           long long *new_tokens, long long *new_frames, long long *new_tlen,
+                                           long long *new_token_frames, void *new_token_conf, hipStream_t stream);
+// Two launches: the plain result kernel, then token_frames / token_conf [B][W] and normalisers [B] by one pull from pos - 1 down
+// to base - tol.  P: B, N and the transition.  It only reads the state (beta rows apart).
+template <typename R>
+hipError_t launch_beam_conf_window_confidence(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, int K, int W, int CP,
+                                              int tol, int C, void *state, int final, void *scores, long long *path,
+                                              long long *tokens, long long *tlen, long long *states, long long *token_frames,
+                                              void *token_conf, void *normalisers, long long *frames, long long *committed,
+                                              long long *status, hipStream_t stream);
 
 // ---- Token confidences and start frames for every row of the n-best list (asg_beam_nbest_conf.hip):
 // asg_beam_graph_nbest_confidence.  One utterance's workspace: asg_beam_graph_confidence's layout at the front (the search's

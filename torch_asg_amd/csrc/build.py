@@ -12,9 +12,9 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["asg_small_f32.hip", "asg_small_f64.hip", "asg_bwd_f32.hip", "asg_bwd_f64.hip", "asg_fused.hip", "asg_generic.hip", "asg_generic_step.hip", "asg_generic_aligned.hip", "asg_generic_grad.hip",
-           "asg_viterbi.hip", "asg_decode.hip", "asg_decode_graph.hip", "asg_beam_graph.hip", "asg_beam_nbest.hip", "asg_beam_stream.hip", "asg_beam_stream_conf.hip", "asg_beam_window.hip", "asg_beam_word.hip", "asg_beam_word_la.hip", "asg_beam_word_stream.hip", "asg_beam_word_stream_conf.hip", "asg_beam_word_nbest.hip", "asg_beam_word_window.hip", "asg_beam_loss.hip", "asg_beam_conf.hip", "asg_beam_nbest_conf.hip", "asg_beam_word_loss.hip", "asg_beam_word_conf.hip", "asg_beam_word_nbest_conf.hip", "asg_graph_loss.hip",
+           "asg_viterbi.hip", "asg_decode.hip", "asg_decode_graph.hip", "asg_beam_graph.hip", "asg_beam_nbest.hip", "asg_beam_stream.hip", "asg_beam_stream_conf.hip", "asg_beam_window.hip", "asg_beam_conf_window.hip", "asg_beam_word.hip", "asg_beam_word_la.hip", "asg_beam_word_stream.hip", "asg_beam_word_stream_conf.hip", "asg_beam_word_nbest.hip", "asg_beam_word_window.hip", "asg_beam_loss.hip", "asg_beam_conf.hip", "asg_beam_nbest_conf.hip", "asg_beam_word_loss.hip", "asg_beam_word_conf.hip", "asg_beam_word_nbest_conf.hip", "asg_graph_loss.hip",
            "asg_api.hip"]
-HEADERS = ["asg_common.h", "asg_kernels.h", "asg_beam_common.h", "asg_beam_frame.h", "asg_beam_word_frame.h", "asg_beam_window_common.h", "asg_beam_stream_lat.h", "asg_beam_lattice.h", "asg_beam_alpha.inc", "asg_beam_token_lat.h", "asg_beam_conf_sink.h", "asg_beam_conf_pull.h", "asg_beam_row_sink.h", "asg_beam_cells.inc", "asg_beam_word_lat.h", "asg_beam_word_alpha.inc", "asg_beam_word_conf_pull.h", "asg_generic_common.h", "asg_chains.h", "asg_outer.h", "asg_assemble.h", "asg_small_impl.inc", "asg_bwd_impl.inc",
+HEADERS = ["asg_common.h", "asg_kernels.h", "asg_beam_common.h", "asg_beam_frame.h", "asg_beam_word_frame.h", "asg_beam_window_common.h", "asg_beam_window_lat.h", "asg_beam_stream_lat.h", "asg_beam_lattice.h", "asg_beam_alpha.inc", "asg_beam_token_lat.h", "asg_beam_conf_sink.h", "asg_beam_conf_pull.h", "asg_beam_row_sink.h", "asg_beam_cells.inc", "asg_beam_word_lat.h", "asg_beam_word_alpha.inc", "asg_beam_word_conf_pull.h", "asg_generic_common.h", "asg_chains.h", "asg_outer.h", "asg_assemble.h", "asg_small_impl.inc", "asg_bwd_impl.inc",
            os.path.join("..", "..", "include", "asg_hip.h")]
 OUT = os.path.join(HERE, "libasg_hip.so")
 ARCH = os.environ.get("ASG_HIP_ARCH", "gfx950")

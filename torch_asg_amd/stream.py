@@ -532,6 +532,11 @@ BeamWindowResult = collections.namedtuple("BeamWindowResult", ["scores", "path",
                                                                "committed", "status"])
 BeamWindowNbest = collections.namedtuple("BeamWindowNbest", ["scores", "tokens", "token_lengths", "num_hyps", "path", "states",
                                                              "frames", "committed", "status"])
+BeamWindowConfCommit = collections.namedtuple("BeamWindowConfCommit", BeamWindowCommit._fields + ("token_frames",
+                                                                                                  "token_confidences"))
+BeamWindowConfidence = collections.namedtuple("BeamWindowConfidence", ["scores", "path", "tokens", "token_lengths", "states",
+                                                                       "token_frames", "token_confidences", "normalisers", "frames",
+                                                                       "committed", "status"])
 
 
 class BeamWindowStream(_Stream):
@@ -557,23 +562,57 @@ class BeamWindowStream(_Stream):
     one kernel launch each, copy nothing and do not synchronise, so they can be captured and replayed.  The other arguments are
     `BeamStream`'s; there is no bound on the number of frames.  `result_nbest` gives the n best hypotheses as their uncommitted
     tails, with `BeamStream.result_nbest`'s scores.
+
+    `keep_lattice=True` makes the state keep the lattice of the search in a ring of window + frame_tolerance + 1 + max_chunk
+    frames (include/asg_hip.h::asg_beam_conf_window_*: the kept sets, the emissions and alpha -- about that many times
+    N + 2 * beam_size values more per slot, whatever the length of the stream).  `advance` then returns a
+    `BeamWindowConfCommit`: the five fields and, for every token it commits, `token_frames` (the absolute frame at which the
+    token starts) and `token_confidences` (the posterior, at the moment of the commit, that a token with this label starts within
+    `frame_tolerance` frames of that frame: `BeamStream(keep_lattice=True).result_confidence(frame_tolerance)`'s value at that
+    position, bit for bit while bit 0 of `status` is clear), -1 and 0 behind the tokens; it is three launches and still captures.
+    `result_confidence` gives the same for the uncommitted tail.  `frame_tolerance` (0 .. 64) and `max_chunk` (default `window`;
+    a longer chunk raises ValueError) size the state and are fixed for the life of the stream.  The five fields, `result`,
+    `result_nbest` and `reset` return what they return without `keep_lattice`, byte for byte.  alpha and the normaliser grow with
+    the stream, as the scores do: float32 loses resolution in a posterior as they pass about 1e5, so streams of hours want
+    float64.
     """
     _API, _WIDE, _NARROW = "asg_beam_window", 3, 4
 
     def __init__(self, transition, graph, batch_size, window, commit_every=None, beam_size=256, beam_threshold=float("inf"),
-                 lm_weight=1.0, token_score=0.0, dtype=torch.float32, device=None):
+                 lm_weight=1.0, token_score=0.0, dtype=torch.float32, device=None, keep_lattice=False, frame_tolerance=0,
+                 max_chunk=None):
         self.lm_weight, self.token_score = lm_weight, token_score
+        self.keep_lattice = bool(keep_lattice)
+        shape = (window, commit_every)
+        if self.keep_lattice:
+            self._API = "asg_beam_conf_window"                 # the same calls in the same order over the wider state, whose
+            shape += (frame_tolerance, max_chunk)              # shape has two more parameters
         self._nbest_work = {}                                  # nbest -> the scratch of result_nbest (not part of the state)
-        super().__init__(transition, (graph,), batch_size, (window, commit_every), beam_size, beam_threshold, dtype, device)
-        self.window, self.commit_every = self._shape
+        super().__init__(transition, (graph,), batch_size, shape, beam_size, beam_threshold, dtype, device)
+        self.window, self.commit_every = self._shape[:2]
+        self.frame_tolerance, self.max_chunk = self._shape[2:] if self.keep_lattice else (None, None)
 
-    def _check_shape(self, batch_size, window, commit_every):
+    def _check_shape(self, batch_size, window, commit_every, frame_tolerance=None, max_chunk=None):
         if int(batch_size) < 1 or int(window) < 1:
             raise ValueError("torch_asg_amd: batch_size and window must be >= 1, got %d and %d" % (int(batch_size), int(window)))
         commit_every = max(1, int(window) // 4) if commit_every is None else int(commit_every)
         if not 1 <= commit_every <= int(window):
             raise ValueError("torch_asg_amd: commit_every must be in 1 .. window = %d, got %d" % (int(window), commit_every))
-        return int(window), commit_every
+        if frame_tolerance is None:
+            return int(window), commit_every
+        if int(frame_tolerance) < 0:
+            raise ValueError("torch_asg_amd: frame_tolerance must be >= 0, got %d" % int(frame_tolerance))
+        max_chunk = int(window) if max_chunk is None else int(max_chunk)
+        if max_chunk < 1:
+            raise ValueError("torch_asg_amd: max_chunk must be >= 1, got %d" % max_chunk)
+        return int(window), commit_every, min(int(frame_tolerance), (1 << 31) - 1), max_chunk
+
+    def _compile(self):
+        if not self.keep_lattice:
+            return super()._compile()
+        from . import graph as _graph
+        compiled = self.graph.compile_beam_loss(self.device, self.dtype, self.lm_weight, self.token_score)
+        return (_graph.abi_graph_beam_loss(compiled),), compiled
 
     def reset(self, mask=None):
         """Start new utterances: in every slot (mask None), or in the slots where `mask` (bool or integer [B]) is not zero --
@@ -585,13 +624,22 @@ class BeamWindowStream(_Stream):
           path, states, tokens [B, window + Tc] int64, -1 behind the data: label and automaton state of every newly committed
           frame, and the tokens they add to the transcript (the collapse goes on across calls); token_lengths [B]; frames [B],
           the number of frames committed by this call."""
+        if self.keep_lattice:
+            if chunk.dim() == 3 and chunk.shape[0] > self.max_chunk:       # (the ring holds max_chunk frames behind an attempt)
+                raise ValueError("torch_asg_amd: a chunk of %d frames exceeds max_chunk = %d" % (chunk.shape[0], self.max_chunk))
+            path, states, tokens, frames, token_lengths, token_frames, conf = self._advance(chunk, chunk_lengths)
+            return BeamWindowConfCommit(path, states, tokens, token_lengths, frames, token_frames, conf)
         path, states, tokens, frames, token_lengths = self._advance(chunk, chunk_lengths)
         return BeamWindowCommit(path, states, tokens, token_lengths, frames)
 
     def _commit_outputs(self, Tc):
-        path, states, tokens = torch.empty(3, self.batch_size, self.window + Tc, dtype=torch.int64, device=self.device)
-        frames, token_lengths = torch.empty(2, self.batch_size, dtype=torch.int64, device=self.device)
-        return path, states, tokens, frames, token_lengths
+        B, cols, dev = self.batch_size, self.window + Tc, self.device
+        path, states, tokens = torch.empty(3, B, cols, dtype=torch.int64, device=dev)
+        frames, token_lengths = torch.empty(2, B, dtype=torch.int64, device=dev)
+        if not self.keep_lattice:
+            return path, states, tokens, frames, token_lengths
+        return (path, states, tokens, frames, token_lengths, torch.empty(B, cols, dtype=torch.int64, device=dev),
+                torch.empty(B, cols, dtype=self.dtype, device=dev))
 
     def result(self, final=False):
         """The best hypothesis of every slot for the frames that are not committed yet, without changing the state -> a named tuple
@@ -618,6 +666,38 @@ class BeamWindowStream(_Stream):
         scores, _, tokens, tlen, nh, path, states, (frames, committed, status) = self._token_nbest(nbest, final, return_alignments,
                                                                                                    False)
         return BeamWindowNbest(scores, tokens, tlen, nh, path, states, frames, committed, status)
+
+    def result_confidence(self, final=False):
+        """`result(final)` with a confidence and a start frame for every token of the uncommitted tail, from the lattice ring
+        (`keep_lattice=True`; RuntimeError without it, without touching the device) -> a named tuple
+          scores, path, tokens, token_lengths, states, frames, committed, status as `result(final)` returns them;
+          token_frames [B, window] int64, the absolute frame at which tail token k starts, -1 behind the tokens;
+          token_confidences [B, window], the posterior that a token with this label starts within the stream's `frame_tolerance`
+          of that frame, over the paths through the kept sets of all frames consumed, 0 behind the tokens; normalisers [B].
+        final=True ends the paths with the final weights: while bit 0 of `status` is clear the values are
+        `beam_decode_graph_confidence`'s for those tokens, bit for bit.  Two launches, no synchronisation; it only reads the
+        state (`advance` has already brought the alpha rows up to the frames consumed)."""
+        if not self.keep_lattice:
+            raise RuntimeError("torch_asg_amd: result_confidence needs the lattice of the search: build the stream with "
+                               "keep_lattice=True")
+        be = _asg.native()
+        L = _lib.lib()
+        B, dev, W = self.batch_size, self.device, self.window
+        transition = self.transition
+        with be._guard(dev):
+            real = torch.empty(2, B, dtype=self.dtype, device=dev)                 # scores, normalisers
+            wide = torch.empty(4, B, W, dtype=torch.int64, device=dev)             # path, tokens, states, token_frames
+            conf = torch.empty(B, W, dtype=self.dtype, device=dev)
+            narrow = torch.empty(4, B, dtype=torch.int64, device=dev)              # token_lengths, frames, committed, status
+            ts = (ctypes.c_int64 * 2)(*transition.stride())
+            _lib.check(L.asg_beam_conf_window_confidence(
+                None, *self._views, B, self.beam_size, *self._shape, self._state.data_ptr(), self._state.numel(),
+                transition.data_ptr(), ts, 1 if final else 0, real[0].data_ptr(), wide[0].data_ptr(), wide[1].data_ptr(),
+                narrow[0].data_ptr(), wide[2].data_ptr(), wide[3].data_ptr(), conf.data_ptr(), real[1].data_ptr(),
+                narrow[1].data_ptr(), narrow[2].data_ptr(), narrow[3].data_ptr(), 0, be._stream(dev)),
+                "asg_beam_conf_window_confidence")
+        return BeamWindowConfidence(real[0], wide[0], wide[1], narrow[0], wide[2], wide[3], conf, real[1], narrow[1], narrow[2],
+                                    narrow[3])
 
     @staticmethod
     def _outputs(scores, wide, narrow):
