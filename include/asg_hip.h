@@ -1631,6 +1631,134 @@ int asg_beam_word_conf_stream_confidence_la(asg_ctx *ctx, const asg_token_graph_
                                             int64_t *word_lengths, int64_t *word_frames, void *word_confidences, void *normalisers,
                                             int64_t *frames, int64_t *status, int flags, void *stream);
 
+/* ---- the LATTICE-KEEPING word window stream: asg_beam_word_window_* with a state that also keeps, in a ring, what
+ * asg_beam_words_confidence computes its word confidences from, so that a word-LM stream WITHOUT A BOUND on its frames gives a
+ * confidence and an end frame for every word at the moment it commits it (additions only; asg_beam_word_window_* and its state
+ * formula are unchanged).  The family has asg_beam_word_window_*'s argument order, the `_la` forms included, with two more
+ * parameters of the state behind W and P: frame_tolerance (tol, 0 .. 64) and max_chunk (C >= 1, the longest chunk an _advance may
+ * bring).  The state is sized by them and every call passes the same four values.
+ *
+ * DEFINITION.  The window never touches the search, so the kept pair sets A_0 .. A_{pos-1} are those of asg_beam_word_conf_stream_*
+ * fed the same frames (with the same look-ahead, if any), and the lattice is its lattice: those sets with plain pair weights, also
+ * behind a look-ahead search, and the event "word w ends at frame t" a separator edge into frame t behind a word-end node, summed
+ * over LM histories.  Take a commit attempt behind frame p1 - 1 (pos, counting the frame, is p1, and p1 mod P == 0).  For a word
+ * that attempt commits, with its separator at absolute frame f:
+ *   new_word_frames      = f (f >= the base before the attempt; a separator on the first frame of a segment behind the carried
+ *                          label counts, as it does for new_words);
+ *   new_word_confidences = the prefix-mode posterior of asg_beam_word_conf_stream_confidence over A_0 .. A_{p1-1}: a path ends in
+ *                          any pair of A_{p1-1} with weight 0, no word is closed at the end, Z is the log-sum-exp of alpha over
+ *                          A_{p1-1}, and the value sums the event over t in [f - tol, f + tol] clipped to [1, p1 - 1].
+ * It is what a listener knows at the moment the word becomes final.  A forced commit of the same attempt uses the same p1: one
+ * attempt is one lattice end.  No finite Z at the attempt: confidence 0, the frame still written; never a NaN.
+ *   - The eight outputs of asg_beam_word_window_advance, and _result, _nbest and _reset, are the plain family's byte for byte.
+ *   - The concatenation of all new_word_frames / new_word_confidences is the same bits for every chunking (attempts, and so
+ *     lattice ends, happen at frame indices).
+ *   - While status bit 0 is clear, the words an attempt at p1 commits carry, at the same word indices, the word_frames and
+ *     word_confidences of asg_beam_word_conf_stream_confidence(final = 0, tol) of a growing stream that stands at pos = p1, bit for
+ *     bit: the alpha text is the same, resumed from stored rows; the sets are the same ascending lists; Z is the same; the beta
+ *     recursion is the same from frame p1 - 1 downwards, and the integer accumulators do not depend on the order of the adds.
+ *   - With status bit 0 set the values are still the cell posteriors defined above.
+ *
+ * STATE.  With a256(x) = x rounded up to 256, e = 4 or 8 (the dtype), K = beam_size, N = gb->graph->N,
+ *     RW = W + tol + 1 + C   (rows of the lattice ring; frame t lives in row t mod RW, computed in 64 bits),
+ *     L  = C / P + 1         (entries of the attempt log, integer division),
+ * one slot is
+ *     per = PW + a256(4 RW) + a256(e RW N) + a256(4 RW) + a256(8 RW K) + a256(e RW K) + a256(24 L) + L a256(2 e K),
+ * where PW = asg_beam_word_window_state_bytes(gb, lm, 1, dtype, beam_size, W, P) is the plain window's slot, unchanged, at the
+ * front, and behind it: cnt int32 [RW], the emissions [RW][N], nu int32 [RW], U uint64 [RW][K] (the pair keys h << qbits | q of A_t,
+ * ascending once caught up), A [RW][K] (alpha), the attempt log (int64 p1, int64 base before the attempt, int32 first and
+ * one-past-last WORD of the call's output row), beta [L][2][K].  The slot's 256-byte header block holds, at byte 64, int64 apos
+ * (the frames whose U / nu / A rows are valid, pos - C <= apos <= pos) and int32 the number of attempts the last _advance logged.
+ * asg_beam_word_conf_window_state_bytes = B * per.  The ring is large enough: an attempt at p1 with old base b0 reads the frames
+ * b0 - tol - 1 .. p1 - 1, p1 - b0 <= W, and the call has written at most C frames behind p1.
+ *
+ * _advance / _advance_la: THREE launches, no host synchronisation, no memset, no copy; it captures and replays.
+ *   (a) the search: asg_beam_word_window_advance[_la]'s kernel, which also copies the chunk's emissions, |A_t| and the kept pairs'
+ *       keys of every frame into the ring, writes new_word_frames, and logs every attempt that committed a word;
+ *   (b) the catch-up over [apos, pos): the rows' keys sorted, alpha by asg_beam_words_full_forward's push, resumed from row
+ *       apos - 1 (or the start weights); apos = pos;
+ *   (c) the pull, one workgroup per (slot, logged attempt): Z over row p1 - 1, beta from frame p1 - 1 down to max(b0 - tol, 1);
+ *       the attempt's words are its sink.
+ *   outputs: asg_beam_word_window_advance's eight, then new_word_frames int64 [B][W + Tc] (-1 behind the data) and
+ *   new_word_confidences [B][W + Tc] in the dtype (0 behind the data).  Every element is written, also for Tc = 0.
+ *   Tc > max_chunk is ASG_ERR_UNSUPPORTED.  p->transition MUST NOT CHANGE within an utterance.  Only (a) reads the look-ahead.
+ * _reset, _result[_la], _nbest[_la], _nbest_work_bytes: asg_beam_word_window_*'s over the wider slot (a reset needs nothing more:
+ *   the next _advance finds pos = 0 and takes apos back to it).
+ * _confidence / _confidence_la (final): TWO launches; it only reads the state (beta rows apart).  _result[_la](final)'s eleven
+ *   outputs, and for the words of the uncommitted tail word_frames int64 [B][W] (absolute, -1 behind the data), word_confidences
+ *   [B][W] (0 behind the data) and normalisers [B]: one pull from frame pos - 1 down to base - tol with the state's tolerance, end
+ *   weight 0 (final = 0) or the end of asg_beam_decode_words through the word-end nodes (final = 1).  The word the end closes has
+ *   frame pos and its event is the final step's, as asg_beam_words_confidence gives a closing word the frame len.  With final = 1
+ *   and status bit 0 clear the tail's values are asg_beam_words_confidence's for those words on the frames consumed, bit for bit,
+ *   and the frames of all _advance calls followed by the tail's are its word_frames.  The catch-up was done by _advance.
+ * Error order: asg_beam_word_window_*'s checks of the state's shape; frame_tolerance < 0 or max_chunk < 1 ASG_ERR_INVALID;
+ * frame_tolerance > 64, W + frame_tolerance + 1 + max_chunk > 2^31 - 1 or L = max_chunk / P + 1 > 65535 (the pull runs one
+ * workgroup per slot and log entry) ASG_ERR_UNSUPPORTED; asg_beam_word_conf_stream_*'s limits for T = W (the lattice pass bounds
+ * beam_size: 8179 float32, 6816 float64); the look-ahead; then the call's own arguments as asg_beam_word_window_* checks them,
+ * with Tc > max_chunk ASG_ERR_UNSUPPORTED behind the problem's shape; a state that is too small ASG_ERR_WORKSPACE.  float32 and
+ * float64.  alpha and Z grow with pos, as the search's own scores do: in float32 a posterior loses resolution as |Z| passes about
+ * 1e5, so streams of hours want float64 (a rebased alpha is not there). */
+size_t asg_beam_word_conf_window_state_bytes(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype,
+                                             int beam_size, int64_t W, int64_t P, int frame_tolerance, int64_t max_chunk);
+int asg_beam_word_conf_window_reset(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
+                                    int64_t W, int64_t P, int frame_tolerance, int64_t max_chunk, void *state, size_t state_bytes,
+                                    const uint8_t *mask, int flags, void *stream);
+int asg_beam_word_conf_window_advance(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                      int beam_size, double beam_threshold, int64_t W, int64_t P, int frame_tolerance,
+                                      int64_t max_chunk, void *state, size_t state_bytes, int64_t *new_path, int64_t *new_states,
+                                      int64_t *new_lm_states, int64_t *new_tokens, int64_t *new_words, int64_t *new_frames,
+                                      int64_t *new_token_lengths, int64_t *new_word_lengths, int64_t *new_word_frames,
+                                      void *new_word_confidences, int flags, void *stream);
+int asg_beam_word_conf_window_advance_la(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                         const asg_word_lookahead *la, int beam_size, double beam_threshold, int64_t W, int64_t P,
+                                         int frame_tolerance, int64_t max_chunk, void *state, size_t state_bytes, int64_t *new_path,
+                                         int64_t *new_states, int64_t *new_lm_states, int64_t *new_tokens, int64_t *new_words,
+                                         int64_t *new_frames, int64_t *new_token_lengths, int64_t *new_word_lengths,
+                                         int64_t *new_word_frames, void *new_word_confidences, int flags, void *stream);
+int asg_beam_word_conf_window_result(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
+                                     int64_t W, int64_t P, int frame_tolerance, int64_t max_chunk, const void *state,
+                                     size_t state_bytes, int final, void *scores, int64_t *path, int64_t *tokens,
+                                     int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words,
+                                     int64_t *word_lengths, int64_t *frames, int64_t *committed, int64_t *status, int flags,
+                                     void *stream);
+int asg_beam_word_conf_window_result_la(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                        const asg_word_lookahead *la, int64_t B, int beam_size, int64_t W, int64_t P,
+                                        int frame_tolerance, int64_t max_chunk, const void *state, size_t state_bytes, int final,
+                                        void *scores, int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states,
+                                        int64_t *lm_states, int64_t *words, int64_t *word_lengths, int64_t *frames,
+                                        int64_t *committed, int64_t *status, int flags, void *stream);
+size_t asg_beam_word_conf_window_nbest_work_bytes(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype,
+                                                  int beam_size, int64_t W, int64_t P, int frame_tolerance, int64_t max_chunk,
+                                                  int nbest);
+int asg_beam_word_conf_window_nbest(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
+                                    int64_t W, int64_t P, int frame_tolerance, int64_t max_chunk, const void *state,
+                                    size_t state_bytes, int final, int nbest, void *work, size_t work_bytes, void *scores,
+                                    int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *lm_states,
+                                    int64_t *words, int64_t *word_lengths, int64_t *num_hyps, int64_t *frames, int64_t *committed,
+                                    int64_t *status, int flags, void *stream);
+int asg_beam_word_conf_window_nbest_la(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                       const asg_word_lookahead *la, int64_t B, int beam_size, int64_t W, int64_t P,
+                                       int frame_tolerance, int64_t max_chunk, const void *state, size_t state_bytes, int final,
+                                       int nbest, void *work, size_t work_bytes, void *scores, int64_t *path, int64_t *tokens,
+                                       int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words,
+                                       int64_t *word_lengths, int64_t *num_hyps, int64_t *frames, int64_t *committed,
+                                       int64_t *status, int flags, void *stream);
+int asg_beam_word_conf_window_confidence(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B,
+                                         int beam_size, int64_t W, int64_t P, int frame_tolerance, int64_t max_chunk, void *state,
+                                         size_t state_bytes, const void *transition, const int64_t *transition_strides, int final,
+                                         void *scores, int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states,
+                                         int64_t *lm_states, int64_t *words, int64_t *word_lengths, int64_t *word_frames,
+                                         void *word_confidences, void *normalisers, int64_t *frames, int64_t *committed,
+                                         int64_t *status, int flags, void *stream);
+int asg_beam_word_conf_window_confidence_la(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                            const asg_word_lookahead *la, int64_t B, int beam_size, int64_t W, int64_t P,
+                                            int frame_tolerance, int64_t max_chunk, void *state, size_t state_bytes,
+                                            const void *transition, const int64_t *transition_strides, int final, void *scores,
+                                            int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states,
+                                            int64_t *lm_states, int64_t *words, int64_t *word_lengths, int64_t *word_frames,
+                                            void *word_confidences, void *normalisers, int64_t *frames, int64_t *committed,
+                                            int64_t *status, int flags, void *stream);
+
 /* ---- whole-loss entry points (no counterpart in the reference's native layer: they fold the Python-side
  * `full - aligned` and reduction of asg.py:128,136-142 and their autograd into the kernels, so one ASGLoss
  * step is 2 + 2 kernel launches with no PyTorch glue kernels in between) ------------------------------------ */

@@ -54,7 +54,11 @@ SYMBOLS = ["asg_hip_version", "asg_hip_strerror", "asg_ctx_create", "asg_ctx_des
            "asg_beam_word_conf_stream_state_bytes", "asg_beam_word_conf_stream_reset", "asg_beam_word_conf_stream_advance",
            "asg_beam_word_conf_stream_advance_la", "asg_beam_word_conf_stream_result", "asg_beam_word_conf_stream_result_la",
            "asg_beam_word_conf_stream_nbest_work_bytes", "asg_beam_word_conf_stream_nbest", "asg_beam_word_conf_stream_nbest_la",
-           "asg_beam_word_conf_stream_confidence", "asg_beam_word_conf_stream_confidence_la"]
+           "asg_beam_word_conf_stream_confidence", "asg_beam_word_conf_stream_confidence_la",
+           "asg_beam_word_conf_window_state_bytes", "asg_beam_word_conf_window_reset", "asg_beam_word_conf_window_advance",
+           "asg_beam_word_conf_window_advance_la", "asg_beam_word_conf_window_result", "asg_beam_word_conf_window_result_la",
+           "asg_beam_word_conf_window_nbest_work_bytes", "asg_beam_word_conf_window_nbest", "asg_beam_word_conf_window_nbest_la",
+           "asg_beam_word_conf_window_confidence", "asg_beam_word_conf_window_confidence_la"]
 ABI_VERSION = 230        # include/asg_hip.h: ASG_HIP_VERSION this package was written against
 
 
@@ -215,11 +219,25 @@ def lib():
     L.asg_beam_word_conf_stream_nbest.argtypes = L.asg_beam_word_stream_nbest.argtypes
     L.asg_beam_word_conf_stream_confidence.argtypes = [vp, bp, wp, i64, ci, i64, vp, sz, vp, ctypes.POINTER(i64), ci,
                                                        ci] + [vp] * 13 + [ci, vp]
+    # the lattice-keeping word window: the plain word window's calls with frame_tolerance and max_chunk behind W and P
+    wshape = [i64, i64, ci, i64]
+    L.asg_beam_word_conf_window_state_bytes.restype = sz
+    L.asg_beam_word_conf_window_state_bytes.argtypes = [bp, wp, i64, ci, ci] + wshape
+    L.asg_beam_word_conf_window_reset.argtypes = [vp, bp, wp, i64, ci] + wshape + [vp, sz, vp, ci, vp]
+    L.asg_beam_word_conf_window_advance.argtypes = [vp, pp, bp, wp, ci, ctypes.c_double] + wshape + [vp, sz] + [vp] * 10 + [ci, vp]
+    L.asg_beam_word_conf_window_result.argtypes = [vp, bp, wp, i64, ci] + wshape + [vp, sz, ci] + [vp] * 11 + [ci, vp]
+    L.asg_beam_word_conf_window_nbest_work_bytes.restype = sz
+    L.asg_beam_word_conf_window_nbest_work_bytes.argtypes = [bp, wp, i64, ci, ci] + wshape + [ci]
+    L.asg_beam_word_conf_window_nbest.argtypes = [vp, bp, wp, i64, ci] + wshape + [vp, sz, ci, ci, vp, sz] + [vp] * 12 + [ci, vp]
+    L.asg_beam_word_conf_window_confidence.argtypes = ([vp, bp, wp, i64, ci] + wshape + [vp, sz, vp, ctypes.POINTER(i64), ci] +
+                                                       [vp] * 14 + [ci, vp])
     for name in ("asg_beam_word_stream_advance", "asg_beam_word_stream_result", "asg_beam_word_window_advance",
                  "asg_beam_word_window_result", "asg_beam_decode_words_nbest",
                  "asg_beam_word_stream_nbest", "asg_beam_word_window_nbest", "asg_beam_word_conf_stream_advance",
                  "asg_beam_word_conf_stream_result", "asg_beam_word_conf_stream_nbest",
-                 "asg_beam_word_conf_stream_confidence"):                          # the plain call with the look-ahead behind the LM
+                 "asg_beam_word_conf_stream_confidence", "asg_beam_word_conf_window_advance",
+                 "asg_beam_word_conf_window_result", "asg_beam_word_conf_window_nbest",
+                 "asg_beam_word_conf_window_confidence"):                          # the plain call with the look-ahead behind the LM
         plain = getattr(L, name).argtypes
         at = plain.index(wp) + 1
         getattr(L, name + "_la").argtypes = plain[:at] + [ctypes.POINTER(AsgWordLookahead)] + plain[at:]

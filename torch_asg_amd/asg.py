@@ -2161,11 +2161,14 @@ class ASGLoss(nn.Module):
                                 token_score, self.transition.dtype, self.transition.device, keep_lattice, frame_tolerance, max_chunk)
 
     def beam_word_window_stream(self, lexicon, word_lm, batch_size, window, commit_every=None, beam_size=256,
-                                beam_threshold=float("inf"), lm_weight=1.0, word_score=0.0, token_score=0.0, lookahead=None):
+                                beam_threshold=float("inf"), lm_weight=1.0, word_score=0.0, token_score=0.0, lookahead=None,
+                                keep_lattice=False, frame_tolerance=0, max_chunk=None):
         """A streaming beam decoder with a lexicon and a word n-gram LM in bounded memory under this module's transition matrix
-        (read again at every chunk): see `torch_asg_amd.BeamWordWindowStream`."""
+        (read again at every chunk): see `torch_asg_amd.BeamWordWindowStream`.  `keep_lattice=True`: `advance` also returns a
+        confidence and an end frame for every word it commits, and the stream has `result_confidence`."""
         return BeamWordWindowStream(self.transition, lexicon, word_lm, batch_size, window, commit_every, beam_size, beam_threshold,
-                                    lm_weight, word_score, token_score, self.transition.dtype, self.transition.device, lookahead)
+                                    lm_weight, word_score, token_score, self.transition.dtype, self.transition.device, lookahead,
+                                    keep_lattice, frame_tolerance, max_chunk)
 
     def graph_loss(self, inputs, targets, graph, input_lengths=None, target_lengths=None, lm_weight=1.0, token_score=0.0,
                    max_work_bytes=1 << 30):
@@ -2324,4 +2327,5 @@ class ASGLoss(nn.Module):
 from .stream import (BeamStream, BeamStreamResult, BeamWordStream, BeamWordStreamResult, BeamWordStreamNbest,  # noqa: E402,F401
                      BeamWindowStream, BeamWindowCommit, BeamWindowResult, BeamWordWindowStream, BeamWordWindowCommit,
                      BeamWordWindowResult, BeamStreamNbest, BeamWindowNbest, BeamWordWindowNbest, BeamStreamConfidence,
-                     BeamWordStreamConfidence, BeamWindowConfCommit, BeamWindowConfidence)
+                     BeamWordStreamConfidence, BeamWindowConfCommit, BeamWindowConfidence, BeamWordWindowConfCommit,
+                     BeamWordWindowConfidence)

@@ -1366,6 +1366,56 @@ static size_t beam_word_window_bytes(const asg_token_graph_beam *gb, int64_t B, 
                                         beam_word_cap(beam_size, gb->max_out, (int) gb->num_start));
 }
 
+// ONE host path for the calls a word window stream has with a plain state (asg_beam_word_window_*) and with a lattice-keeping one
+// (asg_beam_word_conf_window_*): reset, advance, result, n-best, each with a look-ahead or without.  `cw`, the two parameters that
+// size the lattice ring, chooses the state's checks, its bytes, the stride of a slot and the advance's launches; NULL: plain.
+struct WordWinConf {
+    int tol;
+    int64_t C;
+};
+static int check_lattice(const asg_problem *p, int K, bool (*fits)(int, int, int));
+
+// The lattice-keeping word window: the checks of a plain word window state, the two parameters that size the ring, then those of
+// the word confidences through a problem of W frames without targets (its emissions are not read).
+static int check_beam_word_conf_window(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype, int beam_size,
+                                       int64_t W, int64_t P, int frame_tolerance, int64_t max_chunk) {
+    int rc = check_beam_word_window(gb, lm, B, dtype, beam_size, W, P);
+    if (rc) return rc;
+    if (frame_tolerance < 0 || max_chunk < 1) return ASG_ERR_INVALID;
+    if (frame_tolerance > kBeamWordConfMaxTol) return ASG_ERR_UNSUPPORTED;
+    if (W + frame_tolerance + 1 + max_chunk > (int64_t) 0x7FFFFFFF) return ASG_ERR_UNSUPPORTED;      // the rows of the ring
+    if (max_chunk / P + 1 > kBeamConfWindowMaxLog) return ASG_ERR_UNSUPPORTED;      // the log's entries are the pull's grid rows
+    asg_problem q{};
+    q.inputs = gb; q.transition = gb;
+    q.T = W; q.B = B; q.N = gb->graph->N; q.S = 1; q.dtype = dtype;
+    return check_lattice(&q, beam_size, beam_word_loss_fits);
+}
+
+static size_t beam_word_conf_window_bytes(const asg_token_graph_beam *gb, int64_t B, int dtype, int beam_size, int64_t W, int64_t P,
+                                          int frame_tolerance, int64_t max_chunk) {
+    return beam_word_conf_window_state_bytes(dtype == ASG_DTYPE_F64 ? 8 : 4, (int) W, (int) P, frame_tolerance, (int) max_chunk,
+                                             (int) B, beam_size, beam_word_cap(beam_size, gb->max_out, (int) gb->num_start),
+                                             (int) gb->graph->N);
+}
+
+static int check_word_window_state(const asg_token_graph_beam *gb, const asg_word_lm *lm, const WordWinConf *cw, int64_t B,
+                                   int dtype, int beam_size, int64_t W, int64_t P) {
+    return cw ? check_beam_word_conf_window(gb, lm, B, dtype, beam_size, W, P, cw->tol, cw->C)
+              : check_beam_word_window(gb, lm, B, dtype, beam_size, W, P);
+}
+
+static size_t word_window_state_bytes(const asg_token_graph_beam *gb, const WordWinConf *cw, int64_t B, int dtype, int beam_size,
+                                      int64_t W, int64_t P) {
+    return cw ? beam_word_conf_window_bytes(gb, B, dtype, beam_size, W, P, cw->tol, cw->C)
+              : beam_word_window_bytes(gb, B, dtype, beam_size, W);
+}
+
+// the stride of a slot for the launchers: 0 (their own layout's) for a plain state
+static size_t word_window_state_per(const asg_token_graph_beam *gb, const WordWinConf *cw, int dtype, int beam_size, int64_t W,
+                                    int64_t P) {
+    return cw ? beam_word_conf_window_bytes(gb, 1, dtype, beam_size, W, P, cw->tol, cw->C) : 0;
+}
+
 // The number of automaton states word_of_state is indexed by, as the kernels clamp to it.
 static int word_lm_states(const asg_word_lm *lm) { return lm->S < ((int64_t) 1 << 31) - 1 ? (int) lm->S : (1 << 31) - 1; }
 
@@ -1375,35 +1425,48 @@ size_t asg_beam_word_window_state_bytes(const asg_token_graph_beam *gb, const as
     return beam_word_window_bytes(gb, B, dtype, beam_size, W);
 }
 
+static int beam_word_window_reset(const asg_token_graph_beam *gb, const asg_word_lm *lm, const WordWinConf *cw, int64_t B,
+                                  int beam_size, int64_t W, int64_t P, void *state, size_t state_bytes, const uint8_t *mask,
+                                  void *stream) {
+    if (!gb || !gb->graph) return ASG_ERR_INVALID;
+    const int dtype = gb->graph->dtype;
+    int rc = check_word_window_state(gb, lm, cw, B, dtype, beam_size, W, P);
+    if (rc) return rc;
+    if (!state) return ASG_ERR_INVALID;
+    if (state_bytes < word_window_state_bytes(gb, cw, B, dtype, beam_size, W, P)) return ASG_ERR_WORKSPACE;
+    return hip_status(launch_beam_word_window_reset(dtype == ASG_DTYPE_F64 ? 8 : 4, to_beam_graph_args(gb), beam_size, (int) W,
+                                                    (int) B, state, mask, (hipStream_t) stream,
+                                                    word_window_state_per(gb, cw, dtype, beam_size, W, P)));
+}
+
 int asg_beam_word_window_reset(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
                                int64_t W, int64_t P, void *state, size_t state_bytes, const uint8_t *mask, int flags, void *stream) {
     (void) ctx; (void) flags;
-    if (!gb || !gb->graph) return ASG_ERR_INVALID;
-    const int dtype = gb->graph->dtype;
-    int rc = check_beam_word_window(gb, lm, B, dtype, beam_size, W, P);
-    if (rc) return rc;
-    if (!state) return ASG_ERR_INVALID;
-    if (state_bytes < beam_word_window_bytes(gb, B, dtype, beam_size, W)) return ASG_ERR_WORKSPACE;
-    return hip_status(launch_beam_word_window_reset(dtype == ASG_DTYPE_F64 ? 8 : 4, to_beam_graph_args(gb), beam_size, (int) W,
-                                                    (int) B, state, mask, (hipStream_t) stream));
+    return beam_word_window_reset(gb, lm, nullptr, B, beam_size, W, P, state, state_bytes, mask, stream);
 }
 
+// (cw: new_word_frames and new_word_confidences are outputs too, the chunk is bounded, and the catch-up reads the transition
+// also when no frame comes)
 static int beam_word_window_advance(const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
-                                    const asg_word_lookahead *la, bool with_la, int beam_size, double beam_threshold, int64_t W,
+                                    const asg_word_lookahead *la, bool with_la, const WordWinConf *cw, int beam_size,
+                                    double beam_threshold, int64_t W,
                                     int64_t P, void *state, size_t state_bytes, int64_t *new_path, int64_t *new_states,
                                     int64_t *new_lm_states, int64_t *new_tokens, int64_t *new_words, int64_t *new_frames,
-                                    int64_t *new_token_lengths, int64_t *new_word_lengths, void *stream) {
+                                    int64_t *new_token_lengths, int64_t *new_word_lengths, int64_t *new_word_frames,
+                                    void *new_word_confidences, void *stream) {
     if (!p) return ASG_ERR_INVALID;
-    int rc = check_beam_word_window(gb, lm, p->B, p->dtype, beam_size, W, P);
+    int rc = check_word_window_state(gb, lm, cw, p->B, p->dtype, beam_size, W, P);
     if (rc) return rc;
     if (with_la && (rc = check_word_lookahead(p->dtype, lm, la)) != ASG_OK) return rc;
     if (p->T < 0 || p->N != gb->graph->N) return ASG_ERR_INVALID;
+    if (cw && p->T > cw->C) return ASG_ERR_UNSUPPORTED;                    // the ring holds max_chunk frames behind an attempt
     if (p->T > 0 && (rc = check_beam_words(p, gb, lm, beam_size)) != ASG_OK) return rc;
+    if (cw && !p->transition) return ASG_ERR_INVALID;
     if (!(beam_threshold >= 0.0)) return ASG_ERR_INVALID;                  // negative or NaN
     if (!state || !new_path || !new_states || !new_lm_states || !new_tokens || !new_words || !new_frames || !new_token_lengths ||
-        !new_word_lengths)
+        !new_word_lengths || (cw && (!new_word_frames || !new_word_confidences)))
         return ASG_ERR_INVALID;
-    if (state_bytes < beam_word_window_bytes(gb, p->B, p->dtype, beam_size, W)) return ASG_ERR_WORKSPACE;
+    if (state_bytes < word_window_state_bytes(gb, cw, p->B, p->dtype, beam_size, W, P)) return ASG_ERR_WORKSPACE;
     const Problem Pr = to_problem(p);                                      // (no frame: the launch still writes the empty outputs)
     const GraphArgs G = to_graph_args(gb->graph);
     const BeamGraphArgs BG = to_beam_graph_args(gb);
@@ -1414,6 +1477,16 @@ static int beam_word_window_advance(const asg_problem *p, const asg_token_graph_
     long long *tl = (long long *) new_token_lengths, *wl = (long long *) new_word_lengths;
     const WordLookArgs LA = with_la ? to_word_look_args(la) : WordLookArgs{};
     const WordLookArgs *look = with_la ? &LA : nullptr;
+    if (cw) {
+        long long *wf = (long long *) new_word_frames;
+        return hip_status(ASG_DISPATCH(p,
+            launch_beam_word_conf_window_advance<float>(Pr, G, BG, LM, look, S, beam_size, beam_threshold, (int) W, (int) P, cw->tol,
+                                                        (int) cw->C, state, np, ns, nl, nt, nw, nf, tl, wl, wf, new_word_confidences,
+                                                        (hipStream_t) stream),
+            launch_beam_word_conf_window_advance<double>(Pr, G, BG, LM, look, S, beam_size, beam_threshold, (int) W, (int) P, cw->tol,
+                                                         (int) cw->C, state, np, ns, nl, nt, nw, nf, tl, wl, wf, new_word_confidences,
+                                                         (hipStream_t) stream)));
+    }
     return hip_status(ASG_DISPATCH(p, launch_beam_word_window_advance<float>(Pr, G, BG, LM, look, S, beam_size, beam_threshold,
                                                                              (int) W, (int) P, state, np, ns, nl, nt, nw, nf, tl,
                                                                              wl, (hipStream_t) stream),
@@ -1428,9 +1501,9 @@ int asg_beam_word_window_advance(asg_ctx *ctx, const asg_problem *p, const asg_t
                                  int64_t *new_words, int64_t *new_frames, int64_t *new_token_lengths, int64_t *new_word_lengths,
                                  int flags, void *stream) {
     (void) ctx; (void) flags;
-    return beam_word_window_advance(p, gb, lm, nullptr, false, beam_size, beam_threshold, W, P, state, state_bytes, new_path,
-                                    new_states, new_lm_states, new_tokens, new_words, new_frames, new_token_lengths,
-                                    new_word_lengths, stream);
+    return beam_word_window_advance(p, gb, lm, nullptr, false, nullptr, beam_size, beam_threshold, W, P, state, state_bytes,
+                                    new_path, new_states, new_lm_states, new_tokens, new_words, new_frames, new_token_lengths,
+                                    new_word_lengths, nullptr, nullptr, stream);
 }
 
 int asg_beam_word_window_advance_la(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
@@ -1439,24 +1512,27 @@ int asg_beam_word_window_advance_la(asg_ctx *ctx, const asg_problem *p, const as
                                     int64_t *new_lm_states, int64_t *new_tokens, int64_t *new_words, int64_t *new_frames,
                                     int64_t *new_token_lengths, int64_t *new_word_lengths, int flags, void *stream) {
     (void) ctx; (void) flags;
-    return beam_word_window_advance(p, gb, lm, la, true, beam_size, beam_threshold, W, P, state, state_bytes, new_path, new_states,
-                                    new_lm_states, new_tokens, new_words, new_frames, new_token_lengths, new_word_lengths, stream);
+    return beam_word_window_advance(p, gb, lm, la, true, nullptr, beam_size, beam_threshold, W, P, state, state_bytes, new_path,
+                                    new_states, new_lm_states, new_tokens, new_words, new_frames, new_token_lengths,
+                                    new_word_lengths, nullptr, nullptr, stream);
 }
 
 static int beam_word_window_result(const asg_token_graph_beam *gb, const asg_word_lm *lm, const asg_word_lookahead *la, bool with_la,
-                                   int64_t B, int beam_size, int64_t W, int64_t P, const void *state, size_t state_bytes, int final,
+                                   const WordWinConf *cw, int64_t B, int beam_size, int64_t W, int64_t P, const void *state,
+                                   size_t state_bytes, int final,
                                    void *scores, int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states,
                                    int64_t *lm_states, int64_t *words, int64_t *word_lengths, int64_t *frames, int64_t *committed,
                                    int64_t *status, void *stream) {
     if (!gb || !gb->graph) return ASG_ERR_INVALID;
     const asg_token_graph *g = gb->graph;
-    int rc = check_beam_word_window(gb, lm, B, g->dtype, beam_size, W, P);
+    int rc = check_word_window_state(gb, lm, cw, B, g->dtype, beam_size, W, P);
     if (rc) return rc;
     if (with_la && (rc = check_word_lookahead(g->dtype, lm, la)) != ASG_OK) return rc;
     if (!state || !scores || !path || !tokens || !token_lengths || !states || !lm_states || !words || !word_lengths || !frames ||
         !committed || !status)
         return ASG_ERR_INVALID;
-    if (state_bytes < beam_word_window_bytes(gb, B, g->dtype, beam_size, W)) return ASG_ERR_WORKSPACE;
+    if (state_bytes < word_window_state_bytes(gb, cw, B, g->dtype, beam_size, W, P)) return ASG_ERR_WORKSPACE;
+    const size_t per = word_window_state_per(gb, cw, g->dtype, beam_size, W, P);
     const GraphArgs G = to_graph_args(g);
     const BeamGraphArgs BG = to_beam_graph_args(gb);
     const WordLmArgs LM = to_word_lm_args(lm);
@@ -1468,10 +1544,10 @@ static int beam_word_window_result(const asg_token_graph_beam *gb, const asg_wor
     const WordLookArgs *look = with_la ? &LA : nullptr;
     return hip_status(ASG_DISPATCH(g, launch_beam_word_window_result<float>(G, BG, LM, look, S, beam_size, (int) W, (int) B, state,
                                                                             final, scores, pa, tk, tl, st, ls, wd, wl, fr, co, su,
-                                                                            (hipStream_t) stream),
+                                                                            (hipStream_t) stream, per),
                                    launch_beam_word_window_result<double>(G, BG, LM, look, S, beam_size, (int) W, (int) B, state,
                                                                           final, scores, pa, tk, tl, st, ls, wd, wl, fr, co, su,
-                                                                          (hipStream_t) stream)));
+                                                                          (hipStream_t) stream, per)));
 }
 
 int asg_beam_word_window_result(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
@@ -1480,7 +1556,7 @@ int asg_beam_word_window_result(asg_ctx *ctx, const asg_token_graph_beam *gb, co
                                 int64_t *word_lengths, int64_t *frames, int64_t *committed, int64_t *status, int flags,
                                 void *stream) {
     (void) ctx; (void) flags;
-    return beam_word_window_result(gb, lm, nullptr, false, B, beam_size, W, P, state, state_bytes, final, scores, path, tokens,
+    return beam_word_window_result(gb, lm, nullptr, false, nullptr, B, beam_size, W, P, state, state_bytes, final, scores, path, tokens,
                                    token_lengths, states, lm_states, words, word_lengths, frames, committed, status, stream);
 }
 
@@ -1491,13 +1567,13 @@ int asg_beam_word_window_result_la(asg_ctx *ctx, const asg_token_graph_beam *gb,
                                    int64_t *word_lengths, int64_t *frames, int64_t *committed, int64_t *status, int flags,
                                    void *stream) {
     (void) ctx; (void) flags;
-    return beam_word_window_result(gb, lm, la, true, B, beam_size, W, P, state, state_bytes, final, scores, path, tokens,
+    return beam_word_window_result(gb, lm, la, true, nullptr, B, beam_size, W, P, state, state_bytes, final, scores, path, tokens,
                                    token_lengths, states, lm_states, words, word_lengths, frames, committed, status, stream);
 }
 
-static int check_beam_word_window_nbest(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype, int beam_size,
-                                        int64_t W, int64_t P, int nbest) {
-    int rc = check_beam_word_window(gb, lm, B, dtype, beam_size, W, P);
+static int check_beam_word_window_nbest(const asg_token_graph_beam *gb, const asg_word_lm *lm, const WordWinConf *cw, int64_t B,
+                                        int dtype, int beam_size, int64_t W, int64_t P, int nbest) {
+    int rc = check_word_window_state(gb, lm, cw, B, dtype, beam_size, W, P);
     if (rc) return rc;
     if (nbest < 1) return ASG_ERR_INVALID;
     if (nbest > kBeamMaxNbest) return ASG_ERR_UNSUPPORTED;
@@ -1506,27 +1582,29 @@ static int check_beam_word_window_nbest(const asg_token_graph_beam *gb, const as
 
 size_t asg_beam_word_window_nbest_work_bytes(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype,
                                              int beam_size, int64_t W, int64_t P, int nbest) {
-    if (check_beam_word_window_nbest(gb, lm, B, dtype, beam_size, W, P, nbest) != ASG_OK) return 0;
+    if (check_beam_word_window_nbest(gb, lm, nullptr, B, dtype, beam_size, W, P, nbest) != ASG_OK) return 0;
     return beam_word_window_nbest_work_bytes((int) W, (int) B, beam_size, nbest);
 }
 
 // asg_beam_word_window_nbest with a look-ahead (`with_la`, checked behind the LM) or without one.
 static int beam_word_window_nbest(const asg_token_graph_beam *gb, const asg_word_lm *lm, const asg_word_lookahead *la, bool with_la,
-                                  int64_t B, int beam_size, int64_t W, int64_t P, const void *state, size_t state_bytes, int final,
+                                  const WordWinConf *cw, int64_t B, int beam_size, int64_t W, int64_t P, const void *state,
+                                  size_t state_bytes, int final,
                                   int nbest, void *work, size_t work_bytes, void *scores, int64_t *path, int64_t *tokens,
                                   int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words,
                                   int64_t *word_lengths, int64_t *num_hyps, int64_t *frames, int64_t *committed, int64_t *status,
                                   void *stream) {
     if (!gb || !gb->graph) return ASG_ERR_INVALID;
     const asg_token_graph *g = gb->graph;
-    int rc = check_beam_word_window_nbest(gb, lm, B, g->dtype, beam_size, W, P, nbest);
+    int rc = check_beam_word_window_nbest(gb, lm, cw, B, g->dtype, beam_size, W, P, nbest);
     if (rc) return rc;
     if (with_la && (rc = check_word_lookahead(g->dtype, lm, la)) != ASG_OK) return rc;
     if (!state || !work || !scores || !tokens || !token_lengths || !words || !word_lengths || !num_hyps || !frames || !committed ||
         !status)
         return ASG_ERR_INVALID;
-    if (state_bytes < beam_word_window_bytes(gb, B, g->dtype, beam_size, W)) return ASG_ERR_WORKSPACE;
+    if (state_bytes < word_window_state_bytes(gb, cw, B, g->dtype, beam_size, W, P)) return ASG_ERR_WORKSPACE;
     if (work_bytes < beam_word_window_nbest_work_bytes((int) W, (int) B, beam_size, nbest)) return ASG_ERR_WORKSPACE;
+    const size_t per = word_window_state_per(gb, cw, g->dtype, beam_size, W, P);
     const GraphArgs G = to_graph_args(g);
     const BeamGraphArgs BG = to_beam_graph_args(gb);
     const WordLmArgs LM = to_word_lm_args(lm);
@@ -1538,10 +1616,10 @@ static int beam_word_window_nbest(const asg_token_graph_beam *gb, const asg_word
     const WordLookArgs *look = with_la ? &LA : nullptr;
     return hip_status(ASG_DISPATCH(g, launch_beam_word_window_nbest<float>(G, BG, LM, look, S, beam_size, (int) W, (int) B, state,
                                                                            final, nbest, work, scores, pa, tk, tl, st, ls, wd, wl,
-                                                                           nh, fr, co, su, (hipStream_t) stream),
+                                                                           nh, fr, co, su, (hipStream_t) stream, per),
                                    launch_beam_word_window_nbest<double>(G, BG, LM, look, S, beam_size, (int) W, (int) B, state,
                                                                          final, nbest, work, scores, pa, tk, tl, st, ls, wd, wl,
-                                                                         nh, fr, co, su, (hipStream_t) stream)));
+                                                                         nh, fr, co, su, (hipStream_t) stream, per)));
 }
 
 int asg_beam_word_window_nbest(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
@@ -1550,7 +1628,7 @@ int asg_beam_word_window_nbest(asg_ctx *ctx, const asg_token_graph_beam *gb, con
                                int64_t *states, int64_t *lm_states, int64_t *words, int64_t *word_lengths, int64_t *num_hyps,
                                int64_t *frames, int64_t *committed, int64_t *status, int flags, void *stream) {
     (void) ctx; (void) flags;
-    return beam_word_window_nbest(gb, lm, nullptr, false, B, beam_size, W, P, state, state_bytes, final, nbest, work, work_bytes,
+    return beam_word_window_nbest(gb, lm, nullptr, false, nullptr, B, beam_size, W, P, state, state_bytes, final, nbest, work, work_bytes,
                                   scores, path, tokens, token_lengths, states, lm_states, words, word_lengths, num_hyps, frames,
                                   committed, status, stream);
 }
@@ -1562,7 +1640,7 @@ int asg_beam_word_window_nbest_la(asg_ctx *ctx, const asg_token_graph_beam *gb, 
                                   int64_t *words, int64_t *word_lengths, int64_t *num_hyps, int64_t *frames, int64_t *committed,
                                   int64_t *status, int flags, void *stream) {
     (void) ctx; (void) flags;
-    return beam_word_window_nbest(gb, lm, la, true, B, beam_size, W, P, state, state_bytes, final, nbest, work, work_bytes, scores,
+    return beam_word_window_nbest(gb, lm, la, true, nullptr, B, beam_size, W, P, state, state_bytes, final, nbest, work, work_bytes, scores,
                                   path, tokens, token_lengths, states, lm_states, words, word_lengths, num_hyps, frames, committed,
                                   status, stream);
 }
@@ -2344,6 +2422,175 @@ int asg_beam_word_conf_stream_confidence_la(asg_ctx *ctx, const asg_token_graph_
                                             transition_strides, final, frame_tolerance, scores, path, tokens, token_lengths, states,
                                             lm_states, words, word_lengths, word_frames, word_confidences, normalisers, frames,
                                             status, stream);
+}
+
+// The lattice-keeping word window stream: reset, advance, result and n-best are the plain word window's host path
+// (beam_word_window_reset and its siblings) with the two parameters that size the ring.
+size_t asg_beam_word_conf_window_state_bytes(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype,
+                                             int beam_size, int64_t W, int64_t P, int frame_tolerance, int64_t max_chunk) {
+    if (check_beam_word_conf_window(gb, lm, B, dtype, beam_size, W, P, frame_tolerance, max_chunk) != ASG_OK) return 0;
+    return beam_word_conf_window_bytes(gb, B, dtype, beam_size, W, P, frame_tolerance, max_chunk);
+}
+
+int asg_beam_word_conf_window_reset(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
+                                    int64_t W, int64_t P, int frame_tolerance, int64_t max_chunk, void *state, size_t state_bytes,
+                                    const uint8_t *mask, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    const WordWinConf cw{frame_tolerance, max_chunk};
+    return beam_word_window_reset(gb, lm, &cw, B, beam_size, W, P, state, state_bytes, mask, stream);
+}
+
+int asg_beam_word_conf_window_advance(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                      int beam_size, double beam_threshold, int64_t W, int64_t P, int frame_tolerance,
+                                      int64_t max_chunk, void *state, size_t state_bytes, int64_t *new_path, int64_t *new_states,
+                                      int64_t *new_lm_states, int64_t *new_tokens, int64_t *new_words, int64_t *new_frames,
+                                      int64_t *new_token_lengths, int64_t *new_word_lengths, int64_t *new_word_frames,
+                                      void *new_word_confidences, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    const WordWinConf cw{frame_tolerance, max_chunk};
+    return beam_word_window_advance(p, gb, lm, nullptr, false, &cw, beam_size, beam_threshold, W, P, state, state_bytes, new_path,
+                                    new_states, new_lm_states, new_tokens, new_words, new_frames, new_token_lengths,
+                                    new_word_lengths, new_word_frames, new_word_confidences, stream);
+}
+
+int asg_beam_word_conf_window_advance_la(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                         const asg_word_lookahead *la, int beam_size, double beam_threshold, int64_t W, int64_t P,
+                                         int frame_tolerance, int64_t max_chunk, void *state, size_t state_bytes, int64_t *new_path,
+                                         int64_t *new_states, int64_t *new_lm_states, int64_t *new_tokens, int64_t *new_words,
+                                         int64_t *new_frames, int64_t *new_token_lengths, int64_t *new_word_lengths,
+                                         int64_t *new_word_frames, void *new_word_confidences, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    const WordWinConf cw{frame_tolerance, max_chunk};
+    return beam_word_window_advance(p, gb, lm, la, true, &cw, beam_size, beam_threshold, W, P, state, state_bytes, new_path,
+                                    new_states, new_lm_states, new_tokens, new_words, new_frames, new_token_lengths,
+                                    new_word_lengths, new_word_frames, new_word_confidences, stream);
+}
+
+int asg_beam_word_conf_window_result(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
+                                     int64_t W, int64_t P, int frame_tolerance, int64_t max_chunk, const void *state,
+                                     size_t state_bytes, int final, void *scores, int64_t *path, int64_t *tokens,
+                                     int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words,
+                                     int64_t *word_lengths, int64_t *frames, int64_t *committed, int64_t *status, int flags,
+                                     void *stream) {
+    (void) ctx; (void) flags;
+    const WordWinConf cw{frame_tolerance, max_chunk};
+    return beam_word_window_result(gb, lm, nullptr, false, &cw, B, beam_size, W, P, state, state_bytes, final, scores, path, tokens,
+                                   token_lengths, states, lm_states, words, word_lengths, frames, committed, status, stream);
+}
+
+int asg_beam_word_conf_window_result_la(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                        const asg_word_lookahead *la, int64_t B, int beam_size, int64_t W, int64_t P,
+                                        int frame_tolerance, int64_t max_chunk, const void *state, size_t state_bytes, int final,
+                                        void *scores, int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states,
+                                        int64_t *lm_states, int64_t *words, int64_t *word_lengths, int64_t *frames,
+                                        int64_t *committed, int64_t *status, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    const WordWinConf cw{frame_tolerance, max_chunk};
+    return beam_word_window_result(gb, lm, la, true, &cw, B, beam_size, W, P, state, state_bytes, final, scores, path, tokens,
+                                   token_lengths, states, lm_states, words, word_lengths, frames, committed, status, stream);
+}
+
+size_t asg_beam_word_conf_window_nbest_work_bytes(const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int dtype,
+                                                  int beam_size, int64_t W, int64_t P, int frame_tolerance, int64_t max_chunk,
+                                                  int nbest) {
+    const WordWinConf cw{frame_tolerance, max_chunk};
+    if (check_beam_word_window_nbest(gb, lm, &cw, B, dtype, beam_size, W, P, nbest) != ASG_OK) return 0;
+    return beam_word_window_nbest_work_bytes((int) W, (int) B, beam_size, nbest);
+}
+
+int asg_beam_word_conf_window_nbest(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,
+                                    int64_t W, int64_t P, int frame_tolerance, int64_t max_chunk, const void *state,
+                                    size_t state_bytes, int final, int nbest, void *work, size_t work_bytes, void *scores,
+                                    int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *lm_states,
+                                    int64_t *words, int64_t *word_lengths, int64_t *num_hyps, int64_t *frames, int64_t *committed,
+                                    int64_t *status, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    const WordWinConf cw{frame_tolerance, max_chunk};
+    return beam_word_window_nbest(gb, lm, nullptr, false, &cw, B, beam_size, W, P, state, state_bytes, final, nbest, work, work_bytes,
+                                  scores, path, tokens, token_lengths, states, lm_states, words, word_lengths, num_hyps, frames,
+                                  committed, status, stream);
+}
+
+int asg_beam_word_conf_window_nbest_la(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                       const asg_word_lookahead *la, int64_t B, int beam_size, int64_t W, int64_t P,
+                                       int frame_tolerance, int64_t max_chunk, const void *state, size_t state_bytes, int final,
+                                       int nbest, void *work, size_t work_bytes, void *scores, int64_t *path, int64_t *tokens,
+                                       int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words,
+                                       int64_t *word_lengths, int64_t *num_hyps, int64_t *frames, int64_t *committed,
+                                       int64_t *status, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    const WordWinConf cw{frame_tolerance, max_chunk};
+    return beam_word_window_nbest(gb, lm, la, true, &cw, B, beam_size, W, P, state, state_bytes, final, nbest, work, work_bytes,
+                                  scores, path, tokens, token_lengths, states, lm_states, words, word_lengths, num_hyps, frames,
+                                  committed, status, stream);
+}
+
+// The tail's confidences: the plain result kernel (with the look-ahead the state was advanced with), then the tail kernel.
+static int beam_word_conf_window_confidence(const asg_token_graph_beam *gb, const asg_word_lm *lm, const asg_word_lookahead *la,
+                                            bool with_la, int64_t B, int beam_size, int64_t W, int64_t P, int frame_tolerance,
+                                            int64_t max_chunk, void *state, size_t state_bytes, const void *transition,
+                                            const int64_t *transition_strides, int final, void *scores, int64_t *path,
+                                            int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *lm_states,
+                                            int64_t *words, int64_t *word_lengths, int64_t *word_frames, void *word_confidences,
+                                            void *normalisers, int64_t *frames, int64_t *committed, int64_t *status, void *stream) {
+    if (!gb || !gb->graph) return ASG_ERR_INVALID;
+    const asg_token_graph *g = gb->graph;
+    int rc = check_beam_word_conf_window(gb, lm, B, g->dtype, beam_size, W, P, frame_tolerance, max_chunk);
+    if (rc) return rc;
+    if (with_la && (rc = check_word_lookahead(g->dtype, lm, la)) != ASG_OK) return rc;
+    if (!state || !transition || !transition_strides || !scores || !path || !tokens || !token_lengths || !states || !lm_states ||
+        !words || !word_lengths || !word_frames || !word_confidences || !normalisers || !frames || !committed || !status)
+        return ASG_ERR_INVALID;
+    if (state_bytes < beam_word_conf_window_bytes(gb, B, g->dtype, beam_size, W, P, frame_tolerance, max_chunk))
+        return ASG_ERR_WORKSPACE;
+    Problem Pr{};
+    Pr.transition = transition; Pr.ts0 = transition_strides[0]; Pr.ts1 = transition_strides[1];
+    Pr.T = (int) W; Pr.B = (int) B; Pr.N = g->N; Pr.S = 1;
+    const GraphArgs G = to_graph_args(g);
+    const BeamGraphArgs BG = to_beam_graph_args(gb);
+    const WordLmArgs LM = to_word_lm_args(lm);
+    const int S = word_lm_states(lm);
+    const WordLookArgs LA = with_la ? to_word_look_args(la) : WordLookArgs{};
+    const WordLookArgs *look = with_la ? &LA : nullptr;
+    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
+    long long *ls = (long long *) lm_states, *wd = (long long *) words, *wl = (long long *) word_lengths;
+    long long *wf = (long long *) word_frames, *fr = (long long *) frames, *co = (long long *) committed, *su = (long long *) status;
+    return hip_status(ASG_DISPATCH(g,
+        launch_beam_word_conf_window_confidence<float>(Pr, G, BG, LM, look, S, beam_size, (int) W, (int) P, frame_tolerance,
+                                                       (int) max_chunk, state, final, scores, pa, tk, tl, st, ls, wd, wl, wf,
+                                                       word_confidences, normalisers, fr, co, su, (hipStream_t) stream),
+        launch_beam_word_conf_window_confidence<double>(Pr, G, BG, LM, look, S, beam_size, (int) W, (int) P, frame_tolerance,
+                                                        (int) max_chunk, state, final, scores, pa, tk, tl, st, ls, wd, wl, wf,
+                                                        word_confidences, normalisers, fr, co, su, (hipStream_t) stream)));
+}
+
+int asg_beam_word_conf_window_confidence(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B,
+                                         int beam_size, int64_t W, int64_t P, int frame_tolerance, int64_t max_chunk, void *state,
+                                         size_t state_bytes, const void *transition, const int64_t *transition_strides, int final,
+                                         void *scores, int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states,
+                                         int64_t *lm_states, int64_t *words, int64_t *word_lengths, int64_t *word_frames,
+                                         void *word_confidences, void *normalisers, int64_t *frames, int64_t *committed,
+                                         int64_t *status, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    return beam_word_conf_window_confidence(gb, lm, nullptr, false, B, beam_size, W, P, frame_tolerance, max_chunk, state,
+                                            state_bytes, transition, transition_strides, final, scores, path, tokens, token_lengths,
+                                            states, lm_states, words, word_lengths, word_frames, word_confidences, normalisers,
+                                            frames, committed, status, stream);
+}
+
+int asg_beam_word_conf_window_confidence_la(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                                            const asg_word_lookahead *la, int64_t B, int beam_size, int64_t W, int64_t P,
+                                            int frame_tolerance, int64_t max_chunk, void *state, size_t state_bytes,
+                                            const void *transition, const int64_t *transition_strides, int final, void *scores,
+                                            int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states,
+                                            int64_t *lm_states, int64_t *words, int64_t *word_lengths, int64_t *word_frames,
+                                            void *word_confidences, void *normalisers, int64_t *frames, int64_t *committed,
+                                            int64_t *status, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    return beam_word_conf_window_confidence(gb, lm, la, true, B, beam_size, W, P, frame_tolerance, max_chunk, state, state_bytes,
+                                            transition, transition_strides, final, scores, path, tokens, token_lengths, states,
+                                            lm_states, words, word_lengths, word_frames, word_confidences, normalisers, frames,
+                                            committed, status, stream);
 }
 
 // The n-best confidences: the checks of asg_beam_words_confidence, then those of asg_beam_decode_words_nbest.

@@ -16,20 +16,9 @@ namespace asg {
 
 namespace {
 
-// Where the lattice rows of a frame lie.  FlatRows: frame t in row t, and the pull ends with the frame-0 term -- every caller
-// with a workspace or a state of T rows.  A state that keeps its rows in a ring (asg_beam_conf_window.hip) passes a policy of its
-// own: row(t) of the frames 0 .. len-1 it is called with, and first() -- whether its frame 0 is the utterance's.  (kFlat: the
-// row of the top frame is chosen by a constant, not by a call of row() -- with the call the flat callers' kernels came out with
-// another register allocation; this way their listings are the ones they had before there was a policy)
-struct FlatRows {
-    static constexpr bool kFlat = true;
-    __device__ __forceinline__ int row(int t) const { return t; }
-    __device__ __forceinline__ bool first() const { return true; }
-};
-
 // The beta pull with the token-event sink.  nb [M] / nq [M]: the dynamic LDS in front of the sink's ring (bwd_front).
 // Lat: TokenLat<R>, or a lattice with its edges and labels and an end term of its own (the prefix mode of the lattice-keeping
-// stream, asg_beam_stream_conf.hip); Lat::Args starts with TokenLat<R>::Args' members.  Rows: see FlatRows.
+// stream, asg_beam_stream_conf.hip); Lat::Args starts with TokenLat<R>::Args' members.  Rows: see FlatRows (asg_beam_conf_sink.h).
 template <typename R, typename Sink, typename Lat = TokenLat<R>, typename Rows = FlatRows>
 __device__ __forceinline__ void beam_conf_pull(const Problem &P, const typename Lat::Args &args, char *wb, size_t beta_off,
                                                R Z, int len, int last, int *nq, R *nb, Sink &sink, Rows rows = Rows{}) {

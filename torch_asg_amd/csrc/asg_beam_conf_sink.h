@@ -14,6 +14,18 @@ constexpr double kConfScale = 18014398509481984.0;            // 2^54: a word su
 constexpr int kConfRing = 256;                                // >= 2 * kBeamWordConfMaxTol + 2, a power of two
 static_assert(kConfRing >= 2 * kBeamWordConfMaxTol + 2 && (kConfRing & (kConfRing - 1)) == 0, "ring");
 
+// Where the lattice rows of a frame lie, for both pulls (asg_beam_conf_pull.h, asg_beam_word_conf_pull.h).  FlatRows: frame t in
+// row t, and the token pull ends with the frame-0 term -- every caller with a workspace or a state of T rows.  A state that keeps
+// its rows in a ring (RingRows, asg_beam_window_lat.h) passes a policy of its own: row(t) of the frames 0 .. len-1 it is called
+// with, and first() -- whether its frame 0 is the utterance's.  (kFlat: the row of the top frame is chosen by a constant, not by a
+// call of row() -- with the call the flat callers' kernels came out with another register allocation; this way their listings
+// are the ones they had before there was a policy)
+struct FlatRows {
+    static constexpr bool kFlat = true;
+    __device__ __forceinline__ int row(int t) const { return t; }
+    __device__ __forceinline__ bool first() const { return true; }
+};
+
 // 5x's sink: the words of ONE hypothesis in frame order.  The words whose window holds the frame the workgroup stands at are
 // [ka, kb), the same in every thread; a word's accumulator is slot k mod 256 of the ring.
 template <typename R>

@@ -40,18 +40,6 @@ namespace asg {
 
 namespace {
 
-// The rows of the pull's frames 0 .. len-1: frame t is frame org + t of the utterance, in row (org + t) mod RW (len <= RW).
-struct RingRows {
-    static constexpr bool kFlat = false;
-    int orow, RW;
-    bool at0;                    // org == 0 and the pull goes down to the utterance's first frame
-    __device__ __forceinline__ int row(int t) const {
-        const int r = orow + t;
-        return r >= RW ? r - RW : r;
-    }
-    __device__ __forceinline__ bool first() const { return at0; }
-};
-
 // Dynamic LDS: [reduction slots][pa R K][pq int K] (beam_loss_fwd's), the sort's int [P2(K)] over the same bytes.
 template <typename R>
 __global__ void __launch_bounds__(kBL) beam_conf_window_catchup(Problem P, GraphArgs g, int K, int C, char *state,

@@ -64,6 +64,7 @@ template <bool FR>
 struct WinOutT {
     static constexpr bool kWords = false;    // (window_commit: no ring of LM states, no words)
     static constexpr bool kFrames = FR;      // (... and the tokens' start frames for a lattice-keeping state)
+    static constexpr bool kWordFrames = false;
     const int *bq, *bs;          // the ring [W][K]
     int K, Q, W;
     const int *label, *state;

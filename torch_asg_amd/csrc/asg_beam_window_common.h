@@ -135,11 +135,33 @@ __device__ inline void collapse_frames_from(const long long *pb, int len, long l
     }
 }
 
+// One wavefront, beside collapse_words_from (asg_beam_word_frame.h) over the same segment and with its rule: the absolute frame
+// of every separator that ends a word -- frame `first` + t for pb[t] == sep behind another label, the carried one for t == 0 --
+// to wf[0..).  -> how many.
+__device__ inline int collapse_word_frames_from(const long long *pb, int len, long long carry, int sep, long long first,
+                                                long long *wf, int lane) {
+    int base = 0;
+    for (int c0 = 0; c0 < len; c0 += 64) {
+        const int t = c0 + lane;
+        const long long cur = t < len ? pb[t] : -1;
+        long long prv = __shfl_up(cur, 1);
+        if (lane == 0) prv = carry;
+        const bool keep = t < len && cur == sep && prv != sep && prv >= 0;
+        const unsigned long long m = __ballot(keep);
+        const int pre = __popcll(m & ((1ull << lane) - 1ull));
+        if (keep) wf[base + pre] = first + t;
+        base += __popcll(m);
+        carry = __shfl(cur, 63);                             // (only read when another 64 frames follow)
+    }
+    return base;
+}
+
 // Commit the frames base .. cto on the path that passes slot k of frame `top`, which lives in row `r` (base <= cto <= top <
 // base + W): one lane walks the chain, one wavefront collapses the segment's labels behind `carry`, and with WO::kWords another
 // finds its words behind `carry` / `carry_state`; with WO::kFrames (the lattice-keeping token window, asg_beam_conf_window.hip)
-// the first wavefront also writes every committed token's start frame to o.tf.  The whole workgroup calls it; it begins after and
-// ends with a __syncthreads.
+// the first wavefront also writes every committed token's start frame to o.tf; with WO::kWordFrames (the lattice-keeping word
+// window, asg_beam_word_conf_window.hip) a third writes every committed word's separator frame to o.wf.  The whole workgroup calls
+// it; it begins after and ends with a __syncthreads.
 // (A slot outside 0 .. K-1 cannot happen; if it did, the token family would stop writing the segment, the word family pad with -1.)
 template <typename WC, typename WO>
 __device__ __forceinline__ void window_commit(WC &wc, const WO &o, long long top, int r, long long cto, int k) {
@@ -190,6 +212,9 @@ __device__ __forceinline__ void window_commit(WC &wc, const WO &o, long long top
                 wc.nword = w0 + nw;
                 if (len > 0) wc.carry_state = (int) o.ns[c0 + len - 1];
             }
+        }
+        if constexpr (WO::kWordFrames) {
+            if (tid >= 128 && tid < 192) (void) collapse_word_frames_from(o.np + c0, len, wcarry, o.sep, base, o.wf + w0, tid - 128);
         }
     }
     __syncthreads();

@@ -10,6 +10,9 @@
 //     before the attempt, and the tokens' range in this call's output row;
 //   - the padding of new_token_frames and the number of logged attempts.
 // The header words of the lattice-keeping state sit in the slot's 256-byte header behind TokenWinHdr, which stays as it is.
+// The word window (asg_beam_word_window.hip with asg_beam_word_conf_window.hip) takes the same two policies: its U
+// rows hold 64-bit pair keys (frame_keys), its log entries the range of WORDS an attempt committed, `tf` is its new_word_frames,
+// and the header words sit behind WordWinHdr (32 bytes as well).
 #pragma once
 #include "asg_beam_frame.h"
 
@@ -32,12 +35,28 @@ struct WinAttempt {
     int k0, k1;
 };
 
-// chunk: before the frames, n frames at pos ..; frame: behind frame gt, which left na states in `bqrow`; skipped: behind the
-// loop, which ran t of the n frames; attempt: behind a commit attempt; done: behind everything, ntok tokens committed.
+// The rows of a pull's frames 0 .. len-1 over the ring (the Rows policy of both pulls, see FlatRows in asg_beam_conf_sink.h):
+// frame t is frame org + t of the utterance, in row (org + t) mod RW (len <= RW).
+struct RingRows {
+    static constexpr bool kFlat = false;
+    int orow, RW;
+    bool at0;                    // org == 0 and the pull goes down to the utterance's first frame
+    __device__ __forceinline__ int row(int t) const {
+        const int r = orow + t;
+        return r >= RW ? r - RW : r;
+    }
+    __device__ __forceinline__ bool first() const { return at0; }
+};
+
+// chunk: before the frames, n frames at pos ..; frame: behind frame gt, which left na states in `bqrow`; frame_keys: the same
+// for a family whose keys are not its bq row (the word window: KeyT = u64, key_of(x) the pair of slot x); skipped: behind the
+// loop, which ran t of the n frames; attempt: behind a commit attempt, items [k0, k1) of the call committed (tokens, or the word
+// window's words); done: behind everything, n items committed.
 struct WinKeepNone {
     static constexpr bool kLattice = false;
     template <typename R> __device__ __forceinline__ void chunk(char *, const R *, const Problem &, long long, int) const {}
     __device__ __forceinline__ void frame(char *, long long, int, const int *, int) const {}
+    template <typename KeyT, typename KeyOf> __device__ __forceinline__ void frame_keys(char *, long long, int, int, KeyOf) const {}
     __device__ __forceinline__ void skipped(char *, long long, int, int) const {}
     __device__ __forceinline__ void attempt(char *, int, long long, long long, int, int) const {}
     __device__ __forceinline__ void done(char *, int, int, long long) const {}
@@ -66,6 +85,13 @@ struct WinKeepLattice {
         const int r = row(gt);
         int *u = (int *) (wb + U) + (int64_t) r * K;
         for (int x = threadIdx.x; x < na; x += kBT) u[x] = bqrow[x];
+        if (threadIdx.x == 0) ((int *) (wb + cnt))[r] = na;
+    }
+    template <typename KeyT, typename KeyOf>
+    __device__ __forceinline__ void frame_keys(char *wb, long long gt, int na, int K, KeyOf key_of) const {
+        const int r = row(gt);
+        KeyT *u = (KeyT *) (wb + U) + (int64_t) r * K;
+        for (int x = threadIdx.x; x < na; x += kBT) u[x] = key_of(x);
         if (threadIdx.x == 0) ((int *) (wb + cnt))[r] = na;
     }
     __device__ __forceinline__ void skipped(char *wb, long long pos, int t, int n) const {

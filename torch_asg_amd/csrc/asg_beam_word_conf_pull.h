@@ -24,10 +24,13 @@ namespace {
 
 // Lat: WordLat<R>, or a lattice with its edges and labels, an end term of its own and its own answer to whether the event of
 // frame len exists (the prefix mode of the lattice-keeping stream, asg_beam_word_stream_conf.hip); Lat::Args starts with
-// WordLat<R>::Args' members.
-template <typename R, typename Sink, typename Lat = WordLat<R>>
+// WordLat<R>::Args' members.  Rows: where the rows of the frames 0 .. len-1 lie (FlatRows, asg_beam_conf_sink.h: frame t in row
+// t; the lattice-keeping word window passes RingRows).  The events of the frames len .. 1 are handed on; a ring caller whose
+// frame 0 is not the utterance's stops above it all the same -- a word never ends at the pull's frame 0.
+template <typename R, typename Sink, typename Lat = WordLat<R>, typename Rows = FlatRows>
 __device__ __forceinline__ void beam_word_conf_pull(const Problem &P, const typename Lat::Args &args, char *wb, size_t beta_off,
-                                                    R Z, int len, int last, unsigned long long *nq, R *nb, Sink &sink) {
+                                                    R Z, int len, int last, unsigned long long *nq, R *nb, Sink &sink,
+                                                    Rows rows = Rows{}) {
     using KeyT = unsigned long long;
     const int M = args.lay.M, tid = threadIdx.x, b = blockIdx.x;
     const R NINF = Num<R>::ninf();
@@ -46,26 +49,28 @@ __device__ __forceinline__ void beam_word_conf_pull(const Problem &P, const type
     // frame len: the final step out of the word-end nodes of the last set
     sink.window(len);
     if constexpr (Sink::kBarrier) __syncthreads();
-    int mt = nu[len - 1];
+    int top = len - 1;                                                         // the row of the last frame
+    if constexpr (!Rows::kFlat) top = rows.row(len - 1);
+    int mt = nu[top];
     for (int x = tid; x < mt; x += kBL) {
-        const KeyT p = U[(int64_t) (len - 1) * M + x];
+        const KeyT p = U[(int64_t) top * M + x];
         R e;
         lat.end(p, e);
         nq[x] = p;
         nb[x] = e;
         const int s = lat.f.state[(int) (p & lat.qmask)];
-        if (lat.end_event() && sink.open() && s != 0 && e > NINF) sink.add(lat.f.wos[s], (A[(int64_t) (len - 1) * M + x] + e) - Z);
+        if (lat.end_event() && sink.open() && s != 0 && e > NINF) sink.add(lat.f.wos[s], (A[(int64_t) top * M + x] + e) - Z);
     }
     for (int t = len - 1; t >= 1; --t) {
         __syncthreads();                                                       // nq, nb and the adds of frame t + 1
         sink.window(t);
         if constexpr (Sink::kBarrier) __syncthreads();
         const bool open = sink.open();
-        const int mp = nu[t - 1];
-        const KeyT *Up = U + (int64_t) (t - 1) * M;
-        const R *Ap = A + (int64_t) (t - 1) * M;
+        const int mp = nu[rows.row(t - 1)];
+        const KeyT *Up = U + (int64_t) rows.row(t - 1) * M;
+        const R *Ap = A + (int64_t) rows.row(t - 1) * M;
         R *Brow = Bv + (int64_t) ((t - 1) & 1) * M;
-        const R *xt = in + (int64_t) t * P.is0;
+        const R *xt = in + (int64_t) rows.row(t) * P.is0;
         const int G = subgroup(mp), per = kBL / G;
         for (int k0 = 0; k0 < mp; k0 += per) {
             const int k = k0 + tid / G, lg = tid % G;

@@ -60,6 +60,21 @@ struct WordLat {
     }
 };
 
+// WordLat with the end of a prefix: a path may end in any kept pair of the last set with weight 0, and no word completes at
+// frame len (there is no final step) -- the lattice-keeping streams, asg_beam_word_stream_conf.hip and
+// asg_beam_word_conf_window.hip.
+template <typename R>
+struct PrefixWordLat : WordLat<R> {
+    using Key = typename WordLat<R>::Key;
+    struct Args : WordLat<R>::Args { int fin; };
+    int fin;
+    __device__ void bind(const Args &a) { WordLat<R>::bind(a); fin = a.fin; }
+    __device__ void end(Key p, R &e) const {
+        if (fin) WordLat<R>::end(p, e); else e = R(0);
+    }
+    __device__ bool end_event() const { return fin != 0; }
+};
+
 }  // namespace
 
 }  // namespace asg

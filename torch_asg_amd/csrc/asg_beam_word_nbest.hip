@@ -543,11 +543,12 @@ hipError_t launch_beam_word_window_nbest(const GraphArgs &G, const BeamGraphArgs
                                          int nbest, void *work, void *scores, long long *path, long long *tokens, long long *tlen,
                                          long long *states, long long *lm_states, long long *words, long long *wlen,
                                          long long *num_hyps, long long *frames, long long *committed, long long *status,
-                                         hipStream_t stream) {
+                                         hipStream_t stream, size_t stride) {
     const int cap = beam_word_cap(K, BG.max_out, BG.num_start);
     const BeamStreamLayout lay = beam_word_window_layout(sizeof(R), W, K, cap);
     BeamWordNbestSrc src{};
-    src.base = (const char *) state; src.per = lay.per; src.set_off = lay.set; src.pos_off = lay.hdr;
+    src.base = (const char *) state; src.per = stride ? stride : lay.per;   // (a slot with parts of the caller's behind it)
+    src.set_off = lay.set; src.pos_off = lay.hdr;
     src.nb = nbest < K ? nbest : K;
     src.cols = (char *) work; src.cols_per = a256((size_t) W * src.nb * 4); src.Tw = W; src.S = S;
     Problem P{};                                                            // no emissions, no lengths: the state has both
@@ -565,7 +566,7 @@ hipError_t launch_beam_word_window_nbest(const GraphArgs &G, const BeamGraphArgs
                                                          const WordLookArgs *, int, int, int, int, const void *, int, int, void *, \
                                                          void *, long long *, long long *, long long *, long long *, long long *, \
                                                          long long *, long long *, long long *, long long *, long long *,        \
-                                                         long long *, hipStream_t);
+                                                         long long *, hipStream_t, size_t);
 ASG_BEAM_WORD_WINDOW_NBEST_INST(float)
 ASG_BEAM_WORD_WINDOW_NBEST_INST(double)
 #undef ASG_BEAM_WORD_WINDOW_NBEST_INST

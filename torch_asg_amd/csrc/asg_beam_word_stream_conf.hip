@@ -113,20 +113,6 @@ __global__ void __launch_bounds__(kBL) beam_word_stream_conf_catchup(Problem P, 
     if (tid == 0) hdr[kHdrApos] = L;
 }
 
-// WordLat with the end of a prefix: a path may end in any kept pair of the last set with weight 0, and no word completes at
-// frame len (there is no final step).
-template <typename R>
-struct PrefixWordLat : WordLat<R> {
-    using Key = typename WordLat<R>::Key;
-    struct Args : WordLat<R>::Args { int fin; };
-    int fin;
-    __device__ void bind(const Args &a) { WordLat<R>::bind(a); fin = a.fin; }
-    __device__ void end(Key p, R &e) const {
-        if (fin) WordLat<R>::end(p, e); else e = R(0);
-    }
-    __device__ bool end_event() const { return fin != 0; }
-};
-
 inline size_t stream_conf_lds(int elem, int K) { return bwd_front(elem, 8, K) + (size_t) kConfRing * 8; }
 
 // Dynamic LDS: [nq u64 K][nb R K][pad to 16][ring u64 256] (beam_word_conf_bwd's).

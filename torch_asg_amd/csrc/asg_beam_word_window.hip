@@ -27,6 +27,11 @@
 // that straddles two commits or two calls gives its word once.  This unit keeps its header, its control blocks and its call of
 // word_best_end.
 //
+// The advance kernel takes a KEEP POLICY (asg_beam_window_lat.h): WinKeepNone for this family's plain state -- empty, no argument,
+// branch or LDS byte --, WinKeepLattice for the lattice-keeping state of asg_beam_word_conf_window.hip, which also
+// keeps the chunk's emissions, |A_t| and the kept pairs' keys in that state's ring, writes the separator frames of the committed
+// words and logs every attempt that committed a word.
+//
 // With LM look-ahead (include/asg_hip.h::asg_beam_word_window_advance_la) the advance and result kernels are compiled a second
 // time with the frame's look-ahead flag on.  Convergence looks at slots only and is the same text; the forced commit follows the
 // best prefix pair, which word_best_end then ranks by value minus look-ahead (word_prefix); the state has the same bytes.
@@ -35,6 +40,7 @@
 #include "asg_beam_common.h"
 #include "asg_beam_word_frame.h"
 #include "asg_beam_window_common.h"   // the commit attempt, shared with asg_beam_window.hip
+#include "asg_beam_window_lat.h"      // the keep policy: what a lattice-keeping state keeps besides (asg_beam_word_conf_window.hip)
 
 namespace asg {
 
@@ -58,16 +64,19 @@ struct WinCtl {
 
 // What the commits of one call write to, and the ring they read (LDS: a commit is rare, and the frame loop keeps its scalar
 // registers for the search).
-struct WinOut {
+template <bool FR>
+struct WinOutT {
     static constexpr bool kWords = true;     // (window_commit: the ring bh, the output nl, the wavefront that finds the words)
     static constexpr bool kFrames = false;   // (... and no start frames of the tokens)
+    static constexpr bool kWordFrames = FR;  // (... and the words' separator frames for a lattice-keeping state)
     const int *bq, *bh, *bs;     // the ring [W][K]
     int K, Q, W, S, sep;
     const int *label, *state, *wos;
     long long *np, *ns, *nl, *nt, *nw;   // this slot's rows of new_path / new_states / new_lm_states / new_tokens / new_words
     long long cols;              // W + Tc
+    long long *wf;               // kWordFrames: this slot's row of new_word_frames
 };
-static_assert(sizeof(WinCtl) <= 64 && kWinOutOff + sizeof(WinOut) <= kFixedLds, "control blocks");
+static_assert(sizeof(WinCtl) <= 64 && kWinOutOff + sizeof(WinOutT<true>) <= kFixedLds, "control blocks");
 
 __global__ void __launch_bounds__(256) beam_word_window_reset_kernel(char *state, BeamStreamLayout lay, BeamWordWorkLayout wl,
                                                                       unsigned C, int key_bytes, const unsigned char *mask) {
@@ -81,15 +90,16 @@ __global__ void __launch_bounds__(256) beam_word_window_reset_kernel(char *state
     }
 }
 
-template <typename R, bool TRL, bool LA = false>
+template <typename R, bool TRL, bool LA, typename Keep>
 __global__ void __launch_bounds__(kBT) beam_word_window_advance_kernel(Problem P, GraphArgs g, BeamGraphArgs bg, WordLmArgs lm, int S,
                                                                        int K, R theta, int cap, int tbits, int W, int CP,
                                                                        char *state, BeamStreamLayout lay, long long *new_path,
                                                                        long long *new_states, long long *new_lm_states,
                                                                        long long *new_tokens, long long *new_words,
                                                                        long long *new_frames, long long *new_tlen,
-                                                                       long long *new_wlen, WordLookParam<LA> la) {
+                                                                       long long *new_wlen, WordLookParam<LA> la, Keep keep) {
     using KT = Key<R>;
+    using WinOut = WinOutT<Keep::kLattice>;
     using U = typename KT::U;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     Ctl<U> &ctl = *(Ctl<U> *) lds;
@@ -113,6 +123,7 @@ __global__ void __launch_bounds__(kBT) beam_word_window_advance_kernel(Problem P
         o.bq = nullptr; o.bh = nullptr; o.bs = nullptr;
         o.K = K; o.Q = g.Q; o.W = W; o.S = S; o.sep = lm.sep; o.label = g.label; o.state = g.state; o.wos = lm.word_of_state;
         o.np = np; o.ns = ns; o.nl = nl; o.nt = nt; o.nw = nwd; o.cols = cols;
+        if constexpr (Keep::kLattice) o.wf = keep.tf + (int64_t) b * cols;
     }
 
     long long pos = hdr->pos, base0 = hdr->base;
@@ -124,6 +135,8 @@ __global__ void __launch_bounds__(kBT) beam_word_window_advance_kernel(Problem P
         wc.base = base0; wc.carry = hdr->carry; wc.carry_state = hdr->carry_state; wc.status = hdr->status;
         wc.ncommit = 0; wc.ntok = 0; wc.nword = 0;
     }
+    keep.chunk(wb, (const R *) P.inputs + (int64_t) b * P.is1, P, pos, n);
+    int logged = 0;                                         // (a lattice-keeping state's: the attempts in its log)
 
     if (n >= 1) {
         const R *in = (const R *) P.inputs + (int64_t) b * P.is1;
@@ -140,12 +153,19 @@ __global__ void __launch_bounds__(kBT) beam_word_window_advance_kernel(Problem P
         beam_word_load_set<R, TRL, LA>(f, trs, set_v, na0);
 
         int row = (int) (pos % W), ph = (int) (pos % CP);   // the next frame's row, and pos mod P; both kept by stepping
+        int ran = 0;
         for (int t = 0; t < n; ++t) {
             const long long gt = pos + t;                   // the frame's index in the utterance
             int na = ctl.na;
             if (gt >= 1 && na == 0) break;                  // an empty beam stays empty (and commits nothing more)
             const int fr = row;
             beam_word_frame<R, TRL, LA>(f, gt == 0, na, in + (int64_t) t * P.is0, P.is2, bq, bh, bs, fr);
+            if constexpr (Keep::kLattice) {                 // the frame's kept pairs as keys, unsorted, into the lattice ring
+                ran = t + 1;
+                const int *bqr = bq + (int64_t) fr * K, *bhr = bh + (int64_t) fr * K;
+                keep.template frame_keys<unsigned long long>(wb, gt, ctl.na < K ? ctl.na : K, K,
+                                                             [&](int x) { return f.pair(bhr[x], bqr[x]); });
+            }
             const long long p1 = gt + 1;                    // pos, counting this frame
             row = row + 1 == W ? 0 : row + 1;
             ph = ph + 1 == CP ? 0 : ph + 1;
@@ -155,6 +175,9 @@ __global__ void __launch_bounds__(kBT) beam_word_window_advance_kernel(Problem P
             // ================================================================ commit attempt
             // ---- convergence: the latest frame at which every survivor has the same ancestor
             long long base = wc.base;
+            const long long b0 = base;
+            int wd0 = 0;
+            if constexpr (Keep::kLattice) wd0 = wc.nword;
             int cslot, crow;
             const long long c = window_converge(bs, K, W, na, p1, base, fr, mark, wc.scan, cslot, crow);
             if (c >= base) {
@@ -173,7 +196,12 @@ __global__ void __launch_bounds__(kBT) beam_word_window_advance_kernel(Problem P
                     window_commit(wc, o, p1 - 1, fr, base + F - 1, bk);
                 }
             }
+            if constexpr (Keep::kLattice) {                 // one attempt is one lattice end, whatever it committed
+                const int wd1 = wc.nword;
+                if (wd1 > wd0) keep.attempt(wb, logged++, p1, b0, wd0, wd1);
+            }
         }
+        keep.skipped(wb, pos, ran, n);
         const int na = beam_word_store_set<R, LA>(f, set_v);
         if (tid == 0) hdr->na = na;
     }
@@ -182,6 +210,7 @@ __global__ void __launch_bounds__(kBT) beam_word_window_advance_kernel(Problem P
     for (long long x = nc + tid; x < cols; x += kBT) { np[x] = -1; ns[x] = -1; nl[x] = -1; }
     for (long long x = ntk + tid; x < cols; x += kBT) nt[x] = -1;
     for (long long x = nwo + tid; x < cols; x += kBT) nwd[x] = -1;
+    keep.done(wb, logged, nwo, cols);
     if (tid == 0) {
         new_frames[b] = nc;
         new_tlen[b] = ntk;
@@ -288,9 +317,10 @@ size_t beam_word_window_state_bytes(int elem, int W, int B, int K, int cap) {
 }
 
 hipError_t launch_beam_word_window_reset(int elem, const BeamGraphArgs &BG, int K, int W, int B, void *state,
-                                         const unsigned char *mask, hipStream_t stream) {
+                                         const unsigned char *mask, hipStream_t stream, size_t stride) {
     const int cap = beam_word_cap(K, BG.max_out, BG.num_start);
-    const BeamStreamLayout lay = beam_word_window_layout(elem, W, K, cap);
+    BeamStreamLayout lay = beam_word_window_layout(elem, W, K, cap);
+    if (stride) lay.per = stride;                                           // (a slot with parts of the caller's behind it)
     const int tbits = word_table_bits(cap);
     const size_t C = (size_t) 1 << tbits;
     hipLaunchKernelGGL(beam_word_window_reset_kernel, dim3(B, reset_blocks(C)), dim3(256), 0, stream, (char *) state, lay,
@@ -298,51 +328,75 @@ hipError_t launch_beam_word_window_reset(int elem, const BeamGraphArgs &BG, int 
     return hipGetLastError();
 }
 
-template <typename R>
-hipError_t launch_beam_word_window_advance(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
-                                           const WordLookArgs *LA, int S, int K, double theta, int W, int CP, void *state,
-                                           long long *new_path,
-                                           long long *new_states, long long *new_lm_states, long long *new_tokens,
-                                           long long *new_words, long long *new_frames, long long *new_tlen, long long *new_wlen,
-                                           hipStream_t stream) {
+namespace {
+
+template <typename R, typename Keep>
+hipError_t beam_word_window_advance(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                                    const WordLookArgs *LA, int S, int K, double theta, int cap, int W, int CP, void *state,
+                                    const BeamStreamLayout &lay, long long *new_path, long long *new_states,
+                                    long long *new_lm_states, long long *new_tokens, long long *new_words, long long *new_frames,
+                                    long long *new_tlen, long long *new_wlen, Keep keep, hipStream_t stream) {
     const int N = P.N;
-    const int cap = beam_word_cap(K, BG.max_out, BG.num_start);
     const int tbits = word_table_bits(cap);
-    const BeamStreamLayout lay = beam_word_window_layout(sizeof(R), W, K, cap);
     // the LDS of the word stream plus the two mark sets: control blocks, marks, the set, and the transitions when they fit
     const size_t beam = kFixedLds + mark_bytes(K) + (size_t) K * (sizeof(R) + 8);
     const bool trl = beam + (size_t) N * N * sizeof(R) <= kLdsMax;
     const size_t dyn = beam + (trl ? (size_t) N * N * sizeof(R) : 0);
 #define ASG_BEAM_WORD_WINDOW(TRL, LAF, LOOK)                                                                                   \
     do {                                                                                                                       \
-        const void *fn = (const void *) beam_word_window_advance_kernel<R, TRL, LAF>;                                         \
+        const void *fn = (const void *) beam_word_window_advance_kernel<R, TRL, LAF, Keep>;                                   \
         if (dyn > 64 * 1024) (void) hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) dyn);         \
-        hipLaunchKernelGGL((beam_word_window_advance_kernel<R, TRL, LAF>), dim3(P.B), dim3(kBT), dyn, stream, P, G, BG, LM,   \
-                           S, K, (R) theta, cap, tbits, W, CP, (char *) state, lay, new_path, new_states, new_lm_states,       \
-                           new_tokens, new_words, new_frames, new_tlen, new_wlen, LOOK);                                       \
+        hipLaunchKernelGGL((beam_word_window_advance_kernel<R, TRL, LAF, Keep>), dim3(P.B), dim3(kBT), dyn, stream, P, G, BG, \
+                           LM, S, K, (R) theta, cap, tbits, W, CP, (char *) state, lay, new_path, new_states, new_lm_states,   \
+                           new_tokens, new_words, new_frames, new_tlen, new_wlen, LOOK, keep);                                 \
     } while (0)
     if (LA) { if (trl) ASG_BEAM_WORD_WINDOW(true, true, *LA); else ASG_BEAM_WORD_WINDOW(false, true, *LA); }
     else if (trl) ASG_BEAM_WORD_WINDOW(true, false, WordNoLook{}); else ASG_BEAM_WORD_WINDOW(false, false, WordNoLook{});
 #undef ASG_BEAM_WORD_WINDOW
     return hipGetLastError();
 }
+
+}  // namespace
+
+template <typename R>
+hipError_t launch_beam_word_window_advance(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                                           const WordLookArgs *LA, int S, int K, double theta, int W, int CP, void *state,
+                                           long long *new_path,
+                                           long long *new_states, long long *new_lm_states, long long *new_tokens,
+                                           long long *new_words, long long *new_frames, long long *new_tlen, long long *new_wlen,
+                                           hipStream_t stream, const BeamWordConfWindowLayout *cw, long long *new_word_frames) {
+    const int cap = beam_word_cap(K, BG.max_out, BG.num_start);
+    if (cw) {
+        WinKeepLattice keep{};
+        keep.hdr = cw->st.hdr; keep.cnt = cw->lat.cnt; keep.em = cw->em; keep.U = cw->lat.U; keep.log = cw->log;
+        keep.RW = cw->RW; keep.nlog = cw->nlog; keep.tf = new_word_frames;
+        return beam_word_window_advance<R>(P, G, BG, LM, LA, S, K, theta, cap, W, CP, state, cw->st, new_path, new_states,
+                                           new_lm_states, new_tokens, new_words, new_frames, new_tlen, new_wlen, keep, stream);
+    }
+    return beam_word_window_advance<R>(P, G, BG, LM, LA, S, K, theta, cap, W, CP, state, beam_word_window_layout(sizeof(R), W, K, cap),
+                                       new_path, new_states, new_lm_states, new_tokens, new_words, new_frames, new_tlen, new_wlen,
+                                       WinKeepNone{}, stream);
+}
 template hipError_t launch_beam_word_window_advance<float>(const Problem &, const GraphArgs &, const BeamGraphArgs &,
                                                            const WordLmArgs &, const WordLookArgs *, int, int, double, int, int, void *, long long *,
                                                            long long *, long long *, long long *, long long *, long long *,
-                                                           long long *, long long *, hipStream_t);
+                                                           long long *, long long *, hipStream_t, const BeamWordConfWindowLayout *,
+                                                           long long *);
 template hipError_t launch_beam_word_window_advance<double>(const Problem &, const GraphArgs &, const BeamGraphArgs &,
                                                             const WordLmArgs &, const WordLookArgs *, int, int, double, int, int, void *, long long *,
                                                             long long *, long long *, long long *, long long *, long long *,
-                                                            long long *, long long *, hipStream_t);
+                                                            long long *, long long *, hipStream_t, const BeamWordConfWindowLayout *,
+                                                            long long *);
 
 template <typename R>
 hipError_t launch_beam_word_window_result(const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
                                           const WordLookArgs *LA, int S, int K, int W, int B, const void *state, int final, void *scores, long long *path, long long *tokens,
                                           long long *tlen, long long *states, long long *lm_states, long long *words,
                                           long long *wlen, long long *frames, long long *committed, long long *status,
-                                          hipStream_t stream) {
+                                          hipStream_t stream, size_t stride) {
     const int cap = beam_word_cap(K, BG.max_out, BG.num_start);
-    const BeamStreamLayout lay = beam_word_window_layout(sizeof(R), W, K, cap);
+    BeamStreamLayout lay = beam_word_window_layout(sizeof(R), W, K, cap);
+    if (stride) lay.per = stride;                                           // (a slot with parts of the caller's behind it)
 #define ASG_BEAM_WORD_WINDOW_RESULT(LAF, LOOK)                                                                                 \
     hipLaunchKernelGGL((beam_word_window_result_kernel<R, LAF>), dim3(B), dim3(kBT), 0, stream, G, LM, S, K, cap,              \
                        word_table_bits(cap), W, (const char *) state, lay, final, (R *) scores, path, tokens, tlen, states,    \
@@ -354,10 +408,10 @@ hipError_t launch_beam_word_window_result(const GraphArgs &G, const BeamGraphArg
 template hipError_t launch_beam_word_window_result<float>(const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &,
                                                           const WordLookArgs *, int, int, int, int, const void *, int, void *, long long *, long long *, long long *,
                                                           long long *, long long *, long long *, long long *, long long *,
-                                                          long long *, long long *, hipStream_t);
+                                                          long long *, long long *, hipStream_t, size_t);
 template hipError_t launch_beam_word_window_result<double>(const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &,
                                                            const WordLookArgs *, int, int, int, int, const void *, int, void *, long long *, long long *, long long *,
                                                            long long *, long long *, long long *, long long *, long long *,
-                                                           long long *, long long *, hipStream_t);
+                                                           long long *, long long *, hipStream_t, size_t);
 
 }  // namespace asg

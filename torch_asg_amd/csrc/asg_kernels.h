@@ -371,24 +371,29 @@ hipError_t launch_beam_window_result(const GraphArgs &G, const BeamGraphArgs &BG
 // the lexicon automaton (word_of_state has S entries).  LA: the look-ahead of asg_beam_word_window_*_la, nullptr without one.
 BeamStreamLayout beam_word_window_layout(int elem, int W, int K, int cap);
 size_t beam_word_window_state_bytes(int elem, int W, int B, int K, int cap);
+// (stride, here and below: as launch_beam_stream_result's -- a lattice-keeping state's slots, asg_beam_word_conf_window.hip)
 hipError_t launch_beam_word_window_reset(int elem, const BeamGraphArgs &BG, int K, int W, int B, void *state,
-                                         const unsigned char *mask, hipStream_t stream);
+                                         const unsigned char *mask, hipStream_t stream, size_t stride = 0);
 // new_path / new_states / new_lm_states / new_tokens / new_words [B][W + P.T], new_frames / new_tlen / new_wlen [B]: every element
-// is written
+// is written.  cw: the state is a lattice-keeping one (beam_word_conf_window_layout below) -- the same kernel with the policy that
+// also keeps the ring's cnt, emissions and unsorted pair keys, writes new_word_frames [B][W + P.T] and logs the attempts that
+// committed a word (asg_beam_window_lat.h).
+struct BeamWordConfWindowLayout;
 template <typename R>
 hipError_t launch_beam_word_window_advance(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
                                            const WordLookArgs *LA, int S, int K, double theta, int W, int CP, void *state,
                                            long long *new_path,
                                            long long *new_states, long long *new_lm_states, long long *new_tokens,
                                            long long *new_words, long long *new_frames, long long *new_tlen, long long *new_wlen,
-                                           hipStream_t stream);
+                                           hipStream_t stream, const BeamWordConfWindowLayout *cw = nullptr,
+                                           long long *new_word_frames = nullptr);
 template <typename R>
 hipError_t launch_beam_word_window_result(const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
                                           const WordLookArgs *LA, int S, int K, int W, int B, const void *state, int final,
                                           void *scores, long long *path, long long *tokens,
                                           long long *tlen, long long *states, long long *lm_states, long long *words,
                                           long long *wlen, long long *frames, long long *committed, long long *status,
-                                          hipStream_t stream);
+                                          hipStream_t stream, size_t stride = 0);
 // The n-best kernel of asg_beam_word_nbest.hip over a window state (read only): asg_beam_word_window_nbest, with LA
 // asg_beam_word_window_nbest_la.  Every row is the uncommitted tail of its chain, [B][nbest][W]; no sums.  work: [B] blocks of
 // a256(W * nb * 4) bytes.  path / states / lm_states may be null.
@@ -399,7 +404,7 @@ hipError_t launch_beam_word_window_nbest(const GraphArgs &G, const BeamGraphArgs
                                          int nbest, void *work, void *scores, long long *path, long long *tokens, long long *tlen,
                                          long long *states, long long *lm_states, long long *words, long long *wlen,
                                          long long *num_hyps, long long *frames, long long *committed, long long *status,
-                                         hipStream_t stream);
+                                         hipStream_t stream, size_t stride = 0);
 
 // ---- The n best final hypotheses of that search, with the score split (asg_beam_nbest.hip): asg_beam_decode_graph_nbest.
 // One utterance's workspace: the beam search's own layout at the front, then (byte offsets, each part 256-byte aligned) fin
@@ -665,6 +670,40 @@ hipError_t launch_beam_word_conf_stream_confidence(const Problem &P, const Graph
                                                    long long *tlen, long long *states, long long *lm_states, long long *words,
                                                    long long *wlen, long long *word_frames, void *word_conf, void *normalisers,
                                                    long long *frames, long long *status, hipStream_t stream);
+
+// ---- The word window stream with a state that keeps its lattice in a ring (asg_beam_word_conf_window.hip):
+// asg_beam_word_conf_window_*.  One slot: the plain word window's slot (beam_word_window_layout) unchanged at the front -- its
+// header block also holds apos and the number of logged attempts (asg_beam_window_lat.h) --, then (byte offsets, each part 256-byte
+// aligned) a ring of RW = W + tol + 1 + C rows, frame t in row t mod RW: cnt int32 [RW], the emissions [RW][N], nu int32 [RW], U u64
+// [RW][K] (pair keys h << qbits | q), A [RW][K]; the attempt log of nlog = C / CP + 1 entries; beta [nlog][2][K], a pair of rows per
+// logged attempt.  C: the longest chunk an advance may bring.  (kBeamConfWindowMaxLog bounds nlog here too.)
+struct BeamWordConfWindowLayout {
+    BeamStreamLayout st;
+    BeamWordLossLayout lat;      // cnt, nu, U, A over the ring (M = K, nf = 0); lat.per is the slot's stride
+    size_t em, log, beta, per;
+    int RW, nlog;
+};
+BeamWordConfWindowLayout beam_word_conf_window_layout(int elem, int W, int CP, int tol, int C, int K, int cap, int N);
+size_t beam_word_conf_window_state_bytes(int elem, int W, int CP, int tol, int C, int B, int K, int cap, int N);
+// Three launches: the search (launch_beam_word_window_advance with cw; LA: its look-ahead or NULL, which nothing else reads), the
+// catch-up of U / nu / A over [apos, pos), the pull of every logged attempt.  new_word_frames / new_word_conf [B][W + P.T]: every
+// element is written.
+template <typename R>
+hipError_t launch_beam_word_conf_window_advance(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                                                const WordLookArgs *LA, int S, int K, double theta, int W, int CP, int tol, int C,
+                                                void *state, long long *new_path, long long *new_states, long long *new_lm_states,
+                                                long long *new_tokens, long long *new_words, long long *new_frames,
+                                                long long *new_tlen, long long *new_wlen, long long *new_word_frames,
+                                                void *new_word_conf, hipStream_t stream);
+// Two launches: the plain result kernel, then word_frames / word_conf [B][W] and normalisers [B] by one pull from pos - 1 down to
+// base - tol.  P: B, N and the transition.  It only reads the state (beta rows apart).
+template <typename R>
+hipError_t launch_beam_word_conf_window_confidence(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG,
+                                                   const WordLmArgs &LM, const WordLookArgs *LA, int S, int K, int W, int CP, int tol,
+                                                   int C, void *state, int final, void *scores, long long *path, long long *tokens,
+                                                   long long *tlen, long long *states, long long *lm_states, long long *words,
+                                                   long long *wlen, long long *word_frames, void *word_conf, void *normalisers,
+                                                   long long *frames, long long *committed, long long *status, hipStream_t stream);
 
 // ---- Word confidences and end frames for every row of the n-best list (asg_beam_word_nbest_conf.hip):
 // asg_beam_words_nbest_confidence.  One utterance's workspace: asg_beam_words_confidence's layout at the front (the search's

@@ -716,6 +716,10 @@ BeamWordWindowResult = collections.namedtuple("BeamWordWindowResult", ["scores",
 BeamWordWindowNbest = collections.namedtuple("BeamWordWindowNbest", ["scores", "tokens", "token_lengths", "words", "word_lengths",
                                                                      "num_hyps", "path", "states", "lm_states", "frames",
                                                                      "committed", "status"])
+BeamWordWindowConfCommit = collections.namedtuple("BeamWordWindowConfCommit", BeamWordWindowCommit._fields + ("word_frames",
+                                                                                                              "word_confidences"))
+BeamWordWindowConfidence = collections.namedtuple("BeamWordWindowConfidence", BeamWordWindowResult._fields + (
+    "word_frames", "word_confidences", "normalisers"))
 
 
 class BeamWordWindowStream(_Stream):
@@ -747,6 +751,21 @@ class BeamWordWindowStream(_Stream):
     look-ahead, everything above holds with `beam_decode_words(..., lookahead=)` in the place of `beam_decode_words`); there is
     no bound on the number of frames.  `result_nbest` gives the n best hypotheses as their uncommitted tails, with
     `BeamWordStream.result_nbest`'s scores, with or without a look-ahead.
+
+    `keep_lattice=True` makes the state keep the lattice of the search in a ring of window + frame_tolerance + 1 + max_chunk
+    frames (include/asg_hip.h::asg_beam_word_conf_window_*: the kept pair sets, the emissions and alpha -- about that many times
+    N + 4 * beam_size values more per slot, whatever the length of the stream).  `advance` then returns a
+    `BeamWordWindowConfCommit`: the eight fields and, for every word it commits, `word_frames` (the absolute frame of the word's
+    separator) and `word_confidences` (the posterior, at the moment of the commit, that this word ends within `frame_tolerance`
+    frames of that frame: `BeamWordStream(keep_lattice=True).result_confidence(frame_tolerance)`'s value at that position, bit
+    for bit while bit 0 of `status` is clear), -1 and 0 behind the words; it is three launches and still captures.
+    `result_confidence` gives the same for the uncommitted tail.  `frame_tolerance` (0 .. 64) and `max_chunk` (default `window`;
+    a longer chunk raises ValueError) size the state and are fixed for the life of the stream.  The eight fields, `result`,
+    `result_nbest` and `reset` return what they return without `keep_lattice`, byte for byte, with or without a look-ahead (the
+    lattice weighs the pairs plainly, as `beam_decode_words_confidence` does).  The lattice pass keeps a frame's set in LDS, so
+    beam_size is bounded as for `beam_decode_words_confidence` (8179 float32, 6816 float64).  alpha and the normaliser grow with
+    the stream, as the scores do: float32 loses resolution in a posterior as they pass about 1e5, so streams of hours want
+    float64.
     """
     _API, _WIDE, _NARROW = "asg_beam_word_window", 5, 5
     _check_automaton, _compile = BeamWordStream._check_automaton, BeamWordStream._compile      # the automaton is BeamWordStream's,
@@ -754,12 +773,18 @@ class BeamWordWindowStream(_Stream):
 
     def __init__(self, transition, lexicon, word_lm, batch_size, window, commit_every=None, beam_size=256,
                  beam_threshold=float("inf"), lm_weight=1.0, word_score=0.0, token_score=0.0, dtype=None, device=None,
-                 lookahead=None):
+                 lookahead=None, keep_lattice=False, frame_tolerance=0, max_chunk=None):
         self.lm_weight, self.word_score, self.token_score, self.lookahead = lm_weight, word_score, token_score, lookahead
+        self.keep_lattice = bool(keep_lattice)
+        shape = (window, commit_every)
+        if self.keep_lattice:
+            self._API = "asg_beam_word_conf_window"            # the same calls in the same order over the wider state, whose
+            shape += (frame_tolerance, max_chunk)              # shape has two more parameters
         self._nbest_work = {}                                  # nbest -> the scratch of result_nbest (not part of the state)
-        super().__init__(transition, (lexicon, word_lm), batch_size, (window, commit_every), beam_size, beam_threshold,
+        super().__init__(transition, (lexicon, word_lm), batch_size, shape, beam_size, beam_threshold,
                          transition.dtype if dtype is None else dtype, device)
-        self.window, self.commit_every = self._shape
+        self.window, self.commit_every = self._shape[:2]
+        self.frame_tolerance, self.max_chunk = self._shape[2:] if self.keep_lattice else (None, None)
 
     def reset(self, mask=None):
         """Start new utterances: in every slot (mask None), or in the slots where `mask` (bool or integer [B]) is not zero --
@@ -771,14 +796,24 @@ class BeamWordWindowStream(_Stream):
         committed, a named tuple
           path, states, lm_states, tokens, words [B, window + Tc] int64, -1 behind the data: label, automaton state and LM state
           of every newly committed frame, and the tokens and words they add to the transcript (both go on across calls);
-          token_lengths, word_lengths [B]; frames [B], the number of frames committed by this call."""
-        path, states, lm_states, tokens, words, frames, token_lengths, word_lengths = self._advance(chunk, chunk_lengths)
-        return BeamWordWindowCommit(path, states, lm_states, tokens, token_lengths, words, word_lengths, frames)
+          token_lengths, word_lengths [B]; frames [B], the number of frames committed by this call.
+        With `keep_lattice` also word_frames [B, window + Tc] int64 (-1 behind the words) and word_confidences [B, window + Tc]
+        (0 behind the words) of the committed words: see the class."""
+        if self.keep_lattice and chunk.dim() == 3 and chunk.shape[0] > self.max_chunk:   # (the ring holds max_chunk frames
+            raise ValueError("torch_asg_amd: a chunk of %d frames exceeds max_chunk = %d"    # behind an attempt)
+                             % (chunk.shape[0], self.max_chunk))
+        path, states, lm_states, tokens, words, frames, token_lengths, word_lengths, *conf = self._advance(chunk, chunk_lengths)
+        plain = BeamWordWindowCommit(path, states, lm_states, tokens, token_lengths, words, word_lengths, frames)
+        return BeamWordWindowConfCommit(*plain, *conf) if self.keep_lattice else plain
 
     def _commit_outputs(self, Tc):
-        wide = torch.empty(5, self.batch_size, self.window + Tc, dtype=torch.int64, device=self.device)
-        narrow = torch.empty(3, self.batch_size, dtype=torch.int64, device=self.device)
-        return tuple(wide) + tuple(narrow)                     # path, states, lm_states, tokens, words; frames, two lengths
+        B, cols, dev = self.batch_size, self.window + Tc, self.device
+        wide = torch.empty(5, B, cols, dtype=torch.int64, device=dev)
+        narrow = torch.empty(3, B, dtype=torch.int64, device=dev)
+        outs = tuple(wide) + tuple(narrow)                     # path, states, lm_states, tokens, words; frames, two lengths
+        if self.keep_lattice:                                  # ... word_frames, word_confidences
+            outs += (torch.empty(B, cols, dtype=torch.int64, device=dev), torch.empty(B, cols, dtype=self.dtype, device=dev))
+        return outs
 
     def result(self, final=False):
         """The best hypothesis of every slot for the frames that are not committed yet, without changing the state -> a named
@@ -816,7 +851,7 @@ class BeamWordWindowStream(_Stream):
         L = _lib.lib()
         B, dev, W = self.batch_size, self.device, self.window
         with be._guard(dev):
-            what = "asg_beam_word_window_nbest" + ("" if self.lookahead is None else "_la")
+            what = self._API + "_nbest" + ("" if self.lookahead is None else "_la")
             fn = getattr(L, what)
 
             def call(work, nbytes, *outs):
@@ -825,8 +860,8 @@ class BeamWordWindowStream(_Stream):
             work = self._nbest_work.get(nbest)
             if work is None:
                 abi_dtype = _lib.ASG_DTYPE_F32 if self.dtype == torch.float32 else _lib.ASG_DTYPE_F64
-                nbytes = int(L.asg_beam_word_window_nbest_work_bytes(*self._views, B, abi_dtype, self.beam_size, *self._shape,
-                                                                     nbest))
+                nbytes = int(getattr(L, self._API + "_nbest_work_bytes")(*self._views, B, abi_dtype, self.beam_size,
+                                                                         *self._shape, nbest))
                 if nbytes == 0:                                # the library refuses the arguments: its call says why
                     _lib.check(call(None, 0, *(None,) * 12, 0, None), what)
                 work = self._nbest_work[nbest] = be._buf(nbytes, dev)
@@ -841,6 +876,38 @@ class BeamWordWindowStream(_Stream):
                             be._stream(dev)), what)
         return BeamWordWindowNbest(scores, wide[0], lengths[0], wide[1], lengths[1], narrow[0], align[0], align[1], align[2],
                                    narrow[1], narrow[2], narrow[3])
+
+    def result_confidence(self, final=False):
+        """`result(final)` with a confidence and an end frame for every word of the uncommitted tail, from the lattice ring
+        (`keep_lattice=True`; RuntimeError without it, without touching the device) -> a named tuple
+          `result(final)`'s eleven fields as it returns them;
+          word_frames [B, window] int64, the absolute frame at which tail word k ends (the frame of its separator, or the number
+          of frames consumed for the word the final step closes), -1 behind the words;
+          word_confidences [B, window], the posterior that this word ends within the stream's `frame_tolerance` of that frame,
+          over the paths through the kept pair sets of all frames consumed, 0 behind the words; normalisers [B].
+        final=True ends the paths as `beam_decode_words` does: while bit 0 of `status` is clear the values are
+        `beam_decode_words_confidence`'s for those words, bit for bit.  Two launches, no synchronisation; it only reads the
+        state (`advance` has already brought the alpha rows up to the frames consumed)."""
+        if not self.keep_lattice:
+            raise RuntimeError("torch_asg_amd: result_confidence needs the lattice of the search: build the stream with "
+                               "keep_lattice=True")
+        be = _asg.native()
+        L = _lib.lib()
+        B, dev, W = self.batch_size, self.device, self.window
+        transition = self.transition
+        what = "asg_beam_word_conf_window_confidence" + ("" if self.lookahead is None else "_la")
+        with be._guard(dev):
+            real = torch.empty(2, B, dtype=self.dtype, device=dev)                 # scores, normalisers
+            wide = torch.empty(6, B, W, dtype=torch.int64, device=dev)             # path, tokens, states, lm_states, words, frames
+            conf = torch.empty(B, W, dtype=self.dtype, device=dev)
+            narrow = torch.empty(5, B, dtype=torch.int64, device=dev)              # two lengths, frames, committed, status
+            res = self._outputs(real[0], wide[:5], narrow)
+            ts = (ctypes.c_int64 * 2)(*transition.stride())
+            _lib.check(getattr(L, what)(
+                None, *self._views, *self._look, B, self.beam_size, *self._shape, self._state.data_ptr(), self._state.numel(),
+                transition.data_ptr(), ts, 1 if final else 0, *[t.data_ptr() for t in res[:8]], wide[5].data_ptr(),
+                conf.data_ptr(), real[1].data_ptr(), *[t.data_ptr() for t in res[8:]], 0, be._stream(dev)), what)
+        return BeamWordWindowConfidence(*res, wide[5], conf, real[1])
 
     @staticmethod
     def _outputs(scores, wide, narrow):
