@@ -1232,6 +1232,59 @@ int asg_graph_full_backward(asg_ctx *ctx, const asg_problem *p, const asg_token_
                             void *grad_transition, void *scratch, size_t scratch_bytes, int flags, void *stream);
 int asg_graph_target_scores(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_loss *gl, void *out, void *stream);
 
+/* ---- Score of one small TARGET GRAPH PER UTTERANCE, and its gradients: the numerator of an ASG loss whose transcript is "one
+ * of these" (alternative spellings, several segmentations, optional fillers).  No counterpart in the reference.  Graph b has
+ * K_b = nk[b] <= Kmax <= 1024 nodes, node k with a label l_k, a start and a final weight (-inf: neither), and E_b = row[b][K_b]
+ * <= Emax weighted edges stored as a CSR of incoming edges per node, ascending by source; the stay on a node is implicit.  For
+ * utterance b with len = clamp(input_lengths[b], 0, T), in the dtype of the problem:
+ *   f_e         = tr[l_k][l_src_e] + edge_w[e]                 (folded once per utterance, rounded in the dtype)
+ *   alpha[0][k] = start_w[k] + I[0][l_k]
+ *   alpha[t][k] = lse(stay: alpha[t-1][k] + tr[l_k][l_k];  edge e into k, ascending: alpha[t-1][src_e] + f_e) + I[t][l_k]
+ *   scores[b]   = lse_k(alpha[len-1][k] + final_w[k])          (-inf, never NaN, when len == 0, K_b == 0 or no path exists)
+ * every lse max-then-sum in that order.  For a chain this is asg_aligned_forward's score.
+ * Backward: grad_inputs [T,B,N] (contiguous, every element written, zero rows at t >= len) = grad_scores[b] * the posteriors of
+ * the nodes summed per label, nodes ascending; grad_transition [N,N] (contiguous, every element written) = for each label pair
+ * the sum, in the order of the batch-wide list pslot, of grad_scores[b] * the posterior of that stay or edge summed over t >= 1.
+ * No float atomics and fixed orders: bit-identical run to run.  It needs the alpha that the forward stored in `work`
+ * (ASG_FLAG_GRAPH_LOSS_KEEP_ALPHA), the scores of that forward and the same problem.  Every output is written by kernels (no
+ * memset), nothing synchronises: a warm call can be captured.
+ *   work:    asg_target_graph_work_bytes(p, tg, store) = store ? T * Kmax * B * e : 0 bytes (e = 4 or 8)
+ *   scratch: asg_target_graph_scratch_bytes(p, tg) = B * (Kmax + Emax) * e bytes
+ * One workgroup per utterance, one thread per node, everything of the graph in LDS.  Limits (ASG_ERR_UNSUPPORTED beyond, and the
+ * size calls return 0): Kmax <= 1024 and Emax <= asg_target_graph_max_edges(dtype, Kmax) = (128 KiB - Kmax * (5 * e + 4)) /
+ * (2 * e + 4), what the backward keeps in LDS beside its vectors; B * (Kmax + Emax) < 2^31; N <= 2^16.  p->B must be tg->B.
+ * Nothing of the graphs is validated on the device. */
+typedef struct asg_target_graphs {
+    int64_t B, Kmax, Emax;         /* utterances; the padded node and edge counts                           */
+    int64_t npairs;                /* distinct label pairs (i, j) over every stay and edge of the batch     */
+    int32_t N, dtype;              /* labels; ASG_DTYPE_F32 / _F64 of the weights                           */
+    const int32_t *nk;             /* [B] nodes of graph b                                                  */
+    const int32_t *label;          /* [B,Kmax] label of node k                                              */
+    const int32_t *row;            /* [B,Kmax+1] CSR offsets of the incoming edges of node k                */
+    const int32_t *src;            /* [B,Emax] source node of each incoming edge, ascending per target      */
+    const int32_t *tgt;            /* [B,Emax] target node of each incoming edge                            */
+    const int32_t *orow;           /* [B,Kmax+1] CSR offsets of the outgoing edges of node k                */
+    const int32_t *oedge;          /* [B,Emax] incoming-edge index of each outgoing edge, ascending by (src, tgt) */
+    const int32_t *nlab;           /* [B] distinct labels of graph b                                        */
+    const int32_t *lab;            /* [B,Kmax] the distinct labels, ascending                               */
+    const int32_t *lrow;           /* [B,Kmax+1] CSR offsets of the nodes of each distinct label            */
+    const int32_t *lnode;          /* [B,Kmax] nodes grouped by label, ascending                            */
+    const void *start_w;           /* [B,Kmax] start weights, -inf where not a start                        */
+    const void *final_w;           /* [B,Kmax] final weights, -inf where not a final                        */
+    const void *edge_w;            /* [B,Emax] edge weights                                                 */
+    const int64_t *pkey;           /* [npairs] label pair l_dst * N + l_src, ascending                      */
+    const int32_t *pseg;           /* [npairs+1] offsets of each pair's entries in pslot                    */
+    const int32_t *pslot;          /* b * (Kmax + Emax) + slot of every stay (slot k) and edge (slot Kmax + e), sorted by (pair, b, slot) */
+} asg_target_graphs;
+int64_t asg_target_graph_max_edges(int dtype, int64_t Kmax);      /* -1: Kmax itself is beyond the limit */
+size_t asg_target_graph_work_bytes(const asg_problem *p, const asg_target_graphs *tg, int store);
+size_t asg_target_graph_scratch_bytes(const asg_problem *p, const asg_target_graphs *tg);
+int asg_target_graph_forward(asg_ctx *ctx, const asg_problem *p, const asg_target_graphs *tg, void *work, size_t work_bytes,
+                             void *scores, int flags, void *stream);
+int asg_target_graph_backward(asg_ctx *ctx, const asg_problem *p, const asg_target_graphs *tg, const void *work,
+                              size_t work_bytes, const void *scores, const void *grad_scores, void *grad_inputs,
+                              void *grad_transition, void *scratch, size_t scratch_bytes, int flags, void *stream);
+
 /* ---- BEAM-PRUNED full score of the same composed lattice, and its gradients: asg_graph_full_forward / _backward over the
  * lattice that asg_beam_decode_graph's search keeps -- a normaliser Z_K whose work per frame follows the beam and not Q or E, so a
  * criterion can be trained with the automata (4-grams, lexicon tries) the beam decoder was built for.  No counterpart in the

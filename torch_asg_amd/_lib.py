@@ -58,7 +58,9 @@ SYMBOLS = ["asg_hip_version", "asg_hip_strerror", "asg_ctx_create", "asg_ctx_des
            "asg_beam_word_conf_window_state_bytes", "asg_beam_word_conf_window_reset", "asg_beam_word_conf_window_advance",
            "asg_beam_word_conf_window_advance_la", "asg_beam_word_conf_window_result", "asg_beam_word_conf_window_result_la",
            "asg_beam_word_conf_window_nbest_work_bytes", "asg_beam_word_conf_window_nbest", "asg_beam_word_conf_window_nbest_la",
-           "asg_beam_word_conf_window_confidence", "asg_beam_word_conf_window_confidence_la"]
+           "asg_beam_word_conf_window_confidence", "asg_beam_word_conf_window_confidence_la",
+           "asg_target_graph_max_edges", "asg_target_graph_work_bytes", "asg_target_graph_scratch_bytes",
+           "asg_target_graph_forward", "asg_target_graph_backward"]
 ABI_VERSION = 230        # include/asg_hip.h: ASG_HIP_VERSION this package was written against
 
 
@@ -82,6 +84,15 @@ class AsgTokenGraphLoss(ctypes.Structure):
     _fields_ = [("graph", ctypes.POINTER(AsgTokenGraph)), ("S", ctypes.c_int64), ("start", ctypes.c_int32),
                 ("reserved", ctypes.c_int32)] + [(n, ctypes.c_void_p) for n in ("tgt", "orow", "oedge", "lrow", "lq", "pkey", "pedge",
                                                                                "next", "arcw", "finw")]
+
+
+TARGET_GRAPH_ARRAYS = ("nk", "label", "row", "src", "tgt", "orow", "oedge", "nlab", "lab", "lrow", "lnode", "start_w", "final_w",
+                       "edge_w", "pkey", "pseg", "pslot")
+
+
+class AsgTargetGraphs(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int64), ("Kmax", ctypes.c_int64), ("Emax", ctypes.c_int64), ("npairs", ctypes.c_int64),
+                ("N", ctypes.c_int32), ("dtype", ctypes.c_int32)] + [(n, ctypes.c_void_p) for n in TARGET_GRAPH_ARRAYS]
 
 
 class AsgTokenGraphBeam(ctypes.Structure):
@@ -301,6 +312,15 @@ def lib():
     L.asg_graph_full_forward.argtypes = [vp, pp, lp, vp, sz, vp, ci, vp]
     L.asg_graph_full_backward.argtypes = [vp, pp, lp, vp, sz, vp, vp, vp, vp, vp, sz, ci, vp]
     L.asg_graph_target_scores.argtypes = [vp, pp, lp, vp, vp]
+    tp = ctypes.POINTER(AsgTargetGraphs)
+    L.asg_target_graph_max_edges.restype = i64
+    L.asg_target_graph_max_edges.argtypes = [ci, i64]
+    L.asg_target_graph_work_bytes.restype = sz
+    L.asg_target_graph_work_bytes.argtypes = [pp, tp, ci]
+    L.asg_target_graph_scratch_bytes.restype = sz
+    L.asg_target_graph_scratch_bytes.argtypes = [pp, tp]
+    L.asg_target_graph_forward.argtypes = [vp, pp, tp, vp, sz, vp, ci, vp]
+    L.asg_target_graph_backward.argtypes = [vp, pp, tp, vp, sz, vp, vp, vp, vp, vp, sz, ci, vp]
     L.asg_loss_fused_supported.argtypes = [pp]
     L.asg_loss_fused_scratch_bytes.restype = sz
     L.asg_loss_fused_scratch_bytes.argtypes = [pp]

@@ -843,6 +843,42 @@ class HipBackend:
                 gtr = gtr_g if gtr is None else gtr + gtr_g
         return gtr, gin
 
+    def _target_graph_args(self, inputs, transition, graphs, input_lengths):
+        """Checks of the target-graph entry points -> `_lattice_forward`'s `prepare` result.  The limits are checked here, by
+        name; the Q it returns is 0 because a workspace size of 0 is no refusal here (a forward that keeps nothing needs none)."""
+        from . import target_graph as _tg
+        self._check(inputs, transition, None, input_lengths, None)
+        if inputs.dtype not in (torch.float32, torch.float64):
+            raise RuntimeError("torch_asg_amd: expected scalar type Float or Double but found %s" % inputs.dtype)
+        if not isinstance(graphs, _tg.TargetGraphs):
+            raise TypeError("torch_asg_amd: graphs must be a torch_asg_amd.TargetGraphs")
+        T, B, N = inputs.shape
+        if graphs.N != N or graphs.B != B:
+            raise RuntimeError("torch_asg_amd: the target graphs are %d utterances over %d labels but the emissions have B = %d, "
+                               "N = %d" % (graphs.B, graphs.N, B, N))
+        if input_lengths is not None and tuple(input_lengths.shape) != (B,):
+            raise RuntimeError("torch_asg_amd: input_lengths must have shape [%d]" % B)
+        bound = int(_lib.lib().asg_target_graph_max_edges(
+            _lib.ASG_DTYPE_F32 if inputs.dtype == torch.float32 else _lib.ASG_DTYPE_F64, graphs.Kmax))
+        if graphs.Emax > bound:
+            raise RuntimeError("torch_asg_amd: target graphs with Kmax = %d nodes and Emax = %d edges do not fit one workgroup's "
+                               "LDS: at most %d edges per graph at this Kmax in %s" % (graphs.Kmax, graphs.Emax, bound, inputs.dtype))
+        compiled = graphs.compile(inputs.device, inputs.dtype)
+        return (_tg.abi_target_graphs(compiled),), 0, compiled
+
+    def target_graph_forward(self, inputs, transition, graphs, input_lengths, store=False):
+        """Score of each utterance's target graph -> (scores[B], saved); see include/asg_hip.h::asg_target_graph_forward.  One
+        launch for the whole batch.  With `store`, saved = [(0, B, work)], the stored alpha for target_graph_backward."""
+        return self._lattice_forward("asg_target_graph_forward", "asg_target_graph_work_bytes",
+                                     lambda: self._target_graph_args(inputs, transition, graphs, input_lengths), (), (), inputs,
+                                     transition, None, input_lengths, None, store, float("inf"))
+
+    def target_graph_backward(self, saved, scores, grad_scores, inputs, transition, graphs, input_lengths):
+        """(grad_transition[N,N], grad_inputs[T,B,N]) of sum_b grad_scores[b] * scores[b] from target_graph_forward's alpha."""
+        return self._lattice_backward("asg_target_graph_backward", "asg_target_graph_scratch_bytes",
+                                      lambda: self._target_graph_args(inputs, transition, graphs, input_lengths), (), saved,
+                                      scores, grad_scores, inputs, transition, None, input_lengths, None)
+
     def _beam_loss_args(self, inputs, transition, graph, input_lengths, targets, target_lengths, lm_weight, token_score):
         """Checks shared by the beam-pruned loss entry points -> ((the asg_token_graph_beam_loss view,), Q, the compiled graph it
         points into): `_lattice_forward`'s `prepare`."""
@@ -1749,6 +1785,62 @@ def graph_asg_loss(inputs, targets, transition, graph, input_lengths=None, targe
                        reduction)
 
 
+class TargetGraphScore(torch.autograd.Function):
+    """Score of each utterance's own target graph, [B] (asg_target_graph_forward / _backward).  alpha is stored only when a
+    gradient w.r.t. inputs or transition is needed."""
+
+    @staticmethod
+    def forward(ctx, inputs, transition, graphs, input_lengths):
+        store = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
+        scores, saved = native().target_graph_forward(inputs, transition, graphs, input_lengths, store)
+        ctx.save_for_backward(inputs, transition, input_lengths, scores)
+        ctx.saved, ctx.graphs = saved, graphs
+        return scores
+
+    @staticmethod
+    def backward(ctx, grad):
+        inputs, transition, input_lengths, scores = ctx.saved_tensors
+        gtr, gin = native().target_graph_backward(ctx.saved, scores, grad, inputs, transition, ctx.graphs, input_lengths)
+        return gin, gtr, None, None
+
+
+def target_graph_score(inputs, transition, graphs, input_lengths=None):
+    """logsumexp over every alignment of every label path of utterance b's own target graph (`graphs`, a `TargetGraphs` of B
+    graphs): "the transcript is one of these" -- alternative spellings, several segmentations, an optional filler.  For a
+    chain it is the force-aligned score (`FAC`).  Differentiable w.r.t. `inputs` and `transition` (the graphs' weights are
+    constants).  Returns [B] in the dtype of the emissions; -inf for an utterance of length 0, an empty graph or a graph without
+    any alignment.  Inputs, strides and widening of float16 / bfloat16 as `graph_full_score`; one launch serves the batch."""
+    return TargetGraphScore.apply(_widen(inputs, transition), transition, graphs, input_lengths)
+
+
+def _target_graph_loss(inputs, graphs, transition, input_lengths, reduction, weights=None):
+    """[B] losses FCC - target_graph_score with `_graph_loss`'s masking, then `weights(inputs, input_lengths, None)` and the
+    reduction."""
+    inputs = _widen(inputs, transition)
+    if input_lengths is None:
+        input_lengths = torch.full((inputs.shape[1],), inputs.shape[0], dtype=torch.int64, device=inputs.device)
+    full = FCC.apply(transition, inputs, None, input_lengths, None)
+    aligned = TargetGraphScore.apply(inputs, transition, graphs, input_lengths)
+    fd, ad = full.detach(), aligned.detach()
+    ok_f, ok_a = torch.isfinite(fd), torch.isfinite(ad)
+    zero = torch.zeros_like(fd)
+    value = torch.where(ok_a, fd - ad, torch.full_like(fd, float("inf")))
+    per = value + torch.where(ok_f, full - fd, zero) - torch.where(ok_a, aligned - ad, zero)
+    w = weights(inputs, input_lengths, None) if weights is not None else None
+    if w is not None:
+        per = per * w
+    return _reduce(per, reduction)
+
+
+def target_graph_asg_loss(inputs, graphs, transition, input_lengths=None, reduction='none'):
+    """ASG loss whose numerator is `target_graph_score`: loss[b] = S_full[b] - target_graph_score[b], the full-lattice score
+    from `FCC`.  exp(-loss) is the probability that the transcript is any label path of the utterance's graph (weighted by the
+    graph's weights).  +inf, never NaN, where the graph has no alignment (length 0, an empty graph, every path longer than the
+    utterance); those utterances' gradient rows hold only the full-lattice posterior.  reduction 'none' (default), 'sum' or
+    'mean'."""
+    return _target_graph_loss(inputs, graphs, transition, input_lengths, reduction)
+
+
 class BeamGraphFullScore(torch.autograd.Function):
     """Beam-pruned full score of the ASG lattice composed with a token automaton, [B] (asg_beam_graph_full_forward /
     _backward).  The kept sets are constants of the gradient; alpha is stored only when a gradient w.r.t. inputs or transition
@@ -2176,6 +2268,14 @@ class ASGLoss(nn.Module):
         emissions are widened to the dtype of `transition`; batch-major views ([B,T,N] transposed) need no copy."""
         return _graph_loss(inputs, targets, self.transition, graph, input_lengths, target_lengths, lm_weight, token_score,
                            max_work_bytes, self.reduction, None, self._utterance_weights)
+
+    def target_graph_loss(self, inputs, graphs, input_lengths=None):
+        """`torch_asg_amd.target_graph_asg_loss` under this module's transition matrix, reduction and scale_mode.  A graph has
+        no single length: the `target_size*` scale modes raise ValueError."""
+        if self.scale_mode.startswith('target'):
+            raise ValueError("ASGLoss.target_graph_loss: scale_mode %r needs one target length per utterance; a target graph "
+                             "has none (use 'none' or 'input_size*')" % self.scale_mode)
+        return _target_graph_loss(inputs, graphs, self.transition, input_lengths, self.reduction, self._utterance_weights)
 
     def beam_graph_loss(self, inputs, targets, graph, input_lengths=None, target_lengths=None, lm_weight=1.0, token_score=0.0,
                         max_work_bytes=1 << 30, beam_size=256, beam_threshold=float("inf")):

@@ -2745,6 +2745,82 @@ int asg_graph_target_scores(asg_ctx *ctx, const asg_problem *p, const asg_token_
                                    launch_graph_target_scores<double>(P, L, out, (hipStream_t) stream)));
 }
 
+// sized: the size calls take the problem of any group of utterances; the launches take the whole batch of the graphs
+static int check_target_graphs(const asg_problem *p, const asg_target_graphs *tg, bool sized) {
+    int rc = check_decode(p);
+    if (rc) return rc;
+    if (!tg || tg->dtype != p->dtype || tg->N != p->N || tg->B < 1 || tg->Kmax < 0 || tg->Emax < 0 || tg->npairs < 0)
+        return ASG_ERR_INVALID;
+    if (!sized && tg->B != p->B) return ASG_ERR_INVALID;
+    if (p->N > (1 << 16) || tg->Kmax > kTargetGraphMaxNodes) return ASG_ERR_UNSUPPORTED;
+    if (tg->Emax > target_graph_max_edges(p->dtype == ASG_DTYPE_F64 ? 8 : 4, (int) tg->Kmax)) return ASG_ERR_UNSUPPORTED;
+    if (tg->B * (tg->Kmax + tg->Emax) >= (int64_t) 1 << 31) return ASG_ERR_UNSUPPORTED;
+    if (!tg->nk || !tg->nlab || !tg->row || !tg->orow || !tg->lrow || !tg->pseg) return ASG_ERR_INVALID;
+    if (tg->Kmax > 0 && (!tg->label || !tg->lab || !tg->lnode || !tg->start_w || !tg->final_w)) return ASG_ERR_INVALID;
+    if (tg->Emax > 0 && (!tg->src || !tg->tgt || !tg->oedge || !tg->edge_w)) return ASG_ERR_INVALID;
+    if (tg->npairs > 0 && (!tg->pkey || !tg->pslot)) return ASG_ERR_INVALID;
+    return ASG_OK;
+}
+
+static TargetGraphArgs to_target_graph_args(const asg_target_graphs *tg) {
+    TargetGraphArgs G{};
+    G.Kmax = (int) tg->Kmax; G.Emax = (int) tg->Emax; G.npairs = tg->npairs;
+    G.nk = tg->nk; G.label = tg->label; G.row = tg->row; G.src = tg->src; G.tgt = tg->tgt; G.orow = tg->orow; G.oedge = tg->oedge;
+    G.nlab = tg->nlab; G.lab = tg->lab; G.lrow = tg->lrow; G.lnode = tg->lnode;
+    G.start_w = tg->start_w; G.final_w = tg->final_w; G.edge_w = tg->edge_w;
+    G.pkey = tg->pkey; G.pseg = tg->pseg; G.pslot = tg->pslot;
+    return G;
+}
+
+int64_t asg_target_graph_max_edges(int dtype, int64_t Kmax) {
+    if ((dtype != ASG_DTYPE_F32 && dtype != ASG_DTYPE_F64) || Kmax < 0 || Kmax > kTargetGraphMaxNodes) return -1;
+    return target_graph_max_edges(dtype == ASG_DTYPE_F64 ? 8 : 4, (int) Kmax);
+}
+
+size_t asg_target_graph_work_bytes(const asg_problem *p, const asg_target_graphs *tg, int store) {
+    if (check_target_graphs(p, tg, true) != ASG_OK) return 0;
+    return target_graph_work_bytes(p->dtype == ASG_DTYPE_F64 ? 8 : 4, (int) p->T, (int) p->B, (int) tg->Kmax, store != 0);
+}
+
+size_t asg_target_graph_scratch_bytes(const asg_problem *p, const asg_target_graphs *tg) {
+    if (check_target_graphs(p, tg, true) != ASG_OK) return 0;
+    return target_graph_scratch_bytes(p->dtype == ASG_DTYPE_F64 ? 8 : 4, (int) p->B, (int) tg->Kmax, tg->Emax);
+}
+
+int asg_target_graph_forward(asg_ctx *ctx, const asg_problem *p, const asg_target_graphs *tg, void *work, size_t work_bytes,
+                             void *scores, int flags, void *stream) {
+    (void) ctx;
+    int rc = check_target_graphs(p, tg, false);
+    if (rc) return rc;
+    const bool store = (flags & ASG_FLAG_GRAPH_LOSS_KEEP_ALPHA) != 0;
+    const size_t need = asg_target_graph_work_bytes(p, tg, store);
+    if (!scores || (need && !work)) return ASG_ERR_INVALID;
+    if (work_bytes < need) return ASG_ERR_WORKSPACE;
+    const Problem P = to_problem(p);
+    const TargetGraphArgs G = to_target_graph_args(tg);
+    return hip_status(ASG_DISPATCH(p, launch_target_graph_forward<float>(P, G, store, work, scores, (hipStream_t) stream),
+                                   launch_target_graph_forward<double>(P, G, store, work, scores, (hipStream_t) stream)));
+}
+
+int asg_target_graph_backward(asg_ctx *ctx, const asg_problem *p, const asg_target_graphs *tg, const void *work,
+                              size_t work_bytes, const void *scores, const void *grad_scores, void *grad_inputs,
+                              void *grad_transition, void *scratch, size_t scratch_bytes, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    int rc = check_target_graphs(p, tg, false);
+    if (rc) return rc;
+    const size_t wneed = asg_target_graph_work_bytes(p, tg, 1), sneed = asg_target_graph_scratch_bytes(p, tg);
+    if (!scores || !grad_scores || !grad_inputs || !grad_transition || (wneed && !work) || (sneed && !scratch))
+        return ASG_ERR_INVALID;
+    if (work_bytes < wneed || scratch_bytes < sneed) return ASG_ERR_WORKSPACE;
+    const Problem P = to_problem(p);
+    const TargetGraphArgs G = to_target_graph_args(tg);
+    return hip_status(ASG_DISPATCH(p,
+        launch_target_graph_backward<float>(P, G, work, scores, grad_scores, grad_inputs, grad_transition, scratch,
+                                            (hipStream_t) stream),
+        launch_target_graph_backward<double>(P, G, work, scores, grad_scores, grad_inputs, grad_transition, scratch,
+                                             (hipStream_t) stream)));
+}
+
 int asg_backward(asg_ctx *ctx, const asg_problem *p, const void *state, size_t state_bytes,
                  const void *grad_full, const void *grad_aligned, void *scratch, size_t scratch_bytes,
                  void *grad_transition, void *grad_inputs, int flags, void *stream) {

@@ -762,6 +762,30 @@ hipError_t launch_graph_loss_backward(const Problem &P, const GraphArgs &G, cons
 template <typename R>
 hipError_t launch_graph_target_scores(const Problem &P, const GraphLossArgs &L, void *out, hipStream_t stream);
 
+// ---- Score and gradients over one small target graph PER UTTERANCE (asg_target_graph.hip).  The padded arrays of
+// asg_target_graphs.  Work = alpha [B][T][Kmax] when stored (nothing otherwise); scratch = [B][Kmax + Emax] per-stay /
+// per-edge posterior sums (slot k: the stay of node k; slot Kmax + e: incoming edge e).
+constexpr int kTargetGraphMaxNodes = 1024;
+struct TargetGraphArgs {
+    int Kmax, Emax;
+    int64_t npairs;
+    const int *nk, *label, *row, *src, *tgt, *orow, *oedge;     // [B], [B,Kmax], [B,Kmax+1], [B,Emax] x2, [B,Kmax+1], [B,Emax]
+    const int *nlab, *lab, *lrow, *lnode;                       // [B], [B,Kmax], [B,Kmax+1], [B,Kmax]
+    const void *start_w, *final_w, *edge_w;                     // [B,Kmax] x2, [B,Emax] in the dtype of the problem
+    const int64_t *pkey;                                        // [npairs] label pair i*N + j, ascending
+    const int *pseg, *pslot;                                    // [npairs+1], [P]: b * (Kmax + Emax) + slot, sorted by (pair, b, slot)
+};
+int64_t target_graph_max_edges(int elem, int Kmax);
+size_t target_graph_work_bytes(int elem, int T, int B, int Kmax, bool store);
+size_t target_graph_scratch_bytes(int elem, int B, int Kmax, int64_t Emax);
+template <typename R>
+hipError_t launch_target_graph_forward(const Problem &P, const TargetGraphArgs &G, bool store, void *work, void *scores,
+                                       hipStream_t stream);
+template <typename R>
+hipError_t launch_target_graph_backward(const Problem &P, const TargetGraphArgs &G, const void *work, const void *scores,
+                                        const void *grad_scores, void *grad_inputs, void *grad_transition, void *scratch,
+                                        hipStream_t stream);
+
 // launches of the resident-slice forward kernel (256 < N <= 2048) of this process whose bounded waits ran out (asg_generic.hip)
 unsigned cluster_timeouts();
 
