@@ -1285,6 +1285,29 @@ int asg_target_graph_backward(asg_ctx *ctx, const asg_problem *p, const asg_targ
                               size_t work_bytes, const void *scores, const void *grad_scores, void *grad_inputs,
                               void *grad_transition, void *scratch, size_t scratch_bytes, int flags, void *stream);
 
+/* ---- BEST PATH of each utterance's target graph: which alternative was spoken, where its tokens lie in time, the hard targets
+ * of a next stage.  No counterpart in the reference.  The max-plus recursion over the arrays of asg_target_graphs, in the dtype
+ * of the problem, adds and compares only (len = clamp(input_lengths[b], 0, T)):
+ *   f_e        = tr[l_k][l_src_e] + edge_w[e]                   (rounded once, as asg_target_graph_forward folds it)
+ *   v[0][k]    = start_w[k] + I[0][l_k]
+ *   v[t][k]    = max(stay: v[t-1][k] + tr[l_k][l_k];  edge e into k, ascending: v[t-1][src_e] + f_e) + I[t][l_k]
+ *   bp[t][k]   = k unless some edge is strictly better than the stay; then the source of the first edge that attains the maximum
+ *   scores[b]  = max_k (v[len-1][k] + final_w[k]), the end node the lowest k that attains it
+ *   nodes[b][len-1] = end, nodes[b][t-1] = bp[t][nodes[b][t]], labels[b][t] = l_{nodes[b][t]}
+ *   tokens[b] / token_frames[b]: labels[b][t] and t at t = 0 and wherever nodes[b][t] != nodes[b][t-1]; token_lengths[b] their count
+ * "Stay wins ties" is asg_viterbi's rule: for chains with edge weight 0 scores and nodes are asg_viterbi's scores and positions.
+ * scores [B] in the dtype of the problem; nodes, labels, tokens, token_frames [B,T] and token_lengths [B], all int64, contiguous.
+ * The integer outputs hold -1 at frames >= len, behind token_lengths[b], and everywhere for an utterance whose score is -inf
+ * (len 0, empty graph, no finite path), whose token_lengths is 0.  One launch: forward, backtrace and compaction in the
+ * utterance's workgroup; every output element is written by it (no memset), no float atomics, nothing synchronises: equal
+ * bits run to run, and a warm call can be captured.
+ *   work: asg_target_graph_viterbi_work_bytes(p, tg) = B * T * Kmax * 2 bytes (the back-pointers, 16 bits each)
+ * Limits and return codes are asg_target_graph_forward's (a batch that scores also aligns); the size call returns 0 beyond them. */
+size_t asg_target_graph_viterbi_work_bytes(const asg_problem *p, const asg_target_graphs *tg);
+int asg_target_graph_viterbi(asg_ctx *ctx, const asg_problem *p, const asg_target_graphs *tg, void *work, size_t work_bytes,
+                             void *scores, int64_t *nodes, int64_t *labels, int64_t *tokens, int64_t *token_frames,
+                             int64_t *token_lengths, int flags, void *stream);
+
 /* ---- BEAM-PRUNED full score of the same composed lattice, and its gradients: asg_graph_full_forward / _backward over the
  * lattice that asg_beam_decode_graph's search keeps -- a normaliser Z_K whose work per frame follows the beam and not Q or E, so a
  * criterion can be trained with the automata (4-grams, lexicon tries) the beam decoder was built for.  No counterpart in the

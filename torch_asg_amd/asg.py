@@ -879,6 +879,26 @@ class HipBackend:
                                       lambda: self._target_graph_args(inputs, transition, graphs, input_lengths), (), saved,
                                       scores, grad_scores, inputs, transition, None, input_lengths, None)
 
+    def target_graph_viterbi(self, inputs, transition, graphs, input_lengths):
+        """Best path of each utterance's target graph -> (scores[B], nodes[B,T], labels[B,T], tokens[B,T], token_frames[B,T],
+        token_lengths[B]); see include/asg_hip.h::asg_target_graph_viterbi.  One launch for the whole batch."""
+        L = _lib.lib()
+        T, B, N = inputs.shape
+        dev = inputs.device
+        with self._guard(dev):
+            (tg,), _, keep = self._target_graph_args(inputs, transition, graphs, input_lengths)
+            p, _, input_lengths, _ = self._device_problem(inputs, transition, None, input_lengths, None)
+            work = self._buf(int(L.asg_target_graph_viterbi_work_bytes(ctypes.byref(p), ctypes.byref(tg))), dev)
+            scores = torch.empty(B, dtype=inputs.dtype, device=dev)
+            out = torch.empty(4, B, T, dtype=torch.int64, device=dev)
+            token_lengths = torch.empty(B, dtype=torch.int64, device=dev)
+            # (no context: the call runs on one stream; nothing is created here, so it may run under capture)
+            _lib.check(L.asg_target_graph_viterbi(None, ctypes.byref(p), ctypes.byref(tg), work.data_ptr(), work.numel(),
+                                                  scores.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
+                                                  out[3].data_ptr(), token_lengths.data_ptr(), 0, self._stream(dev)),
+                       "asg_target_graph_viterbi")
+        return scores, out[0], out[1], out[2], out[3], token_lengths
+
     def _beam_loss_args(self, inputs, transition, graph, input_lengths, targets, target_lengths, lm_weight, token_score):
         """Checks shared by the beam-pruned loss entry points -> ((the asg_token_graph_beam_loss view,), Q, the compiled graph it
         points into): `_lattice_forward`'s `prepare`."""
@@ -1841,6 +1861,42 @@ def target_graph_asg_loss(inputs, graphs, transition, input_lengths=None, reduct
     return _target_graph_loss(inputs, graphs, transition, input_lengths, reduction)
 
 
+TargetGraphAlignment = collections.namedtuple("TargetGraphAlignment", ["scores", "nodes", "labels", "tokens", "token_frames",
+                                                                       "token_lengths", "alternatives"])
+
+
+def target_graph_viterbi(inputs, transition, graphs, input_lengths=None):
+    """Best path of utterance b's own target graph (`graphs`, a `TargetGraphs` of B graphs) and its best alignment: which
+    alternative was spoken and where its tokens lie -- the max where `target_graph_score` takes the log-sum.  No gradient.
+
+    Inputs, strides and errors as `target_graph_score`; float16 / bfloat16 emissions are widened to the dtype of `transition`
+    as `viterbi_align` widens them.  Returns a `TargetGraphAlignment`: scores [B]; nodes [B,T], the node occupied at every
+    frame, and labels [B,T], its label; tokens [B,T] and token_frames [B,T], the label and the first frame of every node the
+    path enters; token_lengths [B]; alternatives [B], for graphs from `from_alternatives` / `from_targets` the index of the
+    sequence the path spells (None for graphs built from arrays).  Integer outputs are int64 and hold -1 behind the
+    utterance's length, behind token_lengths[b], and everywhere for an utterance whose score is -inf (length 0, an empty
+    graph, no finite path), whose token_lengths is 0.  A stay wins a tie against an edge, the first (lowest-source) edge wins
+    among edges and the lowest node among ends: for a chain, scores and nodes are `viterbi_align`'s scores and positions."""
+    with torch.no_grad():
+        inputs, transition = _plain(inputs, transition)
+        scores, nodes, labels, tokens, frames, token_lengths = native().target_graph_viterbi(inputs, transition, graphs,
+                                                                                             input_lengths)
+        alternatives = None
+        fa = graphs.final_alternative_on(inputs.device)
+        if fa is not None:
+            T, B = inputs.shape[0], inputs.shape[1]
+            if T == 0 or fa.shape[1] == 0:
+                alternatives = torch.full((B,), -1, dtype=torch.int64, device=inputs.device)
+            else:
+                if input_lengths is None:
+                    at = torch.full((B, 1), T - 1, dtype=torch.int64, device=inputs.device)
+                else:
+                    at = (_on_device(input_lengths, inputs.device, True).clamp(0, T) - 1).clamp(min=0).unsqueeze(1)
+                end = nodes.gather(1, at)                             # -1 where the score is -inf
+                alternatives = torch.where(end >= 0, fa.gather(1, end.clamp(min=0)), end).squeeze(1)
+    return TargetGraphAlignment(scores, nodes, labels, tokens, frames, token_lengths, alternatives)
+
+
 class BeamGraphFullScore(torch.autograd.Function):
     """Beam-pruned full score of the ASG lattice composed with a token automaton, [B] (asg_beam_graph_full_forward /
     _backward).  The kept sets are constants of the gradient; alpha is stored only when a gradient w.r.t. inputs or transition
@@ -2276,6 +2332,11 @@ class ASGLoss(nn.Module):
             raise ValueError("ASGLoss.target_graph_loss: scale_mode %r needs one target length per utterance; a target graph "
                              "has none (use 'none' or 'input_size*')" % self.scale_mode)
         return _target_graph_loss(inputs, graphs, self.transition, input_lengths, self.reduction, self._utterance_weights)
+
+    def target_graph_viterbi(self, inputs, graphs, input_lengths=None):
+        """Best path of each utterance's target graph under this module's transition matrix: see
+        `torch_asg_amd.target_graph_viterbi`."""
+        return target_graph_viterbi(inputs, self.transition, graphs, input_lengths)
 
     def beam_graph_loss(self, inputs, targets, graph, input_lengths=None, target_lengths=None, lm_weight=1.0, token_score=0.0,
                         max_work_bytes=1 << 30, beam_size=256, beam_threshold=float("inf")):

@@ -2821,6 +2821,29 @@ int asg_target_graph_backward(asg_ctx *ctx, const asg_problem *p, const asg_targ
                                              (hipStream_t) stream)));
 }
 
+size_t asg_target_graph_viterbi_work_bytes(const asg_problem *p, const asg_target_graphs *tg) {
+    if (check_target_graphs(p, tg, true) != ASG_OK) return 0;
+    return target_graph_viterbi_work_bytes((int) p->T, (int) p->B, (int) tg->Kmax);
+}
+
+int asg_target_graph_viterbi(asg_ctx *ctx, const asg_problem *p, const asg_target_graphs *tg, void *work, size_t work_bytes,
+                             void *scores, int64_t *nodes, int64_t *labels, int64_t *tokens, int64_t *token_frames,
+                             int64_t *token_lengths, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    int rc = check_target_graphs(p, tg, false);
+    if (rc) return rc;
+    const size_t need = asg_target_graph_viterbi_work_bytes(p, tg);
+    if (!scores || !nodes || !labels || !tokens || !token_frames || !token_lengths || (need && !work)) return ASG_ERR_INVALID;
+    if (work_bytes < need) return ASG_ERR_WORKSPACE;
+    const Problem P = to_problem(p);
+    const TargetGraphArgs G = to_target_graph_args(tg);
+    return hip_status(ASG_DISPATCH(p,
+        launch_target_graph_viterbi<float>(P, G, work, scores, nodes, labels, tokens, token_frames, token_lengths,
+                                           (hipStream_t) stream),
+        launch_target_graph_viterbi<double>(P, G, work, scores, nodes, labels, tokens, token_frames, token_lengths,
+                                            (hipStream_t) stream)));
+}
+
 int asg_backward(asg_ctx *ctx, const asg_problem *p, const void *state, size_t state_bytes,
                  const void *grad_full, const void *grad_aligned, void *scratch, size_t scratch_bytes,
                  void *grad_transition, void *grad_inputs, int flags, void *stream) {

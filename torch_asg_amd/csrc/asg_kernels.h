@@ -786,6 +786,14 @@ hipError_t launch_target_graph_backward(const Problem &P, const TargetGraphArgs 
                                         const void *grad_scores, void *grad_inputs, void *grad_transition, void *scratch,
                                         hipStream_t stream);
 
+// ---- Best path of each utterance's target graph (asg_target_graph_viterbi.hip): one launch, forward + backtrace + token
+// compaction.  Work = the back-pointers [B][T][Kmax], 16 bits each; the integer outputs are [B][T] (token_lengths [B]).
+size_t target_graph_viterbi_work_bytes(int T, int B, int Kmax);
+template <typename R>
+hipError_t launch_target_graph_viterbi(const Problem &P, const TargetGraphArgs &G, void *work, void *scores, int64_t *nodes,
+                                       int64_t *labels, int64_t *tokens, int64_t *token_frames, int64_t *token_lengths,
+                                       hipStream_t stream);
+
 // launches of the resident-slice forward kernel (256 < N <= 2048) of this process whose bounded waits ran out (asg_generic.hip)
 unsigned cluster_timeouts();
 

@@ -22,17 +22,13 @@
 // stay and of its outgoing edges are owned by the thread that pulls beta into that node, live in LDS for the whole utterance
 // and are written once.  No float atomics, every output element written by a kernel (no memset): bit-identical run to run and
 // capturable.  grad_transition: a zero-fill, then one wavefront per label pair that any graph uses.
-#include "asg_common.h"
-#include "asg_kernels.h"
+#include "asg_target_graph_common.h"
 
 namespace asg {
 
 namespace {
 
-constexpr int kTgRed = 256;                     // LDS bytes in front of the vectors (reduction slots, 16 of either dtype)
 constexpr int kTgF = 256;                       // workgroup of the two grad_transition kernels
-// what one workgroup may ask for: the resident route of asg_graph_loss.hip (128 KiB of vectors + its scratch)
-constexpr size_t kTgLds = 128 * 1024 + 256;
 
 template <typename R> __device__ __forceinline__ R texp(R x);
 template <> __device__ __forceinline__ float texp<float>(float x) { return expf(x); }
@@ -40,47 +36,6 @@ template <> __device__ __forceinline__ double texp<double>(double x) { return ::
 template <typename R> __device__ __forceinline__ R tlog(R x);
 template <> __device__ __forceinline__ float tlog<float>(float x) { return logf(x); }
 template <> __device__ __forceinline__ double tlog<double>(double x) { return ::log(x); }
-template <typename R> __device__ __forceinline__ R tmax(R a, R b) { return b > a ? b : a; }
-
-__device__ __forceinline__ int tg_len(const int64_t *in_len, int b, int T) {
-    if (!in_len) return T;
-    const int64_t l = in_len[b];
-    return (int) (l < 0 ? 0 : (l > T ? T : l));
-}
-
-// Workgroup max / sum over W threads in a fixed tree (butterfly in the wavefront, then the wavefronts ascending); the result
-// in every thread.  One wavefront needs neither LDS nor a barrier.
-template <typename R, int W, bool MAX>
-__device__ __forceinline__ R tg_reduce(R v, R *red) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const R u = (R) __shfl_xor(v, o);
-        v = MAX ? tmax(v, u) : v + u;
-    }
-    if (W == 64) return v;
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    v = red[0];
-#pragma unroll
-    for (int s = 1; s < W / 64; ++s) v = MAX ? tmax(v, red[s]) : v + red[s];
-    __syncthreads();
-    return v;
-}
-
-// The arrays of utterance b.
-struct TgView {
-    const int *label, *row, *src, *tgt, *orow, *oedge, *lab, *lrow, *lnode;
-    int K, E, nlab;
-};
-__device__ __forceinline__ TgView tg_view(const TargetGraphArgs &G, int b) {
-    TgView v;
-    const int64_t k0 = (int64_t) b * G.Kmax, r0 = (int64_t) b * (G.Kmax + 1), e0 = (int64_t) b * G.Emax;
-    v.label = G.label + k0; v.row = G.row + r0; v.src = G.src + e0; v.tgt = G.tgt + e0;
-    v.orow = G.orow + r0; v.oedge = G.oedge + e0; v.lab = G.lab + k0; v.lrow = G.lrow + r0; v.lnode = G.lnode + k0;
-    v.K = G.nk[b]; v.nlab = G.nlab[b];
-    v.E = v.K > 0 ? v.row[v.K] : 0;
-    return v;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Forward.  Dynamic LDS: [reduction slots 256 B][alpha 2*Kmax R][f Emax R][src Emax int].
@@ -276,13 +231,8 @@ __global__ void __launch_bounds__(kTgF) target_graph_tr_reduce(TargetGraphArgs G
     if (lane == 0) gtr[G.pkey[pair]] = s;
 }
 
-inline size_t tg_fwd_lds(int elem, int Kmax, int64_t Emax) { return kTgRed + 2 * (size_t) Kmax * elem + (size_t) Emax * (elem + 4); }
 inline size_t tg_bwd_lds(int elem, int Kmax, int64_t Emax) {
     return kTgRed + (size_t) Kmax * (5 * elem + 4) + (size_t) Emax * (2 * elem + 4);
-}
-
-inline void tg_set_lds(const void *fn, size_t dyn) {
-    if (dyn > 64 * 1024) (void) hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) dyn);
 }
 
 template <typename R, int W>

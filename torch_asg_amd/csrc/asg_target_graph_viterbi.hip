@@ -1,0 +1,257 @@
+// torch_asg_amd/csrc/asg_target_graph_viterbi.hip -- the BEST path of a per-utterance target graph (asg_target_graph.hip sums
+// over all of them): which alternative was spoken, where its tokens lie in time, the hard targets of a next stage.  Utterance
+// b, node k of label l_k, len = clamp(input_lengths[b], 0, T), in the dtype of the problem, adds and compares only:
+//   f_e        = tr[l_k][l_src_e] + edge_w[e]                        (rounded once, as the score folds it)
+//   v[0][k]    = start_w[k] + I[0][l_k]
+//   stay       = v[t-1][k] + tr[l_k][l_k];   cand_e = v[t-1][src_e] + f_e   (edges into k in incoming-CSR order: ascending source)
+//   v[t][k]    = max(stay, cand_e ...) + I[t][l_k]
+//   bp[t][k]   = k unless some cand_e > stay (strictly); then the source of the FIRST edge in that order that attains the maximum
+//   score[b]   = max_k (v[len-1][k] + final_w[k]);  end node = the LOWEST k that attains it
+//   nodes[len-1] = end;  nodes[t-1] = bp[t][nodes[t]];  labels[t] = l_{nodes[t]}
+//   tokens / token_frames: labels[t] and t at t = 0 and at every t with nodes[t] != nodes[t-1], in order; token_lengths = their count
+// "Stay wins ties" is asg_viterbi.hip's rule (come > stay): for a chain with edge weight 0 the scores are asg_viterbi's and
+// the nodes its positions.  A score of -inf (len 0, empty graph, no finite path) walks nothing: every integer output is -1
+// and token_lengths 0; so are the frames >= len and the tokens behind token_lengths.
+//
+// ONE launch, one workgroup per utterance, one thread per node, 64 / 256 / 1024 threads wide as the score's kernels; three
+// phases in that workgroup:
+//  1. forward: the score's prologue (f_e and the sources folded into LDS, tr[l_k][l_k] in a register), v ping-pongs between
+//     two LDS vectors, the next emission is loaded before the barrier.  ONE pass over the incoming edges carries (best value,
+//     best source) in registers -- no second pass, no transcendental -- and the winning source goes to work[b][t][k] as 16
+//     bits (K <= 1024), a frame's row one coalesced store.  Then a workgroup max and a workgroup min over the nodes that
+//     attain it, both in the fixed tree.
+//  2. backtrace: the workgroup wrote those rows itself, so a barrier makes them readable.  The walk is serial but must not be
+//     a chain of dependent GLOBAL loads: the frames are cut into blocks of F (64; 16 at 1024 threads), all threads stage a
+//     block's F x Kmax rows into LDS (16-byte loads over the block's aligned interior, guarded 2-byte loads in its first and
+//     last granule), lane 0 walks the block in LDS and leaves its nodes in an LDS line, and the workgroup writes nodes and
+//     labels for those frames as coalesced int64 stores.  Two staging buffers and two lines: the loads of block i-1 are
+//     issued into registers before block i is walked and land in LDS after it, one barrier per block.  The staging reuses the
+//     LDS of the forward loop.
+//  3. compaction, chunks of W frames ascending: thread i flags t == 0 || nodes[t] != nodes[t-1], ballot + popcount rank it
+//     in the wavefront, the wavefronts' counts go through the reduction slots, tokens and token_frames land at base + rank.
+// Every output element is written here (the -1 fills too: no memset), no float atomics, nothing synchronises the host:
+// bit-identical run to run and capturable.  Every byte offset into the workspace is 64-bit.
+#include "asg_target_graph_common.h"
+
+namespace asg {
+
+namespace {
+
+// frames per staged block, and the 16-byte granules one thread moves per block: F * Kmax elements + up to 7 in front of
+// them (the block need not start on a 16-byte boundary) + the tail
+template <int W> struct Tgv {
+    static constexpr int F = W == 1024 ? 16 : 64;
+    static constexpr int NG = ((F * W + 14) / 8 + W - 1) / W;
+};
+inline int tgv_frames(int Kmax) { return Kmax <= 256 ? 64 : 16; }
+inline size_t tgv_granules(int Kmax) { return ((size_t) tgv_frames(Kmax) * Kmax + 14) / 8; }
+// [reduction slots 256 B] then the larger of the forward's [v 2*Kmax R][f Emax R][src Emax int] and the backtrace's
+// [stage 2 x granules x 16 B][line 2 x F int]
+inline size_t tgv_lds(int elem, int Kmax, int64_t Emax) {
+    const size_t back = kTgRed + 2 * tgv_granules(Kmax) * 16 + 2 * (size_t) tgv_frames(Kmax) * 4;
+    const size_t fwd = tg_fwd_lds(elem, Kmax, Emax);
+    return fwd > back ? fwd : back;
+}
+
+// n elements from `rows` into registers: granule g of the enclosing 16-byte-aligned range belongs to thread g mod W.
+template <int W>
+__device__ __forceinline__ void tgv_fetch(const uint16_t *rows, int n, uint4 (&r)[Tgv<W>::NG]) {
+    const int mis = (int) (((uintptr_t) rows & 15) >> 1), total = (mis + n + 7) >> 3;
+#pragma unroll
+    for (int q = 0; q < Tgv<W>::NG; ++q) {
+        const int g = (int) threadIdx.x + q * W, lo = g * 8 - mis;
+        if (g >= total) continue;
+        if (lo >= 0 && lo + 8 <= n) {
+            r[q] = *(const uint4 *) (rows + lo);
+        } else {                                      // the first or the last granule: nothing outside the block is read
+            unsigned h[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) h[j] = (lo + j >= 0 && lo + j < n) ? rows[lo + j] : 0u;
+            r[q] = make_uint4(h[0] | h[1] << 16, h[2] | h[3] << 16, h[4] | h[5] << 16, h[6] | h[7] << 16);
+        }
+    }
+}
+
+template <int W>
+__device__ __forceinline__ void tgv_put(const uint16_t *rows, int n, const uint4 (&r)[Tgv<W>::NG], uint4 *stage) {
+    const int mis = (int) (((uintptr_t) rows & 15) >> 1), total = (mis + n + 7) >> 3;
+#pragma unroll
+    for (int q = 0; q < Tgv<W>::NG; ++q) {
+        const int g = (int) threadIdx.x + q * W;
+        if (g < total) stage[g] = r[q];
+    }
+}
+
+template <typename R, int W>
+__global__ void __launch_bounds__(W) target_graph_viterbi(Problem P, TargetGraphArgs G, uint16_t *bp, R *scores, int64_t *nodes,
+                                                          int64_t *labels, int64_t *tokens, int64_t *frames, int64_t *tlen) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    constexpr int F = Tgv<W>::F;
+    R *red = (R *) lds;
+    R *av = (R *) (lds + kTgRed);
+    R *fe = av + 2 * (size_t) G.Kmax;
+    int *se = (int *) (fe + G.Emax);
+    const R NINF = Num<R>::ninf();
+    const int k = threadIdx.x, b = blockIdx.x, T = P.T, Kmax = G.Kmax;
+    const TgView g = tg_view(G, b);
+    const int len = g.K > 0 ? tg_len(P.in_len, b, T) : 0;
+    int64_t *nb = nodes + (int64_t) b * T, *lb = labels + (int64_t) b * T;
+    int64_t *kb = tokens + (int64_t) b * T, *fb = frames + (int64_t) b * T;
+    // ---- 1. forward ----
+    R m = NINF;
+    int end = 0;
+    if (len >= 1) {                                   // (uniform over the workgroup)
+        const bool mine = k < g.K;
+        const R *trm = (const R *) P.transition;
+        const R *in = (const R *) P.inputs + (int64_t) b * P.is1;
+        uint16_t *bpb = bp + (int64_t) b * T * Kmax;
+        int e0 = 0, e1 = 0;
+        R trs = R(0), fin = NINF, em = R(0), x = NINF;
+        if (mine) {
+            const int lk = g.label[k];
+            in += (int64_t) lk * P.is2;
+            e0 = g.row[k]; e1 = g.row[k + 1];
+            const R *ew = (const R *) G.edge_w + (int64_t) b * G.Emax;
+            for (int e = e0; e < e1; ++e) {           // the fold: one gather per edge per utterance
+                const int s = g.src[e];
+                fe[e] = trm[(int64_t) lk * P.ts0 + (int64_t) g.label[s] * P.ts1] + ew[e];
+                se[e] = s;
+            }
+            trs = trm[(int64_t) lk * (P.ts0 + P.ts1)];
+            fin = ((const R *) G.final_w)[(int64_t) b * Kmax + k];
+            x = ((const R *) G.start_w)[(int64_t) b * Kmax + k] + in[0];
+            if (len > 1) em = in[P.is0];
+            av[k] = x;
+            bpb[k] = (uint16_t) k;                    // (row 0 is never followed; written so that a staged block holds no stale bytes)
+        }
+        __syncthreads();
+        for (int t = 1; t < len; ++t) {
+            const R *vp = av + (size_t) ((t - 1) & 1) * Kmax;
+            if (mine) {
+                const R emt = em;
+                if (t + 1 < len) em = in[(int64_t) (t + 1) * P.is0];     // next frame's emission: in flight across the barrier
+                R best = vp[k] + trs;                 // stay wins ties
+                int from = k;
+                for (int e = e0; e < e1; ++e) {
+                    const int s = se[e];
+                    const R c = vp[s] + fe[e];
+                    if (c > best) { best = c; from = s; }
+                }
+                x = best + emt;
+                av[(size_t) (t & 1) * Kmax + k] = x;
+                bpb[(int64_t) t * Kmax + k] = (uint16_t) from;
+            }
+            __syncthreads();
+        }
+        const R c = mine ? x + fin : NINF;            // x = v[len-1][k]
+        m = tg_reduce<R, W, true>(c, red);
+        end = -tg_reduce<int, W, true>(mine && c == m ? -k : -(1 << 30), (int *) red);
+    }
+    if (k == 0) scores[b] = m;
+    const int n = m > NINF ? len : 0;                 // frames that carry a path; the rest of every row is -1
+    for (int t = n + k; t < T; t += W) nb[t] = lb[t] = -1;
+    if (n == 0) {                                     // (uniform)
+        for (int t = k; t < T; t += W) kb[t] = fb[t] = -1;
+        if (k == 0) tlen[b] = 0;
+        return;
+    }
+    // ---- 2. backtrace, block by block from the end ----
+    __syncthreads();                                  // the rows of this workgroup are written; the forward's LDS is free
+    {
+        const uint16_t *bpb = bp + (int64_t) b * T * Kmax;
+        const size_t cap = ((size_t) F * Kmax + 14) / 8;
+        uint4 *stage = (uint4 *) (lds + kTgRed);      // two buffers of `cap` granules
+        int *line = (int *) (stage + 2 * cap);        // two lines of F nodes
+        uint4 r[Tgv<W>::NG];
+        const int last = (n - 1) / F;
+        {
+            const uint16_t *rows = bpb + (int64_t) last * F * Kmax;
+            tgv_fetch<W>(rows, (n - last * F) * Kmax, r);
+            tgv_put<W>(rows, (n - last * F) * Kmax, r, stage);
+        }
+        __syncthreads();
+        int cur = end, p = 0;
+        for (int j = last; j >= 0; --j, p ^= 1) {
+            const int lo = j * F, hi = (lo + F < n ? lo + F : n) - 1;
+            const uint16_t *rows = bpb + (int64_t) lo * Kmax, *next = rows - (int64_t) F * Kmax;
+            if (j > 0) tgv_fetch<W>(next, F * Kmax, r);            // block j-1: in flight while block j is walked
+            if (k == 0) {
+                const uint16_t *st = (const uint16_t *) (stage + (size_t) p * cap) + (((uintptr_t) rows & 15) >> 1);
+                int *ln = line + p * F;
+                for (int t = hi; t >= lo; --t) {
+                    ln[t - lo] = cur;
+                    if (t > 0) cur = st[(t - lo) * Kmax + cur];
+                }
+            }
+            if (j > 0) tgv_put<W>(next, F * Kmax, r, stage + (size_t) (p ^ 1) * cap);
+            __syncthreads();
+            if (k <= hi - lo) {
+                const int nd = line[p * F + k];
+                nb[lo + k] = nd;
+                lb[lo + k] = g.label[nd];
+            }
+        }
+    }
+    // ---- 3. compaction ----
+    __syncthreads();                                  // nodes and labels of this utterance are written
+    int base = 0;
+    for (int c0 = 0; c0 < n; c0 += W) {
+        const int t = c0 + k;
+        bool f = false;
+        if (t < n) f = t == 0 || nb[t] != nb[t - 1];
+        const unsigned long long mask = __ballot(f);
+        const int rank = __popcll(mask & ((1ull << (k & 63)) - 1));
+        int off = 0, tot = __popcll(mask);
+        if (W > 64) {
+            int *cnt = (int *) red;
+            if ((k & 63) == 0) cnt[k >> 6] = tot;
+            __syncthreads();
+            tot = 0;
+#pragma unroll
+            for (int s = 0; s < W / 64; ++s) {
+                const int c = cnt[s];
+                if (s < (k >> 6)) off += c;
+                tot += c;
+            }
+            __syncthreads();
+        }
+        if (f) {
+            kb[base + off + rank] = lb[t];
+            fb[base + off + rank] = t;
+        }
+        base += tot;
+    }
+    for (int t = base + k; t < T; t += W) kb[t] = fb[t] = -1;
+    if (k == 0) tlen[b] = base;
+}
+
+template <typename R, int W>
+hipError_t tgv_launch(const Problem &P, const TargetGraphArgs &G, void *work, void *scores, int64_t *const out[5],
+                      hipStream_t stream) {
+    const size_t dyn = tgv_lds(sizeof(R), G.Kmax, G.Emax);
+    tg_set_lds((const void *) target_graph_viterbi<R, W>, dyn);
+    hipLaunchKernelGGL((target_graph_viterbi<R, W>), dim3(P.B), dim3(W), dyn, stream, P, G, (uint16_t *) work, (R *) scores,
+                       out[0], out[1], out[2], out[3], out[4]);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+size_t target_graph_viterbi_work_bytes(int T, int B, int Kmax) { return (size_t) B * T * Kmax * 2; }
+
+template <typename R>
+hipError_t launch_target_graph_viterbi(const Problem &P, const TargetGraphArgs &G, void *work, void *scores, int64_t *nodes,
+                                       int64_t *labels, int64_t *tokens, int64_t *token_frames, int64_t *token_lengths,
+                                       hipStream_t stream) {
+    int64_t *const out[5] = {nodes, labels, tokens, token_frames, token_lengths};
+    if (G.Kmax <= 64) return tgv_launch<R, 64>(P, G, work, scores, out, stream);
+    if (G.Kmax <= 256) return tgv_launch<R, 256>(P, G, work, scores, out, stream);
+    return tgv_launch<R, 1024>(P, G, work, scores, out, stream);
+}
+
+template hipError_t launch_target_graph_viterbi<float>(const Problem &, const TargetGraphArgs &, void *, void *, int64_t *,
+                                                       int64_t *, int64_t *, int64_t *, int64_t *, hipStream_t);
+template hipError_t launch_target_graph_viterbi<double>(const Problem &, const TargetGraphArgs &, void *, void *, int64_t *,
+                                                        int64_t *, int64_t *, int64_t *, int64_t *, hipStream_t);
+
+}  // namespace asg

@@ -1,5 +1,5 @@
 """Per-utterance target graphs: the transcript of an utterance as "one of these" (`torch_asg_amd.target_graph_score`,
-`target_graph_asg_loss`, `ASGLoss.target_graph_loss`).
+`target_graph_asg_loss`, `ASGLoss.target_graph_loss`, `target_graph_viterbi`).
 
 A `TargetGraphs` is a batch of B small node-labelled graphs.  Node k of graph b carries a label in [0, N), a start weight and a
 final weight (-inf: not a start / not a final); a directed edge src -> dst carries a weight (finite or -inf).  The stay on a
@@ -71,6 +71,8 @@ class TargetGraphs:
         if B * (self.Kmax + self.Emax) > (1 << 31) - 1:
             raise ValueError("TargetGraphs: B * (Kmax + Emax) must stay below 2^31")
         self._compiled = {}
+        self.final_alternative = None   # from_alternatives: host [B,Kmax] int64, the index of the sequence that ends in a node, -1 elsewhere
+        self._final_alternative = {}
 
     @classmethod
     def from_targets(cls, targets, target_lengths, num_labels):
@@ -92,10 +94,11 @@ class TargetGraphs:
         """Per utterance a list of label sequences, any of which is the transcript: the prefix tree of the sequences, its
         nodes numbered in order of first creation while the sequences are inserted in the given order.  The first nodes are
         starts with weight 0, every sequence end is final with that sequence's weight (weights[b][n], default 0), edges
-        weigh 0.  An empty sequence, two equal consecutive labels and the same sequence given twice (the log semiring would
+        weigh 0.  `final_alternative[b, k]` records which sequence ends in node k.  An empty sequence, two equal consecutive labels and the same sequence given twice (the log semiring would
         count it once) raise ValueError."""
-        labels, start, final, edges = [], [], [], []
+        labels, start, final, edges, ends = [], [], [], [], []
         for b, seqs in enumerate(alternatives):
+            ends.append([])
             ws = [0.0] * len(seqs) if weights is None else list(weights[b])
             if len(ws) != len(seqs):
                 raise ValueError("TargetGraphs.from_alternatives: %d weights for %d sequences of utterance %d" % (len(ws), len(seqs), b))
@@ -125,8 +128,25 @@ class TargetGraphs:
                 fw[at] = float(w)
                 if fw[at] == -np.inf:
                     raise ValueError("TargetGraphs.from_alternatives: a sequence weight must be finite")
+                ends[-1].append(at)
             labels.append(lab); start.append(sw); final.append(fw); edges.append(ed)
-        return cls(labels, start, final, edges, num_labels)
+        self = cls(labels, start, final, edges, num_labels)
+        self.final_alternative = np.full((self.B, self.Kmax), -1, np.int64)
+        for b, at in enumerate(ends):
+            self.final_alternative[b, at] = np.arange(len(at))
+        return self
+
+    def final_alternative_on(self, device):
+        """`final_alternative` as a tensor on `device` (cached), or None for graphs built from arrays."""
+        if self.final_alternative is None:
+            return None
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        hit = self._final_alternative.get(device)
+        if hit is None:
+            hit = self._final_alternative[device] = torch.from_numpy(self.final_alternative).to(device)
+        return hit
 
     def compile_host(self, dt):
         """The padded arrays as numpy arrays, weights in dtype `dt`; integer arrays int32 (pkey int64):
