@@ -2,7 +2,7 @@
 `beam_decode_words_confidence` (csrc/asg_beam_word_conf.hip) and `beam_decode_words_nbest_confidence`
 (csrc/asg_beam_word_nbest_conf.hip) -- at the sizes of tests/test_hip_beam_word_regimes.py, which was written before they
 existed.  They bring device text that no other call compiles: the search with the decoder's end
-(`beam_word_conf_search<R, TRL, LA, FIN>`), the beta pull over 64-bit pair keys with a word-event sink
+(`beam_word_search<R, TRL, LA, FIN, WordSearch::DecodeSets>` of csrc/asg_beam_word_search.h), the beta pull over 64-bit pair keys with a word-event sink
 (csrc/asg_beam_word_conf_pull.h) and the two sinks.
 
   1. pairs h << qbits | q of 9, 17, 33 and 35 bits: in the pull `find_sorted`, `pp & qmask`, `label`, `end` and the copy of
@@ -123,7 +123,7 @@ def test_walks_of_63_and_64_backoff_steps_inside_the_pull(depth, form, dtype):
 def test_every_instantiation_of_the_search_with_the_decoders_end(elem, N0, side):
     """4096 + K (e + 8) + N N e against 160 KiB at K = 8: N = 199 | 200 (float32) and 141 | 142 (float64).  Each of the four
     cases runs the one-best call (FIN = false) and the 3-row n-best call (FIN = true), plain (LA = false) and with look-ahead
-    of order 2 (LA = true); over the four cases that is every instantiation of beam_word_conf_search<R, TRL, LA, FIN>:
+    of order 2 (LA = true); over the four cases that is every instantiation of beam_word_search<R, TRL, LA, FIN, WordSearch::DecodeSets>:
 
       <float,  true,  *, *>  f32, N = 199      <float,  false, *, *>  f32, N = 200
       <double, true,  *, *>  f64, N = 141      <double, false, *, *>  f64, N = 142

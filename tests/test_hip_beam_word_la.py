@@ -1,5 +1,5 @@
 """GPU tests (-m gpu) of LM look-ahead in the lexicon + word-LM beam decoder (`beam_decode_words(..., lookahead=)`,
-csrc/asg_beam_word_la.hip): all eight outputs bit-identical to the test-side numpy restatement (tests/beam_word_la_ref.py, pinned
+csrc/asg_beam_word.hip over csrc/asg_beam_word_search.h with the LA flag): all eight outputs bit-identical to the test-side numpy restatement (tests/beam_word_la_ref.py, pinned
 on the CPU by tests/test_beam_word_la_cpu.py).  Every case first asserts, from the restatement's own sets, that its input is in
 the regime it names."""
 import numpy as np

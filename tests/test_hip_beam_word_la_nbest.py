@@ -1,6 +1,6 @@
 """GPU tests (-m gpu) of the n-best lists of the word-LM beam search WITH LM LOOK-AHEAD (`beam_decode_words_nbest(...,
 lookahead=)`, `BeamWordStream._result_nbest` of a look-ahead stream, csrc/asg_beam_word_nbest.hip with the LA flag behind
-csrc/asg_beam_word_la.hip with the FIN flag): the bytes of every output against the test-side numpy restatement
+the search of csrc/asg_beam_word_search.h with the LA and FIN flags): the bytes of every output against the test-side numpy restatement
 (tests/beam_word_la_nbest_ref.py, pinned on the CPU by tests/test_beam_word_la_nbest_cpu.py).  Every case first asserts from the
 restatement that its input is in the regime it names; then the four required properties on the device, capture, determinism,
 grouping, the stream and the neighbours."""

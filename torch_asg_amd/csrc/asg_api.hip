@@ -636,29 +636,6 @@ size_t asg_beam_decode_words_work_bytes(const asg_problem *p, const asg_token_gr
                                 beam_word_cap(beam_size, gb->max_out, (int) gb->num_start));
 }
 
-int asg_beam_decode_words(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm, int beam_size,
-                          double beam_threshold, void *work, size_t work_bytes, void *scores, int64_t *path, int64_t *tokens,
-                          int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words, int64_t *word_lengths,
-                          int flags, void *stream) {
-    (void) ctx; (void) flags;
-    int rc = check_beam_words(p, gb, lm, beam_size);
-    if (rc) return rc;
-    if (!(beam_threshold >= 0.0)) return ASG_ERR_INVALID;                  // negative or NaN
-    if (!work || !scores || !path || !tokens || !token_lengths || !states || !lm_states || !words || !word_lengths)
-        return ASG_ERR_INVALID;
-    if (work_bytes < asg_beam_decode_words_work_bytes(p, gb, lm, beam_size)) return ASG_ERR_WORKSPACE;
-    const Problem P = to_problem(p);
-    const GraphArgs G = to_graph_args(gb->graph);
-    const BeamGraphArgs BG = to_beam_graph_args(gb);
-    const WordLmArgs LM = to_word_lm_args(lm);
-    long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
-    long long *ls = (long long *) lm_states, *wd = (long long *) words, *wl = (long long *) word_lengths;
-    return hip_status(ASG_DISPATCH(p, launch_beam_words<float>(P, G, BG, LM, beam_size, beam_threshold, work, scores, pa, tk, tl,
-                                                               st, ls, wd, wl, (hipStream_t) stream),
-                                   launch_beam_words<double>(P, G, BG, LM, beam_size, beam_threshold, work, scores, pa, tk, tl,
-                                                             st, ls, wd, wl, (hipStream_t) stream)));
-}
-
 // The look-ahead of a (lexicon, LM) pair: its arrays, sized for that pair's S and H.
 static int check_word_lookahead(int dtype, const asg_word_lm *lm, const asg_word_lookahead *la) {
     if (!la || la->dtype != dtype || la->S != lm->S || la->H != lm->H) return ASG_ERR_INVALID;
@@ -677,14 +654,14 @@ static WordLookArgs to_word_look_args(const asg_word_lookahead *la) {
     return LA;
 }
 
-int asg_beam_decode_words_la(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
-                             const asg_word_lookahead *la, int beam_size, double beam_threshold, void *work, size_t work_bytes,
-                             void *scores, int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states,
-                             int64_t *lm_states, int64_t *words, int64_t *word_lengths, int flags, void *stream) {
-    (void) ctx; (void) flags;
+// asg_beam_decode_words with a look-ahead (`with_la`: la is checked behind the LM) or without one.
+static int beam_decode_words(const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm, const asg_word_lookahead *la,
+                             bool with_la, int beam_size, double beam_threshold, void *work, size_t work_bytes, void *scores,
+                             int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states, int64_t *lm_states,
+                             int64_t *words, int64_t *word_lengths, void *stream) {
     int rc = check_beam_words(p, gb, lm, beam_size);
     if (rc) return rc;
-    if ((rc = check_word_lookahead(p->dtype, lm, la)) != ASG_OK) return rc;
+    if (with_la && (rc = check_word_lookahead(p->dtype, lm, la)) != ASG_OK) return rc;
     if (!(beam_threshold >= 0.0)) return ASG_ERR_INVALID;                  // negative or NaN
     if (!work || !scores || !path || !tokens || !token_lengths || !states || !lm_states || !words || !word_lengths)
         return ASG_ERR_INVALID;
@@ -693,13 +670,32 @@ int asg_beam_decode_words_la(asg_ctx *ctx, const asg_problem *p, const asg_token
     const GraphArgs G = to_graph_args(gb->graph);
     const BeamGraphArgs BG = to_beam_graph_args(gb);
     const WordLmArgs LM = to_word_lm_args(lm);
-    const WordLookArgs LA = to_word_look_args(la);
+    const WordLookArgs LA = with_la ? to_word_look_args(la) : WordLookArgs{};
+    const WordLookArgs *look = with_la ? &LA : nullptr;
     long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
     long long *ls = (long long *) lm_states, *wd = (long long *) words, *wl = (long long *) word_lengths;
-    return hip_status(ASG_DISPATCH(p, launch_beam_words_la<float>(P, G, BG, LM, LA, beam_size, beam_threshold, work, scores, pa, tk,
-                                                                  tl, st, ls, wd, wl, (hipStream_t) stream),
-                                   launch_beam_words_la<double>(P, G, BG, LM, LA, beam_size, beam_threshold, work, scores, pa, tk,
-                                                                tl, st, ls, wd, wl, (hipStream_t) stream)));
+    return hip_status(ASG_DISPATCH(p, launch_beam_words<float>(P, G, BG, LM, look, beam_size, beam_threshold, work, scores, pa, tk,
+                                                               tl, st, ls, wd, wl, (hipStream_t) stream),
+                                   launch_beam_words<double>(P, G, BG, LM, look, beam_size, beam_threshold, work, scores, pa, tk,
+                                                             tl, st, ls, wd, wl, (hipStream_t) stream)));
+}
+
+int asg_beam_decode_words(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm, int beam_size,
+                          double beam_threshold, void *work, size_t work_bytes, void *scores, int64_t *path, int64_t *tokens,
+                          int64_t *token_lengths, int64_t *states, int64_t *lm_states, int64_t *words, int64_t *word_lengths,
+                          int flags, void *stream) {
+    (void) ctx; (void) flags;
+    return beam_decode_words(p, gb, lm, nullptr, false, beam_size, beam_threshold, work, work_bytes, scores, path, tokens,
+                             token_lengths, states, lm_states, words, word_lengths, stream);
+}
+
+int asg_beam_decode_words_la(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
+                             const asg_word_lookahead *la, int beam_size, double beam_threshold, void *work, size_t work_bytes,
+                             void *scores, int64_t *path, int64_t *tokens, int64_t *token_lengths, int64_t *states,
+                             int64_t *lm_states, int64_t *words, int64_t *word_lengths, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    return beam_decode_words(p, gb, lm, la, true, beam_size, beam_threshold, work, work_bytes, scores, path, tokens, token_lengths,
+                             states, lm_states, words, word_lengths, stream);
 }
 
 static int check_beam_words_nbest(const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm, int beam_size,
@@ -740,21 +736,14 @@ static int beam_decode_words_nbest(const asg_problem *p, const asg_token_graph_b
     long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
     long long *ls = (long long *) lm_states, *wd = (long long *) words, *wl = (long long *) word_lengths;
     long long *nh = (long long *) num_hyps;
-    if (with_la) {
-        const WordLookArgs LA = to_word_look_args(la);
-        return hip_status(ASG_DISPATCH(p, launch_beam_words_nbest_la<float>(P, G, BG, LM, LA, beam_size, beam_threshold, nbest, work,
-                                                                            scores, emission_scores, graph_scores, lm_scores, pa, tk,
-                                                                            tl, st, ls, wd, wl, nh, (hipStream_t) stream),
-                                       launch_beam_words_nbest_la<double>(P, G, BG, LM, LA, beam_size, beam_threshold, nbest, work,
-                                                                          scores, emission_scores, graph_scores, lm_scores, pa, tk,
-                                                                          tl, st, ls, wd, wl, nh, (hipStream_t) stream)));
-    }
-    return hip_status(ASG_DISPATCH(p, launch_beam_words_nbest<float>(P, G, BG, LM, beam_size, beam_threshold, nbest, work, scores,
-                                                                     emission_scores, graph_scores, lm_scores, pa, tk, tl, st, ls,
-                                                                     wd, wl, nh, (hipStream_t) stream),
-                                   launch_beam_words_nbest<double>(P, G, BG, LM, beam_size, beam_threshold, nbest, work, scores,
-                                                                   emission_scores, graph_scores, lm_scores, pa, tk, tl, st, ls,
-                                                                   wd, wl, nh, (hipStream_t) stream)));
+    const WordLookArgs LA = with_la ? to_word_look_args(la) : WordLookArgs{};
+    const WordLookArgs *look = with_la ? &LA : nullptr;
+    return hip_status(ASG_DISPATCH(p, launch_beam_words_nbest<float>(P, G, BG, LM, look, beam_size, beam_threshold, nbest, work,
+                                                                     scores, emission_scores, graph_scores, lm_scores, pa, tk, tl,
+                                                                     st, ls, wd, wl, nh, (hipStream_t) stream),
+                                   launch_beam_words_nbest<double>(P, G, BG, LM, look, beam_size, beam_threshold, nbest, work,
+                                                                   scores, emission_scores, graph_scores, lm_scores, pa, tk, tl,
+                                                                   st, ls, wd, wl, nh, (hipStream_t) stream)));
 }
 
 int asg_beam_decode_words_nbest(asg_ctx *ctx, const asg_problem *p, const asg_token_graph_beam *gb, const asg_word_lm *lm,
@@ -1135,25 +1124,16 @@ static int beam_word_stream_nbest(const asg_token_graph_beam *gb, const asg_word
     long long *pa = (long long *) path, *tk = (long long *) tokens, *tl = (long long *) token_lengths, *st = (long long *) states;
     long long *ls = (long long *) lm_states, *wd = (long long *) words, *wl = (long long *) word_lengths;
     long long *nh = (long long *) num_hyps, *fr = (long long *) frames, *su = (long long *) status;
-    if (with_la) {
-        const WordLookArgs LA = to_word_look_args(la);
-        return hip_status(ASG_DISPATCH(g, launch_beam_word_stream_nbest_la<float>(G, BG, LM, LA, beam_size, (int) max_frames, (int) B,
-                                                                                  state, final, nbest, work, scores, graph_scores,
-                                                                                  lm_scores, pa, tk, tl, st, ls, wd, wl, nh, fr, su,
-                                                                                  (hipStream_t) stream, per),
-                                       launch_beam_word_stream_nbest_la<double>(G, BG, LM, LA, beam_size, (int) max_frames, (int) B,
-                                                                                state, final, nbest, work, scores, graph_scores,
-                                                                                lm_scores, pa, tk, tl, st, ls, wd, wl, nh, fr, su,
-                                                                                (hipStream_t) stream, per)));
-    }
-    return hip_status(ASG_DISPATCH(g, launch_beam_word_stream_nbest<float>(G, BG, LM, beam_size, (int) max_frames, (int) B, state,
-                                                                           final, nbest, work, scores, graph_scores, lm_scores, pa,
-                                                                           tk, tl, st, ls, wd, wl, nh, fr, su, (hipStream_t) stream,
-                                                                           per),
-                                   launch_beam_word_stream_nbest<double>(G, BG, LM, beam_size, (int) max_frames, (int) B, state,
-                                                                         final, nbest, work, scores, graph_scores, lm_scores, pa,
-                                                                         tk, tl, st, ls, wd, wl, nh, fr, su, (hipStream_t) stream,
-                                                                         per)));
+    const WordLookArgs LA = with_la ? to_word_look_args(la) : WordLookArgs{};
+    const WordLookArgs *look = with_la ? &LA : nullptr;
+    return hip_status(ASG_DISPATCH(g, launch_beam_word_stream_nbest<float>(G, BG, LM, look, beam_size, (int) max_frames, (int) B,
+                                                                           state, final, nbest, work, scores, graph_scores,
+                                                                           lm_scores, pa, tk, tl, st, ls, wd, wl, nh, fr, su,
+                                                                           (hipStream_t) stream, per),
+                                   launch_beam_word_stream_nbest<double>(G, BG, LM, look, beam_size, (int) max_frames, (int) B,
+                                                                         state, final, nbest, work, scores, graph_scores,
+                                                                         lm_scores, pa, tk, tl, st, ls, wd, wl, nh, fr, su,
+                                                                         (hipStream_t) stream, per)));
 }
 
 int asg_beam_word_stream_nbest(asg_ctx *ctx, const asg_token_graph_beam *gb, const asg_word_lm *lm, int64_t B, int beam_size,

@@ -3,11 +3,11 @@
 // tests/beam_word_conf_ref.py restates it in numpy.
 //
 // Five launches on one stream, the frame loop of the search in one of them:
-//   1  beam_word_conf_search: asg_beam_word_loss.hip's search (the frame of asg_beam_word_frame.h in a loop that leaves |A_t|
-//      beside the [T][K] lists bq / bh) followed by the decoder's own end in the same launch -- word_best_end and
-//      word_backtrace of asg_beam_word_frame.h, the device text beam_word_kernel / beam_word_la_kernel end with -- so the eight
-//      outputs of the decoder have that call's bits.  It also writes word_frames: the frames of the winning path's separator
-//      edges and, for the word of the final step, len.
+//   1  beam_word_search<.., WordSearch::DecodeSets> (asg_beam_word_search.h, the one text of the family's one-shot search): the
+//      loop that leaves |A_t| beside the [T][K] lists bq / bh, as the loss's mode does, followed by the decoder's own end in the
+//      same launch -- word_best_end and word_backtrace of asg_beam_word_frame.h -- so the eight outputs of the decoder have that
+//      call's bits.  It also writes word_frames (word_end_frames): the frames of the winning path's separator edges and, for the
+//      word of the final step, len; -1 everywhere where there is no path.
 //   2 - 4  launch_beam_word_loss_lattice: the target walk (there is no target: it writes the header's 0), beam_loss_sets<WordSets>
 //      and beam_word_loss_fwd with alpha stored for every frame -> U, alpha, Z_K (the normalisers).  Unchanged kernels.
 //   5  beam_word_conf_bwd: asg_beam_word_conf_pull.h over HypSink -- beam_loss_bwd's beta pull (one 1024-thread workgroup per utterance, frames len-1 .. 1, U_{t+1} with its
@@ -24,7 +24,7 @@
 #include "asg_common.h"
 #include "asg_kernels.h"
 #include "asg_beam_common.h"
-#include "asg_beam_word_frame.h"  // the frame of the search and its end
+#include "asg_beam_word_search.h" // launch 1: the search and its end
 #include "asg_beam_lattice.h"     // the helpers of the lattice pass: subgroup, find_sorted, the butterflies, to_fixed
 #include "asg_beam_word_lat.h"    // WordLat: how a pair's edges are walked
 #include "asg_beam_word_conf_pull.h"  // the beta pull, shared with asg_beam_word_nbest_conf.hip
@@ -33,94 +33,6 @@
 namespace asg {
 
 namespace {
-
-// ---------------------------------------------------------------------------------------------------------------------
-// 1: the search with its end.  beam_word_loss_search's loop (cnt[t] = |A_t| for t < len), then beam_word_kernel's end.
-// ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void conf_no_path(int T, long long *pb, long long *tk, long long *st, long long *ls, long long *wd,
-                                             long long *wf, long long *tlen, long long *wlen) {
-    word_no_path(T, pb, tk, st, ls, wd, tlen, wlen);
-    for (int t = threadIdx.x; t < T; t += kBT) wf[t] = -1;
-}
-
-// FIN: the instantiation behind the n-best confidences (asg_beam_word_nbest_conf.hip), which also leaves the last set in memory
-// at fin_off, as beam_word_kernel<R, TRL, FIN> does; without it the text is what it was before the flag existed.
-template <typename R, bool TRL, bool LA, bool FIN>
-__global__ void __launch_bounds__(kBT) beam_word_conf_search(Problem P, GraphArgs g, BeamGraphArgs bg, WordLmArgs lm, int K, R theta,
-                                                             int cap, int tbits, char *work, size_t per_utt, size_t cnt_off,
-                                                             WordLookParam<LA> la, R *scores, long long *path, long long *tokens,
-                                                             long long *tlen, long long *states, long long *lm_states,
-                                                             long long *words, long long *wlen, long long *wframes,
-                                                             size_t fin_off) {
-    using U = typename Key<R>::U;
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    Ctl<U> &ctl = *(Ctl<U> *) lds;
-    WordCtl &wctl = *(WordCtl *) (lds + kWordCtlOff);
-    R *cur_v = (R *) (lds + kFixedLds);                    // [K]
-    int *cur_q = (int *) (cur_v + K);                      // [K]
-    int *cur_h = cur_q + K;                                // [K]
-    R *trs = (R *) (cur_h + K);                            // [N][N] if TRL
-    const int tid = threadIdx.x, b = blockIdx.x;
-    const int N = P.N, T = P.T;
-    const R NINF = Num<R>::ninf();
-    const int len = clamp_len(P.in_len, b, T);
-    const R *in = (const R *) P.inputs + (int64_t) b * P.is1;
-    const R *tr = (const R *) P.transition;
-    const R *fw = (const R *) g.final_w;
-    long long *pb = path + (int64_t) b * T, *tk = tokens + (int64_t) b * T, *st = states + (int64_t) b * T;
-    long long *ls = lm_states + (int64_t) b * T, *wd = words + (int64_t) b * T, *wf = wframes + (int64_t) b * T;
-    BeamWordFrame<R, LA> f;
-    f.ctl = &ctl; f.wctl = &wctl; f.cur_v = cur_v; f.cur_q = cur_q; f.cur_h = cur_h; f.trs = trs; f.tr = tr;
-    f.ts0 = P.ts0; f.ts1 = P.ts1; f.N = N; f.theta = theta;
-    bind_graph<R, LA>(f, g, bg, lm, K, cap, tbits);
-    bind_look<R>(f, la);
-    int *bq, *bh, *bs;
-    char *wb = work + (size_t) b * per_utt;
-    f.bind_work(wb, T, bq, bh, bs);
-    int *cnt = (int *) (wb + cnt_off);
-    if (len < 1) {
-        conf_no_path(T, pb, tk, st, ls, wd, wf, tlen + b, wlen + b);
-        if (tid == 0) scores[b] = NINF;
-        return;
-    }
-    if constexpr (TRL)
-        for (int x = tid; x < N * N; x += kBT) trs[x] = tr[(int64_t) (x / N) * P.ts0 + (int64_t) (x % N) * P.ts1];
-    if (len >= 2) {
-        const size_t C = (size_t) 1 << tbits;
-        for (size_t s = tid; s < C; s += kBT) { dev_store(f.tkey + s, 0ull); dev_store(f.val + s, (U) 0); dev_store(f.arg + s, ~0ull); }
-    }
-    if (tid == 0) { ctl.na = 0; ctl.n = 0; }
-    __syncthreads();
-    int t = 0;
-    for (; t < len; ++t) {
-        const int na = ctl.na;
-        if (t >= 1 && na == 0) break;                       // an empty beam stays empty
-        beam_word_frame<R, TRL, LA>(f, t == 0, na, in + (int64_t) t * P.is0, P.is2, bq, bh, bs, t);
-        if (tid == 0) cnt[t] = ctl.na < K ? ctl.na : K;
-    }
-    for (int u = t + tid; u < len; u += kBT) cnt[u] = 0;
-
-    // ---- the decoder's end: the best end over the last kept set, the smallest pair on a tie; the backtrace, the words, the tokens
-    const int na = ctl.na < K ? ctl.na : K;
-    if constexpr (FIN) {                                    // the n-best stage reads the last set from memory
-        char *fin = wb + fin_off;
-        R *fv = (R *) (fin + 8);
-        int *fq = (int *) (fv + K), *fh = fq + K;
-        for (int k = tid; k < na; k += kBT) { fv[k] = cur_v[k]; fq[k] = cur_q[k]; fh[k] = cur_h[k]; }
-        if (tid == 0) *(int *) fin = na;
-    }
-    U bkey;
-    int bk;
-    word_best_end<R, LA>(f, fw, true, cur_h, cur_q, cur_v, na, bkey, bk);
-    if (bkey == 0) {                                        // an empty beam, or no kept pair with a finite end
-        conf_no_path(T, pb, tk, st, ls, wd, wf, tlen + b, wlen + b);
-        if (tid == 0) scores[b] = NINF;
-        return;
-    }
-    word_backtrace<R, LA>(f, fw, true, cur_h, cur_q, cur_v, bk, bq, bh, bs, len, T, scores + b, pb, tk, st, ls, wd, tlen + b,
-                          wlen + b);
-    word_end_frames(pb, f.sep, len, T, wlen + b, wf);      // (with the word of the final step)
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // 5: beta with the word-event sink.  Dynamic LDS: [nq u64 M][nb R M][pad to 16][ring u64 256].  beta[t-1] crosses from the lanes
@@ -169,37 +81,17 @@ size_t beam_word_conf_work_bytes(int elem, int T, int B, int K, int cap) {
 }
 
 // Launch 1 alone.  `per` and `cnt_off` say where an utterance's block starts and where its kept counts go; with fin_off != 0 the
-// search also leaves |A_{len-1}| and its last set there (the FIN instantiations: the n-best confidences).
+// search also leaves |A_{len-1}| and its last set there (the FIN instantiations: the n-best confidences,
+// asg_beam_word_nbest_conf.hip; without it the code objects are what they were before the flag existed).
 template <typename R>
 hipError_t launch_beam_word_conf_search(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
                                         const WordLookArgs *LA, int K, double theta, void *work, size_t per, size_t cnt_off,
                                         size_t fin_off, void *scores, long long *path, long long *tokens, long long *tlen,
                                         long long *states, long long *lm_states, long long *words, long long *wlen,
                                         long long *word_frames, hipStream_t stream) {
-    const int B = P.B, N = P.N;
-    const int cap = beam_word_cap(K, BG.max_out, BG.num_start);
-    const int tbits = word_table_bits(cap);
-    char *w = (char *) work;
-    const size_t beam = kFixedLds + (size_t) K * (sizeof(R) + 8);
-    const bool trl = beam + (size_t) N * N * sizeof(R) <= kLdsMax;
-    const size_t dyn = beam + (trl ? (size_t) N * N * sizeof(R) : 0);
-#define ASG_BEAM_WORD_CONF_SEARCH(TRL, LAF, FIN, LOOK)                                                                        \
-    do {                                                                                                                     \
-        set_lds((const void *) beam_word_conf_search<R, TRL, LAF, FIN>, dyn);                                               \
-        hipLaunchKernelGGL((beam_word_conf_search<R, TRL, LAF, FIN>), dim3(B), dim3(kBT), dyn, stream, P, G, BG, LM, K,    \
-                           (R) theta, cap, tbits, w, per, cnt_off, LOOK, (R *) scores, path, tokens, tlen, states,           \
-                           lm_states, words, wlen, word_frames, fin_off);                                                    \
-    } while (0)
-#define ASG_BEAM_WORD_CONF_SEARCH_F(TRL, LAF, LOOK)                                                                           \
-    do {                                                                                                                     \
-        if (fin_off) ASG_BEAM_WORD_CONF_SEARCH(TRL, LAF, true, LOOK); else ASG_BEAM_WORD_CONF_SEARCH(TRL, LAF, false, LOOK); \
-    } while (0)
-    if (LA) { if (trl) ASG_BEAM_WORD_CONF_SEARCH_F(true, true, *LA); else ASG_BEAM_WORD_CONF_SEARCH_F(false, true, *LA); }
-    else if (trl) ASG_BEAM_WORD_CONF_SEARCH_F(true, false, WordNoLook{});
-    else ASG_BEAM_WORD_CONF_SEARCH_F(false, false, WordNoLook{});
-#undef ASG_BEAM_WORD_CONF_SEARCH_F
-#undef ASG_BEAM_WORD_CONF_SEARCH
-    return hipGetLastError();
+    return launch_beam_word_search<R, WordSearch::DecodeSets>(P, G, BG, LM, LA, K, theta, work, per, cnt_off, fin_off,
+                                                              {scores, path, tokens, tlen, states, lm_states, words, wlen},
+                                                              word_frames, stream);
 }
 
 template <typename R>

@@ -113,21 +113,7 @@ __device__ __forceinline__ void beam_word_conf_pull(const Problem &P, const type
     sink.window(last);                                                         // every window is closed
 }
 
-// Where the words of a hypothesis end, behind word_backtrace (pb: its path of len frames, *wlen: its word count): the frames of
-// the separator edges word_backtrace read its words from, then len for the word of a final step (the one word it appended behind
-// them; a prefix has none: its word count is the separator count).  Every thread of the search's or the pull's workgroup.
-static_assert(kBT == kBL, "word_end_frames strides by either workgroup");
-__device__ __forceinline__ void word_end_frames(const long long *pb, int sep, int len, int T, const long long *wlen, long long *wf) {
-    for (int u = threadIdx.x; u < T; u += kBL) wf[u] = -1;
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int nw = 0;
-        for (int u = 1; u < len; ++u)
-            if (pb[u] == sep && pb[u - 1] != sep) wf[nw++] = u;
-        if (nw < (int) *wlen) wf[nw] = len;
-    }
-}
+static_assert(kBT == kBL, "word_end_frames (asg_beam_word_frame.h) strides by the search's or the pull's workgroup");
 
 // The tail of a one-best confidence kernel (beam_word_conf_bwd of asg_beam_word_conf.hip, beam_word_stream_conf_bwd of
 // asg_beam_word_stream_conf.hip), behind Z and the count nw of the hypothesis' words that get a confidence: the zero fill, the ring,

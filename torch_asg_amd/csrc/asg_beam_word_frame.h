@@ -1,8 +1,8 @@
 // torch_asg_amd/csrc/asg_beam_word_frame.h -- ONE FRAME of the beam search over pairs (LM history h, lexicon product state q)
-// and the END of that search, shared by the one-shot decoder (asg_beam_word.hip: beam_word_kernel walks all frames of an
-// utterance in one launch) and the streaming decoder (asg_beam_word_stream.hip: beam_word_stream_advance_kernel enters the frame
-// loop with the set an earlier call left, beam_word_stream_result_kernel is the end as a call of its own).  Both translation
-// units compile this text, as asg_beam_graph.hip and asg_beam_stream.hip compile asg_beam_frame.h: that is what "decoding in
+// and the END of that search, shared by the one-shot search (asg_beam_word_search.h: beam_word_search walks all frames of an
+// utterance in one launch, for the decoder, the loss and the confidences) and the streaming decoder (asg_beam_word_stream.hip:
+// beam_word_stream_advance_kernel enters the frame loop with the set an earlier call left, beam_word_stream_result_kernel is the
+// end as a call of its own).  All of them compile this text, as asg_beam_graph.hip and asg_beam_stream.hip compile asg_beam_frame.h: that is what "decoding in
 // chunks gives the bits of decoding in one call" rests on (include/asg_hip.h::asg_beam_word_stream_advance).  The frame is
 // described at the top of asg_beam_word.hip.  Also here, for the two word streams (asg_beam_word_stream.hip,
 // asg_beam_word_window.hip): bind_graph, the clearing loop of their resets (beam_word_reset_tables), the way their advance kernels
@@ -32,9 +32,17 @@ static_assert(kWordCtlOff + sizeof(WordCtl) <= kFixedLds, "control block");
 
 __device__ __forceinline__ int bits_of(int n) { return 32 - __clz(n > 1 ? n - 1 : 1); }   // >= 1
 
-// LM look-ahead (asg_beam_word_la.hip, include/asg_hip.h::asg_beam_decode_words_la; the `_la` forms of the two word streams) is a
-// compile-time flag of the frame and the end, off by default: every instantiation without it compiles the text it compiled
-// before the flag existed.
+// LM look-ahead (include/asg_hip.h::asg_beam_decode_words_la and the other `_la` calls of the one-shot search and the two word
+// streams) is a compile-time flag of the frame and the end, off by default: every instantiation without it compiles the text it
+// compiled before the flag existed.  With it, inside a word a pair's value also carries L(h, node), the best LM score a word below
+// its trie node can get after h, and every edge adds the difference of its two ends (a separator edge the difference between the
+// word's own LM score and the L it entered with), so that one value per pair stays the only search state.  L is evaluated on
+// the device per expanded edge against the pair's history (BeamWordFrame::look): the words below a node are a range of ranks
+// (pre-order of the trie), every LM state keeps its arcs sorted by rank, and a sparse table of maxima over those rows answers
+// "the best arc of state s in the range" with two binary searches and two reads (state 0, where the chains end and the row is the
+// longest, has its answers in a dense [S] array: one read); the walk down the backoff chain adds the backoff weights as the LM
+// walk does.  L of the source pair is the same for all its edges: it is taken once per pair and phase.  Plain loads of read-only
+// arrays: no workspace, no atomics, nothing to clear.
 template <typename R, bool LA>
 struct WordLook {};
 template <typename R>
@@ -632,6 +640,22 @@ __device__ __forceinline__ void word_backtrace(const BeamWordFrame<R, LA> &f, co
     __syncthreads();
     for (int t = wctl.rk[0] + tid; t < T; t += kBT) wd[t] = -1;
     if (tid < 64) collapse_tokens(pb, len, T, tk, tlen, tid);
+}
+
+// Where the words of a hypothesis end, behind word_backtrace (pb: its path of len frames, *wlen: its word count): the frames of
+// the separator edges word_backtrace read its words from, then len for the word of a final step (the one word it appended behind
+// them; a prefix has none: its word count is the separator count).  Every thread of the search's or the pull's workgroup (both
+// of kBT threads: asg_beam_word_conf_pull.h asserts it).
+__device__ __forceinline__ void word_end_frames(const long long *pb, int sep, int len, int T, const long long *wlen, long long *wf) {
+    for (int u = threadIdx.x; u < T; u += kBT) wf[u] = -1;
+    __threadfence();
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int nw = 0;
+        for (int u = 1; u < len; ++u)
+            if (pb[u] == sep && pb[u - 1] != sep) wf[nw++] = u;
+        if (nw < (int) *wlen) wf[nw] = len;
+    }
 }
 
 // The table of a frame has C slots, the power of two >= 2 * cap.

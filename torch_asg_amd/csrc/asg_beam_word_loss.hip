@@ -4,8 +4,8 @@
 // specification is include/asg_hip.h::asg_beam_words_full_forward; tests/beam_word_loss_ref.py restates it in numpy.
 //
 // Forward, four launches on one stream:
-//   1  beam_word_loss_search: the frame of asg_beam_word_frame.h in a loop of its own (the same device text as beam_word_kernel,
-//      so the same kept sets bit for bit) that leaves |A_t| of every frame beside the [T][K] lists bq / bh; no end, no backtrace;
+//   1  beam_word_search<.., WordSearch::Sets>: the decoder's own search (asg_beam_word_search.h, one text for the family: the same
+//      kept sets bit for bit) in the mode that leaves |A_t| of every frame beside the [T][K] lists bq / bh; no end, no backtrace;
 //   2  beam_word_loss_targets: one thread per utterance walks the lexicon's outgoing rows along the merged target, the LM walk
 //      on every separator edge included -> the forced pairs as 64-bit keys h << qbits | q; hdr[0] = n (0: nothing is forced);
 //   3  beam_loss_sets<WordSets>: one workgroup per (utterance, frame) -- utterances in x, frames strided over y -- sorts the keys of A_t
@@ -30,7 +30,8 @@
 #include "asg_common.h"
 #include "asg_kernels.h"
 #include "asg_beam_common.h"
-#include "asg_beam_word_frame.h"  // the frame of the search, the LM walk and the end of a pair
+#include "asg_beam_word_search.h" // launch 1: the search
+#include "asg_beam_word_frame.h"  // the LM walk and the end of a pair
 #include "asg_beam_word_lat.h"    // bind_walk and WordLat: how a pair's edges are walked (shared with asg_beam_word_conf.hip)
 #include "asg_beam_lattice.h"     // everything behind the search that the token family's loss shares
 
@@ -39,55 +40,11 @@ namespace asg {
 namespace {
 
 // ---------------------------------------------------------------------------------------------------------------------
-// 1: the search.  beam_word_kernel's frame loop; cnt[t] = |A_t| for t < len.  With LA it is beam_word_la_kernel's frame loop
-// (include/asg_hip.h::asg_beam_words_full_forward_la): the frame compiled with the look-ahead flag on, as the two word streams
-// compile theirs, so the sets are the look-ahead decoder's.  The values the frame ranks by stay in LDS: launches 2 - 4 and the
-// backward read the pairs alone and weigh them plainly.
+// 1: the search.  beam_word_search<.., WordSearch::Sets> (asg_beam_word_search.h): the decoder's prologue and frame loop, cnt[t] =
+// |A_t| for t < len, no end.  With LA (include/asg_hip.h::asg_beam_words_full_forward_la) the frame is compiled with the
+// look-ahead flag on, so the sets are the look-ahead decoder's.  The values the frame ranks by stay in LDS: launches 2 - 4 and
+// the backward read the pairs alone and weigh them plainly.
 // ---------------------------------------------------------------------------------------------------------------------
-template <typename R, bool TRL, bool LA = false>
-__global__ void __launch_bounds__(kBT) beam_word_loss_search(Problem P, GraphArgs g, BeamGraphArgs bg, WordLmArgs lm, int K, R theta,
-                                                             int cap, int tbits, char *work, size_t per_utt, size_t cnt_off,
-                                                             WordLookParam<LA> la) {
-    using U = typename Key<R>::U;
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    Ctl<U> &ctl = *(Ctl<U> *) lds;
-    WordCtl &wctl = *(WordCtl *) (lds + kWordCtlOff);
-    R *cur_v = (R *) (lds + kFixedLds);                    // [K]
-    int *cur_q = (int *) (cur_v + K);                      // [K]
-    int *cur_h = cur_q + K;                                // [K]
-    R *trs = (R *) (cur_h + K);                            // [N][N] if TRL
-    const int tid = threadIdx.x, b = blockIdx.x;
-    const int N = P.N, T = P.T;
-    const int len = clamp_len(P.in_len, b, T);
-    const R *in = (const R *) P.inputs + (int64_t) b * P.is1;
-    const R *tr = (const R *) P.transition;
-    BeamWordFrame<R, LA> f;
-    f.ctl = &ctl; f.wctl = &wctl; f.cur_v = cur_v; f.cur_q = cur_q; f.cur_h = cur_h; f.trs = trs; f.tr = tr;
-    f.ts0 = P.ts0; f.ts1 = P.ts1; f.N = N; f.theta = theta;
-    bind_graph<R, LA>(f, g, bg, lm, K, cap, tbits);
-    bind_look<R>(f, la);
-    int *bq, *bh, *bs;
-    char *wb = work + (size_t) b * per_utt;
-    f.bind_work(wb, T, bq, bh, bs);
-    int *cnt = (int *) (wb + cnt_off);
-    if (len < 1) return;
-    if constexpr (TRL)
-        for (int x = tid; x < N * N; x += kBT) trs[x] = tr[(int64_t) (x / N) * P.ts0 + (int64_t) (x % N) * P.ts1];
-    if (len >= 2) {
-        const size_t C = (size_t) 1 << tbits;
-        for (size_t s = tid; s < C; s += kBT) { dev_store(f.tkey + s, 0ull); dev_store(f.val + s, (U) 0); dev_store(f.arg + s, ~0ull); }
-    }
-    if (tid == 0) { ctl.na = 0; ctl.n = 0; }
-    __syncthreads();
-    int t = 0;
-    for (; t < len; ++t) {
-        const int na = ctl.na;
-        if (t >= 1 && na == 0) break;                       // an empty beam stays empty
-        beam_word_frame<R, TRL, LA>(f, t == 0, na, in + (int64_t) t * P.is0, P.is2, bq, bh, bs, t);
-        if (tid == 0) cnt[t] = ctl.na < K ? ctl.na : K;
-    }
-    for (int u = t + tid; u < len; u += kBT) cnt[u] = 0;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // 2: the walk of the merged target through the lexicon and the LM.  -> n pairs into key[0 .. n) (when key is not null) and the
@@ -292,28 +249,12 @@ template <typename R>
 hipError_t launch_beam_word_loss_forward(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
                                          const WordLookArgs *LA, int K, double theta, bool store, void *work, void *scores,
                                          hipStream_t stream) {
-    const int T = P.T, B = P.B, N = P.N;
+    const int T = P.T;
     const int cap = beam_word_cap(K, BG.max_out, BG.num_start);
-    const int tbits = word_table_bits(cap);
     const int nf = P.targets ? (P.S < T ? P.S : T) : 0;
     const BeamWordLossLayout lay = beam_word_loss_layout(sizeof(R), T, K, cap, nf, store);
-    char *w = (char *) work;
-    {
-        const size_t beam = kFixedLds + (size_t) K * (sizeof(R) + 8);
-        const bool trl = beam + (size_t) N * N * sizeof(R) <= kLdsMax;
-        const size_t dyn = beam + (trl ? (size_t) N * N * sizeof(R) : 0);
-#define ASG_BEAM_WORD_LOSS_SEARCH(TRL, LAF, LOOK)                                                                             \
-    do {                                                                                                                     \
-        set_lds((const void *) beam_word_loss_search<R, TRL, LAF>, dyn);                                                    \
-        hipLaunchKernelGGL((beam_word_loss_search<R, TRL, LAF>), dim3(B), dim3(kBT), dyn, stream, P, G, BG, LM, K,         \
-                           (R) theta, cap, tbits, w, lay.per, lay.cnt, LOOK);                                                \
-    } while (0)
-        if (LA) { if (trl) ASG_BEAM_WORD_LOSS_SEARCH(true, true, *LA); else ASG_BEAM_WORD_LOSS_SEARCH(false, true, *LA); }
-        else if (trl) ASG_BEAM_WORD_LOSS_SEARCH(true, false, WordNoLook{});
-        else ASG_BEAM_WORD_LOSS_SEARCH(false, false, WordNoLook{});
-#undef ASG_BEAM_WORD_LOSS_SEARCH
-    }
-    const hipError_t e = hipGetLastError();
+    const hipError_t e = launch_beam_word_search<R, WordSearch::Sets>(P, G, BG, LM, LA, K, theta, work, lay.per, lay.cnt, 0, {}, nullptr,
+                                                                      stream);
     if (e != hipSuccess) return e;
     return launch_beam_word_loss_lattice<R>(P, G, BG, LM, lay, K, store, work, scores, stream);
 }

@@ -8,7 +8,7 @@
 // token sequences, and the search has left (q, h, source slot) of every kept pair of every frame on the device.  ONE kernel,
 // beam_word_nbest_kernel, one 1024-thread workgroup per utterance or stream slot, told where the last set and the [T][K] rows
 // live (BeamWordNbestSrc):
-//   one-shot   behind beam_word_kernel on the same stream (the decoder's own device code, so the same sets and back-pointers bit
+//   one-shot   behind the decoder's search (asg_beam_word.hip) on the same stream (its own device code, so the same sets and back-pointers bit
 //              for bit), asked to leave |A_{len-1}| and that set beside its rows;
 //   stream     over a stream state, which holds the set in memory already; it is only read.
 //   window     over a window state of asg_beam_word_window.hip, whose rows are rings: every row is the uncommitted tail of its
@@ -29,7 +29,7 @@
 // Every output, padding row and scratch word that is read is written here: no memset, no copy.  One integer LDS counter; no
 // atomics on values: bit-identical run to run.
 //
-// The same kernel with the look-ahead flag (LA) serves the searches with LM look-ahead: behind beam_word_la_kernel, or over a state
+// The same kernel with the look-ahead flag (LA) serves the searches with LM look-ahead: behind the decoder's search with one, or over a state
 // that asg_beam_word_stream_advance_la left.  The end of an entry is then word_end<R, true>'s / word_prefix<R, true>'s, which take
 // the estimate the value still carries back; the walk, the three sums and the write stage are the same text.
 #include "asg_common.h"
@@ -357,7 +357,7 @@ hipError_t launch_nbest_kernel(const Problem &P, const GraphArgs &G, const BeamG
 }  // namespace
 
 // The n-best kernel alone over what a search of this family left (src), one-shot (final = 1, the lengths of the problem): behind
-// the decoder's search here, behind beam_word_conf_search in asg_beam_word_nbest_conf.hip.  LA: that search's look-ahead, or NULL.
+// the decoder's search here, behind launch_beam_word_conf_search in asg_beam_word_nbest_conf.hip.  LA: that search's look-ahead, or NULL.
 template <typename R>
 hipError_t launch_beam_word_nbest_over(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
                                        const WordLookArgs *LA, const BeamWordNbestSrc &src, int K, int nbest, void *scores,
@@ -398,83 +398,47 @@ size_t beam_word_stream_nbest_work_bytes(int max_frames, int B, int K, int nbest
     return (size_t) B * a256((size_t) max_frames * (nbest < K ? nbest : K) * 4);
 }
 
-namespace {
-
-// The search -- asg_beam_word.hip's, or with LA asg_beam_word_la.hip's -- asked to leave its last set, then the n-best kernel
-// over what it left, on one stream.
-template <typename R, bool LA>
-hipError_t beam_words_nbest(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
-                            const WordLookParam<LA> &look, int K, double theta, int nbest, void *work, void *scores,
-                            void *emission_scores, void *graph_scores, void *lm_scores, long long *path, long long *tokens,
-                            long long *tlen, long long *states, long long *lm_states, long long *words, long long *wlen,
-                            long long *num_hyps, hipStream_t stream) {
+// The search of asg_beam_word.hip (LA: its look-ahead, or NULL) asked to leave its last set, then the n-best kernel over what it
+// left, on one stream.
+template <typename R>
+hipError_t launch_beam_words_nbest(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                                   const WordLookArgs *LA, int K, double theta, int nbest, void *work, void *scores,
+                                   void *emission_scores, void *graph_scores, void *lm_scores, long long *path, long long *tokens,
+                                   long long *tlen, long long *states, long long *lm_states, long long *words, long long *wlen,
+                                   long long *num_hyps, hipStream_t stream) {
     const int T = P.T, B = P.B;
     const int cap = beam_word_cap(K, BG.max_out, BG.num_start);
     const BeamWordNbestLayout lay = beam_word_nbest_layout(sizeof(R), T, K, cap, nbest);
     char *w = (char *) work, *tail = w + (size_t) B * lay.per;
     const size_t bb = a256((size_t) B * 8), BT = (size_t) B * T;
     long long *wide = (long long *) (tail + 3 * bb);                        // path, tokens, states, lm_states, words of the one best
-    hipError_t e;
-    if constexpr (LA)
-        e = launch_beam_words_la<R>(P, G, BG, LM, look, K, theta, work, tail, wide, wide + BT, (long long *) (tail + bb),
-                                    wide + 2 * BT, wide + 3 * BT, wide + 4 * BT, (long long *) (tail + 2 * bb), stream, lay.per,
-                                    lay.fin);
-    else
-        e = launch_beam_words<R>(P, G, BG, LM, K, theta, work, tail, wide, wide + BT, (long long *) (tail + bb), wide + 2 * BT,
-                                 wide + 3 * BT, wide + 4 * BT, (long long *) (tail + 2 * bb), stream, lay.per, lay.fin);
+    const hipError_t e = launch_beam_words<R>(P, G, BG, LM, LA, K, theta, work, tail, wide, wide + BT, (long long *) (tail + bb),
+                                              wide + 2 * BT, wide + 3 * BT, wide + 4 * BT, (long long *) (tail + 2 * bb), stream,
+                                              lay.per, lay.fin);
     if (e != hipSuccess) return e;
     BeamWordNbestSrc src{};
     src.base = w; src.per = lay.per; src.set_off = lay.fin + 8; src.na_off = lay.fin; src.pos_off = 0; src.ovf_off = 0;
     src.cols = w + lay.rows; src.cols_per = lay.per; src.Tw = T; src.nb = lay.nb;
-    return launch_nbest_kernel<R, LA>(P, G, BG, LM, look, src, B, K, nbest, 1, scores, emission_scores, graph_scores, lm_scores, path,
-                                      tokens, tlen, states, lm_states, words, wlen, num_hyps, nullptr, nullptr, stream);
+    return launch_beam_word_nbest_over<R>(P, G, BG, LM, LA, src, K, nbest, scores, emission_scores, graph_scores, lm_scores, path,
+                                          tokens, tlen, states, lm_states, words, wlen, num_hyps, stream);
 }
-
-}  // namespace
-
-template <typename R>
-hipError_t launch_beam_words_nbest(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int K,
-                                   double theta, int nbest, void *work, void *scores, void *emission_scores, void *graph_scores,
-                                   void *lm_scores, long long *path, long long *tokens, long long *tlen, long long *states,
-                                   long long *lm_states, long long *words, long long *wlen, long long *num_hyps,
-                                   hipStream_t stream) {
-    return beam_words_nbest<R, false>(P, G, BG, LM, WordNoLook{}, K, theta, nbest, work, scores, emission_scores, graph_scores,
-                                      lm_scores, path, tokens, tlen, states, lm_states, words, wlen, num_hyps, stream);
-}
-template <typename R>
-hipError_t launch_beam_words_nbest_la(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
-                                      const WordLookArgs &LA, int K, double theta, int nbest, void *work, void *scores,
-                                      void *emission_scores, void *graph_scores, void *lm_scores, long long *path,
-                                      long long *tokens, long long *tlen, long long *states, long long *lm_states,
-                                      long long *words, long long *wlen, long long *num_hyps, hipStream_t stream) {
-    return beam_words_nbest<R, true>(P, G, BG, LM, LA, K, theta, nbest, work, scores, emission_scores, graph_scores, lm_scores,
-                                     path, tokens, tlen, states, lm_states, words, wlen, num_hyps, stream);
-}
-template hipError_t launch_beam_words_nbest<float>(const Problem &, const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &, int,
-                                                   double, int, void *, void *, void *, void *, void *, long long *, long long *,
+template hipError_t launch_beam_words_nbest<float>(const Problem &, const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &,
+                                                   const WordLookArgs *, int, double, int, void *, void *, void *, void *, void *,
                                                    long long *, long long *, long long *, long long *, long long *, long long *,
-                                                   hipStream_t);
-template hipError_t launch_beam_words_nbest<double>(const Problem &, const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &, int,
-                                                    double, int, void *, void *, void *, void *, void *, long long *, long long *,
+                                                   long long *, long long *, hipStream_t);
+template hipError_t launch_beam_words_nbest<double>(const Problem &, const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &,
+                                                    const WordLookArgs *, int, double, int, void *, void *, void *, void *, void *,
                                                     long long *, long long *, long long *, long long *, long long *, long long *,
-                                                    hipStream_t);
-template hipError_t launch_beam_words_nbest_la<float>(const Problem &, const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &,
-                                                      const WordLookArgs &, int, double, int, void *, void *, void *, void *, void *,
-                                                      long long *, long long *, long long *, long long *, long long *, long long *,
-                                                      long long *, long long *, hipStream_t);
-template hipError_t launch_beam_words_nbest_la<double>(const Problem &, const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &,
-                                                       const WordLookArgs &, int, double, int, void *, void *, void *, void *,
-                                                       void *, long long *, long long *, long long *, long long *, long long *,
-                                                       long long *, long long *, long long *, hipStream_t);
+                                                    long long *, long long *, hipStream_t);
 
-namespace {
-
-template <typename R, bool LA>
-hipError_t beam_word_stream_nbest(const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, const WordLookParam<LA> &look,
-                                  int K, int max_frames, int B, const void *state, int final, int nbest, void *work, void *scores,
-                                  void *graph_scores, void *lm_scores, long long *path, long long *tokens, long long *tlen,
-                                  long long *states, long long *lm_states, long long *words, long long *wlen, long long *num_hyps,
-                                  long long *frames, long long *status, hipStream_t stream, size_t stride) {
+// The kernel over a stream state (LA: the look-ahead launch_beam_word_stream_advance left it with, or NULL).
+template <typename R>
+hipError_t launch_beam_word_stream_nbest(const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, const WordLookArgs *LA,
+                                         int K, int max_frames, int B, const void *state, int final, int nbest, void *work,
+                                         void *scores, void *graph_scores, void *lm_scores, long long *path, long long *tokens,
+                                         long long *tlen, long long *states, long long *lm_states, long long *words,
+                                         long long *wlen, long long *num_hyps, long long *frames, long long *status,
+                                         hipStream_t stream, size_t stride) {
     const int cap = beam_word_cap(K, BG.max_out, BG.num_start);
     const BeamStreamLayout lay = beam_word_stream_layout(sizeof(R), max_frames, K, cap);
     BeamWordNbestSrc src{};
@@ -485,52 +449,23 @@ hipError_t beam_word_stream_nbest(const GraphArgs &G, const BeamGraphArgs &BG, c
     src.cols = (char *) work; src.cols_per = a256((size_t) max_frames * src.nb * 4); src.Tw = max_frames;
     Problem P{};                                                            // no emissions, no lengths: the state has both
     P.T = max_frames; P.B = B; P.N = 0;
-    return launch_nbest_kernel<R, LA>(P, G, BG, LM, look, src, B, K, nbest, final != 0, scores, nullptr, graph_scores, lm_scores, path,
-                                      tokens, tlen, states, lm_states, words, wlen, num_hyps, frames, status, stream);
+    if (LA)
+        return launch_nbest_kernel<R, true>(P, G, BG, LM, *LA, src, B, K, nbest, final != 0, scores, nullptr, graph_scores, lm_scores,
+                                            path, tokens, tlen, states, lm_states, words, wlen, num_hyps, frames, status, stream);
+    return launch_nbest_kernel<R, false>(P, G, BG, LM, WordNoLook{}, src, B, K, nbest, final != 0, scores, nullptr, graph_scores,
+                                         lm_scores, path, tokens, tlen, states, lm_states, words, wlen, num_hyps, frames, status,
+                                         stream);
 }
-
-}  // namespace
-
-template <typename R>
-hipError_t launch_beam_word_stream_nbest(const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int K, int max_frames,
-                                         int B, const void *state, int final, int nbest, void *work, void *scores,
-                                         void *graph_scores, void *lm_scores, long long *path, long long *tokens, long long *tlen,
-                                         long long *states, long long *lm_states, long long *words, long long *wlen,
-                                         long long *num_hyps, long long *frames, long long *status, hipStream_t stream,
-                                         size_t stride) {
-    return beam_word_stream_nbest<R, false>(G, BG, LM, WordNoLook{}, K, max_frames, B, state, final, nbest, work, scores,
-                                            graph_scores, lm_scores, path, tokens, tlen, states, lm_states, words, wlen, num_hyps,
-                                            frames, status, stream, stride);
-}
-template <typename R>
-hipError_t launch_beam_word_stream_nbest_la(const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
-                                            const WordLookArgs &LA, int K, int max_frames, int B, const void *state, int final,
-                                            int nbest, void *work, void *scores, void *graph_scores, void *lm_scores,
-                                            long long *path, long long *tokens, long long *tlen, long long *states,
-                                            long long *lm_states, long long *words, long long *wlen, long long *num_hyps,
-                                            long long *frames, long long *status, hipStream_t stream, size_t stride) {
-    return beam_word_stream_nbest<R, true>(G, BG, LM, LA, K, max_frames, B, state, final, nbest, work, scores, graph_scores,
-                                           lm_scores, path, tokens, tlen, states, lm_states, words, wlen, num_hyps, frames, status,
-                                           stream, stride);
-}
-template hipError_t launch_beam_word_stream_nbest<float>(const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &, int, int, int,
-                                                         const void *, int, int, void *, void *, void *, void *, long long *,
+template hipError_t launch_beam_word_stream_nbest<float>(const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &,
+                                                         const WordLookArgs *, int, int, int, const void *, int, int, void *,
+                                                         void *, void *, void *, long long *, long long *, long long *,
                                                          long long *, long long *, long long *, long long *, long long *,
-                                                         long long *, long long *, long long *, long long *, hipStream_t, size_t);
-template hipError_t launch_beam_word_stream_nbest<double>(const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &, int, int, int,
-                                                          const void *, int, int, void *, void *, void *, void *, long long *,
+                                                         long long *, long long *, hipStream_t, size_t);
+template hipError_t launch_beam_word_stream_nbest<double>(const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &,
+                                                          const WordLookArgs *, int, int, int, const void *, int, int, void *,
+                                                          void *, void *, void *, long long *, long long *, long long *,
                                                           long long *, long long *, long long *, long long *, long long *,
-                                                          long long *, long long *, long long *, long long *, hipStream_t, size_t);
-template hipError_t launch_beam_word_stream_nbest_la<float>(const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &,
-                                                            const WordLookArgs &, int, int, int, const void *, int, int, void *,
-                                                            void *, void *, void *, long long *, long long *, long long *,
-                                                            long long *, long long *, long long *, long long *, long long *,
-                                                            long long *, long long *, hipStream_t, size_t);
-template hipError_t launch_beam_word_stream_nbest_la<double>(const GraphArgs &, const BeamGraphArgs &, const WordLmArgs &,
-                                                             const WordLookArgs &, int, int, int, const void *, int, int, void *,
-                                                             void *, void *, void *, long long *, long long *, long long *,
-                                                             long long *, long long *, long long *, long long *, long long *,
-                                                             long long *, long long *, hipStream_t, size_t);
+                                                          long long *, long long *, hipStream_t, size_t);
 
 size_t beam_word_window_nbest_work_bytes(int W, int B, int K, int nbest) {
     return (size_t) B * a256((size_t) W * (nbest < K ? nbest : K) * 4);

@@ -4,7 +4,8 @@
 //
 // P(w, t) of asg_beam_words_confidence does not depend on the hypothesis: a row only selects which (word, frame) CELLS are read
 // out.  Eight launches on one stream, the frame loop of the search in one of them:
-//   1  beam_word_conf_search<.., FIN> (asg_beam_word_conf.hip): the search with the decoder's end, which also leaves the last set;
+//   1  launch_beam_word_conf_search (asg_beam_word_conf.hip; beam_word_search<.., FIN, WordSearch::DecodeSets> of
+//      asg_beam_word_search.h): the search with the decoder's end, which also leaves the last set;
 //      its one-best outputs go to the tail of the workspace, as the n-best call's decoder's do.
 //   2  beam_word_nbest_kernel (asg_beam_word_nbest.hip) over what it left: the twelve n-best outputs.
 //   3  nbest_conf_prep: a wavefront per row collapses the row's column of product states into word_frames (ballot and popcount,

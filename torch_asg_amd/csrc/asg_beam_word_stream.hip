@@ -30,7 +30,7 @@
 // device-scope loads and atomics of the frame body.  Integer atomics only: bit-identical run to run.
 //
 // With LM look-ahead (include/asg_hip.h::asg_beam_word_stream_advance_la) the advance and result kernels are compiled a second
-// time with the frame's look-ahead flag on, as asg_beam_word_la.hip compiles the one-shot kernel: the stored values then carry
+// time with the frame's look-ahead flag on, as asg_beam_word.hip compiles the one-shot kernel: the stored values then carry
 // L(h, state(q)), the end takes it back as the one-shot's does and the best prefix by word_prefix.  `look` reads static arrays
 // and the pair's own (h, q), so the argument above holds as it stands; the state has the same bytes.
 #include "asg_common.h"

@@ -21,8 +21,8 @@
 //                                         frame's alpha is computed once however often confidences are asked for, and what it
 //                                         writes depends on nothing but the frames.
 //   beam_word_stream_conf_bwd             one workgroup per slot: the hypothesis by beam_word_stream_hyp (the function
-//                                         beam_word_stream_result_kernel is), word_frames by word_end_frames (the walk of
-//                                         beam_word_conf_search), Z by lattice_z over the last set, and the tail of
+//                                         beam_word_stream_result_kernel is), word_frames by word_end_frames (the walk of the
+//                                         one-shot confidence search), Z by lattice_z over the last set, and the tail of
 //                                         beam_word_conf_bwd by beam_word_conf_words (asg_beam_word_conf_pull.h) over the stored
 //                                         emissions.  The one new thing is the end of a PREFIX (weight 0, no event at frame len),
 //                                         which the pull takes as its lattice type (PrefixWordLat).

@@ -206,14 +206,24 @@ struct WordLmArgs {
 constexpr int kBeamWordMaxIndex = 1 << 25;    // H, Q: (source pair, source slot) is one 64-bit word
 int beam_word_cap(int K, int max_out, int num_start);
 size_t beam_word_work_bytes(int elem, int T, int B, int K, int cap);
+// LM look-ahead (asg_beam_decode_words_la and every other `_la` call of the family): read-only arrays beside the LM and nothing per
+// utterance -- K, cap, the table and the workspace do not depend on it.  The launchers take a pointer: the look-ahead, or null.
+struct WordLookArgs {
+    int A, levels;                            // ranked arcs A', levels of the range-maximum table
+    const int *rlo, *rhi;                     // [S] rank range of the words below each trie node
+    const int *la_state;                      // [H] the (truncated) history whose rows the look-ahead of h reads
+    const int *krow, *krank;                  // [H+1], [A'] ranked arcs of each LM state, rank ascending
+    const void *tab;                          // [levels][A'] in the dtype of the problem
+    const void *dense0;                       // [S] E(0, n): the range maximum of state 0 for every node
+};
 // stride != 0: the utterances' workspaces lie `stride` bytes apart (each with the layout above at its front); fin_off != 0: the
 // kernel also leaves |A_{len-1}| (int32) at that offset of each and, from byte 8 behind it, that set's values [K], then its int32
 // product states [K], then its int32 LM states [K] (asg_beam_word_nbest.hip).  0, 0: the decoder.
 template <typename R>
-hipError_t launch_beam_words(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int K,
-                             double theta, void *work, void *scores, long long *path, long long *tokens, long long *tlen,
-                             long long *states, long long *lm_states, long long *words, long long *wlen, hipStream_t stream,
-                             size_t stride = 0, size_t fin_off = 0);
+hipError_t launch_beam_words(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                             const WordLookArgs *LA, int K, double theta, void *work, void *scores, long long *path,
+                             long long *tokens, long long *tlen, long long *states, long long *lm_states, long long *words,
+                             long long *wlen, hipStream_t stream, size_t stride = 0, size_t fin_off = 0);
 
 // ---- The same search carried across chunks of frames (asg_beam_stream.hip): asg_beam_stream_*.  One slot of the state (byte
 // offsets, each part 256-byte aligned): the beam search's own layout for T = max_frames at the front, then hdr (int32 pos, |A|,
@@ -237,22 +247,6 @@ hipError_t launch_beam_stream_result(const GraphArgs &G, const BeamGraphArgs &BG
                                      int final, void *scores, long long *path, long long *tokens, long long *tlen,
                                      long long *states, long long *frames, long long *status, hipStream_t stream,
                                      size_t stride = 0);      // != 0: the slots lie `stride` bytes apart (asg_beam_stream_conf.hip)
-
-// ---- The same search with LM look-ahead (asg_beam_word_la.hip): asg_beam_decode_words_la.  K, cap, the table and the workspace
-// are those of launch_beam_words, stride and fin_off too; the look-ahead adds read-only arrays and nothing per utterance.
-struct WordLookArgs {
-    int A, levels;                            // ranked arcs A', levels of the range-maximum table
-    const int *rlo, *rhi;                     // [S] rank range of the words below each trie node
-    const int *la_state;                      // [H] the (truncated) history whose rows the look-ahead of h reads
-    const int *krow, *krank;                  // [H+1], [A'] ranked arcs of each LM state, rank ascending
-    const void *tab;                          // [levels][A'] in the dtype of the problem
-    const void *dense0;                       // [S] E(0, n): the range maximum of state 0 for every node
-};
-template <typename R>
-hipError_t launch_beam_words_la(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
-                                const WordLookArgs &LA, int K, double theta, void *work, void *scores, long long *path,
-                                long long *tokens, long long *tlen, long long *states, long long *lm_states, long long *words,
-                                long long *wlen, hipStream_t stream, size_t stride = 0, size_t fin_off = 0);
 
 // ---- The search over pairs carried across chunks of frames (asg_beam_word_stream.hip): asg_beam_word_stream_*.  One slot of the
 // state: the word decoder's own layout for T = max_frames at the front, then hdr (int32 pos, |A|, overflow) and the stored set
@@ -311,36 +305,22 @@ hipError_t launch_beam_word_nbest_over(const Problem &P, const GraphArgs &G, con
                                        void *emission_scores, void *graph_scores, void *lm_scores, long long *path,
                                        long long *tokens, long long *tlen, long long *states, long long *lm_states,
                                        long long *words, long long *wlen, long long *num_hyps, hipStream_t stream);
-// path / states / lm_states may be null (then they are not written)
+// path / states / lm_states may be null (then they are not written).  LA: the look-ahead of the search (launch_beam_words), or NULL.
 template <typename R>
-hipError_t launch_beam_words_nbest(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int K,
-                                   double theta, int nbest, void *work, void *scores, void *emission_scores, void *graph_scores,
-                                   void *lm_scores, long long *path, long long *tokens, long long *tlen, long long *states,
-                                   long long *lm_states, long long *words, long long *wlen, long long *num_hyps,
-                                   hipStream_t stream);
-// ... behind the search with LM look-ahead (launch_beam_words_la): asg_beam_decode_words_nbest_la.  Same workspace.
+hipError_t launch_beam_words_nbest(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
+                                   const WordLookArgs *LA, int K, double theta, int nbest, void *work, void *scores,
+                                   void *emission_scores, void *graph_scores, void *lm_scores, long long *path, long long *tokens,
+                                   long long *tlen, long long *states, long long *lm_states, long long *words, long long *wlen,
+                                   long long *num_hyps, hipStream_t stream);
+// The same kernel over a stream state (read only).  The state holds no emissions: there is no emission sum.  LA: the look-ahead
+// launch_beam_word_stream_advance left the state with, or NULL.
 template <typename R>
-hipError_t launch_beam_words_nbest_la(const Problem &P, const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
-                                      const WordLookArgs &LA, int K, double theta, int nbest, void *work, void *scores,
-                                      void *emission_scores, void *graph_scores, void *lm_scores, long long *path,
-                                      long long *tokens, long long *tlen, long long *states, long long *lm_states,
-                                      long long *words, long long *wlen, long long *num_hyps, hipStream_t stream);
-// The same kernel over a stream state (read only).  The state holds no emissions: there is no emission sum.
-template <typename R>
-hipError_t launch_beam_word_stream_nbest(const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, int K, int max_frames,
-                                         int B, const void *state, int final, int nbest, void *work, void *scores,
-                                         void *graph_scores, void *lm_scores, long long *path, long long *tokens, long long *tlen,
-                                         long long *states, long long *lm_states, long long *words, long long *wlen,
-                                         long long *num_hyps, long long *frames, long long *status, hipStream_t stream,
-                                         size_t stride = 0);    // as launch_beam_word_stream_result's
-// ... over a state that launch_beam_word_stream_advance left with the look-ahead LA: asg_beam_word_stream_nbest_la.
-template <typename R>
-hipError_t launch_beam_word_stream_nbest_la(const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM,
-                                            const WordLookArgs &LA, int K, int max_frames, int B, const void *state, int final,
-                                            int nbest, void *work, void *scores, void *graph_scores, void *lm_scores,
-                                            long long *path, long long *tokens, long long *tlen, long long *states,
-                                            long long *lm_states, long long *words, long long *wlen, long long *num_hyps,
-                                            long long *frames, long long *status, hipStream_t stream, size_t stride = 0);
+hipError_t launch_beam_word_stream_nbest(const GraphArgs &G, const BeamGraphArgs &BG, const WordLmArgs &LM, const WordLookArgs *LA,
+                                         int K, int max_frames, int B, const void *state, int final, int nbest, void *work,
+                                         void *scores, void *graph_scores, void *lm_scores, long long *path, long long *tokens,
+                                         long long *tlen, long long *states, long long *lm_states, long long *words,
+                                         long long *wlen, long long *num_hyps, long long *frames, long long *status,
+                                         hipStream_t stream, size_t stride = 0);    // as launch_beam_word_stream_result's
 
 // ---- The stream in bounded memory (asg_beam_window.hip): asg_beam_window_*.  One slot of the state has the layout of a stream
 // of W frames -- the back-pointers are a ring, frame u in row u mod W -- with the header int64 pos, int64 base, int32 |A|, carry,
