@@ -1308,6 +1308,31 @@ int asg_target_graph_viterbi(asg_ctx *ctx, const asg_problem *p, const asg_targe
                              void *scores, int64_t *nodes, int64_t *labels, int64_t *tokens, int64_t *token_frames,
                              int64_t *token_lengths, int flags, void *stream);
 
+/* ---- How sure that best path is: TOKEN CONFIDENCES of asg_target_graph_viterbi's path and the POSTERIORS OF THE FINAL NODES
+ * under asg_target_graph_forward's sum.  No counterpart in the reference.  scores, nodes, labels, tokens, token_frames and
+ * token_lengths are asg_target_graph_viterbi's bits and normalisers [B] asg_target_graph_forward's scores on the same
+ * arguments.  With alpha, f_e and Z = normalisers[b] of that forward and beta its backward's, in the dtype of the problem:
+ *   a token of label i STARTS at frame t on a path whose first node has label i (t = 0) or that enters a node of label i
+ *   over an edge at frame t (1 <= t <= len-1); the stay starts none.
+ *   P(i, 0)      = sum over the nodes k of label i of exp((alpha[0][k] + beta[0][k]) - Z)
+ *   P(i, t >= 1) = sum over the edges e into nodes k of label i of exp((alpha[t-1][src_e] + ((beta[t][k] + f_e) + I[t][l_k])) - Z)
+ *   token_confidences[b][j] = sum of P(tokens[b][j], t) over |t - token_frames[b][j]| <= frame_tolerance, t in [0, len-1];
+ *                             0 for j >= token_lengths[b]                                     [B,T], dtype of the problem
+ *   final_posteriors[b][k]  = exp((alpha[len-1][k] + final_w[k]) - Z); 0 for k >= K_b          [B,Kmax], dtype of the problem
+ * With frame_tolerance 0 a confidence is a probability, between exp(scores - normalisers) and 1 up to rounding; with a
+ * tolerance it is an expected count and may pass 1.  An utterance whose normaliser is -inf (len 0, empty graph, no finite
+ * path) has both float outputs 0, never a NaN.  A token's terms are summed as 64-bit fixed point at 2^54 (integer adds, any
+ * order, the same bits); three launches (the forward with alpha kept, the best path, the beta pull), every output element
+ * written by a kernel, nothing synchronises: bit-identical run to run, and a warm call can be captured.
+ *   work: asg_target_graph_confidence_work_bytes(p, tg) = (B * T * Kmax * e rounded up to 16) + B * T * Kmax * 2 bytes
+ * 0 <= frame_tolerance <= 64 (negative: ASG_ERR_INVALID; larger: ASG_ERR_UNSUPPORTED).  Otherwise limits and return codes are
+ * asg_target_graph_forward's (a batch that scores also gets confidences); the size call returns 0 beyond them. */
+size_t asg_target_graph_confidence_work_bytes(const asg_problem *p, const asg_target_graphs *tg);
+int asg_target_graph_confidence(asg_ctx *ctx, const asg_problem *p, const asg_target_graphs *tg, int frame_tolerance, void *work,
+                                size_t work_bytes, void *scores, int64_t *nodes, int64_t *labels, int64_t *tokens,
+                                int64_t *token_frames, int64_t *token_lengths, void *normalisers, void *token_confidences,
+                                void *final_posteriors, int flags, void *stream);
+
 /* ---- BEAM-PRUNED full score of the same composed lattice, and its gradients: asg_graph_full_forward / _backward over the
  * lattice that asg_beam_decode_graph's search keeps -- a normaliser Z_K whose work per frame follows the beam and not Q or E, so a
  * criterion can be trained with the automata (4-grams, lexicon tries) the beam decoder was built for.  No counterpart in the

@@ -899,6 +899,30 @@ class HipBackend:
                        "asg_target_graph_viterbi")
         return scores, out[0], out[1], out[2], out[3], token_lengths
 
+    def target_graph_confidence(self, inputs, transition, graphs, input_lengths, frame_tolerance=0):
+        """target_graph_viterbi's six outputs, then normalisers[B], token_confidences[B,T] and final_posteriors[B,Kmax]; see
+        include/asg_hip.h::asg_target_graph_confidence.  Three launches for the whole batch, one workspace."""
+        L = _lib.lib()
+        T, B, N = inputs.shape
+        dev = inputs.device
+        tol = max(-1, min(int(frame_tolerance), (1 << 31) - 1))
+        with self._guard(dev):
+            (tg,), _, keep = self._target_graph_args(inputs, transition, graphs, input_lengths)
+            p, _, input_lengths, _ = self._device_problem(inputs, transition, None, input_lengths, None)
+            work = self._buf(int(L.asg_target_graph_confidence_work_bytes(ctypes.byref(p), ctypes.byref(tg))), dev)
+            both = torch.empty(2, B, dtype=inputs.dtype, device=dev)
+            out = torch.empty(4, B, T, dtype=torch.int64, device=dev)
+            token_lengths = torch.empty(B, dtype=torch.int64, device=dev)
+            conf = torch.empty(B, T, dtype=inputs.dtype, device=dev)
+            post = torch.empty(B, graphs.Kmax, dtype=inputs.dtype, device=dev)
+            # (as target_graph_viterbi: one stream, nothing created here, so a warm call may run under capture)
+            _lib.check(L.asg_target_graph_confidence(None, ctypes.byref(p), ctypes.byref(tg), tol, work.data_ptr(), work.numel(),
+                                                     both[0].data_ptr(), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
+                                                     out[3].data_ptr(), token_lengths.data_ptr(), both[1].data_ptr(),
+                                                     conf.data_ptr(), post.data_ptr(), 0, self._stream(dev)),
+                       "asg_target_graph_confidence")
+        return both[0], out[0], out[1], out[2], out[3], token_lengths, both[1], conf, post
+
     def _beam_loss_args(self, inputs, transition, graph, input_lengths, targets, target_lengths, lm_weight, token_score):
         """Checks shared by the beam-pruned loss entry points -> ((the asg_token_graph_beam_loss view,), Q, the compiled graph it
         points into): `_lattice_forward`'s `prepare`."""
@@ -1881,20 +1905,64 @@ def target_graph_viterbi(inputs, transition, graphs, input_lengths=None):
         inputs, transition = _plain(inputs, transition)
         scores, nodes, labels, tokens, frames, token_lengths = native().target_graph_viterbi(inputs, transition, graphs,
                                                                                              input_lengths)
-        alternatives = None
-        fa = graphs.final_alternative_on(inputs.device)
-        if fa is not None:
-            T, B = inputs.shape[0], inputs.shape[1]
-            if T == 0 or fa.shape[1] == 0:
-                alternatives = torch.full((B,), -1, dtype=torch.int64, device=inputs.device)
-            else:
-                if input_lengths is None:
-                    at = torch.full((B, 1), T - 1, dtype=torch.int64, device=inputs.device)
-                else:
-                    at = (_on_device(input_lengths, inputs.device, True).clamp(0, T) - 1).clamp(min=0).unsqueeze(1)
-                end = nodes.gather(1, at)                             # -1 where the score is -inf
-                alternatives = torch.where(end >= 0, fa.gather(1, end.clamp(min=0)), end).squeeze(1)
+        alternatives = _target_graph_alternatives(graphs, nodes, inputs, input_lengths)
     return TargetGraphAlignment(scores, nodes, labels, tokens, frames, token_lengths, alternatives)
+
+
+def _target_graph_alternatives(graphs, nodes, inputs, input_lengths):
+    """The sequence that the path `nodes` [B,T] spells: `final_alternative` at its last node, a device gather (None for graphs
+    built from arrays)."""
+    fa = graphs.final_alternative_on(inputs.device)
+    if fa is None:
+        return None
+    T, B = inputs.shape[0], inputs.shape[1]
+    if T == 0 or fa.shape[1] == 0:
+        return torch.full((B,), -1, dtype=torch.int64, device=inputs.device)
+    if input_lengths is None:
+        at = torch.full((B, 1), T - 1, dtype=torch.int64, device=inputs.device)
+    else:
+        at = (_on_device(input_lengths, inputs.device, True).clamp(0, T) - 1).clamp(min=0).unsqueeze(1)
+    end = nodes.gather(1, at)                                         # -1 where the score is -inf
+    return torch.where(end >= 0, fa.gather(1, end.clamp(min=0)), end).squeeze(1)
+
+
+TargetGraphConfidence = collections.namedtuple("TargetGraphConfidence", TargetGraphAlignment._fields + (
+    "normalisers", "token_confidences", "final_posteriors", "alternative_posteriors"))
+
+
+def target_graph_confidence(inputs, transition, graphs, input_lengths=None, frame_tolerance=0):
+    """`target_graph_viterbi` with how sure it is: the best path of each utterance's target graph, the confidence of each of
+    its tokens and the posterior of each alternative under `target_graph_score`'s sum over all paths.  No gradient.
+
+    Inputs, strides, widening and errors as `target_graph_viterbi`.  Returns a `TargetGraphConfidence`: first the seven fields
+    of `TargetGraphAlignment`, bit for bit what `target_graph_viterbi` returns on the same arguments; then
+      normalisers [B]              `target_graph_score`'s bits on the same arguments
+      token_confidences [B,T]      for token j the sum of P(tokens[j], t) over |t - token_frames[j]| <= frame_tolerance inside
+                                   the utterance, P(i, t) the posterior that a token of label i starts at frame t (a path
+                                   begins in a node of label i at t = 0, or enters one over an edge at t); 0 behind token_lengths
+      final_posteriors [B,Kmax]    the posterior that a path ends in node k, 0 behind the graph's nodes
+      alternative_posteriors [B,Amax]  for graphs from `from_alternatives` / `from_targets` final_posteriors at the node in
+                                   which sequence a ends, 0 behind the utterance's sequences: they sum to 1 where the normaliser
+                                   is finite.  None for graphs built from arrays.
+    With frame_tolerance = 0 a confidence is a probability, between exp(scores - normalisers) and 1 up to rounding.  With a
+    tolerance it is an expected count, unclipped: "a b a" inside one window passes 1.  An utterance whose normaliser is -inf
+    (length 0, an empty graph, no finite path) has the float outputs 0; there is never a NaN.  frame_tolerance < 0 raises
+    ValueError, > 64 is refused by the library (RuntimeError).  Bit-identical run to run; a warm call can be captured."""
+    if int(frame_tolerance) < 0:
+        raise ValueError("torch_asg_amd.target_graph_confidence: frame_tolerance must be >= 0")
+    with torch.no_grad():
+        inputs, transition = _plain(inputs, transition)
+        out = native().target_graph_confidence(inputs, transition, graphs, input_lengths, frame_tolerance)
+        nodes, post = out[1], out[8]
+        alternatives = _target_graph_alternatives(graphs, nodes, inputs, input_lengths)
+        alt_post = None
+        af = graphs.alternative_final_on(inputs.device)
+        if af is not None:
+            if af.shape[1] == 0 or post.shape[1] == 0:
+                alt_post = torch.zeros(af.shape, dtype=post.dtype, device=post.device)
+            else:
+                alt_post = torch.where(af >= 0, post.gather(1, af.clamp(min=0)), torch.zeros((), dtype=post.dtype, device=post.device))
+    return TargetGraphConfidence(*out[:6], alternatives, *out[6:], alt_post)
 
 
 class BeamGraphFullScore(torch.autograd.Function):
@@ -2337,6 +2405,11 @@ class ASGLoss(nn.Module):
         """Best path of each utterance's target graph under this module's transition matrix: see
         `torch_asg_amd.target_graph_viterbi`."""
         return target_graph_viterbi(inputs, self.transition, graphs, input_lengths)
+
+    def target_graph_confidence(self, inputs, graphs, input_lengths=None, frame_tolerance=0):
+        """That best path with its token confidences and the alternatives' posteriors under this module's transition matrix:
+        `torch_asg_amd.target_graph_confidence`."""
+        return target_graph_confidence(inputs, self.transition, graphs, input_lengths, frame_tolerance)
 
     def beam_graph_loss(self, inputs, targets, graph, input_lengths=None, target_lengths=None, lm_weight=1.0, token_score=0.0,
                         max_work_bytes=1 << 30, beam_size=256, beam_threshold=float("inf")):

@@ -2824,6 +2824,49 @@ int asg_target_graph_viterbi(asg_ctx *ctx, const asg_problem *p, const asg_targe
                                             (hipStream_t) stream)));
 }
 
+// work of the confidences: [alpha B*T*Kmax elements, rounded up to 16 bytes][back-pointers B*T*Kmax x 16 bits]
+static size_t target_graph_conf_alpha_bytes(const asg_problem *p, const asg_target_graphs *tg) {
+    const size_t a = target_graph_work_bytes(p->dtype == ASG_DTYPE_F64 ? 8 : 4, (int) p->T, (int) p->B, (int) tg->Kmax, true);
+    return (a + 15) & ~(size_t) 15;
+}
+
+size_t asg_target_graph_confidence_work_bytes(const asg_problem *p, const asg_target_graphs *tg) {
+    if (check_target_graphs(p, tg, true) != ASG_OK) return 0;
+    return target_graph_conf_alpha_bytes(p, tg) + target_graph_viterbi_work_bytes((int) p->T, (int) p->B, (int) tg->Kmax);
+}
+
+int asg_target_graph_confidence(asg_ctx *ctx, const asg_problem *p, const asg_target_graphs *tg, int frame_tolerance, void *work,
+                                size_t work_bytes, void *scores, int64_t *nodes, int64_t *labels, int64_t *tokens,
+                                int64_t *token_frames, int64_t *token_lengths, void *normalisers, void *token_confidences,
+                                void *final_posteriors, int flags, void *stream) {
+    (void) ctx; (void) flags;
+    int rc = check_target_graphs(p, tg, false);
+    if (rc) return rc;
+    if (frame_tolerance < 0) return ASG_ERR_INVALID;
+    if (frame_tolerance > kTargetGraphConfMaxTol) return ASG_ERR_UNSUPPORTED;
+    const size_t need = asg_target_graph_confidence_work_bytes(p, tg);
+    if (!scores || !nodes || !labels || !tokens || !token_frames || !token_lengths || !normalisers || !token_confidences ||
+        (tg->Kmax > 0 && !final_posteriors) || (need && !work))
+        return ASG_ERR_INVALID;
+    if (work_bytes < need) return ASG_ERR_WORKSPACE;
+    const Problem P = to_problem(p);
+    const TargetGraphArgs G = to_target_graph_args(tg);
+    void *bp = (char *) work + target_graph_conf_alpha_bytes(p, tg);
+    hipStream_t s = (hipStream_t) stream;
+    hipError_t e = ASG_DISPATCH(p, launch_target_graph_forward<float>(P, G, true, work, normalisers, s),
+                                launch_target_graph_forward<double>(P, G, true, work, normalisers, s));
+    if (e != hipSuccess) return hip_status(e);
+    e = ASG_DISPATCH(p,
+        launch_target_graph_viterbi<float>(P, G, bp, scores, nodes, labels, tokens, token_frames, token_lengths, s),
+        launch_target_graph_viterbi<double>(P, G, bp, scores, nodes, labels, tokens, token_frames, token_lengths, s));
+    if (e != hipSuccess) return hip_status(e);
+    return hip_status(ASG_DISPATCH(p,
+        launch_target_graph_conf<float>(P, G, frame_tolerance, work, normalisers, tokens, token_frames, token_lengths,
+                                        token_confidences, final_posteriors, s),
+        launch_target_graph_conf<double>(P, G, frame_tolerance, work, normalisers, tokens, token_frames, token_lengths,
+                                         token_confidences, final_posteriors, s)));
+}
+
 int asg_backward(asg_ctx *ctx, const asg_problem *p, const void *state, size_t state_bytes,
                  const void *grad_full, const void *grad_aligned, void *scratch, size_t scratch_bytes,
                  void *grad_transition, void *grad_inputs, int flags, void *stream) {

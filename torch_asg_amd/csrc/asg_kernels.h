@@ -774,6 +774,15 @@ hipError_t launch_target_graph_viterbi(const Problem &P, const TargetGraphArgs &
                                        int64_t *labels, int64_t *tokens, int64_t *token_frames, int64_t *token_lengths,
                                        hipStream_t stream);
 
+// ---- Token confidences of that best path and the posteriors of the final nodes (asg_target_graph_conf.hip): the beta pull
+// behind launch_target_graph_forward with alpha stored (`alpha`, `normalisers`) and launch_target_graph_viterbi (the tokens).
+constexpr int kTargetGraphConfMaxTol = 64;  // the ring of 256 accumulators, as kBeamConfMaxTol
+template <typename R>
+hipError_t launch_target_graph_conf(const Problem &P, const TargetGraphArgs &G, int tol, const void *alpha,
+                                    const void *normalisers, const int64_t *tokens, const int64_t *token_frames,
+                                    const int64_t *token_lengths, void *token_confidences, void *final_posteriors,
+                                    hipStream_t stream);
+
 // launches of the resident-slice forward kernel (256 < N <= 2048) of this process whose bounded waits ran out (asg_generic.hip)
 unsigned cluster_timeouts();
 

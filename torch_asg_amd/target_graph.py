@@ -1,5 +1,5 @@
 """Per-utterance target graphs: the transcript of an utterance as "one of these" (`torch_asg_amd.target_graph_score`,
-`target_graph_asg_loss`, `ASGLoss.target_graph_loss`, `target_graph_viterbi`).
+`target_graph_asg_loss`, `ASGLoss.target_graph_loss`, `target_graph_viterbi`, `target_graph_confidence`).
 
 A `TargetGraphs` is a batch of B small node-labelled graphs.  Node k of graph b carries a label in [0, N), a start weight and a
 final weight (-inf: not a start / not a final); a directed edge src -> dst carries a weight (finite or -inf).  The stay on a
@@ -72,7 +72,8 @@ class TargetGraphs:
             raise ValueError("TargetGraphs: B * (Kmax + Emax) must stay below 2^31")
         self._compiled = {}
         self.final_alternative = None   # from_alternatives: host [B,Kmax] int64, the index of the sequence that ends in a node, -1 elsewhere
-        self._final_alternative = {}
+        self.alternative_final = None   # from_alternatives: host [B,Amax] int64, its inverse: the node in which sequence a ends, -1 behind them
+        self._maps = {}    # (name, device) -> tensor
 
     @classmethod
     def from_targets(cls, targets, target_lengths, num_labels):
@@ -132,20 +133,30 @@ class TargetGraphs:
             labels.append(lab); start.append(sw); final.append(fw); edges.append(ed)
         self = cls(labels, start, final, edges, num_labels)
         self.final_alternative = np.full((self.B, self.Kmax), -1, np.int64)
+        self.alternative_final = np.full((self.B, max(len(at) for at in ends)), -1, np.int64)
         for b, at in enumerate(ends):
             self.final_alternative[b, at] = np.arange(len(at))
+            self.alternative_final[b, :len(at)] = at
         return self
 
     def final_alternative_on(self, device):
         """`final_alternative` as a tensor on `device` (cached), or None for graphs built from arrays."""
-        if self.final_alternative is None:
+        return self._map_on("final_alternative", device)
+
+    def alternative_final_on(self, device):
+        """`alternative_final` as a tensor on `device` (cached), or None for graphs built from arrays."""
+        return self._map_on("alternative_final", device)
+
+    def _map_on(self, name, device):
+        host = getattr(self, name)
+        if host is None:
             return None
         device = torch.device(device)
         if device.type == "cuda" and device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())
-        hit = self._final_alternative.get(device)
+        hit = self._maps.get((name, device))
         if hit is None:
-            hit = self._final_alternative[device] = torch.from_numpy(self.final_alternative).to(device)
+            hit = self._maps[(name, device)] = torch.from_numpy(host).to(device)
         return hit
 
     def compile_host(self, dt):
