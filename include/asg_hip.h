@@ -1333,6 +1333,40 @@ int asg_target_graph_confidence(asg_ctx *ctx, const asg_problem *p, const asg_ta
                                 int64_t *token_frames, int64_t *token_lengths, void *normalisers, void *token_confidences,
                                 void *final_posteriors, int flags, void *stream);
 
+/* ---- The N BEST paths of each utterance's target graph, ONE PER FINAL NODE, ranked: which alternative was spoken, which was
+ * the runner-up, and by how much.  No counterpart in the reference.  v, bp, f_e and len are asg_target_graph_viterbi's; in
+ * the dtype of the problem, adds and compares only, with nb = nbest:
+ *   end[k]      = v[len-1][k] + final_w[k]                                      for k < K_b
+ *   candidates  = the nodes with end[k] > -inf, ordered by (end descending, k ascending)
+ *   num_hyps[b] = min(nbest, number of candidates)                 (0 for len 0, an empty graph, no finite path)
+ *   row r < num_hyps[b]:
+ *     end_nodes[b][r] = candidate r;  scores[b][r] = end[candidate r]
+ *     nodes[b][r][len-1] = candidate r, nodes[b][r][t-1] = bp[t][nodes[b][r][t]], labels[b][r][t] = l_{nodes[b][r][t]}
+ *     tokens / token_frames / token_lengths: asg_target_graph_viterbi's rule applied to this row's nodes
+ *     emission_scores[b][r]: a = I[0][labels[0]], then for t = 1 .. len-1 in order a = (a + tr[labels[t]][labels[t-1]]) + I[t][labels[t]]
+ *   rows >= num_hyps[b]: scores and emission_scores -inf, every integer -1, token_lengths 0
+ *   frames >= len and tokens behind token_lengths: -1
+ * A row is "the best path that ends in this final node" (the contract of asg_beam_decode_graph_nbest: n best final states,
+ * each with the best path the search has for it).  In a prefix tree a node determines its label sequence, so the rows are
+ * distinct alternatives: the ranking of the given sequences by their best alignment.  In other graphs two rows can spell the
+ * same labels (a diamond's two branches that end in different final nodes).  Row 0 is asg_target_graph_viterbi's result bit
+ * for bit.  emission_scores is the acoustic part of a row's score; the graph part (start, edge and final weights) is
+ * scores - emission_scores up to the rounding of two sums -- no third array.
+ * num_hyps [B] int64; scores, emission_scores [B,nb] in the dtype of the problem; end_nodes, token_lengths [B,nb], tokens,
+ * token_frames [B,nb,T] int64, contiguous; nodes and labels [B,nb,T] int64 or BOTH null (not wanted).  One launch: forward,
+ * rank, one walk over the back-pointers shared by all rows, write; every output element is written by it (no memset), no
+ * float atomics, nothing synchronises: equal bits run to run, and a warm call can be captured.
+ *   work: asg_target_graph_nbest_work_bytes(p, tg, nbest) = (B * T * Kmax * 2 rounded up to 16)
+ *         + (B * min(nbest, Kmax) * T * 2 rounded up to 16) bytes (the back-pointers, then every row's nodes, 16 bits each)
+ * 1 <= nbest <= 1024 (smaller: ASG_ERR_INVALID; larger: ASG_ERR_UNSUPPORTED).  Otherwise limits and return codes are
+ * asg_target_graph_forward's (a batch that aligns also gives its n-best, for every accepted nbest); the size call returns 0
+ * beyond them. */
+size_t asg_target_graph_nbest_work_bytes(const asg_problem *p, const asg_target_graphs *tg, int nbest);
+int asg_target_graph_nbest(asg_ctx *ctx, const asg_problem *p, const asg_target_graphs *tg, int nbest, void *work,
+                           size_t work_bytes, int64_t *num_hyps, void *scores, int64_t *end_nodes, void *emission_scores,
+                           int64_t *tokens, int64_t *token_frames, int64_t *token_lengths, int64_t *nodes, int64_t *labels,
+                           int flags, void *stream);
+
 /* ---- BEAM-PRUNED full score of the same composed lattice, and its gradients: asg_graph_full_forward / _backward over the
  * lattice that asg_beam_decode_graph's search keeps -- a normaliser Z_K whose work per frame follows the beam and not Q or E, so a
  * criterion can be trained with the automata (4-grams, lexicon tries) the beam decoder was built for.  No counterpart in the

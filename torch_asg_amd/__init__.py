@@ -22,6 +22,7 @@ from .asg import BeamWordsFullScore, beam_words_full_score, beam_words_asg_loss 
 from .asg import TargetGraphScore, target_graph_score, target_graph_asg_loss  # noqa: F401
 from .asg import TargetGraphAlignment, target_graph_viterbi  # noqa: F401
 from .asg import TargetGraphConfidence, target_graph_confidence  # noqa: F401
+from .asg import TargetGraphNBest, target_graph_nbest  # noqa: F401
 from .graph import TokenGraph  # noqa: F401
 from .target_graph import TargetGraphs  # noqa: F401
 from .wordlm import Lexicon, WordLM, WordLookahead  # noqa: F401
@@ -62,4 +63,5 @@ __all__ = ["ASGLoss", "ASGLossFunction", "FAC", "FCC", "ASGGPUFast", "ASGGPUFast
            "BeamWords", "beam_decode_words", "BeamWordsConfidence", "beam_decode_words_confidence", "BeamGraphConfidence", "beam_decode_graph_confidence", "BeamNbestConfidence", "beam_decode_graph_nbest_confidence", "BeamWordStream", "BeamWordStreamResult", "BeamWordsNbest", "beam_decode_words_nbest", "BeamWordStreamNbest", "BeamWordsNbestConfidence", "beam_decode_words_nbest_confidence", "BeamWordWindowStream", "BeamWordWindowCommit", "BeamWordWindowResult", "BeamWordWindowNbest", "BeamWordsFullScore", "beam_words_full_score",
            "beam_words_asg_loss", "Lexicon", "WordLM", "WordLookahead", "shard_batch", "sharded_asg_loss", "allreduce_transition_grad", "reserve", "release", "check_faults", "graphed", "GraphedStep",
            "TargetGraphs", "TargetGraphScore", "target_graph_score", "target_graph_asg_loss",
-           "TargetGraphAlignment", "target_graph_viterbi", "TargetGraphConfidence", "target_graph_confidence"]
+           "TargetGraphAlignment", "target_graph_viterbi", "TargetGraphConfidence", "target_graph_confidence",
+           "TargetGraphNBest", "target_graph_nbest"]

@@ -923,6 +923,36 @@ class HipBackend:
                        "asg_target_graph_confidence")
         return both[0], out[0], out[1], out[2], out[3], token_lengths, both[1], conf, post
 
+    def target_graph_nbest(self, inputs, transition, graphs, input_lengths, nbest, return_alignments=False):
+        """The n best paths of each utterance's target graph, one per final node -> (num_hyps[B], scores[B,nb], end_nodes[B,nb],
+        emission_scores[B,nb], tokens[B,nb,T], token_frames[B,nb,T], token_lengths[B,nb], nodes, labels [B,nb,T] or None); see
+        include/asg_hip.h::asg_target_graph_nbest.  One launch for the whole batch."""
+        L = _lib.lib()
+        T, B, N = inputs.shape
+        dev = inputs.device
+        nb = max(-1, min(int(nbest), (1 << 31) - 1))
+        with self._guard(dev):
+            (tg,), _, keep = self._target_graph_args(inputs, transition, graphs, input_lengths)
+            p, _, input_lengths, _ = self._device_problem(inputs, transition, None, input_lengths, None)
+            stream = self._stream(dev)
+
+            def call(work, nbytes, *outs):
+                return L.asg_target_graph_nbest(None, ctypes.byref(p), ctypes.byref(tg), nb, work, nbytes, *outs, 0, stream)
+            if nb > 1024:                             # the library's refusal, before anything is sized by nbest
+                _lib.check(call(None, 0, *(None,) * 9), "asg_target_graph_nbest")
+            work = self._buf(int(L.asg_target_graph_nbest_work_bytes(ctypes.byref(p), ctypes.byref(tg), nb)), dev)
+            both = torch.empty(2, B, nb, dtype=inputs.dtype, device=dev)
+            out = torch.empty(4 if return_alignments else 2, B, nb, T, dtype=torch.int64, device=dev)
+            per = torch.empty(2, B, nb, dtype=torch.int64, device=dev)
+            num = torch.empty(B, dtype=torch.int64, device=dev)
+            nodes, labels = (out[2], out[3]) if return_alignments else (None, None)
+            # (as target_graph_viterbi: one stream, nothing created here, so a warm call may run under capture)
+            _lib.check(call(work.data_ptr(), work.numel(), num.data_ptr(), both[0].data_ptr(), per[0].data_ptr(),
+                            both[1].data_ptr(), out[0].data_ptr(), out[1].data_ptr(), per[1].data_ptr(),
+                            None if nodes is None else nodes.data_ptr(), None if labels is None else labels.data_ptr()),
+                       "asg_target_graph_nbest")
+        return num, both[0], per[0], both[1], out[0], out[1], per[1], nodes, labels
+
     def _beam_loss_args(self, inputs, transition, graph, input_lengths, targets, target_lengths, lm_weight, token_score):
         """Checks shared by the beam-pruned loss entry points -> ((the asg_token_graph_beam_loss view,), Q, the compiled graph it
         points into): `_lattice_forward`'s `prepare`."""
@@ -1965,6 +1995,47 @@ def target_graph_confidence(inputs, transition, graphs, input_lengths=None, fram
     return TargetGraphConfidence(*out[:6], alternatives, *out[6:], alt_post)
 
 
+TargetGraphNBest = collections.namedtuple("TargetGraphNBest", ["num_hyps", "scores", "end_nodes", "emission_scores", "tokens",
+                                                               "token_frames", "token_lengths", "alternatives", "nodes", "labels"])
+
+
+def target_graph_nbest(inputs, transition, graphs, input_lengths=None, nbest=10, return_alignments=False):
+    """The `nbest` best paths of utterance b's own target graph, ONE PER FINAL NODE, ranked: which alternative was spoken,
+    which was the runner-up, and by how much.  Row r is the best path (and its best alignment) that ends in the r-th best
+    final node, under (score descending, node ascending); row 0 is `target_graph_viterbi`'s result bit for bit.  No gradient.
+
+    For graphs from `from_alternatives` / `from_targets` (prefix trees) a node determines its label sequence, so the rows are
+    distinct alternatives: the ranking of the given sequences by their best alignment.  For other graphs two rows can spell
+    the same labels (two branches of a diamond that end in different final nodes): n best final nodes, each with the best
+    path the search has for it, as `beam_decode_graph_nbest`.
+
+    Inputs, strides, widening and errors as `target_graph_viterbi`.  Returns a `TargetGraphNBest`, nb = nbest:
+      num_hyps [B]                 the number of valid rows: min(nbest, final nodes that a finite path reaches); 0 for length
+                                   0, an empty graph, no finite path
+      scores [B,nb]                the score of each row, descending
+      end_nodes [B,nb]             the final node of each row
+      emission_scores [B,nb]       the acoustic part of the score, emissions and transitions summed in frame order; the graph
+                                   part (start, edge and final weights) is scores - emission_scores up to the rounding of
+                                   two sums
+      tokens, token_frames [B,nb,T]  each row's tokens and their first frames;  token_lengths [B,nb] their number
+      alternatives [B,nb]          the index of the sequence each row spells (None for graphs built from arrays)
+      nodes, labels [B,nb,T]       the node occupied at every frame and its label, only with return_alignments=True (else None)
+    Integers are int64.  Rows behind num_hyps hold -inf in both scores, -1 in every integer and token_lengths 0; frames behind
+    the utterance's length and tokens behind token_lengths hold -1.  nbest < 1 raises ValueError, > 1024 is refused by the
+    library (RuntimeError).  One launch; bit-identical run to run; a warm call can be captured."""
+    if int(nbest) < 1:
+        raise ValueError("torch_asg_amd.target_graph_nbest: nbest must be >= 1")
+    with torch.no_grad():
+        inputs, transition = _plain(inputs, transition)
+        num, scores, ends, emis, tokens, frames, token_lengths, nodes, labels = native().target_graph_nbest(
+            inputs, transition, graphs, input_lengths, nbest, return_alignments)
+        fa = graphs.final_alternative_on(inputs.device)
+        alternatives = None
+        if fa is not None:
+            alternatives = ends if fa.shape[1] == 0 else torch.where(ends >= 0, fa.gather(1, ends.clamp(min=0)), ends)
+    return TargetGraphNBest(num, scores, ends, emis, tokens, frames, token_lengths, alternatives, nodes, labels)
+
+
 class BeamGraphFullScore(torch.autograd.Function):
     """Beam-pruned full score of the ASG lattice composed with a token automaton, [B] (asg_beam_graph_full_forward /
     _backward).  The kept sets are constants of the gradient; alpha is stored only when a gradient w.r.t. inputs or transition
@@ -2410,6 +2481,11 @@ class ASGLoss(nn.Module):
         """That best path with its token confidences and the alternatives' posteriors under this module's transition matrix:
         `torch_asg_amd.target_graph_confidence`."""
         return target_graph_confidence(inputs, self.transition, graphs, input_lengths, frame_tolerance)
+
+    def target_graph_nbest(self, inputs, graphs, input_lengths=None, nbest=10, return_alignments=False):
+        """The n best paths of each utterance's target graph, one per final node, under this module's transitions: see
+        `torch_asg_amd.target_graph_nbest`."""
+        return target_graph_nbest(inputs, self.transition, graphs, input_lengths, nbest, return_alignments)
 
     def beam_graph_loss(self, inputs, targets, graph, input_lengths=None, target_lengths=None, lm_weight=1.0, token_score=0.0,
                         max_work_bytes=1 << 30, beam_size=256, beam_threshold=float("inf")):

@@ -2867,6 +2867,32 @@ int asg_target_graph_confidence(asg_ctx *ctx, const asg_problem *p, const asg_ta
                                          token_confidences, final_posteriors, s)));
 }
 
+size_t asg_target_graph_nbest_work_bytes(const asg_problem *p, const asg_target_graphs *tg, int nbest) {
+    if (check_target_graphs(p, tg, true) != ASG_OK || nbest < 1 || nbest > kTargetGraphMaxNBest) return 0;
+    return target_graph_nbest_work_bytes((int) p->T, (int) p->B, (int) tg->Kmax, nbest);
+}
+
+int asg_target_graph_nbest(asg_ctx *ctx, const asg_problem *p, const asg_target_graphs *tg, int nbest, void *work,
+                           size_t work_bytes, int64_t *num_hyps, void *scores, int64_t *end_nodes, void *emission_scores,
+                           int64_t *tokens, int64_t *token_frames, int64_t *token_lengths, int64_t *nodes, int64_t *labels,
+                           int flags, void *stream) {
+    (void) ctx; (void) flags;
+    int rc = check_target_graphs(p, tg, false);
+    if (rc) return rc;
+    if (nbest < 1) return ASG_ERR_INVALID;
+    if (nbest > kTargetGraphMaxNBest) return ASG_ERR_UNSUPPORTED;
+    const size_t need = asg_target_graph_nbest_work_bytes(p, tg, nbest);
+    if (!num_hyps || !scores || !end_nodes || !emission_scores || !tokens || !token_frames || !token_lengths ||
+        !nodes != !labels || (need && !work))
+        return ASG_ERR_INVALID;
+    if (work_bytes < need) return ASG_ERR_WORKSPACE;
+    const Problem P = to_problem(p);
+    const TargetGraphArgs G = to_target_graph_args(tg);
+    const TargetGraphNBestOut out = {num_hyps, scores, end_nodes, emission_scores, tokens, token_frames, token_lengths, nodes, labels};
+    return hip_status(ASG_DISPATCH(p, launch_target_graph_nbest<float>(P, G, nbest, work, out, (hipStream_t) stream),
+                                   launch_target_graph_nbest<double>(P, G, nbest, work, out, (hipStream_t) stream)));
+}
+
 int asg_backward(asg_ctx *ctx, const asg_problem *p, const void *state, size_t state_bytes,
                  const void *grad_full, const void *grad_aligned, void *scratch, size_t scratch_bytes,
                  void *grad_transition, void *grad_inputs, int flags, void *stream) {

@@ -774,6 +774,23 @@ hipError_t launch_target_graph_viterbi(const Problem &P, const TargetGraphArgs &
                                        int64_t *labels, int64_t *tokens, int64_t *token_frames, int64_t *token_lengths,
                                        hipStream_t stream);
 
+// ---- The n best paths of each utterance's target graph, one per final node (asg_target_graph_nbest.hip): one launch, the same
+// forward, then rank, a shared walk and a write phase.  Work = the back-pointers [B][T][Kmax], then the node columns
+// [B][min(nbest, Kmax)][T], 16 bits each, either part rounded up to 16 bytes.  num_hyps [B]; scores, emission_scores (dtype of
+// the problem), end_nodes, token_lengths [B][nbest]; tokens, token_frames and, unless both are null, nodes, labels [B][nbest][T].
+constexpr int kTargetGraphMaxNBest = 1024;
+struct TargetGraphNBestOut {
+    int64_t *num_hyps;
+    void *scores;
+    int64_t *end_nodes;
+    void *emission_scores;
+    int64_t *tokens, *token_frames, *token_lengths, *nodes, *labels;
+};
+size_t target_graph_nbest_work_bytes(int T, int B, int Kmax, int nbest);
+template <typename R>
+hipError_t launch_target_graph_nbest(const Problem &P, const TargetGraphArgs &G, int nbest, void *work,
+                                     const TargetGraphNBestOut &out, hipStream_t stream);
+
 // ---- Token confidences of that best path and the posteriors of the final nodes (asg_target_graph_conf.hip): the beta pull
 // behind launch_target_graph_forward with alpha stored (`alpha`, `normalisers`) and launch_target_graph_viterbi (the tokens).
 constexpr int kTargetGraphConfMaxTol = 64;  // the ring of 256 accumulators, as kBeamConfMaxTol
