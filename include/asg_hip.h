@@ -1308,6 +1308,38 @@ int asg_target_graph_viterbi(asg_ctx *ctx, const asg_problem *p, const asg_targe
                              void *scores, int64_t *nodes, int64_t *labels, int64_t *tokens, int64_t *token_frames,
                              int64_t *token_lengths, int flags, void *stream);
 
+/* ---- That BEST-PATH SCORE AS A TRAINING CRITERION (a Viterbi / hard numerator), and its gradients.  No counterpart in the
+ * reference.  scores [B] are asg_target_graph_viterbi's scores bit for bit; v, bp, f_e, len and the tie rules (stay wins ties,
+ * first lowest-source edge, lowest end node) are its own, in the dtype of the problem.  With nodes[0..n-1] that path (n = len
+ * where the score is finite, else 0), labels[t] = l_{nodes[t]} and g = grad_scores[b]:
+ *   grad_inputs[t][b][i]  = g if t < n and i == labels[t], else 0         (every element of [T,B,N] written, no memset)
+ *   count_b[slot]         = number of t in [1, n) whose step nodes[t-1] -> nodes[t] is that slot: slot k (the stay on node k)
+ *                           when nodes[t] == nodes[t-1] == k, else slot Kmax + e with e the FIRST edge in incoming-CSR order of
+ *                           nodes[t] whose source is nodes[t-1]
+ *   grad_transition[i][j] = sum over the batch-wide list (pkey / pseg / pslot, in list order: 64 lanes striding the pair's
+ *                           segment, then the fixed xor butterfly, exactly asg_target_graph_backward's order) of
+ *                           g_b * count_b[slot];  0 for pairs no graph uses
+ * Parallel edges with one source and one target share a label pair, so which of them is counted never changes
+ * grad_transition.  Utterances whose score is -inf (len 0, empty graph, no finite path) get zero gradient rows and add zeros
+ * to grad_transition.  The graphs' weights are constants.  The counts are integers added with integer atomics in LDS, the
+ * products g_b * count are summed in a fixed order: no float atomics, bit-identical run to run; every output element is written
+ * by a kernel (no memset), nothing synchronises: a warm call can be captured.  The backward needs the path that the forward left
+ * in `work` (ASG_FLAG_GRAPH_LOSS_KEEP_ALPHA: "keep the path") and the same problem; without the flag the forward stores no
+ * back-pointers and needs no workspace.
+ *   work:    asg_target_graph_viterbi_train_work_bytes(p, tg, store) = store ? r16(B * T * Kmax * 2) + r16(B * T * 4)
+ *            + r16(B * (Kmax + Emax) * 4) + r16(B * T * 2) : 0 bytes, r16 = rounded up to 16: the back-pointers (16 bits), the
+ *            path's labels (int32 [B][T], -1 from n on), the slot counts (int32 [B][Kmax + Emax]), the path's nodes (16 bits)
+ *   scratch: asg_target_graph_viterbi_train_scratch_bytes(p, tg) = 0 (the pointer may be anything)
+ * Limits and return codes are asg_target_graph_forward's (a batch that scores also trains hard); the work size call returns 0
+ * beyond them. */
+size_t asg_target_graph_viterbi_train_work_bytes(const asg_problem *p, const asg_target_graphs *tg, int store);
+size_t asg_target_graph_viterbi_train_scratch_bytes(const asg_problem *p, const asg_target_graphs *tg);
+int asg_target_graph_viterbi_forward(asg_ctx *ctx, const asg_problem *p, const asg_target_graphs *tg, void *work,
+                                     size_t work_bytes, void *scores, int flags, void *stream);
+int asg_target_graph_viterbi_backward(asg_ctx *ctx, const asg_problem *p, const asg_target_graphs *tg, const void *work,
+                                      size_t work_bytes, const void *scores, const void *grad_scores, void *grad_inputs,
+                                      void *grad_transition, void *scratch, size_t scratch_bytes, int flags, void *stream);
+
 /* ---- How sure that best path is: TOKEN CONFIDENCES of asg_target_graph_viterbi's path and the POSTERIORS OF THE FINAL NODES
  * under asg_target_graph_forward's sum.  No counterpart in the reference.  scores, nodes, labels, tokens, token_frames and
  * token_lengths are asg_target_graph_viterbi's bits and normalisers [B] asg_target_graph_forward's scores on the same

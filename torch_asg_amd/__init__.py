@@ -21,6 +21,7 @@ from .asg import BeamWordsNbestConfidence, beam_decode_words_nbest_confidence  #
 from .asg import BeamWordsFullScore, beam_words_full_score, beam_words_asg_loss  # noqa: F401
 from .asg import TargetGraphScore, target_graph_score, target_graph_asg_loss  # noqa: F401
 from .asg import TargetGraphAlignment, target_graph_viterbi  # noqa: F401
+from .asg import TargetGraphViterbiScore, target_graph_viterbi_score, target_graph_viterbi_loss  # noqa: F401
 from .asg import TargetGraphConfidence, target_graph_confidence  # noqa: F401
 from .asg import TargetGraphNBest, target_graph_nbest  # noqa: F401
 from .graph import TokenGraph  # noqa: F401
@@ -64,4 +65,5 @@ __all__ = ["ASGLoss", "ASGLossFunction", "FAC", "FCC", "ASGGPUFast", "ASGGPUFast
            "beam_words_asg_loss", "Lexicon", "WordLM", "WordLookahead", "shard_batch", "sharded_asg_loss", "allreduce_transition_grad", "reserve", "release", "check_faults", "graphed", "GraphedStep",
            "TargetGraphs", "TargetGraphScore", "target_graph_score", "target_graph_asg_loss",
            "TargetGraphAlignment", "target_graph_viterbi", "TargetGraphConfidence", "target_graph_confidence",
-           "TargetGraphNBest", "target_graph_nbest"]
+           "TargetGraphNBest", "target_graph_nbest",
+           "TargetGraphViterbiScore", "target_graph_viterbi_score", "target_graph_viterbi_loss"]

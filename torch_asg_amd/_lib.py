@@ -62,6 +62,8 @@ SYMBOLS = ["asg_hip_version", "asg_hip_strerror", "asg_ctx_create", "asg_ctx_des
            "asg_target_graph_max_edges", "asg_target_graph_work_bytes", "asg_target_graph_scratch_bytes",
            "asg_target_graph_forward", "asg_target_graph_backward",
            "asg_target_graph_viterbi_work_bytes", "asg_target_graph_viterbi",
+           "asg_target_graph_viterbi_train_work_bytes", "asg_target_graph_viterbi_train_scratch_bytes",
+           "asg_target_graph_viterbi_forward", "asg_target_graph_viterbi_backward",
            "asg_target_graph_confidence_work_bytes", "asg_target_graph_confidence",
            "asg_target_graph_nbest_work_bytes", "asg_target_graph_nbest"]
 ABI_VERSION = 230        # include/asg_hip.h: ASG_HIP_VERSION this package was written against
@@ -327,6 +329,12 @@ def lib():
     L.asg_target_graph_viterbi_work_bytes.restype = sz
     L.asg_target_graph_viterbi_work_bytes.argtypes = [pp, tp]
     L.asg_target_graph_viterbi.argtypes = [vp, pp, tp, vp, sz, vp, vp, vp, vp, vp, vp, ci, vp]
+    L.asg_target_graph_viterbi_train_work_bytes.restype = sz
+    L.asg_target_graph_viterbi_train_work_bytes.argtypes = [pp, tp, ci]
+    L.asg_target_graph_viterbi_train_scratch_bytes.restype = sz
+    L.asg_target_graph_viterbi_train_scratch_bytes.argtypes = [pp, tp]
+    L.asg_target_graph_viterbi_forward.argtypes = [vp, pp, tp, vp, sz, vp, ci, vp]
+    L.asg_target_graph_viterbi_backward.argtypes = [vp, pp, tp, vp, sz, vp, vp, vp, vp, vp, sz, ci, vp]
     L.asg_target_graph_confidence_work_bytes.restype = sz
     L.asg_target_graph_confidence_work_bytes.argtypes = [pp, tp]
     L.asg_target_graph_confidence.argtypes = [vp, pp, tp, ci, vp, sz] + [vp] * 9 + [ci, vp]

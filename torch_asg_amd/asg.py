@@ -879,6 +879,21 @@ class HipBackend:
                                       lambda: self._target_graph_args(inputs, transition, graphs, input_lengths), (), saved,
                                       scores, grad_scores, inputs, transition, None, input_lengths, None)
 
+    def target_graph_viterbi_forward(self, inputs, transition, graphs, input_lengths, store=False):
+        """Best-path score of each utterance's target graph -> (scores[B], saved); see
+        include/asg_hip.h::asg_target_graph_viterbi_forward.  One launch for the whole batch.  With `store`, saved = [(0, B,
+        work)], the path for target_graph_viterbi_backward; without, no back-pointers are kept and no workspace is needed."""
+        return self._lattice_forward("asg_target_graph_viterbi_forward", "asg_target_graph_viterbi_train_work_bytes",
+                                     lambda: self._target_graph_args(inputs, transition, graphs, input_lengths), (), (), inputs,
+                                     transition, None, input_lengths, None, store, float("inf"))
+
+    def target_graph_viterbi_backward(self, saved, scores, grad_scores, inputs, transition, graphs, input_lengths):
+        """(grad_transition[N,N], grad_inputs[T,B,N]) of sum_b grad_scores[b] * scores[b] from the path that
+        target_graph_viterbi_forward kept."""
+        return self._lattice_backward("asg_target_graph_viterbi_backward", "asg_target_graph_viterbi_train_scratch_bytes",
+                                      lambda: self._target_graph_args(inputs, transition, graphs, input_lengths), (), saved,
+                                      scores, grad_scores, inputs, transition, None, input_lengths, None)
+
     def target_graph_viterbi(self, inputs, transition, graphs, input_lengths):
         """Best path of each utterance's target graph -> (scores[B], nodes[B,T], labels[B,T], tokens[B,T], token_frames[B,T],
         token_lengths[B]); see include/asg_hip.h::asg_target_graph_viterbi.  One launch for the whole batch."""
@@ -1887,14 +1902,44 @@ def target_graph_score(inputs, transition, graphs, input_lengths=None):
     return TargetGraphScore.apply(_widen(inputs, transition), transition, graphs, input_lengths)
 
 
-def _target_graph_loss(inputs, graphs, transition, input_lengths, reduction, weights=None):
-    """[B] losses FCC - target_graph_score with `_graph_loss`'s masking, then `weights(inputs, input_lengths, None)` and the
-    reduction."""
+class TargetGraphViterbiScore(torch.autograd.Function):
+    """Best-path score of each utterance's own target graph, [B] (asg_target_graph_viterbi_forward / _backward).  The path
+    is kept only when a gradient w.r.t. inputs or transition is needed."""
+
+    @staticmethod
+    def forward(ctx, inputs, transition, graphs, input_lengths):
+        store = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
+        scores, saved = native().target_graph_viterbi_forward(inputs, transition, graphs, input_lengths, store)
+        ctx.save_for_backward(inputs, transition, input_lengths, scores)
+        ctx.saved, ctx.graphs = saved, graphs
+        return scores
+
+    @staticmethod
+    def backward(ctx, grad):
+        inputs, transition, input_lengths, scores = ctx.saved_tensors
+        gtr, gin = native().target_graph_viterbi_backward(ctx.saved, scores, grad, inputs, transition, ctx.graphs, input_lengths)
+        return gin, gtr, None, None
+
+
+def target_graph_viterbi_score(inputs, transition, graphs, input_lengths=None):
+    """The max where `target_graph_score` takes the log-sum: the score of the best alignment of the best label path of
+    utterance b's own target graph, bit for bit `target_graph_viterbi(...).scores`, and differentiable w.r.t. `inputs` and
+    `transition` (the graphs' weights are constants).  Its gradient is a one-hot over that very path: grad_inputs[t, b] holds
+    grad[b] at the path's label of frame t, grad_transition[i, j] grad[b] times the steps from label j to label i.  Returns
+    [B] in the dtype of the emissions; -inf, with zero gradients, for an utterance of length 0, an empty graph or a graph
+    without any alignment.  Inputs, strides, widening of float16 / bfloat16 and errors as `target_graph_score`; one launch
+    serves the batch, and no float atomics: equal bits run to run."""
+    return TargetGraphViterbiScore.apply(_widen(inputs, transition), transition, graphs, input_lengths)
+
+
+def _target_graph_loss(inputs, graphs, transition, input_lengths, reduction, weights=None, score=TargetGraphScore):
+    """[B] losses FCC - `score` (the sum over all paths of the target graph, or its best path) with `_graph_loss`'s masking,
+    then `weights(inputs, input_lengths, None)` and the reduction."""
     inputs = _widen(inputs, transition)
     if input_lengths is None:
         input_lengths = torch.full((inputs.shape[1],), inputs.shape[0], dtype=torch.int64, device=inputs.device)
     full = FCC.apply(transition, inputs, None, input_lengths, None)
-    aligned = TargetGraphScore.apply(inputs, transition, graphs, input_lengths)
+    aligned = score.apply(inputs, transition, graphs, input_lengths)
     fd, ad = full.detach(), aligned.detach()
     ok_f, ok_a = torch.isfinite(fd), torch.isfinite(ad)
     zero = torch.zeros_like(fd)
@@ -1913,6 +1958,14 @@ def target_graph_asg_loss(inputs, graphs, transition, input_lengths=None, reduct
     utterance); those utterances' gradient rows hold only the full-lattice posterior.  reduction 'none' (default), 'sum' or
     'mean'."""
     return _target_graph_loss(inputs, graphs, transition, input_lengths, reduction)
+
+
+def target_graph_viterbi_loss(inputs, graphs, transition, input_lengths=None, reduction='none'):
+    """ASG loss whose numerator is `target_graph_viterbi_score` (Viterbi / hard training): loss[b] = S_full[b] - the score of
+    the best path of the utterance's graph, the path `target_graph_viterbi` reports.  +inf, never NaN, where the graph has no
+    alignment (length 0, an empty graph, every path longer than the utterance); those utterances' gradient rows hold only the
+    full-lattice posterior.  reduction 'none' (default), 'sum' or 'mean'."""
+    return _target_graph_loss(inputs, graphs, transition, input_lengths, reduction, score=TargetGraphViterbiScore)
 
 
 TargetGraphAlignment = collections.namedtuple("TargetGraphAlignment", ["scores", "nodes", "labels", "tokens", "token_frames",
@@ -2471,6 +2524,15 @@ class ASGLoss(nn.Module):
             raise ValueError("ASGLoss.target_graph_loss: scale_mode %r needs one target length per utterance; a target graph "
                              "has none (use 'none' or 'input_size*')" % self.scale_mode)
         return _target_graph_loss(inputs, graphs, self.transition, input_lengths, self.reduction, self._utterance_weights)
+
+    def target_graph_viterbi_loss(self, inputs, graphs, input_lengths=None):
+        """`torch_asg_amd.target_graph_viterbi_loss` under this module's transition matrix, reduction and scale_mode.  A graph
+        has no single length: the `target_size*` scale modes raise ValueError, as in `target_graph_loss`."""
+        if self.scale_mode.startswith('target'):
+            raise ValueError("ASGLoss.target_graph_viterbi_loss: scale_mode %r needs one target length per utterance; a target "
+                             "graph has none (use 'none' or 'input_size*')" % self.scale_mode)
+        return _target_graph_loss(inputs, graphs, self.transition, input_lengths, self.reduction, self._utterance_weights,
+                                  TargetGraphViterbiScore)
 
     def target_graph_viterbi(self, inputs, graphs, input_lengths=None):
         """Best path of each utterance's target graph under this module's transition matrix: see

@@ -2824,6 +2824,47 @@ int asg_target_graph_viterbi(asg_ctx *ctx, const asg_problem *p, const asg_targe
                                             (hipStream_t) stream)));
 }
 
+size_t asg_target_graph_viterbi_train_work_bytes(const asg_problem *p, const asg_target_graphs *tg, int store) {
+    if (check_target_graphs(p, tg, true) != ASG_OK) return 0;
+    return target_graph_hard_work_bytes((int) p->T, (int) p->B, (int) tg->Kmax, tg->Emax, store != 0);
+}
+
+size_t asg_target_graph_viterbi_train_scratch_bytes(const asg_problem *p, const asg_target_graphs *tg) {
+    (void) p; (void) tg;
+    return 0;
+}
+
+int asg_target_graph_viterbi_forward(asg_ctx *ctx, const asg_problem *p, const asg_target_graphs *tg, void *work,
+                                     size_t work_bytes, void *scores, int flags, void *stream) {
+    (void) ctx;
+    int rc = check_target_graphs(p, tg, false);
+    if (rc) return rc;
+    const bool store = (flags & ASG_FLAG_GRAPH_LOSS_KEEP_ALPHA) != 0;
+    const size_t need = asg_target_graph_viterbi_train_work_bytes(p, tg, store);
+    if (!scores || (need && !work)) return ASG_ERR_INVALID;
+    if (work_bytes < need) return ASG_ERR_WORKSPACE;
+    const Problem P = to_problem(p);
+    const TargetGraphArgs G = to_target_graph_args(tg);
+    return hip_status(ASG_DISPATCH(p, launch_target_graph_hard_forward<float>(P, G, store, work, scores, (hipStream_t) stream),
+                                   launch_target_graph_hard_forward<double>(P, G, store, work, scores, (hipStream_t) stream)));
+}
+
+int asg_target_graph_viterbi_backward(asg_ctx *ctx, const asg_problem *p, const asg_target_graphs *tg, const void *work,
+                                      size_t work_bytes, const void *scores, const void *grad_scores, void *grad_inputs,
+                                      void *grad_transition, void *scratch, size_t scratch_bytes, int flags, void *stream) {
+    (void) ctx; (void) flags; (void) scratch; (void) scratch_bytes;
+    int rc = check_target_graphs(p, tg, false);
+    if (rc) return rc;
+    const size_t wneed = asg_target_graph_viterbi_train_work_bytes(p, tg, 1);
+    if (!scores || !grad_scores || !grad_inputs || !grad_transition || (wneed && !work)) return ASG_ERR_INVALID;
+    if (work_bytes < wneed) return ASG_ERR_WORKSPACE;
+    const Problem P = to_problem(p);
+    const TargetGraphArgs G = to_target_graph_args(tg);
+    return hip_status(ASG_DISPATCH(p,
+        launch_target_graph_hard_backward<float>(P, G, work, grad_scores, grad_inputs, grad_transition, (hipStream_t) stream),
+        launch_target_graph_hard_backward<double>(P, G, work, grad_scores, grad_inputs, grad_transition, (hipStream_t) stream)));
+}
+
 // work of the confidences: [alpha B*T*Kmax elements, rounded up to 16 bytes][back-pointers B*T*Kmax x 16 bits]
 static size_t target_graph_conf_alpha_bytes(const asg_problem *p, const asg_target_graphs *tg) {
     const size_t a = target_graph_work_bytes(p->dtype == ASG_DTYPE_F64 ? 8 : 4, (int) p->T, (int) p->B, (int) tg->Kmax, true);

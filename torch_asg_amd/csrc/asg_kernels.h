@@ -774,6 +774,19 @@ hipError_t launch_target_graph_viterbi(const Problem &P, const TargetGraphArgs &
                                        int64_t *labels, int64_t *tokens, int64_t *token_frames, int64_t *token_lengths,
                                        hipStream_t stream);
 
+// ---- That best path's score as a training criterion (asg_target_graph_hard.hip): the forward is the same max-plus pass and,
+// when stored, leaves the path in `work`: back-pointers [B][T][Kmax] x 16 bits, labels int32 [B][T] (-1 behind the path), slot
+// counts int32 [B][Kmax + Emax], nodes [B][T] x 16 bits, each part rounded up to 16 bytes (nothing when not stored).  The
+// backward writes the one-hot grad_inputs and sums the counts per label pair in launch_target_graph_backward's order.
+size_t target_graph_hard_work_bytes(int T, int B, int Kmax, int64_t Emax, bool store);
+template <typename R>
+hipError_t launch_target_graph_hard_forward(const Problem &P, const TargetGraphArgs &G, bool store, void *work, void *scores,
+                                            hipStream_t stream);
+template <typename R>
+hipError_t launch_target_graph_hard_backward(const Problem &P, const TargetGraphArgs &G, const void *work,
+                                             const void *grad_scores, void *grad_inputs, void *grad_transition,
+                                             hipStream_t stream);
+
 // ---- The n best paths of each utterance's target graph, one per final node (asg_target_graph_nbest.hip): one launch, the same
 // forward, then rank, a shared walk and a write phase.  Work = the back-pointers [B][T][Kmax], then the node columns
 // [B][min(nbest, Kmax)][T], 16 bits each, either part rounded up to 16 bytes.  num_hyps [B]; scores, emission_scores (dtype of

@@ -1,6 +1,7 @@
-// torch_asg_amd/csrc/asg_target_graph_path.h -- what the two path kernels over per-utterance target graphs share
-// (asg_target_graph_viterbi.hip: the best path; asg_target_graph_nbest.hip: the best path into every final node, ranked): the
-// max-plus forward with its back-pointer rows, written ONCE, and the staging of those rows into LDS for the walk back.
+// torch_asg_amd/csrc/asg_target_graph_path.h -- what the three path kernels over per-utterance target graphs share
+// (asg_target_graph_viterbi.hip: the best path; asg_target_graph_nbest.hip: the best path into every final node, ranked;
+// asg_target_graph_hard.hip: the best path's score as a training criterion): the max-plus forward with its back-pointer rows,
+// written ONCE, and the staging of those rows into LDS for the walk back.
 #pragma once
 #include "asg_target_graph_common.h"
 
@@ -16,6 +17,13 @@ template <int W> struct Tgv {
 };
 inline int tgv_frames(int Kmax) { return Kmax <= 256 ? 64 : 16; }
 inline size_t tgv_granules(int Kmax) { return ((size_t) tgv_frames(Kmax) * Kmax + 14) / 8; }
+// LDS of a workgroup that runs the forward and then walks one path: [reduction slots 256 B] then the larger of the forward's
+// [v 2*Kmax R][f Emax R][src Emax int] and the backtrace's [stage 2 x granules x 16 B][line 2 x F int]
+inline size_t tgv_lds(int elem, int Kmax, int64_t Emax) {
+    const size_t back = kTgRed + 2 * tgv_granules(Kmax) * 16 + 2 * (size_t) tgv_frames(Kmax) * 4;
+    const size_t fwd = tg_fwd_lds(elem, Kmax, Emax);
+    return fwd > back ? fwd : back;
+}
 
 // n elements from `rows` into registers: granule g of the enclosing 16-byte-aligned range belongs to thread g mod W.
 template <int W>
@@ -51,7 +59,8 @@ __device__ __forceinline__ void tgv_put(const uint16_t *rows, int n, const uint4
 // vectors, the next emission is loaded before the barrier.  ONE pass over the incoming edges carries (best value, best
 // source) in registers, and the winning source goes to bpb[t][k] as 16 bits, a frame's row one coalesced store.  Returns
 // end[k] = v[len-1][k] + final_w[k] (-inf for k >= K); every thread is behind the last frame's barrier, so the LDS is free.
-template <typename R>
+// BP = false (a score that nobody walks back: asg_target_graph_hard.hip without a gradient) drops the stores; bpb is not read.
+template <typename R, bool BP = true>
 __device__ __forceinline__ R tgv_forward(const Problem &P, const TargetGraphArgs &G, const TgView &g, int b, int len,
                                          unsigned char *lds, uint16_t *bpb) {
     const int k = threadIdx.x, Kmax = G.Kmax;
@@ -79,7 +88,7 @@ __device__ __forceinline__ R tgv_forward(const Problem &P, const TargetGraphArgs
         x = ((const R *) G.start_w)[(int64_t) b * Kmax + k] + in[0];
         if (len > 1) em = in[P.is0];
         av[k] = x;
-        bpb[k] = (uint16_t) k;                        // (row 0 is never followed; written so that a staged block holds no stale bytes)
+        if (BP) bpb[k] = (uint16_t) k;                // (row 0 is never followed; written so that a staged block holds no stale bytes)
     }
     __syncthreads();
     for (int t = 1; t < len; ++t) {
@@ -96,7 +105,7 @@ __device__ __forceinline__ R tgv_forward(const Problem &P, const TargetGraphArgs
             }
             x = best + emt;
             av[(size_t) (t & 1) * Kmax + k] = x;
-            bpb[(int64_t) t * Kmax + k] = (uint16_t) from;
+            if (BP) bpb[(int64_t) t * Kmax + k] = (uint16_t) from;
         }
         __syncthreads();
     }

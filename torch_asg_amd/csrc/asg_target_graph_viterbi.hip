@@ -37,14 +37,7 @@ namespace asg {
 
 namespace {
 
-// [reduction slots 256 B] then the larger of the forward's [v 2*Kmax R][f Emax R][src Emax int] and the backtrace's
-// [stage 2 x granules x 16 B][line 2 x F int]
-inline size_t tgv_lds(int elem, int Kmax, int64_t Emax) {
-    const size_t back = kTgRed + 2 * tgv_granules(Kmax) * 16 + 2 * (size_t) tgv_frames(Kmax) * 4;
-    const size_t fwd = tg_fwd_lds(elem, Kmax, Emax);
-    return fwd > back ? fwd : back;
-}
-
+// (the LDS of the workgroup: tgv_lds, asg_target_graph_path.h)
 template <typename R, int W>
 __global__ void __launch_bounds__(W) target_graph_viterbi(Problem P, TargetGraphArgs G, uint16_t *bp, R *scores, int64_t *nodes,
                                                           int64_t *labels, int64_t *tokens, int64_t *frames, int64_t *tlen) {

@@ -12,7 +12,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["asg_small_f32.hip", "asg_small_f64.hip", "asg_bwd_f32.hip", "asg_bwd_f64.hip", "asg_fused.hip", "asg_generic.hip", "asg_generic_step.hip", "asg_generic_aligned.hip", "asg_generic_grad.hip",
-           "asg_viterbi.hip", "asg_decode.hip", "asg_decode_graph.hip", "asg_beam_graph.hip", "asg_beam_nbest.hip", "asg_beam_stream.hip", "asg_beam_stream_conf.hip", "asg_beam_window.hip", "asg_beam_conf_window.hip", "asg_beam_word.hip", "asg_beam_word_stream.hip", "asg_beam_word_stream_conf.hip", "asg_beam_word_nbest.hip", "asg_beam_word_window.hip", "asg_beam_word_conf_window.hip", "asg_beam_loss.hip", "asg_beam_conf.hip", "asg_beam_nbest_conf.hip", "asg_beam_word_loss.hip", "asg_beam_word_conf.hip", "asg_beam_word_nbest_conf.hip", "asg_graph_loss.hip", "asg_target_graph.hip", "asg_target_graph_viterbi.hip", "asg_target_graph_conf.hip", "asg_target_graph_nbest.hip",
+           "asg_viterbi.hip", "asg_decode.hip", "asg_decode_graph.hip", "asg_beam_graph.hip", "asg_beam_nbest.hip", "asg_beam_stream.hip", "asg_beam_stream_conf.hip", "asg_beam_window.hip", "asg_beam_conf_window.hip", "asg_beam_word.hip", "asg_beam_word_stream.hip", "asg_beam_word_stream_conf.hip", "asg_beam_word_nbest.hip", "asg_beam_word_window.hip", "asg_beam_word_conf_window.hip", "asg_beam_loss.hip", "asg_beam_conf.hip", "asg_beam_nbest_conf.hip", "asg_beam_word_loss.hip", "asg_beam_word_conf.hip", "asg_beam_word_nbest_conf.hip", "asg_graph_loss.hip", "asg_target_graph.hip", "asg_target_graph_viterbi.hip", "asg_target_graph_hard.hip", "asg_target_graph_conf.hip", "asg_target_graph_nbest.hip",
            "asg_api.hip"]
 HEADERS = ["asg_common.h", "asg_kernels.h", "asg_beam_common.h", "asg_beam_frame.h", "asg_beam_word_frame.h", "asg_beam_word_search.h", "asg_beam_window_common.h", "asg_beam_window_lat.h", "asg_beam_stream_lat.h", "asg_beam_lattice.h", "asg_beam_alpha.inc", "asg_beam_token_lat.h", "asg_beam_conf_sink.h", "asg_beam_conf_pull.h", "asg_beam_row_sink.h", "asg_beam_cells.inc", "asg_beam_word_lat.h", "asg_beam_word_alpha.inc", "asg_beam_word_conf_pull.h", "asg_generic_common.h", "asg_target_graph_common.h", "asg_target_graph_path.h", "asg_chains.h", "asg_outer.h", "asg_assemble.h", "asg_small_impl.inc", "asg_bwd_impl.inc",
            os.path.join("..", "..", "include", "asg_hip.h")]
@@ -23,10 +23,10 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # clang reports as "reserved register" once per statement)
 CFLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function", "-Wno-inline-asm",
           "-ffp-contract=off"]
-# per-unit flags: the two path units of the target graphs (one forward, asg_target_graph_path.h) are compiled without packed
+# per-unit flags: the three path units of the target graphs (one forward, asg_target_graph_path.h) are compiled without packed
 # fp32 arithmetic
 _NO_PK = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-EXTRA = {"asg_target_graph_viterbi.hip": _NO_PK, "asg_target_graph_nbest.hip": _NO_PK}
+EXTRA = {"asg_target_graph_viterbi.hip": _NO_PK, "asg_target_graph_hard.hip": _NO_PK, "asg_target_graph_nbest.hip": _NO_PK}
 
 
 def _mtime(p):
