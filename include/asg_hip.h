@@ -1285,6 +1285,41 @@ int asg_target_graph_backward(asg_ctx *ctx, const asg_problem *p, const asg_targ
                               size_t work_bytes, const void *scores, const void *grad_scores, void *grad_inputs,
                               void *grad_transition, void *scratch, size_t scratch_bytes, int flags, void *stream);
 
+/* ---- The score of EVERY FINAL NODE of each utterance's target graph, each summed over all alignments, and the gradients of
+ * any signed combination of them: what a sequence-discriminative criterion over an n-best list takes (minimum word error rate,
+ * minimum Bayes risk, pairwise ranking), where asg_target_graph_forward collapses the finals into one log-sum.  No counterpart
+ * in the reference.  alpha, f_e and len are asg_target_graph_forward's, bit for bit (the same frame loop), and so is the alpha
+ * stored in `work`:
+ *   final_scores[b][k] = alpha[len-1][k] + final_w[k]       [B,Kmax], every element written; -inf, never NaN, where k >= K_b,
+ *                                                           final_w[k] is -inf, len == 0 or no path reaches k
+ * lse_k of row b is asg_target_graph_forward's score.  Backward, g = grad_final_scores [B,Kmax]; entries of g where
+ * final_scores is -inf are ignored whatever they hold, NaN included.  Reverse mode through the alpha recursion in the linear
+ * domain (signed weights do not fit a log-semiring beta pass):
+ *   d[len-1][k] = g[b][k] where final_scores[b][k] > -inf, else 0
+ *   q[t][k]     = I[t][l_k] - alpha[t][k]                   (-inf where alpha[t][k] is -inf: every weight into k is then 0)
+ *   w_stay      = exp((alpha[t-1][j] + q[t][j]) + tr[l_j][l_j])
+ *   w_e         = exp((alpha[t-1][j] + q[t][k]) + f_e)       (edge e: j -> k; the adds in this order)
+ *   d[t-1][j]   = d[t][j] * w_stay + sum over the edges out of j, ascending by target, of d[t][k] * w_e,  t = len-1 .. 1
+ *   acc_stay[j] = sum_t d[t][j] * w_stay,  acc_e = sum_t d[t][k] * w_e    (in that order of t)
+ *   grad_inputs[t][b][i]  = sum of d[t][k] over the nodes of label i, ascending      (zero rows at t >= len)
+ *   grad_transition[i][j] = the sum of acc over every stay and edge of label pair (i, j) in the order of the batch-wide list
+ *                           pslot (64 lanes striding the pair's segment, then the fixed xor butterfly: asg_target_graph_backward's
+ *                           order, without its factor grad_scores[b]: g is inside d)
+ * The weights into a node sum to 1 up to the rounding of the stored alpha, so for every t < len row t of grad_inputs sums to
+ * the sum of g over the finite finals of b.  The graphs' weights are constants.  No float atomics and fixed orders:
+ * bit-identical run to run; every output element is written by a kernel (no memset), nothing synchronises: a warm call can be
+ * captured.  The backward needs the alpha that the forward stored (ASG_FLAG_GRAPH_LOSS_KEEP_ALPHA), its final_scores and the
+ * same problem.  work and scratch are asg_target_graph_forward's / _backward's: asg_target_graph_work_bytes(p, tg, store) and
+ * asg_target_graph_scratch_bytes(p, tg).  Limits and return codes are theirs too (the backward keeps 256 + Kmax * (4 * e + 4) +
+ * Emax * (2 * e + 4) bytes in LDS, under asg_target_graph_backward's layout: a batch that scores also gets these); with
+ * Kmax == 0 the [B,0] pointers may be null. */
+int asg_target_graph_final_forward(asg_ctx *ctx, const asg_problem *p, const asg_target_graphs *tg, void *work,
+                                   size_t work_bytes, void *final_scores, int flags, void *stream);
+int asg_target_graph_final_backward(asg_ctx *ctx, const asg_problem *p, const asg_target_graphs *tg, const void *work,
+                                    size_t work_bytes, const void *final_scores, const void *grad_final_scores,
+                                    void *grad_inputs, void *grad_transition, void *scratch, size_t scratch_bytes, int flags,
+                                    void *stream);
+
 /* ---- BEST PATH of each utterance's target graph: which alternative was spoken, where its tokens lie in time, the hard targets
  * of a next stage.  No counterpart in the reference.  The max-plus recursion over the arrays of asg_target_graphs, in the dtype
  * of the problem, adds and compares only (len = clamp(input_lengths[b], 0, T)):

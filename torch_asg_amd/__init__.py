@@ -24,6 +24,7 @@ from .asg import TargetGraphAlignment, target_graph_viterbi  # noqa: F401
 from .asg import TargetGraphViterbiScore, target_graph_viterbi_score, target_graph_viterbi_loss  # noqa: F401
 from .asg import TargetGraphConfidence, target_graph_confidence  # noqa: F401
 from .asg import TargetGraphNBest, target_graph_nbest  # noqa: F401
+from .asg import TargetGraphFinalScores, target_graph_final_scores, target_graph_alternative_scores, target_graph_risk  # noqa: F401
 from .graph import TokenGraph  # noqa: F401
 from .target_graph import TargetGraphs  # noqa: F401
 from .wordlm import Lexicon, WordLM, WordLookahead  # noqa: F401
@@ -66,4 +67,5 @@ __all__ = ["ASGLoss", "ASGLossFunction", "FAC", "FCC", "ASGGPUFast", "ASGGPUFast
            "TargetGraphs", "TargetGraphScore", "target_graph_score", "target_graph_asg_loss",
            "TargetGraphAlignment", "target_graph_viterbi", "TargetGraphConfidence", "target_graph_confidence",
            "TargetGraphNBest", "target_graph_nbest",
-           "TargetGraphViterbiScore", "target_graph_viterbi_score", "target_graph_viterbi_loss"]
+           "TargetGraphViterbiScore", "target_graph_viterbi_score", "target_graph_viterbi_loss",
+           "TargetGraphFinalScores", "target_graph_final_scores", "target_graph_alternative_scores", "target_graph_risk"]

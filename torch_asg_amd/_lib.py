@@ -61,6 +61,7 @@ SYMBOLS = ["asg_hip_version", "asg_hip_strerror", "asg_ctx_create", "asg_ctx_des
            "asg_beam_word_conf_window_confidence", "asg_beam_word_conf_window_confidence_la",
            "asg_target_graph_max_edges", "asg_target_graph_work_bytes", "asg_target_graph_scratch_bytes",
            "asg_target_graph_forward", "asg_target_graph_backward",
+           "asg_target_graph_final_forward", "asg_target_graph_final_backward",
            "asg_target_graph_viterbi_work_bytes", "asg_target_graph_viterbi",
            "asg_target_graph_viterbi_train_work_bytes", "asg_target_graph_viterbi_train_scratch_bytes",
            "asg_target_graph_viterbi_forward", "asg_target_graph_viterbi_backward",
@@ -326,6 +327,8 @@ def lib():
     L.asg_target_graph_scratch_bytes.argtypes = [pp, tp]
     L.asg_target_graph_forward.argtypes = [vp, pp, tp, vp, sz, vp, ci, vp]
     L.asg_target_graph_backward.argtypes = [vp, pp, tp, vp, sz, vp, vp, vp, vp, vp, sz, ci, vp]
+    L.asg_target_graph_final_forward.argtypes = [vp, pp, tp, vp, sz, vp, ci, vp]
+    L.asg_target_graph_final_backward.argtypes = [vp, pp, tp, vp, sz, vp, vp, vp, vp, vp, sz, ci, vp]
     L.asg_target_graph_viterbi_work_bytes.restype = sz
     L.asg_target_graph_viterbi_work_bytes.argtypes = [pp, tp]
     L.asg_target_graph_viterbi.argtypes = [vp, pp, tp, vp, sz, vp, vp, vp, vp, vp, vp, ci, vp]

@@ -735,8 +735,9 @@ class HipBackend:
                          align[0] if return_alignments else None, align[1] if return_alignments else None)
 
     def _lattice_forward(self, entry, sizer, prepare, size_args, call_args, inputs, transition, targets, input_lengths,
-                         target_lengths, store, max_work_bytes, flags=0):
-        """The forward of the graph loss and of the two beam-pruned losses -> (scores[B], saved).  `entry` / `sizer` name the
+                         target_lengths, store, max_work_bytes, flags=0, width=None):
+        """The forward of the graph loss and of the two beam-pruned losses -> (scores[B], saved; scores [B,width] with a
+        `width`: a row of scores per utterance).  `entry` / `sizer` name the
         library's *_full_forward / *_full_work_bytes; `prepare()`, called under the device guard, checks the family's
         arguments and returns (the ctypes views that follow the problem in both calls, Q, what those views point into) and,
         as an optional fourth element, the views that follow those in the forward alone (a look-ahead: it sizes nothing);
@@ -759,7 +760,7 @@ class HipBackend:
             groups = self._groups(p, B, max_work_bytes, lambda: work_bytes(*head, *size_args, int(store)), Q,
                                   lambda: _lib.check(call(None, 0, None, None), entry),
                                   inputs, targets, input_lengths, target_lengths, store=store)
-            scores = torch.empty(B, dtype=inputs.dtype, device=dev)
+            scores = torch.empty((B,) if width is None else (B, width), dtype=inputs.dtype, device=dev)
             stream = self._stream(dev)
             saved = []
             for b0, b1, work in groups:
@@ -876,6 +877,21 @@ class HipBackend:
     def target_graph_backward(self, saved, scores, grad_scores, inputs, transition, graphs, input_lengths):
         """(grad_transition[N,N], grad_inputs[T,B,N]) of sum_b grad_scores[b] * scores[b] from target_graph_forward's alpha."""
         return self._lattice_backward("asg_target_graph_backward", "asg_target_graph_scratch_bytes",
+                                      lambda: self._target_graph_args(inputs, transition, graphs, input_lengths), (), saved,
+                                      scores, grad_scores, inputs, transition, None, input_lengths, None)
+
+    def target_graph_final_forward(self, inputs, transition, graphs, input_lengths, store=False):
+        """Score of every final node of each utterance's target graph -> (final_scores[B,Kmax], saved); see
+        include/asg_hip.h::asg_target_graph_final_forward.  One launch for the whole batch; `saved` as target_graph_forward."""
+        return self._lattice_forward("asg_target_graph_final_forward", "asg_target_graph_work_bytes",
+                                     lambda: self._target_graph_args(inputs, transition, graphs, input_lengths), (), (), inputs,
+                                     transition, None, input_lengths, None, store, float("inf"),
+                                     width=getattr(graphs, "Kmax", 0))      # (anything but a TargetGraphs: prepare raises)
+
+    def target_graph_final_backward(self, saved, scores, grad_scores, inputs, transition, graphs, input_lengths):
+        """(grad_transition[N,N], grad_inputs[T,B,N]) of sum_{b,k} grad_scores[b,k] * final_scores[b,k] from
+        target_graph_final_forward's alpha."""
+        return self._lattice_backward("asg_target_graph_final_backward", "asg_target_graph_scratch_bytes",
                                       lambda: self._target_graph_args(inputs, transition, graphs, input_lengths), (), saved,
                                       scores, grad_scores, inputs, transition, None, input_lengths, None)
 
@@ -1902,6 +1918,69 @@ def target_graph_score(inputs, transition, graphs, input_lengths=None):
     return TargetGraphScore.apply(_widen(inputs, transition), transition, graphs, input_lengths)
 
 
+class TargetGraphFinalScores(torch.autograd.Function):
+    """Score of every final node of each utterance's own target graph, [B,Kmax] (asg_target_graph_final_forward /
+    _backward).  alpha is stored only when a gradient w.r.t. inputs or transition is needed."""
+
+    @staticmethod
+    def forward(ctx, inputs, transition, graphs, input_lengths):
+        store = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
+        scores, saved = native().target_graph_final_forward(inputs, transition, graphs, input_lengths, store)
+        ctx.save_for_backward(inputs, transition, input_lengths, scores)
+        ctx.saved, ctx.graphs = saved, graphs
+        return scores
+
+    @staticmethod
+    def backward(ctx, grad):
+        inputs, transition, input_lengths, scores = ctx.saved_tensors
+        gtr, gin = native().target_graph_final_backward(ctx.saved, scores, grad, inputs, transition, ctx.graphs, input_lengths)
+        return gin, gtr, None, None
+
+
+def target_graph_final_scores(inputs, transition, graphs, input_lengths=None):
+    """`target_graph_score` before the finals are summed: [B,Kmax], for every node k of utterance b's own target graph the
+    logsumexp over every alignment of every label path that ENDS in k, final weight included.  logsumexp over k gives
+    `target_graph_score`.  -inf, never NaN, behind the graph's nodes, where node k is not final, for an utterance of length 0
+    and where no path reaches k.  Differentiable w.r.t. `inputs` and `transition` with any signed gradient per node (the
+    graphs' weights are constants); gradient entries at -inf scores are ignored, NaN included.  One launch serves the batch
+    and its alternatives, whose shared prefixes are computed once; no float atomics: equal bits run to run.  Inputs, strides,
+    widening of float16 / bfloat16 and errors as `target_graph_score`."""
+    return TargetGraphFinalScores.apply(_widen(inputs, transition), transition, graphs, input_lengths)
+
+
+def target_graph_alternative_scores(inputs, transition, graphs, input_lengths=None):
+    """The full (summed over alignments) score of every sequence of graphs from `TargetGraphs.from_alternatives` /
+    `from_targets`, [B,Amax]: `target_graph_final_scores` at the node in which sequence a ends, -inf behind the utterance's
+    sequences.  What one `FAC` call per alternative gives, in one launch.  Differentiable as `target_graph_final_scores`.
+    ValueError for graphs built from arrays."""
+    if getattr(graphs, "alternative_final", None) is None:
+        raise ValueError("torch_asg_amd.target_graph_alternative_scores: the graphs must come from TargetGraphs.from_alternatives "
+                         "or from_targets")
+    fs = target_graph_final_scores(inputs, transition, graphs, input_lengths)
+    af = graphs.alternative_final_on(fs.device)
+    if af.shape[1] == 0 or fs.shape[1] == 0:
+        return torch.full(af.shape, float("-inf"), dtype=fs.dtype, device=fs.device)
+    return torch.where(af >= 0, fs.gather(1, af.clamp(min=0)), torch.full((), float("-inf"), dtype=fs.dtype, device=fs.device))
+
+
+def target_graph_risk(inputs, transition, graphs, costs, input_lengths=None, reduction='none'):
+    """The expected cost of an n-best list under the model (minimum word error rate / minimum Bayes risk training):
+    risk[b] = sum_a softmax_a(target_graph_alternative_scores[b])[a] * costs[b, a] over the utterance's sequences whose score
+    is finite; 0, with zero gradient, where there is none.  `costs` [B,Amax] (word errors, say) is a constant; entries behind
+    an utterance's sequences are ignored.  reduction 'none' (default), 'sum' or 'mean'."""
+    s = target_graph_alternative_scores(inputs, transition, graphs, input_lengths)
+    costs = torch.as_tensor(costs, device=s.device).to(s.dtype)
+    if tuple(costs.shape) != tuple(s.shape):
+        raise ValueError("torch_asg_amd.target_graph_risk: costs must have shape [%d, %d]" % tuple(s.shape))
+    ok = torch.isfinite(s.detach())
+    top = s.detach().amax(1, keepdim=True) if s.shape[1] else s.detach()        # (a score is finite or -inf)
+    top = torch.where(torch.isfinite(top), top, torch.zeros_like(top))
+    e =torch.where(ok, torch.exp(torch.where(ok, s - top, torch.zeros_like(s))), torch.zeros_like(s))
+    den = e.sum(1)
+    risk = (e * torch.where(ok, costs, torch.zeros_like(costs))).sum(1) / torch.where(den > 0, den, torch.ones_like(den))
+    return _reduce(risk, reduction)
+
+
 class TargetGraphViterbiScore(torch.autograd.Function):
     """Best-path score of each utterance's own target graph, [B] (asg_target_graph_viterbi_forward / _backward).  The path
     is kept only when a gradient w.r.t. inputs or transition is needed."""
@@ -2548,6 +2627,21 @@ class ASGLoss(nn.Module):
         """The n best paths of each utterance's target graph, one per final node, under this module's transitions: see
         `torch_asg_amd.target_graph_nbest`."""
         return target_graph_nbest(inputs, self.transition, graphs, input_lengths, nbest, return_alignments)
+
+    def target_graph_final_scores(self, inputs, graphs, input_lengths=None):
+        """The score of every final node of each utterance's target graph under this module's transitions, differentiable:
+        `torch_asg_amd.target_graph_final_scores`."""
+        return target_graph_final_scores(inputs, self.transition, graphs, input_lengths)
+
+    def target_graph_alternative_scores(self, inputs, graphs, input_lengths=None):
+        """The full score of every sequence of `TargetGraphs.from_alternatives` under this module's transitions,
+        differentiable: `torch_asg_amd.target_graph_alternative_scores`."""
+        return target_graph_alternative_scores(inputs, self.transition, graphs, input_lengths)
+
+    def target_graph_risk(self, inputs, graphs, costs, input_lengths=None):
+        """The expected cost of each utterance's alternatives (minimum word error rate training) under this module's
+        transitions and reduction: `torch_asg_amd.target_graph_risk`."""
+        return target_graph_risk(inputs, self.transition, graphs, costs, input_lengths, self.reduction)
 
     def beam_graph_loss(self, inputs, targets, graph, input_lengths=None, target_lengths=None, lm_weight=1.0, token_score=0.0,
                         max_work_bytes=1 << 30, beam_size=256, beam_threshold=float("inf")):

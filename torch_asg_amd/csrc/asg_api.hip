@@ -2801,6 +2801,43 @@ int asg_target_graph_backward(asg_ctx *ctx, const asg_problem *p, const asg_targ
                                              (hipStream_t) stream)));
 }
 
+int asg_target_graph_final_forward(asg_ctx *ctx, const asg_problem *p, const asg_target_graphs *tg, void *work,
+                                   size_t work_bytes, void *final_scores, int flags, void *stream) {
+    (void) ctx;
+    int rc = check_target_graphs(p, tg, false);
+    if (rc) return rc;
+    const bool store = (flags & ASG_FLAG_GRAPH_LOSS_KEEP_ALPHA) != 0;
+    const size_t need = asg_target_graph_work_bytes(p, tg, store);
+    if ((tg->Kmax > 0 && !final_scores) || (need && !work)) return ASG_ERR_INVALID;
+    if (work_bytes < need) return ASG_ERR_WORKSPACE;
+    const Problem P = to_problem(p);
+    const TargetGraphArgs G = to_target_graph_args(tg);
+    return hip_status(ASG_DISPATCH(p,
+        launch_target_graph_final_forward<float>(P, G, store, work, final_scores, (hipStream_t) stream),
+        launch_target_graph_final_forward<double>(P, G, store, work, final_scores, (hipStream_t) stream)));
+}
+
+int asg_target_graph_final_backward(asg_ctx *ctx, const asg_problem *p, const asg_target_graphs *tg, const void *work,
+                                    size_t work_bytes, const void *final_scores, const void *grad_final_scores,
+                                    void *grad_inputs, void *grad_transition, void *scratch, size_t scratch_bytes, int flags,
+                                    void *stream) {
+    (void) ctx; (void) flags;
+    int rc = check_target_graphs(p, tg, false);
+    if (rc) return rc;
+    const size_t wneed = asg_target_graph_work_bytes(p, tg, 1), sneed = asg_target_graph_scratch_bytes(p, tg);
+    if ((tg->Kmax > 0 && (!final_scores || !grad_final_scores)) || !grad_inputs || !grad_transition || (wneed && !work) ||
+        (sneed && !scratch))
+        return ASG_ERR_INVALID;
+    if (work_bytes < wneed || scratch_bytes < sneed) return ASG_ERR_WORKSPACE;
+    const Problem P = to_problem(p);
+    const TargetGraphArgs G = to_target_graph_args(tg);
+    return hip_status(ASG_DISPATCH(p,
+        launch_target_graph_final_backward<float>(P, G, work, final_scores, grad_final_scores, grad_inputs, grad_transition,
+                                                  scratch, (hipStream_t) stream),
+        launch_target_graph_final_backward<double>(P, G, work, final_scores, grad_final_scores, grad_inputs, grad_transition,
+                                                   scratch, (hipStream_t) stream)));
+}
+
 size_t asg_target_graph_viterbi_work_bytes(const asg_problem *p, const asg_target_graphs *tg) {
     if (check_target_graphs(p, tg, true) != ASG_OK) return 0;
     return target_graph_viterbi_work_bytes((int) p->T, (int) p->B, (int) tg->Kmax);

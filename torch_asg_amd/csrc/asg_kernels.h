@@ -766,6 +766,17 @@ hipError_t launch_target_graph_backward(const Problem &P, const TargetGraphArgs 
                                         const void *grad_scores, void *grad_inputs, void *grad_transition, void *scratch,
                                         hipStream_t stream);
 
+// ---- The score of every final node of each utterance's target graph and the gradients of a signed combination of them
+// (asg_target_graph_final.hip).  Work and scratch are launch_target_graph_forward's / _backward's (target_graph_work_bytes,
+// target_graph_scratch_bytes); final_scores and grad_final_scores are [B][Kmax].
+template <typename R>
+hipError_t launch_target_graph_final_forward(const Problem &P, const TargetGraphArgs &G, bool store, void *work,
+                                             void *final_scores, hipStream_t stream);
+template <typename R>
+hipError_t launch_target_graph_final_backward(const Problem &P, const TargetGraphArgs &G, const void *work,
+                                              const void *final_scores, const void *grad_final_scores, void *grad_inputs,
+                                              void *grad_transition, void *scratch, hipStream_t stream);
+
 // ---- Best path of each utterance's target graph (asg_target_graph_viterbi.hip): one launch, forward + backtrace + token
 // compaction.  Work = the back-pointers [B][T][Kmax], 16 bits each; the integer outputs are [B][T] (token_lengths [B]).
 size_t target_graph_viterbi_work_bytes(int T, int B, int Kmax);

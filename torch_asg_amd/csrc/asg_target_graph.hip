@@ -22,20 +22,11 @@
 // stay and of its outgoing edges are owned by the thread that pulls beta into that node, live in LDS for the whole utterance
 // and are written once.  No float atomics, every output element written by a kernel (no memset): bit-identical run to run and
 // capturable.  grad_transition: a zero-fill, then one wavefront per label pair that any graph uses.
-#include "asg_target_graph_common.h"
+#include "asg_target_graph_sum.h"
 
 namespace asg {
 
 namespace {
-
-constexpr int kTgF = 256;                       // workgroup of the two grad_transition kernels
-
-template <typename R> __device__ __forceinline__ R texp(R x);
-template <> __device__ __forceinline__ float texp<float>(float x) { return expf(x); }
-template <> __device__ __forceinline__ double texp<double>(double x) { return ::exp(x); }
-template <typename R> __device__ __forceinline__ R tlog(R x);
-template <> __device__ __forceinline__ float tlog<float>(float x) { return logf(x); }
-template <> __device__ __forceinline__ double tlog<double>(double x) { return ::log(x); }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Forward.  Dynamic LDS: [reduction slots 256 B][alpha 2*Kmax R][f Emax R][src Emax int].
@@ -44,61 +35,16 @@ template <typename R, int W>
 __global__ void __launch_bounds__(W) target_graph_fwd(Problem P, TargetGraphArgs G, R *A, R *scores) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     R *red = (R *) lds;
-    R *av = (R *) (lds + kTgRed);
-    R *fe = av + 2 * (size_t) G.Kmax;
-    int *se = (int *) (fe + G.Emax);
     const R NINF = Num<R>::ninf();
-    const int k = threadIdx.x, b = blockIdx.x, T = P.T, Kmax = G.Kmax;
+    const int k = threadIdx.x, b = blockIdx.x;
     const TgView g = tg_view(G, b);
-    const int len = g.K > 0 ? tg_len(P.in_len, b, T) : 0;
+    const int len = g.K > 0 ? tg_len(P.in_len, b, P.T) : 0;
     if (len < 1) {                                    // (uniform over the workgroup)
         if (k == 0) scores[b] = NINF;
         return;
     }
     const bool mine = k < g.K;
-    const R *trm = (const R *) P.transition;
-    const R *in = (const R *) P.inputs + (int64_t) b * P.is1;
-    int e0 = 0, e1 = 0;
-    R trs = R(0), fin = NINF, em = R(0), x = NINF;
-    if (mine) {
-        const int lk = g.label[k];
-        in += (int64_t) lk * P.is2;
-        e0 = g.row[k]; e1 = g.row[k + 1];
-        const R *ew = (const R *) G.edge_w + (int64_t) b * G.Emax;
-        for (int e = e0; e < e1; ++e) {               // the fold: one gather per edge per utterance
-            const int s = g.src[e];
-            fe[e] = trm[(int64_t) lk * P.ts0 + (int64_t) g.label[s] * P.ts1] + ew[e];
-            se[e] = s;
-        }
-        trs = trm[(int64_t) lk * (P.ts0 + P.ts1)];
-        fin = ((const R *) G.final_w)[(int64_t) b * Kmax + k];
-        x = ((const R *) G.start_w)[(int64_t) b * Kmax + k] + in[0];
-        if (len > 1) em = in[P.is0];
-        av[k] = x;
-    }
-    R *Ab = A ? A + (int64_t) b * T * Kmax : nullptr;
-    if (mine && Ab) Ab[k] = x;
-    __syncthreads();
-    for (int t = 1; t < len; ++t) {
-        const R *vp = av + (size_t) ((t - 1) & 1) * Kmax;
-        if (mine) {
-            const R emt = em;
-            if (t + 1 < len) em = in[(int64_t) (t + 1) * P.is0];     // next frame's emission: in flight across the barrier
-            const R stay = vp[k] + trs;
-            R m = stay;
-            for (int e = e0; e < e1; ++e) m = tmax(m, vp[se[e]] + fe[e]);
-            x = NINF;
-            if (m > NINF) {
-                R s = texp(stay - m);
-                for (int e = e0; e < e1; ++e) s += texp((vp[se[e]] + fe[e]) - m);
-                x = (m + tlog(s)) + emt;
-            }
-            av[(size_t) (t & 1) * Kmax + k] = x;
-            if (Ab) Ab[(int64_t) t * Kmax + k] = x;
-        }
-        __syncthreads();
-    }
-    const R c = mine ? x + fin : NINF;                // x = alpha[len-1][k]
+    const R c = tg_alpha_forward<R>(P, G, g, b, len, lds, A);     // alpha[len-1][k] + final_w[k] (asg_target_graph_sum.h)
     const R m = tg_reduce<R, W, true>(c, red);
     R Z = NINF;
     if (m > NINF) Z = m + tlog(tg_reduce<R, W, false>(mine ? texp(c - m) : R(0), red));
@@ -205,36 +151,6 @@ __global__ void __launch_bounds__(W) target_graph_bwd(Problem P, TargetGraphArgs
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// grad_transition: zeros everywhere, then a wavefront per label pair that some graph of the batch uses; the lanes stride
-// the pair's segment of the batch-wide list in list order and end in a fixed butterfly.
-// ---------------------------------------------------------------------------------------------------------------------
-template <typename R>
-__global__ void __launch_bounds__(kTgF) target_graph_tr_zero(R *gtr, int64_t n) {
-    const int64_t x = (int64_t) blockIdx.x * kTgF + threadIdx.x;
-    if (x < n) gtr[x] = R(0);
-}
-
-template <typename R>
-__global__ void __launch_bounds__(kTgF) target_graph_tr_reduce(TargetGraphArgs G, const R *acc, const R *gs, R *gtr) {
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int64_t pair = (int64_t) blockIdx.x * (kTgF / 64) + w;
-    if (pair >= G.npairs) return;
-    const int slots = G.Kmax + G.Emax;
-    R s = R(0);
-    for (int x = G.pseg[pair] + lane, x1 = G.pseg[pair + 1]; x < x1; x += 64) {
-        const int at = G.pslot[x];                    // b * (Kmax + Emax) + slot
-        s += gs[at / slots] * acc[at];
-    }
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) s += (R) __shfl_xor(s, o);
-    if (lane == 0) gtr[G.pkey[pair]] = s;
-}
-
-inline size_t tg_bwd_lds(int elem, int Kmax, int64_t Emax) {
-    return kTgRed + (size_t) Kmax * (5 * elem + 4) + (size_t) Emax * (2 * elem + 4);
-}
-
 template <typename R, int W>
 hipError_t tg_forward(const Problem &P, const TargetGraphArgs &G, R *A, R *scores, hipStream_t stream) {
     const size_t dyn = tg_fwd_lds(sizeof(R), G.Kmax, G.Emax);
@@ -290,12 +206,7 @@ hipError_t launch_target_graph_backward(const Problem &P, const TargetGraphArgs 
     else if (G.Kmax <= 256) e = tg_backward<R, 256>(P, G, A, Zs, gs, gin, acc, stream);
     else e = tg_backward<R, 1024>(P, G, A, Zs, gs, gin, acc, stream);
     if (e != hipSuccess) return e;
-    const int64_t NN = (int64_t) P.N * P.N;
-    hipLaunchKernelGGL((target_graph_tr_zero<R>), dim3((unsigned) ((NN + kTgF - 1) / kTgF)), dim3(kTgF), 0, stream, gtr, NN);
-    if ((e = hipGetLastError()) != hipSuccess || G.npairs == 0) return e;
-    hipLaunchKernelGGL((target_graph_tr_reduce<R>), dim3((unsigned) ((G.npairs + kTgF / 64 - 1) / (kTgF / 64))), dim3(kTgF), 0,
-                       stream, G, (const R *) acc, gs, gtr);
-    return hipGetLastError();
+    return tg_grad_transition<R, true>(P, G, (const R *) acc, gs, gtr, stream);
 }
 
 template hipError_t launch_target_graph_forward<float>(const Problem &, const TargetGraphArgs &, bool, void *, void *, hipStream_t);
